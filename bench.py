@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""bench.py -- queries/sec (+ p50 latency) of top-1000 search on a synthetic 1M-passage corpus
+"""bench.py -- queries/sec (+ p50 latency with --full) of top-1000 search on a synthetic 1M-passage corpus
 (BASELINE.json: dim 128, nbits 2, doclen ~80, query_maxlen 32, nprobe 2, k 1000) on N MI355X.
 
 A step = one pass of the search hot path (centroid scoring -> candidates -> fused decompress+MaxSim
@@ -7,13 +7,17 @@ A step = one pass of the search hot path (centroid scoring -> candidates -> fuse
 that are already resident in HBM.  The passage collection is sharded over the N ranks (strong scaling:
 the corpus is fixed).  Prints ONE JSON line on rank 0.
 
-Besides the headline the line carries (N = 1): `worst_case_uniform_codes` (the same corpus size with uniformly drawn
+A plain run does only what the headline needs: set up, warm up (the --min-seconds pre-conditioning loop and --warmup
+steps), time exactly --steps steps, write the last step's top-k with --dump-outputs DIR, print the line.  Every other leg
+below runs with --full, and its fields are null without it.
+
+With --full the line also carries (N = 1): `worst_case_uniform_codes` (the same corpus size with uniformly drawn
 centroid codes: no id-adjacent codes, the largest candidate sets), `built_index` (BASELINE config 2: 100k passages
 of mixture embeddings -> this repo's own k-means / codec / compress / IVF build -> search, oracle-checked, with an
 `index_build` record) and `batch_sweep` (N = 1 at the batch sizes the N-GPU runs use); for N > 1: `fixed_batch_32`
 (the same 32-query batch at every N) and `single_exchange` (one all-gather per batch instead of two).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--docs D] [--batch B] [--mode {0,1}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--docs D] [--batch B] [--mode {0,1}] [--full] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -417,6 +421,14 @@ def main():
     ap.add_argument("--built-1m-docs", type=int, default=0,
                     help="passages of the built_index_1M workload (0: 1 000 000 when --docs is at least that, else skipped; tests pass a small value)")
     ap.add_argument("--no-index-build", action="store_true", help="N > 1: skip the sharded index build over the process group")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg of the line, not only the headline: one-batch-at-a-time and per-kernel (roofline) passes, the "
+                         "in-flight check, the query-encoder legs, latencies, the CPU baseline, the oracle check of the N-rank "
+                         "preflight, the sub-records (uniform codes, built indexes, batch sweep, fixed_batch_32, single_exchange) "
+                         "and the sharded index build.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to DIR: pids.npy (float64, 1-based "
+                         "passage ids) and scores.npy (float32), both (batch, k)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -606,13 +618,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    last_out = [None]           # (pids, scores) the last step of the latest timed region returned
+
     def timed(n_steps, first, pl=None):
         """n_steps steps between two barrier + synchronize pairs; MAX over ranks of the wall time."""
         pl = pl or plan
         barrier()
         t0 = time.perf_counter()
         for i in range(n_steps):
-            pl.step(first + i)
+            last_out[0] = pl.step(first + i)
         barrier()
         dt = time.perf_counter() - t0
         if world > 1:
@@ -681,7 +695,7 @@ def main():
             return merged
         mp_, ms_ = first_contact("one batch: search of every shard + exchange + merge", one_batch)
         verdict = torch.ones(1, dtype=torch.int32, device=dev if backend == "nccl" else "cpu")
-        if rank == 0 and world > 1 and not args.no_cpu and not args.built_index:
+        if rank == 0 and world > 1 and args.full and not args.no_cpu and not args.built_index:
             from oracle import oracle as orc
             orc.build()
             t1 = time.time()
@@ -719,49 +733,58 @@ def main():
         plan.step(i)
     elapsed = timed(args.steps, args.warmup)
     qps = B * args.steps / elapsed
-    # (3) a separate pass with HIP events around every kernel (on the stream they are launched on) for the roofline
-    #     -- on ONE stream, so that a kernel's time is its own (with two batches in flight kernels share the chip)
-    was = overlap[0]
-    overlap[0] = False
-    serial_s = timed(args.steps, args.warmup)
-    s.profile_enable(True)
-    prof_steps = args.steps
-    timed(prof_steps, args.warmup)
-    prof = s.profile_read()
-    s.profile_enable(False)
-    overlap[0] = was
+    # (2) --dump-outputs: what the last timed step returned (the merged top-k with N ranks), before any later step can
+    #     reuse its result buffers; pids as float64 (exact below 2^53), scores as the fp32 the caller receives
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "pids.npy"), last_out[0][0].cpu().numpy().astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), last_out[0][1].cpu().numpy().astype(np.float32))
+    two_pass_mode = s.mode == 1
+    serial_s = in_flight_ok = None
+    prof, prof_steps = {}, args.steps
+    if args.full:
+        # (3) a separate pass with HIP events around every kernel (on the stream they are launched on) for the roofline
+        #     -- on ONE stream, so that a kernel's time is its own (with two batches in flight kernels share the chip)
+        was = overlap[0]
+        overlap[0] = False
+        serial_s = timed(args.steps, args.warmup)
+        s.profile_enable(True)
+        timed(prof_steps, args.warmup)
+        prof = s.profile_read()
+        s.profile_enable(False)
+        overlap[0] = was
 
-    # ---- batches in flight do not disturb each other: one batch computed alone == the same batch computed in the middle
-    # of NF batches in flight on NF streams (every rank checks its own results)
-    def result_of(i):
-        out = plan.step(i)
-        st = comm if gather else (compute[i % NF] if overlap[0] else compute[0])
-        with torch.cuda.stream(st):
-            return out[0].clone(), out[1].clone()
-    probe_i = args.warmup + 2 * NF + 1
-    was = overlap[0]
-    overlap[0] = False
-    barrier()
-    alone = result_of(probe_i)
-    barrier()
-    overlap[0] = was
-    for i in range(probe_i - NF, probe_i):
-        plan.step(i)
-    busy = result_of(probe_i)
-    for i in range(probe_i + 1, probe_i + 1 + NF):
-        plan.step(i)
-    barrier()
-    in_flight_ok = bool(torch.equal(alone[0], busy[0]) and torch.equal(alone[1], busy[1]))
-    if world > 1:
-        okt = torch.tensor([1 if in_flight_ok else 0], dtype=torch.int64, device=dev)
-        dist.all_reduce(okt, op=dist.ReduceOp.MIN)
-        in_flight_ok = bool(okt.item())
+        # ---- batches in flight do not disturb each other: one batch computed alone == the same batch computed in the middle
+        # of NF batches in flight on NF streams (every rank checks its own results)
+        def result_of(i):
+            out = plan.step(i)
+            st = comm if gather else (compute[i % NF] if overlap[0] else compute[0])
+            with torch.cuda.stream(st):
+                return out[0].clone(), out[1].clone()
+        probe_i = args.warmup + 2 * NF + 1
+        was = overlap[0]
+        overlap[0] = False
+        barrier()
+        alone = result_of(probe_i)
+        barrier()
+        overlap[0] = was
+        for i in range(probe_i - NF, probe_i):
+            plan.step(i)
+        busy = result_of(probe_i)
+        for i in range(probe_i + 1, probe_i + 1 + NF):
+            plan.step(i)
+        barrier()
+        in_flight_ok = bool(torch.equal(alone[0], busy[0]) and torch.equal(alone[1], busy[1]))
+        if world > 1:
+            okt = torch.tensor([1 if in_flight_ok else 0], dtype=torch.int64, device=dev)
+            dist.all_reduce(okt, op=dist.ReduceOp.MIN)
+            in_flight_ok = bool(okt.item())
 
     # ---- N > 1: the same 32-query batch at every N (so that the N-GPU point and the 1-GPU point of a strong-scaling
     # curve run the same batch), and the single-exchange mode north_star describes (ONE all-gather of the per-shard top-k
     # per batch, every shard cutting at its own threshold) beside the two-phase default
     fixed32 = single_exchange = two_phase_leg = None
-    if world > 1:
+    if world > 1 and args.full:
         if B != 32:
             p32 = Plan(32, two_phase_default)
             n32, s32 = sustained_of(p32, min(args.min_seconds, 0.3))
@@ -786,7 +809,7 @@ def main():
     # step costs exactly "encode B queries + search B queries", back to back on one stream.  With N ranks every rank
     # encodes B / N of the batch's queries and one all-gather (B x 32 x 128 fp32) gives every shard all of them.
     e2e = None
-    if not args.no_encoder:
+    if args.full and not args.no_encoder:
         from colbert_jl_amd.encoder import BERT_BASE, random_weights
         enc = clb.BertEncoder(random_weights(BERT_BASE, 128, seed=5), dict(BERT_BASE), dim=128, device=local_rank)
         rng = np.random.default_rng(6)
@@ -1067,25 +1090,26 @@ def main():
         enc.close()
 
     # ---- work counters of one batch (for the roofline) and p50 latency, outside the timed region
-    s.profile_enable(True, counters=True)
-    plan.step(args.warmup)
-    torch.cuda.synchronize()
-    stats = s.last_batch_stats()
-    s.profile_read()
-    s.profile_enable(False)
-    lat = []
-    one = DeviceSearch(s, T, 1, k, args.nprobe)
-    for i in range(0 if args.no_latency else 40):
+    stats, lat = None, []
+    if args.full:
+        s.profile_enable(True, counters=True)
+        plan.step(args.warmup)
         torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        if two_phase:
-            one.phase2(Qdev[i:i + 1], all_gather_scores(one.phase1(Qdev[i:i + 1])))
-        else:
-            one(Qdev[i:i + 1])
-        if gather:
-            merge_packed(all_gather_packed(one.packed), 1, k)
-        torch.cuda.synchronize()
-        lat.append(time.perf_counter() - t1)
+        stats = s.last_batch_stats()
+        s.profile_read()
+        s.profile_enable(False)
+        one = DeviceSearch(s, T, 1, k, args.nprobe)
+        for i in range(0 if args.no_latency else 40):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            if two_phase:
+                one.phase2(Qdev[i:i + 1], all_gather_scores(one.phase1(Qdev[i:i + 1])))
+            else:
+                one(Qdev[i:i + 1])
+            if gather:
+                merge_packed(all_gather_packed(one.packed), 1, k)
+            torch.cuda.synchronize()
+            lat.append(time.perf_counter() - t1)
     p50_ms = float(np.median(lat[5:]) * 1e3) if lat else None
     # the same single query as a captured HIP graph over a static query buffer (what a serving loop whose encoder
     # writes into that buffer would replay); one GPU only
@@ -1188,7 +1212,7 @@ def main():
 
     # ---- CPU baseline: the oracle (a port of the reference algorithm) on the host cores, rank 0, N = 1
     cpu = None
-    if world == 1 and not args.no_cpu:
+    if world == 1 and args.full and not args.no_cpu:
         from oracle import oracle as orc
         orc.build()
         emb2pid = orc.build_emb2pid(shard["doclens"])
@@ -1209,12 +1233,12 @@ def main():
     # ---- N = 1 sub-records: the batch sizes the N-GPU runs use, the worst-case code distribution, and BASELINE config 2
     batch_sweep = worst = built = built_1m = None
     device_bytes = s.device_bytes
-    if world > 1 and not args.no_index_build and not args.built_index:
+    if world > 1 and args.full and not args.no_index_build and not args.built_index:
         try:
             index_build = sharded_index_build(torch, dist, rank, world, args.docs, args.built_kmeans_iters, dev)
         except Exception as e:      # the search figures of the line stand on their own
             index_build = {"error": f"{type(e).__name__}: {e}"}
-    if world == 1 and not args.no_sub and not args.force_gather:
+    if world == 1 and args.full and not args.no_sub and not args.force_gather:
         batch_sweep = {}
         for Bs in (64, 128, 256):
             if Bs == B or Bs > n_queries:
@@ -1294,7 +1318,8 @@ def main():
                                        f"{', uniform codes' if args.uniform_codes else ''}), ") +
                                       f"top-{k}, nprobe {args.nprobe}, query_maxlen {T}, batch {B} queries/step, "
                                       f"passages sharded over {world} GPU(s)",
-                          "search_mode": ("two-pass (fp16 MFMA prefilter + exact fp32 re-score)" if (prof and "score_approx" in prof) else "exact fp32 single pass")
+                          "search_mode": ("two-pass (fp16 MFMA prefilter + exact fp32 re-score)" if (("score_approx" in prof) if prof else two_pass_mode)
+                                          else "exact fp32 single pass")
                                          + (", global threshold exchange between the passes" if two_phase else ""),
                           # scalars a reader of the first 2 KB needs (the full records follow further down the line)
                           "batch": B,
@@ -1313,7 +1338,8 @@ def main():
                "query_pool": {"distinct_queries": int(n_queries), "issued_in_timed_region": int(B * args.steps),
                               "note": "warmup + timed steps never issue a query twice; the sustained leg and the sweeps cycle the pool"},
                "batches_in_flight": NF if overlap[0] else 1, "in_flight_matches_serial": in_flight_ok,
-               "one_batch_at_a_time": {"value": round(B * args.steps / serial_s, 2), "ms_per_step": round(serial_s / args.steps * 1e3, 4)},
+               "one_batch_at_a_time": None if serial_s is None else {"value": round(B * args.steps / serial_s, 2),
+                                                                     "ms_per_step": round(serial_s / args.steps * 1e3, 4)},
                "sustained": {"steps": sustained_steps, "seconds": round(sustained_s, 4),
                              "value": round(B * sustained_steps / sustained_s, 2),
                              "note": "the same loop repeated until the timed region lasts --min-seconds"},
@@ -1328,7 +1354,8 @@ def main():
                             else "single (north_star: 1 all-gather of the per-shard top-k per batch)"),
                "fixed_batch_32": fixed32, "single_exchange": single_exchange, "two_phase_exchange": two_phase_leg, "index_build": index_build,
                "setup_seconds": {"generate": round(t_gen, 1), "upload_and_build": round(t_load, 1)},
-               "hbm_bytes": device_bytes}
+               "hbm_bytes": device_bytes,
+               "full": args.full}
         sys.stdout.flush()
         os.dup2(real_stdout, 1)
         print(json.dumps(out), flush=True)

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_fields():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--docs", "40000", "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--docs", "40000", "--steps", "3", "--warmup", "1",
                           "--no-encoder", "--cpu-seconds", "1", "--min-seconds", "0.05", "--k", "100", "--built-docs", "3000",
                           "--built-kmeans-iters", "3", "--built-1m-docs", "4000"],
                          capture_output=True, text=True, timeout=600)
@@ -22,7 +23,7 @@ def test_bench_line_has_the_contract_fields():
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
-    assert d["n_gpus"] == 1 and d["ranks_seen"] == 1 and d["steps"] == 3 and d["warmup"] == 1
+    assert d["n_gpus"] == 1 and d["ranks_seen"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["full"] is True
     assert d["higher_is_better"] is True and d["vs_baseline"] is None and d["data"] == "synthetic"
     assert d["value"] > 0 and abs(d["value"] - 32 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-3
     assert "workload" in d["config"] and "model" not in d["config"]
@@ -65,3 +66,37 @@ def test_bench_line_has_the_contract_fields():
                 "sample_points", "total_build_s"):
         assert key in m["index_build"], key
     assert set(d["batch_sweep"]) == {"64", "128", "256"}
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_the_headline_only_and_dumps_the_last_step(tmp_path, oracle):
+    """Without --full the line carries the headline alone (the other legs are null), and --dump-outputs writes the top-k the
+    last timed step returned: float64 pids and float32 scores, identical to the CPU oracle's search of the same queries."""
+    from colbert_jl_amd import synthetic
+    docs, steps, warmup, k, B = 40000, 3, 1, 100, 32
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--docs", str(docs), "--steps", str(steps),
+                          "--warmup", str(warmup), "--k", str(k), "--min-seconds", "0.05", "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == steps and d["warmup"] == warmup and d["unit"] == "queries/s"
+    assert d["metric"] == "queries/sec, top-1000 on 1M-passage corpus" and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["value"] - B * steps / (d["ms_per_step"] * steps * 1e-3)) / d["value"] < 1e-3
+    for key in ("roofline", "cpu_baseline", "end_to_end_with_query_encoder", "worst_case_uniform_codes", "built_index",
+                "built_index_1M", "batch_sweep", "one_batch_at_a_time", "in_flight_matches_serial", "p50_latency_ms"):
+        assert d[key] is None, key
+    pids, scores = np.load(dump / "pids.npy"), np.load(dump / "scores.npy")
+    assert pids.dtype == np.float64 and scores.dtype == np.float32 and pids.shape == scores.shape == (B, k)
+    # the queries of the last timed step: bench.py's pool (seed 77, 768 queries at these sizes), batch `warmup + steps - 1`
+    idx = synthetic.make_index(seed=2024, n_docs=docs, K=synthetic.num_partitions_for(docs, 80.0), n_blocks=8, blocks=range(8))
+    n_queries = max(B * 8, 768, -(-B * (steps + warmup + 1) // 256) * 256)
+    Q = synthetic.make_topic_queries(idx["centroids"], seed=77, n_queries=n_queries, T=32)
+    off = ((warmup + steps - 1) * B) % (n_queries - B + 1)
+    oidx = dict(idx, emb2pid=oracle.build_emb2pid(idx["doclens"]))
+    for b in (0, 1, B - 1):
+        rp, rs, _ = oracle.search(oidx, Q[:, :, off + b], 2, k)
+        assert np.array_equal(pids[b], rp.astype(np.float64)), b
+        assert np.array_equal(scores[b].view(np.uint32), rs.view(np.uint32)), b

@@ -92,10 +92,17 @@ def test_readme_parser(tmp_path):
     passages, query = t.parse_readme_example(str(md))
     assert passages == ['first "quoted" passage, costs $5 [not a bracket]', "second passage", "third"]
     assert query == "what was Cesar Milan's trick?"
-    ref = "/root/reference/README.md"                  # the real file, when the reference checkout is present (not on the GPU box)
-    if os.path.exists(ref):
-        passages, query = t.parse_readme_example(ref)
-        assert len(passages) == 10 and query == t.README_EXPECTED["query"] and "Cesar Milan" in passages[9]
+    # the README's own example, laid out as it is there: its passages and query are stored data (tests/golden/readme_example.json)
+    with open(os.path.join(ROOT, "tests", "golden", "readme_example.json"), encoding="utf-8") as f:
+        ex = json.load(f)
+
+    def lit(s):
+        return '"' + s.replace("\\", "\\\\").replace('"', '\\"').replace("$", "\\$") + '"'
+    md.write_text("## Get Started\n\n```julia\ndocument_passages = [\n" + "".join(f"    {lit(p)},\n" for p in ex["passages"]) +
+                  "]\n```\n\ntext\n\n```julia\njulia>  query = " + lit(ex["query"]) + ";\n```\n", encoding="utf-8")
+    passages, query = t.parse_readme_example(str(md))
+    assert passages == ex["passages"] and query == ex["query"]
+    assert len(passages) == 10 and query == t.README_EXPECTED["query"] and "Cesar Milan" in passages[9]
 
 
 def test_export_then_fails_loudly_without_a_gpu(tmp_path):

@@ -5,7 +5,7 @@ set -u
 OUT=gpurun_out/$1; shift
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python3 bench.py --steps 5 --warmup 2 --no-cpu --no-latency --no-encoder --no-overlap --no-sub --min-seconds 0 $*"
+BENCH="python3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-latency --no-encoder --no-overlap --no-sub --min-seconds 0 $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/trace.json 2> $OUT/trace.err
 # PMC_LIGHT=1: the two passes roofline.traffic needs (FETCH_SIZE, WRITE_SIZE + L2 hit / miss) -- the sub-records' workloads
 if [ "${PMC_LIGHT:-0}" = "1" ]; then

@@ -6,7 +6,7 @@ OUT=gpurun_out/r06_bench_inflight.jsonl
 : > $OUT
 for NF in 2 3; do
 for SUF in "" _w8 _w4 ""; do
-  COLBERT_HIP_LIB=colbert.jl_amd/csrc/libcolbert_hip$SUF.so python3 bench.py --no-encoder --no-cpu --no-sub --no-latency --min-seconds 1.0 --in-flight $NF 2>> gpurun_out/r06_bench_inflight.err | \
+  COLBERT_HIP_LIB=colbert.jl_amd/csrc/libcolbert_hip$SUF.so python3 bench.py --full --no-encoder --no-cpu --no-sub --no-latency --min-seconds 1.0 --in-flight $NF 2>> ${OUT%.jsonl}.err | \
     python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())

@@ -6,7 +6,7 @@ TAG=$1; shift
 OUT=gpurun_out/r06_bench_libs_$TAG.jsonl
 : > $OUT
 for SUF in "" "$@" ""; do
-  COLBERT_HIP_LIB=colbert.jl_amd/csrc/libcolbert_hip$SUF.so python3 bench.py --no-encoder --no-cpu --no-sub --no-latency --min-seconds 1.0 2>> gpurun_out/r06_bench_libs_$TAG.err | \
+  COLBERT_HIP_LIB=colbert.jl_amd/csrc/libcolbert_hip$SUF.so python3 bench.py --full --no-encoder --no-cpu --no-sub --no-latency --min-seconds 1.0 2>> ${OUT%.jsonl}.err | \
     python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())

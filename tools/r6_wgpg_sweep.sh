@@ -6,7 +6,7 @@ set -u
 OUT=gpurun_out/r06_wgpg_sweep.jsonl
 : > $OUT
 for W in 32 31 30 28 24 32; do
-  CLB_DEBUG_APPROX_WGPG=$W COLBERT_HIP_LIB=colbert.jl_amd/csrc/libcolbert_hip_abl.so python3 bench.py --no-encoder --no-cpu --no-sub --no-latency --min-seconds 1.0 2>> gpurun_out/r06_wgpg_sweep.err | \
+  CLB_DEBUG_APPROX_WGPG=$W COLBERT_HIP_LIB=colbert.jl_amd/csrc/libcolbert_hip_abl.so python3 bench.py --full --no-encoder --no-cpu --no-sub --no-latency --min-seconds 1.0 2>> ${OUT%.jsonl}.err | \
     python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
