@@ -1062,9 +1062,15 @@ static __global__ __launch_bounds__(256) void cells_to_half_kernel(const float* 
 //     through a 128-byte per-wave LDS patch: 1 ds_write_b32 + 4 ds_read_b128;
 //   * epilogue: 16 v_mul_f32 + 8 v_max3 per lane; at a passage's last step the two lane halves are combined and the
 //     32 per-token maxima summed.
-// Rows past the end of a passage (tail step) are DUPLICATES of the passage's last row -- the lane clamps its row
-// index before it forms any address, so residual, code, score row and inv_norm all belong to that row -- and a
-// duplicate cannot change a maximum: no masking anywhere, and no bytes fetched from behind the passage.
+// Packed steps: a passage is padded to a multiple of 8 rows, not 32.  Register quad g (registers 4g .. 4g+3) of the
+// accumulator holds rows 8g .. 8g+7 in both lane halves, so when a passage ends at quad g < 4 of a step, the wave's next
+// passage starts at quad g of the SAME step: which passage a value belongs to is a wave-uniform choice per register quad
+// (StepTag.g), and no accumulator value needs a per-lane mask.  A step carries at most two passages (more buys nothing on
+// passages of ~80 rows: 1.047 row slots per real embedding with two, 1.193 with one passage per step); the row sweep
+// (ROWS) keeps one passage per step (kPack).  Rows past the end
+// of a passage (inside its last quad) are DUPLICATES of the passage's last row -- the lane clamps its row index before
+// it forms any address, so residual, code, score row and inv_norm all belong to that row -- and a duplicate cannot
+// change a maximum: no masking anywhere, and no bytes fetched from behind a passage.
 // Software pipeline, three steps in flight per wave: A(i+2) residual + code loads; G(i+1) score-row gather + inv_norm
 // (both need A's data: the code, resp. nothing); C(i) compute.  The loop body is branch-free apart from the
 // end-of-passage store; steps past the end of the wave's work are redirected to embedding 0 and discarded.
@@ -1075,14 +1081,23 @@ static __global__ __launch_bounds__(256) void cells_to_half_kernel(const float* 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-struct StepTag {      // wave-uniform description of a step
-    int j;            // candidate slot (ROWS: list position), -1 = dummy
-    int rows;         // valid rows (1..32)
-    int last;         // 1 = last step of its passage; 3 = ... which is also the last passage of the wave's 64-passage chunk
-    int base;         // index of the step's first embedding inside its passage
+struct StepTag {      // wave-uniform description of a step: an optional head passage in quads 0 .. g-1, the tail passage after it
+    int j;            // tail: candidate slot (ROWS: list position), -1 = dummy
+    int rows;         // tail: valid rows (from row 8g of the step on)
+    int last;         // tail: 1 = last step of its passage; 3 = ... which is also the last passage of the wave's 64-passage chunk
+    int base;         // tail: index of its first row in this step inside its passage (a multiple of 8)
+    int g;            // 0: the tail fills the step; 1..3: quads 0 .. g-1 hold the last rows of the head passage, which ends here
+    int jh;           // head: candidate slot
+    int rowsh;        // head: valid rows (1 .. 8g)
+    int baseh;        // head: index of its first row in this step inside its passage
 };
 
 constexpr int kStepRows = 32;      // embeddings per step; codes0 / residuals / inv_norm are padded by this many entries
+                                   // (a dummy step reads embeddings 0 .. 31; a real one never reads past its passages)
+// A packed step addresses both passages from the head's first row with 32-bit lane byte offsets (row * 32 + 16h): the
+// tail is packed only if its step rows start less than this many embeddings behind that row, so that every offset
+// stays below 2^32.  Candidate ranges of a large shard can be farther apart; the tail then starts a step of its own.
+constexpr uint32_t kPackSpan = (1u << 27) - kStepRows;
 
 // fp32 -> fp16 rounded toward -inf (a lower bound of x that is at most one fp16 ulp away)
 __device__ __forceinline__ uint32_t f32_to_f16_floor(float x) {
@@ -1154,8 +1169,8 @@ constexpr int kApproxLdsLut = 256 * 256;            // 256 entries x 32 lane slo
 // wrong by design): 1 no score-row gather; 2 gather from a 64-KB window of the table (always L2-hot); 3 no residual
 // stream; 4 plain (temporal) stream loads; 5 no LUT expansion / MFMA; 6 v_pk_mul_f32 instead of v_mul_f32; 7 no memory
 // access in the loop at all; 8 no result stores (what the passage-end stores and the waits they widen cost).
-// Round 6: 11 = the walk over the passages in closed form (every passage three steps, no v_readlane header look-ups, a third of
-// the scalar instructions): the most a step-descriptor table read with s_load could save (profiles/r06_experiments.md section 2).
+// (11, the walk in closed form of round 6 -- profiles/r06_experiments.md section 2 -- modelled one passage per 32-row step and
+// was retired with the packed steps.)
 // Round 5 (profiles/r05_pass1_ablations.jsonl): 10 = the row-mask sweep folded into pass 1 (every step compares its 16 values
 // against the RUNNING per-token maximum and the passage's 256-bit mask is stored at its last step: what that costs the
 // dominant kernel).  (Variant 9 of that round, the timing side of the 8-bit score rows, became CELL8.)
@@ -1222,6 +1237,11 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
     // A wave therefore owns a CONTIGUOUS range of candidate slots now (it used to take every stride-th one), so that the
     // results of consecutive passages are consecutive in memory.
     constexpr int kStageBytes = 16 * 64 + 64;
+    // packed steps (StepTag.g > 0) in pass 1 only.  The row sweep walks each passage alone: with a second stored maximum per step
+    // and a window per quad it measured slower (0.070 -> 0.073 ms on the headline: it waits on latency, and the packed walk adds
+    // scalar work and a second load per step), and over 8-bit rows it did not fit three waves per SIMD without spilling.  ABL 10
+    // (the row mask fused into pass 1) keeps one passage per step too: its mask code knows a single passage per step
+    constexpr bool kPack = !ROWS && ABL != 10;
     __shared__ __attribute__((aligned(16))) unsigned char stage_s[ROWS ? 16 : (kApproxThreads / 64) * kStageBytes];
     unsigned char* mystage = stage_s + (ROWS ? 0 : wave * kStageBytes);
     for (int i = threadIdx.x; i < 256 * 32; i += kApproxThreads) {
@@ -1310,7 +1330,8 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
 
         // ---- wave-uniform iterator over the steps of passages j0, j0 + 1, ... ---------------------------------
         // The headers {first embedding, length} of the wave's next 64 passages sit in one VGPR pair (lane k =
-        // k-th passage) and are extracted with v_readlane: no memory wait at a passage switch.
+        // k-th passage) and are extracted with v_readlane: no memory wait at a passage switch.  it_* is the passage
+        // whose rows start the next step, at row it_base of it.
         for (int j0 = j_first; j0 < j_end; j0 += 64) {
         const int jl = j0 + lane;
         int slot_l = jl < j_end ? jl : j0;                   // candidate slot of this lane's passage
@@ -1322,49 +1343,73 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
         int it_len = (int)__builtin_amdgcn_readlane(hv.y, 0);
         int it_slot = __builtin_amdgcn_readlane(slot_l, 0);
         int it_base = 0;
-        // ABL 11: every passage of the chunk 82 embeddings long (the headline mean; 3 steps, mean 3.05), their first embeddings evenly
-        // spread over the chunk's real span: the memory pattern of the real walk without its per-passage header look-ups
-        const uint32_t abl_stride = ABL == 11 ? ((uint32_t)__builtin_amdgcn_readlane(hv.x, nd - 1) - it_off) / (uint32_t)nd : 0u;
-        if (ABL == 11) it_len = 82;
-        const uint32_t abl_bound = ABL == 11 ? (uint32_t)__builtin_amdgcn_readlane(hv.x, nd - 1) : 0u;   // (the arrays are padded by a step)
 
-        // stage A: residual bytes (16 B / lane), code and inv_norm of the lane's row (dword each), ROWS: stored maximum
+        // stage A: residual bytes (16 B / lane), code and inv_norm of the lane's row (dword each), ROWS: stored maximum.
+        // When the passage it_* ends at quad g < 4 of the step and the chunk holds a next passage, that one fills quads
+        // g .. 3: it becomes the step's tail and the ending passage its head (StepTag).  Lane r < 8g takes row r of the
+        // head, every other lane row r - 8g of the tail, each clamped to its passage's last row; both are addressed from
+        // the head's first row e0 (the tail's first row is d rows behind it).
 #define CLB_STAGE_A(RB, CV, PM, TAG)                                                                    \
     {                                                                                                       \
         const bool live = it_k < nd;                                                                        \
-        const uint32_t e0 = live ? (ABL == 11 ? min(it_off + (uint32_t)it_base, abl_bound) : it_off + (uint32_t)it_base) : 0u; \
+        const uint32_t e0 = live ? it_off + (uint32_t)it_base : 0u;                                         \
         const int left = live ? it_len - it_base : kStepRows;                                               \
         const int rows = left < kStepRows ? left : kStepRows;                                               \
-        if (ROWS) PM = tmax[(size_t)(live ? it_slot : 0) * 32];   /* the passage's stored maximum of token r */ \
-        const uint32_t rr = min((uint32_t)r, (uint32_t)(rows - 1));   /* tail lanes duplicate the last row */ \
+        int slot_t = live ? it_slot : 0;                                                                    \
+        uint32_t d_ = 0;                                                                                    \
+        TAG.j = live ? j0 + it_k : -1;                                                                      \
+        TAG.rows = rows;                                                                                    \
+        TAG.last = 0;                                                                                       \
+        TAG.base = it_base;                                                                                 \
+        TAG.g = 0; TAG.jh = -1; TAG.rowsh = rows; TAG.baseh = 0;                                            \
+        if (left <= kStepRows) {        /* the passage ends in this step */                                \
+            const int kb = it_k + 1;                                                                        \
+            const int kk = kb < 64 ? kb : 63;                                                               \
+            const uint32_t off_b = __builtin_amdgcn_readlane(hv.x, kk);                                     \
+            const int len_b = (int)__builtin_amdgcn_readlane(hv.y, kk);                                     \
+            const int slot_b = __builtin_amdgcn_readlane(slot_l, kk);                                       \
+            const int gq = (rows + 7) >> 3;                                                                 \
+            d_ = off_b - e0;            /* (wraps to a huge value if the next passage lies below) */         \
+            if (kPack && gq >= 1 && gq < 4 && kb < nd && len_b > 0 && d_ < kPackSpan) {   /* pack it behind quad gq */ \
+                const int cap = kStepRows - 8 * gq;                                                         \
+                TAG.g = gq; TAG.jh = TAG.j; TAG.rowsh = rows; TAG.baseh = it_base;                          \
+                TAG.j = j0 + kb; TAG.rows = len_b < cap ? len_b : cap; TAG.base = 0;                         \
+                slot_t = slot_b;                                                                            \
+                if (len_b <= cap) {     /* ... and it ends here too */                                      \
+                    TAG.last = kb + 1 >= nd ? 3 : 1;                                                        \
+                    it_k = kb + 1;                                                                          \
+                    const int kc = it_k < 64 ? it_k : 63;                                                   \
+                    it_off = __builtin_amdgcn_readlane(hv.x, kc);                                           \
+                    it_len = (int)__builtin_amdgcn_readlane(hv.y, kc);                                      \
+                    it_slot = __builtin_amdgcn_readlane(slot_l, kc);                                        \
+                    it_base = 0;                                                                            \
+                } else {                                                                                    \
+                    it_k = kb; it_off = off_b; it_len = len_b; it_slot = slot_b; it_base = cap;             \
+                }                                                                                           \
+            } else {                                                                                        \
+                d_ = 0;                                                                                     \
+                TAG.last = kb >= nd ? 3 : 1;                                                                \
+                it_k = kb; it_off = off_b; it_len = len_b; it_slot = slot_b; it_base = 0;                   \
+            }                                                                                               \
+        } else it_base += kStepRows;                                                                        \
+        if (ROWS) PM = tmax[(size_t)slot_t * 32];   /* the passage's stored maximum of token r */            \
+        const uint32_t q8_ = 8u * (uint32_t)TAG.g;                                                          \
+        /* row of lane r relative to e0; lanes past a passage's end duplicate its last row */               \
+        const uint32_t rr = (uint32_t)r < q8_ ? min((uint32_t)r, (uint32_t)(TAG.rowsh - 1))                 \
+                                              : min((uint32_t)r, q8_ + (uint32_t)(TAG.rows - 1)) + (d_ - q8_); \
         /* wave-uniform 64-bit bases + 32-bit lane offsets: the scalar-base form of global_load        */ \
         const uint8_t* rbase_ = residuals + (size_t)e0 * 32;                                                \
-        const uint32_t* cbase_ = codeinv + (size_t)e0;                                                      \
+        const char* cbase_ = reinterpret_cast<const char*>(codeinv + (size_t)e0);                           \
         const uint32_t roff_ = rr * 32u + h16;                                                              \
+        const uint32_t coff_ = rr * 4u;                                                                     \
         /* the three streams are read once per query: non-temporal loads keep them from evicting the score  */ \
         /* table, which the gathers want in L2 (measured: 0.779 -> 0.762 ms)                               */ \
         if (ABL == 3 || ABL == 7) RB = u32x4{e0 * 2654435761u + rr, e0 ^ h16, e0 + 77u * rr, e0 * 40503u};  \
         else if (ABL == 4) RB = *reinterpret_cast<const u32x4*>(rbase_ + roff_);                            \
         else RB = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(rbase_ + roff_));               \
         if (ABL == 7) CV = (e0 * 97u + rr) & 131071u;                                                       \
-        else if (ABL == 4) CV = cbase_[rr];                                                                 \
-        else CV = __builtin_nontemporal_load(cbase_ + rr);      /* code | quantised inv_norm */              \
-        TAG.j = live ? j0 + it_k : -1;                                                                      \
-        TAG.rows = rows;                                                                                    \
-        TAG.last = left <= kStepRows ? (it_k + 1 >= nd ? 3 : 1) : 0;                                        \
-        TAG.base = it_base;                                                                                 \
-        it_base += kStepRows;                                                                               \
-        if (ABL == 11) {        /* closed-form walk: no header look-ups (what a step-descriptor table could save at most) */ \
-            if (TAG.last) { it_k += 1; it_off += abl_stride; it_base = 0; }                                 \
-        } else                                                                                              \
-        if (TAG.last) {                                                                                     \
-            it_k += 1;                                                                                      \
-            const int kk = it_k < 64 ? it_k : 63;                                                           \
-            it_off = __builtin_amdgcn_readlane(hv.x, kk);                                                   \
-            it_len = (int)__builtin_amdgcn_readlane(hv.y, kk);                                              \
-            it_slot = __builtin_amdgcn_readlane(slot_l, kk);                                                \
-            it_base = 0;                                                                                    \
-        }                                                                                                   \
+        else if (ABL == 4) CV = *reinterpret_cast<const uint32_t*>(cbase_ + coff_);                         \
+        else CV = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(cbase_ + coff_));   /* code | quantised inv_norm */ \
     }
         // stage G: the score row of the lane's embedding: tokens 8h..8h+7 and 16+8h..16+8h+7 (fp16), 2 x 16 B
 #define CLB_STAGE_G(CV, X0, X1, SLOT)                                                                       \
@@ -1448,6 +1493,31 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
         }                                                                                                   \
         CLB_APPROX_PRIO_DOWN                                                                                \
     }
+        // pass 1: a passage ends with the per-token maxima MX of its lane half: the two halves combined, the 32 maxima summed,
+        // both into the wave's staging block (LAST == 3: the chunk's last passage, the block leaves)
+#define CLB_PASSAGE_END(MX, J, LAST)                                                                        \
+    {                                                                                                       \
+        float m_ = max_lane_halves(MX);                                                                     \
+        if (CELL8) m_ *= stp;                /* cells -> score units, once per passage and token */         \
+        const float sum = sum_lanes_0_31(r < T ? m_ : 0.f);     /* valid in lanes 16..31 */                 \
+        if (ABL == 8) { if (sum == 12345.678f) out[0] = m_; }    /* ablation: no result stores */            \
+        else if ((J) >= 0) {                                                                                \
+            /* into the wave's staging block: passage p = (j - j0) & 15 of the current group of 16 */       \
+            const int p_ = ((J) - j0) & 15;                                                                 \
+            if (h == 0) *reinterpret_cast<uint16_t*>(mystage + p_ * 64 + 2 * r) = (uint16_t)f32_to_f16_floor(m_); \
+            if (lane == 16) *reinterpret_cast<float*>(mystage + 1024 + 4 * p_) = sum;                       \
+            if (p_ == 15 || (LAST) == 3) {    /* the group is full, or the chunk ends: p_ + 1 passages leave */ \
+                const int jb_ = (J) - p_;                                                                   \
+                __builtin_amdgcn_wave_barrier();                                                            \
+                const u32x4 tk_ = *reinterpret_cast<const u32x4*>(mystage + 16 * lane);                     \
+                const float sc_ = *reinterpret_cast<const float*>(mystage + 1024 + 4 * (lane & 15));         \
+                if (lane < 4 * (p_ + 1))                                                                    \
+                    *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned char*>(tokmax + ((size_t)b * cand_cap + jb_) * 32) + 16 * lane) = tk_; \
+                if (lane <= p_) out[jb_ + lane] = sc_;                                                      \
+                __builtin_amdgcn_wave_barrier();                                                            \
+            }                                                                                               \
+        }                                                                                                   \
+    }
 #define CLB_STAGE_E(ACC, INVB, PM, TAG)                                                                     \
     {                                                                                                       \
         f32x4 iq[4];                                                                                        \
@@ -1495,6 +1565,15 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
                 wm0 = wm1 = wm2 = wm3 = 0;                                                                  \
             }                                                                                               \
         } else {                                                                                            \
+            if (TAG.g) {            /* quads 0 .. g-1 end the head passage, quads g .. 3 start the tail */   \
+                const float q0_ = fmaxf(fmaxf(fmaxf(v[0], v[1]), v[2]), v[3]);                              \
+                const float q1_ = fmaxf(fmaxf(fmaxf(v[4], v[5]), v[6]), v[7]);                              \
+                const float q2_ = fmaxf(fmaxf(fmaxf(v[8], v[9]), v[10]), v[11]);                            \
+                const float q3_ = fmaxf(fmaxf(fmaxf(v[12], v[13]), v[14]), v[15]);                          \
+                const float mh_ = fmaxf(fmaxf(mx, q0_), fmaxf(TAG.g > 1 ? q1_ : kNegInf, TAG.g > 2 ? q2_ : kNegInf)); \
+                CLB_PASSAGE_END(mh_, TAG.jh, 1);                                                            \
+                mx = fmaxf(fmaxf(TAG.g > 1 ? kNegInf : q1_, TAG.g > 2 ? kNegInf : q2_), q3_);               \
+            } else {                                                                                        \
             float m01 = fmaxf(fmaxf(v[0], v[1]), v[2]);                                                     \
             float m23 = fmaxf(fmaxf(v[3], v[4]), v[5]);                                                     \
             float m45 = fmaxf(fmaxf(v[6], v[7]), v[8]);                                                     \
@@ -1503,6 +1582,7 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
             m01 = fmaxf(fmaxf(m01, m23), m45);                                                              \
             m67 = fmaxf(fmaxf(m67, m89), v[15]);                                                            \
             mx = fmaxf(fmaxf(mx, m01), m67);                                                                \
+            }                                                                                               \
             if (ABL == 10) {     /* the sweep's window test against the RUNNING maximum, mask kept per passage */ \
                 const float lo = r < T ? mx - 0.09f : __builtin_inff();                                     \
                 uint32_t lm = 0;                                                                            \
@@ -1529,26 +1609,7 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
                     }                                                                                       \
                     wm0 = wm1 = wm2 = wm3 = 0;                                                              \
                 }                                                                                           \
-                mx = max_lane_halves(mx);                                                                   \
-                if (CELL8) mx *= stp;                /* cells -> score units, once per passage and token */    \
-                const float sum = sum_lanes_0_31(r < T ? mx : 0.f);     /* valid in lanes 16..31 */         \
-                if (ABL == 8) { if (sum == 12345.678f) out[0] = mx; }    /* ablation: no result stores */     \
-                else if (TAG.j >= 0) {                                                                      \
-                    /* into the wave's staging block: passage p = (j - j0) & 15 of the current group of 16 */ \
-                    const int p_ = (TAG.j - j0) & 15;                                                       \
-                    if (h == 0) *reinterpret_cast<uint16_t*>(mystage + p_ * 64 + 2 * r) = (uint16_t)f32_to_f16_floor(mx); \
-                    if (lane == 16) *reinterpret_cast<float*>(mystage + 1024 + 4 * p_) = sum;               \
-                    if (p_ == 15 || TAG.last == 3) {    /* the group is full, or the chunk ends: p_ + 1 passages leave */ \
-                        const int jb_ = TAG.j - p_;                                                         \
-                        __builtin_amdgcn_wave_barrier();                                                    \
-                        const u32x4 tk_ = *reinterpret_cast<const u32x4*>(mystage + 16 * lane);             \
-                        const float sc_ = *reinterpret_cast<const float*>(mystage + 1024 + 4 * (lane & 15)); \
-                        if (lane < 4 * (p_ + 1))                                                            \
-                            *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned char*>(tokmax + ((size_t)b * cand_cap + jb_) * 32) + 16 * lane) = tk_; \
-                        if (lane <= p_) out[jb_ + lane] = sc_;                                              \
-                        __builtin_amdgcn_wave_barrier();                                                    \
-                    }                                                                                       \
-                }                                                                                           \
+                CLB_PASSAGE_END(mx, TAG.j, TAG.last);                                                       \
                 mx = kNegInf;                                                                               \
             }                                                                                               \
         }                                                                                                   \
@@ -1582,6 +1643,7 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
             // tp / pmp: tag and stored maximum of the step whose epilogue is pending; the dummy "previous step" of a
             // chunk's first iteration ends a passage nobody stores (j < 0), which also resets mx and the row mask
             StepTag tp; tp.j = -1; tp.rows = kStepRows; tp.last = 1; tp.base = 0;
+            tp.g = 0; tp.jh = -1; tp.rowsh = kStepRows; tp.baseh = 0;
             uint16_t pmp = 0;
 #pragma unroll
             for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
@@ -1625,6 +1687,7 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
 #undef CLB_STAGE_G
 #undef CLB_STAGE_CM
 #undef CLB_STAGE_E
+#undef CLB_PASSAGE_END
 #undef CLB_LUT
     }
 }
