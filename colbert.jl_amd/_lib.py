@@ -11,7 +11,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
-# COLBERT_HIP_LIB: another build of the same library (e.g. the tuning build `make ABLATIONS=1`)
+# COLBERT_HIP_LIB: another build of the same library (e.g. a parent commit's build, `make SUF=_old`)
 LIB_PATH = os.environ.get("COLBERT_HIP_LIB") or os.path.join(CSRC, "libcolbert_hip.so")
 HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "colbert_hip.h"))
 

@@ -746,16 +746,11 @@ static __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll
     for (int p = 0; p < kTopPartial; ++p) { bv0[p] = bv1[p] = kNegInf; bi0[p] = bi1[p] = 0x7fffffff; }
     // 48 MFMAs: the staged tile against this wave's two queries
-    // (-DCLB_ABL_CENTROID_X1, tuning builds only: ONE product per fp32 product -- what a single-fp16-product table would cost)
-#ifdef CLB_ABL_CENTROID_X1
-#define CLB_TM_LO_PRODUCTS(S)      /* (the lo plane is still loaded and staged: an upper bound of the single-product kernel's time) */
-#else
 #define CLB_TM_LO_PRODUCTS(S)                                                                             \
             acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, __builtin_bit_cast(bf16x8, qh[0][S]), acc0, 0, 0, 0); \
             acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, __builtin_bit_cast(bf16x8, qh[1][S]), acc1, 0, 0, 0); \
             acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, __builtin_bit_cast(bf16x8, ql[0][X1 ? 0 : S]), acc0, 0, 0, 0); \
             acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, __builtin_bit_cast(bf16x8, ql[1][X1 ? 0 : S]), acc1, 0, 0, 0);
-#endif
 #define CLB_TM_STORE(DATA, ADDR) asm volatile("global_store_dwordx4 %0, %1, off" :: "v"(ADDR), "v"(DATA));
 #define CLB_TM_MFMA(MY)                                                                                   \
     {                                                                                                     \
@@ -1067,7 +1062,7 @@ static __global__ __launch_bounds__(256) void cells_to_half_kernel(const float* 
 // passage starts at quad g of the SAME step: which passage a value belongs to is a wave-uniform choice per register quad
 // (StepTag.g), and no accumulator value needs a per-lane mask.  A step carries at most two passages (more buys nothing on
 // passages of ~80 rows: 1.047 row slots per real embedding with two, 1.193 with one passage per step); the row sweep
-// (ROWS) keeps one passage per step (kPack).  Rows past the end
+// (ROWS) keeps one passage per step.  Rows past the end
 // of a passage (inside its last quad) are DUPLICATES of the passage's last row -- the lane clamps its row index before
 // it forms any address, so residual, code, score row and inv_norm all belong to that row -- and a duplicate cannot
 // change a maximum: no masking anywhere, and no bytes fetched from behind a passage.
@@ -1079,7 +1074,6 @@ static __global__ __launch_bounds__(256) void cells_to_half_kernel(const float* 
 // grid = 8 * wg_per_group (1-D) or (G, B) (2-D: few passages per query), block = kApproxThreads (12 waves).
 // -------------------------------------------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct StepTag {      // wave-uniform description of a step: an optional head passage in quads 0 .. g-1, the tail passage after it
     int j;            // tail: candidate slot (ROWS: list position), -1 = dummy
@@ -1129,29 +1123,7 @@ __device__ __forceinline__ float sum_lanes_0_31(float s) {
 // (hipcc drops the second result of __builtin_amdgcn_permlane32_swap(m, m): one ds_bpermute per passage instead)
 __device__ __forceinline__ float max_lane_halves(float m) { return fmaxf(m, __shfl_xor(m, 32, 64)); }
 
-#ifndef CLB_APPROX_WAVES
-#define CLB_APPROX_WAVES 12
-#endif
-#ifdef CLB_APPROX_SPLIT_LUT
-constexpr bool kSplitLut = true;    // experiment: the 16 table reads of a step in two halves (16 VGPRs less)
-#else
-constexpr bool kSplitLut = false;
-#endif
-// experiment builds (make SUF=_prio EXTRA=-DCLB_APPROX_PRIO=1): the wave raises its issue priority for the ten dependent MFMAs of a step
-#if defined(CLB_APPROX_PRIO) && CLB_APPROX_PRIO
-#define CLB_APPROX_PRIO_UP __builtin_amdgcn_s_setprio(CLB_APPROX_PRIO);
-#define CLB_APPROX_PRIO_DOWN __builtin_amdgcn_s_setprio(0);
-#else
-#define CLB_APPROX_PRIO_UP
-#define CLB_APPROX_PRIO_DOWN
-#endif
-// waves per SIMD the register budget is set for: the work-group's own by default; an experiment build may ask for more than its
-// waves need (make SUF=_w8 EXTRA='-DCLB_APPROX_WAVES=8 -DCLB_APPROX_MINOCC=3': two waves per SIMD within the registers of three,
-// which leaves a third of every SIMD's register file to the kernels of the OTHER batch in flight)
-#ifndef CLB_APPROX_MINOCC
-#define CLB_APPROX_MINOCC (CLB_APPROX_WAVES / 4)
-#endif
-constexpr int kApproxThreads = 64 * CLB_APPROX_WAVES;   // 12 waves per work-group = 3 per SIMD, one work-group per CU
+constexpr int kApproxThreads = 768;                 // 12 waves per work-group = 3 per SIMD, one work-group per CU
 constexpr int kApproxLdsLut = 256 * 256;            // 256 entries x 32 lane slots x 8 B
 
 // ROWS = false: pass 1 over every candidate; besides the score it leaves tokmax[b][slot][32] = the per-token maxima
@@ -1165,15 +1137,8 @@ constexpr int kApproxLdsLut = 256 * 256;            // 256 entries x 32 lane slo
 //        more permissive) a_t and writes rowmask[b][list position][4] x 64 bits; passages longer than kMaxMaskedRows
 //        embeddings are ignored downstream (the exact kernel then takes every row).  Comparisons are written
 //        !(v < lo): a NaN or an infinite window (guarded query, select_margin_kernel) selects the row.
-// ABL != 0: ablation variants for the roofline analysis (instantiated only in -DCLB_ABLATIONS builds; results are
-// wrong by design): 1 no score-row gather; 2 gather from a 64-KB window of the table (always L2-hot); 3 no residual
-// stream; 4 plain (temporal) stream loads; 5 no LUT expansion / MFMA; 6 v_pk_mul_f32 instead of v_mul_f32; 7 no memory
-// access in the loop at all; 8 no result stores (what the passage-end stores and the waits they widen cost).
-// (11, the walk in closed form of round 6 -- profiles/r06_experiments.md section 2 -- modelled one passage per 32-row step and
-// was retired with the packed steps.)
-// Round 5 (profiles/r05_pass1_ablations.jsonl): 10 = the row-mask sweep folded into pass 1 (every step compares its 16 values
-// against the RUNNING per-token maximum and the passage's 256-bit mask is stored at its last step: what that costs the
-// dominant kernel).  (Variant 9 of that round, the timing side of the 8-bit score rows, became CELL8.)
+// The ablation variants and the pipelined epilogue (PIPE) that were measured on this kernel are retired: their results are in
+// DESIGN 4.3 and profiles/r0{3,5,6}_experiments.md.
 // GL = 1 ("LDS-DMA gather", round 3): the score rows reach the wave through LDS instead of VGPRs.  Four ADJACENT lanes
 // fetch the 64 bytes of one row with global_load_lds_dwordx4 (16 rows per instruction, 2 instructions per step) -- one
 // L1 tag look-up per row where the VGPR form (lane (r, h) fetching 2 x 16 B of row r, the lanes of a row 32 apart)
@@ -1191,12 +1156,6 @@ constexpr int kApproxLdsLut = 256 * 256;            // 256 entries x 32 lane slo
 // own vmcnt arithmetic for the VGPR loads does not see the DMAs; its waits are therefore stronger than needed by the
 // DMAs in between, never weaker.  A slot is re-filled three stages after its reads were waited for (lgkmcnt) -- both
 // in program order, and the "memory" clobbers keep the compiler from moving the ring reads across either.
-// PIPE = 1 (round-3 experiment, instantiated in -DCLB_ABLATIONS builds only): the epilogue of step i-1 (16 multiplies by
-// inv_norm, the maxima, the row-mask bits) is issued in the shadow of step i's MFMA chain -- a wave issues in order and
-// the ten MFMAs of a step depend on each other (SQ_WAIT_INST_ANY: 36 % of the wave cycles).  hipcc does interleave the
-// two streams, but the second accumulator set takes the kernel to the 168-VGPR cap of three waves per SIMD (7-24 spilled
-// registers) and the pass got SLOWER on every workload (0.662 -> 0.672 ms, uniform codes 1.46 -> 1.56, built index
-// 0.653 -> 0.699; the row sweep 0.069 -> 0.107): the pass is not short of issue slots, it waits on memory.
 // CELL8 = true (round 6): the score rows are 32-byte rows of 8-bit cells (token_range_kernel's comment).  Lane (r, h) fetches
 // ONE 16-byte piece (tokens 16h .. 16h+15 of row code_r) and expands it with eight v_perm_b32 to the fp16 values 1024 + cell
 // (0x6400 | cell), which the two selection MFMAs add into an accumulator that starts at k_t - 1024 (lane = token): after
@@ -1204,8 +1163,8 @@ constexpr int kApproxLdsLut = 256 * 256;            // 256 entries x 32 lane slo
 // acc * step_t is the token's score: the positive per-token factor commutes with the maximum over a passage's embeddings and
 // is applied once per passage (the row sweep applies it per value: the same product for the row that holds the maximum).
 // GL = 1: two adjacent lanes fetch a row -- ONE DMA instruction per step, a 1-KB ring slot, vmcnt(3).
-template <bool ROWS, int ABL = 0, int GL = 0, int PIPE = 0, bool CELL8 = false>
-static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void score_approx32_kernel(
+template <bool ROWS, int GL = 0, bool CELL8 = false>
+static __global__ __launch_bounds__(kApproxThreads, kApproxThreads / 256) void score_approx32_kernel(
     const float* __restrict__ weights, const uint32_t* __restrict__ codeinv, const uint8_t* __restrict__ residuals,
     int cbits, float inv_lo, float inv_step, const float* __restrict__ Q, const uint32_t* __restrict__ cells16,
     const uint2* __restrict__ cand_hdr, const int* __restrict__ ncand, float* __restrict__ scores, int K, int T,
@@ -1224,12 +1183,11 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
     // bank pair, so the 16 table reads of a step are conflict-free whatever the bytes are (a single 2-KB table costs
     // ~2 extra LDS cycles per read on random bytes and made the LDS pipe the busiest unit of the kernel)
     __shared__ __attribute__((aligned(16))) unsigned char lut_s[kApproxLdsLut];
-    __shared__ __attribute__((aligned(16))) float invx[kApproxThreads / 64][2 * kStepRows];   // two patches (PIPE)
-    static_assert(GL == 0 || ABL == 0, "the ablation variants exist for the VGPR gather only");
-    static_assert(!CELL8 || ABL == 0, "the ablation variants exist for the fp16 score rows only");
+    // (two patches per wave, one of them unused: the second served the retired PIPE variant, and dropping it changes the LDS
+    // layout and so the code -- left to a measured change)
+    __shared__ __attribute__((aligned(16))) float invx[kApproxThreads / 64][2 * kStepRows];
     constexpr int kSlotBytes = CELL8 ? 1024 : 2048;      // 32 rows x 32 B / 64 B
     constexpr int kRingBytes = 3 * kSlotBytes;           // three steps in flight, per wave
-    static_assert(GL == 0 || CLB_APPROX_WAVES <= 12, "the 3-slot ring of the LDS-DMA form fits 160 KB of LDS up to 12 waves");
     __shared__ __attribute__((aligned(16))) unsigned char ring_s[GL ? (kApproxThreads / 64) * kRingBytes : 16];
     // Results of up to 16 consecutive passages of a wave wait here (32 fp16 token maxima + the fp32 score each) and leave as
     // TWO full-width stores (round 6).  A wave used to issue a 2-byte-per-lane and a one-lane store at every passage end, inside
@@ -1239,9 +1197,7 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
     constexpr int kStageBytes = 16 * 64 + 64;
     // packed steps (StepTag.g > 0) in pass 1 only.  The row sweep walks each passage alone: with a second stored maximum per step
     // and a window per quad it measured slower (0.070 -> 0.073 ms on the headline: it waits on latency, and the packed walk adds
-    // scalar work and a second load per step), and over 8-bit rows it did not fit three waves per SIMD without spilling.  ABL 10
-    // (the row mask fused into pass 1) keeps one passage per step too: its mask code knows a single passage per step
-    constexpr bool kPack = !ROWS && ABL != 10;
+    // scalar work and a second load per step), and over 8-bit rows it did not fit three waves per SIMD without spilling
     __shared__ __attribute__((aligned(16))) unsigned char stage_s[ROWS ? 16 : (kApproxThreads / 64) * kStageBytes];
     unsigned char* mystage = stage_s + (ROWS ? 0 : wave * kStageBytes);
     for (int i = threadIdx.x; i < 256 * 32; i += kApproxThreads) {
@@ -1370,7 +1326,7 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
             const int slot_b = __builtin_amdgcn_readlane(slot_l, kk);                                       \
             const int gq = (rows + 7) >> 3;                                                                 \
             d_ = off_b - e0;            /* (wraps to a huge value if the next passage lies below) */         \
-            if (kPack && gq >= 1 && gq < 4 && kb < nd && len_b > 0 && d_ < kPackSpan) {   /* pack it behind quad gq */ \
+            if (!ROWS && gq >= 1 && gq < 4 && kb < nd && len_b > 0 && d_ < kPackSpan) {   /* pack it behind quad gq */ \
                 const int cap = kStepRows - 8 * gq;                                                         \
                 TAG.g = gq; TAG.jh = TAG.j; TAG.rowsh = rows; TAG.baseh = it_base;                          \
                 TAG.j = j0 + kb; TAG.rows = len_b < cap ? len_b : cap; TAG.base = 0;                         \
@@ -1404,12 +1360,8 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
         const uint32_t coff_ = rr * 4u;                                                                     \
         /* the three streams are read once per query: non-temporal loads keep them from evicting the score  */ \
         /* table, which the gathers want in L2 (measured: 0.779 -> 0.762 ms)                               */ \
-        if (ABL == 3 || ABL == 7) RB = u32x4{e0 * 2654435761u + rr, e0 ^ h16, e0 + 77u * rr, e0 * 40503u};  \
-        else if (ABL == 4) RB = *reinterpret_cast<const u32x4*>(rbase_ + roff_);                            \
-        else RB = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(rbase_ + roff_));               \
-        if (ABL == 7) CV = (e0 * 97u + rr) & 131071u;                                                       \
-        else if (ABL == 4) CV = *reinterpret_cast<const uint32_t*>(cbase_ + coff_);                         \
-        else CV = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(cbase_ + coff_));   /* code | quantised inv_norm */ \
+        RB = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(rbase_ + roff_));                    \
+        CV = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(cbase_ + coff_));   /* code | quantised inv_norm */ \
     }
         // stage G: the score row of the lane's embedding: tokens 8h..8h+7 and 16+8h..16+8h+7 (fp16), 2 x 16 B
 #define CLB_STAGE_G(CV, X0, X1, SLOT)                                                                       \
@@ -1426,17 +1378,15 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
                      :: "v"(c16 + ((ca_ << 6) + gl_poff)), "v"(c16 + ((cb_ << 6) + gl_poff)),               \
                         "s"(ring_lds + (SLOT) * 2048u) : "memory", "scc");                                   \
     } else {                                                                                                \
-        const char* row_ = CELL8 ? c16 + (((CV & cmask) << 5) + h16)                                        \
-                                 : c16 + (((ABL == 2 ? (CV & 1023u) : (CV & cmask)) << 6) + h16);           \
-        if (ABL == 1 || ABL == 7) { X0 = u32x4{CV, CV, CV, CV}; X1 = X0; }                                  \
-        else if (CELL8) X0 = *reinterpret_cast<const u32x4*>(row_);      /* 16 one-byte cells: tokens 16h .. 16h+15 */ \
+        const char* row_ = CELL8 ? c16 + (((CV & cmask) << 5) + h16) : c16 + (((CV & cmask) << 6) + h16);   \
+        if (CELL8) X0 = *reinterpret_cast<const u32x4*>(row_);      /* 16 one-byte cells: tokens 16h .. 16h+15 */ \
         else {                                                                                              \
         X0 = *reinterpret_cast<const u32x4*>(row_);                                                         \
         X1 = *reinterpret_cast<const u32x4*>(row_ + 32);                                                    \
         }                                                                                                   \
     }
 #define CLB_LUT(W, N) (*reinterpret_cast<const uint2*>(lut + lut_offset<N>(W, lane8)))
-#define CLB_STAGE_CM(RB, CV, X0, X1, SLOT, ACC, INVB)                                                       \
+#define CLB_STAGE_CM(RB, CV, X0, X1, SLOT, ACC)                                                       \
     {                                                                                                       \
         if (GL && CELL8) {                                                                                  \
             /* one DMA per step: behind it are at least the next stage A's two loads and the next stage G's DMA */ \
@@ -1450,22 +1400,17 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
         }                                                                                                   \
         /* inv_norm: lane layout (row = r) -> accumulator layout (register i = row (i&3) + 8(i>>2) + 4h)  */ \
         __builtin_amdgcn_wave_barrier();                                                                    \
-        myinv[(INVB) * kStepRows + r] = fmaf((float)(CV >> cbits), inv_step, inv_lo);                                            \
+        myinv[r] = fmaf((float)(CV >> cbits), inv_step, inv_lo);                                            \
         __builtin_amdgcn_wave_barrier();                                                                    \
         /* residual byte -> 4 fp16 bucket weights through the LDS table; k-step s = bytes 2s, 2s+1.  All 16  */ \
         /* reads are issued before the first MFMA (an LDS read takes longer than an MFMA: interleaved one  */ \
         /* pair ahead, as the compiler schedules them on its own, the MFMA chain runs at the LDS latency)   */ \
         uint2 tl[16];                                                                                       \
-        if (ABL != 5) {                                                                                     \
-            tl[0] = CLB_LUT(RB[0], 0); tl[1] = CLB_LUT(RB[0], 1); tl[2] = CLB_LUT(RB[0], 2); tl[3] = CLB_LUT(RB[0], 3);     \
-            tl[4] = CLB_LUT(RB[1], 0); tl[5] = CLB_LUT(RB[1], 1); tl[6] = CLB_LUT(RB[1], 2); tl[7] = CLB_LUT(RB[1], 3);     \
-            if (!kSplitLut) {                                                                               \
-            tl[8] = CLB_LUT(RB[2], 0); tl[9] = CLB_LUT(RB[2], 1); tl[10] = CLB_LUT(RB[2], 2); tl[11] = CLB_LUT(RB[2], 3);   \
-            tl[12] = CLB_LUT(RB[3], 0); tl[13] = CLB_LUT(RB[3], 1); tl[14] = CLB_LUT(RB[3], 2); tl[15] = CLB_LUT(RB[3], 3); \
-            }                                                                                               \
-        }                                                                                                   \
+        tl[0] = CLB_LUT(RB[0], 0); tl[1] = CLB_LUT(RB[0], 1); tl[2] = CLB_LUT(RB[0], 2); tl[3] = CLB_LUT(RB[0], 3);         \
+        tl[4] = CLB_LUT(RB[1], 0); tl[5] = CLB_LUT(RB[1], 1); tl[6] = CLB_LUT(RB[1], 2); tl[7] = CLB_LUT(RB[1], 3);         \
+        tl[8] = CLB_LUT(RB[2], 0); tl[9] = CLB_LUT(RB[2], 1); tl[10] = CLB_LUT(RB[2], 2); tl[11] = CLB_LUT(RB[2], 3);       \
+        tl[12] = CLB_LUT(RB[3], 0); tl[13] = CLB_LUT(RB[3], 1); tl[14] = CLB_LUT(RB[3], 2); tl[15] = CLB_LUT(RB[3], 3);     \
         __builtin_amdgcn_sched_barrier(0);                                                                  \
-        CLB_APPROX_PRIO_UP                                                                                  \
         _Pragma("unroll") for (int i = 0; i < 16; ++i) ACC[i] = acc_init;                                   \
         if (CELL8) {         /* byte b -> fp16 1024 + b (0x6400 | b): two cells per v_perm_b32 */            \
             const u32x4 raw_ = X0;                                                                          \
@@ -1476,22 +1421,10 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
         }                                                                                                   \
         ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, X0), sel1, ACC, 0, 0, 0);    \
         ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, X1), sel2, ACC, 0, 0, 0);    \
-        if (ABL == 5) { ACC[0] += __uint_as_float(RB[0] ^ RB[1]); ACC[1] += __uint_as_float(RB[2] ^ RB[3]); } \
-        else {                                                                                              \
-            _Pragma("unroll") for (int s_ = 0; s_ < 8; ++s_) {                                              \
-                if (kSplitLut && s_ == 4) {      /* second half of the table reads, into the registers of the first */ \
-                    __builtin_amdgcn_sched_barrier(0);                                                      \
-                    tl[0] = CLB_LUT(RB[2], 0); tl[1] = CLB_LUT(RB[2], 1); tl[2] = CLB_LUT(RB[2], 2); tl[3] = CLB_LUT(RB[2], 3);   \
-                    tl[4] = CLB_LUT(RB[3], 0); tl[5] = CLB_LUT(RB[3], 1); tl[6] = CLB_LUT(RB[3], 2); tl[7] = CLB_LUT(RB[3], 3);   \
-                    __builtin_amdgcn_sched_barrier(0);                                                      \
-                }                                                                                           \
-                const int ti_ = kSplitLut ? 2 * (s_ & 3) : 2 * s_;                                          \
-                ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(                                               \
-                    __builtin_bit_cast(f16x8, u32x4{tl[ti_].x, tl[ti_].y, tl[ti_ + 1].x, tl[ti_ + 1].y}),   \
-                    __builtin_bit_cast(f16x8, qb[s_]), ACC, 0, 0, 0);                                       \
-            }                                                                                               \
-        }                                                                                                   \
-        CLB_APPROX_PRIO_DOWN                                                                                \
+        _Pragma("unroll") for (int s_ = 0; s_ < 8; ++s_)                                                    \
+            ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(                                                   \
+                __builtin_bit_cast(f16x8, u32x4{tl[2 * s_].x, tl[2 * s_].y, tl[2 * s_ + 1].x, tl[2 * s_ + 1].y}), \
+                __builtin_bit_cast(f16x8, qb[s_]), ACC, 0, 0, 0);                                           \
     }
         // pass 1: a passage ends with the per-token maxima MX of its lane half: the two halves combined, the 32 maxima summed,
         // both into the wave's staging block (LAST == 3: the chunk's last passage, the block leaves)
@@ -1500,8 +1433,7 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
         float m_ = max_lane_halves(MX);                                                                     \
         if (CELL8) m_ *= stp;                /* cells -> score units, once per passage and token */         \
         const float sum = sum_lanes_0_31(r < T ? m_ : 0.f);     /* valid in lanes 16..31 */                 \
-        if (ABL == 8) { if (sum == 12345.678f) out[0] = m_; }    /* ablation: no result stores */            \
-        else if ((J) >= 0) {                                                                                \
+        if ((J) >= 0) {                                                                                \
             /* into the wave's staging block: passage p = (j - j0) & 15 of the current group of 16 */       \
             const int p_ = ((J) - j0) & 15;                                                                 \
             if (h == 0) *reinterpret_cast<uint16_t*>(mystage + p_ * 64 + 2 * r) = (uint16_t)f32_to_f16_floor(m_); \
@@ -1518,21 +1450,16 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
             }                                                                                               \
         }                                                                                                   \
     }
-#define CLB_STAGE_E(ACC, INVB, PM, TAG)                                                                     \
+#define CLB_STAGE_E(ACC, PM, TAG)                                                                     \
     {                                                                                                       \
         f32x4 iq[4];                                                                                        \
         _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                       \
-            iq[q] = *reinterpret_cast<const f32x4*>(myinv + (INVB) * kStepRows + 8 * q + 4 * h);                                 \
+            iq[q] = *reinterpret_cast<const f32x4*>(myinv + 8 * q + 4 * h);                                 \
         /* plain v_mul_f32: packed f32 ops (v_pk_mul_f32) do not overlap the MFMAs of the co-resident waves  */ \
         /* (tools/microbench/issue_overlap: 3 per MFMA gap cost 27 cycles, 6 plain multiplies cost 3); the  */ \
-        /* empty asm keeps the SLP vectoriser from re-packing them.  ABL 6: the packed form, for comparison */ \
+        /* empty asm keeps the SLP vectoriser from re-packing them                                          */ \
         float v[16];                                                                                        \
-        if (ABL != 6) { _Pragma("unroll") for (int i = 0; i < 16; ++i) { v[i] = ACC[i] * iq[i >> 2][i & 3]; asm volatile("" : "+v"(v[i])); } } \
-        else                                                                                                \
-        _Pragma("unroll") for (int i = 0; i < 16; i += 2) {    /* v_pk_mul_f32: two rows per instruction */ \
-            const f32x2 p_ = f32x2{ACC[i], ACC[i + 1]} * f32x2{iq[i >> 2][i & 3], iq[i >> 2][(i & 3) + 1]}; \
-            v[i] = p_[0]; v[i + 1] = p_[1];                                                                 \
-        }                                                                                                   \
+        _Pragma("unroll") for (int i = 0; i < 16; ++i) { v[i] = ACC[i] * iq[i >> 2][i & 3]; asm volatile("" : "+v"(v[i])); } \
         if (ROWS) {                                                                                         \
             const __half pmh = *reinterpret_cast<const __half*>(&PM);                                       \
             const float lo = r < T ? __half2float(pmh) - window : __builtin_inff();   /* tokens past T select nothing */ \
@@ -1583,32 +1510,7 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
             m67 = fmaxf(fmaxf(m67, m89), v[15]);                                                            \
             mx = fmaxf(fmaxf(mx, m01), m67);                                                                \
             }                                                                                               \
-            if (ABL == 10) {     /* the sweep's window test against the RUNNING maximum, mask kept per passage */ \
-                const float lo = r < T ? mx - 0.09f : __builtin_inff();                                     \
-                uint32_t lm = 0;                                                                            \
-                _Pragma("unroll") for (int i = 0; i < 16; ++i) lm |= !(v[i] < lo) ? (1u << i) : 0u;         \
-                lm |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lm, 0xB1, 0xf, 0xf, true);              \
-                lm |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lm, 0x4E, 0xf, 0xf, true);              \
-                lm |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lm, 0x141, 0xf, 0xf, true);             \
-                lm |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lm, 0x140, 0xf, 0xf, true);             \
-                const uint32_t m0_ = __builtin_amdgcn_readlane(lm, 0) | __builtin_amdgcn_readlane(lm, 16);  \
-                const uint32_t m1_ = __builtin_amdgcn_readlane(lm, 32) | __builtin_amdgcn_readlane(lm, 48); \
-                uint32_t bits = ((m0_ & 0xFu) | ((m0_ & 0xF0u) << 4) | ((m0_ & 0xF00u) << 8) | ((m0_ & 0xF000u) << 12)) | \
-                                (((m1_ & 0xFu) | ((m1_ & 0xF0u) << 4) | ((m1_ & 0xF00u) << 8) | ((m1_ & 0xF000u) << 12)) << 4); \
-                if (TAG.rows < kStepRows) bits &= (1u << TAG.rows) - 1u;                                    \
-                const unsigned long long wbits = (unsigned long long)bits << (TAG.base & 32);               \
-                const int wi = TAG.base >> 6;                                                               \
-                wm0 |= wi == 0 ? wbits : 0ull; wm1 |= wi == 1 ? wbits : 0ull;                               \
-                wm2 |= wi == 2 ? wbits : 0ull; wm3 |= wi == 3 ? wbits : 0ull;                               \
-            }                                                                                               \
             if (TAG.last) {                                                                                 \
-                if (ABL == 10) {     /* 32 bytes per candidate passage into the (slot-indexed) row-mask buffer */ \
-                    if (lane == 0 && TAG.j >= 0) {                                                          \
-                        unsigned long long* o = rowmask + ((size_t)b * cand_cap + TAG.j) * 4;               \
-                        o[0] = wm0; o[1] = wm1; o[2] = wm2; o[3] = wm3;                                     \
-                    }                                                                                       \
-                    wm0 = wm1 = wm2 = wm3 = 0;                                                              \
-                }                                                                                           \
                 CLB_PASSAGE_END(mx, TAG.j, TAG.last);                                                       \
                 mx = kNegInf;                                                                               \
             }                                                                                               \
@@ -1620,67 +1522,23 @@ static __global__ __launch_bounds__(kApproxThreads, CLB_APPROX_MINOCC) void scor
         uint32_t cv0, cv1, cv2, cw0, cw1, cw2;       // cv: as loaded (stage A); cw: the copy stage C dequantises
         uint16_t pm0 = 0, pm1 = 0, pm2 = 0;
         StepTag t0, t1, t2;
-        f32x16 acc0, acc1;
+        f32x16 acc0;
         CLB_STAGE_A(rb0, cv0, pm0, t0);
         CLB_STAGE_A(rb1, cv1, pm1, t1);
         CLB_STAGE_G(cv0, xa0, xb0, 0); cw0 = cv0;
-        if (!PIPE) {
-            while (t0.j >= 0) {
-                CLB_STAGE_A(rb2, cv2, pm2, t2);
-                CLB_STAGE_G(cv1, xa1, xb1, 1); cw1 = cv1;
-                CLB_STAGE_CM(rb0, cw0, xa0, xb0, 0, acc0, 0);
-                CLB_STAGE_E(acc0, 0, pm0, t0);
-                CLB_STAGE_A(rb0, cv0, pm0, t0);
-                CLB_STAGE_G(cv2, xa2, xb2, 2); cw2 = cv2;
-                CLB_STAGE_CM(rb1, cw1, xa1, xb1, 1, acc0, 0);
-                CLB_STAGE_E(acc0, 0, pm1, t1);
-                CLB_STAGE_A(rb1, cv1, pm1, t1);
-                CLB_STAGE_G(cv0, xa0, xb0, 0); cw0 = cv0;
-                CLB_STAGE_CM(rb2, cw2, xa2, xb2, 2, acc0, 0);
-                CLB_STAGE_E(acc0, 0, pm2, t2);
-            }
-        } else {
-            // tp / pmp: tag and stored maximum of the step whose epilogue is pending; the dummy "previous step" of a
-            // chunk's first iteration ends a passage nobody stores (j < 0), which also resets mx and the row mask
-            StepTag tp; tp.j = -1; tp.rows = kStepRows; tp.last = 1; tp.base = 0;
-            tp.g = 0; tp.jh = -1; tp.rowsh = kStepRows; tp.baseh = 0;
-            uint16_t pmp = 0;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
-            for (;;) {
-                if (t0.j < 0) { CLB_STAGE_E(acc1, 1, pmp, tp); break; }
-                CLB_STAGE_A(rb2, cv2, pm2, t2);
-                CLB_STAGE_G(cv1, xa1, xb1, 1); cw1 = cv1;
-                CLB_STAGE_CM(rb0, cw0, xa0, xb0, 0, acc0, 0);
-                CLB_STAGE_E(acc1, 1, pmp, tp);
-                tp = t0; pmp = pm0;
-                CLB_STAGE_A(rb0, cv0, pm0, t0);
-                CLB_STAGE_G(cv2, xa2, xb2, 2); cw2 = cv2;
-                CLB_STAGE_CM(rb1, cw1, xa1, xb1, 1, acc1, 1);
-                CLB_STAGE_E(acc0, 0, pmp, tp);
-                tp = t1; pmp = pm1;
-                CLB_STAGE_A(rb1, cv1, pm1, t1);
-                CLB_STAGE_G(cv0, xa0, xb0, 0); cw0 = cv0;
-                CLB_STAGE_CM(rb2, cw2, xa2, xb2, 2, acc0, 0);
-                CLB_STAGE_E(acc1, 1, pmp, tp);
-                tp = t2; pmp = pm2;
-                if (t0.j < 0) { CLB_STAGE_E(acc0, 0, pmp, tp); break; }
-                CLB_STAGE_A(rb2, cv2, pm2, t2);
-                CLB_STAGE_G(cv1, xa1, xb1, 1); cw1 = cv1;
-                CLB_STAGE_CM(rb0, cw0, xa0, xb0, 0, acc1, 1);
-                CLB_STAGE_E(acc0, 0, pmp, tp);
-                tp = t0; pmp = pm0;
-                CLB_STAGE_A(rb0, cv0, pm0, t0);
-                CLB_STAGE_G(cv2, xa2, xb2, 2); cw2 = cv2;
-                CLB_STAGE_CM(rb1, cw1, xa1, xb1, 1, acc0, 0);
-                CLB_STAGE_E(acc1, 1, pmp, tp);
-                tp = t1; pmp = pm1;
-                CLB_STAGE_A(rb1, cv1, pm1, t1);
-                CLB_STAGE_G(cv0, xa0, xb0, 0); cw0 = cv0;
-                CLB_STAGE_CM(rb2, cw2, xa2, xb2, 2, acc1, 1);
-                CLB_STAGE_E(acc0, 0, pmp, tp);
-                tp = t2; pmp = pm2;
-            }
+        while (t0.j >= 0) {
+            CLB_STAGE_A(rb2, cv2, pm2, t2);
+            CLB_STAGE_G(cv1, xa1, xb1, 1); cw1 = cv1;
+            CLB_STAGE_CM(rb0, cw0, xa0, xb0, 0, acc0);
+            CLB_STAGE_E(acc0, pm0, t0);
+            CLB_STAGE_A(rb0, cv0, pm0, t0);
+            CLB_STAGE_G(cv2, xa2, xb2, 2); cw2 = cv2;
+            CLB_STAGE_CM(rb1, cw1, xa1, xb1, 1, acc0);
+            CLB_STAGE_E(acc0, pm1, t1);
+            CLB_STAGE_A(rb1, cv1, pm1, t1);
+            CLB_STAGE_G(cv0, xa0, xb0, 0); cw0 = cv0;
+            CLB_STAGE_CM(rb2, cw2, xa2, xb2, 2, acc0);
+            CLB_STAGE_E(acc0, pm2, t2);
         }
         }   // chunk of 64 passages
 #undef CLB_STAGE_A
@@ -1822,7 +1680,7 @@ static __global__ __launch_bounds__(1024) void select_margin_kernel(const float*
                                                                    const float* __restrict__ tau_in = nullptr,
                                                                    int coarse_tau = 0,
                                                                    const float4* __restrict__ tscale = nullptr,
-                                                                   int cell8 = 0, int dbg_stop = 0 /* tuning builds: leave after phase N */) {
+                                                                   int cell8 = 0) {
     __shared__ __attribute__((aligned(16))) int hist[256];
     __shared__ float s_aux[4];
     __shared__ int sh_scan[16];
@@ -1851,16 +1709,6 @@ static __global__ __launch_bounds__(1024) void select_margin_kernel(const float*
     float thr = kNegInf, tau_f = kNegInf, eps = 0.f;
     const bool unsafe = qb.unsafe;
     if (tid == 0) eps_pair[b] = unsafe ? __builtin_inff() : kEpsSafety * qb.eps_t;
-    if (kAblations && dbg_stop == 1) return;
-    if (kAblations && dbg_stop == 2) {     // (the keys must be used, or the loads go away)
-        uint32_t x = 0;
-        if (cached) {
-#pragma unroll
-            for (int c = 0; c < kSelCache; ++c) x ^= ckey[c];
-        }
-        if (x == 0x12345u) nlist[b] = 0;
-        return;
-    }
 #define CLB_SEL_FOR_EACH(...)                                                                   \
     if (cached) {                                                                               \
         _Pragma("unroll") for (int c = 0; c < kSelCache; ++c) {                                 \
@@ -1896,7 +1744,6 @@ static __global__ __launch_bounds__(1024) void select_margin_kernel(const float*
         tau_f = f32_from_order_key(s_prefix);
         thr = tau_f - 2.f * eps;
     }
-    if (kAblations && dbg_stop == 3) { if (tid == 0 && thr == 12345.f) nlist[b] = 0; return; }
     // ordered compaction of the slots with approx >= thr (all of them when n <= k): one block-wide scan of the
     // per-thread counts places every chunk in order
     if (!cached) {

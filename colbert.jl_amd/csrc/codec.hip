@@ -42,8 +42,7 @@ template <int MODE>
 int nearest_centroids(hipStream_t st, const float* dC, const float* dc2, int dim, int K, const float* dX, int64_t n,
                       uint32_t* dOut, NearestScratch* scratch = nullptr) {
     if (n == 0) return CLB_OK;
-    const bool force_fp32 = CLB_KNOB("CLB_DEBUG_NEAREST_FP32", 0) != 0;
-    if (dim == kDim && K >= 32 && scratch && !force_fp32) {
+    if (dim == kDim && K >= 32 && scratch) {
         NearestScratch& w = *scratch;
         const size_t cel = (size_t)K * kDim;
         const int kpad = (K + 31) / 32 * 32 + 32;
@@ -53,7 +52,7 @@ int nearest_centroids(hipStream_t st, const float* dC, const float* dc2, int dim
         CLB_HIP(hipMemsetAsync(w.cn.p, 0, 2 * sizeof(unsigned int), st));
         hipLaunchKernelGGL(max_row_norm_kernel, dim3(std::max(1, std::min(1024, K / 256))), dim3(256), 0, st, dC, K,
                            w.cn.as<unsigned int>());
-        // One fp16 product per fp32 product (nearest_top_f16_kernel) unless a centroid component is outside the fp16 range
+        // One fp16 product per fp32 product (nearest_top_f16_dma_kernel) unless a centroid component is outside the fp16 range
         // (the measured max ||c - fp16(c)|| comes back infinite: 4 bytes and one wait per call) or a comparison run asks
         // for the three-product bf16 split, COLBERT_NEAREST_PRODUCTS=3
         const char* products = getenv("COLBERT_NEAREST_PRODUCTS");        // read per call: tests and comparison runs switch it
@@ -68,14 +67,10 @@ int nearest_centroids(hipStream_t st, const float* dC, const float* dc2, int dim
             x1 = dc > 0.f && std::isfinite(dc);
             if (!x1) CLB_HIP(hipMemsetAsync(w.cn.as<unsigned int>() + 1, 0, sizeof(unsigned int), st));
         }
-        const char* staging = CLB_ENV("COLBERT_NEAREST_STAGING");         // "registers": the first form of the kernel (tuning builds)
-        const bool dma = x1 && !(staging && strcmp(staging, "registers") == 0);
-        if (dma) {          // the tiled table of nearest_top_f16_dma_kernel: whole tiles, the last one padded with copies of row K - 1
+        if (x1) {           // the tiled table of nearest_top_f16_dma_kernel: whole tiles, the last one padded with copies of row K - 1
             const int64_t n_chunks = (int64_t)((K + 31) / 32) * 512;
             CLB_TRY(w.hi.ensure(16 * (size_t)n_chunks));
             hipLaunchKernelGGL(to_f16_tiled_kernel, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, st, dC, K, w.hi.as<uint16_t>(), n_chunks);
-        } else if (x1) {
-            hipLaunchKernelGGL(to_f16_kernel, dim3((unsigned)((cel + 255) / 256)), dim3(256), 0, st, dC, w.hi.as<uint16_t>(), (int64_t)cel);
         } else {
             CLB_TRY(w.lo.ensure(sizeof(uint16_t) * cel));
             hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)((cel + 255) / 256)), dim3(256), 0, st, dC,
@@ -97,20 +92,12 @@ int nearest_centroids(hipStream_t st, const float* dC, const float* dc2, int dim
             const dim3 grid(1, (unsigned)((groups32 + kMqQueries - 1) / kMqQueries));
             constexpr int kNq = 4;                                      // groups of 32 points per wave of the single-product kernel
             const dim3 grid1((unsigned)((groups32 + 4 * kNq - 1) / (4 * kNq)));
-if (dma && MODE == 1)
+            if (x1 && MODE == 1)
                 hipLaunchKernelGGL((nearest_top_f16_dma_kernel<true>), grid1, dim3(256), 3 * 8192, st, w.hi.as<uint16_t>(),
                                    dX + (size_t)p0 * kDim, w.partial.as<ValIdx>(), K, groups32, n_tiles, w.bias.as<float>(), m);
-            else if (dma)
+            else if (x1)
                 hipLaunchKernelGGL((nearest_top_f16_dma_kernel<false>), grid1, dim3(256), 3 * 8192, st, w.hi.as<uint16_t>(),
                                    dX + (size_t)p0 * kDim, w.partial.as<ValIdx>(), K, groups32, n_tiles, (const float*)nullptr, m);
-#ifdef CLB_ABLATIONS
-            else if (x1 && MODE == 1)
-                hipLaunchKernelGGL((nearest_top_f16_kernel<true, kNq>), grid1, dim3(256), lds / 2, st, w.hi.as<uint16_t>(),
-                                   dX + (size_t)p0 * kDim, w.partial.as<ValIdx>(), K, groups32, n_tiles, w.bias.as<float>(), m);
-            else if (x1)
-                hipLaunchKernelGGL((nearest_top_f16_kernel<false, kNq>), grid1, dim3(256), lds / 2, st, w.hi.as<uint16_t>(),
-                                   dX + (size_t)p0 * kDim, w.partial.as<ValIdx>(), K, groups32, n_tiles, (const float*)nullptr, m);
-#endif
             else if (MODE == 1)
                 hipLaunchKernelGGL((centroid_top_bf16x3_mq_kernel<false, true>), grid, dim3(256), lds, st,
                                    w.hi.as<uint16_t>(), w.lo.as<uint16_t>(), dX + (size_t)p0 * kDim,
@@ -131,7 +118,7 @@ if (dma && MODE == 1)
             // points -- so more than a handful go through the three-product lists first (their margin is five times tighter) and
             // only what THOSE cannot decide is scanned.  One 4-byte read-back per chunk of up to 4 M points.
             const int slices = std::max(1, std::min(n_tiles / 8, 128));
-            unsigned int undecided = 0, undecided2 = 0;
+            unsigned int undecided = 0;
             if (x1) {
                 CLB_HIP(hipMemcpyAsync(&undecided, w.ovf_count.p, sizeof undecided, hipMemcpyDeviceToHost, st));
                 CLB_HIP(hipStreamSynchronize(st));
@@ -179,10 +166,6 @@ if (dma && MODE == 1)
                                    w.ovf2_count.as<unsigned int>(), w.ovf2_keys.as<unsigned long long>(), w.codes_c.as<uint32_t>());
                 hipLaunchKernelGGL(scatter_codes_kernel, dim3(blocks_for(mc)), dim3(256), 0, st, w.ovf_list.as<uint32_t>(), mc,
                                    w.codes_c.as<uint32_t>(), dOut + p0);
-                if (CLB_ENV("COLBERT_DEBUG_NEAREST")) {
-                    CLB_HIP(hipMemcpyAsync(&undecided2, w.ovf2_count.p, sizeof undecided2, hipMemcpyDeviceToHost, st));
-                    CLB_HIP(hipStreamSynchronize(st));
-                }
             } else {
                 // on the fp32 MFMA, all K centroids per point, the centroid tiles dealt to `slices` work-groups per pair of 32-point tiles
                 const int pairs = (int)std::max<int64_t>(1, std::min<int64_t>(2048 / slices, (m + 63) / 64));
@@ -191,14 +174,6 @@ if (dma && MODE == 1)
                                    w.ovf_list.as<uint32_t>(), w.ovf_count.as<unsigned int>(), w.ovf_keys.as<unsigned long long>());
                 hipLaunchKernelGGL(nearest_list_finalize_kernel, dim3(64), dim3(256), 0, st, w.ovf_list.as<uint32_t>(),
                                    w.ovf_count.as<unsigned int>(), w.ovf_keys.as<unsigned long long>(), dOut + p0);
-            }
-            if (CLB_ENV("COLBERT_DEBUG_NEAREST")) {      // how many points the lists left undecided (a wait per chunk: debugging only)
-                unsigned int cnt = 0;
-                CLB_HIP(hipMemcpyAsync(&cnt, w.ovf_count.p, sizeof cnt, hipMemcpyDeviceToHost, st));
-                CLB_HIP(hipStreamSynchronize(st));
-                fprintf(stderr, "nearest_centroids<%d>: %lld points, K = %d, %s lists, %u undecided, %u of them also by the bf16 x3 lists "
-                        "(scanned against all centroids: %u)\n", MODE, (long long)m, K, x1 ? "fp16 x1" : "bf16 x3", cnt,
-                        x1 && cnt > 64 ? undecided2 : 0u, x1 && cnt > 64 ? undecided2 : cnt);
             }
         }
     } else if (dim == kDim) {

@@ -484,107 +484,20 @@ static __global__ __launch_bounds__(256) void epilogue_query_fused_kernel(const 
 // within a PROVEN margin of the best listed one (the winner itself is re-scored in canonical fp32), and the margin can
 // carry the measured conversion errors of both operands (centroid_product_bound in approx_kernels.hpp):
 // |x.c - x'.c'| <= ||x - x'|| ||c'|| + ||x|| ||c - c'||.  A third of the MFMAs, half the centroid bytes, and -- the point
-// operands needing half the registers -- NQ = 4 groups of 32 points per wave: 512 points share each staged 32-centroid tile
+// operands needing half the registers -- four groups of 32 points per wave: 512 points share each staged 32-centroid tile
 // (256 before), and one A fragment read from LDS feeds four MFMAs.
-// Layout and roles as in the mq kernel: A = 32 centroids x 16 dims from LDS (rows of 272 B, dims 64h + 8s + j in k-step s),
+// Layout and roles as in the mq kernel: A = 32 centroids x 16 dims from LDS (dims 64h + 8s + j in k-step s),
 // B = the wave's points in registers, lane (i, h) = (point i of the group, dim half h); accumulator lane (i, h) register r =
 // centroid c0 + (r & 3) + 8 (r >> 2) + 4 h.  bias[c] (= -||c||^2 / 2 for the k-means distance) is where the fp32 sums start.
-// partial: [group of 32 points][32 points][2 halves][kTopPartial].  grid = ceil(groups32 / (4 NQ)), block = 256,
-// LDS = 2 buffers x 32 rows x 272 B.
-// -------------------------------------------------------------------------------------------------------------
-template <bool BIAS, int NQ, int WPE = 2>
-static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void nearest_top_f16_kernel(
-    const uint16_t* __restrict__ C16, const float* __restrict__ X, ValIdx* __restrict__ partial, int K, int groups32,
-    int n_tiles, const float* __restrict__ bias, int64_t n_rows) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds16[];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int i = lane & 31, h = lane >> 5;
-    const int bq0 = (int)blockIdx.x * (4 * NQ) + wave * NQ;      // this wave's groups: bq0 .. bq0 + NQ - 1
-    u32x4 xq[NQ][8];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const int b = bq0 + q < groups32 ? bq0 + q : groups32 - 1;   // past the input: a duplicate whose lists are dropped
-        int64_t row = (int64_t)b * 32 + i;
-        row = row < n_rows ? row : n_rows - 1;
-        const float* xrow = X + (size_t)row * kDim + 64 * h;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const float4 a = *reinterpret_cast<const float4*>(xrow + 8 * s);
-            const float4 c = *reinterpret_cast<const float4*>(xrow + 8 * s + 4);
-            xq[q][s] = u32x4{pack_f16(a.x, a.y), pack_f16(a.z, a.w), pack_f16(c.x, c.y), pack_f16(c.z, c.w)};
-        }
-    }
-    float bv[NQ][kTopPartial];
-    int bi[NQ][kTopPartial];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-#pragma unroll
-        for (int p = 0; p < kTopPartial; ++p) { bv[q][p] = kNegInf; bi[q][p] = 0x7fffffff; }
-    // loader: thread tid moves the 16-byte chunk (tid & 15) of rows (tid >> 4) and 16 + (tid >> 4)
-    const int prow = threadIdx.x >> 4, pchunk = threadIdx.x & 15;
-    auto tile_rows = [&](int tl, u32x4& r0, u32x4& r1) {
-        int c0 = tl * 32 + prow, c1 = c0 + 16;
-        c0 = c0 < K ? c0 : K - 1;                      // rows past K are copies of row K - 1 (group_max16 masks them)
-        c1 = c1 < K ? c1 : K - 1;
-        r0 = *reinterpret_cast<const u32x4*>(C16 + (size_t)c0 * kDim + 8 * pchunk);
-        r1 = *reinterpret_cast<const u32x4*>(C16 + (size_t)c1 * kDim + 8 * pchunk);
-    };
-    u32x4 p0, p1;
-    tile_rows(0, p0, p1);
-    // the tile's 32 bias values come through the scalar cache one tile ahead (the address is uniform): as vector loads next to
-    // their use they exposed an L2 round trip per tile
-    float bcur[32];
-#pragma unroll
-    for (int r = 0; r < 32; ++r) bcur[r] = BIAS ? bias[r] : 0.f;
-    int buf = 0;
-    for (int tile = 0; tile < n_tiles; ++tile) {
-        unsigned char* my = lds16 + buf * (32 * kRowBytes16);
-        *reinterpret_cast<u32x4*>(my + prow * kRowBytes16 + 16 * pchunk) = p0;
-        *reinterpret_cast<u32x4*>(my + (16 + prow) * kRowBytes16 + 16 * pchunk) = p1;
-        tile_rows(tile + 1 < n_tiles ? tile + 1 : n_tiles - 1, p0, p1);
-        // one barrier per tile: the buffer written now was last read two iterations ago, before the previous barrier
-        __syncthreads();
-        const int c0 = tile * 32;
-        // the accumulators START at the bias (this lane's rows c0 + (r & 3) + 8 (r >> 2) + 4 h: four aligned float4 of the
-        // padded bias row) -- the first MFMA of every group reads it as its C operand: no add per score afterwards
-        f32x16 init;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) init[r] = h ? bcur[(r & 3) + 8 * (r >> 2) + 4] : bcur[(r & 3) + 8 * (r >> 2)];
-        if (BIAS) {
-            const float* bn = bias + (tile + 1 < n_tiles ? c0 + 32 : c0);      // (the bias row is padded by 32 entries)
-#pragma unroll
-            for (int r = 0; r < 32; ++r) bcur[r] = bn[r];
-        }
-        f32x16 acc[NQ];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const f16x8 a = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(my + i * kRowBytes16 + 16 * (8 * h + s)));
-#pragma unroll
-            for (int q = 0; q < NQ; ++q)
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, __builtin_bit_cast(f16x8, xq[q][s]), s == 0 ? init : acc[q], 0, 0, 0);
-        }
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) topn_insert_lazy<kTopPartial>(bv[q], bi[q], group_max16(acc[q], c0, h, K), 2 * tile + h);
-        buf ^= 1;
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        if (bq0 + q >= groups32) continue;
-        ValIdx* out = partial + (((size_t)(bq0 + q) * 32 + i) * 2 + h) * kTopPartial;
-#pragma unroll
-        for (int p = 0; p < kTopPartial; ++p) out[p] = ValIdx{bv[q][p], bi[q][p]};
-    }
-}
-
-// -------------------------------------------------------------------------------------------------------------
-// The same lists with the centroid tiles moved by LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write) from a
+// partial: [group of 32 points][32 points][2 halves][kTopPartial].
+// The centroid tiles are moved by LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write) from a
 // TILED fp16 table -- to_f16_tiled_kernel writes [tile of 32 centroids][16-byte chunk c of the row: dims 8c .. 8c+7][row][8 halfs],
 // 8 KB per tile, rows past K = copies of row K - 1 -- so that a tile is one contiguous block in memory AND lands in LDS
 // chunk-major: lane (i, h) reads its A fragment of k-step s at (8h + s) * 512 + 16 i, 32 lanes x 16 contiguous bytes per chunk
 // (no bank conflicts, no padding, one base address + immediate offsets).  Ring of three tile buffers, one barrier per tile as
 // in gemm_planes2_kernel (encoder_kernels.hpp): tile k waits for its own two DMAs (vmcnt(2): only those of tile k + 1 are
 // younger), meets the barrier -- every wave has left buffer (k - 1) % 3 -- and refills that buffer with tile k + 2.
-// The eight registers the staging took hold two more A fragments: four are in flight, re-filled three k-steps (12 MFMAs) ahead,
+// The eight registers a register-staged tile would take hold two more A fragments: four are in flight, re-filled three k-steps (12 MFMAs) ahead,
 // and the first four of tile k + 1 are requested BEFORE the list epilogue of tile k, which then runs under their latency.
 // grid = ceil(groups32 / 16), block = 256, LDS = 3 x 8 KB.
 // -------------------------------------------------------------------------------------------------------------

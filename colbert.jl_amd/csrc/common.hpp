@@ -108,27 +108,6 @@ inline void allow_dynamic_lds(const void* kernel, int bytes) {
     (void)hipGetLastError();
 }
 
-// Launch-geometry knobs used while tuning: the shipped library compiles them to their defaults; a build with
-// -DCLB_ABLATIONS reads CLB_DEBUG_* from the environment instead (make ABLATIONS=1).
-// Comparison switches read from the environment (COLBERT_ENC_PLAN, COLBERT_PASS1_GATHER, ...): tuning builds only.  The product
-// library answers "not set" without looking, and the kernels only those switches select are not compiled into it.
-#ifdef CLB_ABLATIONS
-#define CLB_ENV(NAME) getenv(NAME)
-constexpr bool kAblations = true;
-#else
-#define CLB_ENV(NAME) (static_cast<const char*>(nullptr))
-constexpr bool kAblations = false;
-#endif
-#ifdef CLB_ABLATIONS
-inline int tuning_knob(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-#define CLB_KNOB(NAME, DFLT) (clb::tuning_knob(NAME, DFLT))      // re-read on every call: a sweep can change it
-#else
-#define CLB_KNOB(NAME, DFLT) (DFLT)
-#endif
-
 // ---- device helpers ------------------------------------------------------------------------------
 // float -> unsigned key with the same ordering (larger float <=> larger key); -0.0 < +0.0 here, which
 // only matters for ties between zeros and is applied identically by the oracle-facing comparison

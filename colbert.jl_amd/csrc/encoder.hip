@@ -13,12 +13,6 @@
 
 using namespace clb;
 
-#ifdef CLB_ABLATIONS
-namespace clb { bool launch_planes2_wide(hipStream_t st, int ln_mode, const GemmPArgs& g, unsigned grid); }   // encoder_big.hip (tuning builds)
-#else
-namespace clb { inline bool launch_planes2_wide(hipStream_t, int, const GemmPArgs&, unsigned) { return false; } }
-#endif
-
 struct clb_encoder {
     int device = 0;
     int64_t vocab = 0, H = 0, layers = 0, heads = 0, I = 0, max_pos = 0, type_vocab = 0, dim = 0;
@@ -28,9 +22,8 @@ struct clb_encoder {
     int attention_mode = 0;     // 0 = fused: the fp16-plane kernel behind the f16x3 Linear layers (attention_f16_kernel), else
                                 // fp32 MFMA (register-resident up to 64 keys, online softmax beyond); 1 = fp32 register-resident
                                 // for every length, 2 = the three-kernel path (comparison; always taken for head sizes != 64),
-                                // 3 = fused on the fp32 MFMA whatever the GEMM mode (comparison); 5 = as 0 with the K / V tiles of a
-                                // (sequence, head) staged once in LDS for all its query blocks (round 5: bit-identical to 0 and
-                                // measured SLOWER -- 1.42 -> 1.92 ms per 64 x 300 batch --, kept for comparison)
+                                // 3 = fused on the fp32 MFMA whatever the GEMM mode (comparison).  (5, the K / V tiles of a
+                                // (sequence, head) staged once in LDS, was bit-identical to 0 and slower: retired)
     int gemm_mode = 3;          // 0 = fp32 MFMA GEMMs, 1 = bf16x3, 2 = bf16x6, 3 = f16x3 (MFMA products of split operands)
     // offsets (in floats) into the blob
     int64_t o_word = 0, o_pos = 0, o_type = 0, o_eg = 0, o_eb = 0, o_layer0 = 0, layer_stride = 0, o_lin_w = 0, o_lin_b = 0;
@@ -54,7 +47,7 @@ struct clb_encoder {
     bool fold_ready = false;
     int ln_fold = -1;                   // -1 (default): whenever the batch is long enough to run without split-K (14.34 -> 13.93 ms per
                                         // 64 x 300 passage batch, profiles/r05_experiments.md); 0: never; 1: always (tests)
-    bool planes = false;        // the Linear layers read pre-split bf16 planes (gemm_planes_kernel); COLBERT_ENCODER_PLANES=0: off
+    bool planes = false;        // the Linear layers read pre-split bf16 planes (gemm_planes2_kernel)
     // workspace
     DevBuf ids, mask, x, qkv, scores, ctx, hbuf, tmp, out, err, qmask, qlens, part, pkeep, prank, scan_tmp;
     DevBuf xp, ctxp, tmpp, hbp; // bf16 planes of the activations the Linear layers read (written by their producers)
@@ -146,9 +139,7 @@ void gemm(hipStream_t st, const float* A, const float* B, float* C, const float*
 // activations (T x K, fp32) x Linear weight (N x K, fp32) on the split-bf16 kernels (both operands are split into
 // bf16 planes while they are staged).  Falls back to the fp32 MFMA GEMM for shapes the kernel does not take.
 struct LnArgs { const float* gamma; const float* beta; float eps; };
-// small tiles (query batches): two LDS tile buffers, one barrier per step (COLBERT_ENCODER_DOUBLE_BUFFER=0: the
-// single-buffer loop, for comparison)
-static const bool g_double_buffer = [] { const char* v = CLB_ENV("COLBERT_ENCODER_DOUBLE_BUFFER"); return !v || atoi(v) != 0; }();
+// small tiles (query batches): two LDS tile buffers, one barrier per step
 
 // ln != null: the caller applies a LayerNorm to the output next; returns true when it was applied here (split-K path:
 // fused into the reduction pass)
@@ -162,14 +153,10 @@ bool linear_split(hipStream_t st, Gemm3Args g, float* part, const LnArgs* ln) {
     if (wgs(128, 128) >= 384) {
         hipLaunchKernelGGL((gemm_bf16split_kernel<2, 2, 2, 2, NS>), dim3((N + 127) / 128, (M + 127) / 128, 1), dim3(256), lds(128, 128), st, g);
     } else if (wgs(64, 128) >= 384 && N >= 128) {
-        if (g_double_buffer) {
-            // 72 KB of dynamic LDS: above the 64-KB default limit of a launch
-            allow_dynamic_lds(reinterpret_cast<const void*>(gemm_bf16split_kernel<2, 2, 1, 2, NS, true>),
-                              2 * NS * (64 + 128) * 64);
-            hipLaunchKernelGGL((gemm_bf16split_kernel<2, 2, 1, 2, NS, true>), dim3((N + 127) / 128, (M + 63) / 64, 1), dim3(256), 2 * lds(64, 128), st, g);
-        }
-        else
-            hipLaunchKernelGGL((gemm_bf16split_kernel<2, 2, 1, 2, NS>), dim3((N + 127) / 128, (M + 63) / 64, 1), dim3(256), lds(64, 128), st, g);
+        // 72 KB of dynamic LDS: above the 64-KB default limit of a launch
+        allow_dynamic_lds(reinterpret_cast<const void*>(gemm_bf16split_kernel<2, 2, 1, 2, NS, true>),
+                          2 * NS * (64 + 128) * 64);
+        hipLaunchKernelGGL((gemm_bf16split_kernel<2, 2, 1, 2, NS, true>), dim3((N + 127) / 128, (M + 63) / 64, 1), dim3(256), 2 * lds(64, 128), st, g);
     } else {
         int ks = 1;
         if (part) {
@@ -179,10 +166,7 @@ bool linear_split(hipStream_t st, Gemm3Args g, float* part, const LnArgs* ln) {
         }
         float* C = g.C;
         if (ks > 1) { g.ksplit = ks; g.C = part; }
-        if (g_double_buffer)
-            hipLaunchKernelGGL((gemm_bf16split_kernel<2, 2, 1, 1, NS, true>), dim3((N + 63) / 64, (M + 63) / 64, ks), dim3(256), 2 * lds(64, 64), st, g);
-        else
-            hipLaunchKernelGGL((gemm_bf16split_kernel<2, 2, 1, 1, NS>), dim3((N + 63) / 64, (M + 63) / 64, ks), dim3(256), lds(64, 64), st, g);
+        hipLaunchKernelGGL((gemm_bf16split_kernel<2, 2, 1, 1, NS, true>), dim3((N + 63) / 64, (M + 63) / 64, ks), dim3(256), 2 * lds(64, 64), st, g);
         if (ks > 1) {
             if (ln && N <= 1024) {
                 if (N <= 768)
@@ -200,55 +184,13 @@ bool linear_split(hipStream_t st, Gemm3Args g, float* part, const LnArgs* ln) {
     return false;
 }
 
-// ---- Linear layers on pre-split bf16 planes (gemm_planes_kernel) ----------------------------------------------------
+// ---- Linear layers on pre-split bf16 planes (gemm_planes2_kernel) ---------------------------------------------------
 struct PlanCfg { int bm, bn, stages, ks; };
 struct AttOut { uint16_t* qk; int64_t qk_plane; uint16_t* vt; int64_t vt_plane; int L, H, heads; const int32_t* seq; const int32_t* pos; };   // EPI_QKV_ATT targets
 // a packed batch: N sequences back to back without padding rows (device arrays: position and sequence of every row, row offsets)
 // `pos`: index of the position embedding; `rank` (null = pos): the row's rank inside its sequence, which is what the attention
 // kernel and the key-blocked V buffer go by -- they differ when a mask has holes (host path), not for prefix masks
 struct Packed { const int32_t* pos; const int32_t* seq; const int32_t* cu; int64_t rows; const int32_t* rank = nullptr; };
-enum LinRole { LR_QKV = 0, LR_ATTN_OUT, LR_FFN_IN, LR_FFN_OUT, LR_PROJ, LR_COUNT };
-// COLBERT_ENC_PLAN="qkv=64x128x3x1,attn_out=64x64x3x4,...": tile / ring depth / K split per Linear role (tuning runs)
-static const PlanCfg* plan_override(int role) {
-    static PlanCfg cfg[LR_COUNT];
-    static bool have[LR_COUNT] = {false, false, false, false, false};
-    static const bool parsed = [] {
-        const char* v = CLB_ENV("COLBERT_ENC_PLAN");
-        if (!v) return true;
-        static const char* names[LR_COUNT] = {"qkv", "attn_out", "ffn_in", "ffn_out", "proj"};
-        std::string sv(v);
-        size_t pos = 0;
-        while (pos < sv.size()) {
-            size_t end = sv.find(',', pos);
-            if (end == std::string::npos) end = sv.size();
-            const std::string item = sv.substr(pos, end - pos);
-            const size_t eq = item.find('=');
-            if (eq != std::string::npos)
-                for (int r = 0; r < LR_COUNT; ++r)
-                    if (item.substr(0, eq) == names[r]) {
-                        PlanCfg c{0, 0, 0, 0};
-                        if (sscanf(item.c_str() + eq + 1, "%dx%dx%dx%d", &c.bm, &c.bn, &c.stages, &c.ks) == 4) { cfg[r] = c; have[r] = true; }
-                    }
-            pos = end + 1;
-        }
-        return true;
-    }();
-    (void)parsed;
-    return have[role] ? &cfg[role] : nullptr;
-}
-
-// COLBERT_ENC_GEMM_FORM=1: the first form of the plane GEMM (element-wise epilogue, LDS reads not pipelined) -- comparison runs
-static bool planes_first_form() {
-    static const bool v = [] { const char* e = CLB_ENV("COLBERT_ENC_GEMM_FORM"); return e && atoi(e) == 1; }();
-    return kAblations && v;
-}
-
-// COLBERT_ENC_ATT_QB=1: one query block per wave in attention_f16_kernel whatever the length -- comparison runs
-static bool att_qb2() {
-    static const bool v = [] { const char* e = CLB_ENV("COLBERT_ENC_ATT_QB"); return !(e && atoi(e) == 1); }();
-    return v;
-}
-
 // what a Linear needs to fold a LayerNorm around itself (GemmPArgs' ln_* fields)
 struct LnFold {
     const float* ln_in = nullptr; int parts = 0, width = 0; float eps = 0.f;     // statistics of A's rows (u set) or of R's rows (r_gamma set)
@@ -259,22 +201,13 @@ struct LnFold {
 
 // the LN instantiations: 1 = consumer (64 x 64 for the projection's 128 columns, 128 x 128 behind GELU, 128 x 256 in front of the
 // attention), 2 = producer (the big plain tiles)
-// COLBERT_ENC_WIDE_WAVES=1: the 256 x 256 tile as four waves of 128 x 128 (encoder_big.hip: a third fewer LDS reads per MFMA,
-// accumulators in AGPRs) instead of eight of 64 x 128 -- bit-identical and SLOWER (a 64 x 300 batch 16.6 against 13.9 ms: with
-// one wave per SIMD nothing covers the barrier and the DMA wait of every step); kept for comparison runs (tools/r5_wide_waves.py)
-static bool wide_waves() {
-    static const bool v = [] { const char* e = CLB_ENV("COLBERT_ENC_WIDE_WAVES"); return e && atoi(e) == 1; }();
-    return kAblations && v;
-}
-
 bool launch_planes_ln(hipStream_t st, const PlanCfg& c, const GemmPArgs& g) {
     const dim3 grid((unsigned)gemm_planes_grid(g.M, g.N, c.bm, c.bn, c.ks));
     const size_t lds = (size_t)c.stages * 2 * (c.bm + c.bn) * 64;
     const int mode = g.ln_u ? 1 : 2;
-    if (c.bm == 256 && c.bn == 256 && c.stages == 2 && wide_waves()) return launch_planes2_wide(st, mode, g, grid.x);
 #define CLB_GPL_CASE(MODE_, BM_, BN_, ST_, WGM_, WGN_, WM_, WN_)                                                      \
     if (mode == MODE_ && c.bm == BM_ && c.bn == BN_ && c.stages == ST_) {                                             \
-        auto kern = gemm_planes2_kernel<WGM_, WGN_, WM_, WN_, 2, ST_, 0, true, MODE_>;                                \
+        auto kern = gemm_planes2_kernel<WGM_, WGN_, WM_, WN_, 2, ST_, true, MODE_>;                                   \
         if (lds > 64 * 1024) allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds);                        \
         hipLaunchKernelGGL(kern, grid, dim3(64 * WGM_ * WGN_), lds, st, g);                                           \
         return true;                                                                                                  \
@@ -285,23 +218,14 @@ bool launch_planes_ln(hipStream_t st, const PlanCfg& c, const GemmPArgs& g) {
     return false;
 }
 
-// (the first form of the plane GEMM, gemm_planes_kernel, is a comparison kernel: tuning builds; it also takes N % 4 != 0, which
-// no Linear of the encoder has -- linear_planes falls back to the fp32 GEMM for such a shape)
-#ifdef CLB_ABLATIONS
-#define CLB_PLANES_KERNEL(SECOND, WGM_, WGN_, WM_, WN_, NS_, ST_, F16_) \
-    ((SECOND) ? gemm_planes2_kernel<WGM_, WGN_, WM_, WN_, NS_, ST_, 0, F16_> : gemm_planes_kernel<WGM_, WGN_, WM_, WN_, NS_, ST_, 0, F16_>)
-#else
-#define CLB_PLANES_KERNEL(SECOND, WGM_, WGN_, WM_, WN_, NS_, ST_, F16_) (gemm_planes2_kernel<WGM_, WGN_, WM_, WN_, NS_, ST_, 0, F16_>)
-#endif
+// (the plane GEMM needs N % 4 == 0, as every Linear of the encoder has -- linear_planes falls back to the fp32 GEMM otherwise)
 template <int NS, bool F16>
 bool launch_planes(hipStream_t st, const PlanCfg& c, const GemmPArgs& g) {
     const dim3 grid((unsigned)gemm_planes_grid(g.M, g.N, c.bm, c.bn, c.ks));
     const size_t lds = (size_t)c.stages * NS * (c.bm + c.bn) * 64;
-    const bool second = g.N % 4 == 0 && !planes_first_form();
-    if (NS == 2 && F16 && second && c.bm == 256 && c.bn == 256 && c.stages == 2 && wide_waves()) return launch_planes2_wide(st, 0, g, grid.x);
 #define CLB_GP_CASE(BM_, BN_, ST_, WGM_, WGN_, WM_, WN_)                                                              \
     if (c.bm == BM_ && c.bn == BN_ && c.stages == ST_) {                                                              \
-        auto kern = CLB_PLANES_KERNEL(second, WGM_, WGN_, WM_, WN_, NS, ST_, F16);                                    \
+        auto kern = gemm_planes2_kernel<WGM_, WGN_, WM_, WN_, NS, ST_, F16>;                                          \
         if (lds > 64 * 1024) allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds);                        \
         hipLaunchKernelGGL(kern, grid, dim3(64 * WGM_ * WGN_), lds, st, g);                                           \
         return true;                                                                                                  \
@@ -340,7 +264,7 @@ static PlanCfg pick_long_tile(int M, int N, bool allow_256, bool allow_128x256) 
 inline int plane_format(int gemm_mode) { return gemm_mode == 3 ? PF_F16X2 : gemm_mode == 1 ? PF_BF16X2 : PF_BF16X3; }
 
 // wscale: the power of two the weight planes were scaled by (PF_F16X2; 1 otherwise)
-void linear_planes(clb_encoder* e, hipStream_t st, int role, const uint16_t* Ap, int64_t a_plane, const uint16_t* Wp, float wscale,
+void linear_planes(clb_encoder* e, hipStream_t st, const uint16_t* Ap, int64_t a_plane, const uint16_t* Wp, float wscale,
                    float* C, uint16_t* Cp, int64_t c_plane, const float* bias, const float* R, int M, int N, int K, int epi,
                    float* part, const LnArgs* ln, const AttOut* att = nullptr, const LnFold* lf = nullptr, int64_t b_plane = 0) {
     const int fmt = plane_format(e->gemm_mode);
@@ -357,7 +281,6 @@ void linear_planes(clb_encoder* e, hipStream_t st, int role, const uint16_t* Ap,
             : wgs(128, 128) >= 256 ? pick_long_tile(M, N, wide && !att && !lf->u, wide) : PlanCfg{128, 128, 2, 1};
         part = nullptr;
     }
-    else if (const PlanCfg* o = plan_override(role)) c = *o;
     else if (M <= 64 && part) {
         // ONE query (search(searcher, query::String, k), 32 rows): every Linear is a weight stream with one tile row.  Split
         // over K until the chip is full (at least three 32-deep steps per slice) with a four-buffer ring: a work-group's
@@ -368,13 +291,13 @@ void linear_planes(clb_encoder* e, hipStream_t st, int role, const uint16_t* Ap,
         while (c.ks < 32 && K % (c.ks * 2 * 32) == 0 && K / (c.ks * 2) >= 96 && tn * c.ks * 2 <= 1024) c.ks *= 2;
     }
     else if (wgs(128, 128) >= 256)      // one 128 x 128 tile per CU and more (sweeps at M = 2 560 ... 19 200: r04_encoder_plan_sweeps.txt)
-        // long activations (passage batches; tools/microbench/gemm_planes_bigm_bench.hip): enough tiles to fill the chip, the
+        // long activations (passage batches): enough tiles to fill the chip, the
         // widest tile that still leaves two waves per SIMD -- 256 x 256 on eight waves of 64 x 128 (two planes: 128 KB of LDS;
         // half the operand bytes of 128 x 128 through L2; not behind the Q/K/V projection, whose epilogue scatters V), 128 x 256, else 128 x 128.
         // A GELU epilogue is ~2/3 of a tile's main loop in vector instructions: two 128 x 128 work-groups per CU overlap one's
         // epilogue with the other's loop, a single large one cannot (FFN-in of 64 x 300 passages: 322 against 358 us)
         {
-            const bool wide = NS == 2 && N % 4 == 0 && !(epi & EPI_GELU) && !planes_first_form();
+            const bool wide = NS == 2 && N % 4 == 0 && !(epi & EPI_GELU);
             c = pick_long_tile(M, N, wide && !att, wide);
             // round 6 (profiles/r06_encoder_plan_n128.txt, 128 queries = 4 096 rows): the Q/K/V projection of a few thousand rows
             // is 576 tiles of 128 x 128 -- two work-groups per CU take them in 1.1 rounds whose tail costs half a round, where
@@ -388,7 +311,7 @@ void linear_planes(clb_encoder* e, hipStream_t st, int role, const uint16_t* Ap,
         c = PlanCfg{128, 128, 2, 2};
     else {
         // A query batch (M ~ 1 000): 64 x 64 tiles with a two-tile ring = 48 KB of LDS, three work-groups per CU.  Measured
-        // (tools/microbench/gemm_planes_bench.hip): the loop is bound by MFMA issue (three 32 x 32 tiles per SIMD at the
+        // on the kernel alone: the loop is bound by MFMA issue (three 32 x 32 tiles per SIMD at the
         // ~1.75 GHz the chip holds) and by the ~65 GB/s an XCD's L2 delivers to one CU, both ~20 us for the 1024 x 2304 x 768
         // product; larger tiles move fewer bytes but leave CUs without a work-group, deeper rings cost the third resident
         // work-group.  Narrow outputs (N = hidden) are split over K until every CU has three work-groups.
@@ -576,7 +499,7 @@ static inline size_t fold_scale_index(int64_t l, int which /* 0 = Q/K/V (l >= 1)
 static bool can_pack(const clb_encoder* e, int64_t L, int64_t rows_max = 0) {
     const int64_t H = e->H, I = e->I;
     return e->planes && e->gemm_mode == 3 && H % 32 == 0 && I % 32 == 0 && e->heads > 0 && H / e->heads == 64 && L <= 512 &&
-           (e->attention_mode == 0 || e->attention_mode == 5) && !planes_first_form() && rows_max * std::max(H, I) * 6 < ((int64_t)1 << 31);
+           e->attention_mode == 0 && rows_max * std::max(H, I) * 6 < ((int64_t)1 << 31);
 }
 
 // pk (packed batch): d_ids holds pk->rows token ids, L is the longest sequence, d_mask is unused; needs the fp16-plane attention.
@@ -605,7 +528,7 @@ int forward(clb_encoder* e, int64_t L, int64_t N, hipStream_t st, const int32_t*
     const int PF = plane_format(e->gemm_mode);
     if (P && e->wp_fmt != PF) CLB_TRY(split_weights(e, PF));
     // attention on fp16 planes: the Q/K/V projection writes them (second GEMM form, never split over K)
-    const bool att16 = P && PF == PF_F16X2 && fused && (e->attention_mode == 0 || e->attention_mode == 5) && H % 4 == 0 && !planes_first_form();
+    const bool att16 = P && PF == PF_F16X2 && fused && e->attention_mode == 0 && H % 4 == 0;
     const int64_t ntile = (L + 31) / 32, qk_plane = T * 2 * H, vt_plane = N * heads * ntile * 64 * 32;
     if (pk && !att16)
         return fail(CLB_EARGUMENT, "a packed batch needs the fp16-plane attention (head size 64, f16x3 Linear layers, attention mode 0)");
@@ -628,8 +551,8 @@ int forward(clb_encoder* e, int64_t L, int64_t N, hipStream_t st, const int32_t*
     auto ws = [&](int64_t layer, int which) { return e->wscale.empty() ? 1.0f : e->wscale[(size_t)(layer * 4 + which)]; };
     const bool short_batch = T <= 4096;         // split-K scratch only where it can be used (query batches)
     // "LayerNorm without a pass of its own": long batches (no split-K anywhere), f16x3 planes, second GEMM form
-    const bool fold = P && PF == PF_F16X2 && e->fold_ready && !planes_first_form() && e->layers >= 1 &&
-                      (e->ln_fold == 1 || (e->ln_fold < 0 && !short_batch)) && !plan_override(LR_ATTN_OUT) && !plan_override(LR_FFN_OUT);
+    const bool fold = P && PF == PF_F16X2 && e->fold_ready && e->layers >= 1 &&
+                      (e->ln_fold == 1 || (e->ln_fold < 0 && !short_batch));
     const int ln_parts = (int)(H / 64);
     if (fold) {
         CLB_TRY(e->stats1.ensure(sizeof(float) * 2 * ln_parts * T));
@@ -667,10 +590,10 @@ int forward(clb_encoder* e, int64_t L, int64_t N, hipStream_t st, const int32_t*
         { EncTimed tm(e, ES_QKV, st);
         if (fold && l >= 1) {   // x holds the RAW output of the previous FFN-out: its LayerNorm is folded into this product
             const LnFold lf{st2, ln_parts, 64, e->eps, LV + e->v_qkv[l], nullptr, nullptr, nullptr};
-            linear_planes(e, st, LR_QKV, xp, hp, WPF + e->f_qkv[l], e->wscale_f[fold_scale_index(l, 0)], qkv, nullptr, 0, LV + e->v_qkv[l] + 3 * H, nullptr,
+            linear_planes(e, st, xp, hp, WPF + e->f_qkv[l], e->wscale_f[fold_scale_index(l, 0)], qkv, nullptr, 0, LV + e->v_qkv[l] + 3 * H, nullptr,
                           (int)T, (int)(3 * H), (int)H, EPI_BIAS, nullptr, nullptr, att16 ? &att_out : nullptr, &lf, e->wpf_plane);
         }
-        else if (P) linear_planes(e, st, LR_QKV, xp, hp, wp(lo + e->r_wqkv), ws(l, 0), qkv, nullptr, 0, P_ + e->r_bqkv, nullptr, (int)T, (int)(3 * H),
+        else if (P) linear_planes(e, st, xp, hp, wp(lo + e->r_wqkv), ws(l, 0), qkv, nullptr, 0, P_ + e->r_bqkv, nullptr, (int)T, (int)(3 * H),
                              (int)H, EPI_BIAS, part_wide, nullptr, att16 ? &att_out : nullptr);
         else linear(e, st, x, P_ + e->r_wqkv, qkv, P_ + e->r_bqkv, nullptr, (int)T, (int)(3 * H), (int)H, EPI_BIAS, nullptr); }
         EncTimed* t_att = new EncTimed(e, ES_ATTENTION, st);
@@ -679,26 +602,7 @@ int forward(clb_encoder* e, int64_t L, int64_t N, hipStream_t st, const int32_t*
             const dim3 grid((unsigned)((L + 31) / 32), (unsigned)heads, (unsigned)N);
             uint16_t* cp_ = P ? ctxp : nullptr;
 #define CLB_ATT(NT_) hipLaunchKernelGGL(attention_fused_kernel<NT_>, grid, dim3(64), 0, st, qkv, d_mask, ctx, (int)L, (int)H, inv_sqrt, cp_, hp, PF)
-#ifdef CLB_ABLATIONS
-            if (att16 && L > 32 && e->attention_mode == 5) {
-                // the query blocks of a (sequence, head) share its K / V tiles through LDS (attention_f16_lds_kernel): NW waves
-                // of QB blocks per work-group -- a whole sequence up to 512 tokens at QB = 2; bit-identical to the kernels below
-                const int QB = L >= 128 && att_qb2() ? 2 : 1;
-                int NW = (int)((L + 32 * QB - 1) / (32 * QB));
-                // QB = 2 needs ~290 registers: up to four waves run one per SIMD with the AGPRs as overflow; five and more share
-                // SIMDs (256 registers) and spill unless the staging is spread over eight waves (idle ones only stage)
-                NW = NW > 8 ? 8 : NW == 7 ? 8 : NW < 2 ? 2 : (QB == 2 && NW >= 5) ? 8 : NW;
-                const dim3 gridl((unsigned)((L + 32 * QB * NW - 1) / (32 * QB * NW)), (unsigned)heads, (unsigned)N);
-#define CLB_ATTL(QB_, NW_)                                                                                              \
-    if (QB == QB_ && NW == NW_)                                                                                         \
-        hipLaunchKernelGGL((attention_f16_lds_kernel<QB_, NW_>), gridl, dim3(64 * NW_), 0, st, att_out.qk, qk_plane, T, att_out.vt, vt_plane, \
-                           d_mask, (int)L, (int)H, inv_sqrt, ctxp, hp, PF, pk ? pk->cu : nullptr);
-                CLB_ATTL(1, 2) CLB_ATTL(1, 3) CLB_ATTL(1, 4) CLB_ATTL(2, 2) CLB_ATTL(2, 3) CLB_ATTL(2, 4) CLB_ATTL(2, 5) CLB_ATTL(2, 6) CLB_ATTL(2, 8)
-                CLB_ATTL(1, 5) CLB_ATTL(1, 6) CLB_ATTL(1, 8)
-#undef CLB_ATTL
-            } else
-#endif
-            if (att16 && L >= 128 && att_qb2()) {     // long sequences: two query blocks per wave share a key tile's K / V fragments
+            if (att16 && L >= 128) {     // long sequences: two query blocks per wave share a key tile's K / V fragments
                 const dim3 grid2((unsigned)((L + 63) / 64), (unsigned)heads, (unsigned)N);
                 hipLaunchKernelGGL(attention_f16_kernel<2>, grid2, dim3(64), 0, st, att_out.qk, qk_plane, T, att_out.vt, vt_plane, d_mask, (int)L,
                                    (int)H, inv_sqrt, ctxp, hp, PF, pk ? pk->cu : nullptr);
@@ -727,10 +631,10 @@ int forward(clb_encoder* e, int64_t L, int64_t N, hipStream_t st, const int32_t*
         { EncTimed tm(e, ES_ATTN_OUT, st);
         if (fold) {     // raw rows + their partial statistics; the residual is x, raw too from layer 1 on (normalised on the fly)
             const LnFold lf{l >= 1 ? st2 : nullptr, ln_parts, 64, e->eps, nullptr, l >= 1 ? Pp_ + e->r_g2 : nullptr, l >= 1 ? Pp_ + e->r_b2n : nullptr, st1};
-            linear_planes(e, st, LR_ATTN_OUT, ctxp, hp, wp(lo + e->r_wo), ws(l, 1), tmp, tmpp, hp, P_ + e->r_bo, x, (int)T, (int)H, (int)H,
+            linear_planes(e, st, ctxp, hp, wp(lo + e->r_wo), ws(l, 1), tmp, tmpp, hp, P_ + e->r_bo, x, (int)T, (int)H, (int)H,
                           EPI_BIAS | EPI_RESID, nullptr, nullptr, nullptr, &lf);
         }
-        else if (P) linear_planes(e, st, LR_ATTN_OUT, ctxp, hp, wp(lo + e->r_wo), ws(l, 1), tmp, tmpp, hp, P_ + e->r_bo, x, (int)T, (int)H, (int)H,
+        else if (P) linear_planes(e, st, ctxp, hp, wp(lo + e->r_wo), ws(l, 1), tmp, tmpp, hp, P_ + e->r_bo, x, (int)T, (int)H, (int)H,
                              EPI_BIAS | EPI_RESID, part, &ln1);
         else linear(e, st, ctx, P_ + e->r_wo, tmp, P_ + e->r_bo, x, (int)T, (int)H, (int)H, EPI_BIAS | EPI_RESID, part, &ln1); }
         // feed-forward: GELU(x W1^T + b1) W2^T + b2 + residual, LayerNorm.  On the plane path the (T x I) intermediate
@@ -738,19 +642,19 @@ int forward(clb_encoder* e, int64_t L, int64_t N, hipStream_t st, const int32_t*
         { EncTimed tm(e, ES_FFN_IN, st);
         if (fold) {
             const LnFold lf{st1, ln_parts, 64, e->eps, LV + e->v_w1[l], nullptr, nullptr, nullptr};
-            linear_planes(e, st, LR_FFN_IN, tmpp, hp, WPF + e->f_w1[l], e->wscale_f[fold_scale_index(l, 1)], nullptr, hbp, ip, LV + e->v_w1[l] + I, nullptr,
+            linear_planes(e, st, tmpp, hp, WPF + e->f_w1[l], e->wscale_f[fold_scale_index(l, 1)], nullptr, hbp, ip, LV + e->v_w1[l] + I, nullptr,
                           (int)T, (int)I, (int)H, EPI_BIAS | EPI_GELU, nullptr, nullptr, nullptr, &lf, e->wpf_plane);
         }
-        else if (P) linear_planes(e, st, LR_FFN_IN, tmpp, hp, wp(lo + e->r_w1), ws(l, 2), nullptr, hbp, ip, P_ + e->r_b1, nullptr, (int)T, (int)I, (int)H,
+        else if (P) linear_planes(e, st, tmpp, hp, wp(lo + e->r_w1), ws(l, 2), nullptr, hbp, ip, P_ + e->r_b1, nullptr, (int)T, (int)I, (int)H,
                              EPI_BIAS | EPI_GELU, part_wide, nullptr);
         else linear(e, st, tmp, P_ + e->r_w1, hb, P_ + e->r_b1, nullptr, (int)T, (int)I, (int)H, EPI_BIAS | EPI_GELU, nullptr); }
         { EncTimed tm(e, ES_FFN_OUT, st);
         if (fold) {     // the residual is the raw attention-output row: its (first) LayerNorm is applied on the fly
             const LnFold lf{st1, ln_parts, 64, e->eps, nullptr, P_ + e->r_g1, P_ + e->r_b1n, st2};
-            linear_planes(e, st, LR_FFN_OUT, hbp, ip, wp(lo + e->r_w2), ws(l, 3), x, xp, hp, P_ + e->r_b2, tmp, (int)T, (int)H, (int)I,
+            linear_planes(e, st, hbp, ip, wp(lo + e->r_w2), ws(l, 3), x, xp, hp, P_ + e->r_b2, tmp, (int)T, (int)H, (int)I,
                           EPI_BIAS | EPI_RESID, nullptr, nullptr, nullptr, &lf);
         }
-        else if (P) linear_planes(e, st, LR_FFN_OUT, hbp, ip, wp(lo + e->r_w2), ws(l, 3), x, xp, hp, P_ + e->r_b2, tmp, (int)T, (int)H, (int)I,
+        else if (P) linear_planes(e, st, hbp, ip, wp(lo + e->r_w2), ws(l, 3), x, xp, hp, P_ + e->r_b2, tmp, (int)T, (int)H, (int)I,
                              EPI_BIAS | EPI_RESID, part, &ln2);
         else linear(e, st, hb, P_ + e->r_w2, x, P_ + e->r_b2, tmp, (int)T, (int)H, (int)I, EPI_BIAS | EPI_RESID, part, &ln2); }
     }
@@ -758,10 +662,10 @@ int forward(clb_encoder* e, int64_t L, int64_t N, hipStream_t st, const int32_t*
     { EncTimed tm(e, ES_PROJECTION, st);
     if (fold) {         // x holds the raw output of the last FFN-out
         const LnFold lf{st2, ln_parts, 64, e->eps, LV + e->v_lin, nullptr, nullptr, nullptr};
-        linear_planes(e, st, LR_PROJ, xp, hp, WPF + e->f_lin, e->wscale_f.back(), e->out.as<float>(), nullptr, 0, LV + e->v_lin + e->dim, nullptr, (int)T,
+        linear_planes(e, st, xp, hp, WPF + e->f_lin, e->wscale_f.back(), e->out.as<float>(), nullptr, 0, LV + e->v_lin + e->dim, nullptr, (int)T,
                       (int)e->dim, (int)H, EPI_BIAS, nullptr, nullptr, nullptr, &lf, e->wpf_plane);
     }
-    else if (P) linear_planes(e, st, LR_PROJ, xp, hp, wp(e->o_lin_w), ws(e->layers, 0), e->out.as<float>(), nullptr, 0, W + e->o_lin_b, nullptr, (int)T,
+    else if (P) linear_planes(e, st, xp, hp, wp(e->o_lin_w), ws(e->layers, 0), e->out.as<float>(), nullptr, 0, W + e->o_lin_b, nullptr, (int)T,
                          (int)e->dim, (int)H, EPI_BIAS, part, nullptr);
     else linear(e, st, x, W + e->o_lin_w, e->out.as<float>(), W + e->o_lin_b, nullptr, (int)T, (int)e->dim, (int)H, EPI_BIAS, part); }
     CLB_HIP(hipGetLastError());
@@ -887,11 +791,9 @@ int clb_encoder_create(int device, int64_t vocab, int64_t hidden, int64_t layers
     }
     {   // the Linear weights as bf16 planes, split ONCE (the region from the first layer to the end of the blob: biases and
         // LayerNorm parameters ride along unused).  1.5x the bytes of the fp32 region.
-        const char* v = CLB_ENV("COLBERT_ENCODER_PLANES");
         const int64_t n_lin = n_weights - e->o_layer0;
         // (every Linear's N must be a multiple of 4 for the plane GEMM of the product library: H, 3H and I are; dim may not be)
-        e->planes = (!v || atoi(v) != 0) && H % 32 == 0 && I % 32 == 0 && e->o_layer0 % 4 == 0 && n_lin * 6 < ((int64_t)1 << 31) &&
-                    (kAblations || e->dim % 4 == 0);
+        e->planes = H % 32 == 0 && I % 32 == 0 && e->o_layer0 % 4 == 0 && n_lin * 6 < ((int64_t)1 << 31) && e->dim % 4 == 0;
         if (e->planes) {
             e->wp_plane = n_lin;
             if ((rc = e->wplanes.alloc(sizeof(uint16_t) * 3 * n_lin)) || (rc = split_weights(e, plane_format(e->gemm_mode)))) {
@@ -933,11 +835,10 @@ int clb_encoder_set_ln_fold(clb_encoder* e, int mode) {
 
 int clb_encoder_set_attention_mode(clb_encoder* e, int mode) {
     if (!e) return fail(CLB_EARGUMENT, "null encoder");
-    if (mode == 5 && !kAblations)
-        return fail(CLB_EUNSUPPORTED, "attention mode 5 (K / V tiles shared through LDS: bit-identical to mode 0 and slower) is built into tuning libraries only (make ABLATIONS=1)");
-    if (mode < 0 || mode > 5 || mode == 4)
-        return fail(CLB_EARGUMENT, "attention mode %d: 0 = fused, 1 = register-resident, 2 = three kernels, 3 = fused on the fp32 MFMA, "
-                                   "5 = fused with the K / V tiles of a (sequence, head) shared through LDS", mode);
+    if (mode == 5)
+        return fail(CLB_EUNSUPPORTED, "attention mode 5 (K / V tiles shared through LDS: bit-identical to mode 0 and slower) was retired");
+    if (mode < 0 || mode > 3)
+        return fail(CLB_EARGUMENT, "attention mode %d: 0 = fused, 1 = register-resident, 2 = three kernels, 3 = fused on the fp32 MFMA", mode);
     e->attention_mode = mode;
     return CLB_OK;
 }

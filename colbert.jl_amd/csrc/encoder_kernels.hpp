@@ -657,7 +657,7 @@ static __global__ __launch_bounds__(256) void ln_fold_vectors_kernel(const float
     if (lane == 0) { out[n] = u; out[N + n] = c + bias[n]; }
 }
 
-// number of work-groups to launch for gemm_planes_kernel's XCD-aware mapping (1-D grid)
+// number of work-groups to launch for gemm_planes2_kernel's XCD-aware mapping (1-D grid)
 inline int gemm_planes_grid(int M, int N, int bm, int bn, int ksplit) {
     const int TM = (M + bm - 1) / bm, TN = (N + bn - 1) / bn;
     const int64_t T = (int64_t)TM * TN * ksplit;
@@ -683,146 +683,11 @@ __device__ __forceinline__ bool gemm_planes_tile(int M, int N, int BM, int BN, i
     return true;
 }
 
-// ABL (tools/microbench/gemm_planes_bench.hip only): 1 = no DMAs (the MFMA / LDS-read side alone), 2 = no LDS reads and
-// MFMAs (the DMA side alone); results are meaningless.  F16: the planes are PF_F16X2 (NS = 2), else bf16.
-template <int WGM, int WGN, int WM, int WN, int NS, int STAGES, int ABL = 0, bool F16 = false>
-static __global__ __launch_bounds__(64 * WGM * WGN) void gemm_planes_kernel(GemmPArgs g) {
-    static_assert(!F16 || NS == 2, "the fp16 split has two planes");
-    constexpr int PFMT = F16 ? PF_F16X2 : (NS == 3 ? PF_BF16X3 : PF_BF16X2);
-    constexpr int NW = WGM * WGN;
-    constexpr int BM = 32 * WM * WGM, BN = 32 * WN * WGN;
-    constexpr int PA = BM * 64, PB = BN * 64;                              // bytes per plane and stage
-    constexpr int STAGEB = NS * (PA + PB);
-    constexpr int NDMA = NS * (BM + BN) / 16;                              // wave-instructions per stage
-    constexpr int DPW = (NDMA + NW - 1) / NW;       // a stage's DMAs dealt over the waves; a surplus slot repeats the last one
-    static_assert(STAGES >= 2 && STAGES <= 4 && DPW * (STAGES - 2) <= 63, "ring depth");
-    extern __shared__ __attribute__((aligned(16))) unsigned char gplds[];
-    // ---- work-group -> tile, XCD-aware (gemm_planes_tile).  Every XCD has its own 4-MB L2: dealt n-major over the whole
-    // chip, every XCD would pull ALL of both operands through its L2 (FFN-out of a query batch: 33 MB of planes per XCD,
-    // 264 MB from the Infinity Cache per GEMM, which then bounds it)
-    const bool split = g.ksplit > 1;
-    int z, m0, n0;
-    if (!gemm_planes_tile(g.M, g.N, BM, BN, g.ksplit, z, m0, n0)) return;
-    const int K_ = split ? g.K / g.ksplit : g.K;                // a multiple of 32 (host)
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave / WGN, wc = wave % WGN;
-    const int i = lane & 31, h = lane >> 5;
-    float* C = g.C ? g.C + (split ? (int64_t)z * g.M * g.ldc : 0) : nullptr;
-    // ---- loader: DMA instruction d = wave + NW j of a stage moves 16 rows x 64 B of one plane of one operand.  Lane l
-    // lands at slot + 16 l: row 16 rb + (l >> 2), chunk position l & 3, i.e. it must FETCH chunk (l & 3) ^ ((l >> 4) & 3)
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)gplds;
-    const int64_t a_step = (int64_t)g.M * 64, b_step = (int64_t)g.N * 64;      // bytes from one 32-deep block to the next
-    const char* a_base = reinterpret_cast<const char*>(g.A) + (split ? (int64_t)z * (K_ / 32) * a_step : 0);
-    const char* b_base = reinterpret_cast<const char*>(g.B) + (split ? (int64_t)z * (K_ / 32) * b_step : 0);
-    uint32_t voff[DPW];           // per-lane byte offset from the operand's base (plane, row, chunk)
-    uint32_t loff[DPW];           // wave-uniform LDS offset inside a stage
-    bool isb[DPW];
-#pragma unroll
-    for (int j = 0; j < DPW; ++j) {
-        const int d = wave + NW * j < NDMA ? wave + NW * j : NDMA - 1;
-        const bool b_op = d >= NS * (BM / 16);
-        const int dd = b_op ? d - NS * (BM / 16) : d;
-        const int rows16 = b_op ? BN / 16 : BM / 16;
-        const int q = dd / rows16, rb = dd % rows16;
-        int row = (b_op ? n0 : m0) + 16 * rb + (lane >> 2);
-        const int lim = b_op ? g.N : g.M;
-        row = row < lim ? row : lim - 1;
-        const uint32_t chunk = ((uint32_t)lane & 3u) ^ (((uint32_t)lane >> 4) & 3u);
-        voff[j] = (uint32_t)(((int64_t)q * (b_op ? g.b_plane : g.a_plane) + (int64_t)row * 32) * 2) + chunk * 16u;
-        loff[j] = (uint32_t)((b_op ? NS * PA : 0) + q * (b_op ? PB : PA) + rb * 1024);
-        isb[j] = b_op;
-    }
-#define CLB_GP_ISSUE(KSTEP, BUF)                                                                                     \
-    {                                                                                                                \
-        const char* ab_ = a_base + (int64_t)(KSTEP) * a_step;                                                        \
-        const char* bb_ = b_base + (int64_t)(KSTEP) * b_step;                                                        \
-        if (ABL != 1) _Pragma("unroll") for (int j = 0; j < DPW; ++j)                                                \
-            asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1"                                        \
-                         :: "v"(voff[j]), "s"(isb[j] ? bb_ : ab_), "s"(lds0 + (uint32_t)(BUF) * STAGEB + loff[j]) : "memory"); \
-    }
-    f32x16 acc[WM][WN];
-#pragma unroll
-    for (int a = 0; a < WM; ++a)
-#pragma unroll
-        for (int b = 0; b < WN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-    const int nsteps = K_ / 32;
-#pragma unroll
-    for (int s = 0; s < STAGES - 1; ++s)
-        if (s < nsteps) CLB_GP_ISSUE(s, s)
-    const int sw = (i >> 2) & 3;
-    const unsigned char* As0 = gplds + (wr * 32 * WM + i) * 64;
-    const unsigned char* Bs0 = gplds + NS * PA + (wc * 32 * WN + i) * 64;
-    int buf = 0;
-    for (int k = 0; k < nsteps; ++k) {
-        // tile k has landed once at most the DMAs of the tiles issued after it are pending
-        if (k + STAGES - 1 <= nsteps) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "n"(DPW * (STAGES - 2)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        if (k + STAGES - 1 < nsteps) {
-            const int nb = buf == 0 ? STAGES - 1 : buf - 1;               // (k + STAGES - 1) % STAGES = (k - 1) % STAGES
-            CLB_GP_ISSUE(k + STAGES - 1, nb)
-        }
-        const unsigned char* As = As0 + buf * STAGEB;
-        const unsigned char* Bs = Bs0 + buf * STAGEB;
-        if (ABL != 2)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const int off = ((2 * s + h) ^ sw) << 4;
-            u32x4 av[NS][WM], bv[NS][WN];
-#pragma unroll
-            for (int q = 0; q < NS; ++q) {
-#pragma unroll
-                for (int a = 0; a < WM; ++a) av[q][a] = *reinterpret_cast<const u32x4*>(As + q * PA + a * 32 * 64 + off);
-#pragma unroll
-                for (int b = 0; b < WN; ++b) bv[q][b] = *reinterpret_cast<const u32x4*>(Bs + q * PB + b * 32 * 64 + off);
-            }
-#define CLB_GP_MFMA(QA, QB)                                                                                            \
-            c = F16 ? __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, av[QA][a]), __builtin_bit_cast(f16x8, bv[QB][b]), c, 0, 0, 0) \
-                    : __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av[QA][a]), __builtin_bit_cast(bf16x8, bv[QB][b]), c, 0, 0, 0);
-#pragma unroll
-            for (int a = 0; a < WM; ++a)
-#pragma unroll
-                for (int b = 0; b < WN; ++b) {
-                    f32x16 c = acc[a][b];
-                    if (NS == 3) { CLB_GP_MFMA(2, 0) CLB_GP_MFMA(0, 2) CLB_GP_MFMA(1, 1) }
-                    CLB_GP_MFMA(1, 0) CLB_GP_MFMA(0, 1) CLB_GP_MFMA(0, 0)
-                    acc[a][b] = c;
-                }
-#undef CLB_GP_MFMA
-        }
-        buf = buf + 1 == STAGES ? 0 : buf + 1;
-    }
-#undef CLB_GP_ISSUE
-    // C layout: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * h
-#pragma unroll
-    for (int a = 0; a < WM; ++a)
-#pragma unroll
-        for (int b = 0; b < WN; ++b) {
-            const int n = n0 + (wc * WN + b) * 32 + i;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + (wr * WM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (m < g.M && n < g.N) {
-                    float v = acc[a][b][r];
-                    if (!split) {
-                        if (F16) v = v * g.out_scale;
-                        if (g.epi & EPI_BIAS) v += g.bias[n];
-                        if (g.epi & EPI_GELU) v = gelu_erf(v);
-                        if (g.epi & EPI_RESID) v += g.R[(int64_t)m * g.ldc + n];
-                        if (g.Cp) store_planes(g.Cp + plane_index(m, n, g.M), g.c_plane, PFMT, v);
-                    }
-                    if (C) C[(int64_t)m * g.ldc + n] = v;
-                }
-            }
-        }
-}
-
-// The same product, second form (the default): (1) the accumulators are TRANSPOSED -- the MFMA takes the weight fragment as
-// its row operand, so a lane owns ONE output row (m = lane & 31) and its registers run along n in groups of four consecutive
-// columns: the epilogue is one 16-byte store (fp32) or one 8-byte store per plane for four outputs, where the first form
-// issued 4-byte / 2-byte stores per element (the epilogue of a 19 200-row passage batch was 45 of 300 us); (2) the two
+// C = A planes . B planes^T on MFMA tiles, the operands moved by LDS-DMA into a ring of STAGES tiles.  F16: the planes are
+// PF_F16X2 (NS = 2), else bf16.  Against the first form of this product (retired): (1) the accumulators are TRANSPOSED -- the
+// MFMA takes the weight fragment as its row operand, so a lane owns ONE output row (m = lane & 31) and its registers run along n
+// in groups of four consecutive columns: the epilogue is one 16-byte store (fp32) or one 8-byte store per plane for four
+// outputs, where the first form issued 4-byte / 2-byte stores per element (the epilogue of a 19 200-row passage batch was 45 of 300 us); (2) the two
 // 16-deep halves of a step are double-buffered in REGISTERS: the LDS reads of the next half are issued before the MFMAs of
 // this one, and the single barrier of a step sits between the halves -- "tile k + 1 has landed and tile k has been read by
 // everyone" -- after which the DMA of tile k + STAGES goes into the buffer just freed: the LDS latency is never exposed and a
@@ -839,7 +704,7 @@ static __global__ __launch_bounds__(64 * WGM * WGN) void gemm_planes_kernel(Gemm
 // LN = 1: the consuming side (ln_u / ln_in); LN = 2: the producing side (stats_out, and r_gamma / r_beta / ln_in for its residual).
 // In both the statistics of the lane's rows are requested BEFORE the operand DMAs of the prologue and merged behind them (their
 // latency hides under the first tile's), and the consumer loads the two column vectors of all its columns in one batch.
-template <int WGM, int WGN, int WM, int WN, int NS, int STAGES, int ABL = 0, bool F16 = false, int LN = 0>
+template <int WGM, int WGN, int WM, int WN, int NS, int STAGES, bool F16 = false, int LN = 0>
 static __global__ __launch_bounds__(64 * WGM * WGN) void gemm_planes2_kernel(GemmPArgs g) {
     static_assert(!F16 || NS == 2, "the fp16 split has two planes");
     constexpr int PFMT = F16 ? PF_F16X2 : (NS == 3 ? PF_BF16X3 : PF_BF16X2);
@@ -851,20 +716,26 @@ static __global__ __launch_bounds__(64 * WGM * WGN) void gemm_planes2_kernel(Gem
     constexpr int DPW = (NDMA + NW - 1) / NW;
     static_assert(STAGES >= 2 && STAGES <= 5 && DPW * (STAGES - 1) <= 63, "ring depth");
     extern __shared__ __attribute__((aligned(16))) unsigned char gplds[];
+    // ---- work-group -> tile, XCD-aware (gemm_planes_tile).  Every XCD has its own 4-MB L2: dealt n-major over the whole
+    // chip, every XCD would pull ALL of both operands through its L2 (FFN-out of a query batch: 33 MB of planes per XCD,
+    // 264 MB from the Infinity Cache per GEMM, which then bounds it)
     const bool split = g.ksplit > 1;
     int z, m0, n0;
     if (!gemm_planes_tile(g.M, g.N, BM, BN, g.ksplit, z, m0, n0)) return;
-    const int K_ = split ? g.K / g.ksplit : g.K;
+    const int K_ = split ? g.K / g.ksplit : g.K;                // a multiple of 32 (host)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave / WGN, wc = wave % WGN;
     const int i = lane & 31, h = lane >> 5;
     float* C = g.C ? g.C + (split ? (int64_t)z * g.M * g.ldc : 0) : nullptr;
+    // ---- loader: DMA instruction d = wave + NW j of a stage moves 16 rows x 64 B of one plane of one operand (a surplus slot
+    // repeats the last one).  Lane l lands at slot + 16 l: row 16 rb + (l >> 2), chunk position l & 3, i.e. it must FETCH
+    // chunk (l & 3) ^ ((l >> 4) & 3)
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)gplds;
-    const int64_t a_step = (int64_t)g.M * 64, b_step = (int64_t)g.N * 64;
+    const int64_t a_step = (int64_t)g.M * 64, b_step = (int64_t)g.N * 64;      // bytes from one 32-deep block to the next
     const char* a_base = reinterpret_cast<const char*>(g.A) + (split ? (int64_t)z * (K_ / 32) * a_step : 0);
     const char* b_base = reinterpret_cast<const char*>(g.B) + (split ? (int64_t)z * (K_ / 32) * b_step : 0);
-    uint32_t voff[DPW], loff[DPW];
+    uint32_t voff[DPW], loff[DPW];   // per-lane byte offset from the operand's base (plane, row, chunk); LDS offset inside a stage
     bool isb[DPW];
 #pragma unroll
     for (int j = 0; j < DPW; ++j) {
@@ -885,7 +756,7 @@ static __global__ __launch_bounds__(64 * WGM * WGN) void gemm_planes2_kernel(Gem
     {                                                                                                                \
         const char* ab_ = a_base + (int64_t)(KSTEP) * a_step;                                                        \
         const char* bb_ = b_base + (int64_t)(KSTEP) * b_step;                                                        \
-        if (ABL != 1 && ABL != 3) _Pragma("unroll") for (int j = 0; j < DPW; ++j)                                                \
+        _Pragma("unroll") for (int j = 0; j < DPW; ++j)                                                              \
             asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1"                                        \
                          :: "v"(voff[j]), "s"(isb[j] ? bb_ : ab_), "s"(lds0 + (uint32_t)(BUF) * STAGEB + loff[j]) : "memory"); \
     }
@@ -927,7 +798,7 @@ static __global__ __launch_bounds__(64 * WGM * WGN) void gemm_planes2_kernel(Gem
     const unsigned char* Bs0 = gplds + NS * PA + (wc * 32 * WN + i) * 64;
     u32x4 fa[2][NS][WM], fb[2][NS][WN];
 #define CLB_GP2_READ(W, BUF, S)                                                                                       \
-    if (ABL != 2) {                                                                                                   \
+    {                                                                                                                 \
         const int off_ = ((2 * (S) + h) ^ sw) << 4;                                                                   \
         const unsigned char* as_ = As0 + (BUF) * STAGEB + off_;                                                       \
         const unsigned char* bs_ = Bs0 + (BUF) * STAGEB + off_;                                                       \
@@ -941,7 +812,7 @@ static __global__ __launch_bounds__(64 * WGM * WGN) void gemm_planes2_kernel(Gem
     c = F16 ? __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fb[W][QB][b]), __builtin_bit_cast(f16x8, fa[W][QA][a]), c, 0, 0, 0) \
             : __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fb[W][QB][b]), __builtin_bit_cast(bf16x8, fa[W][QA][a]), c, 0, 0, 0);
 #define CLB_GP2_MFMA(W)                                                                                               \
-    if (ABL != 2) {                                                                                                   \
+    {                                                                                                                 \
         _Pragma("unroll") for (int a = 0; a < WM; ++a)                                                                \
             _Pragma("unroll") for (int b = 0; b < WN; ++b) {                                                          \
                 f32x16 c = acc[a][b];                                                                                 \
@@ -964,8 +835,7 @@ static __global__ __launch_bounds__(64 * WGM * WGN) void gemm_planes2_kernel(Gem
         if (k + 1 < nsteps) {
             // my reads of tile k are complete (lgkmcnt) and my DMAs of tile k + 1 have landed (vmcnt); after the barrier that
             // holds for every wave: buffer `buf` is free for tile k + STAGES and tile k + 1 can be read
-            if (ABL == 3) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            else if (k + STAGES <= nsteps) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(DPW * (STAGES - 2)) : "memory");
+            if (k + STAGES <= nsteps) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(DPW * (STAGES - 2)) : "memory");
             else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
             if (k + STAGES < nsteps) CLB_GP2_ISSUE(k + STAGES, buf)
             CLB_GP2_READ(0, nbuf, 0)
@@ -1494,7 +1364,7 @@ static __global__ __launch_bounds__(64) void attention_fused_kernel(const float*
     for (int r = 0; r < 16; ++r) {
         const int q = q0 + (r & 3) + 8 * (r >> 2) + 4 * h;
         if (q < L) {
-            if (ctxp) {      // the output projection reads bf16 planes (gemm_planes_kernel): no fp32 copy is kept
+            if (ctxp) {      // the output projection reads bf16 planes (gemm_planes2_kernel): no fp32 copy is kept
                 const int64_t trow = n * L + q, rows_ = (int64_t)gridDim.z * L;
                 store_planes(ctxp + plane_index(trow, head * 64 + i, rows_), c_plane, ns, o0[r]);
                 store_planes(ctxp + plane_index(trow, head * 64 + 32 + i, rows_), c_plane, ns, o1[r]);
@@ -1772,227 +1642,6 @@ static __global__ __launch_bounds__(64, QB == 1 ? 3 : 2) void attention_f16_kern
                 const int64_t trow = row0 + q;
                 store_planes(ctxp + plane_index(trow, head * 64 + i, rows_), c_plane, ns, o0[qb][r] * sc);
                 store_planes(ctxp + plane_index(trow, head * 64 + 32 + i, rows_), c_plane, ns, o1[qb][r] * sc);
-            }
-        }
-    }
-}
-
-// Round 5: the same attention with the K / V tiles of a (sequence, head) SHARED by its query blocks through LDS.  In the kernel
-// above every wave pulls all key tiles of its sequence through L2 on its own -- 16 KB per tile and wave, 1.2 GB per layer on a
-// 64 x 300 passage batch, and the kernel is bound by those loads (halving them bought 20 %, cutting a third of its vector
-// instructions 3 %).  Here a work-group of NW waves owns 32 QB NW queries of one (sequence, head) -- a whole 300-token passage
-// at QB = 2, NW = 5 -- and stages every key tile ONCE: 2 planes x (K: 2 feature blocks x 32 keys x 64 B, V: 64 d x 64 B) = 16 KB,
-// double-buffered (global -> registers while the previous tile is multiplied, registers -> LDS behind it, one barrier per tile);
-// rows are padded to 80 bytes, so the ds_read_b128 of 16 consecutive lanes touch 64 different banks.  Every wave then reads
-// exactly the fragments it used to load: the same MFMAs on the same operands in the same order -- bit-identical output.
-// A wave whose queries lie past the end of a (packed) sequence still stages and meets the barriers.  grid = (ceil(L / (32 QB
-// NW)), heads, N), block = 64 NW.
-template <int QB, int NW>
-static __global__ __launch_bounds__(64 * NW) void attention_f16_lds_kernel(const uint16_t* __restrict__ qk, int64_t qk_plane, int64_t rows,
-                                                                          const uint16_t* __restrict__ vt, int64_t vt_plane,
-                                                                          const uint8_t* __restrict__ mask, int L, int H, float scale,
-                                                                          uint16_t* __restrict__ ctxp, int64_t c_plane, int ns,
-                                                                          const int32_t* __restrict__ cu = nullptr) {
-    constexpr int NT = 64 * NW;
-    constexpr int kRow = 80;                              // padded LDS row (64 B of data)
-    constexpr int kKBytes = 2 * 2 * 32 * kRow, kVBytes = 2 * 64 * kRow, kStage = kKBytes + kVBytes;     // 20 480 B per tile
-    constexpr int kChunks = 1024;                         // 16-byte pieces of a tile: 512 of K, 512 of V
-    constexpr int CPT = (kChunks + NT - 1) / NT;          // pieces per thread
-    __shared__ __attribute__((aligned(16))) unsigned char tiles[2 * kStage];
-    const int tid = threadIdx.x, lane = tid & 63, i = lane & 31, h = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int head = blockIdx.y, heads = gridDim.y;
-    const int64_t n = blockIdx.z;
-    const int nt_layout = (L + 31) >> 5;
-    const int64_t row0 = cu ? (int64_t)cu[n] : n * L;
-    if (cu) L = cu[n + 1] - cu[n];
-    if ((int)blockIdx.x * NW * 32 * QB >= L) return;                     // the whole work-group lies past the sequence
-    const int q0 = ((int)blockIdx.x * NW + wave) * 32 * QB;
-    const bool active = q0 < L;
-    const uint8_t* mk = cu ? nullptr : mask + n * L;
-    // key tiles up to the last attended key (padding behind it is all masked: nothing to add, nothing to stage)
-    int nt = (L + 31) >> 5;
-    if (mk) {
-        int last = -1;
-        for (int k0 = lane; k0 < L; k0 += 64) last = mk[k0] ? k0 : last;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const int y = __shfl_xor(last, o, 64); last = y > last ? y : last; }
-        nt = (last + 32) >> 5;                                           // last = -1: no tile
-    }
-    // ---- staging: piece c of a tile -> (source address, LDS offset); tile jt adds its own strides
-    u32x4 stg[CPT];
-    auto load_tile = [&](int jt) {
-#pragma unroll
-        for (int p = 0; p < CPT; ++p) {
-            const int c = tid + NT * p;
-            if (c >= kChunks) break;
-            const int plane = (c >> 8) & 1, ch = c & 3;
-            if (c < 512) {
-                const int blk = (c >> 7) & 1, r = (c >> 2) & 31;
-                const int key = 32 * jt + r;
-                const int krow = key < L ? key : L - 1;
-                const uint16_t* src = qk + (int64_t)plane * qk_plane + plane_index(row0 + krow, H + head * 64 + 32 * blk, rows) + 8 * ch;
-                stg[p] = *reinterpret_cast<const u32x4*>(src);
-            } else {
-                const int d = (c >> 2) & 63;
-                const uint16_t* src = vt + (int64_t)plane * vt_plane + (((((n * heads + head) * nt_layout + jt) * 64) + d) << 5) + 8 * ch;
-                stg[p] = *reinterpret_cast<const u32x4*>(src);
-            }
-        }
-    };
-    auto store_tile = [&](int buf) {
-        unsigned char* base = tiles + buf * kStage;
-#pragma unroll
-        for (int p = 0; p < CPT; ++p) {
-            const int c = tid + NT * p;
-            if (c >= kChunks) break;
-            const int plane = (c >> 8) & 1, ch = c & 3;
-            if (c < 512) {
-                const int blk = (c >> 7) & 1, r = (c >> 2) & 31;
-                *reinterpret_cast<u32x4*>(base + ((plane * 2 + blk) * 32 + r) * kRow + 16 * ch) = stg[p];
-            } else {
-                const int d = (c >> 2) & 63;
-                *reinterpret_cast<u32x4*>(base + kKBytes + (plane * 64 + d) * kRow + 16 * ch) = stg[p];
-            }
-        }
-    };
-    u32x4 qh[QB][4], ql[QB][4];
-#pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {
-        const int qi = q0 + 32 * qb + i;
-        const int64_t qrow = row0 + (qi < L ? qi : L - 1);
-        const uint16_t* qp = qk + plane_index(qrow, head * 64 + 32 * h, rows);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            qh[qb][s] = reinterpret_cast<const u32x4*>(qp)[s];
-            ql[qb][s] = reinterpret_cast<const u32x4*>(qp + qk_plane)[s];
-        }
-    }
-    f32x16 o0[QB], o1[QB];
-    float m[QB], l[QB];
-#pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {
-        m[qb] = kNegInf; l[qb] = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { o0[qb][r] = 0.f; o1[qb][r] = 0.f; }
-    }
-    const float sscale = scale * (1.0f / (kF16ActScale * kF16ActScale)) * 1.44269504088896340736f;     // -> log2 domain
-    constexpr float kPScale = 1024.0f;
-    if (nt > 0) { load_tile(0); store_tile(0); }
-    __syncthreads();
-    for (int jt = 0; jt < nt; ++jt) {
-        const bool more = jt + 1 < nt;
-        if (more) load_tile(jt + 1);                                    // in flight under this tile's products
-        const int key = 32 * jt + i;
-        const int krow = key < L ? key : L - 1;
-        const uint32_t valid = (uint32_t)__builtin_amdgcn_ballot_w64(h == 0 && key < L && (!mk || mk[krow] != 0));
-        if (active && valid != 0u) {
-            const unsigned char* kb = tiles + (jt & 1) * kStage + (h * 32 + i) * kRow;
-            const unsigned char* vb = tiles + (jt & 1) * kStage + kKBytes + i * kRow + 32 * h;
-            // phase 1, every query block: scores, running maximum / sum, probabilities (split in registers).  The K fragments
-            // are dead before the V fragments are read (from LDS there is no latency to hide by requesting them early): the
-            // kernel stays under the 256 registers of two waves per SIMD
-            u32x4 ph[QB][2], pl[QB][2];
-            {
-                u32x4 kh[4], kl[4];
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    kh[s] = *reinterpret_cast<const u32x4*>(kb + 16 * s);
-                    kl[s] = *reinterpret_cast<const u32x4*>(kb + 2 * 32 * kRow + 16 * s);
-                }
-#pragma unroll
-                for (int qb = 0; qb < QB; ++qb) {
-                    f32x16 st;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) st[r] = 0.f;
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        st = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, kl[s]), __builtin_bit_cast(f16x8, qh[qb][s]), st, 0, 0, 0);
-                        st = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, kh[s]), __builtin_bit_cast(f16x8, ql[qb][s]), st, 0, 0, 0);
-                        st = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, kh[s]), __builtin_bit_cast(f16x8, qh[qb][s]), st, 0, 0, 0);
-                    }
-                    float tmax = kNegInf;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int kbit = (r & 3) + 8 * (r >> 2) + 4 * h;
-                        const float v = ((valid >> kbit) & 1u) ? st[r] * sscale : kNegInf;
-                        st[r] = v;
-                        tmax = fmaxf(tmax, v);
-                    }
-                    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-                    const float m_new = fmaxf(m[qb], tmax);
-                    const float alpha = __builtin_amdgcn_exp2f(m[qb] - m_new);
-                    float psum = 0.f;
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-#pragma unroll
-                        for (int j2 = 0; j2 < 4; ++j2) {
-                            const float e0 = __builtin_amdgcn_exp2f(st[8 * u + 2 * j2] - m_new);
-                            const float e1 = __builtin_amdgcn_exp2f(st[8 * u + 2 * j2 + 1] - m_new);
-                            psum += e0;
-                            psum += e1;
-                            const f16x2 hh = {(_Float16)(e0 * kPScale), (_Float16)(e1 * kPScale)};
-                            const f16x2 ll = {(_Float16)(e0 * kPScale - (float)hh[0]), (_Float16)(e1 * kPScale - (float)hh[1])};
-                            ph[qb][u][j2] = __builtin_bit_cast(uint32_t, hh);
-                            pl[qb][u][j2] = __builtin_bit_cast(uint32_t, ll);
-                        }
-                    l[qb] = l[qb] * alpha + psum;
-                    if (__builtin_amdgcn_ballot_w64(m_new > m[qb]) != 0ull) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int qa = (r & 3) + 8 * (r >> 2);
-                            const float a0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, alpha), qa));
-                            const float a1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, alpha), qa + 4));
-                            const float a = h ? a1 : a0;
-                            o0[qb][r] *= a;
-                            o1[qb][r] *= a;
-                        }
-                    }
-                    m[qb] = m_new;
-                }
-            }
-            // phase 2, every query block: P . V (the products of a block in the order of the kernel above)
-            {
-                u32x4 vh[2][2], vl[2][2];
-#pragma unroll
-                for (int c = 0; c < 2; ++c)
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        vh[c][u] = *reinterpret_cast<const u32x4*>(vb + c * 32 * kRow + 16 * u);
-                        vl[c][u] = *reinterpret_cast<const u32x4*>(vb + (64 + c * 32) * kRow + 16 * u);
-                    }
-#pragma unroll
-                for (int qb = 0; qb < QB; ++qb)
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        o0[qb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, pl[qb][u]), __builtin_bit_cast(f16x8, vh[0][u]), o0[qb], 0, 0, 0);
-                        o0[qb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ph[qb][u]), __builtin_bit_cast(f16x8, vl[0][u]), o0[qb], 0, 0, 0);
-                        o0[qb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ph[qb][u]), __builtin_bit_cast(f16x8, vh[0][u]), o0[qb], 0, 0, 0);
-                        o1[qb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, pl[qb][u]), __builtin_bit_cast(f16x8, vh[1][u]), o1[qb], 0, 0, 0);
-                        o1[qb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ph[qb][u]), __builtin_bit_cast(f16x8, vl[1][u]), o1[qb], 0, 0, 0);
-                        o1[qb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ph[qb][u]), __builtin_bit_cast(f16x8, vh[1][u]), o1[qb], 0, 0, 0);
-                    }
-            }
-        }
-        if (more) store_tile((jt + 1) & 1);       // the other buffer: every wave left it at the barrier that ended tile jt - 1
-        __syncthreads();
-    }
-    if (!active) return;
-#pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {
-        const float lsum = l[qb] + __shfl_xor(l[qb], 32, 64);
-        const float inv = lsum > 0.f ? 1.0f / (lsum * kPScale * kF16ActScale) : 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int qa = (r & 3) + 8 * (r >> 2);
-            const float s0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inv), qa));
-            const float s1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, inv), qa + 4));
-            const float sc = h ? s1 : s0;
-            const int q = q0 + 32 * qb + qa + 4 * h;
-            if (q < L) {
-                const int64_t trow = row0 + q;
-                store_planes(ctxp + plane_index(trow, head * 64 + i, rows), c_plane, ns, o0[qb][r] * sc);
-                store_planes(ctxp + plane_index(trow, head * 64 + 32 + i, rows), c_plane, ns, o1[qb][r] * sc);
             }
         }
     }

@@ -278,11 +278,9 @@ int run_retrieve(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ,
         const int groups = (B + kMqQueries - 1) / kMqQueries;
         int gx = mq ? std::max(1, std::min(n_tiles, std::min(256, std::max(512 / groups, 16))))
                           : std::max(1, std::min(n_tiles / 2 + 1, std::min(256, std::max(1024 / std::max(1, B), 16))));
-        const int gx_dbg = CLB_KNOB("CLB_DEBUG_S1_GX", 0);
-        if (gx_dbg > 0 && !mq) gx = std::min(gx_dbg, n_tiles / 2 + 1);
         // 16+ queries and a score table to write: two teams of four waves per work-group, 16 queries per staged tile
         // (centroid_top_bf16x3_teams_kernel); one 8-wave work-group per CU
-        const bool teams = mq && want_half && B >= kTeamQueries && CLB_KNOB("CLB_DEBUG_S1_TEAMS", 1);
+        const bool teams = mq && want_half && B >= kTeamQueries;
         const int team_groups = (B + kTeamQueries - 1) / kTeamQueries;
         if (teams) gx = std::max(1, std::min(n_tiles, std::min(256, std::max(256 / team_groups, 16))));
         const bool x1 = teams && (s->s1_x1 == 1 || (s->s1_x1 < 0 && s->bounds_synced)) && s->cent_f16.p && s->dc_f16 > 0.f;
@@ -399,7 +397,7 @@ int mark_and_compact(clb_searcher* s, Workspace& w, hipStream_t st, int B, int T
     // it saves -- unless the lists are sorted by passage id: then slice_bounds_kernel cuts every list at the slice
     // boundaries first (binary searches) and larger slices keep the number of work-groups down.  For a few queries the
     // 64 one-list work-groups of the atomic path finish sooner (one query: 8 us against 27)
-    const bool sliced = (nslices <= 16 || s->ivf_sorted) && B >= 8 && !CLB_KNOB("CLB_DEBUG_ATOMIC_MARK", 0);
+    const bool sliced = (nslices <= 16 || s->ivf_sorted) && B >= 8;
     {
         Timed t(s, KID_MARK, st);
         if (sliced && nslices <= 16)     // mark + per-block counts, the bitmap slice of a work-group in LDS (no global atomics)
@@ -534,7 +532,7 @@ int run_retrieve_general_batched(clb_searcher* s, Workspace& w, hipStream_t st, 
 int run_search_general(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, int B, int T, int nprobe, int k,
                        int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand) {
     s->prof.chain = nullptr;
-    if (general_batched_ok(s, T) && !CLB_KNOB("CLB_DEBUG_GENERIC_SCALAR", 0)) {
+    if (general_batched_ok(s, T)) {
         // batched: every stage is one launch for the B queries (the loop below: ~12 launches per query, the scoring
         // kernel a chain of dependent loads)
         CLB_TRY(run_retrieve_general_batched(s, w, st, dQ, B, T, nprobe));
@@ -570,7 +568,7 @@ int run_search_general(clb_searcher* s, Workspace& w, hipStream_t st, const floa
     CLB_TRY(w.g_scratch.ensure(sizeof(float) * grid * max_len * s->dim));
     for (int b = 0; b < B; ++b) {
         CLB_TRY(run_retrieve_general(s, w, st, dQ, b, T, nprobe));
-        if (T <= 16 * kGenericMaxTokenGroups && s->dim % 4 == 0 && !CLB_KNOB("CLB_DEBUG_GENERIC_SCALAR", 0))
+        if (T <= 16 * kGenericMaxTokenGroups && s->dim % 4 == 0)
             // fp32 MFMA, one wave per passage (the canonical arithmetic of the scalar kernel, bit for bit)
             hipLaunchKernelGGL(generic_score_mfma_kernel, dim3(grid), dim3(256), sizeof(float) * ((size_t)1 << s->nbits), st,
                                s->centroids.as<float>(), s->weights.as<float>(), s->codes0.as<uint32_t>(),
@@ -612,12 +610,8 @@ constexpr size_t kWideSelectCap = 131072;
 
 // Pass 1 over every candidate of the batch: the gather form by the index's code statistics, the row format by the batch's table
 void launch_pass1(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, dim3 grid, int B, int T) {
-#if CLB_APPROX_WAVES <= 12
-    auto kern = w.cell8 ? (s->gather_lds ? score_approx32_kernel<false, 0, 1, 0, true> : score_approx32_kernel<false, 0, 0, 0, true>)
-                        : (s->gather_lds ? score_approx32_kernel<false, 0, 1, 0, false> : score_approx32_kernel<false, 0, 0, 0, false>);
-#else
-    auto kern = w.cell8 ? score_approx32_kernel<false, 0, 0, 0, true> : score_approx32_kernel<false, 0, 0, 0, false>;
-#endif
+    auto kern = w.cell8 ? (s->gather_lds ? score_approx32_kernel<false, 1, true> : score_approx32_kernel<false, 0, true>)
+                        : (s->gather_lds ? score_approx32_kernel<false, 1, false> : score_approx32_kernel<false, 0, false>);
     hipLaunchKernelGGL(kern, grid, dim3(kApproxThreads), 0, st, s->weights.as<float>(),
                        s->codeinv.as<uint32_t>(), s->residuals.as<uint8_t>(), s->cbits, s->inv_lo, s->inv_step, dQ,
                        w.cell8 ? w.cells8.as<uint32_t>() : w.cells_q.as<uint32_t>(), w.cand_hdr.as<uint2>(), w.ncand.as<int>(),
@@ -637,15 +631,10 @@ int launch_select(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ
     if (!wide) {
         ApproxConsts ac = s->approx_consts;
         ac.dc_max = bound_dc(s, w);
-        // tuning builds: CLB_DEBUG_EPS_T_ADD_1E6 widens the per-(token, embedding) bound by about that many millionths
-        // through the inv_norm quantisation term (1.01 * inv_qerr * qn * (cn + rn)) -- what a coarser score-table format
-        // would cost pass 2 (lists and row masks grow), measured on the real pipeline with correct results
-        if (const int add = CLB_KNOB("CLB_DEBUG_EPS_T_ADD_1E6", 0)) ac.inv_qerr += add * 1e-6f / (1.01f * (ac.cn_max + ac.rn_max));
         hipLaunchKernelGGL(select_margin_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), dQ, T, k,
                            w.cand_cap, ac, w.list.as<int>(), w.nlist.as<int>(), w.thresh.as<float>(),
                            w.eps_pair.as<float>(), tau_in, coarse_tau ? 1 : 0,
-                           w.have_range ? (const float4*)w.tscale.as<float4>() : (const float4*)nullptr, w.cell8 ? 1 : 0,
-                           CLB_KNOB("CLB_DEBUG_SELECT_STOP", 0));
+                           w.have_range ? (const float4*)w.tscale.as<float4>() : (const float4*)nullptr, w.cell8 ? 1 : 0);
         return CLB_OK;
     }
     CLB_TRY(w.wsel.ensure(sizeof(WideSel) * B));
@@ -699,60 +688,18 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, i
     if (two_pass) {
         {
             Timed t(s, KID_SCORE_APPROX, st);
-            const int wgpg = CLB_KNOB("CLB_DEBUG_APPROX_WGPG", 32);   // x 8 XCD groups: one 12-wave work-group per CU
+            constexpr int kWgPerGroup = 32;   // x 8 XCD groups: one 12-wave work-group per CU
             // Grid: XCD-affine 1-D launch (all work-groups of an XCD share one query's score table in L2) for
             // large candidate sets; for small ones (a shard of a multi-GPU run: < ~6 k candidate passages per
             // query, estimated from the mean IVF list) a (G, B) launch whose few waves per query each get a long
             // run of passages -- the pipeline fill otherwise dominates.
-            const int approx_2d = CLB_KNOB("CLB_DEBUG_APPROX_2D", -1);
             const double est_cand = 0.5 * T * nprobe * (double)s->n_emb / (double)std::max<int64_t>(1, s->K);
             // work-groups per query of the (G, B) launch (0 = the 1-D launch): enough to fill the chip for small batches,
             // eight for large ones (measured at 4 and 8 shards, B = 8 ... 256: one or two per query cost 12 % of the pass
             // at B = 256, sixteen and more cost as much at B = 32)
-            int gxq = est_cand < 6000.0 ? std::max(8, 256 / B) : 0;
-            if (approx_2d >= 0) gxq = approx_2d > 0 ? std::max(1, approx_2d / B) : 0;
-            const dim3 approx_grid = gxq > 0 && B > 1 ? dim3(gxq, B) : dim3(8 * wgpg);
-#define CLB_LAUNCH_APPROX(ABL)                                                                                        \
-    hipLaunchKernelGGL((score_approx32_kernel<false, ABL>), approx_grid, dim3(kApproxThreads), 0, st, s->weights.as<float>(), \
-                       s->codeinv.as<uint32_t>(), s->residuals.as<uint8_t>(), s->cbits, s->inv_lo, s->inv_step, dQ,  \
-                       w.cells_q.as<uint32_t>(), w.cand_hdr.as<uint2>(), w.ncand.as<int>(), w.scores.as<float>(), \
-                       (int)s->K, T, B, w.cand_cap, w.tokmax.as<uint16_t>(), (const int*)nullptr,                    \
-                       (const int*)nullptr, (const float*)nullptr, (unsigned long long*)nullptr)
-#ifdef CLB_ABLATIONS
-            if (CLB_KNOB("CLB_DEBUG_APPROX_PIPE", 0)) {     // round-3 experiment: epilogue of step i-1 under step i's MFMAs (slower: profiles/r03_experiments.md)
-#if CLB_APPROX_WAVES <= 12
-                auto kern = s->gather_lds ? score_approx32_kernel<false, 0, 1, 1> : score_approx32_kernel<false, 0, 0, 1>;
-#else
-                auto kern = score_approx32_kernel<false, 0, 0, 1>;
-#endif
-                hipLaunchKernelGGL(kern, approx_grid, dim3(kApproxThreads), 0, st, s->weights.as<float>(),
-                                   s->codeinv.as<uint32_t>(), s->residuals.as<uint8_t>(), s->cbits, s->inv_lo, s->inv_step, dQ,
-                                   w.cells_q.as<uint32_t>(), w.cand_hdr.as<uint2>(), w.ncand.as<int>(), w.scores.as<float>(),
-                                   (int)s->K, T, B, w.cand_cap, w.tokmax.as<uint16_t>(), (const int*)nullptr,
-                                   (const int*)nullptr, (const float*)nullptr, (unsigned long long*)nullptr, (const float4*)nullptr);
-            } else
-            switch (CLB_KNOB("CLB_DEBUG_APPROX_VARIANT", 0)) {
-                case 1: CLB_LAUNCH_APPROX(1); break;
-                case 2: CLB_LAUNCH_APPROX(2); break;
-                case 3: CLB_LAUNCH_APPROX(3); break;
-                case 4: CLB_LAUNCH_APPROX(4); break;
-                case 5: CLB_LAUNCH_APPROX(5); break;
-                case 6: CLB_LAUNCH_APPROX(6); break;
-                case 7: CLB_LAUNCH_APPROX(7); break;
-                case 8: CLB_LAUNCH_APPROX(8); break;
-                case 10:     // the fused row mask writes the slot-indexed row-mask buffer (4 words per candidate slot)
-                    hipLaunchKernelGGL((score_approx32_kernel<false, 10>), approx_grid, dim3(kApproxThreads), 0, st, s->weights.as<float>(),
-                                       s->codeinv.as<uint32_t>(), s->residuals.as<uint8_t>(), s->cbits, s->inv_lo, s->inv_step, dQ,
-                                       w.cells_q.as<uint32_t>(), w.cand_hdr.as<uint2>(), w.ncand.as<int>(), w.scores.as<float>(),
-                                       (int)s->K, T, B, w.cand_cap, w.tokmax.as<uint16_t>(), (const int*)nullptr,
-                                       (const int*)nullptr, (const float*)nullptr, w.rowmask.as<unsigned long long>());
-                    break;
-                default: launch_pass1(s, w, st, dQ, approx_grid, B, T);
-            }
-#else
+            const int gxq = est_cand < 6000.0 ? std::max(8, 256 / B) : 0;
+            const dim3 approx_grid = gxq > 0 && B > 1 ? dim3(gxq, B) : dim3(8 * kWgPerGroup);
             launch_pass1(s, w, st, dQ, approx_grid, B, T);
-#endif
-#undef CLB_LAUNCH_APPROX
         }
         {
             Timed t(s, KID_SELECT, st);
@@ -768,14 +715,14 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, i
         CLB_HIP(hipGetLastError());
         return CLB_OK;
     }
-    const bool subset = list && !CLB_KNOB("CLB_DEBUG_NO_SUBSET", 0);   // two-pass mode: re-score only the rows that matter
+    const bool subset = list != nullptr;   // two-pass mode: re-score only the rows that matter
     if (subset) {
         Timed t(s, KID_ROWS, st);
         // the pass-1 pipeline again, over the listed passages only: marks the rows that can hold a token maximum
-        const int rows_gx = CLB_KNOB("CLB_DEBUG_ROWS_GX", 256);
-        const dim3 rows_grid = B > 1 ? dim3(std::max(1, rows_gx / B), B) : dim3(8 * 32);
+        constexpr int kRowsGx = 256;
+        const dim3 rows_grid = B > 1 ? dim3(std::max(1, kRowsGx / B), B) : dim3(8 * 32);
         // (the row sweep keeps the VGPR gather: its ~1 200 passages per query are faster with it on every workload measured)
-        auto rows_kernel = w.cell8 ? score_approx32_kernel<true, 0, 0, 0, true> : score_approx32_kernel<true, 0, 0, 0, false>;
+        auto rows_kernel = w.cell8 ? score_approx32_kernel<true, 0, true> : score_approx32_kernel<true, 0, false>;
         hipLaunchKernelGGL(rows_kernel, rows_grid, dim3(kApproxThreads), 0, st, s->weights.as<float>(),
                            s->codeinv.as<uint32_t>(), s->residuals.as<uint8_t>(), s->cbits, s->inv_lo, s->inv_step, dQ,
                            w.cell8 ? w.cells8.as<uint32_t>() : w.cells_q.as<uint32_t>(), w.cand_hdr.as<uint2>(), w.ncand.as<int>(),
@@ -784,11 +731,10 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, i
     }
     {
         Timed t(s, KID_SCORE_EXACT, st);
-        const int gxl = CLB_KNOB("CLB_DEBUG_EXACT_GX", 1024);
-        const int gx = list ? std::max(1, gxl / B) : std::max(1, 2048 / B);
-        const int flat_gx = CLB_KNOB("CLB_DEBUG_FLAT_GX", 768);   // one resident round at 3 work-groups per CU
+        const int gx = list ? std::max(1, 1024 / B) : std::max(1, 2048 / B);
+        constexpr int kFlatGx = 768;   // one resident round at 3 work-groups per CU
         if (subset) {
-            hipLaunchKernelGGL(score_exact_flat_kernel, dim3(std::max(1, flat_gx / B), B), dim3(256), 0, st, s->centroids.as<float>(),
+            hipLaunchKernelGGL(score_exact_flat_kernel, dim3(std::max(1, kFlatGx / B), B), dim3(256), 0, st, s->centroids.as<float>(),
                                s->weights.as<float>(), s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(),
                                w.cand_hdr.as<uint2>(), dQ, w.scores.as<float>(), T, w.cand_cap, list, nlist,
                                w.rowmask.as<unsigned long long>());
@@ -805,7 +751,7 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, i
         allow_large_topk_lds();
         // two-pass mode: the ~1.2 k listed passages of a query are ranked by kRankBlocks work-groups (no sorting network);
         // a query whose list is longer than kRankMax falls through to the one-work-group select + sort
-        const int ranked = list != nullptr && !CLB_KNOB("CLB_DEBUG_NO_RANK", 0);
+        const int ranked = list != nullptr;
         if (ranked)
             hipLaunchKernelGGL(topk_rank_kernel, dim3(kRankBlocks, B), dim3(1024), 0, st, w.scores.as<float>(),
                                w.cand.as<uint32_t>(), w.ncand.as<int>(), list, nlist, k, w.cand_cap, s->pid_offset,
@@ -831,11 +777,7 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, i
 
 extern "C" {
 
-#ifdef CLB_ABLATIONS
-const char* clb_version(void) { return "colbert_hip 0.1 (gfx950, tuning build: ablation variants and comparison kernels)"; }
-#else
 const char* clb_version(void) { return "colbert_hip 0.1 (gfx950)"; }
-#endif
 const char* clb_last_error(void) { return clb::last_error().c_str(); }
 int clb_device_count(void) {
     int n = 0;
@@ -953,7 +895,7 @@ static int searcher_create_impl(int device, int64_t dim, int nbits, int64_t K, c
     if (herr & 2) return bail(fail(CLB_EDOMAIN, "All the codes must be in the valid range of centroid IDs!"));
     s->ivf_sorted = !(herr & 4);
 
-    if (!s->generic && n_emb > 0 && !CLB_KNOB("CLB_DEBUG_NO_SORT", 0)) {
+    if (!s->generic && n_emb > 0) {
         // Order every passage's embeddings by centroid code (results cannot change: MaxSim maximises over a passage's
         // embeddings; row masks, headers and the IVF are positional or per passage).  Equal and neighbouring codes then
         // sit in adjacent lanes of a pass-1 step: their 64-byte score rows coalesce into fewer, larger requests.
@@ -998,7 +940,6 @@ static int searcher_create_impl(int device, int64_t dim, int nbits, int64_t K, c
         if ((rc = s->cent_f16.alloc(sizeof(uint16_t) * dim * K))) return bail(rc);
         hipLaunchKernelGGL(to_f16_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, s->stream,
                            s->centroids.as<float>(), s->cent_f16.as<uint16_t>(), nel);
-        if (const char* g = CLB_ENV("COLBERT_S1_PRODUCTS")) s->s1_x1 = strcmp(g, "1") == 0;      // "1" / "3": comparison runs
     }
     s->cbits = 1;
     while (((int64_t)1 << s->cbits) < K) ++s->cbits;
@@ -1023,7 +964,6 @@ static int searcher_create_impl(int device, int64_t dim, int nbits, int64_t K, c
         // ... and only pays when the query's score table (64 B per centroid) does not fit the 4-MB L2 of an XCD: with a
         // resident table the two forms are equal within 2 % (built index, K = 32 768: 0.663 / 0.668 ms)
         s->gather_lds = s->code_adjacency < 0.2 && (int64_t)K * 64 > ((int64_t)4 << 20);
-        if (const char* g = CLB_ENV("COLBERT_PASS1_GATHER")) s->gather_lds = strcmp(g, "vgpr") != 0;   // "vgpr" / "lds": comparison runs
     }
     if (s->approx_ok) {
         if ((rc = s->codeinv.alloc(sizeof(uint32_t) * (n_emb + kStepRows)))) return bail(rc);

@@ -384,9 +384,8 @@ int clb_encoder_set_gemm_mode(clb_encoder* e, int mode);
  * layers on the 16-bit matrix pipe, on fp16 planes the Q/K/V projection writes for it (three exact products per fp32
  * product; batches of more than 64 tokens), else fp32 MFMA (all score tiles resident up to 64 keys, online softmax beyond);
  * 1 = fp32 MFMA, register-resident for every length; 2 = the three-kernel path (scores in memory; always taken for other head
- * sizes); 3 = mode 0 on the fp32 MFMA whatever the GEMM mode; 5 = mode 0 with the K / V tiles of a (sequence, head) staged once
- * in LDS for all its query blocks instead of every wave loading its own (round 5: bit-identical to 0, measured slower) --
- * 1 to 5 exist for comparison. */
+ * sizes); 3 = mode 0 on the fp32 MFMA whatever the GEMM mode -- 1 to 3 exist for comparison.  5 (the K / V tiles of a
+ * (sequence, head) staged once in LDS: bit-identical to 0 and slower) was retired and returns CLB_EUNSUPPORTED. */
 int clb_encoder_set_attention_mode(clb_encoder* e, int mode);
 /* LayerNorm folded around the Linear layers (f16x3 only): the Linear that produces a LayerNorm's input stores the raw rows and
  * their partial (mean, M2); the Linear that consumes it multiplies the raw rows with gamma (.) W and applies

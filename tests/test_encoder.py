@@ -155,7 +155,6 @@ def _state(bert, linear):
 # products per fp32 product (differences are summation order / < 2^-22 per product); "bf16x3" = three plane products,
 # < 2^-15 relative error per product on top of that
 # "f16x3" (round 4) = two fp16 planes per (power-of-two scaled) operand, three products: held to bf16x6's tolerances
-TUNING_BUILD = b"tuning build" in clb.lib().clb_version()      # make ABLATIONS=1: the comparison kernels exist
 GEMM_TOL = {"f32": 2e-4, "bf16x6": 2e-4, "f16x3": 2e-4, "bf16x3": 6e-4}
 GEMM_TOL_BASE = {"f32": 1e-3, "bf16x6": 1e-3, "f16x3": 1e-3, "bf16x3": 6e-3}
 
@@ -293,17 +292,10 @@ def test_fused_attention_long_sequences(L):
     alt = enc.doc((ids0.T + 1).astype(np.int32), mask.T)
     enc.close()
     assert np.abs(g16 - alt).transpose(2, 1, 0)[mask].max() < 1e-4
-    # round 5: the K / V tiles of a (sequence, head) staged once in LDS for all its query blocks (attention="fused_lds",
-    # from 33 tokens on) against every wave loading its own -- the same products in the same order: identical bits
-    # (a comparison kernel: in tuning builds of the library only -- the product library refuses the mode)
-    if TUNING_BUILD:
-        enc = clb.BertEncoder(w, bcfg, dim=32, gemm="f16x3", attention="fused_lds")
-        per_wave = enc.doc((ids0.T + 1).astype(np.int32), mask.T)
-        enc.close()
-        assert np.array_equal(g16.view(np.uint32), per_wave.view(np.uint32))
-    else:
-        with pytest.raises(clb.Unsupported):
-            clb.BertEncoder(w, bcfg, dim=32, gemm="f16x3", attention="fused_lds")
+    # round 5's K / V tiles staged once in LDS for all query blocks of a (sequence, head) (attention="fused_lds") were
+    # retired: the library refuses the mode
+    with pytest.raises(clb.Unsupported):
+        clb.BertEncoder(w, bcfg, dim=32, gemm="f16x3", attention="fused_lds")
 
 
 @pytest.mark.gpu
@@ -626,12 +618,6 @@ def test_packed_passage_batches_match_padded_ones(tok):
             if lo <= pid < hi:
                 assert torch.equal(x[off[pid] - off[lo]:off[pid + 1] - off[lo]], smp[soff[j]:soff[j + 1]])
     assert packed.reused_passages == 4 and packed._cache is None      # released with the last chunk
-    # packed sequences of different lengths through the LDS-shared K / V tiles == every wave loading its own, bit for bit
-    if TUNING_BUILD:
-        enc_pw = clb.BertEncoder(w, bcfg, dim=64, tokenizer=tok, config=config, attention="fused_lds")
-        a_pw = EncoderSource(enc_pw, collection, 0, packed=True).encode_pids(order)
-        assert torch.equal(a.view(torch.int32), a_pw.view(torch.int32))
-        enc_pw.close()
     # the host entry point (clb_encode_docs: what the Julia shim calls) packs by itself -- also a mask with holes, whose
     # attended tokens keep their positions; reference: the same call on an encoder that cannot pack (fp32-MFMA attention)
     ref_enc = clb.BertEncoder(w, bcfg, dim=64, tokenizer=tok, config=config, attention="fused_f32")

@@ -1,11 +1,8 @@
 #!/usr/bin/env python3
-"""Sweeps the CLB_DEBUG_* knobs / ablation variants of the tuning build (make -C colbert.jl_amd/csrc ABLATIONS=1)
-over bench.py's workload in ONE process: per setting, the average HIP-event time of every search kernel.
+"""Sweeps the searcher's mode setters (--api) over bench.py's workload in ONE process: per setting, the average HIP-event
+time of every search kernel.  COLBERT_HIP_LIB selects another build of the library (e.g. a parent commit's, for A/B runs).
 
-    COLBERT_HIP_LIB=colbert.jl_amd/csrc/libcolbert_hip_abl.so python tools/abl_sweep.py [--docs N] \
-        --set CLB_DEBUG_APPROX_VARIANT=0,1,2 --set CLB_DEBUG_APPROX_WGPG=64,128
-
-Results of ablation variants are wrong by design; nothing here is a product path."""
+    python tools/abl_sweep.py [--docs N] --api score_rows=0,1 --api pass1_gather=0,1"""
 import argparse
 import itertools
 import json
@@ -22,10 +19,8 @@ def main():
     ap.add_argument("--docs", type=int, default=1_000_000)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--set", action="append", default=[], help="NAME=v1,v2,...")
     ap.add_argument("--api", action="append", default=[],
-                    help="score_rows=0,1 / pass1_gather=0,1 / centroid_products=1,3: product-library setters swept like --set "
-                         "(results stay correct; works on the product build)")
+                    help="NAME=v1,v2,...: score_rows=0,1 / pass1_gather=0,1 / centroid_products=1,3 (Searcher.set_NAME)")
     ap.add_argument("--uniform-codes", action="store_true")
     ap.add_argument("--built-docs", type=int, default=0,
                     help="instead of the generator-made index: this many passages of mixture embeddings through the repo's own "
@@ -70,8 +65,8 @@ def main():
                                               "note": "(max - min over the K centroids of Q_t.c) / 510, per (query, token)"}}), flush=True)
         del Cd
     run = DeviceSearch(s, T, B, k, 2)
-    names = [x.split("=")[0] for x in args.set] + ["api:" + x.split("=")[0] for x in args.api]
-    values = [x.split("=")[1].split(",") for x in args.set + args.api]
+    names = ["api:" + x.split("=")[0] for x in args.api]
+    values = [x.split("=")[1].split(",") for x in args.api]
     # the first measurement of a process used to come out ~8 % slow (0.72 against 0.665 ms for the same pass 1: the device
     # has just spent seconds in host-side index generation and idles at a low clock): one second of untimed batches first
     import time
@@ -82,10 +77,7 @@ def main():
         torch.cuda.synchronize()
     for combo in itertools.product(*values) if values else [()]:
         for n, v in zip(names, combo):
-            if n.startswith("api:"):
-                getattr(s, "set_" + n[4:])(int(v))
-            else:
-                os.environ[n] = v
+            getattr(s, "set_" + n[4:])(int(v))
         for i in range(3):
             run(Qdev[i * B:(i + 1) * B])
         torch.cuda.synchronize()

@@ -27,7 +27,7 @@ def main():
     t0 = time.time()
     src = synthetic.DeviceMixtureSource(seed=61, n_docs=args.docs, device=dev)
     index, rec = indexer.index_device(src, nbits=2, kmeans_niters=args.iters, seed=62, log=lambda m: print(m, flush=True))
-    # the group lists of the nearest-centroid search: one fp16 product per fp32 product (nearest_top_f16_kernel, round 5) unless
+    # the group lists of the nearest-centroid search: one fp16 product per fp32 product (nearest_top_f16_dma_kernel, round 5) unless
     # COLBERT_NEAREST_PRODUCTS=3 asks for the three-product bf16 split; both run at the same dense MFMA peak
     products = 3 if os.environ.get("COLBERT_NEAREST_PRODUCTS") == "3" else 1
     what = "bf16, 3 products per fp32 product" if products == 3 else "fp16, 1 product per fp32 product"

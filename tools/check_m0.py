@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Build check for the hand-issued LDS-DMA blocks (global_load_lds_dwordx4 behind `s_mov_b32 m0, ...` in inline asm:
-approx_kernels.hpp score_approx32_kernel's GL = 1 gather, encoder_kernels.hpp gemm_planes_kernel / gemm_planes2_kernel).
+approx_kernels.hpp score_approx32_kernel's GL = 1 gather, encoder_kernels.hpp gemm_planes2_kernel, codec_kernels.hpp nearest_top_f16_dma_kernel).
 
 hipcc does not accept M0 in an asm clobber list (a reserved register), so those blocks write M0 without telling the
 compiler.  That is safe only while NOTHING ELSE in the same kernel keeps a value in M0 -- a builtin that lowers to

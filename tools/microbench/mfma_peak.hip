@@ -1,6 +1,6 @@
 // What the matrix pipe sustains chip-wide on v_mfma_f32_32x32x16_f16 (2 waves per SIMD, four independent accumulators,
 // operands with fp16 bit patterns of moderate magnitude), alone and with the plane GEMM's LDS-read mix next to it
-// (8 ds_read_b128 per 12 MFMAs, conflict-free addresses) -- the ceiling gemm_planes_kernel's compute side is measured against.
+// (8 ds_read_b128 per 12 MFMAs, conflict-free addresses) -- the ceiling gemm_planes2_kernel's compute side is measured against.
 //   hipcc --offload-arch=gfx950 -O3 mfma_peak.hip -o mfma_peak
 #include <hip/hip_runtime.h>
 #include <cstdio>

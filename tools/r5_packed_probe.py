@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Packed passage batches of real lengths (~86 tokens) through the encoder: ms per call and passages/s for a given number of
-passages per call.  Environment knobs of the library (COLBERT_ENC_ATT_QB, COLBERT_ENC_LNFOLD ...) are read once per process:
+passages per call.  Environment knobs of the encoder (COLBERT_ENC_LNFOLD ...) are read once per process:
 run one process per setting.   python tools/r5_packed_probe.py [passages ...]"""
 import json
 import os
