@@ -8,6 +8,6 @@ from . import codec, storage, synthetic, tokenization  # noqa: F401
 from ._lib import (ArgumentError, BoundsError, ColBERTError, DimensionMismatch, DomainError, HipError,  # noqa: F401
                    Unsupported, build, declared_symbols, lib)
 from .config import ColBERTConfig  # noqa: F401
-from .encoder import BertEncoder  # noqa: F401
+from .encoder import BertEncoder, encoder_plan  # noqa: F401
 from .indexer import Indexer, PrecomputedEncoder, index, train  # noqa: F401
 from .searcher import Searcher, TextSearch, search  # noqa: F401

@@ -59,6 +59,12 @@ struct clb_encoder {
     std::vector<hipEvent_t> prof_pool;
     double prof_ms[8] = {0};
     int64_t prof_launches[8] = {0};
+    // the tile plan of every Linear (and the attention kernel) of the LAST forward, in launch order (clb_encoder_last_plans):
+    // written on the host while the launches are enqueued
+    struct PlanRec { int stage; int64_t v[CLB_ENCODER_PLAN_FIELDS]; };
+    std::vector<PlanRec> plan_log;
+    int cur_stage = 0, cur_layer = -1;  // what forward() is enqueueing (EncTimed sets the stage)
+    bool cur_packed = false;
 };
 
 namespace {
@@ -74,6 +80,7 @@ struct EncTimed {
         return hipEventCreate(&v) == hipSuccess ? v : nullptr;
     }
     EncTimed(clb_encoder* e_, int id_, hipStream_t st_) : e(e_), id(id_), st(st_) {
+        e->cur_stage = id;
         if (!e->prof_on) return;
         a = get(e); b = get(e);
         if (a && b) (void)hipEventRecord(a, st);
@@ -259,27 +266,29 @@ static PlanCfg pick_long_tile(int M, int N, bool allow_256, bool allow_128x256) 
     return best;
 }
 
-// A planes (M x K) . W planes (N x K)^T -> C fp32 and / or Cp planes, epilogue bias / GELU / residual, optional LayerNorm
-// of the output (then both C and, if given, Cp hold the normalised rows).  part: split-K scratch (8 * M * N floats) or null.
+// What decides the plan of a Linear on planes: the shape, the epilogue and what surrounds the product.  part: split-K scratch is
+// there; ln: a LayerNorm of the output follows; att: the output goes to the fp16-plane attention (EPI_QKV_ATT); fold: a LayerNorm
+// is folded around the product (fold_stats: it produces row statistics, fold_u: it consumes them through the vector u)
+struct PlanIn { int gemm_mode, M, N, K, epi; bool part, ln, att, fold, fold_stats, fold_u; };
 inline int plane_format(int gemm_mode) { return gemm_mode == 3 ? PF_F16X2 : gemm_mode == 1 ? PF_BF16X2 : PF_BF16X3; }
 
-// wscale: the power of two the weight planes were scaled by (PF_F16X2; 1 otherwise)
-void linear_planes(clb_encoder* e, hipStream_t st, const uint16_t* Ap, int64_t a_plane, const uint16_t* Wp, float wscale,
-                   float* C, uint16_t* Cp, int64_t c_plane, const float* bias, const float* R, int M, int N, int K, int epi,
-                   float* part, const LnArgs* ln, const AttOut* att = nullptr, const LnFold* lf = nullptr, int64_t b_plane = 0) {
-    const int fmt = plane_format(e->gemm_mode);
-    const int NS = fmt == PF_BF16X3 ? 3 : 2;
-    const float out_scale = fmt == PF_F16X2 ? 1.0f / (kF16ActScale * wscale) : 1.0f;
+// The tile, ring depth and K slices of a Linear on planes: a pure function (no device), so that tests can ask which plan a shape
+// takes (clb_debug_encoder_plan) -- linear_planes launches what this returns.
+static PlanCfg plan_linear(const PlanIn& p) {
+    const int M = p.M, N = p.N, K = p.K, epi = p.epi;
+    const bool att = p.att;
+    bool part = p.part;
+    const int NS = plane_format(p.gemm_mode) == PF_BF16X3 ? 3 : 2;
     auto wgs = [&](int bm, int bn) { return (int64_t)((N + bn - 1) / bn) * ((M + bm - 1) / bm); };
     PlanCfg c;
-    if (lf) {
+    if (p.fold) {
         // a Linear with a LayerNorm folded around it: never split over K (the statistics are taken from finished rows), the
         // big-tile rule of long activations below, 128 x 128 at least when it produces statistics (a part = two 32-wide tiles
         // of one wave); the narrow projection (N = dim) only consumes: 64 x 64
         const bool wide = N % 4 == 0 && !(epi & EPI_GELU);
-        c = N <= 128 && !lf->stats_out ? PlanCfg{64, 64, 2, 1}
-            : wgs(128, 128) >= 256 ? pick_long_tile(M, N, wide && !att && !lf->u, wide) : PlanCfg{128, 128, 2, 1};
-        part = nullptr;
+        c = N <= 128 && !p.fold_stats ? PlanCfg{64, 64, 2, 1}
+            : wgs(128, 128) >= 256 ? pick_long_tile(M, N, wide && !att && !p.fold_u, wide) : PlanCfg{128, 128, 2, 1};
+        part = false;
     }
     else if (M <= 64 && part) {
         // ONE query (search(searcher, query::String, k), 32 rows): every Linear is a weight stream with one tile row.  Split
@@ -326,6 +335,35 @@ void linear_planes(clb_encoder* e, hipStream_t st, const uint16_t* Ap, int64_t a
         }
     }
     if (!part || K % (c.ks * 32) != 0) c.ks = 1;
+    return c;
+}
+
+static int plan_flags(const PlanIn& p) {
+    return (p.part ? CLB_PLAN_PART : 0) | (p.ln ? CLB_PLAN_LN : 0) | (p.att ? CLB_PLAN_ATT : 0) | (p.fold ? CLB_PLAN_FOLD : 0) |
+           (p.fold_stats ? CLB_PLAN_FOLD_STATS : 0) | (p.fold_u ? CLB_PLAN_FOLD_U : 0);
+}
+
+// the pass that sums the K slices of a split product
+enum PlanReduce { PR_NONE = 0, PR_LN4 = 1, PR_LN3 = 2, PR_LN_WIDE = 3, PR_PLAIN = 4, PR_ATT = 5 };
+static int plan_reduce(const PlanIn& p, const PlanCfg& c) {
+    if (c.ks <= 1) return PR_NONE;
+    if (p.ln && p.N <= 1024) return p.N % 4 == 0 ? PR_LN4 : p.N <= 768 ? PR_LN3 : PR_LN_WIDE;
+    return p.att ? PR_ATT : PR_PLAIN;
+}
+
+// A planes (M x K) . W planes (N x K)^T -> C fp32 and / or Cp planes, epilogue bias / GELU / residual, optional LayerNorm
+// of the output (then both C and, if given, Cp hold the normalised rows).  part: split-K scratch (8 * M * N floats) or null.
+// wscale: the power of two the weight planes were scaled by (PF_F16X2; 1 otherwise)
+void linear_planes(clb_encoder* e, hipStream_t st, const uint16_t* Ap, int64_t a_plane, const uint16_t* Wp, float wscale,
+                   float* C, uint16_t* Cp, int64_t c_plane, const float* bias, const float* R, int M, int N, int K, int epi,
+                   float* part, const LnArgs* ln, const AttOut* att = nullptr, const LnFold* lf = nullptr, int64_t b_plane = 0) {
+    const int fmt = plane_format(e->gemm_mode);
+    const int NS = fmt == PF_BF16X3 ? 3 : 2;
+    const float out_scale = fmt == PF_F16X2 ? 1.0f / (kF16ActScale * wscale) : 1.0f;
+    const PlanIn pin{e->gemm_mode, M, N, K, epi, part != nullptr, ln != nullptr, att != nullptr, lf != nullptr,
+                     lf && lf->stats_out, lf && lf->u};
+    PlanCfg c = plan_linear(pin);
+    if (lf) part = nullptr;
     GemmPArgs g{Ap, Wp, a_plane, b_plane ? b_plane : e->wp_plane, C, bias, R, Cp, c_plane, M, N, K, N, epi, c.ks, out_scale};
     if (lf) {
         g.ln_in = lf->ln_in; g.ln_parts = lf->parts; g.ln_width = lf->width; g.ln_eps = lf->eps;
@@ -347,6 +385,8 @@ void linear_planes(clb_encoder* e, hipStream_t st, const uint16_t* Ap, int64_t a
         if (lf) { (void)fail(CLB_EUNSUPPORTED, "no LayerNorm-folding GEMM for a %d x %d tile", c.bm, c.bn); return; }
         c = {64, 64, 2, c.ks}; (void)go(c);
     }
+    e->plan_log.push_back({e->cur_stage, {e->cur_layer, M, N, K, c.bm, c.bn, c.stages, c.ks, plan_reduce(pin, c),
+                                          plan_flags(pin) | (e->cur_packed ? CLB_PLAN_PACKED : 0), epi}});
     if (c.ks > 1) {
         if (ln && N <= 1024) {
             if (N % 4 == 0)
@@ -507,6 +547,7 @@ int forward(clb_encoder* e, int64_t L, int64_t N, hipStream_t st, const int32_t*
             bool sync = true, const Packed* pk = nullptr) {
     const int64_t T = pk ? pk->rows : L * N, H = e->H, I = e->I, heads = e->heads, dh = H / heads;
     const float* W = e->weights.as<float>();
+    e->plan_log.clear(); e->cur_layer = -1; e->cur_packed = pk != nullptr;
     CLB_TRY(e->x.ensure(sizeof(float) * T * H));
     CLB_TRY(e->qkv.ensure(sizeof(float) * T * 3 * H));
     const bool fused = dh == 64 && L <= 512 && e->attention_mode != 2;
@@ -584,6 +625,7 @@ int forward(clb_encoder* e, int64_t L, int64_t N, hipStream_t st, const int32_t*
     const float inv_sqrt = 1.0f / std::sqrt((float)dh);
     for (int64_t l = 0; l < e->layers; ++l) {
         const float* P_ = W + e->o_layer0 + l * e->layer_stride;
+        e->cur_layer = (int)l;
         // q, k, v projections in one GEMM: (T x H) . (3H x H)^T
         const int64_t lo = e->o_layer0 + l * e->layer_stride;       // blob offset of this layer's parameters
         const float* Pp_ = l >= 1 ? W + e->o_layer0 + (l - 1) * e->layer_stride : nullptr;     // the previous layer's parameters
@@ -626,6 +668,11 @@ int forward(clb_encoder* e, int64_t L, int64_t N, hipStream_t st, const int32_t*
             if (P) hipLaunchKernelGGL(split_planes_kernel, dim3(blocks_for(hp / 4)), dim3(256), 0, st, ctx, ctxp, T, (int)H, hp, PF, kF16ActScale);
         }
         delete t_att;
+        {   // the attention kernel of this layer: query blocks of 32 per wave (fp16 planes), key tiles, kind
+            const int kind = !fused ? 3 : att16 ? 0 : (L > 64 && e->attention_mode != 1) ? 1 : 2;
+            e->plan_log.push_back({ES_ATTENTION, {l, T, L, dh, att16 ? (L >= 128 ? 2 : 1) : 0, (L + 31) / 32, 0, 0, 0,
+                                                  (att16 ? CLB_PLAN_ATT : 0) | (pk ? CLB_PLAN_PACKED : 0), kind}});
+        }
         // attention output + residual, LayerNorm
         const LnArgs ln1{P_ + e->r_g1, P_ + e->r_b1n, e->eps}, ln2{P_ + e->r_g2, P_ + e->r_b2n, e->eps};
         { EncTimed tm(e, ES_ATTN_OUT, st);
@@ -659,6 +706,7 @@ int forward(clb_encoder* e, int64_t L, int64_t N, hipStream_t st, const int32_t*
         else linear(e, st, hb, P_ + e->r_w2, x, P_ + e->r_b2, tmp, (int)T, (int)H, (int)I, EPI_BIAS | EPI_RESID, part, &ln2); }
     }
     // ColBERT projection: Layers.Dense(hidden -> dim)
+    e->cur_layer = (int)e->layers;
     { EncTimed tm(e, ES_PROJECTION, st);
     if (fold) {         // x holds the raw output of the last FFN-out
         const LnFold lf{st2, ln_parts, 64, e->eps, LV + e->v_lin, nullptr, nullptr, nullptr};
@@ -1061,6 +1109,31 @@ int clb_encoder_error_flag_device(clb_encoder* e, void** d_flag) {
     }
     *d_flag = e->err.p;
     return CLB_OK;
+}
+
+int clb_debug_encoder_plan(int gemm_mode, int64_t M, int64_t N, int64_t K, int epi, int flags, int* out) {
+    if (!out) return fail(CLB_EARGUMENT, "clb_debug_encoder_plan: out is null");
+    if (gemm_mode < 1 || gemm_mode > 3) return fail(CLB_EARGUMENT, "clb_debug_encoder_plan: the Linear layers run on planes in GEMM modes 1 to 3");
+    if (M < 1 || N < 1 || K < 1 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX || K % 32 != 0)
+        return fail(CLB_EARGUMENT, "clb_debug_encoder_plan: M, N, K >= 1, K a multiple of 32");
+    const bool fold = (flags & CLB_PLAN_FOLD) != 0;
+    const PlanIn p{gemm_mode, (int)M, (int)N, (int)K, epi, (flags & CLB_PLAN_PART) != 0, (flags & CLB_PLAN_LN) != 0,
+                   (flags & CLB_PLAN_ATT) != 0, fold, fold && (flags & CLB_PLAN_FOLD_STATS), fold && (flags & CLB_PLAN_FOLD_U)};
+    const PlanCfg c = plan_linear(p);
+    out[0] = c.bm; out[1] = c.bn; out[2] = c.stages; out[3] = c.ks; out[4] = plan_reduce(p, c);
+    return CLB_OK;
+}
+
+int clb_encoder_last_plans(clb_encoder* e, const char** names, int64_t* records, int cap) {
+    if (!e || !names || !records || cap < 0) return -1;
+    int n = 0;
+    for (const auto& r : e->plan_log) {
+        if (n >= cap) break;
+        names[n] = kEncStageNames[r.stage];
+        for (int i = 0; i < CLB_ENCODER_PLAN_FIELDS; ++i) records[(size_t)n * CLB_ENCODER_PLAN_FIELDS + i] = r.v[i];
+        ++n;
+    }
+    return n;
 }
 
 int clb_encoder_profile_enable(clb_encoder* e, int on) {

@@ -65,6 +65,27 @@ def random_weights(bert_cfg: dict, dim: int = 128, seed: int = 0) -> np.ndarray:
     return np.concatenate(parts)
 
 
+# ---- the tile plans of the encoder's Linear layers (clb_debug_encoder_plan / clb_encoder_last_plans: test hooks) -----------
+GEMM_MODES = {"f32": 0, "bf16x3": 1, "bf16x6": 2, "f16x3": 3}
+EPI_BIAS, EPI_GELU, EPI_RESID = 1, 2, 4
+PLAN_PART, PLAN_LN, PLAN_ATT, PLAN_FOLD, PLAN_FOLD_STATS, PLAN_FOLD_U, PLAN_PACKED = 1, 2, 4, 8, 16, 32, 64
+REDUCE_NAMES = ["none", "ln4", "ln3", "ln_wide", "plain", "att"]
+PLAN_FIELDS = 11                         # CLB_ENCODER_PLAN_FIELDS
+
+
+def encoder_plan(gemm: str, M: int, N: int, K: int, epi: int = EPI_BIAS, part: bool = False, ln: bool = False,
+                 att: bool = False, fold: bool = False, fold_stats: bool = False, fold_u: bool = False) -> dict:
+    """The plan `linear_planes` picks for an (M x K) . (N x K)^T Linear: {"tile": (rows, columns), "stages", "ks", "reduce"}.
+    Pure host arithmetic -- needs no device.  part: split-K scratch is available (forward(): at most 4 096 rows; the wide
+    outputs only at most 64); ln: a LayerNorm of the output follows; att: the output feeds the fp16-plane attention; fold*:
+    a LayerNorm folded around the product, producing (`fold_stats`) or consuming (`fold_u`) row statistics."""
+    flags = ((PLAN_PART if part else 0) | (PLAN_LN if ln else 0) | (PLAN_ATT if att else 0) | (PLAN_FOLD if fold else 0) |
+             (PLAN_FOLD_STATS if fold_stats else 0) | (PLAN_FOLD_U if fold_u else 0))
+    out = (C.c_int * 5)()
+    check(lib().clb_debug_encoder_plan(C.c_int(GEMM_MODES[gemm]), i64(M), i64(N), i64(K), C.c_int(epi), C.c_int(flags), out))
+    return {"tile": (out[0], out[1]), "stages": out[2], "ks": out[3], "reduce": REDUCE_NAMES[out[4]]}
+
+
 class BertEncoder:
     def __init__(self, weights: np.ndarray, bert_cfg: dict, dim: int = 128, device: int = 0,
                  tokenizer=None, config: Optional[ColBERTConfig] = None, gemm: Optional[str] = None,
@@ -86,7 +107,7 @@ class BertEncoder:
                                        C.c_float(bert_cfg.get("layer_norm_eps", 1e-12)), fptr(w), i64(w.size),
                                        C.byref(self._h)))
         self.gemm = gemm or os.environ.get("COLBERT_ENCODER_GEMM", "f16x3")
-        modes = {"f32": 0, "bf16x3": 1, "bf16x6": 2, "f16x3": 3}
+        modes = GEMM_MODES
         if self.gemm not in modes:
             raise ValueError(f"gemm must be one of {sorted(modes)}, not {self.gemm!r}")
         check(lib().clb_encoder_set_gemm_mode(self._h, modes[self.gemm]))
@@ -236,6 +257,29 @@ class BertEncoder:
         p = C.c_void_p(0)
         check(lib().clb_encoder_error_flag_device(self._h, C.byref(p)))
         return int(p.value)
+
+    def last_plans(self) -> List[dict]:
+        """What the last forward of this encoder launched, in launch order (clb_encoder_last_plans): one dict per Linear --
+        stage (the names of profile_read), layer, M, N, K, tile, stages, ks, reduce, fold / att / packed / part / ln flags -- and
+        one per attention launch (stage "attention": M rows, N = sequence length, query_blocks per wave, key_tiles, kind)."""
+        cap = 512
+        names = (C.c_char_p * cap)(); rec = (C.c_int64 * (cap * PLAN_FIELDS))()
+        n = lib().clb_encoder_last_plans(self._h, names, rec, cap)
+        if n < 0:
+            check(4)
+        out = []
+        for i in range(n):
+            layer, M, N, K, bm, bn, stages, ks, red, flags, epi = rec[i * PLAN_FIELDS:(i + 1) * PLAN_FIELDS]
+            d = {"stage": names[i].decode(), "layer": layer, "M": M, "N": N, "K": K, "att": bool(flags & PLAN_ATT),
+                 "packed": bool(flags & PLAN_PACKED)}
+            if d["stage"] == "attention":
+                d.update(query_blocks=bm, key_tiles=bn, kind=["f16_planes", "f32_online", "f32_resident", "unfused"][epi])
+            else:
+                d.update(tile=(bm, bn), stages=stages, ks=ks, reduce=REDUCE_NAMES[red], epi=epi, part=bool(flags & PLAN_PART),
+                         ln=bool(flags & PLAN_LN), fold=bool(flags & PLAN_FOLD), fold_stats=bool(flags & PLAN_FOLD_STATS),
+                         fold_u=bool(flags & PLAN_FOLD_U))
+            out.append(d)
+        return out
 
     # -- profiling (bench.py) -----------------------------------------------------------------------
     def profile_enable(self, on: bool = True):

@@ -450,6 +450,32 @@ int clb_encoder_error_flag_device(clb_encoder* e, void** d_flag);
  * milliseconds and stage executions since the last read.  Returns the number of entries written (<= cap), -1 on error. */
 int clb_encoder_profile_enable(clb_encoder* e, int on);
 int clb_encoder_profile_read(clb_encoder* e, const char** names, double* total_ms, int64_t* launches, int cap);
+/* Test hooks of the encoder's tile plans.  Every Linear of `doc` (src/modelling/checkpoint.jl:21-25) picks its work-group tile,
+ * the depth of its LDS ring and the number of K slices from (M, N, K), its epilogue and what surrounds it; the rule is one pure
+ * function.  clb_debug_encoder_plan evaluates it without a device: gemm_mode 1 to 3 (the modes whose Linear layers run on
+ * planes), epi = the epilogue bits (1 bias, 2 GELU, 4 residual), flags = CLB_PLAN_* -> out[0..4] = tile rows, tile columns, ring
+ * stages, K slices, and the pass that sums the slices (0 none, 1 fused with the LayerNorm four columns per lane, 2 / 3 fused
+ * with the LayerNorm for widths that are not multiples of four (<= 768 / <= 1 024), 4 plain, 5 plain writing the attention
+ * planes).  clb_encoder_last_plans: what the LAST forward of this handle launched, in launch order -- names[i] is the stage
+ * (the names of clb_encoder_profile_read), records[i * CLB_ENCODER_PLAN_FIELDS ...] = layer (the projection: the number of
+ * layers), M, N, K, tile rows, tile columns, stages, K slices, reduce pass, flags, epilogue bits.  The attention kernel of a
+ * layer has a record of its own under "attention": M = rows, N = sequence length, K = head size, tile rows = query blocks of
+ * 32 per wave (0: an fp32 kernel), tile columns = key tiles of 32, epilogue field = 0 fp16 planes, 1 fp32 online softmax,
+ * 2 fp32 register-resident, 3 three kernels.  Filled on the host while the launches are enqueued (a replayed graph does not
+ * touch it); the fp32 GEMM path (mode 0, or a model whose shape keeps it off the planes) records its attention only.
+ * Returns the number of records written (<= cap), -1 on error. */
+enum {
+    CLB_ENCODER_PLAN_FIELDS = 11,
+    CLB_PLAN_PART = 1,         /* split-K scratch is available to this Linear */
+    CLB_PLAN_LN = 2,           /* a LayerNorm of the output follows (its own pass, or fused into the reduce pass) */
+    CLB_PLAN_ATT = 4,          /* the output feeds the fp16-plane attention (Q | K planes, key-blocked V) */
+    CLB_PLAN_FOLD = 8,         /* a LayerNorm is folded around the product (clb_encoder_set_ln_fold) ... */
+    CLB_PLAN_FOLD_STATS = 16,  /* ... whose row statistics it produces */
+    CLB_PLAN_FOLD_U = 32,      /* ... whose row statistics it consumes (gamma (.) W planes, vectors u and c) */
+    CLB_PLAN_PACKED = 64       /* records only: the batch was packed (clb_encode_docs_packed_device) */
+};
+int clb_debug_encoder_plan(int gemm_mode, int64_t M, int64_t N, int64_t K, int epi, int flags, int* out);
+int clb_encoder_last_plans(clb_encoder* e, const char** names, int64_t* records, int cap);
 
 
 /* Encoder epilogue as stand-alone calls  (src/modelling/checkpoint.jl:27-71, embedding_utils.jl:172-205) */

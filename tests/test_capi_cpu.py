@@ -348,3 +348,55 @@ def test_chunk_rows_from_cached_sample_and_new_passages():
                 want.extend(range(tail, tail + int(dl[j]))); tail += int(dl[j])
         got = _chunk_source_rows(known, dl, first, n_cached)
         assert got.dtype == np.int64 and np.array_equal(got, np.asarray(want, dtype=np.int64)), trial
+
+
+def test_encoder_plan_function_checks_its_arguments_and_restates_the_known_plans():
+    """clb_debug_encoder_plan needs no device: argument contract, and the plans the comments of the rule quote."""
+    import ctypes as C
+    l = clb.lib()
+    out = (C.c_int * 5)()
+    i64 = C.c_int64
+    assert l.clb_debug_encoder_plan(3, i64(32), i64(768), i64(768), 1, 0, None) == 4
+    assert l.clb_debug_encoder_plan(0, i64(32), i64(768), i64(768), 1, 0, out) == 4            # mode 0 has no planes
+    assert l.clb_debug_encoder_plan(3, i64(32), i64(768), i64(100), 1, 0, out) == 4            # K % 32
+    assert l.clb_encoder_last_plans(C.c_void_p(), None, None, 0) == -1
+    # the serving shape (128 queries = 4 096 rows): FFN-out as 128 x 128 tiles over two K slices, reduced inside the LayerNorm pass
+    assert clb.encoder_plan("f16x3", 4096, 768, 3072, 5, part=True, ln=True) == {"tile": (128, 128), "stages": 2, "ks": 2, "reduce": "ln4"}
+    # ... and its Q/K/V projection on 128 x 128 (the `att` exception: fewer than 1 024 such tiles), 128 x 256 for a passage batch
+    assert clb.encoder_plan("f16x3", 4096, 2304, 768, 1, att=True)["tile"] == (128, 128)
+    assert clb.encoder_plan("f16x3", 19200, 2304, 768, 1, att=True)["tile"] == (128, 256)
+    # the rounds of pick_long_tile: 264 tiles of 256 x 256 at 22 386 rows are two rounds, 225 at 19 200 one
+    assert clb.encoder_plan("f16x3", 22386, 768, 3072, 5, fold=True, fold_stats=True)["tile"] == (128, 256)
+    assert clb.encoder_plan("f16x3", 19200, 768, 3072, 5, fold=True, fold_stats=True)["tile"] == (256, 256)
+    # no scratch, no split; bf16x6 (three planes) has no eight-wave tiles
+    assert clb.encoder_plan("f16x3", 32, 768, 3072, 5, ln=True)["ks"] == 1
+    assert clb.encoder_plan("bf16x6", 19200, 768, 3072, 5, ln=True)["tile"] == (128, 128)
+
+
+def test_every_production_plan_of_the_encoder_is_one_the_shape_ladder_runs():
+    """The plans (role, tile, ring stages, K slices, reduce pass, fold) that bert-base geometry takes at the shapes the product
+    and the benchmark run -- one query, 32 queries, the serving shape, 64 x 300 passages, a full packed batch -- must all be plans
+    that tests/test_gpu_encoder_shapes.py asserts and compares with the float64 reference.  A retune that sends a production
+    shape to a plan no test runs fails here, without a GPU."""
+    from tests import encoder_ladder as el
+    import inspect
+    from colbert_jl_amd import indexer
+    assert '"COLBERT_PACK_ROWS", 170 * 256' in inspect.getsource(indexer) and el.PACK_ROWS_DEFAULT == 170 * 256
+    # the ladder's hand-written tables are what the plan function says today (the GPU module asserts them against the launches)
+    covered = set()
+    for case, c in el.LADDER.items():
+        recs = el.predict_plans("f16x3", el.case_rows(case), c["L"])
+        el.check_expectation(c["expect"], c["att"], recs)
+        covered |= el.expected_signatures(c["expect"])
+    for (case, ln_fold), expect in el.LADDER_FOLD_VARIANTS.items():
+        el.check_expectation(expect, None, el.predict_plans("f16x3", el.case_rows(case), el.LADDER[case]["L"], ln_fold=ln_fold))
+    assert len(covered) >= 25, len(covered)
+    for rows in el.PRODUCTION_ROWS:
+        for L in (32, 300):                                   # the sequence length does not enter a Linear's plan; both, to be sure
+            for r in el.predict_plans("f16x3", rows, L, layers=12):
+                if r["stage"] != "attention":
+                    assert el.signature(r) in covered, f"{rows} rows: {el.signature(r)} is a plan no ladder case runs"
+    # both sides of every switch on the row count are in the ladder
+    rows = sorted(el.case_rows(c) for c in el.LADDER)
+    for edge in (el.ONE_QUERY_ROWS, el.SHORT_BATCH_ROWS):
+        assert edge in rows and any(edge < r <= edge + 64 for r in rows), edge
