@@ -2,6 +2,7 @@
 // Replaces: struct Searcher / Searcher(index_path) (src/searching.jl:1-91) and search() after the
 // encoder (src/searching.jl:102-127), retrieve/gather/maxsim (src/search/ranking.jl).
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
@@ -57,6 +58,15 @@ struct Prof {
 
 }  // namespace
 
+// A resident passage filter (include/colbert_hip.h): one bitmap in the layout of the candidate bitmap.  It owns its words
+// and remembers its searcher by serial number only, so it may outlive the searcher (clb_filter_destroy then just frees).
+struct clb_filter {
+    uint64_t owner = 0;         // clb_searcher::serial of the searcher it was made for
+    int device = 0;
+    int64_t n_docs = 0, count = 0;
+    DevBuf bits;                // u32 [ceil(n_docs / 32)]
+};
+
 // Per-batch workspace (everything a batch of queries needs besides the resident index).
 struct Workspace {
     int64_t Bcap = 0, Tcap = 0, npcap = 0, kcap = 0;
@@ -67,6 +77,13 @@ struct Workspace {
     bool have_range = false;    // tscale holds this batch's measured score ranges (the batched centroid kernel ran)
     bool cell8 = false;         // pass 1 gathers from cells8: 32-byte rows of 8-bit cells requantised from cells_q by tscale
     bool stats_keep = false;    // set for the 2nd, 3rd ... sub-batch of one call: the work counters accumulate over the call
+    // filtered search: the handles of the running sub-batch (a HOST array, one entry per query, nullptr = unfiltered) and
+    // their scope; set by the filtered entry points around run_search, nullptr whenever no query of the sub-batch is filtered
+    const clb_filter* const* filt = nullptr;
+    int filt_all = 0;
+    size_t filt_cap = 0;        // largest filter population a CLB_FILTER_ALL call has asked this slot to hold (cand_cap covers it)
+    size_t filt_now = 0;        // ... and the running call's
+    size_t ivf_cap = 0;         // cand_cap before filt_cap was taken into account: the most candidates the IVF lists can give
     // two-phase sharded search: what clb_search_shard_phase1 left behind (phase 2 must continue exactly that batch)
     struct { bool valid = false; const float* dQ = nullptr; int64_t T = 0, B = 0, nprobe = 0, k = 0; void* stream = nullptr; } pending;
     DevBuf Qdev, cells, cells_q, partial, sel, bitmap, blocksum, ncand, cand, cand_hdr, scores, list, nlist, thresh,
@@ -78,6 +95,7 @@ constexpr int kWorkspaceSlots = 4;
 
 struct clb_searcher {
     int device = 0;
+    uint64_t serial = 0;       // unique per handle of this process: what a clb_filter remembers of its searcher
     int64_t dim = 0, K = 0, n_docs = 0, n_emb = 0, pid_offset = 0;
     int nbits = 0;
     int mode = 0;
@@ -170,9 +188,12 @@ int next_pow2(int x) {
     return p;
 }
 
-int ensure_workspace(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_t nprobe, int64_t k) {
+// filt_count: the largest filter population of a CLB_FILTER_ALL call (0 otherwise) -- such a query's candidates are its
+// filter's passages, however few the IVF lists would give
+int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_t nprobe, int64_t k, size_t filt_count) {
     const int64_t t_tuned = T <= 128 ? T : 0;       // queries of up to 128 tokens take the tuned (or batched general) kernels
-    if (B <= w.Bcap && T <= w.Tcap && t_tuned <= w.Ttuned && nprobe <= w.npcap && k <= w.kcap) return CLB_OK;
+    if (B <= w.Bcap && T <= w.Tcap && t_tuned <= w.Ttuned && nprobe <= w.npcap && k <= w.kcap && filt_count <= w.filt_cap)
+        return CLB_OK;
     CLB_HIP(hipDeviceSynchronize());       // buffers may be in use on any of the caller's streams
     B = std::max(B, w.Bcap); T = std::max(T, w.Tcap);
     nprobe = std::max(nprobe, w.npcap); k = std::max(k, w.kcap);
@@ -187,6 +208,8 @@ int ensure_workspace(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_
     size_t cap = 0;
     for (size_t i = 0; i < lists; ++i) cap += s->ivf_len_sorted[i];
     cap = std::min<size_t>(cap, (size_t)s->n_docs);
+    w.ivf_cap = (std::max<size_t>(cap, 1) + 3) & ~(size_t)3;
+    cap = std::max<size_t>(cap, std::max(filt_count, w.filt_cap));      // <= n_docs: a filter's population
     cap = std::max<size_t>(cap, 1);
     w.cand_cap = (cap + 3) & ~(size_t)3;
     w.W = (int)((s->n_docs + 31) / 32);
@@ -234,8 +257,21 @@ int ensure_workspace(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_
         CLB_TRY(w.tokmax.ensure(sizeof(uint16_t) * 32 * B * w.cand_cap));
     }
     w.Bcap = B; w.Tcap = T; w.Ttuned = Ttuned; w.npcap = nprobe; w.kcap = k;
+    w.filt_cap = std::max(w.filt_cap, filt_count);
     CLB_HIP(hipStreamSynchronize(s->stream));
     return CLB_OK;
+}
+
+int ensure_workspace(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_t nprobe, int64_t k, size_t filt_count = 0) {
+    const int rc = ensure_workspace_sized(s, w, B, T, nprobe, k, filt_count);
+    if (rc) {
+        w.Bcap = 0;       // some buffers may have grown and others not: the next call sizes all of them again
+        // a candidate set the size of a filter that does not fit is this call's own request, not a fault of the device
+        if (rc == CLB_ENOMEM && filt_count > w.filt_cap)
+            return fail(CLB_EUNSUPPORTED, "no room for the candidate buffers of a filter of %zu passages (CLB_FILTER_ALL, %lld "
+                                          "queries per pass): %s", filt_count, (long long)B, std::string(last_error()).c_str());
+    }
+    return rc;
 }
 
 template <int NP>
@@ -389,8 +425,23 @@ int run_retrieve(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ,
 
 // S3: the union of the selected IVF lists as an ascending pid list + passage headers, for B queries (w.sel -> w.cand,
 // w.cand_hdr, w.ncand); shared by the tuned and the general-shape path
-int mark_and_compact(clb_searcher* s, Workspace& w, hipStream_t st, int B, int T, int Tpad, int NPs, int nprobe) {
+// the filter operand of queries b0 .. b0 + n - 1 of the running sub-batch
+FilterArgs filter_args(const Workspace& w, int b0, int n) {
+    FilterArgs fa{};
+    for (int i = 0; i < n && i < kFilterQueries; ++i) fa.bits[i] = w.filt[b0 + i] ? w.filt[b0 + i]->bits.as<uint32_t>() : nullptr;
+    fa.all = w.filt_all;
+    return fa;
+}
+inline NoFilter filter_operand(std::false_type, const Workspace&, int, int) { return {}; }
+inline FilterArgs filter_operand(std::true_type, const Workspace& w, int b0, int n) { return filter_args(w, b0, n); }
+
+// FILT: some query of the sub-batch carries a filter (S3f) -- the same launches with the filter operand; false: the
+// unfiltered kernels, launched as ever
+template <bool FILT>
+int mark_and_compact_impl(clb_searcher* s, Workspace& w, hipStream_t st, int B, int T, int Tpad, int NPs, int nprobe) {
     static_assert(kScanBlock * kWordsPerThread == 1024, "mark_count_kernel writes 1024-word count blocks");
+    static_assert(kSubBatch <= kFilterQueries, "the filter handles of a sub-batch travel in one kernel argument block");
+    const auto fa = filter_operand(std::integral_constant<bool, FILT>(), w, 0, B);
     const int nslices = (w.nblk_bitmap + kMarkSliceBlocks - 1) / kMarkSliceBlocks;
     const int nslices_big = (w.nblk_bitmap + kMarkSliceBlocksBig - 1) / kMarkSliceBlocksBig;
     // every slice re-reads the query's lists: beyond 16 slices (2 M passages per shard) that costs more than the atomics
@@ -401,34 +452,46 @@ int mark_and_compact(clb_searcher* s, Workspace& w, hipStream_t st, int B, int T
     {
         Timed t(s, KID_MARK, st);
         if (sliced && nslices <= 16)     // mark + per-block counts, the bitmap slice of a work-group in LDS (no global atomics)
-            hipLaunchKernelGGL((mark_count_kernel<false, kMarkSliceBlocks>), dim3(nslices, B), dim3(1024), 0, st, w.sel.as<int>(),
+            hipLaunchKernelGGL((mark_count_kernel<false, kMarkSliceBlocks, FILT>), dim3(nslices, B), dim3(1024), 0, st, w.sel.as<int>(),
                                s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), w.bitmap.as<uint32_t>(),
-                               w.blocksum.as<int>(), T, Tpad, NPs, nprobe, w.W, w.nblk_bitmap);
+                               w.blocksum.as<int>(), T, Tpad, NPs, nprobe, w.W, w.nblk_bitmap, (const uint32_t*)nullptr, fa);
         else if (sliced) {
             const int nb = T * nprobe * (nslices_big + 1);
             hipLaunchKernelGGL(slice_bounds_kernel, dim3((nb + 255) / 256, B), dim3(256), 0, st, w.sel.as<int>(),
                                s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), T, Tpad, NPs, nprobe, nslices_big,
                                (uint32_t)(kMarkSliceBlocksBig * 1024 * 32), w.bounds.as<uint32_t>());
-            hipLaunchKernelGGL((mark_count_kernel<true, kMarkSliceBlocksBig>), dim3(nslices_big, B), dim3(1024), 0, st,
+            hipLaunchKernelGGL((mark_count_kernel<true, kMarkSliceBlocksBig, FILT>), dim3(nslices_big, B), dim3(1024), 0, st,
                                w.sel.as<int>(), s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), w.bitmap.as<uint32_t>(),
                                w.blocksum.as<int>(), T, Tpad, NPs, nprobe, w.W, w.nblk_bitmap,
-                               (const uint32_t*)w.bounds.as<uint32_t>());
+                               (const uint32_t*)w.bounds.as<uint32_t>(), fa);
         } else
-            hipLaunchKernelGGL(mark_candidates_kernel, dim3(T * nprobe, B), dim3(256), 0, st, w.sel.as<int>(),
+            hipLaunchKernelGGL(mark_candidates_kernel<FILT>, dim3(T * nprobe, B), dim3(256), 0, st, w.sel.as<int>(),
                                s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), w.bitmap.as<uint32_t>(), T,
-                               Tpad, NPs, nprobe, w.W);
+                               Tpad, NPs, nprobe, w.W, fa);
     }
     {
         Timed t(s, KID_COMPACT, st);
         if (!sliced)
-            hipLaunchKernelGGL(bitmap_count_kernel, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st,
-                               w.bitmap.as<uint32_t>(), w.blocksum.as<int>(), w.W);
-        hipLaunchKernelGGL(bitmap_emit_kernel, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st,
+            hipLaunchKernelGGL(bitmap_count_kernel<FILT>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st,
+                               w.bitmap.as<uint32_t>(), w.blocksum.as<int>(), w.W, fa);
+        // after the sliced marking the bitmap already holds marked AND filter: only a filter that IS the candidate set
+        // (CLB_FILTER_ALL) still has to reach the emit kernel
+        if (FILT && (!sliced || w.filt_all))
+            hipLaunchKernelGGL(bitmap_emit_kernel<FILT>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st,
+                               w.bitmap.as<uint32_t>(), w.blocksum.as<int>(), w.cand.as<uint32_t>(),
+                               s->doc_off.as<uint32_t>(), w.cand_hdr.as<uint2>(), w.W, w.cand_cap, w.ncand.as<int>(), fa);
+        else
+        hipLaunchKernelGGL(bitmap_emit_kernel<false>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st,
                            w.bitmap.as<uint32_t>(), w.blocksum.as<int>(), w.cand.as<uint32_t>(),
                            s->doc_off.as<uint32_t>(), w.cand_hdr.as<uint2>(), w.W, w.cand_cap, w.ncand.as<int>());
     }
     CLB_HIP(hipGetLastError());
     return CLB_OK;
+}
+
+int mark_and_compact(clb_searcher* s, Workspace& w, hipStream_t st, int B, int T, int Tpad, int NPs, int nprobe) {
+    return w.filt ? mark_and_compact_impl<true>(s, w, st, B, T, Tpad, NPs, nprobe)
+                  : mark_and_compact_impl<false>(s, w, st, B, T, Tpad, NPs, nprobe);
 }
 
 int check_search_args(clb_searcher* s, int64_t T, int64_t B, int64_t nprobe, int64_t k) {
@@ -494,10 +557,21 @@ int run_retrieve_general(clb_searcher* s, Workspace& w, hipStream_t st, const fl
     CLB_TRY(select_by_sort(s, w, st, w.g_cells.as<float>(), (size_t)s->K, 1, T, nprobe, nprobe, sel_b));
     uint32_t* bm = w.bitmap.as<uint32_t>() + (size_t)b * w.W;
     int* bs = w.blocksum.as<int>() + (size_t)b * w.nblk_bitmap;
-    hipLaunchKernelGGL(mark_candidates_kernel, dim3(T * nprobe, 1), dim3(256), 0, st, sel_b, s->ivf_off.as<uint32_t>(),
+    if (w.filt && w.filt[b]) {      // S3f: this query's filter as entry 0 of the operand (the launches are one query wide)
+        const FilterArgs fa = filter_args(w, b, 1);
+        hipLaunchKernelGGL(mark_candidates_kernel<true>, dim3(T * nprobe, 1), dim3(256), 0, st, sel_b, s->ivf_off.as<uint32_t>(),
+                           s->ivf_pid.as<uint32_t>(), bm, T, T, nprobe, nprobe, w.W, fa);
+        hipLaunchKernelGGL(bitmap_count_kernel<true>, dim3(w.nblk_bitmap, 1), dim3(kScanBlock), 0, st, bm, bs, w.W, fa);
+        hipLaunchKernelGGL(bitmap_emit_kernel<true>, dim3(w.nblk_bitmap, 1), dim3(kScanBlock), 0, st, bm, bs,
+                           w.cand.as<uint32_t>() + (size_t)b * w.cand_cap, s->doc_off.as<uint32_t>(),
+                           w.cand_hdr.as<uint2>() + (size_t)b * w.cand_cap, w.W, w.cand_cap, w.ncand.as<int>() + b, fa);
+        CLB_HIP(hipGetLastError());
+        return CLB_OK;
+    }
+    hipLaunchKernelGGL(mark_candidates_kernel<false>, dim3(T * nprobe, 1), dim3(256), 0, st, sel_b, s->ivf_off.as<uint32_t>(),
                        s->ivf_pid.as<uint32_t>(), bm, T, T, nprobe, nprobe, w.W);
-    hipLaunchKernelGGL(bitmap_count_kernel, dim3(w.nblk_bitmap, 1), dim3(kScanBlock), 0, st, bm, bs, w.W);
-    hipLaunchKernelGGL(bitmap_emit_kernel, dim3(w.nblk_bitmap, 1), dim3(kScanBlock), 0, st, bm, bs,
+    hipLaunchKernelGGL(bitmap_count_kernel<false>, dim3(w.nblk_bitmap, 1), dim3(kScanBlock), 0, st, bm, bs, w.W);
+    hipLaunchKernelGGL(bitmap_emit_kernel<false>, dim3(w.nblk_bitmap, 1), dim3(kScanBlock), 0, st, bm, bs,
                        w.cand.as<uint32_t>() + (size_t)b * w.cand_cap, s->doc_off.as<uint32_t>(),
                        w.cand_hdr.as<uint2>() + (size_t)b * w.cand_cap, w.W, w.cand_cap, w.ncand.as<int>() + b);
     CLB_HIP(hipGetLastError());
@@ -627,7 +701,10 @@ inline float bound_dc(const clb_searcher* s, const Workspace& w) {
 }
 int launch_select(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, int B, int T, int k, const float* tau_in,
                   bool coarse_tau = false) {
-    const bool wide = s->wide_select == 1 || (s->wide_select < 0 && w.cand_cap >= kWideSelectCap);
+    // by the most candidates a query of THIS sub-batch can have: a slot that once grew for a large CLB_FILTER_ALL set
+    // goes on selecting its unfiltered batches as before
+    const size_t most = w.filt && w.filt_all ? std::max(w.ivf_cap, w.filt_now) : w.ivf_cap;
+    const bool wide = s->wide_select == 1 || (s->wide_select < 0 && most >= kWideSelectCap);
     if (!wide) {
         ApproxConsts ac = s->approx_consts;
         ac.dc_max = bound_dc(s, w);
@@ -842,7 +919,9 @@ static int searcher_create_impl(int device, int64_t dim, int nbits, int64_t K, c
     if (run != n_emb) return fail(CLB_EDIMENSION, "length(ivf) must be equal to sum(ivf_lengths)!");
     CLB_TRY(use_device(device));
 
+    static std::atomic<uint64_t> next_serial{1};
     clb_searcher* s = new clb_searcher();
+    s->serial = next_serial.fetch_add(1);
     s->device = device; s->dim = dim; s->nbits = nbits; s->K = K; s->n_docs = n_docs; s->n_emb = n_emb;
     s->pid_offset = pid_offset;
     s->generic = !(dim == kDim && nbits <= 4);     // the tuned kernels are built for dim 128, nbits 1/2/4
@@ -1098,11 +1177,41 @@ int clb_search_batch_device(clb_searcher* s, const float* d_Q, int64_t T, int64_
     return clb_search_batch_device_slot(s, 0, d_Q, T, B, nprobe, k, d_out_pids, d_out_scores, d_n_cand, hip_stream);
 }
 
-int clb_search_batch_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                 int64_t k, int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand,
-                                 void* hip_stream) {
+// the filters of a call (a host array of B handles, or nullptr): every one must be this searcher's; *filt_count = the largest
+// population a CLB_FILTER_ALL search has to hold as a candidate set (a host value: sizing the workspace needs no read-back)
+static int check_filters(const clb_searcher* s, const clb_filter* const* filters, int64_t B, int scope, size_t* filt_count) {
+    *filt_count = 0;
+    if (scope != CLB_FILTER_CANDIDATES && scope != CLB_FILTER_ALL)
+        return fail(CLB_EARGUMENT, "scope must be CLB_FILTER_CANDIDATES (0) or CLB_FILTER_ALL (1), got %d", scope);
+    if (!filters) return CLB_OK;
+    for (int64_t b = 0; b < B; ++b) {
+        const clb_filter* f = filters[b];
+        if (!f) continue;
+        if (f->owner != s->serial || f->n_docs != s->n_docs)
+            return fail(CLB_EARGUMENT, "the filter of query %lld was made for another searcher", (long long)b);
+        if (scope == CLB_FILTER_ALL) *filt_count = std::max(*filt_count, (size_t)f->count);
+    }
+    return CLB_OK;
+}
+// the sub-batch b0 .. b0 + bn - 1 as run_search sees it: its slice of the handle array, or nullptr when none of its queries is
+// filtered (that sub-batch then launches the unfiltered kernels)
+static void set_sub_batch_filters(Workspace& w, const clb_filter* const* filters, int64_t b0, int64_t bn, int scope,
+                                  size_t filt_count) {
+    w.filt = nullptr;
+    w.filt_all = scope == CLB_FILTER_ALL;
+    w.filt_now = filt_count;
+    if (!filters) return;
+    for (int64_t b = b0; b < b0 + bn; ++b)
+        if (filters[b]) { w.filt = filters + b0; return; }
+}
+
+static int search_batch_device_slot_impl(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const clb_filter* const* filters, int scope, int64_t* d_out_pids,
+                                         float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     if (slot < 0 || slot >= kWorkspaceSlots) return fail(CLB_EARGUMENT, "workspace slot must be 0..%d", kWorkspaceSlots - 1);
+    size_t filt_count = 0;
+    CLB_TRY(check_filters(s, filters, B, scope, &filt_count));
     CLB_TRY(use_device(s->device));
     hipStream_t st = (hipStream_t)hip_stream;   // NULL = the HIP null stream, as for any HIP API
     Workspace& w = s->ws[slot];
@@ -1114,14 +1223,30 @@ int clb_search_batch_device_slot(clb_searcher* s, int slot, const float* d_Q, in
     // (The two-phase sharded calls keep the whole batch: phase 2 continues on the scratch of phase 1.)
     for (int64_t b0 = 0; b0 < B; b0 += kSubBatch) {
         const int64_t bn = std::min<int64_t>(kSubBatch, B - b0);
-        CLB_TRY(ensure_workspace(s, w, bn, T, nprobe, k));
+        CLB_TRY(ensure_workspace(s, w, bn, T, nprobe, k, filt_count));
         w.stats_keep = b0 > 0;
+        set_sub_batch_filters(w, filters, b0, bn, scope, filt_count);
         const int rc = run_search(s, w, st, d_Q + (size_t)b0 * T * s->dim, (int)bn, (int)T, (int)nprobe, (int)k, d_out_pids + (size_t)b0 * k,
                                   d_out_scores + (size_t)b0 * k, d_n_cand ? d_n_cand + b0 : nullptr);
         w.stats_keep = false;
+        w.filt = nullptr;
         if (rc) return rc;
     }
     return CLB_OK;
+}
+
+int clb_search_batch_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                 int64_t k, int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand,
+                                 void* hip_stream) {
+    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, nullptr, CLB_FILTER_CANDIDATES, d_out_pids, d_out_scores,
+                                         d_n_cand, hip_stream);
+}
+
+int clb_search_batch_filtered_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                          int64_t k, const clb_filter* const* filters, int scope, int64_t* d_out_pids,
+                                          float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
+    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, d_out_pids, d_out_scores, d_n_cand,
+                                         hip_stream);
 }
 
 int clb_search_shard_phase1(clb_searcher* s, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
@@ -1175,9 +1300,12 @@ int clb_search_shard_phase2_slot(clb_searcher* s, int slot, const float* d_Q, in
                       d_n_cand, 2, nullptr, d_all_top, (int)n_shards);
 }
 
-int clb_search_batch(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                     int pad_short, int64_t* out_pids, float* out_scores, int64_t* n_cand) {
+static int search_batch_impl(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                             const clb_filter* const* filters, int scope, int pad_short, int64_t* out_pids, float* out_scores,
+                             int64_t* n_cand) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
+    size_t filt_count = 0;
+    CLB_TRY(check_filters(s, filters, B, scope, &filt_count));
     CLB_TRY(use_device(s->device));
     Workspace& w = s->ws[0];
     w.pending.valid = false;
@@ -1185,11 +1313,13 @@ int clb_search_batch(clb_searcher* s, const float* Q, int64_t T, int64_t B, int6
     std::vector<int> nc((size_t)B), fl((size_t)B);
     for (int64_t b0 = 0; b0 < B; b0 += kSubBatch) {           // sub-batches: see clb_search_batch_device_slot
         const int64_t bn = std::min<int64_t>(kSubBatch, B - b0);
-        CLB_TRY(ensure_workspace(s, w, bn, T, nprobe, k));
+        CLB_TRY(ensure_workspace(s, w, bn, T, nprobe, k, filt_count));
         CLB_HIP(hipMemcpyAsync(w.Qdev.p, Q + (size_t)b0 * T * s->dim, sizeof(float) * bn * T * s->dim, hipMemcpyHostToDevice, st));
         w.stats_keep = b0 > 0;
+        set_sub_batch_filters(w, filters, b0, bn, scope, filt_count);
         const int rc = run_search(s, w, st, w.Qdev.as<float>(), (int)bn, (int)T, (int)nprobe, (int)k, w.outp.as<int64_t>(), w.outs.as<float>());
         w.stats_keep = false;
+        w.filt = nullptr;
         if (rc) return rc;
         CLB_HIP(hipMemcpyAsync(out_pids + (size_t)b0 * k, w.outp.p, sizeof(int64_t) * bn * k, hipMemcpyDeviceToHost, st));
         CLB_HIP(hipMemcpyAsync(out_scores + (size_t)b0 * k, w.outs.p, sizeof(float) * bn * k, hipMemcpyDeviceToHost, st));
@@ -1207,6 +1337,106 @@ int clb_search_batch(clb_searcher* s, const float* Q, int64_t T, int64_t B, int6
         for (int64_t b = 0; b < B; ++b)
             if (fl[b])  // searching.jl:127 `pids[1:k]` on a shorter vector
                 return fail(CLB_EBOUNDS, "query %lld has %d candidate passages, fewer than k=%lld", (long long)b, nc[b], (long long)k);
+    return CLB_OK;
+}
+
+int clb_search_batch(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                     int pad_short, int64_t* out_pids, float* out_scores, int64_t* n_cand) {
+    return search_batch_impl(s, Q, T, B, nprobe, k, nullptr, CLB_FILTER_CANDIDATES, pad_short, out_pids, out_scores, n_cand);
+}
+
+int clb_search_batch_filtered(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                              const clb_filter* const* filters, int scope, int64_t* out_pids, float* out_scores,
+                              int64_t* n_cand) {
+    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, 1, out_pids, out_scores, n_cand);
+}
+
+// ---- clb_filter ---------------------------------------------------------------------------------------------------
+// the words are on the device: clear the tail bits, count once (creation may synchronise, searching never reads the count back)
+static int filter_finish(clb_searcher* s, clb_filter* f, clb_filter** out) {
+    DevBuf cnt;
+    int rc = cnt.alloc(sizeof(unsigned long long));
+    unsigned long long h = 0;
+    const int W = (int)((s->n_docs + 31) / 32);
+    if (!rc && hipMemsetAsync(cnt.p, 0, sizeof h, s->stream) != hipSuccess) rc = fail(CLB_EHIP, "memset failed");
+    if (!rc && W > 0)
+        hipLaunchKernelGGL(filter_count_kernel, dim3((unsigned)std::max(1, std::min(1024, (W + 255) / 256))), dim3(256), 0, s->stream,
+                           f->bits.as<uint32_t>(), W, (int)s->n_docs, cnt.as<unsigned long long>());
+    if (!rc && (hipMemcpyAsync(&h, cnt.p, sizeof h, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                hipStreamSynchronize(s->stream) != hipSuccess || hipGetLastError() != hipSuccess))
+        rc = fail(CLB_EHIP, "building the filter failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) { delete f; return rc; }
+    f->count = (int64_t)h;
+    *out = f;
+    return CLB_OK;
+}
+static int filter_new(clb_searcher* s, clb_filter** out, clb_filter** f_out) {
+    if (!out) return fail(CLB_EARGUMENT, "out is null");
+    *out = nullptr;
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    CLB_TRY(use_device(s->device));
+    clb_filter* f = new clb_filter();
+    f->owner = s->serial; f->device = s->device; f->n_docs = s->n_docs;
+    const int rc = f->bits.alloc(sizeof(uint32_t) * (size_t)((s->n_docs + 31) / 32));
+    if (rc) { delete f; return rc; }
+    *f_out = f;
+    return CLB_OK;
+}
+
+int clb_filter_create_pids(clb_searcher* s, const int64_t* pids, int64_t n, clb_filter** out) {
+    if (out) *out = nullptr;
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    if (!out) return fail(CLB_EARGUMENT, "out is null");
+    if (n < 0 || (n > 0 && !pids)) return fail(CLB_EARGUMENT, "pids is null or n < 0");
+    for (int64_t i = 0; i < n; ++i)
+        if (pids[i] <= s->pid_offset || pids[i] > s->pid_offset + s->n_docs)
+            return fail(CLB_EBOUNDS, "pid %lld (entry %lld) outside %lld..%lld", (long long)pids[i], (long long)i,
+                        (long long)(s->pid_offset + 1), (long long)(s->pid_offset + s->n_docs));
+    clb_filter* f = nullptr;
+    CLB_TRY(filter_new(s, out, &f));
+    DevBuf d_pids, err;
+    int rc = CLB_OK, herr = 0;
+    if (hipMemsetAsync(f->bits.p, 0, f->bits.bytes, s->stream) != hipSuccess) rc = fail(CLB_EHIP, "memset failed");
+    if (!rc && n > 0) {
+        if (!(rc = upload(d_pids, pids, sizeof(int64_t) * n, s->stream)) && !(rc = err.alloc(sizeof(int)))) {
+            if (hipMemsetAsync(err.p, 0, sizeof(int), s->stream) != hipSuccess) rc = fail(CLB_EHIP, "memset failed");
+            else {
+                hipLaunchKernelGGL(filter_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, d_pids.as<int64_t>(),
+                                   n, s->pid_offset, (int)s->n_docs, f->bits.as<uint32_t>(), err.as<int>());
+                if (hipMemcpyAsync(&herr, err.p, sizeof(int), hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                    hipStreamSynchronize(s->stream) != hipSuccess)        // ... before d_pids and the host array go away
+                    rc = fail(CLB_EHIP, "building the filter failed: %s", hipGetErrorString(hipGetLastError()));
+                else if (herr) rc = fail(CLB_EBOUNDS, "a pid outside the searcher's passages");
+            }
+        }
+    }
+    if (rc) { delete f; return rc; }
+    return filter_finish(s, f, out);
+}
+
+int clb_filter_create_bitmap(clb_searcher* s, const uint32_t* words, int64_t n_words, clb_filter** out) {
+    if (out) *out = nullptr;
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    if (!out) return fail(CLB_EARGUMENT, "out is null");
+    const int64_t W = (s->n_docs + 31) / 32;
+    if (n_words != W) return fail(CLB_EARGUMENT, "n_words=%lld, the searcher's bitmap has ceil(n_docs / 32) = %lld words", (long long)n_words, (long long)W);
+    if (W > 0 && !words) return fail(CLB_EARGUMENT, "words is null");
+    clb_filter* f = nullptr;
+    CLB_TRY(filter_new(s, out, &f));
+    if (W > 0 && (hipMemcpyAsync(f->bits.p, words, sizeof(uint32_t) * W, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+                  hipStreamSynchronize(s->stream) != hipSuccess)) {       // the library never retains a host pointer
+        delete f;
+        return fail(CLB_EHIP, "uploading the filter failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    return filter_finish(s, f, out);
+}
+
+int64_t clb_filter_count(const clb_filter* f) { return f ? f->count : 0; }
+
+int clb_filter_destroy(clb_filter* f) {
+    if (!f) return CLB_OK;
+    (void)hipSetDevice(f->device);
+    delete f;
     return CLB_OK;
 }
 

@@ -15,6 +15,8 @@
 #pragma once
 #include <hip/hip_fp16.h>
 
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace clb {
@@ -296,12 +298,32 @@ static __global__ __launch_bounds__(64) void top2_merge_kernel(const ValIdx* __r
 // a bitmap over the shard's passages (atomicOr), and the ascending pid list falls out of a bitmap
 // compaction -- no sort.  grid = (T*nprobe, B), block = 256.
 // -------------------------------------------------------------------------------------------------
+// S3f  the passage filter of a query (clb_filter): a resident bitmap in the layout of the candidate bitmap -- bit i of
+// word j = local passage 32 j + i -- that the marking / compaction kernels take as one more operand.  The handles of a
+// sub-batch (at most 64 queries) travel in the kernel arguments, so a filtered search stays stream-ordered: no table to
+// upload, nothing for a captured graph to re-read.  bits[b] == nullptr: query b is not filtered.
+// all == 0 (CLB_FILTER_CANDIDATES): candidates = marked AND filter.  all == 1 (CLB_FILTER_ALL): the filter IS the
+// candidate set of a filtered query -- nothing is marked for it, count and emit read the filter's words and leave them
+// alone.  FILT = false instantiations are the unfiltered kernels: the operand is an empty struct and no code is added.
+constexpr int kFilterQueries = 64;
+struct FilterArgs {
+    const uint32_t* bits[kFilterQueries];
+    int all;
+};
+struct NoFilter {};
+template <bool FILT> using FilterOperand = std::conditional_t<FILT, FilterArgs, NoFilter>;
+
+template <bool FILT = false>
 static __global__ __launch_bounds__(256) void mark_candidates_kernel(const int* __restrict__ sel,
                                                               const uint32_t* __restrict__ ivf_off,
                                                               const uint32_t* __restrict__ ivf_pid,
                                                               uint32_t* __restrict__ bitmap, int T,
-                                                              int Tpad, int NP, int nprobe, int W) {
+                                                              int Tpad, int NP, int nprobe, int W,
+                                                              FilterOperand<FILT> fa = {}) {
     const int b = blockIdx.y;
+    if constexpr (FILT) {
+        if (fa.all && fa.bits[b]) return;     // the filter is the candidate set: the bitmap stays clear
+    }
     const int t = blockIdx.x / nprobe, p = blockIdx.x % nprobe;
     const int* s = sel + (size_t)b * Tpad * NP;
     const int cid = s[t * NP + p];
@@ -395,14 +417,15 @@ static __global__ __launch_bounds__(256) void slice_bounds_kernel(const int* __r
 // SB = count blocks (1 024 bitmap words = 32 768 passages each) per slice: 4 (16 KB of LDS) for small shards, 16 (64 KB) with
 // SEARCH -- a work-group's fixed costs (zeroing, two rounds of list loads, the write-out) are ~30 us whatever the slice
 // holds, and a 10 M-passage shard has 77 four-block slices per query.
-template <bool SEARCH, int SB>
+template <bool SEARCH, int SB, bool FILT = false>
 static __global__ __launch_bounds__(1024) void mark_count_kernel(const int* __restrict__ sel,
                                                                  const uint32_t* __restrict__ ivf_off,
                                                                  const uint32_t* __restrict__ ivf_pid,
                                                                  uint32_t* __restrict__ bitmap,
                                                                  int* __restrict__ blocksum, int T, int Tpad, int NP,
                                                                  int nprobe, int W, int nblk,
-                                                                 const uint32_t* __restrict__ bounds = nullptr) {
+                                                                 const uint32_t* __restrict__ bounds = nullptr,
+                                                                 FilterOperand<FILT> fa = {}) {
     __shared__ uint32_t lbm[(SB * 1024)];
     __shared__ int cnt[SB];
     __shared__ uint32_t s_lo[kMarkLists], s_hi[kMarkLists];
@@ -412,7 +435,13 @@ static __global__ __launch_bounds__(1024) void mark_count_kernel(const int* __re
     __syncthreads();
     const int* s = sel + (size_t)b * Tpad * NP;
     const uint32_t p_lo = (uint32_t)slice * (SB * 1024) * 32u, p_n = (uint32_t)(SB * 1024) * 32u;
-    const int nl = T * nprobe;
+    const uint32_t* fw = nullptr;        // this query's filter words; from_filter: they are its candidate set
+    bool from_filter = false;
+    if constexpr (FILT) {
+        fw = fa.bits[b];
+        from_filter = fw && fa.all;
+    }
+    const int nl = from_filter ? 0 : T * nprobe;
     // kMarkLists lists per round, 1024 / kMarkLists threads each.  The bounds of the round's lists are fetched ONCE (one thread per
     // list) and shared through LDS -- every thread used to load all of them itself: 1 536 broadcast loads per wave and round,
     // two thirds of this kernel's 30 us -- and a thread keeps kMarkDepth entries of its list in flight.
@@ -459,8 +488,15 @@ static __global__ __launch_bounds__(1024) void mark_count_kernel(const int* __re
 #pragma unroll
     for (int j = 0; j < SB; ++j) {
         const int wi = j * 1024 + tid;
-        const uint32_t word = lbm[wi];
-        if (w0 + wi < W) bm[w0 + wi] = word;
+        uint32_t word = lbm[wi];
+        if constexpr (FILT) {
+            // the filter word goes in BEFORE the count and the write-out: blocksum and the bitmap the emit kernel reads agree
+            if (fw) {
+                const uint32_t f = w0 + wi < W ? fw[w0 + wi] : 0u;
+                word = from_filter ? f : word & f;
+            }
+        }
+        if (w0 + wi < W && !from_filter) bm[w0 + wi] = word;
         int c = __popc(word);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
@@ -472,16 +508,26 @@ static __global__ __launch_bounds__(1024) void mark_count_kernel(const int* __re
 }
 
 // grid = (nblk, B)
+template <bool FILT = false>
 static __global__ __launch_bounds__(kScanBlock) void bitmap_count_kernel(const uint32_t* __restrict__ bitmap,
-                                                                  int* __restrict__ blocksum, int W) {
+                                                                  int* __restrict__ blocksum, int W,
+                                                                  FilterOperand<FILT> fa = {}) {
     __shared__ int sh[8];
     const int b = blockIdx.y;
     const uint32_t* bm = bitmap + (size_t)b * W;
     const int w0 = (blockIdx.x * kScanBlock + threadIdx.x) * kWordsPerThread;
     int cnt = 0;
+    if constexpr (FILT) {
+        const uint32_t* fw = fa.bits[b];
+        const bool from_filter = fw && fa.all;
+#pragma unroll
+        for (int j = 0; j < kWordsPerThread; ++j)
+            if (w0 + j < W) cnt += __popc(!fw ? bm[w0 + j] : from_filter ? fw[w0 + j] : bm[w0 + j] & fw[w0 + j]);
+    } else {
 #pragma unroll
     for (int j = 0; j < kWordsPerThread; ++j)
         if (w0 + j < W) cnt += __popc(bm[w0 + j]);
+    }
     int total;
     (void)block_exclusive_scan_256(cnt, sh, total);
     if (threadIdx.x == 0) blocksum[(size_t)b * gridDim.x + blockIdx.x] = total;
@@ -490,12 +536,16 @@ static __global__ __launch_bounds__(kScanBlock) void bitmap_count_kernel(const u
 // grid = (nblk, B): emit ascending local pids (0-based) and clear the bitmap for the next query
 // The position of a block's first candidate is the sum of the counts of the blocks before it: every block adds them up
 // itself (at most a few hundred values) instead of waiting for a scan kernel; block 0 also leaves the total in ncand.
+// FILT: the words come through the query's filter exactly as bitmap_count_kernel counted them; what is cleared is the
+// candidate bitmap (every word that was marked, whether or not the filter kept it), never the filter.
+template <bool FILT = false>
 static __global__ __launch_bounds__(kScanBlock) void bitmap_emit_kernel(uint32_t* __restrict__ bitmap,
                                                                  const int* __restrict__ blockcnt,
                                                                  uint32_t* __restrict__ cand,
                                                                  const uint32_t* __restrict__ doc_off,
                                                                  uint2* __restrict__ cand_hdr, int W,
-                                                                 size_t cand_cap, int* __restrict__ ncand) {
+                                                                 size_t cand_cap, int* __restrict__ ncand,
+                                                                 FilterOperand<FILT> fa = {}) {
     __shared__ int sh[8];
     const int b = blockIdx.y;
     int before = 0;
@@ -512,11 +562,24 @@ static __global__ __launch_bounds__(kScanBlock) void bitmap_emit_kernel(uint32_t
     uint32_t* bm = bitmap + (size_t)b * W;
     const int w0 = (blockIdx.x * kScanBlock + threadIdx.x) * kWordsPerThread;
     uint32_t w[kWordsPerThread];
+    uint32_t marked[FILT ? kWordsPerThread : 1];    // FILT: the unfiltered words, for the clearing below
     int cnt = 0;
+    if constexpr (FILT) {
+        const uint32_t* fw = fa.bits[b];
+        const bool from_filter = fw && fa.all;
+#pragma unroll
+        for (int j = 0; j < kWordsPerThread; ++j) {
+            const bool in = w0 + j < W;
+            marked[j] = in && !from_filter ? bm[w0 + j] : 0u;
+            w[j] = !fw ? marked[j] : !in ? 0u : from_filter ? fw[w0 + j] : marked[j] & fw[w0 + j];
+            cnt += __popc(w[j]);
+        }
+    } else {
 #pragma unroll
     for (int j = 0; j < kWordsPerThread; ++j) {
         w[j] = (w0 + j < W) ? bm[w0 + j] : 0u;
         cnt += __popc(w[j]);
+    }
     }
     int total;
     int pos = block_exclusive_scan_256(cnt, sh, total) + before;
@@ -525,7 +588,9 @@ static __global__ __launch_bounds__(kScanBlock) void bitmap_emit_kernel(uint32_t
 #pragma unroll
     for (int j = 0; j < kWordsPerThread; ++j) {
         uint32_t x = w[j];
-        if (x) bm[w0 + j] = 0u;
+        bool clear = x != 0u;
+        if constexpr (FILT) clear = marked[j] != 0u;
+        if (clear) bm[w0 + j] = 0u;
         while (x) {
             const int bit = __ffs((int)x) - 1;
             x &= x - 1;
@@ -538,6 +603,35 @@ static __global__ __launch_bounds__(kScanBlock) void bitmap_emit_kernel(uint32_t
             ++pos;
         }
     }
+}
+
+// Building a clb_filter.  From a pid list (as search returns them: 1-based, pid_offset added; duplicates and any order):
+// one thread per pid sets its bit, like mark_candidates_kernel; a pid outside the shard sets *err and marks nothing.
+// grid = ceil(n / 256), block = 256.
+static __global__ __launch_bounds__(256) void filter_mark_kernel(const int64_t* __restrict__ pids, int64_t n, int64_t pid_offset,
+                                                                 int n_docs, uint32_t* __restrict__ bits, int* __restrict__ err) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t p = pids[i] - pid_offset - 1;
+    if (p < 0 || p >= (int64_t)n_docs) { atomicOr(err, 1); return; }
+    atomicOr(&bits[p >> 5], 1u << (p & 31));
+}
+// ... and its population count, after clearing the bits past n_docs in the last word (a caller's bitmap is not trusted with
+// them: the emit kernel reads doc_off[pid + 1] of every set bit).  Grid-stride; one atomic per wave.
+static __global__ __launch_bounds__(256) void filter_count_kernel(uint32_t* __restrict__ bits, int W, int n_docs,
+                                                                  unsigned long long* __restrict__ count) {
+    int c = 0;
+    for (int w = blockIdx.x * 256 + threadIdx.x; w < W; w += gridDim.x * 256) {
+        uint32_t x = bits[w];
+        if (w == W - 1 && (n_docs & 31)) {
+            x &= (1u << (n_docs & 31)) - 1u;
+            bits[w] = x;
+        }
+        c += __popc(x);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, (unsigned long long)c);
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -253,7 +253,7 @@ class DeviceSearch:
                                             C.c_void_p(st)))
         return self.out_p, self.out_s
 
-    def capture(self, Qstatic):
+    def capture(self, Qstatic, filters=None, scope="candidates"):
         """A HIP graph of one search over the STATIC query buffer `Qstatic` (B, T, dim): the library enqueues nothing but
         kernels and memsets on the stream it is handed, so the nine launches of a search can be captured once and
         replayed -- write the next queries into `Qstatic` (e.g. let the encoder write there), `graph.replay()`, read
@@ -261,25 +261,35 @@ class DeviceSearch:
         no faster than the stream launches (0.171-0.184 against 0.171-0.179 ms with a new query per replay) -- the host
         enqueues the eleven launches ahead of the device either way; on a 10 M-passage index, where a search is ~20
         launches, the replay is faster (0.259 against 0.318 ms).  The
-        search runs once on a side stream first, so that the workspace is sized outside the capture."""
+        search runs once on a side stream first, so that the workspace is sized outside the capture.
+        `filters` / `scope` as in __call__: the graph holds the filters' device addresses -- keep them open while it is replayed."""
         import torch
         self._check_queries(Qstatic)
         cur = torch.cuda.current_stream(self.dev)
         side = torch.cuda.Stream(self.dev)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            self(Qstatic)
+            self(Qstatic, filters, scope)
         cur.wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self(Qstatic)
+            self(Qstatic, filters, scope)
         return graph
 
-    def __call__(self, Qdev):
-        """Qdev: torch float32 tensor holding B queries laid out (B, T, dim) contiguous == Julia (dim, T, B)."""
+    def __call__(self, Qdev, filters=None, scope="candidates"):
+        """Qdev: torch float32 tensor holding B queries laid out (B, T, dim) contiguous == Julia (dim, T, B).
+        `filters`: one PassageFilter or a sequence of B entries (None = unfiltered), `scope` "candidates" / "all"
+        (Searcher.search_batch); `ncand` then holds the counts after the filter."""
         import torch
         self._check_queries(Qdev)
         st = torch.cuda.current_stream(self.dev).cuda_stream
+        if filters is not None:
+            from .searcher import _scope_code
+            check(lib().clb_search_batch_filtered_device_slot(
+                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
+                self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)), C.c_void_p(self.out_p.data_ptr()),
+                C.c_void_p(self.out_s.data_ptr()), C.c_void_p(self.ncand.data_ptr()), C.c_void_p(st)))
+            return self.out_p, self.out_s
         check(lib().clb_search_batch_device_slot(self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T),
                                                  i64(self.B), i64(self.nprobe), i64(self.k),
                                                  C.c_void_p(self.out_p.data_ptr()), C.c_void_p(self.out_s.data_ptr()),

@@ -16,6 +16,44 @@ from ._lib import BoundsError, ColBERTError, check, colmajor, fptr, i64, lib
 from .config import ColBERTConfig
 
 
+_SCOPES = {"candidates": 0, "all": 1}      # CLB_FILTER_CANDIDATES / CLB_FILTER_ALL
+
+
+def _scope_code(scope) -> int:
+    if scope not in _SCOPES:
+        raise ColBERTError(f"scope must be 'candidates' or 'all', got {scope!r}")
+    return _SCOPES[scope]
+
+
+class PassageFilter:
+    """A set of passages resident in HBM as one bitmap (clb_filter, include/colbert_hip.h): made once by
+    `Searcher.make_filter`, reused over any number of searches of that searcher.  Keep it alive while a search that uses
+    it may still be running (or a graph that captured it may be replayed)."""
+
+    def __init__(self, searcher: "Searcher", handle, count: int):
+        self.searcher, self._h, self.count = searcher, handle, int(count)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().clb_filter_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.count
+
+
 class Searcher:
     """struct Searcher (searching.jl:1-16).  Fields that the reference holds as arrays live in HBM
     behind `self._h`; the shapes/meta are kept for introspection."""
@@ -151,13 +189,58 @@ class Searcher:
         assert c.shape == (6,)
         check(lib().clb_searcher_set_bound_consts(self._h, fptr(c)))
 
+    # -- filters ----------------------------------------------------------------------------------
+    def make_filter(self, pids=None, mask=None) -> PassageFilter:
+        """A resident passage set for filtered search.  Exactly one of: `pids`, passage ids as `search` returns them
+        (1-based, this searcher's pid_offset included; any order, duplicates allowed; outside the searcher's passages:
+        BoundsError), or `mask`, a boolean array of `num_docs` entries (entry i = local passage i + 1)."""
+        if (pids is None) == (mask is None):
+            raise ColBERTError("make_filter takes exactly one of pids= and mask=")
+        h = C.c_void_p()
+        if pids is not None:
+            p = np.ascontiguousarray(np.asarray(pids).reshape(-1), dtype=np.int64)
+            check(lib().clb_filter_create_pids(self._h, fptr(p), i64(p.size), C.byref(h)))
+        else:
+            m = np.asarray(mask)
+            if m.dtype != np.bool_ or m.shape != (self.num_docs,):
+                raise ColBERTError(f"mask must be a boolean array of num_docs={self.num_docs} entries")
+            words = np.ascontiguousarray(np.packbits(m, bitorder="little"))
+            words = np.concatenate([words, np.zeros(-words.size % 4, np.uint8)]).view("<u4")
+            check(lib().clb_filter_create_bitmap(self._h, fptr(words), i64(words.size), C.byref(h)))
+        return PassageFilter(self, h, lib().clb_filter_count(h))
+
+    def _filter_handles(self, filters, B: int):
+        """`filters` of a search call -> a ctypes array of B clb_filter handles (NULL = that query is unfiltered)."""
+        if isinstance(filters, PassageFilter):
+            filters = [filters] * B
+        filters = list(filters)
+        if len(filters) != B:
+            raise ColBERTError(f"filters must be one PassageFilter or a sequence of B={B} entries (None = unfiltered)")
+        arr = (C.c_void_p * B)()
+        for j, f in enumerate(filters):
+            if f is None:
+                continue
+            if not isinstance(f, PassageFilter) or not f._h:
+                raise ColBERTError(f"filters[{j}] is not an open PassageFilter")
+            arr[j] = f._h.value
+        return arr
+
     # -- search -----------------------------------------------------------------------------------
-    def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None):
+    def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates"):
         """search() after encode_queries (searching.jl:102-127).  Q: (dim, T) Float32.
-        Returns (pids Int64[k] 1-based, scores Float32[k])."""
+        Returns (pids Int64[k] 1-based, scores Float32[k]).
+        `filter` (a PassageFilter of this searcher): search among its passages only -- scope "candidates": the query's
+        candidates that are in the filter; "all": every passage of the filter (a re-rank of that list).  A filtered search
+        never raises for a short result: the k-vectors come back padded, entries past min(k, last_num_candidates) are
+        pid 0 / -Inf."""
         q = colmajor(Q, np.float32)
         if q.ndim != 2 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T)")
+        _scope_code(scope)
+        if filter is not None:
+            p, s, n = self.search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe, filters=[filter], scope=scope)
+            self.last_num_candidates = int(n[0])
+            return np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(s[:, 0])
         pids = np.zeros(k, dtype=np.int64); scores = np.zeros(k, dtype=np.float32)
         ncand = i64(0)
         check(lib().clb_search(self._h, fptr(q), i64(q.shape[1]), i64(nprobe or self.config.nprobe), i64(k), fptr(pids),
@@ -165,14 +248,24 @@ class Searcher:
         self.last_num_candidates = ncand.value
         return pids, scores
 
-    def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False):
-        """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B])."""
+    def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
+                     scope="candidates"):
+        """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B]).
+        `filters`: one PassageFilter for every query, or a sequence of B entries (None = that query is unfiltered); with
+        filters the results are always padded (pid 0 / -Inf past n_candidates[b], the count AFTER the filter) and `scope`
+        is "candidates" (candidates that are in the filter) or "all" (the filter's passages themselves)."""
         q = colmajor(Q, np.float32)
         if q.ndim != 3 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T, B)")
         B = q.shape[2]
+        code = _scope_code(scope)
         pids = np.zeros((k, B), dtype=np.int64, order="F"); scores = np.zeros((k, B), dtype=np.float32, order="F")
         ncand = np.zeros(B, dtype=np.int64)
+        if filters is not None:
+            handles = self._filter_handles(filters, B)
+            check(lib().clb_search_batch_filtered(self._h, fptr(q), i64(q.shape[1]), i64(B), i64(nprobe or self.config.nprobe),
+                                                  i64(k), handles, C.c_int(code), fptr(pids), fptr(scores), fptr(ncand)))
+            return pids, scores, ncand
         check(lib().clb_search_batch(self._h, fptr(q), i64(q.shape[1]), i64(B), i64(nprobe or self.config.nprobe), i64(k),
                                      C.c_int(1 if pad_short else 0), fptr(pids), fptr(scores), fptr(ncand)))
         return pids, scores, ncand
@@ -197,13 +290,14 @@ class Searcher:
         return {"pids": pids[:m].copy(), "approx": ap[:m].copy(), "exact": ex[:m].copy(), "tau": tau.value,
                 "eps": eps.value, "n_rescore": nr.value}
 
-    def search(self, query: str, k: int):
-        """search(searcher, query::String, k) (searching.jl:93-128)."""
+    def search(self, query: str, k: int, *, filter=None, scope="candidates"):
+        """search(searcher, query::String, k) (searching.jl:93-128); `filter` / `scope` as in search_embeddings."""
+        _scope_code(scope)
         if self.encoder is None:
             raise ColBERTError("no query encoder attached: pass encoder=... or use search_embeddings(Q, k)")
         Q = self.encoder.encode_queries([query])
         assert Q.shape[2] == 1 and Q.shape[1] == self.config.query_maxlen, Q.shape
-        return self.search_embeddings(Q[:, :, 0], k)
+        return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope)
 
     def text_search(self, k: int, nprobe: Optional[int] = None, graph: bool = True) -> "TextSearch":
         """A session for repeated `search(searcher, query::String, k)` calls with everything after the tokenizer on the
@@ -401,9 +495,9 @@ class TextSearch:
         self._many = None
 
 
-def search(searcher: Searcher, query, k: int):
+def search(searcher: Searcher, query, k: int, *, filter=None, scope="candidates"):
     """The reference's exported `search` (src/ColBERT.jl:40).  `query` may be a string (needs an
-    encoder) or a (dim, T) Float32 matrix of query embeddings."""
+    encoder) or a (dim, T) Float32 matrix of query embeddings.  `filter` / `scope`: Searcher.search_embeddings."""
     if isinstance(query, str):
-        return searcher.search(query, k)
-    return searcher.search_embeddings(query, k)
+        return searcher.search(query, k, filter=filter, scope=scope)
+    return searcher.search_embeddings(query, k, filter=filter, scope=scope)

@@ -167,6 +167,50 @@ int clb_searcher_get_centroid_products(const clb_searcher* s, float* max_f16_err
 int clb_searcher_get_bound_consts(const clb_searcher* s, float* consts /* 6 */);
 int clb_searcher_set_bound_consts(clb_searcher* s, const float* consts /* 6 */);
 
+/* ------------------------------------------------------------------------------------------------
+ * Filtered search: "search, but only among these passages" (no counterpart in the reference; upstream ColBERT's
+ * search(..., filter_fn=...) and search(..., pids=...)).  A clb_filter is a passage set resident in HBM as one bitmap of
+ * ceil(n_docs / 32) words -- bit i of word j = local passage 32 j + i, the layout of the candidate bitmap of retrieve()
+ * (ranking.jl:32-43) -- which the marking / compaction kernels take as one more operand: tau, eps, the re-score list and the
+ * top-k are then computed over the filtered candidates by the unchanged scoring kernels.  A filter is bound to the searcher
+ * it was made for, is created once and reused over any number of calls (one per tenant, say), and is never written by a
+ * search.  It MUST outlive every call that uses it, including calls still enqueued on a stream or captured in a graph;
+ * it may be destroyed before or after its searcher.  Creation synchronises (the population count is read back once);
+ * searching with it does not.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct clb_filter clb_filter;
+/* pids as search returns them: 1-based with the searcher's pid_offset added, n entries in any order, duplicates allowed;
+ * a pid outside pid_offset+1 .. pid_offset+n_docs is CLB_EBOUNDS.  n = 0 is the empty filter.  The bitmap is built on the
+ * device. */
+int clb_filter_create_pids(clb_searcher* s, const int64_t* pids, int64_t n, clb_filter** out);
+/* the bitmap itself (host words): n_words must be ceil(n_docs / 32), else CLB_EARGUMENT; bits past n_docs are cleared. */
+int clb_filter_create_bitmap(clb_searcher* s, const uint32_t* words, int64_t n_words, clb_filter** out);
+/* number of passages in the set (a host value, fixed at creation); 0 for a null handle */
+int64_t clb_filter_count(const clb_filter* f);
+/* a null handle is CLB_OK, like clb_searcher_destroy */
+int clb_filter_destroy(clb_filter* f);
+/* scope of a filtered search:
+ *   CLB_FILTER_CANDIDATES  candidates = retrieve(Q) INTERSECT filter (upstream's filter_fn): S1-S3 run as ever and the filter
+ *                          word is AND-ed in where the candidate bitmap is counted and written out;
+ *   CLB_FILTER_ALL         candidates = the filter's passages, whatever retrieve(Q) would give: a re-rank of a caller-chosen
+ *                          list (upstream's pids=).  nprobe is validated and otherwise unused; the workspace grows to hold
+ *                          the largest clb_filter_count of the batch per query (CLB_EUNSUPPORTED, naming the count, if it
+ *                          cannot).  A query whose entry is NULL is an ordinary unfiltered query in either scope. */
+enum { CLB_FILTER_CANDIDATES = 0, CLB_FILTER_ALL = 1 };
+/* clb_search_batch with a filter per query: `filters` is a HOST array of B handles (a NULL entry: that query is not
+ * filtered; a NULL array: none is), each made for `s` (CLB_EARGUMENT otherwise).  Short results are always padded with
+ * pid 0 / -Inf -- a filter routinely leaves fewer than k passages, which is no error -- and n_cand[b] is the number of
+ * candidates AFTER the filter.  A call in which no query is filtered launches exactly what clb_search_batch launches. */
+int clb_search_batch_filtered(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                              const clb_filter* const* filters, int scope, int64_t* out_pids, float* out_scores,
+                              int64_t* n_cand);
+/* clb_search_batch_device_slot with a filter per query: `filters` is still a HOST array, read before the call returns (the
+ * handles reach the kernels in their arguments: stream-ordered, no copy, capturable in a HIP graph -- the captured graph
+ * holds the filters' device addresses, so they must live as long as it is replayed). */
+int clb_search_batch_filtered_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                          int64_t k, const clb_filter* const* filters, int scope, int64_t* d_out_pids,
+                                          float* d_out_scores, int64_t* d_n_cand, void* hip_stream);
+
 /* retrieve()  (src/search/ranking.jl:23-44) on its own -- test hook.  out_pids needs n_docs entries. */
 int clb_retrieve(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe, int64_t* out_pids,
                  int64_t* n_out);

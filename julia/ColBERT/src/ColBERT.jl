@@ -18,7 +18,7 @@ using Logging
 using Random
 using Unicode
 
-export ColBERTConfig, Indexer, index, Searcher, search
+export ColBERTConfig, Indexer, index, Searcher, search, PassageFilter
 
 include("config.jl")
 include("capi.jl")

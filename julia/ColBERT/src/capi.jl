@@ -53,6 +53,42 @@ function _search(handle::Ptr{Cvoid}, Q::Matrix{Float32}, nprobe::Int, k::Int)
     pids, scores
 end
 
+# ---- passage filters (no counterpart in the reference; include/colbert_hip.h "Filtered search") ---------------
+"a resident passage set from pids as `search` returns them (1-based, any order, duplicates allowed)"
+function _filter_create_pids(handle::Ptr{Cvoid}, pids::Vector{Int})
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve pids begin
+        _check(ccall((:clb_filter_create_pids, libcolbert), Cint, (Ptr{Cvoid}, Ptr{Int64}, Int64, Ref{Ptr{Cvoid}}),
+            handle, pids, length(pids), h))
+    end
+    h[]
+end
+"the same from the bitmap itself: bit i of word j = passage 32 j + i + 1, ceil(num_documents / 32) words"
+function _filter_create_bitmap(handle::Ptr{Cvoid}, words::Vector{UInt32})
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve words begin
+        _check(ccall((:clb_filter_create_bitmap, libcolbert), Cint, (Ptr{Cvoid}, Ptr{UInt32}, Int64, Ref{Ptr{Cvoid}}),
+            handle, words, length(words), h))
+    end
+    h[]
+end
+_filter_count(h::Ptr{Cvoid}) = Int(ccall((:clb_filter_count, libcolbert), Int64, (Ptr{Cvoid},), h))
+_filter_destroy(h::Ptr{Cvoid}) = ccall((:clb_filter_destroy, libcolbert), Cint, (Ptr{Cvoid},), h)
+
+"search() among a filter's passages: always k entries, padded with pid 0 / -Inf32 past the candidate count (third value)"
+function _search_filtered(handle::Ptr{Cvoid}, Q::Matrix{Float32}, nprobe::Int, k::Int, filter::Ptr{Cvoid}, scope::Int)
+    pids = Vector{Int}(undef, k)
+    scores = Vector{Float32}(undef, k)
+    ncand = Ref{Int64}(0)
+    filters = Ptr{Cvoid}[filter]
+    GC.@preserve Q pids scores filters begin
+        _check(ccall((:clb_search_batch_filtered, libcolbert), Cint,
+            (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Int64, Int64, Ptr{Ptr{Cvoid}}, Cint, Ptr{Int64}, Ptr{Float32}, Ref{Int64}),
+            handle, Q, size(Q, 2), 1, nprobe, k, filters, scope, pids, scores, ncand))
+    end
+    pids, scores, Int(ncand[])
+end
+
 # ---- codec / index-build call sites (src/indexing/codecs/residual.jl, src/utils.jl, collection_indexer.jl)
 function compress(centroids::Matrix{Float32}, bucket_cutoffs::Vector{Float32}, dim::Int, nbits::Int,
         embs::AbstractMatrix{Float32}; device::Int = 0)

@@ -36,19 +36,67 @@ function Searcher(index_path::String; device::Int = 0)
 end
 
 """
-    search(searcher, query::String, k::Int) -> (pids::Vector{Int}, scores::Vector{Float32})
+    search(searcher, query::String, k::Int; filter = nothing, scope = :candidates) -> (pids::Vector{Int}, scores::Vector{Float32})
 
 Same contract as src/searching.jl:93-128: 1-based pids by descending score, ties by ascending pid; a BoundsError if
-fewer than `k` passages are candidates.
+fewer than `k` passages are candidates.  `filter` / `scope`: see the method on query embeddings below.
 """
-function search(searcher::Searcher, query::String, k::Int)
+function search(searcher::Searcher, query::String, k::Int; filter = nothing, scope::Symbol = :candidates)
     c = searcher.config
     Q = encode_queries(searcher.checkpoint, searcher.tokenizer, [query], c.dim, c.index_bsize, c.query_token,
         c.attend_to_mask_tokens, searcher.skiplist, c.query_maxlen)
     @assert size(Q)[3]==1 "size(Q): $(size(Q))"
     @assert isequal(size(Q)[2], c.query_maxlen) "size(Q): $(size(Q)), query_maxlen: $(c.query_maxlen)"
-    search(searcher, reshape(Q, size(Q, 1), size(Q, 2)), k)
+    search(searcher, reshape(Q, size(Q, 1), size(Q, 2)), k; filter = filter, scope = scope)
 end
 
-"search from query embeddings (dim, query_maxlen)"
-search(searcher::Searcher, Q::Matrix{Float32}, k::Int) = _search(searcher.handle, Q, searcher.config.nprobe, k)
+"""
+    PassageFilter(searcher; pids)            # or: PassageFilter(searcher; mask)
+
+A set of passages resident on the device, for `search(...; filter = f)`: `pids` as `search` returns them (1-based, any
+order, duplicates allowed; outside 1:num_documents is a BoundsError), or `mask`, one Bool per passage.  Made once,
+reused over any number of searches of that searcher; freed by its finalizer (after or before the searcher's).
+"""
+mutable struct PassageFilter
+    searcher::Searcher          # keeps the searcher alive as long as the filter
+    handle::Ptr{Cvoid}
+    count::Int
+    function PassageFilter(searcher::Searcher; pids::Union{Nothing, AbstractVector{<:Integer}} = nothing,
+            mask::Union{Nothing, AbstractVector{Bool}} = nothing)
+        isnothing(pids) == isnothing(mask) && throw(ArgumentError("PassageFilter takes exactly one of pids and mask"))
+        if isnothing(pids)
+            length(mask) == searcher.num_documents ||
+                throw(ArgumentError("mask must have num_documents = $(searcher.num_documents) entries"))
+            words = zeros(UInt32, cld(length(mask), 32))
+            for i in findall(mask)
+                words[(i - 1) >> 5 + 1] |= UInt32(1) << ((i - 1) & 31)
+            end
+            handle = _filter_create_bitmap(searcher.handle, words)
+        else
+            handle = _filter_create_pids(searcher.handle, Vector{Int}(pids))
+        end
+        f = new(searcher, handle, _filter_count(handle))
+        finalizer(f -> _filter_destroy(f.handle), f)
+    end
+end
+Base.length(f::PassageFilter) = f.count
+
+_filter_scope(scope::Symbol) = scope === :candidates ? 0 : scope === :all ? 1 :
+                               throw(ArgumentError("scope must be :candidates or :all, got $(repr(scope))"))
+
+"""
+    search(searcher, Q::Matrix{Float32}, k; filter = nothing, scope = :candidates)
+
+Search from query embeddings (dim, query_maxlen).  With a `PassageFilter` only its passages are ranked -- `scope =
+:candidates`: the query's candidates that are in the filter; `:all`: every passage of the filter (a re-rank of that
+list) -- and a short result is not an error: both vectors have k entries, padded with pid 0 / -Inf32.
+"""
+function search(searcher::Searcher, Q::Matrix{Float32}, k::Int; filter::Union{Nothing, PassageFilter} = nothing,
+        scope::Symbol = :candidates)
+    sc = _filter_scope(scope)
+    isnothing(filter) && return _search(searcher.handle, Q, searcher.config.nprobe, k)
+    GC.@preserve filter begin
+        pids, scores, _ = _search_filtered(searcher.handle, Q, searcher.config.nprobe, k, filter.handle, sc)
+    end
+    pids, scores
+end
