@@ -76,13 +76,7 @@ struct Workspace {
     bool x1_table = false;      // the score table in cells_q came from the single-fp16-product kernel: the bound carries its terms
     bool have_range = false;    // tscale holds this batch's measured score ranges (the batched centroid kernel ran)
     bool cell8 = false;         // pass 1 gathers from cells8: 32-byte rows of 8-bit cells requantised from cells_q by tscale
-    bool stats_keep = false;    // set for the 2nd, 3rd ... sub-batch of one call: the work counters accumulate over the call
-    // filtered search: the handles of the running sub-batch (a HOST array, one entry per query, nullptr = unfiltered) and
-    // their scope; set by the filtered entry points around run_search, nullptr whenever no query of the sub-batch is filtered
-    const clb_filter* const* filt = nullptr;
-    int filt_all = 0;
     size_t filt_cap = 0;        // largest filter population a CLB_FILTER_ALL call has asked this slot to hold (cand_cap covers it)
-    size_t filt_now = 0;        // ... and the running call's
     size_t ivf_cap = 0;         // cand_cap before filt_cap was taken into account: the most candidates the IVF lists can give
     // two-phase sharded search: what clb_search_shard_phase1 left behind (phase 2 must continue exactly that batch)
     struct { bool valid = false; const float* dQ = nullptr; int64_t T = 0, B = 0, nprobe = 0, k = 0; void* stream = nullptr; } pending;
@@ -124,7 +118,6 @@ struct clb_searcher {
                               // -1 by the handle's role: yes on a shard of a group (bounds_synced: the centroid stage is replicated on every
                               // shard while the pass-2 rows its wider bound adds are divided among them), no on a single GPU, where
                               // -0.020 ms on the centroid kernel meets +0.01-0.02 ms on pass 2 (profiles/r05_experiments.md)
-    int s1_mode = 1;    // 1: bf16x3 + exact refine, 0: fp32 MFMA
     int gather_lds = 0; // pass 1: score rows through LDS-DMA, four adjacent lanes per row (0: the per-lane VGPR gather); set at load
     double code_adjacency = 0.0;   // fraction of consecutive embeddings that share a 128-B line of the score table
     int cell8 = -1;     // batches of 16+ queries: score rows as 32 bytes of 8-bit cells?  1 yes, 0 / -1 (default) fp16 rows.  On the
@@ -139,13 +132,35 @@ struct clb_searcher {
 
 namespace {
 
+// One sub-batch as run_search and its helpers are asked to run it.  It lives on the caller's stack: what belongs to a call
+// never outlives it in the Workspace.
+struct Batch {
+    const float* dQ = nullptr;  // [B][T][dim] on the device
+    int B = 0, T = 0, nprobe = 0, k = 0;
+    int64_t* d_out_pids = nullptr; float* d_out_scores = nullptr; int64_t* d_n_cand = nullptr;
+    // filtered search: the handles of the sub-batch (a HOST array, one entry per query, nullptr = unfiltered; nullptr
+    // altogether when no query of the sub-batch is filtered: it then launches the unfiltered kernels), their scope, and
+    // the largest filter population of the CLB_FILTER_ALL call this sub-batch belongs to
+    const clb_filter* const* filt = nullptr;
+    int filt_all = 0;
+    size_t filt_now = 0;
+    bool stats_keep = false;    // the 2nd, 3rd ... sub-batch of one call: the work counters accumulate over the call
+    int phase = 0, n_shards = 0;    // two-phase sharded search (run_search)
+    float* d_local_top = nullptr; const float* d_all_top = nullptr;
+};
+Batch make_batch(const float* dQ, int64_t B, int64_t T, int64_t nprobe, int64_t k) {
+    Batch q;
+    q.dQ = dQ; q.B = (int)B; q.T = (int)T; q.nprobe = (int)nprobe; q.k = (int)k;
+    return q;
+}
+
 struct Timed {
     clb_searcher* s;
-    int id;
+    int id;                 // a KernelId; negative: the scope times nothing and leaves the event chain alone
     hipStream_t st;
     hipEvent_t a = nullptr, b = nullptr;
     Timed(clb_searcher* s_, int id_, hipStream_t st_) : s(s_), id(id_), st(st_) {
-        if (s->prof.on) {
+        if (s->prof.on && id >= 0) {
             if (s->prof.chain && s->prof.chain_stream == st) {
                 a = s->prof.chain;
             } else {
@@ -156,7 +171,7 @@ struct Timed {
         }
     }
     ~Timed() {
-        if (!s->prof.on) return;
+        if (!s->prof.on || id < 0) return;
         if (a && b && hipEventRecord(b, st) == hipSuccess) {
             s->prof.pending[id].push_back({a, b});
             s->prof.chain = b;
@@ -170,6 +185,8 @@ struct Timed {
 
 // token tiles of 32 for the cells table: Tpad in {32, 64, 128} so that it divides the 256-thread scan
 inline int token_tiles(int64_t T) { return T <= 32 ? 1 : T <= 64 ? 2 : 4; }
+// entries per token of the selection buffer: the top-nprobe kernels come in widths 2, 8 and 32; beyond that a sort selects
+inline int64_t padded_nprobe(int64_t nprobe) { return nprobe <= 2 ? 2 : nprobe <= 8 ? 8 : nprobe <= 32 ? 32 : nprobe; }
 
 // 8-bit score rows for this handle's batches of 16+ queries?
 // (round 6: only when asked for -- measured end to end the format loses on all four workloads, profiles/r06_experiments.md)
@@ -180,7 +197,7 @@ void allow_large_topk_lds() {
     allow_dynamic_lds(reinterpret_cast<const void*>(topk_kernel), (int)(sizeof(unsigned long long) * kMaxTopK));
 }
 
-constexpr int64_t kSubBatch = 64;      // queries per pass of the single-call search entry points (see clb_search_batch_device_slot)
+constexpr int64_t kSubBatch = 64;      // queries per pass of the single-call search entry points (see for_sub_batches)
 
 int next_pow2(int x) {
     int p = 1;
@@ -215,7 +232,7 @@ int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, 
     w.W = (int)((s->n_docs + 31) / 32);
     w.nblk_bitmap = (w.W + kScanBlock * kWordsPerThread - 1) / (kScanBlock * kWordsPerThread);
     w.topn_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(256, s->K / 512));
-    const int64_t NPs = nprobe <= 2 ? 2 : nprobe <= 8 ? 8 : nprobe <= 32 ? 32 : nprobe;
+    const int64_t NPs = padded_nprobe(nprobe);
     const bool general = s->generic;
     CLB_TRY(w.Qdev.ensure(sizeof(float) * B * T * s->dim));
     // the fp32 T x K score matrix is only materialised by the unfused S1/S2 path (nprobe > 2 or T > 32)
@@ -294,12 +311,26 @@ void launch_score_exact(clb_searcher* s, Workspace& w, hipStream_t st, const flo
 int select_by_sort(clb_searcher* s, Workspace& w, hipStream_t st, const float* cells, size_t stride_t, size_t stride_c,
                    int T, int nprobe, int NP, int* sel_b);
 
-// Candidate generation S1-S3 for B queries on stream st; leaves cand/ncand on the device.
-int mark_and_compact(clb_searcher* s, Workspace& w, hipStream_t st, int B, int T, int Tpad, int NPs, int nprobe);
+// S2 from the fp32 score matrix w.cells ([b][centroid][Tpad]): the top nprobe centroids of every token of B queries to w.sel
+int select_top_nprobe(clb_searcher* s, Workspace& w, hipStream_t st, int B, int T, int Tpad, int nprobe) {
+    const int NPs = (int)padded_nprobe(nprobe);
+    if (NPs == 2) launch_topn<2>(s, w, st, B, Tpad);
+    else if (NPs == 8) launch_topn<8>(s, w, st, B, Tpad);
+    else if (NPs == 32) launch_topn<32>(s, w, st, B, Tpad);
+    else   // nprobe > 32: stable sort of every token's K scores (one query at a time)
+        for (int b = 0; b < B; ++b)
+            CLB_TRY(select_by_sort(s, w, st, w.cells.as<float>() + (size_t)b * s->K * Tpad, 1, (size_t)Tpad, T, nprobe, NPs,
+                                   w.sel.as<int>() + (size_t)b * Tpad * NPs));
+    return CLB_OK;
+}
 
-int run_retrieve(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, int B, int T, int nprobe) {
+int mark_and_compact(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int B, int Tpad, int NPs, bool timed);
+
+// Candidate generation S1-S3 for the queries of q on stream st; leaves cand/ncand on the device.
+int run_retrieve(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
+    const float* dQ = q.dQ;
+    const int B = q.B, T = q.T, nprobe = q.nprobe;
     const int TT = token_tiles(T), Tpad = TT * 32;
-    const int NPs = nprobe <= 2 ? 2 : nprobe <= 8 ? 8 : nprobe <= 32 ? 32 : nprobe;
     const int n_tiles = (int)((s->K + 31) / 32);
     const bool want_half = s->mode == 1 && s->approx_ok && T <= 32;
     w.x1_table = false;
@@ -310,7 +341,7 @@ int run_retrieve(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ,
         // batches of 8+ queries share each staged centroid tile between 8 queries (centroid_top_bf16x3_mq_kernel)
         // (from 6 queries: the shared-tile kernel with two idle query slots, 0.047 ms, beats six or seven per-query passes
         // over the table, 0.06-0.07 ms)
-        const bool mq = s->s1_mode == 1 && s->cent_hi.p && B >= 6;
+        const bool mq = B >= 6;
         const int groups = (B + kMqQueries - 1) / kMqQueries;
         int gx = mq ? std::max(1, std::min(n_tiles, std::min(256, std::max(512 / groups, 16))))
                           : std::max(1, std::min(n_tiles / 2 + 1, std::min(256, std::max(1024 / std::max(1, B), 16))));
@@ -330,72 +361,52 @@ int run_retrieve(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ,
         }
         const int nslots = mq ? gx * 2 : gx * 4;
         CLB_TRY(w.partial.ensure(sizeof(ValIdx) * (size_t)B * nslots * 32 * kTopPartial));
-        const size_t lds_f32 = 2 * 32 * kCentTileStride * sizeof(float);
-        if (s->s1_mode == 1 && s->cent_hi.p) {
-            if (w.redo.bytes < sizeof(int) * B) {          // cumulative fallback counter (statistics only)
-                CLB_TRY(w.redo.ensure(sizeof(int) * B));
-                CLB_HIP(hipMemsetAsync(w.redo.p, 0, w.redo.bytes, st));
-            }
-            {
-                Timed t(s, KID_CENTROID_SCORES, st);
-                const size_t lds_b16 = 2 * 2 * 32 * kRowBytes16;
-                if (teams) {
-                    // 66 KB of dynamic LDS: above the 64-KB default limit of a launch
-                    auto kern = x1 ? (w.cell8 ? centroid_top_bf16x3_teams_kernel<true, true> : centroid_top_bf16x3_teams_kernel<true, false>)
-                                   : (w.cell8 ? centroid_top_bf16x3_teams_kernel<false, true> : centroid_top_bf16x3_teams_kernel<false, false>);
-                    allow_dynamic_lds(reinterpret_cast<const void*>(kern), 2 * 2 * 32 * kRowBytes16 + 8 * 4096);
-                    hipLaunchKernelGGL(kern, dim3(gx, team_groups), dim3(512), lds_b16 + 8 * 4096, st,
-                                       x1 ? s->cent_f16.as<uint16_t>() : s->cent_hi.as<uint16_t>(),
-                                       x1 ? (const uint16_t*)nullptr : (const uint16_t*)s->cent_lo.as<uint16_t>(), dQ,
-                                       w.partial.as<ValIdx>(), w.cells_q.as<uint32_t>(), (int)s->K, T, B, n_tiles,
-                                       w.rangep.as<float2>());
-                    if (w.cell8) {     // 8-bit rows: every token's measured score range, then the table rewritten by it
-                        hipLaunchKernelGGL(token_range_kernel, dim3(B), dim3(1024), 0, st, (const float2*)w.rangep.as<float2>(), gx, T,
-                                           w.tscale.as<float4>());
-                        hipLaunchKernelGGL(requantise_cells_kernel, dim3(std::max(1, 2048 / B), B), dim3(256), 0, st,
-                                           (const uint32_t*)w.cells_q.as<uint32_t>(), (const float4*)w.tscale.as<float4>(),
-                                           w.cells8.as<uint32_t>(), (int)s->K);
-                    }
-                } else if (mq && want_half)
-                    hipLaunchKernelGGL(centroid_top_bf16x3_mq_kernel<true>, dim3(gx, groups), dim3(256), lds_b16 + 4 * 2048, st,
-                                       s->cent_hi.as<uint16_t>(), s->cent_lo.as<uint16_t>(), dQ,
-                                       w.partial.as<ValIdx>(), w.cells_q.as<uint32_t>(), (int)s->K, T, B, n_tiles);
-                else if (mq)
-                    hipLaunchKernelGGL(centroid_top_bf16x3_mq_kernel<false>, dim3(gx, groups), dim3(256), lds_b16, st,
-                                       s->cent_hi.as<uint16_t>(), s->cent_lo.as<uint16_t>(), dQ,
-                                       w.partial.as<ValIdx>(), (uint32_t*)nullptr, (int)s->K, T, B, n_tiles);
-                else if (want_half)
-                    hipLaunchKernelGGL(centroid_top_bf16x3_kernel<true>, dim3(gx, B), dim3(128), lds_b16 + 2 * 2048, st,
-                                       s->cent_hi.as<uint16_t>(), s->cent_lo.as<uint16_t>(), dQ,
-                                       w.partial.as<ValIdx>(), w.cells_q.as<uint32_t>(), (int)s->K, T, n_tiles);
-                else
-                    hipLaunchKernelGGL(centroid_top_bf16x3_kernel<false>, dim3(gx, B), dim3(128), lds_b16, st,
-                                       s->cent_hi.as<uint16_t>(), s->cent_lo.as<uint16_t>(), dQ,
-                                       w.partial.as<ValIdx>(), (uint32_t*)nullptr, (int)s->K, T, n_tiles);
-            }
-            {
-                Timed t(s, KID_TOPN, st);
-                hipLaunchKernelGGL(top_refine_kernel, dim3(32, B), dim3(64), 0, st, w.partial.as<ValIdx>(),
-                                   s->centroids.as<float>(), dQ, T, (int)s->K, nslots, s->approx_consts.cn_max,
-                                   w.sel.as<int>(), w.redo.as<int>(), x1 ? s->dc_f16 : 0.f);
-            }
-        } else {
-            {
-                Timed t(s, KID_CENTROID_SCORES, st);
-                if (want_half)
-                    hipLaunchKernelGGL(centroid_top2_kernel<true>, dim3(gx, B), dim3(128), lds_f32, st,
-                                       s->centroids.as<float>(), dQ, w.partial.as<ValIdx>(),
-                                       w.cells_q.as<uint32_t>(), (int)s->K, T, n_tiles, (const int*)nullptr);
-                else
-                    hipLaunchKernelGGL(centroid_top2_kernel<false>, dim3(gx, B), dim3(128), lds_f32, st,
-                                       s->centroids.as<float>(), dQ, w.partial.as<ValIdx>(), (uint32_t*)nullptr,
-                                       (int)s->K, T, n_tiles, (const int*)nullptr);
-            }
-            {
-                Timed t(s, KID_TOPN, st);
-                hipLaunchKernelGGL(top2_merge_kernel, dim3(32, B), dim3(64), 0, st, w.partial.as<ValIdx>(),
-                                   w.sel.as<int>(), nslots, (const int*)nullptr);
-            }
+        if (w.redo.bytes < sizeof(int) * B) {          // cumulative fallback counter (statistics only)
+            CLB_TRY(w.redo.ensure(sizeof(int) * B));
+            CLB_HIP(hipMemsetAsync(w.redo.p, 0, w.redo.bytes, st));
+        }
+        {
+            Timed t(s, KID_CENTROID_SCORES, st);
+            const size_t lds_b16 = 2 * 2 * 32 * kRowBytes16;
+            if (teams) {
+                // 66 KB of dynamic LDS: above the 64-KB default limit of a launch
+                auto kern = x1 ? (w.cell8 ? centroid_top_bf16x3_teams_kernel<true, true> : centroid_top_bf16x3_teams_kernel<true, false>)
+                               : (w.cell8 ? centroid_top_bf16x3_teams_kernel<false, true> : centroid_top_bf16x3_teams_kernel<false, false>);
+                allow_dynamic_lds(reinterpret_cast<const void*>(kern), 2 * 2 * 32 * kRowBytes16 + 8 * 4096);
+                hipLaunchKernelGGL(kern, dim3(gx, team_groups), dim3(512), lds_b16 + 8 * 4096, st,
+                                   x1 ? s->cent_f16.as<uint16_t>() : s->cent_hi.as<uint16_t>(),
+                                   x1 ? (const uint16_t*)nullptr : (const uint16_t*)s->cent_lo.as<uint16_t>(), dQ,
+                                   w.partial.as<ValIdx>(), w.cells_q.as<uint32_t>(), (int)s->K, T, B, n_tiles,
+                                   w.rangep.as<float2>());
+                if (w.cell8) {     // 8-bit rows: every token's measured score range, then the table rewritten by it
+                    hipLaunchKernelGGL(token_range_kernel, dim3(B), dim3(1024), 0, st, (const float2*)w.rangep.as<float2>(), gx, T,
+                                       w.tscale.as<float4>());
+                    hipLaunchKernelGGL(requantise_cells_kernel, dim3(std::max(1, 2048 / B), B), dim3(256), 0, st,
+                                       (const uint32_t*)w.cells_q.as<uint32_t>(), (const float4*)w.tscale.as<float4>(),
+                                       w.cells8.as<uint32_t>(), (int)s->K);
+                }
+            } else if (mq && want_half)
+                hipLaunchKernelGGL(centroid_top_bf16x3_mq_kernel<true>, dim3(gx, groups), dim3(256), lds_b16 + 4 * 2048, st,
+                                   s->cent_hi.as<uint16_t>(), s->cent_lo.as<uint16_t>(), dQ,
+                                   w.partial.as<ValIdx>(), w.cells_q.as<uint32_t>(), (int)s->K, T, B, n_tiles);
+            else if (mq)
+                hipLaunchKernelGGL(centroid_top_bf16x3_mq_kernel<false>, dim3(gx, groups), dim3(256), lds_b16, st,
+                                   s->cent_hi.as<uint16_t>(), s->cent_lo.as<uint16_t>(), dQ,
+                                   w.partial.as<ValIdx>(), (uint32_t*)nullptr, (int)s->K, T, B, n_tiles);
+            else if (want_half)
+                hipLaunchKernelGGL(centroid_top_bf16x3_kernel<true>, dim3(gx, B), dim3(128), lds_b16 + 2 * 2048, st,
+                                   s->cent_hi.as<uint16_t>(), s->cent_lo.as<uint16_t>(), dQ,
+                                   w.partial.as<ValIdx>(), w.cells_q.as<uint32_t>(), (int)s->K, T, n_tiles);
+            else
+                hipLaunchKernelGGL(centroid_top_bf16x3_kernel<false>, dim3(gx, B), dim3(128), lds_b16, st,
+                                   s->cent_hi.as<uint16_t>(), s->cent_lo.as<uint16_t>(), dQ,
+                                   w.partial.as<ValIdx>(), (uint32_t*)nullptr, (int)s->K, T, n_tiles);
+        }
+        {
+            Timed t(s, KID_TOPN, st);
+            hipLaunchKernelGGL(top_refine_kernel, dim3(32, B), dim3(64), 0, st, w.partial.as<ValIdx>(),
+                               s->centroids.as<float>(), dQ, T, (int)s->K, nslots, s->approx_consts.cn_max,
+                               w.sel.as<int>(), w.redo.as<int>(), x1 ? s->dc_f16 : 0.f);
         }
     } else {
         {
@@ -407,41 +418,42 @@ int run_retrieve(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ,
         }
         {
             Timed t(s, KID_TOPN, st);
-            if (NPs == 2) launch_topn<2>(s, w, st, B, Tpad);
-            else if (NPs == 8) launch_topn<8>(s, w, st, B, Tpad);
-            else if (NPs == 32) launch_topn<32>(s, w, st, B, Tpad);
-            else   // nprobe > 32: stable sort of every token's K scores (one query at a time)
-                for (int b = 0; b < B; ++b)
-                    CLB_TRY(select_by_sort(s, w, st, w.cells.as<float>() + (size_t)b * s->K * Tpad, 1, (size_t)Tpad, T,
-                                           nprobe, NPs, w.sel.as<int>() + (size_t)b * Tpad * NPs));
+            CLB_TRY(select_top_nprobe(s, w, st, B, T, Tpad, nprobe));
         }
         s->prof.chain = nullptr;   // untimed conversion below
         if (want_half)
             hipLaunchKernelGGL(cells_to_half_kernel, dim3(std::max(1, 1024 / B), B), dim3(256), 0, st,
                                w.cells.as<float>(), w.cells_q.as<uint32_t>(), (int)s->K);
     }
-    return mark_and_compact(s, w, st, B, T, Tpad, NPs, nprobe);
+    return mark_and_compact(s, w, st, q, 0, B, Tpad, (int)padded_nprobe(nprobe), /*timed=*/true);
 }
 
-// S3: the union of the selected IVF lists as an ascending pid list + passage headers, for B queries (w.sel -> w.cand,
-// w.cand_hdr, w.ncand); shared by the tuned and the general-shape path
-// the filter operand of queries b0 .. b0 + n - 1 of the running sub-batch
-FilterArgs filter_args(const Workspace& w, int b0, int n) {
+// the filter operand of queries b0 .. b0 + n - 1 of the sub-batch: query b0 is entry 0, as a launch over those queries counts
+FilterArgs filter_args(const Batch& q, int b0, int n) {
     FilterArgs fa{};
-    for (int i = 0; i < n && i < kFilterQueries; ++i) fa.bits[i] = w.filt[b0 + i] ? w.filt[b0 + i]->bits.as<uint32_t>() : nullptr;
-    fa.all = w.filt_all;
+    for (int i = 0; i < n && i < kFilterQueries; ++i) fa.bits[i] = q.filt[b0 + i] ? q.filt[b0 + i]->bits.as<uint32_t>() : nullptr;
+    fa.all = q.filt_all;
     return fa;
 }
-inline NoFilter filter_operand(std::false_type, const Workspace&, int, int) { return {}; }
-inline FilterArgs filter_operand(std::true_type, const Workspace& w, int b0, int n) { return filter_args(w, b0, n); }
 
-// FILT: some query of the sub-batch carries a filter (S3f) -- the same launches with the filter operand; false: the
+// S3: the union of the selected IVF lists as an ascending pid list + passage headers, for the B queries from b0 on
+// (w.sel, entries 0 .. B - 1 of Tpad x NPs -> cand, cand_hdr, ncand of queries b0 ...); shared by the tuned and the
+// general-shape path, whose per-query loop calls it one query at a time and untimed
+// FILT: some query of the launch carries a filter (S3f) -- the same launches with the filter operand; false: the
 // unfiltered kernels, launched as ever
 template <bool FILT>
-int mark_and_compact_impl(clb_searcher* s, Workspace& w, hipStream_t st, int B, int T, int Tpad, int NPs, int nprobe) {
+int mark_and_compact_impl(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int B, int Tpad, int NPs,
+                          bool timed) {
     static_assert(kScanBlock * kWordsPerThread == 1024, "mark_count_kernel writes 1024-word count blocks");
     static_assert(kSubBatch <= kFilterQueries, "the filter handles of a sub-batch travel in one kernel argument block");
-    const auto fa = filter_operand(std::integral_constant<bool, FILT>(), w, 0, B);
+    FilterOperand<FILT> fa{};
+    if constexpr (FILT) fa = filter_args(q, b0, B);
+    const int T = q.T, nprobe = q.nprobe;
+    uint32_t* bitmap = w.bitmap.as<uint32_t>() + (size_t)b0 * w.W;
+    int* blocksum = w.blocksum.as<int>() + (size_t)b0 * w.nblk_bitmap;
+    uint32_t* cand = w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap;
+    uint2* cand_hdr = w.cand_hdr.as<uint2>() + (size_t)b0 * w.cand_cap;
+    int* ncand = w.ncand.as<int>() + b0;
     const int nslices = (w.nblk_bitmap + kMarkSliceBlocks - 1) / kMarkSliceBlocks;
     const int nslices_big = (w.nblk_bitmap + kMarkSliceBlocksBig - 1) / kMarkSliceBlocksBig;
     // every slice re-reads the query's lists: beyond 16 slices (2 M passages per shard) that costs more than the atomics
@@ -450,48 +462,45 @@ int mark_and_compact_impl(clb_searcher* s, Workspace& w, hipStream_t st, int B, 
     // 64 one-list work-groups of the atomic path finish sooner (one query: 8 us against 27)
     const bool sliced = (nslices <= 16 || s->ivf_sorted) && B >= 8;
     {
-        Timed t(s, KID_MARK, st);
+        Timed t(s, timed ? KID_MARK : -1, st);
         if (sliced && nslices <= 16)     // mark + per-block counts, the bitmap slice of a work-group in LDS (no global atomics)
             hipLaunchKernelGGL((mark_count_kernel<false, kMarkSliceBlocks, FILT>), dim3(nslices, B), dim3(1024), 0, st, w.sel.as<int>(),
-                               s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), w.bitmap.as<uint32_t>(),
-                               w.blocksum.as<int>(), T, Tpad, NPs, nprobe, w.W, w.nblk_bitmap, (const uint32_t*)nullptr, fa);
+                               s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), bitmap, blocksum, T, Tpad, NPs, nprobe, w.W,
+                               w.nblk_bitmap, (const uint32_t*)nullptr, fa);
         else if (sliced) {
             const int nb = T * nprobe * (nslices_big + 1);
             hipLaunchKernelGGL(slice_bounds_kernel, dim3((nb + 255) / 256, B), dim3(256), 0, st, w.sel.as<int>(),
                                s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), T, Tpad, NPs, nprobe, nslices_big,
                                (uint32_t)(kMarkSliceBlocksBig * 1024 * 32), w.bounds.as<uint32_t>());
             hipLaunchKernelGGL((mark_count_kernel<true, kMarkSliceBlocksBig, FILT>), dim3(nslices_big, B), dim3(1024), 0, st,
-                               w.sel.as<int>(), s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), w.bitmap.as<uint32_t>(),
-                               w.blocksum.as<int>(), T, Tpad, NPs, nprobe, w.W, w.nblk_bitmap,
-                               (const uint32_t*)w.bounds.as<uint32_t>(), fa);
+                               w.sel.as<int>(), s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), bitmap, blocksum, T, Tpad,
+                               NPs, nprobe, w.W, w.nblk_bitmap, (const uint32_t*)w.bounds.as<uint32_t>(), fa);
         } else
             hipLaunchKernelGGL(mark_candidates_kernel<FILT>, dim3(T * nprobe, B), dim3(256), 0, st, w.sel.as<int>(),
-                               s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), w.bitmap.as<uint32_t>(), T,
-                               Tpad, NPs, nprobe, w.W, fa);
+                               s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), bitmap, T, Tpad, NPs, nprobe, w.W, fa);
     }
     {
-        Timed t(s, KID_COMPACT, st);
+        Timed t(s, timed ? KID_COMPACT : -1, st);
         if (!sliced)
-            hipLaunchKernelGGL(bitmap_count_kernel<FILT>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st,
-                               w.bitmap.as<uint32_t>(), w.blocksum.as<int>(), w.W, fa);
+            hipLaunchKernelGGL(bitmap_count_kernel<FILT>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st, bitmap, blocksum, w.W, fa);
         // after the sliced marking the bitmap already holds marked AND filter: only a filter that IS the candidate set
         // (CLB_FILTER_ALL) still has to reach the emit kernel
-        if (FILT && (!sliced || w.filt_all))
-            hipLaunchKernelGGL(bitmap_emit_kernel<FILT>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st,
-                               w.bitmap.as<uint32_t>(), w.blocksum.as<int>(), w.cand.as<uint32_t>(),
-                               s->doc_off.as<uint32_t>(), w.cand_hdr.as<uint2>(), w.W, w.cand_cap, w.ncand.as<int>(), fa);
+        if (FILT && (!sliced || q.filt_all))
+            hipLaunchKernelGGL(bitmap_emit_kernel<FILT>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st, bitmap, blocksum, cand,
+                               s->doc_off.as<uint32_t>(), cand_hdr, w.W, w.cand_cap, ncand, fa);
         else
-        hipLaunchKernelGGL(bitmap_emit_kernel<false>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st,
-                           w.bitmap.as<uint32_t>(), w.blocksum.as<int>(), w.cand.as<uint32_t>(),
-                           s->doc_off.as<uint32_t>(), w.cand_hdr.as<uint2>(), w.W, w.cand_cap, w.ncand.as<int>());
+            hipLaunchKernelGGL(bitmap_emit_kernel<false>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st, bitmap, blocksum, cand,
+                               s->doc_off.as<uint32_t>(), cand_hdr, w.W, w.cand_cap, ncand);
     }
     CLB_HIP(hipGetLastError());
     return CLB_OK;
 }
 
-int mark_and_compact(clb_searcher* s, Workspace& w, hipStream_t st, int B, int T, int Tpad, int NPs, int nprobe) {
-    return w.filt ? mark_and_compact_impl<true>(s, w, st, B, T, Tpad, NPs, nprobe)
-                  : mark_and_compact_impl<false>(s, w, st, B, T, Tpad, NPs, nprobe);
+int mark_and_compact(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int B, int Tpad, int NPs, bool timed) {
+    bool filt = false;
+    for (int b = b0; q.filt && b < b0 + B; ++b) filt |= q.filt[b] != nullptr;
+    return filt ? mark_and_compact_impl<true>(s, w, st, q, b0, B, Tpad, NPs, timed)
+                : mark_and_compact_impl<false>(s, w, st, q, b0, B, Tpad, NPs, timed);
 }
 
 int check_search_args(clb_searcher* s, int64_t T, int64_t B, int64_t nprobe, int64_t k) {
@@ -528,8 +537,8 @@ int select_by_sort(clb_searcher* s, Workspace& w, hipStream_t st, const float* c
 // emit kernel writes the short-result flag and the candidate count; rocPRIM's temporary storage lives in the workspace
 // slot (g_sort_tmp, sized on first use), so the sort is only enqueued -- no allocation and no host synchronisation per
 // query.  The price of keeping the count on the device: the sort covers cand_cap keys, not the query's own count.
-int topk_by_sort(clb_searcher* s, Workspace& w, hipStream_t st, int b, const int* list, const int* nlist, int k,
-                 int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand) {
+int topk_by_sort(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b, const int* list, const int* nlist) {
+    const int k = q.k;
     const int cap = (int)w.cand_cap;
     const float* sc = w.scores.as<float>() + (size_t)b * w.cand_cap;
     const int* lst = list ? list + (size_t)b * w.cand_cap : nullptr;
@@ -541,107 +550,83 @@ int topk_by_sort(clb_searcher* s, Workspace& w, hipStream_t st, int b, const int
     CLB_TRY(sort_keys_u64(w.g_keys.as<uint64_t>(), w.g_keys2.as<uint64_t>(), (size_t)cap, st, &w.g_sort_tmp));
     hipLaunchKernelGGL(generic_topk_emit_kernel, dim3((std::max(k, 1) + 255) / 256), dim3(256), 0, st,
                        w.g_keys2.as<unsigned long long>(), sc, w.cand.as<uint32_t>() + (size_t)b * w.cand_cap, lst, n_ptr,
-                       w.ncand.as<int>() + b, k, s->pid_offset, d_out_pids + (size_t)b * k, d_out_scores + (size_t)b * k,
-                       w.flags.as<int>() + b, d_n_cand ? d_n_cand + b : nullptr);
+                       w.ncand.as<int>() + b, k, s->pid_offset, q.d_out_pids + (size_t)b * k, q.d_out_scores + (size_t)b * k,
+                       w.flags.as<int>() + b, q.d_n_cand ? q.d_n_cand + b : nullptr);
     CLB_HIP(hipGetLastError());
     return CLB_OK;
 }
 
-// S1-S3 of ONE query on the general-shape path: leaves cand / cand_hdr / ncand of slot b
-int run_retrieve_general(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, int b, int T, int nprobe) {
-    const float* q = dQ + (size_t)b * T * s->dim;
-    CLB_TRY(w.g_cells.ensure(sizeof(float) * (size_t)T * s->K));
-    hipLaunchKernelGGL(generic_cells_kernel, dim3((unsigned)((s->K + 127) / 128), T), dim3(128), sizeof(float) * s->dim, st,
-                       s->centroids.as<float>(), q, (int)s->dim, (int)s->K, w.g_cells.as<float>());
-    int* sel_b = w.sel.as<int>();                 // one query at a time: slot 0 of the selection buffer
-    CLB_TRY(select_by_sort(s, w, st, w.g_cells.as<float>(), (size_t)s->K, 1, T, nprobe, nprobe, sel_b));
-    uint32_t* bm = w.bitmap.as<uint32_t>() + (size_t)b * w.W;
-    int* bs = w.blocksum.as<int>() + (size_t)b * w.nblk_bitmap;
-    if (w.filt && w.filt[b]) {      // S3f: this query's filter as entry 0 of the operand (the launches are one query wide)
-        const FilterArgs fa = filter_args(w, b, 1);
-        hipLaunchKernelGGL(mark_candidates_kernel<true>, dim3(T * nprobe, 1), dim3(256), 0, st, sel_b, s->ivf_off.as<uint32_t>(),
-                           s->ivf_pid.as<uint32_t>(), bm, T, T, nprobe, nprobe, w.W, fa);
-        hipLaunchKernelGGL(bitmap_count_kernel<true>, dim3(w.nblk_bitmap, 1), dim3(kScanBlock), 0, st, bm, bs, w.W, fa);
-        hipLaunchKernelGGL(bitmap_emit_kernel<true>, dim3(w.nblk_bitmap, 1), dim3(kScanBlock), 0, st, bm, bs,
-                           w.cand.as<uint32_t>() + (size_t)b * w.cand_cap, s->doc_off.as<uint32_t>(),
-                           w.cand_hdr.as<uint2>() + (size_t)b * w.cand_cap, w.W, w.cand_cap, w.ncand.as<int>() + b, fa);
-        CLB_HIP(hipGetLastError());
+// S7 for queries b0 .. b0 + n - 1: the single-work-group select + sort of topk_kernel, one work-group per query, or for
+// k above it a full stable sort per query.  list / nlist: the two-pass mode's re-scored passages ([B][cand_cap] / [B]) or
+// nullptr; ranked: topk_rank_kernel has already written the queries with short lists
+int launch_topk(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int n, const int* list, const int* nlist,
+                int ranked) {
+    if (q.k > kMaxTopK) {
+        for (int b = b0; b < b0 + n; ++b) CLB_TRY(topk_by_sort(s, w, st, q, b, list, nlist));
         return CLB_OK;
     }
-    hipLaunchKernelGGL(mark_candidates_kernel<false>, dim3(T * nprobe, 1), dim3(256), 0, st, sel_b, s->ivf_off.as<uint32_t>(),
-                       s->ivf_pid.as<uint32_t>(), bm, T, T, nprobe, nprobe, w.W);
-    hipLaunchKernelGGL(bitmap_count_kernel<false>, dim3(w.nblk_bitmap, 1), dim3(kScanBlock), 0, st, bm, bs, w.W);
-    hipLaunchKernelGGL(bitmap_emit_kernel<false>, dim3(w.nblk_bitmap, 1), dim3(kScanBlock), 0, st, bm, bs,
-                       w.cand.as<uint32_t>() + (size_t)b * w.cand_cap, s->doc_off.as<uint32_t>(),
-                       w.cand_hdr.as<uint2>() + (size_t)b * w.cand_cap, w.W, w.cand_cap, w.ncand.as<int>() + b);
+    const int kpow2 = next_pow2(q.k);
+    allow_large_topk_lds();
+    hipLaunchKernelGGL(topk_kernel, dim3(n), dim3(1024), sizeof(unsigned long long) * kpow2, st,
+                       w.scores.as<float>() + (size_t)b0 * w.cand_cap, w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap,
+                       w.ncand.as<int>() + b0, list ? list + (size_t)b0 * w.cand_cap : nullptr, list ? nlist + b0 : nullptr, q.k, kpow2,
+                       w.cand_cap, s->pid_offset, q.d_out_pids + (size_t)b0 * q.k, q.d_out_scores + (size_t)b0 * q.k,
+                       w.flags.as<int>() + b0, q.d_n_cand ? q.d_n_cand + b0 : nullptr, ranked);
     CLB_HIP(hipGetLastError());
     return CLB_OK;
+}
+
+// S1-S3 of query b of the sub-batch on the general-shape path: leaves cand / cand_hdr / ncand of slot b
+int run_retrieve_general(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b) {
+    const int T = q.T, nprobe = q.nprobe;
+    CLB_TRY(w.g_cells.ensure(sizeof(float) * (size_t)T * s->K));
+    hipLaunchKernelGGL(generic_cells_kernel, dim3((unsigned)((s->K + 127) / 128), T), dim3(128), sizeof(float) * s->dim, st,
+                       s->centroids.as<float>(), q.dQ + (size_t)b * T * s->dim, (int)s->dim, (int)s->K, w.g_cells.as<float>());
+    // one query at a time: slot 0 of the selection buffer, rows of nprobe entries for T tokens
+    CLB_TRY(select_by_sort(s, w, st, w.g_cells.as<float>(), (size_t)s->K, 1, T, nprobe, nprobe, w.sel.as<int>()));
+    return mark_and_compact(s, w, st, q, b, 1, /*Tpad=*/T, /*NPs=*/nprobe, /*timed=*/false);
 }
 
 // S1..S3 of B queries on the general-shape path when the shape allows the batched kernels: fp32-MFMA centroid scores in
 // the tuned path's [b][centroid][Tpad] layout, then the tuned path's own selection, marking and compaction
 bool general_batched_ok(const clb_searcher* s, int T) { return s->dim % 4 == 0 && s->dim <= 256 && T <= 128; }
 
-int run_retrieve_general_batched(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, int B, int T, int nprobe) {
-    const int TT = token_tiles(T), Tpad = TT * 32;
-    const int NPs = nprobe <= 2 ? 2 : nprobe <= 8 ? 8 : nprobe <= 32 ? 32 : nprobe;
-    const dim3 grid((unsigned)((s->K + 63) / 64), (unsigned)B);
-    if (s->dim <= 128)
-        hipLaunchKernelGGL(generic_cells_mfma_kernel<32>, grid, dim3(256), 0, st, s->centroids.as<float>(), dQ, (int)s->dim, (int)s->K,
-                           T, Tpad, w.cells.as<float>());
-    else
-        hipLaunchKernelGGL(generic_cells_mfma_kernel<64>, grid, dim3(256), 0, st, s->centroids.as<float>(), dQ, (int)s->dim, (int)s->K,
-                           T, Tpad, w.cells.as<float>());
-    if (NPs == 2) launch_topn<2>(s, w, st, B, Tpad);
-    else if (NPs == 8) launch_topn<8>(s, w, st, B, Tpad);
-    else if (NPs == 32) launch_topn<32>(s, w, st, B, Tpad);
-    else
-        for (int b = 0; b < B; ++b)
-            CLB_TRY(select_by_sort(s, w, st, w.cells.as<float>() + (size_t)b * s->K * Tpad, 1, (size_t)Tpad, T, nprobe, NPs,
-                                   w.sel.as<int>() + (size_t)b * Tpad * NPs));
-    return mark_and_compact(s, w, st, B, T, Tpad, NPs, nprobe);
+int run_retrieve_general_batched(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
+    const int Tpad = token_tiles(q.T) * 32;
+    auto cells_kernel = s->dim <= 128 ? generic_cells_mfma_kernel<32> : generic_cells_mfma_kernel<64>;
+    hipLaunchKernelGGL(cells_kernel, dim3((unsigned)((s->K + 63) / 64), (unsigned)q.B), dim3(256), 0, st, s->centroids.as<float>(),
+                       q.dQ, (int)s->dim, (int)s->K, q.T, Tpad, w.cells.as<float>());
+    CLB_TRY(select_top_nprobe(s, w, st, q.B, q.T, Tpad, q.nprobe));
+    return mark_and_compact(s, w, st, q, 0, q.B, Tpad, (int)padded_nprobe(q.nprobe), /*timed=*/true);
 }
 
 // the whole search of B queries on the general-shape path (exact scoring only)
-int run_search_general(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, int B, int T, int nprobe, int k,
-                       int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand) {
+int run_search_general(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
+    const float* dQ = q.dQ;
+    const int B = q.B, T = q.T;
     s->prof.chain = nullptr;
     if (general_batched_ok(s, T)) {
         // batched: every stage is one launch for the B queries (the loop below: ~12 launches per query, the scoring
         // kernel a chain of dependent loads)
-        CLB_TRY(run_retrieve_general_batched(s, w, st, dQ, B, T, nprobe));
+        CLB_TRY(run_retrieve_general_batched(s, w, st, q));
         const dim3 grid((unsigned)std::max(64, 2048 / std::max(1, B)), (unsigned)B);
         const size_t lds = sizeof(float) * (((size_t)1 << s->nbits) + (size_t)T * (s->dim + 1));   // <= 133 KB (T 128, dim 256)
         if (lds > 64 * 1024) {
             allow_dynamic_lds(reinterpret_cast<const void*>(generic_score_mfma_fast_kernel<32>), (int)lds);
             allow_dynamic_lds(reinterpret_cast<const void*>(generic_score_mfma_fast_kernel<64>), (int)lds);
         }
-        if (s->dim <= 128)
-            hipLaunchKernelGGL(generic_score_mfma_fast_kernel<32>, grid, dim3(256), lds, st, s->centroids.as<float>(),
-                               s->weights.as<float>(), s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(), w.cand_hdr.as<uint2>(),
-                               w.ncand.as<int>(), dQ, (int)s->dim, s->nbits, T, w.cand_cap, w.scores.as<float>());
-        else
-            hipLaunchKernelGGL(generic_score_mfma_fast_kernel<64>, grid, dim3(256), lds, st, s->centroids.as<float>(),
-                               s->weights.as<float>(), s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(), w.cand_hdr.as<uint2>(),
-                               w.ncand.as<int>(), dQ, (int)s->dim, s->nbits, T, w.cand_cap, w.scores.as<float>());
+        auto score_kernel = s->dim <= 128 ? generic_score_mfma_fast_kernel<32> : generic_score_mfma_fast_kernel<64>;
+        hipLaunchKernelGGL(score_kernel, grid, dim3(256), lds, st, s->centroids.as<float>(), s->weights.as<float>(),
+                           s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(), w.cand_hdr.as<uint2>(), w.ncand.as<int>(), dQ,
+                           (int)s->dim, s->nbits, T, w.cand_cap, w.scores.as<float>());
         CLB_HIP(hipGetLastError());
-        if (k <= kMaxTopK) {
-            const int kpow2 = next_pow2(k);
-            allow_large_topk_lds();
-            hipLaunchKernelGGL(topk_kernel, dim3(B), dim3(1024), sizeof(unsigned long long) * kpow2, st, w.scores.as<float>(),
-                               w.cand.as<uint32_t>(), w.ncand.as<int>(), (const int*)nullptr, (const int*)nullptr, k, kpow2,
-                               w.cand_cap, s->pid_offset, d_out_pids, d_out_scores, w.flags.as<int>(), d_n_cand);
-            CLB_HIP(hipGetLastError());
-        } else {
-            for (int b = 0; b < B; ++b) CLB_TRY(topk_by_sort(s, w, st, b, nullptr, nullptr, k, d_out_pids, d_out_scores, d_n_cand));
-        }
-        return CLB_OK;
+        return launch_topk(s, w, st, q, 0, B, nullptr, nullptr, 0);
     }
     const int grid = 1024;
     const size_t max_len = (size_t)std::max<int64_t>(s->max_doclen, 1);
     CLB_TRY(w.g_scratch.ensure(sizeof(float) * grid * max_len * s->dim));
     for (int b = 0; b < B; ++b) {
-        CLB_TRY(run_retrieve_general(s, w, st, dQ, b, T, nprobe));
+        CLB_TRY(run_retrieve_general(s, w, st, q, b));
         if (T <= 16 * kGenericMaxTokenGroups && s->dim % 4 == 0)
             // fp32 MFMA, one wave per passage (the canonical arithmetic of the scalar kernel, bit for bit)
             hipLaunchKernelGGL(generic_score_mfma_kernel, dim3(grid), dim3(256), sizeof(float) * ((size_t)1 << s->nbits), st,
@@ -650,33 +635,17 @@ int run_search_general(clb_searcher* s, Workspace& w, hipStream_t st, const floa
                                w.ncand.as<int>() + b, dQ + (size_t)b * T * s->dim, (int)s->dim, s->nbits, T,
                                w.scores.as<float>() + (size_t)b * w.cand_cap);
         else
-        hipLaunchKernelGGL(generic_score_kernel, dim3(grid), dim3(256), sizeof(float) * T, st, s->centroids.as<float>(),
-                           s->weights.as<float>(), s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(),
-                           w.cand_hdr.as<uint2>() + (size_t)b * w.cand_cap, w.ncand.as<int>() + b,
-                           dQ + (size_t)b * T * s->dim, (int)s->dim, s->nbits, T, w.g_scratch.as<float>(), max_len,
-                           w.scores.as<float>() + (size_t)b * w.cand_cap);
+            hipLaunchKernelGGL(generic_score_kernel, dim3(grid), dim3(256), sizeof(float) * T, st, s->centroids.as<float>(),
+                               s->weights.as<float>(), s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(),
+                               w.cand_hdr.as<uint2>() + (size_t)b * w.cand_cap, w.ncand.as<int>() + b,
+                               dQ + (size_t)b * T * s->dim, (int)s->dim, s->nbits, T, w.g_scratch.as<float>(), max_len,
+                               w.scores.as<float>() + (size_t)b * w.cand_cap);
         CLB_HIP(hipGetLastError());
-        if (k <= kMaxTopK) {
-            const int kpow2 = next_pow2(k);
-            allow_large_topk_lds();
-            hipLaunchKernelGGL(topk_kernel, dim3(1), dim3(1024), sizeof(unsigned long long) * kpow2, st,
-                               w.scores.as<float>() + (size_t)b * w.cand_cap, w.cand.as<uint32_t>() + (size_t)b * w.cand_cap,
-                               w.ncand.as<int>() + b, (const int*)nullptr, (const int*)nullptr, k, kpow2, w.cand_cap,
-                               s->pid_offset, d_out_pids + (size_t)b * k, d_out_scores + (size_t)b * k,
-                               w.flags.as<int>() + b, d_n_cand ? d_n_cand + b : nullptr);
-            CLB_HIP(hipGetLastError());
-        } else {
-            CLB_TRY(topk_by_sort(s, w, st, b, nullptr, nullptr, k, d_out_pids, d_out_scores, d_n_cand));
-        }
+        CLB_TRY(launch_topk(s, w, st, q, b, 1, nullptr, nullptr, 0));
     }
     return CLB_OK;
 }
 
-// The whole search for B device-resident queries, enqueued on st.
-// phase 0: the whole search.  Sharded search in two calls (clb_search_shard_phase1/2, two-pass mode only):
-// phase 1 = candidate generation, pass 1, local selection, and the shard's k largest approximate scores per query
-// to `d_local_top`; phase 2 = global tau from the gathered scores `d_all_top` ([n_shards][B][k]), selection at that
-// tau, pass 2, top-k.  Phase 2 continues on the workspace phase 1 left behind.
 // tau and the list {approx >= tau - 2 eps} of every query of the batch (two-pass mode).  One work-group per query keeps
 // up to 32 768 candidates in registers; shards whose queries can have several times that (candidate capacity >= 131 072:
 // roughly 3 M passages and up) take the wide selection -- kWideBlocks work-groups per query, one launch per radix pass.
@@ -699,11 +668,12 @@ void launch_pass1(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ
 inline float bound_dc(const clb_searcher* s, const Workspace& w) {
     return (w.x1_table || (s->bounds_synced && s->s1_x1 != 0 && s->cent_f16.p)) ? s->dc_f16 : 0.f;
 }
-int launch_select(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, int B, int T, int k, const float* tau_in,
-                  bool coarse_tau = false) {
+int launch_select(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, const float* tau_in, bool coarse_tau = false) {
+    const float* dQ = q.dQ;
+    const int B = q.B, T = q.T, k = q.k;
     // by the most candidates a query of THIS sub-batch can have: a slot that once grew for a large CLB_FILTER_ALL set
     // goes on selecting its unfiltered batches as before
-    const size_t most = w.filt && w.filt_all ? std::max(w.ivf_cap, w.filt_now) : w.ivf_cap;
+    const size_t most = q.filt && q.filt_all ? std::max(w.ivf_cap, q.filt_now) : w.ivf_cap;
     const bool wide = s->wide_select == 1 || (s->wide_select < 0 && most >= kWideSelectCap);
     if (!wide) {
         ApproxConsts ac = s->approx_consts;
@@ -733,62 +703,58 @@ int launch_select(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ
     return CLB_OK;
 }
 
-int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, int B, int T, int nprobe, int k,
-               int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand = nullptr, int phase = 0,
-               float* d_local_top = nullptr, const float* d_all_top = nullptr, int n_shards = 0) {
-    if (s->generic || T > 128) {
-        if (phase != 0) return fail(CLB_EUNSUPPORTED, "the two-phase sharded search needs the two-pass mode");
-        return run_search_general(s, w, st, dQ, B, T, nprobe, k, d_out_pids, d_out_scores, d_n_cand);
-    }
-    const int kpow2 = next_pow2(std::min(k, (int)kMaxTopK));
-    const int* list = nullptr;
-    const int* nlist = nullptr;
-    s->prof.chain = nullptr;           // the first timed kernel of a call records its own start
+// The whole search for the B device-resident queries of q, enqueued on st.
+// phase 0: the whole search.  Sharded search in two calls (clb_search_shard_phase1/2, two-pass mode only):
+// phase 1 = candidate generation, pass 1, local selection, and the shard's k largest approximate scores per query
+// to `d_local_top`; phase 2 = global tau from the gathered scores `d_all_top` ([n_shards][B][k]), selection at that
+// tau, pass 2, top-k.  Phase 2 continues on the workspace phase 1 left behind.
+int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
+    const float* dQ = q.dQ;
+    const int B = q.B, T = q.T, k = q.k, phase = q.phase;
     const bool two_pass = s->mode == 1 && s->approx_ok && T <= 32;
     if (phase != 0 && !two_pass) return fail(CLB_EUNSUPPORTED, "the two-phase sharded search needs the two-pass mode");
+    if (s->generic || T > 128) return run_search_general(s, w, st, q);
+    s->prof.chain = nullptr;           // the first timed kernel of a call records its own start
     if (phase == 2) {
         CLB_TRY(w.tau_glob.ensure(sizeof(float) * B));
-        hipLaunchKernelGGL(global_tau_kernel, dim3(B), dim3(1024), 0, st, d_all_top, n_shards, B, k,
-                           w.tau_glob.as<float>());
+        hipLaunchKernelGGL(global_tau_kernel, dim3(B), dim3(1024), 0, st, q.d_all_top, q.n_shards, B, k, w.tau_glob.as<float>());
         Timed t(s, KID_SELECT, st);
-        CLB_TRY(launch_select(s, w, st, dQ, B, T, k, (const float*)w.tau_glob.as<float>()));
-        list = w.list.as<int>();
-        nlist = w.nlist.as<int>();
-    }
-    if (phase != 2) {
-    CLB_TRY(run_retrieve(s, w, st, dQ, B, T, nprobe));
-    if (s->prof.counters) {
-        // one set of counters per CALL: the sub-batches of a large batch add onto those of the sub-batches before them
-        if (!w.stats_keep) CLB_HIP(hipMemsetAsync(w.stats.p, 0, sizeof(unsigned long long) * 8, st));
-        s->prof.chain = nullptr;
-    }
-    if (two_pass) {
-        {
-            Timed t(s, KID_SCORE_APPROX, st);
-            constexpr int kWgPerGroup = 32;   // x 8 XCD groups: one 12-wave work-group per CU
-            // Grid: XCD-affine 1-D launch (all work-groups of an XCD share one query's score table in L2) for
-            // large candidate sets; for small ones (a shard of a multi-GPU run: < ~6 k candidate passages per
-            // query, estimated from the mean IVF list) a (G, B) launch whose few waves per query each get a long
-            // run of passages -- the pipeline fill otherwise dominates.
-            const double est_cand = 0.5 * T * nprobe * (double)s->n_emb / (double)std::max<int64_t>(1, s->K);
-            // work-groups per query of the (G, B) launch (0 = the 1-D launch): enough to fill the chip for small batches,
-            // eight for large ones (measured at 4 and 8 shards, B = 8 ... 256: one or two per query cost 12 % of the pass
-            // at B = 256, sixteen and more cost as much at B = 32)
-            const int gxq = est_cand < 6000.0 ? std::max(8, 256 / B) : 0;
-            const dim3 approx_grid = gxq > 0 && B > 1 ? dim3(gxq, B) : dim3(8 * kWgPerGroup);
-            launch_pass1(s, w, st, dQ, approx_grid, B, T);
+        CLB_TRY(launch_select(s, w, st, q, (const float*)w.tau_glob.as<float>()));
+    } else {
+        CLB_TRY(run_retrieve(s, w, st, q));
+        if (s->prof.counters) {
+            // one set of counters per CALL: the sub-batches of a large batch add onto those of the sub-batches before them
+            if (!q.stats_keep) CLB_HIP(hipMemsetAsync(w.stats.p, 0, sizeof(unsigned long long) * 8, st));
+            s->prof.chain = nullptr;
         }
-        {
-            Timed t(s, KID_SELECT, st);
-            CLB_TRY(launch_select(s, w, st, dQ, B, T, k, nullptr, /*coarse_tau=*/phase == 0));
+        if (two_pass) {
+            {
+                Timed t(s, KID_SCORE_APPROX, st);
+                constexpr int kWgPerGroup = 32;   // x 8 XCD groups: one 12-wave work-group per CU
+                // Grid: XCD-affine 1-D launch (all work-groups of an XCD share one query's score table in L2) for
+                // large candidate sets; for small ones (a shard of a multi-GPU run: < ~6 k candidate passages per
+                // query, estimated from the mean IVF list) a (G, B) launch whose few waves per query each get a long
+                // run of passages -- the pipeline fill otherwise dominates.
+                const double est_cand = 0.5 * T * q.nprobe * (double)s->n_emb / (double)std::max<int64_t>(1, s->K);
+                // work-groups per query of the (G, B) launch (0 = the 1-D launch): enough to fill the chip for small batches,
+                // eight for large ones (measured at 4 and 8 shards, B = 8 ... 256: one or two per query cost 12 % of the pass
+                // at B = 256, sixteen and more cost as much at B = 32)
+                const int gxq = est_cand < 6000.0 ? std::max(8, 256 / B) : 0;
+                const dim3 approx_grid = gxq > 0 && B > 1 ? dim3(gxq, B) : dim3(8 * kWgPerGroup);
+                launch_pass1(s, w, st, dQ, approx_grid, B, T);
+            }
+            {
+                Timed t(s, KID_SELECT, st);
+                CLB_TRY(launch_select(s, w, st, q, nullptr, /*coarse_tau=*/phase == 0));
+            }
         }
-        list = w.list.as<int>();
-        nlist = w.nlist.as<int>();
     }
-    }   // phase != 2
+    // two-pass mode: only the selected passages go on
+    const int* list = two_pass ? w.list.as<int>() : nullptr;
+    const int* nlist = two_pass ? w.nlist.as<int>() : nullptr;
     if (phase == 1) {
         hipLaunchKernelGGL(local_top_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(), list, nlist,
-                           w.thresh.as<float>(), k, w.cand_cap, d_local_top);
+                           w.thresh.as<float>(), k, w.cand_cap, q.d_local_top);
         CLB_HIP(hipGetLastError());
         return CLB_OK;
     }
@@ -810,35 +776,32 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, i
         Timed t(s, KID_SCORE_EXACT, st);
         const int gx = list ? std::max(1, 1024 / B) : std::max(1, 2048 / B);
         constexpr int kFlatGx = 768;   // one resident round at 3 work-groups per CU
-        if (subset) {
+        if (subset)
             hipLaunchKernelGGL(score_exact_flat_kernel, dim3(std::max(1, kFlatGx / B), B), dim3(256), 0, st, s->centroids.as<float>(),
                                s->weights.as<float>(), s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(),
                                w.cand_hdr.as<uint2>(), dQ, w.scores.as<float>(), T, w.cand_cap, list, nlist,
                                w.rowmask.as<unsigned long long>());
-        } else
-        switch (s->nbits) {
-            case 1: launch_score_exact<1>(s, w, st, dQ, B, T, list, nlist, gx); break;
-            case 2: launch_score_exact<2>(s, w, st, dQ, B, T, list, nlist, gx); break;
-            case 4: launch_score_exact<4>(s, w, st, dQ, B, T, list, nlist, gx); break;
-            default: return fail(CLB_EUNSUPPORTED, "nbits=%d not supported by the HIP search path", s->nbits);
-        }
+        else
+            switch (s->nbits) {
+                case 1: launch_score_exact<1>(s, w, st, dQ, B, T, list, nlist, gx); break;
+                case 2: launch_score_exact<2>(s, w, st, dQ, B, T, list, nlist, gx); break;
+                case 4: launch_score_exact<4>(s, w, st, dQ, B, T, list, nlist, gx); break;
+                default: return fail(CLB_EUNSUPPORTED, "nbits=%d not supported by the HIP search path", s->nbits);
+            }
     }
     if (k <= kMaxTopK) {
         Timed t(s, KID_TOPK, st);
-        allow_large_topk_lds();
         // two-pass mode: the ~1.2 k listed passages of a query are ranked by kRankBlocks work-groups (no sorting network);
         // a query whose list is longer than kRankMax falls through to the one-work-group select + sort
         const int ranked = list != nullptr;
         if (ranked)
             hipLaunchKernelGGL(topk_rank_kernel, dim3(kRankBlocks, B), dim3(1024), 0, st, w.scores.as<float>(),
                                w.cand.as<uint32_t>(), w.ncand.as<int>(), list, nlist, k, w.cand_cap, s->pid_offset,
-                               d_out_pids, d_out_scores, w.flags.as<int>(), d_n_cand);
-        hipLaunchKernelGGL(topk_kernel, dim3(B), dim3(1024), sizeof(unsigned long long) * kpow2, st,
-                           w.scores.as<float>(), w.cand.as<uint32_t>(), w.ncand.as<int>(), list, nlist, k,
-                           kpow2, w.cand_cap, s->pid_offset, d_out_pids, d_out_scores, w.flags.as<int>(), d_n_cand, ranked);
-    } else {      // k above the single-work-group sort: a full stable sort per query (synchronises)
+                               q.d_out_pids, q.d_out_scores, w.flags.as<int>(), q.d_n_cand);
+        CLB_TRY(launch_topk(s, w, st, q, 0, B, list, nlist, ranked));
+    } else {      // k above the single-work-group sort: a full stable sort per query, untimed
         s->prof.chain = nullptr;
-        for (int b = 0; b < B; ++b) CLB_TRY(topk_by_sort(s, w, st, b, list, nlist, k, d_out_pids, d_out_scores, d_n_cand));
+        CLB_TRY(launch_topk(s, w, st, q, 0, B, list, nlist, 0));
     }
     if (s->prof.counters) {
         hipLaunchKernelGGL(batch_stats_kernel, dim3(32, B), dim3(256), 0, st, w.cand.as<uint32_t>(),
@@ -847,6 +810,57 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, i
                            subset ? w.rowmask.as<unsigned long long>() : (const unsigned long long*)nullptr);
     }
     CLB_HIP(hipGetLastError());
+    return CLB_OK;
+}
+
+// the filters of a call (a host array of B handles, or nullptr): every one must be this searcher's; *filt_count = the largest
+// population a CLB_FILTER_ALL search has to hold as a candidate set (a host value: sizing the workspace needs no read-back)
+int check_filters(const clb_searcher* s, const clb_filter* const* filters, int64_t B, int scope, size_t* filt_count) {
+    *filt_count = 0;
+    if (scope != CLB_FILTER_CANDIDATES && scope != CLB_FILTER_ALL)
+        return fail(CLB_EARGUMENT, "scope must be CLB_FILTER_CANDIDATES (0) or CLB_FILTER_ALL (1), got %d", scope);
+    if (!filters) return CLB_OK;
+    for (int64_t b = 0; b < B; ++b) {
+        const clb_filter* f = filters[b];
+        if (!f) continue;
+        if (f->owner != s->serial || f->n_docs != s->n_docs)
+            return fail(CLB_EARGUMENT, "the filter of query %lld was made for another searcher", (long long)b);
+        if (scope == CLB_FILTER_ALL) *filt_count = std::max(*filt_count, (size_t)f->count);
+    }
+    return CLB_OK;
+}
+
+// the workspace of a slot of the *_slot entry points, with the searcher's device made current
+int slot_workspace(clb_searcher* s, int slot, Workspace** w) {
+    if (slot < 0 || slot >= kWorkspaceSlots) return fail(CLB_EARGUMENT, "workspace slot must be 0..%d", kWorkspaceSlots - 1);
+    CLB_TRY(use_device(s->device));
+    *w = &s->ws[slot];
+    return CLB_OK;
+}
+
+// A large batch runs as sub-batches of kSubBatch queries, back to back on one stream and on one slot's scratch:
+// every query carries an 8-MB fp16 score table (K = 131 072), and from ~64 queries on the tables of a batch outgrow
+// the 256-MB Infinity Cache before pass 1 reads them (measured: 29.4 k queries/s at 64, 27.8 k at 256 in one piece);
+// the centroid kernel shares a staged tile between 16 queries whatever the batch, so nothing is lost above that.
+// (The two-phase sharded calls keep the whole batch: phase 2 continues on the scratch of phase 1.)
+// run_one(b0, q): points q at the queries and outputs of the sub-batch that starts at query b0 and runs it.  q arrives with
+// the sub-batch's size, its slice of the handle array -- nullptr when none of its queries is filtered -- and stats_keep set
+template <class RunOne>
+int for_sub_batches(clb_searcher* s, Workspace& w, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                    const clb_filter* const* filters, int scope, RunOne run_one) {
+    size_t filt_count = 0;
+    CLB_TRY(check_filters(s, filters, B, scope, &filt_count));
+    w.pending.valid = false;
+    for (int64_t b0 = 0; b0 < B; b0 += kSubBatch) {
+        Batch q = make_batch(nullptr, std::min<int64_t>(kSubBatch, B - b0), T, nprobe, k);
+        CLB_TRY(ensure_workspace(s, w, q.B, T, nprobe, k, filt_count));
+        q.stats_keep = b0 > 0;
+        q.filt_all = scope == CLB_FILTER_ALL;
+        q.filt_now = filt_count;
+        for (int64_t b = b0; filters && b < b0 + q.B; ++b)
+            if (filters[b]) q.filt = filters + b0;
+        CLB_TRY(run_one(b0, q));
+    }
     return CLB_OK;
 }
 
@@ -1082,6 +1096,7 @@ int64_t clb_searcher_device_bytes(const clb_searcher* s) {
     if (!s) return 0;
     int64_t tot = s->index_bytes;
     for (const auto& w : s->ws) {
+        // not every buffer of Workspace is summed: bounds, wsel and the g_* buffers are left out (the reported figure is unchanged)
         const DevBuf* bufs[] = {&w.Qdev, &w.cells, &w.cells_q, &w.partial, &w.sel, &w.bitmap, &w.blocksum, &w.ncand, &w.cand,
                                 &w.cand_hdr, &w.scores, &w.list, &w.nlist, &w.thresh, &w.outp, &w.outs, &w.flags, &w.stats, &w.redo, &w.rowmask, &w.eps_pair, &w.tokmax, &w.tau_glob, &w.tscale, &w.rangep, &w.cells8};
         for (auto* b : bufs) tot += (int64_t)b->bytes;
@@ -1177,62 +1192,20 @@ int clb_search_batch_device(clb_searcher* s, const float* d_Q, int64_t T, int64_
     return clb_search_batch_device_slot(s, 0, d_Q, T, B, nprobe, k, d_out_pids, d_out_scores, d_n_cand, hip_stream);
 }
 
-// the filters of a call (a host array of B handles, or nullptr): every one must be this searcher's; *filt_count = the largest
-// population a CLB_FILTER_ALL search has to hold as a candidate set (a host value: sizing the workspace needs no read-back)
-static int check_filters(const clb_searcher* s, const clb_filter* const* filters, int64_t B, int scope, size_t* filt_count) {
-    *filt_count = 0;
-    if (scope != CLB_FILTER_CANDIDATES && scope != CLB_FILTER_ALL)
-        return fail(CLB_EARGUMENT, "scope must be CLB_FILTER_CANDIDATES (0) or CLB_FILTER_ALL (1), got %d", scope);
-    if (!filters) return CLB_OK;
-    for (int64_t b = 0; b < B; ++b) {
-        const clb_filter* f = filters[b];
-        if (!f) continue;
-        if (f->owner != s->serial || f->n_docs != s->n_docs)
-            return fail(CLB_EARGUMENT, "the filter of query %lld was made for another searcher", (long long)b);
-        if (scope == CLB_FILTER_ALL) *filt_count = std::max(*filt_count, (size_t)f->count);
-    }
-    return CLB_OK;
-}
-// the sub-batch b0 .. b0 + bn - 1 as run_search sees it: its slice of the handle array, or nullptr when none of its queries is
-// filtered (that sub-batch then launches the unfiltered kernels)
-static void set_sub_batch_filters(Workspace& w, const clb_filter* const* filters, int64_t b0, int64_t bn, int scope,
-                                  size_t filt_count) {
-    w.filt = nullptr;
-    w.filt_all = scope == CLB_FILTER_ALL;
-    w.filt_now = filt_count;
-    if (!filters) return;
-    for (int64_t b = b0; b < b0 + bn; ++b)
-        if (filters[b]) { w.filt = filters + b0; return; }
-}
-
 static int search_batch_device_slot_impl(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
                                          int64_t k, const clb_filter* const* filters, int scope, int64_t* d_out_pids,
                                          float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
-    if (slot < 0 || slot >= kWorkspaceSlots) return fail(CLB_EARGUMENT, "workspace slot must be 0..%d", kWorkspaceSlots - 1);
-    size_t filt_count = 0;
-    CLB_TRY(check_filters(s, filters, B, scope, &filt_count));
-    CLB_TRY(use_device(s->device));
+    Workspace* w = nullptr;
+    CLB_TRY(slot_workspace(s, slot, &w));
     hipStream_t st = (hipStream_t)hip_stream;   // NULL = the HIP null stream, as for any HIP API
-    Workspace& w = s->ws[slot];
-    w.pending.valid = false;
-    // A large batch runs as sub-batches of kSubBatch queries, back to back on the caller's stream and on this slot's scratch:
-    // every query carries an 8-MB fp16 score table (K = 131 072), and from ~64 queries on the tables of a batch outgrow
-    // the 256-MB Infinity Cache before pass 1 reads them (measured: 29.4 k queries/s at 64, 27.8 k at 256 in one piece);
-    // the centroid kernel shares a staged tile between 16 queries whatever the batch, so nothing is lost above that.
-    // (The two-phase sharded calls keep the whole batch: phase 2 continues on the scratch of phase 1.)
-    for (int64_t b0 = 0; b0 < B; b0 += kSubBatch) {
-        const int64_t bn = std::min<int64_t>(kSubBatch, B - b0);
-        CLB_TRY(ensure_workspace(s, w, bn, T, nprobe, k, filt_count));
-        w.stats_keep = b0 > 0;
-        set_sub_batch_filters(w, filters, b0, bn, scope, filt_count);
-        const int rc = run_search(s, w, st, d_Q + (size_t)b0 * T * s->dim, (int)bn, (int)T, (int)nprobe, (int)k, d_out_pids + (size_t)b0 * k,
-                                  d_out_scores + (size_t)b0 * k, d_n_cand ? d_n_cand + b0 : nullptr);
-        w.stats_keep = false;
-        w.filt = nullptr;
-        if (rc) return rc;
-    }
-    return CLB_OK;
+    return for_sub_batches(s, *w, T, B, nprobe, k, filters, scope, [&](int64_t b0, Batch& q) -> int {
+        q.dQ = d_Q + (size_t)b0 * T * s->dim;
+        q.d_out_pids = d_out_pids + (size_t)b0 * k;
+        q.d_out_scores = d_out_scores + (size_t)b0 * k;
+        q.d_n_cand = d_n_cand ? d_n_cand + b0 : nullptr;
+        return run_search(s, *w, st, q);
+    });
 }
 
 int clb_search_batch_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
@@ -1258,13 +1231,14 @@ int clb_search_shard_phase1_slot(clb_searcher* s, int slot, const float* d_Q, in
                                  int64_t k, float* d_local_top, void* hip_stream) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     if (!d_local_top) return fail(CLB_EARGUMENT, "d_local_top is null");
-    if (slot < 0 || slot >= kWorkspaceSlots) return fail(CLB_EARGUMENT, "workspace slot must be 0..%d", kWorkspaceSlots - 1);
-    CLB_TRY(use_device(s->device));
-    Workspace& w = s->ws[slot];
+    Workspace* wp = nullptr;
+    CLB_TRY(slot_workspace(s, slot, &wp));
+    Workspace& w = *wp;
     CLB_TRY(ensure_workspace(s, w, B, T, nprobe, k));
     w.pending.valid = false;
-    CLB_TRY(run_search(s, w, (hipStream_t)hip_stream, d_Q, (int)B, (int)T, (int)nprobe, (int)k, nullptr, nullptr, nullptr,
-                       1, d_local_top));
+    Batch q = make_batch(d_Q, B, T, nprobe, k);     // the sharded search takes no filters
+    q.phase = 1; q.d_local_top = d_local_top;
+    CLB_TRY(run_search(s, w, (hipStream_t)hip_stream, q));
     w.pending.valid = true; w.pending.dQ = d_Q; w.pending.T = T; w.pending.B = B; w.pending.nprobe = nprobe;
     w.pending.k = k; w.pending.stream = hip_stream;
     return CLB_OK;
@@ -1282,9 +1256,9 @@ int clb_search_shard_phase2_slot(clb_searcher* s, int slot, const float* d_Q, in
                                  float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     if (!d_all_top || n_shards < 1) return fail(CLB_EARGUMENT, "d_all_top is null or n_shards < 1");
-    if (slot < 0 || slot >= kWorkspaceSlots) return fail(CLB_EARGUMENT, "workspace slot must be 0..%d", kWorkspaceSlots - 1);
-    CLB_TRY(use_device(s->device));
-    Workspace& w = s->ws[slot];
+    Workspace* wp = nullptr;
+    CLB_TRY(slot_workspace(s, slot, &wp));
+    Workspace& w = *wp;
     const auto& pd = w.pending;
     if (!pd.valid || pd.dQ != d_Q || pd.T != T || pd.B != B || pd.nprobe != nprobe || pd.k != k || pd.stream != hip_stream)
         return fail(CLB_EARGUMENT, "clb_search_shard_phase2 without a matching clb_search_shard_phase1 "
@@ -1296,36 +1270,34 @@ int clb_search_shard_phase2_slot(clb_searcher* s, int slot, const float* d_Q, in
         return fail(CLB_EARGUMENT, "clb_search_shard_phase2 with %lld shards before clb_searcher_set_bound_consts: the shards "
                                    "must share one error bound (all-reduce MAX of clb_searcher_get_bound_consts)", (long long)n_shards);
     w.pending.valid = false;
-    return run_search(s, w, (hipStream_t)hip_stream, d_Q, (int)B, (int)T, (int)nprobe, (int)k, d_out_pids, d_out_scores,
-                      d_n_cand, 2, nullptr, d_all_top, (int)n_shards);
+    Batch q = make_batch(d_Q, B, T, nprobe, k);     // unfiltered, as phase 1 was
+    q.d_out_pids = d_out_pids; q.d_out_scores = d_out_scores; q.d_n_cand = d_n_cand;
+    q.phase = 2; q.d_all_top = d_all_top; q.n_shards = (int)n_shards;
+    return run_search(s, w, (hipStream_t)hip_stream, q);
 }
 
 static int search_batch_impl(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
                              const clb_filter* const* filters, int scope, int pad_short, int64_t* out_pids, float* out_scores,
                              int64_t* n_cand) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
-    size_t filt_count = 0;
-    CLB_TRY(check_filters(s, filters, B, scope, &filt_count));
-    CLB_TRY(use_device(s->device));
-    Workspace& w = s->ws[0];
-    w.pending.valid = false;
+    Workspace* wp = nullptr;
+    CLB_TRY(slot_workspace(s, 0, &wp));
+    Workspace& w = *wp;
     hipStream_t st = s->stream;
     std::vector<int> nc((size_t)B), fl((size_t)B);
-    for (int64_t b0 = 0; b0 < B; b0 += kSubBatch) {           // sub-batches: see clb_search_batch_device_slot
-        const int64_t bn = std::min<int64_t>(kSubBatch, B - b0);
-        CLB_TRY(ensure_workspace(s, w, bn, T, nprobe, k, filt_count));
-        CLB_HIP(hipMemcpyAsync(w.Qdev.p, Q + (size_t)b0 * T * s->dim, sizeof(float) * bn * T * s->dim, hipMemcpyHostToDevice, st));
-        w.stats_keep = b0 > 0;
-        set_sub_batch_filters(w, filters, b0, bn, scope, filt_count);
-        const int rc = run_search(s, w, st, w.Qdev.as<float>(), (int)bn, (int)T, (int)nprobe, (int)k, w.outp.as<int64_t>(), w.outs.as<float>());
-        w.stats_keep = false;
-        w.filt = nullptr;
-        if (rc) return rc;
-        CLB_HIP(hipMemcpyAsync(out_pids + (size_t)b0 * k, w.outp.p, sizeof(int64_t) * bn * k, hipMemcpyDeviceToHost, st));
-        CLB_HIP(hipMemcpyAsync(out_scores + (size_t)b0 * k, w.outs.p, sizeof(float) * bn * k, hipMemcpyDeviceToHost, st));
-        CLB_HIP(hipMemcpyAsync(nc.data() + b0, w.ncand.p, sizeof(int) * bn, hipMemcpyDeviceToHost, st));
-        CLB_HIP(hipMemcpyAsync(fl.data() + b0, w.flags.p, sizeof(int) * bn, hipMemcpyDeviceToHost, st));
-    }
+    // the queries go up into the slot's own buffer and the results come back from it, sub-batch by sub-batch
+    CLB_TRY(for_sub_batches(s, w, T, B, nprobe, k, filters, scope, [&](int64_t b0, Batch& q) -> int {
+        CLB_HIP(hipMemcpyAsync(w.Qdev.p, Q + (size_t)b0 * T * s->dim, sizeof(float) * q.B * T * s->dim, hipMemcpyHostToDevice, st));
+        q.dQ = w.Qdev.as<float>();
+        q.d_out_pids = w.outp.as<int64_t>();
+        q.d_out_scores = w.outs.as<float>();
+        CLB_TRY(run_search(s, w, st, q));
+        CLB_HIP(hipMemcpyAsync(out_pids + (size_t)b0 * k, w.outp.p, sizeof(int64_t) * q.B * k, hipMemcpyDeviceToHost, st));
+        CLB_HIP(hipMemcpyAsync(out_scores + (size_t)b0 * k, w.outs.p, sizeof(float) * q.B * k, hipMemcpyDeviceToHost, st));
+        CLB_HIP(hipMemcpyAsync(nc.data() + b0, w.ncand.p, sizeof(int) * q.B, hipMemcpyDeviceToHost, st));
+        CLB_HIP(hipMemcpyAsync(fl.data() + b0, w.flags.p, sizeof(int) * q.B, hipMemcpyDeviceToHost, st));
+        return CLB_OK;
+    }));
     CLB_HIP(hipStreamSynchronize(st));
     int64_t docs = 0;
     for (int64_t b = 0; b < B; ++b) {
@@ -1454,8 +1426,9 @@ int clb_retrieve(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe, int
     CLB_TRY(ensure_workspace(s, w, 1, T, nprobe, 1));
     hipStream_t st = s->stream;
     CLB_HIP(hipMemcpyAsync(w.Qdev.p, Q, sizeof(float) * T * s->dim, hipMemcpyHostToDevice, st));
-    if (s->generic || T > 128) CLB_TRY(run_retrieve_general(s, w, st, w.Qdev.as<float>(), 0, (int)T, (int)nprobe));
-    else CLB_TRY(run_retrieve(s, w, st, w.Qdev.as<float>(), 1, (int)T, (int)nprobe));
+    const Batch q = make_batch(w.Qdev.as<float>(), 1, T, nprobe, 1);     // one query, no filter
+    if (s->generic || T > 128) CLB_TRY(run_retrieve_general(s, w, st, q, 0));
+    else CLB_TRY(run_retrieve(s, w, st, q));
     int nc = 0;
     CLB_HIP(hipMemcpyAsync(&nc, w.ncand.p, sizeof(int), hipMemcpyDeviceToHost, st));
     CLB_HIP(hipStreamSynchronize(st));
@@ -1515,7 +1488,7 @@ int clb_debug_scores(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe,
     for (int c = 0; c < Bd; ++c)
         CLB_HIP(hipMemcpyAsync(w.Qdev.as<float>() + (size_t)c * T * kDim, Q, sizeof(float) * T * kDim, hipMemcpyHostToDevice, st));
     const float* dQ = w.Qdev.as<float>();
-    CLB_TRY(run_retrieve(s, w, st, dQ, Bd, (int)T, (int)nprobe));
+    CLB_TRY(run_retrieve(s, w, st, make_batch(dQ, Bd, T, nprobe, k)));     // no filter
     launch_pass1(s, w, st, dQ, dim3(8 * 32), Bd, (int)T);
     hipLaunchKernelGGL(select_margin_kernel, dim3(1), dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), dQ,
                        (int)T, (int)k, w.cand_cap, s->approx_consts, w.list.as<int>(), w.nlist.as<int>(),
