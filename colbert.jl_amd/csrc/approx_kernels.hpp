@@ -1670,6 +1670,75 @@ __device__ __forceinline__ QueryBound query_bound(const float* __restrict__ Q, i
     return r;
 }
 
+// The cut of the two-pass mode for one query: every slot with approx >= thr = tau - 2 eps is listed.  `unsafe`: no
+// pre-filtering (eps = inf, thr = -inf: everything is listed).  tau_in (sharded search, phase 2): tau is the GLOBAL k-th
+// approximate score over all shards (global_tau_kernel); -inf means fewer than k candidates exist anywhere, i.e.
+// everything is listed.  Otherwise a query with more than k candidates cuts at its own k-th approximate score, which the
+// caller selects when needs_local_tau() says so; with at most k candidates everything is listed.
+struct Margin { float thr, tau, eps; };
+__device__ __forceinline__ bool needs_local_tau(bool unsafe, const float* tau_in, int n, int k) { return !unsafe && !tau_in && n > k; }
+__device__ __forceinline__ Margin margin_threshold(bool unsafe, float eps_sum, const float* __restrict__ tau_in, int b,
+                                                   bool local, float tau_local) {
+    Margin m{kNegInf, kNegInf, 0.f};
+    if (unsafe) {
+        m.eps = __builtin_inff();
+    } else if (tau_in) {
+        m.eps = eps_sum;
+        m.tau = tau_in[b];
+        m.thr = m.tau == kNegInf ? kNegInf : m.tau - 2.f * m.eps;
+    } else if (local) {
+        m.eps = eps_sum;
+        m.tau = tau_local;
+        m.thr = m.tau - 2.f * m.eps;
+    }
+    return m;
+}
+
+// Ordered compaction of the slots [lo, hi) with approx >= thr, appended to lst at position `run`; returns the position
+// behind them.  Blocks of 8 x 1024 consecutive slots: a thread's eight loads are in flight together and a block costs
+// ONE barrier (the wave counts alternate between the two halves of sh_big; the running total lives in a register of
+// every thread) -- with one load and three barriers per 1024 slots the load latency of every block was exposed: 0.37 ms
+// per batch at 96 k candidates per query.  Called by all 1 024 threads of the work-group.
+__device__ __forceinline__ int compact_blocks_ordered(const float* __restrict__ sc, int lo, int hi, float thr, int run,
+                                                      int* __restrict__ lst, int (&sh_big)[2][8][16]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int it = 0;
+    for (int base = lo; base < hi; base += 8192, ++it) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int i = base + j * 1024 + tid;
+            v[j] = i < hi ? sc[i] : 0.f;
+        }
+        int pre[8];
+        bool take[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int i = base + j * 1024 + tid;
+            take[j] = i < hi && !(v[j] < thr);   // NaN (unsafe query) is listed
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(take[j]);
+            pre[j] = (int)__popcll(m & ((1ull << lane) - 1ull));
+            if (lane == 0) sh_big[it & 1][j][wave] = (int)__popcll(m);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = lane < 16 ? sh_big[it & 1][j][lane] : 0;   // lanes 0..15: the 16 waves' counts of sub-block j
+            int x = c;
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) {
+                const int y = __shfl_up(x, o, 64);
+                if (lane >= o) x += y;
+            }
+            const int wbase = __shfl(x - c, wave, 64);
+            const int tot = __shfl(x, 15, 64);
+            if (take[j]) lst[run + wbase + pre[j]] = base + j * 1024 + tid;
+            run += tot;
+        }
+    }
+    return run;
+}
+
 static __global__ __launch_bounds__(1024) void select_margin_kernel(const float* __restrict__ scores,
                                                                    const int* __restrict__ ncand,
                                                                    const float* __restrict__ Q, int T, int k,
@@ -1706,9 +1775,7 @@ static __global__ __launch_bounds__(1024) void select_margin_kernel(const float*
         for (int c = 0; c < kSelCache; ++c) ckey[c] = (c < chunk && i0 + c < n) ? f32_order_key(sc[i0 + c]) : 0u;
     }
     const QueryBound qb = query_bound(Q, b, T, ac, &s_qn, &s_dq, tscale, s_aux, cell8 != 0);
-    float thr = kNegInf, tau_f = kNegInf, eps = 0.f;
-    const bool unsafe = qb.unsafe;
-    if (tid == 0) eps_pair[b] = unsafe ? __builtin_inff() : kEpsSafety * qb.eps_t;
+    if (tid == 0) eps_pair[b] = qb.unsafe ? __builtin_inff() : kEpsSafety * qb.eps_t;
 #define CLB_SEL_FOR_EACH(...)                                                                   \
     if (cached) {                                                                               \
         _Pragma("unroll") for (int c = 0; c < kSelCache; ++c) {                                 \
@@ -1726,70 +1793,22 @@ static __global__ __launch_bounds__(1024) void select_margin_kernel(const float*
             __VA_ARGS__                                                                         \
         }                                                                                       \
     }
-    if (unsafe) {
-        eps = __builtin_inff();          // thr stays -inf: everything is listed
-    } else if (tau_in) {
-        // sharded search, phase 2: tau is the GLOBAL k-th approximate score over all shards (global_tau_kernel); -inf
-        // means fewer than k candidates exist anywhere, i.e. everything is listed
-        eps = qb.eps_sum;
-        tau_f = tau_in[b];
-        thr = tau_f == kNegInf ? kNegInf : tau_f - 2.f * eps;
-    } else if (n > k) {
+    const bool local = needs_local_tau(qb.unsafe, tau_in, n, k);
+    if (local) {
         // coarse_tau (the unsharded search): two digit passes instead of four.  Any LOWER bound of the k-th approximate
         // score keeps the proof of the two-pass mode (it only lists more); the lower edge of the k-th key's 16-bit bin
         // is below it by at most 2^-16 of the score range (~5e-4 here against 2 eps ~ 0.09), and six block-wide
         // barriers of the 32-us kernel go away.  The sharded protocol publishes EXACT local thresholds and keeps all passes
         if (coarse_tau) { CLB_RADIX_SELECT_N(2) } else { CLB_RADIX_SELECT() }
-        eps = qb.eps_sum;
-        tau_f = f32_from_order_key(s_prefix);
-        thr = tau_f - 2.f * eps;
     }
-    // ordered compaction of the slots with approx >= thr (all of them when n <= k): one block-wide scan of the
-    // per-thread counts places every chunk in order
+    const Margin m = margin_threshold(qb.unsafe, qb.eps_sum, tau_in, b, local, f32_from_order_key(s_prefix));
+    const float thr = m.thr;
+    // ordered compaction of the slots with approx >= thr (all of them when n <= k)
     if (!cached) {
-        // large inputs: the same compaction in blocks of 8 x 1024 consecutive slots.  A thread's eight loads are in
-        // flight together and a block costs ONE barrier (the wave counts alternate between two LDS buffers; the running
-        // total lives in a register of every thread) -- with one load and three barriers per 1024 slots the load
-        // latency of every block was exposed: 0.37 ms per batch at 96 k candidates per query.
-        const int lane = tid & 63, wave = tid >> 6;
-        int run = 0, it = 0;
-        for (int base = 0; base < n; base += 8192, ++it) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int i = base + j * 1024 + tid;
-                v[j] = i < n ? sc[i] : 0.f;
-            }
-            int pre[8];
-            bool take[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int i = base + j * 1024 + tid;
-                take[j] = i < n && !(v[j] < thr);   // NaN (unsafe query) is listed
-                const unsigned long long m = __builtin_amdgcn_ballot_w64(take[j]);
-                pre[j] = (int)__popcll(m & ((1ull << lane) - 1ull));
-                if (lane == 0) sh_big[it & 1][j][wave] = (int)__popcll(m);
-            }
-            __syncthreads();
-            int offs = run;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int c = lane < 16 ? sh_big[it & 1][j][lane] : 0;   // lanes 0..15: the 16 waves' counts of sub-block j
-                int x = c;
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) {
-                    const int y = __shfl_up(x, o, 64);
-                    if (lane >= o) x += y;
-                }
-                const int wbase = __shfl(x - c, wave, 64);
-                const int tot = __shfl(x, 15, 64);
-                if (take[j]) lst[offs + wbase + pre[j]] = base + j * 1024 + tid;
-                offs += tot;
-            }
-            run = offs;
-        }
+        const int run = compact_blocks_ordered(sc, 0, n, thr, 0, lst, sh_big);
         if (tid == 0) s_run = run;
     } else {
+        // one block-wide scan of the per-thread counts places every chunk in order
         int cnt = 0;
         CLB_SEL_FOR_EACH((void)i; cnt += valid && !(f32_from_order_key(key) < thr);)
         const int lane = tid & 63, wave = tid >> 6;
@@ -1815,8 +1834,8 @@ static __global__ __launch_bounds__(1024) void select_margin_kernel(const float*
 #undef CLB_SEL_FOR_EACH
     if (tid == 0) {
         nlist[b] = s_run;
-        thresh[2 * b] = tau_f;
-        thresh[2 * b + 1] = eps;
+        thresh[2 * b] = m.tau;
+        thresh[2 * b + 1] = m.eps;
     }
 }
 
@@ -1841,9 +1860,10 @@ struct WideSel {
 };
 struct WideState {
     uint32_t prefix;
-    int remaining, shift, width;
+    int remaining;
+    DigitWindow win;     // the window of the next pass
     bool done;
-    float thr, tau, eps;
+    Margin m;
 };
 
 // slots [lo, hi) of work-group g: segments of whole 1 024-slot blocks
@@ -1859,51 +1879,31 @@ __device__ __forceinline__ void wide_segment(int n, int g, int& lo, int& hi) {
 __device__ __forceinline__ WideState wide_replay(const WideSel& w, int n, int k, const float* __restrict__ tau_in, int b,
                                                  int upto, int* hist, uint32_t* s_prefix, int* s_remaining) {
     const int tid = threadIdx.x;
-    WideState st;
-    st.prefix = 0u; st.remaining = 0; st.shift = 0; st.width = 0; st.done = true;
-    st.thr = kNegInf; st.tau = kNegInf; st.eps = 0.f;
-    if (w.unsafe) {
-        st.eps = __builtin_inff();                        // everything is listed
-    } else if (tau_in) {                                  // sharded search, phase 2: the global threshold
-        st.eps = w.eps_sum;
-        st.tau = tau_in[b];
-        st.thr = st.tau == kNegInf ? kNegInf : st.tau - 2.f * st.eps;
-    } else if (n > k) {
-        st.eps = w.eps_sum;
-        const uint32_t gmax = w.kmax, gmin = ~w.kmin_inv;
-        const uint32_t diff = gmin ^ gmax;
-        if (diff == 0u) {
-            st.prefix = gmax;
-            st.tau = f32_from_order_key(gmax);
-            st.thr = st.tau - 2.f * st.eps;
-        } else {
-            const int top = 31 - __clz((int)diff);
-            st.shift = top > 7 ? top - 7 : 0;
-            st.width = top - st.shift + 1;
-            st.prefix = top == 31 ? 0u : (gmax & (0xffffffffu << (top + 1)));
+    WideState st{0u, 0, DigitWindow(), true, {}};
+    const bool local = needs_local_tau(w.unsafe != 0, tau_in, n, k);
+    if (local) {
+        const uint32_t gmax = w.kmax, diff = ~w.kmin_inv ^ gmax;
+        st.prefix = gmax;                                 // all keys equal: that key
+        if (diff != 0u) {
+            st.win = DigitWindow(diff);
+            st.prefix = st.win.seed_prefix(gmax);
             st.remaining = k;
             st.done = false;
             for (int p = 0; p < upto && !st.done; ++p) {  // uniform over the work-group
                 __syncthreads();
                 if (tid < 256) hist[tid] = w.hist[p][tid];
                 __syncthreads();
-                if (tid < 64) radix_pick(hist, st.remaining, st.prefix, st.shift, s_prefix, s_remaining);
+                if (tid < 64) radix_pick(hist, st.remaining, st.prefix, st.win.shift, s_prefix, s_remaining);
                 __syncthreads();
                 st.prefix = *s_prefix;
                 st.remaining = *s_remaining;
-                if (st.shift == 0) {
-                    st.tau = f32_from_order_key(st.prefix);
-                    st.thr = st.tau - 2.f * st.eps;
-                    st.done = true;
-                } else {
-                    const int ns = st.shift > 8 ? st.shift - 8 : 0;
-                    st.width = st.shift - ns;
-                    st.shift = ns;
-                }
+                if (st.win.last()) st.done = true; else st.win.advance();
             }
             __syncthreads();
         }
     }
+    // (passes still to come: the cut is not known yet, nothing is read from it)
+    st.m = margin_threshold(w.unsafe != 0, w.eps_sum, tau_in, b, local, st.done ? f32_from_order_key(st.prefix) : kNegInf);
     return st;
 }
 
@@ -1940,12 +1940,7 @@ static __global__ __launch_bounds__(1024) void wide_minmax_kernel(const float* _
         kmin = key < kmin ? key : kmin;
         kmax = key > kmax ? key : kmax;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t a = __shfl_xor(kmin, o, 64), c = __shfl_xor(kmax, o, 64);
-        kmin = a < kmin ? a : kmin;
-        kmax = c > kmax ? c : kmax;
-    }
+    wave_minmax_keys(kmin, kmax);
     if ((tid & 63) == 0) { atomicMin(&s_kmin, kmin); atomicMax(&s_kmax, kmax); }
     __syncthreads();
     if (tid == 0 && lo < hi) { atomicMax(&w.kmax, s_kmax); atomicMax(&w.kmin_inv, ~s_kmin); }
@@ -1964,10 +1959,8 @@ static __global__ __launch_bounds__(1024) void wide_hist_kernel(const float* __r
     const WideState st = wide_replay(w, n, k, nullptr, b, pass, hist, &s_prefix, &s_remaining);
     if (st.done) return;                                  // uniform over the work-group
     const float* sc = scores + (size_t)b * cand_cap;
-    const uint32_t prefix = st.prefix;
-    const int shift = st.shift, width = st.width;
-    const uint32_t himask = shift + width >= 32 ? 0u : (0xffffffffu << (shift + width));
-    const uint32_t bmask = (1u << width) - 1u;
+    const uint32_t prefix = st.prefix, himask = st.win.himask(), bmask = st.win.bmask();
+    const int shift = st.win.shift;
     __syncthreads();
     if (tid < 256) hist[tid] = 0;
     __syncthreads();
@@ -1996,7 +1989,7 @@ static __global__ __launch_bounds__(1024) void wide_count_kernel(const float* __
     WideSel& w = wsel[b];
     const int n = ncand[b];
     const float* sc = scores + (size_t)b * cand_cap;
-    const float thr = wide_replay(w, n, k, tau_in, b, 4, hist, &s_prefix, &s_remaining).thr;
+    const float thr = wide_replay(w, n, k, tau_in, b, 4, hist, &s_prefix, &s_remaining).m.thr;
     __syncthreads();
     if (tid == 0) s_cnt = 0;
     __syncthreads();
@@ -2025,10 +2018,7 @@ static __global__ __launch_bounds__(1024) void wide_emit_kernel(const float* __r
     const int b = blockIdx.y, g = blockIdx.x, tid = threadIdx.x;
     const WideSel& w = wsel[b];
     const int n = ncand[b];
-    const float* sc = scores + (size_t)b * cand_cap;
-    int* lst = list + (size_t)b * cand_cap;
-    const WideState st = wide_replay(w, n, k, tau_in, b, 4, hist, &s_prefix, &s_remaining);
-    const float thr = st.thr;
+    const Margin m = wide_replay(w, n, k, tau_in, b, 4, hist, &s_prefix, &s_remaining).m;
     int run = 0, total = 0;
 #pragma unroll
     for (int j = 0; j < kWideBlocks; ++j) {
@@ -2038,48 +2028,12 @@ static __global__ __launch_bounds__(1024) void wide_emit_kernel(const float* __r
     }
     if (g == 0 && tid == 0) {
         nlist[b] = total;
-        thresh[2 * b] = st.tau;
-        thresh[2 * b + 1] = st.eps;
+        thresh[2 * b] = m.tau;
+        thresh[2 * b + 1] = m.eps;
     }
     int lo, hi;
     wide_segment(n, g, lo, hi);
-    const int lane = tid & 63, wave = tid >> 6;
-    int it = 0;
-    for (int base = lo; base < hi; base += 8192, ++it) {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int i = base + j * 1024 + tid;
-            v[j] = i < hi ? sc[i] : 0.f;
-        }
-        int pre[8];
-        bool take[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int i = base + j * 1024 + tid;
-            take[j] = i < hi && !(v[j] < thr);
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(take[j]);
-            pre[j] = (int)__popcll(m & ((1ull << lane) - 1ull));
-            if (lane == 0) sh_big[it & 1][j][wave] = (int)__popcll(m);
-        }
-        __syncthreads();
-        int offs = run;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int c = lane < 16 ? sh_big[it & 1][j][lane] : 0;
-            int x = c;
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) {
-                const int y = __shfl_up(x, o, 64);
-                if (lane >= o) x += y;
-            }
-            const int wbase = __shfl(x - c, wave, 64);
-            const int tot = __shfl(x, 15, 64);
-            if (take[j]) lst[offs + wbase + pre[j]] = base + j * 1024 + tid;
-            offs += tot;
-        }
-        run = offs;
-    }
+    compact_blocks_ordered(scores + (size_t)b * cand_cap, lo, hi, m.thr, run, list + (size_t)b * cand_cap, sh_big);
 }
 
 // -------------------------------------------------------------------------------------------------------------

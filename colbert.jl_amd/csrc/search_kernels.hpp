@@ -780,9 +780,6 @@ static __global__ __launch_bounds__(256, 3) void score_exact_kernel(
 #undef CLB_ROW_STORE
 }
 
-// hist[bin] += 1 for every active lane.  MaxSim scores of one query share their exponent and leading mantissa bits,
-// so in the first radix passes a whole wave hits one or two bins and per-lane LDS atomics serialise 64 deep; lanes
-// sharing a bin are therefore merged into one atomic (up to four distinct bins per call, plain atomics after that).
 // -------------------------------------------------------------------------------------------------
 // Pass 2 of the two-pass mode as a flat step pipeline (nbits 2, T <= 32).  Same arithmetic per step as
 // score_exact_kernel<2, true>; what changes is the control structure.  With the row subset a listed passage is
@@ -1107,6 +1104,9 @@ __device__ __forceinline__ void radix_pick(const int* hist, int rem, uint32_t pr
 
 constexpr int kSelCache = 32;   // elements per thread kept in registers by the selection kernels
 
+// hist[bin] += 1 for every active lane.  MaxSim scores of one query share their exponent and leading mantissa bits,
+// so in the first radix passes a whole wave hits one or two bins and per-lane LDS atomics serialise 64 deep; lanes
+// sharing a bin are therefore merged into one atomic (up to four distinct bins per call, plain atomics after that).
 __device__ __forceinline__ void hist_add_aggregated(int* hist, uint32_t bin, bool active) {
     const int lane = threadIdx.x & 63;
     unsigned long long todo = __builtin_amdgcn_ballot_w64(active);
@@ -1120,6 +1120,39 @@ __device__ __forceinline__ void hist_add_aggregated(int* hist, uint32_t bin, boo
         todo &= ~same;
     }
     if ((todo >> lane) & 1ull) atomicAdd(&hist[bin], 1);
+}
+
+// The digit schedule of the radix selection: the bits [shift, shift + width) of the current pass.  The first window is the
+// (up to) eight bits ending at the highest bit in which the smallest and the largest key differ, then eight bits at a time.
+struct DigitWindow {
+    int shift = 0, width = 0;
+    DigitWindow() = default;
+    __device__ __forceinline__ explicit DigitWindow(uint32_t diff /* kmin ^ kmax, not 0 */) {
+        const int top = 31 - __clz((int)diff);
+        shift = top > 7 ? top - 7 : 0;
+        width = top - shift + 1;
+    }
+    // the bits above the window: a key takes part in the pass when (key & himask()) == prefix
+    __device__ __forceinline__ uint32_t himask() const { return shift + width >= 32 ? 0u : (0xffffffffu << (shift + width)); }
+    __device__ __forceinline__ uint32_t bmask() const { return (1u << width) - 1u; }
+    // the prefix before the first pass: the leading bits all keys share (none when the sign bit differs)
+    __device__ __forceinline__ uint32_t seed_prefix(uint32_t kmax) const { return kmax & himask(); }
+    __device__ __forceinline__ bool last() const { return shift == 0; }
+    __device__ __forceinline__ void advance() {
+        const int ns = shift > 8 ? shift - 8 : 0;
+        width = shift - ns;
+        shift = ns;
+    }
+};
+
+// min / max of order keys over the 64 lanes of a wave, left in every lane
+__device__ __forceinline__ void wave_minmax_keys(uint32_t& kmin, uint32_t& kmax) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t a = __shfl_xor(kmin, o, 64), b = __shfl_xor(kmax, o, 64);
+        kmin = a < kmin ? a : kmin;
+        kmax = b > kmax ? b : kmax;
+    }
 }
 
 // Radix select of the rem-th largest of the block's keys, written with the CLB_SEL_FOR_EACH macro of the calling
@@ -1137,11 +1170,7 @@ __device__ __forceinline__ void hist_add_aggregated(int* hist, uint32_t bin, boo
     {                                                                                                       \
         uint32_t kmin_ = 0xffffffffu, kmax_ = 0u;                                                           \
         CLB_SEL_FOR_EACH(if (valid) { kmin_ = key < kmin_ ? key : kmin_; kmax_ = key > kmax_ ? key : kmax_; }) \
-        _Pragma("unroll") for (int o_ = 32; o_ > 0; o_ >>= 1) {                                             \
-            const uint32_t a_ = __shfl_xor(kmin_, o_, 64), b_ = __shfl_xor(kmax_, o_, 64);                  \
-            kmin_ = a_ < kmin_ ? a_ : kmin_;                                                                \
-            kmax_ = b_ > kmax_ ? b_ : kmax_;                                                                \
-        }                                                                                                   \
+        wave_minmax_keys(kmin_, kmax_);                                                                     \
         if (tid == 0) { s_kmin = 0xffffffffu; s_kmax = 0u; }                                                \
         __syncthreads();                                                                                    \
         if ((tid & 63) == 0) { atomicMin(&s_kmin, kmin_); atomicMax(&s_kmax, kmax_); }                      \
@@ -1151,26 +1180,20 @@ __device__ __forceinline__ void hist_add_aggregated(int* hist, uint32_t bin, boo
             if (tid == 0) s_prefix = s_kmax;          /* all keys equal: rank unchanged */                  \
             __syncthreads();                                                                                \
         } else {                                                                                            \
-            const int top_ = 31 - __clz((int)diff_);                                                        \
-            int shift_ = top_ > 7 ? top_ - 7 : 0;                                                           \
-            int width_ = top_ - shift_ + 1;                                                                 \
-            if (tid == 0) s_prefix = top_ == 31 ? 0u : (s_kmax & (0xffffffffu << (top_ + 1)));              \
-            int passes_ = 0;                                                                                \
-            for (;;) {                                                                                      \
+            DigitWindow win_(diff_);                                                                        \
+            if (tid == 0) s_prefix = win_.seed_prefix(s_kmax);                                              \
+            for (int passes_ = 0;;) {                                                                       \
                 if (tid < 256) hist[tid] = 0;                                                               \
                 __syncthreads();                                                                            \
-                const uint32_t prefix_ = s_prefix;                                                          \
-                const uint32_t himask_ = shift_ + width_ >= 32 ? 0u : (0xffffffffu << (shift_ + width_));   \
-                const uint32_t bmask_ = (1u << width_) - 1u;                                                \
+                const uint32_t prefix_ = s_prefix, himask_ = win_.himask(), bmask_ = win_.bmask();          \
+                const int shift_ = win_.shift;                                                              \
                 CLB_SEL_FOR_EACH(hist_add_aggregated(hist, (key >> shift_) & bmask_,                        \
                                                      valid && (key & himask_) == prefix_);)                 \
                 __syncthreads();                                                                            \
                 if (tid < 64) radix_pick(hist, s_remaining, prefix_, shift_, &s_prefix, &s_remaining);      \
                 __syncthreads();                                                                            \
-                if (shift_ == 0 || ++passes_ >= (LIMIT)) break;                                             \
-                const int ns_ = shift_ > 8 ? shift_ - 8 : 0;                                                \
-                width_ = shift_ - ns_;                                                                      \
-                shift_ = ns_;                                                                               \
+                if (win_.last() || ++passes_ >= (LIMIT)) break;                                             \
+                win_.advance();                                                                             \
             }                                                                                               \
         }                                                                                                   \
     }

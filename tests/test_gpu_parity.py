@@ -570,6 +570,24 @@ def test_search_ties_keep_ascending_pid(oracle):
     check_search(oracle, idx, synthetic.make_queries(idx, 18, 2), k=60)
 
 
+def test_search_all_scores_equal(oracle):
+    """Every passage a copy of passage 0: all candidates of a query score the same, so the smallest and the largest
+    key of every selection agree (no digit is ever picked).  The single pass returns pids 1..k in order, the two-pass
+    modes list everything with the same tau -- one work-group per query and sixteen."""
+    idx = synthetic.make_index(seed=31, n_docs=400, K=32, constant_doclen=True, doclen_mean=16)
+    L = 16
+    for p in range(1, 400):
+        idx["codes"][p * L:(p + 1) * L] = idx["codes"][:L]
+        idx["residuals"][:, p * L:(p + 1) * L] = idx["residuals"][:, :L]
+    idx["ivf"], idx["ivf_lengths"] = synthetic.build_ivf(idx["codes"], 32)
+    Qs = synthetic.make_queries(idx, 32, 3)
+    for j in range(3):                                           # seeds chosen so: nothing passes on an empty list
+        rp, rs, rn = oracle.search(idx, Qs[:, :, j], nprobe=2, k=60)
+        assert rn == 400 and np.array_equal(rp, np.arange(1, 61)) and len(set(bits(rs).tolist())) == 1
+    check_search(oracle, idx, Qs, k=60)
+    check_search(oracle, idx, Qs, k=60, wide=1)
+
+
 def test_search_tied_centroids(oracle):
     """Many identical centroids: every score ties, the bf16x3 candidate lists overflow and the refine kernel must
     fall back to the exhaustive canonical scan -- the selected centroids are still the lowest indices
