@@ -94,6 +94,9 @@ def lib() -> C.CDLL:
         l.clb_comm_unique_id_bytes.restype = C.c_int64
         l.clb_kmeans_shard_block_bytes.restype = C.c_int64
         l.clb_filter_count.restype = C.c_int64
+        l.clb_searcher_generation.restype = C.c_int64
+        l.clb_searcher_num_docs.restype = C.c_int64
+        l.clb_searcher_num_embeddings.restype = C.c_int64
         _lib = l
     return _lib
 

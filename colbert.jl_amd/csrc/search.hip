@@ -7,6 +7,7 @@
 #include <cstring>
 #include <numeric>
 
+#include "append_kernels.hpp"
 #include "approx_kernels.hpp"
 #include "generic_kernels.hpp"
 #include "search_kernels.hpp"
@@ -128,6 +129,7 @@ struct clb_searcher {
     Prof prof;
     int64_t last_cand_docs = 0, last_cand_embs = 0, last_resc_docs = 0, last_resc_embs = 0;
     int64_t index_bytes = 0;
+    int64_t generation = 0;    // clb_searcher_append calls that changed the handle
 };
 
 namespace {
@@ -823,8 +825,10 @@ int check_filters(const clb_searcher* s, const clb_filter* const* filters, int64
     for (int64_t b = 0; b < B; ++b) {
         const clb_filter* f = filters[b];
         if (!f) continue;
-        if (f->owner != s->serial || f->n_docs != s->n_docs)
+        if (f->owner != s->serial)
             return fail(CLB_EARGUMENT, "the filter of query %lld was made for another searcher", (long long)b);
+        if (f->n_docs != s->n_docs)       // its bitmap has the old length
+            return fail(CLB_EARGUMENT, "the filter of query %lld: filter made before an append; make another", (long long)b);
         if (scope == CLB_FILTER_ALL) *filt_count = std::max(*filt_count, (size_t)f->count);
     }
     return CLB_OK;
@@ -862,6 +866,82 @@ int for_sub_batches(clb_searcher* s, Workspace& w, int64_t T, int64_t B, int64_t
         CLB_TRY(run_one(b0, q));
     }
     return CLB_OK;
+}
+
+// ---- what a handle derives from its resident index: clb_searcher_create and clb_searcher_append both end here ----------
+
+// the list lengths, descending, from the host copy of ivf_off (K + 1 entries): the candidate-capacity bound
+std::vector<uint32_t> sorted_list_lengths(const std::vector<uint32_t>& ivf_off) {
+    std::vector<uint32_t> len(ivf_off.size() - 1);
+    for (size_t c = 0; c + 1 < ivf_off.size(); ++c) len[c] = ivf_off[c + 1] - ivf_off[c];
+    std::sort(len.begin(), len.end(), std::greater<uint32_t>());
+    return len;
+}
+
+int64_t resident_bytes(const clb_searcher* s) {
+    return (int64_t)(s->centroids.bytes + s->weights.bytes + s->codes0.bytes + s->residuals.bytes + s->doc_off.bytes +
+                     s->ivf_off.bytes + s->ivf_pid.bytes + s->codeinv.bytes);
+}
+
+// Statistics and tables of the tuned path over a whole index (codes0 / residuals as the handle stores them, padded by
+// kStepRows).  Derived beside the handle and installed in one step, so that a failure leaves the handle as it was.
+struct IndexTables {
+    double code_adjacency = 0.0;
+    ApproxConsts consts{};
+    float inv_lo = 0.f, inv_step = 0.f;
+    DevBuf codeinv;
+};
+
+int derive_index_tables(const clb_searcher* s, const uint32_t* codes0, const uint8_t* residuals, int64_t n_emb, IndexTables* t) {
+    {   // Pass 1's gather form, by the index's own code statistics: when neighbouring embeddings of a passage often share
+        // a 128-byte line of the score table (id-adjacent codes: the L1 merges those requests of the per-lane VGPR
+        // gather) the VGPR form is faster (1 M topical passages: 0.67 against 0.76 ms per batch); when they do not
+        // (uniform codes, a k-means-built index) the LDS-DMA form is (uniform: 1.47 against 1.61 ms)
+        DevBuf cnt;
+        CLB_TRY(cnt.alloc(sizeof(unsigned long long)));
+        unsigned long long adj = 0;
+        const int64_t n_sample = std::min<int64_t>(n_emb, (int64_t)1 << 24);
+        if (hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), s->stream) != hipSuccess) return fail(CLB_EHIP, "memset failed");
+        if (n_sample > 1)
+            hipLaunchKernelGGL(code_adjacency_kernel, dim3(1024), dim3(256), 0, s->stream, codes0, n_sample,
+                               cnt.as<unsigned long long>());
+        if (hipMemcpyAsync(&adj, cnt.p, sizeof adj, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+            hipStreamSynchronize(s->stream) != hipSuccess)
+            return fail(CLB_EHIP, "code statistics failed");
+        t->code_adjacency = n_sample > 1 ? (double)adj / (double)(n_sample - 1) : 0.0;
+    }
+    if (s->approx_ok) {
+        CLB_TRY(t->codeinv.alloc(sizeof(uint32_t) * (n_emb + kStepRows)));
+        if (hipMemsetAsync(t->codeinv.p, 0, t->codeinv.bytes, s->stream) != hipSuccess) return fail(CLB_EHIP, "memset failed");
+    }
+    return build_approx_tables(s->stream, s->centroids.as<float>(), s->weights.as<float>(), codes0, residuals, n_emb, (int)s->K,
+                               s->approx_ok ? t->codeinv.as<uint32_t>() : nullptr, s->cbits, 1 << s->nbits, &t->consts,
+                               &t->inv_lo, &t->inv_step);
+}
+
+inline void swap_buf(DevBuf& a, DevBuf& b) { std::swap(a.p, b.p); std::swap(a.bytes, b.bytes); }
+
+// keep_max: the handle's bound constants are a shard group's (bounds_synced) -- like `set`, an append never lowers one
+void install_index_tables(clb_searcher* s, IndexTables& t, bool keep_max = false) {
+    s->code_adjacency = t.code_adjacency;
+    // ... and only pays when the query's score table (64 B per centroid) does not fit the 4-MB L2 of an XCD: with a
+    // resident table the two forms are equal within 2 % (built index, K = 32 768: 0.663 / 0.668 ms)
+    s->gather_lds = s->code_adjacency < 0.2 && (int64_t)s->K * 64 > ((int64_t)4 << 20);
+    swap_buf(s->codeinv, t.codeinv);
+    s->inv_lo = t.inv_lo; s->inv_step = t.inv_step;
+    const ApproxConsts old = s->approx_consts;
+    s->approx_consts = t.consts;
+    // the fp16 side's error lives beside the consts: a table made by the three-product kernels (fewer than 16 queries) keeps
+    // the tighter bound.  Infinite (a centroid component beyond the fp16 range): the single-product kernel is never chosen.
+    s->dc_f16 = std::isfinite(s->approx_consts.dc_max) ? s->approx_consts.dc_max : 0.f;
+    s->approx_consts.dc_max = 0.f;
+    if (keep_max) {
+        ApproxConsts& a = s->approx_consts;
+        a.cn_max = std::max(a.cn_max, old.cn_max); a.rn_max = std::max(a.rn_max, old.rn_max);
+        a.inv_max = std::max(a.inv_max, old.inv_max); a.rb_max = std::max(a.rb_max, old.rb_max);
+        a.dw_rn = std::max(a.dw_rn, old.dw_rn); a.inv_qerr = std::max(a.inv_qerr, old.inv_qerr);
+    }
+    s->index_bytes = resident_bytes(s);
 }
 
 }  // namespace
@@ -943,9 +1023,7 @@ static int searcher_create_impl(int device, int64_t dim, int nbits, int64_t K, c
     auto bail = [&](int rc) { clb_searcher_destroy(s); return rc; };
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess)
         return bail(fail(CLB_EHIP, "hipStreamCreate failed"));
-    s->ivf_len_sorted.resize((size_t)K);
-    for (int64_t c = 0; c < K; ++c) s->ivf_len_sorted[c] = (uint32_t)ivf_lengths[c];
-    std::sort(s->ivf_len_sorted.begin(), s->ivf_len_sorted.end(), std::greater<uint32_t>());
+    s->ivf_len_sorted = sorted_list_lengths(ivf_off);
 
     const size_t rows = (size_t)(dim / 8 * nbits);
     int rc;
@@ -1019,8 +1097,7 @@ static int searcher_create_impl(int device, int64_t dim, int nbits, int64_t K, c
     }
     if (s->generic) {
         s->mode = 0;
-        s->index_bytes = (int64_t)(s->centroids.bytes + s->weights.bytes + s->codes0.bytes + s->residuals.bytes +
-                                   s->doc_off.bytes + s->ivf_off.bytes + s->ivf_pid.bytes);
+        s->index_bytes = resident_bytes(s);
         *out = s;
         return CLB_OK;
     }
@@ -1038,42 +1115,10 @@ static int searcher_create_impl(int device, int64_t dim, int nbits, int64_t K, c
     while (((int64_t)1 << s->cbits) < K) ++s->cbits;
     // the packed word leaves 32 - cbits bits for inv_norm: at least 12 (K <= 2^20), otherwise exact mode only
     s->approx_ok = approx_supported((int)dim, nbits) && s->cbits <= 20;
-    {   // Pass 1's gather form, by the index's own code statistics: when neighbouring embeddings of a passage often share
-        // a 128-byte line of the score table (id-adjacent codes: the L1 merges those requests of the per-lane VGPR
-        // gather) the VGPR form is faster (1 M topical passages: 0.67 against 0.76 ms per batch); when they do not
-        // (uniform codes, a k-means-built index) the LDS-DMA form is (uniform: 1.47 against 1.61 ms)
-        DevBuf cnt;
-        if ((rc = cnt.alloc(sizeof(unsigned long long)))) return bail(rc);
-        unsigned long long adj = 0;
-        const int64_t n_sample = std::min<int64_t>(n_emb, (int64_t)1 << 24);
-        if (hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), s->stream) != hipSuccess) return bail(fail(CLB_EHIP, "memset failed"));
-        if (n_sample > 1)
-            hipLaunchKernelGGL(code_adjacency_kernel, dim3(1024), dim3(256), 0, s->stream, s->codes0.as<uint32_t>(), n_sample,
-                               cnt.as<unsigned long long>());
-        if (hipMemcpyAsync(&adj, cnt.p, sizeof adj, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-            hipStreamSynchronize(s->stream) != hipSuccess)
-            return bail(fail(CLB_EHIP, "code statistics failed"));
-        s->code_adjacency = n_sample > 1 ? (double)adj / (double)(n_sample - 1) : 0.0;
-        // ... and only pays when the query's score table (64 B per centroid) does not fit the 4-MB L2 of an XCD: with a
-        // resident table the two forms are equal within 2 % (built index, K = 32 768: 0.663 / 0.668 ms)
-        s->gather_lds = s->code_adjacency < 0.2 && (int64_t)K * 64 > ((int64_t)4 << 20);
-    }
-    if (s->approx_ok) {
-        if ((rc = s->codeinv.alloc(sizeof(uint32_t) * (n_emb + kStepRows)))) return bail(rc);
-        if (hipMemsetAsync(s->codeinv.p, 0, s->codeinv.bytes, s->stream) != hipSuccess) return bail(fail(CLB_EHIP, "memset failed"));
-    }
-    if ((rc = build_approx_tables(s->stream, s->centroids.as<float>(), s->weights.as<float>(),
-                                  s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(), n_emb, (int)K,
-                                  s->approx_ok ? s->codeinv.as<uint32_t>() : nullptr, s->cbits, 1 << nbits,
-                                  &s->approx_consts, &s->inv_lo, &s->inv_step)))
-        return bail(rc);
-    // the fp16 side's error lives beside the consts: a table made by the three-product kernels (fewer than 16 queries) keeps
-    // the tighter bound.  Infinite (a centroid component beyond the fp16 range): the single-product kernel is never chosen.
-    s->dc_f16 = std::isfinite(s->approx_consts.dc_max) ? s->approx_consts.dc_max : 0.f;
-    s->approx_consts.dc_max = 0.f;
+    IndexTables tables;
+    if ((rc = derive_index_tables(s, s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(), n_emb, &tables))) return bail(rc);
+    install_index_tables(s, tables);
     s->mode = s->approx_ok ? 1 : 0;
-    s->index_bytes = (int64_t)(s->centroids.bytes + s->weights.bytes + s->codes0.bytes + s->residuals.bytes +
-                               s->doc_off.bytes + s->ivf_off.bytes + s->ivf_pid.bytes + s->codeinv.bytes);
     *out = s;
     return CLB_OK;
 }
@@ -1091,6 +1136,172 @@ int clb_searcher_destroy(clb_searcher* s) {
     delete s;
     return CLB_OK;
 }
+
+// clb_searcher_append / _device (include/colbert_hip.h).  Everything is built beside the handle's arrays -- the grown codes0 /
+// residuals / doc_off, the merged inverted lists, the approximate-pass tables of the WHOLE grown index -- and swapped in
+// after the last device work has been waited for: any return before that leaves the handle untouched.
+static int searcher_append_impl(clb_searcher* s, int64_t n_new, const int64_t* doclens, int64_t n_new_emb,
+                                const uint32_t* codes, const uint8_t* residuals, bool on_device) {
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    if (n_new < 0 || n_new_emb < 0) return fail(CLB_EARGUMENT, "negative sizes");
+    if ((n_new > 0 && !doclens) || (n_new_emb > 0 && (!codes || !residuals))) return fail(CLB_EARGUMENT, "null argument");
+    std::vector<uint32_t> new_off((size_t)n_new + 1);       // offsets of the appended passages among the appended embeddings
+    int64_t run = 0, new_max_doclen = 0;
+    for (int64_t p = 0; p < n_new; ++p) {
+        if (doclens[p] < 0) return fail(CLB_EARGUMENT, "negative doclen at appended passage %lld", (long long)(p + 1));
+        new_off[p] = (uint32_t)run;
+        run += doclens[p];
+        new_max_doclen = std::max(new_max_doclen, doclens[p]);
+    }
+    new_off[n_new] = (uint32_t)run;
+    if (run != n_new_emb)
+        return fail(CLB_EDIMENSION, "sum(doclens)=%lld must equal the number of embeddings %lld", (long long)run, (long long)n_new_emb);
+    if (n_new == 0) return CLB_OK;
+    const int64_t n_old = s->n_emb, d_old = s->n_docs, n_tot = n_old + n_new_emb, d_tot = d_old + n_new, K = s->K;
+    if (n_tot >= (int64_t)0xffffffffll || d_tot >= (int64_t)0x7fffffffll)
+        return fail(CLB_EUNSUPPORTED, "a shard holds at most 2^32-1 embeddings / 2^31-1 passages");
+    CLB_TRY(use_device(s->device));
+    CLB_HIP(hipDeviceSynchronize());      // searches of this handle and whatever wrote the caller's device arrays
+    const hipStream_t st = s->stream;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const size_t rows = (size_t)(s->dim / 8 * s->nbits);
+    const int blocks = (int)((n_new_emb + 255) / 256);
+    constexpr int64_t kPad = kStepRows;
+
+    // the new codes, 0-based and checked, in a buffer of the call's own (the caller's array is never written)
+    DevBuf codes_in, err;
+    CLB_TRY(codes_in.alloc(sizeof(uint32_t) * n_new_emb));
+    CLB_TRY(err.alloc(sizeof(int)));
+    CLB_HIP(hipMemsetAsync(err.p, 0, sizeof(int), st));
+    if (n_new_emb > 0) {
+        CLB_HIP(hipMemcpyAsync(codes_in.p, codes, sizeof(uint32_t) * n_new_emb, kind, st));
+        hipLaunchKernelGGL(codes_to_zero_based_kernel, dim3(blocks), dim3(256), 0, st, codes_in.as<uint32_t>(), n_new_emb,
+                           (uint32_t)K, err.as<int>());
+    }
+    int herr = 0;
+    CLB_HIP(hipMemcpyAsync(&herr, err.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    CLB_HIP(hipStreamSynchronize(st));
+    if (herr & 2) return fail(CLB_EDOMAIN, "All the codes must be in the valid range of centroid IDs!");
+
+    // grown per-embedding and per-passage arrays: the old rows, the new rows behind them, the zero padding of one step
+    DevBuf codes0, res, doc_off, new_off_d;
+    CLB_TRY(codes0.alloc(sizeof(uint32_t) * (n_tot + kPad)));
+    CLB_TRY(res.alloc(rows * (n_tot + kPad)));
+    CLB_TRY(doc_off.alloc(sizeof(uint32_t) * (d_tot + 1)));
+    CLB_TRY(upload(new_off_d, new_off.data(), sizeof(uint32_t) * new_off.size(), st));
+    uint32_t* codes0_tail = codes0.as<uint32_t>() + n_old;
+    uint8_t* res_tail = res.as<uint8_t>() + rows * n_old;
+    CLB_HIP(hipMemcpyAsync(codes0.p, s->codes0.p, sizeof(uint32_t) * n_old, hipMemcpyDeviceToDevice, st));
+    CLB_HIP(hipMemcpyAsync(res.p, s->residuals.p, rows * n_old, hipMemcpyDeviceToDevice, st));
+    CLB_HIP(hipMemsetAsync(codes0.as<uint32_t>() + n_tot, 0, sizeof(uint32_t) * kPad, st));
+    CLB_HIP(hipMemsetAsync(res.as<uint8_t>() + rows * n_tot, 0, rows * kPad, st));
+    CLB_HIP(hipMemcpyAsync(doc_off.p, s->doc_off.p, sizeof(uint32_t) * (d_old + 1), hipMemcpyDeviceToDevice, st));
+    std::vector<uint32_t> off_tail((size_t)n_new);
+    for (int64_t p = 0; p < n_new; ++p) off_tail[p] = (uint32_t)(n_old + new_off[p + 1]);
+    CLB_HIP(hipMemcpyAsync(doc_off.as<uint32_t>() + d_old + 1, off_tail.data(), sizeof(uint32_t) * n_new, hipMemcpyHostToDevice, st));
+    if (n_new_emb > 0 && !s->generic) {
+        // the per-passage code order of create, on the new passages alone (old passages keep theirs): the same key, sort
+        // and permute kernels over the new rows and their own offsets, written straight into the tail of the grown arrays
+        DevBuf res_in, keys, keys2, vals, perm;
+        const uint8_t* res_src = residuals;
+        if (!on_device || ((uintptr_t)residuals & 15)) {        // the row permutation reads 16-byte pieces
+            CLB_TRY(res_in.alloc(rows * n_new_emb));
+            CLB_HIP(hipMemcpyAsync(res_in.p, residuals, rows * n_new_emb, kind, st));
+            res_src = res_in.as<uint8_t>();
+        }
+        CLB_TRY(keys.alloc(sizeof(uint64_t) * n_new_emb));
+        CLB_TRY(keys2.alloc(sizeof(uint64_t) * n_new_emb));
+        CLB_TRY(vals.alloc(sizeof(uint32_t) * n_new_emb));
+        CLB_TRY(perm.alloc(sizeof(uint32_t) * n_new_emb));
+        hipLaunchKernelGGL(passage_code_keys_kernel, dim3(blocks), dim3(256), 0, st, codes_in.as<uint32_t>(),
+                           new_off_d.as<uint32_t>(), n_new_emb, (int)n_new, keys.as<unsigned long long>(), vals.as<uint32_t>());
+        CLB_TRY(sort_pairs_u64(keys.as<uint64_t>(), keys2.as<uint64_t>(), vals.as<uint32_t>(), perm.as<uint32_t>(),
+                               (size_t)n_new_emb, st));
+        hipLaunchKernelGGL(permute_codes_kernel, dim3(blocks), dim3(256), 0, st, perm.as<uint32_t>(), codes_in.as<uint32_t>(),
+                           codes0_tail, n_new_emb);
+        const int pieces = (int)(rows / 16);
+        hipLaunchKernelGGL(permute_rows16_kernel, dim3((unsigned)((n_new_emb * pieces + 255) / 256)), dim3(256), 0, st,
+                           perm.as<uint32_t>(), reinterpret_cast<const uint4*>(res_src), reinterpret_cast<uint4*>(res_tail),
+                           n_new_emb, pieces);
+        CLB_HIP(hipGetLastError());
+        CLB_HIP(hipStreamSynchronize(st));          // the scratch above is freed here
+    } else if (n_new_emb > 0) {
+        CLB_HIP(hipMemcpyAsync(codes0_tail, codes_in.p, sizeof(uint32_t) * n_new_emb, hipMemcpyDeviceToDevice, st));
+        CLB_HIP(hipMemcpyAsync(res_tail, residuals, rows * n_new_emb, kind, st));
+    }
+
+    // the inverted lists: histogram and scan of the new codes, their (code, embedding)-stable order as local pids, one merge
+    DevBuf hist, add_off, ivf_off, ivf_pid, add_pid, add_pid_sorted, codes_sorted;
+    CLB_TRY(hist.alloc(sizeof(uint32_t) * (K + 1)));
+    CLB_TRY(add_off.alloc(sizeof(uint32_t) * (K + 1)));
+    CLB_TRY(ivf_off.alloc(sizeof(uint32_t) * (K + 1)));
+    CLB_TRY(ivf_pid.alloc(sizeof(uint32_t) * n_tot));
+    CLB_TRY(add_pid.alloc(sizeof(uint32_t) * n_new_emb));
+    CLB_TRY(add_pid_sorted.alloc(sizeof(uint32_t) * n_new_emb));
+    CLB_TRY(codes_sorted.alloc(sizeof(uint32_t) * n_new_emb));
+    CLB_HIP(hipMemsetAsync(hist.p, 0, sizeof(uint32_t) * (K + 1), st));
+    if (n_new_emb > 0)
+        hipLaunchKernelGGL(append_hist_pid_kernel, dim3(blocks), dim3(256), 0, st, codes_in.as<uint32_t>(),
+                           new_off_d.as<uint32_t>(), n_new_emb, (int)n_new, (uint32_t)d_old, hist.as<uint32_t>(),
+                           add_pid.as<uint32_t>());
+    CLB_TRY(exclusive_scan_u32(hist.as<uint32_t>(), add_off.as<uint32_t>(), (size_t)K, st));
+    int end_bit = 1;
+    while (((int64_t)1 << end_bit) < K) ++end_bit;
+    CLB_TRY(sort_pairs_u32(codes_in.as<uint32_t>(), codes_sorted.as<uint32_t>(), add_pid.as<uint32_t>(),
+                           add_pid_sorted.as<uint32_t>(), (size_t)n_new_emb, end_bit, st));
+    hipLaunchKernelGGL(append_offsets_kernel, dim3((unsigned)((K + 1 + 255) / 256)), dim3(256), 0, st, s->ivf_off.as<uint32_t>(),
+                       add_off.as<uint32_t>(), (int)(K + 1), ivf_off.as<uint32_t>());
+    if (n_tot > 0) {
+        const int64_t tiles = (n_tot + kMergeTile - 1) / kMergeTile;
+        hipLaunchKernelGGL(ivf_merge_kernel, dim3((unsigned)std::min<int64_t>(tiles, 8192)), dim3(256), 0, st,
+                           s->ivf_off.as<uint32_t>(), add_off.as<uint32_t>(), ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(),
+                           add_pid_sorted.as<uint32_t>(), (int)K, n_tot, ivf_pid.as<uint32_t>());
+    }
+    CLB_HIP(hipGetLastError());
+    std::vector<uint32_t> h_ivf_off((size_t)K + 1);
+    CLB_HIP(hipMemcpyAsync(h_ivf_off.data(), ivf_off.p, sizeof(uint32_t) * (K + 1), hipMemcpyDeviceToHost, st));
+    CLB_HIP(hipStreamSynchronize(st));
+    if ((int64_t)h_ivf_off[K] != n_tot) return fail(CLB_EHIP, "merged inverted lists hold %lld entries, expected %lld",
+                                                     (long long)h_ivf_off[K], (long long)n_tot);
+
+    // code | inv_norm words and bound constants: one streaming pass over the whole grown index -- inv_norm is quantised over
+    // the index's own range, which a new row may widen
+    IndexTables tables;
+    if (!s->generic) CLB_TRY(derive_index_tables(s, codes0.as<uint32_t>(), res.as<uint8_t>(), n_tot, &tables));
+    CLB_HIP(hipStreamSynchronize(st));
+    CLB_HIP(hipGetLastError());
+
+    // ---- nothing below can fail ----
+    swap_buf(s->codes0, codes0); swap_buf(s->residuals, res); swap_buf(s->doc_off, doc_off);
+    swap_buf(s->ivf_off, ivf_off); swap_buf(s->ivf_pid, ivf_pid);
+    s->n_docs = d_tot; s->n_emb = n_tot;
+    s->max_doclen = std::max(s->max_doclen, new_max_doclen);
+    s->ivf_len_sorted = sorted_list_lengths(h_ivf_off);
+    if (s->generic) s->index_bytes = resident_bytes(s);
+    else install_index_tables(s, tables, s->bounds_synced);
+    for (auto& w : s->ws) {       // sized for the old index: the next ensure_workspace sizes every buffer again
+        w.Bcap = 0;
+        w.filt_cap = 0;           // populations of filters that no longer fit the handle
+        w.bitmap.release();       // its rows had the old word count
+        w.pending.valid = false;
+    }
+    ++s->generation;
+    return CLB_OK;
+}
+
+int clb_searcher_append(clb_searcher* s, int64_t n_new, const int64_t* doclens, int64_t n_new_emb, const uint32_t* codes,
+                        const uint8_t* residuals) {
+    return searcher_append_impl(s, n_new, doclens, n_new_emb, codes, residuals, false);
+}
+int clb_searcher_append_device(clb_searcher* s, int64_t n_new, const int64_t* doclens, int64_t n_new_emb,
+                               const uint32_t* d_codes, const uint8_t* d_residuals, void* hip_stream) {
+    (void)hip_stream;     // the call waits for the whole device on entry, the work of that stream included
+    return searcher_append_impl(s, n_new, doclens, n_new_emb, d_codes, d_residuals, true);
+}
+// a count cannot carry an error code: a null handle gives -CLB_EARGUMENT and the message
+int64_t clb_searcher_generation(const clb_searcher* s) { return s ? s->generation : -(int64_t)fail(CLB_EARGUMENT, "null searcher"); }
+int64_t clb_searcher_num_docs(const clb_searcher* s) { return s ? s->n_docs : -(int64_t)fail(CLB_EARGUMENT, "null searcher"); }
+int64_t clb_searcher_num_embeddings(const clb_searcher* s) { return s ? s->n_emb : -(int64_t)fail(CLB_EARGUMENT, "null searcher"); }
 
 int64_t clb_searcher_device_bytes(const clb_searcher* s) {
     if (!s) return 0;
@@ -1488,7 +1699,14 @@ int clb_debug_scores(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe,
     for (int c = 0; c < Bd; ++c)
         CLB_HIP(hipMemcpyAsync(w.Qdev.as<float>() + (size_t)c * T * kDim, Q, sizeof(float) * T * kDim, hipMemcpyHostToDevice, st));
     const float* dQ = w.Qdev.as<float>();
-    CLB_TRY(run_retrieve(s, w, st, make_batch(dQ, Bd, T, nprobe, k)));     // no filter
+    {   // the fp16 score table pass 1 gathers from is only written in two-pass mode: on a handle set to the exact mode the
+        // hook would otherwise score against whatever an earlier query left in the slot (or nothing at all)
+        const int mode = s->mode;
+        s->mode = 1;
+        const int rc = run_retrieve(s, w, st, make_batch(dQ, Bd, T, nprobe, k));     // no filter
+        s->mode = mode;
+        CLB_TRY(rc);
+    }
     launch_pass1(s, w, st, dQ, dim3(8 * 32), Bd, (int)T);
     hipLaunchKernelGGL(select_margin_kernel, dim3(1), dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), dQ,
                        (int)T, (int)k, w.cand_cap, s->approx_consts, w.list.as<int>(), w.nlist.as<int>(),

@@ -211,6 +211,23 @@ class DeviceSearch:
         self.out_p = self.packed[:B * k * 8].view(torch.int64).view(B, k)
         self.out_s = self.packed[B * k * 8:B * k * 12].view(torch.float32).view(B, k)
         self.ncand = torch.zeros(B, dtype=torch.int64, device=self.dev)
+        # the searcher's generation (Searcher.generation) at construction, then at the latest `capture`: an append un-sizes
+        # the workspace slot and frees the index arrays a captured graph points into
+        self.generation = searcher.generation
+
+    def graph_is_stale(self) -> bool:
+        """True once the searcher has grown since the latest `capture`: that graph must not be replayed any more --
+        `capture` again (it runs the sizing pass first), or go through `replay`."""
+        return self.generation != self.s.generation
+
+    def replay(self, graph, Qstatic, filters=None, scope="candidates"):
+        """`graph.replay()` for a graph `capture` returned, made safe against appends: when the searcher has grown since
+        the capture, the sizing pass runs again and the search is captured anew before anything is replayed.  Returns the
+        graph that was replayed (keep it for the next call)."""
+        if self.graph_is_stale():
+            graph = self.capture(Qstatic, filters, scope)
+        graph.replay()
+        return graph
 
     def _check_queries(self, Qdev):
         """The C ABI takes a bare pointer: a tensor with fewer than B x T x dim contiguous floats on this device would
@@ -265,6 +282,7 @@ class DeviceSearch:
         `filters` / `scope` as in __call__: the graph holds the filters' device addresses -- keep them open while it is replayed."""
         import torch
         self._check_queries(Qstatic)
+        self.generation = self.s.generation
         cur = torch.cuda.current_stream(self.dev)
         side = torch.cuda.Stream(self.dev)
         side.wait_stream(cur)

@@ -68,6 +68,11 @@ class Searcher:
         self.config = config or ColBERTConfig(nbits=int(index["nbits"]), dim=int(index["dim"]))
         self.device = device
         self.encoder = encoder
+        self.index_path = index_path          # where add_*(..., persist=True) writes
+        self.pid_offset = int(pid_offset)
+        # what add_embeddings compresses with: the index's own centroids and cutoffs (references, not copies)
+        self._codec_src = (index["centroids"], index.get("bucket_cutoffs"))
+        self._codec = None
         self.dim = int(index["dim"]); self.nbits = int(index["nbits"])
         if hasattr(index["codes"], "data_ptr"):
             self._create_from_device_arrays(index, pid_offset)
@@ -121,6 +126,9 @@ class Searcher:
 
     # -- lifetime ---------------------------------------------------------------------------------
     def close(self):
+        if getattr(self, "_codec", None) is not None:
+            self._codec.close()
+            self._codec = None
         if getattr(self, "_h", None):
             lib().clb_searcher_destroy(self._h)
             self._h = None
@@ -130,6 +138,89 @@ class Searcher:
             self.close()
         except Exception:
             pass
+
+    # -- ingest: append passages to the resident index (clb_searcher_append) ---------------------------
+    @property
+    def generation(self) -> int:
+        """Number of appends that changed this searcher (0 after the constructor).  A HIP graph captured over the searcher,
+        and every PassageFilter, belongs to the generation it was made in."""
+        return int(lib().clb_searcher_generation(self._h))
+
+    def add_compressed(self, codes, residuals, doclens, persist: bool = False) -> range:
+        """Append passages compressed with the index's own codec behind the last passage, without rebuilding the resident
+        index; returns the range of their pids.  Layouts as in the constructor: numpy `codes` UInt32[n] (1-based) and
+        `residuals` (dim/8*nbits, n), or CUDA tensors `codes` 32-bit [n] and `residuals` uint8 (n, dim/8*nbits) on this
+        searcher's device (clb_searcher_append_device); `doclens` on the host.  Afterwards every search answers as a
+        Searcher made from the concatenated index would; filters made before must be made again.  If the call raises,
+        the searcher is unchanged.  `persist`: also write the passages to the index directory the searcher was opened
+        from (storage.append_chunk), after the device append has succeeded."""
+        if persist and self.index_path is None:
+            raise ColBERTError("persist=True needs a Searcher opened from an index_path")
+        rows = self.dim // 8 * self.nbits
+        dl = np.ascontiguousarray(np.asarray(doclens.cpu() if hasattr(doclens, "data_ptr") else doclens), dtype=np.int64)
+        first = self.pid_offset + self.num_docs + 1
+        if hasattr(codes, "data_ptr"):
+            import torch
+            if not (codes.is_cuda and residuals.is_cuda and codes.is_contiguous() and residuals.is_contiguous()
+                    and codes.device.index == self.device and residuals.device.index == self.device):
+                raise ColBERTError("device arrays must be contiguous CUDA tensors on the searcher's device")
+            if codes.element_size() != 4 or codes.dim() != 1 or residuals.dtype != torch.uint8:
+                raise ColBERTError("codes must be a 32-bit vector, residuals uint8")
+            if tuple(residuals.shape) != (codes.numel(), rows):
+                raise ColBERTError("residuals must be (n_emb, dim/8*nbits)")
+            st = torch.cuda.current_stream(codes.device).cuda_stream
+            check(lib().clb_searcher_append_device(self._h, i64(dl.size), fptr(dl), i64(codes.numel()),
+                                                   C.c_void_p(codes.data_ptr()), C.c_void_p(residuals.data_ptr()),
+                                                   C.c_void_p(st)))
+            if persist:
+                co = codes.cpu().numpy().view(np.uint32)
+                r = np.asfortranarray(residuals.cpu().numpy().T)
+        else:
+            co = np.ascontiguousarray(codes, dtype=np.uint32)
+            r = colmajor(residuals, np.uint8)
+            if co.ndim != 1 or r.shape != (rows, co.size):
+                raise ColBERTError("residuals must be (dim/8*nbits, n_emb)")
+            check(lib().clb_searcher_append(self._h, i64(dl.size), fptr(dl), i64(co.size), fptr(co), fptr(r)))
+        self.num_docs = int(lib().clb_searcher_num_docs(self._h))
+        self.num_embeddings = int(lib().clb_searcher_num_embeddings(self._h))
+        if persist and dl.size:
+            storage.append_chunk(self.index_path, co, r, dl)
+        return range(first, self.pid_offset + self.num_docs + 1)
+
+    def _index_codec(self):
+        """The index's own codec, resident (codec.Codec): built on first use from the centroids and bucket_cutoffs the
+        index dict or directory carries -- the codec stays fixed over appends."""
+        if self._codec is None:
+            from .codec import Codec
+            cent, cut = self._codec_src
+            if cut is None:
+                raise ColBERTError("this index carries no bucket_cutoffs: embeddings cannot be compressed with its codec "
+                                   "(pass an index with 'bucket_cutoffs', or use add_compressed)")
+            cut = np.asarray(cut.cpu() if hasattr(cut, "data_ptr") else cut, dtype=np.float32)
+            self._codec = Codec(cent, cut, self.dim, self.nbits, device=self.device)
+        return self._codec
+
+    def add_embeddings(self, embs, doclens, persist: bool = False) -> range:
+        """Compress passage embeddings with the index's own codec on the device (compress, residual.jl:586-604) and append
+        them: `embs` numpy (dim, n) or a CUDA tensor (n, dim) float32, `doclens` their passages' lengths.  -> the new pids."""
+        import torch
+        codec = self._index_codec()
+        if hasattr(embs, "data_ptr"):
+            x = embs
+        else:
+            e = colmajor(embs, np.float32)
+            if e.ndim != 2 or e.shape[0] != self.dim:
+                raise ColBERTError(f"embs must be (dim={self.dim}, n)")
+            x = torch.from_numpy(np.ascontiguousarray(e.T)).to(torch.device("cuda", self.device))
+        codes, res = codec.compress_device(x)
+        return self.add_compressed(codes, res, doclens, persist=persist)
+
+    def add_passages(self, texts, persist: bool = False) -> range:
+        """encode_passages (checkpoint.jl:159-189) with the attached encoder, then add_embeddings.  -> the new pids."""
+        if self.encoder is None:
+            raise ColBERTError("no encoder attached: pass encoder=... or use add_embeddings(embs, doclens)")
+        embs, doclens = self.encoder.encode_passages(list(texts))
+        return self.add_embeddings(embs, doclens, persist=persist)
 
     @property
     def device_bytes(self) -> int:
@@ -359,13 +450,24 @@ class TextSearch:
         self.d_err = torch.as_tensor(flag, device=self.dev)
         self.stream = torch.cuda.Stream(self.dev)
         self.graph = None
+        self.want_graph = bool(graph)
+        self._prepare()
+
+    def _prepare(self):
+        """Size the workspaces and (graph=True) capture the graph, for the searcher as it is now.  Run again whenever the
+        searcher's generation has moved: an append frees the arrays a captured graph points into and un-sizes the
+        workspaces, so the stale graph is dropped before anything is enqueued."""
+        import torch
+        self.graph = None
+        self.generation = self.s.generation
         # a first pass sizes every workspace (allocations cannot be captured)
-        self.d_ids.fill_(tok.lookup("[MASK]"))
+        self.d_ids.fill_(self.enc.tokenizer.lookup("[MASK]"))
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(self.stream):
             self._enqueue()
         self.stream.synchronize()
         self.enc.check_last_ids()
-        if graph:
+        if self.want_graph:
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph, stream=self.stream):
                 self._enqueue()
@@ -382,6 +484,8 @@ class TextSearch:
         ids, mask = tokenization.tensorize_queries(cfg.query_token, cfg.attend_to_mask_tokens, self.enc.tokenizer, [query], self.T)
         self.h_ids.numpy()[0, :] = ids[:, 0]
         self.h_mask.numpy()[0, :] = mask[:, 0]
+        if self.s.generation != self.generation:      # the searcher has grown since the capture
+            self._prepare()
         with torch.cuda.stream(self.stream):
             self.d_ids.copy_(self.h_ids, non_blocking=True)
             self.d_mask.copy_(self.h_mask, non_blocking=True)

@@ -70,6 +70,72 @@ def check_all_files_are_saved(index_path: str) -> bool:
     return all(os.path.isfile(os.path.join(index_path, f)) for f in files)
 
 
+def merge_ivf(ivf, ivf_lengths, n_old_emb: int, new_codes):
+    """The IVF of an index grown by `new_codes` (1-based centroid codes of the embeddings n_old_emb+1 ...): per centroid
+    the old list followed by the new embedding ids in their stable order -- what `_build_ivf` (collection_indexer.jl:
+    349-353) gives on the concatenated codes, because every new id exceeds every old one.  Pure numpy, no sort of the
+    old entries.  Returns (ivf, ivf_lengths)."""
+    ivf = np.asarray(ivf, dtype=np.int64); old_len = np.asarray(ivf_lengths, dtype=np.int64)
+    new_codes = np.asarray(new_codes).astype(np.int64)
+    K = old_len.size
+    if ivf.size != int(old_len.sum()):
+        raise ValueError("length(ivf) must be equal to sum(ivf_lengths)!")
+    if new_codes.size and (new_codes.min() < 1 or new_codes.max() > K):
+        raise ValueError("codes outside 1..num_partitions")
+    add_len = np.bincount(new_codes - 1, minlength=K).astype(np.int64)
+    add = np.argsort(new_codes, kind="stable").astype(np.int64) + int(n_old_emb) + 1
+    old_off = np.concatenate([[0], np.cumsum(old_len)]); add_off = np.concatenate([[0], np.cumsum(add_len)])
+    out = np.empty(ivf.size + add.size, dtype=np.int64)
+    # every old entry moves up by the new entries of the centroids before its own; every new one by the old entries up to its own
+    out[np.arange(ivf.size) + np.repeat(add_off[:-1], old_len)] = ivf
+    out[np.arange(add.size) + np.repeat(old_off[1:], add_len)] = add
+    return out, old_len + add_len
+
+
+def append_chunk(index_path: str, codes, residuals, doclens) -> None:
+    """Make appended passages (Searcher.add_compressed) part of the index directory: one more chunk behind the last.
+    Order of the writes: the chunk's files; the merged ivf / ivf_lengths under temporary names, renamed into place;
+    plan.json last (through a rename as well).  Until plan.json names the new chunk `load_index` and
+    `check_all_files_are_saved` read the directory as the old index -- `load_index` drops the inverted-list entries of
+    embeddings the plan does not know."""
+    plan = load_json(index_path, "plan.json")
+    codes = np.asarray(codes, dtype=np.uint32); doclens = np.asarray(doclens, dtype=np.int64)
+    residuals = np.asfortranarray(residuals, dtype=np.uint8)
+    if int(doclens.sum()) != codes.size or residuals.shape[1] != codes.size:
+        raise ValueError("sum(doclens), length(codes) and the residual columns must agree")
+    n_chunks = int(plan["num_chunks"])
+    old_codes = np.concatenate([_load(os.path.join(index_path, f"{i}.codes")) for i in range(1, n_chunks + 1)])
+    n_docs = sum(_load(os.path.join(index_path, f"doclens.{i}")).size for i in range(1, n_chunks + 1))
+    n_emb = int(old_codes.size)
+    new_ivf, new_lens = merge_ivf(*_read_ivf(index_path, old_codes), n_emb, codes)
+    chunk = n_chunks + 1
+    save_chunk(index_path, codes, residuals, chunk, n_docs + 1, doclens)
+    with open(os.path.join(index_path, f"{chunk}.metadata.json")) as f:
+        meta = json.load(f)
+    meta["embedding_offset"] = n_emb + 1                    # 1-based, like passage_offset (collection_indexer.jl:270-296)
+    save_json(index_path, f"{chunk}.metadata.json", meta)
+    for name, a in (("ivf", new_ivf), ("ivf_lengths", new_lens)):
+        _save(os.path.join(index_path, name + ".tmp"), a)
+        os.replace(os.path.join(index_path, name + ".tmp" + EXT), os.path.join(index_path, name + EXT))
+    plan["num_chunks"] = chunk
+    plan["num_embeddings"] = n_emb + int(codes.size)
+    if "embeddings_offsets" in plan:
+        plan["embeddings_offsets"] = [int(o) for o in plan["embeddings_offsets"]] + [n_emb + 1]
+    save_json(index_path, "plan.json.tmp", plan)
+    os.replace(os.path.join(index_path, "plan.json.tmp"), os.path.join(index_path, "plan.json"))
+
+
+def _read_ivf(index_path: str, codes):
+    """ivf / ivf_lengths of the directory for the embeddings `codes` (all chunks plan.json names).  A directory whose
+    append_chunk was interrupted holds merged lists beside a plan that does not name the new chunk yet: a merged list is
+    the old list followed by larger ids, so dropping the ids past len(codes) gives the old lists back exactly."""
+    ivf, ivf_lengths = _load(os.path.join(index_path, "ivf")), _load(os.path.join(index_path, "ivf_lengths"))
+    if ivf.size > codes.size:
+        ivf = ivf[ivf <= codes.size]
+        ivf_lengths = np.bincount(codes.astype(np.int64) - 1, minlength=ivf_lengths.size).astype(ivf_lengths.dtype)
+    return ivf, ivf_lengths
+
+
 def load_index(index_path: str) -> dict:
     """load_codec / load_doclens / load_compressed_embs (loaders.jl:10-38, 76-113) + ivf files."""
     plan = load_json(index_path, "plan.json")
@@ -79,11 +145,12 @@ def load_index(index_path: str) -> dict:
         codes.append(_load(os.path.join(index_path, f"{i}.codes")))
         res.append(_load(os.path.join(index_path, f"{i}.residuals")))
         dl.append(_load(os.path.join(index_path, f"doclens.{i}")))
+    codes = np.concatenate(codes)
+    ivf, ivf_lengths = _read_ivf(index_path, codes)
     return {"dim": cfg["dim"], "nbits": cfg["nbits"],
             "centroids": _load(os.path.join(index_path, "centroids")),
             "bucket_cutoffs": _load(os.path.join(index_path, "bucket_cutoffs")),
             "bucket_weights": _load(os.path.join(index_path, "bucket_weights")),
             "avg_residual": np.float32(_load(os.path.join(index_path, "avg_residual"))),
-            "codes": np.concatenate(codes), "residuals": np.asfortranarray(np.concatenate(res, axis=1)),
-            "doclens": np.concatenate(dl), "ivf": _load(os.path.join(index_path, "ivf")),
-            "ivf_lengths": _load(os.path.join(index_path, "ivf_lengths"))}
+            "codes": codes, "residuals": np.asfortranarray(np.concatenate(res, axis=1)),
+            "doclens": np.concatenate(dl), "ivf": ivf, "ivf_lengths": ivf_lengths}

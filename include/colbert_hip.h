@@ -14,6 +14,8 @@
  * retains a host pointer.  All device memory belongs to the library (handles are opaque).
  * Threading: every call is synchronous (results are in the output buffers on return) except the
  * *_device entry points, which enqueue on the given HIP stream.  One handle, one thread at a time.
+ * clb_searcher_append / clb_searcher_append_device replace the handle's device arrays: they wait for the whole device on
+ * entry and before the swap, and the caller must have no search of that handle in flight on another thread.
  * Errors: every function returns 0 or a CLB_E* code; codes 1..4 map 1:1 onto the Julia exception the
  * reference throws in the same situation.  clb_last_error() returns a message for the calling thread.
  * There is NO CPU fallback: without a GPU every compute entry point fails with CLB_EHIP.
@@ -71,6 +73,38 @@ int clb_searcher_create_device(int device, int64_t dim, int nbits, int64_t K, co
                                const uint32_t* d_codes, const uint8_t* d_residuals, const int64_t* d_ivf,
                                const int64_t* ivf_lengths, int64_t pid_offset, clb_searcher** out);
 int clb_searcher_destroy(clb_searcher* s);
+/* Append passages to the resident index (no counterpart in the reference, whose index is built once; upstream ColBERT's
+ * IndexUpdater.add with a fixed codec).  The n_new passages come after the handle's last passage: they become local passages
+ * n_docs+1 .. n_docs+n_new (returned pids: pid_offset + those).  codes: UInt32[n_new_emb], 1-based; residuals:
+ * (dim/8*nbits, n_new_emb); doclens: Int64[n_new] -- what compress() with the index's own centroids and cutoffs gives.
+ * Afterwards every entry point behaves bit for bit as on a handle made by clb_searcher_create from the concatenated arrays
+ * with ivf = stable sortperm(all codes) (_build_ivf, collection_indexer.jl:349-353): every new embedding id exceeds every old
+ * one, so a centroid's merged list is its old list followed by its new entries in embedding order.  Bound constants that
+ * were set or synced (clb_searcher_set_bound_consts) are never lowered: the handle keeps the element-wise maximum of the old
+ * values and the grown index's own; sync a shard group again after an append.  What create derives from the index is derived
+ * again -- pass 1's gather form returns to the choice by the grown index's code statistics (clb_searcher_set_pass1_gather
+ * to force one again); the mode and the other settings of the handle are kept.
+ * Failure leaves the handle unchanged and searchable: CLB_EDIMENSION sum(doclens) != n_new_emb; CLB_EARGUMENT a negative
+ * doclen or a null pointer; CLB_EDOMAIN a code outside 1..K (checked on the device, as create does); CLB_EUNSUPPORTED the
+ * totals exceed create's 2^32-1 embeddings / 2^31-1 passages; CLB_ENOMEM.  n_new = 0 is CLB_OK and changes nothing.
+ * Memory: the grown arrays are built beside the old ones and swapped in at the end, so the call transiently holds about
+ * the old index plus the new index (and the sort scratch of the new rows).
+ * Threading: the call waits for the whole device on entry and again before the swap; the caller must have no search of
+ * this handle in flight on another thread.  All four workspace slots are sized again by the next search, a pending
+ * clb_search_shard_phase1 is dropped, a HIP graph captured over this handle holds freed addresses and must be captured again
+ * (compare clb_searcher_generation), and a clb_filter made before the append is refused (CLB_EARGUMENT): make another. */
+int clb_searcher_append(clb_searcher* s, int64_t n_new, const int64_t* doclens, int64_t n_new_emb, const uint32_t* codes,
+                        const uint8_t* residuals);
+/* The same with d_codes / d_residuals on the searcher's device (what clb_codec_compress_device wrote; neither is written);
+ * doclens on the host.  hip_stream names the stream that produced them: its work, like all work of the device, is waited
+ * for on entry, and the call returns with the append complete. */
+int clb_searcher_append_device(clb_searcher* s, int64_t n_new, const int64_t* doclens, int64_t n_new_emb,
+                               const uint32_t* d_codes, const uint8_t* d_residuals, void* hip_stream);
+/* Number of appends that changed the handle (0 after create), its passages and its embeddings.  These return counts, not
+ * CLB_* codes: a null handle gives -CLB_EARGUMENT (and the message in clb_last_error). */
+int64_t clb_searcher_generation(const clb_searcher* s);
+int64_t clb_searcher_num_docs(const clb_searcher* s);
+int64_t clb_searcher_num_embeddings(const clb_searcher* s);
 /* bytes of HBM held by the handle (index + workspace) */
 int64_t clb_searcher_device_bytes(const clb_searcher* s);
 
@@ -217,7 +251,8 @@ int clb_retrieve(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe, int
 
 /* Test hook for the two-pass mode: for one query returns every candidate pid with its approximate (pass 1) and
  * exact score, the selection threshold tau (k-th largest approximate score), the proven error bound eps and the
- * number of candidates with approx >= tau - 2 eps (those the exact pass re-scores). */
+ * number of candidates with approx >= tau - 2 eps (those the exact pass re-scores).  The report is that of the two-pass
+ * pipeline whatever clb_searcher_set_mode says (the handle's mode is left as it was). */
 int clb_debug_scores(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe, int64_t k, int64_t cap,
                      int64_t* out_pids, float* out_approx, float* out_exact, int64_t* n_out, float* tau,
                      float* eps, int64_t* n_rescore);

@@ -18,7 +18,7 @@ using Logging
 using Random
 using Unicode
 
-export ColBERTConfig, Indexer, index, Searcher, search, PassageFilter
+export ColBERTConfig, Indexer, index, Searcher, search, PassageFilter, add_compressed!
 
 include("config.jl")
 include("capi.jl")

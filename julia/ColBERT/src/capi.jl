@@ -30,6 +30,19 @@ function _searcher_create(nbits::Int, centroids::Matrix{Float32}, bucket_weights
     h[]
 end
 _searcher_destroy(h::Ptr{Cvoid}) = ccall((:clb_searcher_destroy, libcolbert), Cint, (Ptr{Cvoid},), h)
+"append compressed passages behind the handle's last passage (clb_searcher_append): the handle is unchanged when this throws"
+function _searcher_append(h::Ptr{Cvoid}, doclens::Vector{Int}, codes::Vector{UInt32}, residuals::Matrix{UInt8})
+    GC.@preserve doclens codes residuals begin
+        _check(ccall((:clb_searcher_append, libcolbert), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{UInt32}, Ptr{UInt8}),
+            h, length(doclens), doclens, length(codes), codes, residuals))
+    end
+    nothing
+end
+"appends that changed the handle (0 after create) / its passages / its embeddings"
+_searcher_generation(h::Ptr{Cvoid}) = Int(ccall((:clb_searcher_generation, libcolbert), Int64, (Ptr{Cvoid},), h))
+_searcher_num_docs(h::Ptr{Cvoid}) = Int(ccall((:clb_searcher_num_docs, libcolbert), Int64, (Ptr{Cvoid},), h))
+_searcher_num_embeddings(h::Ptr{Cvoid}) = Int(ccall((:clb_searcher_num_embeddings, libcolbert), Int64, (Ptr{Cvoid},), h))
 "selection step by one (0) or sixteen (1) work-groups per query; -1 (default): chosen by the candidate capacity"
 _searcher_set_wide_select(h::Ptr{Cvoid}, on::Integer) =
     _check(ccall((:clb_searcher_set_wide_select, libcolbert), Cint, (Ptr{Cvoid}, Cint), h, on))

@@ -36,6 +36,26 @@ function Searcher(index_path::String; device::Int = 0)
 end
 
 """
+    add_compressed!(searcher, codes, residuals, doclens) -> UnitRange{Int}
+
+Append passages that were compressed with the index's own codec (`compress` with its centroids and bucket cutoffs) behind
+the searcher's last passage, without rebuilding the resident index; returns their pids.  Afterwards `search` answers as a
+`Searcher` opened on the concatenated index would.  A `PassageFilter` made before the call is refused by `search`: make
+another.  On an exception the searcher is unchanged.  No counterpart in the reference (upstream ColBERT: IndexUpdater.add).
+"""
+function add_compressed!(searcher::Searcher, codes::Vector{UInt32}, residuals::Matrix{UInt8}, doclens::Vector{Int})
+    size(residuals, 2) == length(codes) ||
+        throw(DimensionMismatch("residuals must have one column per code ($(length(codes))), got $(size(residuals, 2))"))
+    first_pid = searcher.num_documents + 1
+    _searcher_append(searcher.handle, doclens, codes, residuals)
+    searcher.num_documents = _searcher_num_docs(searcher.handle)
+    first_pid:searcher.num_documents
+end
+"number of `add_compressed!` calls that changed the searcher"
+generation(searcher::Searcher) = _searcher_generation(searcher.handle)
+num_embeddings(searcher::Searcher) = _searcher_num_embeddings(searcher.handle)
+
+"""
     search(searcher, query::String, k::Int; filter = nothing, scope = :candidates) -> (pids::Vector{Int}, scores::Vector{Float32})
 
 Same contract as src/searching.jl:93-128: 1-based pids by descending score, ties by ascending pid; a BoundsError if
