@@ -5,6 +5,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <numeric>
 
 #include "append_kernels.hpp"
@@ -194,6 +195,16 @@ inline int64_t padded_nprobe(int64_t nprobe) { return nprobe <= 2 ? 2 : nprobe <
 // (round 6: only when asked for -- measured end to end the format loses on all four workloads, profiles/r06_experiments.md)
 inline bool cell8_rows(const clb_searcher* s) { return s->cell8 == 1 && s->approx_ok; }
 
+// the score table of this handle's batches of 16+ queries from ONE fp16 product (clb_searcher::s1_x1)?
+inline bool single_product_table(const clb_searcher* s) {
+    return (s->s1_x1 == 1 || (s->s1_x1 < 0 && s->bounds_synced)) && s->cent_f16.p && s->dc_f16 > 0.f;
+}
+
+// Pass 1's gather form by the index's own code statistics (derive_index_tables): LDS-DMA when neighbouring embeddings
+// seldom share a line of the score table -- and only when the query's score table (64 B per centroid) does not fit the
+// 4-MB L2 of an XCD: with a resident table the two forms are equal within 2 % (built index, K = 32 768: 0.663 / 0.668 ms)
+inline int default_gather_lds(const clb_searcher* s) { return s->code_adjacency < 0.2 && s->K * 64 > ((int64_t)4 << 20); }
+
 // the top-k kernel sorts up to kMaxTopK 8-byte keys in LDS: beyond 64 KB the attribute has to be raised
 void allow_large_topk_lds() {
     allow_dynamic_lds(reinterpret_cast<const void*>(topk_kernel), (int)(sizeof(unsigned long long) * kMaxTopK));
@@ -352,7 +363,7 @@ int run_retrieve(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) 
         const bool teams = mq && want_half && B >= kTeamQueries;
         const int team_groups = (B + kTeamQueries - 1) / kTeamQueries;
         if (teams) gx = std::max(1, std::min(n_tiles, std::min(256, std::max(256 / team_groups, 16))));
-        const bool x1 = teams && (s->s1_x1 == 1 || (s->s1_x1 < 0 && s->bounds_synced)) && s->cent_f16.p && s->dc_f16 > 0.f;
+        const bool x1 = teams && single_product_table(s);
         w.x1_table = x1;
         w.cell8 = teams && cell8_rows(s);
         w.have_range = w.cell8;
@@ -868,7 +879,109 @@ int for_sub_batches(clb_searcher* s, Workspace& w, int64_t T, int64_t B, int64_t
     return CLB_OK;
 }
 
-// ---- what a handle derives from its resident index: clb_searcher_create and clb_searcher_append both end here ----------
+// ---- shared by clb_searcher_create and clb_searcher_append: the steps that check, order and write a batch of rows, and
+// the tables a handle derives from its resident index --------------------------------------------------------------------
+
+using FilterPtr = std::unique_ptr<clb_filter, decltype(&clb_filter_destroy)>;
+
+int check_shard_limits(int64_t n_emb, int64_t n_docs) {
+    if (n_emb >= (int64_t)0xffffffffll || n_docs >= (int64_t)0x7fffffffll)
+        return fail(CLB_EUNSUPPORTED, "a shard holds at most 2^32-1 embeddings / 2^31-1 passages");
+    return CLB_OK;
+}
+
+struct Offsets {
+    std::vector<uint32_t> off;      // off[i] = lens[0] + ... + lens[i - 1], i = 0 .. n
+    int64_t total = 0, longest = 0;
+};
+// -> the position of the first negative length, or -1
+int64_t running_offsets(const int64_t* lens, int64_t n, Offsets* o) {
+    o->off.resize((size_t)n + 1);
+    for (int64_t i = 0; i < n; ++i) {
+        if (lens[i] < 0) return i;
+        o->off[i] = (uint32_t)o->total;
+        o->total += lens[i];
+        o->longest = std::max(o->longest, lens[i]);
+    }
+    o->off[n] = (uint32_t)o->total;
+    return -1;
+}
+// the offsets of n passages among their own n_emb embeddings (the reference's DimensionMismatch in _cids_to_eids!,
+// ranking.jl:9-12); noun: what the message calls a passage of this batch
+int passage_offsets(const int64_t* doclens, int64_t n, int64_t n_emb, const char* noun, Offsets* o) {
+    const int64_t bad = running_offsets(doclens, n, o);
+    if (bad >= 0) return fail(CLB_EARGUMENT, "negative doclen at %s %lld", noun, (long long)(bad + 1));
+    if (o->total != n_emb)
+        return fail(CLB_EDIMENSION, "sum(doclens)=%lld must equal the number of embeddings %lld", (long long)o->total, (long long)n_emb);
+    return CLB_OK;
+}
+
+// One word that kernels report through (an error mask, a count): zeroed on the stream, read into `value` once the stream is done
+template <class T>
+struct DevWord {
+    DevBuf buf;
+    T value{};
+    T* ptr() const { return buf.as<T>(); }
+    int init(hipStream_t st) {
+        CLB_TRY(buf.alloc(sizeof(T)));
+        CLB_HIP(hipMemsetAsync(buf.p, 0, sizeof(T), st));
+        return CLB_OK;
+    }
+    int read(hipStream_t st) {
+        CLB_HIP(hipMemcpyAsync(&value, buf.p, sizeof(T), hipMemcpyDeviceToHost, st));
+        CLB_HIP(hipStreamSynchronize(st));
+        CLB_HIP(hipGetLastError());
+        return CLB_OK;
+    }
+};
+// the bits of an ingest's error word (ivf_to_pid_kernel, codes_to_zero_based_kernel, ivf_lists_sorted_kernel)
+enum { kErrIvfId = 1, kErrCode = 2, kErrUnsortedList = 4 };
+
+// the caller's 1-based codes as 0-based words in `dst`, a buffer of the library's (the caller's array is never written);
+// a code outside 1..K raises kErrCode in *err (decompress's DomainError, residual.jl:766-768)
+int stage_codes(hipStream_t st, const uint32_t* codes, hipMemcpyKind kind, int64_t n, int64_t K, uint32_t* dst, int* err) {
+    if (n == 0) return CLB_OK;
+    CLB_HIP(hipMemcpyAsync(dst, codes, sizeof(uint32_t) * n, kind, st));
+    hipLaunchKernelGGL(codes_to_zero_based_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dst, n, (uint32_t)K, err);
+    return CLB_OK;
+}
+int bad_codes() { return fail(CLB_EDOMAIN, "All the codes must be in the valid range of centroid IDs!"); }
+
+// codes and residual rows of n embeddings, padded by one step of zero rows (dummy steps read embeddings 0 .. kStepRows-1
+// even of a tiny index); rows 0 .. n - 1 are the caller's to write
+int alloc_padded_rows(hipStream_t st, int64_t n, size_t row_bytes, DevBuf* codes, DevBuf* res) {
+    CLB_TRY(codes->alloc(sizeof(uint32_t) * (n + kStepRows)));
+    CLB_TRY(res->alloc(row_bytes * (n + kStepRows)));
+    CLB_HIP(hipMemsetAsync(codes->as<uint32_t>() + n, 0, sizeof(uint32_t) * kStepRows, st));
+    CLB_HIP(hipMemsetAsync(res->as<uint8_t>() + row_bytes * n, 0, row_bytes * kStepRows, st));
+    return CLB_OK;
+}
+
+// Order every passage's embeddings by centroid code (results cannot change: MaxSim maximises over a passage's embeddings;
+// row masks, headers and the IVF are positional or per passage).  Equal and neighbouring codes then sit in adjacent lanes
+// of a pass-1 step: their 64-byte score rows coalesce into fewer, larger requests.
+// The n_emb > 0 source rows (0-based codes; residual rows of row_bytes, a multiple of 16, 16-byte aligned) belong to n_docs
+// passages at offsets_dev (n_docs + 1 offsets among these rows); all n_emb rows of codes_dst / res_dst are written.
+// Padding is the caller's.  Waits for the stream: the scratch is gone on return.
+int order_rows_by_code(hipStream_t st, const uint32_t* codes_src, const uint32_t* offsets_dev, int64_t n_emb, int64_t n_docs,
+                       const uint8_t* res_src, size_t row_bytes, uint32_t* codes_dst, uint8_t* res_dst) {
+    DevBuf keys, keys2, vals, perm;
+    CLB_TRY(keys.alloc(sizeof(uint64_t) * n_emb));
+    CLB_TRY(keys2.alloc(sizeof(uint64_t) * n_emb));
+    CLB_TRY(vals.alloc(sizeof(uint32_t) * n_emb));
+    CLB_TRY(perm.alloc(sizeof(uint32_t) * n_emb));
+    const dim3 blocks((unsigned)((n_emb + 255) / 256));
+    hipLaunchKernelGGL(passage_code_keys_kernel, blocks, dim3(256), 0, st, codes_src, offsets_dev, n_emb, (int)n_docs,
+                       keys.as<unsigned long long>(), vals.as<uint32_t>());
+    CLB_TRY(sort_pairs_u64(keys.as<uint64_t>(), keys2.as<uint64_t>(), vals.as<uint32_t>(), perm.as<uint32_t>(), (size_t)n_emb, st));
+    hipLaunchKernelGGL(permute_codes_kernel, blocks, dim3(256), 0, st, perm.as<uint32_t>(), codes_src, codes_dst, n_emb);
+    const int pieces = (int)(row_bytes / 16);
+    hipLaunchKernelGGL(permute_rows16_kernel, dim3((unsigned)((n_emb * pieces + 255) / 256)), dim3(256), 0, st, perm.as<uint32_t>(),
+                       reinterpret_cast<const uint4*>(res_src), reinterpret_cast<uint4*>(res_dst), n_emb, pieces);
+    CLB_HIP(hipGetLastError());
+    CLB_HIP(hipStreamSynchronize(st));
+    return CLB_OK;
+}
 
 // the list lengths, descending, from the host copy of ivf_off (K + 1 entries): the candidate-capacity bound
 std::vector<uint32_t> sorted_list_lengths(const std::vector<uint32_t>& ivf_off) {
@@ -897,22 +1010,17 @@ int derive_index_tables(const clb_searcher* s, const uint32_t* codes0, const uin
         // a 128-byte line of the score table (id-adjacent codes: the L1 merges those requests of the per-lane VGPR
         // gather) the VGPR form is faster (1 M topical passages: 0.67 against 0.76 ms per batch); when they do not
         // (uniform codes, a k-means-built index) the LDS-DMA form is (uniform: 1.47 against 1.61 ms)
-        DevBuf cnt;
-        CLB_TRY(cnt.alloc(sizeof(unsigned long long)));
-        unsigned long long adj = 0;
+        DevWord<unsigned long long> adj;
         const int64_t n_sample = std::min<int64_t>(n_emb, (int64_t)1 << 24);
-        if (hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), s->stream) != hipSuccess) return fail(CLB_EHIP, "memset failed");
+        CLB_TRY(adj.init(s->stream));
         if (n_sample > 1)
-            hipLaunchKernelGGL(code_adjacency_kernel, dim3(1024), dim3(256), 0, s->stream, codes0, n_sample,
-                               cnt.as<unsigned long long>());
-        if (hipMemcpyAsync(&adj, cnt.p, sizeof adj, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-            hipStreamSynchronize(s->stream) != hipSuccess)
-            return fail(CLB_EHIP, "code statistics failed");
-        t->code_adjacency = n_sample > 1 ? (double)adj / (double)(n_sample - 1) : 0.0;
+            hipLaunchKernelGGL(code_adjacency_kernel, dim3(1024), dim3(256), 0, s->stream, codes0, n_sample, adj.ptr());
+        CLB_TRY(adj.read(s->stream));
+        t->code_adjacency = n_sample > 1 ? (double)adj.value / (double)(n_sample - 1) : 0.0;
     }
     if (s->approx_ok) {
         CLB_TRY(t->codeinv.alloc(sizeof(uint32_t) * (n_emb + kStepRows)));
-        if (hipMemsetAsync(t->codeinv.p, 0, t->codeinv.bytes, s->stream) != hipSuccess) return fail(CLB_EHIP, "memset failed");
+        CLB_HIP(hipMemsetAsync(t->codeinv.p, 0, t->codeinv.bytes, s->stream));
     }
     return build_approx_tables(s->stream, s->centroids.as<float>(), s->weights.as<float>(), codes0, residuals, n_emb, (int)s->K,
                                s->approx_ok ? t->codeinv.as<uint32_t>() : nullptr, s->cbits, 1 << s->nbits, &t->consts,
@@ -921,26 +1029,30 @@ int derive_index_tables(const clb_searcher* s, const uint32_t* codes0, const uin
 
 inline void swap_buf(DevBuf& a, DevBuf& b) { std::swap(a.p, b.p); std::swap(a.bytes, b.bytes); }
 
+// the six constants of the error bound that shards share, in the order of the C ABI (clb_searcher_get_bound_consts);
+// dc_max travels beside them (clb_searcher::dc_f16)
+constexpr float ApproxConsts::* kBoundConsts[6] = {&ApproxConsts::cn_max, &ApproxConsts::rn_max, &ApproxConsts::inv_max,
+                                                   &ApproxConsts::rb_max, &ApproxConsts::dw_rn,  &ApproxConsts::inv_qerr};
+void bound_consts_to_abi(const ApproxConsts& a, float* c) { for (int i = 0; i < 6; ++i) c[i] = a.*kBoundConsts[i]; }
+// element-wise maximum: a shard group's bound is never lowered
+void raise_bound_consts(ApproxConsts& a, const float* c) {
+    for (int i = 0; i < 6; ++i) a.*kBoundConsts[i] = std::max(a.*kBoundConsts[i], c[i]);
+}
+
 // keep_max: the handle's bound constants are a shard group's (bounds_synced) -- like `set`, an append never lowers one
 void install_index_tables(clb_searcher* s, IndexTables& t, bool keep_max = false) {
     s->code_adjacency = t.code_adjacency;
-    // ... and only pays when the query's score table (64 B per centroid) does not fit the 4-MB L2 of an XCD: with a
-    // resident table the two forms are equal within 2 % (built index, K = 32 768: 0.663 / 0.668 ms)
-    s->gather_lds = s->code_adjacency < 0.2 && (int64_t)s->K * 64 > ((int64_t)4 << 20);
+    s->gather_lds = default_gather_lds(s);
     swap_buf(s->codeinv, t.codeinv);
     s->inv_lo = t.inv_lo; s->inv_step = t.inv_step;
-    const ApproxConsts old = s->approx_consts;
+    float old[6];
+    bound_consts_to_abi(s->approx_consts, old);
     s->approx_consts = t.consts;
     // the fp16 side's error lives beside the consts: a table made by the three-product kernels (fewer than 16 queries) keeps
     // the tighter bound.  Infinite (a centroid component beyond the fp16 range): the single-product kernel is never chosen.
     s->dc_f16 = std::isfinite(s->approx_consts.dc_max) ? s->approx_consts.dc_max : 0.f;
     s->approx_consts.dc_max = 0.f;
-    if (keep_max) {
-        ApproxConsts& a = s->approx_consts;
-        a.cn_max = std::max(a.cn_max, old.cn_max); a.rn_max = std::max(a.rn_max, old.rn_max);
-        a.inv_max = std::max(a.inv_max, old.inv_max); a.rb_max = std::max(a.rb_max, old.rb_max);
-        a.dw_rn = std::max(a.dw_rn, old.dw_rn); a.inv_qerr = std::max(a.inv_qerr, old.inv_qerr);
-    }
+    if (keep_max) raise_bound_consts(s->approx_consts, old);
     s->index_bytes = resident_bytes(s);
 }
 
@@ -957,11 +1069,96 @@ int clb_device_count(void) {
 }
 
 // `big_on_device`: centroids, codes, residuals and ivf are device pointers on `device` (an index that was built there:
-// clb_codec_compress_device / clb_build_ivf_device); the per-passage and per-centroid lengths are host arrays either way
+// clb_codec_compress_device / clb_build_ivf_device); the per-passage and per-centroid lengths are host arrays either way.
+// The handle is owned until the last step has succeeded: any failure frees everything and leaves *out null.
 static int searcher_create_impl(int device, int64_t dim, int nbits, int64_t K, const float* centroids,
                                 const float* bucket_weights, int64_t n_docs, const int64_t* doclens, int64_t n_emb,
                                 const uint32_t* codes, const uint8_t* residuals, const int64_t* ivf,
-                                const int64_t* ivf_lengths, int64_t pid_offset, bool big_on_device, clb_searcher** out);
+                                const int64_t* ivf_lengths, int64_t pid_offset, bool big_on_device, clb_searcher** out) {
+    const hipMemcpyKind big_kind = big_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (!out) return fail(CLB_EARGUMENT, "out is null");
+    *out = nullptr;
+    if (dim < 8 || dim % 8 != 0) return fail(CLB_EDOMAIN, "dim should be a multiple of 8!");          // residual.jl:763-768
+    if (nbits != 1 && nbits != 2 && nbits != 4 && nbits != 8)
+        return fail(CLB_EUNSUPPORTED, "the HIP codec supports nbits in {1,2,4,8} (got %d)", nbits);
+    if (K < 1 || n_docs < 0 || n_emb < 0) return fail(CLB_EARGUMENT, "negative or empty sizes");
+    CLB_TRY(check_shard_limits(n_emb, n_docs));
+    Offsets docs, lists;
+    CLB_TRY(passage_offsets(doclens, n_docs, n_emb, "passage", &docs));
+    if (running_offsets(ivf_lengths, K, &lists) >= 0) return fail(CLB_EARGUMENT, "negative ivf length");
+    if (lists.total != n_emb) return fail(CLB_EDIMENSION, "length(ivf) must be equal to sum(ivf_lengths)!");
+    CLB_TRY(use_device(device));
+
+    static std::atomic<uint64_t> next_serial{1};
+    std::unique_ptr<clb_searcher, decltype(&clb_searcher_destroy)> owned(new clb_searcher(), clb_searcher_destroy);
+    clb_searcher* s = owned.get();
+    s->serial = next_serial.fetch_add(1);
+    s->device = device; s->dim = dim; s->nbits = nbits; s->K = K; s->n_docs = n_docs; s->n_emb = n_emb;
+    s->pid_offset = pid_offset;
+    s->generic = !(dim == kDim && nbits <= 4);     // the tuned kernels are built for dim 128, nbits 1/2/4
+    s->max_doclen = docs.longest;
+    CLB_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    const hipStream_t st = s->stream;
+    s->ivf_len_sorted = sorted_list_lengths(lists.off);
+
+    const size_t rows = (size_t)(dim / 8 * nbits);
+    CLB_TRY(s->centroids.alloc(sizeof(float) * dim * K));
+    CLB_HIP(hipMemcpyAsync(s->centroids.p, centroids, sizeof(float) * dim * K, big_kind, st));
+    CLB_TRY(upload(s->weights, bucket_weights, sizeof(float) * ((size_t)1 << nbits), st));
+    CLB_TRY(alloc_padded_rows(st, n_emb, rows, &s->codes0, &s->residuals));
+    CLB_HIP(hipMemcpyAsync(s->residuals.p, residuals, rows * n_emb, big_kind, st));
+    CLB_TRY(upload(s->doc_off, docs.off.data(), sizeof(uint32_t) * docs.off.size(), st));
+    CLB_TRY(upload(s->ivf_off, lists.off.data(), sizeof(uint32_t) * lists.off.size(), st));
+    CLB_TRY(s->ivf_pid.alloc(sizeof(uint32_t) * n_emb));
+    DevBuf ivf_raw;
+    DevWord<int> err;       // the three device checks share one word and one read-back
+    CLB_TRY(ivf_raw.alloc(sizeof(int64_t) * n_emb));
+    CLB_TRY(err.init(st));
+    CLB_TRY(stage_codes(st, codes, big_kind, n_emb, K, s->codes0.as<uint32_t>(), err.ptr()));
+    if (n_emb > 0) {
+        CLB_HIP(hipMemcpyAsync(ivf_raw.p, ivf, sizeof(int64_t) * n_emb, big_kind, st));
+        hipLaunchKernelGGL(ivf_to_pid_kernel, dim3((unsigned)((n_emb + 255) / 256)), dim3(256), 0, st, ivf_raw.as<int64_t>(),
+                           s->doc_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), n_emb, (int)n_docs, err.ptr());
+        hipLaunchKernelGGL(ivf_lists_sorted_kernel, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, st,
+                           s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), (int)K, err.ptr());
+    }
+    CLB_TRY(err.read(st));
+    if (err.value & kErrIvfId) return fail(CLB_EBOUNDS, "ivf holds embedding ids outside 1..n_emb");
+    if (err.value & kErrCode) return bad_codes();
+    s->ivf_sorted = !(err.value & kErrUnsortedList);
+
+    if (s->generic) {       // the general-shape path keeps the caller's row order and needs no tables
+        s->index_bytes = resident_bytes(s);
+        *out = owned.release();
+        return CLB_OK;
+    }
+    if (n_emb > 0) {
+        DevBuf codes_new, res_new;
+        CLB_TRY(alloc_padded_rows(st, n_emb, rows, &codes_new, &res_new));
+        CLB_TRY(order_rows_by_code(st, s->codes0.as<uint32_t>(), s->doc_off.as<uint32_t>(), n_emb, n_docs,
+                                   s->residuals.as<uint8_t>(), rows, codes_new.as<uint32_t>(), res_new.as<uint8_t>()));
+        swap_buf(s->codes0, codes_new); swap_buf(s->residuals, res_new);
+    }
+    // bf16 hi/lo split of the centroids for the bf16x3 centroid scoring, and their fp16 image
+    const int64_t nel = dim * K;
+    CLB_TRY(s->cent_hi.alloc(sizeof(uint16_t) * nel));
+    CLB_TRY(s->cent_lo.alloc(sizeof(uint16_t) * nel));
+    CLB_TRY(s->cent_f16.alloc(sizeof(uint16_t) * nel));
+    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st,
+                       s->centroids.as<float>(), s->cent_hi.as<uint16_t>(), s->cent_lo.as<uint16_t>(), nel);
+    hipLaunchKernelGGL(to_f16_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st,
+                       s->centroids.as<float>(), s->cent_f16.as<uint16_t>(), nel);
+    s->cbits = 1;
+    while (((int64_t)1 << s->cbits) < K) ++s->cbits;
+    // the packed word leaves 32 - cbits bits for inv_norm: at least 12 (K <= 2^20), otherwise exact mode only
+    s->approx_ok = approx_supported((int)dim, nbits) && s->cbits <= 20;
+    IndexTables tables;
+    CLB_TRY(derive_index_tables(s, s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(), n_emb, &tables));
+    install_index_tables(s, tables);
+    s->mode = s->approx_ok ? 1 : 0;
+    *out = owned.release();
+    return CLB_OK;
+}
 
 int clb_searcher_create(int device, int64_t dim, int nbits, int64_t K, const float* centroids,
                         const float* bucket_weights, int64_t n_docs, const int64_t* doclens, int64_t n_emb,
@@ -977,150 +1174,6 @@ int clb_searcher_create_device(int device, int64_t dim, int nbits, int64_t K, co
                                const int64_t* ivf_lengths, int64_t pid_offset, clb_searcher** out) {
     return searcher_create_impl(device, dim, nbits, K, d_centroids, bucket_weights, n_docs, doclens, n_emb, d_codes,
                                 d_residuals, d_ivf, ivf_lengths, pid_offset, true, out);
-}
-
-static int searcher_create_impl(int device, int64_t dim, int nbits, int64_t K, const float* centroids,
-                                const float* bucket_weights, int64_t n_docs, const int64_t* doclens, int64_t n_emb,
-                                const uint32_t* codes, const uint8_t* residuals, const int64_t* ivf,
-                                const int64_t* ivf_lengths, int64_t pid_offset, bool big_on_device, clb_searcher** out) {
-    const hipMemcpyKind big_kind = big_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (!out) return fail(CLB_EARGUMENT, "out is null");
-    *out = nullptr;
-    if (dim < 8 || dim % 8 != 0) return fail(CLB_EDOMAIN, "dim should be a multiple of 8!");          // residual.jl:763-768
-    if (nbits != 1 && nbits != 2 && nbits != 4 && nbits != 8)
-        return fail(CLB_EUNSUPPORTED, "the HIP codec supports nbits in {1,2,4,8} (got %d)", nbits);
-    if (K < 1 || n_docs < 0 || n_emb < 0) return fail(CLB_EARGUMENT, "negative or empty sizes");
-    if (n_emb >= (int64_t)0xffffffffll || n_docs >= (int64_t)0x7fffffffll)
-        return fail(CLB_EUNSUPPORTED, "a shard holds at most 2^32-1 embeddings / 2^31-1 passages");
-    // host-side structure checks (the reference's DimensionMismatch in _cids_to_eids!, ranking.jl:9-12)
-    std::vector<uint32_t> doc_off((size_t)n_docs + 1);
-    int64_t run = 0;
-    for (int64_t p = 0; p < n_docs; ++p) {
-        if (doclens[p] < 0) return fail(CLB_EARGUMENT, "negative doclen at passage %lld", (long long)(p + 1));
-        doc_off[p] = (uint32_t)run;
-        run += doclens[p];
-    }
-    doc_off[n_docs] = (uint32_t)run;
-    if (run != n_emb) return fail(CLB_EDIMENSION, "sum(doclens)=%lld must equal the number of embeddings %lld", (long long)run, (long long)n_emb);
-    std::vector<uint32_t> ivf_off((size_t)K + 1);
-    run = 0;
-    for (int64_t c = 0; c < K; ++c) {
-        if (ivf_lengths[c] < 0) return fail(CLB_EARGUMENT, "negative ivf length");
-        ivf_off[c] = (uint32_t)run;
-        run += ivf_lengths[c];
-    }
-    ivf_off[K] = (uint32_t)run;
-    if (run != n_emb) return fail(CLB_EDIMENSION, "length(ivf) must be equal to sum(ivf_lengths)!");
-    CLB_TRY(use_device(device));
-
-    static std::atomic<uint64_t> next_serial{1};
-    clb_searcher* s = new clb_searcher();
-    s->serial = next_serial.fetch_add(1);
-    s->device = device; s->dim = dim; s->nbits = nbits; s->K = K; s->n_docs = n_docs; s->n_emb = n_emb;
-    s->pid_offset = pid_offset;
-    s->generic = !(dim == kDim && nbits <= 4);     // the tuned kernels are built for dim 128, nbits 1/2/4
-    for (int64_t p = 0; p < n_docs; ++p) s->max_doclen = std::max(s->max_doclen, doclens[p]);
-    auto bail = [&](int rc) { clb_searcher_destroy(s); return rc; };
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess)
-        return bail(fail(CLB_EHIP, "hipStreamCreate failed"));
-    s->ivf_len_sorted = sorted_list_lengths(ivf_off);
-
-    const size_t rows = (size_t)(dim / 8 * nbits);
-    int rc;
-    if ((rc = s->centroids.alloc(sizeof(float) * dim * K))) return bail(rc);
-    if (hipMemcpyAsync(s->centroids.p, centroids, sizeof(float) * dim * K, big_kind, s->stream) != hipSuccess)
-        return bail(fail(CLB_EHIP, "index upload failed"));
-    if ((rc = upload(s->weights, bucket_weights, sizeof(float) * ((size_t)1 << nbits), s->stream))) return bail(rc);
-    // pad the per-embedding arrays by one step (dummy steps read embeddings 0 .. kStepRows-1 even of a tiny index)
-    constexpr int64_t kPad = kStepRows;
-    if ((rc = s->codes0.alloc(sizeof(uint32_t) * (n_emb + kPad)))) return bail(rc);
-    if ((rc = s->residuals.alloc(rows * (n_emb + kPad)))) return bail(rc);
-    if (hipMemsetAsync(s->codes0.p, 0, s->codes0.bytes, s->stream) != hipSuccess ||
-        hipMemsetAsync(s->residuals.p, 0, s->residuals.bytes, s->stream) != hipSuccess ||
-        hipMemcpyAsync(s->codes0.p, codes, sizeof(uint32_t) * n_emb, big_kind, s->stream) != hipSuccess ||
-        hipMemcpyAsync(s->residuals.p, residuals, rows * n_emb, big_kind, s->stream) != hipSuccess)
-        return bail(fail(CLB_EHIP, "index upload failed"));
-    if ((rc = upload(s->doc_off, doc_off.data(), sizeof(uint32_t) * doc_off.size(), s->stream))) return bail(rc);
-    if ((rc = upload(s->ivf_off, ivf_off.data(), sizeof(uint32_t) * ivf_off.size(), s->stream))) return bail(rc);
-    if ((rc = s->ivf_pid.alloc(sizeof(uint32_t) * n_emb))) return bail(rc);
-    DevBuf ivf_raw, err;
-    if ((rc = ivf_raw.alloc(sizeof(int64_t) * n_emb))) return bail(rc);
-    if (n_emb > 0 && hipMemcpyAsync(ivf_raw.p, ivf, sizeof(int64_t) * n_emb, big_kind, s->stream) != hipSuccess)
-        return bail(fail(CLB_EHIP, "index upload failed"));
-    if ((rc = err.alloc(sizeof(int)))) return bail(rc);
-    if (hipMemsetAsync(err.p, 0, sizeof(int), s->stream) != hipSuccess) return bail(fail(CLB_EHIP, "memset failed"));
-    if (n_emb > 0) {
-        const int blocks = (int)((n_emb + 255) / 256);
-        hipLaunchKernelGGL(ivf_to_pid_kernel, dim3(blocks), dim3(256), 0, s->stream, ivf_raw.as<int64_t>(),
-                           s->doc_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), n_emb, (int)n_docs, err.as<int>());
-        hipLaunchKernelGGL(codes_to_zero_based_kernel, dim3(blocks), dim3(256), 0, s->stream,
-                           s->codes0.as<uint32_t>(), n_emb, (uint32_t)K, err.as<int>());
-        hipLaunchKernelGGL(ivf_lists_sorted_kernel, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, s->stream,
-                           s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), (int)K, err.as<int>());
-    }
-    int herr = 0;
-    if (hipMemcpyAsync(&herr, err.p, sizeof(int), hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-        hipStreamSynchronize(s->stream) != hipSuccess)
-        return bail(fail(CLB_EHIP, "index upload failed: %s", hipGetErrorString(hipGetLastError())));
-    if (herr & 1) return bail(fail(CLB_EBOUNDS, "ivf holds embedding ids outside 1..n_emb"));
-    if (herr & 2) return bail(fail(CLB_EDOMAIN, "All the codes must be in the valid range of centroid IDs!"));
-    s->ivf_sorted = !(herr & 4);
-
-    if (!s->generic && n_emb > 0) {
-        // Order every passage's embeddings by centroid code (results cannot change: MaxSim maximises over a passage's
-        // embeddings; row masks, headers and the IVF are positional or per passage).  Equal and neighbouring codes then
-        // sit in adjacent lanes of a pass-1 step: their 64-byte score rows coalesce into fewer, larger requests.
-        const size_t row_bytes = rows;                    // multiple of 16 for dim 128
-        DevBuf keys, keys2, vals, perm, codes_new, res_new;
-        if ((rc = keys.alloc(sizeof(uint64_t) * n_emb)) || (rc = keys2.alloc(sizeof(uint64_t) * n_emb)) ||
-            (rc = vals.alloc(sizeof(uint32_t) * n_emb)) || (rc = perm.alloc(sizeof(uint32_t) * n_emb)) ||
-            (rc = codes_new.alloc(sizeof(uint32_t) * (n_emb + kPad))) || (rc = res_new.alloc(row_bytes * (n_emb + kPad))))
-            return bail(rc);
-        const int blocks = (int)((n_emb + 255) / 256);
-        hipLaunchKernelGGL(passage_code_keys_kernel, dim3(blocks), dim3(256), 0, s->stream, s->codes0.as<uint32_t>(),
-                           s->doc_off.as<uint32_t>(), n_emb, (int)n_docs, keys.as<unsigned long long>(), vals.as<uint32_t>());
-        if ((rc = sort_pairs_u64(keys.as<uint64_t>(), keys2.as<uint64_t>(), vals.as<uint32_t>(), perm.as<uint32_t>(),
-                                 (size_t)n_emb, s->stream)))
-            return bail(rc);
-        if (hipMemsetAsync(codes_new.p, 0, codes_new.bytes, s->stream) != hipSuccess ||
-            hipMemsetAsync(res_new.p, 0, res_new.bytes, s->stream) != hipSuccess)
-            return bail(fail(CLB_EHIP, "memset failed"));
-        hipLaunchKernelGGL(permute_codes_kernel, dim3(blocks), dim3(256), 0, s->stream, perm.as<uint32_t>(),
-                           s->codes0.as<uint32_t>(), codes_new.as<uint32_t>(), n_emb);
-        const int pieces = (int)(row_bytes / 16);
-        hipLaunchKernelGGL(permute_rows16_kernel, dim3((unsigned)(((int64_t)n_emb * pieces + 255) / 256)), dim3(256), 0,
-                           s->stream, perm.as<uint32_t>(), s->residuals.as<uint4>(), res_new.as<uint4>(), n_emb, pieces);
-        if (hipStreamSynchronize(s->stream) != hipSuccess || hipGetLastError() != hipSuccess)
-            return bail(fail(CLB_EHIP, "reordering the index failed"));
-        std::swap(s->codes0.p, codes_new.p); std::swap(s->codes0.bytes, codes_new.bytes);
-        std::swap(s->residuals.p, res_new.p); std::swap(s->residuals.bytes, res_new.bytes);
-    }
-    if (s->generic) {
-        s->mode = 0;
-        s->index_bytes = resident_bytes(s);
-        *out = s;
-        return CLB_OK;
-    }
-    {   // bf16 hi/lo split of the centroids for the bf16x3 centroid scoring
-        if ((rc = s->cent_hi.alloc(sizeof(uint16_t) * dim * K))) return bail(rc);
-        if ((rc = s->cent_lo.alloc(sizeof(uint16_t) * dim * K))) return bail(rc);
-        const int64_t nel = dim * K;
-        hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, s->stream,
-                           s->centroids.as<float>(), s->cent_hi.as<uint16_t>(), s->cent_lo.as<uint16_t>(), nel);
-        if ((rc = s->cent_f16.alloc(sizeof(uint16_t) * dim * K))) return bail(rc);
-        hipLaunchKernelGGL(to_f16_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, s->stream,
-                           s->centroids.as<float>(), s->cent_f16.as<uint16_t>(), nel);
-    }
-    s->cbits = 1;
-    while (((int64_t)1 << s->cbits) < K) ++s->cbits;
-    // the packed word leaves 32 - cbits bits for inv_norm: at least 12 (K <= 2^20), otherwise exact mode only
-    s->approx_ok = approx_supported((int)dim, nbits) && s->cbits <= 20;
-    IndexTables tables;
-    if ((rc = derive_index_tables(s, s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(), n_emb, &tables))) return bail(rc);
-    install_index_tables(s, tables);
-    s->mode = s->approx_ok ? 1 : 0;
-    *out = s;
-    return CLB_OK;
 }
 
 int clb_searcher_destroy(clb_searcher* s) {
@@ -1145,86 +1198,52 @@ static int searcher_append_impl(clb_searcher* s, int64_t n_new, const int64_t* d
     if (!s) return fail(CLB_EARGUMENT, "null searcher");
     if (n_new < 0 || n_new_emb < 0) return fail(CLB_EARGUMENT, "negative sizes");
     if ((n_new > 0 && !doclens) || (n_new_emb > 0 && (!codes || !residuals))) return fail(CLB_EARGUMENT, "null argument");
-    std::vector<uint32_t> new_off((size_t)n_new + 1);       // offsets of the appended passages among the appended embeddings
-    int64_t run = 0, new_max_doclen = 0;
-    for (int64_t p = 0; p < n_new; ++p) {
-        if (doclens[p] < 0) return fail(CLB_EARGUMENT, "negative doclen at appended passage %lld", (long long)(p + 1));
-        new_off[p] = (uint32_t)run;
-        run += doclens[p];
-        new_max_doclen = std::max(new_max_doclen, doclens[p]);
-    }
-    new_off[n_new] = (uint32_t)run;
-    if (run != n_new_emb)
-        return fail(CLB_EDIMENSION, "sum(doclens)=%lld must equal the number of embeddings %lld", (long long)run, (long long)n_new_emb);
+    Offsets add;            // the appended passages among the appended embeddings
+    CLB_TRY(passage_offsets(doclens, n_new, n_new_emb, "appended passage", &add));
     if (n_new == 0) return CLB_OK;
     const int64_t n_old = s->n_emb, d_old = s->n_docs, n_tot = n_old + n_new_emb, d_tot = d_old + n_new, K = s->K;
-    if (n_tot >= (int64_t)0xffffffffll || d_tot >= (int64_t)0x7fffffffll)
-        return fail(CLB_EUNSUPPORTED, "a shard holds at most 2^32-1 embeddings / 2^31-1 passages");
+    CLB_TRY(check_shard_limits(n_tot, d_tot));
     CLB_TRY(use_device(s->device));
     CLB_HIP(hipDeviceSynchronize());      // searches of this handle and whatever wrote the caller's device arrays
     const hipStream_t st = s->stream;
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const size_t rows = (size_t)(s->dim / 8 * s->nbits);
     const int blocks = (int)((n_new_emb + 255) / 256);
-    constexpr int64_t kPad = kStepRows;
 
-    // the new codes, 0-based and checked, in a buffer of the call's own (the caller's array is never written)
-    DevBuf codes_in, err;
+    // the new codes, 0-based and checked, in a buffer of the call's own
+    DevBuf codes_in;
+    DevWord<int> err;
     CLB_TRY(codes_in.alloc(sizeof(uint32_t) * n_new_emb));
-    CLB_TRY(err.alloc(sizeof(int)));
-    CLB_HIP(hipMemsetAsync(err.p, 0, sizeof(int), st));
-    if (n_new_emb > 0) {
-        CLB_HIP(hipMemcpyAsync(codes_in.p, codes, sizeof(uint32_t) * n_new_emb, kind, st));
-        hipLaunchKernelGGL(codes_to_zero_based_kernel, dim3(blocks), dim3(256), 0, st, codes_in.as<uint32_t>(), n_new_emb,
-                           (uint32_t)K, err.as<int>());
-    }
-    int herr = 0;
-    CLB_HIP(hipMemcpyAsync(&herr, err.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    CLB_HIP(hipStreamSynchronize(st));
-    if (herr & 2) return fail(CLB_EDOMAIN, "All the codes must be in the valid range of centroid IDs!");
+    CLB_TRY(err.init(st));
+    CLB_TRY(stage_codes(st, codes, kind, n_new_emb, K, codes_in.as<uint32_t>(), err.ptr()));
+    CLB_TRY(err.read(st));
+    if (err.value & kErrCode) return bad_codes();
 
     // grown per-embedding and per-passage arrays: the old rows, the new rows behind them, the zero padding of one step
     DevBuf codes0, res, doc_off, new_off_d;
-    CLB_TRY(codes0.alloc(sizeof(uint32_t) * (n_tot + kPad)));
-    CLB_TRY(res.alloc(rows * (n_tot + kPad)));
+    CLB_TRY(alloc_padded_rows(st, n_tot, rows, &codes0, &res));
     CLB_TRY(doc_off.alloc(sizeof(uint32_t) * (d_tot + 1)));
-    CLB_TRY(upload(new_off_d, new_off.data(), sizeof(uint32_t) * new_off.size(), st));
+    CLB_TRY(upload(new_off_d, add.off.data(), sizeof(uint32_t) * add.off.size(), st));
     uint32_t* codes0_tail = codes0.as<uint32_t>() + n_old;
     uint8_t* res_tail = res.as<uint8_t>() + rows * n_old;
     CLB_HIP(hipMemcpyAsync(codes0.p, s->codes0.p, sizeof(uint32_t) * n_old, hipMemcpyDeviceToDevice, st));
     CLB_HIP(hipMemcpyAsync(res.p, s->residuals.p, rows * n_old, hipMemcpyDeviceToDevice, st));
-    CLB_HIP(hipMemsetAsync(codes0.as<uint32_t>() + n_tot, 0, sizeof(uint32_t) * kPad, st));
-    CLB_HIP(hipMemsetAsync(res.as<uint8_t>() + rows * n_tot, 0, rows * kPad, st));
     CLB_HIP(hipMemcpyAsync(doc_off.p, s->doc_off.p, sizeof(uint32_t) * (d_old + 1), hipMemcpyDeviceToDevice, st));
     std::vector<uint32_t> off_tail((size_t)n_new);
-    for (int64_t p = 0; p < n_new; ++p) off_tail[p] = (uint32_t)(n_old + new_off[p + 1]);
+    for (int64_t p = 0; p < n_new; ++p) off_tail[p] = (uint32_t)(n_old + add.off[p + 1]);
     CLB_HIP(hipMemcpyAsync(doc_off.as<uint32_t>() + d_old + 1, off_tail.data(), sizeof(uint32_t) * n_new, hipMemcpyHostToDevice, st));
     if (n_new_emb > 0 && !s->generic) {
-        // the per-passage code order of create, on the new passages alone (old passages keep theirs): the same key, sort
-        // and permute kernels over the new rows and their own offsets, written straight into the tail of the grown arrays
-        DevBuf res_in, keys, keys2, vals, perm;
+        // create's per-passage code order on the new passages alone (old passages keep theirs), over the new rows and their
+        // own offsets, written straight into the tail of the grown arrays
+        DevBuf res_in;
         const uint8_t* res_src = residuals;
         if (!on_device || ((uintptr_t)residuals & 15)) {        // the row permutation reads 16-byte pieces
             CLB_TRY(res_in.alloc(rows * n_new_emb));
             CLB_HIP(hipMemcpyAsync(res_in.p, residuals, rows * n_new_emb, kind, st));
             res_src = res_in.as<uint8_t>();
         }
-        CLB_TRY(keys.alloc(sizeof(uint64_t) * n_new_emb));
-        CLB_TRY(keys2.alloc(sizeof(uint64_t) * n_new_emb));
-        CLB_TRY(vals.alloc(sizeof(uint32_t) * n_new_emb));
-        CLB_TRY(perm.alloc(sizeof(uint32_t) * n_new_emb));
-        hipLaunchKernelGGL(passage_code_keys_kernel, dim3(blocks), dim3(256), 0, st, codes_in.as<uint32_t>(),
-                           new_off_d.as<uint32_t>(), n_new_emb, (int)n_new, keys.as<unsigned long long>(), vals.as<uint32_t>());
-        CLB_TRY(sort_pairs_u64(keys.as<uint64_t>(), keys2.as<uint64_t>(), vals.as<uint32_t>(), perm.as<uint32_t>(),
-                               (size_t)n_new_emb, st));
-        hipLaunchKernelGGL(permute_codes_kernel, dim3(blocks), dim3(256), 0, st, perm.as<uint32_t>(), codes_in.as<uint32_t>(),
-                           codes0_tail, n_new_emb);
-        const int pieces = (int)(rows / 16);
-        hipLaunchKernelGGL(permute_rows16_kernel, dim3((unsigned)((n_new_emb * pieces + 255) / 256)), dim3(256), 0, st,
-                           perm.as<uint32_t>(), reinterpret_cast<const uint4*>(res_src), reinterpret_cast<uint4*>(res_tail),
-                           n_new_emb, pieces);
-        CLB_HIP(hipGetLastError());
-        CLB_HIP(hipStreamSynchronize(st));          // the scratch above is freed here
+        CLB_TRY(order_rows_by_code(st, codes_in.as<uint32_t>(), new_off_d.as<uint32_t>(), n_new_emb, n_new, res_src, rows,
+                                   codes0_tail, res_tail));
     } else if (n_new_emb > 0) {
         CLB_HIP(hipMemcpyAsync(codes0_tail, codes_in.p, sizeof(uint32_t) * n_new_emb, hipMemcpyDeviceToDevice, st));
         CLB_HIP(hipMemcpyAsync(res_tail, residuals, rows * n_new_emb, kind, st));
@@ -1275,7 +1294,7 @@ static int searcher_append_impl(clb_searcher* s, int64_t n_new, const int64_t* d
     swap_buf(s->codes0, codes0); swap_buf(s->residuals, res); swap_buf(s->doc_off, doc_off);
     swap_buf(s->ivf_off, ivf_off); swap_buf(s->ivf_pid, ivf_pid);
     s->n_docs = d_tot; s->n_emb = n_tot;
-    s->max_doclen = std::max(s->max_doclen, new_max_doclen);
+    s->max_doclen = std::max(s->max_doclen, add.longest);
     s->ivf_len_sorted = sorted_list_lengths(h_ivf_off);
     if (s->generic) s->index_bytes = resident_bytes(s);
     else install_index_tables(s, tables, s->bounds_synced);
@@ -1347,7 +1366,7 @@ int clb_searcher_sync_bound_consts(clb_searcher* s, clb_comm* c) {
 int clb_searcher_set_pass1_gather(clb_searcher* s, int form) {
     if (!s) return fail(CLB_EARGUMENT, "null searcher");
     if (form < -1 || form > 1) return fail(CLB_EARGUMENT, "pass-1 gather form must be -1 (by the code statistics), 0 (VGPR) or 1 (LDS-DMA)");
-    s->gather_lds = form < 0 ? (s->code_adjacency < 0.2 && s->K * 64 > ((int64_t)4 << 20)) : form;
+    s->gather_lds = form < 0 ? default_gather_lds(s) : form;
     return CLB_OK;
 }
 int clb_searcher_get_pass1_gather(const clb_searcher* s, double* adjacency) {
@@ -1374,25 +1393,19 @@ int clb_searcher_set_centroid_products(clb_searcher* s, int n) {
 int clb_searcher_get_centroid_products(const clb_searcher* s, float* max_f16_error) {
     if (!s) return -1;
     if (max_f16_error) *max_f16_error = s->dc_f16;
-    return (s->s1_x1 == 1 || (s->s1_x1 < 0 && s->bounds_synced)) && s->cent_f16.p && s->dc_f16 > 0.f ? 1 : 3;
+    return single_product_table(s) ? 1 : 3;
 }
 
 int clb_searcher_get_bound_consts(const clb_searcher* s, float* consts) {
     if (!s || !consts) return fail(CLB_EARGUMENT, "null argument");
-    consts[0] = s->approx_consts.cn_max; consts[1] = s->approx_consts.rn_max; consts[2] = s->approx_consts.inv_max;
-    consts[3] = s->approx_consts.rb_max; consts[4] = s->approx_consts.dw_rn; consts[5] = s->approx_consts.inv_qerr;
+    bound_consts_to_abi(s->approx_consts, consts);
     return CLB_OK;
 }
 int clb_searcher_set_bound_consts(clb_searcher* s, const float* consts) {
     if (!s || !consts) return fail(CLB_EARGUMENT, "null argument");
     for (int i = 0; i < 6; ++i)
         if (!(consts[i] >= 0.f)) return fail(CLB_EARGUMENT, "bound constants must be non-negative numbers");
-    s->approx_consts.cn_max = std::max(s->approx_consts.cn_max, consts[0]);
-    s->approx_consts.rn_max = std::max(s->approx_consts.rn_max, consts[1]);
-    s->approx_consts.inv_max = std::max(s->approx_consts.inv_max, consts[2]);
-    s->approx_consts.rb_max = std::max(s->approx_consts.rb_max, consts[3]);
-    s->approx_consts.dw_rn = std::max(s->approx_consts.dw_rn, consts[4]);
-    s->approx_consts.inv_qerr = std::max(s->approx_consts.inv_qerr, consts[5]);
+    raise_bound_consts(s->approx_consts, consts);
     s->bounds_synced = true;
     return CLB_OK;
 }
@@ -1536,34 +1549,24 @@ int clb_search_batch_filtered(clb_searcher* s, const float* Q, int64_t T, int64_
 
 // ---- clb_filter ---------------------------------------------------------------------------------------------------
 // the words are on the device: clear the tail bits, count once (creation may synchronise, searching never reads the count back)
-static int filter_finish(clb_searcher* s, clb_filter* f, clb_filter** out) {
-    DevBuf cnt;
-    int rc = cnt.alloc(sizeof(unsigned long long));
-    unsigned long long h = 0;
+static int filter_finish(clb_searcher* s, FilterPtr f, clb_filter** out) {
+    DevWord<unsigned long long> cnt;
     const int W = (int)((s->n_docs + 31) / 32);
-    if (!rc && hipMemsetAsync(cnt.p, 0, sizeof h, s->stream) != hipSuccess) rc = fail(CLB_EHIP, "memset failed");
-    if (!rc && W > 0)
+    CLB_TRY(cnt.init(s->stream));
+    if (W > 0)
         hipLaunchKernelGGL(filter_count_kernel, dim3((unsigned)std::max(1, std::min(1024, (W + 255) / 256))), dim3(256), 0, s->stream,
-                           f->bits.as<uint32_t>(), W, (int)s->n_docs, cnt.as<unsigned long long>());
-    if (!rc && (hipMemcpyAsync(&h, cnt.p, sizeof h, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                hipStreamSynchronize(s->stream) != hipSuccess || hipGetLastError() != hipSuccess))
-        rc = fail(CLB_EHIP, "building the filter failed: %s", hipGetErrorString(hipGetLastError()));
-    if (rc) { delete f; return rc; }
-    f->count = (int64_t)h;
-    *out = f;
+                           f->bits.as<uint32_t>(), W, (int)s->n_docs, cnt.ptr());
+    CLB_TRY(cnt.read(s->stream));
+    f->count = (int64_t)cnt.value;
+    *out = f.release();
     return CLB_OK;
 }
-static int filter_new(clb_searcher* s, clb_filter** out, clb_filter** f_out) {
-    if (!out) return fail(CLB_EARGUMENT, "out is null");
-    *out = nullptr;
-    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+// a filter of s with its words allocated, on s's device; the callers have checked their arguments
+static int filter_new(const clb_searcher* s, FilterPtr& f) {
     CLB_TRY(use_device(s->device));
-    clb_filter* f = new clb_filter();
+    f.reset(new clb_filter());
     f->owner = s->serial; f->device = s->device; f->n_docs = s->n_docs;
-    const int rc = f->bits.alloc(sizeof(uint32_t) * (size_t)((s->n_docs + 31) / 32));
-    if (rc) { delete f; return rc; }
-    *f_out = f;
-    return CLB_OK;
+    return f->bits.alloc(sizeof(uint32_t) * (size_t)((s->n_docs + 31) / 32));
 }
 
 int clb_filter_create_pids(clb_searcher* s, const int64_t* pids, int64_t n, clb_filter** out) {
@@ -1575,26 +1578,20 @@ int clb_filter_create_pids(clb_searcher* s, const int64_t* pids, int64_t n, clb_
         if (pids[i] <= s->pid_offset || pids[i] > s->pid_offset + s->n_docs)
             return fail(CLB_EBOUNDS, "pid %lld (entry %lld) outside %lld..%lld", (long long)pids[i], (long long)i,
                         (long long)(s->pid_offset + 1), (long long)(s->pid_offset + s->n_docs));
-    clb_filter* f = nullptr;
-    CLB_TRY(filter_new(s, out, &f));
-    DevBuf d_pids, err;
-    int rc = CLB_OK, herr = 0;
-    if (hipMemsetAsync(f->bits.p, 0, f->bits.bytes, s->stream) != hipSuccess) rc = fail(CLB_EHIP, "memset failed");
-    if (!rc && n > 0) {
-        if (!(rc = upload(d_pids, pids, sizeof(int64_t) * n, s->stream)) && !(rc = err.alloc(sizeof(int)))) {
-            if (hipMemsetAsync(err.p, 0, sizeof(int), s->stream) != hipSuccess) rc = fail(CLB_EHIP, "memset failed");
-            else {
-                hipLaunchKernelGGL(filter_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, d_pids.as<int64_t>(),
-                                   n, s->pid_offset, (int)s->n_docs, f->bits.as<uint32_t>(), err.as<int>());
-                if (hipMemcpyAsync(&herr, err.p, sizeof(int), hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                    hipStreamSynchronize(s->stream) != hipSuccess)        // ... before d_pids and the host array go away
-                    rc = fail(CLB_EHIP, "building the filter failed: %s", hipGetErrorString(hipGetLastError()));
-                else if (herr) rc = fail(CLB_EBOUNDS, "a pid outside the searcher's passages");
-            }
-        }
+    FilterPtr f(nullptr, clb_filter_destroy);
+    CLB_TRY(filter_new(s, f));
+    CLB_HIP(hipMemsetAsync(f->bits.p, 0, f->bits.bytes, s->stream));
+    if (n > 0) {
+        DevBuf d_pids;
+        DevWord<int> err;
+        CLB_TRY(upload(d_pids, pids, sizeof(int64_t) * n, s->stream));
+        CLB_TRY(err.init(s->stream));
+        hipLaunchKernelGGL(filter_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, d_pids.as<int64_t>(),
+                           n, s->pid_offset, (int)s->n_docs, f->bits.as<uint32_t>(), err.ptr());
+        CLB_TRY(err.read(s->stream));        // ... before d_pids and the host array go away
+        if (err.value) return fail(CLB_EBOUNDS, "a pid outside the searcher's passages");
     }
-    if (rc) { delete f; return rc; }
-    return filter_finish(s, f, out);
+    return filter_finish(s, std::move(f), out);
 }
 
 int clb_filter_create_bitmap(clb_searcher* s, const uint32_t* words, int64_t n_words, clb_filter** out) {
@@ -1604,14 +1601,13 @@ int clb_filter_create_bitmap(clb_searcher* s, const uint32_t* words, int64_t n_w
     const int64_t W = (s->n_docs + 31) / 32;
     if (n_words != W) return fail(CLB_EARGUMENT, "n_words=%lld, the searcher's bitmap has ceil(n_docs / 32) = %lld words", (long long)n_words, (long long)W);
     if (W > 0 && !words) return fail(CLB_EARGUMENT, "words is null");
-    clb_filter* f = nullptr;
-    CLB_TRY(filter_new(s, out, &f));
-    if (W > 0 && (hipMemcpyAsync(f->bits.p, words, sizeof(uint32_t) * W, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-                  hipStreamSynchronize(s->stream) != hipSuccess)) {       // the library never retains a host pointer
-        delete f;
-        return fail(CLB_EHIP, "uploading the filter failed: %s", hipGetErrorString(hipGetLastError()));
+    FilterPtr f(nullptr, clb_filter_destroy);
+    CLB_TRY(filter_new(s, f));
+    if (W > 0) {       // the library never retains a host pointer
+        CLB_HIP(hipMemcpyAsync(f->bits.p, words, sizeof(uint32_t) * W, hipMemcpyHostToDevice, s->stream));
+        CLB_HIP(hipStreamSynchronize(s->stream));
     }
-    return filter_finish(s, f, out);
+    return filter_finish(s, std::move(f), out);
 }
 
 int64_t clb_filter_count(const clb_filter* f) { return f ? f->count : 0; }

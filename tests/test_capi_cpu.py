@@ -132,6 +132,42 @@ def test_round4_entry_points_check_their_arguments_first():
                                             None, p(il), i64(0), C.byref(out)) == 10
 
 
+def test_create_and_append_check_their_arguments_before_the_device():
+    """What clb_searcher_create and clb_searcher_append refuse before they select a device: code and message of each."""
+    import ctypes as C
+    l = clb.lib()
+    i64 = C.c_int64
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    idx = clb.synthetic.make_index(0, 20, K=8)
+    w = np.ascontiguousarray(idx["bucket_weights"], np.float32)
+
+    def create(dim=128, nbits=2, doclens=idx["doclens"], ivf_lengths=idx["ivf_lengths"], with_out=True):
+        dl, il = np.ascontiguousarray(doclens, np.int64), np.ascontiguousarray(ivf_lengths, np.int64)
+        out = C.c_void_p(0xdead0)
+        rc = l.clb_searcher_create_device(0, i64(dim), nbits, i64(8), None, p(w), i64(dl.size), p(dl), i64(idx["codes"].size), None,
+                                          None, None, p(il), i64(0), C.byref(out) if with_out else None)
+        assert not with_out or rc == 0 or out.value is None          # a failed create leaves no handle
+        return rc, l.clb_last_error().decode()
+
+    def off_by_one(a, at):
+        b = a.copy(); b[at] += 1
+        return b
+    negative = idx["doclens"].copy(); negative[4] = -negative[4]
+    for kw, code, text in ((dict(with_out=False), 4, "out is null"),
+                           (dict(dim=132), 2, "dim should be a multiple of 8!"),
+                           (dict(nbits=3), 11, "nbits in {1,2,4,8} (got 3)"),
+                           (dict(doclens=negative), 4, "negative doclen at passage 5"),
+                           (dict(doclens=off_by_one(idx["doclens"], -1)), 1, "sum(doclens)=%d must equal the number of embeddings %d"
+                            % (idx["codes"].size + 1, idx["codes"].size)),
+                           (dict(ivf_lengths=off_by_one(idx["ivf_lengths"], 0)), 1, "length(ivf) must be equal to sum(ivf_lengths)!")):
+        rc, msg = create(**kw)
+        assert rc == code and text in msg, (kw.keys(), rc, msg)
+    dl = np.ascontiguousarray(idx["doclens"][:2], np.int64)
+    for append in (lambda *a: l.clb_searcher_append(*a), lambda *a: l.clb_searcher_append_device(*a, None)):
+        assert append(C.c_void_p(), i64(2), p(dl), i64(int(dl.sum())), None, None) == 4
+        assert "null searcher" in l.clb_last_error().decode()
+
+
 def test_round5_entry_points_check_their_arguments_first():
     """Round 5: plain device arrays + the row gather for hosts without their own (the Julia shim's device-resident index()),
     and the encoder's sticky error flag: argument contracts first, then the device check -- no CPU fallback."""

@@ -285,6 +285,24 @@ def test_synced_bound_constants_are_never_lowered(small):
         s.close(); fresh.close()
 
 
+def test_raised_bound_constants_read_back_as_the_maximum_and_switch_the_centroid_products(small):
+    """raise_bound_consts(x) with x below the old value in some fields and above it in others: the constants read back are
+    maximum(old, x), and the handle now counts as a shard of a group -- batches of 16+ queries default to the score table
+    from one fp16 product (centroid_products 3 -> 1; the measured fp16 error of the centroids is what it was)."""
+    idx, _, _ = small
+    s = clb.Searcher(index=idx)
+    try:
+        old = s.bound_consts
+        n, dc = s.centroid_products
+        assert n == 3 and dc > 0 and (old > 0).all(), (n, dc, old)
+        x = old * np.array([2, 0.5, 1, 0.25, 3, 0.5], np.float32)
+        s.raise_bound_consts(x)
+        assert np.array_equal(s.bound_consts, np.maximum(old, x))
+        assert s.centroid_products == (1, dc)
+    finally:
+        s.close()
+
+
 def test_add_embeddings_equals_add_compressed_of_the_oracle_codec(oracle, small):
     """50 passages of Gaussian-mixture embeddings compressed with the index's own centroids and cutoffs on the device, against
     oracle.compress of the same columns appended as codes and residuals."""
