@@ -97,6 +97,8 @@ def lib() -> C.CDLL:
         l.clb_searcher_generation.restype = C.c_int64
         l.clb_searcher_num_docs.restype = C.c_int64
         l.clb_searcher_num_embeddings.restype = C.c_int64
+        l.clb_searcher_remove.restype = C.c_int
+        l.clb_searcher_remove.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         _lib = l
     return _lib
 

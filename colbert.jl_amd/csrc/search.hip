@@ -11,6 +11,7 @@
 #include "append_kernels.hpp"
 #include "approx_kernels.hpp"
 #include "generic_kernels.hpp"
+#include "remove_kernels.hpp"
 #include "search_kernels.hpp"
 #include "sort.hpp"
 
@@ -108,6 +109,7 @@ struct clb_searcher {
     DevBuf codes0;      // u32 [n_emb], 0-based
     DevBuf residuals;   // u8 [n_emb][16*nbits]
     DevBuf doc_off;     // u32 [n_docs+1]
+    DevBuf live;        // u32 [ceil(n_docs / 32)]: the passages that hold embeddings, in a filter's layout (FilterArgs::live)
     DevBuf ivf_off;     // u32 [K+1]
     DevBuf ivf_pid;     // u32 [n_emb] local passage ids grouped by centroid
     DevBuf codeinv;     // u32 [n_emb]: code | quantised inv_norm, the one word pass 1 streams per embedding (two-pass mode)
@@ -130,7 +132,7 @@ struct clb_searcher {
     Prof prof;
     int64_t last_cand_docs = 0, last_cand_embs = 0, last_resc_docs = 0, last_resc_embs = 0;
     int64_t index_bytes = 0;
-    int64_t generation = 0;    // clb_searcher_append calls that changed the handle
+    int64_t generation = 0;    // clb_searcher_append / clb_searcher_remove calls that changed the handle
 };
 
 namespace {
@@ -442,8 +444,9 @@ int run_retrieve(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) 
 }
 
 // the filter operand of queries b0 .. b0 + n - 1 of the sub-batch: query b0 is entry 0, as a launch over those queries counts
-FilterArgs filter_args(const Batch& q, int b0, int n) {
+FilterArgs filter_args(const clb_searcher* s, const Batch& q, int b0, int n) {
     FilterArgs fa{};
+    fa.live = s->live.as<uint32_t>();
     for (int i = 0; i < n && i < kFilterQueries; ++i) fa.bits[i] = q.filt[b0 + i] ? q.filt[b0 + i]->bits.as<uint32_t>() : nullptr;
     fa.all = q.filt_all;
     return fa;
@@ -460,7 +463,7 @@ int mark_and_compact_impl(clb_searcher* s, Workspace& w, hipStream_t st, const B
     static_assert(kScanBlock * kWordsPerThread == 1024, "mark_count_kernel writes 1024-word count blocks");
     static_assert(kSubBatch <= kFilterQueries, "the filter handles of a sub-batch travel in one kernel argument block");
     FilterOperand<FILT> fa{};
-    if constexpr (FILT) fa = filter_args(q, b0, B);
+    if constexpr (FILT) fa = filter_args(s, q, b0, B);
     const int T = q.T, nprobe = q.nprobe;
     uint32_t* bitmap = w.bitmap.as<uint32_t>() + (size_t)b0 * w.W;
     int* blocksum = w.blocksum.as<int>() + (size_t)b0 * w.nblk_bitmap;
@@ -879,8 +882,8 @@ int for_sub_batches(clb_searcher* s, Workspace& w, int64_t T, int64_t B, int64_t
     return CLB_OK;
 }
 
-// ---- shared by clb_searcher_create and clb_searcher_append: the steps that check, order and write a batch of rows, and
-// the tables a handle derives from its resident index --------------------------------------------------------------------
+// ---- shared by clb_searcher_create, clb_searcher_append and clb_searcher_remove: the steps that check, order and write a
+// batch of rows, and the tables a handle derives from its resident index ---------------------------------------------
 
 using FilterPtr = std::unique_ptr<clb_filter, decltype(&clb_filter_destroy)>;
 
@@ -983,6 +986,15 @@ int order_rows_by_code(hipStream_t st, const uint32_t* codes_src, const uint32_t
     return CLB_OK;
 }
 
+// the bitmap of the passages that hold embeddings (clb_searcher::live) from n_docs + 1 passage offsets on the device
+int build_live_bitmap(hipStream_t st, const uint32_t* doc_off, int64_t n_docs, DevBuf* live) {
+    const int64_t W = (n_docs + 31) / 32;
+    CLB_TRY(live->alloc(sizeof(uint32_t) * (size_t)W));
+    if (W > 0) hipLaunchKernelGGL(passage_live_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, doc_off, (int)n_docs,
+                                  live->as<uint32_t>());
+    return CLB_OK;
+}
+
 // the list lengths, descending, from the host copy of ivf_off (K + 1 entries): the candidate-capacity bound
 std::vector<uint32_t> sorted_list_lengths(const std::vector<uint32_t>& ivf_off) {
     std::vector<uint32_t> len(ivf_off.size() - 1);
@@ -993,7 +1005,7 @@ std::vector<uint32_t> sorted_list_lengths(const std::vector<uint32_t>& ivf_off) 
 
 int64_t resident_bytes(const clb_searcher* s) {
     return (int64_t)(s->centroids.bytes + s->weights.bytes + s->codes0.bytes + s->residuals.bytes + s->doc_off.bytes +
-                     s->ivf_off.bytes + s->ivf_pid.bytes + s->codeinv.bytes);
+                     s->ivf_off.bytes + s->ivf_pid.bytes + s->codeinv.bytes + s->live.bytes);
 }
 
 // Statistics and tables of the tuned path over a whole index (codes0 / residuals as the handle stores them, padded by
@@ -1039,7 +1051,8 @@ void raise_bound_consts(ApproxConsts& a, const float* c) {
     for (int i = 0; i < 6; ++i) a.*kBoundConsts[i] = std::max(a.*kBoundConsts[i], c[i]);
 }
 
-// keep_max: the handle's bound constants are a shard group's (bounds_synced) -- like `set`, an append never lowers one
+// keep_max: the handle's bound constants are a shard group's (bounds_synced) -- like `set`, an append or a removal never
+// lowers one
 void install_index_tables(clb_searcher* s, IndexTables& t, bool keep_max = false) {
     s->code_adjacency = t.code_adjacency;
     s->gather_lds = default_gather_lds(s);
@@ -1054,6 +1067,31 @@ void install_index_tables(clb_searcher* s, IndexTables& t, bool keep_max = false
     s->approx_consts.dc_max = 0.f;
     if (keep_max) raise_bound_consts(s->approx_consts, old);
     s->index_bytes = resident_bytes(s);
+}
+
+// the row compaction of clb_searcher_remove (remove_kernels.hpp) in pieces of one size: s still holds the unreduced index
+template <class Piece>
+void launch_remove_rows(hipStream_t st, const clb_searcher* s, const uint32_t* new_off, int64_t n_rows, size_t row_bytes,
+                        uint32_t* codes_dst, uint8_t* res_dst) {
+    const int64_t tiles = (n_rows + kRemoveTile - 1) / kRemoveTile;
+    hipLaunchKernelGGL(remove_rows_kernel<Piece>, dim3((unsigned)std::min<int64_t>(tiles, 8192)), dim3(256), 0, st,
+                       s->doc_off.as<uint32_t>(), new_off, (int)s->n_docs, n_rows, s->codes0.as<uint32_t>(),
+                       s->residuals.as<Piece>(), (int)(row_bytes / sizeof(Piece)), codes_dst, reinterpret_cast<Piece*>(res_dst));
+}
+
+// The end of an append or a removal, after the arrays and counts of the changed index have been swapped in (h_ivf_off: the
+// host copy of its K + 1 list offsets): what the handle derives from them, the workspaces, the generation.  Cannot fail.
+void finish_index_change(clb_searcher* s, IndexTables& tables, const std::vector<uint32_t>& h_ivf_off) {
+    s->ivf_len_sorted = sorted_list_lengths(h_ivf_off);
+    if (s->generic) s->index_bytes = resident_bytes(s);
+    else install_index_tables(s, tables, s->bounds_synced);
+    for (auto& w : s->ws) {       // sized for the old index: the next ensure_workspace sizes every buffer again
+        w.Bcap = 0;
+        w.filt_cap = 0;           // populations of filters that no longer fit the handle
+        w.bitmap.release();       // its rows had the old word count
+        w.pending.valid = false;
+    }
+    ++s->generation;
 }
 
 }  // namespace
@@ -1108,6 +1146,7 @@ static int searcher_create_impl(int device, int64_t dim, int nbits, int64_t K, c
     CLB_TRY(alloc_padded_rows(st, n_emb, rows, &s->codes0, &s->residuals));
     CLB_HIP(hipMemcpyAsync(s->residuals.p, residuals, rows * n_emb, big_kind, st));
     CLB_TRY(upload(s->doc_off, docs.off.data(), sizeof(uint32_t) * docs.off.size(), st));
+    CLB_TRY(build_live_bitmap(st, s->doc_off.as<uint32_t>(), n_docs, &s->live));
     CLB_TRY(upload(s->ivf_off, lists.off.data(), sizeof(uint32_t) * lists.off.size(), st));
     CLB_TRY(s->ivf_pid.alloc(sizeof(uint32_t) * n_emb));
     DevBuf ivf_raw;
@@ -1232,6 +1271,8 @@ static int searcher_append_impl(clb_searcher* s, int64_t n_new, const int64_t* d
     std::vector<uint32_t> off_tail((size_t)n_new);
     for (int64_t p = 0; p < n_new; ++p) off_tail[p] = (uint32_t)(n_old + add.off[p + 1]);
     CLB_HIP(hipMemcpyAsync(doc_off.as<uint32_t>() + d_old + 1, off_tail.data(), sizeof(uint32_t) * n_new, hipMemcpyHostToDevice, st));
+    DevBuf live;
+    CLB_TRY(build_live_bitmap(st, doc_off.as<uint32_t>(), d_tot, &live));
     if (n_new_emb > 0 && !s->generic) {
         // create's per-passage code order on the new passages alone (old passages keep theirs), over the new rows and their
         // own offsets, written straight into the tail of the grown arrays
@@ -1292,19 +1333,10 @@ static int searcher_append_impl(clb_searcher* s, int64_t n_new, const int64_t* d
 
     // ---- nothing below can fail ----
     swap_buf(s->codes0, codes0); swap_buf(s->residuals, res); swap_buf(s->doc_off, doc_off);
-    swap_buf(s->ivf_off, ivf_off); swap_buf(s->ivf_pid, ivf_pid);
+    swap_buf(s->ivf_off, ivf_off); swap_buf(s->ivf_pid, ivf_pid); swap_buf(s->live, live);
     s->n_docs = d_tot; s->n_emb = n_tot;
     s->max_doclen = std::max(s->max_doclen, add.longest);
-    s->ivf_len_sorted = sorted_list_lengths(h_ivf_off);
-    if (s->generic) s->index_bytes = resident_bytes(s);
-    else install_index_tables(s, tables, s->bounds_synced);
-    for (auto& w : s->ws) {       // sized for the old index: the next ensure_workspace sizes every buffer again
-        w.Bcap = 0;
-        w.filt_cap = 0;           // populations of filters that no longer fit the handle
-        w.bitmap.release();       // its rows had the old word count
-        w.pending.valid = false;
-    }
-    ++s->generation;
+    finish_index_change(s, tables, h_ivf_off);
     return CLB_OK;
 }
 
@@ -1316,6 +1348,100 @@ int clb_searcher_append_device(clb_searcher* s, int64_t n_new, const int64_t* do
                                const uint32_t* d_codes, const uint8_t* d_residuals, void* hip_stream) {
     (void)hip_stream;     // the call waits for the whole device on entry, the work of that stream included
     return searcher_append_impl(s, n_new, doclens, n_new_emb, d_codes, d_residuals, true);
+}
+// clb_searcher_remove (include/colbert_hip.h), built like an append: the reduced codes0 / residuals / doc_off, the compacted
+// inverted lists and the approximate-pass tables of the reduced index stand beside the handle's arrays until the last device
+// work has been waited for; any return before the swaps leaves the handle untouched.
+static int searcher_remove_impl(clb_searcher* s, const int64_t* pids, int64_t n, int64_t* n_removed) {
+    if (n_removed) *n_removed = 0;
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    if (n < 0 || (n > 0 && !pids)) return fail(CLB_EARGUMENT, "pids is null or n < 0");
+    for (int64_t i = 0; i < n; ++i)
+        if (pids[i] <= s->pid_offset || pids[i] > s->pid_offset + s->n_docs)
+            return fail(CLB_EBOUNDS, "pid %lld (entry %lld) outside %lld..%lld", (long long)pids[i], (long long)i,
+                        (long long)(s->pid_offset + 1), (long long)(s->pid_offset + s->n_docs));
+    if (n == 0 || s->n_emb == 0) return CLB_OK;       // no pid named, or every named passage is empty already
+    const int64_t n_old = s->n_emb, n_docs = s->n_docs, K = s->K;
+    CLB_TRY(use_device(s->device));
+    CLB_HIP(hipDeviceSynchronize());      // searches of this handle
+    const hipStream_t st = s->stream;
+    const size_t rows = (size_t)(s->dim / 8 * s->nbits);
+
+    // the removed passages as a bitmap in a filter's layout, the lengths that stay, their offsets
+    DevBuf d_pids, gone, len, doc_off;
+    DevWord<int> err;
+    DevWord<RemoveCounts> counts;
+    CLB_TRY(upload(d_pids, pids, sizeof(int64_t) * n, st));
+    CLB_TRY(gone.alloc(sizeof(uint32_t) * (size_t)((n_docs + 31) / 32)));
+    CLB_TRY(len.alloc(sizeof(uint32_t) * (n_docs + 1)));
+    CLB_TRY(doc_off.alloc(sizeof(uint32_t) * (n_docs + 1)));
+    CLB_TRY(err.init(st));
+    CLB_TRY(counts.init(st));
+    CLB_HIP(hipMemsetAsync(gone.p, 0, gone.bytes, st));
+    hipLaunchKernelGGL(filter_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_pids.as<int64_t>(), n,
+                       s->pid_offset, (int)n_docs, gone.as<uint32_t>(), err.ptr());
+    hipLaunchKernelGGL(remove_lengths_kernel, dim3((unsigned)((n_docs + 1 + 255) / 256)), dim3(256), 0, st,
+                       s->doc_off.as<uint32_t>(), gone.as<uint32_t>(), (int)n_docs, len.as<uint32_t>(), counts.ptr());
+    CLB_TRY(exclusive_scan_u32(len.as<uint32_t>(), doc_off.as<uint32_t>(), (size_t)n_docs, st));
+    uint32_t n_left = 0;
+    CLB_HIP(hipMemcpyAsync(&n_left, doc_off.as<uint32_t>() + n_docs, sizeof n_left, hipMemcpyDeviceToHost, st));
+    CLB_TRY(err.read(st));                // ... before d_pids and the host array go away
+    CLB_TRY(counts.read(st));
+    if (err.value) return fail(CLB_EBOUNDS, "a pid outside the searcher's passages");
+    if (counts.value.removed == 0) return CLB_OK;
+    const int64_t n_new = n_left;
+
+    // the rows that stay, in their old order, and the zero padding of one step
+    DevBuf codes0, res, live;
+    CLB_TRY(build_live_bitmap(st, doc_off.as<uint32_t>(), n_docs, &live));
+    CLB_TRY(alloc_padded_rows(st, n_new, rows, &codes0, &res));
+    if (n_new > 0) {
+        if (rows % 16 == 0) launch_remove_rows<uint4>(st, s, doc_off.as<uint32_t>(), n_new, rows, codes0.as<uint32_t>(), res.as<uint8_t>());
+        else if (rows % 4 == 0) launch_remove_rows<uint32_t>(st, s, doc_off.as<uint32_t>(), n_new, rows, codes0.as<uint32_t>(), res.as<uint8_t>());
+        else launch_remove_rows<uint8_t>(st, s, doc_off.as<uint32_t>(), n_new, rows, codes0.as<uint32_t>(), res.as<uint8_t>());
+    }
+
+    // the inverted lists: a flag per entry, its scan, one scatter of the entries that stay, the offsets from the same scan
+    DevBuf flag, pos, ivf_off, ivf_pid;
+    CLB_TRY(flag.alloc(sizeof(uint32_t) * (n_old + 1)));
+    CLB_TRY(pos.alloc(sizeof(uint32_t) * (n_old + 1)));
+    CLB_TRY(ivf_off.alloc(sizeof(uint32_t) * (K + 1)));
+    CLB_TRY(ivf_pid.alloc(sizeof(uint32_t) * n_new));
+    const dim3 entries((unsigned)((n_old + 1 + 255) / 256));
+    hipLaunchKernelGGL(ivf_keep_flags_kernel, entries, dim3(256), 0, st, s->ivf_pid.as<uint32_t>(), gone.as<uint32_t>(), n_old,
+                       flag.as<uint32_t>());
+    CLB_TRY(exclusive_scan_u32(flag.as<uint32_t>(), pos.as<uint32_t>(), (size_t)n_old, st));
+    flag.release();         // the scan has been waited for
+    hipLaunchKernelGGL(ivf_compact_kernel, entries, dim3(256), 0, st, s->ivf_pid.as<uint32_t>(), pos.as<uint32_t>(), n_old,
+                       ivf_pid.as<uint32_t>());
+    hipLaunchKernelGGL(ivf_compact_offsets_kernel, dim3((unsigned)((K + 1 + 255) / 256)), dim3(256), 0, st,
+                       s->ivf_off.as<uint32_t>(), pos.as<uint32_t>(), (int)(K + 1), ivf_off.as<uint32_t>());
+    CLB_HIP(hipGetLastError());
+    std::vector<uint32_t> h_ivf_off((size_t)K + 1);
+    CLB_HIP(hipMemcpyAsync(h_ivf_off.data(), ivf_off.p, sizeof(uint32_t) * (K + 1), hipMemcpyDeviceToHost, st));
+    CLB_HIP(hipStreamSynchronize(st));
+    if ((int64_t)h_ivf_off[K] != n_new) return fail(CLB_EHIP, "compacted inverted lists hold %lld entries, expected %lld",
+                                                    (long long)h_ivf_off[K], (long long)n_new);
+    pos.release();
+
+    // code | inv_norm words and bound constants of the reduced index: inv_norm is quantised over the index's own range, which
+    // a removed row may narrow
+    IndexTables tables;
+    if (!s->generic) CLB_TRY(derive_index_tables(s, codes0.as<uint32_t>(), res.as<uint8_t>(), n_new, &tables));
+    CLB_HIP(hipStreamSynchronize(st));
+    CLB_HIP(hipGetLastError());
+
+    // ---- nothing below can fail ----
+    swap_buf(s->codes0, codes0); swap_buf(s->residuals, res); swap_buf(s->doc_off, doc_off);
+    swap_buf(s->ivf_off, ivf_off); swap_buf(s->ivf_pid, ivf_pid); swap_buf(s->live, live);
+    s->n_emb = n_new;
+    s->max_doclen = counts.value.longest;
+    finish_index_change(s, tables, h_ivf_off);
+    if (n_removed) *n_removed = counts.value.removed;
+    return CLB_OK;
+}
+int clb_searcher_remove(clb_searcher* s, const int64_t* pids, int64_t n, int64_t* n_removed) {
+    return searcher_remove_impl(s, pids, n, n_removed);
 }
 // a count cannot carry an error code: a null handle gives -CLB_EARGUMENT and the message
 int64_t clb_searcher_generation(const clb_searcher* s) { return s ? s->generation : -(int64_t)fail(CLB_EARGUMENT, "null searcher"); }

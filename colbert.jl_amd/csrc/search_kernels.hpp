@@ -180,10 +180,13 @@ static __global__ void topn_final_kernel(const ValIdx* __restrict__ partial, int
 // upload, nothing for a captured graph to re-read.  bits[b] == nullptr: query b is not filtered.
 // all == 0 (CLB_FILTER_CANDIDATES): candidates = marked AND filter.  all == 1 (CLB_FILTER_ALL): the filter IS the
 // candidate set of a filtered query -- nothing is marked for it, count and emit read the filter's words and leave them
-// alone.  FILT = false instantiations are the unfiltered kernels: the operand is an empty struct and no code is added.
+// alone.  A passage without embeddings (create accepts one; clb_searcher_remove leaves one behind) cannot be scored -- the
+// scoring kernels address row len - 1 of every candidate -- and never is a candidate of retrieve(): `live`, the searcher's
+// bitmap of the passages that hold embeddings, is AND-ed into the filter's words there.  FILT = false instantiations are the unfiltered kernels: the operand is an empty struct and no code is added.
 constexpr int kFilterQueries = 64;
 struct FilterArgs {
     const uint32_t* bits[kFilterQueries];
+    const uint32_t* live;
     int all;
 };
 struct NoFilter {};
@@ -369,7 +372,7 @@ static __global__ __launch_bounds__(1024) void mark_count_kernel(const int* __re
             // the filter word goes in BEFORE the count and the write-out: blocksum and the bitmap the emit kernel reads agree
             if (fw) {
                 const uint32_t f = w0 + wi < W ? fw[w0 + wi] : 0u;
-                word = from_filter ? f : word & f;
+                word = from_filter ? (w0 + wi < W ? f & fa.live[w0 + wi] : 0u) : word & f;
             }
         }
         if (w0 + wi < W && !from_filter) bm[w0 + wi] = word;
@@ -398,7 +401,7 @@ static __global__ __launch_bounds__(kScanBlock) void bitmap_count_kernel(const u
         const bool from_filter = fw && fa.all;
 #pragma unroll
         for (int j = 0; j < kWordsPerThread; ++j)
-            if (w0 + j < W) cnt += __popc(!fw ? bm[w0 + j] : from_filter ? fw[w0 + j] : bm[w0 + j] & fw[w0 + j]);
+            if (w0 + j < W) cnt += __popc(!fw ? bm[w0 + j] : from_filter ? fw[w0 + j] & fa.live[w0 + j] : bm[w0 + j] & fw[w0 + j]);
     } else {
 #pragma unroll
     for (int j = 0; j < kWordsPerThread; ++j)
@@ -447,7 +450,7 @@ static __global__ __launch_bounds__(kScanBlock) void bitmap_emit_kernel(uint32_t
         for (int j = 0; j < kWordsPerThread; ++j) {
             const bool in = w0 + j < W;
             marked[j] = in && !from_filter ? bm[w0 + j] : 0u;
-            w[j] = !fw ? marked[j] : !in ? 0u : from_filter ? fw[w0 + j] : marked[j] & fw[w0 + j];
+            w[j] = !fw ? marked[j] : !in ? 0u : from_filter ? fw[w0 + j] & fa.live[w0 + j] : marked[j] & fw[w0 + j];
             cnt += __popc(w[j]);
         }
     } else {
@@ -491,6 +494,21 @@ static __global__ __launch_bounds__(256) void filter_mark_kernel(const int64_t* 
     const int64_t p = pids[i] - pid_offset - 1;
     if (p < 0 || p >= (int64_t)n_docs) { atomicOr(err, 1); return; }
     atomicOr(&bits[p >> 5], 1u << (p & 31));
+}
+// The searcher's passages that hold at least one embedding, in the same layout (FilterArgs::live): one thread per word.
+static __global__ __launch_bounds__(256) void passage_live_kernel(const uint32_t* __restrict__ doc_off, int n_docs,
+                                                                  uint32_t* __restrict__ bits) {
+    const int w = blockIdx.x * 256 + threadIdx.x;
+    if (w >= (n_docs + 31) / 32) return;
+    uint32_t x = 0;
+    const int p0 = w * 32, n = min(32, n_docs - p0);
+    uint32_t at = doc_off[p0];
+    for (int i = 0; i < n; ++i) {
+        const uint32_t next = doc_off[p0 + i + 1];
+        x |= (uint32_t)(next != at) << i;
+        at = next;
+    }
+    bits[w] = x;
 }
 // ... and its population count, after clearing the bits past n_docs in the last word (a caller's bitmap is not trusted with
 // them: the emit kernel reads doc_off[pid + 1] of every set bit).  Grid-stride; one atomic per wave.

@@ -142,8 +142,8 @@ class Searcher:
     # -- ingest: append passages to the resident index (clb_searcher_append) ---------------------------
     @property
     def generation(self) -> int:
-        """Number of appends that changed this searcher (0 after the constructor).  A HIP graph captured over the searcher,
-        and every PassageFilter, belongs to the generation it was made in."""
+        """Number of appends and removals that changed this searcher (0 after the constructor).  A HIP graph captured over
+        the searcher belongs to the generation it was made in; a PassageFilter outlives removals, not appends."""
         return int(lib().clb_searcher_generation(self._h))
 
     def add_compressed(self, codes, residuals, doclens, persist: bool = False) -> range:
@@ -186,6 +186,24 @@ class Searcher:
         if persist and dl.size:
             storage.append_chunk(self.index_path, co, r, dl)
         return range(first, self.pid_offset + self.num_docs + 1)
+
+    def remove_passages(self, pids, persist: bool = False) -> int:
+        """Remove passages from the resident index without rebuilding it (clb_searcher_remove); returns how many lost
+        embeddings.  `pids` as `search` returns them (1-based, this searcher's pid_offset included; any order, duplicates
+        allowed; outside the searcher's passages: BoundsError).  Pids are stable: a removed passage stays in the numbering
+        as an empty passage, `num_docs` does not change, and a later add numbers from `num_docs + 1` as before.  Afterwards
+        every search answers as a Searcher made from the reduced index would; filters made before stay valid.  If the call
+        raises, the searcher is unchanged.  `persist`: also rewrite the index directory the searcher was opened from
+        (storage.remove_passages), after the device call has succeeded."""
+        if persist and self.index_path is None:
+            raise ColBERTError("persist=True needs a Searcher opened from an index_path")
+        p = np.ascontiguousarray(np.asarray(pids).reshape(-1), dtype=np.int64)
+        n = i64(0)
+        check(lib().clb_searcher_remove(self._h, fptr(p), i64(p.size), C.byref(n)))
+        self.num_embeddings = int(lib().clb_searcher_num_embeddings(self._h))
+        if persist and n.value:
+            storage.remove_passages(self.index_path, p - self.pid_offset)
+        return int(n.value)
 
     def _index_codec(self):
         """The index's own codec, resident (codec.Codec): built on first use from the centroids and bucket_cutoffs the
@@ -455,7 +473,7 @@ class TextSearch:
 
     def _prepare(self):
         """Size the workspaces and (graph=True) capture the graph, for the searcher as it is now.  Run again whenever the
-        searcher's generation has moved: an append frees the arrays a captured graph points into and un-sizes the
+        searcher's generation has moved: an append or a removal frees the arrays a captured graph points into and un-sizes the
         workspaces, so the stale graph is dropped before anything is enqueued."""
         import torch
         self.graph = None
@@ -484,7 +502,7 @@ class TextSearch:
         ids, mask = tokenization.tensorize_queries(cfg.query_token, cfg.attend_to_mask_tokens, self.enc.tokenizer, [query], self.T)
         self.h_ids.numpy()[0, :] = ids[:, 0]
         self.h_mask.numpy()[0, :] = mask[:, 0]
-        if self.s.generation != self.generation:      # the searcher has grown since the capture
+        if self.s.generation != self.generation:      # the searcher has grown or shrunk since the capture
             self._prepare()
         with torch.cuda.stream(self.stream):
             self.d_ids.copy_(self.h_ids, non_blocking=True)

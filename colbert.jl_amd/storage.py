@@ -60,6 +60,7 @@ def load_json(index_path, name):
 
 def check_all_files_are_saved(index_path: str) -> bool:
     """_check_all_files_are_saved (collection_indexer.jl:299-340)"""
+    _finish_journal(index_path)
     if not os.path.isfile(os.path.join(index_path, "plan.json")):
         return False
     plan = load_json(index_path, "plan.json")
@@ -92,12 +93,133 @@ def merge_ivf(ivf, ivf_lengths, n_old_emb: int, new_codes):
     return out, old_len + add_len
 
 
+def remove_from_ivf(ivf, ivf_lengths, keep):
+    """The IVF of an index reduced to the embeddings with `keep[e - 1]` true (a boolean per embedding; ids 1-based): per
+    centroid the old list without the dropped ids, the rest renumbered by cumsum(keep) -- what `_build_ivf`
+    (collection_indexer.jl:349-353) gives on the reduced codes, because renumbering keeps the order of the ids.  Pure
+    numpy, no sort.  Returns (ivf, ivf_lengths)."""
+    ivf = np.asarray(ivf, dtype=np.int64); old_len = np.asarray(ivf_lengths, dtype=np.int64)
+    keep = np.asarray(keep)
+    if keep.dtype != np.bool_ or keep.ndim != 1:
+        raise ValueError("keep must be a boolean vector, one entry per embedding")
+    if ivf.size != int(old_len.sum()) or ivf.size != keep.size:
+        raise ValueError("length(ivf) must be equal to sum(ivf_lengths) and to length(keep)!")
+    new_id = np.cumsum(keep, dtype=np.int64)
+    stays = keep[ivf - 1]
+    before = np.concatenate([[0], np.cumsum(stays, dtype=np.int64)])      # kept entries in front of entry j
+    off = np.concatenate([[0], np.cumsum(old_len)])
+    return new_id[ivf[stays] - 1], (before[off[1:]] - before[off[:-1]]).astype(old_len.dtype)
+
+
+JOURNAL = "remove.journal.json"
+_TMP = ".rmtmp"
+_rename = os.replace        # one rename of a journal (its own name: what a test of an interrupted removal replaces)
+
+
+def _write_journal(index_path: str, renames) -> None:
+    """The journal of a removal: the (temporary name, final name) pairs, complete on disk before it has its name."""
+    save_json(index_path, JOURNAL + ".tmp", {"renames": [list(r) for r in renames]})
+    os.replace(os.path.join(index_path, JOURNAL + ".tmp"), os.path.join(index_path, JOURNAL))
+
+
+def _finish_journal(index_path: str) -> None:
+    """Finish the renames of a journal an interrupted remove_passages left behind.  A temporary file that is gone was
+    renamed already; the journal goes last."""
+    journal = os.path.join(index_path, JOURNAL)
+    if not os.path.isfile(journal):
+        return
+    for tmp, final in load_json(index_path, JOURNAL)["renames"]:
+        if os.path.isfile(os.path.join(index_path, tmp)):
+            _rename(os.path.join(index_path, tmp), os.path.join(index_path, final))
+    os.remove(journal)
+
+
+def remove_passages(index_path: str, pids) -> int:
+    """Make a removal (Searcher.remove_passages) part of the index directory; `pids` are the directory's own, 1-based, in
+    any order, duplicates allowed.  The passages stay in the numbering with doclen 0: the chunks that lose embeddings get
+    new `.codes`, `.residuals`, `doclens.i` and metadata `num_embeddings`, every chunk behind the first of them its new
+    `embedding_offset`, and ivf, ivf_lengths and plan.json (`num_embeddings`, `embeddings_offsets`) follow; the layout stays
+    the reference's.  Several files change, so: every new file is written under a temporary name, then ONE journal file
+    listing the renames, then the renames, then the journal is deleted.  Before the journal exists the directory reads as
+    the old index; once it exists every reader finishes the renames first (_finish_journal) and reads the new one.
+    That holds against an interrupted PROCESS: neither the staged files nor the journal are fsync'ed, so after a power
+    loss the file system may show a journal without the data it names.  Staged files that an interruption before the
+    journal left behind are deleted on entry (nothing reads them).
+    -> the number of passages that lost embeddings."""
+    _finish_journal(index_path)
+    for f in os.listdir(index_path):        # no journal names them: leftovers of a removal that never got that far
+        if f.endswith(_TMP) or f.endswith(_TMP + EXT):
+            os.remove(os.path.join(index_path, f))
+    plan = load_json(index_path, "plan.json")
+    n_chunks = int(plan["num_chunks"])
+    chunk = lambda i, kind: os.path.join(index_path, f"doclens.{i}" if kind == "doclens" else f"{i}.{kind}")
+    doclens = [np.asarray(_load(chunk(i, "doclens")), dtype=np.int64) for i in range(1, n_chunks + 1)]
+    codes = [_load(chunk(i, "codes")) for i in range(1, n_chunks + 1)]
+    n_docs = sum(d.size for d in doclens)
+    pids = np.unique(np.asarray(pids, dtype=np.int64).reshape(-1))
+    if pids.size and (pids[0] < 1 or pids[-1] > n_docs):
+        raise IndexError(f"pid outside 1..{n_docs}")
+    gone = np.zeros(n_docs, dtype=bool)
+    gone[pids - 1] = True
+    all_lens = np.concatenate(doclens) if doclens else np.zeros(0, np.int64)
+    gone &= all_lens > 0
+    if not gone.any():
+        return 0
+    keep = np.repeat(~gone, all_lens)
+    all_codes = np.concatenate(codes)
+    new_ivf, new_lens = remove_from_ivf(*_read_ivf(index_path, all_codes), keep)
+
+    renames = []
+
+    def arrays(name, a):            # under the temporary name; the journal will rename it
+        _save(os.path.join(index_path, name + _TMP), a)
+        renames.append((name + _TMP + EXT, name + EXT))
+
+    def json_file(name, obj):
+        save_json(index_path, name + _TMP, obj)
+        renames.append((name + _TMP, name))
+
+    p0 = e0 = 0                     # passages / OLD embeddings in front of the chunk
+    offsets, moved = [], False      # new 1-based embedding offset of every chunk; moved: a chunk before this one shrank
+    n_left = 0
+    for i in range(1, n_chunks + 1):
+        dl = doclens[i - 1]
+        g = gone[p0:p0 + dl.size]
+        meta = load_json(index_path, f"{i}.metadata.json")
+        offsets.append(n_left + 1)
+        changed = False
+        if moved and "embedding_offset" in meta:
+            meta["embedding_offset"] = n_left + 1
+            changed = True
+        if g.any():
+            k = keep[e0:e0 + codes[i - 1].size]
+            arrays(f"{i}.codes", np.asarray(codes[i - 1][k], dtype=np.uint32))
+            arrays(f"{i}.residuals", np.asfortranarray(_load(chunk(i, "residuals"))[:, k], dtype=np.uint8))
+            arrays(f"doclens.{i}", np.where(g, 0, dl).astype(np.int64))
+            meta["num_embeddings"] = int(k.sum())
+            changed = moved = True
+        if changed:
+            json_file(f"{i}.metadata.json", meta)
+        n_left += int(keep[e0:e0 + codes[i - 1].size].sum())
+        p0 += dl.size; e0 += codes[i - 1].size
+    arrays("ivf", new_ivf)
+    arrays("ivf_lengths", new_lens)
+    plan["num_embeddings"] = n_left
+    if "embeddings_offsets" in plan:
+        plan["embeddings_offsets"] = offsets
+    json_file("plan.json", plan)
+    _write_journal(index_path, renames)
+    _finish_journal(index_path)
+    return int(gone.sum())
+
+
 def append_chunk(index_path: str, codes, residuals, doclens) -> None:
     """Make appended passages (Searcher.add_compressed) part of the index directory: one more chunk behind the last.
     Order of the writes: the chunk's files; the merged ivf / ivf_lengths under temporary names, renamed into place;
     plan.json last (through a rename as well).  Until plan.json names the new chunk `load_index` and
     `check_all_files_are_saved` read the directory as the old index -- `load_index` drops the inverted-list entries of
     embeddings the plan does not know."""
+    _finish_journal(index_path)
     plan = load_json(index_path, "plan.json")
     codes = np.asarray(codes, dtype=np.uint32); doclens = np.asarray(doclens, dtype=np.int64)
     residuals = np.asfortranarray(residuals, dtype=np.uint8)
@@ -138,6 +260,7 @@ def _read_ivf(index_path: str, codes):
 
 def load_index(index_path: str) -> dict:
     """load_codec / load_doclens / load_compressed_embs (loaders.jl:10-38, 76-113) + ivf files."""
+    _finish_journal(index_path)
     plan = load_json(index_path, "plan.json")
     cfg = load_json(index_path, "config.json")
     codes, res, dl = [], [], []

@@ -14,8 +14,8 @@
  * retains a host pointer.  All device memory belongs to the library (handles are opaque).
  * Threading: every call is synchronous (results are in the output buffers on return) except the
  * *_device entry points, which enqueue on the given HIP stream.  One handle, one thread at a time.
- * clb_searcher_append / clb_searcher_append_device replace the handle's device arrays: they wait for the whole device on
- * entry and before the swap, and the caller must have no search of that handle in flight on another thread.
+ * clb_searcher_append / clb_searcher_append_device / clb_searcher_remove replace the handle's device arrays: they wait for the
+ * whole device on entry and before the swap, and the caller must have no search of that handle in flight on another thread.
  * Errors: every function returns 0 or a CLB_E* code; codes 1..4 map 1:1 onto the Julia exception the
  * reference throws in the same situation.  clb_last_error() returns a message for the calling thread.
  * There is NO CPU fallback: without a GPU every compute entry point fails with CLB_EHIP.
@@ -100,8 +100,30 @@ int clb_searcher_append(clb_searcher* s, int64_t n_new, const int64_t* doclens, 
  * for on entry, and the call returns with the append complete. */
 int clb_searcher_append_device(clb_searcher* s, int64_t n_new, const int64_t* doclens, int64_t n_new_emb,
                                const uint32_t* d_codes, const uint8_t* d_residuals, void* hip_stream);
-/* Number of appends that changed the handle (0 after create), its passages and its embeddings.  These return counts, not
- * CLB_* codes: a null handle gives -CLB_EARGUMENT (and the message in clb_last_error). */
+/* Remove passages from the resident index (no counterpart in the reference; upstream ColBERT's IndexUpdater.remove).  pids
+ * are as search returns them: 1-based with pid_offset added, n entries in any order, duplicates allowed.  Pids are stable: a
+ * removed passage stays in the numbering as an EMPTY passage (doclen 0, as create accepts one); n_docs, pid_offset and every
+ * other passage's pid are unchanged, and a later append numbers its passages from n_docs + 1 as before.  Naming a passage
+ * that is empty already is no error and does nothing for that pid.  *n_removed (may be null) receives the number of passages
+ * that lost at least one embedding in this call.
+ * Afterwards every entry point behaves bit for bit as on a handle made by clb_searcher_create from the reduced index: the same
+ * centroids and weights, doclens with the removed entries set to 0, codes / residuals with those passages' columns deleted,
+ * ivf = stable sortperm(reduced codes) (_build_ivf, collection_indexer.jl:349-353) -- a centroid's list is its old list
+ * without the removed passages' entries, in the old order.  Bound constants that were set or synced
+ * (clb_searcher_set_bound_consts) are never lowered; otherwise they are the reduced index's own.  What create derives from
+ * the index is derived again (pass 1's gather form returns to the choice by the code statistics); the mode and the other
+ * settings of the handle are kept.
+ * n = 0, or *n_removed = 0, is CLB_OK, changes nothing and does not bump the generation.
+ * Failure leaves the handle unchanged and searchable: CLB_EBOUNDS a pid outside pid_offset+1 .. pid_offset+n_docs (checked on
+ * the host before any device work); CLB_EARGUMENT a null handle, null pids with n > 0, or n < 0; CLB_ENOMEM.
+ * Memory, threading and invalidation are append's: the reduced arrays are built beside the old ones (the call transiently
+ * holds the old plus the reduced index and two words of scan scratch per old embedding); the call waits for the whole device
+ * on entry and again before the swap; all four workspace slots are sized again by the next search, a pending
+ * clb_search_shard_phase1 is dropped, and a HIP graph captured over this handle must be captured again (compare
+ * clb_searcher_generation).  A clb_filter made before the removal STAYS valid: n_docs, and so its bitmap, did not change. */
+int clb_searcher_remove(clb_searcher* s, const int64_t* pids, int64_t n, int64_t* n_removed);
+/* Number of appends and removals that changed the handle (0 after create), its passages and its embeddings.  These return
+ * counts, not CLB_* codes: a null handle gives -CLB_EARGUMENT (and the message in clb_last_error). */
 int64_t clb_searcher_generation(const clb_searcher* s);
 int64_t clb_searcher_num_docs(const clb_searcher* s);
 int64_t clb_searcher_num_embeddings(const clb_searcher* s);
@@ -210,7 +232,11 @@ int clb_searcher_set_bound_consts(clb_searcher* s, const float* consts /* 6 */);
  * it was made for, is created once and reused over any number of calls (one per tenant, say), and is never written by a
  * search.  It MUST outlive every call that uses it, including calls still enqueued on a stream or captured in a graph;
  * it may be destroyed before or after its searcher.  Creation synchronises (the population count is read back once);
- * searching with it does not.
+ * searching with it does not.  An append (n_docs changes) invalidates it; a removal does not: after clb_searcher_remove the
+ * handle answers with it as a fresh handle on the reduced index answers with the same bitmap, in both scopes (a
+ * passage without embeddings -- an empty passage of create, or one emptied by clb_searcher_remove -- holds nothing to score
+ * and is never a candidate: CLB_FILTER_ALL ranks the set's passages that hold embeddings, n_cand counts those, while
+ * clb_filter_count stays the population of the set).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct clb_filter clb_filter;
 /* pids as search returns them: 1-based with the searcher's pid_offset added, n entries in any order, duplicates allowed;

@@ -39,7 +39,16 @@ function _searcher_append(h::Ptr{Cvoid}, doclens::Vector{Int}, codes::Vector{UIn
     end
     nothing
 end
-"appends that changed the handle (0 after create) / its passages / its embeddings"
+"remove passages (pids as `search` returns them) from the handle (clb_searcher_remove); they stay in the numbering as empty passages -> how many lost embeddings; the handle is unchanged when this throws"
+function _searcher_remove(h::Ptr{Cvoid}, pids::Vector{Int})
+    n = Ref{Int64}(0)
+    GC.@preserve pids begin
+        _check(ccall((:clb_searcher_remove, libcolbert), Cint, (Ptr{Cvoid}, Ptr{Int64}, Int64, Ref{Int64}),
+            h, pids, length(pids), n))
+    end
+    Int(n[])
+end
+"appends and removals that changed the handle (0 after create) / its passages / its embeddings"
 _searcher_generation(h::Ptr{Cvoid}) = Int(ccall((:clb_searcher_generation, libcolbert), Int64, (Ptr{Cvoid},), h))
 _searcher_num_docs(h::Ptr{Cvoid}) = Int(ccall((:clb_searcher_num_docs, libcolbert), Int64, (Ptr{Cvoid},), h))
 _searcher_num_embeddings(h::Ptr{Cvoid}) = Int(ccall((:clb_searcher_num_embeddings, libcolbert), Int64, (Ptr{Cvoid},), h))

@@ -51,7 +51,18 @@ function add_compressed!(searcher::Searcher, codes::Vector{UInt32}, residuals::M
     searcher.num_documents = _searcher_num_docs(searcher.handle)
     first_pid:searcher.num_documents
 end
-"number of `add_compressed!` calls that changed the searcher"
+"""
+    remove_passages!(searcher, pids) -> Int
+
+Remove passages from the resident index without rebuilding it; `pids` as `search` returns them (any order, duplicates
+allowed; outside 1:num_documents is a BoundsError).  Pids are stable: a removed passage stays in the numbering as an empty
+passage, `num_documents` does not change and `add_compressed!` numbers from `num_documents + 1` as before.  Returns how many
+passages lost embeddings.  Afterwards `search` answers as a `Searcher` opened on the reduced index would; a `PassageFilter`
+made before the call stays valid.  On an exception the searcher is unchanged.  No counterpart in the reference (upstream
+ColBERT: IndexUpdater.remove).
+"""
+remove_passages!(searcher::Searcher, pids::Vector{Int}) = _searcher_remove(searcher.handle, pids)
+"number of `add_compressed!` / `remove_passages!` calls that changed the searcher"
 generation(searcher::Searcher) = _searcher_generation(searcher.handle)
 num_embeddings(searcher::Searcher) = _searcher_num_embeddings(searcher.handle)
 
