@@ -1830,8 +1830,10 @@ int clb_debug_scores(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe,
         CLB_TRY(rc);
     }
     launch_pass1(s, w, st, dQ, dim3(8 * 32), Bd, (int)T);
+    ApproxConsts ac = s->approx_consts;          // the bound a search of this table reports (launch_select)
+    ac.dc_max = bound_dc(s, w);
     hipLaunchKernelGGL(select_margin_kernel, dim3(1), dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), dQ,
-                       (int)T, (int)k, w.cand_cap, s->approx_consts, w.list.as<int>(), w.nlist.as<int>(),
+                       (int)T, (int)k, w.cand_cap, ac, w.list.as<int>(), w.nlist.as<int>(),
                        w.thresh.as<float>(), w.eps_pair.as<float>(), (const float*)nullptr, 0,
                        w.have_range ? (const float4*)w.tscale.as<float4>() : (const float4*)nullptr, w.cell8 ? 1 : 0);
     int nc = 0, nl = 0;

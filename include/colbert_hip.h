@@ -216,8 +216,8 @@ int clb_searcher_get_score_rows(const clb_searcher* s);
 int clb_searcher_set_centroid_products(clb_searcher* s, int n);
 int clb_searcher_get_centroid_products(const clb_searcher* s, float* max_f16_error);
 /* Constants of the two-pass error bound of this handle: consts[0] = max ||centroid||, [1] = sqrt(dim) * max |bucket
- * weight|, [2] = max over the shard's embeddings of 1/(||c + r|| + eps), [3] = max ||bf16-rounded residual vector||,
- * [4] = sqrt(dim) * max |w - bf16(w)|, [5] = the quantisation error of the packed inv_norm.  Sharded search with a global threshold (clb_search_shard_phase1/2) needs ONE
+ * weight|, [2] = max over the shard's embeddings of 1/(||c + r|| + eps), [3] = max ||fp16-rounded residual vector||,
+ * [4] = sqrt(dim) * max |w - fp16(w)|, [5] = the quantisation error of the packed inv_norm.  Sharded search with a global threshold (clb_search_shard_phase1/2) needs ONE
  * bound on every shard: take the element-wise maximum over the shards (an all-reduce MAX of six floats at load time)
  * and set it on each handle.  `set` never lowers a value. */
 int clb_searcher_get_bound_consts(const clb_searcher* s, float* consts /* 6 */);
