@@ -51,6 +51,7 @@ struct clb_encoder {
     // workspace
     DevBuf ids, mask, x, qkv, scores, ctx, hbuf, tmp, out, err, qmask, qlens, part, pkeep, prank, scan_tmp;
     DevBuf xp, ctxp, tmpp, hbp; // bf16 planes of the activations the Linear layers read (written by their producers)
+    DevBuf h_skip, h_out, h_lens, h_n, h_pos, h_rank, h_seq, h_cu;     // what the host-buffer entry points upload and read back
     DevBuf qkp, vtp;            // attention_f16_kernel's operands: Q | K planes (T x 2H, K-blocked) and V key-blocked (vt_index)
     int64_t vt_L = 0, vt_N = 0; // the shape vtp was last cleared for (key slots past L are never written: they must stay finite)
     // per-stage HIP-event timing (clb_encoder_profile_*): off in timed runs
@@ -143,11 +144,38 @@ void gemm(hipStream_t st, const float* A, const float* B, float* C, const float*
     }
 }
 
-// activations (T x K, fp32) x Linear weight (N x K, fp32) on the split-bf16 kernels (both operands are split into
-// bf16 planes while they are staged).  Falls back to the fp32 MFMA GEMM for shapes the kernel does not take.
 struct LnArgs { const float* gamma; const float* beta; float eps; };
-// small tiles (query batches): two LDS tile buffers, one barrier per step
+struct AttOut { uint16_t* qk; int64_t qk_plane; uint16_t* vt; int64_t vt_plane; int L, H, heads; const int32_t* seq; const int32_t* pos; };   // EPI_QKV_ATT targets
 
+// the pass that sums the K slices of a split product (plan_reduce names it for the Linears on planes)
+enum PlanReduce { PR_NONE = 0, PR_LN4 = 1, PR_LN3 = 2, PR_LN_WIDE = 3, PR_PLAIN = 4, PR_ATT = 5 };
+inline bool reduce_normalises(int pr) { return pr == PR_LN4 || pr == PR_LN3 || pr == PR_LN_WIDE; }
+// ln: the LayerNorm fused into the PR_LN* passes; after PR_PLAIN the caller's layernorm_kernel writes the planes, so that pass
+// gets none.  att: PR_ATT's targets.  Cp / c_plane / fmt: the planes of the output (null / 0 / 0 off the plane path)
+void launch_reduce(hipStream_t st, int pr, const float* part, int ks, int M, int N, float* C, const float* bias, const float* R,
+                   float scale, int epi, const LnArgs* ln, uint16_t* Cp, int64_t c_plane, int fmt, const AttOut* att) {
+#define CLB_REDUCE_LN(KERNEL_) hipLaunchKernelGGL(KERNEL_, dim3(M), dim3(256), 0, st, part, ks, (int64_t)M, N, C, bias, R, scale, epi, \
+                                                  ln->gamma, ln->beta, ln->eps, Cp, c_plane, fmt)
+    const dim3 flat(blocks_for((int64_t)M * N));
+    switch (pr) {
+    case PR_LN4: CLB_REDUCE_LN(gemm_splitk_reduce_ln4_kernel); break;
+    case PR_LN3: CLB_REDUCE_LN(gemm_splitk_reduce_ln_kernel<3>); break;
+    case PR_LN_WIDE: CLB_REDUCE_LN(gemm_splitk_reduce_ln_kernel<4>); break;
+    case PR_PLAIN:
+        hipLaunchKernelGGL(gemm_splitk_reduce_kernel, flat, dim3(256), 0, st, part, ks, (int64_t)M, N, C, bias, R, scale, epi,
+                           ln ? (uint16_t*)nullptr : Cp, c_plane, fmt);
+        break;
+    case PR_ATT:
+        hipLaunchKernelGGL(gemm_splitk_reduce_kernel, flat, dim3(256), 0, st, part, ks, (int64_t)M, N, (float*)nullptr, bias, R, scale, epi,
+                           att->qk, att->qk_plane, fmt, att->vt, att->vt_plane, att->L, att->H, att->heads, att->seq, att->pos);
+        break;
+    default: break;     // PR_NONE
+    }
+#undef CLB_REDUCE_LN
+}
+
+// activations (T x K, fp32) x Linear weight (N x K, fp32) on the split-bf16 kernels (both operands are split into
+// bf16 planes while they are staged).
 // ln != null: the caller applies a LayerNorm to the output next; returns true when it was applied here (split-K path:
 // fused into the reduction pass)
 template <int NS>
@@ -165,6 +193,7 @@ bool linear_split(hipStream_t st, Gemm3Args g, float* part, const LnArgs* ln) {
                           2 * NS * (64 + 128) * 64);
         hipLaunchKernelGGL((gemm_bf16split_kernel<2, 2, 1, 2, NS, true>), dim3((N + 127) / 128, (M + 63) / 64, 1), dim3(256), 2 * lds(64, 128), st, g);
     } else {
+        // small tiles (query batches): two LDS tile buffers, one barrier per step
         int ks = 1;
         if (part) {
             // K slices of at least 256 (192 for the few-tile outputs such as the hidden -> dim projection of a query batch)
@@ -174,26 +203,16 @@ bool linear_split(hipStream_t st, Gemm3Args g, float* part, const LnArgs* ln) {
         float* C = g.C;
         if (ks > 1) { g.ksplit = ks; g.C = part; }
         hipLaunchKernelGGL((gemm_bf16split_kernel<2, 2, 1, 1, NS, true>), dim3((N + 63) / 64, (M + 63) / 64, ks), dim3(256), 2 * lds(64, 64), st, g);
-        if (ks > 1) {
-            if (ln && N <= 1024) {
-                if (N <= 768)
-                    hipLaunchKernelGGL(gemm_splitk_reduce_ln_kernel<3>, dim3(M), dim3(256), 0, st, part, ks, (int64_t)M, N,
-                                       C, g.bias, g.R, 1.0f, g.epi, ln->gamma, ln->beta, ln->eps);
-                else
-                    hipLaunchKernelGGL(gemm_splitk_reduce_ln_kernel<4>, dim3(M), dim3(256), 0, st, part, ks, (int64_t)M, N,
-                                       C, g.bias, g.R, 1.0f, g.epi, ln->gamma, ln->beta, ln->eps);
-                return true;
-            }
-            hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks_for((int64_t)M * N)), dim3(256), 0, st, part, ks,
-                               (int64_t)M, N, C, g.bias, g.R, 1.0f, g.epi);
-        }
+        // (the strided LayerNorm passes whatever N % 4 is: plan_reduce's four-column pass sums mean and variance in another order)
+        const int pr = ks <= 1 ? PR_NONE : !(ln && N <= 1024) ? PR_PLAIN : N <= 768 ? PR_LN3 : PR_LN_WIDE;
+        launch_reduce(st, pr, part, ks, M, N, C, g.bias, g.R, 1.0f, g.epi, ln, nullptr, 0, 0, nullptr);
+        return reduce_normalises(pr);
     }
     return false;
 }
 
 // ---- Linear layers on pre-split bf16 planes (gemm_planes2_kernel) ---------------------------------------------------
 struct PlanCfg { int bm, bn, stages, ks; };
-struct AttOut { uint16_t* qk; int64_t qk_plane; uint16_t* vt; int64_t vt_plane; int L, H, heads; const int32_t* seq; const int32_t* pos; };   // EPI_QKV_ATT targets
 // a packed batch: N sequences back to back without padding rows (device arrays: position and sequence of every row, row offsets)
 // `pos`: index of the position embedding; `rank` (null = pos): the row's rank inside its sequence, which is what the attention
 // kernel and the key-blocked V buffer go by -- they differ when a mask has holes (host path), not for prefix masks
@@ -343,8 +362,6 @@ static int plan_flags(const PlanIn& p) {
            (p.fold_stats ? CLB_PLAN_FOLD_STATS : 0) | (p.fold_u ? CLB_PLAN_FOLD_U : 0);
 }
 
-// the pass that sums the K slices of a split product
-enum PlanReduce { PR_NONE = 0, PR_LN4 = 1, PR_LN3 = 2, PR_LN_WIDE = 3, PR_PLAIN = 4, PR_ATT = 5 };
 static int plan_reduce(const PlanIn& p, const PlanCfg& c) {
     if (c.ks <= 1) return PR_NONE;
     if (p.ln && p.N <= 1024) return p.N % 4 == 0 ? PR_LN4 : p.N <= 768 ? PR_LN3 : PR_LN_WIDE;
@@ -354,7 +371,7 @@ static int plan_reduce(const PlanIn& p, const PlanCfg& c) {
 // A planes (M x K) . W planes (N x K)^T -> C fp32 and / or Cp planes, epilogue bias / GELU / residual, optional LayerNorm
 // of the output (then both C and, if given, Cp hold the normalised rows).  part: split-K scratch (8 * M * N floats) or null.
 // wscale: the power of two the weight planes were scaled by (PF_F16X2; 1 otherwise)
-void linear_planes(clb_encoder* e, hipStream_t st, const uint16_t* Ap, int64_t a_plane, const uint16_t* Wp, float wscale,
+int linear_planes(clb_encoder* e, hipStream_t st, const uint16_t* Ap, int64_t a_plane, const uint16_t* Wp, float wscale,
                    float* C, uint16_t* Cp, int64_t c_plane, const float* bias, const float* R, int M, int N, int K, int epi,
                    float* part, const LnArgs* ln, const AttOut* att = nullptr, const LnFold* lf = nullptr, int64_t b_plane = 0) {
     const int fmt = plane_format(e->gemm_mode);
@@ -363,6 +380,9 @@ void linear_planes(clb_encoder* e, hipStream_t st, const uint16_t* Ap, int64_t a
     const PlanIn pin{e->gemm_mode, M, N, K, epi, part != nullptr, ln != nullptr, att != nullptr, lf != nullptr,
                      lf && lf->stats_out, lf && lf->u};
     PlanCfg c = plan_linear(pin);
+    const int pr = plan_reduce(pin, c);
+    // (a LayerNorm follows a Linear whose N is a multiple of 4 here -- create sets `planes` only then: never the strided passes)
+    if (pr == PR_LN3 || pr == PR_LN_WIDE) return fail(CLB_EUNSUPPORTED, "no split-K LayerNorm pass on planes for N = %d", N);
     if (lf) part = nullptr;
     GemmPArgs g{Ap, Wp, a_plane, b_plane ? b_plane : e->wp_plane, C, bias, R, Cp, c_plane, M, N, K, N, epi, c.ks, out_scale};
     if (lf) {
@@ -382,34 +402,16 @@ void linear_planes(clb_encoder* e, hipStream_t st, const uint16_t* Ap, int64_t a
         return fmt == PF_F16X2 ? launch_planes<2, true>(st, cc, g) : NS == 2 ? launch_planes<2, false>(st, cc, g) : launch_planes<3, false>(st, cc, g);
     };
     if (!go(c)) {
-        if (lf) { (void)fail(CLB_EUNSUPPORTED, "no LayerNorm-folding GEMM for a %d x %d tile", c.bm, c.bn); return; }
+        if (lf) return fail(CLB_EUNSUPPORTED, "no LayerNorm-folding GEMM for a %d x %d tile", c.bm, c.bn);
         c = {64, 64, 2, c.ks}; (void)go(c);
     }
-    e->plan_log.push_back({e->cur_stage, {e->cur_layer, M, N, K, c.bm, c.bn, c.stages, c.ks, plan_reduce(pin, c),
+    e->plan_log.push_back({e->cur_stage, {e->cur_layer, M, N, K, c.bm, c.bn, c.stages, c.ks, pr,
                                           plan_flags(pin) | (e->cur_packed ? CLB_PLAN_PACKED : 0), epi}});
-    if (c.ks > 1) {
-        if (ln && N <= 1024) {
-            if (N % 4 == 0)
-                hipLaunchKernelGGL(gemm_splitk_reduce_ln4_kernel, dim3(M), dim3(256), 0, st, part, c.ks, (int64_t)M, N, C, bias, R,
-                                   out_scale, epi, ln->gamma, ln->beta, ln->eps, Cp, c_plane, fmt);
-            else if (N <= 768)
-                hipLaunchKernelGGL(gemm_splitk_reduce_ln_kernel<3>, dim3(M), dim3(256), 0, st, part, c.ks, (int64_t)M, N, C, bias, R,
-                                   out_scale, epi, ln->gamma, ln->beta, ln->eps, Cp, c_plane, fmt);
-            else
-                hipLaunchKernelGGL(gemm_splitk_reduce_ln_kernel<4>, dim3(M), dim3(256), 0, st, part, c.ks, (int64_t)M, N, C, bias, R,
-                                   out_scale, epi, ln->gamma, ln->beta, ln->eps, Cp, c_plane, fmt);
-            return;
-        }
-        if (att)
-            hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks_for((int64_t)M * N)), dim3(256), 0, st, part, c.ks, (int64_t)M, N,
-                               (float*)nullptr, bias, R, out_scale, epi, att->qk, att->qk_plane, fmt, att->vt, att->vt_plane, att->L, att->H,
-                               att->heads, att->seq, att->pos);
-        else
-        hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(blocks_for((int64_t)M * N)), dim3(256), 0, st, part, c.ks, (int64_t)M, N,
-                           C, bias, R, out_scale, epi, ln ? (uint16_t*)nullptr : Cp, c_plane, fmt);
-    }
-    if (ln) hipLaunchKernelGGL(layernorm_kernel, dim3(blocks_for(M, 4)), dim3(256), 0, st, C, (int64_t)M, N, ln->gamma, ln->beta,
-                               ln->eps, Cp, c_plane, fmt);
+    launch_reduce(st, pr, part, c.ks, M, N, C, bias, R, out_scale, epi, ln, Cp, c_plane, fmt, att);
+    if (ln && !reduce_normalises(pr))
+        hipLaunchKernelGGL(layernorm_kernel, dim3(blocks_for(M, 4)), dim3(256), 0, st, C, (int64_t)M, N, ln->gamma, ln->beta,
+                           ln->eps, Cp, c_plane, fmt);
+    return CLB_OK;
 }
 
 // Linear (+ optional LayerNorm of the output, in place)
@@ -424,6 +426,23 @@ void linear(clb_encoder* e, hipStream_t st, const float* A, const float* Wt, flo
         if (done) return;
     }
     if (ln) hipLaunchKernelGGL(layernorm_kernel, dim3(blocks_for(M, 4)), dim3(256), 0, st, C, (int64_t)M, N, ln->gamma, ln->beta, ln->eps);
+}
+
+// PF_F16X2: per matrix, the power of two that brings its largest |entry| -- `mx`: the n max-abs bit patterns the max_abs kernels
+// left on the device -- into [2^13, 2^14)
+int pow2_scales(hipStream_t st, const DevBuf& mx, size_t n, std::vector<float>& scales) {
+    std::vector<unsigned int> bits(n);
+    CLB_HIP(hipMemcpyAsync(bits.data(), mx.p, sizeof(unsigned int) * n, hipMemcpyDeviceToHost, st));
+    CLB_HIP(hipStreamSynchronize(st));
+    scales.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        float m;
+        memcpy(&m, &bits[i], sizeof m);
+        int ex = 0;
+        if (m > 0.f && m <= FLT_MAX) (void)std::frexp(m, &ex);          // m = f * 2^ex, f in [0.5, 1)
+        scales[i] = std::ldexp(1.0f, std::max(-100, std::min(100, 14 - ex)));   // m * scale in [2^13, 2^14)
+    }
+    return CLB_OK;
 }
 
 // Every Linear weight (N x K, torch layout) into K-blocked planes of format `fmt` at its own blob offset.  PF_F16X2: each
@@ -449,16 +468,9 @@ int split_weights(clb_encoder* e, int fmt) {
         for (size_t i = 0; i < mats.size(); ++i)
             hipLaunchKernelGGL(max_abs_kernel, dim3(256), dim3(256), 0, st, e->weights.as<float>() + mats[i].off,
                                (int)(mats[i].rows * mats[i].cols), mx.as<unsigned int>() + i);
-        std::vector<unsigned int> bits(mats.size());
-        CLB_HIP(hipMemcpyAsync(bits.data(), mx.p, sizeof(unsigned int) * mats.size(), hipMemcpyDeviceToHost, st));
-        CLB_HIP(hipStreamSynchronize(st));
-        for (size_t i = 0; i < mats.size(); ++i) {
-            float m;
-            memcpy(&m, &bits[i], sizeof m);
-            int ex = 0;
-            if (m > 0.f && m <= FLT_MAX) (void)std::frexp(m, &ex);          // m = f * 2^ex, f in [0.5, 1)
-            e->wscale[i] = std::ldexp(1.0f, std::max(-100, std::min(100, 14 - ex)));   // m * scale in [2^13, 2^14)
-        }
+        std::vector<float> scales;
+        CLB_TRY(pow2_scales(st, mx, mats.size(), scales));
+        std::copy(scales.begin(), scales.end(), e->wscale.begin());
     }
     for (size_t i = 0; i < mats.size(); ++i)
         hipLaunchKernelGGL(split_planes_kernel, dim3(blocks_for(mats[i].rows * mats[i].cols / 4)), dim3(256), 0, st,
@@ -505,16 +517,8 @@ int split_weights(clb_encoder* e, int fmt) {
             for (size_t i = 0; i < folds.size(); ++i)
                 hipLaunchKernelGGL(max_abs_colscaled_kernel, dim3(256), dim3(256), 0, st, W + folds[i].w_off, folds[i].rows, (int)H,
                                    W + folds[i].g_off, mx.as<unsigned int>() + i);
-            std::vector<unsigned int> bits(folds.size());
-            CLB_HIP(hipMemcpyAsync(bits.data(), mx.p, sizeof(unsigned int) * folds.size(), hipMemcpyDeviceToHost, st));
-            CLB_HIP(hipStreamSynchronize(st));
-            e->wscale_f.assign(folds.size(), 1.0f);
+            CLB_TRY(pow2_scales(st, mx, folds.size(), e->wscale_f));
             for (size_t i = 0; i < folds.size(); ++i) {
-                float m;
-                memcpy(&m, &bits[i], sizeof m);
-                int ex = 0;
-                if (m > 0.f && m <= FLT_MAX) (void)std::frexp(m, &ex);
-                e->wscale_f[i] = std::ldexp(1.0f, std::max(-100, std::min(100, 14 - ex)));
                 hipLaunchKernelGGL(split_planes_kernel, dim3(blocks_for(folds[i].rows * H / 4)), dim3(256), 0, st, W + folds[i].w_off,
                                    e->wplanes_f.as<uint16_t>() + folds[i].p_off, folds[i].rows, (int)H, po, fmt, e->wscale_f[i],
                                    W + folds[i].g_off);
@@ -533,8 +537,6 @@ int split_weights(clb_encoder* e, int fmt) {
 // index into wscale_f (the order split_weights folds in): Q/K/V of layer l >= 1, FFN-in of layer l, the projection last
 static inline size_t fold_scale_index(int64_t l, int which /* 0 = Q/K/V (l >= 1), 1 = FFN-in */) { return (size_t)(l == 0 ? 0 : 2 * l - 1 + which); }
 
-// forward for N sequences of length L; ids / mask are device pointers; result in e->out ((N*L) x dim).
-// sync = false: everything is only enqueued on `st` (an out-of-vocabulary id is then clamped silently).
 // whether a batch of at most `rows_max` rows and sequences up to L can run packed (the conditions of the fp16-plane attention)
 static bool can_pack(const clb_encoder* e, int64_t L, int64_t rows_max = 0) {
     const int64_t H = e->H, I = e->I;
@@ -542,9 +544,20 @@ static bool can_pack(const clb_encoder* e, int64_t L, int64_t rows_max = 0) {
            e->attention_mode == 0 && rows_max * std::max(H, I) * 6 < ((int64_t)1 << 31);
 }
 
+// the attention kernel of a layer.  kind: 0 = fp16 planes (attention_f16_kernel, `qblocks` query blocks of 32 per wave: long
+// sequences share a key tile's K / V fragments between two), 1 = fp32 online softmax, 2 = fp32 register-resident, 3 = three kernels
+struct AttPlan { int kind, qblocks; };
+static AttPlan plan_attention(bool fused, bool att16, int64_t L, int attention_mode) {
+    if (!fused) return {3, 0};
+    if (att16) return {0, L >= 128 ? 2 : 1};
+    return {L > 64 && attention_mode != 1 ? 1 : 2, 0};
+}
+
+// forward for N sequences of length L; ids / mask are device pointers; result in e->out ((N*L) x dim).  Everything is only
+// enqueued on `st`: an out-of-vocabulary id is clamped and left in the sticky flag (read_flag).
 // pk (packed batch): d_ids holds pk->rows token ids, L is the longest sequence, d_mask is unused; needs the fp16-plane attention.
 int forward(clb_encoder* e, int64_t L, int64_t N, hipStream_t st, const int32_t* d_ids, const uint8_t* d_mask,
-            bool sync = true, const Packed* pk = nullptr) {
+            const Packed* pk = nullptr) {
     const int64_t T = pk ? pk->rows : L * N, H = e->H, I = e->I, heads = e->heads, dh = H / heads;
     const float* W = e->weights.as<float>();
     e->plan_log.clear(); e->cur_layer = -1; e->cur_packed = pk != nullptr;
@@ -632,31 +645,28 @@ int forward(clb_encoder* e, int64_t L, int64_t N, hipStream_t st, const int32_t*
         { EncTimed tm(e, ES_QKV, st);
         if (fold && l >= 1) {   // x holds the RAW output of the previous FFN-out: its LayerNorm is folded into this product
             const LnFold lf{st2, ln_parts, 64, e->eps, LV + e->v_qkv[l], nullptr, nullptr, nullptr};
-            linear_planes(e, st, xp, hp, WPF + e->f_qkv[l], e->wscale_f[fold_scale_index(l, 0)], qkv, nullptr, 0, LV + e->v_qkv[l] + 3 * H, nullptr,
-                          (int)T, (int)(3 * H), (int)H, EPI_BIAS, nullptr, nullptr, att16 ? &att_out : nullptr, &lf, e->wpf_plane);
+            CLB_TRY(linear_planes(e, st, xp, hp, WPF + e->f_qkv[l], e->wscale_f[fold_scale_index(l, 0)], qkv, nullptr, 0, LV + e->v_qkv[l] + 3 * H, nullptr,
+                          (int)T, (int)(3 * H), (int)H, EPI_BIAS, nullptr, nullptr, att16 ? &att_out : nullptr, &lf, e->wpf_plane));
         }
-        else if (P) linear_planes(e, st, xp, hp, wp(lo + e->r_wqkv), ws(l, 0), qkv, nullptr, 0, P_ + e->r_bqkv, nullptr, (int)T, (int)(3 * H),
-                             (int)H, EPI_BIAS, part_wide, nullptr, att16 ? &att_out : nullptr);
+        else if (P) CLB_TRY(linear_planes(e, st, xp, hp, wp(lo + e->r_wqkv), ws(l, 0), qkv, nullptr, 0, P_ + e->r_bqkv, nullptr, (int)T, (int)(3 * H),
+                             (int)H, EPI_BIAS, part_wide, nullptr, att16 ? &att_out : nullptr));
         else linear(e, st, x, P_ + e->r_wqkv, qkv, P_ + e->r_bqkv, nullptr, (int)T, (int)(3 * H), (int)H, EPI_BIAS, nullptr); }
-        EncTimed* t_att = new EncTimed(e, ES_ATTENTION, st);
-        if (fused) {
-            // softmax(Q K^T / sqrt(dh) + mask) V, one wave per (sequence, head, 32 queries), scores never leave registers
-            const dim3 grid((unsigned)((L + 31) / 32), (unsigned)heads, (unsigned)N);
-            uint16_t* cp_ = P ? ctxp : nullptr;
+        const AttPlan ap = plan_attention(fused, att16, L, e->attention_mode);
+        { EncTimed tm(e, ES_ATTENTION, st);
+        // fused: softmax(Q K^T / sqrt(dh) + mask) V, one wave per (sequence, head, 32 * qblocks queries), scores never leave registers
+        const dim3 grid((unsigned)((L + 31) / 32), (unsigned)heads, (unsigned)N), grid2((unsigned)((L + 63) / 64), (unsigned)heads, (unsigned)N);
+        uint16_t* cp_ = P ? ctxp : nullptr;
 #define CLB_ATT(NT_) hipLaunchKernelGGL(attention_fused_kernel<NT_>, grid, dim3(64), 0, st, qkv, d_mask, ctx, (int)L, (int)H, inv_sqrt, cp_, hp, PF)
-            if (att16 && L >= 128) {     // long sequences: two query blocks per wave share a key tile's K / V fragments
-                const dim3 grid2((unsigned)((L + 63) / 64), (unsigned)heads, (unsigned)N);
-                hipLaunchKernelGGL(attention_f16_kernel<2>, grid2, dim3(64), 0, st, att_out.qk, qk_plane, T, att_out.vt, vt_plane, d_mask, (int)L,
-                                   (int)H, inv_sqrt, ctxp, hp, PF, pk ? pk->cu : nullptr);
-            } else if (att16)
-                hipLaunchKernelGGL(attention_f16_kernel<1>, grid, dim3(64), 0, st, att_out.qk, qk_plane, T, att_out.vt, vt_plane, d_mask, (int)L,
-                                   (int)H, inv_sqrt, ctxp, hp, PF, pk ? pk->cu : nullptr);
-            else if (L > 64 && e->attention_mode != 1)
-                hipLaunchKernelGGL(attention_online_kernel, grid, dim3(64), 0, st, qkv, d_mask, ctx, (int)L, (int)H, inv_sqrt, cp_, hp, PF);
-            else if (L <= 32) CLB_ATT(1); else if (L <= 64) CLB_ATT(2); else if (L <= 128) CLB_ATT(4); else if (L <= 192) CLB_ATT(6);
+#define CLB_ATT16(QB_, GRID_) hipLaunchKernelGGL(attention_f16_kernel<QB_>, GRID_, dim3(64), 0, st, att_out.qk, qk_plane, T, att_out.vt, vt_plane, \
+                                                 d_mask, (int)L, (int)H, inv_sqrt, ctxp, hp, PF, pk ? pk->cu : nullptr)
+        switch (ap.kind) {
+        case 0: if (ap.qblocks == 2) CLB_ATT16(2, grid2); else CLB_ATT16(1, grid); break;
+        case 1: hipLaunchKernelGGL(attention_online_kernel, grid, dim3(64), 0, st, qkv, d_mask, ctx, (int)L, (int)H, inv_sqrt, cp_, hp, PF); break;
+        case 2:
+            if (L <= 32) CLB_ATT(1); else if (L <= 64) CLB_ATT(2); else if (L <= 128) CLB_ATT(4); else if (L <= 192) CLB_ATT(6);
             else if (L <= 256) CLB_ATT(8); else if (L <= 320) CLB_ATT(10); else if (L <= 384) CLB_ATT(12); else CLB_ATT(16);
-#undef CLB_ATT
-        } else {
+            break;
+        default:
             // scores[n, head] = Q K^T / sqrt(dh)
             gemm(st, qkv, qkv + H, sc, nullptr, nullptr, (int)L, (int)L, (int)dh, 3 * H, 3 * H, 1, L, 0, inv_sqrt, (int)N, (int)heads,
                  L * 3 * H, dh, L * 3 * H, dh, heads * L * L, L * L);
@@ -667,42 +677,42 @@ int forward(clb_encoder* e, int64_t L, int64_t N, hipStream_t st, const int32_t*
                  heads * L * L, L * L, L * 3 * H, dh, L * H, dh);
             if (P) hipLaunchKernelGGL(split_planes_kernel, dim3(blocks_for(hp / 4)), dim3(256), 0, st, ctx, ctxp, T, (int)H, hp, PF, kF16ActScale);
         }
-        delete t_att;
-        {   // the attention kernel of this layer: query blocks of 32 per wave (fp16 planes), key tiles, kind
-            const int kind = !fused ? 3 : att16 ? 0 : (L > 64 && e->attention_mode != 1) ? 1 : 2;
-            e->plan_log.push_back({ES_ATTENTION, {l, T, L, dh, att16 ? (L >= 128 ? 2 : 1) : 0, (L + 31) / 32, 0, 0, 0,
-                                                  (att16 ? CLB_PLAN_ATT : 0) | (pk ? CLB_PLAN_PACKED : 0), kind}});
+#undef CLB_ATT16
+#undef CLB_ATT
         }
+        // its plan record: query blocks of 32 per wave (fp16 planes), key tiles, kind
+        e->plan_log.push_back({ES_ATTENTION, {l, T, L, dh, ap.qblocks, (L + 31) / 32, 0, 0, 0,
+                                              (att16 ? CLB_PLAN_ATT : 0) | (pk ? CLB_PLAN_PACKED : 0), ap.kind}});
         // attention output + residual, LayerNorm
         const LnArgs ln1{P_ + e->r_g1, P_ + e->r_b1n, e->eps}, ln2{P_ + e->r_g2, P_ + e->r_b2n, e->eps};
         { EncTimed tm(e, ES_ATTN_OUT, st);
         if (fold) {     // raw rows + their partial statistics; the residual is x, raw too from layer 1 on (normalised on the fly)
             const LnFold lf{l >= 1 ? st2 : nullptr, ln_parts, 64, e->eps, nullptr, l >= 1 ? Pp_ + e->r_g2 : nullptr, l >= 1 ? Pp_ + e->r_b2n : nullptr, st1};
-            linear_planes(e, st, ctxp, hp, wp(lo + e->r_wo), ws(l, 1), tmp, tmpp, hp, P_ + e->r_bo, x, (int)T, (int)H, (int)H,
-                          EPI_BIAS | EPI_RESID, nullptr, nullptr, nullptr, &lf);
+            CLB_TRY(linear_planes(e, st, ctxp, hp, wp(lo + e->r_wo), ws(l, 1), tmp, tmpp, hp, P_ + e->r_bo, x, (int)T, (int)H, (int)H,
+                          EPI_BIAS | EPI_RESID, nullptr, nullptr, nullptr, &lf));
         }
-        else if (P) linear_planes(e, st, ctxp, hp, wp(lo + e->r_wo), ws(l, 1), tmp, tmpp, hp, P_ + e->r_bo, x, (int)T, (int)H, (int)H,
-                             EPI_BIAS | EPI_RESID, part, &ln1);
+        else if (P) CLB_TRY(linear_planes(e, st, ctxp, hp, wp(lo + e->r_wo), ws(l, 1), tmp, tmpp, hp, P_ + e->r_bo, x, (int)T, (int)H, (int)H,
+                             EPI_BIAS | EPI_RESID, part, &ln1));
         else linear(e, st, ctx, P_ + e->r_wo, tmp, P_ + e->r_bo, x, (int)T, (int)H, (int)H, EPI_BIAS | EPI_RESID, part, &ln1); }
         // feed-forward: GELU(x W1^T + b1) W2^T + b2 + residual, LayerNorm.  On the plane path the (T x I) intermediate
         // exists only as the bf16 planes the second Linear reads
         { EncTimed tm(e, ES_FFN_IN, st);
         if (fold) {
             const LnFold lf{st1, ln_parts, 64, e->eps, LV + e->v_w1[l], nullptr, nullptr, nullptr};
-            linear_planes(e, st, tmpp, hp, WPF + e->f_w1[l], e->wscale_f[fold_scale_index(l, 1)], nullptr, hbp, ip, LV + e->v_w1[l] + I, nullptr,
-                          (int)T, (int)I, (int)H, EPI_BIAS | EPI_GELU, nullptr, nullptr, nullptr, &lf, e->wpf_plane);
+            CLB_TRY(linear_planes(e, st, tmpp, hp, WPF + e->f_w1[l], e->wscale_f[fold_scale_index(l, 1)], nullptr, hbp, ip, LV + e->v_w1[l] + I, nullptr,
+                          (int)T, (int)I, (int)H, EPI_BIAS | EPI_GELU, nullptr, nullptr, nullptr, &lf, e->wpf_plane));
         }
-        else if (P) linear_planes(e, st, tmpp, hp, wp(lo + e->r_w1), ws(l, 2), nullptr, hbp, ip, P_ + e->r_b1, nullptr, (int)T, (int)I, (int)H,
-                             EPI_BIAS | EPI_GELU, part_wide, nullptr);
+        else if (P) CLB_TRY(linear_planes(e, st, tmpp, hp, wp(lo + e->r_w1), ws(l, 2), nullptr, hbp, ip, P_ + e->r_b1, nullptr, (int)T, (int)I, (int)H,
+                             EPI_BIAS | EPI_GELU, part_wide, nullptr));
         else linear(e, st, tmp, P_ + e->r_w1, hb, P_ + e->r_b1, nullptr, (int)T, (int)I, (int)H, EPI_BIAS | EPI_GELU, nullptr); }
         { EncTimed tm(e, ES_FFN_OUT, st);
         if (fold) {     // the residual is the raw attention-output row: its (first) LayerNorm is applied on the fly
             const LnFold lf{st1, ln_parts, 64, e->eps, nullptr, P_ + e->r_g1, P_ + e->r_b1n, st2};
-            linear_planes(e, st, hbp, ip, wp(lo + e->r_w2), ws(l, 3), x, xp, hp, P_ + e->r_b2, tmp, (int)T, (int)H, (int)I,
-                          EPI_BIAS | EPI_RESID, nullptr, nullptr, nullptr, &lf);
+            CLB_TRY(linear_planes(e, st, hbp, ip, wp(lo + e->r_w2), ws(l, 3), x, xp, hp, P_ + e->r_b2, tmp, (int)T, (int)H, (int)I,
+                          EPI_BIAS | EPI_RESID, nullptr, nullptr, nullptr, &lf));
         }
-        else if (P) linear_planes(e, st, hbp, ip, wp(lo + e->r_w2), ws(l, 3), x, xp, hp, P_ + e->r_b2, tmp, (int)T, (int)H, (int)I,
-                             EPI_BIAS | EPI_RESID, part, &ln2);
+        else if (P) CLB_TRY(linear_planes(e, st, hbp, ip, wp(lo + e->r_w2), ws(l, 3), x, xp, hp, P_ + e->r_b2, tmp, (int)T, (int)H, (int)I,
+                             EPI_BIAS | EPI_RESID, part, &ln2));
         else linear(e, st, hb, P_ + e->r_w2, x, P_ + e->r_b2, tmp, (int)T, (int)H, (int)I, EPI_BIAS | EPI_RESID, part, &ln2); }
     }
     // ColBERT projection: Layers.Dense(hidden -> dim)
@@ -710,32 +720,25 @@ int forward(clb_encoder* e, int64_t L, int64_t N, hipStream_t st, const int32_t*
     { EncTimed tm(e, ES_PROJECTION, st);
     if (fold) {         // x holds the raw output of the last FFN-out
         const LnFold lf{st2, ln_parts, 64, e->eps, LV + e->v_lin, nullptr, nullptr, nullptr};
-        linear_planes(e, st, xp, hp, WPF + e->f_lin, e->wscale_f.back(), e->out.as<float>(), nullptr, 0, LV + e->v_lin + e->dim, nullptr, (int)T,
-                      (int)e->dim, (int)H, EPI_BIAS, nullptr, nullptr, nullptr, &lf, e->wpf_plane);
+        CLB_TRY(linear_planes(e, st, xp, hp, WPF + e->f_lin, e->wscale_f.back(), e->out.as<float>(), nullptr, 0, LV + e->v_lin + e->dim, nullptr, (int)T,
+                      (int)e->dim, (int)H, EPI_BIAS, nullptr, nullptr, nullptr, &lf, e->wpf_plane));
     }
-    else if (P) linear_planes(e, st, xp, hp, wp(e->o_lin_w), ws(e->layers, 0), e->out.as<float>(), nullptr, 0, W + e->o_lin_b, nullptr, (int)T,
-                         (int)e->dim, (int)H, EPI_BIAS, part, nullptr);
+    else if (P) CLB_TRY(linear_planes(e, st, xp, hp, wp(e->o_lin_w), ws(e->layers, 0), e->out.as<float>(), nullptr, 0, W + e->o_lin_b, nullptr, (int)T,
+                         (int)e->dim, (int)H, EPI_BIAS, part, nullptr));
     else linear(e, st, x, W + e->o_lin_w, e->out.as<float>(), W + e->o_lin_b, nullptr, (int)T, (int)e->dim, (int)H, EPI_BIAS, part); }
     CLB_HIP(hipGetLastError());
-    if (!sync) return CLB_OK;
+    return CLB_OK;
+}
+
+// Waits for `st`, then reads, clears and decodes the sticky flag the encode kernels OR their findings into: bit 0 = a token id
+// outside the vocabulary (embed_layernorm_kernel clamped it), bit 1 = a non-finite output row (the epilogue kernels).  The one
+// reader: a host-buffer entry point calls it once, after everything is enqueued; clb_encoder_check_last_ids on request.
+int read_flag(clb_encoder* e, hipStream_t st) {
     int herr = 0;
     CLB_HIP(hipMemcpyAsync(&herr, e->err.p, sizeof(int), hipMemcpyDeviceToHost, st));
     CLB_HIP(hipMemsetAsync(e->err.p, 0, sizeof(int), st));
     CLB_HIP(hipStreamSynchronize(st));
     if (herr & 1) return fail(CLB_EBOUNDS, "token id outside the vocabulary (ids are 1-based, 1..%lld)", (long long)e->vocab);
-    // bit 2 can only have been left by an EARLIER asynchronous encode nobody has checked yet (this call's epilogue has not run):
-    // it was read and cleared with bit 1 above, so it is reported here rather than dropped
-    if (herr & 2) return fail(CLB_EDOMAIN, "non-finite encoder output in an earlier asynchronous encode on this handle (an activation "
-                                           "outside the range of the f16 operand split? clb_encoder_set_gemm_mode(e, 2) selects bf16x6)");
-    return CLB_OK;
-}
-
-// waits for `st`, then reads and clears the non-finite-output bit of the sticky flag (set by the epilogue kernels)
-int finish_checked(clb_encoder* e, hipStream_t st) {
-    int herr = 0;
-    CLB_HIP(hipMemcpyAsync(&herr, e->err.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    CLB_HIP(hipMemsetAsync(e->err.p, 0, sizeof(int), st));
-    CLB_HIP(hipStreamSynchronize(st));
     if (herr & 2) return fail(CLB_EDOMAIN, "non-finite encoder output (an activation outside the range of the f16 operand split? "
                                            "clb_encoder_set_gemm_mode(e, 2) selects the bf16x6 split)");
     return CLB_OK;
@@ -773,16 +776,109 @@ __global__ void packed_normalize_kernel(const float* __restrict__ D, int dim, in
     for (int d = 0; d < dim; ++d) o[d] = x[d] / den;
 }
 
-int upload_inputs(clb_encoder* e, const int32_t* ids, const uint8_t* mask, int64_t L, int64_t N) {
-    if (!e) return fail(CLB_EARGUMENT, "null encoder");
+// The argument checks every encode entry point starts with; makes the encoder's device current.  ptrs_ok: no pointer argument
+// of the call is null -- the host-buffer entry points check only their handle and say so (null_text).  rows: the batch is packed
+// into that many rows, L being its longest sequence
+int check_batch(const clb_encoder* e, bool ptrs_ok, const char* null_text, int64_t L, int64_t N, const int64_t* rows = nullptr) {
+    if (!e || !ptrs_ok) return fail(CLB_EARGUMENT, "%s", null_text);
+    if (rows && (N < 1 || L < 1 || *rows < N || *rows > N * L)) return fail(CLB_EARGUMENT, "packed batch: N >= 1, N <= rows <= N * Lmax");
     if (L < 1 || N < 1) return fail(CLB_EARGUMENT, "empty batch");
     if (L > e->max_pos) return fail(CLB_EBOUNDS, "sequence length %lld exceeds max_position_embeddings %lld", (long long)L, (long long)e->max_pos);
-    CLB_TRY(use_device(e->device));
-    CLB_TRY(e->ids.ensure(sizeof(int32_t) * L * N));
-    CLB_TRY(e->mask.ensure((size_t)L * N));
-    CLB_HIP(hipMemcpyAsync(e->ids.p, ids, sizeof(int32_t) * L * N, hipMemcpyHostToDevice, e->stream));
-    CLB_HIP(hipMemcpyAsync(e->mask.p, mask, (size_t)L * N, hipMemcpyHostToDevice, e->stream));
+    return use_device(e->device);
+}
+
+// ---- one enqueue function per output form: forward + epilogue on `st`, device pointers only, nothing is waited for.  The device
+// entry points call them on the caller's stream, the host-buffer ones on e->stream over workspaces of the handle.
+// _query_embeddings (checkpoint.jl:54-71): d_out (dim, L, N)
+int enqueue_queries(clb_encoder* e, hipStream_t st, const int32_t* d_ids, const uint8_t* d_mask, int64_t L, int64_t N,
+                    const int64_t* d_skip, int64_t n_skip, float* d_out) {
+    CLB_TRY(e->qmask.ensure((size_t)L * N));
+    CLB_TRY(e->qlens.ensure(sizeof(int64_t) * N));
+    CLB_TRY(forward(e, L, N, st, d_ids, d_mask));
+    {
+        EncTimed tm(e, ES_EPILOGUE, st);
+        if (e->dim % 4 == 0)
+            hipLaunchKernelGGL(epilogue_query_fused_kernel, dim3(blocks_for(L * N * 4, 256)), dim3(256), 0, st, e->out.as<float>(),
+                               (int)e->dim, (int64_t)(L * N), d_ids, d_skip, (int)n_skip, d_out, e->err.as<int>());
+        else {
+            hipLaunchKernelGGL(epilogue_mask_kernel, dim3(blocks_for(N, 64)), dim3(64), 0, st, d_ids, (int)L, (int)N, d_skip, (int)n_skip,
+                               e->qmask.as<uint8_t>(), e->qlens.as<int64_t>());
+            hipLaunchKernelGGL(epilogue_normalize_kernel, dim3(blocks_for(L * N, 64)), dim3(64), 0, st, e->out.as<float>(), (int)e->dim,
+                               (int)L, (int)N, e->qmask.as<uint8_t>(), (const int64_t*)nullptr, d_out, e->err.as<int>());
+        }
+    }
+    CLB_HIP(hipGetLastError());
     return CLB_OK;
+}
+
+// _doc_embeddings_and_doclens (checkpoint.jl:27-52) of a padded (L, N) batch: d_out_embs has room for (dim, L * N), the first
+// *d_n_out columns are written
+int enqueue_docs(clb_encoder* e, hipStream_t st, const int32_t* d_ids, const uint8_t* d_mask, int64_t L, int64_t N,
+                 const int64_t* d_skip, int64_t n_skip, float* d_out_embs, int64_t* d_doclens, int64_t* d_n_out) {
+    CLB_TRY(e->qmask.ensure((size_t)L * N));
+    CLB_TRY(e->qlens.ensure(sizeof(int64_t) * N));          // here: the exclusive scan of the document lengths
+    CLB_TRY(forward(e, L, N, st, d_ids, d_mask));
+    {
+        EncTimed tm(e, ES_EPILOGUE, st);
+        hipLaunchKernelGGL(epilogue_mask_kernel, dim3(blocks_for(N, 64)), dim3(64), 0, st, d_ids, (int)L, (int)N, d_skip, (int)n_skip,
+                           e->qmask.as<uint8_t>(), d_doclens);
+        hipLaunchKernelGGL(doclens_scan_kernel, dim3(1), dim3(64), 0, st, d_doclens, (int)N, e->qlens.as<int64_t>(), d_n_out);
+        hipLaunchKernelGGL(epilogue_normalize_kernel, dim3(blocks_for(L * N, 64)), dim3(64), 0, st, e->out.as<float>(), (int)e->dim,
+                           (int)L, (int)N, e->qmask.as<uint8_t>(), e->qlens.as<int64_t>(), d_out_embs, e->err.as<int>());
+    }
+    CLB_HIP(hipGetLastError());
+    return CLB_OK;
+}
+
+// the same of a packed batch (d_ids: pk.rows token ids, Lmax the longest sequence): d_out_embs has room for (dim, pk.rows)
+int enqueue_docs_packed(clb_encoder* e, hipStream_t st, const int32_t* d_ids, const Packed& pk, int64_t Lmax, int64_t N,
+                        const int64_t* d_skip, int64_t n_skip, float* d_out_embs, int64_t* d_doclens, int64_t* d_n_out) {
+    const int64_t rows = pk.rows;
+    CLB_TRY(e->pkeep.ensure(sizeof(uint32_t) * (rows + 1)));
+    CLB_TRY(e->prank.ensure(sizeof(uint32_t) * (rows + 1)));
+    CLB_TRY(forward(e, Lmax, N, st, d_ids, nullptr, &pk));
+    {
+        EncTimed tm(e, ES_EPILOGUE, st);
+        hipLaunchKernelGGL(packed_keep_kernel, dim3(blocks_for(rows + 1, 256)), dim3(256), 0, st, d_ids, rows, d_skip, (int)n_skip,
+                           e->pkeep.as<uint32_t>());
+        CLB_TRY(exclusive_scan_u32(e->pkeep.as<uint32_t>(), e->prank.as<uint32_t>(), (size_t)rows, st, &e->scan_tmp));
+        hipLaunchKernelGGL(packed_doclens_kernel, dim3(blocks_for(N, 64)), dim3(64), 0, st, e->prank.as<uint32_t>(), pk.cu, (int)N, d_doclens,
+                           d_n_out);
+        hipLaunchKernelGGL(packed_normalize_kernel, dim3(blocks_for(rows, 64)), dim3(64), 0, st, e->out.as<float>(), (int)e->dim, rows,
+                           e->pkeep.as<uint32_t>(), e->prank.as<uint32_t>(), d_out_embs, e->err.as<int>());
+    }
+    CLB_HIP(hipGetLastError());
+    return CLB_OK;
+}
+
+// ---- the host-buffer entry points: upload into workspaces of the handle (on e->stream), enqueue, read the flag ONCE, copy out
+int upload_to(clb_encoder* e, DevBuf& b, const void* host, size_t bytes) {
+    CLB_TRY(b.ensure(bytes));
+    if (bytes) CLB_HIP(hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, e->stream));
+    return CLB_OK;
+}
+int upload_inputs(clb_encoder* e, const int32_t* ids, const uint8_t* mask, int64_t L, int64_t N, const int64_t* skiplist = nullptr,
+                  int64_t n_skip = 0) {
+    CLB_TRY(upload_to(e, e->ids, ids, sizeof(int32_t) * L * N));
+    CLB_TRY(upload_to(e, e->mask, mask, (size_t)L * N));
+    return upload_to(e, e->h_skip, skiplist, sizeof(int64_t) * n_skip);
+}
+int download(clb_encoder* e, void* host, const DevBuf& b, size_t bytes) {
+    if (bytes) CLB_HIP(hipMemcpyAsync(host, b.p, bytes, hipMemcpyDeviceToHost, e->stream));
+    CLB_HIP(hipStreamSynchronize(e->stream));
+    return CLB_OK;
+}
+// the two document forms write h_out (room for `rows` embeddings), h_lens and h_n; n_out and doclens are copied out first
+int ensure_doc_outputs(clb_encoder* e, int64_t rows, int64_t N) {
+    CLB_TRY(e->h_out.ensure(sizeof(float) * e->dim * rows));
+    CLB_TRY(e->h_lens.ensure(sizeof(int64_t) * N));
+    return e->h_n.ensure(sizeof(int64_t));
+}
+int finish_docs(clb_encoder* e, int64_t N, float* out_embs, int64_t* doclens, int64_t* n_out) {
+    CLB_TRY(read_flag(e, e->stream));
+    CLB_HIP(hipMemcpyAsync(n_out, e->h_n.p, sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+    CLB_TRY(download(e, doclens, e->h_lens, sizeof(int64_t) * N));
+    return download(e, out_embs, e->h_out, sizeof(float) * e->dim * (*n_out));
 }
 
 }  // namespace
@@ -892,8 +988,10 @@ int clb_encoder_set_attention_mode(clb_encoder* e, int mode) {
 }
 
 int clb_encode(clb_encoder* e, const int32_t* integer_ids, const uint8_t* bitmask, int64_t L, int64_t N, float* out) {
+    CLB_TRY(check_batch(e, true, "null encoder", L, N));
     CLB_TRY(upload_inputs(e, integer_ids, bitmask, L, N));
     CLB_TRY(forward(e, L, N, e->stream, e->ids.as<int32_t>(), e->mask.as<uint8_t>()));
+    CLB_TRY(read_flag(e, e->stream));
     CLB_HIP(hipMemcpy(out, e->out.p, sizeof(float) * L * N * e->dim, hipMemcpyDeviceToHost));
     return CLB_OK;
 }
@@ -901,10 +999,10 @@ int clb_encode(clb_encoder* e, const int32_t* integer_ids, const uint8_t* bitmas
 // The host entry point packs its batch itself when it may: every unattended token must be one the skiplist drops (the [PAD]
 // padding of tensorize_docs is; a caller's own mask need not be) and the encoder must be able to (can_pack) -- then the rows
 // the output never sees are not computed.  Attended tokens keep their positions, so any mask shape packs, not only prefixes.
+// *done stays false when the batch has to take the padded path.
 static int encode_docs_packed_host(clb_encoder* e, const int32_t* ids, const uint8_t* mask, int64_t L, int64_t N, const int64_t* skiplist,
                                    int64_t n_skip, float* out_embs, int64_t* doclens, int64_t* n_out, bool* done) {
     *done = false;
-    if (L * N < 1) return CLB_OK;
     std::vector<int32_t> pid, ppos, pseq, cu((size_t)N + 1, 0);      // ids, positions and sequence of every attended row; row offsets
     pid.reserve((size_t)L * N); ppos.reserve((size_t)L * N); pseq.reserve((size_t)L * N);
     for (int64_t n = 0; n < N; ++n) {
@@ -928,176 +1026,72 @@ static int encode_docs_packed_host(clb_encoder* e, const int32_t* ids, const uin
         for (int32_t r = cu[(size_t)n]; r < cu[(size_t)n + 1]; ++r) prank[(size_t)r] = r - cu[(size_t)n];
         longest = std::max<int64_t>(longest, cu[(size_t)n + 1] - cu[(size_t)n]);
     }
-    hipStream_t st = e->stream;
-    DevBuf dIds, dPos, dRank, dSeq, dCu, dSkip, dOut, dLens, dN;
-    CLB_TRY(upload(dIds, pid.data(), sizeof(int32_t) * rows, st));
-    CLB_TRY(upload(dPos, ppos.data(), sizeof(int32_t) * rows, st));
-    CLB_TRY(upload(dRank, prank.data(), sizeof(int32_t) * rows, st));
-    CLB_TRY(upload(dSeq, pseq.data(), sizeof(int32_t) * rows, st));
-    CLB_TRY(upload(dCu, cu.data(), sizeof(int32_t) * (N + 1), st));
-    CLB_TRY(upload(dSkip, skiplist, sizeof(int64_t) * std::max<int64_t>(n_skip, 1), st));
-    CLB_TRY(dOut.alloc(sizeof(float) * e->dim * rows));
-    CLB_TRY(dLens.alloc(sizeof(int64_t) * N));
-    CLB_TRY(dN.alloc(sizeof(int64_t)));
-    CLB_TRY(e->pkeep.ensure(sizeof(uint32_t) * (rows + 1)));
-    CLB_TRY(e->prank.ensure(sizeof(uint32_t) * (rows + 1)));
-    const Packed pk{dPos.as<int32_t>(), dSeq.as<int32_t>(), dCu.as<int32_t>(), rows, dRank.as<int32_t>()};
-    CLB_TRY(forward(e, longest, N, st, dIds.as<int32_t>(), nullptr, /*sync=*/true, &pk));
-    hipLaunchKernelGGL(packed_keep_kernel, dim3(blocks_for(rows + 1, 256)), dim3(256), 0, st, dIds.as<int32_t>(), rows, dSkip.as<int64_t>(),
-                       (int)n_skip, e->pkeep.as<uint32_t>());
-    CLB_TRY(exclusive_scan_u32(e->pkeep.as<uint32_t>(), e->prank.as<uint32_t>(), (size_t)rows, st, &e->scan_tmp));
-    hipLaunchKernelGGL(packed_doclens_kernel, dim3(blocks_for(N, 64)), dim3(64), 0, st, e->prank.as<uint32_t>(), dCu.as<int32_t>(), (int)N,
-                       dLens.as<int64_t>(), dN.as<int64_t>());
-    hipLaunchKernelGGL(packed_normalize_kernel, dim3(blocks_for(rows, 64)), dim3(64), 0, st, e->out.as<float>(), (int)e->dim, rows,
-                       e->pkeep.as<uint32_t>(), e->prank.as<uint32_t>(), dOut.as<float>(), e->err.as<int>());
-    CLB_HIP(hipGetLastError());
-    CLB_HIP(hipMemcpyAsync(doclens, dLens.p, sizeof(int64_t) * N, hipMemcpyDeviceToHost, st));
-    CLB_HIP(hipMemcpyAsync(n_out, dN.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    CLB_HIP(hipStreamSynchronize(st));
-    if (*n_out > 0) CLB_HIP(hipMemcpyAsync(out_embs, dOut.p, sizeof(float) * e->dim * (*n_out), hipMemcpyDeviceToHost, st));
+    CLB_TRY(upload_to(e, e->ids, pid.data(), sizeof(int32_t) * rows));
+    CLB_TRY(upload_to(e, e->h_pos, ppos.data(), sizeof(int32_t) * rows));
+    CLB_TRY(upload_to(e, e->h_rank, prank.data(), sizeof(int32_t) * rows));
+    CLB_TRY(upload_to(e, e->h_seq, pseq.data(), sizeof(int32_t) * rows));
+    CLB_TRY(upload_to(e, e->h_cu, cu.data(), sizeof(int32_t) * (N + 1)));
+    CLB_TRY(upload_to(e, e->h_skip, skiplist, sizeof(int64_t) * n_skip));
+    CLB_TRY(ensure_doc_outputs(e, rows, N));
+    const Packed pk{e->h_pos.as<int32_t>(), e->h_seq.as<int32_t>(), e->h_cu.as<int32_t>(), rows, e->h_rank.as<int32_t>()};
+    CLB_TRY(enqueue_docs_packed(e, e->stream, e->ids.as<int32_t>(), pk, longest, N, e->h_skip.as<int64_t>(), n_skip, e->h_out.as<float>(),
+                                e->h_lens.as<int64_t>(), e->h_n.as<int64_t>()));
     *done = true;
-    return finish_checked(e, st);
+    return finish_docs(e, N, out_embs, doclens, n_out);
 }
 
 int clb_encode_docs(clb_encoder* e, const int32_t* integer_ids, const uint8_t* bitmask, int64_t L, int64_t N,
                     const int64_t* skiplist, int64_t n_skip, float* out_embs, int64_t* doclens, int64_t* n_out) {
-    if (e && integer_ids && bitmask && skiplist && out_embs && doclens && n_out && L >= 1 && N >= 1 && L <= e->max_pos && can_pack(e, L, L * N)) {
-        CLB_TRY(use_device(e->device));
+    CLB_TRY(check_batch(e, true, "null encoder", L, N));
+    if (can_pack(e, L, L * N)) {
         bool done = false;
         CLB_TRY(encode_docs_packed_host(e, integer_ids, bitmask, L, N, skiplist, n_skip, out_embs, doclens, n_out, &done));
         if (done) return CLB_OK;
     }
-    CLB_TRY(upload_inputs(e, integer_ids, bitmask, L, N));
-    CLB_TRY(forward(e, L, N, e->stream, e->ids.as<int32_t>(), e->mask.as<uint8_t>()));
-    hipStream_t st = e->stream;
-    DevBuf dSkip, dMask, dLens, dStart, dOut;
-    CLB_TRY(upload(dSkip, skiplist, sizeof(int64_t) * std::max<int64_t>(n_skip, 1), st));
-    CLB_TRY(dMask.alloc((size_t)L * N));
-    CLB_TRY(dLens.alloc(sizeof(int64_t) * N));
-    hipLaunchKernelGGL(epilogue_mask_kernel, dim3(blocks_for(N, 64)), dim3(64), 0, st, e->ids.as<int32_t>(), (int)L, (int)N,
-                       dSkip.as<int64_t>(), (int)n_skip, dMask.as<uint8_t>(), dLens.as<int64_t>());
-    CLB_HIP(hipMemcpyAsync(doclens, dLens.p, sizeof(int64_t) * N, hipMemcpyDeviceToHost, st));
-    CLB_HIP(hipStreamSynchronize(st));
-    std::vector<int64_t> start((size_t)N);
-    int64_t run = 0;
-    for (int64_t i = 0; i < N; ++i) { start[i] = run; run += doclens[i]; }
-    *n_out = run;
-    if (run == 0) return CLB_OK;
-    CLB_TRY(upload(dStart, start.data(), sizeof(int64_t) * N, st));
-    CLB_TRY(dOut.alloc(sizeof(float) * e->dim * run));
-    hipLaunchKernelGGL(epilogue_normalize_kernel, dim3(blocks_for(L * N, 64)), dim3(64), 0, st, e->out.as<float>(), (int)e->dim,
-                       (int)L, (int)N, dMask.as<uint8_t>(), dStart.as<int64_t>(), dOut.as<float>(), e->err.as<int>());
-    CLB_HIP(hipGetLastError());
-    CLB_HIP(hipMemcpyAsync(out_embs, dOut.p, sizeof(float) * e->dim * run, hipMemcpyDeviceToHost, st));
-    return finish_checked(e, st);
+    CLB_TRY(upload_inputs(e, integer_ids, bitmask, L, N, skiplist, n_skip));
+    CLB_TRY(ensure_doc_outputs(e, L * N, N));
+    CLB_TRY(enqueue_docs(e, e->stream, e->ids.as<int32_t>(), e->mask.as<uint8_t>(), L, N, e->h_skip.as<int64_t>(), n_skip, e->h_out.as<float>(),
+                         e->h_lens.as<int64_t>(), e->h_n.as<int64_t>()));
+    return finish_docs(e, N, out_embs, doclens, n_out);
 }
 
 int clb_encode_queries(clb_encoder* e, const int32_t* integer_ids, const uint8_t* bitmask, int64_t L, int64_t N,
                        const int64_t* skiplist, int64_t n_skip, float* out) {
-    CLB_TRY(upload_inputs(e, integer_ids, bitmask, L, N));
-    CLB_TRY(forward(e, L, N, e->stream, e->ids.as<int32_t>(), e->mask.as<uint8_t>()));
-    hipStream_t st = e->stream;
-    DevBuf dSkip, dMask, dLens, dOut;
-    CLB_TRY(upload(dSkip, skiplist, sizeof(int64_t) * std::max<int64_t>(n_skip, 1), st));
-    CLB_TRY(dMask.alloc((size_t)L * N));
-    CLB_TRY(dLens.alloc(sizeof(int64_t) * N));
-    CLB_TRY(dOut.alloc(sizeof(float) * e->dim * L * N));
-    hipLaunchKernelGGL(epilogue_mask_kernel, dim3(blocks_for(N, 64)), dim3(64), 0, st, e->ids.as<int32_t>(), (int)L, (int)N,
-                       dSkip.as<int64_t>(), (int)n_skip, dMask.as<uint8_t>(), dLens.as<int64_t>());
-    hipLaunchKernelGGL(epilogue_normalize_kernel, dim3(blocks_for(L * N, 64)), dim3(64), 0, st, e->out.as<float>(), (int)e->dim,
-                       (int)L, (int)N, dMask.as<uint8_t>(), (const int64_t*)nullptr, dOut.as<float>(), e->err.as<int>());
-    CLB_HIP(hipGetLastError());
-    CLB_HIP(hipMemcpyAsync(out, dOut.p, sizeof(float) * e->dim * L * N, hipMemcpyDeviceToHost, st));
-    return finish_checked(e, st);
+    CLB_TRY(check_batch(e, true, "null encoder", L, N));
+    CLB_TRY(upload_inputs(e, integer_ids, bitmask, L, N, skiplist, n_skip));
+    CLB_TRY(e->h_out.ensure(sizeof(float) * e->dim * L * N));
+    CLB_TRY(enqueue_queries(e, e->stream, e->ids.as<int32_t>(), e->mask.as<uint8_t>(), L, N, e->h_skip.as<int64_t>(), n_skip, e->h_out.as<float>()));
+    CLB_TRY(read_flag(e, e->stream));
+    return download(e, out, e->h_out, sizeof(float) * e->dim * L * N);
 }
 
 int clb_encode_queries_device(clb_encoder* e, const int32_t* d_integer_ids, const uint8_t* d_bitmask, int64_t L, int64_t N,
                               const int64_t* d_skiplist, int64_t n_skip, float* d_out, void* hip_stream) {
-    if (!e || !d_integer_ids || !d_bitmask || !d_out) return fail(CLB_EARGUMENT, "null argument");
-    if (L < 1 || N < 1) return fail(CLB_EARGUMENT, "empty batch");
-    if (L > e->max_pos) return fail(CLB_EBOUNDS, "sequence length %lld exceeds max_position_embeddings %lld", (long long)L, (long long)e->max_pos);
-    CLB_TRY(use_device(e->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    CLB_TRY(e->qmask.ensure((size_t)L * N));
-    CLB_TRY(e->qlens.ensure(sizeof(int64_t) * N));
-    CLB_TRY(forward(e, L, N, st, d_integer_ids, d_bitmask, /*sync=*/false));
-    {
-        EncTimed tm(e, ES_EPILOGUE, st);
-        if (e->dim % 4 == 0)
-            hipLaunchKernelGGL(epilogue_query_fused_kernel, dim3(blocks_for(L * N * 4, 256)), dim3(256), 0, st, e->out.as<float>(),
-                               (int)e->dim, (int64_t)(L * N), d_integer_ids, d_skiplist, (int)n_skip, d_out, e->err.as<int>());
-        else {
-            hipLaunchKernelGGL(epilogue_mask_kernel, dim3(blocks_for(N, 64)), dim3(64), 0, st, d_integer_ids, (int)L, (int)N,
-                               d_skiplist, (int)n_skip, e->qmask.as<uint8_t>(), e->qlens.as<int64_t>());
-            hipLaunchKernelGGL(epilogue_normalize_kernel, dim3(blocks_for(L * N, 64)), dim3(64), 0, st, e->out.as<float>(), (int)e->dim,
-                               (int)L, (int)N, e->qmask.as<uint8_t>(), (const int64_t*)nullptr, d_out);
-        }
-    }
-    CLB_HIP(hipGetLastError());
-    return CLB_OK;
+    CLB_TRY(check_batch(e, d_integer_ids && d_bitmask && d_out, "null argument", L, N));
+    return enqueue_queries(e, (hipStream_t)hip_stream, d_integer_ids, d_bitmask, L, N, d_skiplist, n_skip, d_out);
 }
 
 int clb_encode_docs_device(clb_encoder* e, const int32_t* d_integer_ids, const uint8_t* d_bitmask, int64_t L, int64_t N,
                            const int64_t* d_skiplist, int64_t n_skip, float* d_out_embs, int64_t* d_doclens, int64_t* d_n_out,
                            void* hip_stream) {
-    if (!e || !d_integer_ids || !d_bitmask || !d_out_embs || !d_doclens || !d_n_out) return fail(CLB_EARGUMENT, "null argument");
-    if (L < 1 || N < 1) return fail(CLB_EARGUMENT, "empty batch");
-    if (L > e->max_pos) return fail(CLB_EBOUNDS, "sequence length %lld exceeds max_position_embeddings %lld", (long long)L, (long long)e->max_pos);
-    CLB_TRY(use_device(e->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    CLB_TRY(e->qmask.ensure((size_t)L * N));
-    CLB_TRY(e->qlens.ensure(sizeof(int64_t) * N));          // here: the exclusive scan of the document lengths
-    CLB_TRY(forward(e, L, N, st, d_integer_ids, d_bitmask, /*sync=*/false));
-    {
-        EncTimed tm(e, ES_EPILOGUE, st);
-        hipLaunchKernelGGL(epilogue_mask_kernel, dim3(blocks_for(N, 64)), dim3(64), 0, st, d_integer_ids, (int)L, (int)N, d_skiplist,
-                           (int)n_skip, e->qmask.as<uint8_t>(), d_doclens);
-        hipLaunchKernelGGL(doclens_scan_kernel, dim3(1), dim3(64), 0, st, d_doclens, (int)N, e->qlens.as<int64_t>(), d_n_out);
-        hipLaunchKernelGGL(epilogue_normalize_kernel, dim3(blocks_for(L * N, 64)), dim3(64), 0, st, e->out.as<float>(), (int)e->dim,
-                           (int)L, (int)N, e->qmask.as<uint8_t>(), e->qlens.as<int64_t>(), d_out_embs, e->err.as<int>());
-    }
-    CLB_HIP(hipGetLastError());
-    return CLB_OK;
+    CLB_TRY(check_batch(e, d_integer_ids && d_bitmask && d_out_embs && d_doclens && d_n_out, "null argument", L, N));
+    return enqueue_docs(e, (hipStream_t)hip_stream, d_integer_ids, d_bitmask, L, N, d_skiplist, n_skip, d_out_embs, d_doclens, d_n_out);
 }
 
 int clb_encode_docs_packed_device(clb_encoder* e, const int32_t* d_ids, const int32_t* d_pos, const int32_t* d_seq, const int32_t* d_cu,
                                   int64_t N, int64_t Lmax, int64_t rows, const int64_t* d_skiplist, int64_t n_skip, float* d_out_embs,
                                   int64_t* d_doclens, int64_t* d_n_out, void* hip_stream) {
-    if (!e || !d_ids || !d_pos || !d_seq || !d_cu || !d_out_embs || !d_doclens || !d_n_out) return fail(CLB_EARGUMENT, "null argument");
-    if (N < 1 || Lmax < 1 || rows < N || rows > N * Lmax) return fail(CLB_EARGUMENT, "packed batch: N >= 1, N <= rows <= N * Lmax");
-    if (Lmax > e->max_pos) return fail(CLB_EBOUNDS, "sequence length %lld exceeds max_position_embeddings %lld", (long long)Lmax, (long long)e->max_pos);
-    CLB_TRY(use_device(e->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    CLB_TRY(e->pkeep.ensure(sizeof(uint32_t) * (rows + 1)));
-    CLB_TRY(e->prank.ensure(sizeof(uint32_t) * (rows + 1)));
-    const Packed pk{d_pos, d_seq, d_cu, rows};
-    CLB_TRY(forward(e, Lmax, N, st, d_ids, nullptr, /*sync=*/false, &pk));
-    {
-        EncTimed tm(e, ES_EPILOGUE, st);
-        hipLaunchKernelGGL(packed_keep_kernel, dim3(blocks_for(rows + 1, 256)), dim3(256), 0, st, d_ids, rows, d_skiplist, (int)n_skip,
-                           e->pkeep.as<uint32_t>());
-        CLB_TRY(exclusive_scan_u32(e->pkeep.as<uint32_t>(), e->prank.as<uint32_t>(), (size_t)rows, st, &e->scan_tmp));
-        hipLaunchKernelGGL(packed_doclens_kernel, dim3(blocks_for(N, 64)), dim3(64), 0, st, e->prank.as<uint32_t>(), d_cu, (int)N, d_doclens,
-                           d_n_out);
-        hipLaunchKernelGGL(packed_normalize_kernel, dim3(blocks_for(rows, 64)), dim3(64), 0, st, e->out.as<float>(), (int)e->dim, rows,
-                           e->pkeep.as<uint32_t>(), e->prank.as<uint32_t>(), d_out_embs, e->err.as<int>());
-    }
-    CLB_HIP(hipGetLastError());
-    return CLB_OK;
+    CLB_TRY(check_batch(e, d_ids && d_pos && d_seq && d_cu && d_out_embs && d_doclens && d_n_out, "null argument", Lmax, N, &rows));
+    return enqueue_docs_packed(e, (hipStream_t)hip_stream, d_ids, Packed{d_pos, d_seq, d_cu, rows}, Lmax, N, d_skiplist, n_skip, d_out_embs,
+                               d_doclens, d_n_out);
 }
 
 int clb_encoder_check_last_ids(clb_encoder* e) {
     if (!e) return fail(CLB_EARGUMENT, "null encoder");
     if (!e->err.p) return CLB_OK;                     // nothing has been encoded yet
     CLB_TRY(use_device(e->device));
-    int herr = 0;
     CLB_HIP(hipDeviceSynchronize());                  // the asynchronous encode may run on any of the caller's streams
-    CLB_HIP(hipMemcpy(&herr, e->err.p, sizeof(int), hipMemcpyDeviceToHost));
-    CLB_HIP(hipMemset(e->err.p, 0, sizeof(int)));     // sticky until read: covers EVERY encode since the previous check
-    if (herr & 1) return fail(CLB_EBOUNDS, "token id outside the vocabulary (ids are 1-based, 1..%lld)", (long long)e->vocab);
-    if (herr & 2) return fail(CLB_EDOMAIN, "non-finite encoder output (an activation outside the range of the f16 operand split? "
-                                           "clb_encoder_set_gemm_mode(e, 2) selects the bf16x6 split)");
-    return CLB_OK;
+    return read_flag(e, e->stream);                   // sticky until read: covers EVERY encode since the previous check
 }
 
 int clb_encoder_error_flag_device(clb_encoder* e, void** d_flag) {

@@ -541,7 +541,9 @@ int clb_encode_docs_packed_device(clb_encoder* e, const int32_t* d_ids, const in
 /* The asynchronous device path cannot report an id outside the vocabulary when it is enqueued (it clamps): this call
  * waits for the device and returns the BoundsError of ANY device-path encode since the previous check (the flag is
  * sticky: set by the kernels, cleared by this call), or CLB_EDOMAIN when an encode produced non-finite embeddings (the
- * f16x3 split's range).  The host-buffer entry points report both themselves. */
+ * f16x3 split's range).  The host-buffer entry points (clb_encode, clb_encode_docs, clb_encode_queries) enqueue the same
+ * forward and epilogue as their device counterparts on the encoder's own stream and read the flag themselves, once per
+ * call, before they copy any result out: they report both from the call itself and leave the flag clear. */
 int clb_encoder_check_last_ids(clb_encoder* e);
 /* The sticky flag itself: *d_flag receives the device address of the int32 the encode kernels OR their findings into
  * (bit 0: id outside the vocabulary, bit 1: non-finite output).  A serving loop copies its 4 bytes back together with the

@@ -250,6 +250,103 @@ def test_bert_forward_matches_fp32_reference(gemm):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("dim", [32, 30])
+def test_host_and_device_entry_points_share_one_epilogue(dim):
+    """Every output form (queries, padded documents, packed documents) has one enqueue function behind its host-buffer and
+    its device entry point: the two return the same bits, and the host one reports a token id outside the vocabulary
+    (BoundsError) and a non-finite output (the error CLB_EDOMAIN maps to) from the call itself, leaving the sticky flag
+    clear.  dim = 30: no planes (so no packing) and the two-kernel query epilogue."""
+    torch, cfg, bert, linear = _random_bert(hidden=128, layers=2, heads=2, inter=256, max_pos=64, dim=dim)
+    from colbert_jl_amd.encoder import pack_weights
+    from colbert_jl_amd._lib import _ERRORS
+    bcfg = cfg.to_dict()
+    w = pack_weights(_state(bert, linear), bcfg, dim)
+    rng = np.random.default_rng(3)
+    L, N, pad = 37, 5, 1
+    lens = [37, 20, 1, 33, 9]
+    skip = [5, 17, 33, pad]
+    mask = np.zeros((N, L), bool)
+    for n, l in enumerate(lens):
+        mask[n, :l] = True
+    ids = (rng.integers(1, cfg.vocab_size, size=(N, L)) + 1).astype(np.int32)       # 1-based, never the pad id
+    ids[~mask] = pad
+    ids_kept = ids.copy()
+    ids_kept[1, 25] = 50                       # an unattended token the skiplist keeps: the host call cannot pack this batch
+    assert not mask[1, 25] and 50 not in skip
+    dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).cuda()      # noqa: E731
+    d_mask, d_skip = dev(mask, np.uint8), dev(skip, np.int64)
+    # a packed batch: the attended rows of every sequence, one after another
+    p_ids = dev(np.concatenate([ids[n, :l] for n, l in enumerate(lens)]), np.int32)
+    p_pos = dev(np.concatenate([np.arange(l) for l in lens]), np.int32)
+    p_seq = dev(np.concatenate([np.full(l, n) for n, l in enumerate(lens)]), np.int32)
+    p_cu = dev(np.concatenate([[0], np.cumsum(lens)]), np.int32)
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)                             # noqa: E731
+
+    def host_docs(enc, which):
+        return enc.doc_embeddings_and_doclens(skip, (ids_kept if which == "padded" else ids).T, mask.T)
+
+    def host_queries(enc):
+        return enc.query_embeddings(skip, ids.T, mask.T)
+
+    def device_calls(enc):
+        d_q = torch.empty((N, L, dim), dtype=torch.float32, device="cuda")
+        yield "queries", lambda: enc.query_embeddings_device(dev(ids, np.int32), d_mask, d_skip, d_q)
+        yield "padded", lambda: enc.doc_embeddings_device(dev(ids_kept, np.int32), d_mask, d_skip)
+        if dim % 4 == 0:
+            yield "packed", lambda: enc.doc_embeddings_packed_device(p_ids, p_pos, p_seq, p_cu, max(lens), d_skip)
+
+    enc = clb.BertEncoder(w, bcfg, dim=dim)
+    device = {name: call() for name, call in device_calls(enc)}
+    torch.cuda.synchronize()
+    enc.check_last_ids()
+    # padded documents
+    D, dl = host_docs(enc, "padded")
+    assert not any(p["packed"] for p in enc.last_plans())
+    assert np.array_equal(dl, device["padded"][1].cpu().numpy())
+    assert D.shape == (dim, int(dl.sum())) and np.array_equal(bits(D.T), bits(device["padded"][0].cpu().numpy()))
+    # packed documents: the host call packs prefix masks whose padding the skiplist drops
+    if dim % 4 == 0:
+        D, dl = host_docs(enc, "packed")
+        assert all(p["packed"] for p in enc.last_plans())
+        assert np.array_equal(dl, device["packed"][1].cpu().numpy())
+        assert D.shape == (dim, int(dl.sum())) and np.array_equal(bits(D.T), bits(device["packed"][0].cpu().numpy()))
+    else:
+        with pytest.raises(clb.ArgumentError):           # no planes, no fp16-plane attention: this encoder cannot run packed batches
+            enc.doc_embeddings_packed_device(p_ids, p_pos, p_seq, p_cu, max(lens), d_skip)
+    # queries
+    Q = host_queries(enc)
+    assert np.array_equal(bits(Q.transpose(2, 1, 0)), bits(device["queries"].cpu().numpy()))
+    # a token id outside the vocabulary: reported by the host call itself, and the flag is clear afterwards
+    bad = ids.copy(); bad[0, 0] = cfg.vocab_size + 1
+    bad_kept = ids_kept.copy(); bad_kept[0, 0] = cfg.vocab_size + 1
+    host_calls = [(lambda i: enc.doc(i.T, mask.T), bad, ids),
+                  (lambda i: enc.doc_embeddings_and_doclens(skip, i.T, mask.T), bad, ids),
+                  (lambda i: enc.doc_embeddings_and_doclens(skip, i.T, mask.T), bad_kept, ids_kept),
+                  (lambda i: enc.query_embeddings(skip, i.T, mask.T), bad, ids)]
+    for call, bad_ids, good_ids in host_calls:
+        with pytest.raises(clb.BoundsError):
+            call(bad_ids)
+        call(good_ids)
+        enc.check_last_ids()
+    enc.close()
+    # a NaN in the projection bias (the last `dim` floats of the blob): every output row is non-finite
+    w_nan = w.copy()
+    w_nan[-dim:] = np.nan
+    enc = clb.BertEncoder(w_nan, bcfg, dim=dim)
+    domain_error = _ERRORS[2]                            # CLB_EDOMAIN
+    for call in (lambda: host_docs(enc, "padded"), lambda: host_docs(enc, "packed"), lambda: host_queries(enc)):
+        with pytest.raises(domain_error):
+            call()
+        enc.check_last_ids()
+    for name, call in device_calls(enc):
+        call()
+        with pytest.raises(domain_error):                # (queries at dim = 30: the two-kernel epilogue carries the flag too)
+            enc.check_last_ids()
+        enc.check_last_ids()
+    enc.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("L", [33, 100, 200, 300, 470])
 def test_fused_attention_long_sequences(L):
     """Head size 64 takes the fused attention kernel (one wave per 32 queries, scores in registers); the key-tile count

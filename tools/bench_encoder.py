@@ -23,8 +23,8 @@ def flops(cfg, L, N):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--gemm", default=None, help="bf16x6 (default), bf16x3 or f32")
-    ap.add_argument("--attention", default="fused", help="fused (default), resident or unfused")
+    ap.add_argument("--gemm", default=None, help="f16x3 (default; COLBERT_ENCODER_GEMM overrides it), bf16x6, bf16x3 or f32")
+    ap.add_argument("--attention", default="fused", help="fused (default), resident, unfused or fused_f32")
     args = ap.parse_args()
     import torch
     import colbert_jl_amd as clb
