@@ -1134,9 +1134,12 @@ constexpr int kApproxLdsLut = 256 * 256;            // 256 entries x 32 lane slo
 //        has to decompress and multiply the rows J = { j : exists t, A[t][j] >= a_t - 2e } -- typically a third of the
 //        passage -- and still finds the identical per-token maxima, hence the identical fp32 score.  The sweep
 //        recomputes A with the same pipeline (bit-identical values), compares against the stored (floored, so only
-//        more permissive) a_t and writes rowmask[b][list position][4] x 64 bits; passages longer than kMaxMaskedRows
-//        embeddings are ignored downstream (the exact kernel then takes every row).  Comparisons are written
-//        !(v < lo): a NaN or an infinite window (guarded query, select_margin_kernel) selects the row.
+//        more permissive) a_t and writes rowmask[b][list position][2][4] x 64 bits: one 256-bit mask per token half,
+//        J_lo = rows selected by a token of 0..15 and J_hi = rows selected by a token of 16..31 (their union is J; token
+//        t's exact maximum lies among the rows t's own window selected, so the exact kernel multiplies J_lo only against
+//        tokens 0..15 and J_hi only against tokens 16..31).  Passages longer than kMaxMaskedRows embeddings are ignored
+//        downstream (the exact kernel then takes every row in both halves).  Comparisons are written !(v < lo): a NaN or
+//        an infinite window (guarded query, select_margin_kernel) selects the row, in the half of the token it belongs to.
 // The ablation variants and the pipelined epilogue (PIPE) that were measured on this kernel are retired: their results are in
 // DESIGN 4.3 and profiles/r0{3,5,6}_experiments.md.
 // GL = 1 ("LDS-DMA gather", round 3): the score rows reach the wave through LDS instead of VGPRs.  Four ADJACENT lanes
@@ -1200,6 +1203,10 @@ static __global__ __launch_bounds__(kApproxThreads, kApproxThreads / 256) void s
     // scalar work and a second load per step), and over 8-bit rows it did not fit three waves per SIMD without spilling
     __shared__ __attribute__((aligned(16))) unsigned char stage_s[ROWS ? 16 : (kApproxThreads / 64) * kStageBytes];
     unsigned char* mystage = stage_s + (ROWS ? 0 : wave * kStageBytes);
+    // ROWS: the two 256-bit row masks of the wave's current passage (CLB_STAGE_E), all zero between passages
+    __shared__ uint32_t mask_s[ROWS ? (kApproxThreads / 64) * 32 : 1];
+    uint32_t* mymask = mask_s + (ROWS ? wave * 32 : 0);
+    if (ROWS && threadIdx.x < (kApproxThreads / 64) * 32) mask_s[threadIdx.x] = 0u;
     for (int i = threadIdx.x; i < 256 * 32; i += kApproxThreads) {
         const int v = i >> 5;
         *reinterpret_cast<uint2*>(lut_s + (size_t)i * 8) =
@@ -1274,7 +1281,7 @@ static __global__ __launch_bounds__(kApproxThreads, kApproxThreads / 256) void s
         float* out = scores + (size_t)b * cand_cap;
         uint16_t* tmax = tokmax + (size_t)b * cand_cap * 32 + r;
         const int* lst = ROWS ? list + (size_t)b * cand_cap : nullptr;
-        unsigned long long* rmask = ROWS ? rowmask + (size_t)b * cand_cap * 4 : nullptr;
+        unsigned long long* rmask = ROWS ? rowmask + (size_t)b * cand_cap * 8 : nullptr;
         const float window = ROWS ? 2.f * eps_pair[b] : 0.f;
         const int n = ROWS ? nlist[b] : ncand[b];
         // this wave's contiguous share of the query's n passages
@@ -1282,7 +1289,6 @@ static __global__ __launch_bounds__(kApproxThreads, kApproxThreads / 256) void s
         const int my_wave = (sub * wg_count + wg_index) * (kApproxThreads / 64) + wave;
         const int per_wave = (n + n_waves - 1) / n_waves;
         const int j_first = min(n, my_wave * per_wave), j_end = min(n, j_first + per_wave);
-        unsigned long long wm0 = 0, wm1 = 0, wm2 = 0, wm3 = 0;   // ROWS: the current passage's mask (wave-uniform)
 
         // ---- wave-uniform iterator over the steps of passages j0, j0 + 1, ... ---------------------------------
         // The headers {first embedding, length} of the wave's next 64 passages sit in one VGPR pair (lane k =
@@ -1463,33 +1469,40 @@ static __global__ __launch_bounds__(kApproxThreads, kApproxThreads / 256) void s
         if (ROWS) {                                                                                         \
             const __half pmh = *reinterpret_cast<const __half*>(&PM);                                       \
             const float lo = r < T ? __half2float(pmh) - window : __builtin_inff();   /* tokens past T select nothing */ \
-            /* per lane (token): bit i of lm = accumulator register i is inside the window; OR over the 32 tokens of */ \
-            /* each lane half with 4 DPP steps + 2 readlanes (16 wave-wide ballots cost ~130 scalar instructions per */ \
-            /* step, and a wave issues one instruction per ~5.7 cycles whatever its type)                            */ \
+            /* per lane (token): bit i of lm = accumulator register i is inside the window; OR over the 16 tokens of */ \
+            /* each 16-lane row with 4 DPP steps (16 wave-wide ballots cost ~130 scalar instructions per step, and a  */ \
+            /* wave issues one instruction per ~5.7 cycles whatever its type)                                        */ \
             uint32_t lm = 0;                                                                                \
             _Pragma("unroll") for (int i = 0; i < 16; ++i) lm |= !((CELL8 ? v[i] * stp : v[i]) < lo) ? (1u << i) : 0u; \
             lm |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lm, 0xB1, 0xf, 0xf, true);    /* lane ^ 1 */     \
             lm |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lm, 0x4E, 0xf, 0xf, true);    /* lane ^ 2 */     \
             lm |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lm, 0x141, 0xf, 0xf, true);   /* row_half_mirror */ \
             lm |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lm, 0x140, 0xf, 0xf, true);   /* row_mirror */   \
-            const uint32_t m0_ = __builtin_amdgcn_readlane(lm, 0) | __builtin_amdgcn_readlane(lm, 16);      \
-            const uint32_t m1_ = __builtin_amdgcn_readlane(lm, 32) | __builtin_amdgcn_readlane(lm, 48);     \
-            /* register i of lane half h is row (i & 3) + 8 (i >> 2) + 4 h: spread the nibbles            */ \
-            uint32_t bits = ((m0_ & 0xFu) | ((m0_ & 0xF0u) << 4) | ((m0_ & 0xF00u) << 8) | ((m0_ & 0xF000u) << 12)) | \
-                            (((m1_ & 0xFu) | ((m1_ & 0xF0u) << 4) | ((m1_ & 0xF00u) << 8) | ((m1_ & 0xF000u) << 12)) << 4); \
-            if (TAG.rows < kStepRows) bits &= (1u << TAG.rows) - 1u;   /* duplicates of the last row */     \
-            const unsigned long long wbits = (unsigned long long)bits << (TAG.base & 32);                   \
-            const int wi = TAG.base >> 6;                                                                   \
-            wm0 |= wi == 0 ? wbits : 0ull;                                                                  \
-            wm1 |= wi == 1 ? wbits : 0ull;                                                                  \
-            wm2 |= wi == 2 ? wbits : 0ull;                                                                  \
-            wm3 |= wi == 3 ? wbits : 0ull;                                                                  \
+            /* after the reduction over each 16-lane row, lanes 0 / 32 hold the bits of tokens 0..15 (lane halves 0 / 1) and  */ \
+            /* lanes 16 / 48 those of tokens 16..31: one mask per token half (the exact kernel multiplies a row only by the   */ \
+            /* half that selected it).  Register i of lane half h is row (i & 3) + 8 (i >> 2) + 4 h: every lane spreads its   */ \
+            /* own nibbles and drops the duplicates of the passage's last row; no lane's bits go through a scalar register    */ \
+            uint32_t sp_ = ((lm & 0xFu) | ((lm & 0xF0u) << 4) | ((lm & 0xF00u) << 8) | ((lm & 0xF000u) << 12)) << (4 * h); \
+            sp_ &= TAG.rows < kStepRows ? (1u << TAG.rows) - 1u : 0xffffffffu;                              \
+            /* the step's 32 rows are dword base / 32 of each 256-bit mask.  The passage's masks gather in the wave's 128-byte   */ \
+            /* LDS block, four parts of 8 dwords: lo mask from lane half 0 / 1, hi mask from lane half 0 / 1 (sixteen SGPRs of   */ \
+            /* wave-uniform accumulators did not fit beside the iterator without spilling): lanes 0, 32, 16, 48 write their part */ \
+            /* of this step, the passage's last step ORs the parts, sends both masks out as one 64-byte store and zeroes the     */ \
+            /* block.  Rows past kMaxMaskedRows are dropped: that passage's masks are not read                                   */ \
+            const int wd_ = TAG.base >> 5;                                                                  \
+            int ln_ = lane;                                                                                 \
+            asm volatile("" : "+v"(ln_));     /* (the block's per-lane addresses are formed here, not kept in registers) */ \
+            if ((ln_ & 15) == 0 && wd_ < 8 && TAG.j >= 0) mymask[wd_ + 8 * (((ln_ >> 3) & 2) | (ln_ >> 5))] = sp_; \
             if (TAG.last) {                                                                                 \
-                if (lane == 0 && TAG.j >= 0) {                                                              \
-                    unsigned long long* o = rmask + (size_t)TAG.j * 4;                                      \
-                    o[0] = wm0; o[1] = wm1; o[2] = wm2; o[3] = wm3;                                         \
+                __builtin_amdgcn_wave_barrier();                                                            \
+                if (ln_ < 16) {         /* lanes 0..7: dwords of the lo mask (parts 0 | 1), lanes 8..15: of the hi mask (2 | 3) */ \
+                    const int d_ = (ln_ & 7) + 16 * (ln_ >> 3);                                             \
+                    const uint32_t mv_ = mymask[d_] | mymask[d_ + 8];                                       \
+                    if (TAG.j >= 0) reinterpret_cast<uint32_t*>(rmask + (size_t)TAG.j * 8)[ln_] = mv_;      \
+                    mymask[d_] = 0u;                                                                        \
+                    mymask[d_ + 8] = 0u;                                                                    \
                 }                                                                                           \
-                wm0 = wm1 = wm2 = wm3 = 0;                                                                  \
+                __builtin_amdgcn_wave_barrier();                                                            \
             }                                                                                               \
         } else {                                                                                            \
             if (TAG.g) {            /* quads 0 .. g-1 end the head passage, quads g .. 3 start the tail */   \

@@ -284,7 +284,7 @@ int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, 
     }
     if (s->approx_ok && Ttuned > 0) {
         CLB_TRY(w.cells_q.ensure(approx_cells_bytes(B, s->K, Tpad)));
-        CLB_TRY(w.rowmask.ensure(sizeof(unsigned long long) * 4 * B * w.cand_cap));
+        CLB_TRY(w.rowmask.ensure(sizeof(unsigned long long) * 8 * B * w.cand_cap));   // [b][list position][token half][4]
         CLB_TRY(w.eps_pair.ensure(sizeof(float) * B));
         CLB_TRY(w.tokmax.ensure(sizeof(uint16_t) * 32 * B * w.cand_cap));
     }
@@ -823,7 +823,7 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
         hipLaunchKernelGGL(batch_stats_kernel, dim3(32, B), dim3(256), 0, st, w.cand.as<uint32_t>(),
                            w.ncand.as<int>(), list, nlist, s->doc_off.as<uint32_t>(), w.cand_cap,
                            w.stats.as<unsigned long long>(),
-                           subset ? w.rowmask.as<unsigned long long>() : (const unsigned long long*)nullptr);
+                           subset ? w.rowmask.as<unsigned long long>() : (const unsigned long long*)nullptr, T);
     }
     CLB_HIP(hipGetLastError());
     return CLB_OK;
@@ -1919,6 +1919,22 @@ int clb_last_batch_stats(clb_searcher* s, int64_t* cand_docs, int64_t* cand_embs
     if (cand_embs) *cand_embs = (int64_t)h[1];
     if (rescored_docs) *rescored_docs = (int64_t)h[2];
     if (rescored_embs) *rescored_embs = (int64_t)h[3];
+    return CLB_OK;
+}
+
+int clb_last_batch_half_rows(clb_searcher* s, int64_t* rows_lo, int64_t* rows_hi) {
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    CLB_TRY(use_device(s->device));
+    CLB_HIP(hipDeviceSynchronize());
+    unsigned long long h[2] = {0, 0};
+    for (auto& w : s->ws) {
+        unsigned long long t[8] = {0};
+        if (w.stats.p) CLB_HIP(hipMemcpy(t, w.stats.p, sizeof t, hipMemcpyDeviceToHost));
+        h[0] += t[4];
+        h[1] += t[5];
+    }
+    if (rows_lo) *rows_lo = (int64_t)h[0];
+    if (rows_hi) *rows_hi = (int64_t)h[1];
     return CLB_OK;
 }
 

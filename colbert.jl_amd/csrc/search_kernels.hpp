@@ -799,25 +799,36 @@ static __global__ __launch_bounds__(256, 3) void score_exact_kernel(
 }
 
 // -------------------------------------------------------------------------------------------------
-// Pass 2 of the two-pass mode as a flat step pipeline (nbits 2, T <= 32).  Same arithmetic per step as
-// score_exact_kernel<2, true>; what changes is the control structure.  With the row subset a listed passage is
-// only ~2.4 steps of 16 rows, so a per-passage loop spends most of its time in the start-up chain of dependent
-// loads (list -> header -> codes -> centroid rows).  Here each wave walks a wave-uniform iterator over the steps
-// of ITS passages (headers and row masks of 64 passages at a time sit in VGPRs and are extracted with v_readlane,
-// as in score_approx32_kernel) and keeps three steps in flight across passage boundaries:
+// Pass 2 of the two-pass mode as a flat step pipeline (nbits 2, T <= 32).  Same arithmetic per product as
+// score_exact_kernel<2>; what changes is the control structure and WHICH token columns a step multiplies.  With the row
+// subset a listed passage is only ~2 steps of 16 rows, so a per-passage loop spends most of its time in the start-up
+// chain of dependent loads (list -> header -> codes -> centroid rows).  Here each wave walks a wave-uniform iterator
+// over the steps of ITS passages (headers and row masks of 32 passages at a time sit in VGPRs and are extracted with
+// v_readlane, as in score_approx32_kernel) and keeps three steps in flight across passage boundaries:
 //   stage A (step i+2): row index of lane r = the (base + r)-th set bit of the passage's 256-bit mask (a
 //                       branch-free popcount search), then its code and 32-B residual are requested;
 //   stage G (step i+1): the 16 centroid rows are requested as whole 512-B rows;
-//   stage C (step i)  : rows -> swizzled LDS tile, decompress, 64 fp32 MFMAs, running per-token max; at the last
-//                       step of a passage reduce, sum the tokens in order, store the score.
+//   stage C (step i)  : rows -> swizzled LDS tile, decompress, 32 fp32 MFMAs against ONE half of the query's tokens,
+//                       running per-token max; at the last step of a passage reduce, sum the tokens in order.
+// Token halves: a row is in a passage's mask only because some token's window selected it, and token t's exact maximum
+// lies among the rows t's own window selected (approx_kernels.hpp, ROWS = true).  The sweep therefore leaves one mask
+// per token half, and a step is a HALF-step: its 16 rows come from the passage's lo mask and meet tokens 0..15 only, or
+// from the hi mask and meet tokens 16..31 only (one accumulator, 32 MFMAs; the query operand is laid out half-major so
+// the half is a scalar base offset).  A chunk of 32 passages is walked twice inside the one pipeline: all lo half-steps,
+// then all hi half-steps; the iterator moves from one walk to the other without draining the three stages, and the last
+// lo step never shares its row slots with the first hi step.  The score stays the sequential fp32 sum 0 + m_0 + ... +
+// m_31: the lo walk adds tokens 0..15 in order from +0.0 and parks that one float in lane k of a VGPR (k = the passage's
+// index in the chunk, of 32 passages: see the header registers below), the hi walk reads it back, continues with tokens 16..T-1 and stores.  With T <= 16 there is no hi
+// walk and the lo walk stores.  Passages longer than kMaxMaskedRows take every row in both halves.
 // Steps past the end of the wave's work read a dummy address and are discarded.
 // grid = (G, B), block = 256; the waves of a query's work-groups take its listed passages round-robin.
 // -------------------------------------------------------------------------------------------------
 struct ExactStepTag {
     int slot;   // candidate slot to store the score to, -1 = dummy step
-    int slot1;  // (round 6) the passage that BEGINS inside this step at row p, see below
+    int slot1;  // the passage that BEGINS inside this step at row p, see below
     int info;   // bits 0..4: p = 16, or the row at which the wave's next passage starts inside this step (rows [0, p) end passage
-                // `slot`, rows [p, 16) begin passage `slot1`); bit 8: `slot` ends in this step; bit 9: `slot1` ends in it too
+                // `slot`, rows [p, 16) begin passage `slot1`); bit 8: `slot` ends in this step; bit 9: `slot1` ends in it too;
+                // bit 10: the token half this step multiplies; bits 16..22 / 24..30: index in the chunk of `slot` / `slot1`
 };
 // the n-th (0-based) set bit of a 256-bit mask held in four wave-uniform 64-bit words; n < popcount(mask)
 __device__ __forceinline__ uint32_t nth_set_bit_256(unsigned long long w0, unsigned long long w1,
@@ -846,15 +857,16 @@ static __global__ __launch_bounds__(256, 3) void score_exact_flat_kernel(
     const int* __restrict__ nlist, const unsigned long long* __restrict__ rowmask) {
     constexpr int NBITS = 2;
     __shared__ float tbl[weight_table_floats<NBITS>()];
-    __shared__ __attribute__((aligned(16))) float qlds[16 * 64 * 4];    // 16 KB
-    __shared__ __attribute__((aligned(16))) float ctiles[4 * 512 * 4];  // 4 waves x 8 KB
+    __shared__ __attribute__((aligned(16))) float qlds[2 * 16 * 64 * 2];   // 16 KB: [half][k][lane] float2
+    __shared__ __attribute__((aligned(16))) float ctiles[4 * 512 * 4];     // 4 waves x 8 KB
     fill_weight_table<NBITS>(tbl, weights);
     const int lane = threadIdx.x & 63;
     const int r = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     float* ctile = ctiles + wave * 2048;
     const int c4 = lane & 31, rhalf = lane >> 5;    // row loader: instruction m moves chunk c4 of row 2m + rhalf
-    const float4* qv = reinterpret_cast<const float4*>(qlds) + lane;
+    const float2* qv = reinterpret_cast<const float2*>(qlds) + lane;
+    const bool has_hi = T > 16;                     // a query of at most 16 tokens has no second half
 
 #define CLB_REP8(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
 #define CLB_ROW_DECL(m) float4 rowA##m;
@@ -880,44 +892,47 @@ static __global__ __launch_bounds__(256, 3) void score_exact_flat_kernel(
     {
         const int b = blockIdx.y;
         __syncthreads();
-        for (int i = threadIdx.x; i < 16 * 64; i += 256) {     // query operand, see score_exact_kernel
-            const int k = i >> 6, l = i & 63;
+        // query operand: lane (token rr of the half, gg) holds {Q[t][8k + gg], Q[t][8k + 4 + gg]}, the B operands of the
+        // step's MFMAs 2k and 2k + 1 (the same products, in the same order, as score_exact_kernel's a0 / a1 chains)
+        for (int i = threadIdx.x; i < 2 * 16 * 64; i += 256) {
+            const int hf = i >> 10, k = (i >> 6) & 15, l = i & 63;
             const int rr = l & 15, gg = l >> 4;
-            const int t0 = rr, t1 = rr + 16;
-            const float* qa = Q + ((size_t)b * T + (t0 < T ? t0 : T - 1)) * kDim + gg;
-            const float* qb = Q + ((size_t)b * T + (t1 < T ? t1 : T - 1)) * kDim + gg;
-            float4 v;
-            v.x = t0 < T ? qa[8 * k] : 0.f;
-            v.y = t1 < T ? qb[8 * k] : 0.f;
-            v.z = t0 < T ? qa[8 * k + 4] : 0.f;
-            v.w = t1 < T ? qb[8 * k + 4] : 0.f;
-            *reinterpret_cast<float4*>(qlds + (size_t)i * 4) = v;
+            const int t = 16 * hf + rr;
+            const float* qa = Q + ((size_t)b * T + (t < T ? t : T - 1)) * kDim + gg;
+            float2 v;
+            v.x = t < T ? qa[8 * k] : 0.f;
+            v.y = t < T ? qa[8 * k + 4] : 0.f;
+            *reinterpret_cast<float2*>(qlds + (size_t)i * 2) = v;
         }
         __syncthreads();
         const int n = nlist[b];
         const int* lst = list + (size_t)b * cand_cap;
         const uint2* hdr = cand_hdr + (size_t)b * cand_cap;
-        const unsigned long long* mw = rowmask + (size_t)b * cand_cap * 4;
+        const unsigned long long* mw = rowmask + (size_t)b * cand_cap * 8;
         float* out = scores + (size_t)b * cand_cap;
         const int stride = gridDim.x * 4;
 
-        for (int j0 = blockIdx.x * 4 + wave; j0 < n; j0 += 64 * stride) {
-            // lane k of the wave holds the description of the wave's k-th passage of this batch
-            const int jl = j0 + lane * stride;
+        for (int j0 = blockIdx.x * 4 + wave; j0 < n; j0 += 32 * stride) {
+            // lanes k and 32 + k of the wave hold the description of the wave's k-th passage of this chunk of 32: the same header
+            // and slot, and the lo mask (lane k) / the hi mask (lane 32 + k) -- the hi walk reads the same registers 32 lanes up,
+            // so the masks of both halves cost the 8 VGPRs one half of 64 passages would (the kernel has none to spare)
+            const int jl = j0 + (lane & 31) * stride;
             const int jj = jl < n ? jl : j0;
+            const int mh_ = 4 * (lane >> 5);
             const int slot_l = lst[jj];
             const uint2 hv = hdr[slot_l];
-            const unsigned long long mk0 = mw[(size_t)jj * 4], mk1 = mw[(size_t)jj * 4 + 1],
-                                     mk2 = mw[(size_t)jj * 4 + 2], mk3 = mw[(size_t)jj * 4 + 3];
-            const bool ident_l = (int)hv.y > kMaxMaskedRows;      // too long for the mask: every row
-            // rows to multiply; bit 31 flags the identity mapping
+            const bool ident_l = (int)hv.y > kMaxMaskedRows;      // too long for the mask: every row, in both halves
+            // the mask of this lane's token half and the rows it selects; bit 31 flags the identity mapping
+            const unsigned long long mk0 = mw[(size_t)jj * 8 + mh_], mk1 = mw[(size_t)jj * 8 + mh_ + 1],
+                                     mk2 = mw[(size_t)jj * 8 + mh_ + 2], mk3 = mw[(size_t)jj * 8 + mh_ + 3];
             const uint32_t nj_l = ident_l ? (hv.y | 0x80000000u)
-                                          : (uint32_t)(__popcll(mk0) + __popcll(mk1) + __popcll(mk2) + __popcll(mk3));
-            const int nd = (n - j0 + stride - 1) / stride < 64 ? (n - j0 + stride - 1) / stride : 64;
-            int it_k = 0, it_base = 0;
+                                    : (uint32_t)(__popcll(mk0) + __popcll(mk1) + __popcll(mk2) + __popcll(mk3));
+            const int nd = (n - j0 + stride - 1) / stride < 32 ? (n - j0 + stride - 1) / stride : 32;
+            int it_k = 0, it_base = 0, it_half = 0;
             uint32_t it_off, it_nj;
             int it_slot;
             unsigned long long it_m0, it_m1, it_m2, it_m3;
+            float park = 0.f;     // lane k: tokens 0..15 of the chunk's k-th passage, summed by the lo walk
 #define CLB_IT_LOAD(KK)                                                                                        \
     {                                                                                                          \
         it_off = __builtin_amdgcn_readlane(hv.x, KK);                                                          \
@@ -929,20 +944,34 @@ static __global__ __launch_bounds__(256, 3) void score_exact_flat_kernel(
         it_m3 = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(mk3 >> 32), KK) << 32) | (uint32_t)__builtin_amdgcn_readlane((uint32_t)mk3, KK); \
     }
             CLB_IT_LOAD(0)
+            // the iterator's passage has ended: on to the wave's next one.  After the chunk's last passage in the lo walk the hi
+            // walk starts at its first (lane 32); the pipeline keeps its steps in flight
+#define CLB_IT_NEXT                                                                                            \
+    {                                                                                                          \
+        it_k += 1;                                                                                             \
+        if (it_k >= nd && it_half == 0 && has_hi) {                                                            \
+            it_half = 1;                                                                                       \
+            it_k = 0;                                                                                          \
+        }                                                                                                      \
+        const int kk = (it_k < 32 ? it_k : 31) + 32 * it_half;                                                 \
+        CLB_IT_LOAD(kk)                                                                                        \
+        it_base = 0;                                                                                           \
+    }
 
             // stage A: describe the next step, request the code and residual of this lane's row.
-            // Round 6: a passage's selected rows (26 on average) used to be padded to whole steps of 16 -- a fifth of all row slots held
-            // copies of a last row.  When the current passage has fewer than 16 rows left and the wave has a further passage in this
-            // chunk, the step's remaining row slots [p, 16) now start that passage (at most two passages per step: a next passage
-            // shorter than 16 - p rows is padded with copies of ITS last row and ends in the same step).
+            // A passage's selected rows are not padded to whole steps of 16: when the current passage has fewer than 16 rows left
+            // and the wave has a further passage in this chunk, the step's remaining row slots [p, 16) start that passage, in the
+            // same token half (at most two passages per step: a next passage shorter than 16 - p rows is padded with copies of ITS
+            // last row and ends in the same step).
 #define CLB_XSTAGE_A(CODE, R0, R1, TAG)                                                                        \
     {                                                                                                          \
         const bool live = it_k < nd;                                                                           \
         const int nj = (int)(it_nj & 0x7fffffffu);                                                             \
         const int rem = nj - it_base;                                                                          \
+        const int hk_ = (it_half << 10) | (it_k << 16);                                                        \
         uint32_t e;                                                                                            \
         if (rem < 16 && it_k + 1 < nd) {     /* (wave-uniform) the boundary step of two passages */             \
-            const int kn = it_k + 1;                                                                           \
+            const int kn = it_k + 1 + 32 * it_half;                                                            \
             const uint32_t nx_off = __builtin_amdgcn_readlane(hv.x, kn);                                       \
             const uint32_t nx_nj = __builtin_amdgcn_readlane(nj_l, kn);                                        \
             const int nx_slot = __builtin_amdgcn_readlane(slot_l, kn);                                         \
@@ -964,13 +993,10 @@ static __global__ __launch_bounds__(256, 3) void score_exact_flat_kernel(
             const int last1 = njn <= 16 - rem;                                                                 \
             TAG.slot = it_slot;                                                                                \
             TAG.slot1 = nx_slot;                                                                               \
-            TAG.info = rem | 0x100 | (last1 << 9);                                                             \
+            TAG.info = rem | 0x100 | (last1 << 9) | hk_ | ((it_k + 1) << 24);                                  \
             it_k += 1;                                                                                         \
             if (last1) {                                                                                       \
-                it_k += 1;                                                                                     \
-                const int kk = it_k < 64 ? it_k : 63;                                                          \
-                CLB_IT_LOAD(kk)                                                                                \
-                it_base = 0;                                                                                   \
+                CLB_IT_NEXT                                                                                    \
             } else {                                                                                           \
                 it_off = nx_off; it_nj = nx_nj; it_slot = nx_slot;                                             \
                 it_m0 = nx_m0; it_m1 = nx_m1; it_m2 = nx_m2; it_m3 = nx_m3;                                    \
@@ -983,14 +1009,9 @@ static __global__ __launch_bounds__(256, 3) void score_exact_flat_kernel(
             const int last = it_base + 16 >= nj;                                                               \
             TAG.slot = live ? it_slot : -1;                                                                    \
             TAG.slot1 = -1;                                                                                    \
-            TAG.info = 16 | (last << 8);                                                                       \
+            TAG.info = 16 | (last << 8) | hk_;                                                                 \
             it_base += 16;                                                                                     \
-            if (last) {                                                                                        \
-                it_k += 1;                                                                                     \
-                const int kk = it_k < 64 ? it_k : 63;                                                          \
-                CLB_IT_LOAD(kk)                                                                                \
-                it_base = 0;                                                                                   \
-            }                                                                                                  \
+            if (last) CLB_IT_NEXT                                                                              \
         }                                                                                                      \
         CODE = codes0[e];                                                                                      \
         const uint4* rp = reinterpret_cast<const uint4*>(residuals + (size_t)e * 32);                          \
@@ -998,7 +1019,7 @@ static __global__ __launch_bounds__(256, 3) void score_exact_flat_kernel(
         R1 = rp[1];                                                                                            \
     }
             // stage C: rows (requested one step ago) -> LDS, decompress, request the next step's rows into the
-            // registers just freed, MFMAs
+            // registers just freed, MFMAs against the step's token half
 #define CLB_XSTAGE_C(P, R0, R1, TAG, CODE_NEXT2)                                                               \
     {                                                                                                          \
         CLB_ROW_STORE8(P)                                                                                      \
@@ -1008,63 +1029,60 @@ static __global__ __launch_bounds__(256, 3) void score_exact_flat_kernel(
         decompress_lane_dims_fast<NBITS>(nullptr, R, g, tbl, x, ctile, r);                                     \
         __builtin_amdgcn_wave_barrier();                                                                       \
         CLB_ROW_LOAD8(P, CODE_NEXT2)                                                                           \
-        f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};                                            \
-        float4 qnext = qv[0];                                                                                  \
+        const int half_ = (TAG.info >> 10) & 1;                                                                \
+        const float2* qh_ = qv + half_ * (16 * 64);     /* scalar base offset: 8 KB per half */                \
+        f32x4 a0 = {0.f, 0.f, 0.f, 0.f};                                                                       \
+        float2 qnext = qh_[0];                                                                                 \
         _Pragma("unroll") for (int k = 0; k < 16; ++k) {                                                       \
-            const float4 q = qnext;                                                                            \
-            if (k < 15) qnext = qv[(k + 1) * 64];                                                              \
+            const float2 q = qnext;                                                                            \
+            if (k < 15) qnext = qh_[(k + 1) * 64];                                                             \
             a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[2 * k], q.x, a0, 0, 0, 0);                             \
-            a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[2 * k], q.y, a1, 0, 0, 0);                             \
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[2 * k + 1], q.z, a0, 0, 0, 0);                         \
-            a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[2 * k + 1], q.w, a1, 0, 0, 0);                         \
+            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x[2 * k + 1], q.y, a0, 0, 0, 0);                         \
         }                                                                                                      \
-        /* rows past the selection are copies of a last row: they cannot change a max.  c0 / c1: the running maxima of the    */ \
-        /* passage rows [0, p) belong to; n0 / n1: those of the passage that begins at row p (accumulator row = 4 g + reg)      */ \
-        float c0, c1, n0 = kNegInf, n1 = kNegInf;                                                              \
+        /* rows past the selection are copies of a last row: they cannot change a max.  c0: the running maxima of the passage   */ \
+        /* rows [0, p) belong to; n0: those of the passage that begins at row p (accumulator row = 4 g + reg)                   */ \
+        float c0, n0 = kNegInf;                                                                                \
         const int p_ = TAG.info & 31;                                                                          \
         if (p_ >= 16) {                                                                                        \
             c0 = fmaxf(fmaxf(m0, fmaxf(a0[0], a0[1])), fmaxf(a0[2], a0[3]));                                   \
-            c1 = fmaxf(fmaxf(m1, fmaxf(a1[0], a1[1])), fmaxf(a1[2], a1[3]));                                   \
         } else {                                                                                               \
             c0 = m0;                                                                                           \
-            c1 = m1;                                                                                           \
             _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                                 \
                 const bool first_ = 4 * g + q_ < p_;                                                           \
                 c0 = fmaxf(c0, first_ ? a0[q_] : kNegInf);                                                     \
-                c1 = fmaxf(c1, first_ ? a1[q_] : kNegInf);                                                     \
                 n0 = fmaxf(n0, first_ ? kNegInf : a0[q_]);                                                     \
-                n1 = fmaxf(n1, first_ ? kNegInf : a1[q_]);                                                     \
             }                                                                                                  \
         }                                                                                                      \
         {                                                                                                      \
             const int nfin_ = ((TAG.info >> 8) & 1) + ((TAG.info >> 9) & 1);       /* passages that end in this step */ \
             int cs_ = TAG.slot;                                                                                \
+            int ck_ = (TAG.info >> 16) & 127;                                                                  \
             _Pragma("unroll 1") for (int f_ = 0; f_ < nfin_; ++f_) {                                           \
                 c0 = fmaxf(c0, __shfl_xor(c0, 16, 64));                                                        \
                 c0 = fmaxf(c0, __shfl_xor(c0, 32, 64));                                                        \
-                c1 = fmaxf(c1, __shfl_xor(c1, 16, 64));                                                        \
-                c1 = fmaxf(c1, __shfl_xor(c1, 32, 64));                                                        \
-                /* sequential sum over tokens (ranking.jl:83).  The maxima reach the adder through v_readlane (a scalar  */ \
-                /* operand, no LDS round trip as with ds_bpermute: 32 of those per passage were a quarter of the wave's  */ \
-                /* non-MFMA time); tokens past T add +0.0, which leaves a sum that started from +0.0 unchanged            */ \
-                float total = 0.f;                                                                             \
-                _Pragma("unroll") for (int t = 0; t < 32; ++t) {                                               \
-                    const uint32_t sv = __builtin_amdgcn_readlane(__float_as_uint(t < 16 ? c0 : c1), t & 15);  \
-                    total = total + __uint_as_float(t < T ? sv : 0u);                                          \
+                /* sequential sum over tokens (ranking.jl:83): the lo walk starts from +0.0, the hi walk from the sum the lo   */ \
+                /* walk parked.  The maxima reach the adder through v_readlane (a scalar operand, no LDS round trip as with   */ \
+                /* ds_bpermute); tokens past T add +0.0, which leaves a sum that started from +0.0 unchanged                   */ \
+                float total = half_ ? __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(park), ck_ & 63)) : 0.f; \
+                _Pragma("unroll") for (int t = 0; t < 16; ++t) {                                               \
+                    const uint32_t sv = __builtin_amdgcn_readlane(__float_as_uint(c0), t);                     \
+                    total = total + __uint_as_float(16 * half_ + t < T ? sv : 0u);                             \
                 }                                                                                              \
-                if (lane == 0 && cs_ >= 0) out[cs_] = total;                                                   \
+                if (half_ || !has_hi) {                                                                        \
+                    if (lane == 0 && cs_ >= 0) out[cs_] = total;                                               \
+                } else if (cs_ >= 0) {                                                                         \
+                    park = lane == ck_ ? total : park;                                                         \
+                }                                                                                              \
                 c0 = n0;                                                                                       \
-                c1 = n1;                                                                                       \
                 n0 = kNegInf;                                                                                  \
-                n1 = kNegInf;                                                                                  \
                 cs_ = TAG.slot1;                                                                               \
+                ck_ = (TAG.info >> 24) & 127;                                                                  \
             }                                                                                                  \
         }                                                                                                      \
         m0 = c0;                                                                                               \
-        m1 = c1;                                                                                               \
     }
 
-            float m0 = kNegInf, m1 = kNegInf;
+            float m0 = kNegInf;
             uint32_t cd0, cd1, cd2;
             uint4 ra0, rb0, ra1, rb1, ra2, rb2;
             ExactStepTag t0, t1, t2;
@@ -1081,6 +1099,7 @@ static __global__ __launch_bounds__(256, 3) void score_exact_flat_kernel(
                 CLB_XSTAGE_C(A, ra2, rb2, t2, cd0)
             }
 #undef CLB_IT_LOAD
+#undef CLB_IT_NEXT
 #undef CLB_XSTAGE_A
 #undef CLB_XSTAGE_C
         }
@@ -1520,15 +1539,17 @@ static __global__ void codes_to_zero_based_kernel(uint32_t* __restrict__ codes, 
 }
 
 // work counters of one batch: [0] candidate passages, [1] candidate embeddings, [2] passages in the
-// exact re-score list, [3] their embeddings.  grid = (32, B), block = 256.
+// exact re-score list, [3] their embeddings (with a row mask: the rows in the union of the two token halves' masks),
+// [4] / [5] the rows the exact kernel multiplies against tokens 0..15 / tokens 16..31 (two-pass mode only; a query of
+// T <= 16 tokens has no second half).  grid = (32, B), block = 256.
 static __global__ void batch_stats_kernel(const uint32_t* __restrict__ cand, const int* __restrict__ ncand,
                                    const int* __restrict__ list, const int* __restrict__ nlist,
                                    const uint32_t* __restrict__ doc_off, size_t cand_cap,
                                    unsigned long long* __restrict__ stats,
-                                   const unsigned long long* __restrict__ rowmask /*optional*/) {
+                                   const unsigned long long* __restrict__ rowmask /*optional*/, int T) {
     const int b = blockIdx.y;
     const uint32_t* cnd = cand + (size_t)b * cand_cap;
-    unsigned long long embs = 0, lembs = 0;
+    unsigned long long embs = 0, lembs = 0, lo_rows = 0, hi_rows = 0;
     const int n = ncand[b];
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t p = cnd[i];
@@ -1539,19 +1560,29 @@ static __global__ void batch_stats_kernel(const uint32_t* __restrict__ cand, con
         const uint32_t p = cnd[list[(size_t)b * cand_cap + i]];
         const uint32_t len = doc_off[p + 1] - doc_off[p];
         if (rowmask && len <= (uint32_t)kMaxMaskedRows) {      // rows the exact kernel really multiplies
-            const unsigned long long* mw = rowmask + ((size_t)b * cand_cap + i) * 4;
-            lembs += __popcll(mw[0]) + __popcll(mw[1]) + __popcll(mw[2]) + __popcll(mw[3]);
+            const unsigned long long* mw = rowmask + ((size_t)b * cand_cap + i) * 8;
+            lembs += __popcll(mw[0] | mw[4]) + __popcll(mw[1] | mw[5]) + __popcll(mw[2] | mw[6]) + __popcll(mw[3] | mw[7]);
+            lo_rows += __popcll(mw[0]) + __popcll(mw[1]) + __popcll(mw[2]) + __popcll(mw[3]);
+            hi_rows += __popcll(mw[4]) + __popcll(mw[5]) + __popcll(mw[6]) + __popcll(mw[7]);
         } else {
             lembs += len;
+            if (rowmask) {                                     // identity mapping in both halves
+                lo_rows += len;
+                hi_rows += T > 16 ? len : 0u;
+            }
         }
     }
     for (int o = 32; o > 0; o >>= 1) {
         embs += __shfl_down(embs, o, 64);
         lembs += __shfl_down(lembs, o, 64);
+        lo_rows += __shfl_down(lo_rows, o, 64);
+        hi_rows += __shfl_down(hi_rows, o, 64);
     }
     if ((threadIdx.x & 63) == 0) {
         if (embs) atomicAdd(&stats[1], embs);
         if (lembs) atomicAdd(&stats[3], lembs);
+        if (lo_rows) atomicAdd(&stats[4], lo_rows);
+        if (hi_rows) atomicAdd(&stats[5], hi_rows);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         atomicAdd(&stats[0], (unsigned long long)n);

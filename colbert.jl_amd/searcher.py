@@ -432,6 +432,13 @@ class Searcher:
         check(lib().clb_last_batch_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return {"cand_docs": a.value, "cand_embs": b.value, "rescored_docs": c.value, "rescored_embs": d.value}
 
+    def last_batch_half_rows(self) -> dict:
+        """Two-pass mode: the rows the exact pass multiplied against query tokens 0..15 and against tokens 16..31 in the
+        last batch (needs `profile_enable(counters=True)`, like `last_batch_stats`)."""
+        a, b = i64(0), i64(0)
+        check(lib().clb_last_batch_half_rows(self._h, C.byref(a), C.byref(b)))
+        return {"rows_lo": a.value, "rows_hi": b.value}
+
 
 class TextSearch:
     """search(searcher, query::String, k) (src/searching.jl:93-128) for a serving loop: one text query per call --

@@ -310,6 +310,11 @@ int clb_profile_read(clb_searcher* s, const char** names, double* total_ms, int6
  * embeddings re-scored by the exact pass */
 int clb_last_batch_stats(clb_searcher* s, int64_t* cand_docs, int64_t* cand_embs, int64_t* rescored_docs,
                          int64_t* rescored_embs);
+/* two-pass mode, same batch and same counters run: the rows the exact pass multiplied against query tokens 0..15
+ * (rows_lo) and against tokens 16..31 (rows_hi; 0 when the query has at most 16 tokens).  A row selected by tokens of
+ * both halves counts in both, so max(rows_lo, rows_hi) <= rescored_embs <= rows_lo + rows_hi.  Both are 0 outside the
+ * two-pass mode. */
+int clb_last_batch_half_rows(clb_searcher* s, int64_t* rows_lo, int64_t* rows_hi);
 
 /* ------------------------------------------------------------------------------------------------
  * Codec and ranking pieces as stand-alone calls (host buffers, run on `device`).
