@@ -99,6 +99,11 @@ def lib() -> C.CDLL:
         l.clb_searcher_num_embeddings.restype = C.c_int64
         l.clb_searcher_remove.restype = C.c_int
         l.clb_searcher_remove.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        l.clb_filter_create_pids_global.restype = C.c_int
+        l.clb_filter_create_pids_global.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+        l.clb_search_shard_phase1_filtered_slot.restype = C.c_int
+        l.clb_search_shard_phase1_filtered_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                                            C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
 

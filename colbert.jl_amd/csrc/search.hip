@@ -82,7 +82,8 @@ struct Workspace {
     size_t filt_cap = 0;        // largest filter population a CLB_FILTER_ALL call has asked this slot to hold (cand_cap covers it)
     size_t ivf_cap = 0;         // cand_cap before filt_cap was taken into account: the most candidates the IVF lists can give
     // two-phase sharded search: what clb_search_shard_phase1 left behind (phase 2 must continue exactly that batch)
-    struct { bool valid = false; const float* dQ = nullptr; int64_t T = 0, B = 0, nprobe = 0, k = 0; void* stream = nullptr; } pending;
+    struct { bool valid = false; const float* dQ = nullptr; int64_t T = 0, B = 0, nprobe = 0, k = 0; void* stream = nullptr;
+             size_t filt_now = 0; } pending;      // filt_now: Batch::filt_now of phase 1 -- phase 2 selects over the same candidates
     DevBuf Qdev, cells, cells_q, partial, sel, bitmap, blocksum, ncand, cand, cand_hdr, scores, list, nlist, thresh,
         outp, outs, flags, stats, redo, rowmask, eps_pair, tokmax, tau_glob, wsel, bounds, tscale, rangep, cells8;
     DevBuf g_cells, g_keys, g_keys2, g_vals, g_vals2, g_scratch, g_sort_tmp;   // general-shape path (generic_kernels.hpp)
@@ -145,7 +146,8 @@ struct Batch {
     int64_t* d_out_pids = nullptr; float* d_out_scores = nullptr; int64_t* d_n_cand = nullptr;
     // filtered search: the handles of the sub-batch (a HOST array, one entry per query, nullptr = unfiltered; nullptr
     // altogether when no query of the sub-batch is filtered: it then launches the unfiltered kernels), their scope, and
-    // the largest filter population of the CLB_FILTER_ALL call this sub-batch belongs to
+    // the largest filter population of the CLB_FILTER_ALL call this sub-batch belongs to when one of ITS queries is
+    // filtered (0 otherwise: its candidates are the IVF lists')
     const clb_filter* const* filt = nullptr;
     int filt_all = 0;
     size_t filt_now = 0;
@@ -689,7 +691,7 @@ int launch_select(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q,
     const int B = q.B, T = q.T, k = q.k;
     // by the most candidates a query of THIS sub-batch can have: a slot that once grew for a large CLB_FILTER_ALL set
     // goes on selecting its unfiltered batches as before
-    const size_t most = q.filt && q.filt_all ? std::max(w.ivf_cap, q.filt_now) : w.ivf_cap;
+    const size_t most = std::max(w.ivf_cap, q.filt_now);
     const bool wide = s->wide_select == 1 || (s->wide_select < 0 && most >= kWideSelectCap);
     if (!wide) {
         ApproxConsts ac = s->approx_consts;
@@ -848,6 +850,15 @@ int check_filters(const clb_searcher* s, const clb_filter* const* filters, int64
     return CLB_OK;
 }
 
+// q's filter operands: queries b0 .. b0 + q.B - 1 of a call whose handle array is `filters` (checked by check_filters, which
+// gave filt_count)
+void set_batch_filters(Batch& q, const clb_filter* const* filters, int64_t b0, int scope, size_t filt_count) {
+    q.filt_all = scope == CLB_FILTER_ALL;
+    for (int64_t b = b0; filters && b < b0 + q.B; ++b)
+        if (filters[b]) q.filt = filters + b0;
+    q.filt_now = q.filt && q.filt_all ? filt_count : 0;
+}
+
 // the workspace of a slot of the *_slot entry points, with the searcher's device made current
 int slot_workspace(clb_searcher* s, int slot, Workspace** w) {
     if (slot < 0 || slot >= kWorkspaceSlots) return fail(CLB_EARGUMENT, "workspace slot must be 0..%d", kWorkspaceSlots - 1);
@@ -873,10 +884,7 @@ int for_sub_batches(clb_searcher* s, Workspace& w, int64_t T, int64_t B, int64_t
         Batch q = make_batch(nullptr, std::min<int64_t>(kSubBatch, B - b0), T, nprobe, k);
         CLB_TRY(ensure_workspace(s, w, q.B, T, nprobe, k, filt_count));
         q.stats_keep = b0 > 0;
-        q.filt_all = scope == CLB_FILTER_ALL;
-        q.filt_now = filt_count;
-        for (int64_t b = b0; filters && b < b0 + q.B; ++b)
-            if (filters[b]) q.filt = filters + b0;
+        set_batch_filters(q, filters, b0, scope, filt_count);
         CLB_TRY(run_one(b0, q));
     }
     return CLB_OK;
@@ -1378,7 +1386,7 @@ static int searcher_remove_impl(clb_searcher* s, const int64_t* pids, int64_t n,
     CLB_TRY(err.init(st));
     CLB_TRY(counts.init(st));
     CLB_HIP(hipMemsetAsync(gone.p, 0, gone.bytes, st));
-    hipLaunchKernelGGL(filter_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_pids.as<int64_t>(), n,
+    hipLaunchKernelGGL(filter_mark_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_pids.as<int64_t>(), n,
                        s->pid_offset, (int)n_docs, gone.as<uint32_t>(), err.ptr());
     hipLaunchKernelGGL(remove_lengths_kernel, dim3((unsigned)((n_docs + 1 + 255) / 256)), dim3(256), 0, st,
                        s->doc_off.as<uint32_t>(), gone.as<uint32_t>(), (int)n_docs, len.as<uint32_t>(), counts.ptr());
@@ -1579,18 +1587,34 @@ int clb_search_shard_phase1(clb_searcher* s, const float* d_Q, int64_t T, int64_
 
 int clb_search_shard_phase1_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
                                  int64_t k, float* d_local_top, void* hip_stream) {
+    return clb_search_shard_phase1_filtered_slot(s, slot, d_Q, T, B, nprobe, k, nullptr, CLB_FILTER_CANDIDATES, d_local_top,
+                                                 hip_stream);
+}
+
+int clb_search_shard_phase1_filtered_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                          int64_t k, const clb_filter* const* filters, int scope, float* d_local_top,
+                                          void* hip_stream) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     if (!d_local_top) return fail(CLB_EARGUMENT, "d_local_top is null");
+    size_t filt_count = 0;
+    CLB_TRY(check_filters(s, filters, B, scope, &filt_count));
+    bool filtered = false;
+    for (int64_t b = 0; filters && b < B; ++b) filtered |= filters[b] != nullptr;
+    // the whole batch stays on the slot for phase 2, and the filter handles of a launch travel in one argument block
+    if (filtered && B > kFilterQueries)
+        return fail(CLB_EUNSUPPORTED, "a filtered clb_search_shard_phase1 takes at most %d queries per call, got %lld: split the batch",
+                    kFilterQueries, (long long)B);
     Workspace* wp = nullptr;
     CLB_TRY(slot_workspace(s, slot, &wp));
     Workspace& w = *wp;
-    CLB_TRY(ensure_workspace(s, w, B, T, nprobe, k));
+    CLB_TRY(ensure_workspace(s, w, B, T, nprobe, k, filt_count));
     w.pending.valid = false;
-    Batch q = make_batch(d_Q, B, T, nprobe, k);     // the sharded search takes no filters
+    Batch q = make_batch(d_Q, B, T, nprobe, k);
+    set_batch_filters(q, filters, 0, scope, filt_count);
     q.phase = 1; q.d_local_top = d_local_top;
     CLB_TRY(run_search(s, w, (hipStream_t)hip_stream, q));
     w.pending.valid = true; w.pending.dQ = d_Q; w.pending.T = T; w.pending.B = B; w.pending.nprobe = nprobe;
-    w.pending.k = k; w.pending.stream = hip_stream;
+    w.pending.k = k; w.pending.stream = hip_stream; w.pending.filt_now = q.filt_now;
     return CLB_OK;
 }
 
@@ -1620,7 +1644,10 @@ int clb_search_shard_phase2_slot(clb_searcher* s, int slot, const float* d_Q, in
         return fail(CLB_EARGUMENT, "clb_search_shard_phase2 with %lld shards before clb_searcher_set_bound_consts: the shards "
                                    "must share one error bound (all-reduce MAX of clb_searcher_get_bound_consts)", (long long)n_shards);
     w.pending.valid = false;
-    Batch q = make_batch(d_Q, B, T, nprobe, k);     // unfiltered, as phase 1 was
+    // phase 1's filters are in the candidate list it left on the slot (cand / cand_hdr / ncand): everything from here on
+    // reads only that list, and the two-pass proof holds for whatever candidate set it is given -- no filter operand
+    Batch q = make_batch(d_Q, B, T, nprobe, k);
+    q.filt_now = pd.filt_now;       // ... but the selection kernels are chosen by the same candidate capacity
     q.d_out_pids = d_out_pids; q.d_out_scores = d_out_scores; q.d_n_cand = d_n_cand;
     q.phase = 2; q.d_all_top = d_all_top; q.n_shards = (int)n_shards;
     return run_search(s, w, (hipStream_t)hip_stream, q);
@@ -1712,10 +1739,36 @@ int clb_filter_create_pids(clb_searcher* s, const int64_t* pids, int64_t n, clb_
         DevWord<int> err;
         CLB_TRY(upload(d_pids, pids, sizeof(int64_t) * n, s->stream));
         CLB_TRY(err.init(s->stream));
-        hipLaunchKernelGGL(filter_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, d_pids.as<int64_t>(),
+        hipLaunchKernelGGL(filter_mark_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, d_pids.as<int64_t>(),
                            n, s->pid_offset, (int)s->n_docs, f->bits.as<uint32_t>(), err.ptr());
         CLB_TRY(err.read(s->stream));        // ... before d_pids and the host array go away
         if (err.value) return fail(CLB_EBOUNDS, "a pid outside the searcher's passages");
+    }
+    return filter_finish(s, std::move(f), out);
+}
+
+int clb_filter_create_pids_global(clb_searcher* s, const int64_t* pids, int64_t n, clb_filter** out, int64_t* n_inside) {
+    if (out) *out = nullptr;
+    if (n_inside) *n_inside = 0;
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    if (!out || !n_inside) return fail(CLB_EARGUMENT, "out or n_inside is null");
+    if (n < 0 || (n > 0 && !pids)) return fail(CLB_EARGUMENT, "pids is null or n < 0");
+    FilterPtr f(nullptr, clb_filter_destroy);
+    CLB_TRY(filter_new(s, f));
+    CLB_HIP(hipMemsetAsync(f->bits.p, 0, f->bits.bytes, s->stream));
+    if (n > 0) {       // range test, marking and count in one pass over the list, on the device
+        DevBuf d_pids;
+        DevWord<int> err;
+        DevWord<unsigned long long> inside;
+        CLB_TRY(upload(d_pids, pids, sizeof(int64_t) * n, s->stream));
+        CLB_TRY(err.init(s->stream));
+        CLB_TRY(inside.init(s->stream));
+        hipLaunchKernelGGL(filter_mark_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream,
+                           d_pids.as<int64_t>(), n, s->pid_offset, (int)s->n_docs, f->bits.as<uint32_t>(), err.ptr(), inside.ptr());
+        CLB_TRY(err.read(s->stream));        // ... before d_pids and the host array go away
+        CLB_TRY(inside.read(s->stream));
+        if (err.value) return fail(CLB_EBOUNDS, "a pid < 1 in a global pid list");
+        *n_inside = (int64_t)inside.value;
     }
     return filter_finish(s, std::move(f), out);
 }

@@ -486,14 +486,36 @@ static __global__ __launch_bounds__(kScanBlock) void bitmap_emit_kernel(uint32_t
 
 // Building a clb_filter.  From a pid list (as search returns them: 1-based, pid_offset added; duplicates and any order):
 // one thread per pid sets its bit, like mark_candidates_kernel; a pid outside the shard sets *err and marks nothing.
+// GLOBAL (clb_filter_create_pids_global): the list is a shard GROUP's, handed to every shard as it is -- a pid of another
+// shard is skipped, only a pid < 1 sets *err -- and *inside receives the number of entries that fell inside this shard
+// (duplicates counted): one wave-reduced atomic per wave, as filter_count_kernel gives its count.
 // grid = ceil(n / 256), block = 256.
+template <bool GLOBAL = false>
 static __global__ __launch_bounds__(256) void filter_mark_kernel(const int64_t* __restrict__ pids, int64_t n, int64_t pid_offset,
-                                                                 int n_docs, uint32_t* __restrict__ bits, int* __restrict__ err) {
+                                                                 int n_docs, uint32_t* __restrict__ bits, int* __restrict__ err,
+                                                                 unsigned long long* __restrict__ inside = nullptr) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int64_t p = pids[i] - pid_offset - 1;
-    if (p < 0 || p >= (int64_t)n_docs) { atomicOr(err, 1); return; }
-    atomicOr(&bits[p >> 5], 1u << (p & 31));
+    if constexpr (!GLOBAL) {
+        if (i >= n) return;
+        const int64_t p = pids[i] - pid_offset - 1;
+        if (p < 0 || p >= (int64_t)n_docs) { atomicOr(err, 1); return; }
+        atomicOr(&bits[p >> 5], 1u << (p & 31));
+    } else {
+        int c = 0;          // every lane stays for the reduction
+        if (i < n) {
+            const int64_t pid = pids[i];
+            if (pid < 1) {
+                atomicOr(err, 1);
+            } else if (pid > pid_offset && pid - pid_offset <= (int64_t)n_docs) {
+                const int64_t p = pid - pid_offset - 1;
+                atomicOr(&bits[p >> 5], 1u << (p & 31));
+                c = 1;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        if ((threadIdx.x & 63) == 0 && c) atomicAdd(inside, (unsigned long long)c);
+    }
 }
 // The searcher's passages that hold at least one embedding, in the same layout (FilterArgs::live): one thread per word.
 static __global__ __launch_bounds__(256) void passage_live_kernel(const uint32_t* __restrict__ doc_off, int n_docs,

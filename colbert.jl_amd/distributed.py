@@ -241,14 +241,23 @@ class DeviceSearch:
                                 f"elements on {self.dev}, got {getattr(Qdev, 'dtype', type(Qdev))} "
                                 f"{tuple(getattr(Qdev, 'shape', ()))} on {getattr(Qdev, 'device', '?')}")
 
-    def phase1(self, Qdev):
+    def phase1(self, Qdev, filters=None, scope="candidates"):
         """Two-phase sharded search, first half (clb_search_shard_phase1): everything up to pass 1 on this shard.
-        Returns the (B, k) tensor of the shard's k largest approximate scores per query, to be all-gathered."""
+        Returns the (B, k) tensor of the shard's k largest approximate scores per query, to be all-gathered.
+        `filters` / `scope` as in __call__ (clb_search_shard_phase1_filtered_slot: at most 64 queries per call when one is
+        filtered); phase2 takes none -- it continues on the filtered candidates phase 1 left on the slot."""
         import torch
         self._check_queries(Qdev)
         if not hasattr(self, "local_top"):
             self.local_top = torch.empty((self.B, self.k), dtype=torch.float32, device=self.dev)
         st = torch.cuda.current_stream(self.dev).cuda_stream
+        if filters is not None:
+            from .searcher import _scope_code
+            check(lib().clb_search_shard_phase1_filtered_slot(
+                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
+                self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)), C.c_void_p(self.local_top.data_ptr()),
+                C.c_void_p(st)))
+            return self.local_top
         check(lib().clb_search_shard_phase1_slot(self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B),
                                             i64(self.nprobe), i64(self.k), C.c_void_p(self.local_top.data_ptr()),
                                             C.c_void_p(st)))

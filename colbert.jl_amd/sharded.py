@@ -1,0 +1,382 @@
+"""ShardedSearcher: one handle over a passage shard group, with `Searcher`'s calling conventions and GLOBAL pids.
+
+The collection is cut into contiguous pid ranges (sharding.py), one `Searcher` per range.  A search runs on every shard and
+the per-shard top-k lists are merged (distributed.py); filters, appends and removals are routed to the shards by pid range.
+Two exchange protocols:
+  * "two_phase": phase 1 on every shard (clb_search_shard_phase1_filtered_slot) -> all-gather of the shards' k largest
+    approximate scores -> phase 2 at the global threshold -> all-gather of the packed per-shard top-k -> merge_packed;
+  * "single": every shard searches with its own threshold (DeviceSearch.__call__) -> packed all-gather -> merge_packed.
+A filter acts where phase 1 makes a shard's candidate list; everything after that reads only the list, so phase 2 takes
+no filter.
+
+The shards live in one process (`group=None`; on one device, or one device each) or one or more per rank of a
+torch.distributed process group: every method is then a COLLECTIVE -- all ranks call it with the same arguments -- and its
+result is identical on every rank.  Over gloo the exchanges are staged through host memory.  Shards of one process on
+SEVERAL devices are served by copying the gathered blocks to each shard's device; that path, like any run on more than
+one physical GPU, is not covered by the test suite (its machines have one GPU)."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence
+
+import numpy as np
+
+from ._lib import BoundsError, ColBERTError, check, colmajor, fptr, i64, lib
+from .searcher import PassageFilter, _scope_code
+
+_PROTOCOLS = ("auto", "two_phase", "single")
+_PIECE = 64          # queries per exchange: a filtered phase 1 carries at most 64 filter handles (include/colbert_hip.h)
+
+
+# ---- host logic (no device): the pid tiling of a group ----------------------------------------------------------------
+def check_tiling(ranges) -> np.ndarray:
+    """ranges: (pid_offset, num_docs) per shard, in pid order -> boundaries [n_shards + 1] (passages before each shard, then
+    the end), or ColBERTError when shard r + 1 does not start where shard r ends."""
+    r = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+    if r.shape[0] == 0:
+        raise ColBERTError("a shard group needs at least one shard")
+    for i in range(r.shape[0] - 1):
+        if r[i + 1, 0] != r[i, 0] + r[i, 1]:
+            raise ColBERTError(f"the shards do not tile a contiguous pid range: shard {i} ends at passage {r[i, 0] + r[i, 1]}, "
+                               f"shard {i + 1} has pid_offset {r[i + 1, 0]}")
+    return np.concatenate([r[:, 0], [r[-1, 0] + r[-1, 1]]])
+
+
+def check_group_pids(pids, bounds) -> np.ndarray:
+    """pids as a flat int64 array; BoundsError when one lies outside the group's passages bounds[0]+1 .. bounds[-1]."""
+    p = np.ascontiguousarray(np.asarray(pids).reshape(-1), dtype=np.int64)
+    bad = np.nonzero((p <= bounds[0]) | (p > bounds[-1]))[0]
+    if bad.size:
+        raise BoundsError(f"pid {int(p[bad[0]])} (entry {int(bad[0])}) outside {int(bounds[0]) + 1}..{int(bounds[-1])}, "
+                          "the passages of the shard group")
+    return p
+
+
+def route_pids(pids, bounds):
+    """Global pids -> one array per shard (the pids of that shard, in list order, duplicates kept)."""
+    p = check_group_pids(pids, bounds)
+    shard = np.searchsorted(bounds, p, side="left") - 1          # bounds[i] < p <= bounds[i + 1]
+    return [p[shard == i] for i in range(len(bounds) - 1)]
+
+
+def slice_mask(mask, bounds):
+    """A boolean array over the group's passages -> one slice per shard."""
+    m = np.asarray(mask)
+    n = int(bounds[-1] - bounds[0])
+    if m.dtype != np.bool_ or m.shape != (n,):
+        raise ColBERTError(f"mask must be a boolean array of num_docs={n} entries")
+    return [m[int(bounds[i] - bounds[0]):int(bounds[i + 1] - bounds[0])] for i in range(len(bounds) - 1)]
+
+
+class ShardedFilter:
+    """A passage set over a shard group: one resident PassageFilter per local shard (`parts`), made by
+    `ShardedSearcher.make_filter` and refused by any other group.  `count` is the population over the whole group.  An append
+    to the group invalidates it (the library refuses it: "filter made before an append; make another"); a removal does not."""
+
+    def __init__(self, group: "ShardedSearcher", parts, count: int):
+        self.group, self.parts, self.count = group, list(parts), int(count)
+
+    def close(self):
+        for f in self.parts:
+            f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self):
+        return self.count
+
+
+class ShardedSearcher:
+    """See the module docstring.  `shards`: this process's open `Searcher`s in pid order (with `group`: this rank's, and
+    every rank holds the same number of them; rank r's pids come before rank r + 1's).  The handle takes the shards over:
+    `close()` closes them."""
+
+    def __init__(self, shards: Sequence, group=None, encoder=None):
+        self.shards = list(shards)
+        self.group, self.encoder = group, encoder
+        if not self.shards:
+            raise ColBERTError("a shard group needs at least one shard")
+        desc = np.array([[s.pid_offset, s.num_docs, s.dim, s.nbits, s.num_centroids] for s in self.shards], dtype=np.int64)
+        self.rank, self.world = 0, 1
+        if group is not None:
+            import torch.distributed as dist
+            self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
+            desc = self._gather(desc).reshape(-1, 5)          # every rank's shards, in rank order
+        for name, col in (("dim", 2), ("nbits", 3), ("K", 4)):
+            if np.any(desc[:, col] != desc[0, col]):
+                raise ColBERTError(f"the shards of a group must agree on {name}: got {desc[:, col].tolist()}")
+        self._bounds = check_tiling(desc[:, :2])
+        self.dim = int(desc[0, 2])
+        self._first = self.rank * len(self.shards)         # group index of this process's first shard
+        self._runs = {}
+        self.last_num_candidates = 0
+        self._share_bounds()
+
+    @classmethod
+    def from_index(cls, index: dict, n_shards: int, devices=None, encoder=None):
+        """Cut an in-memory index into `n_shards` contiguous shards (sharding.shard_index) in this process; `devices`: one
+        device index per shard (default: all on device 0)."""
+        from .searcher import Searcher
+        from .sharding import shard_index
+        devices = [0] * n_shards if devices is None else list(devices)
+        if len(devices) != n_shards:
+            raise ColBERTError("devices must name one device per shard")
+        shards = []
+        try:
+            for r in range(n_shards):
+                sub, off = shard_index(index, r, n_shards)
+                shards.append(Searcher(index=sub, device=devices[r], pid_offset=off))
+            return cls(shards, encoder=encoder)
+        except Exception:
+            for s in shards:
+                s.close()
+            raise
+
+    # -- members ----------------------------------------------------------------------------------
+    @property
+    def num_docs(self) -> int:
+        return int(self._bounds[-1] - self._bounds[0])
+
+    @property
+    def shard_ranges(self):
+        """The global pids of every shard of the group, in order: a list of `range`s."""
+        return [range(int(self._bounds[i]) + 1, int(self._bounds[i + 1]) + 1) for i in range(len(self._bounds) - 1)]
+
+    def close(self):
+        self._runs = {}
+        for s in self.shards:
+            s.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # -- exchanges --------------------------------------------------------------------------------
+    def _staged(self) -> bool:
+        import torch.distributed as dist
+        return dist.get_backend(self.group) != "nccl"        # gloo: through host memory
+
+    def _gather_tensor(self, t, gather):
+        """`gather` (all_gather_scores / all_gather_packed) of tensor t over the group, staged through the host where the
+        backend has no device collectives; the result stays where the exchange left it."""
+        return gather(t.cpu().contiguous() if self._staged() else t.contiguous(), self.group)
+
+    def _gather(self, a: np.ndarray) -> np.ndarray:
+        """host array (n, m) int64 -> (world, n, m) on every rank"""
+        import torch
+        from .distributed import all_gather_scores
+        t = torch.from_numpy(np.ascontiguousarray(a))
+        if not self._staged():
+            t = t.to(torch.device("cuda", self.shards[0].device))
+        return self._gather_tensor(t, all_gather_scores).cpu().numpy()
+
+    def _share_bounds(self):
+        """One error bound on every shard of the group.  Set constants are only ever raised: get on every shard, element-wise
+        maximum, set on every shard."""
+        from .distributed import share_bound_consts, sync_bound_consts
+        share_bound_consts(self.shards)
+        if self.group is not None:
+            sync_bound_consts(self.shards[0], self.group)
+            share_bound_consts(self.shards)
+
+    def _local_bounds(self, j: int):
+        return int(self._bounds[self._first + j]), int(self._bounds[self._first + j + 1])
+
+    # -- filters ----------------------------------------------------------------------------------
+    def make_filter(self, pids=None, mask=None) -> ShardedFilter:
+        """A resident passage set over the group.  Exactly one of: `pids`, GLOBAL passage ids (any order, duplicates allowed;
+        outside 1..num_docs of the group: BoundsError before any shard is called) -- the list goes unchanged to every local
+        shard (clb_filter_create_pids_global) -- or `mask`, a boolean array over the group's passages."""
+        if (pids is None) == (mask is None):
+            raise ColBERTError("make_filter takes exactly one of pids= and mask=")
+        parts = []
+        try:
+            if pids is not None:
+                p = check_group_pids(pids, self._bounds)
+                for s in self.shards:
+                    h, n_in = C.c_void_p(), i64(0)
+                    check(lib().clb_filter_create_pids_global(s._h, fptr(p), i64(p.size), C.byref(h), C.byref(n_in)))
+                    f = PassageFilter(s, h, lib().clb_filter_count(h))
+                    f.n_inside = int(n_in.value)
+                    parts.append(f)
+            else:
+                slices = slice_mask(mask, self._bounds)
+                for j, s in enumerate(self.shards):
+                    parts.append(s.make_filter(mask=np.ascontiguousarray(slices[self._first + j])))
+            count = sum(f.count for f in parts)
+            if self.group is not None:
+                count = int(self._gather(np.array([[count]], dtype=np.int64)).sum())
+        except Exception:
+            for f in parts:
+                f.close()
+            raise
+        return ShardedFilter(self, parts, count)
+
+    def _shard_filters(self, filters, B: int):
+        """`filters` of a search call -> per local shard a list of B PassageFilters / None, or None when no query is filtered."""
+        if filters is None:
+            return None
+        if isinstance(filters, ShardedFilter):
+            filters = [filters] * B
+        filters = list(filters)
+        if len(filters) != B:
+            raise ColBERTError(f"filters must be one ShardedFilter or a sequence of B={B} entries (None = unfiltered)")
+        for j, f in enumerate(filters):
+            if f is None:
+                continue
+            if not isinstance(f, ShardedFilter) or f.group is not self:
+                raise ColBERTError(f"filters[{j}] is not a ShardedFilter of this shard group")
+        if all(f is None for f in filters):
+            return None
+        return [[None if f is None else f.parts[i] for f in filters] for i in range(len(self.shards))]
+
+    # -- search -----------------------------------------------------------------------------------
+    def _run(self, i: int, T: int, B: int, k: int, nprobe: int):
+        from .distributed import DeviceSearch
+        key = (i, T, B, k, nprobe)
+        if key not in self._runs:
+            self._runs[key] = DeviceSearch(self.shards[i], T, B, k, nprobe)
+        return self._runs[key]
+
+    def _two_pass(self, T: int) -> bool:
+        """every local shard runs the two-pass mode for queries of T tokens (set the mode alike on all ranks)"""
+        return all(s.mode == 1 for s in self.shards) and T <= 32
+
+    def _piece(self, q, k: int, nprobe: int, filters, scope: str, two_phase: bool):
+        """One exchange for the queries q (dim, T, B <= 64) -> (pids (B, k), scores (B, k), n_cand [B]) as numpy."""
+        import torch
+        from .distributed import all_gather_packed, all_gather_scores, merge_packed, packed_topk_bytes
+        T, B = q.shape[1], q.shape[2]
+        L = len(self.shards)
+        host_q = torch.from_numpy(np.array(q.transpose(2, 1, 0), order="C"))            # (B, T, dim), a copy of the caller's
+        runs = [self._run(i, T, B, k, nprobe) for i in range(L)]
+        Qd = [host_q.to(r.dev) for r in runs]
+        if two_phase:
+            tops = [r.phase1(Qd[i], None if filters is None else filters[i], scope) for i, r in enumerate(runs)]
+            dev0 = runs[0].dev
+            local = torch.stack([t.to(dev0) for t in tops]).view(L * B, k)             # this process's blocks
+            if self.group is not None:
+                local = self._gather_tensor(local, all_gather_scores)                   # (world, L * B, k)
+            all_top = local.reshape(-1, B, k)
+            for i, r in enumerate(runs):
+                r.phase2(Qd[i], all_top.to(r.dev).contiguous())
+        else:
+            for i, r in enumerate(runs):
+                r(Qd[i], None if filters is None else filters[i], scope)
+        # one block per process: its shards' packed top-k lists, then its candidate counts
+        dev0 = runs[0].dev
+        nbytes = packed_topk_bytes(k, B)
+        ncand = torch.stack([r.ncand.to(dev0) for r in runs]).sum(0)
+        block = torch.cat([r.packed.to(dev0) for r in runs] + [ncand.view(torch.uint8)])
+        g = self._gather_tensor(block, all_gather_packed) if self.group is not None else block.view(1, -1)
+        g = g.to(dev0)
+        lists = g[:, :L * nbytes].contiguous().view(-1, nbytes)
+        n = g[:, L * nbytes:].contiguous().view(torch.int64).view(-1, B).sum(0)
+        mp, ms = merge_packed(lists, B, k)
+        return mp.cpu().numpy(), ms.cpu().numpy(), n.cpu().numpy()
+
+    def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
+                     scope="candidates", protocol="auto"):
+        """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B]), GLOBAL pids, layouts and padding (pid 0 /
+        -Inf) as `Searcher.search_batch`; n_candidates is the sum over the shards.  `filters`: one ShardedFilter or a sequence
+        of B entries (None = that query is unfiltered); with filters the result is always padded.  Without, a query for which
+        the whole group holds fewer than k candidates raises BoundsError unless `pad_short`.  Any B: batches of more than 64
+        queries run as pieces of 64.  `protocol`: "two_phase", "single", or "auto" -- two-phase where every shard runs the
+        two-pass mode for this query length, the single exchange otherwise (general-shape shards)."""
+        q = colmajor(Q, np.float32)
+        if q.ndim != 3 or q.shape[0] != self.dim:
+            raise ColBERTError(f"Q must be (dim={self.dim}, T, B)")
+        if protocol not in _PROTOCOLS:
+            raise ColBERTError(f"protocol must be one of {_PROTOCOLS}, got {protocol!r}")
+        _scope_code(scope)
+        k, B = int(k), q.shape[2]
+        nprobe = int(nprobe or self.shards[0].config.nprobe)
+        per_shard = self._shard_filters(filters, B)
+        two_phase = protocol == "two_phase" or (protocol == "auto" and self._two_pass(q.shape[1]))
+        pids = np.zeros((k, B), dtype=np.int64, order="F"); scores = np.zeros((k, B), dtype=np.float32, order="F")
+        ncand = np.zeros(B, dtype=np.int64)
+        for b0 in range(0, B, _PIECE):
+            b1 = min(B, b0 + _PIECE)
+            f = None if per_shard is None else [x[b0:b1] for x in per_shard]
+            p, s, n = self._piece(q[:, :, b0:b1], k, nprobe, f, scope, two_phase)
+            pids[:, b0:b1] = p.T; scores[:, b0:b1] = s.T; ncand[b0:b1] = n
+        if filters is None and not pad_short:
+            short = np.nonzero(ncand < k)[0]
+            if short.size:                                                         # searching.jl:127
+                b = int(short[0])
+                raise BoundsError(f"query {b} has {int(ncand[b])} candidate passages, fewer than k={k}")
+        return pids, scores, ncand
+
+    def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates", protocol="auto"):
+        """One query, Q (dim, T) -> (pids Int64[k], scores Float32[k]) as `Searcher.search_embeddings`; the candidate count
+        is left in `last_num_candidates`."""
+        q = colmajor(Q, np.float32)
+        if q.ndim != 2 or q.shape[0] != self.dim:
+            raise ColBERTError(f"Q must be (dim={self.dim}, T)")
+        p, s, n = self.search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe,
+                                    filters=None if filter is None else [filter], scope=scope, protocol=protocol)
+        self.last_num_candidates = int(n[0])
+        return np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(s[:, 0])
+
+    def search(self, query: str, k: int, *, filter=None, scope="candidates", protocol="auto"):
+        """search(searcher, query::String, k) over the group, with the attached encoder."""
+        if self.encoder is None:
+            raise ColBERTError("no query encoder attached: pass encoder=... or use search_embeddings(Q, k)")
+        Q = self.encoder.encode_queries([query])
+        return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope, protocol=protocol)
+
+    # -- append: to the LAST shard, the only range that can grow without colliding with a neighbour -------------------
+    def _owns_last(self) -> bool:
+        return self.rank == self.world - 1
+
+    def _appended(self, n_new: int) -> range:
+        first = int(self._bounds[-1]) + 1
+        self._bounds[-1] += n_new
+        self._share_bounds()          # the grown shard's constants may have risen: the next two-phase search needs one bound
+        return range(first, int(self._bounds[-1]) + 1)
+
+    def add_compressed(self, codes, residuals, doclens) -> range:
+        """`Searcher.add_compressed` on the group's last shard; returns the GLOBAL pids of the new passages.  Afterwards the
+        group's bound constants are shared again.  ShardedFilters made before are refused by the next search."""
+        n_new = int(np.asarray(doclens.cpu() if hasattr(doclens, "data_ptr") else doclens).size)
+        if self._owns_last():
+            self.shards[-1].add_compressed(codes, residuals, doclens)
+        return self._appended(n_new)
+
+    def add_embeddings(self, embs, doclens) -> range:
+        """`Searcher.add_embeddings` (compressed with the index's own codec) on the group's last shard."""
+        n_new = int(np.asarray(doclens.cpu() if hasattr(doclens, "data_ptr") else doclens).size)
+        if self._owns_last():
+            self.shards[-1].add_embeddings(embs, doclens)
+        return self._appended(n_new)
+
+    def add_passages(self, texts) -> range:
+        """encode_passages with the attached encoder, then add_embeddings."""
+        if self.encoder is None:
+            raise ColBERTError("no encoder attached: pass encoder=... or use add_embeddings(embs, doclens)")
+        texts = list(texts)
+        if self._owns_last():
+            embs, doclens = self.encoder.encode_passages(texts)
+            self.shards[-1].add_embeddings(embs, doclens)
+        return self._appended(len(texts))
+
+    # -- remove -----------------------------------------------------------------------------------
+    def remove_passages(self, pids) -> int:
+        """`Searcher.remove_passages` with GLOBAL pids routed to their shards by range (a pid outside the group: BoundsError
+        before any shard is touched); returns the number of passages that lost embeddings, over the whole group.  Pids are
+        stable and filters made before stay valid."""
+        parts = route_pids(pids, self._bounds)
+        n = 0
+        for j, s in enumerate(self.shards):
+            p = parts[self._first + j]
+            if p.size:
+                n += s.remove_passages(p)
+        if self.group is not None:
+            n = int(self._gather(np.array([[n]], dtype=np.int64)).sum())
+        return n

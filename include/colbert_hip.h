@@ -161,7 +161,8 @@ int clb_search_batch_device_slot(clb_searcher* s, int slot, const float* d_Q, in
  *   phase 1: S1..pass 1 on this shard; d_local_top (B, k) = its k largest approximate scores per query (-Inf padded);
  *   the caller all-gathers these blocks over the shards: d_all_top = [n_shards][B][k];
  *   phase 2: selection at the k-th largest gathered score, exact pass, top-k -- outputs as clb_search_batch_device.
- * Phase 2 must follow phase 1 of the same batch on the same handle and stream. */
+ * Phase 2 must follow phase 1 of the same batch on the same handle and stream.  With filters:
+ * clb_search_shard_phase1_filtered_slot (below, "Filtered search"). */
 int clb_search_shard_phase1(clb_searcher* s, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
                             float* d_local_top, void* hip_stream);
 int clb_search_shard_phase2(clb_searcher* s, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
@@ -243,6 +244,13 @@ typedef struct clb_filter clb_filter;
  * a pid outside pid_offset+1 .. pid_offset+n_docs is CLB_EBOUNDS.  n = 0 is the empty filter.  The bitmap is built on the
  * device. */
 int clb_filter_create_pids(clb_searcher* s, const int64_t* pids, int64_t n, clb_filter** out);
+/* clb_filter_create_pids for a shard GROUP: `pids` is a GLOBAL list, handed unchanged to every shard of the group.  The pids
+ * inside this shard's range pid_offset+1 .. pid_offset+n_docs set their bit; pids of other shards are skipped, not errors;
+ * a pid < 1 is CLB_EBOUNDS (that the list stays inside the GROUP's passages is the caller's check: a shard does not know
+ * its group).  *n_inside = the number of list entries that fell inside this shard, duplicates counted (clb_filter_count
+ * stays the population).  Range test, marking and count are one pass over the list on the device.  n = 0, or a list wholly
+ * outside the shard, gives a valid empty filter: under CLB_FILTER_ALL the shard then has no candidate. */
+int clb_filter_create_pids_global(clb_searcher* s, const int64_t* pids, int64_t n, clb_filter** out, int64_t* n_inside);
 /* the bitmap itself (host words): n_words must be ceil(n_docs / 32), else CLB_EARGUMENT; bits past n_docs are cleared. */
 int clb_filter_create_bitmap(clb_searcher* s, const uint32_t* words, int64_t n_words, clb_filter** out);
 /* number of passages in the set (a host value, fixed at creation); 0 for a null handle */
@@ -270,6 +278,20 @@ int clb_search_batch_filtered(clb_searcher* s, const float* Q, int64_t T, int64_
 int clb_search_batch_filtered_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
                                           int64_t k, const clb_filter* const* filters, int scope, int64_t* d_out_pids,
                                           float* d_out_scores, int64_t* d_n_cand, void* hip_stream);
+/* clb_search_shard_phase1_slot with the `filters` / `scope` operands of clb_search_batch_filtered_device_slot: the filtered
+ * search across the shards of a group.  Each shard's filters are its OWN (clb_filter_create_pids_global cuts one global pid
+ * list per shard); they act where phase 1 makes the shard's candidate list, so d_local_top holds approximate scores of
+ * filtered candidates only, and clb_search_shard_phase2(_slot) -- its signature unchanged, and with no filter operand: it
+ * continues on the candidate list phase 1 left on the slot, and the two-pass proof holds for whatever candidate set it is
+ * given -- returns the filtered result, d_n_cand the counts AFTER the filter.  The same argument checks as both calls it
+ * extends (a bad scope, a filter of another searcher or from before an append: CLB_EARGUMENT).  filters == NULL, or no
+ * non-NULL entry, launches exactly what clb_search_shard_phase1_slot launches (which IS this call with filters == NULL).
+ * The phase calls keep the whole batch on one slot, and a launch carries at most 64 filter handles: a call in which some
+ * query is filtered takes B <= 64 queries, CLB_EUNSUPPORTED (naming the limit) beyond -- split the batch, one phase-1 /
+ * phase-2 pair per piece (ShardedSearcher does). */
+int clb_search_shard_phase1_filtered_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                          int64_t k, const clb_filter* const* filters, int scope, float* d_local_top,
+                                          void* hip_stream);
 
 /* retrieve()  (src/search/ranking.jl:23-44) on its own -- test hook.  out_pids needs n_docs entries. */
 int clb_retrieve(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe, int64_t* out_pids,

@@ -94,6 +94,19 @@ function _filter_create_bitmap(handle::Ptr{Cvoid}, words::Vector{UInt32})
     end
     h[]
 end
+"""
+the same for a shard GROUP: `pids` is a global list handed unchanged to every shard; pids of other shards are skipped
+(clb_filter_create_pids_global).  Returns the filter and the number of list entries that fell inside this shard.
+"""
+function _filter_create_pids_global(handle::Ptr{Cvoid}, pids::Vector{Int})
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    n_inside = Ref{Int64}(0)
+    GC.@preserve pids begin
+        _check(ccall((:clb_filter_create_pids_global, libcolbert), Cint,
+            (Ptr{Cvoid}, Ptr{Int64}, Int64, Ref{Ptr{Cvoid}}, Ref{Int64}), handle, pids, length(pids), h, n_inside))
+    end
+    h[], Int(n_inside[])
+end
 _filter_count(h::Ptr{Cvoid}) = Int(ccall((:clb_filter_count, libcolbert), Int64, (Ptr{Cvoid},), h))
 _filter_destroy(h::Ptr{Cvoid}) = ccall((:clb_filter_destroy, libcolbert), Cint, (Ptr{Cvoid},), h)
 
@@ -277,6 +290,25 @@ The library refuses phase 2 with more than one shard until this (or clb_searcher
 """
 sync_bound_consts!(handle::Ptr{Cvoid}, c::Communicator) =
     _check(ccall((:clb_searcher_sync_bound_consts, libcolbert), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), handle, c.handle))
+
+"""
+    shard_phase1_filtered!(searcher_handle, slot, d_Q, T, B, nprobe, k, filters, scope, d_local_top, stream)
+
+Phase 1 of the two-phase sharded search with one filter handle per query (clb_search_shard_phase1_filtered_slot):
+`filters` holds B handles of THIS shard (`C_NULL` = that query is unfiltered; an empty vector = none is), `scope` is 0
+(candidates) or 1 (all).  `d_Q` and `d_local_top` are device pointers; at most 64 queries per call when one is filtered.
+Phase 2 (clb_search_shard_phase2_slot) takes no filter: it continues on the candidate list phase 1 left on the slot.
+"""
+function shard_phase1_filtered!(handle::Ptr{Cvoid}, slot::Integer, d_Q::Ptr{Cvoid}, T::Integer, B::Integer, nprobe::Integer,
+                                k::Integer, filters::Vector{Ptr{Cvoid}}, scope::Integer, d_local_top::Ptr{Cvoid},
+                                stream::Ptr{Cvoid} = C_NULL)
+    isempty(filters) || length(filters) == B || throw(ArgumentError("filters must hold B handles"))
+    GC.@preserve filters begin
+        _check(ccall((:clb_search_shard_phase1_filtered_slot, libcolbert), Cint,
+            (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Int64, Int64, Int64, Ptr{Ptr{Cvoid}}, Cint, Ptr{Cvoid}, Ptr{Cvoid}),
+            handle, slot, d_Q, T, B, nprobe, k, isempty(filters) ? C_NULL : pointer(filters), scope, d_local_top, stream))
+    end
+end
 
 
 # ---- plain device arrays (clb_device_*): what the device-resident route of index() keeps in HBM ---------------------
