@@ -99,6 +99,12 @@ def lib() -> C.CDLL:
         l.clb_searcher_num_embeddings.restype = C.c_int64
         l.clb_searcher_remove.restype = C.c_int
         l.clb_searcher_remove.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        l.clb_searcher_update.restype = C.c_int
+        l.clb_searcher_update.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_int64)]
+        l.clb_searcher_update_device.restype = C.c_int
+        l.clb_searcher_update_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.POINTER(C.c_int64)]
         l.clb_filter_create_pids_global.restype = C.c_int
         l.clb_filter_create_pids_global.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
         l.clb_search_shard_phase1_filtered_slot.restype = C.c_int

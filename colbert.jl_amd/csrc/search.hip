@@ -14,6 +14,7 @@
 #include "remove_kernels.hpp"
 #include "search_kernels.hpp"
 #include "sort.hpp"
+#include "update_kernels.hpp"
 
 using namespace clb;
 
@@ -1087,7 +1088,19 @@ void launch_remove_rows(hipStream_t st, const clb_searcher* s, const uint32_t* n
                        s->residuals.as<Piece>(), (int)(row_bytes / sizeof(Piece)), codes_dst, reinterpret_cast<Piece*>(res_dst));
 }
 
-// The end of an append or a removal, after the arrays and counts of the changed index have been swapped in (h_ivf_off: the
+// the row splice of clb_searcher_update (update_kernels.hpp) in pieces of one size: s still holds the old index
+template <class Piece>
+void launch_splice_rows(hipStream_t st, const clb_searcher* s, const uint32_t* new_off, const uint32_t* named,
+                        const uint32_t* slot, const uint32_t* stage_off, int64_t n_rows, size_t row_bytes,
+                        const uint32_t* codes_stage, const uint8_t* res_stage, uint32_t* codes_dst, uint8_t* res_dst) {
+    const int64_t tiles = (n_rows + kSpliceTile - 1) / kSpliceTile;
+    hipLaunchKernelGGL(splice_rows_kernel<Piece>, dim3((unsigned)std::min<int64_t>(tiles, 8192)), dim3(256), 0, st,
+                       s->doc_off.as<uint32_t>(), new_off, named, slot, stage_off, (int)s->n_docs, n_rows,
+                       s->codes0.as<uint32_t>(), s->residuals.as<Piece>(), codes_stage, reinterpret_cast<const Piece*>(res_stage),
+                       (int)(row_bytes / sizeof(Piece)), codes_dst, reinterpret_cast<Piece*>(res_dst));
+}
+
+// The end of an append, a removal or an update, after the arrays and counts of the changed index have been swapped in (h_ivf_off: the
 // host copy of its K + 1 list offsets): what the handle derives from them, the workspaces, the generation.  Cannot fail.
 void finish_index_change(clb_searcher* s, IndexTables& tables, const std::vector<uint32_t>& h_ivf_off) {
     s->ivf_len_sorted = sorted_list_lengths(h_ivf_off);
@@ -1450,6 +1463,201 @@ static int searcher_remove_impl(clb_searcher* s, const int64_t* pids, int64_t n,
 }
 int clb_searcher_remove(clb_searcher* s, const int64_t* pids, int64_t n, int64_t* n_removed) {
     return searcher_remove_impl(s, pids, n, n_removed);
+}
+
+// clb_searcher_update / _device (include/colbert_hip.h), built like an append and a removal: the spliced codes0 / residuals /
+// doc_off, the merged inverted lists and the approximate-pass tables of the changed index stand beside the handle's arrays
+// until the last device work has been waited for; any return before the swaps leaves the handle untouched.
+static int searcher_update_impl(clb_searcher* s, int64_t n, const int64_t* pids, const int64_t* doclens, int64_t n_new_emb,
+                                const uint32_t* codes, const uint8_t* residuals, bool on_device, int64_t* n_changed) {
+    if (n_changed) *n_changed = 0;
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    if (n < 0 || n_new_emb < 0) return fail(CLB_EARGUMENT, "negative sizes");
+    if ((n > 0 && (!pids || !doclens)) || (n_new_emb > 0 && (!codes || !residuals))) return fail(CLB_EARGUMENT, "null argument");
+    Offsets add;            // the named passages among the new embeddings
+    CLB_TRY(passage_offsets(doclens, n, n_new_emb, "replaced passage", &add));
+    for (int64_t i = 0; i < n; ++i)
+        if (pids[i] <= s->pid_offset || pids[i] > s->pid_offset + s->n_docs)
+            return fail(CLB_EBOUNDS, "pid %lld (entry %lld) outside %lld..%lld", (long long)pids[i], (long long)i,
+                        (long long)(s->pid_offset + 1), (long long)(s->pid_offset + s->n_docs));
+    {   // a pid named twice: which of its two contents is meant?
+        std::vector<int64_t> sorted(pids, pids + n);
+        std::sort(sorted.begin(), sorted.end());
+        const auto twice = std::adjacent_find(sorted.begin(), sorted.end());
+        if (twice != sorted.end())
+            return fail(CLB_EARGUMENT, "pid %lld is named twice: an update takes one new content per passage", (long long)*twice);
+    }
+    if (n == 0) return CLB_OK;
+    const int64_t n_old = s->n_emb, n_docs = s->n_docs, K = s->K;
+    CLB_TRY(use_device(s->device));
+    CLB_HIP(hipDeviceSynchronize());      // searches of this handle and whatever wrote the caller's device arrays
+    const hipStream_t st = s->stream;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const size_t rows = (size_t)(s->dim / 8 * s->nbits);
+
+    // the new codes, 0-based and checked, in a buffer of the call's own; the replaced passages as a bitmap in a filter's
+    // layout and their place in the caller's list; the lengths of the changed index and their offsets
+    DevBuf codes_in, d_pids, stage_off, named, slot, len, doc_off;
+    DevWord<int> err;
+    DevWord<UpdateCounts> counts;
+    CLB_TRY(codes_in.alloc(sizeof(uint32_t) * n_new_emb));
+    CLB_TRY(err.init(st));
+    CLB_TRY(counts.init(st));
+    CLB_TRY(stage_codes(st, codes, kind, n_new_emb, K, codes_in.as<uint32_t>(), err.ptr()));
+    CLB_TRY(upload(d_pids, pids, sizeof(int64_t) * n, st));
+    CLB_TRY(upload(stage_off, add.off.data(), sizeof(uint32_t) * add.off.size(), st));
+    CLB_TRY(named.alloc(sizeof(uint32_t) * (size_t)((n_docs + 31) / 32)));
+    CLB_TRY(slot.alloc(sizeof(uint32_t) * n_docs));
+    CLB_TRY(len.alloc(sizeof(uint32_t) * (n_docs + 1)));
+    CLB_TRY(doc_off.alloc(sizeof(uint32_t) * (n_docs + 1)));
+    CLB_HIP(hipMemsetAsync(named.p, 0, named.bytes, st));
+    const dim3 per_pid((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(filter_mark_kernel<false>, per_pid, dim3(256), 0, st, d_pids.as<int64_t>(), n, s->pid_offset, (int)n_docs,
+                       named.as<uint32_t>(), err.ptr());
+    hipLaunchKernelGGL(update_slots_kernel, per_pid, dim3(256), 0, st, d_pids.as<int64_t>(), n, s->pid_offset, (int)n_docs,
+                       slot.as<uint32_t>());
+    hipLaunchKernelGGL(update_lengths_kernel, dim3((unsigned)((n_docs + 1 + 255) / 256)), dim3(256), 0, st,
+                       s->doc_off.as<uint32_t>(), named.as<uint32_t>(), slot.as<uint32_t>(), stage_off.as<uint32_t>(), (int)n_docs,
+                       len.as<uint32_t>(), counts.ptr());
+    CLB_TRY(err.read(st));                // ... before the host arrays go away
+    CLB_TRY(counts.read(st));
+    if (err.value & kErrCode) return bad_codes();
+    if (err.value) return fail(CLB_EBOUNDS, "a pid outside the searcher's passages");
+    const int64_t n_tot = n_old - (int64_t)counts.value.dropped + n_new_emb;
+    CLB_TRY(check_shard_limits(n_tot, n_docs));
+    if (counts.value.changed == 0) return CLB_OK;       // every named passage was empty and stays empty
+    CLB_TRY(exclusive_scan_u32(len.as<uint32_t>(), doc_off.as<uint32_t>(), (size_t)n_docs, st));
+
+    // the new rows where the splice reads them: in create's per-passage code order on the tuned path (over the new rows and
+    // their own offsets, as an append orders them), as given on the general path
+    DevBuf codes_staged, res_staged, res_in;
+    const uint32_t* codes_stage = codes_in.as<uint32_t>();
+    const uint8_t* res_stage = residuals;
+    if (n_new_emb > 0 && (!on_device || ((uintptr_t)residuals & 15))) {     // the kernels read 16-byte pieces
+        CLB_TRY(res_in.alloc(rows * n_new_emb));
+        CLB_HIP(hipMemcpyAsync(res_in.p, residuals, rows * n_new_emb, kind, st));
+        res_stage = res_in.as<uint8_t>();
+    }
+    if (n_new_emb > 0 && !s->generic) {
+        CLB_TRY(codes_staged.alloc(sizeof(uint32_t) * n_new_emb));
+        CLB_TRY(res_staged.alloc(rows * n_new_emb));
+        CLB_TRY(order_rows_by_code(st, codes_in.as<uint32_t>(), stage_off.as<uint32_t>(), n_new_emb, n, res_stage, rows,
+                                   codes_staged.as<uint32_t>(), res_staged.as<uint8_t>()));
+        res_in.release();       // order_rows_by_code has waited for the stream
+        codes_stage = codes_staged.as<uint32_t>();
+        res_stage = res_staged.as<uint8_t>();
+    }
+
+    // one splice of the rows, and the zero padding of one step
+    DevBuf codes0, res, live;
+    CLB_TRY(build_live_bitmap(st, doc_off.as<uint32_t>(), n_docs, &live));
+    CLB_TRY(alloc_padded_rows(st, n_tot, rows, &codes0, &res));
+    if (n_tot > 0) {
+        if (rows % 16 == 0)
+            launch_splice_rows<uint4>(st, s, doc_off.as<uint32_t>(), named.as<uint32_t>(), slot.as<uint32_t>(), stage_off.as<uint32_t>(),
+                                      n_tot, rows, codes_stage, res_stage, codes0.as<uint32_t>(), res.as<uint8_t>());
+        else if (rows % 4 == 0)
+            launch_splice_rows<uint32_t>(st, s, doc_off.as<uint32_t>(), named.as<uint32_t>(), slot.as<uint32_t>(), stage_off.as<uint32_t>(),
+                                         n_tot, rows, codes_stage, res_stage, codes0.as<uint32_t>(), res.as<uint8_t>());
+        else
+            launch_splice_rows<uint8_t>(st, s, doc_off.as<uint32_t>(), named.as<uint32_t>(), slot.as<uint32_t>(), stage_off.as<uint32_t>(),
+                                        n_tot, rows, codes_stage, res_stage, codes0.as<uint32_t>(), res.as<uint8_t>());
+    }
+
+    // the inverted lists.  Kept entries: a flag per old entry and its scan, as in a removal.  New entries: their local pids and
+    // the histogram of their codes, then two stable sorts -- by pid, then by code -- so that every list's new entries hold
+    // non-decreasing pids.  One pass over the lists puts both where a fresh build would.
+    DevBuf flag, pos, hist, add_off, ivf_off, ivf_pid, add_pid, add_pid2, add_code, add_code2;
+    CLB_TRY(flag.alloc(sizeof(uint32_t) * (n_old + 1)));
+    CLB_TRY(pos.alloc(sizeof(uint32_t) * (n_old + 1)));
+    CLB_TRY(hist.alloc(sizeof(uint32_t) * (K + 1)));
+    CLB_TRY(add_off.alloc(sizeof(uint32_t) * (K + 1)));
+    CLB_TRY(ivf_off.alloc(sizeof(uint32_t) * (K + 1)));
+    CLB_TRY(ivf_pid.alloc(sizeof(uint32_t) * n_tot));
+    CLB_TRY(add_pid.alloc(sizeof(uint32_t) * n_new_emb));
+    CLB_TRY(add_pid2.alloc(sizeof(uint32_t) * n_new_emb));
+    CLB_TRY(add_code.alloc(sizeof(uint32_t) * n_new_emb));
+    CLB_TRY(add_code2.alloc(sizeof(uint32_t) * n_new_emb));
+    hipLaunchKernelGGL(ivf_keep_flags_kernel, dim3((unsigned)((n_old + 1 + 255) / 256)), dim3(256), 0, st, s->ivf_pid.as<uint32_t>(),
+                       named.as<uint32_t>(), n_old, flag.as<uint32_t>());
+    CLB_TRY(exclusive_scan_u32(flag.as<uint32_t>(), pos.as<uint32_t>(), (size_t)n_old, st));
+    flag.release();         // the scan has been waited for
+    CLB_HIP(hipMemsetAsync(hist.p, 0, sizeof(uint32_t) * (K + 1), st));
+    if (n_new_emb > 0)
+        hipLaunchKernelGGL(update_hist_pid_kernel, dim3((unsigned)((n_new_emb + 255) / 256)), dim3(256), 0, st, codes_in.as<uint32_t>(),
+                           stage_off.as<uint32_t>(), d_pids.as<int64_t>(), s->pid_offset, n_new_emb, (int)n, hist.as<uint32_t>(),
+                           add_pid.as<uint32_t>());
+    CLB_TRY(exclusive_scan_u32(hist.as<uint32_t>(), add_off.as<uint32_t>(), (size_t)K, st));
+    int pid_bits = 1, code_bits = 1;
+    while (((int64_t)1 << pid_bits) < n_docs) ++pid_bits;
+    while (((int64_t)1 << code_bits) < K) ++code_bits;
+    CLB_TRY(sort_pairs_u32(add_pid.as<uint32_t>(), add_pid2.as<uint32_t>(), codes_in.as<uint32_t>(), add_code2.as<uint32_t>(),
+                           (size_t)n_new_emb, pid_bits, st));
+    CLB_TRY(sort_pairs_u32(add_code2.as<uint32_t>(), add_code.as<uint32_t>(), add_pid2.as<uint32_t>(), add_pid.as<uint32_t>(),
+                           (size_t)n_new_emb, code_bits, st));
+    const dim3 per_list((unsigned)((K + 1 + 255) / 256));
+    if (s->ivf_sorted) {
+        hipLaunchKernelGGL(ivf_splice_offsets_kernel, per_list, dim3(256), 0, st, s->ivf_off.as<uint32_t>(), pos.as<uint32_t>(),
+                           add_off.as<uint32_t>(), (int)(K + 1), ivf_off.as<uint32_t>());
+        const int64_t tiles = (n_old + kSpliceTile - 1) / kSpliceTile + (n_new_emb + kSpliceTile - 1) / kSpliceTile;
+        if (tiles > 0)
+            hipLaunchKernelGGL(ivf_splice_kernel, dim3((unsigned)std::min<int64_t>(tiles, 8192)), dim3(256), 0, st,
+                               s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), pos.as<uint32_t>(), n_old, add_off.as<uint32_t>(),
+                               add_code.as<uint32_t>(), add_pid.as<uint32_t>(), n_new_emb, (int)K, ivf_pid.as<uint32_t>());
+    } else {
+        // the caller's own list order: the kept entries in that order (a removal's compaction), the new ones behind them list
+        // by list (an append's merge); the lists stay unsorted
+        DevBuf kept_pid, kept_off;
+        const int64_t n_kept = n_tot - n_new_emb;
+        CLB_TRY(kept_pid.alloc(sizeof(uint32_t) * n_kept));
+        CLB_TRY(kept_off.alloc(sizeof(uint32_t) * (K + 1)));
+        hipLaunchKernelGGL(ivf_compact_kernel, dim3((unsigned)((n_old + 1 + 255) / 256)), dim3(256), 0, st, s->ivf_pid.as<uint32_t>(),
+                           pos.as<uint32_t>(), n_old, kept_pid.as<uint32_t>());
+        hipLaunchKernelGGL(ivf_compact_offsets_kernel, per_list, dim3(256), 0, st, s->ivf_off.as<uint32_t>(), pos.as<uint32_t>(),
+                           (int)(K + 1), kept_off.as<uint32_t>());
+        hipLaunchKernelGGL(append_offsets_kernel, per_list, dim3(256), 0, st, kept_off.as<uint32_t>(), add_off.as<uint32_t>(),
+                           (int)(K + 1), ivf_off.as<uint32_t>());
+        if (n_tot > 0) {
+            const int64_t tiles = (n_tot + kMergeTile - 1) / kMergeTile;
+            hipLaunchKernelGGL(ivf_merge_kernel, dim3((unsigned)std::min<int64_t>(tiles, 8192)), dim3(256), 0, st,
+                               kept_off.as<uint32_t>(), add_off.as<uint32_t>(), ivf_off.as<uint32_t>(), kept_pid.as<uint32_t>(),
+                               add_pid.as<uint32_t>(), (int)K, n_tot, ivf_pid.as<uint32_t>());
+        }
+        CLB_HIP(hipStreamSynchronize(st));      // kept_pid and kept_off go away here
+    }
+    CLB_HIP(hipGetLastError());
+    std::vector<uint32_t> h_ivf_off((size_t)K + 1);
+    CLB_HIP(hipMemcpyAsync(h_ivf_off.data(), ivf_off.p, sizeof(uint32_t) * (K + 1), hipMemcpyDeviceToHost, st));
+    CLB_HIP(hipStreamSynchronize(st));
+    if ((int64_t)h_ivf_off[K] != n_tot) return fail(CLB_EHIP, "spliced inverted lists hold %lld entries, expected %lld",
+                                                    (long long)h_ivf_off[K], (long long)n_tot);
+    pos.release();
+    codes_staged.release(); res_staged.release(); res_in.release();
+
+    // code | inv_norm words and bound constants of the changed index: inv_norm is quantised over the index's own range, which
+    // a new row may widen and a dropped row may narrow
+    IndexTables tables;
+    if (!s->generic) CLB_TRY(derive_index_tables(s, codes0.as<uint32_t>(), res.as<uint8_t>(), n_tot, &tables));
+    CLB_HIP(hipStreamSynchronize(st));
+    CLB_HIP(hipGetLastError());
+
+    // ---- nothing below can fail ----
+    swap_buf(s->codes0, codes0); swap_buf(s->residuals, res); swap_buf(s->doc_off, doc_off);
+    swap_buf(s->ivf_off, ivf_off); swap_buf(s->ivf_pid, ivf_pid); swap_buf(s->live, live);
+    s->n_emb = n_tot;
+    s->max_doclen = counts.value.longest;
+    finish_index_change(s, tables, h_ivf_off);
+    if (n_changed) *n_changed = counts.value.changed;
+    return CLB_OK;
+}
+int clb_searcher_update(clb_searcher* s, int64_t n, const int64_t* pids, const int64_t* doclens, int64_t n_new_emb,
+                        const uint32_t* codes, const uint8_t* residuals, int64_t* n_changed) {
+    return searcher_update_impl(s, n, pids, doclens, n_new_emb, codes, residuals, false, n_changed);
+}
+int clb_searcher_update_device(clb_searcher* s, int64_t n, const int64_t* pids, const int64_t* doclens, int64_t n_new_emb,
+                               const uint32_t* d_codes, const uint8_t* d_residuals, void* hip_stream, int64_t* n_changed) {
+    (void)hip_stream;     // the call waits for the whole device on entry, the work of that stream included
+    return searcher_update_impl(s, n, pids, doclens, n_new_emb, d_codes, d_residuals, true, n_changed);
 }
 // a count cannot carry an error code: a null handle gives -CLB_EARGUMENT and the message
 int64_t clb_searcher_generation(const clb_searcher* s) { return s ? s->generation : -(int64_t)fail(CLB_EARGUMENT, "null searcher"); }

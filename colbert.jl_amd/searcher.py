@@ -142,9 +142,35 @@ class Searcher:
     # -- ingest: append passages to the resident index (clb_searcher_append) ---------------------------
     @property
     def generation(self) -> int:
-        """Number of appends and removals that changed this searcher (0 after the constructor).  A HIP graph captured over
-        the searcher belongs to the generation it was made in; a PassageFilter outlives removals, not appends."""
+        """Number of appends, removals and updates that changed this searcher (0 after the constructor).  A HIP graph captured
+        over the searcher belongs to the generation it was made in; a PassageFilter outlives removals and updates, not appends."""
         return int(lib().clb_searcher_generation(self._h))
+
+    def _check_device_rows(self, codes, residuals):
+        """compressed rows as CUDA tensors -- `codes` 32-bit [n], `residuals` uint8 (n, dim/8*nbits) on this searcher's
+        device -> the HIP stream that produced them"""
+        import torch
+        if not (codes.is_cuda and residuals.is_cuda and codes.is_contiguous() and residuals.is_contiguous()
+                and codes.device.index == self.device and residuals.device.index == self.device):
+            raise ColBERTError("device arrays must be contiguous CUDA tensors on the searcher's device")
+        if codes.element_size() != 4 or codes.dim() != 1 or residuals.dtype != torch.uint8:
+            raise ColBERTError("codes must be a 32-bit vector, residuals uint8")
+        if tuple(residuals.shape) != (codes.numel(), self.dim // 8 * self.nbits):
+            raise ColBERTError("residuals must be (n_emb, dim/8*nbits)")
+        return torch.cuda.current_stream(codes.device).cuda_stream
+
+    @staticmethod
+    def _rows_to_host(codes, residuals):
+        """device rows in the layout of the index directory: codes UInt32[n], residuals (dim/8*nbits, n) column-major"""
+        return codes.cpu().numpy().view(np.uint32), np.asfortranarray(residuals.cpu().numpy().T)
+
+    def _check_host_rows(self, codes, residuals):
+        """compressed rows as numpy arrays -> codes UInt32[n], residuals (dim/8*nbits, n) column-major"""
+        co = np.ascontiguousarray(codes, dtype=np.uint32)
+        r = colmajor(residuals, np.uint8)
+        if co.ndim != 1 or r.shape != (self.dim // 8 * self.nbits, co.size):
+            raise ColBERTError("residuals must be (dim/8*nbits, n_emb)")
+        return co, r
 
     def add_compressed(self, codes, residuals, doclens, persist: bool = False) -> range:
         """Append passages compressed with the index's own codec behind the last passage, without rebuilding the resident
@@ -156,30 +182,17 @@ class Searcher:
         from (storage.append_chunk), after the device append has succeeded."""
         if persist and self.index_path is None:
             raise ColBERTError("persist=True needs a Searcher opened from an index_path")
-        rows = self.dim // 8 * self.nbits
         dl = np.ascontiguousarray(np.asarray(doclens.cpu() if hasattr(doclens, "data_ptr") else doclens), dtype=np.int64)
         first = self.pid_offset + self.num_docs + 1
         if hasattr(codes, "data_ptr"):
-            import torch
-            if not (codes.is_cuda and residuals.is_cuda and codes.is_contiguous() and residuals.is_contiguous()
-                    and codes.device.index == self.device and residuals.device.index == self.device):
-                raise ColBERTError("device arrays must be contiguous CUDA tensors on the searcher's device")
-            if codes.element_size() != 4 or codes.dim() != 1 or residuals.dtype != torch.uint8:
-                raise ColBERTError("codes must be a 32-bit vector, residuals uint8")
-            if tuple(residuals.shape) != (codes.numel(), rows):
-                raise ColBERTError("residuals must be (n_emb, dim/8*nbits)")
-            st = torch.cuda.current_stream(codes.device).cuda_stream
+            st = self._check_device_rows(codes, residuals)
             check(lib().clb_searcher_append_device(self._h, i64(dl.size), fptr(dl), i64(codes.numel()),
                                                    C.c_void_p(codes.data_ptr()), C.c_void_p(residuals.data_ptr()),
                                                    C.c_void_p(st)))
             if persist:
-                co = codes.cpu().numpy().view(np.uint32)
-                r = np.asfortranarray(residuals.cpu().numpy().T)
+                co, r = self._rows_to_host(codes, residuals)
         else:
-            co = np.ascontiguousarray(codes, dtype=np.uint32)
-            r = colmajor(residuals, np.uint8)
-            if co.ndim != 1 or r.shape != (rows, co.size):
-                raise ColBERTError("residuals must be (dim/8*nbits, n_emb)")
+            co, r = self._check_host_rows(codes, residuals)
             check(lib().clb_searcher_append(self._h, i64(dl.size), fptr(dl), i64(co.size), fptr(co), fptr(r)))
         self.num_docs = int(lib().clb_searcher_num_docs(self._h))
         self.num_embeddings = int(lib().clb_searcher_num_embeddings(self._h))
@@ -205,6 +218,53 @@ class Searcher:
             storage.remove_passages(self.index_path, p - self.pid_offset)
         return int(n.value)
 
+    def update_compressed(self, pids, codes, residuals, doclens, persist: bool = False) -> int:
+        """Replace the content of passages in place, keeping their pids (clb_searcher_update): passage `pids[i]` loses its
+        embeddings and receives the next `doclens[i]` columns of `codes` / `residuals` (compressed with the index's own
+        codec; layouts and checks as in `add_compressed`: numpy arrays, or CUDA tensors on this searcher's device).  `pids`
+        as `search` returns them, in any order, each at most once (twice: ArgumentError; outside the searcher's passages:
+        BoundsError).  A doclen of 0 empties a passage as `remove_passages` does; an empty passage may be filled again.
+        `num_docs` and every other pid are unchanged.  Returns how many named passages had or have embeddings.  Afterwards
+        every search answers as a Searcher made from the changed index would; filters made before stay valid.  If the call
+        raises, the searcher is unchanged.  `persist`: also rewrite the index directory the searcher was opened from
+        (storage.update_passages), after the device call has succeeded."""
+        if persist and self.index_path is None:
+            raise ColBERTError("persist=True needs a Searcher opened from an index_path")
+        p = np.ascontiguousarray(np.asarray(pids.cpu() if hasattr(pids, "data_ptr") else pids).reshape(-1), dtype=np.int64)
+        dl = np.ascontiguousarray(np.asarray(doclens.cpu() if hasattr(doclens, "data_ptr") else doclens).reshape(-1), dtype=np.int64)
+        if p.size != dl.size:
+            raise ColBERTError(f"one doclen per pid: {p.size} pids, {dl.size} doclens")
+        n = i64(0)
+        if hasattr(codes, "data_ptr"):
+            st = self._check_device_rows(codes, residuals)
+            check(lib().clb_searcher_update_device(self._h, i64(p.size), fptr(p), fptr(dl), i64(codes.numel()),
+                                                   C.c_void_p(codes.data_ptr()), C.c_void_p(residuals.data_ptr()),
+                                                   C.c_void_p(st), C.byref(n)))
+            if persist:
+                co, r = self._rows_to_host(codes, residuals)
+        else:
+            co, r = self._check_host_rows(codes, residuals)
+            check(lib().clb_searcher_update(self._h, i64(p.size), fptr(p), fptr(dl), i64(co.size), fptr(co), fptr(r),
+                                            C.byref(n)))
+        self.num_embeddings = int(lib().clb_searcher_num_embeddings(self._h))
+        if persist and n.value:
+            storage.update_passages(self.index_path, p - self.pid_offset, co, r, dl)
+        return int(n.value)
+
+    def update_embeddings(self, pids, embs, doclens, persist: bool = False) -> int:
+        """Compress passage embeddings with the index's own codec on the device, as `add_embeddings` does, and put them in
+        the place of the passages `pids` (update_compressed): `embs` numpy (dim, n) or a CUDA tensor (n, dim) float32."""
+        codes, res = self._compress(embs)
+        return self.update_compressed(pids, codes, res, doclens, persist=persist)
+
+    def update_passages(self, pids, texts, persist: bool = False) -> int:
+        """encode_passages (checkpoint.jl:159-189) with the attached encoder, then update_embeddings: texts[i] becomes the
+        content of passage pids[i]."""
+        if self.encoder is None:
+            raise ColBERTError("no encoder attached: pass encoder=... or use update_embeddings(pids, embs, doclens)")
+        embs, doclens = self.encoder.encode_passages(list(texts))
+        return self.update_embeddings(pids, embs, doclens, persist=persist)
+
     def _index_codec(self):
         """The index's own codec, resident (codec.Codec): built on first use from the centroids and bucket_cutoffs the
         index dict or directory carries -- the codec stays fixed over appends."""
@@ -218,9 +278,8 @@ class Searcher:
             self._codec = Codec(cent, cut, self.dim, self.nbits, device=self.device)
         return self._codec
 
-    def add_embeddings(self, embs, doclens, persist: bool = False) -> range:
-        """Compress passage embeddings with the index's own codec on the device (compress, residual.jl:586-604) and append
-        them: `embs` numpy (dim, n) or a CUDA tensor (n, dim) float32, `doclens` their passages' lengths.  -> the new pids."""
+    def _compress(self, embs):
+        """`embs` numpy (dim, n) or a CUDA tensor (n, dim) float32 -> (codes, residuals) on the device, by the index's codec"""
         import torch
         codec = self._index_codec()
         if hasattr(embs, "data_ptr"):
@@ -230,7 +289,12 @@ class Searcher:
             if e.ndim != 2 or e.shape[0] != self.dim:
                 raise ColBERTError(f"embs must be (dim={self.dim}, n)")
             x = torch.from_numpy(np.ascontiguousarray(e.T)).to(torch.device("cuda", self.device))
-        codes, res = codec.compress_device(x)
+        return codec.compress_device(x)
+
+    def add_embeddings(self, embs, doclens, persist: bool = False) -> range:
+        """Compress passage embeddings with the index's own codec on the device (compress, residual.jl:586-604) and append
+        them: `embs` numpy (dim, n) or a CUDA tensor (n, dim) float32, `doclens` their passages' lengths.  -> the new pids."""
+        codes, res = self._compress(embs)
         return self.add_compressed(codes, res, doclens, persist=persist)
 
     def add_passages(self, texts, persist: bool = False) -> range:

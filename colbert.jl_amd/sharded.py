@@ -21,7 +21,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import BoundsError, ColBERTError, check, colmajor, fptr, i64, lib
+from ._lib import ArgumentError, BoundsError, ColBERTError, check, colmajor, fptr, i64, lib
 from .searcher import PassageFilter, _scope_code
 
 _PROTOCOLS = ("auto", "two_phase", "single")
@@ -57,6 +57,14 @@ def route_pids(pids, bounds):
     p = check_group_pids(pids, bounds)
     shard = np.searchsorted(bounds, p, side="left") - 1          # bounds[i] < p <= bounds[i + 1]
     return [p[shard == i] for i in range(len(bounds) - 1)]
+
+
+def route_positions(pids, bounds):
+    """Global pids -> one array per shard: the POSITIONS in the list of that shard's pids, ascending (what route_pids selects,
+    for a caller that routes other per-pid data with them)."""
+    p = check_group_pids(pids, bounds)
+    shard = np.searchsorted(bounds, p, side="left") - 1
+    return [np.nonzero(shard == i)[0] for i in range(len(bounds) - 1)]
 
 
 def slice_mask(mask, bounds):
@@ -380,3 +388,68 @@ class ShardedSearcher:
         if self.group is not None:
             n = int(self._gather(np.array([[n]], dtype=np.int64)).sum())
         return n
+
+    # -- update: every passage stays on the shard that owns its pid --------------------------------------------
+    def _update(self, pids, doclens, call) -> int:
+        """Route an update by pid range: call(shard, its pids, the positions of those pids in the caller's list) on every
+        local shard that owns one; a pid outside the group raises BoundsError before any shard is touched.  -> the changed
+        count over the whole group.  The group's bound constants are shared again, as after an append."""
+        p = check_group_pids(pids, self._bounds)
+        if p.size != np.asarray(doclens).size:
+            raise ColBERTError(f"one doclen per pid: {p.size} pids, {np.asarray(doclens).size} doclens")
+        if np.unique(p).size != p.size:             # a shard would refuse it, after the shards before it had changed
+            raise ArgumentError("a pid is named twice: an update takes one new content per passage")
+        where = route_positions(p, self._bounds)
+        n = 0
+        for j, s in enumerate(self.shards):
+            at = where[self._first + j]
+            if at.size:
+                n += call(s, p[at], at)
+        if self.group is not None:
+            n = int(self._gather(np.array([[n]], dtype=np.int64)).sum())
+        self._share_bounds()
+        return n
+
+    def update_compressed(self, pids, codes, residuals, doclens) -> int:
+        """`Searcher.update_compressed` with GLOBAL pids: every passage and its rows go to the shard that owns the pid (numpy
+        arrays, layouts as there).  Pids are stable, no passage changes its shard, and ShardedFilters made before stay valid.
+        Returns the number of named passages that had or have embeddings, over the whole group."""
+        dl = np.ascontiguousarray(np.asarray(doclens).reshape(-1), dtype=np.int64)
+        co = np.ascontiguousarray(codes, dtype=np.uint32)
+        r = colmajor(residuals, np.uint8)
+        if co.ndim != 1 or r.ndim != 2 or r.shape[1] != co.size:
+            raise ColBERTError("residuals must be (dim/8*nbits, n_emb)")
+        if dl.size and (dl.min() < 0 or int(dl.sum()) != co.size):
+            raise ColBERTError(f"doclens must be non-negative and sum to the {co.size} embeddings")
+        off = np.concatenate([[0], np.cumsum(dl)])
+
+        def call(s, p, at):
+            cols = np.concatenate([np.arange(off[i], off[i + 1]) for i in at]) if at.size else np.zeros(0, np.int64)
+            return s.update_compressed(p, co[cols], np.asfortranarray(r[:, cols]), dl[at])
+        return self._update(pids, dl, call)
+
+    def update_embeddings(self, pids, embs, doclens) -> int:
+        """`Searcher.update_embeddings` with GLOBAL pids: `embs` numpy (dim, n), compressed on the owning shard with the
+        index's own codec."""
+        dl = np.ascontiguousarray(np.asarray(doclens).reshape(-1), dtype=np.int64)
+        e = colmajor(embs, np.float32)
+        if e.ndim != 2 or e.shape[0] != self.dim or (dl.size and dl.min() < 0) or int(dl.sum()) != e.shape[1]:
+            raise ColBERTError(f"embs must be (dim={self.dim}, sum(doclens))")
+        off = np.concatenate([[0], np.cumsum(dl)])
+
+        def call(s, p, at):
+            cols = np.concatenate([np.arange(off[i], off[i + 1]) for i in at]) if at.size else np.zeros(0, np.int64)
+            return s.update_embeddings(p, np.asfortranarray(e[:, cols]), dl[at])
+        return self._update(pids, dl, call)
+
+    def update_passages(self, pids, texts) -> int:
+        """encode_passages with the attached encoder on the owning shard's process, then update_embeddings: texts[i] becomes
+        the content of passage pids[i]."""
+        if self.encoder is None:
+            raise ColBERTError("no encoder attached: pass encoder=... or use update_embeddings(pids, embs, doclens)")
+        texts = list(texts)
+
+        def call(s, p, at):
+            embs, doclens = self.encoder.encode_passages([texts[i] for i in at])
+            return s.update_embeddings(p, embs, doclens)
+        return self._update(pids, np.zeros(len(texts), np.int64), call)

@@ -134,6 +134,28 @@ def _finish_journal(index_path: str) -> None:
     os.remove(journal)
 
 
+def _clear_staged(index_path: str) -> None:
+    """Delete the staged files an interruption before the journal left behind: no journal names them, nothing reads them."""
+    for f in os.listdir(index_path):
+        if f.endswith(_TMP) or f.endswith(_TMP + EXT):
+            os.remove(os.path.join(index_path, f))
+
+
+class _Staged:
+    """Files written under temporary names, and the renames a journal will make of them."""
+
+    def __init__(self, index_path: str):
+        self.index_path, self.renames = index_path, []
+
+    def arrays(self, name, a):
+        _save(os.path.join(self.index_path, name + _TMP), a)
+        self.renames.append((name + _TMP + EXT, name + EXT))
+
+    def json_file(self, name, obj):
+        save_json(self.index_path, name + _TMP, obj)
+        self.renames.append((name + _TMP, name))
+
+
 def remove_passages(index_path: str, pids) -> int:
     """Make a removal (Searcher.remove_passages) part of the index directory; `pids` are the directory's own, 1-based, in
     any order, duplicates allowed.  The passages stay in the numbering with doclen 0: the chunks that lose embeddings get
@@ -147,9 +169,7 @@ def remove_passages(index_path: str, pids) -> int:
     journal left behind are deleted on entry (nothing reads them).
     -> the number of passages that lost embeddings."""
     _finish_journal(index_path)
-    for f in os.listdir(index_path):        # no journal names them: leftovers of a removal that never got that far
-        if f.endswith(_TMP) or f.endswith(_TMP + EXT):
-            os.remove(os.path.join(index_path, f))
+    _clear_staged(index_path)
     plan = load_json(index_path, "plan.json")
     n_chunks = int(plan["num_chunks"])
     chunk = lambda i, kind: os.path.join(index_path, f"doclens.{i}" if kind == "doclens" else f"{i}.{kind}")
@@ -169,15 +189,8 @@ def remove_passages(index_path: str, pids) -> int:
     all_codes = np.concatenate(codes)
     new_ivf, new_lens = remove_from_ivf(*_read_ivf(index_path, all_codes), keep)
 
-    renames = []
-
-    def arrays(name, a):            # under the temporary name; the journal will rename it
-        _save(os.path.join(index_path, name + _TMP), a)
-        renames.append((name + _TMP + EXT, name + EXT))
-
-    def json_file(name, obj):
-        save_json(index_path, name + _TMP, obj)
-        renames.append((name + _TMP, name))
+    staged = _Staged(index_path)
+    arrays, json_file = staged.arrays, staged.json_file
 
     p0 = e0 = 0                     # passages / OLD embeddings in front of the chunk
     offsets, moved = [], False      # new 1-based embedding offset of every chunk; moved: a chunk before this one shrank
@@ -208,9 +221,106 @@ def remove_passages(index_path: str, pids) -> int:
     if "embeddings_offsets" in plan:
         plan["embeddings_offsets"] = offsets
     json_file("plan.json", plan)
-    _write_journal(index_path, renames)
+    _write_journal(index_path, staged.renames)
     _finish_journal(index_path)
     return int(gone.sum())
+
+
+def update_passages(index_path: str, pids, codes, residuals, doclens) -> int:
+    """Make an update (Searcher.update_compressed) part of the index directory: passage `pids[i]` (the directory's own,
+    1-based, any order, each at most once) gets the next `doclens[i]` columns of `codes` / `residuals` in the place of its old
+    ones.  No passage moves to another chunk: the chunks that hold a changed passage get new `.codes`, `.residuals`,
+    `doclens.i` and metadata `num_embeddings`, every chunk behind the first whose size changed its new `embedding_offset`,
+    and ivf, ivf_lengths and plan.json (`num_embeddings`, `embeddings_offsets`) follow.  ivf is `_build_ivf`
+    (collection_indexer.jl:349-353) of the changed codes: a stable sort on the host, the cost of a rewrite of the directory
+    being the files'.  The protocol is remove_passages': temporary names, one journal, the renames; before the journal the
+    directory reads as the old index, after it every reader finishes the renames and reads the new one.
+    -> the number of named passages whose old or new length is not zero."""
+    _finish_journal(index_path)
+    _clear_staged(index_path)
+    plan = load_json(index_path, "plan.json")
+    n_chunks = int(plan["num_chunks"])
+    chunk = lambda i, kind: os.path.join(index_path, f"doclens.{i}" if kind == "doclens" else f"{i}.{kind}")
+    old_lens = [np.asarray(_load(chunk(i, "doclens")), dtype=np.int64) for i in range(1, n_chunks + 1)]
+    old_codes = [_load(chunk(i, "codes")) for i in range(1, n_chunks + 1)]
+    n_docs = sum(d.size for d in old_lens)
+    pids = np.asarray(pids, dtype=np.int64).reshape(-1)
+    codes = np.asarray(codes, dtype=np.uint32); doclens = np.asarray(doclens, dtype=np.int64).reshape(-1)
+    residuals = np.asfortranarray(residuals, dtype=np.uint8)
+    if pids.size != doclens.size or (doclens < 0).any():
+        raise ValueError("one non-negative doclen per pid")
+    if int(doclens.sum()) != codes.size or residuals.shape[1] != codes.size:
+        raise ValueError("sum(doclens), length(codes) and the residual columns must agree")
+    if pids.size and (pids.min() < 1 or pids.max() > n_docs):
+        raise IndexError(f"pid outside 1..{n_docs}")
+    if np.unique(pids).size != pids.size:
+        raise ValueError("a pid is named twice: an update takes one new content per passage")
+    K = int(_load(os.path.join(index_path, "ivf_lengths")).size)
+    if codes.size and (codes.min() < 1 or codes.max() > K):
+        raise ValueError("codes outside 1..num_partitions")
+    all_lens = np.concatenate(old_lens) if old_lens else np.zeros(0, np.int64)
+    n_changed = int(np.count_nonzero((all_lens[pids - 1] > 0) | (doclens > 0)))
+    if n_changed == 0:
+        return 0
+    new_off = np.concatenate([[0], np.cumsum(doclens)])          # passage pids[i] among the new columns
+    slot = np.full(n_docs, -1, dtype=np.int64)
+    slot[pids - 1] = np.arange(pids.size)
+
+    staged = _Staged(index_path)
+    p0 = n_emb = 0                  # passages / NEW embeddings in front of the chunk
+    offsets, moved = [], False      # new 1-based embedding offset of every chunk; moved: a chunk before this one changed size
+    all_codes = []
+    for i in range(1, n_chunks + 1):
+        dl, co = old_lens[i - 1], old_codes[i - 1]
+        sl = slot[p0:p0 + dl.size]
+        named = np.nonzero(sl >= 0)[0]
+        named = named[(dl[named] > 0) | (doclens[sl[named]] > 0)]
+        meta = load_json(index_path, f"{i}.metadata.json")
+        offsets.append(n_emb + 1)
+        changed = False
+        if moved and "embedding_offset" in meta:
+            meta["embedding_offset"] = n_emb + 1
+            changed = True
+        if named.size:
+            # the chunk's columns, passage by passage: a kept passage's old ones, a named passage's new ones (col < 0: -1 - column)
+            off = np.concatenate([[0], np.cumsum(dl)])
+            new_dl = dl.copy()
+            new_dl[named] = doclens[sl[named]]
+            start = off[:-1].copy()
+            start[named] = -1 - new_off[sl[named]]
+            rank = np.arange(int(new_dl.sum())) - np.repeat(np.concatenate([[0], np.cumsum(new_dl)])[:-1], new_dl)
+            first = np.repeat(start, new_dl)
+            from_new = first < 0
+            col = np.where(from_new, -1 - first, first) + rank
+            res_old = _load(chunk(i, "residuals"))
+            new_co = np.empty(col.size, dtype=np.uint32)
+            new_co[from_new] = codes[col[from_new]]
+            new_co[~from_new] = co[col[~from_new]]
+            new_res = np.empty((residuals.shape[0], col.size), dtype=np.uint8, order="F")
+            new_res[:, from_new] = residuals[:, col[from_new]]
+            new_res[:, ~from_new] = res_old[:, col[~from_new]]
+            staged.arrays(f"{i}.codes", new_co)
+            staged.arrays(f"{i}.residuals", new_res)
+            staged.arrays(f"doclens.{i}", new_dl.astype(np.int64))
+            meta["num_embeddings"] = int(new_co.size)
+            changed = True
+            moved = moved or new_co.size != co.size
+            co = new_co
+        if changed:
+            staged.json_file(f"{i}.metadata.json", meta)
+        all_codes.append(co)
+        n_emb += int(co.size)
+        p0 += dl.size
+    all_codes = np.concatenate(all_codes)
+    staged.arrays("ivf", np.argsort(all_codes, kind="stable").astype(np.int64) + 1)
+    staged.arrays("ivf_lengths", np.bincount(all_codes.astype(np.int64) - 1, minlength=K).astype(np.int64))
+    plan["num_embeddings"] = n_emb
+    if "embeddings_offsets" in plan:
+        plan["embeddings_offsets"] = offsets
+    staged.json_file("plan.json", plan)
+    _write_journal(index_path, staged.renames)
+    _finish_journal(index_path)
+    return n_changed
 
 
 def append_chunk(index_path: str, codes, residuals, doclens) -> None:

@@ -14,8 +14,8 @@
  * retains a host pointer.  All device memory belongs to the library (handles are opaque).
  * Threading: every call is synchronous (results are in the output buffers on return) except the
  * *_device entry points, which enqueue on the given HIP stream.  One handle, one thread at a time.
- * clb_searcher_append / clb_searcher_append_device / clb_searcher_remove replace the handle's device arrays: they wait for the
- * whole device on entry and before the swap, and the caller must have no search of that handle in flight on another thread.
+ * clb_searcher_append / clb_searcher_append_device / clb_searcher_remove / clb_searcher_update / clb_searcher_update_device
+ * replace the handle's device arrays: they wait for the whole device on entry and before the swap, and the caller must have no search of that handle in flight on another thread.
  * Errors: every function returns 0 or a CLB_E* code; codes 1..4 map 1:1 onto the Julia exception the
  * reference throws in the same situation.  clb_last_error() returns a message for the calling thread.
  * There is NO CPU fallback: without a GPU every compute entry point fails with CLB_EHIP.
@@ -122,7 +122,39 @@ int clb_searcher_append_device(clb_searcher* s, int64_t n_new, const int64_t* do
  * clb_search_shard_phase1 is dropped, and a HIP graph captured over this handle must be captured again (compare
  * clb_searcher_generation).  A clb_filter made before the removal STAYS valid: n_docs, and so its bitmap, did not change. */
 int clb_searcher_remove(clb_searcher* s, const int64_t* pids, int64_t n, int64_t* n_removed);
-/* Number of appends and removals that changed the handle (0 after create), its passages and its embeddings.  These return
+/* Replace the content of passages of the resident index in place, keeping their pids (no counterpart in the reference, nor in
+ * upstream ColBERT's IndexUpdater, which has remove and add only).  pids are as search returns them (1-based with pid_offset
+ * added), n entries in any order, each pid at most once.  Passage pids[i] loses all its rows and receives doclens[i] new ones:
+ * the columns sum(doclens[:i]) .. sum(doclens[:i+1]) - 1 of codes (UInt32[n_new_emb], 1-based) / residuals ((dim/8*nbits,
+ * n_new_emb)), in append's layouts -- what compress() with the index's own centroids and cutoffs gives.  doclens[i] == 0
+ * empties the passage exactly as clb_searcher_remove does; a passage that is empty now (doclen 0 at create, or removed
+ * earlier) may be named and is filled again.  n_docs, pid_offset and every other passage's pid are unchanged.  *n_changed
+ * (may be null) receives the number of named passages whose old or new length is not zero.
+ * Afterwards every entry point behaves bit for bit as on a handle made by clb_searcher_create from the index with those
+ * passages' columns replaced, their doclens set, and ivf = stable sortperm(codes) (_build_ivf, collection_indexer.jl:349-353):
+ * a passage is wholly kept or wholly replaced, so a centroid's list is the merge by passage of its kept entries and the new
+ * entries with that code.  On a handle created with lists in an order of the caller's own (not ascending embedding ids) the
+ * new entries go behind the kept ones of their list; results do not depend on the order inside a list.  Bound constants, the
+ * gather form, the mode and the other settings follow append's and remove's rules.
+ * n = 0, or *n_changed = 0, is CLB_OK, changes nothing and does not bump the generation.
+ * Failure leaves the handle unchanged and searchable; all of these are decided before the changed index is allocated:
+ * CLB_EARGUMENT a null handle, a null array with a non-zero count, n < 0, a negative doclen, or a pid named twice (two
+ * contents for one passage: the message names the pid); CLB_EBOUNDS a pid outside pid_offset+1 .. pid_offset+n_docs;
+ * CLB_EDIMENSION sum(doclens) != n_new_emb; CLB_EDOMAIN a code outside 1..K (checked on the device); CLB_EUNSUPPORTED the new
+ * totals exceed create's limits; CLB_ENOMEM.
+ * Memory, threading and invalidation are append's and remove's: the changed arrays are built beside the old ones (the call
+ * transiently holds the old plus the new index, two words of scan scratch per old embedding and the staged new rows with
+ * their sort scratch); the call waits for the whole device on entry and again before the swap; all four workspace slots are
+ * sized again by the next search, a pending clb_search_shard_phase1 is dropped, and a HIP graph captured over this handle must
+ * be captured again (compare clb_searcher_generation).  A clb_filter made before the update STAYS valid: n_docs did not
+ * change. */
+int clb_searcher_update(clb_searcher* s, int64_t n, const int64_t* pids, const int64_t* doclens, int64_t n_new_emb,
+                        const uint32_t* codes, const uint8_t* residuals, int64_t* n_changed);
+/* The same with d_codes / d_residuals on the searcher's device (neither is written); pids and doclens on the host.
+ * hip_stream as in clb_searcher_append_device. */
+int clb_searcher_update_device(clb_searcher* s, int64_t n, const int64_t* pids, const int64_t* doclens, int64_t n_new_emb,
+                               const uint32_t* d_codes, const uint8_t* d_residuals, void* hip_stream, int64_t* n_changed);
+/* Number of appends, removals and updates that changed the handle (0 after create), its passages and its embeddings.  These return
  * counts, not CLB_* codes: a null handle gives -CLB_EARGUMENT (and the message in clb_last_error). */
 int64_t clb_searcher_generation(const clb_searcher* s);
 int64_t clb_searcher_num_docs(const clb_searcher* s);

@@ -18,7 +18,7 @@ using Logging
 using Random
 using Unicode
 
-export ColBERTConfig, Indexer, index, Searcher, search, PassageFilter, add_compressed!, remove_passages!
+export ColBERTConfig, Indexer, index, Searcher, search, PassageFilter, add_compressed!, remove_passages!, update_passages!
 
 include("config.jl")
 include("capi.jl")

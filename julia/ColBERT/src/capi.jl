@@ -48,7 +48,17 @@ function _searcher_remove(h::Ptr{Cvoid}, pids::Vector{Int})
     end
     Int(n[])
 end
-"appends and removals that changed the handle (0 after create) / its passages / its embeddings"
+"replace the content of passages in place, keeping their pids (clb_searcher_update): passage pids[i] receives the next doclens[i] columns of codes / residuals -> how many named passages had or have embeddings; the handle is unchanged when this throws"
+function _searcher_update(h::Ptr{Cvoid}, pids::Vector{Int}, doclens::Vector{Int}, codes::Vector{UInt32}, residuals::Matrix{UInt8})
+    n = Ref{Int64}(0)
+    GC.@preserve pids doclens codes residuals begin
+        _check(ccall((:clb_searcher_update, libcolbert), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{UInt32}, Ptr{UInt8}, Ref{Int64}),
+            h, length(pids), pids, doclens, length(codes), codes, residuals, n))
+    end
+    Int(n[])
+end
+"appends, removals and updates that changed the handle (0 after create) / its passages / its embeddings"
 _searcher_generation(h::Ptr{Cvoid}) = Int(ccall((:clb_searcher_generation, libcolbert), Int64, (Ptr{Cvoid},), h))
 _searcher_num_docs(h::Ptr{Cvoid}) = Int(ccall((:clb_searcher_num_docs, libcolbert), Int64, (Ptr{Cvoid},), h))
 _searcher_num_embeddings(h::Ptr{Cvoid}) = Int(ccall((:clb_searcher_num_embeddings, libcolbert), Int64, (Ptr{Cvoid},), h))

@@ -62,7 +62,24 @@ made before the call stays valid.  On an exception the searcher is unchanged.  N
 ColBERT: IndexUpdater.remove).
 """
 remove_passages!(searcher::Searcher, pids::Vector{Int}) = _searcher_remove(searcher.handle, pids)
-"number of `add_compressed!` / `remove_passages!` calls that changed the searcher"
+"""
+    update_passages!(searcher, pids, codes, residuals, doclens) -> Int
+
+Replace the content of passages in place: passage `pids[i]` loses its embeddings and receives the next `doclens[i]` columns of
+`codes` / `residuals` (compressed with the index's own codec, as for `add_compressed!`).  Pids are stable -- no other passage
+moves, `num_documents` does not change -- a doclen of 0 empties a passage as `remove_passages!` does, and an empty passage
+may be filled again.  Each pid may be named once (twice is an ArgumentError).  Returns how many named passages had or have
+embeddings.  Afterwards `search` answers as a `Searcher` opened on the changed index would; a `PassageFilter` made before the
+call stays valid.  On an exception the searcher is unchanged.  No counterpart in the reference or in upstream ColBERT.
+"""
+function update_passages!(searcher::Searcher, pids::Vector{Int}, codes::Vector{UInt32}, residuals::Matrix{UInt8}, doclens::Vector{Int})
+    size(residuals, 2) == length(codes) ||
+        throw(DimensionMismatch("residuals must have one column per code ($(length(codes))), got $(size(residuals, 2))"))
+    length(pids) == length(doclens) ||
+        throw(DimensionMismatch("one doclen per pid: $(length(pids)) pids, $(length(doclens)) doclens"))
+    _searcher_update(searcher.handle, pids, doclens, codes, residuals)
+end
+"number of `add_compressed!` / `remove_passages!` / `update_passages!` calls that changed the searcher"
 generation(searcher::Searcher) = _searcher_generation(searcher.handle)
 num_embeddings(searcher::Searcher) = _searcher_num_embeddings(searcher.handle)
 
