@@ -94,6 +94,19 @@ def lib() -> C.CDLL:
         l.clb_comm_unique_id_bytes.restype = C.c_int64
         l.clb_kmeans_shard_block_bytes.restype = C.c_int64
         l.clb_filter_count.restype = C.c_int64
+        l.clb_grouping_count.restype = C.c_int64
+        l.clb_grouping_count.argtypes = [C.c_void_p]
+        l.clb_grouping_create.restype = C.c_int
+        l.clb_grouping_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+        l.clb_grouping_destroy.argtypes = [C.c_void_p]
+        l.clb_search_batch_grouped.restype = C.c_int
+        l.clb_search_batch_grouped.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                               C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
+        l.clb_search_batch_grouped_device_slot.restype = C.c_int
+        l.clb_search_batch_grouped_device_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                                           C.c_int64, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p]
         l.clb_searcher_generation.restype = C.c_int64
         l.clb_searcher_num_docs.restype = C.c_int64
         l.clb_searcher_num_embeddings.restype = C.c_int64

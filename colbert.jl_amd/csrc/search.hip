@@ -11,6 +11,7 @@
 #include "append_kernels.hpp"
 #include "approx_kernels.hpp"
 #include "generic_kernels.hpp"
+#include "group_kernels.hpp"
 #include "remove_kernels.hpp"
 #include "search_kernels.hpp"
 #include "sort.hpp"
@@ -71,6 +72,15 @@ struct clb_filter {
     DevBuf bits;                // u32 [ceil(n_docs / 32)]
 };
 
+// A resident passage grouping (include/colbert_hip.h): the dense 0-based group index of every local passage, non-decreasing
+// in pid.  Like a clb_filter it owns its words and remembers its searcher by serial number only.
+struct clb_grouping {
+    uint64_t owner = 0;         // clb_searcher::serial of the searcher it was made for
+    int device = 0;
+    int64_t n_docs = 0, count = 0;
+    DevBuf gid;                 // u32 [n_docs]
+};
+
 // Per-batch workspace (everything a batch of queries needs besides the resident index).
 struct Workspace {
     int64_t Bcap = 0, Tcap = 0, npcap = 0, kcap = 0;
@@ -87,6 +97,11 @@ struct Workspace {
              size_t filt_now = 0; } pending;      // filt_now: Batch::filt_now of phase 1 -- phase 2 selects over the same candidates
     DevBuf Qdev, cells, cells_q, partial, sel, bitmap, blocksum, ncand, cand, cand_hdr, scores, list, nlist, thresh,
         outp, outs, flags, stats, redo, rowmask, eps_pair, tokmax, tau_glob, wsel, bounds, tscale, rangep, cells8;
+    // grouped search (group_kernels.hpp), sized once a call has passed a grouping: the best slot of every group among all
+    // candidates (grp_list / grp_n: grp_n is the query's group count) and among the re-scored passages of the two-pass mode
+    // (grp_list2 / grp_n2), and the threshold at the k-th best group
+    bool grouped = false;
+    DevBuf grp_list, grp_n, grp_list2, grp_n2, grp_tau;
     DevBuf g_cells, g_keys, g_keys2, g_vals, g_vals2, g_scratch, g_sort_tmp;   // general-shape path (generic_kernels.hpp)
 };
 
@@ -152,6 +167,7 @@ struct Batch {
     const clb_filter* const* filt = nullptr;
     int filt_all = 0;
     size_t filt_now = 0;
+    const clb_grouping* grp = nullptr;      // grouped search: one grouping for the whole batch (checked by check_grouping)
     bool stats_keep = false;    // the 2nd, 3rd ... sub-batch of one call: the work counters accumulate over the call
     int phase = 0, n_shards = 0;    // two-phase sharded search (run_search)
     float* d_local_top = nullptr; const float* d_all_top = nullptr;
@@ -225,9 +241,11 @@ int next_pow2(int x) {
 
 // filt_count: the largest filter population of a CLB_FILTER_ALL call (0 otherwise) -- such a query's candidates are its
 // filter's passages, however few the IVF lists would give
-int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_t nprobe, int64_t k, size_t filt_count) {
+int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_t nprobe, int64_t k, size_t filt_count,
+                           bool grouped) {
     const int64_t t_tuned = T <= 128 ? T : 0;       // queries of up to 128 tokens take the tuned (or batched general) kernels
-    if (B <= w.Bcap && T <= w.Tcap && t_tuned <= w.Ttuned && nprobe <= w.npcap && k <= w.kcap && filt_count <= w.filt_cap)
+    if (B <= w.Bcap && T <= w.Tcap && t_tuned <= w.Ttuned && nprobe <= w.npcap && k <= w.kcap && filt_count <= w.filt_cap &&
+        (!grouped || w.grouped))
         return CLB_OK;
     CLB_HIP(hipDeviceSynchronize());       // buffers may be in use on any of the caller's streams
     B = std::max(B, w.Bcap); T = std::max(T, w.Tcap);
@@ -291,14 +309,25 @@ int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, 
         CLB_TRY(w.eps_pair.ensure(sizeof(float) * B));
         CLB_TRY(w.tokmax.ensure(sizeof(uint16_t) * 32 * B * w.cand_cap));
     }
+    if (grouped || w.grouped) {     // a slot that has served a grouped call keeps these in step with its other buffers
+        CLB_TRY(w.grp_list.ensure(sizeof(int) * B * w.cand_cap));
+        CLB_TRY(w.grp_n.ensure(sizeof(int) * B));
+        CLB_TRY(w.grp_tau.ensure(sizeof(float) * B));
+        if (s->approx_ok) {
+            CLB_TRY(w.grp_list2.ensure(sizeof(int) * B * w.cand_cap));
+            CLB_TRY(w.grp_n2.ensure(sizeof(int) * B));
+        }
+        w.grouped = true;
+    }
     w.Bcap = B; w.Tcap = T; w.Ttuned = Ttuned; w.npcap = nprobe; w.kcap = k;
     w.filt_cap = std::max(w.filt_cap, filt_count);
     CLB_HIP(hipStreamSynchronize(s->stream));
     return CLB_OK;
 }
 
-int ensure_workspace(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_t nprobe, int64_t k, size_t filt_count = 0) {
-    const int rc = ensure_workspace_sized(s, w, B, T, nprobe, k, filt_count);
+int ensure_workspace(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_t nprobe, int64_t k, size_t filt_count = 0,
+                     bool grouped = false) {
+    const int rc = ensure_workspace_sized(s, w, B, T, nprobe, k, filt_count, grouped);
     if (rc) {
         w.Bcap = 0;       // some buffers may have grown and others not: the next call sizes all of them again
         // a candidate set the size of a filter that does not fit is this call's own request, not a fault of the device
@@ -551,6 +580,9 @@ int select_by_sort(clb_searcher* s, Workspace& w, hipStream_t st, const float* c
     return CLB_OK;
 }
 
+// the count a search reports as n_cand: the query's candidates, or with a grouping the groups among them
+inline const int* reported_count(const Workspace& w, const Batch& q) { return q.grp ? w.grp_n.as<int>() : w.ncand.as<int>(); }
+
 // top-k of ONE query by a full stable sort (k above the single-work-group sort of topk_kernel).  The count stays on the
 // device: the sort runs over the slot's candidate capacity with the positions past the count keyed to the end, the
 // emit kernel writes the short-result flag and the candidate count; rocPRIM's temporary storage lives in the workspace
@@ -569,10 +601,20 @@ int topk_by_sort(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, 
     CLB_TRY(sort_keys_u64(w.g_keys.as<uint64_t>(), w.g_keys2.as<uint64_t>(), (size_t)cap, st, &w.g_sort_tmp));
     hipLaunchKernelGGL(generic_topk_emit_kernel, dim3((std::max(k, 1) + 255) / 256), dim3(256), 0, st,
                        w.g_keys2.as<unsigned long long>(), sc, w.cand.as<uint32_t>() + (size_t)b * w.cand_cap, lst, n_ptr,
-                       w.ncand.as<int>() + b, k, s->pid_offset, q.d_out_pids + (size_t)b * k, q.d_out_scores + (size_t)b * k,
+                       reported_count(w, q) + b, k, s->pid_offset, q.d_out_pids + (size_t)b * k, q.d_out_scores + (size_t)b * k,
                        w.flags.as<int>() + b, q.d_n_cand ? q.d_n_cand + b : nullptr);
     CLB_HIP(hipGetLastError());
     return CLB_OK;
+}
+
+// S7g-a for queries b0 .. b0 + n - 1 (group_collapse_kernel): the best slot of every group among the listed slots (list /
+// nlist, [B][cand_cap] / [B]) or, with list == nullptr, among all candidates, to out_list / out_n of the same layout
+void launch_collapse(Workspace& w, hipStream_t st, const Batch& q, int b0, int n, const int* list, const int* nlist,
+                     int* out_list, int* out_n) {
+    hipLaunchKernelGGL(group_collapse_kernel, dim3(n), dim3(1024), 0, st, w.scores.as<float>() + (size_t)b0 * w.cand_cap,
+                       w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap, w.ncand.as<int>() + b0,
+                       list ? list + (size_t)b0 * w.cand_cap : nullptr, list ? nlist + b0 : nullptr, q.grp->gid.as<uint32_t>(),
+                       w.cand_cap, out_list + (size_t)b0 * w.cand_cap, out_n + b0);
 }
 
 // S7 for queries b0 .. b0 + n - 1: the single-work-group select + sort of topk_kernel, one work-group per query, or for
@@ -588,11 +630,19 @@ int launch_topk(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, i
     allow_large_topk_lds();
     hipLaunchKernelGGL(topk_kernel, dim3(n), dim3(1024), sizeof(unsigned long long) * kpow2, st,
                        w.scores.as<float>() + (size_t)b0 * w.cand_cap, w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap,
-                       w.ncand.as<int>() + b0, list ? list + (size_t)b0 * w.cand_cap : nullptr, list ? nlist + b0 : nullptr, q.k, kpow2,
+                       reported_count(w, q) + b0, list ? list + (size_t)b0 * w.cand_cap : nullptr, list ? nlist + b0 : nullptr, q.k, kpow2,
                        w.cand_cap, s->pid_offset, q.d_out_pids + (size_t)b0 * q.k, q.d_out_scores + (size_t)b0 * q.k,
                        w.flags.as<int>() + b0, q.d_n_cand ? q.d_n_cand + b0 : nullptr, ranked);
     CLB_HIP(hipGetLastError());
     return CLB_OK;
+}
+
+// S7 of the general-shape path for queries b0 .. b0 + n - 1, the exact scores of all their candidates in place -- with a
+// grouping: one collapse, then the top-k forms rank its list
+int topk_of(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int n) {
+    if (!q.grp) return launch_topk(s, w, st, q, b0, n, nullptr, nullptr, 0);
+    launch_collapse(w, st, q, b0, n, nullptr, nullptr, w.grp_list.as<int>(), w.grp_n.as<int>());
+    return launch_topk(s, w, st, q, b0, n, w.grp_list.as<int>(), w.grp_n.as<int>(), 0);
 }
 
 // S1-S3 of query b of the sub-batch on the general-shape path: leaves cand / cand_hdr / ncand of slot b
@@ -639,7 +689,7 @@ int run_search_general(clb_searcher* s, Workspace& w, hipStream_t st, const Batc
                            s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(), w.cand_hdr.as<uint2>(), w.ncand.as<int>(), dQ,
                            (int)s->dim, s->nbits, T, w.cand_cap, w.scores.as<float>());
         CLB_HIP(hipGetLastError());
-        return launch_topk(s, w, st, q, 0, B, nullptr, nullptr, 0);
+        return topk_of(s, w, st, q, 0, B);
     }
     const int grid = 1024;
     const size_t max_len = (size_t)std::max<int64_t>(s->max_doclen, 1);
@@ -660,7 +710,7 @@ int run_search_general(clb_searcher* s, Workspace& w, hipStream_t st, const Batc
                                dQ + (size_t)b * T * s->dim, (int)s->dim, s->nbits, T, w.g_scratch.as<float>(), max_len,
                                w.scores.as<float>() + (size_t)b * w.cand_cap);
         CLB_HIP(hipGetLastError());
-        CLB_TRY(launch_topk(s, w, st, q, b, 1, nullptr, nullptr, 0));
+        CLB_TRY(topk_of(s, w, st, q, b, 1));
     }
     return CLB_OK;
 }
@@ -764,7 +814,15 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
             }
             {
                 Timed t(s, KID_SELECT, st);
-                CLB_TRY(launch_select(s, w, st, q, nullptr, /*coarse_tau=*/phase == 0));
+                if (q.grp) {
+                    // grouped: the cut is at the k-th best GROUP by approximate score -- the best
+                    // approximate score of every group, their k-th largest, and the unchanged selection at that tau
+                    launch_collapse(w, st, q, 0, B, nullptr, nullptr, w.grp_list.as<int>(), w.grp_n.as<int>());
+                    hipLaunchKernelGGL(group_tau_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(), w.grp_list.as<int>(),
+                                       w.grp_n.as<int>(), k, w.cand_cap, w.grp_tau.as<float>());
+                    CLB_TRY(launch_select(s, w, st, q, (const float*)w.grp_tau.as<float>()));
+                } else
+                    CLB_TRY(launch_select(s, w, st, q, nullptr, /*coarse_tau=*/phase == 0));
             }
         }
     }
@@ -808,19 +866,32 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
                 default: return fail(CLB_EUNSUPPORTED, "nbits=%d not supported by the HIP search path", s->nbits);
             }
     }
+    // what S7 ranks: the re-scored passages (two-pass mode) or all candidates -- with a grouping, the best of every group
+    // among them by exact score (two-pass mode: grp_n, the group count of ALL candidates, stays what the call reports)
+    const int* tlist = list;
+    const int* tnlist = nlist;
+    auto collapse_exact = [&]() {
+        if (!q.grp) return;
+        int* gl = list ? w.grp_list2.as<int>() : w.grp_list.as<int>();
+        int* gn = list ? w.grp_n2.as<int>() : w.grp_n.as<int>();
+        launch_collapse(w, st, q, 0, B, list, nlist, gl, gn);
+        tlist = gl; tnlist = gn;
+    };
     if (k <= kMaxTopK) {
         Timed t(s, KID_TOPK, st);
+        collapse_exact();
         // two-pass mode: the ~1.2 k listed passages of a query are ranked by kRankBlocks work-groups (no sorting network);
         // a query whose list is longer than kRankMax falls through to the one-work-group select + sort
-        const int ranked = list != nullptr;
+        const int ranked = tlist != nullptr;
         if (ranked)
             hipLaunchKernelGGL(topk_rank_kernel, dim3(kRankBlocks, B), dim3(1024), 0, st, w.scores.as<float>(),
-                               w.cand.as<uint32_t>(), w.ncand.as<int>(), list, nlist, k, w.cand_cap, s->pid_offset,
+                               w.cand.as<uint32_t>(), reported_count(w, q), tlist, tnlist, k, w.cand_cap, s->pid_offset,
                                q.d_out_pids, q.d_out_scores, w.flags.as<int>(), q.d_n_cand);
-        CLB_TRY(launch_topk(s, w, st, q, 0, B, list, nlist, ranked));
+        CLB_TRY(launch_topk(s, w, st, q, 0, B, tlist, tnlist, ranked));
     } else {      // k above the single-work-group sort: a full stable sort per query, untimed
         s->prof.chain = nullptr;
-        CLB_TRY(launch_topk(s, w, st, q, 0, B, list, nlist, 0));
+        collapse_exact();
+        CLB_TRY(launch_topk(s, w, st, q, 0, B, tlist, tnlist, 0));
     }
     if (s->prof.counters) {
         hipLaunchKernelGGL(batch_stats_kernel, dim3(32, B), dim3(256), 0, st, w.cand.as<uint32_t>(),
@@ -851,6 +922,15 @@ int check_filters(const clb_searcher* s, const clb_filter* const* filters, int64
     return CLB_OK;
 }
 
+// the grouping of a call (or nullptr): it must be this searcher's, made for the passages it holds now
+int check_grouping(const clb_searcher* s, const clb_grouping* g) {
+    if (!g) return CLB_OK;
+    if (g->owner != s->serial) return fail(CLB_EARGUMENT, "the grouping was made for another searcher");
+    if (g->n_docs != s->n_docs)     // its table has the old length
+        return fail(CLB_EARGUMENT, "grouping made before an append; make another");
+    return CLB_OK;
+}
+
 // q's filter operands: queries b0 .. b0 + q.B - 1 of a call whose handle array is `filters` (checked by check_filters, which
 // gave filt_count)
 void set_batch_filters(Batch& q, const clb_filter* const* filters, int64_t b0, int scope, size_t filt_count) {
@@ -875,15 +955,18 @@ int slot_workspace(clb_searcher* s, int slot, Workspace** w) {
 // (The two-phase sharded calls keep the whole batch: phase 2 continues on the scratch of phase 1.)
 // run_one(b0, q): points q at the queries and outputs of the sub-batch that starts at query b0 and runs it.  q arrives with
 // the sub-batch's size, its slice of the handle array -- nullptr when none of its queries is filtered -- and stats_keep set
+// grp: the grouping of a grouped call (every sub-batch carries it) or nullptr
 template <class RunOne>
 int for_sub_batches(clb_searcher* s, Workspace& w, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                    const clb_filter* const* filters, int scope, RunOne run_one) {
+                    const clb_filter* const* filters, int scope, const clb_grouping* grp, RunOne run_one) {
     size_t filt_count = 0;
     CLB_TRY(check_filters(s, filters, B, scope, &filt_count));
+    CLB_TRY(check_grouping(s, grp));
     w.pending.valid = false;
     for (int64_t b0 = 0; b0 < B; b0 += kSubBatch) {
         Batch q = make_batch(nullptr, std::min<int64_t>(kSubBatch, B - b0), T, nprobe, k);
-        CLB_TRY(ensure_workspace(s, w, q.B, T, nprobe, k, filt_count));
+        CLB_TRY(ensure_workspace(s, w, q.B, T, nprobe, k, filt_count, grp != nullptr));
+        q.grp = grp;
         q.stats_keep = b0 > 0;
         set_batch_filters(q, filters, b0, scope, filt_count);
         CLB_TRY(run_one(b0, q));
@@ -1759,13 +1842,13 @@ int clb_search_batch_device(clb_searcher* s, const float* d_Q, int64_t T, int64_
 }
 
 static int search_batch_device_slot_impl(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                         int64_t k, const clb_filter* const* filters, int scope, int64_t* d_out_pids,
-                                         float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
+                                         int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grp,
+                                         int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     Workspace* w = nullptr;
     CLB_TRY(slot_workspace(s, slot, &w));
     hipStream_t st = (hipStream_t)hip_stream;   // NULL = the HIP null stream, as for any HIP API
-    return for_sub_batches(s, *w, T, B, nprobe, k, filters, scope, [&](int64_t b0, Batch& q) -> int {
+    return for_sub_batches(s, *w, T, B, nprobe, k, filters, scope, grp, [&](int64_t b0, Batch& q) -> int {
         q.dQ = d_Q + (size_t)b0 * T * s->dim;
         q.d_out_pids = d_out_pids + (size_t)b0 * k;
         q.d_out_scores = d_out_scores + (size_t)b0 * k;
@@ -1777,15 +1860,22 @@ static int search_batch_device_slot_impl(clb_searcher* s, int slot, const float*
 int clb_search_batch_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
                                  int64_t k, int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand,
                                  void* hip_stream) {
-    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, nullptr, CLB_FILTER_CANDIDATES, d_out_pids, d_out_scores,
-                                         d_n_cand, hip_stream);
+    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, nullptr, CLB_FILTER_CANDIDATES, nullptr, d_out_pids,
+                                         d_out_scores, d_n_cand, hip_stream);
 }
 
 int clb_search_batch_filtered_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
                                           int64_t k, const clb_filter* const* filters, int scope, int64_t* d_out_pids,
                                           float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
-    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, d_out_pids, d_out_scores, d_n_cand,
-                                         hip_stream);
+    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, nullptr, d_out_pids, d_out_scores,
+                                         d_n_cand, hip_stream);
+}
+
+int clb_search_batch_grouped_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
+                                         int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
+    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, grouping, d_out_pids, d_out_scores,
+                                         d_n_cand, hip_stream);
 }
 
 int clb_search_shard_phase1(clb_searcher* s, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
@@ -1862,8 +1952,8 @@ int clb_search_shard_phase2_slot(clb_searcher* s, int slot, const float* d_Q, in
 }
 
 static int search_batch_impl(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                             const clb_filter* const* filters, int scope, int pad_short, int64_t* out_pids, float* out_scores,
-                             int64_t* n_cand) {
+                             const clb_filter* const* filters, int scope, const clb_grouping* grp, int pad_short,
+                             int64_t* out_pids, float* out_scores, int64_t* n_cand) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     Workspace* wp = nullptr;
     CLB_TRY(slot_workspace(s, 0, &wp));
@@ -1871,7 +1961,7 @@ static int search_batch_impl(clb_searcher* s, const float* Q, int64_t T, int64_t
     hipStream_t st = s->stream;
     std::vector<int> nc((size_t)B), fl((size_t)B);
     // the queries go up into the slot's own buffer and the results come back from it, sub-batch by sub-batch
-    CLB_TRY(for_sub_batches(s, w, T, B, nprobe, k, filters, scope, [&](int64_t b0, Batch& q) -> int {
+    CLB_TRY(for_sub_batches(s, w, T, B, nprobe, k, filters, scope, grp, [&](int64_t b0, Batch& q) -> int {
         CLB_HIP(hipMemcpyAsync(w.Qdev.p, Q + (size_t)b0 * T * s->dim, sizeof(float) * q.B * T * s->dim, hipMemcpyHostToDevice, st));
         q.dQ = w.Qdev.as<float>();
         q.d_out_pids = w.outp.as<int64_t>();
@@ -1879,7 +1969,7 @@ static int search_batch_impl(clb_searcher* s, const float* Q, int64_t T, int64_t
         CLB_TRY(run_search(s, w, st, q));
         CLB_HIP(hipMemcpyAsync(out_pids + (size_t)b0 * k, w.outp.p, sizeof(int64_t) * q.B * k, hipMemcpyDeviceToHost, st));
         CLB_HIP(hipMemcpyAsync(out_scores + (size_t)b0 * k, w.outs.p, sizeof(float) * q.B * k, hipMemcpyDeviceToHost, st));
-        CLB_HIP(hipMemcpyAsync(nc.data() + b0, w.ncand.p, sizeof(int) * q.B, hipMemcpyDeviceToHost, st));
+        CLB_HIP(hipMemcpyAsync(nc.data() + b0, reported_count(w, q), sizeof(int) * q.B, hipMemcpyDeviceToHost, st));
         CLB_HIP(hipMemcpyAsync(fl.data() + b0, w.flags.p, sizeof(int) * q.B, hipMemcpyDeviceToHost, st));
         return CLB_OK;
     }));
@@ -1893,19 +1983,74 @@ static int search_batch_impl(clb_searcher* s, const float* Q, int64_t T, int64_t
     if (!pad_short)
         for (int64_t b = 0; b < B; ++b)
             if (fl[b])  // searching.jl:127 `pids[1:k]` on a shorter vector
-                return fail(CLB_EBOUNDS, "query %lld has %d candidate passages, fewer than k=%lld", (long long)b, nc[b], (long long)k);
+                return fail(CLB_EBOUNDS, "query %lld has %d candidate %s, fewer than k=%lld", (long long)b, nc[b],
+                            grp ? "groups" : "passages", (long long)k);
     return CLB_OK;
 }
 
 int clb_search_batch(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
                      int pad_short, int64_t* out_pids, float* out_scores, int64_t* n_cand) {
-    return search_batch_impl(s, Q, T, B, nprobe, k, nullptr, CLB_FILTER_CANDIDATES, pad_short, out_pids, out_scores, n_cand);
+    return search_batch_impl(s, Q, T, B, nprobe, k, nullptr, CLB_FILTER_CANDIDATES, nullptr, pad_short, out_pids, out_scores, n_cand);
 }
 
 int clb_search_batch_filtered(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
                               const clb_filter* const* filters, int scope, int64_t* out_pids, float* out_scores,
                               int64_t* n_cand) {
-    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, 1, out_pids, out_scores, n_cand);
+    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, nullptr, 1, out_pids, out_scores, n_cand);
+}
+
+int clb_search_batch_grouped(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                             const clb_filter* const* filters, int scope, const clb_grouping* grouping, int pad_short,
+                             int64_t* out_pids, float* out_scores, int64_t* n_cand) {
+    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, grouping, pad_short, out_pids, out_scores, n_cand);
+}
+
+// ---- clb_grouping -------------------------------------------------------------------------------------------------
+int clb_grouping_create(clb_searcher* s, const int64_t* group_ids, int64_t n, clb_grouping** out) {
+    if (out) *out = nullptr;
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    if (!out) return fail(CLB_EARGUMENT, "out is null");
+    if (n != s->n_docs)
+        return fail(CLB_EARGUMENT, "a grouping holds one group id per passage: n=%lld, the searcher has %lld passages", (long long)n,
+                    (long long)s->n_docs);
+    if (n > 0 && !group_ids) return fail(CLB_EARGUMENT, "group_ids is null");
+    // equal ids must be one contiguous pid range: checked on the host, before anything is allocated
+    for (int64_t i = 1; i < n; ++i)
+        if (group_ids[i] < group_ids[i - 1])
+            return fail(CLB_EARGUMENT, "group ids must be non-decreasing in pid: they decrease at passage %lld (%lld after %lld)",
+                        (long long)(s->pid_offset + i + 1), (long long)group_ids[i], (long long)group_ids[i - 1]);
+    CLB_TRY(use_device(s->device));
+    std::unique_ptr<clb_grouping, decltype(&clb_grouping_destroy)> g(new clb_grouping(), clb_grouping_destroy);
+    g->owner = s->serial; g->device = s->device; g->n_docs = n;
+    if (n > 0) {
+        hipStream_t st = s->stream;
+        DevBuf d_ids, flag, before;
+        CLB_TRY(g->gid.alloc(sizeof(uint32_t) * (size_t)n));
+        CLB_TRY(upload(d_ids, group_ids, sizeof(int64_t) * n, st));
+        CLB_TRY(flag.alloc(sizeof(uint32_t) * (size_t)(n + 1)));
+        CLB_TRY(before.alloc(sizeof(uint32_t) * (size_t)(n + 1)));
+        const dim3 blocks((unsigned)((n + 1 + 255) / 256));
+        hipLaunchKernelGGL(grouping_flags_kernel, blocks, dim3(256), 0, st, d_ids.as<int64_t>(), n, flag.as<uint32_t>());
+        CLB_TRY(exclusive_scan_u32(flag.as<uint32_t>(), before.as<uint32_t>(), (size_t)n, st));
+        hipLaunchKernelGGL(grouping_index_kernel, blocks, dim3(256), 0, st, flag.as<uint32_t>(), before.as<uint32_t>(), n,
+                           g->gid.as<uint32_t>());
+        uint32_t total = 0;     // the heads among passages 1 .. n - 1
+        CLB_HIP(hipMemcpyAsync(&total, before.as<uint32_t>() + n, sizeof total, hipMemcpyDeviceToHost, st));
+        CLB_HIP(hipStreamSynchronize(st));      // ... before the scratch and the host array go away
+        CLB_HIP(hipGetLastError());
+        g->count = (int64_t)total + 1;
+    }
+    *out = g.release();
+    return CLB_OK;
+}
+
+int64_t clb_grouping_count(const clb_grouping* g) { return g ? g->count : 0; }
+
+int clb_grouping_destroy(clb_grouping* g) {
+    if (!g) return CLB_OK;
+    (void)hipSetDevice(g->device);
+    delete g;
+    return CLB_OK;
 }
 
 // ---- clb_filter ---------------------------------------------------------------------------------------------------

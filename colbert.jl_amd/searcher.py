@@ -54,6 +54,46 @@ class PassageFilter:
         return self.count
 
 
+class PassageGrouping:
+    """A map passage -> group (document) resident in HBM (clb_grouping, include/colbert_hip.h): made once by
+    `Searcher.make_grouping`, reused over any number of grouped searches of that searcher.  Immutable; valid across
+    `remove_passages` and `update_*`, not across an append (make another).  Keep it alive while a search that uses it may
+    still be running (or a graph that captured it may be replayed).  `count`: the number of groups."""
+
+    def __init__(self, searcher: "Searcher", handle, count: int, group_ids: np.ndarray):
+        self.searcher, self._h, self.count = searcher, handle, int(count)
+        self._ids = group_ids                  # host copy of the caller's ids, entry i = local passage i + 1
+        self._pid_offset = int(getattr(searcher, "pid_offset", 0))
+
+    def groups_of(self, pids) -> np.ndarray:
+        """The caller's group ids of passages as a search returns them (1-based, the searcher's pid_offset included)."""
+        p = np.asarray(pids, dtype=np.int64) - self._pid_offset
+        if p.size and (p.min() < 1 or p.max() > self._ids.size):
+            raise BoundsError(f"pid outside {self._pid_offset + 1}..{self._pid_offset + self._ids.size} "
+                              "(pid 0 pads a short result: cut the result at n_candidates first)")
+        return self._ids[p - 1]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().clb_grouping_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.count
+
+
 class Searcher:
     """struct Searcher (searching.jl:1-16).  Fields that the reference holds as arrays live in HBM
     behind `self._h`; the shapes/meta are kept for introspection."""
@@ -398,20 +438,52 @@ class Searcher:
             arr[j] = f._h.value
         return arr
 
+    # -- groupings --------------------------------------------------------------------------------
+    def make_grouping(self, group_ids=None, group_lens=None) -> PassageGrouping:
+        """A resident passage -> document map for grouped search (`grouping=` of the search calls: the top-k DOCUMENTS, each
+        by its best passage).  Exactly one of: `group_ids`, one integer per passage (`num_docs` entries, entry i = local
+        passage i + 1), non-decreasing -- equal ids are one contiguous pid range, anything else is an ArgumentError naming the
+        passage where the ids decrease -- or `group_lens`, the number of passages of every document in pid order (non-negative,
+        summing to `num_docs`; document j gets id j, 0-based)."""
+        if (group_ids is None) == (group_lens is None):
+            raise ColBERTError("make_grouping takes exactly one of group_ids= and group_lens=")
+        if group_lens is not None:
+            lens = np.asarray(group_lens)
+            if lens.ndim != 1 or lens.dtype.kind not in "iu" or (lens.size and int(lens.min()) < 0) or int(lens.sum()) != self.num_docs:
+                raise ColBERTError(f"group_lens must be non-negative integers summing to num_docs={self.num_docs}")
+            ids = np.repeat(np.arange(lens.size, dtype=np.int64), lens.astype(np.int64))
+        else:
+            ids = np.asarray(group_ids)
+            if ids.ndim != 1 or ids.dtype.kind not in "iu":
+                raise ColBERTError("group_ids must be a vector of integers, one per passage")
+            ids = np.ascontiguousarray(ids, dtype=np.int64).copy()
+        h = C.c_void_p()
+        check(lib().clb_grouping_create(self._h, fptr(ids), i64(ids.size), C.byref(h)))
+        return PassageGrouping(self, h, lib().clb_grouping_count(h), ids)
+
+    def _grouping_handle(self, grouping):
+        if not isinstance(grouping, PassageGrouping) or not grouping._h:
+            raise ColBERTError("grouping is not an open PassageGrouping")
+        return grouping._h
+
     # -- search -----------------------------------------------------------------------------------
-    def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates"):
+    def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates", grouping=None):
         """search() after encode_queries (searching.jl:102-127).  Q: (dim, T) Float32.
         Returns (pids Int64[k] 1-based, scores Float32[k]).
         `filter` (a PassageFilter of this searcher): search among its passages only -- scope "candidates": the query's
         candidates that are in the filter; "all": every passage of the filter (a re-rank of that list).  A filtered search
         never raises for a short result: the k-vectors come back padded, entries past min(k, last_num_candidates) are
-        pid 0 / -Inf."""
+        pid 0 / -Inf.
+        `grouping` (a PassageGrouping of this searcher): the top-k GROUPS, each by its best passage (that passage's pid and
+        score; `grouping.groups_of(pids)` gives the groups); last_num_candidates then counts the candidate groups, and fewer
+        than k of them raise BoundsError as fewer than k candidates do without a grouping (never with a filter)."""
         q = colmajor(Q, np.float32)
         if q.ndim != 2 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T)")
         _scope_code(scope)
-        if filter is not None:
-            p, s, n = self.search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe, filters=[filter], scope=scope)
+        if filter is not None or grouping is not None:
+            p, s, n = self.search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe,
+                                        filters=None if filter is None else [filter], scope=scope, grouping=grouping)
             self.last_num_candidates = int(n[0])
             return np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(s[:, 0])
         pids = np.zeros(k, dtype=np.int64); scores = np.zeros(k, dtype=np.float32)
@@ -422,11 +494,13 @@ class Searcher:
         return pids, scores
 
     def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
-                     scope="candidates"):
+                     scope="candidates", grouping=None):
         """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B]).
         `filters`: one PassageFilter for every query, or a sequence of B entries (None = that query is unfiltered); with
         filters the results are always padded (pid 0 / -Inf past n_candidates[b], the count AFTER the filter) and `scope`
-        is "candidates" (candidates that are in the filter) or "all" (the filter's passages themselves)."""
+        is "candidates" (candidates that are in the filter) or "all" (the filter's passages themselves).
+        `grouping`: one PassageGrouping for the whole batch -- every query returns its k best GROUPS, each by its best
+        passage, and n_candidates counts the candidate groups (after any filter); short results as without a grouping."""
         q = colmajor(Q, np.float32)
         if q.ndim != 3 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T, B)")
@@ -434,6 +508,13 @@ class Searcher:
         code = _scope_code(scope)
         pids = np.zeros((k, B), dtype=np.int64, order="F"); scores = np.zeros((k, B), dtype=np.float32, order="F")
         ncand = np.zeros(B, dtype=np.int64)
+        if grouping is not None:
+            handles = None if filters is None else self._filter_handles(filters, B)
+            check(lib().clb_search_batch_grouped(self._h, fptr(q), i64(q.shape[1]), i64(B), i64(nprobe or self.config.nprobe),
+                                                 i64(k), handles, C.c_int(code), self._grouping_handle(grouping),
+                                                 C.c_int(1 if (pad_short or filters is not None) else 0), fptr(pids),
+                                                 fptr(scores), fptr(ncand)))
+            return pids, scores, ncand
         if filters is not None:
             handles = self._filter_handles(filters, B)
             check(lib().clb_search_batch_filtered(self._h, fptr(q), i64(q.shape[1]), i64(B), i64(nprobe or self.config.nprobe),
@@ -463,18 +544,18 @@ class Searcher:
         return {"pids": pids[:m].copy(), "approx": ap[:m].copy(), "exact": ex[:m].copy(), "tau": tau.value,
                 "eps": eps.value, "n_rescore": nr.value}
 
-    def search(self, query: str, k: int, *, filter=None, scope="candidates"):
-        """search(searcher, query::String, k) (searching.jl:93-128); `filter` / `scope` as in search_embeddings."""
+    def search(self, query: str, k: int, *, filter=None, scope="candidates", grouping=None):
+        """search(searcher, query::String, k) (searching.jl:93-128); `filter` / `scope` / `grouping` as in search_embeddings."""
         _scope_code(scope)
         if self.encoder is None:
             raise ColBERTError("no query encoder attached: pass encoder=... or use search_embeddings(Q, k)")
         Q = self.encoder.encode_queries([query])
         assert Q.shape[2] == 1 and Q.shape[1] == self.config.query_maxlen, Q.shape
-        return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope)
+        return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope, grouping=grouping)
 
     def text_search(self, k: int, nprobe: Optional[int] = None, graph: bool = True) -> "TextSearch":
         """A session for repeated `search(searcher, query::String, k)` calls with everything after the tokenizer on the
-        device (TextSearch below)."""
+        device (TextSearch below).  A session takes no grouping: grouped search is `search(..., grouping=)`."""
         return TextSearch(self, k, nprobe, graph)
 
     # -- profiling (bench.py) -----------------------------------------------------------------------
@@ -688,9 +769,9 @@ class TextSearch:
         self._many = None
 
 
-def search(searcher: Searcher, query, k: int, *, filter=None, scope="candidates"):
+def search(searcher: Searcher, query, k: int, *, filter=None, scope="candidates", grouping=None):
     """The reference's exported `search` (src/ColBERT.jl:40).  `query` may be a string (needs an
-    encoder) or a (dim, T) Float32 matrix of query embeddings.  `filter` / `scope`: Searcher.search_embeddings."""
+    encoder) or a (dim, T) Float32 matrix of query embeddings.  `filter` / `scope` / `grouping`: Searcher.search_embeddings."""
     if isinstance(query, str):
-        return searcher.search(query, k, filter=filter, scope=scope)
-    return searcher.search_embeddings(query, k, filter=filter, scope=scope)
+        return searcher.search(query, k, filter=filter, scope=scope, grouping=grouping)
+    return searcher.search_embeddings(query, k, filter=filter, scope=scope, grouping=grouping)

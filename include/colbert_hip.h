@@ -325,6 +325,50 @@ int clb_search_shard_phase1_filtered_slot(clb_searcher* s, int slot, const float
                                           int64_t k, const clb_filter* const* filters, int scope, float* d_local_top,
                                           void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Grouped search: rank DOCUMENTS by their best passage (no counterpart in the reference; the "collapse" of Elasticsearch and
+ * Vespa, the docs2passages evaluation of upstream ColBERT).  A clb_grouping maps every local passage to a group.  The
+ * caller's group_ids -- exactly n_docs entries, entry i = local passage i -- must be NON-DECREASING in pid, so that equal
+ * ids are one contiguous pid range (anything else is CLB_EARGUMENT, naming the first passage at which the ids decrease;
+ * the check runs on the host before anything is allocated; groups that are not contiguous are not supported).  Resident
+ * form: one u32 per passage, the dense 0-based index of its group (4 MB per million passages), computed on the device.
+ *
+ * A grouped search of a query returns k GROUPS, each by its representative passage and that passage's fp32 score: the
+ * candidate passage of the group with the largest exact MaxSim score, the lowest pid among equal scores; groups ordered by
+ * score descending, the lower representative pid first among equal scores.  That is the reference's full stable ranking of
+ * the query's candidates with the first occurrence of every group kept and then the first k taken -- pids and score bits are
+ * identical to that.  n_cand is the number of distinct groups among the query's candidates (after any filter); fewer than
+ * k of them is a short result.  Filters compose in both scopes: the filter defines the candidates, the grouping acts on what
+ * is left.  A passage without embeddings is never a candidate, so a group of only such passages never appears.
+ *
+ * Like a filter, a grouping is immutable, bound to the searcher it was made for and to its n_docs: it stays valid over
+ * clb_searcher_remove and clb_searcher_update, one made before an append is refused ("grouping made before an append; make
+ * another"), one made for another searcher is refused (both CLB_EARGUMENT).  It MUST outlive every call that uses it,
+ * including calls still enqueued on a stream or captured in a graph; it may be destroyed before or after its searcher.
+ * Creation synchronises; searching with it does not.  A call takes ONE grouping for the whole batch.  The two-phase shard
+ * calls take none: a group may straddle shards.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct clb_grouping clb_grouping;
+int clb_grouping_create(clb_searcher* s, const int64_t* group_ids, int64_t n, clb_grouping** out);
+/* number of groups (a host value, fixed at creation); 0 for a null handle */
+int64_t clb_grouping_count(const clb_grouping* g);
+/* a null handle is CLB_OK, like clb_filter_destroy */
+int clb_grouping_destroy(clb_grouping* g);
+/* clb_search_batch_filtered with a grouping: `filters` / `scope` as there (filters == NULL: nothing is filtered), pad_short
+ * as in clb_search_batch (0: a query with fewer than k candidate groups is CLB_EBOUNDS; 1: pid 0 / -Inf padding).
+ * grouping == NULL launches exactly what clb_search_batch_filtered launches. */
+int clb_search_batch_grouped(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                             const clb_filter* const* filters, int scope, const clb_grouping* grouping, int pad_short,
+                             int64_t* out_pids, float* out_scores, int64_t* n_cand);
+/* clb_search_batch_filtered_device_slot with a grouping: stream-ordered, no host synchronisation; after the slot's first
+ * grouped call it allocates nothing (the first one grows the slot by two slot lists of its candidate capacity per query).
+ * Capturable in a HIP graph under the rule of the filtered search: the graph holds the grouping's device address, and a
+ * call that grows the workspace makes a captured graph stale.  grouping == NULL launches exactly what
+ * clb_search_batch_filtered_device_slot launches. */
+int clb_search_batch_grouped_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
+                                         int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand, void* hip_stream);
+
 /* retrieve()  (src/search/ranking.jl:23-44) on its own -- test hook.  out_pids needs n_docs entries. */
 int clb_retrieve(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe, int64_t* out_pids,
                  int64_t* n_out);
