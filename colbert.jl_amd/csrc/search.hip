@@ -8,14 +8,12 @@
 #include <memory>
 #include <numeric>
 
-#include "append_kernels.hpp"
 #include "approx_kernels.hpp"
 #include "generic_kernels.hpp"
 #include "group_kernels.hpp"
-#include "remove_kernels.hpp"
+#include "index_change_kernels.hpp"
 #include "search_kernels.hpp"
 #include "sort.hpp"
-#include "update_kernels.hpp"
 
 using namespace clb;
 
@@ -1161,34 +1159,169 @@ void install_index_tables(clb_searcher* s, IndexTables& t, bool keep_max = false
     s->index_bytes = resident_bytes(s);
 }
 
-// the row compaction of clb_searcher_remove (remove_kernels.hpp) in pieces of one size: s still holds the unreduced index
-template <class Piece>
-void launch_remove_rows(hipStream_t st, const clb_searcher* s, const uint32_t* new_off, int64_t n_rows, size_t row_bytes,
-                        uint32_t* codes_dst, uint8_t* res_dst) {
-    const int64_t tiles = (n_rows + kRemoveTile - 1) / kRemoveTile;
-    hipLaunchKernelGGL(remove_rows_kernel<Piece>, dim3((unsigned)std::min<int64_t>(tiles, 8192)), dim3(256), 0, st,
-                       s->doc_off.as<uint32_t>(), new_off, (int)s->n_docs, n_rows, s->codes0.as<uint32_t>(),
-                       s->residuals.as<Piece>(), (int)(row_bytes / sizeof(Piece)), codes_dst, reinterpret_cast<Piece*>(res_dst));
+// ---- index changes: clb_searcher_append, clb_searcher_remove, clb_searcher_update (index_change_kernels.hpp) ----------------
+// What a change builds BESIDE the handle's arrays: the per-embedding and per-passage arrays and the inverted lists of the
+// changed index, its counts and -- filled by commit_index_change -- the host copy of the list offsets and the approximate-pass
+// tables.  commit_index_change swaps all of it in after the last device work has been waited for: any return before that
+// leaves the handle untouched.
+struct IndexChange {
+    DevBuf codes0, residuals, doc_off, live, ivf_off, ivf_pid;
+    IndexTables tables;
+    std::vector<uint32_t> h_ivf_off;        // K + 1 list offsets
+    int64_t n_docs = 0, n_emb = 0, max_doclen = 0;
+};
+
+// the first device step of a change, after the arguments have been checked on the host
+int begin_index_change(const clb_searcher* s) {
+    CLB_TRY(use_device(s->device));
+    CLB_HIP(hipDeviceSynchronize());      // searches of this handle and whatever wrote the caller's device arrays
+    return CLB_OK;
 }
 
-// the row splice of clb_searcher_update (update_kernels.hpp) in pieces of one size: s still holds the old index
-template <class Piece>
-void launch_splice_rows(hipStream_t st, const clb_searcher* s, const uint32_t* new_off, const uint32_t* named,
-                        const uint32_t* slot, const uint32_t* stage_off, int64_t n_rows, size_t row_bytes,
-                        const uint32_t* codes_stage, const uint8_t* res_stage, uint32_t* codes_dst, uint8_t* res_dst) {
-    const int64_t tiles = (n_rows + kSpliceTile - 1) / kSpliceTile;
-    hipLaunchKernelGGL(splice_rows_kernel<Piece>, dim3((unsigned)std::min<int64_t>(tiles, 8192)), dim3(256), 0, st,
-                       s->doc_off.as<uint32_t>(), new_off, named, slot, stage_off, (int)s->n_docs, n_rows,
-                       s->codes0.as<uint32_t>(), s->residuals.as<Piece>(), codes_stage, reinterpret_cast<const Piece*>(res_stage),
-                       (int)(row_bytes / sizeof(Piece)), codes_dst, reinterpret_cast<Piece*>(res_dst));
+int check_pid_range(const clb_searcher* s, const int64_t* pids, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (pids[i] <= s->pid_offset || pids[i] > s->pid_offset + s->n_docs)
+            return fail(CLB_EBOUNDS, "pid %lld (entry %lld) outside %lld..%lld", (long long)pids[i], (long long)i,
+                        (long long)(s->pid_offset + 1), (long long)(s->pid_offset + s->n_docs));
+    return CLB_OK;
 }
 
-// The end of an append, a removal or an update, after the arrays and counts of the changed index have been swapped in (h_ivf_off: the
-// host copy of its K + 1 list offsets): what the handle derives from them, the workspaces, the generation.  Cannot fail.
-void finish_index_change(clb_searcher* s, IndexTables& tables, const std::vector<uint32_t>& h_ivf_off) {
-    s->ivf_len_sorted = sorted_list_lengths(h_ivf_off);
+// The n_emb > 0 new rows of n passages, where the change reads them: codes_dst / res_dst, the tail of the grown arrays for an
+// append and a staging pair for an update.  codes_in: their 0-based, checked codes on the device; off_dev: the passages' n + 1
+// offsets among them.  The tuned path gives them create's per-passage code order over the new rows alone (old passages keep
+// theirs); the general path keeps the caller's order.
+int stage_new_rows(const clb_searcher* s, const uint32_t* codes_in, const uint32_t* off_dev, int64_t n_emb, int64_t n,
+                   const uint8_t* residuals, bool on_device, uint32_t* codes_dst, uint8_t* res_dst) {
+    const hipStream_t st = s->stream;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const size_t rows = (size_t)(s->dim / 8 * s->nbits);
+    if (s->generic) {
+        CLB_HIP(hipMemcpyAsync(codes_dst, codes_in, sizeof(uint32_t) * n_emb, hipMemcpyDeviceToDevice, st));
+        CLB_HIP(hipMemcpyAsync(res_dst, residuals, rows * n_emb, kind, st));
+        return CLB_OK;
+    }
+    DevBuf res_in;
+    if (!on_device || ((uintptr_t)residuals & 15)) {        // the row permutation reads 16-byte pieces
+        CLB_TRY(res_in.alloc(rows * n_emb));
+        CLB_HIP(hipMemcpyAsync(res_in.p, residuals, rows * n_emb, kind, st));
+        residuals = res_in.as<uint8_t>();
+    }
+    return order_rows_by_code(st, codes_in, off_dev, n_emb, n, residuals, rows, codes_dst, res_dst);
+}
+
+// the n named passages as a bitmap in a filter's layout (a SET bit: named; naming one twice is the caller's to refuse); a pid
+// outside the handle raises *err.  d_pids: the pids on the device -- read *err before it and the host array go away.
+int mark_passages(const clb_searcher* s, const int64_t* pids, int64_t n, DevBuf* d_pids, DevBuf* bits, int* err) {
+    CLB_TRY(upload(*d_pids, pids, sizeof(int64_t) * n, s->stream));
+    CLB_TRY(bits->alloc(sizeof(uint32_t) * (size_t)((s->n_docs + 31) / 32)));
+    CLB_HIP(hipMemsetAsync(bits->p, 0, bits->bytes, s->stream));
+    hipLaunchKernelGGL(filter_mark_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, d_pids->as<int64_t>(), n,
+                       s->pid_offset, (int)s->n_docs, bits->as<uint32_t>(), err);
+    return CLB_OK;
+}
+
+// pos (n_emb + 1 entries): the entries of the handle's inverted lists in front of each one whose passage is not named
+int scan_kept_entries(const clb_searcher* s, const uint32_t* named, DevBuf* pos) {
+    DevBuf flag;
+    CLB_TRY(flag.alloc(sizeof(uint32_t) * (s->n_emb + 1)));
+    CLB_TRY(pos->alloc(sizeof(uint32_t) * (s->n_emb + 1)));
+    hipLaunchKernelGGL(ivf_keep_flags_kernel, dim3((unsigned)((s->n_emb + 1 + 255) / 256)), dim3(256), 0, s->stream,
+                       s->ivf_pid.as<uint32_t>(), named, s->n_emb, flag.as<uint32_t>());
+    return exclusive_scan_u32(flag.as<uint32_t>(), pos->as<uint32_t>(), (size_t)s->n_emb, s->stream);     // waits: flag may go
+}
+
+// the kept entries in their old order and the offsets of their lists, from the same scan: no sort
+int compact_lists(const clb_searcher* s, const DevBuf& pos, int64_t n_kept, DevBuf* off, DevBuf* pid) {
+    CLB_TRY(off->alloc(sizeof(uint32_t) * (s->K + 1)));
+    CLB_TRY(pid->alloc(sizeof(uint32_t) * n_kept));
+    hipLaunchKernelGGL(ivf_compact_kernel, dim3((unsigned)((s->n_emb + 1 + 255) / 256)), dim3(256), 0, s->stream,
+                       s->ivf_pid.as<uint32_t>(), pos.as<uint32_t>(), s->n_emb, pid->as<uint32_t>());
+    hipLaunchKernelGGL((list_offsets_kernel<true, false>), dim3((unsigned)((s->K + 1 + 255) / 256)), dim3(256), 0, s->stream,
+                       s->ivf_off.as<uint32_t>(), pos.as<uint32_t>(), (const uint32_t*)nullptr, (int)(s->K + 1), off->as<uint32_t>());
+    return CLB_OK;
+}
+
+// The inverted-list entries of n_emb new embeddings: the scan of the histogram of their codes (off, K + 1 entries) and their
+// local pids in list order (pid; code beside them).  codes_in / off_dev as in stage_new_rows; the passages are d_pids (the
+// caller's pids on the device) or, without them, pid_base onwards.  One stable sort by code gives the (code, embedding) order
+// of a fresh build when the pids ascend with the embeddings (an append); by_pid sorts by pid first, so that every list's new
+// entries hold non-decreasing pids whatever the caller's order is (an update).  Waits for the stream.
+struct NewEntries {
+    DevBuf off, code, pid;
+};
+int sort_new_entries(const clb_searcher* s, const uint32_t* codes_in, const uint32_t* off_dev, int64_t n, const int64_t* d_pids,
+                     int64_t pid_base, int64_t n_emb, bool by_pid, NewEntries* e) {
+    const hipStream_t st = s->stream;
+    DevBuf hist, pid_in, pid2, code2;
+    CLB_TRY(hist.alloc(sizeof(uint32_t) * (s->K + 1)));
+    CLB_TRY(pid_in.alloc(sizeof(uint32_t) * n_emb));
+    CLB_TRY(e->off.alloc(sizeof(uint32_t) * (s->K + 1)));
+    CLB_TRY(e->code.alloc(sizeof(uint32_t) * n_emb));
+    CLB_TRY(e->pid.alloc(sizeof(uint32_t) * n_emb));
+    CLB_HIP(hipMemsetAsync(hist.p, 0, hist.bytes, st));
+    if (n_emb > 0)
+        hipLaunchKernelGGL(hist_pid_kernel, dim3((unsigned)((n_emb + 255) / 256)), dim3(256), 0, st, codes_in, off_dev, d_pids,
+                           s->pid_offset, (uint32_t)pid_base, n_emb, (int)n, hist.as<uint32_t>(), pid_in.as<uint32_t>());
+    CLB_TRY(exclusive_scan_u32(hist.as<uint32_t>(), e->off.as<uint32_t>(), (size_t)s->K, st));
+    int pid_bits = 1, code_bits = 1;
+    while (((int64_t)1 << pid_bits) < s->n_docs) ++pid_bits;
+    while (((int64_t)1 << code_bits) < s->K) ++code_bits;
+    const uint32_t *codes = codes_in, *pids = pid_in.as<uint32_t>();
+    if (by_pid) {
+        CLB_TRY(pid2.alloc(sizeof(uint32_t) * n_emb));
+        CLB_TRY(code2.alloc(sizeof(uint32_t) * n_emb));
+        CLB_TRY(sort_pairs_u32(pids, pid2.as<uint32_t>(), codes, code2.as<uint32_t>(), (size_t)n_emb, pid_bits, st));
+        codes = code2.as<uint32_t>(); pids = pid2.as<uint32_t>();
+    }
+    return sort_pairs_u32(codes, e->code.as<uint32_t>(), pids, e->pid.as<uint32_t>(), (size_t)n_emb, code_bits, st);
+}
+
+// c's lists: those of old_off / old_pid (K lists, c->n_emb - the new entries) with e's new entries behind them, list by list
+int merge_lists(const clb_searcher* s, const uint32_t* old_off, const uint32_t* old_pid, const NewEntries& e, IndexChange* c) {
+    CLB_TRY(c->ivf_off.alloc(sizeof(uint32_t) * (s->K + 1)));
+    CLB_TRY(c->ivf_pid.alloc(sizeof(uint32_t) * c->n_emb));
+    hipLaunchKernelGGL((list_offsets_kernel<false, true>), dim3((unsigned)((s->K + 1 + 255) / 256)), dim3(256), 0, s->stream, old_off,
+                       (const uint32_t*)nullptr, e.off.as<uint32_t>(), (int)(s->K + 1), c->ivf_off.as<uint32_t>());
+    const int64_t tiles = (c->n_emb + kTile - 1) / kTile;
+    if (tiles > 0)
+        hipLaunchKernelGGL(ivf_merge_kernel, dim3((unsigned)std::min<int64_t>(tiles, 8192)), dim3(256), 0, s->stream, old_off,
+                           e.off.as<uint32_t>(), c->ivf_off.as<uint32_t>(), old_pid, e.pid.as<uint32_t>(), (int)s->K, c->n_emb,
+                           c->ivf_pid.as<uint32_t>());
+    return CLB_OK;
+}
+
+// f(Piece{}) with the widest piece that a residual row of row_bytes is a whole number of
+template <class F>
+void with_piece(size_t row_bytes, F&& f) {
+    if (row_bytes % 16 == 0) f(uint4{});
+    else if (row_bytes % 4 == 0) f(uint32_t{});
+    else f(uint8_t{});
+}
+
+// The end of a change, once everything of `c` but the tables has been enqueued: checks the lists, derives what the handle
+// keeps of the changed index, waits, and only then touches the handle.
+int commit_index_change(clb_searcher* s, IndexChange& c) {
+    const hipStream_t st = s->stream;
+    CLB_HIP(hipGetLastError());
+    c.h_ivf_off.resize((size_t)s->K + 1);
+    CLB_HIP(hipMemcpyAsync(c.h_ivf_off.data(), c.ivf_off.p, sizeof(uint32_t) * (s->K + 1), hipMemcpyDeviceToHost, st));
+    CLB_HIP(hipStreamSynchronize(st));
+    if ((int64_t)c.h_ivf_off[s->K] != c.n_emb)
+        return fail(CLB_EHIP, "the changed inverted lists hold %lld entries, expected %lld", (long long)c.h_ivf_off[s->K],
+                    (long long)c.n_emb);
+    // code | inv_norm words and bound constants: one streaming pass over the whole changed index -- inv_norm is quantised over
+    // the index's own range, which a new row may widen and a dropped row may narrow
+    if (!s->generic) CLB_TRY(derive_index_tables(s, c.codes0.as<uint32_t>(), c.residuals.as<uint8_t>(), c.n_emb, &c.tables));
+    CLB_HIP(hipStreamSynchronize(st));
+    CLB_HIP(hipGetLastError());
+
+    // ---- nothing below can fail ----
+    swap_buf(s->codes0, c.codes0); swap_buf(s->residuals, c.residuals); swap_buf(s->doc_off, c.doc_off);
+    swap_buf(s->ivf_off, c.ivf_off); swap_buf(s->ivf_pid, c.ivf_pid); swap_buf(s->live, c.live);
+    s->n_docs = c.n_docs; s->n_emb = c.n_emb; s->max_doclen = c.max_doclen;
+    s->ivf_len_sorted = sorted_list_lengths(c.h_ivf_off);
     if (s->generic) s->index_bytes = resident_bytes(s);
-    else install_index_tables(s, tables, s->bounds_synced);
+    else install_index_tables(s, c.tables, s->bounds_synced);
     for (auto& w : s->ws) {       // sized for the old index: the next ensure_workspace sizes every buffer again
         w.Bcap = 0;
         w.filt_cap = 0;           // populations of filters that no longer fit the handle
@@ -1196,6 +1329,110 @@ void finish_index_change(clb_searcher* s, IndexTables& tables, const std::vector
         w.pending.valid = false;
     }
     ++s->generation;
+    return CLB_OK;
+}
+
+// clb_searcher_remove and clb_searcher_update / _device after their host checks: the n passages `pids` lose their rows and, with
+// `add`, get the add->total new ones that it delimits in the caller's order (codes, residuals).  Without new rows -- a removal, or
+// an update to all-empty content -- no row is staged and the lists are only compacted.  *n_changed: the named passages whose
+// old or new length is not zero; none: the handle stays as it is, generation included.
+int replace_passages(clb_searcher* s, int64_t n, const int64_t* pids, const Offsets* add, const uint32_t* codes,
+                     const uint8_t* residuals, bool on_device, int64_t* n_changed) {
+    const int64_t n_old = s->n_emb, n_docs = s->n_docs, K = s->K, n_add = add ? add->total : 0;
+    const bool staged = n_add > 0;
+    CLB_TRY(begin_index_change(s));
+    const hipStream_t st = s->stream;
+    const size_t rows = (size_t)(s->dim / 8 * s->nbits);
+    IndexChange c;
+    DevWord<ChangeCounts> counts;
+    {   // the scratch of the call
+        // the new codes, 0-based and checked, in a buffer of the call's own; the named passages as a bitmap and their place in
+        // the caller's list; the lengths of the changed index
+        DevBuf codes_in, d_pids, stage_off, named, slot, len;
+        DevWord<int> err;
+        CLB_TRY(err.init(st));
+        CLB_TRY(counts.init(st));
+        CLB_TRY(mark_passages(s, pids, n, &d_pids, &named, err.ptr()));
+        if (staged) {
+            CLB_TRY(codes_in.alloc(sizeof(uint32_t) * n_add));
+            CLB_TRY(stage_codes(st, codes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, n_add, K,
+                                codes_in.as<uint32_t>(), err.ptr()));
+            CLB_TRY(upload(stage_off, add->off.data(), sizeof(uint32_t) * add->off.size(), st));
+            CLB_TRY(slot.alloc(sizeof(uint32_t) * n_docs));
+            hipLaunchKernelGGL(update_slots_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_pids.as<int64_t>(), n,
+                               s->pid_offset, (int)n_docs, slot.as<uint32_t>());
+        }
+        CLB_TRY(len.alloc(sizeof(uint32_t) * (n_docs + 1)));
+        CLB_TRY(c.doc_off.alloc(sizeof(uint32_t) * (n_docs + 1)));
+        const auto lengths_kernel = staged ? change_lengths_kernel<true> : change_lengths_kernel<false>;
+        hipLaunchKernelGGL(lengths_kernel, dim3((unsigned)((n_docs + 1 + 255) / 256)), dim3(256), 0, st, s->doc_off.as<uint32_t>(),
+                           named.as<uint32_t>(), slot.as<uint32_t>(), stage_off.as<uint32_t>(), (int)n_docs, len.as<uint32_t>(),
+                           counts.ptr());
+        CLB_TRY(err.read(st));                // ... before the host arrays go away
+        CLB_TRY(counts.read(st));
+        if (err.value & kErrCode) return bad_codes();
+        if (err.value) return fail(CLB_EBOUNDS, "a pid outside the searcher's passages");
+        if (staged) CLB_TRY(check_shard_limits(n_old - (int64_t)counts.value.dropped + n_add, n_docs));
+        if (counts.value.changed == 0) return CLB_OK;       // every named passage was empty and stays empty
+        uint32_t n_rows = 0;
+        CLB_TRY(exclusive_scan_u32(len.as<uint32_t>(), c.doc_off.as<uint32_t>(), (size_t)n_docs, st));
+        CLB_HIP(hipMemcpyAsync(&n_rows, c.doc_off.as<uint32_t>() + n_docs, sizeof n_rows, hipMemcpyDeviceToHost, st));
+        CLB_HIP(hipStreamSynchronize(st));
+        c.n_docs = n_docs; c.n_emb = n_rows; c.max_doclen = counts.value.longest;
+        CLB_TRY(build_live_bitmap(st, c.doc_off.as<uint32_t>(), n_docs, &c.live));
+
+        // one splice of the kept rows and the staged new ones, and the zero padding of one step
+        DevBuf codes_staged, res_staged;
+        if (staged) {
+            CLB_TRY(codes_staged.alloc(sizeof(uint32_t) * n_add));
+            CLB_TRY(res_staged.alloc(rows * n_add));
+            CLB_TRY(stage_new_rows(s, codes_in.as<uint32_t>(), stage_off.as<uint32_t>(), n_add, n, residuals, on_device,
+                                   codes_staged.as<uint32_t>(), res_staged.as<uint8_t>()));
+        }
+        CLB_TRY(alloc_padded_rows(st, c.n_emb, rows, &c.codes0, &c.residuals));
+        const int64_t row_tiles = (c.n_emb + kTile - 1) / kTile;
+        if (row_tiles > 0)
+            with_piece(rows, [&](auto piece) {
+                using Piece = decltype(piece);
+                const auto rows_kernel = staged ? splice_rows_kernel<Piece, true> : splice_rows_kernel<Piece, false>;
+                hipLaunchKernelGGL(rows_kernel, dim3((unsigned)std::min<int64_t>(row_tiles, 8192)), dim3(256), 0, st, s->doc_off.as<uint32_t>(),
+                                   c.doc_off.as<uint32_t>(), named.as<uint32_t>(), slot.as<uint32_t>(), stage_off.as<uint32_t>(),
+                                   (int)n_docs, c.n_emb, s->codes0.as<uint32_t>(), s->residuals.as<Piece>(),
+                                   codes_staged.as<uint32_t>(), res_staged.as<Piece>(), (int)(rows / sizeof(Piece)),
+                                   c.codes0.as<uint32_t>(), c.residuals.as<Piece>());
+            });
+
+        // the inverted lists.  Kept entries: a flag per old entry and its scan.  Without new entries one scatter of the entries
+        // that stay, in their old order.  With them, on lists that hold non-decreasing pids, one pass puts both where a fresh
+        // build would; on lists in the caller's own order the kept entries stay in that order (the same compaction) and the
+        // new ones go behind them list by list (an append's merge): the lists stay unsorted.
+        DevBuf pos, kept_off, kept_pid;
+        NewEntries e;
+        CLB_TRY(scan_kept_entries(s, named.as<uint32_t>(), &pos));
+        if (!staged) {
+            CLB_TRY(compact_lists(s, pos, c.n_emb, &c.ivf_off, &c.ivf_pid));
+        } else {
+            CLB_TRY(sort_new_entries(s, codes_in.as<uint32_t>(), stage_off.as<uint32_t>(), n, d_pids.as<int64_t>(), 0, n_add, true, &e));
+            if (s->ivf_sorted) {
+                CLB_TRY(c.ivf_off.alloc(sizeof(uint32_t) * (K + 1)));
+                CLB_TRY(c.ivf_pid.alloc(sizeof(uint32_t) * c.n_emb));
+                hipLaunchKernelGGL((list_offsets_kernel<true, true>), dim3((unsigned)((K + 1 + 255) / 256)), dim3(256), 0, st,
+                                   s->ivf_off.as<uint32_t>(), pos.as<uint32_t>(), e.off.as<uint32_t>(), (int)(K + 1),
+                                   c.ivf_off.as<uint32_t>());
+                const int64_t tiles = (n_old + kTile - 1) / kTile + (n_add + kTile - 1) / kTile;
+                hipLaunchKernelGGL(ivf_splice_kernel, dim3((unsigned)std::min<int64_t>(tiles, 8192)), dim3(256), 0, st,
+                                   s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), pos.as<uint32_t>(), n_old, e.off.as<uint32_t>(),
+                                   e.code.as<uint32_t>(), e.pid.as<uint32_t>(), n_add, (int)K, c.ivf_pid.as<uint32_t>());
+            } else {
+                CLB_TRY(compact_lists(s, pos, c.n_emb - n_add, &kept_off, &kept_pid));
+                CLB_TRY(merge_lists(s, kept_off.as<uint32_t>(), kept_pid.as<uint32_t>(), e, &c));
+            }
+        }
+        CLB_HIP(hipStreamSynchronize(st));      // the scratch goes away here
+    }
+    CLB_TRY(commit_index_change(s, c));
+    if (n_changed) *n_changed = counts.value.changed;
+    return CLB_OK;
 }
 
 }  // namespace
@@ -1333,9 +1570,8 @@ int clb_searcher_destroy(clb_searcher* s) {
     return CLB_OK;
 }
 
-// clb_searcher_append / _device (include/colbert_hip.h).  Everything is built beside the handle's arrays -- the grown codes0 /
-// residuals / doc_off, the merged inverted lists, the approximate-pass tables of the WHOLE grown index -- and swapped in
-// after the last device work has been waited for: any return before that leaves the handle untouched.
+// clb_searcher_append / _device (include/colbert_hip.h).  The old rows move with plain device copies and the new ones go
+// behind them; the inverted lists are the old lists with the new entries behind them, list by list.
 static int searcher_append_impl(clb_searcher* s, int64_t n_new, const int64_t* doclens, int64_t n_new_emb,
                                 const uint32_t* codes, const uint8_t* residuals, bool on_device) {
     if (!s) return fail(CLB_EARGUMENT, "null searcher");
@@ -1344,104 +1580,46 @@ static int searcher_append_impl(clb_searcher* s, int64_t n_new, const int64_t* d
     Offsets add;            // the appended passages among the appended embeddings
     CLB_TRY(passage_offsets(doclens, n_new, n_new_emb, "appended passage", &add));
     if (n_new == 0) return CLB_OK;
-    const int64_t n_old = s->n_emb, d_old = s->n_docs, n_tot = n_old + n_new_emb, d_tot = d_old + n_new, K = s->K;
-    CLB_TRY(check_shard_limits(n_tot, d_tot));
-    CLB_TRY(use_device(s->device));
-    CLB_HIP(hipDeviceSynchronize());      // searches of this handle and whatever wrote the caller's device arrays
+    const int64_t n_old = s->n_emb, d_old = s->n_docs;
+    IndexChange c;
+    c.n_docs = d_old + n_new; c.n_emb = n_old + n_new_emb; c.max_doclen = std::max<int64_t>(s->max_doclen, add.longest);
+    CLB_TRY(check_shard_limits(c.n_emb, c.n_docs));
+    CLB_TRY(begin_index_change(s));
     const hipStream_t st = s->stream;
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const size_t rows = (size_t)(s->dim / 8 * s->nbits);
-    const int blocks = (int)((n_new_emb + 255) / 256);
+    {   // the scratch of the call
+        // the new codes, 0-based and checked, in a buffer of the call's own
+        DevBuf codes_in, new_off_d;
+        DevWord<int> err;
+        CLB_TRY(codes_in.alloc(sizeof(uint32_t) * n_new_emb));
+        CLB_TRY(err.init(st));
+        CLB_TRY(stage_codes(st, codes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, n_new_emb, s->K,
+                            codes_in.as<uint32_t>(), err.ptr()));
+        CLB_TRY(err.read(st));
+        if (err.value & kErrCode) return bad_codes();
 
-    // the new codes, 0-based and checked, in a buffer of the call's own
-    DevBuf codes_in;
-    DevWord<int> err;
-    CLB_TRY(codes_in.alloc(sizeof(uint32_t) * n_new_emb));
-    CLB_TRY(err.init(st));
-    CLB_TRY(stage_codes(st, codes, kind, n_new_emb, K, codes_in.as<uint32_t>(), err.ptr()));
-    CLB_TRY(err.read(st));
-    if (err.value & kErrCode) return bad_codes();
+        // grown per-embedding and per-passage arrays: the old rows, the new rows behind them, the zero padding of one step
+        CLB_TRY(alloc_padded_rows(st, c.n_emb, rows, &c.codes0, &c.residuals));
+        CLB_TRY(c.doc_off.alloc(sizeof(uint32_t) * (c.n_docs + 1)));
+        CLB_TRY(upload(new_off_d, add.off.data(), sizeof(uint32_t) * add.off.size(), st));
+        CLB_HIP(hipMemcpyAsync(c.codes0.p, s->codes0.p, sizeof(uint32_t) * n_old, hipMemcpyDeviceToDevice, st));
+        CLB_HIP(hipMemcpyAsync(c.residuals.p, s->residuals.p, rows * n_old, hipMemcpyDeviceToDevice, st));
+        CLB_HIP(hipMemcpyAsync(c.doc_off.p, s->doc_off.p, sizeof(uint32_t) * (d_old + 1), hipMemcpyDeviceToDevice, st));
+        std::vector<uint32_t> off_tail((size_t)n_new);
+        for (int64_t p = 0; p < n_new; ++p) off_tail[p] = (uint32_t)(n_old + add.off[p + 1]);
+        CLB_HIP(hipMemcpyAsync(c.doc_off.as<uint32_t>() + d_old + 1, off_tail.data(), sizeof(uint32_t) * n_new, hipMemcpyHostToDevice, st));
+        CLB_TRY(build_live_bitmap(st, c.doc_off.as<uint32_t>(), c.n_docs, &c.live));
+        if (n_new_emb > 0)
+            CLB_TRY(stage_new_rows(s, codes_in.as<uint32_t>(), new_off_d.as<uint32_t>(), n_new_emb, n_new, residuals, on_device,
+                                   c.codes0.as<uint32_t>() + n_old, c.residuals.as<uint8_t>() + rows * n_old));
 
-    // grown per-embedding and per-passage arrays: the old rows, the new rows behind them, the zero padding of one step
-    DevBuf codes0, res, doc_off, new_off_d;
-    CLB_TRY(alloc_padded_rows(st, n_tot, rows, &codes0, &res));
-    CLB_TRY(doc_off.alloc(sizeof(uint32_t) * (d_tot + 1)));
-    CLB_TRY(upload(new_off_d, add.off.data(), sizeof(uint32_t) * add.off.size(), st));
-    uint32_t* codes0_tail = codes0.as<uint32_t>() + n_old;
-    uint8_t* res_tail = res.as<uint8_t>() + rows * n_old;
-    CLB_HIP(hipMemcpyAsync(codes0.p, s->codes0.p, sizeof(uint32_t) * n_old, hipMemcpyDeviceToDevice, st));
-    CLB_HIP(hipMemcpyAsync(res.p, s->residuals.p, rows * n_old, hipMemcpyDeviceToDevice, st));
-    CLB_HIP(hipMemcpyAsync(doc_off.p, s->doc_off.p, sizeof(uint32_t) * (d_old + 1), hipMemcpyDeviceToDevice, st));
-    std::vector<uint32_t> off_tail((size_t)n_new);
-    for (int64_t p = 0; p < n_new; ++p) off_tail[p] = (uint32_t)(n_old + add.off[p + 1]);
-    CLB_HIP(hipMemcpyAsync(doc_off.as<uint32_t>() + d_old + 1, off_tail.data(), sizeof(uint32_t) * n_new, hipMemcpyHostToDevice, st));
-    DevBuf live;
-    CLB_TRY(build_live_bitmap(st, doc_off.as<uint32_t>(), d_tot, &live));
-    if (n_new_emb > 0 && !s->generic) {
-        // create's per-passage code order on the new passages alone (old passages keep theirs), over the new rows and their
-        // own offsets, written straight into the tail of the grown arrays
-        DevBuf res_in;
-        const uint8_t* res_src = residuals;
-        if (!on_device || ((uintptr_t)residuals & 15)) {        // the row permutation reads 16-byte pieces
-            CLB_TRY(res_in.alloc(rows * n_new_emb));
-            CLB_HIP(hipMemcpyAsync(res_in.p, residuals, rows * n_new_emb, kind, st));
-            res_src = res_in.as<uint8_t>();
-        }
-        CLB_TRY(order_rows_by_code(st, codes_in.as<uint32_t>(), new_off_d.as<uint32_t>(), n_new_emb, n_new, res_src, rows,
-                                   codes0_tail, res_tail));
-    } else if (n_new_emb > 0) {
-        CLB_HIP(hipMemcpyAsync(codes0_tail, codes_in.p, sizeof(uint32_t) * n_new_emb, hipMemcpyDeviceToDevice, st));
-        CLB_HIP(hipMemcpyAsync(res_tail, residuals, rows * n_new_emb, kind, st));
+        // the inverted lists: the new entries in the (code, embedding) order of a fresh build, one merge
+        NewEntries e;
+        CLB_TRY(sort_new_entries(s, codes_in.as<uint32_t>(), new_off_d.as<uint32_t>(), n_new, nullptr, d_old, n_new_emb, false, &e));
+        CLB_TRY(merge_lists(s, s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), e, &c));
+        CLB_HIP(hipStreamSynchronize(st));      // the scratch goes away here
     }
-
-    // the inverted lists: histogram and scan of the new codes, their (code, embedding)-stable order as local pids, one merge
-    DevBuf hist, add_off, ivf_off, ivf_pid, add_pid, add_pid_sorted, codes_sorted;
-    CLB_TRY(hist.alloc(sizeof(uint32_t) * (K + 1)));
-    CLB_TRY(add_off.alloc(sizeof(uint32_t) * (K + 1)));
-    CLB_TRY(ivf_off.alloc(sizeof(uint32_t) * (K + 1)));
-    CLB_TRY(ivf_pid.alloc(sizeof(uint32_t) * n_tot));
-    CLB_TRY(add_pid.alloc(sizeof(uint32_t) * n_new_emb));
-    CLB_TRY(add_pid_sorted.alloc(sizeof(uint32_t) * n_new_emb));
-    CLB_TRY(codes_sorted.alloc(sizeof(uint32_t) * n_new_emb));
-    CLB_HIP(hipMemsetAsync(hist.p, 0, sizeof(uint32_t) * (K + 1), st));
-    if (n_new_emb > 0)
-        hipLaunchKernelGGL(append_hist_pid_kernel, dim3(blocks), dim3(256), 0, st, codes_in.as<uint32_t>(),
-                           new_off_d.as<uint32_t>(), n_new_emb, (int)n_new, (uint32_t)d_old, hist.as<uint32_t>(),
-                           add_pid.as<uint32_t>());
-    CLB_TRY(exclusive_scan_u32(hist.as<uint32_t>(), add_off.as<uint32_t>(), (size_t)K, st));
-    int end_bit = 1;
-    while (((int64_t)1 << end_bit) < K) ++end_bit;
-    CLB_TRY(sort_pairs_u32(codes_in.as<uint32_t>(), codes_sorted.as<uint32_t>(), add_pid.as<uint32_t>(),
-                           add_pid_sorted.as<uint32_t>(), (size_t)n_new_emb, end_bit, st));
-    hipLaunchKernelGGL(append_offsets_kernel, dim3((unsigned)((K + 1 + 255) / 256)), dim3(256), 0, st, s->ivf_off.as<uint32_t>(),
-                       add_off.as<uint32_t>(), (int)(K + 1), ivf_off.as<uint32_t>());
-    if (n_tot > 0) {
-        const int64_t tiles = (n_tot + kMergeTile - 1) / kMergeTile;
-        hipLaunchKernelGGL(ivf_merge_kernel, dim3((unsigned)std::min<int64_t>(tiles, 8192)), dim3(256), 0, st,
-                           s->ivf_off.as<uint32_t>(), add_off.as<uint32_t>(), ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(),
-                           add_pid_sorted.as<uint32_t>(), (int)K, n_tot, ivf_pid.as<uint32_t>());
-    }
-    CLB_HIP(hipGetLastError());
-    std::vector<uint32_t> h_ivf_off((size_t)K + 1);
-    CLB_HIP(hipMemcpyAsync(h_ivf_off.data(), ivf_off.p, sizeof(uint32_t) * (K + 1), hipMemcpyDeviceToHost, st));
-    CLB_HIP(hipStreamSynchronize(st));
-    if ((int64_t)h_ivf_off[K] != n_tot) return fail(CLB_EHIP, "merged inverted lists hold %lld entries, expected %lld",
-                                                     (long long)h_ivf_off[K], (long long)n_tot);
-
-    // code | inv_norm words and bound constants: one streaming pass over the whole grown index -- inv_norm is quantised over
-    // the index's own range, which a new row may widen
-    IndexTables tables;
-    if (!s->generic) CLB_TRY(derive_index_tables(s, codes0.as<uint32_t>(), res.as<uint8_t>(), n_tot, &tables));
-    CLB_HIP(hipStreamSynchronize(st));
-    CLB_HIP(hipGetLastError());
-
-    // ---- nothing below can fail ----
-    swap_buf(s->codes0, codes0); swap_buf(s->residuals, res); swap_buf(s->doc_off, doc_off);
-    swap_buf(s->ivf_off, ivf_off); swap_buf(s->ivf_pid, ivf_pid); swap_buf(s->live, live);
-    s->n_docs = d_tot; s->n_emb = n_tot;
-    s->max_doclen = std::max(s->max_doclen, add.longest);
-    finish_index_change(s, tables, h_ivf_off);
-    return CLB_OK;
+    return commit_index_change(s, c);
 }
 
 int clb_searcher_append(clb_searcher* s, int64_t n_new, const int64_t* doclens, int64_t n_new_emb, const uint32_t* codes,
@@ -1453,104 +1631,18 @@ int clb_searcher_append_device(clb_searcher* s, int64_t n_new, const int64_t* do
     (void)hip_stream;     // the call waits for the whole device on entry, the work of that stream included
     return searcher_append_impl(s, n_new, doclens, n_new_emb, d_codes, d_residuals, true);
 }
-// clb_searcher_remove (include/colbert_hip.h), built like an append: the reduced codes0 / residuals / doc_off, the compacted
-// inverted lists and the approximate-pass tables of the reduced index stand beside the handle's arrays until the last device
-// work has been waited for; any return before the swaps leaves the handle untouched.
-static int searcher_remove_impl(clb_searcher* s, const int64_t* pids, int64_t n, int64_t* n_removed) {
+
+// clb_searcher_remove (include/colbert_hip.h): replace_passages without new content.  A pid may be named twice.
+int clb_searcher_remove(clb_searcher* s, const int64_t* pids, int64_t n, int64_t* n_removed) {
     if (n_removed) *n_removed = 0;
     if (!s) return fail(CLB_EARGUMENT, "null searcher");
     if (n < 0 || (n > 0 && !pids)) return fail(CLB_EARGUMENT, "pids is null or n < 0");
-    for (int64_t i = 0; i < n; ++i)
-        if (pids[i] <= s->pid_offset || pids[i] > s->pid_offset + s->n_docs)
-            return fail(CLB_EBOUNDS, "pid %lld (entry %lld) outside %lld..%lld", (long long)pids[i], (long long)i,
-                        (long long)(s->pid_offset + 1), (long long)(s->pid_offset + s->n_docs));
+    CLB_TRY(check_pid_range(s, pids, n));
     if (n == 0 || s->n_emb == 0) return CLB_OK;       // no pid named, or every named passage is empty already
-    const int64_t n_old = s->n_emb, n_docs = s->n_docs, K = s->K;
-    CLB_TRY(use_device(s->device));
-    CLB_HIP(hipDeviceSynchronize());      // searches of this handle
-    const hipStream_t st = s->stream;
-    const size_t rows = (size_t)(s->dim / 8 * s->nbits);
-
-    // the removed passages as a bitmap in a filter's layout, the lengths that stay, their offsets
-    DevBuf d_pids, gone, len, doc_off;
-    DevWord<int> err;
-    DevWord<RemoveCounts> counts;
-    CLB_TRY(upload(d_pids, pids, sizeof(int64_t) * n, st));
-    CLB_TRY(gone.alloc(sizeof(uint32_t) * (size_t)((n_docs + 31) / 32)));
-    CLB_TRY(len.alloc(sizeof(uint32_t) * (n_docs + 1)));
-    CLB_TRY(doc_off.alloc(sizeof(uint32_t) * (n_docs + 1)));
-    CLB_TRY(err.init(st));
-    CLB_TRY(counts.init(st));
-    CLB_HIP(hipMemsetAsync(gone.p, 0, gone.bytes, st));
-    hipLaunchKernelGGL(filter_mark_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_pids.as<int64_t>(), n,
-                       s->pid_offset, (int)n_docs, gone.as<uint32_t>(), err.ptr());
-    hipLaunchKernelGGL(remove_lengths_kernel, dim3((unsigned)((n_docs + 1 + 255) / 256)), dim3(256), 0, st,
-                       s->doc_off.as<uint32_t>(), gone.as<uint32_t>(), (int)n_docs, len.as<uint32_t>(), counts.ptr());
-    CLB_TRY(exclusive_scan_u32(len.as<uint32_t>(), doc_off.as<uint32_t>(), (size_t)n_docs, st));
-    uint32_t n_left = 0;
-    CLB_HIP(hipMemcpyAsync(&n_left, doc_off.as<uint32_t>() + n_docs, sizeof n_left, hipMemcpyDeviceToHost, st));
-    CLB_TRY(err.read(st));                // ... before d_pids and the host array go away
-    CLB_TRY(counts.read(st));
-    if (err.value) return fail(CLB_EBOUNDS, "a pid outside the searcher's passages");
-    if (counts.value.removed == 0) return CLB_OK;
-    const int64_t n_new = n_left;
-
-    // the rows that stay, in their old order, and the zero padding of one step
-    DevBuf codes0, res, live;
-    CLB_TRY(build_live_bitmap(st, doc_off.as<uint32_t>(), n_docs, &live));
-    CLB_TRY(alloc_padded_rows(st, n_new, rows, &codes0, &res));
-    if (n_new > 0) {
-        if (rows % 16 == 0) launch_remove_rows<uint4>(st, s, doc_off.as<uint32_t>(), n_new, rows, codes0.as<uint32_t>(), res.as<uint8_t>());
-        else if (rows % 4 == 0) launch_remove_rows<uint32_t>(st, s, doc_off.as<uint32_t>(), n_new, rows, codes0.as<uint32_t>(), res.as<uint8_t>());
-        else launch_remove_rows<uint8_t>(st, s, doc_off.as<uint32_t>(), n_new, rows, codes0.as<uint32_t>(), res.as<uint8_t>());
-    }
-
-    // the inverted lists: a flag per entry, its scan, one scatter of the entries that stay, the offsets from the same scan
-    DevBuf flag, pos, ivf_off, ivf_pid;
-    CLB_TRY(flag.alloc(sizeof(uint32_t) * (n_old + 1)));
-    CLB_TRY(pos.alloc(sizeof(uint32_t) * (n_old + 1)));
-    CLB_TRY(ivf_off.alloc(sizeof(uint32_t) * (K + 1)));
-    CLB_TRY(ivf_pid.alloc(sizeof(uint32_t) * n_new));
-    const dim3 entries((unsigned)((n_old + 1 + 255) / 256));
-    hipLaunchKernelGGL(ivf_keep_flags_kernel, entries, dim3(256), 0, st, s->ivf_pid.as<uint32_t>(), gone.as<uint32_t>(), n_old,
-                       flag.as<uint32_t>());
-    CLB_TRY(exclusive_scan_u32(flag.as<uint32_t>(), pos.as<uint32_t>(), (size_t)n_old, st));
-    flag.release();         // the scan has been waited for
-    hipLaunchKernelGGL(ivf_compact_kernel, entries, dim3(256), 0, st, s->ivf_pid.as<uint32_t>(), pos.as<uint32_t>(), n_old,
-                       ivf_pid.as<uint32_t>());
-    hipLaunchKernelGGL(ivf_compact_offsets_kernel, dim3((unsigned)((K + 1 + 255) / 256)), dim3(256), 0, st,
-                       s->ivf_off.as<uint32_t>(), pos.as<uint32_t>(), (int)(K + 1), ivf_off.as<uint32_t>());
-    CLB_HIP(hipGetLastError());
-    std::vector<uint32_t> h_ivf_off((size_t)K + 1);
-    CLB_HIP(hipMemcpyAsync(h_ivf_off.data(), ivf_off.p, sizeof(uint32_t) * (K + 1), hipMemcpyDeviceToHost, st));
-    CLB_HIP(hipStreamSynchronize(st));
-    if ((int64_t)h_ivf_off[K] != n_new) return fail(CLB_EHIP, "compacted inverted lists hold %lld entries, expected %lld",
-                                                    (long long)h_ivf_off[K], (long long)n_new);
-    pos.release();
-
-    // code | inv_norm words and bound constants of the reduced index: inv_norm is quantised over the index's own range, which
-    // a removed row may narrow
-    IndexTables tables;
-    if (!s->generic) CLB_TRY(derive_index_tables(s, codes0.as<uint32_t>(), res.as<uint8_t>(), n_new, &tables));
-    CLB_HIP(hipStreamSynchronize(st));
-    CLB_HIP(hipGetLastError());
-
-    // ---- nothing below can fail ----
-    swap_buf(s->codes0, codes0); swap_buf(s->residuals, res); swap_buf(s->doc_off, doc_off);
-    swap_buf(s->ivf_off, ivf_off); swap_buf(s->ivf_pid, ivf_pid); swap_buf(s->live, live);
-    s->n_emb = n_new;
-    s->max_doclen = counts.value.longest;
-    finish_index_change(s, tables, h_ivf_off);
-    if (n_removed) *n_removed = counts.value.removed;
-    return CLB_OK;
-}
-int clb_searcher_remove(clb_searcher* s, const int64_t* pids, int64_t n, int64_t* n_removed) {
-    return searcher_remove_impl(s, pids, n, n_removed);
+    return replace_passages(s, n, pids, nullptr, nullptr, nullptr, false, n_removed);
 }
 
-// clb_searcher_update / _device (include/colbert_hip.h), built like an append and a removal: the spliced codes0 / residuals /
-// doc_off, the merged inverted lists and the approximate-pass tables of the changed index stand beside the handle's arrays
-// until the last device work has been waited for; any return before the swaps leaves the handle untouched.
+// clb_searcher_update / _device (include/colbert_hip.h): replace_passages with one new content per named passage
 static int searcher_update_impl(clb_searcher* s, int64_t n, const int64_t* pids, const int64_t* doclens, int64_t n_new_emb,
                                 const uint32_t* codes, const uint8_t* residuals, bool on_device, int64_t* n_changed) {
     if (n_changed) *n_changed = 0;
@@ -1559,10 +1651,7 @@ static int searcher_update_impl(clb_searcher* s, int64_t n, const int64_t* pids,
     if ((n > 0 && (!pids || !doclens)) || (n_new_emb > 0 && (!codes || !residuals))) return fail(CLB_EARGUMENT, "null argument");
     Offsets add;            // the named passages among the new embeddings
     CLB_TRY(passage_offsets(doclens, n, n_new_emb, "replaced passage", &add));
-    for (int64_t i = 0; i < n; ++i)
-        if (pids[i] <= s->pid_offset || pids[i] > s->pid_offset + s->n_docs)
-            return fail(CLB_EBOUNDS, "pid %lld (entry %lld) outside %lld..%lld", (long long)pids[i], (long long)i,
-                        (long long)(s->pid_offset + 1), (long long)(s->pid_offset + s->n_docs));
+    CLB_TRY(check_pid_range(s, pids, n));
     {   // a pid named twice: which of its two contents is meant?
         std::vector<int64_t> sorted(pids, pids + n);
         std::sort(sorted.begin(), sorted.end());
@@ -1571,167 +1660,7 @@ static int searcher_update_impl(clb_searcher* s, int64_t n, const int64_t* pids,
             return fail(CLB_EARGUMENT, "pid %lld is named twice: an update takes one new content per passage", (long long)*twice);
     }
     if (n == 0) return CLB_OK;
-    const int64_t n_old = s->n_emb, n_docs = s->n_docs, K = s->K;
-    CLB_TRY(use_device(s->device));
-    CLB_HIP(hipDeviceSynchronize());      // searches of this handle and whatever wrote the caller's device arrays
-    const hipStream_t st = s->stream;
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    const size_t rows = (size_t)(s->dim / 8 * s->nbits);
-
-    // the new codes, 0-based and checked, in a buffer of the call's own; the replaced passages as a bitmap in a filter's
-    // layout and their place in the caller's list; the lengths of the changed index and their offsets
-    DevBuf codes_in, d_pids, stage_off, named, slot, len, doc_off;
-    DevWord<int> err;
-    DevWord<UpdateCounts> counts;
-    CLB_TRY(codes_in.alloc(sizeof(uint32_t) * n_new_emb));
-    CLB_TRY(err.init(st));
-    CLB_TRY(counts.init(st));
-    CLB_TRY(stage_codes(st, codes, kind, n_new_emb, K, codes_in.as<uint32_t>(), err.ptr()));
-    CLB_TRY(upload(d_pids, pids, sizeof(int64_t) * n, st));
-    CLB_TRY(upload(stage_off, add.off.data(), sizeof(uint32_t) * add.off.size(), st));
-    CLB_TRY(named.alloc(sizeof(uint32_t) * (size_t)((n_docs + 31) / 32)));
-    CLB_TRY(slot.alloc(sizeof(uint32_t) * n_docs));
-    CLB_TRY(len.alloc(sizeof(uint32_t) * (n_docs + 1)));
-    CLB_TRY(doc_off.alloc(sizeof(uint32_t) * (n_docs + 1)));
-    CLB_HIP(hipMemsetAsync(named.p, 0, named.bytes, st));
-    const dim3 per_pid((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(filter_mark_kernel<false>, per_pid, dim3(256), 0, st, d_pids.as<int64_t>(), n, s->pid_offset, (int)n_docs,
-                       named.as<uint32_t>(), err.ptr());
-    hipLaunchKernelGGL(update_slots_kernel, per_pid, dim3(256), 0, st, d_pids.as<int64_t>(), n, s->pid_offset, (int)n_docs,
-                       slot.as<uint32_t>());
-    hipLaunchKernelGGL(update_lengths_kernel, dim3((unsigned)((n_docs + 1 + 255) / 256)), dim3(256), 0, st,
-                       s->doc_off.as<uint32_t>(), named.as<uint32_t>(), slot.as<uint32_t>(), stage_off.as<uint32_t>(), (int)n_docs,
-                       len.as<uint32_t>(), counts.ptr());
-    CLB_TRY(err.read(st));                // ... before the host arrays go away
-    CLB_TRY(counts.read(st));
-    if (err.value & kErrCode) return bad_codes();
-    if (err.value) return fail(CLB_EBOUNDS, "a pid outside the searcher's passages");
-    const int64_t n_tot = n_old - (int64_t)counts.value.dropped + n_new_emb;
-    CLB_TRY(check_shard_limits(n_tot, n_docs));
-    if (counts.value.changed == 0) return CLB_OK;       // every named passage was empty and stays empty
-    CLB_TRY(exclusive_scan_u32(len.as<uint32_t>(), doc_off.as<uint32_t>(), (size_t)n_docs, st));
-
-    // the new rows where the splice reads them: in create's per-passage code order on the tuned path (over the new rows and
-    // their own offsets, as an append orders them), as given on the general path
-    DevBuf codes_staged, res_staged, res_in;
-    const uint32_t* codes_stage = codes_in.as<uint32_t>();
-    const uint8_t* res_stage = residuals;
-    if (n_new_emb > 0 && (!on_device || ((uintptr_t)residuals & 15))) {     // the kernels read 16-byte pieces
-        CLB_TRY(res_in.alloc(rows * n_new_emb));
-        CLB_HIP(hipMemcpyAsync(res_in.p, residuals, rows * n_new_emb, kind, st));
-        res_stage = res_in.as<uint8_t>();
-    }
-    if (n_new_emb > 0 && !s->generic) {
-        CLB_TRY(codes_staged.alloc(sizeof(uint32_t) * n_new_emb));
-        CLB_TRY(res_staged.alloc(rows * n_new_emb));
-        CLB_TRY(order_rows_by_code(st, codes_in.as<uint32_t>(), stage_off.as<uint32_t>(), n_new_emb, n, res_stage, rows,
-                                   codes_staged.as<uint32_t>(), res_staged.as<uint8_t>()));
-        res_in.release();       // order_rows_by_code has waited for the stream
-        codes_stage = codes_staged.as<uint32_t>();
-        res_stage = res_staged.as<uint8_t>();
-    }
-
-    // one splice of the rows, and the zero padding of one step
-    DevBuf codes0, res, live;
-    CLB_TRY(build_live_bitmap(st, doc_off.as<uint32_t>(), n_docs, &live));
-    CLB_TRY(alloc_padded_rows(st, n_tot, rows, &codes0, &res));
-    if (n_tot > 0) {
-        if (rows % 16 == 0)
-            launch_splice_rows<uint4>(st, s, doc_off.as<uint32_t>(), named.as<uint32_t>(), slot.as<uint32_t>(), stage_off.as<uint32_t>(),
-                                      n_tot, rows, codes_stage, res_stage, codes0.as<uint32_t>(), res.as<uint8_t>());
-        else if (rows % 4 == 0)
-            launch_splice_rows<uint32_t>(st, s, doc_off.as<uint32_t>(), named.as<uint32_t>(), slot.as<uint32_t>(), stage_off.as<uint32_t>(),
-                                         n_tot, rows, codes_stage, res_stage, codes0.as<uint32_t>(), res.as<uint8_t>());
-        else
-            launch_splice_rows<uint8_t>(st, s, doc_off.as<uint32_t>(), named.as<uint32_t>(), slot.as<uint32_t>(), stage_off.as<uint32_t>(),
-                                        n_tot, rows, codes_stage, res_stage, codes0.as<uint32_t>(), res.as<uint8_t>());
-    }
-
-    // the inverted lists.  Kept entries: a flag per old entry and its scan, as in a removal.  New entries: their local pids and
-    // the histogram of their codes, then two stable sorts -- by pid, then by code -- so that every list's new entries hold
-    // non-decreasing pids.  One pass over the lists puts both where a fresh build would.
-    DevBuf flag, pos, hist, add_off, ivf_off, ivf_pid, add_pid, add_pid2, add_code, add_code2;
-    CLB_TRY(flag.alloc(sizeof(uint32_t) * (n_old + 1)));
-    CLB_TRY(pos.alloc(sizeof(uint32_t) * (n_old + 1)));
-    CLB_TRY(hist.alloc(sizeof(uint32_t) * (K + 1)));
-    CLB_TRY(add_off.alloc(sizeof(uint32_t) * (K + 1)));
-    CLB_TRY(ivf_off.alloc(sizeof(uint32_t) * (K + 1)));
-    CLB_TRY(ivf_pid.alloc(sizeof(uint32_t) * n_tot));
-    CLB_TRY(add_pid.alloc(sizeof(uint32_t) * n_new_emb));
-    CLB_TRY(add_pid2.alloc(sizeof(uint32_t) * n_new_emb));
-    CLB_TRY(add_code.alloc(sizeof(uint32_t) * n_new_emb));
-    CLB_TRY(add_code2.alloc(sizeof(uint32_t) * n_new_emb));
-    hipLaunchKernelGGL(ivf_keep_flags_kernel, dim3((unsigned)((n_old + 1 + 255) / 256)), dim3(256), 0, st, s->ivf_pid.as<uint32_t>(),
-                       named.as<uint32_t>(), n_old, flag.as<uint32_t>());
-    CLB_TRY(exclusive_scan_u32(flag.as<uint32_t>(), pos.as<uint32_t>(), (size_t)n_old, st));
-    flag.release();         // the scan has been waited for
-    CLB_HIP(hipMemsetAsync(hist.p, 0, sizeof(uint32_t) * (K + 1), st));
-    if (n_new_emb > 0)
-        hipLaunchKernelGGL(update_hist_pid_kernel, dim3((unsigned)((n_new_emb + 255) / 256)), dim3(256), 0, st, codes_in.as<uint32_t>(),
-                           stage_off.as<uint32_t>(), d_pids.as<int64_t>(), s->pid_offset, n_new_emb, (int)n, hist.as<uint32_t>(),
-                           add_pid.as<uint32_t>());
-    CLB_TRY(exclusive_scan_u32(hist.as<uint32_t>(), add_off.as<uint32_t>(), (size_t)K, st));
-    int pid_bits = 1, code_bits = 1;
-    while (((int64_t)1 << pid_bits) < n_docs) ++pid_bits;
-    while (((int64_t)1 << code_bits) < K) ++code_bits;
-    CLB_TRY(sort_pairs_u32(add_pid.as<uint32_t>(), add_pid2.as<uint32_t>(), codes_in.as<uint32_t>(), add_code2.as<uint32_t>(),
-                           (size_t)n_new_emb, pid_bits, st));
-    CLB_TRY(sort_pairs_u32(add_code2.as<uint32_t>(), add_code.as<uint32_t>(), add_pid2.as<uint32_t>(), add_pid.as<uint32_t>(),
-                           (size_t)n_new_emb, code_bits, st));
-    const dim3 per_list((unsigned)((K + 1 + 255) / 256));
-    if (s->ivf_sorted) {
-        hipLaunchKernelGGL(ivf_splice_offsets_kernel, per_list, dim3(256), 0, st, s->ivf_off.as<uint32_t>(), pos.as<uint32_t>(),
-                           add_off.as<uint32_t>(), (int)(K + 1), ivf_off.as<uint32_t>());
-        const int64_t tiles = (n_old + kSpliceTile - 1) / kSpliceTile + (n_new_emb + kSpliceTile - 1) / kSpliceTile;
-        if (tiles > 0)
-            hipLaunchKernelGGL(ivf_splice_kernel, dim3((unsigned)std::min<int64_t>(tiles, 8192)), dim3(256), 0, st,
-                               s->ivf_off.as<uint32_t>(), s->ivf_pid.as<uint32_t>(), pos.as<uint32_t>(), n_old, add_off.as<uint32_t>(),
-                               add_code.as<uint32_t>(), add_pid.as<uint32_t>(), n_new_emb, (int)K, ivf_pid.as<uint32_t>());
-    } else {
-        // the caller's own list order: the kept entries in that order (a removal's compaction), the new ones behind them list
-        // by list (an append's merge); the lists stay unsorted
-        DevBuf kept_pid, kept_off;
-        const int64_t n_kept = n_tot - n_new_emb;
-        CLB_TRY(kept_pid.alloc(sizeof(uint32_t) * n_kept));
-        CLB_TRY(kept_off.alloc(sizeof(uint32_t) * (K + 1)));
-        hipLaunchKernelGGL(ivf_compact_kernel, dim3((unsigned)((n_old + 1 + 255) / 256)), dim3(256), 0, st, s->ivf_pid.as<uint32_t>(),
-                           pos.as<uint32_t>(), n_old, kept_pid.as<uint32_t>());
-        hipLaunchKernelGGL(ivf_compact_offsets_kernel, per_list, dim3(256), 0, st, s->ivf_off.as<uint32_t>(), pos.as<uint32_t>(),
-                           (int)(K + 1), kept_off.as<uint32_t>());
-        hipLaunchKernelGGL(append_offsets_kernel, per_list, dim3(256), 0, st, kept_off.as<uint32_t>(), add_off.as<uint32_t>(),
-                           (int)(K + 1), ivf_off.as<uint32_t>());
-        if (n_tot > 0) {
-            const int64_t tiles = (n_tot + kMergeTile - 1) / kMergeTile;
-            hipLaunchKernelGGL(ivf_merge_kernel, dim3((unsigned)std::min<int64_t>(tiles, 8192)), dim3(256), 0, st,
-                               kept_off.as<uint32_t>(), add_off.as<uint32_t>(), ivf_off.as<uint32_t>(), kept_pid.as<uint32_t>(),
-                               add_pid.as<uint32_t>(), (int)K, n_tot, ivf_pid.as<uint32_t>());
-        }
-        CLB_HIP(hipStreamSynchronize(st));      // kept_pid and kept_off go away here
-    }
-    CLB_HIP(hipGetLastError());
-    std::vector<uint32_t> h_ivf_off((size_t)K + 1);
-    CLB_HIP(hipMemcpyAsync(h_ivf_off.data(), ivf_off.p, sizeof(uint32_t) * (K + 1), hipMemcpyDeviceToHost, st));
-    CLB_HIP(hipStreamSynchronize(st));
-    if ((int64_t)h_ivf_off[K] != n_tot) return fail(CLB_EHIP, "spliced inverted lists hold %lld entries, expected %lld",
-                                                    (long long)h_ivf_off[K], (long long)n_tot);
-    pos.release();
-    codes_staged.release(); res_staged.release(); res_in.release();
-
-    // code | inv_norm words and bound constants of the changed index: inv_norm is quantised over the index's own range, which
-    // a new row may widen and a dropped row may narrow
-    IndexTables tables;
-    if (!s->generic) CLB_TRY(derive_index_tables(s, codes0.as<uint32_t>(), res.as<uint8_t>(), n_tot, &tables));
-    CLB_HIP(hipStreamSynchronize(st));
-    CLB_HIP(hipGetLastError());
-
-    // ---- nothing below can fail ----
-    swap_buf(s->codes0, codes0); swap_buf(s->residuals, res); swap_buf(s->doc_off, doc_off);
-    swap_buf(s->ivf_off, ivf_off); swap_buf(s->ivf_pid, ivf_pid); swap_buf(s->live, live);
-    s->n_emb = n_tot;
-    s->max_doclen = counts.value.longest;
-    finish_index_change(s, tables, h_ivf_off);
-    if (n_changed) *n_changed = counts.value.changed;
-    return CLB_OK;
+    return replace_passages(s, n, pids, &add, codes, residuals, on_device, n_changed);
 }
 int clb_searcher_update(clb_searcher* s, int64_t n, const int64_t* pids, const int64_t* doclens, int64_t n_new_emb,
                         const uint32_t* codes, const uint8_t* residuals, int64_t* n_changed) {
