@@ -123,6 +123,22 @@ def lib() -> C.CDLL:
         l.clb_search_shard_phase1_filtered_slot.restype = C.c_int
         l.clb_search_shard_phase1_filtered_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                                             C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
+        vp, i64_, ci = C.c_void_p, C.c_int64, C.c_int
+        l.clb_search_shard_phase1_grouped_slot.restype = ci
+        l.clb_search_shard_phase1_grouped_slot.argtypes = [vp, ci, vp, i64_, i64_, i64_, i64_, C.POINTER(vp), ci, vp, i64_, vp, vp, vp]
+        l.clb_search_shard_phase2_grouped_slot.restype = ci
+        l.clb_search_shard_phase2_grouped_slot.argtypes = [vp, ci, vp, i64_, i64_, i64_, i64_, vp, vp, i64_, vp, i64_, vp, vp, vp,
+                                                           vp, vp, vp]
+        l.clb_search_result_groups_slot.restype = ci
+        l.clb_search_result_groups_slot.argtypes = [vp, ci, vp, i64_, vp, i64_, i64_, vp, vp, vp]
+        l.clb_debug_group_tau_device.restype = ci
+        l.clb_debug_group_tau_device.argtypes = [vp, vp, i64_, i64_, i64_, vp, vp]
+        l.clb_merge_topk_grouped_device.restype = ci
+        l.clb_merge_topk_grouped_device.argtypes = [ci, vp, vp, vp, i64_, i64_, i64_, vp, vp, vp, vp, vp, vp]
+        l.clb_packed_grouped_bytes.restype = i64_
+        l.clb_packed_grouped_bytes.argtypes = [i64_, i64_]
+        l.clb_merge_topk_grouped_packed_device.restype = ci
+        l.clb_merge_topk_grouped_packed_device.argtypes = [ci, vp, i64_, i64_, i64_, vp, vp, vp, vp]
         _lib = l
     return _lib
 

@@ -3,6 +3,8 @@
 // non-decreasing in pid, so the passages of one group are consecutive pids -- and, the candidates of a query being an
 // ascending pid list (bitmap_emit_kernel), consecutive entries of every candidate list.  "Best passage per group" is
 // therefore a run reduction over that list: no sort, no hash, no atomics.
+// Across the shards of a group (second half of this file) a group may lie on both sides of a cut: the shards then name it by
+// one global index, the threshold and the merge count it once.
 #pragma once
 #include "search_kernels.hpp"
 
@@ -169,6 +171,273 @@ static __global__ __launch_bounds__(1024) void group_tau_kernel(const float* __r
     CLB_RADIX_SELECT_N(2)
 #undef CLB_SEL_FOR_EACH
     if (tid == 0) tau_g[b] = f32_from_order_key(s_prefix);
+}
+
+// ---- grouped search across a shard group -----------------------------------------------------------------------------
+// A shard's grouping is made from its slice of the group ids; group_base is the GLOBAL dense index of the group of the
+// shard's first passage, so the global index of local passage p is group_base + gid[p].  Shards are contiguous pid ranges
+// and groups are contiguous too: a group that lies on two shards is the LAST group of the one and the FIRST of the other
+// (a group over three shards: the only group of the middle one).  Among the records a shard publishes for one query --
+// distinct groups, one record each -- only the record with the lowest and the one with the highest group index can
+// therefore meet the same index in another shard's records: at most two "boundary records" per shard and query, found
+// by one wave per shard and resolved against each other in LDS.
+constexpr int kMaxGroupShards = 256;                // lists whose boundary records one work-group holds (2 each)
+
+// The lowest and the highest valid (>= 0) group index among g[0 .. k) and where they stand, by one wave; -1 when the list
+// has no valid record.  Every lane returns the same positions.
+__device__ __forceinline__ void wave_list_edges(const int64_t* __restrict__ g, int k, int lane, int* at_lo, int* at_hi) {
+    long long glo = 0, ghi = 0;
+    int ilo = -1, ihi = -1;
+    for (int i = lane; i < k; i += 64) {
+        const long long v = g[i];
+        if (v < 0) continue;
+        if (ilo < 0 || v < glo) { glo = v; ilo = i; }
+        if (ihi < 0 || v > ghi) { ghi = v; ihi = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const long long a = __shfl_xor(glo, o, 64), c = __shfl_xor(ghi, o, 64);
+        const int ai = __shfl_xor(ilo, o, 64), ci = __shfl_xor(ihi, o, 64);
+        if (ai >= 0 && (ilo < 0 || a < glo || (a == glo && ai < ilo))) { glo = a; ilo = ai; }
+        if (ci >= 0 && (ihi < 0 || c > ghi || (c == ghi && ci < ihi))) { ghi = c; ihi = ci; }
+    }
+    *at_lo = ilo;
+    *at_hi = ihi;
+}
+
+// S7g-c (phase 1 of the grouped two-phase search).  Of the query's groups -- glist[b][r] = the slot of the best approximate
+// score of run r, nglist[b] runs (group_collapse_kernel over all candidates) -- the k with the largest score: out_top[b][i]
+// the score, out_gid[b][i] the GLOBAL group index, in no particular order, padded with (-inf, -1).  Among scores equal to
+// the k-th largest any may be taken: they are equal values, and the threshold phase 2 derives from them is a lower bound
+// of the k-th best group whichever groups they name.  grid = B, block = 1024.
+static __global__ __launch_bounds__(1024) void group_local_top_kernel(const float* __restrict__ scores,
+                                                                     const uint32_t* __restrict__ cand,
+                                                                     const int* __restrict__ glist,
+                                                                     const int* __restrict__ nglist,
+                                                                     const uint32_t* __restrict__ gid, int64_t group_base,
+                                                                     int k, size_t cand_cap, float* __restrict__ out_top,
+                                                                     int64_t* __restrict__ out_gid) {
+    __shared__ __attribute__((aligned(16))) int hist[256];
+    __shared__ uint32_t s_prefix, s_kmin, s_kmax;
+    __shared__ int s_remaining, s_gt, s_eq;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = nglist[b];
+    const float* sc = scores + (size_t)b * cand_cap;
+    const uint32_t* cnd = cand + (size_t)b * cand_cap;
+    const int* lst = glist + (size_t)b * cand_cap;
+    float* o = out_top + (size_t)b * k;
+    int64_t* og = out_gid + (size_t)b * k;
+    if (n <= k) {                                      // uniform over the block: every group, then the padding
+        for (int i = tid; i < k; i += 1024) {
+            const int slot = i < n ? lst[i] : 0;
+            o[i] = i < n ? sc[slot] : kNegInf;
+            og[i] = i < n ? group_base + (int64_t)gid[cnd[slot]] : (int64_t)-1;
+        }
+        return;
+    }
+    const int chunk = (n + 1023) >> 10;
+#define CLB_SEL_FOR_EACH(...)                                                                   \
+    for (int c = 0; c < chunk; ++c) {                                                           \
+        const int i_ = c * 1024 + tid;                                                          \
+        const bool valid = i_ < n;                                                              \
+        const uint32_t key = valid ? f32_order_key(sc[lst[i_]]) : 0u;                           \
+        __VA_ARGS__                                                                             \
+    }
+    if (tid == 0) { s_prefix = 0u; s_remaining = k; s_gt = 0; s_eq = 0; }
+    __syncthreads();
+    CLB_RADIX_SELECT()
+#undef CLB_SEL_FOR_EACH
+    __syncthreads();
+    const uint32_t tau = s_prefix;
+    const int need_eq = s_remaining;                   // of the scores == tau, as many as the k places leave
+    const int n_gt = k - need_eq;                      // scores > tau
+    for (int i = tid; i < n; i += 1024) {
+        const int slot = lst[i];
+        const float v = sc[slot];
+        const uint32_t key = f32_order_key(v);
+        int pos = -1;
+        if (key > tau) {
+            pos = atomicAdd(&s_gt, 1);
+        } else if (key == tau) {
+            const int e = atomicAdd(&s_eq, 1);
+            pos = e < need_eq ? n_gt + e : -1;
+        }
+        if (pos >= 0 && pos < k) {
+            o[pos] = v;
+            og[pos] = group_base + (int64_t)gid[cnd[slot]];
+        }
+    }
+}
+
+// S7g-d (phase 2).  tau[b] = the k-th largest score over the DISTINCT group indices of the gathered records
+// all_top / all_gid [n_shards][B][k]: a repeated index counts once, with its largest score; -inf when fewer than k
+// distinct finite records exist.  Records with index -1 (padding), and the boundary records that lose to a record of the
+// same group, take part as -inf; the select over the n_shards * k keys is the radix-select core, run to the last bit.
+// n_shards <= kMaxGroupShards.  grid = B, block = 1024.
+static __global__ __launch_bounds__(1024) void group_global_tau_kernel(const float* __restrict__ all_top,
+                                                                      const int64_t* __restrict__ all_gid, int n_shards,
+                                                                      int B, int k, float* __restrict__ tau_glob) {
+    __shared__ __attribute__((aligned(16))) int hist[256];
+    __shared__ uint32_t s_prefix, s_kmin, s_kmax;
+    __shared__ int s_remaining;
+    __shared__ long long e_gid[2 * kMaxGroupShards];
+    __shared__ uint32_t e_key[2 * kMaxGroupShards];
+    __shared__ int e_at[2 * kMaxGroupShards];          // position in the query's n_shards * k records, -1: no such record
+    __shared__ int e_dead[2 * kMaxGroupShards];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = n_shards * k;
+    for (int l = wave; l < n_shards; l += 16) {
+        const size_t base = ((size_t)l * B + b) * k;
+        int lo, hi;
+        wave_list_edges(all_gid + base, k, lane, &lo, &hi);
+        if (lane == 0) {
+            if (hi == lo) hi = -1;                     // one valid record: one boundary record
+            e_at[2 * l] = lo < 0 ? -1 : l * k + lo;
+            e_at[2 * l + 1] = hi < 0 ? -1 : l * k + hi;
+            e_gid[2 * l] = lo < 0 ? -1 : all_gid[base + lo];
+            e_gid[2 * l + 1] = hi < 0 ? -1 : all_gid[base + hi];
+            e_key[2 * l] = lo < 0 ? 0u : f32_order_key(all_top[base + lo]);
+            e_key[2 * l + 1] = hi < 0 ? 0u : f32_order_key(all_top[base + hi]);
+        }
+    }
+    __syncthreads();
+    for (int t = tid; t < 2 * n_shards; t += 1024) {
+        int dead = 0;
+        if (e_at[t] >= 0)
+            for (int j = 0; j < 2 * n_shards; ++j)
+                dead |= j != t && e_at[j] >= 0 && e_gid[j] == e_gid[t] && (e_key[j] > e_key[t] || (e_key[j] == e_key[t] && j < t));
+        e_dead[t] = dead;
+    }
+    if (tid == 0) { s_prefix = 0u; s_remaining = k; }
+    __syncthreads();
+    const uint32_t neg_key = f32_order_key(kNegInf);
+    const int chunk = (n + 1023) >> 10;
+#define CLB_SEL_FOR_EACH(...)                                                                   \
+    for (int c = 0; c < chunk; ++c) {                                                           \
+        const int i_ = c * 1024 + tid;                                                          \
+        const bool valid = i_ < n;                                                              \
+        uint32_t key = 0u;                                                                      \
+        if (valid) {                                                                            \
+            const int l_ = i_ / k;                                                              \
+            const size_t at_ = ((size_t)l_ * B + b) * k + (i_ - l_ * k);                        \
+            const bool gone_ = all_gid[at_] < 0 || (e_at[2 * l_] == i_ && e_dead[2 * l_]) ||    \
+                               (e_at[2 * l_ + 1] == i_ && e_dead[2 * l_ + 1]);                  \
+            key = gone_ ? neg_key : f32_order_key(all_top[at_]);                                \
+        }                                                                                       \
+        __VA_ARGS__                                                                             \
+    }
+    CLB_RADIX_SELECT()
+#undef CLB_SEL_FOR_EACH
+    if (tid == 0) tau_glob[b] = f32_from_order_key(s_prefix);
+}
+
+// After a grouped search on a shard: out_gids[b][i] = the GLOBAL group index of result pid out_pids[b][i] (-1 for the
+// pid-0 padding), and edge_gids[b] = the global group index of the query's lowest-pid and highest-pid candidate (the slot's
+// candidate list is ascending in pid), (-1, -1) for a query without candidates: what the merge across the shards needs to
+// find a group that two shards both returned, and to count a group that straddles a cut once.
+// grid = ceil(max(B * k, B) / 256), block = 256.
+static __global__ __launch_bounds__(256) void group_result_kernel(const int64_t* __restrict__ out_pids, int B, int k,
+                                                                 int64_t pid_offset, const uint32_t* __restrict__ gid,
+                                                                 int64_t n_docs, int64_t group_base,
+                                                                 const uint32_t* __restrict__ cand, const int* __restrict__ ncand,
+                                                                 size_t cand_cap, int64_t* __restrict__ out_gids,
+                                                                 int64_t* __restrict__ edge_gids) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (int64_t)B * k) {
+        const int64_t local = out_pids[i] - pid_offset - 1;
+        out_gids[i] = (out_pids[i] > 0 && local >= 0 && local < n_docs) ? group_base + (int64_t)gid[local] : (int64_t)-1;
+    }
+    if (i < B) {
+        int n = ncand[i];
+        n = n < 0 ? 0 : ((size_t)n > cand_cap ? (int)cand_cap : n);
+        const uint32_t* cnd = cand + (size_t)i * cand_cap;
+        edge_gids[2 * i] = n > 0 ? group_base + (int64_t)gid[cnd[0]] : (int64_t)-1;
+        edge_gids[2 * i + 1] = n > 0 ? group_base + (int64_t)gid[cnd[n - 1]] : (int64_t)-1;
+    }
+}
+
+// The merge of the shards' grouped top-k lists: merge_topk_kernel with one record per GROUP.  in: [n_lists][B][k] records
+// (pid, score, global group index) sorted by (score desc, pid asc), padded with (0, -inf, -1), the groups of one list
+// distinct.  Of the records of one group only the first in that order survives; a survivor's place is its rank in the
+// plain merge minus the dead records ranked before it.  The dead are boundary records (at most 2 n_lists of them), so
+// every work-group finds them again -- one wave per list -- and keeps them in LDS.  Work-group (0, b) also writes
+// out_n_cand[b] = the sum of the lists' candidate-group counts minus the lists whose first edge group equals the last edge
+// group of the nearest list before it that has candidates: a group that straddles cuts is counted once, however many
+// shards it spans.  Strides as in merge_topk_kernel, in elements.  n_lists <= kMaxGroupShards.
+// grid = (ceil(n_lists * k / 256), B), block = 256; the output is filled with padding beforehand (fill_pad_kernel).
+static __global__ __launch_bounds__(256) void merge_topk_grouped_kernel(
+    const int64_t* __restrict__ pids, const float* __restrict__ scores, const int64_t* __restrict__ gids, int k, int n_lists,
+    int B, size_t pid_stride, size_t score_stride, size_t gid_stride, const int64_t* __restrict__ n_cand_lists,
+    size_t n_cand_stride, const int64_t* __restrict__ edge_gids, size_t edge_stride, int64_t* __restrict__ out_pids,
+    float* __restrict__ out_scores, int64_t* __restrict__ out_n_cand) {
+    __shared__ long long e_gid[2 * kMaxGroupShards], e_pid[2 * kMaxGroupShards];
+    __shared__ float e_sc[2 * kMaxGroupShards];
+    __shared__ int e_at[2 * kMaxGroupShards], e_dead[2 * kMaxGroupShards];
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int l = wave; l < n_lists; l += 4) {
+        int lo, hi;
+        wave_list_edges(gids + (size_t)l * gid_stride + (size_t)b * k, k, lane, &lo, &hi);
+        if (lane == 0) {
+            if (hi == lo) hi = -1;
+            const int at[2] = {lo, hi};
+            for (int h = 0; h < 2; ++h) {
+                const int a = at[h];
+                const int64_t p = a < 0 ? 0 : pids[(size_t)l * pid_stride + (size_t)b * k + a];
+                e_at[2 * l + h] = (a < 0 || p <= 0) ? -1 : l * k + a;
+                e_pid[2 * l + h] = p;
+                e_gid[2 * l + h] = a < 0 ? -1 : gids[(size_t)l * gid_stride + (size_t)b * k + a];
+                e_sc[2 * l + h] = a < 0 ? kNegInf : scores[(size_t)l * score_stride + (size_t)b * k + a];
+            }
+        }
+    }
+    __syncthreads();
+    for (int t = tid; t < 2 * n_lists; t += 256) {
+        int dead = 0;
+        if (e_at[t] >= 0)
+            for (int j = 0; j < 2 * n_lists; ++j)
+                dead |= j != t && e_at[j] >= 0 && e_gid[j] == e_gid[t] && rec_before(e_sc[j], e_pid[j], e_sc[t], e_pid[t]);
+        e_dead[t] = dead;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && tid == 0) {
+        int64_t total = 0, prev_last = -1;
+        for (int l = 0; l < n_lists; ++l) {
+            total += n_cand_lists[(size_t)l * n_cand_stride + b];
+            const int64_t first = edge_gids[(size_t)l * edge_stride + 2 * (size_t)b];
+            const int64_t last = edge_gids[(size_t)l * edge_stride + 2 * (size_t)b + 1];
+            if (first < 0) continue;                   // a list without candidates
+            if (first == prev_last) total -= 1;
+            prev_last = last;
+        }
+        out_n_cand[b] = total;
+    }
+    const int idx = blockIdx.x * blockDim.x + tid;
+    if (idx >= n_lists * k) return;
+    const int l = idx / k, i = idx % k;
+    const int64_t p = pids[(size_t)l * pid_stride + (size_t)b * k + i];
+    const float s = scores[(size_t)l * score_stride + (size_t)b * k + i];
+    if (p <= 0) return;  // padding
+    if ((e_at[2 * l] == idx && e_dead[2 * l]) || (e_at[2 * l + 1] == idx && e_dead[2 * l + 1])) return;
+    int rank = i;
+    for (int l2 = 0; l2 < n_lists; ++l2) {
+        if (l2 == l) continue;
+        const int64_t* pl = pids + (size_t)l2 * pid_stride + (size_t)b * k;
+        const float* sl = scores + (size_t)l2 * score_stride + (size_t)b * k;
+        int lo = 0, hi = k;  // number of records of list l2 that come before (s, p)
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            const int64_t p2 = pl[mid];
+            const float s2 = sl[mid];
+            if (p2 > 0 && rec_before(s2, p2, s, p)) lo = mid + 1; else hi = mid;
+        }
+        rank += lo;
+    }
+    for (int j = 0; j < 2 * n_lists; ++j)
+        rank -= (e_at[j] >= 0 && e_dead[j] && rec_before(e_sc[j], (int64_t)e_pid[j], s, p)) ? 1 : 0;
+    if (rank < k) {
+        out_pids[(size_t)b * k + rank] = p;
+        out_scores[(size_t)b * k + rank] = s;
+    }
 }
 
 // ---- load time: the dense group index of every passage from the caller's ids -----------------------------------------

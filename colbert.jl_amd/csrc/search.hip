@@ -92,7 +92,12 @@ struct Workspace {
     size_t ivf_cap = 0;         // cand_cap before filt_cap was taken into account: the most candidates the IVF lists can give
     // two-phase sharded search: what clb_search_shard_phase1 left behind (phase 2 must continue exactly that batch)
     struct { bool valid = false; const float* dQ = nullptr; int64_t T = 0, B = 0, nprobe = 0, k = 0; void* stream = nullptr;
-             size_t filt_now = 0; } pending;      // filt_now: Batch::filt_now of phase 1 -- phase 2 selects over the same candidates
+             size_t filt_now = 0; const clb_grouping* grp = nullptr; int64_t group_base = 0; } pending;
+    // filt_now: Batch::filt_now of phase 1 -- phase 2 selects over the same candidates; grp / group_base: the grouping operands of
+    // a grouped phase 1 (clb_search_shard_phase1_grouped_slot) -- phase 2 must be the grouped call with the same ones
+    // single-exchange grouped sharded search: the last whole search on this slot was a grouped one of B <= 64 queries (one
+    // sub-batch, so its candidate lists are still here) -- clb_search_result_groups_slot reads the edge groups from them
+    struct { bool valid = false; int64_t B = 0, k = 0, generation = 0; const clb_grouping* grp = nullptr; void* stream = nullptr; } grouped_done;
     DevBuf Qdev, cells, cells_q, partial, sel, bitmap, blocksum, ncand, cand, cand_hdr, scores, list, nlist, thresh,
         outp, outs, flags, stats, redo, rowmask, eps_pair, tokmax, tau_glob, wsel, bounds, tscale, rangep, cells8;
     // grouped search (group_kernels.hpp), sized once a call has passed a grouping: the best slot of every group among all
@@ -169,6 +174,11 @@ struct Batch {
     bool stats_keep = false;    // the 2nd, 3rd ... sub-batch of one call: the work counters accumulate over the call
     int phase = 0, n_shards = 0;    // two-phase sharded search (run_search)
     float* d_local_top = nullptr; const float* d_all_top = nullptr;
+    // ... with a grouping (grp): the global index of the shard's first group, the group indices that travel with the scores
+    // between the phases, and what the grouped merge needs of phase 2's result (group_result_kernel)
+    int64_t group_base = 0;
+    int64_t* d_local_gid = nullptr; const int64_t* d_all_gid = nullptr;
+    int64_t* d_out_gids = nullptr; int64_t* d_edge_gids = nullptr;
 };
 Batch make_batch(const float* dQ, int64_t B, int64_t T, int64_t nprobe, int64_t k) {
     Batch q;
@@ -615,6 +625,15 @@ void launch_collapse(Workspace& w, hipStream_t st, const Batch& q, int b0, int n
                        w.cand_cap, out_list + (size_t)b0 * w.cand_cap, out_n + b0);
 }
 
+// the global group index of every result pid and the edge groups of every query's candidate list (group_result_kernel)
+void launch_result_groups(const clb_searcher* s, Workspace& w, hipStream_t st, const clb_grouping* g, int64_t group_base,
+                          const int64_t* d_pids, int B, int k, int64_t* d_out_gids, int64_t* d_edge_gids) {
+    const int64_t n = std::max<int64_t>((int64_t)B * k, B);
+    hipLaunchKernelGGL(group_result_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_pids, B, k, s->pid_offset,
+                       g->gid.as<uint32_t>(), s->n_docs, group_base, w.cand.as<uint32_t>(), w.ncand.as<int>(), w.cand_cap,
+                       d_out_gids, d_edge_gids);
+}
+
 // S7 for queries b0 .. b0 + n - 1: the single-work-group select + sort of topk_kernel, one work-group per query, or for
 // k above it a full stable sort per query.  list / nlist: the two-pass mode's re-scored passages ([B][cand_cap] / [B]) or
 // nullptr; ranked: topk_rank_kernel has already written the queries with short lists
@@ -775,6 +794,9 @@ int launch_select(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q,
 // phase 1 = candidate generation, pass 1, local selection, and the shard's k largest approximate scores per query
 // to `d_local_top`; phase 2 = global tau from the gathered scores `d_all_top` ([n_shards][B][k]), selection at that
 // tau, pass 2, top-k.  Phase 2 continues on the workspace phase 1 left behind.
+// With a grouping (q.grp) the phases exchange GROUPS: phase 1 publishes the best approximate score and the global index of the
+// shard's k best groups (d_local_top / d_local_gid), phase 2 cuts at the k-th best DISTINCT group of the gathered records and
+// adds what the grouped merge needs to its result (d_out_gids / d_edge_gids).
 int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
     const float* dQ = q.dQ;
     const int B = q.B, T = q.T, k = q.k, phase = q.phase;
@@ -784,7 +806,11 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
     s->prof.chain = nullptr;           // the first timed kernel of a call records its own start
     if (phase == 2) {
         CLB_TRY(w.tau_glob.ensure(sizeof(float) * B));
-        hipLaunchKernelGGL(global_tau_kernel, dim3(B), dim3(1024), 0, st, q.d_all_top, q.n_shards, B, k, w.tau_glob.as<float>());
+        if (q.grp)      // the k-th best GROUP over the shards: a group that straddles a cut counts once
+            hipLaunchKernelGGL(group_global_tau_kernel, dim3(B), dim3(1024), 0, st, q.d_all_top, q.d_all_gid, q.n_shards, B, k,
+                               w.tau_glob.as<float>());
+        else
+            hipLaunchKernelGGL(global_tau_kernel, dim3(B), dim3(1024), 0, st, q.d_all_top, q.n_shards, B, k, w.tau_glob.as<float>());
         Timed t(s, KID_SELECT, st);
         CLB_TRY(launch_select(s, w, st, q, (const float*)w.tau_glob.as<float>()));
     } else {
@@ -812,6 +838,16 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
             }
             {
                 Timed t(s, KID_SELECT, st);
+                if (q.grp && phase == 1) {
+                    // grouped phase 1: the shard's k best groups by approximate score, with their global indices; the
+                    // selection waits for the threshold of phase 2
+                    launch_collapse(w, st, q, 0, B, nullptr, nullptr, w.grp_list.as<int>(), w.grp_n.as<int>());
+                    hipLaunchKernelGGL(group_local_top_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(),
+                                       w.cand.as<uint32_t>(), w.grp_list.as<int>(), w.grp_n.as<int>(), q.grp->gid.as<uint32_t>(),
+                                       q.group_base, k, w.cand_cap, q.d_local_top, q.d_local_gid);
+                    CLB_HIP(hipGetLastError());
+                    return CLB_OK;
+                }
                 if (q.grp) {
                     // grouped: the cut is at the k-th best GROUP by approximate score -- the best
                     // approximate score of every group, their k-th largest, and the unchanged selection at that tau
@@ -891,6 +927,7 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
         collapse_exact();
         CLB_TRY(launch_topk(s, w, st, q, 0, B, tlist, tnlist, 0));
     }
+    if (q.grp && q.d_out_gids) launch_result_groups(s, w, st, q.grp, q.group_base, q.d_out_pids, B, k, q.d_out_gids, q.d_edge_gids);
     if (s->prof.counters) {
         hipLaunchKernelGGL(batch_stats_kernel, dim3(32, B), dim3(256), 0, st, w.cand.as<uint32_t>(),
                            w.ncand.as<int>(), list, nlist, s->doc_off.as<uint32_t>(), w.cand_cap,
@@ -961,6 +998,7 @@ int for_sub_batches(clb_searcher* s, Workspace& w, int64_t T, int64_t B, int64_t
     CLB_TRY(check_filters(s, filters, B, scope, &filt_count));
     CLB_TRY(check_grouping(s, grp));
     w.pending.valid = false;
+    w.grouped_done.valid = false;
     for (int64_t b0 = 0; b0 < B; b0 += kSubBatch) {
         Batch q = make_batch(nullptr, std::min<int64_t>(kSubBatch, B - b0), T, nprobe, k);
         CLB_TRY(ensure_workspace(s, w, q.B, T, nprobe, k, filt_count, grp != nullptr));
@@ -1777,13 +1815,18 @@ static int search_batch_device_slot_impl(clb_searcher* s, int slot, const float*
     Workspace* w = nullptr;
     CLB_TRY(slot_workspace(s, slot, &w));
     hipStream_t st = (hipStream_t)hip_stream;   // NULL = the HIP null stream, as for any HIP API
-    return for_sub_batches(s, *w, T, B, nprobe, k, filters, scope, grp, [&](int64_t b0, Batch& q) -> int {
+    CLB_TRY(for_sub_batches(s, *w, T, B, nprobe, k, filters, scope, grp, [&](int64_t b0, Batch& q) -> int {
         q.dQ = d_Q + (size_t)b0 * T * s->dim;
         q.d_out_pids = d_out_pids + (size_t)b0 * k;
         q.d_out_scores = d_out_scores + (size_t)b0 * k;
         q.d_n_cand = d_n_cand ? d_n_cand + b0 : nullptr;
         return run_search(s, *w, st, q);
-    });
+    }));
+    if (grp && B <= kSubBatch) {
+        auto& d = w->grouped_done;
+        d.valid = true; d.B = B; d.k = k; d.generation = s->generation; d.grp = grp; d.stream = hip_stream;
+    }
+    return CLB_OK;
 }
 
 int clb_search_batch_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
@@ -1818,13 +1861,16 @@ int clb_search_shard_phase1_slot(clb_searcher* s, int slot, const float* d_Q, in
                                                  hip_stream);
 }
 
-int clb_search_shard_phase1_filtered_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                          int64_t k, const clb_filter* const* filters, int scope, float* d_local_top,
-                                          void* hip_stream) {
+static int shard_phase1_impl(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                            const clb_filter* const* filters, int scope, const clb_grouping* grp, int64_t group_base,
+                            float* d_local_top, int64_t* d_local_gid, void* hip_stream) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     if (!d_local_top) return fail(CLB_EARGUMENT, "d_local_top is null");
+    if (grp && !d_local_gid) return fail(CLB_EARGUMENT, "d_local_gid is null");
+    if (grp && group_base < 0) return fail(CLB_EARGUMENT, "group_base must be >= 0, got %lld", (long long)group_base);
     size_t filt_count = 0;
     CLB_TRY(check_filters(s, filters, B, scope, &filt_count));
+    CLB_TRY(check_grouping(s, grp));
     bool filtered = false;
     for (int64_t b = 0; filters && b < B; ++b) filtered |= filters[b] != nullptr;
     // the whole batch stays on the slot for phase 2, and the filter handles of a launch travel in one argument block
@@ -1834,15 +1880,32 @@ int clb_search_shard_phase1_filtered_slot(clb_searcher* s, int slot, const float
     Workspace* wp = nullptr;
     CLB_TRY(slot_workspace(s, slot, &wp));
     Workspace& w = *wp;
-    CLB_TRY(ensure_workspace(s, w, B, T, nprobe, k, filt_count));
+    CLB_TRY(ensure_workspace(s, w, B, T, nprobe, k, filt_count, grp != nullptr));
+    if (grp) CLB_TRY(w.tau_glob.ensure(sizeof(float) * B));      // phase 2 then allocates nothing
     w.pending.valid = false;
+    w.grouped_done.valid = false;
     Batch q = make_batch(d_Q, B, T, nprobe, k);
     set_batch_filters(q, filters, 0, scope, filt_count);
     q.phase = 1; q.d_local_top = d_local_top;
+    q.grp = grp; q.group_base = group_base; q.d_local_gid = d_local_gid;
     CLB_TRY(run_search(s, w, (hipStream_t)hip_stream, q));
     w.pending.valid = true; w.pending.dQ = d_Q; w.pending.T = T; w.pending.B = B; w.pending.nprobe = nprobe;
     w.pending.k = k; w.pending.stream = hip_stream; w.pending.filt_now = q.filt_now;
+    w.pending.grp = grp; w.pending.group_base = group_base;
     return CLB_OK;
+}
+
+int clb_search_shard_phase1_filtered_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                          int64_t k, const clb_filter* const* filters, int scope, float* d_local_top,
+                                          void* hip_stream) {
+    return shard_phase1_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, nullptr, 0, d_local_top, nullptr, hip_stream);
+}
+
+int clb_search_shard_phase1_grouped_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
+                                         int64_t group_base, float* d_local_top, int64_t* d_local_gid, void* hip_stream) {
+    return shard_phase1_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, grouping, group_base, d_local_top, d_local_gid,
+                             hip_stream);
 }
 
 int clb_search_shard_phase2(clb_searcher* s, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
@@ -1852,16 +1915,26 @@ int clb_search_shard_phase2(clb_searcher* s, const float* d_Q, int64_t T, int64_
                                         hip_stream);
 }
 
-int clb_search_shard_phase2_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                 int64_t k, const float* d_all_top, int64_t n_shards, int64_t* d_out_pids,
-                                 float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
+static int shard_phase2_impl(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                            const float* d_all_top, const int64_t* d_all_gid, int64_t n_shards, const clb_grouping* grp,
+                            int64_t group_base, int64_t* d_out_pids, float* d_out_scores, int64_t* d_out_gids, int64_t* d_n_cand,
+                            int64_t* d_edge_gids, void* hip_stream) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     if (!d_all_top || n_shards < 1) return fail(CLB_EARGUMENT, "d_all_top is null or n_shards < 1");
+    if (grp) {
+        if (!d_all_gid) return fail(CLB_EARGUMENT, "d_all_gid is null");
+        if (!d_out_pids || !d_out_scores || !d_out_gids || !d_n_cand || !d_edge_gids)
+            return fail(CLB_EARGUMENT, "an output of the grouped phase 2 is null (d_out_pids, d_out_scores, d_out_gids, d_n_cand, d_edge_gids)");
+        CLB_TRY(check_grouping(s, grp));
+        if (n_shards > kMaxGroupShards)
+            return fail(CLB_EUNSUPPORTED, "the grouped phase 2 takes at most %d shards, got %lld", kMaxGroupShards, (long long)n_shards);
+    }
     Workspace* wp = nullptr;
     CLB_TRY(slot_workspace(s, slot, &wp));
     Workspace& w = *wp;
     const auto& pd = w.pending;
-    if (!pd.valid || pd.dQ != d_Q || pd.T != T || pd.B != B || pd.nprobe != nprobe || pd.k != k || pd.stream != hip_stream)
+    if (!pd.valid || pd.dQ != d_Q || pd.T != T || pd.B != B || pd.nprobe != nprobe || pd.k != k || pd.stream != hip_stream ||
+        pd.grp != grp || (grp && pd.group_base != group_base))
         return fail(CLB_EARGUMENT, "clb_search_shard_phase2 without a matching clb_search_shard_phase1 "
                                    "on this workspace slot (same queries, T, B, nprobe, k and stream, and no other search on the slot in between)");
     // every shard must cut at tau_global - 2 eps with ONE eps (the largest): a shard still on its own bound constants
@@ -1877,7 +1950,45 @@ int clb_search_shard_phase2_slot(clb_searcher* s, int slot, const float* d_Q, in
     q.filt_now = pd.filt_now;       // ... but the selection kernels are chosen by the same candidate capacity
     q.d_out_pids = d_out_pids; q.d_out_scores = d_out_scores; q.d_n_cand = d_n_cand;
     q.phase = 2; q.d_all_top = d_all_top; q.n_shards = (int)n_shards;
+    q.grp = grp; q.group_base = group_base; q.d_all_gid = d_all_gid; q.d_out_gids = d_out_gids; q.d_edge_gids = d_edge_gids;
     return run_search(s, w, (hipStream_t)hip_stream, q);
+}
+
+int clb_search_shard_phase2_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                 int64_t k, const float* d_all_top, int64_t n_shards, int64_t* d_out_pids,
+                                 float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
+    return shard_phase2_impl(s, slot, d_Q, T, B, nprobe, k, d_all_top, nullptr, n_shards, nullptr, 0, d_out_pids, d_out_scores,
+                             nullptr, d_n_cand, nullptr, hip_stream);
+}
+
+int clb_search_shard_phase2_grouped_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const float* d_all_top, const int64_t* d_all_gid, int64_t n_shards,
+                                         const clb_grouping* grouping, int64_t group_base, int64_t* d_out_pids,
+                                         float* d_out_scores, int64_t* d_out_gids, int64_t* d_n_cand, int64_t* d_edge_gids,
+                                         void* hip_stream) {
+    if (!grouping) return fail(CLB_EARGUMENT, "grouping is null (without one: clb_search_shard_phase2_slot)");
+    return shard_phase2_impl(s, slot, d_Q, T, B, nprobe, k, d_all_top, d_all_gid, n_shards, grouping, group_base, d_out_pids,
+                             d_out_scores, d_out_gids, d_n_cand, d_edge_gids, hip_stream);
+}
+
+int clb_search_result_groups_slot(clb_searcher* s, int slot, const clb_grouping* grouping, int64_t group_base,
+                                  const int64_t* d_pids, int64_t B, int64_t k, int64_t* d_out_gids, int64_t* d_edge_gids,
+                                  void* hip_stream) {
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    if (!grouping) return fail(CLB_EARGUMENT, "grouping is null");
+    if (!d_pids || !d_out_gids || !d_edge_gids) return fail(CLB_EARGUMENT, "d_pids, d_out_gids or d_edge_gids is null");
+    if (B < 1 || k < 1 || group_base < 0) return fail(CLB_EARGUMENT, "B and k must be >= 1 and group_base >= 0");
+    CLB_TRY(check_grouping(s, grouping));
+    Workspace* wp = nullptr;
+    CLB_TRY(slot_workspace(s, slot, &wp));
+    const auto& d = wp->grouped_done;
+    if (!d.valid || d.B != B || d.k != k || d.grp != grouping || d.stream != hip_stream || d.generation != s->generation)
+        return fail(CLB_EARGUMENT, "clb_search_result_groups_slot without a matching clb_search_batch_grouped_device_slot on this "
+                                   "workspace slot (same grouping, B <= %lld, k and stream, and nothing else on the slot in between)",
+                    (long long)kSubBatch);
+    launch_result_groups(s, *wp, (hipStream_t)hip_stream, grouping, group_base, d_pids, (int)B, (int)k, d_out_gids, d_edge_gids);
+    CLB_HIP(hipGetLastError());
+    return CLB_OK;
 }
 
 static int search_batch_impl(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
@@ -2129,6 +2240,66 @@ int clb_merge_topk_device(int device, const int64_t* d_pids, const float* d_scor
 }
 
 int64_t clb_packed_topk_bytes(int64_t k, int64_t B) { return (B * k * 12 + 7) / 8 * 8; }
+
+static int merge_topk_grouped_launch(int device, const int64_t* d_pids, const float* d_scores, const int64_t* d_gids, int64_t k,
+                                     int64_t n_lists, int64_t B, size_t pid_stride, size_t score_stride, size_t gid_stride,
+                                     const int64_t* d_n_cand_lists, size_t n_cand_stride, const int64_t* d_edge_gids,
+                                     size_t edge_stride, int64_t* d_out_pids, float* d_out_scores, int64_t* d_out_n_cand,
+                                     void* hip_stream) {
+    if (k < 1 || n_lists < 1 || B < 1) return fail(CLB_EARGUMENT, "k, n_lists and B must be >= 1");
+    if (!d_pids || !d_scores || !d_gids || !d_n_cand_lists || !d_edge_gids)
+        return fail(CLB_EARGUMENT, "an input of the grouped merge is null");
+    if (!d_out_pids || !d_out_scores || !d_out_n_cand) return fail(CLB_EARGUMENT, "an output of the grouped merge is null");
+    if (n_lists > kMaxGroupShards)
+        return fail(CLB_EUNSUPPORTED, "the grouped merge takes at most %d lists, got %lld", kMaxGroupShards, (long long)n_lists);
+    if (n_lists * k > INT32_MAX) return fail(CLB_EUNSUPPORTED, "n_lists * k exceeds 2^31 - 1");
+    CLB_TRY(use_device(device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    hipLaunchKernelGGL(fill_pad_kernel, dim3((unsigned)((B * k + 255) / 256)), dim3(256), 0, st, d_out_pids, d_out_scores, B * k);
+    hipLaunchKernelGGL(merge_topk_grouped_kernel, dim3((unsigned)((n_lists * k + 255) / 256), (unsigned)B), dim3(256), 0, st,
+                       d_pids, d_scores, d_gids, (int)k, (int)n_lists, (int)B, pid_stride, score_stride, gid_stride,
+                       d_n_cand_lists, n_cand_stride, d_edge_gids, edge_stride, d_out_pids, d_out_scores, d_out_n_cand);
+    CLB_HIP(hipGetLastError());
+    return CLB_OK;
+}
+
+int clb_merge_topk_grouped_device(int device, const int64_t* d_pids, const float* d_scores, const int64_t* d_gids, int64_t k,
+                                  int64_t n_lists, int64_t B, const int64_t* d_n_cand_lists, const int64_t* d_edge_gids,
+                                  int64_t* d_out_pids, float* d_out_scores, int64_t* d_out_n_cand, void* hip_stream) {
+    return merge_topk_grouped_launch(device, d_pids, d_scores, d_gids, k, n_lists, B, (size_t)(B * k), (size_t)(B * k),
+                                     (size_t)(B * k), d_n_cand_lists, (size_t)B, d_edge_gids, (size_t)(2 * B), d_out_pids,
+                                     d_out_scores, d_out_n_cand, hip_stream);
+}
+
+int64_t clb_packed_grouped_bytes(int64_t k, int64_t B) { return clb_packed_topk_bytes(k, B) + 8 * B * k + 8 * B + 16 * B; }
+
+int clb_merge_topk_grouped_packed_device(int device, const void* d_packed, int64_t k, int64_t n_lists, int64_t B,
+                                         int64_t* d_out_pids, float* d_out_scores, int64_t* d_out_n_cand, void* hip_stream) {
+    if (k < 1 || B < 1) return fail(CLB_EARGUMENT, "k, n_lists and B must be >= 1");
+    if (!d_packed) return fail(CLB_EARGUMENT, "d_packed is null");
+    const size_t block = (size_t)clb_packed_grouped_bytes(k, B);       // a multiple of 8
+    const size_t at_gids = (size_t)clb_packed_topk_bytes(k, B), at_n = at_gids + (size_t)B * k * 8, at_edges = at_n + (size_t)B * 8;
+    const char* base = static_cast<const char*>(d_packed);
+    return merge_topk_grouped_launch(device, reinterpret_cast<const int64_t*>(base),
+                                     reinterpret_cast<const float*>(base + (size_t)B * k * 8),
+                                     reinterpret_cast<const int64_t*>(base + at_gids), k, n_lists, B, block / 8, block / 4, block / 8,
+                                     reinterpret_cast<const int64_t*>(base + at_n), block / 8,
+                                     reinterpret_cast<const int64_t*>(base + at_edges), block / 8, d_out_pids, d_out_scores,
+                                     d_out_n_cand, hip_stream);
+}
+
+int clb_debug_group_tau_device(const float* d_all_top, const int64_t* d_all_gid, int64_t n_shards, int64_t B, int64_t k,
+                               float* d_tau, void* hip_stream) {
+    if (!d_all_top || !d_all_gid || !d_tau) return fail(CLB_EARGUMENT, "d_all_top, d_all_gid or d_tau is null");
+    if (n_shards < 1 || B < 1 || k < 1) return fail(CLB_EARGUMENT, "n_shards, B and k must be >= 1");
+    if (n_shards > kMaxGroupShards)
+        return fail(CLB_EUNSUPPORTED, "at most %d shards, got %lld", kMaxGroupShards, (long long)n_shards);
+    if (n_shards * k > INT32_MAX) return fail(CLB_EUNSUPPORTED, "n_shards * k exceeds 2^31 - 1");
+    hipLaunchKernelGGL(group_global_tau_kernel, dim3((unsigned)B), dim3(1024), 0, (hipStream_t)hip_stream, d_all_top, d_all_gid,
+                       (int)n_shards, (int)B, (int)k, d_tau);
+    CLB_HIP(hipGetLastError());
+    return CLB_OK;
+}
 
 int clb_merge_topk_packed_device(int device, const void* d_packed, int64_t k, int64_t n_lists, int64_t B,
                                  int64_t* d_out_pids, float* d_out_scores, void* hip_stream) {

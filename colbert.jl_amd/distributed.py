@@ -102,6 +102,28 @@ def all_gather_packed(packed, group=None):
     return out.view(world, packed.numel())
 
 
+def packed_grouped_bytes(k: int, B: int) -> int:
+    """Bytes of one shard's packed GROUPED result block (clb_packed_grouped_bytes): the `packed_topk_bytes` block of pids and
+    scores, then [B*k int64 global group indices][B int64 candidate groups][B*2 int64 edge groups]."""
+    return packed_topk_bytes(k, B) + 8 * B * k + 8 * B + 16 * B
+
+
+def merge_grouped_packed(gathered, B: int, k: int):
+    """(n_lists, nbytes) gathered packed grouped blocks on a GPU -> (pids (B, k), scores (B, k), n_cand [B]): the merge that
+    keeps one record per group and counts a group that straddles shards once (clb_merge_topk_grouped_packed_device), on
+    torch's current stream."""
+    import torch
+    n_lists = gathered.shape[0]
+    out_p = torch.empty((B, k), dtype=torch.int64, device=gathered.device)
+    out_s = torch.empty((B, k), dtype=torch.float32, device=gathered.device)
+    out_n = torch.empty(B, dtype=torch.int64, device=gathered.device)
+    st = torch.cuda.current_stream(gathered.device).cuda_stream
+    check(lib().clb_merge_topk_grouped_packed_device(gathered.device.index, C.c_void_p(gathered.data_ptr()), i64(k), i64(n_lists),
+                                                     i64(B), C.c_void_p(out_p.data_ptr()), C.c_void_p(out_s.data_ptr()),
+                                                     C.c_void_p(out_n.data_ptr()), C.c_void_p(st)))
+    return out_p, out_s, out_n
+
+
 def merge_packed(gathered, B: int, k: int, out_p=None, out_s=None):
     """(world, nbytes) gathered packed blocks -> (B, k) merged top-k via clb_merge_topk_packed_device on torch's
     current stream."""
@@ -241,16 +263,63 @@ class DeviceSearch:
                                 f"elements on {self.dev}, got {getattr(Qdev, 'dtype', type(Qdev))} "
                                 f"{tuple(getattr(Qdev, 'shape', ()))} on {getattr(Qdev, 'device', '?')}")
 
-    def phase1(self, Qdev, filters=None, scope="candidates"):
+    def _grouped_block(self):
+        """The packed grouped result block of this shard (packed_grouped_bytes) and the views the grouped calls write into."""
+        import torch
+        if not hasattr(self, "gpacked"):
+            B, k = self.B, self.k
+            self.gpacked = torch.zeros(packed_grouped_bytes(k, B), dtype=torch.uint8, device=self.dev)
+            at_g = packed_topk_bytes(k, B); at_n = at_g + 8 * B * k; at_e = at_n + 8 * B
+            self.g_out_p = self.gpacked[:B * k * 8].view(torch.int64).view(B, k)
+            self.g_out_s = self.gpacked[B * k * 8:B * k * 12].view(torch.float32).view(B, k)
+            self.g_out_g = self.gpacked[at_g:at_n].view(torch.int64).view(B, k)
+            self.g_ncand = self.gpacked[at_n:at_e].view(torch.int64)
+            self.g_edges = self.gpacked[at_e:].view(torch.int64).view(B, 2)
+        return self.gpacked
+
+    def search_grouped_shard(self, Qdev, filters, scope, grouping, group_base: int):
+        """The single exchange of a grouped sharded search on this shard: the whole grouped search
+        (clb_search_batch_grouped_device_slot), then the global group index of every result and the edge groups of every
+        query (clb_search_result_groups_slot), all into the packed grouped block, which is returned.  B <= 64."""
+        import torch
+        from .searcher import _scope_code
+        self._check_queries(Qdev)
+        block = self._grouped_block()
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        gh = self.s._grouping_handle(grouping)
+        check(lib().clb_search_batch_grouped_device_slot(
+            self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
+            None if filters is None else self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)), gh,
+            C.c_void_p(self.g_out_p.data_ptr()), C.c_void_p(self.g_out_s.data_ptr()), C.c_void_p(self.g_ncand.data_ptr()),
+            C.c_void_p(st)))
+        check(lib().clb_search_result_groups_slot(
+            self.s._h, C.c_int(self.slot), gh, i64(group_base), C.c_void_p(self.g_out_p.data_ptr()), i64(self.B), i64(self.k),
+            C.c_void_p(self.g_out_g.data_ptr()), C.c_void_p(self.g_edges.data_ptr()), C.c_void_p(st)))
+        return block
+
+    def phase1(self, Qdev, filters=None, scope="candidates", grouping=None, group_base: int = 0):
         """Two-phase sharded search, first half (clb_search_shard_phase1): everything up to pass 1 on this shard.
         Returns the (B, k) tensor of the shard's k largest approximate scores per query, to be all-gathered.
         `filters` / `scope` as in __call__ (clb_search_shard_phase1_filtered_slot: at most 64 queries per call when one is
-        filtered); phase2 takes none -- it continues on the filtered candidates phase 1 left on the slot."""
+        filtered); phase2 takes none -- it continues on the filtered candidates phase 1 left on the slot.
+        `grouping` (this shard's PassageGrouping) with `group_base` (the global index of the shard's first group): the grouped
+        form, clb_search_shard_phase1_grouped_slot -- returns (local_top, local_gid), the best approximate score of the
+        shard's k best groups and their global group indices (int64), both (B, k) and both to be all-gathered."""
         import torch
         self._check_queries(Qdev)
         if not hasattr(self, "local_top"):
             self.local_top = torch.empty((self.B, self.k), dtype=torch.float32, device=self.dev)
         st = torch.cuda.current_stream(self.dev).cuda_stream
+        if grouping is not None:
+            from .searcher import _scope_code
+            if not hasattr(self, "local_gid"):
+                self.local_gid = torch.empty((self.B, self.k), dtype=torch.int64, device=self.dev)
+            check(lib().clb_search_shard_phase1_grouped_slot(
+                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
+                None if filters is None else self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)),
+                self.s._grouping_handle(grouping), i64(group_base), C.c_void_p(self.local_top.data_ptr()),
+                C.c_void_p(self.local_gid.data_ptr()), C.c_void_p(st)))
+            return self.local_top, self.local_gid
         if filters is not None:
             from .searcher import _scope_code
             check(lib().clb_search_shard_phase1_filtered_slot(
@@ -263,8 +332,11 @@ class DeviceSearch:
                                             C.c_void_p(st)))
         return self.local_top
 
-    def phase2(self, Qdev, all_top):
-        """Second half (clb_search_shard_phase2).  all_top: (n_shards, B, k) gathered `local_top` blocks."""
+    def phase2(self, Qdev, all_top, all_gid=None, grouping=None, group_base: int = 0):
+        """Second half (clb_search_shard_phase2).  all_top: (n_shards, B, k) gathered `local_top` blocks.
+        With `grouping` / `group_base` as in phase1 and `all_gid`, the gathered `local_gid` blocks: the grouped form
+        (clb_search_shard_phase2_grouped_slot) -- the result goes into the packed grouped block, which is returned (for
+        merge_grouped_packed, after the all-gather)."""
         import torch
         from ._lib import ArgumentError
         self._check_queries(Qdev)
@@ -272,6 +344,18 @@ class DeviceSearch:
                 or not all_top.is_contiguous() or all_top.device != self.dev):
             raise ArgumentError(f"all_top must be a contiguous float32 (n_shards, {self.B}, {self.k}) tensor on {self.dev}")
         st = torch.cuda.current_stream(self.dev).cuda_stream
+        if grouping is not None:
+            if (all_gid is None or all_gid.dtype != torch.int64 or all_gid.shape != all_top.shape or not all_gid.is_contiguous()
+                    or all_gid.device != self.dev):
+                raise ArgumentError(f"all_gid must be a contiguous int64 tensor of all_top's shape on {self.dev}")
+            block = self._grouped_block()
+            check(lib().clb_search_shard_phase2_grouped_slot(
+                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
+                C.c_void_p(all_top.data_ptr()), C.c_void_p(all_gid.data_ptr()), i64(all_top.shape[0]),
+                self.s._grouping_handle(grouping), i64(group_base), C.c_void_p(self.g_out_p.data_ptr()),
+                C.c_void_p(self.g_out_s.data_ptr()), C.c_void_p(self.g_out_g.data_ptr()), C.c_void_p(self.g_ncand.data_ptr()),
+                C.c_void_p(self.g_edges.data_ptr()), C.c_void_p(st)))
+            return block
         check(lib().clb_search_shard_phase2_slot(self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B),
                                             i64(self.nprobe), i64(self.k), C.c_void_p(all_top.data_ptr()),
                                             i64(all_top.shape[0]), C.c_void_p(self.out_p.data_ptr()),

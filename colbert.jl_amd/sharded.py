@@ -8,6 +8,11 @@ Two exchange protocols:
   * "single": every shard searches with its own threshold (DeviceSearch.__call__) -> packed all-gather -> merge_packed.
 A filter acts where phase 1 makes a shard's candidate list; everything after that reads only the list, so phase 2 takes
 no filter.
+Grouped search (`make_grouping`, `grouping=`): the group ids are cut at the shard boundaries, and a group that straddles a cut
+keeps ONE global index on both sides (`group_base` of a shard + its local index).  Under "two_phase" the shards publish their
+k best groups with those indices, the threshold counts a repeated index once, and the merge (merge_grouped_packed) keeps one
+record per group and counts a straddling candidate group once; under "single" every shard runs its whole grouped search and
+the same merge follows.
 
 The shards live in one process (`group=None`; on one device, or one device each) or one or more per rank of a
 torch.distributed process group: every method is then a COLLECTIVE -- all ranks call it with the same arguments -- and its
@@ -74,6 +79,70 @@ def slice_mask(mask, bounds):
     if m.dtype != np.bool_ or m.shape != (n,):
         raise ColBERTError(f"mask must be a boolean array of num_docs={n} entries")
     return [m[int(bounds[i] - bounds[0]):int(bounds[i + 1] - bounds[0])] for i in range(len(bounds) - 1)]
+
+
+def dense_group_index(group_ids, n: int) -> np.ndarray:
+    """The caller's group ids over the n passages of a shard group -> the dense 0-based index of every passage's group (the
+    number of id changes before it; for non-decreasing ids this is np.unique's inverse).  ColBERTError for anything but one
+    integer per passage, ArgumentError naming the first position at which the ids decrease."""
+    ids = np.asarray(group_ids)
+    if ids.ndim != 1 or ids.dtype.kind not in "iu" or ids.size != n:
+        raise ColBERTError(f"group_ids must be a vector of integers, one per passage of the shard group (num_docs={n})")
+    ids = ids.astype(np.int64)
+    down = np.nonzero(ids[1:] < ids[:-1])[0]
+    if down.size:
+        i = int(down[0]) + 1
+        raise ArgumentError(f"group ids must be non-decreasing in pid: they decrease at position {i} ({int(ids[i])} after {int(ids[i - 1])})")
+    dense = np.zeros(n, dtype=np.int64)
+    if n > 1:
+        dense[1:] = np.cumsum(ids[1:] != ids[:-1])
+    return dense
+
+
+def slice_groups(group_ids, bounds):
+    """Global group ids -> (one slice of the ids per shard, the group_base of every shard: the dense global index of the
+    group of the shard's first passage -- 0 for a shard without passages)."""
+    n = int(bounds[-1] - bounds[0])
+    dense = dense_group_index(group_ids, n)
+    ids = np.ascontiguousarray(np.asarray(group_ids), dtype=np.int64)
+    cuts = [int(b - bounds[0]) for b in bounds]
+    parts = [ids[cuts[i]:cuts[i + 1]] for i in range(len(cuts) - 1)]
+    bases = [int(dense[cuts[i]]) if cuts[i] < cuts[i + 1] else 0 for i in range(len(cuts) - 1)]
+    return parts, bases
+
+
+class ShardedGrouping:
+    """A passage -> group (document) map over a shard group: one resident PassageGrouping per local shard (`parts`), made
+    from that shard's slice of the ids, and the `group_base` of each (`bases`).  Made by `ShardedSearcher.make_grouping`
+    and refused by any other group.  `count` is the number of groups of the whole collection.  An append to the group
+    invalidates it ("grouping made before an append; make another"); removals and updates do not."""
+
+    def __init__(self, group: "ShardedSearcher", parts, bases, group_ids: np.ndarray, count: int):
+        self.group, self.parts, self.bases, self.count = group, list(parts), [int(b) for b in bases], int(count)
+        self._ids = group_ids                      # host copy of the caller's ids, entry i = global passage first + i
+        self._first = int(group._bounds[0])        # passages before the group
+        self.num_docs = int(group_ids.size)        # the group's passages when it was made
+
+    def groups_of(self, pids) -> np.ndarray:
+        """The caller's group ids of GLOBAL pids as a search returns them."""
+        p = np.asarray(pids, dtype=np.int64) - self._first
+        if p.size and (p.min() < 1 or p.max() > self._ids.size):
+            raise BoundsError(f"pid outside {self._first + 1}..{self._first + self._ids.size} "
+                              "(pid 0 pads a short result: cut the result at n_candidates first)")
+        return self._ids[p - 1]
+
+    def close(self):
+        for g in self.parts:
+            g.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self):
+        return self.count
 
 
 class ShardedFilter:
@@ -244,6 +313,45 @@ class ShardedSearcher:
             return None
         return [[None if f is None else f.parts[i] for f in filters] for i in range(len(self.shards))]
 
+    # -- groupings --------------------------------------------------------------------------------
+    def make_grouping(self, group_ids=None, group_lens=None) -> ShardedGrouping:
+        """A resident passage -> document map over the group, for `grouping=` of the search calls.  Exactly one of:
+        `group_ids`, one integer per passage of the GROUP in pid order, non-decreasing (checked on the host before any shard
+        is called: ArgumentError naming the position), or `group_lens`, the number of passages of every document in pid order
+        (summing to num_docs; document j gets id j).  Every rank passes the same array, as with make_filter(mask=...).  The ids
+        are cut at the shard boundaries; a document may straddle them."""
+        if (group_ids is None) == (group_lens is None):
+            raise ColBERTError("make_grouping takes exactly one of group_ids= and group_lens=")
+        if group_lens is not None:
+            lens = np.asarray(group_lens)
+            if lens.ndim != 1 or lens.dtype.kind not in "iu" or (lens.size and int(lens.min()) < 0) or int(lens.sum()) != self.num_docs:
+                raise ColBERTError(f"group_lens must be non-negative integers summing to num_docs={self.num_docs}")
+            ids = np.repeat(np.arange(lens.size, dtype=np.int64), lens.astype(np.int64))
+        else:
+            ids = np.asarray(group_ids)
+        slices, bases = slice_groups(ids, self._bounds)                 # raises before any shard is called
+        ids = np.ascontiguousarray(ids, dtype=np.int64).copy()
+        count = int(np.count_nonzero(ids[1:] != ids[:-1])) + 1 if ids.size else 0
+        parts = []
+        try:
+            for j, s in enumerate(self.shards):
+                parts.append(s.make_grouping(group_ids=np.ascontiguousarray(slices[self._first + j])))
+        except Exception:
+            for g in parts:
+                g.close()
+            raise
+        L = len(self.shards)
+        return ShardedGrouping(self, parts, bases[self._first:self._first + L], ids, count)
+
+    def _check_grouping(self, grouping):
+        if grouping is None:
+            return None
+        if not isinstance(grouping, ShardedGrouping) or grouping.group is not self:
+            raise ColBERTError("grouping is not a ShardedGrouping of this shard group")
+        if grouping.num_docs != self.num_docs:
+            raise ArgumentError("grouping made before an append; make another")
+        return grouping
+
     # -- search -----------------------------------------------------------------------------------
     def _run(self, i: int, T: int, B: int, k: int, nprobe: int):
         from .distributed import DeviceSearch
@@ -256,7 +364,34 @@ class ShardedSearcher:
         """every local shard runs the two-pass mode for queries of T tokens (set the mode alike on all ranks)"""
         return all(s.mode == 1 for s in self.shards) and T <= 32
 
-    def _piece(self, q, k: int, nprobe: int, filters, scope: str, two_phase: bool):
+    def _piece_grouped(self, runs, Qd, B: int, k: int, filters, scope: str, two_phase: bool, grouping):
+        """_piece with a grouping: between the phases the shards' k best groups travel as (score, global group index); at the
+        end every shard's packed grouped block (pids, scores, group indices, candidate groups, edge groups) is gathered and
+        merged with one record per group."""
+        import torch
+        from .distributed import all_gather_packed, all_gather_scores, merge_grouped_packed, packed_grouped_bytes
+        L = len(self.shards)
+        dev0 = runs[0].dev
+        f = [None if filters is None else filters[i] for i in range(L)]
+        if two_phase:
+            outs = [r.phase1(Qd[i], f[i], scope, grouping.parts[i], grouping.bases[i]) for i, r in enumerate(runs)]
+            top = torch.stack([o[0].to(dev0) for o in outs]).view(L * B, k)
+            gid = torch.stack([o[1].to(dev0) for o in outs]).view(L * B, k)
+            if self.group is not None:
+                top = self._gather_tensor(top, all_gather_scores)
+                gid = self._gather_tensor(gid, all_gather_scores)
+            top, gid = top.reshape(-1, B, k), gid.reshape(-1, B, k)
+            blocks = [r.phase2(Qd[i], top.to(r.dev).contiguous(), gid.to(r.dev).contiguous(), grouping.parts[i], grouping.bases[i])
+                      for i, r in enumerate(runs)]
+        else:
+            blocks = [r.search_grouped_shard(Qd[i], f[i], scope, grouping.parts[i], grouping.bases[i]) for i, r in enumerate(runs)]
+        block = torch.cat([x.to(dev0) for x in blocks])
+        g = self._gather_tensor(block, all_gather_packed) if self.group is not None else block.view(1, -1)
+        lists = g.to(dev0).contiguous().view(-1, packed_grouped_bytes(k, B))
+        mp, ms, n = merge_grouped_packed(lists, B, k)
+        return mp.cpu().numpy(), ms.cpu().numpy(), n.cpu().numpy()
+
+    def _piece(self, q, k: int, nprobe: int, filters, scope: str, two_phase: bool, grouping=None):
         """One exchange for the queries q (dim, T, B <= 64) -> (pids (B, k), scores (B, k), n_cand [B]) as numpy."""
         import torch
         from .distributed import all_gather_packed, all_gather_scores, merge_packed, packed_topk_bytes
@@ -265,6 +400,8 @@ class ShardedSearcher:
         host_q = torch.from_numpy(np.array(q.transpose(2, 1, 0), order="C"))            # (B, T, dim), a copy of the caller's
         runs = [self._run(i, T, B, k, nprobe) for i in range(L)]
         Qd = [host_q.to(r.dev) for r in runs]
+        if grouping is not None:
+            return self._piece_grouped(runs, Qd, B, k, filters, scope, two_phase, grouping)
         if two_phase:
             tops = [r.phase1(Qd[i], None if filters is None else filters[i], scope) for i, r in enumerate(runs)]
             dev0 = runs[0].dev
@@ -290,19 +427,24 @@ class ShardedSearcher:
         return mp.cpu().numpy(), ms.cpu().numpy(), n.cpu().numpy()
 
     def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
-                     scope="candidates", protocol="auto"):
+                     scope="candidates", protocol="auto", grouping=None):
         """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B]), GLOBAL pids, layouts and padding (pid 0 /
         -Inf) as `Searcher.search_batch`; n_candidates is the sum over the shards.  `filters`: one ShardedFilter or a sequence
         of B entries (None = that query is unfiltered); with filters the result is always padded.  Without, a query for which
         the whole group holds fewer than k candidates raises BoundsError unless `pad_short`.  Any B: batches of more than 64
         queries run as pieces of 64.  `protocol`: "two_phase", "single", or "auto" -- two-phase where every shard runs the
-        two-pass mode for this query length, the single exchange otherwise (general-shape shards)."""
+        two-pass mode for this query length, the single exchange otherwise (general-shape shards).
+        `grouping`: one ShardedGrouping of this group for the whole batch -- every query returns its k best GROUPS, each by
+        its best passage (`grouping.groups_of(pids)` names them), exactly as `Searcher.search_batch(grouping=)` on the
+        unsharded index does; n_candidates counts the candidate groups, a group that straddles shards once.  Composes with
+        `filters` in both scopes, under every protocol."""
         q = colmajor(Q, np.float32)
         if q.ndim != 3 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T, B)")
         if protocol not in _PROTOCOLS:
             raise ColBERTError(f"protocol must be one of {_PROTOCOLS}, got {protocol!r}")
         _scope_code(scope)
+        grouping = self._check_grouping(grouping)
         k, B = int(k), q.shape[2]
         nprobe = int(nprobe or self.shards[0].config.nprobe)
         per_shard = self._shard_filters(filters, B)
@@ -312,32 +454,35 @@ class ShardedSearcher:
         for b0 in range(0, B, _PIECE):
             b1 = min(B, b0 + _PIECE)
             f = None if per_shard is None else [x[b0:b1] for x in per_shard]
-            p, s, n = self._piece(q[:, :, b0:b1], k, nprobe, f, scope, two_phase)
+            p, s, n = self._piece(q[:, :, b0:b1], k, nprobe, f, scope, two_phase, grouping)
             pids[:, b0:b1] = p.T; scores[:, b0:b1] = s.T; ncand[b0:b1] = n
         if filters is None and not pad_short:
             short = np.nonzero(ncand < k)[0]
             if short.size:                                                         # searching.jl:127
                 b = int(short[0])
-                raise BoundsError(f"query {b} has {int(ncand[b])} candidate passages, fewer than k={k}")
+                what = "passages" if grouping is None else "groups"
+                raise BoundsError(f"query {b} has {int(ncand[b])} candidate {what}, fewer than k={k}")
         return pids, scores, ncand
 
-    def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates", protocol="auto"):
+    def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates", protocol="auto",
+                          grouping=None):
         """One query, Q (dim, T) -> (pids Int64[k], scores Float32[k]) as `Searcher.search_embeddings`; the candidate count
-        is left in `last_num_candidates`."""
+        (with a grouping: the candidate groups) is left in `last_num_candidates`."""
         q = colmajor(Q, np.float32)
         if q.ndim != 2 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T)")
         p, s, n = self.search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe,
-                                    filters=None if filter is None else [filter], scope=scope, protocol=protocol)
+                                    filters=None if filter is None else [filter], scope=scope, protocol=protocol,
+                                    grouping=grouping)
         self.last_num_candidates = int(n[0])
         return np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(s[:, 0])
 
-    def search(self, query: str, k: int, *, filter=None, scope="candidates", protocol="auto"):
+    def search(self, query: str, k: int, *, filter=None, scope="candidates", protocol="auto", grouping=None):
         """search(searcher, query::String, k) over the group, with the attached encoder."""
         if self.encoder is None:
             raise ColBERTError("no query encoder attached: pass encoder=... or use search_embeddings(Q, k)")
         Q = self.encoder.encode_queries([query])
-        return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope, protocol=protocol)
+        return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope, protocol=protocol, grouping=grouping)
 
     # -- append: to the LAST shard, the only range that can grow without colliding with a neighbour -------------------
     def _owns_last(self) -> bool:

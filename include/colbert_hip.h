@@ -345,8 +345,8 @@ int clb_search_shard_phase1_filtered_slot(clb_searcher* s, int slot, const float
  * clb_searcher_remove and clb_searcher_update, one made before an append is refused ("grouping made before an append; make
  * another"), one made for another searcher is refused (both CLB_EARGUMENT).  It MUST outlive every call that uses it,
  * including calls still enqueued on a stream or captured in a graph; it may be destroyed before or after its searcher.
- * Creation synchronises; searching with it does not.  A call takes ONE grouping for the whole batch.  The two-phase shard
- * calls take none: a group may straddle shards.
+ * Creation synchronises; searching with it does not.  A call takes ONE grouping for the whole batch.  Across the shards of
+ * a group: "Grouped search across a shard group" below.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct clb_grouping clb_grouping;
 int clb_grouping_create(clb_searcher* s, const int64_t* group_ids, int64_t n, clb_grouping** out);
@@ -368,6 +368,53 @@ int clb_search_batch_grouped(clb_searcher* s, const float* Q, int64_t T, int64_t
 int clb_search_batch_grouped_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
                                          int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
                                          int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Grouped search across a shard group.  Every shard holds a clb_grouping made from ITS slice of the group ids (a dense
+ * local index per local passage, as ever) and the caller passes `group_base`: the GLOBAL dense index of the group of the
+ * shard's first passage, so that the global index of local passage p is group_base + index[p].  (The host has the whole id
+ * array: the global dense index of passage i is the number of id changes before it.)  A group that straddles a cut is the
+ * last group of one shard and the first of the next, and its index is the same on both: that is how the three steps below
+ * recognise it.  Global group indices travel as int64, -1 is "none".
+ *
+ *   phase 1: clb_search_shard_phase1_filtered_slot, then the best approximate score of every candidate group; d_local_top /
+ *            d_local_gid (B, k) = up to k groups per query with the largest such scores and their global indices, in no
+ *            order, padded with -Inf / -1.  The caller all-gathers both: d_all_top / d_all_gid = [n_shards][B][k];
+ *   phase 2: tau = the k-th largest score over the DISTINCT indices of the gathered records (a repeated index counts once,
+ *            with its largest score; -Inf when fewer than k exist), the selection at tau, the row sweep, the exact pass,
+ *            the best passage of every group among the re-scored, their top-k.  d_out_pids / d_out_scores (B, k) as
+ *            clb_search_batch_grouped_device_slot, d_out_gids (B, k) the global group index of every result (-1 for
+ *            padding), d_n_cand[b] the shard's distinct candidate groups, d_edge_gids (B, 2) the global group index of the
+ *            query's lowest-pid and highest-pid candidate (-1, -1 without candidates);
+ *   merge:   clb_merge_topk_grouped_device over the gathered results (below).
+ * Checks as the calls they extend: a grouping of another searcher or from before an append is CLB_EARGUMENT, a handle
+ * outside the two-pass mode CLB_EUNSUPPORTED, a null output CLB_EARGUMENT, more than 64 queries with a filter
+ * CLB_EUNSUPPORTED; phase 2 must follow the grouped phase 1 of the same batch, grouping and group_base; at most 256 shards.
+ * grouping == NULL in phase 1 launches exactly what clb_search_shard_phase1_filtered_slot launches and leaves d_local_gid
+ * untouched (phase 2 is then clb_search_shard_phase2_slot).  Stream-ordered, no host synchronisation; after a slot's first
+ * grouped phase 1 nothing is allocated.
+ * ---------------------------------------------------------------------------------------------- */
+int clb_search_shard_phase1_grouped_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
+                                         int64_t group_base, float* d_local_top, int64_t* d_local_gid, void* hip_stream);
+int clb_search_shard_phase2_grouped_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const float* d_all_top, const int64_t* d_all_gid, int64_t n_shards,
+                                         const clb_grouping* grouping, int64_t group_base, int64_t* d_out_pids,
+                                         float* d_out_scores, int64_t* d_out_gids, int64_t* d_n_cand, int64_t* d_edge_gids,
+                                         void* hip_stream);
+/* The single exchange (every shard runs its whole grouped search, clb_search_batch_grouped_device_slot, in any mode): this
+ * call, stream-ordered behind that search on the same slot and stream, gives the merge what the search does not return --
+ * d_out_gids (B, k) from the result pids d_pids, and d_edge_gids (B, 2) from the candidate lists the search left on the
+ * slot.  B <= 64 (one sub-batch: the slot holds the lists of the last one); anything else on the slot in between, another
+ * grouping, B, k or stream is CLB_EARGUMENT. */
+int clb_search_result_groups_slot(clb_searcher* s, int slot, const clb_grouping* grouping, int64_t group_base,
+                                  const int64_t* d_pids, int64_t B, int64_t k, int64_t* d_out_gids, int64_t* d_edge_gids,
+                                  void* hip_stream);
+/* Test hook: the de-duplicated threshold of the grouped phase 2 alone, d_tau[b] from d_all_top / d_all_gid
+ * [n_shards][B][k].  Input as phase 1 makes it: the indices of one list are distinct, and an index two lists share is the
+ * lowest or the highest of each. */
+int clb_debug_group_tau_device(const float* d_all_top, const int64_t* d_all_gid, int64_t n_shards, int64_t B, int64_t k,
+                               float* d_tau, void* hip_stream);
 
 /* retrieve()  (src/search/ranking.jl:23-44) on its own -- test hook.  out_pids needs n_docs entries. */
 int clb_retrieve(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe, int64_t* out_pids,
@@ -394,6 +441,24 @@ int clb_merge_topk_device(int device, const int64_t* d_pids, const float* d_scor
 int64_t clb_packed_topk_bytes(int64_t k, int64_t B);
 int clb_merge_topk_packed_device(int device, const void* d_packed, int64_t k, int64_t n_lists, int64_t B,
                                  int64_t* d_out_pids, float* d_out_scores, void* hip_stream);
+
+/* clb_merge_topk_device for grouped results: every record carries its global group index (d_gids, [n_lists][B][k], -1
+ * for padding; the indices of one list are distinct, and an index two lists share is the lowest or the highest of each --
+ * what contiguous shards give).  Records are ordered by (score desc, pid asc); of the records of one group only the first
+ * survives; the first k survivors are written, padded with (0, -Inf).  d_n_cand_lists [n_lists][B] and d_edge_gids
+ * [n_lists][B][2] are the shards' d_n_cand and d_edge_gids: d_out_n_cand[b] = the sum of the lists' counts minus the number
+ * of lists whose first edge group equals the last edge group of the nearest list before it that has candidates -- a group
+ * over two or more shards is counted once.  At most 256 lists. */
+int clb_merge_topk_grouped_device(int device, const int64_t* d_pids, const float* d_scores, const int64_t* d_gids, int64_t k,
+                                  int64_t n_lists, int64_t B, const int64_t* d_n_cand_lists, const int64_t* d_edge_gids,
+                                  int64_t* d_out_pids, float* d_out_scores, int64_t* d_out_n_cand, void* hip_stream);
+/* The same over PACKED per-shard blocks, so that one all-gather moves a shard's whole grouped result: block r of `d_packed`
+ * is clb_packed_grouped_bytes(k, B) bytes = [the clb_packed_topk_bytes(k, B) block of pids and scores][B*k int64 group
+ * indices][B int64 n_cand][B*2 int64 edge groups].  A shard produces its block by pointing the outputs of
+ * clb_search_shard_phase2_grouped_slot (or of the grouped search and clb_search_result_groups_slot) into one such buffer. */
+int64_t clb_packed_grouped_bytes(int64_t k, int64_t B);
+int clb_merge_topk_grouped_packed_device(int device, const void* d_packed, int64_t k, int64_t n_lists, int64_t B,
+                                         int64_t* d_out_pids, float* d_out_scores, int64_t* d_out_n_cand, void* hip_stream);
 
 /* Per-kernel timing with HIP events on the stream the kernels are launched on (bench.py's roofline).
  * enable, run searches, then read: names[i] (static strings), total milliseconds and launch counts.
