@@ -33,22 +33,19 @@ constexpr int kGroupTile = 1024 * kGroupChunk;      // entries of one tile of th
 //   3. it walks its chunk again from that carry: at every head the run that ends there is final and its slot is stored.
 // The run open at the end of a tile is carried into the next one in registers (every thread computes the same value);
 // the last run is written after the last tile.  Writes: one word per RUN.  grid = B, block = 1024.
-static __global__ __launch_bounds__(1024) void group_collapse_kernel(const float* __restrict__ scores,
-                                                                    const uint32_t* __restrict__ cand,
-                                                                    const int* __restrict__ ncand,
-                                                                    const int* __restrict__ list /*optional*/,
-                                                                    const int* __restrict__ nlist,
-                                                                    const uint32_t* __restrict__ gid, size_t cand_cap,
-                                                                    int* __restrict__ glist, int* __restrict__ nglist) {
-    __shared__ uint32_t sh_last[1024];                 // group of every thread's last entry
-    __shared__ unsigned long long sh_v[16];            // per wave: the stretch behind the wave's last head
-    __shared__ int sh_f[16], sh_c[16];                 // per wave: has a head / number of heads
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = list ? nlist[b] : ncand[b];
-    const float* sc = scores + (size_t)b * cand_cap;
-    const uint32_t* cnd = cand + (size_t)b * cand_cap;
-    const int* lst = list ? list + (size_t)b * cand_cap : nullptr;
-    int* out = glist + (size_t)b * cand_cap;
+//
+// run_max_tiles is that reduction for the n entries of one query, by all 1 024 threads of a work-group, shared with the
+// m-th best of every run (group_extend_kernel): `load(i, &g, &e)` gives entry i its group and its word,
+// `out.run(r, best)` takes the final word of run r (every run once, by one thread), `out.entry(i, r)` the run index of
+// entry i.  Returns the number of runs (every thread the same).
+struct RunScanShared {
+    uint32_t last[1024];                // group of every thread's last entry
+    unsigned long long v[16];           // per wave: the stretch behind the wave's last head
+    int f[16], c[16];                   // per wave: has a head / number of heads
+};
+template <class Load, class Out>
+__device__ __forceinline__ int run_max_tiles(int n, RunScanShared& sh, Load load, Out out) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr uint32_t kNoGroup = 0xffffffffu;         // a group index is below n_docs < 2^31
     unsigned long long carry = 0ull;                   // best of the run open at the tile's start (uniform)
     uint32_t prev_tile = kNoGroup;                     // group of the entry before the tile (read by thread 0 only)
@@ -62,20 +59,18 @@ static __global__ __launch_bounds__(1024) void group_collapse_kernel(const float
 #pragma unroll
         for (int c = 0; c < kGroupChunk; ++c) {
             const int i = i0 + c;
-            const bool valid = c < chunk && i < n;
-            const int slot = valid ? (lst ? lst[i] : i) : 0;
-            g[c] = valid ? gid[cnd[slot]] : kNoGroup;
-            e[c] = valid ? ((unsigned long long)f32_order_key(sc[slot]) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)slot)
-                         : 0ull;
+            g[c] = kNoGroup;
+            e[c] = 0ull;
+            if (c < chunk && i < n) load(i, &g[c], &e[c]);
         }
         // the group of the thread's last valid entry (valid entries are a prefix of the chunk, and of the tile)
         uint32_t last = kNoGroup;
 #pragma unroll
         for (int c = 0; c < kGroupChunk; ++c) last = g[c] != kNoGroup ? g[c] : last;
-        sh_last[tid] = last;
+        sh.last[tid] = last;
         __syncthreads();
-        uint32_t prev = tid > 0 ? sh_last[tid - 1] : prev_tile;
-        if (tid == 0) prev_tile = sh_last[1023];       // only a full tile has a successor
+        uint32_t prev = tid > 0 ? sh.last[tid - 1] : prev_tile;
+        if (tid == 0) prev_tile = sh.last[1023];       // only a full tile has a successor
         // 2. heads, and the stretch behind the last head
         uint32_t heads = 0u;                           // bit c: entry c is a head
         unsigned long long tail = 0ull;
@@ -100,7 +95,7 @@ static __global__ __launch_bounds__(1024) void group_collapse_kernel(const float
                 xf |= yf;
             }
         }
-        if (lane == 63) { sh_c[wave] = xc; sh_f[wave] = xf; sh_v[wave] = xv; }
+        if (lane == 63) { sh.c[wave] = xc; sh.f[wave] = xf; sh.v[wave] = xv; }
         // what the lanes before this one leave open, inside the wave
         int ef = __shfl_up(xf, 1, 64);
         unsigned long long ev = __shfl_up(xv, 1, 64);
@@ -111,11 +106,11 @@ static __global__ __launch_bounds__(1024) void group_collapse_kernel(const float
         unsigned long long open_all = carry;
         int heads_all = 0;
         for (int w2 = 0; w2 < 16; ++w2) {
-            const unsigned long long v = sh_v[w2];
-            open_all = sh_f[w2] ? v : (v > open_all ? v : open_all);
-            heads_all += sh_c[w2];
+            const unsigned long long v = sh.v[w2];
+            open_all = sh.f[w2] ? v : (v > open_all ? v : open_all);
+            heads_all += sh.c[w2];
             if (w2 + 1 == wave) open = open_all;
-            if (w2 < wave) runs_before += sh_c[w2];
+            if (w2 < wave) runs_before += sh.c[w2];
         }
         unsigned long long acc = ef ? ev : (ev > open ? ev : open);    // ... and as the thread itself does
         // 3. the runs that end inside the chunk
@@ -123,19 +118,217 @@ static __global__ __launch_bounds__(1024) void group_collapse_kernel(const float
 #pragma unroll
         for (int c = 0; c < kGroupChunk; ++c) {
             if ((heads >> c) & 1u) {
-                if (r >= 0) out[r] = (int)(0xffffffffu - (uint32_t)(acc & 0xffffffffull));
+                if (r >= 0) out.run(r, acc);
                 ++r;
                 acc = e[c];
             } else {
                 acc = e[c] > acc ? e[c] : acc;
             }
+            if (g[c] != kNoGroup) out.entry(i0 + c, r);
         }
         carry = open_all;
         nruns += heads_all;
     }
-    if (tid == 0) {
-        if (nruns > 0) out[nruns - 1] = (int)(0xffffffffu - (uint32_t)(carry & 0xffffffffull));
-        nglist[b] = nruns;
+    if (tid == 0 && nruns > 0) out.run(nruns - 1, carry);
+    return nruns;
+}
+
+// the word of a slot: order key << 32 | ~slot
+__device__ __forceinline__ unsigned long long slot_word(float score, int slot) {
+    return ((unsigned long long)f32_order_key(score) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)slot);
+}
+__device__ __forceinline__ int word_slot(unsigned long long w) { return (int)(0xffffffffu - (uint32_t)(w & 0xffffffffull)); }
+__device__ __forceinline__ float word_score(unsigned long long w) { return f32_from_order_key((uint32_t)(w >> 32)); }
+
+static __global__ __launch_bounds__(1024) void group_collapse_kernel(const float* __restrict__ scores,
+                                                                    const uint32_t* __restrict__ cand,
+                                                                    const int* __restrict__ ncand,
+                                                                    const int* __restrict__ list /*optional*/,
+                                                                    const int* __restrict__ nlist,
+                                                                    const uint32_t* __restrict__ gid, size_t cand_cap,
+                                                                    int* __restrict__ glist, int* __restrict__ nglist) {
+    __shared__ RunScanShared sh;
+    const int b = blockIdx.x;
+    const int n = list ? nlist[b] : ncand[b];
+    const float* sc = scores + (size_t)b * cand_cap;
+    const uint32_t* cnd = cand + (size_t)b * cand_cap;
+    const int* lst = list ? list + (size_t)b * cand_cap : nullptr;
+    struct Out {
+        int* out;
+        __device__ void run(int r, unsigned long long best) const { out[r] = word_slot(best); }
+        __device__ void entry(int, int) const {}
+    } out{glist + (size_t)b * cand_cap};
+    const int nruns = run_max_tiles(n, sh, [&](int i, uint32_t* g, unsigned long long* e) {
+        const int slot = lst ? lst[i] : i;
+        *g = gid[cnd[slot]];
+        *e = slot_word(sc[slot], slot);
+    }, out);
+    if (threadIdx.x == 0) nglist[b] = nruns;
+}
+
+// S7g-e (hits of a grouped search, per_group = m > 1; two-pass mode, behind the selection).  The list of the selection is
+// L0 = {slot : !(a[slot] < thr)}, thr = tau - 2 eps from thresh[b] = {tau, eps} exactly as margin_threshold forms it (-inf:
+// everything is listed, and this kernel only copies).  It is extended by the passages that can be one of the m best of a
+// listed group:  xlist = L0 + {slot : its run has a member in L0 and !(a[slot] < a_m - 2 eps)},
+// a_m = the m-th largest approximate score of the run among ALL the query's candidates (a run shorter than m: all of it),
+// slots ascending, xnlist[b] their number.
+// The m-th largest of every run at once, whatever the run lengths: m rounds of the run reduction of the collapse over the
+// query's candidates.  Round 0 leaves cut[r] = the largest word of run r -- or kDeadRun when that score is below thr: the
+// run has no member in L0 -- and runidx[slot] = r; round i > 0 reduces the words BELOW cut[run] and leaves the next
+// largest (0: the run has no more entries; a dead run stays dead).  Words are distinct, so i rounds remove exactly the i
+// largest.  cut[r] of a round is written at the head of run r + 1, behind the two barriers of a tile in which or before
+// which every entry of run r has been loaded: the rounds work in place.  grid = B, block = 1024.
+constexpr unsigned long long kDeadRun = ~0ull;
+static __global__ __launch_bounds__(1024) void group_extend_kernel(const float* __restrict__ scores,
+                                                                  const uint32_t* __restrict__ cand,
+                                                                  const int* __restrict__ ncand,
+                                                                  const uint32_t* __restrict__ gid,
+                                                                  const float* __restrict__ thresh, int m, size_t cand_cap,
+                                                                  unsigned long long* cut, int* runidx,
+                                                                  int* __restrict__ xlist, int* __restrict__ xnlist) {
+    __shared__ RunScanShared sh;
+    __shared__ int sh_scan[16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int n = ncand[b];
+    n = n < 0 ? 0 : ((size_t)n > cand_cap ? (int)cand_cap : n);
+    const float* sc = scores + (size_t)b * cand_cap;
+    const uint32_t* cnd = cand + (size_t)b * cand_cap;
+    unsigned long long* ct = cut + (size_t)b * cand_cap;
+    int* ri = runidx + (size_t)b * cand_cap;
+    int* out = xlist + (size_t)b * cand_cap;
+    const float tau = thresh[2 * b], eps = thresh[2 * b + 1];
+    const float thr = tau == kNegInf ? kNegInf : tau - 2.f * eps;
+    if (thr == kNegInf) {                              // uniform: an unsafe query, or one with fewer than k groups
+        for (int i = tid; i < n; i += 1024) out[i] = i;
+        if (tid == 0) xnlist[b] = n;
+        return;
+    }
+    struct First {
+        unsigned long long* ct; int* ri; float thr;
+        __device__ void run(int r, unsigned long long best) const { ct[r] = !(word_score(best) < thr) ? best : kDeadRun; }
+        __device__ void entry(int i, int r) const { ri[i] = r; }
+    };
+    struct Next {
+        unsigned long long* ct;
+        __device__ void run(int r, unsigned long long best) const { ct[r] = best; }
+        __device__ void entry(int, int) const {}
+    };
+    run_max_tiles(n, sh, [&](int i, uint32_t* g, unsigned long long* e) {
+        *g = gid[cnd[i]];
+        *e = slot_word(sc[i], i);
+    }, First{ct, ri, thr});
+    __syncthreads();
+    for (int round = 1; round < m; ++round) {
+        run_max_tiles(n, sh, [&](int i, uint32_t* g, unsigned long long* e) {
+            const int r = ri[i];
+            const unsigned long long c = ct[r], w = slot_word(sc[i], i);
+            *g = (uint32_t)r;
+            *e = c == kDeadRun ? kDeadRun : (w < c ? w : 0ull);
+        }, Next{ct});
+        __syncthreads();
+    }
+    // the ordered union: thread t owns the slots [t * chunk, (t + 1) * chunk), one block-wide scan of the counts places them
+    const float two_eps = 2.f * eps;
+    auto take = [&](int i) {
+        const float a = sc[i];
+        if (!(a < thr)) return true;
+        const unsigned long long c = ct[ri[i]];
+        return c != kDeadRun && (c == 0ull || !(a < word_score(c) - two_eps));
+    };
+    const int chunk = (n + 1023) >> 10;
+    const int lo = min(tid * chunk, n), hi = min(lo + chunk, n);
+    int cnt = 0;
+    for (int i = lo; i < hi; ++i) cnt += take(i) ? 1 : 0;
+    int xv = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(xv, o, 64);
+        if (lane >= o) xv += y;
+    }
+    if (lane == 63) sh_scan[wave] = xv;
+    __syncthreads();
+    int wbase = 0, tot = 0;
+    for (int w2 = 0; w2 < 16; ++w2) {
+        const int sv = sh_scan[w2];
+        if (w2 < wave) wbase += sv;
+        tot += sv;
+    }
+    int pos = wbase + xv - cnt;
+    for (int i = lo; i < hi; ++i)
+        if (take(i)) out[pos++] = i;
+    if (tid == 0) xnlist[b] = tot;
+}
+
+// S7g-f (hits of a grouped search, behind the top-k).  One wave per result (b, j): top_pids[b][j] is the representative of
+// the j-th group (0: a padded row -- all padding).  Its group's run in the exact-scored set -- the re-scored list (list /
+// nlist, slots ascending) or, with list == nullptr, all ncand[b] candidates -- is found by two binary searches on the group
+// index, which is non-decreasing along the set; out[b][j][0 .. m) = the m largest words of the run, largest first (score
+// order key descending, slot ascending: entry 0 is the representative itself), as pid and score, padded with (0, -inf).
+// Entry i is the largest word below entry i - 1: m sweeps of the run by the wave, the first 64 entries kept in registers.
+// grid = ceil(nq * k / 4), block = 256.
+static __global__ __launch_bounds__(256) void group_hits_kernel(const float* __restrict__ scores,
+                                                               const uint32_t* __restrict__ cand,
+                                                               const int* __restrict__ ncand,
+                                                               const int* __restrict__ list /*optional*/,
+                                                               const int* __restrict__ nlist,
+                                                               const uint32_t* __restrict__ gid, int64_t n_docs,
+                                                               const int64_t* __restrict__ top_pids, int nq, int k, int m,
+                                                               size_t cand_cap, int64_t pid_offset,
+                                                               int64_t* __restrict__ out_pids, float* __restrict__ out_scores) {
+    const int lane = threadIdx.x & 63;
+    const int64_t res = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (res >= (int64_t)nq * k) return;                // uniform over the wave
+    const int b = (int)(res / k);
+    int64_t* op = out_pids + (size_t)res * m;
+    float* os = out_scores + (size_t)res * m;
+    const int64_t local = top_pids[res] - pid_offset - 1;
+    int n = list ? nlist[b] : ncand[b];
+    n = n < 0 ? 0 : ((size_t)n > cand_cap ? (int)cand_cap : n);
+    if (top_pids[res] <= 0 || local < 0 || local >= n_docs || n == 0) {
+        for (int i = lane; i < m; i += 64) { op[i] = 0; os[i] = kNegInf; }
+        return;
+    }
+    const float* sc = scores + (size_t)b * cand_cap;
+    const uint32_t* cnd = cand + (size_t)b * cand_cap;
+    const int* lst = list ? list + (size_t)b * cand_cap : nullptr;
+    const uint32_t g = gid[local];
+    auto group_at = [&](int p) { return gid[cnd[lst ? lst[p] : p]]; };
+    int lo = 0, hi = n;                                // first entry of a group >= g
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (group_at(mid) < g) lo = mid + 1; else hi = mid;
+    }
+    const int first = lo;
+    hi = n;                                            // first entry of a group > g
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (group_at(mid) <= g) lo = mid + 1; else hi = mid;
+    }
+    const int end = lo;
+    unsigned long long w0 = 0ull;                      // the lane's entry among the run's first 64
+    if (first + lane < end) {
+        const int slot = lst ? lst[first + lane] : first + lane;
+        w0 = slot_word(sc[slot], slot);
+    }
+    unsigned long long prev = ~0ull;
+    for (int i = 0; i < m; ++i) {
+        unsigned long long best = w0 < prev ? w0 : 0ull;
+        for (int p = first + 64 + lane; p < end; p += 64) {
+            const int slot = lst ? lst[p] : p;
+            const unsigned long long w = slot_word(sc[slot], slot);
+            best = (w < prev && w > best) ? w : best;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long y = __shfl_xor(best, o, 64);
+            best = y > best ? y : best;
+        }
+        if (lane == 0) {
+            const int slot = word_slot(best);
+            op[i] = best ? (int64_t)cnd[slot] + pid_offset + 1 : 0;
+            os[i] = best ? sc[slot] : kNegInf;
+        }
+        prev = best;                                   // 0 once the run is exhausted: nothing is below it
     }
 }
 

@@ -105,6 +105,11 @@ struct Workspace {
     // (grp_list2 / grp_n2), and the threshold at the k-th best group
     bool grouped = false;
     DevBuf grp_list, grp_n, grp_list2, grp_n2, grp_tau;
+    // hits of a grouped search (per_group = m > 1), sized once a call has asked for them: the largest m so far (outp / outs
+    // then hold B k mcap entries), the top-k the hits are read from (hit_p / hit_s, [B][k]) and, in the two-pass mode, the
+    // state of group_extend_kernel (hit_cut / hit_run) with the extended list it leaves (hit_list / hit_n)
+    int64_t mcap = 0;
+    DevBuf hit_p, hit_s, hit_cut, hit_run, hit_list, hit_n;
     DevBuf g_cells, g_keys, g_keys2, g_vals, g_vals2, g_scratch, g_sort_tmp;   // general-shape path (generic_kernels.hpp)
 };
 
@@ -171,6 +176,10 @@ struct Batch {
     int filt_all = 0;
     size_t filt_now = 0;
     const clb_grouping* grp = nullptr;      // grouped search: one grouping for the whole batch (checked by check_grouping)
+    // ... with hits (per_group = m > 1; 0: none): d_out_pids / d_out_scores are the slot's hit_p / hit_s, the m best
+    // passages of every result go to d_hit_pids / d_hit_scores [B][k][m]
+    int per_group = 0;
+    int64_t* d_hit_pids = nullptr; float* d_hit_scores = nullptr;
     bool stats_keep = false;    // the 2nd, 3rd ... sub-batch of one call: the work counters accumulate over the call
     int phase = 0, n_shards = 0;    // two-phase sharded search (run_search)
     float* d_local_top = nullptr; const float* d_all_top = nullptr;
@@ -250,14 +259,15 @@ int next_pow2(int x) {
 // filt_count: the largest filter population of a CLB_FILTER_ALL call (0 otherwise) -- such a query's candidates are its
 // filter's passages, however few the IVF lists would give
 int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_t nprobe, int64_t k, size_t filt_count,
-                           bool grouped) {
+                           bool grouped, int64_t per_group) {
     const int64_t t_tuned = T <= 128 ? T : 0;       // queries of up to 128 tokens take the tuned (or batched general) kernels
     if (B <= w.Bcap && T <= w.Tcap && t_tuned <= w.Ttuned && nprobe <= w.npcap && k <= w.kcap && filt_count <= w.filt_cap &&
-        (!grouped || w.grouped))
+        (!grouped || w.grouped) && per_group <= w.mcap)
         return CLB_OK;
     CLB_HIP(hipDeviceSynchronize());       // buffers may be in use on any of the caller's streams
     B = std::max(B, w.Bcap); T = std::max(T, w.Tcap);
     nprobe = std::max(nprobe, w.npcap); k = std::max(k, w.kcap);
+    per_group = std::max(per_group, w.mcap);
     // T is the LARGEST query length this slot has seen; the buffers of the tuned kernels (the fp32 / fp16 score tables:
     // B K Tpad entries, 2 GB at B = 32, K = 131 072) are sized for the largest query of UP TO 128 tokens it has seen --
     // a longer query (per-query general path, which touches none of them) neither allocates them for 128 tokens nor
@@ -304,8 +314,8 @@ int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, 
     CLB_TRY(w.list.ensure(sizeof(int) * B * w.cand_cap));
     CLB_TRY(w.nlist.ensure(sizeof(int) * B));
     CLB_TRY(w.thresh.ensure(sizeof(float) * B * 2));
-    CLB_TRY(w.outp.ensure(sizeof(int64_t) * B * k));
-    CLB_TRY(w.outs.ensure(sizeof(float) * B * k));
+    CLB_TRY(w.outp.ensure(sizeof(int64_t) * B * k * std::max<int64_t>(per_group, 1)));
+    CLB_TRY(w.outs.ensure(sizeof(float) * B * k * std::max<int64_t>(per_group, 1)));
     CLB_TRY(w.flags.ensure(sizeof(int) * B));
     if (!w.stats.p) {
         CLB_TRY(w.stats.ensure(sizeof(unsigned long long) * 8));
@@ -327,15 +337,25 @@ int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, 
         }
         w.grouped = true;
     }
-    w.Bcap = B; w.Tcap = T; w.Ttuned = Ttuned; w.npcap = nprobe; w.kcap = k;
+    if (per_group > 0) {            // ... and one that has returned hits, these
+        CLB_TRY(w.hit_p.ensure(sizeof(int64_t) * B * k));
+        CLB_TRY(w.hit_s.ensure(sizeof(float) * B * k));
+        if (s->approx_ok) {
+            CLB_TRY(w.hit_cut.ensure(sizeof(unsigned long long) * B * w.cand_cap));
+            CLB_TRY(w.hit_run.ensure(sizeof(int) * B * w.cand_cap));
+            CLB_TRY(w.hit_list.ensure(sizeof(int) * B * w.cand_cap));
+            CLB_TRY(w.hit_n.ensure(sizeof(int) * B));
+        }
+    }
+    w.Bcap = B; w.Tcap = T; w.Ttuned = Ttuned; w.npcap = nprobe; w.kcap = k; w.mcap = per_group;
     w.filt_cap = std::max(w.filt_cap, filt_count);
     CLB_HIP(hipStreamSynchronize(s->stream));
     return CLB_OK;
 }
 
 int ensure_workspace(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_t nprobe, int64_t k, size_t filt_count = 0,
-                     bool grouped = false) {
-    const int rc = ensure_workspace_sized(s, w, B, T, nprobe, k, filt_count, grouped);
+                     bool grouped = false, int64_t per_group = 0) {
+    const int rc = ensure_workspace_sized(s, w, B, T, nprobe, k, filt_count, grouped, per_group);
     if (rc) {
         w.Bcap = 0;       // some buffers may have grown and others not: the next call sizes all of them again
         // a candidate set the size of a filter that does not fit is this call's own request, not a fault of the device
@@ -634,6 +654,19 @@ void launch_result_groups(const clb_searcher* s, Workspace& w, hipStream_t st, c
                        d_out_gids, d_edge_gids);
 }
 
+// S7g-f for queries b0 .. b0 + n - 1 of a call with hits (group_hits_kernel; nothing otherwise): the per_group best passages
+// of every result among the exact-scored set -- the re-scored list (list / nlist) or, with list == nullptr, all candidates
+void launch_hits(const clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int n, const int* list,
+                 const int* nlist) {
+    if (q.per_group <= 0) return;
+    const int64_t waves = (int64_t)n * q.k;
+    hipLaunchKernelGGL(group_hits_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st,
+                       w.scores.as<float>() + (size_t)b0 * w.cand_cap, w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap,
+                       w.ncand.as<int>() + b0, list ? list + (size_t)b0 * w.cand_cap : nullptr, list ? nlist + b0 : nullptr,
+                       q.grp->gid.as<uint32_t>(), s->n_docs, q.d_out_pids + (size_t)b0 * q.k, n, q.k, q.per_group, w.cand_cap,
+                       s->pid_offset, q.d_hit_pids + (size_t)b0 * q.k * q.per_group, q.d_hit_scores + (size_t)b0 * q.k * q.per_group);
+}
+
 // S7 for queries b0 .. b0 + n - 1: the single-work-group select + sort of topk_kernel, one work-group per query, or for
 // k above it a full stable sort per query.  list / nlist: the two-pass mode's re-scored passages ([B][cand_cap] / [B]) or
 // nullptr; ranked: topk_rank_kernel has already written the queries with short lists
@@ -659,7 +692,9 @@ int launch_topk(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, i
 int topk_of(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int n) {
     if (!q.grp) return launch_topk(s, w, st, q, b0, n, nullptr, nullptr, 0);
     launch_collapse(w, st, q, b0, n, nullptr, nullptr, w.grp_list.as<int>(), w.grp_n.as<int>());
-    return launch_topk(s, w, st, q, b0, n, w.grp_list.as<int>(), w.grp_n.as<int>(), 0);
+    CLB_TRY(launch_topk(s, w, st, q, b0, n, w.grp_list.as<int>(), w.grp_n.as<int>(), 0));
+    launch_hits(s, w, st, q, b0, n, nullptr, nullptr);
+    return CLB_OK;
 }
 
 // S1-S3 of query b of the sub-batch on the general-shape path: leaves cand / cand_hdr / ncand of slot b
@@ -855,14 +890,21 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
                     hipLaunchKernelGGL(group_tau_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(), w.grp_list.as<int>(),
                                        w.grp_n.as<int>(), k, w.cand_cap, w.grp_tau.as<float>());
                     CLB_TRY(launch_select(s, w, st, q, (const float*)w.grp_tau.as<float>()));
+                    // hits: the list grows by the passages that can be among the per_group best of a listed group
+                    if (q.per_group > 0)
+                        hipLaunchKernelGGL(group_extend_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(),
+                                           w.cand.as<uint32_t>(), w.ncand.as<int>(), q.grp->gid.as<uint32_t>(),
+                                           w.thresh.as<float>(), q.per_group, w.cand_cap, w.hit_cut.as<unsigned long long>(),
+                                           w.hit_run.as<int>(), w.hit_list.as<int>(), w.hit_n.as<int>());
                 } else
                     CLB_TRY(launch_select(s, w, st, q, nullptr, /*coarse_tau=*/phase == 0));
             }
         }
     }
     // two-pass mode: only the selected passages go on
-    const int* list = two_pass ? w.list.as<int>() : nullptr;
-    const int* nlist = two_pass ? w.nlist.as<int>() : nullptr;
+    const bool extended = two_pass && q.grp && q.per_group > 0 && phase == 0;     // group_extend_kernel has left its own list
+    const int* list = two_pass ? (extended ? w.hit_list.as<int>() : w.list.as<int>()) : nullptr;
+    const int* nlist = two_pass ? (extended ? w.hit_n.as<int>() : w.nlist.as<int>()) : nullptr;
     if (phase == 1) {
         hipLaunchKernelGGL(local_top_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(), list, nlist,
                            w.thresh.as<float>(), k, w.cand_cap, q.d_local_top);
@@ -927,6 +969,7 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
         collapse_exact();
         CLB_TRY(launch_topk(s, w, st, q, 0, B, tlist, tnlist, 0));
     }
+    if (q.grp) launch_hits(s, w, st, q, 0, B, list, nlist);
     if (q.grp && q.d_out_gids) launch_result_groups(s, w, st, q.grp, q.group_base, q.d_out_pids, B, k, q.d_out_gids, q.d_edge_gids);
     if (s->prof.counters) {
         hipLaunchKernelGGL(batch_stats_kernel, dim3(32, B), dim3(256), 0, st, w.cand.as<uint32_t>(),
@@ -990,10 +1033,10 @@ int slot_workspace(clb_searcher* s, int slot, Workspace** w) {
 // (The two-phase sharded calls keep the whole batch: phase 2 continues on the scratch of phase 1.)
 // run_one(b0, q): points q at the queries and outputs of the sub-batch that starts at query b0 and runs it.  q arrives with
 // the sub-batch's size, its slice of the handle array -- nullptr when none of its queries is filtered -- and stats_keep set
-// grp: the grouping of a grouped call (every sub-batch carries it) or nullptr
+// grp: the grouping of a grouped call (every sub-batch carries it) or nullptr; per_group: its hits per result (0: none)
 template <class RunOne>
 int for_sub_batches(clb_searcher* s, Workspace& w, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                    const clb_filter* const* filters, int scope, const clb_grouping* grp, RunOne run_one) {
+                    const clb_filter* const* filters, int scope, const clb_grouping* grp, int64_t per_group, RunOne run_one) {
     size_t filt_count = 0;
     CLB_TRY(check_filters(s, filters, B, scope, &filt_count));
     CLB_TRY(check_grouping(s, grp));
@@ -1001,8 +1044,9 @@ int for_sub_batches(clb_searcher* s, Workspace& w, int64_t T, int64_t B, int64_t
     w.grouped_done.valid = false;
     for (int64_t b0 = 0; b0 < B; b0 += kSubBatch) {
         Batch q = make_batch(nullptr, std::min<int64_t>(kSubBatch, B - b0), T, nprobe, k);
-        CLB_TRY(ensure_workspace(s, w, q.B, T, nprobe, k, filt_count, grp != nullptr));
+        CLB_TRY(ensure_workspace(s, w, q.B, T, nprobe, k, filt_count, grp != nullptr, per_group));
         q.grp = grp;
+        q.per_group = (int)per_group;
         q.stats_keep = b0 > 0;
         set_batch_filters(q, filters, b0, scope, filt_count);
         CLB_TRY(run_one(b0, q));
@@ -1810,19 +1854,22 @@ int clb_search_batch_device(clb_searcher* s, const float* d_Q, int64_t T, int64_
 
 static int search_batch_device_slot_impl(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
                                          int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grp,
-                                         int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
+                                         int64_t per_group /* hits per result, 0: none */, int64_t* d_out_pids,
+                                         float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     Workspace* w = nullptr;
     CLB_TRY(slot_workspace(s, slot, &w));
     hipStream_t st = (hipStream_t)hip_stream;   // NULL = the HIP null stream, as for any HIP API
-    CLB_TRY(for_sub_batches(s, *w, T, B, nprobe, k, filters, scope, grp, [&](int64_t b0, Batch& q) -> int {
+    CLB_TRY(for_sub_batches(s, *w, T, B, nprobe, k, filters, scope, grp, per_group, [&](int64_t b0, Batch& q) -> int {
         q.dQ = d_Q + (size_t)b0 * T * s->dim;
-        q.d_out_pids = d_out_pids + (size_t)b0 * k;
-        q.d_out_scores = d_out_scores + (size_t)b0 * k;
+        q.d_out_pids = per_group ? w->hit_p.as<int64_t>() : d_out_pids + (size_t)b0 * k;
+        q.d_out_scores = per_group ? w->hit_s.as<float>() : d_out_scores + (size_t)b0 * k;
+        q.d_hit_pids = d_out_pids + (size_t)b0 * k * per_group;
+        q.d_hit_scores = d_out_scores + (size_t)b0 * k * per_group;
         q.d_n_cand = d_n_cand ? d_n_cand + b0 : nullptr;
         return run_search(s, *w, st, q);
     }));
-    if (grp && B <= kSubBatch) {
+    if (grp && !per_group && B <= kSubBatch) {
         auto& d = w->grouped_done;
         d.valid = true; d.B = B; d.k = k; d.generation = s->generation; d.grp = grp; d.stream = hip_stream;
     }
@@ -1832,22 +1879,40 @@ static int search_batch_device_slot_impl(clb_searcher* s, int slot, const float*
 int clb_search_batch_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
                                  int64_t k, int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand,
                                  void* hip_stream) {
-    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, nullptr, CLB_FILTER_CANDIDATES, nullptr, d_out_pids,
+    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, nullptr, CLB_FILTER_CANDIDATES, nullptr, 0, d_out_pids,
                                          d_out_scores, d_n_cand, hip_stream);
 }
 
 int clb_search_batch_filtered_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
                                           int64_t k, const clb_filter* const* filters, int scope, int64_t* d_out_pids,
                                           float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
-    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, nullptr, d_out_pids, d_out_scores,
+    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, nullptr, 0, d_out_pids, d_out_scores,
                                          d_n_cand, hip_stream);
 }
 
 int clb_search_batch_grouped_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
                                          int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
                                          int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
-    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, grouping, d_out_pids, d_out_scores,
+    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, grouping, 0, d_out_pids, d_out_scores,
                                          d_n_cand, hip_stream);
+}
+
+// the hits of a grouped call: a grouping and 1 <= per_group <= CLB_MAX_PER_GROUP
+static int check_per_group(const clb_grouping* grouping, int64_t per_group) {
+    if (!grouping) return fail(CLB_EARGUMENT, "grouping is null: per_group needs a grouping");
+    if (per_group < 1 || per_group > CLB_MAX_PER_GROUP)
+        return fail(CLB_EARGUMENT, "per_group must be 1..%d, got %lld", CLB_MAX_PER_GROUP, (long long)per_group);
+    return CLB_OK;
+}
+
+int clb_search_batch_grouped_hits_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                              int64_t k, const clb_filter* const* filters, int scope,
+                                              const clb_grouping* grouping, int64_t per_group, int64_t* d_out_pids,
+                                              float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
+    CLB_TRY(check_per_group(grouping, per_group));
+    // one hit per result is the representative: exactly the grouped search
+    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, grouping, per_group > 1 ? per_group : 0,
+                                         d_out_pids, d_out_scores, d_n_cand, hip_stream);
 }
 
 int clb_search_shard_phase1(clb_searcher* s, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
@@ -1992,23 +2057,27 @@ int clb_search_result_groups_slot(clb_searcher* s, int slot, const clb_grouping*
 }
 
 static int search_batch_impl(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                             const clb_filter* const* filters, int scope, const clb_grouping* grp, int pad_short,
-                             int64_t* out_pids, float* out_scores, int64_t* n_cand) {
+                             const clb_filter* const* filters, int scope, const clb_grouping* grp,
+                             int64_t per_group /* hits per result, 0: none */, int pad_short, int64_t* out_pids,
+                             float* out_scores, int64_t* n_cand) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
+    const int64_t km = k * std::max<int64_t>(per_group, 1);     // entries of one query's result
     Workspace* wp = nullptr;
     CLB_TRY(slot_workspace(s, 0, &wp));
     Workspace& w = *wp;
     hipStream_t st = s->stream;
     std::vector<int> nc((size_t)B), fl((size_t)B);
     // the queries go up into the slot's own buffer and the results come back from it, sub-batch by sub-batch
-    CLB_TRY(for_sub_batches(s, w, T, B, nprobe, k, filters, scope, grp, [&](int64_t b0, Batch& q) -> int {
+    CLB_TRY(for_sub_batches(s, w, T, B, nprobe, k, filters, scope, grp, per_group, [&](int64_t b0, Batch& q) -> int {
         CLB_HIP(hipMemcpyAsync(w.Qdev.p, Q + (size_t)b0 * T * s->dim, sizeof(float) * q.B * T * s->dim, hipMemcpyHostToDevice, st));
         q.dQ = w.Qdev.as<float>();
-        q.d_out_pids = w.outp.as<int64_t>();
-        q.d_out_scores = w.outs.as<float>();
+        q.d_out_pids = per_group ? w.hit_p.as<int64_t>() : w.outp.as<int64_t>();
+        q.d_out_scores = per_group ? w.hit_s.as<float>() : w.outs.as<float>();
+        q.d_hit_pids = w.outp.as<int64_t>();
+        q.d_hit_scores = w.outs.as<float>();
         CLB_TRY(run_search(s, w, st, q));
-        CLB_HIP(hipMemcpyAsync(out_pids + (size_t)b0 * k, w.outp.p, sizeof(int64_t) * q.B * k, hipMemcpyDeviceToHost, st));
-        CLB_HIP(hipMemcpyAsync(out_scores + (size_t)b0 * k, w.outs.p, sizeof(float) * q.B * k, hipMemcpyDeviceToHost, st));
+        CLB_HIP(hipMemcpyAsync(out_pids + (size_t)b0 * km, w.outp.p, sizeof(int64_t) * q.B * km, hipMemcpyDeviceToHost, st));
+        CLB_HIP(hipMemcpyAsync(out_scores + (size_t)b0 * km, w.outs.p, sizeof(float) * q.B * km, hipMemcpyDeviceToHost, st));
         CLB_HIP(hipMemcpyAsync(nc.data() + b0, reported_count(w, q), sizeof(int) * q.B, hipMemcpyDeviceToHost, st));
         CLB_HIP(hipMemcpyAsync(fl.data() + b0, w.flags.p, sizeof(int) * q.B, hipMemcpyDeviceToHost, st));
         return CLB_OK;
@@ -2030,19 +2099,27 @@ static int search_batch_impl(clb_searcher* s, const float* Q, int64_t T, int64_t
 
 int clb_search_batch(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
                      int pad_short, int64_t* out_pids, float* out_scores, int64_t* n_cand) {
-    return search_batch_impl(s, Q, T, B, nprobe, k, nullptr, CLB_FILTER_CANDIDATES, nullptr, pad_short, out_pids, out_scores, n_cand);
+    return search_batch_impl(s, Q, T, B, nprobe, k, nullptr, CLB_FILTER_CANDIDATES, nullptr, 0, pad_short, out_pids, out_scores, n_cand);
 }
 
 int clb_search_batch_filtered(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
                               const clb_filter* const* filters, int scope, int64_t* out_pids, float* out_scores,
                               int64_t* n_cand) {
-    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, nullptr, 1, out_pids, out_scores, n_cand);
+    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, nullptr, 0, 1, out_pids, out_scores, n_cand);
 }
 
 int clb_search_batch_grouped(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
                              const clb_filter* const* filters, int scope, const clb_grouping* grouping, int pad_short,
                              int64_t* out_pids, float* out_scores, int64_t* n_cand) {
-    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, grouping, pad_short, out_pids, out_scores, n_cand);
+    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, grouping, 0, pad_short, out_pids, out_scores, n_cand);
+}
+
+int clb_search_batch_grouped_hits(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                                  const clb_filter* const* filters, int scope, const clb_grouping* grouping, int64_t per_group,
+                                  int pad_short, int64_t* out_pids, float* out_scores, int64_t* n_cand) {
+    CLB_TRY(check_per_group(grouping, per_group));
+    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, grouping, per_group > 1 ? per_group : 0, pad_short, out_pids,
+                             out_scores, n_cand);
 }
 
 // ---- clb_grouping -------------------------------------------------------------------------------------------------

@@ -25,6 +25,21 @@ def _scope_code(scope) -> int:
     return _SCOPES[scope]
 
 
+MAX_PER_GROUP = 16                         # CLB_MAX_PER_GROUP
+
+
+def _per_group(per_group, grouping) -> int:
+    """The `per_group=` of a search call as the integer the C ABI takes: it needs a grouping and lies in 1..16."""
+    from ._lib import ArgumentError
+    if isinstance(per_group, bool) or not isinstance(per_group, (int, np.integer)):
+        raise ArgumentError(f"per_group must be an integer 1..{MAX_PER_GROUP} or None, got {per_group!r}")
+    if grouping is None:
+        raise ArgumentError("per_group needs grouping=: the hits are the best passages of every GROUP")
+    if not 1 <= int(per_group) <= MAX_PER_GROUP:
+        raise ArgumentError(f"per_group must be 1..{MAX_PER_GROUP}, got {int(per_group)}")
+    return int(per_group)
+
+
 class PassageFilter:
     """A set of passages resident in HBM as one bitmap (clb_filter, include/colbert_hip.h): made once by
     `Searcher.make_filter`, reused over any number of searches of that searcher.  Keep it alive while a search that uses
@@ -467,7 +482,8 @@ class Searcher:
         return grouping._h
 
     # -- search -----------------------------------------------------------------------------------
-    def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates", grouping=None):
+    def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates", grouping=None,
+                          per_group=None):
         """search() after encode_queries (searching.jl:102-127).  Q: (dim, T) Float32.
         Returns (pids Int64[k] 1-based, scores Float32[k]).
         `filter` (a PassageFilter of this searcher): search among its passages only -- scope "candidates": the query's
@@ -476,16 +492,19 @@ class Searcher:
         pid 0 / -Inf.
         `grouping` (a PassageGrouping of this searcher): the top-k GROUPS, each by its best passage (that passage's pid and
         score; `grouping.groups_of(pids)` gives the groups); last_num_candidates then counts the candidate groups, and fewer
-        than k of them raise BoundsError as fewer than k candidates do without a grouping (never with a filter)."""
+        than k of them raise BoundsError as fewer than k candidates do without a grouping (never with a filter).
+        `per_group` (an integer m, 1..16, with `grouping`): pids and scores are (m, k) -- column j the m best candidate
+        passages of the j-th group, best first, padded with pid 0 / -Inf (Searcher.search_batch)."""
         q = colmajor(Q, np.float32)
         if q.ndim != 2 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T)")
         _scope_code(scope)
-        if filter is not None or grouping is not None:
+        if filter is not None or grouping is not None or per_group is not None:
             p, s, n = self.search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe,
-                                        filters=None if filter is None else [filter], scope=scope, grouping=grouping)
+                                        filters=None if filter is None else [filter], scope=scope, grouping=grouping,
+                                        per_group=per_group)
             self.last_num_candidates = int(n[0])
-            return np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(s[:, 0])
+            return np.asfortranarray(p[..., 0]), np.asfortranarray(s[..., 0])
         pids = np.zeros(k, dtype=np.int64); scores = np.zeros(k, dtype=np.float32)
         ncand = i64(0)
         check(lib().clb_search(self._h, fptr(q), i64(q.shape[1]), i64(nprobe or self.config.nprobe), i64(k), fptr(pids),
@@ -494,18 +513,32 @@ class Searcher:
         return pids, scores
 
     def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
-                     scope="candidates", grouping=None):
+                     scope="candidates", grouping=None, per_group=None):
         """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B]).
         `filters`: one PassageFilter for every query, or a sequence of B entries (None = that query is unfiltered); with
         filters the results are always padded (pid 0 / -Inf past n_candidates[b], the count AFTER the filter) and `scope`
         is "candidates" (candidates that are in the filter) or "all" (the filter's passages themselves).
         `grouping`: one PassageGrouping for the whole batch -- every query returns its k best GROUPS, each by its best
-        passage, and n_candidates counts the candidate groups (after any filter); short results as without a grouping."""
+        passage, and n_candidates counts the candidate groups (after any filter); short results as without a grouping.
+        `per_group` (an integer m, 1..16; needs `grouping`): pids and scores are (m, k, B) -- [:, j, b] the m best CANDIDATE
+        passages of query b's j-th group, score descending, the lower pid first among equal scores, padded with pid 0 / -Inf
+        when the group has fewer (clb_search_batch_grouped_hits); row 0 is what the call returns without per_group, and the
+        groups, their order and n_candidates are unchanged."""
         q = colmajor(Q, np.float32)
         if q.ndim != 3 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T, B)")
         B = q.shape[2]
         code = _scope_code(scope)
+        if per_group is not None:
+            m = _per_group(per_group, grouping)
+            handles = None if filters is None else self._filter_handles(filters, B)
+            pids = np.zeros((m, k, B), dtype=np.int64, order="F"); scores = np.zeros((m, k, B), dtype=np.float32, order="F")
+            ncand = np.zeros(B, dtype=np.int64)
+            check(lib().clb_search_batch_grouped_hits(self._h, fptr(q), i64(q.shape[1]), i64(B), i64(nprobe or self.config.nprobe),
+                                                      i64(k), handles, C.c_int(code), self._grouping_handle(grouping), i64(m),
+                                                      C.c_int(1 if (pad_short or filters is not None) else 0), fptr(pids),
+                                                      fptr(scores), fptr(ncand)))
+            return pids, scores, ncand
         pids = np.zeros((k, B), dtype=np.int64, order="F"); scores = np.zeros((k, B), dtype=np.float32, order="F")
         ncand = np.zeros(B, dtype=np.int64)
         if grouping is not None:
@@ -544,18 +577,20 @@ class Searcher:
         return {"pids": pids[:m].copy(), "approx": ap[:m].copy(), "exact": ex[:m].copy(), "tau": tau.value,
                 "eps": eps.value, "n_rescore": nr.value}
 
-    def search(self, query: str, k: int, *, filter=None, scope="candidates", grouping=None):
-        """search(searcher, query::String, k) (searching.jl:93-128); `filter` / `scope` / `grouping` as in search_embeddings."""
+    def search(self, query: str, k: int, *, filter=None, scope="candidates", grouping=None, per_group=None):
+        """search(searcher, query::String, k) (searching.jl:93-128); `filter` / `scope` / `grouping` / `per_group` as in
+        search_embeddings."""
         _scope_code(scope)
         if self.encoder is None:
             raise ColBERTError("no query encoder attached: pass encoder=... or use search_embeddings(Q, k)")
         Q = self.encoder.encode_queries([query])
         assert Q.shape[2] == 1 and Q.shape[1] == self.config.query_maxlen, Q.shape
-        return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope, grouping=grouping)
+        return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope, grouping=grouping, per_group=per_group)
 
     def text_search(self, k: int, nprobe: Optional[int] = None, graph: bool = True) -> "TextSearch":
         """A session for repeated `search(searcher, query::String, k)` calls with everything after the tokenizer on the
-        device (TextSearch below).  A session takes no grouping: grouped search is `search(..., grouping=)`."""
+        device (TextSearch below).  A session takes no grouping and no per_group: grouped search and its hits are
+        `search(..., grouping=, per_group=)`."""
         return TextSearch(self, k, nprobe, graph)
 
     # -- profiling (bench.py) -----------------------------------------------------------------------
@@ -769,9 +804,10 @@ class TextSearch:
         self._many = None
 
 
-def search(searcher: Searcher, query, k: int, *, filter=None, scope="candidates", grouping=None):
+def search(searcher: Searcher, query, k: int, *, filter=None, scope="candidates", grouping=None, per_group=None):
     """The reference's exported `search` (src/ColBERT.jl:40).  `query` may be a string (needs an
-    encoder) or a (dim, T) Float32 matrix of query embeddings.  `filter` / `scope` / `grouping`: Searcher.search_embeddings."""
+    encoder) or a (dim, T) Float32 matrix of query embeddings.  `filter` / `scope` / `grouping` / `per_group`:
+    Searcher.search_embeddings."""
     if isinstance(query, str):
-        return searcher.search(query, k, filter=filter, scope=scope, grouping=grouping)
-    return searcher.search_embeddings(query, k, filter=filter, scope=scope, grouping=grouping)
+        return searcher.search(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group)
+    return searcher.search_embeddings(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group)

@@ -12,7 +12,8 @@ Grouped search (`make_grouping`, `grouping=`): the group ids are cut at the shar
 keeps ONE global index on both sides (`group_base` of a shard + its local index).  Under "two_phase" the shards publish their
 k best groups with those indices, the threshold counts a repeated index once, and the merge (merge_grouped_packed) keeps one
 record per group and counts a straddling candidate group once; under "single" every shard runs its whole grouped search and
-the same merge follows.
+the same merge follows.  The hits of a grouped search (`per_group=` of `Searcher`) are not served across a shard group:
+the search calls accept the keyword and raise Unsupported.
 
 The shards live in one process (`group=None`; on one device, or one device each) or one or more per rank of a
 torch.distributed process group: every method is then a COLLECTIVE -- all ranks call it with the same arguments -- and its
@@ -26,7 +27,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import ArgumentError, BoundsError, ColBERTError, check, colmajor, fptr, i64, lib
+from ._lib import ArgumentError, BoundsError, ColBERTError, Unsupported, check, colmajor, fptr, i64, lib
 from .searcher import PassageFilter, _scope_code
 
 _PROTOCOLS = ("auto", "two_phase", "single")
@@ -427,7 +428,7 @@ class ShardedSearcher:
         return mp.cpu().numpy(), ms.cpu().numpy(), n.cpu().numpy()
 
     def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
-                     scope="candidates", protocol="auto", grouping=None):
+                     scope="candidates", protocol="auto", grouping=None, per_group=None):
         """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B]), GLOBAL pids, layouts and padding (pid 0 /
         -Inf) as `Searcher.search_batch`; n_candidates is the sum over the shards.  `filters`: one ShardedFilter or a sequence
         of B entries (None = that query is unfiltered); with filters the result is always padded.  Without, a query for which
@@ -437,7 +438,9 @@ class ShardedSearcher:
         `grouping`: one ShardedGrouping of this group for the whole batch -- every query returns its k best GROUPS, each by
         its best passage (`grouping.groups_of(pids)` names them), exactly as `Searcher.search_batch(grouping=)` on the
         unsharded index does; n_candidates counts the candidate groups, a group that straddles shards once.  Composes with
-        `filters` in both scopes, under every protocol."""
+        `filters` in both scopes, under every protocol.
+        `per_group`: anything but None raises Unsupported (the hits of a grouped search are a single handle's)."""
+        self._no_per_group(per_group)
         q = colmajor(Q, np.float32)
         if q.ndim != 3 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T, B)")
@@ -464,10 +467,17 @@ class ShardedSearcher:
                 raise BoundsError(f"query {b} has {int(ncand[b])} candidate {what}, fewer than k={k}")
         return pids, scores, ncand
 
+    @staticmethod
+    def _no_per_group(per_group):
+        if per_group is not None:
+            raise Unsupported("per_group= (the best passages of every group) is not supported across a shard group: search "
+                              "the unsharded Searcher, or the winners' passages with a filter and scope='all'")
+
     def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates", protocol="auto",
-                          grouping=None):
+                          grouping=None, per_group=None):
         """One query, Q (dim, T) -> (pids Int64[k], scores Float32[k]) as `Searcher.search_embeddings`; the candidate count
         (with a grouping: the candidate groups) is left in `last_num_candidates`."""
+        self._no_per_group(per_group)
         q = colmajor(Q, np.float32)
         if q.ndim != 2 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T)")
@@ -477,8 +487,9 @@ class ShardedSearcher:
         self.last_num_candidates = int(n[0])
         return np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(s[:, 0])
 
-    def search(self, query: str, k: int, *, filter=None, scope="candidates", protocol="auto", grouping=None):
+    def search(self, query: str, k: int, *, filter=None, scope="candidates", protocol="auto", grouping=None, per_group=None):
         """search(searcher, query::String, k) over the group, with the attached encoder."""
+        self._no_per_group(per_group)
         if self.encoder is None:
             raise ColBERTError("no query encoder attached: pass encoder=... or use search_embeddings(Q, k)")
         Q = self.encoder.encode_queries([query])

@@ -370,6 +370,32 @@ int clb_search_batch_grouped_device_slot(clb_searcher* s, int slot, const float*
                                          int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Hits of a grouped search: each of the k groups by its best `per_group` candidate passages (the inner_hits of an
+ * Elasticsearch collapse), 1 <= per_group <= CLB_MAX_PER_GROUP.  The groups, their order, n_cand and the short-result
+ * behaviour are those of the grouped search; the outputs hold B * k * per_group entries, [b][j][0 .. per_group) being the
+ * passages of query b's j-th group: score descending, the lower pid first among equal scores, padded with pid 0 / -Inf when
+ * the group has fewer candidate passages (never an error); a padded group (short result) is all padding.  That is the
+ * reference's full stable ranking of the query's candidates (after any filter) with the first k distinct groups kept in
+ * order of first occurrence and of each its first per_group occurrences -- pids and score bits are identical to that.
+ * Entry 0 of a group is the representative the grouped search returns, bit for bit.  A passage of the group that is not a
+ * candidate of the query does not appear (CLB_FILTER_ALL ranks all passages of a filter).
+ * per_group == 1 launches exactly what the grouped call launches.  per_group outside 1..CLB_MAX_PER_GROUP or a null
+ * grouping is CLB_EARGUMENT.  filters / scope / pad_short, the sub-batches of a large batch and the slot entry's rules
+ * (stream-ordered, no host synchronisation, capturable; B <= 64 when a query is filtered) are those of the calls they
+ * extend.  A slot's first call with hits grows it (in the two-pass mode by 16 bytes per query and candidate of its
+ * capacity), as does a call with a larger per_group than the slot has seen; later calls allocate nothing.  The phase calls
+ * of a shard group take no per_group.
+ * ---------------------------------------------------------------------------------------------- */
+enum { CLB_MAX_PER_GROUP = 16 };
+int clb_search_batch_grouped_hits(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                                  const clb_filter* const* filters, int scope, const clb_grouping* grouping, int64_t per_group,
+                                  int pad_short, int64_t* out_pids, float* out_scores, int64_t* n_cand);
+int clb_search_batch_grouped_hits_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                              int64_t k, const clb_filter* const* filters, int scope,
+                                              const clb_grouping* grouping, int64_t per_group, int64_t* d_out_pids,
+                                              float* d_out_scores, int64_t* d_n_cand, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Grouped search across a shard group.  Every shard holds a clb_grouping made from ITS slice of the group ids (a dense
  * local index per local passage, as ever) and the caller passes `group_base`: the GLOBAL dense index of the group of the
  * shard's first passage, so that the global index of local passage p is group_base + index[p].  (The host has the whole id
