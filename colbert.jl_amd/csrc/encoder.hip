@@ -776,6 +776,13 @@ __global__ void packed_normalize_kernel(const float* __restrict__ D, int dim, in
     for (int d = 0; d < dim; ++d) o[d] = x[d] / den;
 }
 
+// `doc` has no epilogue: the check the epilogue kernels make of every projected row, on its own
+__global__ void nonfinite_rows_kernel(const float* __restrict__ D, int dim, int64_t rows, int* __restrict__ err) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= rows) return;
+    if (!(sumsq_canonical(D + j * dim, dim) <= FLT_MAX)) atomicOr(err, 2);
+}
+
 // The argument checks every encode entry point starts with; makes the encoder's device current.  ptrs_ok: no pointer argument
 // of the call is null -- the host-buffer entry points check only their handle and say so (null_text).  rows: the batch is packed
 // into that many rows, L being its longest sequence
@@ -991,6 +998,9 @@ int clb_encode(clb_encoder* e, const int32_t* integer_ids, const uint8_t* bitmas
     CLB_TRY(check_batch(e, true, "null encoder", L, N));
     CLB_TRY(upload_inputs(e, integer_ids, bitmask, L, N));
     CLB_TRY(forward(e, L, N, e->stream, e->ids.as<int32_t>(), e->mask.as<uint8_t>()));
+    hipLaunchKernelGGL(nonfinite_rows_kernel, dim3(blocks_for(L * N, 64)), dim3(64), 0, e->stream, e->out.as<float>(), (int)e->dim, L * N,
+                       e->err.as<int>());
+    CLB_HIP(hipGetLastError());
     CLB_TRY(read_flag(e, e->stream));
     CLB_HIP(hipMemcpy(out, e->out.p, sizeof(float) * L * N * e->dim, hipMemcpyDeviceToHost));
     return CLB_OK;

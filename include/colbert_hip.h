@@ -694,7 +694,8 @@ int clb_encoder_set_attention_mode(clb_encoder* e, int mode);
  * profiles/r05_experiments.md), 0 = never, 1 = always (tests). */
 int clb_encoder_set_ln_fold(clb_encoder* e, int mode);
 /* doc(bert, linear, integer_ids, bitmask)  (checkpoint.jl:21-25): integer_ids Int32 (L, N), 1-based token ids;
- * bitmask (L, N) 0/1 bytes = attention (key) mask; out Float32 (dim, L, N). */
+ * bitmask (L, N) 0/1 bytes = attention (key) mask; out Float32 (dim, L, N).  No epilogue follows this forward, so one
+ * small pass of its own looks for non-finite rows: CLB_EDOMAIN, like the other entry points. */
 int clb_encode(clb_encoder* e, const int32_t* integer_ids, const uint8_t* bitmask, int64_t L, int64_t N, float* out);
 /* _doc_embeddings_and_doclens  (checkpoint.jl:27-52): forward, clear skiplist tokens, normalise, doclens,
  * compaction.  out_embs (dim, <= L*N); doclens Int64[N]; *n_out = kept columns.
