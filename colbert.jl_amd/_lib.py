@@ -148,6 +148,13 @@ def lib() -> C.CDLL:
         l.clb_packed_grouped_bytes.argtypes = [i64_, i64_]
         l.clb_merge_topk_grouped_packed_device.restype = ci
         l.clb_merge_topk_grouped_packed_device.argtypes = [ci, vp, i64_, i64_, i64_, vp, vp, vp, vp]
+        if hasattr(l, "clb_debug_nearest"):
+            l.clb_debug_nearest_scratch_create.restype = ci
+            l.clb_debug_nearest_scratch_create.argtypes = [ci, C.POINTER(vp)]
+            l.clb_debug_nearest_scratch_destroy.restype = ci
+            l.clb_debug_nearest_scratch_destroy.argtypes = [vp]
+            l.clb_debug_nearest.restype = ci
+            l.clb_debug_nearest.argtypes = [ci, ci, ci, i64_, vp, i64_, vp, i64_, vp, vp, vp, vp, vp, vp]
         _lib = l
     return _lib
 

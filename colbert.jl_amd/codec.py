@@ -333,6 +333,54 @@ def compute_avg_residuals(nbits: int, centroids, heldout, device: int = 0, n_cod
     return cut, w, np.float32(avg.value), codes
 
 
+NEAREST_CHUNK_MAX = 1 << 22          # points per launch of the build's nearest-centroid search (codec.hip)
+TIER_LISTS, TIER_SECOND, TIER_EXHAUSTIVE = 0, 1, 2
+
+
+class NearestScratch:
+    """The device scratch of the nearest-centroid search, kept across debug_nearest calls the way k-means keeps it."""
+
+    def __init__(self, device: int = 0):
+        self._h = C.c_void_p()
+        check(lib().clb_debug_nearest_scratch_create(device, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            check(lib().clb_debug_nearest_scratch_destroy(self._h))
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def debug_nearest(centroids, embs, mode: int = 0, products: int = -1, chunk_max: int = NEAREST_CHUNK_MAX,
+                  scratch: NearestScratch | None = None, device: int = 0) -> dict:
+    """Test hook (clb_debug_nearest): the build's nearest-centroid search at dim 128 -- mode 0 argmax dot, 1 k-means distance --
+    and what its tiers saw.  Returns codes (1-based), vals / gids (n, 2, L): the first tier's group lists per half (gid
+    0x7fffffff = empty), margin (n,), tier (n,): TIER_LISTS / TIER_SECOND / TIER_EXHAUSTIVE, and the per-call words x1, cn, dc,
+    chunks, undecided1, tier2_points, undecided2."""
+    c = colmajor(centroids, np.float32); x = colmajor(embs, np.float32)
+    if c.shape[0] != 128 or x.shape[0] != 128:
+        raise ValueError("debug_nearest: dim must be 128")
+    n, L = x.shape[1], 4
+    codes = np.zeros(n, dtype=np.uint32)
+    lists = np.zeros((n, 2, L), dtype=np.dtype([("v", "<f4"), ("i", "<i4")]))
+    margin = np.zeros(n, dtype=np.float32); tier = np.zeros(n, dtype=np.uint8)
+    stats = np.zeros(8, dtype=np.int64)
+    check(lib().clb_debug_nearest(device, mode, products, chunk_max, fptr(c), c.shape[1], fptr(x), n,
+                                  scratch._h if scratch is not None else None, fptr(codes), fptr(lists), fptr(margin), fptr(tier),
+                                  fptr(stats)))
+    if stats[7] != L:
+        raise RuntimeError(f"debug_nearest: the library's lists hold {stats[7]} entries, this binding reads {L}")
+    bits = lambda v: float(np.array([v], dtype=np.uint32).view(np.float32)[0])      # noqa: E731
+    return {"codes": codes, "vals": lists["v"].copy(), "gids": lists["i"].copy(), "margin": margin, "tier": tier,
+            "x1": bool(stats[0]), "cn": bits(stats[1]), "dc": bits(stats[2]), "chunks": int(stats[3]),
+            "undecided1": int(stats[4]), "tier2_points": int(stats[5]), "undecided2": int(stats[6])}
+
+
 def build_ivf(codes, num_partitions: int, device: int = 0):
     """_build_ivf  (collection_indexer.jl:349-353) -> (ivf Int64[n] 1-based, ivf_lengths Int64[K])"""
     co = np.ascontiguousarray(codes, dtype=np.uint32)

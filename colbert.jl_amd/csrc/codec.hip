@@ -31,6 +31,18 @@ struct NearestScratch {
     DevBuf hi3, lo3, cn3, xc, codes_c, partial_c, ovf2_list, ovf2_count, ovf2_keys;
 };
 
+// What clb_debug_nearest reads out of a call (nullptr everywhere else: nothing below is touched then).  The device arrays are
+// the caller's, n points each; the counters are summed over the chunks.
+struct NearestDebug {
+    ValIdx* lists = nullptr;        // [n][2 halves][kTopPartial]: the first-tier lists
+    float* margin = nullptr;        // the first refine pass's margin
+    uint8_t* tier = nullptr;        // 0 first lists, 1 second tier's lists, 2 exhaustive scan
+    DevBuf undecided_c;             // the second refine pass's verdicts on its dense block
+    bool x1 = false;
+    unsigned int cn_bits[2] = {0, 0};
+    int64_t chunks = 0, undecided1 = 0, tier2_points = 0, undecided2 = 0;
+};
+
 // device-side: codes (1-based UInt32) of n embeddings against K centroids; MODE 0 argmax dot, 1 k-means.
 // dim 128, K >= 32: approximate scores at the 16-bit MFMA rate with a proven bound -- ONE fp16 product per fp32 product since
 // round 5 (nearest_top_f16_dma_kernel: 512 points per staged centroid tile, the measured conversion errors of points and
@@ -38,9 +50,13 @@ struct NearestScratch {
 // of rounds 2-4 (256 points per tile) when a centroid component is outside the fp16 range -- then an exact re-evaluation
 // of the few candidates per point with the canonical arithmetic: the same codes as the all-fp32 kernel (kept as the small-K /
 // other-dim path), bit for bit.
+// chunk_max: points per launch (the default is 256 MB of group lists); force_products: 1 or 3, -1 leaves the choice to
+// COLBERT_NEAREST_PRODUCTS; dbg: see NearestDebug.  Only clb_debug_nearest passes any of the three.
+constexpr int64_t kNearestChunkMax = (int64_t)1 << 22;
 template <int MODE>
 int nearest_centroids(hipStream_t st, const float* dC, const float* dc2, int dim, int K, const float* dX, int64_t n,
-                      uint32_t* dOut, NearestScratch* scratch = nullptr) {
+                      uint32_t* dOut, NearestScratch* scratch = nullptr, int64_t chunk_max = kNearestChunkMax,
+                      int force_products = -1, NearestDebug* dbg = nullptr) {
     if (n == 0) return CLB_OK;
     if (dim == kDim && K >= 32 && scratch) {
         NearestScratch& w = *scratch;
@@ -56,7 +72,7 @@ int nearest_centroids(hipStream_t st, const float* dC, const float* dc2, int dim
         // (the measured max ||c - fp16(c)|| comes back infinite: 4 bytes and one wait per call) or a comparison run asks
         // for the three-product bf16 split, COLBERT_NEAREST_PRODUCTS=3
         const char* products = getenv("COLBERT_NEAREST_PRODUCTS");        // read per call: tests and comparison runs switch it
-        const bool want_x1 = !(products && strcmp(products, "3") == 0);
+        const bool want_x1 = force_products == 1 || (force_products != 3 && !(products && strcmp(products, "3") == 0));
         bool x1 = false;
         if (want_x1) {
             float dc = 0.f;
@@ -79,7 +95,10 @@ int nearest_centroids(hipStream_t st, const float* dC, const float* dc2, int dim
         if (MODE == 1)
             hipLaunchKernelGGL(half_neg_kernel, dim3((kpad + 255) / 256), dim3(256), 0, st, dc2, K, w.bias.as<float>(), kpad);
         const int n_tiles = (K + 31) / 32;
-        const int64_t chunk_max = (int64_t)1 << 22;                     // points per launch: 256 MB of group lists
+        if (dbg) {
+            dbg->x1 = x1;
+            CLB_HIP(hipMemcpyAsync(dbg->cn_bits, w.cn.p, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+        }
         CLB_TRY(w.partial.ensure(sizeof(ValIdx) * (size_t)((std::min(n, chunk_max) + 31) / 32) * 2 * 32 * kTopPartial));
         CLB_TRY(w.ovf_list.ensure(sizeof(uint32_t) * (size_t)std::min(n, chunk_max)));
         CLB_TRY(w.ovf_count.ensure(sizeof(unsigned int)));
@@ -109,9 +128,18 @@ int nearest_centroids(hipStream_t st, const float* dC, const float* dc2, int dim
                                    w.partial.as<ValIdx>(), (uint32_t*)nullptr, K, 32, groups32, n_tiles,
                                    (const float*)nullptr, m);
             CLB_HIP(hipMemsetAsync(w.ovf_count.p, 0, sizeof(unsigned int), st));
-            hipLaunchKernelGGL(nearest_refine_kernel<MODE>, dim3((unsigned)((m + 15) / 16)), dim3(256), 0, st,
-                               w.partial.as<ValIdx>(), dC, dc2, dX + (size_t)p0 * kDim, m, K, w.cn.as<unsigned int>(),
-                               dOut + p0, w.ovf_list.as<uint32_t>(), w.ovf_count.as<unsigned int>(), w.ovf_keys.as<unsigned long long>());
+            if (dbg) {
+                ++dbg->chunks;
+                CLB_HIP(hipMemcpyAsync(dbg->lists + (size_t)p0 * 2 * kTopPartial, w.partial.p, sizeof(ValIdx) * (size_t)m * 2 * kTopPartial,
+                                       hipMemcpyDeviceToDevice, st));
+                hipLaunchKernelGGL((nearest_refine_kernel<MODE, true>), dim3((unsigned)((m + 15) / 16)), dim3(256), 0, st,
+                                   w.partial.as<ValIdx>(), dC, dc2, dX + (size_t)p0 * kDim, m, K, w.cn.as<unsigned int>(),
+                                   dOut + p0, w.ovf_list.as<uint32_t>(), w.ovf_count.as<unsigned int>(),
+                                   w.ovf_keys.as<unsigned long long>(), dbg->margin + p0, dbg->tier + p0);
+            } else
+                hipLaunchKernelGGL(nearest_refine_kernel<MODE>, dim3((unsigned)((m + 15) / 16)), dim3(256), 0, st,
+                                   w.partial.as<ValIdx>(), dC, dc2, dX + (size_t)p0 * kDim, m, K, w.cn.as<unsigned int>(),
+                                   dOut + p0, w.ovf_list.as<uint32_t>(), w.ovf_count.as<unsigned int>(), w.ovf_keys.as<unsigned long long>());
             // The undecided points.  Three-product lists: straight to the exhaustive scan (the list is normally empty: the launch
             // reads a zero and ends).  Single-product lists: a few dozen points per million on well-spread data, but 2.5 % on nearly
             // degenerate embeddings (a random-weight encoder), where the exhaustive scan of them cost as much as the lists of all
@@ -119,10 +147,11 @@ int nearest_centroids(hipStream_t st, const float* dC, const float* dc2, int dim
             // only what THOSE cannot decide is scanned.  One 4-byte read-back per chunk of up to 4 M points.
             const int slices = std::max(1, std::min(n_tiles / 8, 128));
             unsigned int undecided = 0;
-            if (x1) {
+            if (x1 || dbg) {
                 CLB_HIP(hipMemcpyAsync(&undecided, w.ovf_count.p, sizeof undecided, hipMemcpyDeviceToHost, st));
                 CLB_HIP(hipStreamSynchronize(st));
             }
+            if (dbg) dbg->undecided1 += undecided;
             if (x1 && undecided > 64) {
                 const int64_t mc = undecided;
                 if (!tier2_ready) {
@@ -154,10 +183,24 @@ int nearest_centroids(hipStream_t st, const float* dC, const float* dc2, int dim
                                        w.hi3.as<uint16_t>(), w.lo3.as<uint16_t>(), w.xc.as<float>(), w.partial_c.as<ValIdx>(),
                                        (uint32_t*)nullptr, K, 32, groups_c, n_tiles, (const float*)nullptr, mc);
                 CLB_HIP(hipMemsetAsync(w.ovf2_count.p, 0, sizeof(unsigned int), st));
-                hipLaunchKernelGGL(nearest_refine_kernel<MODE>, dim3((unsigned)((mc + 15) / 16)), dim3(256), 0, st,
-                                   w.partial_c.as<ValIdx>(), dC, dc2, w.xc.as<float>(), mc, K, w.cn3.as<unsigned int>(),
-                                   w.codes_c.as<uint32_t>(), w.ovf2_list.as<uint32_t>(), w.ovf2_count.as<unsigned int>(),
-                                   w.ovf2_keys.as<unsigned long long>());
+                if (dbg) {
+                    CLB_TRY(dbg->undecided_c.ensure((size_t)mc));
+                    hipLaunchKernelGGL((nearest_refine_kernel<MODE, true>), dim3((unsigned)((mc + 15) / 16)), dim3(256), 0, st,
+                                       w.partial_c.as<ValIdx>(), dC, dc2, w.xc.as<float>(), mc, K, w.cn3.as<unsigned int>(),
+                                       w.codes_c.as<uint32_t>(), w.ovf2_list.as<uint32_t>(), w.ovf2_count.as<unsigned int>(),
+                                       w.ovf2_keys.as<unsigned long long>(), (float*)nullptr, dbg->undecided_c.as<uint8_t>());
+                    hipLaunchKernelGGL(nearest_debug_tier_kernel, dim3(blocks_for(mc)), dim3(256), 0, st, w.ovf_list.as<uint32_t>(), mc,
+                                       dbg->undecided_c.as<uint8_t>(), dbg->tier + p0);
+                    unsigned int undecided2 = 0;        // (this read-back exists for the hook alone)
+                    CLB_HIP(hipMemcpyAsync(&undecided2, w.ovf2_count.p, sizeof undecided2, hipMemcpyDeviceToHost, st));
+                    CLB_HIP(hipStreamSynchronize(st));
+                    dbg->tier2_points += mc;
+                    dbg->undecided2 += undecided2;
+                } else
+                    hipLaunchKernelGGL(nearest_refine_kernel<MODE>, dim3((unsigned)((mc + 15) / 16)), dim3(256), 0, st,
+                                       w.partial_c.as<ValIdx>(), dC, dc2, w.xc.as<float>(), mc, K, w.cn3.as<unsigned int>(),
+                                       w.codes_c.as<uint32_t>(), w.ovf2_list.as<uint32_t>(), w.ovf2_count.as<unsigned int>(),
+                                       w.ovf2_keys.as<unsigned long long>());
                 const int pairs = (int)std::max<int64_t>(1, std::min<int64_t>(2048 / slices, (mc + 63) / 64));
                 hipLaunchKernelGGL(nearest_centroid_mfma_list_kernel<MODE>, dim3(pairs, slices), dim3(128),
                                    2 * 32 * kCentTileStride * sizeof(float), st, dC, dc2, K, w.xc.as<float>(),
@@ -174,6 +217,9 @@ int nearest_centroids(hipStream_t st, const float* dC, const float* dc2, int dim
                                    w.ovf_list.as<uint32_t>(), w.ovf_count.as<unsigned int>(), w.ovf_keys.as<unsigned long long>());
                 hipLaunchKernelGGL(nearest_list_finalize_kernel, dim3(64), dim3(256), 0, st, w.ovf_list.as<uint32_t>(),
                                    w.ovf_count.as<unsigned int>(), w.ovf_keys.as<unsigned long long>(), dOut + p0);
+                if (dbg && undecided > 0)
+                    hipLaunchKernelGGL(nearest_debug_tier_kernel, dim3(blocks_for(undecided)), dim3(256), 0, st, w.ovf_list.as<uint32_t>(),
+                                       (int64_t)undecided, (const uint8_t*)nullptr, dbg->tier + p0);
             }
         }
     } else if (dim == kDim) {
@@ -469,7 +515,7 @@ struct clb_kmeans_shard {
     Stream s;
     const float* X = nullptr;      // the shard's points: dX (uploaded copy) or the caller's device array (create_device)
     DevBuf dX, dC, dNew, dC2, dAssign, dOrder, dIota, dKeys, dCounts, dStart, dErr, dCnt32, dCnt64;
-    DevBuf sort_tmp, scan_tmp;     // rocPRIM temporaries (kept: the per-iteration sort and scan are only enqueued)
+    DevBuf sort_tmp, scan_tmp;     // temporaries of the radix sort and the scan (kept: the per-iteration sort and scan are only enqueued)
     DevBuf dNext, dDelta;          // update_device: next centroids and max-abs delta (allocated once: a hipFree per
                                    // iteration would be a device-wide synchronisation under the exchange)
     NearestScratch nscratch;
@@ -822,6 +868,75 @@ int clb_debug_exclusive_scan(int device, const uint32_t* in, int64_t n, uint32_t
     CLB_TRY(exclusive_scan_u32(di.as<uint32_t>(), dout.as<uint32_t>(), (size_t)n, s.st));
     CLB_HIP(hipMemcpyAsync(out, dout.p, 4 * (size_t)(n + 1), hipMemcpyDeviceToHost, s.st));
     CLB_HIP(hipStreamSynchronize(s.st));
+    return CLB_OK;
+}
+
+// Test hook of nearest_centroids<MODE> at dim 128 (include/colbert_hip.h): the build's own launch sequence, host arrays in and out,
+// plus what the tiers saw.  `scratch` (clb_debug_nearest_scratch_create, or null) plays the NearestScratch k-means keeps across
+// its iterations.
+struct clb_nearest_scratch {
+    int device = 0;
+    NearestScratch w;
+};
+
+int clb_debug_nearest_scratch_create(int device, clb_nearest_scratch** out) {
+    if (!out) return fail(CLB_EARGUMENT, "clb_debug_nearest_scratch_create: out is null");
+    *out = nullptr;
+    CLB_TRY(use_device(device));
+    *out = new clb_nearest_scratch();
+    (*out)->device = device;
+    return CLB_OK;
+}
+
+int clb_debug_nearest_scratch_destroy(clb_nearest_scratch* s) {
+    if (!s) return CLB_OK;
+    (void)hipSetDevice(s->device);
+    (void)hipDeviceSynchronize();
+    delete s;
+    return CLB_OK;
+}
+
+int clb_debug_nearest(int device, int mode, int products, int64_t chunk_max, const float* centroids, int64_t K, const float* embs,
+                      int64_t n, clb_nearest_scratch* scratch, uint32_t* codes, void* lists, float* margins, uint8_t* tiers,
+                      int64_t* stats) {
+    if (mode != 0 && mode != 1) return fail(CLB_EARGUMENT, "clb_debug_nearest: mode must be 0 (argmax dot) or 1 (k-means distance)");
+    if (products != -1 && products != 1 && products != 3) return fail(CLB_EARGUMENT, "clb_debug_nearest: products must be -1, 1 or 3");
+    if (chunk_max < 1 || K < 1 || n < 1) return fail(CLB_EARGUMENT, "clb_debug_nearest: chunk_max, K and n must be positive");
+    if (K > 0x7fffffff || n >= (int64_t)0xffffffffll) return fail(CLB_EUNSUPPORTED, "clb_debug_nearest: K or n too large");
+    if (!centroids || !embs || !codes || !lists || !margins || !tiers || !stats) return fail(CLB_EARGUMENT, "clb_debug_nearest: null argument");
+    if (scratch && scratch->device != device) return fail(CLB_EARGUMENT, "clb_debug_nearest: the scratch lives on another device");
+    CLB_TRY(use_device(device));
+    Stream s; CLB_TRY(s.init());
+    const size_t nl = (size_t)n * 2 * kTopPartial;
+    DevBuf dC, dC2, dX, dOut, dLists, dMargin, dTier;
+    CLB_TRY(upload(dC, centroids, sizeof(float) * kDim * K, s.st));
+    CLB_TRY(upload(dX, embs, sizeof(float) * kDim * n, s.st));
+    CLB_TRY(dC2.alloc(sizeof(float) * K));
+    CLB_TRY(dOut.alloc(sizeof(uint32_t) * n));
+    CLB_TRY(dLists.alloc(sizeof(ValIdx) * nl));
+    CLB_TRY(dMargin.alloc(sizeof(float) * n));
+    CLB_TRY(dTier.alloc((size_t)n));
+    CLB_HIP(hipMemsetAsync(dLists.p, 0xff, sizeof(ValIdx) * nl, s.st));       // K < 32 has no lists, margins or tiers: all ones
+    CLB_HIP(hipMemsetAsync(dMargin.p, 0xff, sizeof(float) * n, s.st));
+    CLB_HIP(hipMemsetAsync(dTier.p, 0xff, (size_t)n, s.st));
+    NearestScratch local;
+    NearestDebug dbg;
+    dbg.lists = dLists.as<ValIdx>(); dbg.margin = dMargin.as<float>(); dbg.tier = dTier.as<uint8_t>();
+    if (mode == 1) {
+        hipLaunchKernelGGL(centroid_sumsq_kernel, dim3(blocks_for(K, 64)), dim3(64), 0, s.st, dC.as<float>(), kDim, (int)K, dC2.as<float>());
+        CLB_TRY(nearest_centroids<1>(s.st, dC.as<float>(), dC2.as<float>(), kDim, (int)K, dX.as<float>(), n, dOut.as<uint32_t>(),
+                                     scratch ? &scratch->w : &local, chunk_max, products, &dbg));
+    } else {
+        CLB_TRY(nearest_centroids<0>(s.st, dC.as<float>(), nullptr, kDim, (int)K, dX.as<float>(), n, dOut.as<uint32_t>(),
+                                     scratch ? &scratch->w : &local, chunk_max, products, &dbg));
+    }
+    CLB_HIP(hipMemcpyAsync(codes, dOut.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s.st));
+    CLB_HIP(hipMemcpyAsync(lists, dLists.p, sizeof(ValIdx) * nl, hipMemcpyDeviceToHost, s.st));
+    CLB_HIP(hipMemcpyAsync(margins, dMargin.p, sizeof(float) * n, hipMemcpyDeviceToHost, s.st));
+    CLB_HIP(hipMemcpyAsync(tiers, dTier.p, (size_t)n, hipMemcpyDeviceToHost, s.st));
+    CLB_HIP(hipStreamSynchronize(s.st));
+    stats[0] = dbg.x1; stats[1] = dbg.cn_bits[0]; stats[2] = dbg.cn_bits[1]; stats[3] = dbg.chunks;
+    stats[4] = dbg.undecided1; stats[5] = dbg.tier2_points; stats[6] = dbg.undecided2; stats[7] = kTopPartial;
     return CLB_OK;
 }
 

@@ -741,16 +741,20 @@ static __global__ void nearest_list_finalize_kernel(const uint32_t* __restrict__
     for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < count; s += (int64_t)gridDim.x * blockDim.x)
         out[list[s]] = (0xffffffffu - (uint32_t)(keys[s] & 0xffffffffull)) + 1u;
 }
-template <int MODE>
+// DEBUG (clb_debug_nearest only; the build launches the default): the point's margin and whether its lists decided it (0) or it
+// went to the overflow list (1) are written out as well.  ovf_list is never null: every caller passes a NearestScratch.
+template <int MODE, bool DEBUG = false>
 static __global__ __launch_bounds__(256) void nearest_refine_kernel(const ValIdx* __restrict__ partial,
                                                                    const float* __restrict__ C,
                                                                    const float* __restrict__ c2,
                                                                    const float* __restrict__ X, int64_t n, int K,
                                                                    const unsigned int* __restrict__ cn_max_bits,
                                                                    uint32_t* __restrict__ out,
-                                                                   uint32_t* __restrict__ ovf_list = nullptr,
-                                                                   unsigned int* __restrict__ ovf_count = nullptr,
-                                                                   unsigned long long* __restrict__ ovf_keys = nullptr) {
+                                                                   uint32_t* __restrict__ ovf_list,
+                                                                   unsigned int* __restrict__ ovf_count,
+                                                                   unsigned long long* __restrict__ ovf_keys,
+                                                                   float* __restrict__ dbg_margin = nullptr,
+                                                                   uint8_t* __restrict__ dbg_undecided = nullptr) {
     const int lane = threadIdx.x & 63, sub = lane & 15;
     const int64_t p = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);
     const int64_t pp = p < n ? p : n - 1;                       // idle quarters shadow the last point
@@ -784,6 +788,10 @@ static __global__ __launch_bounds__(256) void nearest_refine_kernel(const ValIdx
     const bool overflow = (ent[kTopPartial - 1].i != 0x7fffffff && ent[kTopPartial - 1].v >= thr) ||
                           (ent[2 * kTopPartial - 1].i != 0x7fffffff && ent[2 * kTopPartial - 1].v >= thr) ||
                           (dc > 0.f && !(margin < 3.0e38f));
+    if (DEBUG && sub == 0 && p < n) {
+        if (dbg_margin) dbg_margin[p] = margin;
+        dbg_undecided[p] = overflow ? 1 : 0;
+    }
     float bestv = 0.f;
     int best = 0x7fffffff;
     auto consider = [&](int c) {
@@ -815,7 +823,7 @@ static __global__ __launch_bounds__(256) void nearest_refine_kernel(const ValIdx
             const int c = (gid >> 1) * 32 + (sub & 3) + 8 * (sub >> 2) + 4 * (gid & 1);
             if (c < K) consider(c);
         }
-    } else if (ovf_list) {
+    } else {
         // mass ties (identical or nearly degenerate centroids: more qualifying groups than a list holds): the point is handed
         // to nearest_centroid_mfma_list_kernel, which scores it against ALL centroids on the fp32 MFMA -- 16 lanes walking K
         // centroids here took ~2 ms per point, and a sample whose embeddings are nearly degenerate sends thousands this way
@@ -825,8 +833,6 @@ static __global__ __launch_bounds__(256) void nearest_refine_kernel(const ValIdx
             ovf_keys[at] = 0ull;                                      // below every key nearest_key forms (index field >= 1)
         }
         return;                                                       // uniform over the point's 16 lanes; no shuffle below is shared
-    } else {
-        for (int c = sub; c < K; c += 16) consider(c);
     }
 #pragma unroll
     for (int o = 1; o < 16; o <<= 1) {
@@ -851,6 +857,14 @@ static __global__ void scatter_codes_kernel(const uint32_t* __restrict__ list, i
                                             uint32_t* __restrict__ out) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < count) out[list[t]] = codes_c[t];
+}
+// clb_debug_nearest: which tier decided a point -- 0 its first lists, 1 the second tier's lists, 2 the exhaustive scan.  The first
+// refine pass leaves 0 / 1 (undecided) per point; tier 2 = false turns the undecided into 2, tier 2 = true writes 1 + the second
+// pass's verdict on the dense block through the list.
+static __global__ void nearest_debug_tier_kernel(const uint32_t* __restrict__ list, int64_t count, const uint8_t* __restrict__ undecided_c,
+                                                 uint8_t* __restrict__ tier) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < count) tier[list[t]] = undecided_c ? (uint8_t)(1 + undecided_c[t]) : (uint8_t)2;
 }
 
 static __global__ void half_neg_kernel(const float* __restrict__ c2, int K, float* __restrict__ out, int n_out) {

@@ -1,7 +1,8 @@
 // sort.hip -- see sort.hpp.  Hand-written for gfx950 (round 6; rocPRIM did this until round 5 -- its radix sort alone was
 // 9 MB of the 14-MB library: every tuning of every architecture it knows, compiled for this one).
 //
-// Stable LSD radix sort, 8-bit digits, ceil(end_bit / 8) passes.  One pass:
+// Stable LSD radix sort on the low end_bit bits, 8-bit digits, ceil(end_bit / 8) passes (the last digit masked to the bits below
+// end_bit: keys that differ only above it keep their input order).  One pass:
 //   radix_hist_kernel     work-group g counts the digits of ITS tile (256 threads x 32 items = 8 192 consecutive elements) into
 //                         counts[digit][g] -- digit-major, so that ONE exclusive scan of the flattened array yields, for every
 //                         (digit, tile), where that tile's elements of that digit start in the output: all smaller digits
@@ -31,11 +32,11 @@ constexpr int kSortWaveTile = 64 * kSortItems;      // 2 048 consecutive element
 constexpr int kSortTile = 4 * kSortWaveTile;        // 8 192 per work-group
 
 template <class K>
-__device__ __forceinline__ uint32_t digit_of(K key, int shift) { return (uint32_t)(key >> shift) & 255u; }
+__device__ __forceinline__ uint32_t digit_of(K key, int shift, uint32_t mask) { return (uint32_t)(key >> shift) & mask; }
 
 template <class K>
 static __global__ __launch_bounds__(256) void radix_hist_kernel(const K* __restrict__ keys, size_t n, int shift,
-                                                               uint32_t* __restrict__ counts, uint32_t ntiles) {
+                                                               uint32_t* __restrict__ counts, uint32_t ntiles, uint32_t mask) {
     __shared__ uint32_t h[256];
     h[threadIdx.x] = 0u;
     __syncthreads();
@@ -43,7 +44,7 @@ static __global__ __launch_bounds__(256) void radix_hist_kernel(const K* __restr
 #pragma unroll 8
     for (int i = 0; i < kSortTile / 256; ++i) {
         const size_t e = base + (size_t)i * 256 + threadIdx.x;
-        if (e < n) atomicAdd(&h[digit_of(keys[e], shift)], 1u);
+        if (e < n) atomicAdd(&h[digit_of(keys[e], shift, mask)], 1u);
     }
     __syncthreads();
     counts[(size_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
@@ -53,7 +54,7 @@ template <class K, bool VALS>
 static __global__ __launch_bounds__(256) void radix_scatter_kernel(const K* __restrict__ keys_in, K* __restrict__ keys_out,
                                                                   const uint32_t* __restrict__ vals_in,
                                                                   uint32_t* __restrict__ vals_out, size_t n, int shift,
-                                                                  const uint32_t* __restrict__ bases, uint32_t ntiles) {
+                                                                  const uint32_t* __restrict__ bases, uint32_t ntiles, uint32_t mask) {
     __shared__ uint32_t cur[4][256];                // per wave: count, then running cursor, of every digit
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int i = threadIdx.x; i < 4 * 256; i += 256) (&cur[0][0])[i] = 0u;
@@ -64,7 +65,7 @@ static __global__ __launch_bounds__(256) void radix_scatter_kernel(const K* __re
     for (int i = 0; i < kSortItems; ++i) {
         const size_t e = wbase + (size_t)i * 64 + lane;
         key[i] = e < n ? keys_in[e] : (K)0;
-        if (e < n) atomicAdd(&cur[wave][digit_of(key[i], shift)], 1u);
+        if (e < n) atomicAdd(&cur[wave][digit_of(key[i], shift, mask)], 1u);
     }
     __syncthreads();
     {   // digit d = threadIdx.x: the tile's base, then the waves in order
@@ -83,7 +84,7 @@ static __global__ __launch_bounds__(256) void radix_scatter_kernel(const K* __re
     for (int i = 0; i < kSortItems; ++i) {
         const size_t e = wbase + (size_t)i * 64 + lane;
         const bool valid = e < n;
-        const uint32_t d = digit_of(key[i], shift);
+        const uint32_t d = digit_of(key[i], shift, mask);
         unsigned long long same = __builtin_amdgcn_ballot_w64(valid);
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
@@ -213,10 +214,12 @@ int radix_sort(const K* keys_in, K* keys_out, const uint32_t* vals_in, uint32_t*
         K* dst_k = to_out ? keys_out : tkeys;
         uint32_t* dst_v = to_out ? vals_out : tvals;
         const int shift = 8 * p;
-        hipLaunchKernelGGL(radix_hist_kernel<K>, dim3((unsigned)ntiles), dim3(256), 0, st, src_k, n, shift, counts, (uint32_t)ntiles);
+        // the digit of the last pass ends at end_bit: bits from there up take no part in the order
+        const uint32_t mask = end_bit - shift < 8 ? (1u << std::max(end_bit - shift, 0)) - 1u : 255u;
+        hipLaunchKernelGGL(radix_hist_kernel<K>, dim3((unsigned)ntiles), dim3(256), 0, st, src_k, n, shift, counts, (uint32_t)ntiles, mask);
         CLB_TRY(scan_u32_device(counts, counts, ncount, st, counts + ncount + 2));
         hipLaunchKernelGGL((radix_scatter_kernel<K, VALS>), dim3((unsigned)ntiles), dim3(256), 0, st, src_k, dst_k, src_v, dst_v, n,
-                           shift, (const uint32_t*)counts, (uint32_t)ntiles);
+                           shift, (const uint32_t*)counts, (uint32_t)ntiles, mask);
         src_k = dst_k;
         src_v = dst_v;
         last_k = dst_k;

@@ -1,6 +1,5 @@
-// sort.hpp -- device radix sorts used by the index build (the only library primitive in this build:
-// rocPRIM's stable LSD radix sort; everything else is hand-written).  Implemented in sort.hip so that
-// the rocPRIM headers are compiled once.
+// sort.hpp -- the device radix sorts and the exclusive scan of the index build and the general-shape search: a hand-written
+// stable LSD radix sort (sort.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,10 +8,10 @@
 
 namespace clb {
 struct DevBuf;
-// Every function takes an optional `scratch` buffer for rocPRIM's temporary storage: with one (grown on demand, kept by
+// Every function takes an optional `scratch` buffer for the sort's temporary storage: with one (grown on demand, kept by
 // the caller across calls) the sort is only ENQUEUED on `st` -- no allocation, no host synchronisation; without one the
 // temporary is allocated and freed inside the call, which therefore waits for the stream.
-// stable sort of (key, value) pairs by key, ascending: values keep their input order among equal keys
+// stable sort of (key, value) pairs by the low end_bit bits of the key, ascending: values keep their input order among keys equal there
 // -- exactly Julia's sortperm(codes) when values = 0..n-1 (collection_indexer.jl:350)
 int sort_pairs_u32(const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out,
                    size_t n, int end_bit, hipStream_t st, DevBuf* scratch = nullptr);

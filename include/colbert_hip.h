@@ -586,6 +586,23 @@ int clb_build_ivf(int device, const uint32_t* codes, int64_t n, int64_t K, int64
 int clb_debug_sort(int device, int key_bits, const void* keys, const uint32_t* vals, int64_t n, int end_bit, void* keys_out,
                    uint32_t* vals_out);
 int clb_debug_exclusive_scan(int device, const uint32_t* in, int64_t n, uint32_t* out);
+/* Test hook of the nearest-centroid search every index build goes through (k-means, compress, the residual statistics), at
+ * dim 128: the build's own launch sequence on host arrays, read-only, plus what its tiers saw.  mode 0 = argmax of the dot
+ * product (compress_into_codes!), 1 = the k-means distance.  products -1 = as shipped (COLBERT_NEAREST_PRODUCTS is honoured),
+ * 1 = one fp16 product if the centroids allow it, 3 = the three-product bf16 split.  chunk_max = points per launch (the build
+ * uses 1 << 22).  scratch: null, or a handle that keeps the device scratch across calls the way k-means does.
+ * Out: codes UInt32[n] (1-based); lists [n][2 halves][L] of {float value, int32 group id} (the first tier's group lists,
+ * L = stats[7]; id 0x7fffffff = empty slot); margins Float32[n] (what the first exact pass allowed below the best listed
+ * value); tiers UInt8[n]: 0 = decided from those lists, 1 = by the second tier's lists, 2 = by the exhaustive scan.
+ * stats Int64[8]: [0] single-product lists in use, [1] bits of max ||c|| (x 1.001), [2] bits of max ||c - fp16(c)|| (0 with three
+ * products), [3] chunks, [4] points the first tier left undecided, [5] points sent through the second tier, [6] points that
+ * tier left undecided, [7] L.  K < 32 has no lists: codes only, every other byte of lists, margins and tiers 0xff. */
+typedef struct clb_nearest_scratch clb_nearest_scratch;
+int clb_debug_nearest_scratch_create(int device, clb_nearest_scratch** out);
+int clb_debug_nearest_scratch_destroy(clb_nearest_scratch* s);
+int clb_debug_nearest(int device, int mode, int products, int64_t chunk_max, const float* centroids, int64_t K, const float* embs,
+                      int64_t n, clb_nearest_scratch* scratch, uint32_t* codes, void* lists, float* margins, uint8_t* tiers,
+                      int64_t* stats);
 /* The same over device arrays (80 M codes at 1 M passages never visit the host): d_codes UInt32[n] 1-based,
  * d_ivf Int64[n], d_ivf_lengths Int64[K], all on `device`; runs on `hip_stream` and waits for it (the range check of
  * counts(values, K) has to be read back: CLB_EBOUNDS). */

@@ -1172,7 +1172,8 @@ def test_radix_sort_is_numpys_stable_sort(n):
     import ctypes as C
     l = clb.lib()
     rng = np.random.default_rng(n)
-    for end_bit, hi in ((18, 1 << 18), (32, 1 << 32), (7, 100), (32, 3)):
+    # (18, 2^24) and (7, 2^16): keys with bits ABOVE end_bit, which take no part in the order -- the last digit is masked
+    for end_bit, hi in ((18, 1 << 18), (32, 1 << 32), (7, 100), (32, 3), (18, 1 << 24), (7, 1 << 16)):
         keys = rng.integers(0, hi, size=n, dtype=np.uint64).astype(np.uint32)
         vals = np.arange(n, dtype=np.uint32)
         ko, vo = np.empty_like(keys), np.empty_like(vals)
