@@ -116,6 +116,23 @@ def lib() -> C.CDLL:
             l.clb_search_batch_grouped_hits_device_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                                     C.c_int64, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int64,
                                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(l, "clb_prior_create"):                     # (absent from a COLBERT_HIP_LIB build of an earlier commit)
+            l.clb_prior_create.restype = C.c_int
+            l.clb_prior_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+            l.clb_prior_create_device.restype = C.c_int
+            l.clb_prior_create_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+            l.clb_prior_max_abs.restype = C.c_float
+            l.clb_prior_max_abs.argtypes = [C.c_void_p]
+            l.clb_prior_destroy.restype = C.c_int
+            l.clb_prior_destroy.argtypes = [C.c_void_p]
+            l.clb_search_batch_prior.restype = C.c_int
+            l.clb_search_batch_prior.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                                 C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+            l.clb_search_batch_prior_device_slot.restype = C.c_int
+            l.clb_search_batch_prior_device_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                                             C.c_int64, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p,
+                                                             C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.clb_searcher_generation.restype = C.c_int64
         l.clb_searcher_num_docs.restype = C.c_int64
         l.clb_searcher_num_embeddings.restype = C.c_int64

@@ -12,6 +12,7 @@
 #include "generic_kernels.hpp"
 #include "group_kernels.hpp"
 #include "index_change_kernels.hpp"
+#include "prior_kernels.hpp"
 #include "search_kernels.hpp"
 #include "sort.hpp"
 
@@ -79,6 +80,16 @@ struct clb_grouping {
     DevBuf gid;                 // u32 [n_docs]
 };
 
+// A resident score prior (include/colbert_hip.h): one finite fp32 value per local passage.  Like a clb_grouping it owns its
+// values and remembers its searcher by serial number only.
+struct clb_prior {
+    uint64_t owner = 0;         // clb_searcher::serial of the searcher it was made for
+    int device = 0;
+    int64_t n_docs = 0;
+    float max_abs = 0.f;        // max |value|: a call's weight must keep |weight| * max_abs below FLT_MAX (check_prior)
+    DevBuf values;              // fp32 [n_docs]
+};
+
 // Per-batch workspace (everything a batch of queries needs besides the resident index).
 struct Workspace {
     int64_t Bcap = 0, Tcap = 0, npcap = 0, kcap = 0;
@@ -110,6 +121,10 @@ struct Workspace {
     // state of group_extend_kernel (hit_cut / hit_run) with the extended list it leaves (hit_list / hit_n)
     int64_t mcap = 0;
     DevBuf hit_p, hit_s, hit_cut, hit_run, hit_list, hit_n;
+    // search with a prior (prior_kernels.hpp), sized once a call has passed one: per query the threshold of the boosted
+    // selection (prior_tau[b]) and the largest boosted approximate score by magnitude (prior_tau[Bcap + b])
+    bool prior = false;
+    DevBuf prior_tau;
     DevBuf g_cells, g_keys, g_keys2, g_vals, g_vals2, g_scratch, g_sort_tmp;   // general-shape path (generic_kernels.hpp)
 };
 
@@ -180,6 +195,10 @@ struct Batch {
     // passages of every result go to d_hit_pids / d_hit_scores [B][k][m]
     int per_group = 0;
     int64_t* d_hit_pids = nullptr; float* d_hit_scores = nullptr;
+    // search with a prior: one prior and one weight for the whole batch (checked by check_prior); nullptr: none, and the
+    // sub-batch launches exactly what it launches without one
+    const clb_prior* prior = nullptr;
+    float prior_weight = 1.f;
     bool stats_keep = false;    // the 2nd, 3rd ... sub-batch of one call: the work counters accumulate over the call
     int phase = 0, n_shards = 0;    // two-phase sharded search (run_search)
     float* d_local_top = nullptr; const float* d_all_top = nullptr;
@@ -259,10 +278,10 @@ int next_pow2(int x) {
 // filt_count: the largest filter population of a CLB_FILTER_ALL call (0 otherwise) -- such a query's candidates are its
 // filter's passages, however few the IVF lists would give
 int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_t nprobe, int64_t k, size_t filt_count,
-                           bool grouped, int64_t per_group) {
+                           bool grouped, int64_t per_group, bool prior) {
     const int64_t t_tuned = T <= 128 ? T : 0;       // queries of up to 128 tokens take the tuned (or batched general) kernels
     if (B <= w.Bcap && T <= w.Tcap && t_tuned <= w.Ttuned && nprobe <= w.npcap && k <= w.kcap && filt_count <= w.filt_cap &&
-        (!grouped || w.grouped) && per_group <= w.mcap)
+        (!grouped || w.grouped) && per_group <= w.mcap && (!prior || w.prior))
         return CLB_OK;
     CLB_HIP(hipDeviceSynchronize());       // buffers may be in use on any of the caller's streams
     B = std::max(B, w.Bcap); T = std::max(T, w.Tcap);
@@ -347,6 +366,10 @@ int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, 
             CLB_TRY(w.hit_n.ensure(sizeof(int) * B));
         }
     }
+    if (prior || w.prior) {         // ... and one that has searched with a prior, this
+        CLB_TRY(w.prior_tau.ensure(sizeof(float) * 2 * B));
+        w.prior = true;
+    }
     w.Bcap = B; w.Tcap = T; w.Ttuned = Ttuned; w.npcap = nprobe; w.kcap = k; w.mcap = per_group;
     w.filt_cap = std::max(w.filt_cap, filt_count);
     CLB_HIP(hipStreamSynchronize(s->stream));
@@ -354,8 +377,8 @@ int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, 
 }
 
 int ensure_workspace(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_t nprobe, int64_t k, size_t filt_count = 0,
-                     bool grouped = false, int64_t per_group = 0) {
-    const int rc = ensure_workspace_sized(s, w, B, T, nprobe, k, filt_count, grouped, per_group);
+                     bool grouped = false, int64_t per_group = 0, bool prior = false) {
+    const int rc = ensure_workspace_sized(s, w, B, T, nprobe, k, filt_count, grouped, per_group, prior);
     if (rc) {
         w.Bcap = 0;       // some buffers may have grown and others not: the next call sizes all of them again
         // a candidate set the size of a filter that does not fit is this call's own request, not a fault of the device
@@ -687,9 +710,20 @@ int launch_topk(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, i
     return CLB_OK;
 }
 
-// S7 of the general-shape path for queries b0 .. b0 + n - 1, the exact scores of all their candidates in place -- with a
-// grouping: one collapse, then the top-k forms rank its list
+// P1 for queries b0 .. b0 + n - 1 of a call with a prior (prior_boost_kernel; nothing otherwise): the scores of the listed
+// slots (list / nlist) or, with list == nullptr, of all candidates become score + weight * value; mabs: prior_tau's M, or nullptr
+void launch_boost(Workspace& w, hipStream_t st, const Batch& q, int b0, int n, const int* list, const int* nlist, float* mabs) {
+    if (!q.prior) return;
+    hipLaunchKernelGGL(prior_boost_kernel, dim3(n), dim3(1024), 0, st, w.scores.as<float>() + (size_t)b0 * w.cand_cap,
+                       w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap, w.ncand.as<int>() + b0,
+                       list ? list + (size_t)b0 * w.cand_cap : nullptr, list ? nlist + b0 : nullptr,
+                       q.prior->values.as<float>(), q.prior_weight, w.cand_cap, mabs ? mabs + b0 : nullptr);
+}
+
+// S7 of the general-shape path for queries b0 .. b0 + n - 1, the exact scores of all their candidates in place (with a
+// prior: boosted first) -- with a grouping: one collapse, then the top-k forms rank its list
 int topk_of(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int n) {
+    launch_boost(w, st, q, b0, n, nullptr, nullptr, nullptr);
     if (!q.grp) return launch_topk(s, w, st, q, b0, n, nullptr, nullptr, 0);
     launch_collapse(w, st, q, b0, n, nullptr, nullptr, w.grp_list.as<int>(), w.grp_n.as<int>());
     CLB_TRY(launch_topk(s, w, st, q, b0, n, w.grp_list.as<int>(), w.grp_n.as<int>(), 0));
@@ -871,7 +905,23 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
                 const dim3 approx_grid = gxq > 0 && B > 1 ? dim3(gxq, B) : dim3(8 * kWgPerGroup);
                 launch_pass1(s, w, st, dQ, approx_grid, B, T);
             }
-            {
+            if (q.prior) {
+                // with a prior (phase 0 only): the selection cuts on the BOOSTED approximate scores, at their k-th largest --
+                // with a grouping the k-th best group's -- lowered by the rounding slack (prior_tau_kernel)
+                Timed t(s, KID_SELECT, st);
+                float* ptau = w.prior_tau.as<float>();
+                float* mabs = ptau + w.Bcap;
+                launch_boost(w, st, q, 0, B, nullptr, nullptr, mabs);
+                if (q.grp) launch_collapse(w, st, q, 0, B, nullptr, nullptr, w.grp_list.as<int>(), w.grp_n.as<int>());
+                ApproxConsts ac = s->approx_consts;
+                ac.dc_max = bound_dc(s, w);
+                hipLaunchKernelGGL(prior_tau_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(),
+                                   q.grp ? (const int*)w.grp_list.as<int>() : (const int*)nullptr,
+                                   q.grp ? (const int*)w.grp_n.as<int>() : (const int*)nullptr, k, w.cand_cap, (const float*)mabs,
+                                   dQ, T, ac, w.have_range ? (const float4*)w.tscale.as<float4>() : (const float4*)nullptr,
+                                   w.cell8 ? 1 : 0, ptau);
+                CLB_TRY(launch_select(s, w, st, q, (const float*)ptau));
+            } else {
                 Timed t(s, KID_SELECT, st);
                 if (q.grp && phase == 1) {
                     // grouped phase 1: the shard's k best groups by approximate score, with their global indices; the
@@ -947,6 +997,7 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
     const int* tlist = list;
     const int* tnlist = nlist;
     auto collapse_exact = [&]() {
+        launch_boost(w, st, q, 0, B, list, nlist, nullptr);     // with a prior: the exact scores become E = e + weight * value
         if (!q.grp) return;
         int* gl = list ? w.grp_list2.as<int>() : w.grp_list.as<int>();
         int* gn = list ? w.grp_n2.as<int>() : w.grp_n.as<int>();
@@ -1000,6 +1051,21 @@ int check_filters(const clb_searcher* s, const clb_filter* const* filters, int64
     return CLB_OK;
 }
 
+// the prior of a call (or nullptr) and its weight: the prior must be this searcher's, made for the passages it holds now, and
+// weight * value must be finite for every value
+int check_prior(const clb_searcher* s, const clb_prior* p, float weight) {
+    if (!p) return CLB_OK;
+    if (!std::isfinite(weight)) return fail(CLB_EARGUMENT, "prior_weight must be finite, got %g", (double)weight);
+    if (p->owner != s->serial) return fail(CLB_EARGUMENT, "the prior was made for another searcher");
+    if (p->n_docs != s->n_docs)     // its table has the old length
+        return fail(CLB_EARGUMENT, "prior made before an append; make another");
+    if (!(std::fabs((double)weight) * (double)p->max_abs < (double)FLT_MAX))
+        return fail(CLB_EARGUMENT, "prior_weight %g times the prior's largest |value| %g is not below FLT_MAX", (double)weight,
+                    (double)p->max_abs);
+    return CLB_OK;
+}
+struct PriorArg { const clb_prior* p = nullptr; float weight = 1.f; };
+
 // the grouping of a call (or nullptr): it must be this searcher's, made for the passages it holds now
 int check_grouping(const clb_searcher* s, const clb_grouping* g) {
     if (!g) return CLB_OK;
@@ -1033,19 +1099,24 @@ int slot_workspace(clb_searcher* s, int slot, Workspace** w) {
 // (The two-phase sharded calls keep the whole batch: phase 2 continues on the scratch of phase 1.)
 // run_one(b0, q): points q at the queries and outputs of the sub-batch that starts at query b0 and runs it.  q arrives with
 // the sub-batch's size, its slice of the handle array -- nullptr when none of its queries is filtered -- and stats_keep set
-// grp: the grouping of a grouped call (every sub-batch carries it) or nullptr; per_group: its hits per result (0: none)
+// grp: the grouping of a grouped call (every sub-batch carries it) or nullptr; per_group: its hits per result (0: none);
+// prior: the prior and weight of a call with one (every sub-batch carries them) or none
 template <class RunOne>
 int for_sub_batches(clb_searcher* s, Workspace& w, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                    const clb_filter* const* filters, int scope, const clb_grouping* grp, int64_t per_group, RunOne run_one) {
+                    const clb_filter* const* filters, int scope, const clb_grouping* grp, int64_t per_group, PriorArg prior,
+                    RunOne run_one) {
     size_t filt_count = 0;
     CLB_TRY(check_filters(s, filters, B, scope, &filt_count));
     CLB_TRY(check_grouping(s, grp));
+    CLB_TRY(check_prior(s, prior.p, prior.weight));      // (no entry point takes a prior and per_group: group_extend_kernel reads MaxSim)
     w.pending.valid = false;
     w.grouped_done.valid = false;
     for (int64_t b0 = 0; b0 < B; b0 += kSubBatch) {
         Batch q = make_batch(nullptr, std::min<int64_t>(kSubBatch, B - b0), T, nprobe, k);
-        CLB_TRY(ensure_workspace(s, w, q.B, T, nprobe, k, filt_count, grp != nullptr, per_group));
+        CLB_TRY(ensure_workspace(s, w, q.B, T, nprobe, k, filt_count, grp != nullptr, per_group, prior.p != nullptr));
         q.grp = grp;
+        q.prior = prior.p;
+        q.prior_weight = prior.weight;
         q.per_group = (int)per_group;
         q.stats_keep = b0 > 0;
         set_batch_filters(q, filters, b0, scope, filt_count);
@@ -1855,12 +1926,12 @@ int clb_search_batch_device(clb_searcher* s, const float* d_Q, int64_t T, int64_
 static int search_batch_device_slot_impl(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
                                          int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grp,
                                          int64_t per_group /* hits per result, 0: none */, int64_t* d_out_pids,
-                                         float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
+                                         float* d_out_scores, int64_t* d_n_cand, void* hip_stream, PriorArg prior = {}) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     Workspace* w = nullptr;
     CLB_TRY(slot_workspace(s, slot, &w));
     hipStream_t st = (hipStream_t)hip_stream;   // NULL = the HIP null stream, as for any HIP API
-    CLB_TRY(for_sub_batches(s, *w, T, B, nprobe, k, filters, scope, grp, per_group, [&](int64_t b0, Batch& q) -> int {
+    CLB_TRY(for_sub_batches(s, *w, T, B, nprobe, k, filters, scope, grp, per_group, prior, [&](int64_t b0, Batch& q) -> int {
         q.dQ = d_Q + (size_t)b0 * T * s->dim;
         q.d_out_pids = per_group ? w->hit_p.as<int64_t>() : d_out_pids + (size_t)b0 * k;
         q.d_out_scores = per_group ? w->hit_s.as<float>() : d_out_scores + (size_t)b0 * k;
@@ -2059,7 +2130,7 @@ int clb_search_result_groups_slot(clb_searcher* s, int slot, const clb_grouping*
 static int search_batch_impl(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
                              const clb_filter* const* filters, int scope, const clb_grouping* grp,
                              int64_t per_group /* hits per result, 0: none */, int pad_short, int64_t* out_pids,
-                             float* out_scores, int64_t* n_cand) {
+                             float* out_scores, int64_t* n_cand, PriorArg prior = {}) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     const int64_t km = k * std::max<int64_t>(per_group, 1);     // entries of one query's result
     Workspace* wp = nullptr;
@@ -2068,7 +2139,7 @@ static int search_batch_impl(clb_searcher* s, const float* Q, int64_t T, int64_t
     hipStream_t st = s->stream;
     std::vector<int> nc((size_t)B), fl((size_t)B);
     // the queries go up into the slot's own buffer and the results come back from it, sub-batch by sub-batch
-    CLB_TRY(for_sub_batches(s, w, T, B, nprobe, k, filters, scope, grp, per_group, [&](int64_t b0, Batch& q) -> int {
+    CLB_TRY(for_sub_batches(s, w, T, B, nprobe, k, filters, scope, grp, per_group, prior, [&](int64_t b0, Batch& q) -> int {
         CLB_HIP(hipMemcpyAsync(w.Qdev.p, Q + (size_t)b0 * T * s->dim, sizeof(float) * q.B * T * s->dim, hipMemcpyHostToDevice, st));
         q.dQ = w.Qdev.as<float>();
         q.d_out_pids = per_group ? w.hit_p.as<int64_t>() : w.outp.as<int64_t>();
@@ -2120,6 +2191,106 @@ int clb_search_batch_grouped_hits(clb_searcher* s, const float* Q, int64_t T, in
     CLB_TRY(check_per_group(grouping, per_group));
     return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, grouping, per_group > 1 ? per_group : 0, pad_short, out_pids,
                              out_scores, n_cand);
+}
+
+// ---- clb_prior ----------------------------------------------------------------------------------------------------
+// a weight that is not a finite number is refused before anything is looked at (the searcher comes next, as in every entry)
+static int check_prior_weight(const clb_prior* prior, float weight) {
+    if (prior && !std::isfinite(weight)) return fail(CLB_EARGUMENT, "prior_weight must be finite, got %g", (double)weight);
+    return CLB_OK;
+}
+
+int clb_search_batch_prior(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                           const clb_filter* const* filters, int scope, const clb_grouping* grouping, const clb_prior* prior,
+                           float weight, int pad_short, int64_t* out_pids, float* out_scores, int64_t* n_cand) {
+    CLB_TRY(check_prior_weight(prior, weight));
+    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, grouping, 0, pad_short, out_pids, out_scores, n_cand,
+                             PriorArg{prior, weight});
+}
+
+int clb_search_batch_prior_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                       int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
+                                       const clb_prior* prior, float weight, int64_t* d_out_pids, float* d_out_scores,
+                                       int64_t* d_n_cand, void* hip_stream) {
+    CLB_TRY(check_prior_weight(prior, weight));
+    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, grouping, 0, d_out_pids, d_out_scores,
+                                         d_n_cand, hip_stream, PriorArg{prior, weight});
+}
+
+using PriorPtr = std::unique_ptr<clb_prior, decltype(&clb_prior_destroy)>;
+// the arguments both creators share, checked before the device is touched
+static int prior_args(clb_searcher* s, const float* values, int64_t n, clb_prior** out) {
+    if (out) *out = nullptr;
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    if (!out) return fail(CLB_EARGUMENT, "out is null");
+    if (n != s->n_docs)
+        return fail(CLB_EARGUMENT, "a prior holds one value per passage: n=%lld, the searcher has %lld passages", (long long)n,
+                    (long long)s->n_docs);
+    if (n > 0 && !values) return fail(CLB_EARGUMENT, "values is null");
+    return CLB_OK;
+}
+// a prior of s with its values allocated, on s's device
+static int prior_alloc(clb_searcher* s, int64_t n, PriorPtr& p) {
+    CLB_TRY(use_device(s->device));
+    p.reset(new clb_prior());
+    p->owner = s->serial; p->device = s->device; p->n_docs = n;
+    return p->values.alloc(sizeof(float) * (size_t)n);
+}
+static int bad_prior_value(const clb_searcher* s, int64_t i) {
+    return fail(CLB_EARGUMENT, "the prior of passage %lld is not a finite number", (long long)(s->pid_offset + i + 1));
+}
+
+int clb_prior_create(clb_searcher* s, const float* values, int64_t n, clb_prior** out) {
+    PriorPtr p(nullptr, clb_prior_destroy);
+    CLB_TRY(prior_args(s, values, n, out));
+    float max_abs = 0.f;            // finiteness and the maximum on the host, before anything is allocated
+    for (int64_t i = 0; i < n; ++i) {
+        if (!std::isfinite(values[i])) return bad_prior_value(s, i);
+        max_abs = std::max(max_abs, std::fabs(values[i]));
+    }
+    CLB_TRY(prior_alloc(s, n, p));
+    p->max_abs = max_abs;
+    if (n > 0) {       // the library never retains a host pointer
+        CLB_HIP(hipMemcpyAsync(p->values.p, values, sizeof(float) * n, hipMemcpyHostToDevice, s->stream));
+        CLB_HIP(hipStreamSynchronize(s->stream));
+    }
+    *out = p.release();
+    return CLB_OK;
+}
+
+int clb_prior_create_device(clb_searcher* s, const float* d_values, int64_t n, clb_prior** out) {
+    PriorPtr p(nullptr, clb_prior_destroy);
+    CLB_TRY(prior_args(s, d_values, n, out));
+    CLB_TRY(prior_alloc(s, n, p));
+    if (n > 0) {
+        CLB_HIP(hipDeviceSynchronize());      // whatever wrote the caller's device array
+        const hipStream_t st = s->stream;
+        CLB_HIP(hipMemcpyAsync(p->values.p, d_values, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
+        // first non-finite value and max |value| on the device, one read-back
+        DevBuf d_res;
+        const unsigned long long init[2] = {(unsigned long long)n, 0ull};
+        unsigned long long res[2] = {0ull, 0ull};
+        CLB_TRY(upload(d_res, init, sizeof init, st));
+        hipLaunchKernelGGL(prior_check_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(1024, (n + 255) / 256))), dim3(256),
+                           0, st, (const float*)p->values.as<float>(), n, d_res.as<unsigned long long>());
+        CLB_HIP(hipMemcpyAsync(res, d_res.p, sizeof res, hipMemcpyDeviceToHost, st));
+        CLB_HIP(hipStreamSynchronize(st));
+        CLB_HIP(hipGetLastError());
+        if (res[0] < (unsigned long long)n) return bad_prior_value(s, (int64_t)res[0]);
+        const uint32_t bits = (uint32_t)res[1];
+        memcpy(&p->max_abs, &bits, sizeof bits);
+    }
+    *out = p.release();
+    return CLB_OK;
+}
+
+float clb_prior_max_abs(const clb_prior* p) { return p ? p->max_abs : 0.f; }
+
+int clb_prior_destroy(clb_prior* p) {
+    if (!p) return CLB_OK;
+    (void)hipSetDevice(p->device);
+    delete p;
+    return CLB_OK;
 }
 
 // ---- clb_grouping -------------------------------------------------------------------------------------------------

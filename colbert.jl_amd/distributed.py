@@ -242,12 +242,13 @@ class DeviceSearch:
         `capture` again (it runs the sizing pass first), or go through `replay`."""
         return self.generation != self.s.generation
 
-    def replay(self, graph, Qstatic, filters=None, scope="candidates", grouping=None, per_group=None):
+    def replay(self, graph, Qstatic, filters=None, scope="candidates", grouping=None, per_group=None, prior=None,
+               prior_weight=1.0):
         """`graph.replay()` for a graph `capture` returned, made safe against appends: when the searcher has grown since
         the capture, the sizing pass runs again and the search is captured anew before anything is replayed.  Returns the
         graph that was replayed (keep it for the next call)."""
         if self.graph_is_stale():
-            graph = self.capture(Qstatic, filters, scope, grouping, per_group)
+            graph = self.capture(Qstatic, filters, scope, grouping, per_group, prior, prior_weight)
         graph.replay()
         return graph
 
@@ -363,7 +364,7 @@ class DeviceSearch:
                                             C.c_void_p(st)))
         return self.out_p, self.out_s
 
-    def capture(self, Qstatic, filters=None, scope="candidates", grouping=None, per_group=None):
+    def capture(self, Qstatic, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0):
         """A HIP graph of one search over the STATIC query buffer `Qstatic` (B, T, dim): the library enqueues nothing but
         kernels and memsets on the stream it is handed, so the nine launches of a search can be captured once and
         replayed -- write the next queries into `Qstatic` (e.g. let the encoder write there), `graph.replay()`, read
@@ -373,7 +374,8 @@ class DeviceSearch:
         launches, the replay is faster (0.259 against 0.318 ms).  The
         search runs once on a side stream first, so that the workspace is sized outside the capture.
         `filters` / `scope` / `grouping` / `per_group` as in __call__: the graph holds the filters' and the grouping's device
-        addresses -- keep them open while it is replayed; with `per_group` the results are in `hit_p` / `hit_s`."""
+        addresses -- keep them open while it is replayed; with `per_group` the results are in `hit_p` / `hit_s`.  `prior` /
+        `prior_weight` likewise: the graph holds the prior's device address and the weight."""
         import torch
         self._check_queries(Qstatic)
         self.generation = self.s.generation
@@ -381,14 +383,14 @@ class DeviceSearch:
         side = torch.cuda.Stream(self.dev)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            self(Qstatic, filters, scope, grouping, per_group)
+            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight)
         cur.wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self(Qstatic, filters, scope, grouping, per_group)
+            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight)
         return graph
 
-    def __call__(self, Qdev, filters=None, scope="candidates", grouping=None, per_group=None):
+    def __call__(self, Qdev, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0):
         """Qdev: torch float32 tensor holding B queries laid out (B, T, dim) contiguous == Julia (dim, T, B).
         `filters`: one PassageFilter or a sequence of B entries (None = unfiltered), `scope` "candidates" / "all"
         (Searcher.search_batch); `ncand` then holds the counts after the filter.
@@ -396,10 +398,22 @@ class DeviceSearch:
         results padded with pid 0 / -inf, `ncand` the candidate groups.
         `per_group` (an integer m, 1..16; needs `grouping`): returns `hit_p` / `hit_s`, (B, k, m) tensors == Julia (m, k, B)
         -- the m best candidate passages of every group, best first, padded with pid 0 / -inf
-        (clb_search_batch_grouped_hits_device_slot); `out_p` / `out_s` are not written."""
+        (clb_search_batch_grouped_hits_device_slot); `out_p` / `out_s` are not written.
+        `prior` (one PassagePrior for the batch) with `prior_weight`: rank by score + prior_weight * value
+        (Searcher.search_batch, clb_search_batch_prior_device_slot); not with `per_group`."""
         import torch
         self._check_queries(Qdev)
         st = torch.cuda.current_stream(self.dev).cuda_stream
+        if prior is not None:
+            from .searcher import _prior_weight, _scope_code
+            w = _prior_weight(prior, prior_weight, per_group)
+            check(lib().clb_search_batch_prior_device_slot(
+                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
+                None if filters is None else self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)),
+                None if grouping is None else self.s._grouping_handle(grouping), prior._h, C.c_float(w),
+                C.c_void_p(self.out_p.data_ptr()), C.c_void_p(self.out_s.data_ptr()), C.c_void_p(self.ncand.data_ptr()),
+                C.c_void_p(st)))
+            return self.out_p, self.out_s
         if per_group is not None:
             from .searcher import _per_group, _scope_code
             m = _per_group(per_group, grouping)

@@ -109,6 +109,58 @@ class PassageGrouping:
         return self.count
 
 
+FLT_MAX = float(np.finfo(np.float32).max)
+
+
+class PassagePrior:
+    """One finite fp32 value per passage resident in HBM (clb_prior, include/colbert_hip.h): made once by
+    `Searcher.make_prior`, reused over any number of searches of that searcher (`prior=`, `prior_weight=`: rank by
+    MaxSim + prior_weight * value).  Immutable; valid across `remove_passages` and `update_*`, not across an append (make
+    another).  Keep it alive while a search that uses it may still be running (or a graph that captured it may be
+    replayed).  `max_abs`: the largest |value|; `len()`: the number of values."""
+
+    def __init__(self, searcher: "Searcher", handle, n: int, max_abs: float):
+        self.searcher, self._h, self._n, self.max_abs = searcher, handle, int(n), float(max_abs)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().clb_prior_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self._n
+
+
+def _prior_weight(prior, prior_weight, per_group) -> float:
+    """The `prior=` / `prior_weight=` of a search call, checked on the host -> the weight as the float the C ABI takes."""
+    from ._lib import ArgumentError, Unsupported
+    if per_group is not None:
+        raise Unsupported("per_group together with a prior is not supported: the hits of a grouped search take no prior")
+    if not isinstance(prior, PassagePrior) or not prior._h:
+        raise ColBERTError("prior is not an open PassagePrior")
+    if isinstance(prior_weight, bool) or not isinstance(prior_weight, (int, float, np.integer, np.floating)):
+        raise ArgumentError(f"prior_weight must be a finite number, got {prior_weight!r}")
+    w = float(prior_weight)
+    with np.errstate(over="ignore"):
+        if not np.isfinite(np.float32(w)):
+            raise ArgumentError(f"prior_weight must be a finite fp32 number, got {prior_weight!r}")
+    if not abs(float(np.float32(w))) * prior.max_abs < FLT_MAX:
+        raise ArgumentError(f"prior_weight {w!r} times the prior's largest |value| {prior.max_abs!r} is not below FLT_MAX")
+    return w
+
+
 class Searcher:
     """struct Searcher (searching.jl:1-16).  Fields that the reference holds as arrays live in HBM
     behind `self._h`; the shapes/meta are kept for introspection."""
@@ -481,9 +533,39 @@ class Searcher:
             raise ColBERTError("grouping is not an open PassageGrouping")
         return grouping._h
 
+    # -- priors -----------------------------------------------------------------------------------
+    def make_prior(self, values) -> PassagePrior:
+        """A resident per-passage score term for `prior=` of the search calls: `values`, one finite number per passage
+        (`num_docs` entries, entry i = local passage i + 1) as a numpy array (converted to float32) or a contiguous float32
+        CUDA tensor on this searcher's device (clb_prior_create_device: checked on the device).  A wrong length or a value
+        that is not finite in fp32 is an ArgumentError, naming the first offending passage."""
+        from ._lib import ArgumentError
+        h = C.c_void_p()
+        if hasattr(values, "data_ptr"):
+            import torch
+            if not (values.is_cuda and values.is_contiguous() and values.device.index == self.device
+                    and values.dtype == torch.float32 and values.dim() == 1):
+                raise ArgumentError("a device prior must be a contiguous float32 CUDA vector on the searcher's device")
+            if values.numel() != self.num_docs:
+                raise ArgumentError(f"a prior holds one value per passage: {values.numel()} values, num_docs={self.num_docs}")
+            torch.cuda.current_stream(values.device).synchronize()
+            check(lib().clb_prior_create_device(self._h, C.c_void_p(values.data_ptr()), i64(values.numel()), C.byref(h)))
+            n = values.numel()
+        else:
+            with np.errstate(over="ignore", invalid="ignore"):
+                v = np.ascontiguousarray(np.asarray(values), dtype=np.float32)
+            if v.ndim != 1 or v.size != self.num_docs:
+                raise ArgumentError(f"a prior holds one value per passage: shape {v.shape}, num_docs={self.num_docs}")
+            bad = np.nonzero(~np.isfinite(v))[0]
+            if bad.size:
+                raise ArgumentError(f"the prior of passage {self.pid_offset + int(bad[0]) + 1} is not a finite number")
+            check(lib().clb_prior_create(self._h, fptr(v), i64(v.size), C.byref(h)))
+            n = v.size
+        return PassagePrior(self, h, n, lib().clb_prior_max_abs(h))
+
     # -- search -----------------------------------------------------------------------------------
     def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates", grouping=None,
-                          per_group=None):
+                          per_group=None, prior=None, prior_weight=1.0):
         """search() after encode_queries (searching.jl:102-127).  Q: (dim, T) Float32.
         Returns (pids Int64[k] 1-based, scores Float32[k]).
         `filter` (a PassageFilter of this searcher): search among its passages only -- scope "candidates": the query's
@@ -494,15 +576,17 @@ class Searcher:
         score; `grouping.groups_of(pids)` gives the groups); last_num_candidates then counts the candidate groups, and fewer
         than k of them raise BoundsError as fewer than k candidates do without a grouping (never with a filter).
         `per_group` (an integer m, 1..16, with `grouping`): pids and scores are (m, k) -- column j the m best candidate
-        passages of the j-th group, best first, padded with pid 0 / -Inf (Searcher.search_batch)."""
+        passages of the j-th group, best first, padded with pid 0 / -Inf (Searcher.search_batch).
+        `prior` (a PassagePrior of this searcher) with `prior_weight`: rank by score + prior_weight * value and return that
+        sum as the score (Searcher.search_batch); short results as without a prior."""
         q = colmajor(Q, np.float32)
         if q.ndim != 2 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T)")
         _scope_code(scope)
-        if filter is not None or grouping is not None or per_group is not None:
+        if filter is not None or grouping is not None or per_group is not None or prior is not None:
             p, s, n = self.search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe,
                                         filters=None if filter is None else [filter], scope=scope, grouping=grouping,
-                                        per_group=per_group)
+                                        per_group=per_group, prior=prior, prior_weight=prior_weight)
             self.last_num_candidates = int(n[0])
             return np.asfortranarray(p[..., 0]), np.asfortranarray(s[..., 0])
         pids = np.zeros(k, dtype=np.int64); scores = np.zeros(k, dtype=np.float32)
@@ -513,7 +597,7 @@ class Searcher:
         return pids, scores
 
     def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
-                     scope="candidates", grouping=None, per_group=None):
+                     scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0):
         """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B]).
         `filters`: one PassageFilter for every query, or a sequence of B entries (None = that query is unfiltered); with
         filters the results are always padded (pid 0 / -Inf past n_candidates[b], the count AFTER the filter) and `scope`
@@ -523,12 +607,27 @@ class Searcher:
         `per_group` (an integer m, 1..16; needs `grouping`): pids and scores are (m, k, B) -- [:, j, b] the m best CANDIDATE
         passages of query b's j-th group, score descending, the lower pid first among equal scores, padded with pid 0 / -Inf
         when the group has fewer (clb_search_batch_grouped_hits); row 0 is what the call returns without per_group, and the
-        groups, their order and n_candidates are unchanged."""
+        groups, their order and n_candidates are unchanged.
+        `prior`: one PassagePrior for the whole batch, with one finite `prior_weight` -- every candidate passage p (after any
+        filter) is ranked by E = fl32(score + fl32(prior_weight * value[p])), the lower pid first among equal E, and the
+        scores returned are E; with `grouping` a document is represented by its candidate with the largest E.  The candidates,
+        n_candidates and short results are those of the call without a prior.  Not with `per_group` (Unsupported)."""
         q = colmajor(Q, np.float32)
         if q.ndim != 3 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T, B)")
         B = q.shape[2]
         code = _scope_code(scope)
+        if prior is not None:
+            w = _prior_weight(prior, prior_weight, per_group)
+            handles = None if filters is None else self._filter_handles(filters, B)
+            pids = np.zeros((k, B), dtype=np.int64, order="F"); scores = np.zeros((k, B), dtype=np.float32, order="F")
+            ncand = np.zeros(B, dtype=np.int64)
+            check(lib().clb_search_batch_prior(self._h, fptr(q), i64(q.shape[1]), i64(B), i64(nprobe or self.config.nprobe), i64(k),
+                                               handles, C.c_int(code),
+                                               None if grouping is None else self._grouping_handle(grouping), prior._h,
+                                               C.c_float(w), C.c_int(1 if (pad_short or filters is not None) else 0),
+                                               fptr(pids), fptr(scores), fptr(ncand)))
+            return pids, scores, ncand
         if per_group is not None:
             m = _per_group(per_group, grouping)
             handles = None if filters is None else self._filter_handles(filters, B)
@@ -577,15 +676,17 @@ class Searcher:
         return {"pids": pids[:m].copy(), "approx": ap[:m].copy(), "exact": ex[:m].copy(), "tau": tau.value,
                 "eps": eps.value, "n_rescore": nr.value}
 
-    def search(self, query: str, k: int, *, filter=None, scope="candidates", grouping=None, per_group=None):
-        """search(searcher, query::String, k) (searching.jl:93-128); `filter` / `scope` / `grouping` / `per_group` as in
-        search_embeddings."""
+    def search(self, query: str, k: int, *, filter=None, scope="candidates", grouping=None, per_group=None, prior=None,
+               prior_weight=1.0):
+        """search(searcher, query::String, k) (searching.jl:93-128); `filter` / `scope` / `grouping` / `per_group` / `prior` /
+        `prior_weight` as in search_embeddings."""
         _scope_code(scope)
         if self.encoder is None:
             raise ColBERTError("no query encoder attached: pass encoder=... or use search_embeddings(Q, k)")
         Q = self.encoder.encode_queries([query])
         assert Q.shape[2] == 1 and Q.shape[1] == self.config.query_maxlen, Q.shape
-        return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope, grouping=grouping, per_group=per_group)
+        return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope, grouping=grouping, per_group=per_group,
+                                      prior=prior, prior_weight=prior_weight)
 
     def text_search(self, k: int, nprobe: Optional[int] = None, graph: bool = True) -> "TextSearch":
         """A session for repeated `search(searcher, query::String, k)` calls with everything after the tokenizer on the
@@ -804,10 +905,17 @@ class TextSearch:
         self._many = None
 
 
-def search(searcher: Searcher, query, k: int, *, filter=None, scope="candidates", grouping=None, per_group=None):
+def search(searcher: Searcher, query, k: int, *, filter=None, scope="candidates", grouping=None, per_group=None, prior=None,
+           prior_weight=1.0):
     """The reference's exported `search` (src/ColBERT.jl:40).  `query` may be a string (needs an
-    encoder) or a (dim, T) Float32 matrix of query embeddings.  `filter` / `scope` / `grouping` / `per_group`:
-    Searcher.search_embeddings."""
+    encoder) or a (dim, T) Float32 matrix of query embeddings.  `filter` / `scope` / `grouping` / `per_group` / `prior` /
+    `prior_weight`: Searcher.search_embeddings."""
+    if prior is None and prior_weight == 1.0:      # (a ShardedSearcher takes no prior: it is not handed the keywords)
+        if isinstance(query, str):
+            return searcher.search(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group)
+        return searcher.search_embeddings(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group)
     if isinstance(query, str):
-        return searcher.search(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group)
-    return searcher.search_embeddings(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group)
+        return searcher.search(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
+                               prior_weight=prior_weight)
+    return searcher.search_embeddings(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
+                                      prior_weight=prior_weight)

@@ -396,6 +396,56 @@ int clb_search_batch_grouped_hits_device_slot(clb_searcher* s, int slot, const f
                                               float* d_out_scores, int64_t* d_n_cand, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Score priors: rank by MaxSim plus a resident per-passage term (no counterpart in the reference; the rank_feature /
+ * function_score of Elasticsearch, a first-phase expression over an attribute in Vespa): recency, popularity, a quality
+ * score, a tenant's boost.  A clb_prior holds one FINITE fp32 value per local passage -- exactly n_docs entries, entry i =
+ * local passage i (4 MB per million passages).  A non-finite value is CLB_EARGUMENT, naming the first offending passage;
+ * creation records max |value| (clb_prior_max_abs).  clb_prior_create checks on the host before anything is allocated;
+ * clb_prior_create_device takes the values from device memory (of the searcher's device) and checks them there, with one
+ * read-back.
+ *
+ * A search call takes at most ONE prior and one finite fp32 `weight` for the whole batch.  For every candidate passage p of
+ * a query (after any filter, in either scope), with e(p) the fp32 MaxSim score the call returns without a prior:
+ *     pi(p) = fl32(weight * value[p])          one rounded multiply
+ *     E(p)  = fl32(e(p) + pi(p))               one rounded add, never contracted into an fma
+ * The result is the first k candidates ordered by E descending, the lower pid first among equal E, and the returned scores
+ * are E, bit for bit.  n_cand, the padding of short results (pid 0 / -Inf) and pad_short behave as without a prior, and the
+ * candidate set is unchanged: a prior never makes a passage a candidate.  With a grouping the representative of a group is
+ * its candidate passage with the largest E (lower pid first) and the groups are ordered by that value.  In the two-pass
+ * mode the cut moves with the prior: a passage that only the prior lifts into the top k is re-scored.
+ * A weight that is not finite, or with |weight| * max|value| not below FLT_MAX, is CLB_EARGUMENT (pi is always finite).
+ *
+ * Like a grouping, a prior is immutable, bound to the searcher it was made for and to its n_docs: it stays valid over
+ * clb_searcher_remove and clb_searcher_update, one made before an append is refused ("prior made before an append; make
+ * another"), one made for another searcher is refused (both CLB_EARGUMENT).  It MUST outlive every call that uses it,
+ * including calls still enqueued on a stream or captured in a graph; it may be destroyed before or after its searcher.
+ * Creation synchronises; searching with it does not.  The hits of a grouped search (clb_search_batch_grouped_hits*) take no
+ * prior -- their extended list is built from approximate MaxSim scores; the Python driver answers `per_group` together with a
+ * prior with Unsupported, naming both -- nor do the phase calls of a shard group.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct clb_prior clb_prior;
+int clb_prior_create(clb_searcher* s, const float* values, int64_t n, clb_prior** out);
+int clb_prior_create_device(clb_searcher* s, const float* d_values, int64_t n, clb_prior** out);
+/* max |value| (a host value, fixed at creation); 0 for a null handle */
+float clb_prior_max_abs(const clb_prior* p);
+/* a null handle is CLB_OK, like clb_filter_destroy */
+int clb_prior_destroy(clb_prior* p);
+/* clb_search_batch_grouped with a prior: `filters` / `scope` / `grouping` / `pad_short` as there (NULL: none).
+ * prior == NULL launches exactly what clb_search_batch_grouped launches (weight is then ignored). */
+int clb_search_batch_prior(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                           const clb_filter* const* filters, int scope, const clb_grouping* grouping, const clb_prior* prior,
+                           float weight, int pad_short, int64_t* out_pids, float* out_scores, int64_t* n_cand);
+/* clb_search_batch_grouped_device_slot with a prior: stream-ordered, no host synchronisation; after the slot's first call
+ * with a prior it allocates nothing (the first one grows the slot by two floats per query: the boosted threshold and the
+ * largest boosted score).  Capturable in a HIP graph under the rule of the filtered search: the graph holds the prior's
+ * device address and the weight, and a call that grows the workspace makes a captured graph stale.  prior == NULL launches
+ * exactly what clb_search_batch_grouped_device_slot launches. */
+int clb_search_batch_prior_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                       int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
+                                       const clb_prior* prior, float weight, int64_t* d_out_pids, float* d_out_scores,
+                                       int64_t* d_n_cand, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Grouped search across a shard group.  Every shard holds a clb_grouping made from ITS slice of the group ids (a dense
  * local index per local passage, as ever) and the caller passes `group_base`: the GLOBAL dense index of the group of the
  * shard's first passage, so that the global index of local passage p is group_base + index[p].  (The host has the whole id
