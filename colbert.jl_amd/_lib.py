@@ -133,6 +133,15 @@ def lib() -> C.CDLL:
             l.clb_search_batch_prior_device_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                              C.c_int64, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p,
                                                              C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(l, "clb_search_batch_after"):               # (absent from a COLBERT_HIP_LIB build of an earlier commit)
+            l.clb_search_batch_after.restype = C.c_int
+            l.clb_search_batch_after.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                                 C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
+            l.clb_search_batch_after_device_slot.restype = C.c_int
+            l.clb_search_batch_after_device_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                                             C.c_int64, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p,
+                                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.clb_searcher_generation.restype = C.c_int64
         l.clb_searcher_num_docs.restype = C.c_int64
         l.clb_searcher_num_embeddings.restype = C.c_int64

@@ -9,6 +9,7 @@
 #include <numeric>
 
 #include "approx_kernels.hpp"
+#include "after_kernels.hpp"
 #include "generic_kernels.hpp"
 #include "group_kernels.hpp"
 #include "index_change_kernels.hpp"
@@ -125,6 +126,10 @@ struct Workspace {
     // selection (prior_tau[b]) and the largest boosted approximate score by magnitude (prior_tau[Bcap + b])
     bool prior = false;
     DevBuf prior_tau;
+    // search after a cursor (after_kernels.hpp), sized once a call has passed one: the slots after_filter_kernel keeps and
+    // their number, the threshold of after_cut_kernel, and the host route's copy of the cursors
+    bool after = false;
+    DevBuf after_list, after_n, after_tau, after_cur_s, after_cur_p;
     DevBuf g_cells, g_keys, g_keys2, g_vals, g_vals2, g_scratch, g_sort_tmp;   // general-shape path (generic_kernels.hpp)
 };
 
@@ -199,6 +204,9 @@ struct Batch {
     // sub-batch launches exactly what it launches without one
     const clb_prior* prior = nullptr;
     float prior_weight = 1.f;
+    // search after a cursor: the sub-batch's cursors on the device, [B] each; nullptr: none, and the sub-batch launches
+    // exactly what it launches without them
+    const float* d_after_s = nullptr; const int64_t* d_after_p = nullptr;
     bool stats_keep = false;    // the 2nd, 3rd ... sub-batch of one call: the work counters accumulate over the call
     int phase = 0, n_shards = 0;    // two-phase sharded search (run_search)
     float* d_local_top = nullptr; const float* d_all_top = nullptr;
@@ -278,10 +286,10 @@ int next_pow2(int x) {
 // filt_count: the largest filter population of a CLB_FILTER_ALL call (0 otherwise) -- such a query's candidates are its
 // filter's passages, however few the IVF lists would give
 int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_t nprobe, int64_t k, size_t filt_count,
-                           bool grouped, int64_t per_group, bool prior) {
+                           bool grouped, int64_t per_group, bool prior, bool after) {
     const int64_t t_tuned = T <= 128 ? T : 0;       // queries of up to 128 tokens take the tuned (or batched general) kernels
     if (B <= w.Bcap && T <= w.Tcap && t_tuned <= w.Ttuned && nprobe <= w.npcap && k <= w.kcap && filt_count <= w.filt_cap &&
-        (!grouped || w.grouped) && per_group <= w.mcap && (!prior || w.prior))
+        (!grouped || w.grouped) && per_group <= w.mcap && (!prior || w.prior) && (!after || w.after))
         return CLB_OK;
     CLB_HIP(hipDeviceSynchronize());       // buffers may be in use on any of the caller's streams
     B = std::max(B, w.Bcap); T = std::max(T, w.Tcap);
@@ -370,6 +378,14 @@ int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, 
         CLB_TRY(w.prior_tau.ensure(sizeof(float) * 2 * B));
         w.prior = true;
     }
+    if (after || w.after) {         // ... and one that has searched after a cursor, these
+        CLB_TRY(w.after_list.ensure(sizeof(int) * B * w.cand_cap));
+        CLB_TRY(w.after_n.ensure(sizeof(int) * B));
+        CLB_TRY(w.after_tau.ensure(sizeof(float) * B));
+        CLB_TRY(w.after_cur_s.ensure(sizeof(float) * B));
+        CLB_TRY(w.after_cur_p.ensure(sizeof(int64_t) * B));
+        w.after = true;
+    }
     w.Bcap = B; w.Tcap = T; w.Ttuned = Ttuned; w.npcap = nprobe; w.kcap = k; w.mcap = per_group;
     w.filt_cap = std::max(w.filt_cap, filt_count);
     CLB_HIP(hipStreamSynchronize(s->stream));
@@ -377,8 +393,8 @@ int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, 
 }
 
 int ensure_workspace(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_t nprobe, int64_t k, size_t filt_count = 0,
-                     bool grouped = false, int64_t per_group = 0, bool prior = false) {
-    const int rc = ensure_workspace_sized(s, w, B, T, nprobe, k, filt_count, grouped, per_group, prior);
+                     bool grouped = false, int64_t per_group = 0, bool prior = false, bool after = false) {
+    const int rc = ensure_workspace_sized(s, w, B, T, nprobe, k, filt_count, grouped, per_group, prior, after);
     if (rc) {
         w.Bcap = 0;       // some buffers may have grown and others not: the next call sizes all of them again
         // a candidate set the size of a filter that does not fit is this call's own request, not a fault of the device
@@ -720,10 +736,27 @@ void launch_boost(Workspace& w, hipStream_t st, const Batch& q, int b0, int n, c
                        q.prior->values.as<float>(), q.prior_weight, w.cand_cap, mabs ? mabs + b0 : nullptr);
 }
 
+// A2 for queries b0 .. b0 + n - 1 of a call with cursors (after_filter_kernel): of the listed slots (list / nlist) or, with
+// list == nullptr, of all candidates, those after the query's cursor go to the slot's after_list / after_n, which the top-k
+// forms then rank.  The cursor arrays of q belong to the sub-batch, as list / nlist do.
+void launch_after(const clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int n, const int* list,
+                  const int* nlist) {
+    hipLaunchKernelGGL(after_filter_kernel, dim3(n), dim3(1024), 0, st, w.scores.as<float>() + (size_t)b0 * w.cand_cap,
+                       w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap, w.ncand.as<int>() + b0,
+                       list ? list + (size_t)b0 * w.cand_cap : nullptr, list ? nlist + b0 : nullptr, q.d_after_s + b0,
+                       q.d_after_p + b0, w.cand_cap, s->pid_offset, w.after_list.as<int>() + (size_t)b0 * w.cand_cap,
+                       w.after_n.as<int>() + b0);
+}
+
 // S7 of the general-shape path for queries b0 .. b0 + n - 1, the exact scores of all their candidates in place (with a
-// prior: boosted first) -- with a grouping: one collapse, then the top-k forms rank its list
+// prior: boosted first; with cursors: the candidates after them) -- with a grouping: one collapse, then the top-k forms
+// rank its list
 int topk_of(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int n) {
     launch_boost(w, st, q, b0, n, nullptr, nullptr, nullptr);
+    if (q.d_after_s) {
+        launch_after(s, w, st, q, b0, n, nullptr, nullptr);
+        return launch_topk(s, w, st, q, b0, n, w.after_list.as<int>(), w.after_n.as<int>(), 0);
+    }
     if (!q.grp) return launch_topk(s, w, st, q, b0, n, nullptr, nullptr, 0);
     launch_collapse(w, st, q, b0, n, nullptr, nullptr, w.grp_list.as<int>(), w.grp_n.as<int>());
     CLB_TRY(launch_topk(s, w, st, q, b0, n, w.grp_list.as<int>(), w.grp_n.as<int>(), 0));
@@ -921,6 +954,17 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
                                    dQ, T, ac, w.have_range ? (const float4*)w.tscale.as<float4>() : (const float4*)nullptr,
                                    w.cell8 ? 1 : 0, ptau);
                 CLB_TRY(launch_select(s, w, st, q, (const float*)ptau));
+            } else if (q.d_after_s) {
+                // with cursors (phase 0 only): the cut sits at the k-th largest approximate score of the candidates that are
+                // SURELY after the cursor, and those surely before it leave the selection (after_cut_kernel)
+                Timed t(s, KID_SELECT, st);
+                ApproxConsts ac = s->approx_consts;
+                ac.dc_max = bound_dc(s, w);
+                hipLaunchKernelGGL(after_cut_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), k,
+                                   w.cand_cap, q.d_after_s, dQ, T, ac,
+                                   w.have_range ? (const float4*)w.tscale.as<float4>() : (const float4*)nullptr, w.cell8 ? 1 : 0,
+                                   w.after_tau.as<float>());
+                CLB_TRY(launch_select(s, w, st, q, (const float*)w.after_tau.as<float>()));
             } else {
                 Timed t(s, KID_SELECT, st);
                 if (q.grp && phase == 1) {
@@ -998,6 +1042,10 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
     const int* tnlist = nlist;
     auto collapse_exact = [&]() {
         launch_boost(w, st, q, 0, B, list, nlist, nullptr);     // with a prior: the exact scores become E = e + weight * value
+        if (q.d_after_s) {      // with cursors (never with a grouping): only what lies after them is ranked
+            launch_after(s, w, st, q, 0, B, list, nlist);
+            tlist = w.after_list.as<int>(); tnlist = w.after_n.as<int>();
+        }
         if (!q.grp) return;
         int* gl = list ? w.grp_list2.as<int>() : w.grp_list.as<int>();
         int* gn = list ? w.grp_n2.as<int>() : w.grp_n.as<int>();
@@ -1065,6 +1113,8 @@ int check_prior(const clb_searcher* s, const clb_prior* p, float weight) {
     return CLB_OK;
 }
 struct PriorArg { const clb_prior* p = nullptr; float weight = 1.f; };
+// the cursors of a call, one (score, pid) per query -- host arrays on the host route, device arrays on the device route -- or none
+struct AfterArg { const float* s = nullptr; const int64_t* p = nullptr; };
 
 // the grouping of a call (or nullptr): it must be this searcher's, made for the passages it holds now
 int check_grouping(const clb_searcher* s, const clb_grouping* g) {
@@ -1100,11 +1150,12 @@ int slot_workspace(clb_searcher* s, int slot, Workspace** w) {
 // run_one(b0, q): points q at the queries and outputs of the sub-batch that starts at query b0 and runs it.  q arrives with
 // the sub-batch's size, its slice of the handle array -- nullptr when none of its queries is filtered -- and stats_keep set
 // grp: the grouping of a grouped call (every sub-batch carries it) or nullptr; per_group: its hits per result (0: none);
-// prior: the prior and weight of a call with one (every sub-batch carries them) or none
+// prior: the prior and weight of a call with one (every sub-batch carries them) or none; after: the call has cursors -- run_one
+// points q at its sub-batch's (AfterArg)
 template <class RunOne>
 int for_sub_batches(clb_searcher* s, Workspace& w, int64_t T, int64_t B, int64_t nprobe, int64_t k,
                     const clb_filter* const* filters, int scope, const clb_grouping* grp, int64_t per_group, PriorArg prior,
-                    RunOne run_one) {
+                    bool after, RunOne run_one) {
     size_t filt_count = 0;
     CLB_TRY(check_filters(s, filters, B, scope, &filt_count));
     CLB_TRY(check_grouping(s, grp));
@@ -1113,7 +1164,7 @@ int for_sub_batches(clb_searcher* s, Workspace& w, int64_t T, int64_t B, int64_t
     w.grouped_done.valid = false;
     for (int64_t b0 = 0; b0 < B; b0 += kSubBatch) {
         Batch q = make_batch(nullptr, std::min<int64_t>(kSubBatch, B - b0), T, nprobe, k);
-        CLB_TRY(ensure_workspace(s, w, q.B, T, nprobe, k, filt_count, grp != nullptr, per_group, prior.p != nullptr));
+        CLB_TRY(ensure_workspace(s, w, q.B, T, nprobe, k, filt_count, grp != nullptr, per_group, prior.p != nullptr, after));
         q.grp = grp;
         q.prior = prior.p;
         q.prior_weight = prior.weight;
@@ -1926,13 +1977,15 @@ int clb_search_batch_device(clb_searcher* s, const float* d_Q, int64_t T, int64_
 static int search_batch_device_slot_impl(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
                                          int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grp,
                                          int64_t per_group /* hits per result, 0: none */, int64_t* d_out_pids,
-                                         float* d_out_scores, int64_t* d_n_cand, void* hip_stream, PriorArg prior = {}) {
+                                         float* d_out_scores, int64_t* d_n_cand, void* hip_stream, PriorArg prior = {},
+                                         AfterArg after = {}) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     Workspace* w = nullptr;
     CLB_TRY(slot_workspace(s, slot, &w));
     hipStream_t st = (hipStream_t)hip_stream;   // NULL = the HIP null stream, as for any HIP API
-    CLB_TRY(for_sub_batches(s, *w, T, B, nprobe, k, filters, scope, grp, per_group, prior, [&](int64_t b0, Batch& q) -> int {
+    CLB_TRY(for_sub_batches(s, *w, T, B, nprobe, k, filters, scope, grp, per_group, prior, after.s != nullptr, [&](int64_t b0, Batch& q) -> int {
         q.dQ = d_Q + (size_t)b0 * T * s->dim;
+        if (after.s) { q.d_after_s = after.s + b0; q.d_after_p = after.p + b0; }
         q.d_out_pids = per_group ? w->hit_p.as<int64_t>() : d_out_pids + (size_t)b0 * k;
         q.d_out_scores = per_group ? w->hit_s.as<float>() : d_out_scores + (size_t)b0 * k;
         q.d_hit_pids = d_out_pids + (size_t)b0 * k * per_group;
@@ -2130,7 +2183,7 @@ int clb_search_result_groups_slot(clb_searcher* s, int slot, const clb_grouping*
 static int search_batch_impl(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
                              const clb_filter* const* filters, int scope, const clb_grouping* grp,
                              int64_t per_group /* hits per result, 0: none */, int pad_short, int64_t* out_pids,
-                             float* out_scores, int64_t* n_cand, PriorArg prior = {}) {
+                             float* out_scores, int64_t* n_cand, PriorArg prior = {}, AfterArg after = {}) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     const int64_t km = k * std::max<int64_t>(per_group, 1);     // entries of one query's result
     Workspace* wp = nullptr;
@@ -2139,8 +2192,13 @@ static int search_batch_impl(clb_searcher* s, const float* Q, int64_t T, int64_t
     hipStream_t st = s->stream;
     std::vector<int> nc((size_t)B), fl((size_t)B);
     // the queries go up into the slot's own buffer and the results come back from it, sub-batch by sub-batch
-    CLB_TRY(for_sub_batches(s, w, T, B, nprobe, k, filters, scope, grp, per_group, prior, [&](int64_t b0, Batch& q) -> int {
+    CLB_TRY(for_sub_batches(s, w, T, B, nprobe, k, filters, scope, grp, per_group, prior, after.s != nullptr, [&](int64_t b0, Batch& q) -> int {
         CLB_HIP(hipMemcpyAsync(w.Qdev.p, Q + (size_t)b0 * T * s->dim, sizeof(float) * q.B * T * s->dim, hipMemcpyHostToDevice, st));
+        if (after.s) {      // the sub-batch's cursors go up beside its queries
+            CLB_HIP(hipMemcpyAsync(w.after_cur_s.p, after.s + b0, sizeof(float) * q.B, hipMemcpyHostToDevice, st));
+            CLB_HIP(hipMemcpyAsync(w.after_cur_p.p, after.p + b0, sizeof(int64_t) * q.B, hipMemcpyHostToDevice, st));
+            q.d_after_s = w.after_cur_s.as<float>(); q.d_after_p = w.after_cur_p.as<int64_t>();
+        }
         q.dQ = w.Qdev.as<float>();
         q.d_out_pids = per_group ? w.hit_p.as<int64_t>() : w.outp.as<int64_t>();
         q.d_out_scores = per_group ? w.hit_s.as<float>() : w.outs.as<float>();
@@ -2215,6 +2273,36 @@ int clb_search_batch_prior_device_slot(clb_searcher* s, int slot, const float* d
     CLB_TRY(check_prior_weight(prior, weight));
     return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, grouping, 0, d_out_pids, d_out_scores,
                                          d_n_cand, hip_stream, PriorArg{prior, weight});
+}
+
+// ---- search after a cursor ----------------------------------------------------------------------------------------
+// what both entry points check before anything else: the handle, the outputs, and that the cursor arrays come as a pair
+static int check_after_args(const clb_searcher* s, const void* after_scores, const void* after_pids, const void* out_pids,
+                            const void* out_scores) {
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    if (!out_pids || !out_scores) return fail(CLB_EARGUMENT, "out_pids / out_scores is null");
+    if ((after_scores == nullptr) != (after_pids == nullptr))
+        return fail(CLB_EARGUMENT, "after_scores and after_pids must both be given or both be null");
+    return CLB_OK;
+}
+
+int clb_search_batch_after(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                           const clb_filter* const* filters, int scope, const float* after_scores, const int64_t* after_pids,
+                           int64_t* out_pids, float* out_scores, int64_t* n_cand) {
+    CLB_TRY(check_after_args(s, after_scores, after_pids, out_pids, out_scores));
+    for (int64_t b = 0; after_scores && b < B; ++b)
+        if (std::isnan(after_scores[b])) return fail(CLB_EARGUMENT, "the cursor score of query %lld is NaN", (long long)b);
+    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, nullptr, 0, /*pad_short=*/1, out_pids, out_scores, n_cand,
+                             PriorArg{}, AfterArg{after_scores, after_pids});
+}
+
+int clb_search_batch_after_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                       int64_t k, const clb_filter* const* filters, int scope, const float* d_after_scores,
+                                       const int64_t* d_after_pids, int64_t* d_out_pids, float* d_out_scores,
+                                       int64_t* d_n_cand, void* hip_stream) {
+    CLB_TRY(check_after_args(s, d_after_scores, d_after_pids, d_out_pids, d_out_scores));
+    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, nullptr, 0, d_out_pids, d_out_scores,
+                                         d_n_cand, hip_stream, PriorArg{}, AfterArg{d_after_scores, d_after_pids});
 }
 
 using PriorPtr = std::unique_ptr<clb_prior, decltype(&clb_prior_destroy)>;

@@ -243,12 +243,13 @@ class DeviceSearch:
         return self.generation != self.s.generation
 
     def replay(self, graph, Qstatic, filters=None, scope="candidates", grouping=None, per_group=None, prior=None,
-               prior_weight=1.0):
+               prior_weight=1.0, after=None):
         """`graph.replay()` for a graph `capture` returned, made safe against appends: when the searcher has grown since
         the capture, the sizing pass runs again and the search is captured anew before anything is replayed.  Returns the
-        graph that was replayed (keep it for the next call)."""
+        graph that was replayed (keep it for the next call).  `after`: the cursor tensors the graph was captured with -- it
+        reads their CONTENTS at every replay."""
         if self.graph_is_stale():
-            graph = self.capture(Qstatic, filters, scope, grouping, per_group, prior, prior_weight)
+            graph = self.capture(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after)
         graph.replay()
         return graph
 
@@ -263,6 +264,19 @@ class DeviceSearch:
             raise ArgumentError(f"queries must be a contiguous float32 tensor of {self.B} x {self.T} x {int(self.s.dim)} "
                                 f"elements on {self.dev}, got {getattr(Qdev, 'dtype', type(Qdev))} "
                                 f"{tuple(getattr(Qdev, 'shape', ()))} on {getattr(Qdev, 'device', '?')}")
+
+    def _check_cursors(self, after):
+        """The cursor arrays go to the kernels as bare pointers, like the queries: a pair of contiguous tensors, float32[B] and
+        int64[B], on this device, or refused."""
+        import torch
+        from ._lib import ArgumentError
+        ok = isinstance(after, (tuple, list)) and len(after) == 2
+        for t, dtype in zip(after if ok else (), (torch.float32, torch.int64)):
+            ok = ok and (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == self.dev and t.is_contiguous()
+                         and t.dim() == 1 and t.numel() == self.B)
+        if not ok:
+            raise ArgumentError(f"after must be a pair of contiguous tensors on {self.dev}: scores float32[{self.B}] and pids "
+                                f"int64[{self.B}]")
 
     def _grouped_block(self):
         """The packed grouped result block of this shard (packed_grouped_bytes) and the views the grouped calls write into."""
@@ -364,7 +378,8 @@ class DeviceSearch:
                                             C.c_void_p(st)))
         return self.out_p, self.out_s
 
-    def capture(self, Qstatic, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0):
+    def capture(self, Qstatic, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0,
+                after=None):
         """A HIP graph of one search over the STATIC query buffer `Qstatic` (B, T, dim): the library enqueues nothing but
         kernels and memsets on the stream it is handed, so the nine launches of a search can be captured once and
         replayed -- write the next queries into `Qstatic` (e.g. let the encoder write there), `graph.replay()`, read
@@ -375,7 +390,9 @@ class DeviceSearch:
         search runs once on a side stream first, so that the workspace is sized outside the capture.
         `filters` / `scope` / `grouping` / `per_group` as in __call__: the graph holds the filters' and the grouping's device
         addresses -- keep them open while it is replayed; with `per_group` the results are in `hit_p` / `hit_s`.  `prior` /
-        `prior_weight` likewise: the graph holds the prior's device address and the weight."""
+        `prior_weight` likewise: the graph holds the prior's device address and the weight.  `after` (a pair of device
+        tensors, as in __call__): the graph holds their ADDRESSES, not their values -- to page, copy the last row of `out_s` /
+        `out_p` into them and replay."""
         import torch
         self._check_queries(Qstatic)
         self.generation = self.s.generation
@@ -383,14 +400,15 @@ class DeviceSearch:
         side = torch.cuda.Stream(self.dev)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight)
+            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after)
         cur.wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight)
+            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after)
         return graph
 
-    def __call__(self, Qdev, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0):
+    def __call__(self, Qdev, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0,
+                 after=None):
         """Qdev: torch float32 tensor holding B queries laid out (B, T, dim) contiguous == Julia (dim, T, B).
         `filters`: one PassageFilter or a sequence of B entries (None = unfiltered), `scope` "candidates" / "all"
         (Searcher.search_batch); `ncand` then holds the counts after the filter.
@@ -400,10 +418,23 @@ class DeviceSearch:
         -- the m best candidate passages of every group, best first, padded with pid 0 / -inf
         (clb_search_batch_grouped_hits_device_slot); `out_p` / `out_s` are not written.
         `prior` (one PassagePrior for the batch) with `prior_weight`: rank by score + prior_weight * value
-        (Searcher.search_batch, clb_search_batch_prior_device_slot); not with `per_group`."""
+        (Searcher.search_batch, clb_search_batch_prior_device_slot); not with `per_group`.
+        `after`: a pair of device tensors (scores float32[B], pids int64[B]) on the searcher's device, one cursor per query --
+        the next k results past it, always padded (Searcher.search_batch, clb_search_batch_after_device_slot); a NaN score
+        gives an empty page here.  Not with `grouping`, `per_group` or `prior`."""
         import torch
         self._check_queries(Qdev)
         st = torch.cuda.current_stream(self.dev).cuda_stream
+        if after is not None:
+            from .searcher import _after_keywords, _scope_code
+            _after_keywords(after, grouping, per_group, prior)
+            self._check_cursors(after)
+            check(lib().clb_search_batch_after_device_slot(
+                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
+                None if filters is None else self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)),
+                C.c_void_p(after[0].data_ptr()), C.c_void_p(after[1].data_ptr()), C.c_void_p(self.out_p.data_ptr()),
+                C.c_void_p(self.out_s.data_ptr()), C.c_void_p(self.ncand.data_ptr()), C.c_void_p(st)))
+            return self.out_p, self.out_s
         if prior is not None:
             from .searcher import _prior_weight, _scope_code
             w = _prior_weight(prior, prior_weight, per_group)

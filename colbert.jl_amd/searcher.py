@@ -161,6 +161,50 @@ def _prior_weight(prior, prior_weight, per_group) -> float:
     return w
 
 
+def _after_keywords(after, grouping, per_group, prior):
+    """The `after=` of a search call against the keywords it is not offered with."""
+    from ._lib import Unsupported
+    if after is None:
+        return
+    for name, value in (("grouping", grouping), ("per_group", per_group), ("prior", prior)):
+        if value is not None:
+            raise Unsupported(f"after together with {name} is not supported: a cursor continues the ranking of passages by MaxSim")
+
+
+def _after_arrays(after, B: int):
+    """`after=(scores[B], pids[B])` of Searcher.search_batch as the two host arrays the C ABI takes."""
+    from ._lib import ArgumentError
+    if not isinstance(after, (tuple, list)) or len(after) != 2:
+        raise ArgumentError("after must be a pair (scores, pids)")
+    try:
+        s = np.ascontiguousarray(after[0], dtype=np.float32).reshape(-1)
+        raw = np.asarray(after[1]).reshape(-1)
+        p = np.ascontiguousarray(raw, dtype=np.int64)
+    except (TypeError, ValueError, OverflowError) as e:
+        raise ArgumentError(f"after must be a pair (scores float32[{B}], pids int64[{B}]): {e}") from None
+    if raw.dtype.kind not in "iu" or (raw.size and raw.dtype.kind == "u" and int(raw.max()) > np.iinfo(np.int64).max):
+        raise ArgumentError(f"the cursor pids must be integers that fit int64, got dtype {raw.dtype}")
+    if s.size != B or p.size != B:
+        raise ArgumentError(f"after holds one cursor per query: {s.size} scores and {p.size} pids for {B} queries")
+    if np.isnan(s).any():
+        raise ArgumentError(f"the cursor score of query {int(np.nonzero(np.isnan(s))[0][0])} is NaN")
+    return s, p
+
+
+def next_cursor(pids, scores):
+    """The cursor that continues after a result: its last row, `(scores[k-1], pids[k-1])` -- per query for the (k, B) arrays of
+    `search_batch` (pass it as `after=`), a `(score, pid)` pair for the k-vectors of `search_embeddings` / `search`.  A padded
+    last row yields (-Inf, 0): the ranking is finished, and the page after it is empty."""
+    p, s = np.asarray(pids), np.asarray(scores, dtype=np.float32)
+    if p.shape != s.shape or p.ndim not in (1, 2) or p.shape[0] < 1:
+        raise ColBERTError(f"next_cursor takes the pids and scores of one result, got shapes {p.shape} and {s.shape}")
+    last_s, last_p = s[-1].copy(), p[-1].astype(np.int64)
+    if p.ndim == 1:
+        return (float("-inf"), 0) if last_p == 0 else (np.float32(last_s), int(last_p))
+    last_s[last_p == 0] = -np.inf
+    return last_s, last_p
+
+
 class Searcher:
     """struct Searcher (searching.jl:1-16).  Fields that the reference holds as arrays live in HBM
     behind `self._h`; the shapes/meta are kept for introspection."""
@@ -565,7 +609,7 @@ class Searcher:
 
     # -- search -----------------------------------------------------------------------------------
     def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates", grouping=None,
-                          per_group=None, prior=None, prior_weight=1.0):
+                          per_group=None, prior=None, prior_weight=1.0, after=None):
         """search() after encode_queries (searching.jl:102-127).  Q: (dim, T) Float32.
         Returns (pids Int64[k] 1-based, scores Float32[k]).
         `filter` (a PassageFilter of this searcher): search among its passages only -- scope "candidates": the query's
@@ -578,15 +622,23 @@ class Searcher:
         `per_group` (an integer m, 1..16, with `grouping`): pids and scores are (m, k) -- column j the m best candidate
         passages of the j-th group, best first, padded with pid 0 / -Inf (Searcher.search_batch).
         `prior` (a PassagePrior of this searcher) with `prior_weight`: rank by score + prior_weight * value and return that
-        sum as the score (Searcher.search_batch); short results as without a prior."""
+        sum as the score (Searcher.search_batch); short results as without a prior.
+        `after` (a pair (score, pid), e.g. `next_cursor` of the previous page): the next k results past that cursor, always
+        padded (Searcher.search_batch); not with `grouping`, `per_group` or `prior`."""
         q = colmajor(Q, np.float32)
         if q.ndim != 2 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T)")
         _scope_code(scope)
-        if filter is not None or grouping is not None or per_group is not None or prior is not None:
+        _after_keywords(after, grouping, per_group, prior)
+        if after is not None:
+            from ._lib import ArgumentError
+            if not isinstance(after, (tuple, list)) or len(after) != 2:
+                raise ArgumentError("after must be a pair (score, pid)")
+            after = ([after[0]], [after[1]])
+        if filter is not None or grouping is not None or per_group is not None or prior is not None or after is not None:
             p, s, n = self.search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe,
                                         filters=None if filter is None else [filter], scope=scope, grouping=grouping,
-                                        per_group=per_group, prior=prior, prior_weight=prior_weight)
+                                        per_group=per_group, prior=prior, prior_weight=prior_weight, after=after)
             self.last_num_candidates = int(n[0])
             return np.asfortranarray(p[..., 0]), np.asfortranarray(s[..., 0])
         pids = np.zeros(k, dtype=np.int64); scores = np.zeros(k, dtype=np.float32)
@@ -597,7 +649,7 @@ class Searcher:
         return pids, scores
 
     def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
-                     scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0):
+                     scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0, after=None):
         """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B]).
         `filters`: one PassageFilter for every query, or a sequence of B entries (None = that query is unfiltered); with
         filters the results are always padded (pid 0 / -Inf past n_candidates[b], the count AFTER the filter) and `scope`
@@ -611,12 +663,28 @@ class Searcher:
         `prior`: one PassagePrior for the whole batch, with one finite `prior_weight` -- every candidate passage p (after any
         filter) is ranked by E = fl32(score + fl32(prior_weight * value[p])), the lower pid first among equal E, and the
         scores returned are E; with `grouping` a document is represented by its candidate with the largest E.  The candidates,
-        n_candidates and short results are those of the call without a prior.  Not with `per_group` (Unsupported)."""
+        n_candidates and short results are those of the call without a prior.  Not with `per_group` (Unsupported).
+        `after`: a pair (scores float32[B], pids int64[B]) of cursors, one per query (clb_search_batch_after) -- query b returns
+        the first k of its candidates p (after any filter) with score < scores[b], or score == scores[b] and pid > pids[b], by
+        (score descending, pid ascending): what its ranking continues with.  `after=next_cursor(pids, scores)` of the previous
+        page walks the whole ranking in pieces of k, bit for bit.  A score of +Inf means no cursor for that query, -Inf an
+        empty page, NaN is ArgumentError.  The result is always padded (pid 0 / -Inf; a page of padding alone is the end) and
+        n_candidates is that of the call without cursors, the same on every page.  Composes with `filters` in both scopes;
+        not with `grouping`, `per_group` or `prior` (Unsupported)."""
         q = colmajor(Q, np.float32)
         if q.ndim != 3 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T, B)")
         B = q.shape[2]
         code = _scope_code(scope)
+        _after_keywords(after, grouping, per_group, prior)
+        if after is not None:
+            cs, cp = _after_arrays(after, B)
+            handles = None if filters is None else self._filter_handles(filters, B)
+            pids = np.zeros((k, B), dtype=np.int64, order="F"); scores = np.zeros((k, B), dtype=np.float32, order="F")
+            ncand = np.zeros(B, dtype=np.int64)
+            check(lib().clb_search_batch_after(self._h, fptr(q), i64(q.shape[1]), i64(B), i64(nprobe or self.config.nprobe), i64(k),
+                                               handles, C.c_int(code), fptr(cs), fptr(cp), fptr(pids), fptr(scores), fptr(ncand)))
+            return pids, scores, ncand
         if prior is not None:
             w = _prior_weight(prior, prior_weight, per_group)
             handles = None if filters is None else self._filter_handles(filters, B)
@@ -677,16 +745,17 @@ class Searcher:
                 "eps": eps.value, "n_rescore": nr.value}
 
     def search(self, query: str, k: int, *, filter=None, scope="candidates", grouping=None, per_group=None, prior=None,
-               prior_weight=1.0):
+               prior_weight=1.0, after=None):
         """search(searcher, query::String, k) (searching.jl:93-128); `filter` / `scope` / `grouping` / `per_group` / `prior` /
-        `prior_weight` as in search_embeddings."""
+        `prior_weight` / `after` as in search_embeddings."""
         _scope_code(scope)
+        _after_keywords(after, grouping, per_group, prior)
         if self.encoder is None:
             raise ColBERTError("no query encoder attached: pass encoder=... or use search_embeddings(Q, k)")
         Q = self.encoder.encode_queries([query])
         assert Q.shape[2] == 1 and Q.shape[1] == self.config.query_maxlen, Q.shape
         return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope, grouping=grouping, per_group=per_group,
-                                      prior=prior, prior_weight=prior_weight)
+                                      prior=prior, prior_weight=prior_weight, after=after)
 
     def text_search(self, k: int, nprobe: Optional[int] = None, graph: bool = True) -> "TextSearch":
         """A session for repeated `search(searcher, query::String, k)` calls with everything after the tokenizer on the
@@ -906,16 +975,17 @@ class TextSearch:
 
 
 def search(searcher: Searcher, query, k: int, *, filter=None, scope="candidates", grouping=None, per_group=None, prior=None,
-           prior_weight=1.0):
+           prior_weight=1.0, after=None):
     """The reference's exported `search` (src/ColBERT.jl:40).  `query` may be a string (needs an
     encoder) or a (dim, T) Float32 matrix of query embeddings.  `filter` / `scope` / `grouping` / `per_group` / `prior` /
-    `prior_weight`: Searcher.search_embeddings."""
+    `prior_weight` / `after`: Searcher.search_embeddings."""
+    more = {} if after is None else {"after": after}      # (a ShardedSearcher answers a cursor with Unsupported itself)
     if prior is None and prior_weight == 1.0:      # (a ShardedSearcher takes no prior: it is not handed the keywords)
         if isinstance(query, str):
-            return searcher.search(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group)
-        return searcher.search_embeddings(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group)
+            return searcher.search(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group, **more)
+        return searcher.search_embeddings(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group, **more)
     if isinstance(query, str):
         return searcher.search(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
-                               prior_weight=prior_weight)
+                               prior_weight=prior_weight, **more)
     return searcher.search_embeddings(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
-                                      prior_weight=prior_weight)
+                                      prior_weight=prior_weight, **more)

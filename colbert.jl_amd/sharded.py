@@ -428,7 +428,7 @@ class ShardedSearcher:
         return mp.cpu().numpy(), ms.cpu().numpy(), n.cpu().numpy()
 
     def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
-                     scope="candidates", protocol="auto", grouping=None, per_group=None):
+                     scope="candidates", protocol="auto", grouping=None, per_group=None, after=None):
         """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B]), GLOBAL pids, layouts and padding (pid 0 /
         -Inf) as `Searcher.search_batch`; n_candidates is the sum over the shards.  `filters`: one ShardedFilter or a sequence
         of B entries (None = that query is unfiltered); with filters the result is always padded.  Without, a query for which
@@ -439,8 +439,10 @@ class ShardedSearcher:
         its best passage (`grouping.groups_of(pids)` names them), exactly as `Searcher.search_batch(grouping=)` on the
         unsharded index does; n_candidates counts the candidate groups, a group that straddles shards once.  Composes with
         `filters` in both scopes, under every protocol.
-        `per_group`: anything but None raises Unsupported (the hits of a grouped search are a single handle's)."""
+        `per_group`: anything but None raises Unsupported (the hits of a grouped search are a single handle's), and so does
+        `after` (a cursor continues the ranking of a single handle)."""
         self._no_per_group(per_group)
+        self._no_after(after)
         q = colmajor(Q, np.float32)
         if q.ndim != 3 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T, B)")
@@ -473,11 +475,18 @@ class ShardedSearcher:
             raise Unsupported("per_group= (the best passages of every group) is not supported across a shard group: search "
                               "the unsharded Searcher, or the winners' passages with a filter and scope='all'")
 
+    @staticmethod
+    def _no_after(after):
+        if after is not None:
+            raise Unsupported("after= (search after a cursor) is not supported across a shard group: search the unsharded "
+                              "Searcher")
+
     def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates", protocol="auto",
-                          grouping=None, per_group=None):
+                          grouping=None, per_group=None, after=None):
         """One query, Q (dim, T) -> (pids Int64[k], scores Float32[k]) as `Searcher.search_embeddings`; the candidate count
         (with a grouping: the candidate groups) is left in `last_num_candidates`."""
         self._no_per_group(per_group)
+        self._no_after(after)
         q = colmajor(Q, np.float32)
         if q.ndim != 2 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T)")
@@ -487,9 +496,11 @@ class ShardedSearcher:
         self.last_num_candidates = int(n[0])
         return np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(s[:, 0])
 
-    def search(self, query: str, k: int, *, filter=None, scope="candidates", protocol="auto", grouping=None, per_group=None):
+    def search(self, query: str, k: int, *, filter=None, scope="candidates", protocol="auto", grouping=None, per_group=None,
+               after=None):
         """search(searcher, query::String, k) over the group, with the attached encoder."""
         self._no_per_group(per_group)
+        self._no_after(after)
         if self.encoder is None:
             raise ColBERTError("no query encoder attached: pass encoder=... or use search_embeddings(Q, k)")
         Q = self.encoder.encode_queries([query])

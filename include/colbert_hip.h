@@ -446,7 +446,51 @@ int clb_search_batch_prior_device_slot(clb_searcher* s, int slot, const float* d
                                        int64_t* d_n_cand, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Grouped search across a shard group.  Every shard holds a clb_grouping made from ITS slice of the group ids (a dense
+ * Search after a cursor: the next k results past a (score, pid), exactly (no counterpart in the reference; the search_after
+ * of Elasticsearch, a continuation token in Vespa).  A cursor is one pair (s*, p*) per query: s* an fp32 score, p* a GLOBAL
+ * 1-based pid (int64).  It need not be a result that was ever returned.  For a query whose candidates (after any filter, in
+ * either scope) have the exact fp32 MaxSim scores e(p),
+ *     after(p)  <=>  e(p) < s*   or   (e(p) == s* and pid(p) > p*)
+ * and the call returns the first k members of {p : after(p)} by (e descending, pid ascending), with their pids and fp32
+ * score bits: what the ranking of the call without a cursor continues with.
+ *   - Paging with the cursor (scores[k-1], pids[k-1]) of the previous page yields the ranking of all candidates cut into
+ *     pieces of k, bit for bit, runs of exactly equal scores that cross a page boundary included.
+ *   - s* = +Inf is "no cursor" for that query (p* is ignored): its result is that of the call without cursors, bit for bit.
+ *     A batch may mix queries with and without a cursor.
+ *   - s* = -Inf gives an empty page.  A NaN s* is CLB_EARGUMENT on the host entry point; on the device entry point, where
+ *     nothing can be raised, it gives an empty page.
+ *   - A page is always padded: entries past the last member are pid 0 / -Inf, and a short page is never CLB_EBOUNDS (the
+ *     last page is short by nature; a page of padding alone is the end marker).
+ *   - n_cand is what the call without cursors reports, the candidates after the filter, the same on every page.  The number
+ *     of candidates after the cursor is not reported: the two-pass mode does not know it.
+ *   - A cursor never changes the candidate set.
+ * In the two-pass mode the cut moves with the cursor: what is re-scored is the page and the
+ * candidates whose approximate score lies within three error bounds of its ends, whatever came before it -- a candidate that is
+ * certainly before the cursor is not re-scored.  Every k is served, above 16 384 by the full sort.
+ * Cursors compose with `filters` in both scopes.  They are not offered with a grouping, with hits or with a prior -- these
+ * entry points have no such parameters; the Python driver answers the combinations with Unsupported, naming both keywords --
+ * nor by the phase calls of a shard group.
+ *
+ * after_scores / after_pids: [B] each.  Both NULL: exactly clb_search_batch_filtered (its launches, its results); one NULL
+ * and one not is CLB_EARGUMENT.  The arguments -- a NULL handle or output, the pair, NaN -- are checked before any device
+ * work; the limits of the filtered calls apply (sub-batches of 64 queries).
+ * ---------------------------------------------------------------------------------------------- */
+int clb_search_batch_after(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                           const clb_filter* const* filters, int scope, const float* after_scores /* [B], host */,
+                           const int64_t* after_pids /* [B], host */, int64_t* out_pids, float* out_scores, int64_t* n_cand);
+/* clb_search_batch_filtered_device_slot with cursors in DEVICE memory (of the searcher's device): stream-ordered, no host
+ * synchronisation; after the slot's first call with cursors it allocates nothing (the first one grows the slot by 4 bytes
+ * per query and candidate of its capacity: the list of the slots after the cursor).  Capturable in a HIP graph under the
+ * rule of the filtered search; the graph holds the ADDRESSES of the cursor arrays, not their values -- paging under a graph
+ * is: copy the last row of the outputs into the cursor arrays, replay.  Both arrays NULL launches exactly what
+ * clb_search_batch_filtered_device_slot launches. */
+int clb_search_batch_after_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                       int64_t k, const clb_filter* const* filters, int scope, const float* d_after_scores,
+                                       const int64_t* d_after_pids, int64_t* d_out_pids, float* d_out_scores,
+                                       int64_t* d_n_cand, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Grouped search across a shard group. Every shard holds a clb_grouping made from ITS slice of the group ids (a dense
  * local index per local passage, as ever) and the caller passes `group_base`: the GLOBAL dense index of the group of the
  * shard's first passage, so that the global index of local passage p is group_base + index[p].  (The host has the whole id
  * array: the global dense index of passage i is the number of id changes before it.)  A group that straddles a cut is the
