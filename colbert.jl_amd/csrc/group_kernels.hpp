@@ -558,6 +558,7 @@ static __global__ __launch_bounds__(256) void group_result_kernel(const int64_t*
 // group of the nearest list before it that has candidates: a group that straddles cuts is counted once, however many
 // shards it spans.  Strides as in merge_topk_kernel, in elements.  n_lists <= kMaxGroupShards.
 // grid = (ceil(n_lists * k / 256), B), block = 256; the output is filled with padding beforehand (fill_pad_kernel).
+// All three comparisons below go through rec_before (search_kernels.hpp), which orders scores by their order keys: -0.0 below +0.0.
 static __global__ __launch_bounds__(256) void merge_topk_grouped_kernel(
     const int64_t* __restrict__ pids, const float* __restrict__ scores, const int64_t* __restrict__ gids, int k, int n_lists,
     int B, size_t pid_stride, size_t score_stride, size_t gid_stride, const int64_t* __restrict__ n_cand_lists,

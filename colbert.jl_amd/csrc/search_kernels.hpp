@@ -1616,8 +1616,14 @@ static __global__ void batch_stats_kernel(const uint32_t* __restrict__ cand, con
 // to the union of the shards' results).  in: [n_lists][B][k] records sorted by (score desc, pid asc),
 // padded with (0, -Inf).  Every record finds its rank in the merged order by binary search in the other
 // lists (pids are unique across shards, so ranks are unique).  grid = (ceil(n_lists*k/256), B).
+// Scores are compared by their order keys, as the top-k kernels that made the lists compare them (-0.0 below +0.0):
+// with the float comparison a list that holds both zeros is not sorted, a binary search over it is not monotone, and
+// two records can be given the same rank.  Every user orders by key through this function: the binary search of
+// merge_topk_kernel below, and in group_kernels.hpp the dead-record test, the binary search and the rank correction of
+// merge_topk_grouped_kernel.
 __device__ __forceinline__ bool rec_before(float s, int64_t p, float s2, int64_t p2) {
-    return s > s2 || (s == s2 && p < p2);
+    const uint32_t a = f32_order_key(s), a2 = f32_order_key(s2);
+    return a > a2 || (a == a2 && p < p2);
 }
 // pid_stride / score_stride: elements between the (B, k) blocks of consecutive lists (B*k when the lists are
 // stacked densely; larger when every rank's pids and scores travel in one packed all-gather buffer).
