@@ -11,4 +11,4 @@ from .config import ColBERTConfig  # noqa: F401
 from .encoder import BertEncoder, encoder_plan  # noqa: F401
 from .indexer import Indexer, PrecomputedEncoder, index, train  # noqa: F401
 from .searcher import PassageFilter, PassageGrouping, PassagePrior, Searcher, TextSearch, next_cursor, search  # noqa: F401
-from .sharded import ShardedFilter, ShardedGrouping, ShardedSearcher  # noqa: F401
+from .sharded import ShardedFilter, ShardedGrouping, ShardedPrior, ShardedSearcher  # noqa: F401

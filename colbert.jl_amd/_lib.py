@@ -168,6 +168,15 @@ def lib() -> C.CDLL:
         l.clb_search_result_groups_slot.argtypes = [vp, ci, vp, i64_, vp, i64_, i64_, vp, vp, vp]
         l.clb_debug_group_tau_device.restype = ci
         l.clb_debug_group_tau_device.argtypes = [vp, vp, i64_, i64_, i64_, vp, vp]
+        if hasattr(l, "clb_search_shard_phase1_prior_slot"):   # (absent from a COLBERT_HIP_LIB build of an earlier commit)
+            l.clb_search_shard_phase1_prior_slot.restype = ci
+            l.clb_search_shard_phase1_prior_slot.argtypes = [vp, ci, vp, i64_, i64_, i64_, i64_, C.POINTER(vp), ci, vp, i64_, vp,
+                                                             C.c_float, vp, vp, vp, vp]
+            l.clb_search_shard_phase2_prior_slot.restype = ci
+            l.clb_search_shard_phase2_prior_slot.argtypes = [vp, ci, vp, i64_, i64_, i64_, i64_, vp, vp, vp, i64_, vp, i64_, vp,
+                                                             C.c_float, vp, vp, vp, vp, vp, vp]
+            l.clb_debug_prior_tau_device.restype = ci
+            l.clb_debug_prior_tau_device.argtypes = [vp, vp, vp, vp, i64_, i64_, i64_, vp, vp]
         l.clb_merge_topk_grouped_device.restype = ci
         l.clb_merge_topk_grouped_device.argtypes = [ci, vp, vp, vp, i64_, i64_, i64_, vp, vp, vp, vp, vp, vp]
         l.clb_packed_grouped_bytes.restype = i64_

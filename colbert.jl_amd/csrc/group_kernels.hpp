@@ -398,6 +398,38 @@ __device__ __forceinline__ void wave_list_edges(const int64_t* __restrict__ g, i
     *at_hi = ihi;
 }
 
+// The boundary records of one query's gathered lists all_top / all_gid [n_shards][B][k], for the 1024 threads of a work-group:
+// e_at[2 l], e_at[2 l + 1] = the positions (in the query's n_shards * k records) of list l's records with the lowest and the
+// highest valid group index, -1 where there is none; e_dead = 1 for a boundary record that loses to another of the same group
+// (the larger score wins, the earlier record among equal ones).  The caller synchronises before it reads e_dead.
+__device__ __forceinline__ void group_boundary_records(const float* __restrict__ all_top, const int64_t* __restrict__ all_gid,
+                                                       int n_shards, int B, int b, int k, long long* e_gid, uint32_t* e_key,
+                                                       int* e_at, int* e_dead) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int l = wave; l < n_shards; l += 16) {
+        const size_t base = ((size_t)l * B + b) * k;
+        int lo, hi;
+        wave_list_edges(all_gid + base, k, lane, &lo, &hi);
+        if (lane == 0) {
+            if (hi == lo) hi = -1;                     // one valid record: one boundary record
+            e_at[2 * l] = lo < 0 ? -1 : l * k + lo;
+            e_at[2 * l + 1] = hi < 0 ? -1 : l * k + hi;
+            e_gid[2 * l] = lo < 0 ? -1 : all_gid[base + lo];
+            e_gid[2 * l + 1] = hi < 0 ? -1 : all_gid[base + hi];
+            e_key[2 * l] = lo < 0 ? 0u : f32_order_key(all_top[base + lo]);
+            e_key[2 * l + 1] = hi < 0 ? 0u : f32_order_key(all_top[base + hi]);
+        }
+    }
+    __syncthreads();
+    for (int t = tid; t < 2 * n_shards; t += 1024) {
+        int dead = 0;
+        if (e_at[t] >= 0)
+            for (int j = 0; j < 2 * n_shards; ++j)
+                dead |= j != t && e_at[j] >= 0 && e_gid[j] == e_gid[t] && (e_key[j] > e_key[t] || (e_key[j] == e_key[t] && j < t));
+        e_dead[t] = dead;
+    }
+}
+
 // S7g-c (phase 1 of the grouped two-phase search).  Of the query's groups -- glist[b][r] = the slot of the best approximate
 // score of run r, nglist[b] runs (group_collapse_kernel over all candidates) -- the k with the largest score: out_top[b][i]
 // the score, out_gid[b][i] the GLOBAL group index, in no particular order, padded with (-inf, -1).  Among scores equal to
@@ -477,30 +509,9 @@ static __global__ __launch_bounds__(1024) void group_global_tau_kernel(const flo
     __shared__ uint32_t e_key[2 * kMaxGroupShards];
     __shared__ int e_at[2 * kMaxGroupShards];          // position in the query's n_shards * k records, -1: no such record
     __shared__ int e_dead[2 * kMaxGroupShards];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int n = n_shards * k;
-    for (int l = wave; l < n_shards; l += 16) {
-        const size_t base = ((size_t)l * B + b) * k;
-        int lo, hi;
-        wave_list_edges(all_gid + base, k, lane, &lo, &hi);
-        if (lane == 0) {
-            if (hi == lo) hi = -1;                     // one valid record: one boundary record
-            e_at[2 * l] = lo < 0 ? -1 : l * k + lo;
-            e_at[2 * l + 1] = hi < 0 ? -1 : l * k + hi;
-            e_gid[2 * l] = lo < 0 ? -1 : all_gid[base + lo];
-            e_gid[2 * l + 1] = hi < 0 ? -1 : all_gid[base + hi];
-            e_key[2 * l] = lo < 0 ? 0u : f32_order_key(all_top[base + lo]);
-            e_key[2 * l + 1] = hi < 0 ? 0u : f32_order_key(all_top[base + hi]);
-        }
-    }
-    __syncthreads();
-    for (int t = tid; t < 2 * n_shards; t += 1024) {
-        int dead = 0;
-        if (e_at[t] >= 0)
-            for (int j = 0; j < 2 * n_shards; ++j)
-                dead |= j != t && e_at[j] >= 0 && e_gid[j] == e_gid[t] && (e_key[j] > e_key[t] || (e_key[j] == e_key[t] && j < t));
-        e_dead[t] = dead;
-    }
+    group_boundary_records(all_top, all_gid, n_shards, B, b, k, e_gid, e_key, e_at, e_dead);
     if (tid == 0) { s_prefix = 0u; s_remaining = k; }
     __syncthreads();
     const uint32_t neg_key = f32_order_key(kNegInf);

@@ -9,8 +9,11 @@
 // A = fl(a + pi), at the threshold prior_tau_kernel leaves) and on the exact scores of the re-scored list after pass 2.
 // Nothing between the two reads the slot's score buffer as a MaxSim value: the row sweep works from tokmax / eps_pair and the
 // exact kernel only writes it.
+// Across a shard group (the two phase calls with a prior) the first boost runs in phase 1, which publishes the shard's k largest
+// A and its largest |A|, and prior_global_tau_kernel forms phase 2's threshold from what all shards published.
 #pragma once
 #include "approx_kernels.hpp"
+#include "group_kernels.hpp"
 #include "search_kernels.hpp"
 
 namespace clb {
@@ -100,6 +103,82 @@ static __global__ __launch_bounds__(1024) void prior_tau_kernel(const float* __r
         const float delta = 4.f * u * (mabs[b] + qb.eps_sum);
         const float t = tau - 2.f * delta;
         tau_out[b] = (qb.unsafe || !(t > kNegInf)) ? kNegInf : t;      // NaN-safe: a non-finite slack lists everything
+    }
+}
+
+// P3 (two-phase search of a shard group with a prior, phase 2).  tau_out[b] = tau - 2 delta from what the shards published in
+// phase 1, all_top [n_shards][B][k] (each shard's k largest boosted approximate scores A, -inf padding) and all_mabs
+// [n_shards][B] (each shard's M_i = max |A| over ITS candidates of the query):
+//     tau   = the k-th largest gathered A -- with all_gid ([n_shards][B][k], the global group index of every record, -1 padding)
+//             over the DISTINCT indices, a repeated index counting once with its largest value (group_global_tau_kernel's
+//             rule) -- -inf with fewer than k: the k-th largest A over the union C of the shards' candidates, or a lower bound;
+//     M     = max_i M_i: |A(p)| <= M for every p in C and |tau| <= M, what P2's argument needs over C.  A shard's own M_i is
+//             NOT enough: another shard's large prior values can lift tau to a magnitude whose rounding its M_i does not cover;
+//     delta = 4 * 2^-24 * (M + eps), eps the query's eps_sum under the group's shared bound constants (eps_in[b] when given
+//             -- the test hook -- else query_bound).
+// -inf for an unsafe query and for a non-finite M or eps.  n_shards <= kMaxGroupShards with all_gid.  grid = B, block = 1024.
+static __global__ __launch_bounds__(1024) void prior_global_tau_kernel(const float* __restrict__ all_top,
+                                                                      const int64_t* __restrict__ all_gid /*optional*/,
+                                                                      const float* __restrict__ all_mabs, int n_shards, int B,
+                                                                      int k, const float* __restrict__ eps_in /*optional*/,
+                                                                      const float* __restrict__ Q, int T, ApproxConsts ac,
+                                                                      const float4* __restrict__ tscale, int cell8,
+                                                                      float* __restrict__ tau_out) {
+    __shared__ __attribute__((aligned(16))) int hist[256];
+    __shared__ uint32_t s_prefix, s_kmin, s_kmax, s_mbits;
+    __shared__ int s_remaining;
+    __shared__ float s_aux[4];
+    __shared__ float s_qn, s_dq;
+    __shared__ long long e_gid[2 * kMaxGroupShards];
+    __shared__ uint32_t e_key[2 * kMaxGroupShards];
+    __shared__ int e_at[2 * kMaxGroupShards];
+    __shared__ int e_dead[2 * kMaxGroupShards];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = n_shards * k;
+    if (tid == 0) { s_prefix = 0u; s_remaining = k; s_mbits = 0u; }
+    if (all_gid) group_boundary_records(all_top, all_gid, n_shards, B, b, k, e_gid, e_key, e_at, e_dead);
+    __syncthreads();
+    {   // M: |x| of a NaN orders above +inf as bits, +inf above every finite value -- a non-finite M_i survives the maximum
+        uint32_t m = 0u;
+        for (int l = tid; l < n_shards; l += 1024) {
+            const uint32_t v = __float_as_uint(fabsf(all_mabs[(size_t)l * B + b]));
+            m = v > m ? v : m;
+        }
+        if (m) atomicMax(&s_mbits, m);
+    }
+    const uint32_t neg_key = f32_order_key(kNegInf);
+    const int chunk = (n + 1023) >> 10;
+#define CLB_SEL_FOR_EACH(...)                                                                   \
+    for (int c = 0; c < chunk; ++c) {                                                           \
+        const int i_ = c * 1024 + tid;                                                          \
+        const bool valid = i_ < n;                                                              \
+        uint32_t key = 0u;                                                                      \
+        if (valid) {                                                                            \
+            const int l_ = i_ / k;                                                              \
+            const size_t at_ = ((size_t)l_ * B + b) * k + (i_ - l_ * k);                        \
+            const bool gone_ = all_gid && (all_gid[at_] < 0 || (e_at[2 * l_] == i_ && e_dead[2 * l_]) || \
+                                           (e_at[2 * l_ + 1] == i_ && e_dead[2 * l_ + 1]));     \
+            key = gone_ ? neg_key : f32_order_key(all_top[at_]);                                \
+        }                                                                                       \
+        __VA_ARGS__                                                                             \
+    }
+    CLB_RADIX_SELECT()
+#undef CLB_SEL_FOR_EACH
+    float eps = 0.f;
+    bool unsafe = false;
+    if (eps_in) {                                      // uniform over the block
+        eps = eps_in[b];
+    } else {
+        const QueryBound qb = query_bound(Q, b, T, ac, &s_qn, &s_dq, tscale, s_aux, cell8 != 0);
+        eps = qb.eps_sum;
+        unsafe = qb.unsafe;
+    }
+    if (tid == 0) {
+        const float tau = f32_from_order_key(s_prefix);
+        const float u = 5.9604645e-08f;  // 2^-24
+        const float delta = 4.f * u * (__uint_as_float(s_mbits) + eps);
+        const float t = tau - 2.f * delta;
+        tau_out[b] = (unsafe || !(t > kNegInf)) ? kNegInf : t;        // NaN-safe: a non-finite slack lists everything
     }
 }
 

@@ -104,9 +104,11 @@ struct Workspace {
     size_t ivf_cap = 0;         // cand_cap before filt_cap was taken into account: the most candidates the IVF lists can give
     // two-phase sharded search: what clb_search_shard_phase1 left behind (phase 2 must continue exactly that batch)
     struct { bool valid = false; const float* dQ = nullptr; int64_t T = 0, B = 0, nprobe = 0, k = 0; void* stream = nullptr;
-             size_t filt_now = 0; const clb_grouping* grp = nullptr; int64_t group_base = 0; } pending;
+             size_t filt_now = 0; const clb_grouping* grp = nullptr; int64_t group_base = 0;
+             const clb_prior* prior = nullptr; float weight = 0.f; } pending;
     // filt_now: Batch::filt_now of phase 1 -- phase 2 selects over the same candidates; grp / group_base: the grouping operands of
-    // a grouped phase 1 (clb_search_shard_phase1_grouped_slot) -- phase 2 must be the grouped call with the same ones
+    // a grouped phase 1 (clb_search_shard_phase1_grouped_slot) -- phase 2 must be the grouped call with the same ones; prior /
+    // weight: those of a phase 1 with a prior (clb_search_shard_phase1_prior_slot) -- phase 2 must be the prior call with the same
     // single-exchange grouped sharded search: the last whole search on this slot was a grouped one of B <= 64 queries (one
     // sub-batch, so its candidate lists are still here) -- clb_search_result_groups_slot reads the edge groups from them
     struct { bool valid = false; int64_t B = 0, k = 0, generation = 0; const clb_grouping* grp = nullptr; void* stream = nullptr; } grouped_done;
@@ -215,6 +217,8 @@ struct Batch {
     int64_t group_base = 0;
     int64_t* d_local_gid = nullptr; const int64_t* d_all_gid = nullptr;
     int64_t* d_out_gids = nullptr; int64_t* d_edge_gids = nullptr;
+    // ... with a prior (prior): the largest boosted approximate score by magnitude, per query, that travels with the scores
+    float* d_local_mabs = nullptr; const float* d_all_mabs = nullptr;
 };
 Batch make_batch(const float* dQ, int64_t B, int64_t T, int64_t nprobe, int64_t k) {
     Batch q;
@@ -899,6 +903,10 @@ int launch_select(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q,
 // With a grouping (q.grp) the phases exchange GROUPS: phase 1 publishes the best approximate score and the global index of the
 // shard's k best groups (d_local_top / d_local_gid), phase 2 cuts at the k-th best DISTINCT group of the gathered records and
 // adds what the grouped merge needs to its result (d_out_gids / d_edge_gids).
+// With a prior (q.prior) in the phases: phase 1 boosts every candidate's approximate score first and publishes, beside the k
+// largest BOOSTED scores (or groups), the largest of them by magnitude (d_local_mabs); phase 2 cuts at the gathered threshold
+// lowered by the rounding slack at the largest magnitude of ALL shards (d_all_mabs, prior_global_tau_kernel) and boosts the
+// re-scored list in front of the ranking, as phase 0 does.
 int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
     const float* dQ = q.dQ;
     const int B = q.B, T = q.T, k = q.k, phase = q.phase;
@@ -908,7 +916,15 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
     s->prof.chain = nullptr;           // the first timed kernel of a call records its own start
     if (phase == 2) {
         CLB_TRY(w.tau_glob.ensure(sizeof(float) * B));
-        if (q.grp)      // the k-th best GROUP over the shards: a group that straddles a cut counts once
+        if (q.prior) {  // the k-th largest BOOSTED score (the k-th best group's) over the shards, lowered by the rounding slack at
+                        // the largest magnitude any shard saw (prior_global_tau_kernel)
+            ApproxConsts ac = s->approx_consts;
+            ac.dc_max = bound_dc(s, w);
+            hipLaunchKernelGGL(prior_global_tau_kernel, dim3(B), dim3(1024), 0, st, q.d_all_top, q.d_all_gid, q.d_all_mabs,
+                               q.n_shards, B, k, (const float*)nullptr, dQ, T, ac,
+                               w.have_range ? (const float4*)w.tscale.as<float4>() : (const float4*)nullptr, w.cell8 ? 1 : 0,
+                               w.tau_glob.as<float>());
+        } else if (q.grp)      // the k-th best GROUP over the shards: a group that straddles a cut counts once
             hipLaunchKernelGGL(group_global_tau_kernel, dim3(B), dim3(1024), 0, st, q.d_all_top, q.d_all_gid, q.n_shards, B, k,
                                w.tau_glob.as<float>());
         else
@@ -938,8 +954,8 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
                 const dim3 approx_grid = gxq > 0 && B > 1 ? dim3(gxq, B) : dim3(8 * kWgPerGroup);
                 launch_pass1(s, w, st, dQ, approx_grid, B, T);
             }
-            if (q.prior) {
-                // with a prior (phase 0 only): the selection cuts on the BOOSTED approximate scores, at their k-th largest --
+            if (q.prior && phase == 0) {
+                // with a prior (the whole search): the selection cuts on the BOOSTED approximate scores, at their k-th largest --
                 // with a grouping the k-th best group's -- lowered by the rounding slack (prior_tau_kernel)
                 Timed t(s, KID_SELECT, st);
                 float* ptau = w.prior_tau.as<float>();
@@ -967,6 +983,8 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
                 CLB_TRY(launch_select(s, w, st, q, (const float*)w.after_tau.as<float>()));
             } else {
                 Timed t(s, KID_SELECT, st);
+                // phase 1 with a prior: everything below works on A = fl(a + pi), and the shard's largest |A| travels with it
+                if (phase == 1) launch_boost(w, st, q, 0, B, nullptr, nullptr, q.d_local_mabs);
                 if (q.grp && phase == 1) {
                     // grouped phase 1: the shard's k best groups by approximate score, with their global indices; the
                     // selection waits for the threshold of phase 2
@@ -2052,14 +2070,17 @@ int clb_search_shard_phase1_slot(clb_searcher* s, int slot, const float* d_Q, in
 
 static int shard_phase1_impl(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
                             const clb_filter* const* filters, int scope, const clb_grouping* grp, int64_t group_base,
-                            float* d_local_top, int64_t* d_local_gid, void* hip_stream) {
+                            float* d_local_top, int64_t* d_local_gid, void* hip_stream, PriorArg prior = {},
+                            float* d_local_mabs = nullptr) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     if (!d_local_top) return fail(CLB_EARGUMENT, "d_local_top is null");
+    if (prior.p && !d_local_mabs) return fail(CLB_EARGUMENT, "d_local_mabs is null");
     if (grp && !d_local_gid) return fail(CLB_EARGUMENT, "d_local_gid is null");
     if (grp && group_base < 0) return fail(CLB_EARGUMENT, "group_base must be >= 0, got %lld", (long long)group_base);
     size_t filt_count = 0;
     CLB_TRY(check_filters(s, filters, B, scope, &filt_count));
     CLB_TRY(check_grouping(s, grp));
+    CLB_TRY(check_prior(s, prior.p, prior.weight));
     bool filtered = false;
     for (int64_t b = 0; filters && b < B; ++b) filtered |= filters[b] != nullptr;
     // the whole batch stays on the slot for phase 2, and the filter handles of a launch travel in one argument block
@@ -2070,17 +2091,19 @@ static int shard_phase1_impl(clb_searcher* s, int slot, const float* d_Q, int64_
     CLB_TRY(slot_workspace(s, slot, &wp));
     Workspace& w = *wp;
     CLB_TRY(ensure_workspace(s, w, B, T, nprobe, k, filt_count, grp != nullptr));
-    if (grp) CLB_TRY(w.tau_glob.ensure(sizeof(float) * B));      // phase 2 then allocates nothing
+    if (grp || prior.p) CLB_TRY(w.tau_glob.ensure(sizeof(float) * B));      // phase 2 then allocates nothing
     w.pending.valid = false;
     w.grouped_done.valid = false;
     Batch q = make_batch(d_Q, B, T, nprobe, k);
     set_batch_filters(q, filters, 0, scope, filt_count);
     q.phase = 1; q.d_local_top = d_local_top;
     q.grp = grp; q.group_base = group_base; q.d_local_gid = d_local_gid;
+    q.prior = prior.p; q.prior_weight = prior.weight; q.d_local_mabs = prior.p ? d_local_mabs : nullptr;
     CLB_TRY(run_search(s, w, (hipStream_t)hip_stream, q));
     w.pending.valid = true; w.pending.dQ = d_Q; w.pending.T = T; w.pending.B = B; w.pending.nprobe = nprobe;
     w.pending.k = k; w.pending.stream = hip_stream; w.pending.filt_now = q.filt_now;
     w.pending.grp = grp; w.pending.group_base = group_base;
+    w.pending.prior = prior.p; w.pending.weight = prior.p ? prior.weight : 0.f;
     return CLB_OK;
 }
 
@@ -2107,9 +2130,15 @@ int clb_search_shard_phase2(clb_searcher* s, const float* d_Q, int64_t T, int64_
 static int shard_phase2_impl(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
                             const float* d_all_top, const int64_t* d_all_gid, int64_t n_shards, const clb_grouping* grp,
                             int64_t group_base, int64_t* d_out_pids, float* d_out_scores, int64_t* d_out_gids, int64_t* d_n_cand,
-                            int64_t* d_edge_gids, void* hip_stream) {
+                            int64_t* d_edge_gids, void* hip_stream, PriorArg prior = {}, const float* d_all_mabs = nullptr) {
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     if (!d_all_top || n_shards < 1) return fail(CLB_EARGUMENT, "d_all_top is null or n_shards < 1");
+    if (prior.p) {
+        if (!d_all_mabs) return fail(CLB_EARGUMENT, "d_all_mabs is null");
+        if (!d_out_pids || !d_out_scores || !d_n_cand)
+            return fail(CLB_EARGUMENT, "an output of the prior phase 2 is null (d_out_pids, d_out_scores, d_n_cand)");
+        CLB_TRY(check_prior(s, prior.p, prior.weight));
+    }
     if (grp) {
         if (!d_all_gid) return fail(CLB_EARGUMENT, "d_all_gid is null");
         if (!d_out_pids || !d_out_scores || !d_out_gids || !d_n_cand || !d_edge_gids)
@@ -2123,9 +2152,11 @@ static int shard_phase2_impl(clb_searcher* s, int slot, const float* d_Q, int64_
     Workspace& w = *wp;
     const auto& pd = w.pending;
     if (!pd.valid || pd.dQ != d_Q || pd.T != T || pd.B != B || pd.nprobe != nprobe || pd.k != k || pd.stream != hip_stream ||
-        pd.grp != grp || (grp && pd.group_base != group_base))
+        pd.grp != grp || (grp && pd.group_base != group_base) || pd.prior != prior.p ||
+        (prior.p && std::memcmp(&pd.weight, &prior.weight, sizeof(float)) != 0))
         return fail(CLB_EARGUMENT, "clb_search_shard_phase2 without a matching clb_search_shard_phase1 "
-                                   "on this workspace slot (same queries, T, B, nprobe, k and stream, and no other search on the slot in between)");
+                                   "on this workspace slot (same queries, T, B, nprobe, k and stream -- with a grouping or a prior: the same "
+                                   "grouping, group_base, prior and weight -- and no other search on the slot in between)");
     // every shard must cut at tau_global - 2 eps with ONE eps (the largest): a shard still on its own bound constants
     // could drop a member of the global top-k silently, so phase 2 with other shards' scores is refused until the host
     // has shared them (clb_searcher_get_bound_consts on every shard -> element-wise maximum -> clb_searcher_set_bound_consts)
@@ -2140,6 +2171,7 @@ static int shard_phase2_impl(clb_searcher* s, int slot, const float* d_Q, int64_
     q.d_out_pids = d_out_pids; q.d_out_scores = d_out_scores; q.d_n_cand = d_n_cand;
     q.phase = 2; q.d_all_top = d_all_top; q.n_shards = (int)n_shards;
     q.grp = grp; q.group_base = group_base; q.d_all_gid = d_all_gid; q.d_out_gids = d_out_gids; q.d_edge_gids = d_edge_gids;
+    q.prior = prior.p; q.prior_weight = prior.weight; q.d_all_mabs = d_all_mabs;
     return run_search(s, w, (hipStream_t)hip_stream, q);
 }
 
@@ -2158,6 +2190,30 @@ int clb_search_shard_phase2_grouped_slot(clb_searcher* s, int slot, const float*
     if (!grouping) return fail(CLB_EARGUMENT, "grouping is null (without one: clb_search_shard_phase2_slot)");
     return shard_phase2_impl(s, slot, d_Q, T, B, nprobe, k, d_all_top, d_all_gid, n_shards, grouping, group_base, d_out_pids,
                              d_out_scores, d_out_gids, d_n_cand, d_edge_gids, hip_stream);
+}
+
+static int check_prior_weight(const clb_prior* prior, float weight);
+
+int clb_search_shard_phase1_prior_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                       int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
+                                       int64_t group_base, const clb_prior* prior, float weight, float* d_local_top,
+                                       int64_t* d_local_gid, float* d_local_mabs, void* hip_stream) {
+    CLB_TRY(check_prior_weight(prior, weight));
+    return shard_phase1_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, grouping, group_base, d_local_top, d_local_gid,
+                             hip_stream, PriorArg{prior, weight}, d_local_mabs);
+}
+
+int clb_search_shard_phase2_prior_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                       int64_t k, const float* d_all_top, const int64_t* d_all_gid, const float* d_all_mabs,
+                                       int64_t n_shards, const clb_grouping* grouping, int64_t group_base, const clb_prior* prior,
+                                       float weight, int64_t* d_out_pids, float* d_out_scores, int64_t* d_out_gids,
+                                       int64_t* d_n_cand, int64_t* d_edge_gids, void* hip_stream) {
+    if (!prior)
+        return fail(CLB_EARGUMENT, "prior is null (without one: clb_search_shard_phase2_slot / clb_search_shard_phase2_grouped_slot)");
+    CLB_TRY(check_prior_weight(prior, weight));
+    return shard_phase2_impl(s, slot, d_Q, T, B, nprobe, k, d_all_top, grouping ? d_all_gid : nullptr, n_shards, grouping,
+                             group_base, d_out_pids, d_out_scores, grouping ? d_out_gids : nullptr, d_n_cand,
+                             grouping ? d_edge_gids : nullptr, hip_stream, PriorArg{prior, weight}, d_all_mabs);
 }
 
 int clb_search_result_groups_slot(clb_searcher* s, int slot, const clb_grouping* grouping, int64_t group_base,
@@ -2633,6 +2689,21 @@ int clb_debug_group_tau_device(const float* d_all_top, const int64_t* d_all_gid,
     if (n_shards * k > INT32_MAX) return fail(CLB_EUNSUPPORTED, "n_shards * k exceeds 2^31 - 1");
     hipLaunchKernelGGL(group_global_tau_kernel, dim3((unsigned)B), dim3(1024), 0, (hipStream_t)hip_stream, d_all_top, d_all_gid,
                        (int)n_shards, (int)B, (int)k, d_tau);
+    CLB_HIP(hipGetLastError());
+    return CLB_OK;
+}
+
+int clb_debug_prior_tau_device(const float* d_all_top, const int64_t* d_all_gid, const float* d_all_mabs, const float* d_eps,
+                               int64_t n_shards, int64_t B, int64_t k, float* d_tau_in, void* hip_stream) {
+    if (!d_all_top || !d_all_mabs || !d_eps || !d_tau_in)
+        return fail(CLB_EARGUMENT, "d_all_top, d_all_mabs, d_eps or d_tau_in is null");
+    if (n_shards < 1 || B < 1 || k < 1) return fail(CLB_EARGUMENT, "n_shards, B and k must be >= 1");
+    if (d_all_gid && n_shards > kMaxGroupShards)
+        return fail(CLB_EUNSUPPORTED, "at most %d shards with group indices, got %lld", kMaxGroupShards, (long long)n_shards);
+    if (n_shards * k > INT32_MAX) return fail(CLB_EUNSUPPORTED, "n_shards * k exceeds 2^31 - 1");
+    hipLaunchKernelGGL(prior_global_tau_kernel, dim3((unsigned)B), dim3(1024), 0, (hipStream_t)hip_stream, d_all_top, d_all_gid,
+                       d_all_mabs, (int)n_shards, (int)B, (int)k, d_eps, (const float*)nullptr, 0, ApproxConsts{},
+                       (const float4*)nullptr, 0, d_tau_in);
     CLB_HIP(hipGetLastError());
     return CLB_OK;
 }

@@ -292,39 +292,66 @@ class DeviceSearch:
             self.g_edges = self.gpacked[at_e:].view(torch.int64).view(B, 2)
         return self.gpacked
 
-    def search_grouped_shard(self, Qdev, filters, scope, grouping, group_base: int):
+    def search_grouped_shard(self, Qdev, filters, scope, grouping, group_base: int, prior=None, prior_weight=1.0):
         """The single exchange of a grouped sharded search on this shard: the whole grouped search
-        (clb_search_batch_grouped_device_slot), then the global group index of every result and the edge groups of every
+        (clb_search_batch_grouped_device_slot; with `prior` / `prior_weight`, this shard's PassagePrior and the group's
+        weight: clb_search_batch_prior_device_slot), then the global group index of every result and the edge groups of every
         query (clb_search_result_groups_slot), all into the packed grouped block, which is returned.  B <= 64."""
         import torch
-        from .searcher import _scope_code
+        from .searcher import _prior_weight, _scope_code
         self._check_queries(Qdev)
         block = self._grouped_block()
         st = torch.cuda.current_stream(self.dev).cuda_stream
         gh = self.s._grouping_handle(grouping)
-        check(lib().clb_search_batch_grouped_device_slot(
-            self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
-            None if filters is None else self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)), gh,
-            C.c_void_p(self.g_out_p.data_ptr()), C.c_void_p(self.g_out_s.data_ptr()), C.c_void_p(self.g_ncand.data_ptr()),
-            C.c_void_p(st)))
+        fh = None if filters is None else self.s._filter_handles(filters, self.B)
+        if prior is not None:
+            w = _prior_weight(prior, prior_weight, None)
+            check(lib().clb_search_batch_prior_device_slot(
+                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
+                fh, C.c_int(_scope_code(scope)), gh, prior._h, C.c_float(w), C.c_void_p(self.g_out_p.data_ptr()),
+                C.c_void_p(self.g_out_s.data_ptr()), C.c_void_p(self.g_ncand.data_ptr()), C.c_void_p(st)))
+        else:
+            check(lib().clb_search_batch_grouped_device_slot(
+                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
+                fh, C.c_int(_scope_code(scope)), gh, C.c_void_p(self.g_out_p.data_ptr()), C.c_void_p(self.g_out_s.data_ptr()),
+                C.c_void_p(self.g_ncand.data_ptr()), C.c_void_p(st)))
         check(lib().clb_search_result_groups_slot(
             self.s._h, C.c_int(self.slot), gh, i64(group_base), C.c_void_p(self.g_out_p.data_ptr()), i64(self.B), i64(self.k),
             C.c_void_p(self.g_out_g.data_ptr()), C.c_void_p(self.g_edges.data_ptr()), C.c_void_p(st)))
         return block
 
-    def phase1(self, Qdev, filters=None, scope="candidates", grouping=None, group_base: int = 0):
+    def phase1(self, Qdev, filters=None, scope="candidates", grouping=None, group_base: int = 0, prior=None, prior_weight=1.0):
         """Two-phase sharded search, first half (clb_search_shard_phase1): everything up to pass 1 on this shard.
         Returns the (B, k) tensor of the shard's k largest approximate scores per query, to be all-gathered.
         `filters` / `scope` as in __call__ (clb_search_shard_phase1_filtered_slot: at most 64 queries per call when one is
         filtered); phase2 takes none -- it continues on the filtered candidates phase 1 left on the slot.
         `grouping` (this shard's PassageGrouping) with `group_base` (the global index of the shard's first group): the grouped
         form, clb_search_shard_phase1_grouped_slot -- returns (local_top, local_gid), the best approximate score of the
-        shard's k best groups and their global group indices (int64), both (B, k) and both to be all-gathered."""
+        shard's k best groups and their global group indices (int64), both (B, k) and both to be all-gathered.
+        `prior` (this shard's PassagePrior) with `prior_weight` (the group's weight): clb_search_shard_phase1_prior_slot --
+        the published scores are the BOOSTED approximate scores, and the call returns (local_top, local_gid or None,
+        local_mabs): local_mabs [B] float32 is the shard's largest boosted approximate score by magnitude per query, to be
+        all-gathered with the others (phase 2 forms its rounding slack from the maximum over the shards)."""
         import torch
         self._check_queries(Qdev)
         if not hasattr(self, "local_top"):
             self.local_top = torch.empty((self.B, self.k), dtype=torch.float32, device=self.dev)
         st = torch.cuda.current_stream(self.dev).cuda_stream
+        if prior is not None:
+            from .searcher import _prior_weight, _scope_code
+            w = _prior_weight(prior, prior_weight, None)
+            if grouping is not None and not hasattr(self, "local_gid"):
+                self.local_gid = torch.empty((self.B, self.k), dtype=torch.int64, device=self.dev)
+            if not hasattr(self, "local_mabs"):
+                self.local_mabs = torch.zeros(self.B, dtype=torch.float32, device=self.dev)
+            gid = self.local_gid if grouping is not None else None
+            check(lib().clb_search_shard_phase1_prior_slot(
+                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
+                None if filters is None else self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)),
+                None if grouping is None else self.s._grouping_handle(grouping), i64(group_base), prior._h, C.c_float(w),
+                C.c_void_p(self.local_top.data_ptr()), None if gid is None else C.c_void_p(gid.data_ptr()),
+                C.c_void_p(self.local_mabs.data_ptr()), C.c_void_p(st)))
+            return self.local_top, gid, self.local_mabs
         if grouping is not None:
             from .searcher import _scope_code
             if not hasattr(self, "local_gid"):
@@ -347,11 +374,15 @@ class DeviceSearch:
                                             C.c_void_p(st)))
         return self.local_top
 
-    def phase2(self, Qdev, all_top, all_gid=None, grouping=None, group_base: int = 0):
+    def phase2(self, Qdev, all_top, all_gid=None, grouping=None, group_base: int = 0, prior=None, prior_weight=1.0,
+               all_mabs=None):
         """Second half (clb_search_shard_phase2).  all_top: (n_shards, B, k) gathered `local_top` blocks.
         With `grouping` / `group_base` as in phase1 and `all_gid`, the gathered `local_gid` blocks: the grouped form
         (clb_search_shard_phase2_grouped_slot) -- the result goes into the packed grouped block, which is returned (for
-        merge_grouped_packed, after the all-gather)."""
+        merge_grouped_packed, after the all-gather).
+        With `prior` / `prior_weight` as in phase1 and `all_mabs`, the gathered `local_mabs` blocks (n_shards, B): the form
+        with a prior (clb_search_shard_phase2_prior_slot), with or without a grouping; it returns what the form without a
+        prior returns."""
         import torch
         from ._lib import ArgumentError
         self._check_queries(Qdev)
@@ -364,6 +395,22 @@ class DeviceSearch:
                     or all_gid.device != self.dev):
                 raise ArgumentError(f"all_gid must be a contiguous int64 tensor of all_top's shape on {self.dev}")
             block = self._grouped_block()
+        if prior is not None:
+            from .searcher import _prior_weight
+            w = _prior_weight(prior, prior_weight, None)
+            if (all_mabs is None or all_mabs.dtype != torch.float32 or tuple(all_mabs.shape) != (all_top.shape[0], self.B)
+                    or not all_mabs.is_contiguous() or all_mabs.device != self.dev):
+                raise ArgumentError(f"all_mabs must be a contiguous float32 (n_shards, {self.B}) tensor on {self.dev}")
+            g = grouping is not None
+            out_p, out_s, ncand = (self.g_out_p, self.g_out_s, self.g_ncand) if g else (self.out_p, self.out_s, self.ncand)
+            check(lib().clb_search_shard_phase2_prior_slot(
+                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
+                C.c_void_p(all_top.data_ptr()), C.c_void_p(all_gid.data_ptr()) if g else None, C.c_void_p(all_mabs.data_ptr()),
+                i64(all_top.shape[0]), self.s._grouping_handle(grouping) if g else None, i64(group_base), prior._h, C.c_float(w),
+                C.c_void_p(out_p.data_ptr()), C.c_void_p(out_s.data_ptr()), C.c_void_p(self.g_out_g.data_ptr()) if g else None,
+                C.c_void_p(ncand.data_ptr()), C.c_void_p(self.g_edges.data_ptr()) if g else None, C.c_void_p(st)))
+            return block if g else (self.out_p, self.out_s)
+        if grouping is not None:
             check(lib().clb_search_shard_phase2_grouped_slot(
                 self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
                 C.c_void_p(all_top.data_ptr()), C.c_void_p(all_gid.data_ptr()), i64(all_top.shape[0]),

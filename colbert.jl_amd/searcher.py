@@ -145,19 +145,29 @@ class PassagePrior:
 
 def _prior_weight(prior, prior_weight, per_group) -> float:
     """The `prior=` / `prior_weight=` of a search call, checked on the host -> the weight as the float the C ABI takes."""
-    from ._lib import ArgumentError, Unsupported
-    if per_group is not None:
-        raise Unsupported("per_group together with a prior is not supported: the hits of a grouped search take no prior")
+    _no_prior_hits(per_group)
     if not isinstance(prior, PassagePrior) or not prior._h:
         raise ColBERTError("prior is not an open PassagePrior")
+    return _weight_value(prior_weight, prior.max_abs)
+
+
+def _no_prior_hits(per_group):
+    from ._lib import Unsupported
+    if per_group is not None:
+        raise Unsupported("per_group together with a prior is not supported: the hits of a grouped search take no prior")
+
+
+def _weight_value(prior_weight, max_abs: float) -> float:
+    """`prior_weight=` against the largest |value| of the prior it multiplies (of a shard group: the largest over all shards)."""
+    from ._lib import ArgumentError
     if isinstance(prior_weight, bool) or not isinstance(prior_weight, (int, float, np.integer, np.floating)):
         raise ArgumentError(f"prior_weight must be a finite number, got {prior_weight!r}")
     w = float(prior_weight)
     with np.errstate(over="ignore"):
         if not np.isfinite(np.float32(w)):
             raise ArgumentError(f"prior_weight must be a finite fp32 number, got {prior_weight!r}")
-    if not abs(float(np.float32(w))) * prior.max_abs < FLT_MAX:
-        raise ArgumentError(f"prior_weight {w!r} times the prior's largest |value| {prior.max_abs!r} is not below FLT_MAX")
+    if not abs(float(np.float32(w))) * max_abs < FLT_MAX:
+        raise ArgumentError(f"prior_weight {w!r} times the prior's largest |value| {max_abs!r} is not below FLT_MAX")
     return w
 
 
@@ -980,7 +990,7 @@ def search(searcher: Searcher, query, k: int, *, filter=None, scope="candidates"
     encoder) or a (dim, T) Float32 matrix of query embeddings.  `filter` / `scope` / `grouping` / `per_group` / `prior` /
     `prior_weight` / `after`: Searcher.search_embeddings."""
     more = {} if after is None else {"after": after}      # (a ShardedSearcher answers a cursor with Unsupported itself)
-    if prior is None and prior_weight == 1.0:      # (a ShardedSearcher takes no prior: it is not handed the keywords)
+    if prior is None and prior_weight == 1.0:      # (a call without a prior hands over the keywords it always has)
         if isinstance(query, str):
             return searcher.search(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group, **more)
         return searcher.search_embeddings(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group, **more)

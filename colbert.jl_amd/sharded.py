@@ -14,6 +14,11 @@ k best groups with those indices, the threshold counts a repeated index once, an
 record per group and counts a straddling candidate group once; under "single" every shard runs its whole grouped search and
 the same merge follows.  The hits of a grouped search (`per_group=` of `Searcher`) are not served across a shard group:
 the search calls accept the keyword and raise Unsupported.
+Score priors (`make_prior`, `prior=`, `prior_weight=`): the values are cut at the shard boundaries, one PassagePrior per shard.
+Under "two_phase" the shards publish their k largest BOOSTED approximate scores and, per query, the largest such score by
+magnitude; the threshold of phase 2 is lowered by a rounding slack formed from the maximum of those magnitudes over ALL shards
+(DESIGN.md section 5), and the usual merge follows -- it orders by (score, pid), which is the order of the boosted scores.
+Under "single" every shard runs its whole search with the prior.  With a grouping both compose as above.
 
 The shards live in one process (`group=None`; on one device, or one device each) or one or more per rank of a
 torch.distributed process group: every method is then a COLLECTIVE -- all ranks call it with the same arguments -- and its
@@ -28,7 +33,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._lib import ArgumentError, BoundsError, ColBERTError, Unsupported, check, colmajor, fptr, i64, lib
-from .searcher import PassageFilter, _scope_code
+from .searcher import PassageFilter, _no_prior_hits, _scope_code, _weight_value
 
 _PROTOCOLS = ("auto", "two_phase", "single")
 _PIECE = 64          # queries per exchange: a filtered phase 1 carries at most 64 filter handles (include/colbert_hip.h)
@@ -80,6 +85,24 @@ def slice_mask(mask, bounds):
     if m.dtype != np.bool_ or m.shape != (n,):
         raise ColBERTError(f"mask must be a boolean array of num_docs={n} entries")
     return [m[int(bounds[i] - bounds[0]):int(bounds[i + 1] - bounds[0])] for i in range(len(bounds) - 1)]
+
+
+def slice_prior(values, bounds):
+    """One finite number per passage of the group -> (the float32 array, one slice per shard).  ArgumentError for a wrong
+    length or a value that is not finite in fp32, naming the first offending GLOBAL pid."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = np.ascontiguousarray(np.asarray(values), dtype=np.float32)
+    first, n = int(bounds[0]), int(bounds[-1] - bounds[0])
+    if v.ndim != 1:
+        raise ArgumentError(f"a prior holds one value per passage of the shard group: shape {v.shape}, num_docs={n}")
+    if v.size != n:
+        what = "has no value" if v.size < n else "is not a passage of the shard group"
+        raise ArgumentError(f"a prior holds one value per passage of the shard group: {v.size} values, num_docs={n} "
+                            f"(pid {first + min(v.size, n) + 1} {what})")
+    bad = np.nonzero(~np.isfinite(v))[0]
+    if bad.size:
+        raise ArgumentError(f"the prior of passage {first + int(bad[0]) + 1} is not a finite number")
+    return v, [v[int(bounds[i]) - first:int(bounds[i + 1]) - first] for i in range(len(bounds) - 1)]
 
 
 def dense_group_index(group_ids, n: int) -> np.ndarray:
@@ -144,6 +167,31 @@ class ShardedGrouping:
 
     def __len__(self):
         return self.count
+
+
+class ShardedPrior:
+    """One finite fp32 value per passage of a shard group: one resident PassagePrior per local shard (`parts`), made from that
+    shard's slice of the values by `ShardedSearcher.make_prior` and refused by any other group.  `max_abs` is the largest
+    |value| over ALL shards of the group (every rank holds the same number): the weight of a search is checked against it.
+    An append to the group invalidates it ("prior made before an append; make another"); removals and updates do not."""
+
+    def __init__(self, group: "ShardedSearcher", parts, max_abs: float, n: int):
+        self.group, self.parts, self.max_abs, self.num_docs = group, list(parts), float(max_abs), int(n)
+        self.closed = False
+
+    def close(self):
+        self.closed = True
+        for p in self.parts:
+            p.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self):
+        return self.num_docs
 
 
 class ShardedFilter:
@@ -353,6 +401,37 @@ class ShardedSearcher:
             raise ArgumentError("grouping made before an append; make another")
         return grouping
 
+    # -- priors -----------------------------------------------------------------------------------
+    def make_prior(self, values) -> ShardedPrior:
+        """A resident per-passage score term over the group, for `prior=` of the search calls: `values`, one finite number
+        per passage of the GROUP (`num_docs` entries, entry i = global pid first + i + 1) as a numpy array (converted to
+        float32).  Checked on the host before any shard is called: a wrong length or a value that is not finite in fp32 is an
+        ArgumentError naming the first offending GLOBAL pid.  Every rank passes the same array, as with make_grouping."""
+        v, slices = slice_prior(values, self._bounds)
+        parts = []
+        try:
+            for j, s in enumerate(self.shards):
+                parts.append(s.make_prior(np.ascontiguousarray(slices[self._first + j])))
+            m = np.float32(max([p.max_abs for p in parts] + [0.0]))
+            if self.group is not None:        # non-negative floats order as their bits
+                m = self._gather(np.array([[int(m.view(np.int32))]], dtype=np.int64)).max().astype(np.int32).view(np.float32)
+        except Exception:
+            for p in parts:
+                p.close()
+            raise
+        return ShardedPrior(self, parts, float(m), v.size)
+
+    def _check_prior(self, prior, prior_weight, per_group):
+        """`prior=` / `prior_weight=` of a search call -> (the ShardedPrior or None, the weight for every shard)."""
+        if prior is None:
+            return None, 1.0
+        _no_prior_hits(per_group)
+        if not isinstance(prior, ShardedPrior) or prior.group is not self or prior.closed:
+            raise ColBERTError("prior is not an open ShardedPrior of this shard group")
+        if prior.num_docs != self.num_docs:
+            raise ArgumentError("prior made before an append; make another")
+        return prior, _weight_value(prior_weight, prior.max_abs)      # against the GROUP's largest |value|
+
     # -- search -----------------------------------------------------------------------------------
     def _run(self, i: int, T: int, B: int, k: int, nprobe: int):
         from .distributed import DeviceSearch
@@ -365,7 +444,7 @@ class ShardedSearcher:
         """every local shard runs the two-pass mode for queries of T tokens (set the mode alike on all ranks)"""
         return all(s.mode == 1 for s in self.shards) and T <= 32
 
-    def _piece_grouped(self, runs, Qd, B: int, k: int, filters, scope: str, two_phase: bool, grouping):
+    def _piece_grouped(self, runs, Qd, B: int, k: int, filters, scope: str, two_phase: bool, grouping, prior=None, weight=1.0):
         """_piece with a grouping: between the phases the shards' k best groups travel as (score, global group index); at the
         end every shard's packed grouped block (pids, scores, group indices, candidate groups, edge groups) is gathered and
         merged with one record per group."""
@@ -374,25 +453,39 @@ class ShardedSearcher:
         L = len(self.shards)
         dev0 = runs[0].dev
         f = [None if filters is None else filters[i] for i in range(L)]
+        pr = [None if prior is None else prior.parts[i] for i in range(L)]
         if two_phase:
-            outs = [r.phase1(Qd[i], f[i], scope, grouping.parts[i], grouping.bases[i]) for i, r in enumerate(runs)]
+            outs = [r.phase1(Qd[i], f[i], scope, grouping.parts[i], grouping.bases[i], pr[i], weight) for i, r in enumerate(runs)]
             top = torch.stack([o[0].to(dev0) for o in outs]).view(L * B, k)
             gid = torch.stack([o[1].to(dev0) for o in outs]).view(L * B, k)
             if self.group is not None:
                 top = self._gather_tensor(top, all_gather_scores)
                 gid = self._gather_tensor(gid, all_gather_scores)
             top, gid = top.reshape(-1, B, k), gid.reshape(-1, B, k)
-            blocks = [r.phase2(Qd[i], top.to(r.dev).contiguous(), gid.to(r.dev).contiguous(), grouping.parts[i], grouping.bases[i])
+            mabs = None if prior is None else self._gather_mabs([o[2] for o in outs], dev0, B)
+            blocks = [r.phase2(Qd[i], top.to(r.dev).contiguous(), gid.to(r.dev).contiguous(), grouping.parts[i], grouping.bases[i],
+                               pr[i], weight, None if mabs is None else mabs.to(r.dev).contiguous())
                       for i, r in enumerate(runs)]
         else:
-            blocks = [r.search_grouped_shard(Qd[i], f[i], scope, grouping.parts[i], grouping.bases[i]) for i, r in enumerate(runs)]
+            blocks = [r.search_grouped_shard(Qd[i], f[i], scope, grouping.parts[i], grouping.bases[i], pr[i], weight)
+                      for i, r in enumerate(runs)]
         block = torch.cat([x.to(dev0) for x in blocks])
         g = self._gather_tensor(block, all_gather_packed) if self.group is not None else block.view(1, -1)
         lists = g.to(dev0).contiguous().view(-1, packed_grouped_bytes(k, B))
         mp, ms, n = merge_grouped_packed(lists, B, k)
         return mp.cpu().numpy(), ms.cpu().numpy(), n.cpu().numpy()
 
-    def _piece(self, q, k: int, nprobe: int, filters, scope: str, two_phase: bool, grouping=None):
+    def _gather_mabs(self, parts, dev0, B: int):
+        """The shards' largest boosted approximate scores by magnitude ([B] each) -> (n_shards, B) over the whole group: the
+        extra number per query and shard that travels between the phases of a search with a prior."""
+        import torch
+        from .distributed import all_gather_scores
+        m = torch.stack([p.to(dev0) for p in parts]).view(-1, 1)
+        if self.group is not None:
+            m = self._gather_tensor(m, all_gather_scores)
+        return m.reshape(-1, B)
+
+    def _piece(self, q, k: int, nprobe: int, filters, scope: str, two_phase: bool, grouping=None, prior=None, weight=1.0):
         """One exchange for the queries q (dim, T, B <= 64) -> (pids (B, k), scores (B, k), n_cand [B]) as numpy."""
         import torch
         from .distributed import all_gather_packed, all_gather_scores, merge_packed, packed_topk_bytes
@@ -402,8 +495,20 @@ class ShardedSearcher:
         runs = [self._run(i, T, B, k, nprobe) for i in range(L)]
         Qd = [host_q.to(r.dev) for r in runs]
         if grouping is not None:
-            return self._piece_grouped(runs, Qd, B, k, filters, scope, two_phase, grouping)
-        if two_phase:
+            return self._piece_grouped(runs, Qd, B, k, filters, scope, two_phase, grouping, prior, weight)
+        if two_phase and prior is not None:
+            f = [None if filters is None else filters[i] for i in range(L)]
+            outs = [r.phase1(Qd[i], f[i], scope, prior=prior.parts[i], prior_weight=weight) for i, r in enumerate(runs)]
+            dev0 = runs[0].dev
+            local = torch.stack([o[0].to(dev0) for o in outs]).view(L * B, k)
+            if self.group is not None:
+                local = self._gather_tensor(local, all_gather_scores)
+            all_top = local.reshape(-1, B, k)
+            mabs = self._gather_mabs([o[2] for o in outs], dev0, B)
+            for i, r in enumerate(runs):
+                r.phase2(Qd[i], all_top.to(r.dev).contiguous(), prior=prior.parts[i], prior_weight=weight,
+                         all_mabs=mabs.to(r.dev).contiguous())
+        elif two_phase:
             tops = [r.phase1(Qd[i], None if filters is None else filters[i], scope) for i, r in enumerate(runs)]
             dev0 = runs[0].dev
             local = torch.stack([t.to(dev0) for t in tops]).view(L * B, k)             # this process's blocks
@@ -414,7 +519,8 @@ class ShardedSearcher:
                 r.phase2(Qd[i], all_top.to(r.dev).contiguous())
         else:
             for i, r in enumerate(runs):
-                r(Qd[i], None if filters is None else filters[i], scope)
+                r(Qd[i], None if filters is None else filters[i], scope, prior=None if prior is None else prior.parts[i],
+                  prior_weight=weight)
         # one block per process: its shards' packed top-k lists, then its candidate counts
         dev0 = runs[0].dev
         nbytes = packed_topk_bytes(k, B)
@@ -428,7 +534,8 @@ class ShardedSearcher:
         return mp.cpu().numpy(), ms.cpu().numpy(), n.cpu().numpy()
 
     def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
-                     scope="candidates", protocol="auto", grouping=None, per_group=None, after=None):
+                     scope="candidates", protocol="auto", grouping=None, per_group=None, after=None, prior=None,
+                     prior_weight=1.0):
         """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B]), GLOBAL pids, layouts and padding (pid 0 /
         -Inf) as `Searcher.search_batch`; n_candidates is the sum over the shards.  `filters`: one ShardedFilter or a sequence
         of B entries (None = that query is unfiltered); with filters the result is always padded.  Without, a query for which
@@ -439,9 +546,15 @@ class ShardedSearcher:
         its best passage (`grouping.groups_of(pids)` names them), exactly as `Searcher.search_batch(grouping=)` on the
         unsharded index does; n_candidates counts the candidate groups, a group that straddles shards once.  Composes with
         `filters` in both scopes, under every protocol.
+        `prior` (one ShardedPrior of this group for the whole batch) with `prior_weight`: rank by
+        E = fl32(score + fl32(prior_weight * value)), the lower pid first among equal E, and return E -- exactly the result of
+        `Searcher.search_batch(prior=)` on the unsharded index: pids, fp32 score bits, counts.  Composes with `filters` and
+        with `grouping` (a group is represented by its candidate with the largest E), under every protocol.  The weight must be
+        finite and keep |weight| * max|value| (over the whole group) below FLT_MAX: ArgumentError.
         `per_group`: anything but None raises Unsupported (the hits of a grouped search are a single handle's), and so does
         `after` (a cursor continues the ranking of a single handle)."""
-        self._no_per_group(per_group)
+        if prior is None:       # (with a prior the refusal is the single handle's: _check_prior)
+            self._no_per_group(per_group)
         self._no_after(after)
         q = colmajor(Q, np.float32)
         if q.ndim != 3 or q.shape[0] != self.dim:
@@ -450,6 +563,7 @@ class ShardedSearcher:
             raise ColBERTError(f"protocol must be one of {_PROTOCOLS}, got {protocol!r}")
         _scope_code(scope)
         grouping = self._check_grouping(grouping)
+        prior, weight = self._check_prior(prior, prior_weight, per_group)
         k, B = int(k), q.shape[2]
         nprobe = int(nprobe or self.shards[0].config.nprobe)
         per_shard = self._shard_filters(filters, B)
@@ -459,7 +573,7 @@ class ShardedSearcher:
         for b0 in range(0, B, _PIECE):
             b1 = min(B, b0 + _PIECE)
             f = None if per_shard is None else [x[b0:b1] for x in per_shard]
-            p, s, n = self._piece(q[:, :, b0:b1], k, nprobe, f, scope, two_phase, grouping)
+            p, s, n = self._piece(q[:, :, b0:b1], k, nprobe, f, scope, two_phase, grouping, prior, weight)
             pids[:, b0:b1] = p.T; scores[:, b0:b1] = s.T; ncand[b0:b1] = n
         if filters is None and not pad_short:
             short = np.nonzero(ncand < k)[0]
@@ -482,29 +596,33 @@ class ShardedSearcher:
                               "Searcher")
 
     def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates", protocol="auto",
-                          grouping=None, per_group=None, after=None):
+                          grouping=None, per_group=None, after=None, prior=None, prior_weight=1.0):
         """One query, Q (dim, T) -> (pids Int64[k], scores Float32[k]) as `Searcher.search_embeddings`; the candidate count
-        (with a grouping: the candidate groups) is left in `last_num_candidates`."""
-        self._no_per_group(per_group)
+        (with a grouping: the candidate groups) is left in `last_num_candidates`.  `prior` / `prior_weight`: search_batch."""
+        if prior is None:
+            self._no_per_group(per_group)
         self._no_after(after)
         q = colmajor(Q, np.float32)
         if q.ndim != 2 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T)")
         p, s, n = self.search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe,
                                     filters=None if filter is None else [filter], scope=scope, protocol=protocol,
-                                    grouping=grouping)
+                                    grouping=grouping, per_group=per_group, prior=prior, prior_weight=prior_weight)
         self.last_num_candidates = int(n[0])
         return np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(s[:, 0])
 
     def search(self, query: str, k: int, *, filter=None, scope="candidates", protocol="auto", grouping=None, per_group=None,
-               after=None):
+               after=None, prior=None, prior_weight=1.0):
         """search(searcher, query::String, k) over the group, with the attached encoder."""
-        self._no_per_group(per_group)
+        if prior is None:
+            self._no_per_group(per_group)
         self._no_after(after)
+        self._check_prior(prior, prior_weight, per_group)         # before the encoder runs
         if self.encoder is None:
             raise ColBERTError("no query encoder attached: pass encoder=... or use search_embeddings(Q, k)")
         Q = self.encoder.encode_queries([query])
-        return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope, protocol=protocol, grouping=grouping)
+        return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope, protocol=protocol, grouping=grouping,
+                                      prior=prior, prior_weight=prior_weight)
 
     # -- append: to the LAST shard, the only range that can grow without colliding with a neighbour -------------------
     def _owns_last(self) -> bool:

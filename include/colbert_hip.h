@@ -421,7 +421,10 @@ int clb_search_batch_grouped_hits_device_slot(clb_searcher* s, int slot, const f
  * including calls still enqueued on a stream or captured in a graph; it may be destroyed before or after its searcher.
  * Creation synchronises; searching with it does not.  The hits of a grouped search (clb_search_batch_grouped_hits*) take no
  * prior -- their extended list is built from approximate MaxSim scores; the Python driver answers `per_group` together with a
- * prior with Unsupported, naming both -- nor do the phase calls of a shard group.
+ * prior with Unsupported, naming both.
+ * Entry points that take a prior: clb_search_batch_prior, clb_search_batch_prior_device_slot and, for a shard group, the two
+ * phase calls clb_search_shard_phase1_prior_slot / clb_search_shard_phase2_prior_slot ("Score priors across a shard group"
+ * below); the other phase calls take none.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct clb_prior clb_prior;
 int clb_prior_create(clb_searcher* s, const float* values, int64_t n, clb_prior** out);
@@ -535,6 +538,53 @@ int clb_search_result_groups_slot(clb_searcher* s, int slot, const clb_grouping*
  * lowest or the highest of each. */
 int clb_debug_group_tau_device(const float* d_all_top, const int64_t* d_all_gid, int64_t n_shards, int64_t B, int64_t k,
                                float* d_tau, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Score priors across a shard group.  Every shard holds a clb_prior made from ITS slice of the values, and every shard gets
+ * the same weight; the caller checks |weight| * max|value| against the largest clb_prior_max_abs of the group.  The result of
+ * the two phases and the merge equals the unsharded clb_search_batch_prior: pids, fp32 score bits, counts.  Two-pass mode only.
+ *
+ *   phase 1: clb_search_shard_phase1_grouped_slot up to pass 1, then A = fl(a + fl(weight * value)) written over the slot's
+ *            approximate scores for ALL candidates; with a grouping the groups collapse on A.  d_local_top (B, k) = the
+ *            shard's k largest A per query (with a grouping: the best A of its k best groups, and d_local_gid their global
+ *            indices), in no order, padded with -Inf / -1; d_local_mabs [B] = M_i, the largest |A| over the shard's
+ *            candidates of the query (0 without candidates).  The caller all-gathers all three: d_all_top / d_all_gid =
+ *            [n_shards][B][k], d_all_mabs = [n_shards][B];
+ *   phase 2: tau = the k-th largest gathered A (with a grouping over the DISTINCT indices, as the grouped phase 2; -Inf with
+ *            fewer than k), M = max_i M_i, delta = 4 * 2^-24 * (M + eps) with eps the query's error bound under the shared
+ *            constants, and the selection cuts at tau - 2 delta - 2 eps (-Inf for an unsafe query or a non-finite M); then the
+ *            row sweep, the exact pass, E = fl(e + pi) over the re-scored, with a grouping the collapse on E, the top-k.
+ *            Outputs as the grouped phase 2; d_all_gid, d_out_gids and d_edge_gids are ignored (may be NULL) without a
+ *            grouping.
+ *   merge:   clb_merge_topk_packed_device, or with a grouping clb_merge_topk_grouped_packed_device: both order by (score
+ *            descending, pid ascending), which is the order of E.
+ * M must be the maximum over ALL shards: a shard that cut with its own M_i could lose a member of the top k that another
+ * shard's large prior values pushed tau towards.
+ * Everything else follows the grouped phase calls: slot rules, stream order, no host synchronisation, nothing allocated
+ * after a slot's first such phase 1, capturable, at most 64 queries when one is filtered, at most 256 shards with a grouping,
+ * CLB_EUNSUPPORTED outside the two-pass mode, the refusal of phase 2 before the bound constants are shared.  The prior is
+ * checked as in clb_search_batch_prior (another searcher's, made before an append, the weight: CLB_EARGUMENT); a null
+ * d_local_mabs / d_all_mabs or output is CLB_EARGUMENT.  Phase 2 must follow the prior phase 1 of the same batch, prior,
+ * weight (bit for bit), grouping and group_base on that slot: anything else, the other phase-2 calls included, is
+ * CLB_EARGUMENT.  prior == NULL in phase 1 launches exactly what clb_search_shard_phase1_grouped_slot launches and leaves
+ * d_local_mabs untouched (phase 2 is then one of the calls without a prior); prior == NULL in phase 2 is CLB_EARGUMENT.
+ * The single exchange needs nothing new: clb_search_batch_prior_device_slot on every shard, then with a grouping
+ * clb_search_result_groups_slot, then the merge.
+ * ---------------------------------------------------------------------------------------------- */
+int clb_search_shard_phase1_prior_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                       int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
+                                       int64_t group_base, const clb_prior* prior, float weight, float* d_local_top,
+                                       int64_t* d_local_gid, float* d_local_mabs, void* hip_stream);
+int clb_search_shard_phase2_prior_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                       int64_t k, const float* d_all_top, const int64_t* d_all_gid,
+                                       const float* d_all_mabs /* [n_shards][B] */, int64_t n_shards,
+                                       const clb_grouping* grouping, int64_t group_base, const clb_prior* prior, float weight,
+                                       int64_t* d_out_pids, float* d_out_scores, int64_t* d_out_gids, int64_t* d_n_cand,
+                                       int64_t* d_edge_gids, void* hip_stream);
+/* Test hook: the threshold kernel of the prior phase 2 alone, d_tau_in[b] = tau - 2 delta from d_all_top / d_all_gid (may be
+ * NULL: no grouping) / d_all_mabs and d_eps [B] in place of the queries' own error bounds. */
+int clb_debug_prior_tau_device(const float* d_all_top, const int64_t* d_all_gid, const float* d_all_mabs, const float* d_eps,
+                               int64_t n_shards, int64_t B, int64_t k, float* d_tau_in, void* hip_stream);
 
 /* retrieve()  (src/search/ranking.jl:23-44) on its own -- test hook.  out_pids needs n_docs entries. */
 int clb_retrieve(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe, int64_t* out_pids,
