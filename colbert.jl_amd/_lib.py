@@ -68,6 +68,28 @@ def declared_symbols() -> list[str]:
     return sorted(set(re.findall(r"\b(clb_[a-z0-9_]+)\s*\(", text)))
 
 
+class SearchRequest(C.Structure):
+    """clb_search_request (include/colbert_hip.h), field for field: what a search call carries besides queries, sizes and outputs."""
+    _fields_ = [("struct_bytes", C.c_int64), ("filters", C.POINTER(C.c_void_p)), ("scope", C.c_int), ("pad_short", C.c_int),
+                ("grouping", C.c_void_p), ("per_group", C.c_int64), ("group_base", C.c_int64), ("prior", C.c_void_p),
+                ("prior_weight", C.c_float), ("after_scores", C.c_void_p), ("after_pids", C.c_void_p)]
+
+
+_entries = {}
+
+
+def request_entry(name: str):
+    """One of the four entry points that take a SearchRequest (every search of this package goes through them), resolved once."""
+    fn = _entries.get(name)
+    if fn is None:
+        fn = getattr(lib(), name, None)
+        if fn is None:
+            raise ColBERTError(f"{LIB_PATH} lacks {name}: a library built before the search request entry points cannot be "
+                               "driven by this package (COLBERT_HIP_LIB) -- drive it from its own checkout")
+        _entries[name] = fn
+    return fn
+
+
 _lib = None
 
 
@@ -177,6 +199,17 @@ def lib() -> C.CDLL:
                                                              C.c_float, vp, vp, vp, vp, vp, vp]
             l.clb_debug_prior_tau_device.restype = ci
             l.clb_debug_prior_tau_device.argtypes = [vp, vp, vp, vp, i64_, i64_, i64_, vp, vp]
+        if hasattr(l, "clb_search_batch_request"):              # (absent from a COLBERT_HIP_LIB build of an earlier commit: request_entry)
+            rq = C.POINTER(SearchRequest)
+            l.clb_search_batch_request.restype = ci
+            l.clb_search_batch_request.argtypes = [vp, vp, i64_, i64_, i64_, i64_, rq, vp, vp, vp]
+            l.clb_search_batch_request_device_slot.restype = ci
+            l.clb_search_batch_request_device_slot.argtypes = [vp, ci, vp, i64_, i64_, i64_, i64_, rq, vp, vp, vp, vp]
+            l.clb_search_shard_phase1_request_slot.restype = ci
+            l.clb_search_shard_phase1_request_slot.argtypes = [vp, ci, vp, i64_, i64_, i64_, i64_, rq, vp, vp, vp, vp]
+            l.clb_search_shard_phase2_request_slot.restype = ci
+            l.clb_search_shard_phase2_request_slot.argtypes = [vp, ci, vp, i64_, i64_, i64_, i64_, rq, vp, vp, vp, i64_, vp, vp, vp,
+                                                               vp, vp, vp]
         l.clb_merge_topk_grouped_device.restype = ci
         l.clb_merge_topk_grouped_device.argtypes = [ci, vp, vp, vp, i64_, i64_, i64_, vp, vp, vp, vp, vp, vp]
         l.clb_packed_grouped_bytes.restype = i64_

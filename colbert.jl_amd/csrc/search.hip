@@ -622,7 +622,7 @@ int mark_and_compact(clb_searcher* s, Workspace& w, hipStream_t st, const Batch&
                 : mark_and_compact_impl<false>(s, w, st, q, b0, B, Tpad, NPs, timed);
 }
 
-int check_search_args(clb_searcher* s, int64_t T, int64_t B, int64_t nprobe, int64_t k) {
+int check_search_args(const clb_searcher* s, int64_t T, int64_t B, int64_t nprobe, int64_t k) {
     if (!s) return fail(CLB_EARGUMENT, "null searcher");
     if (T < 1) return fail(CLB_EARGUMENT, "query length must be >= 1");
     if (B < 1) return fail(CLB_EARGUMENT, "batch size must be >= 1");
@@ -860,6 +860,14 @@ void launch_pass1(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ
 inline float bound_dc(const clb_searcher* s, const Workspace& w) {
     return (w.x1_table || (s->bounds_synced && s->s1_x1 != 0 && s->cent_f16.p)) ? s->dc_f16 : 0.f;
 }
+// What every kernel that evaluates the error bound of this batch takes: the handle's constants with that centroid term, the
+// score ranges the batched centroid kernel measured (or none) and the row format of the score table
+struct BoundOperands { ApproxConsts ac; const float4* tscale; int cell8; };
+inline BoundOperands bound_operands(const clb_searcher* s, const Workspace& w) {
+    ApproxConsts ac = s->approx_consts;
+    ac.dc_max = bound_dc(s, w);
+    return {ac, w.have_range ? (const float4*)w.tscale.as<float4>() : (const float4*)nullptr, w.cell8 ? 1 : 0};
+}
 int launch_select(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, const float* tau_in, bool coarse_tau = false) {
     const float* dQ = q.dQ;
     const int B = q.B, T = q.T, k = q.k;
@@ -867,23 +875,18 @@ int launch_select(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q,
     // goes on selecting its unfiltered batches as before
     const size_t most = std::max(w.ivf_cap, q.filt_now);
     const bool wide = s->wide_select == 1 || (s->wide_select < 0 && most >= kWideSelectCap);
+    const BoundOperands bo = bound_operands(s, w);
     if (!wide) {
-        ApproxConsts ac = s->approx_consts;
-        ac.dc_max = bound_dc(s, w);
         hipLaunchKernelGGL(select_margin_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), dQ, T, k,
-                           w.cand_cap, ac, w.list.as<int>(), w.nlist.as<int>(), w.thresh.as<float>(),
-                           w.eps_pair.as<float>(), tau_in, coarse_tau ? 1 : 0,
-                           w.have_range ? (const float4*)w.tscale.as<float4>() : (const float4*)nullptr, w.cell8 ? 1 : 0);
+                           w.cand_cap, bo.ac, w.list.as<int>(), w.nlist.as<int>(), w.thresh.as<float>(),
+                           w.eps_pair.as<float>(), tau_in, coarse_tau ? 1 : 0, bo.tscale, bo.cell8);
         return CLB_OK;
     }
     CLB_TRY(w.wsel.ensure(sizeof(WideSel) * B));
     CLB_HIP(hipMemsetAsync(w.wsel.p, 0, sizeof(WideSel) * B, st));
     const dim3 grid(kWideBlocks, B);
-    ApproxConsts acw = s->approx_consts;
-    acw.dc_max = bound_dc(s, w);
     hipLaunchKernelGGL(wide_minmax_kernel, grid, dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), dQ, T, w.cand_cap,
-                       acw, w.wsel.as<WideSel>(), w.eps_pair.as<float>(),
-                       w.have_range ? (const float4*)w.tscale.as<float4>() : (const float4*)nullptr, w.cell8 ? 1 : 0);
+                       bo.ac, w.wsel.as<WideSel>(), w.eps_pair.as<float>(), bo.tscale, bo.cell8);
     if (!tau_in)
         for (int pass = 0; pass < 4; ++pass)
             hipLaunchKernelGGL(wide_hist_kernel, grid, dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), k, w.cand_cap,
@@ -918,12 +921,9 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
         CLB_TRY(w.tau_glob.ensure(sizeof(float) * B));
         if (q.prior) {  // the k-th largest BOOSTED score (the k-th best group's) over the shards, lowered by the rounding slack at
                         // the largest magnitude any shard saw (prior_global_tau_kernel)
-            ApproxConsts ac = s->approx_consts;
-            ac.dc_max = bound_dc(s, w);
+            const BoundOperands bo = bound_operands(s, w);
             hipLaunchKernelGGL(prior_global_tau_kernel, dim3(B), dim3(1024), 0, st, q.d_all_top, q.d_all_gid, q.d_all_mabs,
-                               q.n_shards, B, k, (const float*)nullptr, dQ, T, ac,
-                               w.have_range ? (const float4*)w.tscale.as<float4>() : (const float4*)nullptr, w.cell8 ? 1 : 0,
-                               w.tau_glob.as<float>());
+                               q.n_shards, B, k, (const float*)nullptr, dQ, T, bo.ac, bo.tscale, bo.cell8, w.tau_glob.as<float>());
         } else if (q.grp)      // the k-th best GROUP over the shards: a group that straddles a cut counts once
             hipLaunchKernelGGL(group_global_tau_kernel, dim3(B), dim3(1024), 0, st, q.d_all_top, q.d_all_gid, q.n_shards, B, k,
                                w.tau_glob.as<float>());
@@ -962,24 +962,19 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
                 float* mabs = ptau + w.Bcap;
                 launch_boost(w, st, q, 0, B, nullptr, nullptr, mabs);
                 if (q.grp) launch_collapse(w, st, q, 0, B, nullptr, nullptr, w.grp_list.as<int>(), w.grp_n.as<int>());
-                ApproxConsts ac = s->approx_consts;
-                ac.dc_max = bound_dc(s, w);
+                const BoundOperands bo = bound_operands(s, w);
                 hipLaunchKernelGGL(prior_tau_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(),
                                    q.grp ? (const int*)w.grp_list.as<int>() : (const int*)nullptr,
                                    q.grp ? (const int*)w.grp_n.as<int>() : (const int*)nullptr, k, w.cand_cap, (const float*)mabs,
-                                   dQ, T, ac, w.have_range ? (const float4*)w.tscale.as<float4>() : (const float4*)nullptr,
-                                   w.cell8 ? 1 : 0, ptau);
+                                   dQ, T, bo.ac, bo.tscale, bo.cell8, ptau);
                 CLB_TRY(launch_select(s, w, st, q, (const float*)ptau));
             } else if (q.d_after_s) {
                 // with cursors (phase 0 only): the cut sits at the k-th largest approximate score of the candidates that are
                 // SURELY after the cursor, and those surely before it leave the selection (after_cut_kernel)
                 Timed t(s, KID_SELECT, st);
-                ApproxConsts ac = s->approx_consts;
-                ac.dc_max = bound_dc(s, w);
+                const BoundOperands bo = bound_operands(s, w);
                 hipLaunchKernelGGL(after_cut_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), k,
-                                   w.cand_cap, q.d_after_s, dQ, T, ac,
-                                   w.have_range ? (const float4*)w.tscale.as<float4>() : (const float4*)nullptr, w.cell8 ? 1 : 0,
-                                   w.after_tau.as<float>());
+                                   w.cand_cap, q.d_after_s, dQ, T, bo.ac, bo.tscale, bo.cell8, w.after_tau.as<float>());
                 CLB_TRY(launch_select(s, w, st, q, (const float*)w.after_tau.as<float>()));
             } else {
                 Timed t(s, KID_SELECT, st);
@@ -1098,7 +1093,7 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
     return CLB_OK;
 }
 
-// the filters of a call (a host array of B handles, or nullptr): every one must be this searcher's; *filt_count = the largest
+// the filters of a request (a host array of B handles, or nullptr): every one must be this searcher's; *filt_count = the largest
 // population a CLB_FILTER_ALL search has to hold as a candidate set (a host value: sizing the workspace needs no read-back)
 int check_filters(const clb_searcher* s, const clb_filter* const* filters, int64_t B, int scope, size_t* filt_count) {
     *filt_count = 0;
@@ -1117,11 +1112,10 @@ int check_filters(const clb_searcher* s, const clb_filter* const* filters, int64
     return CLB_OK;
 }
 
-// the prior of a call (or nullptr) and its weight: the prior must be this searcher's, made for the passages it holds now, and
-// weight * value must be finite for every value
+// the prior of a request (or nullptr) and its weight, which check_request has found finite: the prior must be this searcher's,
+// made for the passages it holds now, and weight * value must be finite for every value
 int check_prior(const clb_searcher* s, const clb_prior* p, float weight) {
     if (!p) return CLB_OK;
-    if (!std::isfinite(weight)) return fail(CLB_EARGUMENT, "prior_weight must be finite, got %g", (double)weight);
     if (p->owner != s->serial) return fail(CLB_EARGUMENT, "the prior was made for another searcher");
     if (p->n_docs != s->n_docs)     // its table has the old length
         return fail(CLB_EARGUMENT, "prior made before an append; make another");
@@ -1130,11 +1124,8 @@ int check_prior(const clb_searcher* s, const clb_prior* p, float weight) {
                     (double)p->max_abs);
     return CLB_OK;
 }
-struct PriorArg { const clb_prior* p = nullptr; float weight = 1.f; };
-// the cursors of a call, one (score, pid) per query -- host arrays on the host route, device arrays on the device route -- or none
-struct AfterArg { const float* s = nullptr; const int64_t* p = nullptr; };
 
-// the grouping of a call (or nullptr): it must be this searcher's, made for the passages it holds now
+// the grouping of a request (or nullptr): it must be this searcher's, made for the passages it holds now
 int check_grouping(const clb_searcher* s, const clb_grouping* g) {
     if (!g) return CLB_OK;
     if (g->owner != s->serial) return fail(CLB_EARGUMENT, "the grouping was made for another searcher");
@@ -1143,13 +1134,83 @@ int check_grouping(const clb_searcher* s, const clb_grouping* g) {
     return CLB_OK;
 }
 
-// q's filter operands: queries b0 .. b0 + q.B - 1 of a call whose handle array is `filters` (checked by check_filters, which
-// gave filt_count)
-void set_batch_filters(Batch& q, const clb_filter* const* filters, int64_t b0, int scope, size_t filt_count) {
-    q.filt_all = scope == CLB_FILTER_ALL;
-    for (int64_t b = b0; filters && b < b0 + q.B; ++b)
-        if (filters[b]) q.filt = filters + b0;
+int bad_per_group(int64_t per_group) {
+    return fail(CLB_EARGUMENT, "per_group must be 1..%d, got %lld", CLB_MAX_PER_GROUP, (long long)per_group);
+}
+int hits_without_grouping() { return fail(CLB_EARGUMENT, "grouping is null: per_group needs a grouping"); }
+
+// The four ways a request reaches run_search: they differ in where the cursor arrays live (host / device memory) and in the
+// fields they offer (the phases of a shard group take no hits and no cursors, phase 2 no filters)
+enum class Route { host, device, phase1, phase2 };
+
+// hits per result of a request: one hit per result is the representative, exactly the grouped search
+inline int64_t request_hits(const clb_search_request& r) { return r.per_group > 1 ? r.per_group : 0; }
+
+// EVERY rule of a search request and of the sizes of its call, in the order the entry points have always answered: first
+// what needs no searcher -- the struct itself, the per_group range, a finite weight, the cursor pair, the combinations that
+// are not offered, NaN cursors where the host can see them -- then the handle and the sizes (check_search_args), the route's
+// buffers and phase 1's group_base, then what is bound to the searcher (filters, grouping, prior) and the batch limit of a
+// filtered phase 1.  *filt_count as check_filters gives it.
+// route_buffers(): the route's own refusals of its plain parameters (the exchange buffers of a phase), answered where they
+// always were -- directly behind the sizes.
+template <class RouteBuffers>
+int check_request(const clb_searcher* s, const clb_search_request* r, int64_t T, int64_t B, int64_t nprobe, int64_t k, Route route,
+                  size_t* filt_count, RouteBuffers route_buffers) {
+    *filt_count = 0;
+    if (!r) return fail(CLB_EARGUMENT, "the search request is null");
+    if (r->struct_bytes != (int64_t)sizeof(clb_search_request))
+        return fail(CLB_EARGUMENT, "struct_bytes of the search request is %lld, not sizeof(clb_search_request) = %zu",
+                    (long long)r->struct_bytes, sizeof(clb_search_request));
+    if (r->per_group < 0 || r->per_group > CLB_MAX_PER_GROUP) return bad_per_group(r->per_group);
+    if (r->per_group && !r->grouping) return hits_without_grouping();
+    if (r->prior && !std::isfinite(r->prior_weight))
+        return fail(CLB_EARGUMENT, "prior_weight must be finite, got %g", (double)r->prior_weight);
+    if ((r->after_scores == nullptr) != (r->after_pids == nullptr))
+        return fail(CLB_EARGUMENT, "after_scores and after_pids must both be given or both be null");
+    const bool after = r->after_scores != nullptr, phases = route == Route::phase1 || route == Route::phase2;
+    if (r->prior && r->per_group > 1)       // group_extend_kernel builds the extended list from approximate MaxSim scores
+        return fail(CLB_EUNSUPPORTED, "per_group together with a prior is not supported: the hits of a grouped search take no prior");
+    if (after && r->grouping)               // a cursor continues the ranking of PASSAGES by MaxSim
+        return fail(CLB_EUNSUPPORTED, "cursors together with a grouping are not supported");
+    if (after && r->prior) return fail(CLB_EUNSUPPORTED, "cursors together with a prior are not supported");
+    if (phases && r->per_group > 1) return fail(CLB_EUNSUPPORTED, "the phase calls of a shard group take no per_group");
+    if (phases && after) return fail(CLB_EUNSUPPORTED, "the phase calls of a shard group take no cursors");
+    if (route == Route::phase2 && r->filters)
+        return fail(CLB_EARGUMENT, "phase 2 takes no filters: it continues on the candidates phase 1 left on the slot");
+    for (int64_t b = 0; route == Route::host && after && b < B; ++b)
+        if (std::isnan(r->after_scores[b])) return fail(CLB_EARGUMENT, "the cursor score of query %lld is NaN", (long long)b);
+    CLB_TRY(check_search_args(s, T, B, nprobe, k));
+    CLB_TRY(route_buffers());
+    if (route == Route::phase1 && r->grouping && r->group_base < 0)
+        return fail(CLB_EARGUMENT, "group_base must be >= 0, got %lld", (long long)r->group_base);
+    CLB_TRY(check_filters(s, r->filters, B, r->scope, filt_count));
+    CLB_TRY(check_grouping(s, r->grouping));
+    CLB_TRY(check_prior(s, r->prior, r->prior_weight));
+    if (route == Route::phase1) {
+        bool filtered = false;
+        for (int64_t b = 0; r->filters && b < B; ++b) filtered |= r->filters[b] != nullptr;
+        // the whole batch stays on the slot for phase 2, and the filter handles of a launch travel in one argument block
+        if (filtered && B > kFilterQueries)
+            return fail(CLB_EUNSUPPORTED, "a filtered clb_search_shard_phase1 takes at most %d queries per call, got %lld: split the batch",
+                        kFilterQueries, (long long)B);
+    }
+    return CLB_OK;
+}
+
+// The sub-batch of queries b0 .. b0 + B - 1 of a call that carries the request r (checked by check_request, which gave
+// filt_count), with everything of r that every route hands to run_search alike: the sub-batch's slice of the handle array --
+// nullptr when none of its queries is filtered --, the grouping with its base and hits, the prior with its weight.  The
+// cursors stay with the route: it knows where they live.
+Batch make_batch(const float* dQ, int64_t B, int64_t T, int64_t nprobe, int64_t k, const clb_search_request& r, int64_t b0,
+                 size_t filt_count) {
+    Batch q = make_batch(dQ, B, T, nprobe, k);
+    q.filt_all = r.scope == CLB_FILTER_ALL;
+    for (int64_t b = b0; r.filters && b < b0 + q.B; ++b)
+        if (r.filters[b]) q.filt = r.filters + b0;
     q.filt_now = q.filt && q.filt_all ? filt_count : 0;
+    q.grp = r.grouping; q.group_base = r.group_base; q.per_group = (int)request_hits(r);
+    q.prior = r.prior; q.prior_weight = r.prior_weight;
+    return q;
 }
 
 // the workspace of a slot of the *_slot entry points, with the searcher's device made current
@@ -1165,30 +1226,18 @@ int slot_workspace(clb_searcher* s, int slot, Workspace** w) {
 // the 256-MB Infinity Cache before pass 1 reads them (measured: 29.4 k queries/s at 64, 27.8 k at 256 in one piece);
 // the centroid kernel shares a staged tile between 16 queries whatever the batch, so nothing is lost above that.
 // (The two-phase sharded calls keep the whole batch: phase 2 continues on the scratch of phase 1.)
-// run_one(b0, q): points q at the queries and outputs of the sub-batch that starts at query b0 and runs it.  q arrives with
-// the sub-batch's size, its slice of the handle array -- nullptr when none of its queries is filtered -- and stats_keep set
-// grp: the grouping of a grouped call (every sub-batch carries it) or nullptr; per_group: its hits per result (0: none);
-// prior: the prior and weight of a call with one (every sub-batch carries them) or none; after: the call has cursors -- run_one
-// points q at its sub-batch's (AfterArg)
+// run_one(b0, q): points q at the queries, cursors and outputs of the sub-batch that starts at query b0 and runs it.  q
+// arrives as make_batch fills it from the request (every sub-batch carries the grouping and the prior), with stats_keep set
 template <class RunOne>
-int for_sub_batches(clb_searcher* s, Workspace& w, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                    const clb_filter* const* filters, int scope, const clb_grouping* grp, int64_t per_group, PriorArg prior,
-                    bool after, RunOne run_one) {
-    size_t filt_count = 0;
-    CLB_TRY(check_filters(s, filters, B, scope, &filt_count));
-    CLB_TRY(check_grouping(s, grp));
-    CLB_TRY(check_prior(s, prior.p, prior.weight));      // (no entry point takes a prior and per_group: group_extend_kernel reads MaxSim)
+int for_sub_batches(clb_searcher* s, Workspace& w, int64_t T, int64_t B, int64_t nprobe, int64_t k, const clb_search_request& r,
+                    size_t filt_count, RunOne run_one) {
     w.pending.valid = false;
     w.grouped_done.valid = false;
     for (int64_t b0 = 0; b0 < B; b0 += kSubBatch) {
-        Batch q = make_batch(nullptr, std::min<int64_t>(kSubBatch, B - b0), T, nprobe, k);
-        CLB_TRY(ensure_workspace(s, w, q.B, T, nprobe, k, filt_count, grp != nullptr, per_group, prior.p != nullptr, after));
-        q.grp = grp;
-        q.prior = prior.p;
-        q.prior_weight = prior.weight;
-        q.per_group = (int)per_group;
+        Batch q = make_batch(nullptr, std::min<int64_t>(kSubBatch, B - b0), T, nprobe, k, r, b0, filt_count);
+        CLB_TRY(ensure_workspace(s, w, q.B, T, nprobe, k, filt_count, r.grouping != nullptr, q.per_group, r.prior != nullptr,
+                                 r.after_scores != nullptr));
         q.stats_keep = b0 > 0;
-        set_batch_filters(q, filters, b0, scope, filt_count);
         CLB_TRY(run_one(b0, q));
     }
     return CLB_OK;
@@ -1986,278 +2035,57 @@ int clb_searcher_set_bound_consts(clb_searcher* s, const float* consts) {
     return CLB_OK;
 }
 
-int clb_search_batch_device(clb_searcher* s, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                            int64_t k, int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand,
-                            void* hip_stream) {
-    return clb_search_batch_device_slot(s, 0, d_Q, T, B, nprobe, k, d_out_pids, d_out_scores, d_n_cand, hip_stream);
-}
-
-static int search_batch_device_slot_impl(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                         int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grp,
-                                         int64_t per_group /* hits per result, 0: none */, int64_t* d_out_pids,
-                                         float* d_out_scores, int64_t* d_n_cand, void* hip_stream, PriorArg prior = {},
-                                         AfterArg after = {}) {
-    CLB_TRY(check_search_args(s, T, B, nprobe, k));
+// ---- the four routes of a search request ------------------------------------------------------------------------------
+int clb_search_batch_request_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const clb_search_request* req, int64_t* d_out_pids, float* d_out_scores,
+                                         int64_t* d_n_cand, void* hip_stream) {
+    size_t filt_count = 0;
+    CLB_TRY(check_request(s, req, T, B, nprobe, k, Route::device, &filt_count, [] { return CLB_OK; }));
+    const clb_search_request& r = *req;
+    const int64_t hits = request_hits(r);
     Workspace* w = nullptr;
     CLB_TRY(slot_workspace(s, slot, &w));
     hipStream_t st = (hipStream_t)hip_stream;   // NULL = the HIP null stream, as for any HIP API
-    CLB_TRY(for_sub_batches(s, *w, T, B, nprobe, k, filters, scope, grp, per_group, prior, after.s != nullptr, [&](int64_t b0, Batch& q) -> int {
+    CLB_TRY(for_sub_batches(s, *w, T, B, nprobe, k, r, filt_count, [&](int64_t b0, Batch& q) -> int {
         q.dQ = d_Q + (size_t)b0 * T * s->dim;
-        if (after.s) { q.d_after_s = after.s + b0; q.d_after_p = after.p + b0; }
-        q.d_out_pids = per_group ? w->hit_p.as<int64_t>() : d_out_pids + (size_t)b0 * k;
-        q.d_out_scores = per_group ? w->hit_s.as<float>() : d_out_scores + (size_t)b0 * k;
-        q.d_hit_pids = d_out_pids + (size_t)b0 * k * per_group;
-        q.d_hit_scores = d_out_scores + (size_t)b0 * k * per_group;
+        if (r.after_scores) { q.d_after_s = r.after_scores + b0; q.d_after_p = r.after_pids + b0; }
+        q.d_out_pids = hits ? w->hit_p.as<int64_t>() : d_out_pids + (size_t)b0 * k;
+        q.d_out_scores = hits ? w->hit_s.as<float>() : d_out_scores + (size_t)b0 * k;
+        q.d_hit_pids = d_out_pids + (size_t)b0 * k * hits;
+        q.d_hit_scores = d_out_scores + (size_t)b0 * k * hits;
         q.d_n_cand = d_n_cand ? d_n_cand + b0 : nullptr;
         return run_search(s, *w, st, q);
     }));
-    if (grp && !per_group && B <= kSubBatch) {
+    if (r.grouping && !hits && B <= kSubBatch) {
         auto& d = w->grouped_done;
-        d.valid = true; d.B = B; d.k = k; d.generation = s->generation; d.grp = grp; d.stream = hip_stream;
+        d.valid = true; d.B = B; d.k = k; d.generation = s->generation; d.grp = r.grouping; d.stream = hip_stream;
     }
     return CLB_OK;
 }
 
-int clb_search_batch_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                 int64_t k, int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand,
-                                 void* hip_stream) {
-    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, nullptr, CLB_FILTER_CANDIDATES, nullptr, 0, d_out_pids,
-                                         d_out_scores, d_n_cand, hip_stream);
-}
-
-int clb_search_batch_filtered_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                          int64_t k, const clb_filter* const* filters, int scope, int64_t* d_out_pids,
-                                          float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
-    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, nullptr, 0, d_out_pids, d_out_scores,
-                                         d_n_cand, hip_stream);
-}
-
-int clb_search_batch_grouped_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                         int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
-                                         int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
-    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, grouping, 0, d_out_pids, d_out_scores,
-                                         d_n_cand, hip_stream);
-}
-
-// the hits of a grouped call: a grouping and 1 <= per_group <= CLB_MAX_PER_GROUP
-static int check_per_group(const clb_grouping* grouping, int64_t per_group) {
-    if (!grouping) return fail(CLB_EARGUMENT, "grouping is null: per_group needs a grouping");
-    if (per_group < 1 || per_group > CLB_MAX_PER_GROUP)
-        return fail(CLB_EARGUMENT, "per_group must be 1..%d, got %lld", CLB_MAX_PER_GROUP, (long long)per_group);
-    return CLB_OK;
-}
-
-int clb_search_batch_grouped_hits_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                              int64_t k, const clb_filter* const* filters, int scope,
-                                              const clb_grouping* grouping, int64_t per_group, int64_t* d_out_pids,
-                                              float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
-    CLB_TRY(check_per_group(grouping, per_group));
-    // one hit per result is the representative: exactly the grouped search
-    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, grouping, per_group > 1 ? per_group : 0,
-                                         d_out_pids, d_out_scores, d_n_cand, hip_stream);
-}
-
-int clb_search_shard_phase1(clb_searcher* s, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                            float* d_local_top, void* hip_stream) {
-    return clb_search_shard_phase1_slot(s, 0, d_Q, T, B, nprobe, k, d_local_top, hip_stream);
-}
-
-int clb_search_shard_phase1_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                 int64_t k, float* d_local_top, void* hip_stream) {
-    return clb_search_shard_phase1_filtered_slot(s, slot, d_Q, T, B, nprobe, k, nullptr, CLB_FILTER_CANDIDATES, d_local_top,
-                                                 hip_stream);
-}
-
-static int shard_phase1_impl(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                            const clb_filter* const* filters, int scope, const clb_grouping* grp, int64_t group_base,
-                            float* d_local_top, int64_t* d_local_gid, void* hip_stream, PriorArg prior = {},
-                            float* d_local_mabs = nullptr) {
-    CLB_TRY(check_search_args(s, T, B, nprobe, k));
-    if (!d_local_top) return fail(CLB_EARGUMENT, "d_local_top is null");
-    if (prior.p && !d_local_mabs) return fail(CLB_EARGUMENT, "d_local_mabs is null");
-    if (grp && !d_local_gid) return fail(CLB_EARGUMENT, "d_local_gid is null");
-    if (grp && group_base < 0) return fail(CLB_EARGUMENT, "group_base must be >= 0, got %lld", (long long)group_base);
+int clb_search_batch_request(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                             const clb_search_request* req, int64_t* out_pids, float* out_scores, int64_t* n_cand) {
     size_t filt_count = 0;
-    CLB_TRY(check_filters(s, filters, B, scope, &filt_count));
-    CLB_TRY(check_grouping(s, grp));
-    CLB_TRY(check_prior(s, prior.p, prior.weight));
-    bool filtered = false;
-    for (int64_t b = 0; filters && b < B; ++b) filtered |= filters[b] != nullptr;
-    // the whole batch stays on the slot for phase 2, and the filter handles of a launch travel in one argument block
-    if (filtered && B > kFilterQueries)
-        return fail(CLB_EUNSUPPORTED, "a filtered clb_search_shard_phase1 takes at most %d queries per call, got %lld: split the batch",
-                    kFilterQueries, (long long)B);
-    Workspace* wp = nullptr;
-    CLB_TRY(slot_workspace(s, slot, &wp));
-    Workspace& w = *wp;
-    CLB_TRY(ensure_workspace(s, w, B, T, nprobe, k, filt_count, grp != nullptr));
-    if (grp || prior.p) CLB_TRY(w.tau_glob.ensure(sizeof(float) * B));      // phase 2 then allocates nothing
-    w.pending.valid = false;
-    w.grouped_done.valid = false;
-    Batch q = make_batch(d_Q, B, T, nprobe, k);
-    set_batch_filters(q, filters, 0, scope, filt_count);
-    q.phase = 1; q.d_local_top = d_local_top;
-    q.grp = grp; q.group_base = group_base; q.d_local_gid = d_local_gid;
-    q.prior = prior.p; q.prior_weight = prior.weight; q.d_local_mabs = prior.p ? d_local_mabs : nullptr;
-    CLB_TRY(run_search(s, w, (hipStream_t)hip_stream, q));
-    w.pending.valid = true; w.pending.dQ = d_Q; w.pending.T = T; w.pending.B = B; w.pending.nprobe = nprobe;
-    w.pending.k = k; w.pending.stream = hip_stream; w.pending.filt_now = q.filt_now;
-    w.pending.grp = grp; w.pending.group_base = group_base;
-    w.pending.prior = prior.p; w.pending.weight = prior.p ? prior.weight : 0.f;
-    return CLB_OK;
-}
-
-int clb_search_shard_phase1_filtered_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                          int64_t k, const clb_filter* const* filters, int scope, float* d_local_top,
-                                          void* hip_stream) {
-    return shard_phase1_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, nullptr, 0, d_local_top, nullptr, hip_stream);
-}
-
-int clb_search_shard_phase1_grouped_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                         int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
-                                         int64_t group_base, float* d_local_top, int64_t* d_local_gid, void* hip_stream) {
-    return shard_phase1_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, grouping, group_base, d_local_top, d_local_gid,
-                             hip_stream);
-}
-
-int clb_search_shard_phase2(clb_searcher* s, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                            const float* d_all_top, int64_t n_shards, int64_t* d_out_pids, float* d_out_scores,
-                            int64_t* d_n_cand, void* hip_stream) {
-    return clb_search_shard_phase2_slot(s, 0, d_Q, T, B, nprobe, k, d_all_top, n_shards, d_out_pids, d_out_scores, d_n_cand,
-                                        hip_stream);
-}
-
-static int shard_phase2_impl(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                            const float* d_all_top, const int64_t* d_all_gid, int64_t n_shards, const clb_grouping* grp,
-                            int64_t group_base, int64_t* d_out_pids, float* d_out_scores, int64_t* d_out_gids, int64_t* d_n_cand,
-                            int64_t* d_edge_gids, void* hip_stream, PriorArg prior = {}, const float* d_all_mabs = nullptr) {
-    CLB_TRY(check_search_args(s, T, B, nprobe, k));
-    if (!d_all_top || n_shards < 1) return fail(CLB_EARGUMENT, "d_all_top is null or n_shards < 1");
-    if (prior.p) {
-        if (!d_all_mabs) return fail(CLB_EARGUMENT, "d_all_mabs is null");
-        if (!d_out_pids || !d_out_scores || !d_n_cand)
-            return fail(CLB_EARGUMENT, "an output of the prior phase 2 is null (d_out_pids, d_out_scores, d_n_cand)");
-        CLB_TRY(check_prior(s, prior.p, prior.weight));
-    }
-    if (grp) {
-        if (!d_all_gid) return fail(CLB_EARGUMENT, "d_all_gid is null");
-        if (!d_out_pids || !d_out_scores || !d_out_gids || !d_n_cand || !d_edge_gids)
-            return fail(CLB_EARGUMENT, "an output of the grouped phase 2 is null (d_out_pids, d_out_scores, d_out_gids, d_n_cand, d_edge_gids)");
-        CLB_TRY(check_grouping(s, grp));
-        if (n_shards > kMaxGroupShards)
-            return fail(CLB_EUNSUPPORTED, "the grouped phase 2 takes at most %d shards, got %lld", kMaxGroupShards, (long long)n_shards);
-    }
-    Workspace* wp = nullptr;
-    CLB_TRY(slot_workspace(s, slot, &wp));
-    Workspace& w = *wp;
-    const auto& pd = w.pending;
-    if (!pd.valid || pd.dQ != d_Q || pd.T != T || pd.B != B || pd.nprobe != nprobe || pd.k != k || pd.stream != hip_stream ||
-        pd.grp != grp || (grp && pd.group_base != group_base) || pd.prior != prior.p ||
-        (prior.p && std::memcmp(&pd.weight, &prior.weight, sizeof(float)) != 0))
-        return fail(CLB_EARGUMENT, "clb_search_shard_phase2 without a matching clb_search_shard_phase1 "
-                                   "on this workspace slot (same queries, T, B, nprobe, k and stream -- with a grouping or a prior: the same "
-                                   "grouping, group_base, prior and weight -- and no other search on the slot in between)");
-    // every shard must cut at tau_global - 2 eps with ONE eps (the largest): a shard still on its own bound constants
-    // could drop a member of the global top-k silently, so phase 2 with other shards' scores is refused until the host
-    // has shared them (clb_searcher_get_bound_consts on every shard -> element-wise maximum -> clb_searcher_set_bound_consts)
-    if (n_shards > 1 && !s->bounds_synced)
-        return fail(CLB_EARGUMENT, "clb_search_shard_phase2 with %lld shards before clb_searcher_set_bound_consts: the shards "
-                                   "must share one error bound (all-reduce MAX of clb_searcher_get_bound_consts)", (long long)n_shards);
-    w.pending.valid = false;
-    // phase 1's filters are in the candidate list it left on the slot (cand / cand_hdr / ncand): everything from here on
-    // reads only that list, and the two-pass proof holds for whatever candidate set it is given -- no filter operand
-    Batch q = make_batch(d_Q, B, T, nprobe, k);
-    q.filt_now = pd.filt_now;       // ... but the selection kernels are chosen by the same candidate capacity
-    q.d_out_pids = d_out_pids; q.d_out_scores = d_out_scores; q.d_n_cand = d_n_cand;
-    q.phase = 2; q.d_all_top = d_all_top; q.n_shards = (int)n_shards;
-    q.grp = grp; q.group_base = group_base; q.d_all_gid = d_all_gid; q.d_out_gids = d_out_gids; q.d_edge_gids = d_edge_gids;
-    q.prior = prior.p; q.prior_weight = prior.weight; q.d_all_mabs = d_all_mabs;
-    return run_search(s, w, (hipStream_t)hip_stream, q);
-}
-
-int clb_search_shard_phase2_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                 int64_t k, const float* d_all_top, int64_t n_shards, int64_t* d_out_pids,
-                                 float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
-    return shard_phase2_impl(s, slot, d_Q, T, B, nprobe, k, d_all_top, nullptr, n_shards, nullptr, 0, d_out_pids, d_out_scores,
-                             nullptr, d_n_cand, nullptr, hip_stream);
-}
-
-int clb_search_shard_phase2_grouped_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                         int64_t k, const float* d_all_top, const int64_t* d_all_gid, int64_t n_shards,
-                                         const clb_grouping* grouping, int64_t group_base, int64_t* d_out_pids,
-                                         float* d_out_scores, int64_t* d_out_gids, int64_t* d_n_cand, int64_t* d_edge_gids,
-                                         void* hip_stream) {
-    if (!grouping) return fail(CLB_EARGUMENT, "grouping is null (without one: clb_search_shard_phase2_slot)");
-    return shard_phase2_impl(s, slot, d_Q, T, B, nprobe, k, d_all_top, d_all_gid, n_shards, grouping, group_base, d_out_pids,
-                             d_out_scores, d_out_gids, d_n_cand, d_edge_gids, hip_stream);
-}
-
-static int check_prior_weight(const clb_prior* prior, float weight);
-
-int clb_search_shard_phase1_prior_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                       int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
-                                       int64_t group_base, const clb_prior* prior, float weight, float* d_local_top,
-                                       int64_t* d_local_gid, float* d_local_mabs, void* hip_stream) {
-    CLB_TRY(check_prior_weight(prior, weight));
-    return shard_phase1_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, grouping, group_base, d_local_top, d_local_gid,
-                             hip_stream, PriorArg{prior, weight}, d_local_mabs);
-}
-
-int clb_search_shard_phase2_prior_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
-                                       int64_t k, const float* d_all_top, const int64_t* d_all_gid, const float* d_all_mabs,
-                                       int64_t n_shards, const clb_grouping* grouping, int64_t group_base, const clb_prior* prior,
-                                       float weight, int64_t* d_out_pids, float* d_out_scores, int64_t* d_out_gids,
-                                       int64_t* d_n_cand, int64_t* d_edge_gids, void* hip_stream) {
-    if (!prior)
-        return fail(CLB_EARGUMENT, "prior is null (without one: clb_search_shard_phase2_slot / clb_search_shard_phase2_grouped_slot)");
-    CLB_TRY(check_prior_weight(prior, weight));
-    return shard_phase2_impl(s, slot, d_Q, T, B, nprobe, k, d_all_top, grouping ? d_all_gid : nullptr, n_shards, grouping,
-                             group_base, d_out_pids, d_out_scores, grouping ? d_out_gids : nullptr, d_n_cand,
-                             grouping ? d_edge_gids : nullptr, hip_stream, PriorArg{prior, weight}, d_all_mabs);
-}
-
-int clb_search_result_groups_slot(clb_searcher* s, int slot, const clb_grouping* grouping, int64_t group_base,
-                                  const int64_t* d_pids, int64_t B, int64_t k, int64_t* d_out_gids, int64_t* d_edge_gids,
-                                  void* hip_stream) {
-    if (!s) return fail(CLB_EARGUMENT, "null searcher");
-    if (!grouping) return fail(CLB_EARGUMENT, "grouping is null");
-    if (!d_pids || !d_out_gids || !d_edge_gids) return fail(CLB_EARGUMENT, "d_pids, d_out_gids or d_edge_gids is null");
-    if (B < 1 || k < 1 || group_base < 0) return fail(CLB_EARGUMENT, "B and k must be >= 1 and group_base >= 0");
-    CLB_TRY(check_grouping(s, grouping));
-    Workspace* wp = nullptr;
-    CLB_TRY(slot_workspace(s, slot, &wp));
-    const auto& d = wp->grouped_done;
-    if (!d.valid || d.B != B || d.k != k || d.grp != grouping || d.stream != hip_stream || d.generation != s->generation)
-        return fail(CLB_EARGUMENT, "clb_search_result_groups_slot without a matching clb_search_batch_grouped_device_slot on this "
-                                   "workspace slot (same grouping, B <= %lld, k and stream, and nothing else on the slot in between)",
-                    (long long)kSubBatch);
-    launch_result_groups(s, *wp, (hipStream_t)hip_stream, grouping, group_base, d_pids, (int)B, (int)k, d_out_gids, d_edge_gids);
-    CLB_HIP(hipGetLastError());
-    return CLB_OK;
-}
-
-static int search_batch_impl(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                             const clb_filter* const* filters, int scope, const clb_grouping* grp,
-                             int64_t per_group /* hits per result, 0: none */, int pad_short, int64_t* out_pids,
-                             float* out_scores, int64_t* n_cand, PriorArg prior = {}, AfterArg after = {}) {
-    CLB_TRY(check_search_args(s, T, B, nprobe, k));
-    const int64_t km = k * std::max<int64_t>(per_group, 1);     // entries of one query's result
+    CLB_TRY(check_request(s, req, T, B, nprobe, k, Route::host, &filt_count, [] { return CLB_OK; }));
+    const clb_search_request& r = *req;
+    const int64_t hits = request_hits(r);
+    const int64_t km = k * std::max<int64_t>(hits, 1);     // entries of one query's result
     Workspace* wp = nullptr;
     CLB_TRY(slot_workspace(s, 0, &wp));
     Workspace& w = *wp;
     hipStream_t st = s->stream;
     std::vector<int> nc((size_t)B), fl((size_t)B);
     // the queries go up into the slot's own buffer and the results come back from it, sub-batch by sub-batch
-    CLB_TRY(for_sub_batches(s, w, T, B, nprobe, k, filters, scope, grp, per_group, prior, after.s != nullptr, [&](int64_t b0, Batch& q) -> int {
+    CLB_TRY(for_sub_batches(s, w, T, B, nprobe, k, r, filt_count, [&](int64_t b0, Batch& q) -> int {
         CLB_HIP(hipMemcpyAsync(w.Qdev.p, Q + (size_t)b0 * T * s->dim, sizeof(float) * q.B * T * s->dim, hipMemcpyHostToDevice, st));
-        if (after.s) {      // the sub-batch's cursors go up beside its queries
-            CLB_HIP(hipMemcpyAsync(w.after_cur_s.p, after.s + b0, sizeof(float) * q.B, hipMemcpyHostToDevice, st));
-            CLB_HIP(hipMemcpyAsync(w.after_cur_p.p, after.p + b0, sizeof(int64_t) * q.B, hipMemcpyHostToDevice, st));
+        if (r.after_scores) {      // the sub-batch's cursors go up beside its queries
+            CLB_HIP(hipMemcpyAsync(w.after_cur_s.p, r.after_scores + b0, sizeof(float) * q.B, hipMemcpyHostToDevice, st));
+            CLB_HIP(hipMemcpyAsync(w.after_cur_p.p, r.after_pids + b0, sizeof(int64_t) * q.B, hipMemcpyHostToDevice, st));
             q.d_after_s = w.after_cur_s.as<float>(); q.d_after_p = w.after_cur_p.as<int64_t>();
         }
         q.dQ = w.Qdev.as<float>();
-        q.d_out_pids = per_group ? w.hit_p.as<int64_t>() : w.outp.as<int64_t>();
-        q.d_out_scores = per_group ? w.hit_s.as<float>() : w.outs.as<float>();
+        q.d_out_pids = hits ? w.hit_p.as<int64_t>() : w.outp.as<int64_t>();
+        q.d_out_scores = hits ? w.hit_s.as<float>() : w.outs.as<float>();
         q.d_hit_pids = w.outp.as<int64_t>();
         q.d_hit_scores = w.outs.as<float>();
         CLB_TRY(run_search(s, w, st, q));
@@ -2274,93 +2102,301 @@ static int search_batch_impl(clb_searcher* s, const float* Q, int64_t T, int64_t
         docs += nc[b];
     }
     s->last_cand_docs = docs;
-    if (!pad_short)
+    if (!r.pad_short)
         for (int64_t b = 0; b < B; ++b)
             if (fl[b])  // searching.jl:127 `pids[1:k]` on a shorter vector
                 return fail(CLB_EBOUNDS, "query %lld has %d candidate %s, fewer than k=%lld", (long long)b, nc[b],
-                            grp ? "groups" : "passages", (long long)k);
+                            r.grouping ? "groups" : "passages", (long long)k);
     return CLB_OK;
 }
 
-int clb_search_batch(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                     int pad_short, int64_t* out_pids, float* out_scores, int64_t* n_cand) {
-    return search_batch_impl(s, Q, T, B, nprobe, k, nullptr, CLB_FILTER_CANDIDATES, nullptr, 0, pad_short, out_pids, out_scores, n_cand);
-}
-
-int clb_search_batch_filtered(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                              const clb_filter* const* filters, int scope, int64_t* out_pids, float* out_scores,
-                              int64_t* n_cand) {
-    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, nullptr, 0, 1, out_pids, out_scores, n_cand);
-}
-
-int clb_search_batch_grouped(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                             const clb_filter* const* filters, int scope, const clb_grouping* grouping, int pad_short,
-                             int64_t* out_pids, float* out_scores, int64_t* n_cand) {
-    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, grouping, 0, pad_short, out_pids, out_scores, n_cand);
-}
-
-int clb_search_batch_grouped_hits(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                                  const clb_filter* const* filters, int scope, const clb_grouping* grouping, int64_t per_group,
-                                  int pad_short, int64_t* out_pids, float* out_scores, int64_t* n_cand) {
-    CLB_TRY(check_per_group(grouping, per_group));
-    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, grouping, per_group > 1 ? per_group : 0, pad_short, out_pids,
-                             out_scores, n_cand);
-}
-
-// ---- clb_prior ----------------------------------------------------------------------------------------------------
-// a weight that is not a finite number is refused before anything is looked at (the searcher comes next, as in every entry)
-static int check_prior_weight(const clb_prior* prior, float weight) {
-    if (prior && !std::isfinite(weight)) return fail(CLB_EARGUMENT, "prior_weight must be finite, got %g", (double)weight);
+int clb_search_shard_phase1_request_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const clb_search_request* req, float* d_local_top, int64_t* d_local_gid,
+                                         float* d_local_mabs, void* hip_stream) {
+    size_t filt_count = 0;
+    CLB_TRY(check_request(s, req, T, B, nprobe, k, Route::phase1, &filt_count, [&] {
+        if (!d_local_top) return fail(CLB_EARGUMENT, "d_local_top is null");
+        if (req->prior && !d_local_mabs) return fail(CLB_EARGUMENT, "d_local_mabs is null");
+        if (req->grouping && !d_local_gid) return fail(CLB_EARGUMENT, "d_local_gid is null");
+        return (int)CLB_OK;
+    }));
+    const clb_search_request& r = *req;
+    Workspace* wp = nullptr;
+    CLB_TRY(slot_workspace(s, slot, &wp));
+    Workspace& w = *wp;
+    CLB_TRY(ensure_workspace(s, w, B, T, nprobe, k, filt_count, r.grouping != nullptr));
+    if (r.grouping || r.prior) CLB_TRY(w.tau_glob.ensure(sizeof(float) * B));      // phase 2 then allocates nothing
+    w.pending.valid = false;
+    w.grouped_done.valid = false;
+    Batch q = make_batch(d_Q, B, T, nprobe, k, r, 0, filt_count);
+    q.phase = 1; q.d_local_top = d_local_top; q.d_local_gid = d_local_gid;
+    q.d_local_mabs = r.prior ? d_local_mabs : nullptr;
+    CLB_TRY(run_search(s, w, (hipStream_t)hip_stream, q));
+    w.pending.valid = true; w.pending.dQ = d_Q; w.pending.T = T; w.pending.B = B; w.pending.nprobe = nprobe;
+    w.pending.k = k; w.pending.stream = hip_stream; w.pending.filt_now = q.filt_now;
+    w.pending.grp = r.grouping; w.pending.group_base = r.group_base;
+    w.pending.prior = r.prior; w.pending.weight = r.prior ? r.prior_weight : 0.f;
     return CLB_OK;
 }
 
-int clb_search_batch_prior(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                           const clb_filter* const* filters, int scope, const clb_grouping* grouping, const clb_prior* prior,
-                           float weight, int pad_short, int64_t* out_pids, float* out_scores, int64_t* n_cand) {
-    CLB_TRY(check_prior_weight(prior, weight));
-    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, grouping, 0, pad_short, out_pids, out_scores, n_cand,
-                             PriorArg{prior, weight});
+int clb_search_shard_phase2_request_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const clb_search_request* req, const float* d_all_top,
+                                         const int64_t* d_all_gid, const float* d_all_mabs, int64_t n_shards, int64_t* d_out_pids,
+                                         float* d_out_scores, int64_t* d_out_gids, int64_t* d_n_cand, int64_t* d_edge_gids,
+                                         void* hip_stream) {
+    size_t filt_count = 0;
+    CLB_TRY(check_request(s, req, T, B, nprobe, k, Route::phase2, &filt_count, [&] {
+        if (!d_all_top || n_shards < 1) return fail(CLB_EARGUMENT, "d_all_top is null or n_shards < 1");
+        if (req->prior) {
+            if (!d_all_mabs) return fail(CLB_EARGUMENT, "d_all_mabs is null");
+            if (!d_out_pids || !d_out_scores || !d_n_cand)
+                return fail(CLB_EARGUMENT, "an output of the prior phase 2 is null (d_out_pids, d_out_scores, d_n_cand)");
+        }
+        if (req->grouping) {
+            if (!d_all_gid) return fail(CLB_EARGUMENT, "d_all_gid is null");
+            if (!d_out_pids || !d_out_scores || !d_out_gids || !d_n_cand || !d_edge_gids)
+                return fail(CLB_EARGUMENT, "an output of the grouped phase 2 is null (d_out_pids, d_out_scores, d_out_gids, d_n_cand, d_edge_gids)");
+        }
+        return (int)CLB_OK;
+    }));
+    const clb_search_request& r = *req;
+    if (r.grouping && n_shards > kMaxGroupShards)
+        return fail(CLB_EUNSUPPORTED, "the grouped phase 2 takes at most %d shards, got %lld", kMaxGroupShards, (long long)n_shards);
+    Workspace* wp = nullptr;
+    CLB_TRY(slot_workspace(s, slot, &wp));
+    Workspace& w = *wp;
+    const auto& pd = w.pending;
+    if (!pd.valid || pd.dQ != d_Q || pd.T != T || pd.B != B || pd.nprobe != nprobe || pd.k != k || pd.stream != hip_stream ||
+        pd.grp != r.grouping || (r.grouping && pd.group_base != r.group_base) || pd.prior != r.prior ||
+        (r.prior && std::memcmp(&pd.weight, &r.prior_weight, sizeof(float)) != 0))
+        return fail(CLB_EARGUMENT, "clb_search_shard_phase2 without a matching clb_search_shard_phase1 "
+                                   "on this workspace slot (same queries, T, B, nprobe, k and stream -- with a grouping or a prior: the same "
+                                   "grouping, group_base, prior and weight -- and no other search on the slot in between)");
+    // every shard must cut at tau_global - 2 eps with ONE eps (the largest): a shard still on its own bound constants
+    // could drop a member of the global top-k silently, so phase 2 with other shards' scores is refused until the host
+    // has shared them (clb_searcher_get_bound_consts on every shard -> element-wise maximum -> clb_searcher_set_bound_consts)
+    if (n_shards > 1 && !s->bounds_synced)
+        return fail(CLB_EARGUMENT, "clb_search_shard_phase2 with %lld shards before clb_searcher_set_bound_consts: the shards "
+                                   "must share one error bound (all-reduce MAX of clb_searcher_get_bound_consts)", (long long)n_shards);
+    w.pending.valid = false;
+    // phase 1's filters are in the candidate list it left on the slot (cand / cand_hdr / ncand): everything from here on
+    // reads only that list, and the two-pass proof holds for whatever candidate set it is given -- no filter operand
+    Batch q = make_batch(d_Q, B, T, nprobe, k, r, 0, filt_count);
+    q.filt_now = pd.filt_now;       // ... but the selection kernels are chosen by the same candidate capacity
+    q.d_out_pids = d_out_pids; q.d_out_scores = d_out_scores; q.d_n_cand = d_n_cand;
+    q.phase = 2; q.d_all_top = d_all_top; q.n_shards = (int)n_shards;
+    // the group and magnitude records are read, and the group outputs written, only with what they belong to
+    q.d_all_gid = r.grouping ? d_all_gid : nullptr; q.d_out_gids = r.grouping ? d_out_gids : nullptr;
+    q.d_edge_gids = r.grouping ? d_edge_gids : nullptr; q.d_all_mabs = r.prior ? d_all_mabs : nullptr;
+    return run_search(s, w, (hipStream_t)hip_stream, q);
+}
+
+// ---- the named entry points: each its own refusal (if it has one), a request, one call -----------------------------------
+// (request fields in order: struct_bytes, filters, scope, pad_short, grouping, per_group, group_base, prior, prior_weight,
+// after_scores, after_pids; what a named entry leaves out is zero)
+constexpr int64_t kReq = sizeof(clb_search_request);
+
+int clb_search_batch_device(clb_searcher* s, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                            int64_t k, int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand,
+                            void* hip_stream) {
+    return clb_search_batch_device_slot(s, 0, d_Q, T, B, nprobe, k, d_out_pids, d_out_scores, d_n_cand, hip_stream);
+}
+
+int clb_search_batch_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                 int64_t k, int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand,
+                                 void* hip_stream) {
+    const clb_search_request r = {kReq};
+    return clb_search_batch_request_device_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_out_pids, d_out_scores, d_n_cand, hip_stream);
+}
+
+int clb_search_batch_filtered_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                          int64_t k, const clb_filter* const* filters, int scope, int64_t* d_out_pids,
+                                          float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
+    const clb_search_request r = {kReq, filters, scope};
+    return clb_search_batch_request_device_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_out_pids, d_out_scores, d_n_cand, hip_stream);
+}
+
+int clb_search_batch_grouped_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
+                                         int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
+    const clb_search_request r = {kReq, filters, scope, 0, grouping};
+    return clb_search_batch_request_device_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_out_pids, d_out_scores, d_n_cand, hip_stream);
+}
+
+// the hits entries' own refusal: they need a grouping, and the request's per_group == 0 ("none") is no number of hits
+static int check_hits_entry(const clb_grouping* grouping, int64_t per_group) {
+    if (!grouping) return hits_without_grouping();
+    return per_group == 0 ? bad_per_group(per_group) : CLB_OK;
+}
+
+int clb_search_batch_grouped_hits_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                              int64_t k, const clb_filter* const* filters, int scope,
+                                              const clb_grouping* grouping, int64_t per_group, int64_t* d_out_pids,
+                                              float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
+    CLB_TRY(check_hits_entry(grouping, per_group));
+    const clb_search_request r = {kReq, filters, scope, 0, grouping, per_group};
+    return clb_search_batch_request_device_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_out_pids, d_out_scores, d_n_cand, hip_stream);
 }
 
 int clb_search_batch_prior_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
                                        int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
                                        const clb_prior* prior, float weight, int64_t* d_out_pids, float* d_out_scores,
                                        int64_t* d_n_cand, void* hip_stream) {
-    CLB_TRY(check_prior_weight(prior, weight));
-    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, grouping, 0, d_out_pids, d_out_scores,
-                                         d_n_cand, hip_stream, PriorArg{prior, weight});
+    const clb_search_request r = {kReq, filters, scope, 0, grouping, 0, 0, prior, weight};
+    return clb_search_batch_request_device_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_out_pids, d_out_scores, d_n_cand, hip_stream);
 }
 
-// ---- search after a cursor ----------------------------------------------------------------------------------------
-// what both entry points check before anything else: the handle, the outputs, and that the cursor arrays come as a pair
-static int check_after_args(const clb_searcher* s, const void* after_scores, const void* after_pids, const void* out_pids,
-                            const void* out_scores) {
+// the cursor entries' own refusal, ahead of everything else: the handle and the outputs
+static int check_after_entry(const clb_searcher* s, const void* out_pids, const void* out_scores) {
     if (!s) return fail(CLB_EARGUMENT, "null searcher");
     if (!out_pids || !out_scores) return fail(CLB_EARGUMENT, "out_pids / out_scores is null");
-    if ((after_scores == nullptr) != (after_pids == nullptr))
-        return fail(CLB_EARGUMENT, "after_scores and after_pids must both be given or both be null");
     return CLB_OK;
-}
-
-int clb_search_batch_after(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
-                           const clb_filter* const* filters, int scope, const float* after_scores, const int64_t* after_pids,
-                           int64_t* out_pids, float* out_scores, int64_t* n_cand) {
-    CLB_TRY(check_after_args(s, after_scores, after_pids, out_pids, out_scores));
-    for (int64_t b = 0; after_scores && b < B; ++b)
-        if (std::isnan(after_scores[b])) return fail(CLB_EARGUMENT, "the cursor score of query %lld is NaN", (long long)b);
-    return search_batch_impl(s, Q, T, B, nprobe, k, filters, scope, nullptr, 0, /*pad_short=*/1, out_pids, out_scores, n_cand,
-                             PriorArg{}, AfterArg{after_scores, after_pids});
 }
 
 int clb_search_batch_after_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
                                        int64_t k, const clb_filter* const* filters, int scope, const float* d_after_scores,
                                        const int64_t* d_after_pids, int64_t* d_out_pids, float* d_out_scores,
                                        int64_t* d_n_cand, void* hip_stream) {
-    CLB_TRY(check_after_args(s, d_after_scores, d_after_pids, d_out_pids, d_out_scores));
-    return search_batch_device_slot_impl(s, slot, d_Q, T, B, nprobe, k, filters, scope, nullptr, 0, d_out_pids, d_out_scores,
-                                         d_n_cand, hip_stream, PriorArg{}, AfterArg{d_after_scores, d_after_pids});
+    CLB_TRY(check_after_entry(s, d_out_pids, d_out_scores));
+    const clb_search_request r = {kReq, filters, scope, 0, nullptr, 0, 0, nullptr, 0.f, d_after_scores, d_after_pids};
+    return clb_search_batch_request_device_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_out_pids, d_out_scores, d_n_cand, hip_stream);
 }
 
+int clb_search_batch(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                     int pad_short, int64_t* out_pids, float* out_scores, int64_t* n_cand) {
+    const clb_search_request r = {kReq, nullptr, CLB_FILTER_CANDIDATES, pad_short};
+    return clb_search_batch_request(s, Q, T, B, nprobe, k, &r, out_pids, out_scores, n_cand);
+}
+
+int clb_search_batch_filtered(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                              const clb_filter* const* filters, int scope, int64_t* out_pids, float* out_scores,
+                              int64_t* n_cand) {
+    const clb_search_request r = {kReq, filters, scope, /*pad_short=*/1};
+    return clb_search_batch_request(s, Q, T, B, nprobe, k, &r, out_pids, out_scores, n_cand);
+}
+
+int clb_search_batch_grouped(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                             const clb_filter* const* filters, int scope, const clb_grouping* grouping, int pad_short,
+                             int64_t* out_pids, float* out_scores, int64_t* n_cand) {
+    const clb_search_request r = {kReq, filters, scope, pad_short, grouping};
+    return clb_search_batch_request(s, Q, T, B, nprobe, k, &r, out_pids, out_scores, n_cand);
+}
+
+int clb_search_batch_grouped_hits(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                                  const clb_filter* const* filters, int scope, const clb_grouping* grouping, int64_t per_group,
+                                  int pad_short, int64_t* out_pids, float* out_scores, int64_t* n_cand) {
+    CLB_TRY(check_hits_entry(grouping, per_group));
+    const clb_search_request r = {kReq, filters, scope, pad_short, grouping, per_group};
+    return clb_search_batch_request(s, Q, T, B, nprobe, k, &r, out_pids, out_scores, n_cand);
+}
+
+int clb_search_batch_prior(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                           const clb_filter* const* filters, int scope, const clb_grouping* grouping, const clb_prior* prior,
+                           float weight, int pad_short, int64_t* out_pids, float* out_scores, int64_t* n_cand) {
+    const clb_search_request r = {kReq, filters, scope, pad_short, grouping, 0, 0, prior, weight};
+    return clb_search_batch_request(s, Q, T, B, nprobe, k, &r, out_pids, out_scores, n_cand);
+}
+
+int clb_search_batch_after(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                           const clb_filter* const* filters, int scope, const float* after_scores, const int64_t* after_pids,
+                           int64_t* out_pids, float* out_scores, int64_t* n_cand) {
+    CLB_TRY(check_after_entry(s, out_pids, out_scores));
+    const clb_search_request r = {kReq, filters, scope, /*pad_short=*/1, nullptr, 0, 0, nullptr, 0.f, after_scores, after_pids};
+    return clb_search_batch_request(s, Q, T, B, nprobe, k, &r, out_pids, out_scores, n_cand);
+}
+
+int clb_search_shard_phase1(clb_searcher* s, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                            float* d_local_top, void* hip_stream) {
+    return clb_search_shard_phase1_slot(s, 0, d_Q, T, B, nprobe, k, d_local_top, hip_stream);
+}
+
+int clb_search_shard_phase1_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                 int64_t k, float* d_local_top, void* hip_stream) {
+    return clb_search_shard_phase1_filtered_slot(s, slot, d_Q, T, B, nprobe, k, nullptr, CLB_FILTER_CANDIDATES, d_local_top,
+                                                 hip_stream);
+}
+
+int clb_search_shard_phase1_filtered_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                          int64_t k, const clb_filter* const* filters, int scope, float* d_local_top,
+                                          void* hip_stream) {
+    const clb_search_request r = {kReq, filters, scope};
+    return clb_search_shard_phase1_request_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_local_top, nullptr, nullptr, hip_stream);
+}
+
+int clb_search_shard_phase1_grouped_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
+                                         int64_t group_base, float* d_local_top, int64_t* d_local_gid, void* hip_stream) {
+    const clb_search_request r = {kReq, filters, scope, 0, grouping, 0, group_base};
+    return clb_search_shard_phase1_request_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_local_top, d_local_gid, nullptr, hip_stream);
+}
+
+int clb_search_shard_phase1_prior_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                       int64_t k, const clb_filter* const* filters, int scope, const clb_grouping* grouping,
+                                       int64_t group_base, const clb_prior* prior, float weight, float* d_local_top,
+                                       int64_t* d_local_gid, float* d_local_mabs, void* hip_stream) {
+    const clb_search_request r = {kReq, filters, scope, 0, grouping, 0, group_base, prior, weight};
+    return clb_search_shard_phase1_request_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_local_top, d_local_gid, d_local_mabs, hip_stream);
+}
+
+int clb_search_shard_phase2(clb_searcher* s, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                            const float* d_all_top, int64_t n_shards, int64_t* d_out_pids, float* d_out_scores,
+                            int64_t* d_n_cand, void* hip_stream) {
+    return clb_search_shard_phase2_slot(s, 0, d_Q, T, B, nprobe, k, d_all_top, n_shards, d_out_pids, d_out_scores, d_n_cand,
+                                        hip_stream);
+}
+
+int clb_search_shard_phase2_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                 int64_t k, const float* d_all_top, int64_t n_shards, int64_t* d_out_pids,
+                                 float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
+    const clb_search_request r = {kReq};
+    return clb_search_shard_phase2_request_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_all_top, nullptr, nullptr, n_shards, d_out_pids,
+                                                d_out_scores, nullptr, d_n_cand, nullptr, hip_stream);
+}
+
+int clb_search_shard_phase2_grouped_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const float* d_all_top, const int64_t* d_all_gid, int64_t n_shards,
+                                         const clb_grouping* grouping, int64_t group_base, int64_t* d_out_pids,
+                                         float* d_out_scores, int64_t* d_out_gids, int64_t* d_n_cand, int64_t* d_edge_gids,
+                                         void* hip_stream) {
+    if (!grouping) return fail(CLB_EARGUMENT, "grouping is null (without one: clb_search_shard_phase2_slot)");
+    const clb_search_request r = {kReq, nullptr, CLB_FILTER_CANDIDATES, 0, grouping, 0, group_base};
+    return clb_search_shard_phase2_request_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_all_top, d_all_gid, nullptr, n_shards,
+                                                d_out_pids, d_out_scores, d_out_gids, d_n_cand, d_edge_gids, hip_stream);
+}
+
+int clb_search_shard_phase2_prior_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                       int64_t k, const float* d_all_top, const int64_t* d_all_gid, const float* d_all_mabs,
+                                       int64_t n_shards, const clb_grouping* grouping, int64_t group_base, const clb_prior* prior,
+                                       float weight, int64_t* d_out_pids, float* d_out_scores, int64_t* d_out_gids,
+                                       int64_t* d_n_cand, int64_t* d_edge_gids, void* hip_stream) {
+    if (!prior)
+        return fail(CLB_EARGUMENT, "prior is null (without one: clb_search_shard_phase2_slot / clb_search_shard_phase2_grouped_slot)");
+    const clb_search_request r = {kReq, nullptr, CLB_FILTER_CANDIDATES, 0, grouping, 0, group_base, prior, weight};
+    return clb_search_shard_phase2_request_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_all_top, d_all_gid, d_all_mabs, n_shards,
+                                                d_out_pids, d_out_scores, d_out_gids, d_n_cand, d_edge_gids, hip_stream);
+}
+
+int clb_search_result_groups_slot(clb_searcher* s, int slot, const clb_grouping* grouping, int64_t group_base,
+                                  const int64_t* d_pids, int64_t B, int64_t k, int64_t* d_out_gids, int64_t* d_edge_gids,
+                                  void* hip_stream) {
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    if (!grouping) return fail(CLB_EARGUMENT, "grouping is null");
+    if (!d_pids || !d_out_gids || !d_edge_gids) return fail(CLB_EARGUMENT, "d_pids, d_out_gids or d_edge_gids is null");
+    if (B < 1 || k < 1 || group_base < 0) return fail(CLB_EARGUMENT, "B and k must be >= 1 and group_base >= 0");
+    CLB_TRY(check_grouping(s, grouping));       // (not a search: it carries no request)
+    Workspace* wp = nullptr;
+    CLB_TRY(slot_workspace(s, slot, &wp));
+    const auto& d = wp->grouped_done;
+    if (!d.valid || d.B != B || d.k != k || d.grp != grouping || d.stream != hip_stream || d.generation != s->generation)
+        return fail(CLB_EARGUMENT, "clb_search_result_groups_slot without a matching clb_search_batch_grouped_device_slot on this "
+                                   "workspace slot (same grouping, B <= %lld, k and stream, and nothing else on the slot in between)",
+                    (long long)kSubBatch);
+    launch_result_groups(s, *wp, (hipStream_t)hip_stream, grouping, group_base, d_pids, (int)B, (int)k, d_out_gids, d_edge_gids);
+    CLB_HIP(hipGetLastError());
+    return CLB_OK;
+}
+
+// ---- clb_prior ----------------------------------------------------------------------------------------------------
 using PriorPtr = std::unique_ptr<clb_prior, decltype(&clb_prior_destroy)>;
 // the arguments both creators share, checked before the device is touched
 static int prior_args(clb_searcher* s, const float* values, int64_t n, clb_prior** out) {
@@ -2743,12 +2779,10 @@ int clb_debug_scores(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe,
         CLB_TRY(rc);
     }
     launch_pass1(s, w, st, dQ, dim3(8 * 32), Bd, (int)T);
-    ApproxConsts ac = s->approx_consts;          // the bound a search of this table reports (launch_select)
-    ac.dc_max = bound_dc(s, w);
+    const BoundOperands bo = bound_operands(s, w);      // the bound a search of this table reports (launch_select)
     hipLaunchKernelGGL(select_margin_kernel, dim3(1), dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), dQ,
-                       (int)T, (int)k, w.cand_cap, ac, w.list.as<int>(), w.nlist.as<int>(),
-                       w.thresh.as<float>(), w.eps_pair.as<float>(), (const float*)nullptr, 0,
-                       w.have_range ? (const float4*)w.tscale.as<float4>() : (const float4*)nullptr, w.cell8 ? 1 : 0);
+                       (int)T, (int)k, w.cand_cap, bo.ac, w.list.as<int>(), w.nlist.as<int>(),
+                       w.thresh.as<float>(), w.eps_pair.as<float>(), (const float*)nullptr, 0, bo.tscale, bo.cell8);
     int nc = 0, nl = 0;
     float th[2];
     CLB_HIP(hipMemcpyAsync(&nc, w.ncand.p, sizeof(int), hipMemcpyDeviceToHost, st));

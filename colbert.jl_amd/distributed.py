@@ -12,7 +12,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, i64, lib
+from ._lib import check, i64, lib, request_entry
+from .searcher import search_request
 from .sharding import merge_topk_host
 
 
@@ -236,6 +237,13 @@ class DeviceSearch:
         # the searcher's generation (Searcher.generation) at construction, then at the latest `capture`: an append un-sizes
         # the workspace slot and frees the index arrays a captured graph points into
         self.generation = searcher.generation
+        # what every call needs, resolved once: the request entries of the device routes, the request of a call without
+        # keywords, and torch's stream query
+        self._search = request_entry("clb_search_batch_request_device_slot")
+        self._phase1 = request_entry("clb_search_shard_phase1_request_slot")
+        self._phase2 = request_entry("clb_search_shard_phase2_request_slot")
+        self._plain = search_request(searcher, B)
+        self._current_stream = torch.cuda.current_stream
 
     def graph_is_stale(self) -> bool:
         """True once the searcher has grown since the latest `capture`: that graph must not be replayed any more --
@@ -277,6 +285,20 @@ class DeviceSearch:
         if not ok:
             raise ArgumentError(f"after must be a pair of contiguous tensors on {self.dev}: scores float32[{self.B}] and pids "
                                 f"int64[{self.B}]")
+        return tuple(after)
+
+    def _request(self, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0, after=None,
+                 group_base: int = 0):
+        """The clb_search_request of a call of this shard (searcher.search_request), its cursors as device tensors.  A call
+        without keywords takes the request made at construction: it has nothing to check and nothing to point at."""
+        if filters is None and grouping is None and per_group is None and prior is None and after is None and scope == "candidates":
+            return self._plain
+        return search_request(self.s, self.B, filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
+                              prior_weight=prior_weight, after=after, group_base=group_base,
+                              cursor_arrays=lambda cursors, _B: self._check_cursors(cursors))
+
+    def _stream(self) -> int:
+        return self._current_stream(self.dev).cuda_stream
 
     def _grouped_block(self):
         """The packed grouped result block of this shard (packed_grouped_bytes) and the views the grouped calls write into."""
@@ -294,94 +316,60 @@ class DeviceSearch:
 
     def search_grouped_shard(self, Qdev, filters, scope, grouping, group_base: int, prior=None, prior_weight=1.0):
         """The single exchange of a grouped sharded search on this shard: the whole grouped search
-        (clb_search_batch_grouped_device_slot; with `prior` / `prior_weight`, this shard's PassagePrior and the group's
-        weight: clb_search_batch_prior_device_slot), then the global group index of every result and the edge groups of every
+        (clb_search_batch_request_device_slot with the grouping; with `prior` / `prior_weight`, this shard's PassagePrior and
+        the group's weight, in the same request), then the global group index of every result and the edge groups of every
         query (clb_search_result_groups_slot), all into the packed grouped block, which is returned.  B <= 64."""
-        import torch
-        from .searcher import _prior_weight, _scope_code
         self._check_queries(Qdev)
         block = self._grouped_block()
-        st = torch.cuda.current_stream(self.dev).cuda_stream
         gh = self.s._grouping_handle(grouping)
-        fh = None if filters is None else self.s._filter_handles(filters, self.B)
-        if prior is not None:
-            w = _prior_weight(prior, prior_weight, None)
-            check(lib().clb_search_batch_prior_device_slot(
-                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
-                fh, C.c_int(_scope_code(scope)), gh, prior._h, C.c_float(w), C.c_void_p(self.g_out_p.data_ptr()),
-                C.c_void_p(self.g_out_s.data_ptr()), C.c_void_p(self.g_ncand.data_ptr()), C.c_void_p(st)))
-        else:
-            check(lib().clb_search_batch_grouped_device_slot(
-                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
-                fh, C.c_int(_scope_code(scope)), gh, C.c_void_p(self.g_out_p.data_ptr()), C.c_void_p(self.g_out_s.data_ptr()),
-                C.c_void_p(self.g_ncand.data_ptr()), C.c_void_p(st)))
+        req = self._request(filters=filters, scope=scope, grouping=grouping, prior=prior, prior_weight=prior_weight)
+        st = self._stream()
+        check(self._search(
+            self.s._h, self.slot, Qdev.data_ptr(), self.T, self.B, self.nprobe, self.k, req, self.g_out_p.data_ptr(),
+            self.g_out_s.data_ptr(), self.g_ncand.data_ptr(), st))
         check(lib().clb_search_result_groups_slot(
             self.s._h, C.c_int(self.slot), gh, i64(group_base), C.c_void_p(self.g_out_p.data_ptr()), i64(self.B), i64(self.k),
             C.c_void_p(self.g_out_g.data_ptr()), C.c_void_p(self.g_edges.data_ptr()), C.c_void_p(st)))
         return block
 
     def phase1(self, Qdev, filters=None, scope="candidates", grouping=None, group_base: int = 0, prior=None, prior_weight=1.0):
-        """Two-phase sharded search, first half (clb_search_shard_phase1): everything up to pass 1 on this shard.
+        """Two-phase sharded search, first half (clb_search_shard_phase1_request_slot): everything up to pass 1 on this shard.
         Returns the (B, k) tensor of the shard's k largest approximate scores per query, to be all-gathered.
-        `filters` / `scope` as in __call__ (clb_search_shard_phase1_filtered_slot: at most 64 queries per call when one is
-        filtered); phase2 takes none -- it continues on the filtered candidates phase 1 left on the slot.
+        `filters` / `scope` as in __call__ (at most 64 queries per call when one is filtered); phase2 takes none -- it continues on the filtered candidates phase 1 left on the slot.
         `grouping` (this shard's PassageGrouping) with `group_base` (the global index of the shard's first group): the grouped
-        form, clb_search_shard_phase1_grouped_slot -- returns (local_top, local_gid), the best approximate score of the
+        form -- returns (local_top, local_gid), the best approximate score of the
         shard's k best groups and their global group indices (int64), both (B, k) and both to be all-gathered.
-        `prior` (this shard's PassagePrior) with `prior_weight` (the group's weight): clb_search_shard_phase1_prior_slot --
+        `prior` (this shard's PassagePrior) with `prior_weight` (the group's weight):
         the published scores are the BOOSTED approximate scores, and the call returns (local_top, local_gid or None,
         local_mabs): local_mabs [B] float32 is the shard's largest boosted approximate score by magnitude per query, to be
         all-gathered with the others (phase 2 forms its rounding slack from the maximum over the shards)."""
         import torch
         self._check_queries(Qdev)
+        req = self._request(filters=filters, scope=scope, grouping=grouping, prior=prior, prior_weight=prior_weight,
+                            group_base=group_base)
         if not hasattr(self, "local_top"):
             self.local_top = torch.empty((self.B, self.k), dtype=torch.float32, device=self.dev)
-        st = torch.cuda.current_stream(self.dev).cuda_stream
+        if grouping is not None and not hasattr(self, "local_gid"):
+            self.local_gid = torch.empty((self.B, self.k), dtype=torch.int64, device=self.dev)
+        if prior is not None and not hasattr(self, "local_mabs"):
+            self.local_mabs = torch.zeros(self.B, dtype=torch.float32, device=self.dev)
+        gid = self.local_gid if grouping is not None else None
+        mabs = self.local_mabs if prior is not None else None
+        check(self._phase1(
+            self.s._h, self.slot, Qdev.data_ptr(), self.T, self.B, self.nprobe, self.k, req, self.local_top.data_ptr(),
+            None if gid is None else gid.data_ptr(), None if mabs is None else mabs.data_ptr(), self._stream()))
         if prior is not None:
-            from .searcher import _prior_weight, _scope_code
-            w = _prior_weight(prior, prior_weight, None)
-            if grouping is not None and not hasattr(self, "local_gid"):
-                self.local_gid = torch.empty((self.B, self.k), dtype=torch.int64, device=self.dev)
-            if not hasattr(self, "local_mabs"):
-                self.local_mabs = torch.zeros(self.B, dtype=torch.float32, device=self.dev)
-            gid = self.local_gid if grouping is not None else None
-            check(lib().clb_search_shard_phase1_prior_slot(
-                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
-                None if filters is None else self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)),
-                None if grouping is None else self.s._grouping_handle(grouping), i64(group_base), prior._h, C.c_float(w),
-                C.c_void_p(self.local_top.data_ptr()), None if gid is None else C.c_void_p(gid.data_ptr()),
-                C.c_void_p(self.local_mabs.data_ptr()), C.c_void_p(st)))
-            return self.local_top, gid, self.local_mabs
-        if grouping is not None:
-            from .searcher import _scope_code
-            if not hasattr(self, "local_gid"):
-                self.local_gid = torch.empty((self.B, self.k), dtype=torch.int64, device=self.dev)
-            check(lib().clb_search_shard_phase1_grouped_slot(
-                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
-                None if filters is None else self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)),
-                self.s._grouping_handle(grouping), i64(group_base), C.c_void_p(self.local_top.data_ptr()),
-                C.c_void_p(self.local_gid.data_ptr()), C.c_void_p(st)))
-            return self.local_top, self.local_gid
-        if filters is not None:
-            from .searcher import _scope_code
-            check(lib().clb_search_shard_phase1_filtered_slot(
-                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
-                self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)), C.c_void_p(self.local_top.data_ptr()),
-                C.c_void_p(st)))
-            return self.local_top
-        check(lib().clb_search_shard_phase1_slot(self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B),
-                                            i64(self.nprobe), i64(self.k), C.c_void_p(self.local_top.data_ptr()),
-                                            C.c_void_p(st)))
-        return self.local_top
+            return self.local_top, gid, mabs
+        return self.local_top if gid is None else (self.local_top, gid)
 
     def phase2(self, Qdev, all_top, all_gid=None, grouping=None, group_base: int = 0, prior=None, prior_weight=1.0,
                all_mabs=None):
-        """Second half (clb_search_shard_phase2).  all_top: (n_shards, B, k) gathered `local_top` blocks.
+        """Second half (clb_search_shard_phase2_request_slot).  all_top: (n_shards, B, k) gathered `local_top` blocks.
         With `grouping` / `group_base` as in phase1 and `all_gid`, the gathered `local_gid` blocks: the grouped form
-        (clb_search_shard_phase2_grouped_slot) -- the result goes into the packed grouped block, which is returned (for
+        -- the result goes into the packed grouped block, which is returned (for
         merge_grouped_packed, after the all-gather).
         With `prior` / `prior_weight` as in phase1 and `all_mabs`, the gathered `local_mabs` blocks (n_shards, B): the form
-        with a prior (clb_search_shard_phase2_prior_slot), with or without a grouping; it returns what the form without a
+        with a prior, with or without a grouping; it returns what the form without a
         prior returns."""
         import torch
         from ._lib import ArgumentError
@@ -389,41 +377,24 @@ class DeviceSearch:
         if (all_top.dtype != torch.float32 or all_top.dim() != 3 or tuple(all_top.shape[1:]) != (self.B, self.k)
                 or not all_top.is_contiguous() or all_top.device != self.dev):
             raise ArgumentError(f"all_top must be a contiguous float32 (n_shards, {self.B}, {self.k}) tensor on {self.dev}")
-        st = torch.cuda.current_stream(self.dev).cuda_stream
-        if grouping is not None:
+        g = grouping is not None
+        if g:
             if (all_gid is None or all_gid.dtype != torch.int64 or all_gid.shape != all_top.shape or not all_gid.is_contiguous()
                     or all_gid.device != self.dev):
                 raise ArgumentError(f"all_gid must be a contiguous int64 tensor of all_top's shape on {self.dev}")
             block = self._grouped_block()
+        req = self._request(grouping=grouping, prior=prior, prior_weight=prior_weight, group_base=group_base)
         if prior is not None:
-            from .searcher import _prior_weight
-            w = _prior_weight(prior, prior_weight, None)
             if (all_mabs is None or all_mabs.dtype != torch.float32 or tuple(all_mabs.shape) != (all_top.shape[0], self.B)
                     or not all_mabs.is_contiguous() or all_mabs.device != self.dev):
                 raise ArgumentError(f"all_mabs must be a contiguous float32 (n_shards, {self.B}) tensor on {self.dev}")
-            g = grouping is not None
-            out_p, out_s, ncand = (self.g_out_p, self.g_out_s, self.g_ncand) if g else (self.out_p, self.out_s, self.ncand)
-            check(lib().clb_search_shard_phase2_prior_slot(
-                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
-                C.c_void_p(all_top.data_ptr()), C.c_void_p(all_gid.data_ptr()) if g else None, C.c_void_p(all_mabs.data_ptr()),
-                i64(all_top.shape[0]), self.s._grouping_handle(grouping) if g else None, i64(group_base), prior._h, C.c_float(w),
-                C.c_void_p(out_p.data_ptr()), C.c_void_p(out_s.data_ptr()), C.c_void_p(self.g_out_g.data_ptr()) if g else None,
-                C.c_void_p(ncand.data_ptr()), C.c_void_p(self.g_edges.data_ptr()) if g else None, C.c_void_p(st)))
-            return block if g else (self.out_p, self.out_s)
-        if grouping is not None:
-            check(lib().clb_search_shard_phase2_grouped_slot(
-                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
-                C.c_void_p(all_top.data_ptr()), C.c_void_p(all_gid.data_ptr()), i64(all_top.shape[0]),
-                self.s._grouping_handle(grouping), i64(group_base), C.c_void_p(self.g_out_p.data_ptr()),
-                C.c_void_p(self.g_out_s.data_ptr()), C.c_void_p(self.g_out_g.data_ptr()), C.c_void_p(self.g_ncand.data_ptr()),
-                C.c_void_p(self.g_edges.data_ptr()), C.c_void_p(st)))
-            return block
-        check(lib().clb_search_shard_phase2_slot(self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B),
-                                            i64(self.nprobe), i64(self.k), C.c_void_p(all_top.data_ptr()),
-                                            i64(all_top.shape[0]), C.c_void_p(self.out_p.data_ptr()),
-                                            C.c_void_p(self.out_s.data_ptr()), C.c_void_p(self.ncand.data_ptr()),
-                                            C.c_void_p(st)))
-        return self.out_p, self.out_s
+        out_p, out_s, ncand = (self.g_out_p, self.g_out_s, self.g_ncand) if g else (self.out_p, self.out_s, self.ncand)
+        check(self._phase2(
+            self.s._h, self.slot, Qdev.data_ptr(), self.T, self.B, self.nprobe, self.k, req, all_top.data_ptr(),
+            all_gid.data_ptr() if g else None, None if prior is None else all_mabs.data_ptr(), all_top.shape[0], out_p.data_ptr(),
+            out_s.data_ptr(), self.g_out_g.data_ptr() if g else None, ncand.data_ptr(), self.g_edges.data_ptr() if g else None,
+            self._stream()))
+        return block if g else (self.out_p, self.out_s)
 
     def capture(self, Qstatic, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0,
                 after=None):
@@ -456,71 +427,32 @@ class DeviceSearch:
 
     def __call__(self, Qdev, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0,
                  after=None):
-        """Qdev: torch float32 tensor holding B queries laid out (B, T, dim) contiguous == Julia (dim, T, B).
+        """Qdev: torch float32 tensor holding B queries laid out (B, T, dim) contiguous == Julia (dim, T, B).  One call of
+        clb_search_batch_request_device_slot, whatever the keywords.
         `filters`: one PassageFilter or a sequence of B entries (None = unfiltered), `scope` "candidates" / "all"
         (Searcher.search_batch); `ncand` then holds the counts after the filter.
         `grouping`: one PassageGrouping for the batch (Searcher.search_batch): the k best groups of every query, short
         results padded with pid 0 / -inf, `ncand` the candidate groups.
         `per_group` (an integer m, 1..16; needs `grouping`): returns `hit_p` / `hit_s`, (B, k, m) tensors == Julia (m, k, B)
         -- the m best candidate passages of every group, best first, padded with pid 0 / -inf
-        (clb_search_batch_grouped_hits_device_slot); `out_p` / `out_s` are not written.
+        (the request's per_group); `out_p` / `out_s` are not written.
         `prior` (one PassagePrior for the batch) with `prior_weight`: rank by score + prior_weight * value
-        (Searcher.search_batch, clb_search_batch_prior_device_slot); not with `per_group`.
+        (Searcher.search_batch); not with `per_group`.
         `after`: a pair of device tensors (scores float32[B], pids int64[B]) on the searcher's device, one cursor per query --
-        the next k results past it, always padded (Searcher.search_batch, clb_search_batch_after_device_slot); a NaN score
+        the next k results past it, always padded (Searcher.search_batch; the cursors stay on the device); a NaN score
         gives an empty page here.  Not with `grouping`, `per_group` or `prior`."""
         import torch
         self._check_queries(Qdev)
-        st = torch.cuda.current_stream(self.dev).cuda_stream
-        if after is not None:
-            from .searcher import _after_keywords, _scope_code
-            _after_keywords(after, grouping, per_group, prior)
-            self._check_cursors(after)
-            check(lib().clb_search_batch_after_device_slot(
-                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
-                None if filters is None else self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)),
-                C.c_void_p(after[0].data_ptr()), C.c_void_p(after[1].data_ptr()), C.c_void_p(self.out_p.data_ptr()),
-                C.c_void_p(self.out_s.data_ptr()), C.c_void_p(self.ncand.data_ptr()), C.c_void_p(st)))
-            return self.out_p, self.out_s
-        if prior is not None:
-            from .searcher import _prior_weight, _scope_code
-            w = _prior_weight(prior, prior_weight, per_group)
-            check(lib().clb_search_batch_prior_device_slot(
-                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
-                None if filters is None else self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)),
-                None if grouping is None else self.s._grouping_handle(grouping), prior._h, C.c_float(w),
-                C.c_void_p(self.out_p.data_ptr()), C.c_void_p(self.out_s.data_ptr()), C.c_void_p(self.ncand.data_ptr()),
-                C.c_void_p(st)))
-            return self.out_p, self.out_s
+        req = self._request(filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
+                            prior_weight=prior_weight, after=after)
+        out_p, out_s = self.out_p, self.out_s
         if per_group is not None:
-            from .searcher import _per_group, _scope_code
-            m = _per_group(per_group, grouping)
+            m = int(req.per_group)
             if getattr(self, "hit_p", None) is None or self.hit_p.shape[2] != m:
                 self.hit_p = torch.zeros((self.B, self.k, m), dtype=torch.int64, device=self.dev)
                 self.hit_s = torch.zeros((self.B, self.k, m), dtype=torch.float32, device=self.dev)
-            check(lib().clb_search_batch_grouped_hits_device_slot(
-                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
-                None if filters is None else self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)),
-                self.s._grouping_handle(grouping), i64(m), C.c_void_p(self.hit_p.data_ptr()), C.c_void_p(self.hit_s.data_ptr()),
-                C.c_void_p(self.ncand.data_ptr()), C.c_void_p(st)))
-            return self.hit_p, self.hit_s
-        if grouping is not None:
-            from .searcher import _scope_code
-            check(lib().clb_search_batch_grouped_device_slot(
-                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
-                None if filters is None else self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)),
-                self.s._grouping_handle(grouping), C.c_void_p(self.out_p.data_ptr()), C.c_void_p(self.out_s.data_ptr()),
-                C.c_void_p(self.ncand.data_ptr()), C.c_void_p(st)))
-            return self.out_p, self.out_s
-        if filters is not None:
-            from .searcher import _scope_code
-            check(lib().clb_search_batch_filtered_device_slot(
-                self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T), i64(self.B), i64(self.nprobe), i64(self.k),
-                self.s._filter_handles(filters, self.B), C.c_int(_scope_code(scope)), C.c_void_p(self.out_p.data_ptr()),
-                C.c_void_p(self.out_s.data_ptr()), C.c_void_p(self.ncand.data_ptr()), C.c_void_p(st)))
-            return self.out_p, self.out_s
-        check(lib().clb_search_batch_device_slot(self.s._h, C.c_int(self.slot), C.c_void_p(Qdev.data_ptr()), i64(self.T),
-                                                 i64(self.B), i64(self.nprobe), i64(self.k),
-                                                 C.c_void_p(self.out_p.data_ptr()), C.c_void_p(self.out_s.data_ptr()),
-                                                 C.c_void_p(self.ncand.data_ptr()), C.c_void_p(st)))
-        return self.out_p, self.out_s
+            out_p, out_s = self.hit_p, self.hit_s
+        check(self._search(
+            self.s._h, self.slot, Qdev.data_ptr(), self.T, self.B, self.nprobe, self.k, req, out_p.data_ptr(), out_s.data_ptr(),
+            self.ncand.data_ptr(), self._stream()))
+        return out_p, out_s

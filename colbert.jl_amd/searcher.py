@@ -12,7 +12,7 @@ from typing import Optional
 import numpy as np
 
 from . import storage
-from ._lib import BoundsError, ColBERTError, check, colmajor, fptr, i64, lib
+from ._lib import BoundsError, ColBERTError, SearchRequest, check, colmajor, fptr, i64, lib, request_entry
 from .config import ColBERTConfig
 
 
@@ -199,6 +199,35 @@ def _after_arrays(after, B: int):
     if np.isnan(s).any():
         raise ArgumentError(f"the cursor score of query {int(np.nonzero(np.isnan(s))[0][0])} is NaN")
     return s, p
+
+
+def search_request(searcher, B: int, *, filters=None, scope="candidates", grouping=None, per_group=None, prior=None,
+                   prior_weight=1.0, after=None, pad_short=False, group_base: int = 0, cursor_arrays=_after_arrays) -> SearchRequest:
+    """The keywords of a search call of `searcher` over B queries, checked on the host, as the clb_search_request every
+    search entry point takes (include/colbert_hip.h).  Raises what the helpers above raise, in their order: scope, `after`
+    against the keywords it is not offered with, the cursors, the prior and its weight (never with `per_group`), `per_group`,
+    the filters, the grouping.  With filters or cursors the host route always pads.  `cursor_arrays(after, B)` gives the two cursor
+    arrays: host arrays here, DeviceSearch passes its own check of device tensors.  The request holds a reference to every
+    array it points at (`_keep`): it is valid as long as it lives."""
+    r = SearchRequest(struct_bytes=C.sizeof(SearchRequest), scope=_scope_code(scope), group_base=int(group_base),
+                      pad_short=1 if (pad_short or filters is not None or after is not None) else 0)
+    cursors = ()
+    if after is not None:
+        _after_keywords(after, grouping, per_group, prior)
+        cursors = tuple(cursor_arrays(after, B))
+        r.after_scores, r.after_pids = (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data for a in cursors)
+    if prior is not None:
+        r.prior_weight = _prior_weight(prior, prior_weight, per_group)
+        r.prior = prior._h
+    if per_group is not None:
+        r.per_group = _per_group(per_group, grouping)
+    handles = None if filters is None else searcher._filter_handles(filters, B)
+    if handles is not None:
+        r.filters = handles
+    if grouping is not None:
+        r.grouping = searcher._grouping_handle(grouping)
+    r._keep = (handles, cursors)
+    return r
 
 
 def next_cursor(pids, scores):
@@ -660,7 +689,7 @@ class Searcher:
 
     def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
                      scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0, after=None):
-        """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B]).
+        """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B]); one call of clb_search_batch_request.
         `filters`: one PassageFilter for every query, or a sequence of B entries (None = that query is unfiltered); with
         filters the results are always padded (pid 0 / -Inf past n_candidates[b], the count AFTER the filter) and `scope`
         is "candidates" (candidates that are in the filter) or "all" (the filter's passages themselves).
@@ -668,13 +697,13 @@ class Searcher:
         passage, and n_candidates counts the candidate groups (after any filter); short results as without a grouping.
         `per_group` (an integer m, 1..16; needs `grouping`): pids and scores are (m, k, B) -- [:, j, b] the m best CANDIDATE
         passages of query b's j-th group, score descending, the lower pid first among equal scores, padded with pid 0 / -Inf
-        when the group has fewer (clb_search_batch_grouped_hits); row 0 is what the call returns without per_group, and the
+        when the group has fewer; row 0 is what the call returns without per_group, and the
         groups, their order and n_candidates are unchanged.
         `prior`: one PassagePrior for the whole batch, with one finite `prior_weight` -- every candidate passage p (after any
         filter) is ranked by E = fl32(score + fl32(prior_weight * value[p])), the lower pid first among equal E, and the
         scores returned are E; with `grouping` a document is represented by its candidate with the largest E.  The candidates,
         n_candidates and short results are those of the call without a prior.  Not with `per_group` (Unsupported).
-        `after`: a pair (scores float32[B], pids int64[B]) of cursors, one per query (clb_search_batch_after) -- query b returns
+        `after`: a pair (scores float32[B], pids int64[B]) of cursors, one per query -- query b returns
         the first k of its candidates p (after any filter) with score < scores[b], or score == scores[b] and pid > pids[b], by
         (score descending, pid ascending): what its ranking continues with.  `after=next_cursor(pids, scores)` of the previous
         page walks the whole ranking in pieces of k, bit for bit.  A score of +Inf means no cursor for that query, -Inf an
@@ -685,53 +714,13 @@ class Searcher:
         if q.ndim != 3 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T, B)")
         B = q.shape[2]
-        code = _scope_code(scope)
-        _after_keywords(after, grouping, per_group, prior)
-        if after is not None:
-            cs, cp = _after_arrays(after, B)
-            handles = None if filters is None else self._filter_handles(filters, B)
-            pids = np.zeros((k, B), dtype=np.int64, order="F"); scores = np.zeros((k, B), dtype=np.float32, order="F")
-            ncand = np.zeros(B, dtype=np.int64)
-            check(lib().clb_search_batch_after(self._h, fptr(q), i64(q.shape[1]), i64(B), i64(nprobe or self.config.nprobe), i64(k),
-                                               handles, C.c_int(code), fptr(cs), fptr(cp), fptr(pids), fptr(scores), fptr(ncand)))
-            return pids, scores, ncand
-        if prior is not None:
-            w = _prior_weight(prior, prior_weight, per_group)
-            handles = None if filters is None else self._filter_handles(filters, B)
-            pids = np.zeros((k, B), dtype=np.int64, order="F"); scores = np.zeros((k, B), dtype=np.float32, order="F")
-            ncand = np.zeros(B, dtype=np.int64)
-            check(lib().clb_search_batch_prior(self._h, fptr(q), i64(q.shape[1]), i64(B), i64(nprobe or self.config.nprobe), i64(k),
-                                               handles, C.c_int(code),
-                                               None if grouping is None else self._grouping_handle(grouping), prior._h,
-                                               C.c_float(w), C.c_int(1 if (pad_short or filters is not None) else 0),
-                                               fptr(pids), fptr(scores), fptr(ncand)))
-            return pids, scores, ncand
-        if per_group is not None:
-            m = _per_group(per_group, grouping)
-            handles = None if filters is None else self._filter_handles(filters, B)
-            pids = np.zeros((m, k, B), dtype=np.int64, order="F"); scores = np.zeros((m, k, B), dtype=np.float32, order="F")
-            ncand = np.zeros(B, dtype=np.int64)
-            check(lib().clb_search_batch_grouped_hits(self._h, fptr(q), i64(q.shape[1]), i64(B), i64(nprobe or self.config.nprobe),
-                                                      i64(k), handles, C.c_int(code), self._grouping_handle(grouping), i64(m),
-                                                      C.c_int(1 if (pad_short or filters is not None) else 0), fptr(pids),
-                                                      fptr(scores), fptr(ncand)))
-            return pids, scores, ncand
-        pids = np.zeros((k, B), dtype=np.int64, order="F"); scores = np.zeros((k, B), dtype=np.float32, order="F")
+        req = search_request(self, B, filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
+                             prior_weight=prior_weight, after=after, pad_short=pad_short)
+        shape = (k, B) if per_group is None else (int(req.per_group), k, B)
+        pids = np.zeros(shape, dtype=np.int64, order="F"); scores = np.zeros(shape, dtype=np.float32, order="F")
         ncand = np.zeros(B, dtype=np.int64)
-        if grouping is not None:
-            handles = None if filters is None else self._filter_handles(filters, B)
-            check(lib().clb_search_batch_grouped(self._h, fptr(q), i64(q.shape[1]), i64(B), i64(nprobe or self.config.nprobe),
-                                                 i64(k), handles, C.c_int(code), self._grouping_handle(grouping),
-                                                 C.c_int(1 if (pad_short or filters is not None) else 0), fptr(pids),
-                                                 fptr(scores), fptr(ncand)))
-            return pids, scores, ncand
-        if filters is not None:
-            handles = self._filter_handles(filters, B)
-            check(lib().clb_search_batch_filtered(self._h, fptr(q), i64(q.shape[1]), i64(B), i64(nprobe or self.config.nprobe),
-                                                  i64(k), handles, C.c_int(code), fptr(pids), fptr(scores), fptr(ncand)))
-            return pids, scores, ncand
-        check(lib().clb_search_batch(self._h, fptr(q), i64(q.shape[1]), i64(B), i64(nprobe or self.config.nprobe), i64(k),
-                                     C.c_int(1 if pad_short else 0), fptr(pids), fptr(scores), fptr(ncand)))
+        check(request_entry("clb_search_batch_request")(self._h, fptr(q), q.shape[1], B, nprobe or self.config.nprobe, k, req,
+                                                        fptr(pids), fptr(scores), fptr(ncand)))
         return pids, scores, ncand
 
     def retrieve(self, Q, nprobe: Optional[int] = None):

@@ -586,6 +586,52 @@ int clb_search_shard_phase2_prior_slot(clb_searcher* s, int slot, const float* d
 int clb_debug_prior_tau_device(const float* d_all_top, const int64_t* d_all_gid, const float* d_all_mabs, const float* d_eps,
                                int64_t n_shards, int64_t B, int64_t k, float* d_tau_in, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The search request: everything a search call may carry besides its queries, sizes and outputs, as ONE struct.  Every named
+ * search entry point above fills a request and makes one of the four calls below; a caller may do the same.  The rules of
+ * the fields are those documented at the named entries; which fields combine, and which named entry fills which, is the
+ * table of DESIGN section 5 ("The search request") and INTEGRATION.md.  All of them are checked in one place, and the checks
+ * that need no searcher (struct_bytes, the per_group range, a finite weight, the cursor pair, the combinations) run before
+ * the searcher is looked at.  Zero-initialise the struct, set struct_bytes, then the fields of the features in use:
+ * everything left zero / NULL means "none".
+ * Refused combinations, all CLB_EUNSUPPORTED: a prior with per_group > 1 (the hits are built from approximate MaxSim scores),
+ * cursors with a grouping, cursors with a prior; on the phase routes also per_group > 1 and cursors, and phase 2 takes no
+ * filters (it continues on the candidates phase 1 left on the slot).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct clb_search_request {
+    int64_t struct_bytes;                 /* sizeof this struct: anything else is CLB_EARGUMENT */
+    const clb_filter* const* filters;     /* HOST array of B handles (a NULL entry: that query is unfiltered), or NULL */
+    int scope;                            /* CLB_FILTER_CANDIDATES / CLB_FILTER_ALL */
+    int pad_short;                        /* host route only (the device routes always pad): see clb_search_batch */
+    const clb_grouping* grouping;         /* or NULL */
+    int64_t per_group;                    /* 0: none; 1: the grouped search itself; 2..CLB_MAX_PER_GROUP: hits (needs grouping) */
+    int64_t group_base;                   /* phase routes with a grouping: the global index of the shard's first group */
+    const clb_prior* prior;               /* or NULL: prior_weight is then ignored */
+    float prior_weight;
+    const float* after_scores;            /* cursors, [B] each, both or neither: HOST arrays on the host route (a NaN score */
+    const int64_t* after_pids;            /* is CLB_EARGUMENT), DEVICE arrays on the device route */
+} clb_search_request;
+/* The host route: clb_search_batch and every clb_search_batch_* entry without _device.  With per_group > 1 the outputs
+ * hold B * k * per_group entries. */
+int clb_search_batch_request(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                             const clb_search_request* req, int64_t* out_pids, float* out_scores, int64_t* n_cand);
+/* The device route: every clb_search_batch_*_device_slot entry. */
+int clb_search_batch_request_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const clb_search_request* req, int64_t* d_out_pids, float* d_out_scores,
+                                         int64_t* d_n_cand, void* hip_stream);
+/* The phase routes: every clb_search_shard_phase1_* / phase2_* entry.  The exchange buffers belong to the phase, not to the
+ * request: d_local_gid / d_all_gid / d_out_gids / d_edge_gids are read or written only with a grouping, d_local_mabs /
+ * d_all_mabs only with a prior (NULL otherwise).  Phase 2 must be given the grouping, group_base, prior and weight (bit for
+ * bit) of the phase 1 it follows. */
+int clb_search_shard_phase1_request_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const clb_search_request* req, float* d_local_top, int64_t* d_local_gid,
+                                         float* d_local_mabs, void* hip_stream);
+int clb_search_shard_phase2_request_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                         int64_t k, const clb_search_request* req, const float* d_all_top,
+                                         const int64_t* d_all_gid, const float* d_all_mabs, int64_t n_shards, int64_t* d_out_pids,
+                                         float* d_out_scores, int64_t* d_out_gids, int64_t* d_n_cand, int64_t* d_edge_gids,
+                                         void* hip_stream);
+
 /* retrieve()  (src/search/ranking.jl:23-44) on its own -- test hook.  out_pids needs n_docs entries. */
 int clb_retrieve(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe, int64_t* out_pids,
                  int64_t* n_out);
