@@ -13,6 +13,7 @@
 #include "generic_kernels.hpp"
 #include "group_kernels.hpp"
 #include "index_change_kernels.hpp"
+#include "list_kernels.hpp"
 #include "prior_kernels.hpp"
 #include "search_kernels.hpp"
 #include "sort.hpp"
@@ -132,6 +133,9 @@ struct Workspace {
     // their number, the threshold of after_cut_kernel, and the host route's copy of the cursors
     bool after = false;
     DevBuf after_list, after_n, after_tau, after_cur_s, after_cur_p;
+    // candidate lists (list_kernels.hpp) on the host route, sized by the first listed call: the sub-batch's rows of the pid
+    // block, its lengths and, when the call asks for them, its list scores
+    DevBuf lst_pids, lst_lens, lst_scores;
     DevBuf g_cells, g_keys, g_keys2, g_vals, g_vals2, g_scratch, g_sort_tmp;   // general-shape path (generic_kernels.hpp)
 };
 
@@ -209,6 +213,12 @@ struct Batch {
     // search after a cursor: the sub-batch's cursors on the device, [B] each; nullptr: none, and the sub-batch launches
     // exactly what it launches without them
     const float* d_after_s = nullptr; const int64_t* d_after_p = nullptr;
+    // candidate lists: the sub-batch's rows of the pid block ([B][list_stride]) and its lengths ([B]) on the device -- they ARE
+    // its candidate sets (nullptr: none, and the sub-batch launches exactly what it launches without them) -- and the list
+    // scores it is to leave ([B][list_stride], or nullptr): asking for them makes the call a single exact pass
+    const int64_t* d_list_pids = nullptr; const int64_t* d_list_lens = nullptr;
+    int64_t list_stride = 0;
+    float* d_list_scores = nullptr;
     bool stats_keep = false;    // the 2nd, 3rd ... sub-batch of one call: the work counters accumulate over the call
     int phase = 0, n_shards = 0;    // two-phase sharded search (run_search)
     float* d_local_top = nullptr; const float* d_all_top = nullptr;
@@ -224,6 +234,12 @@ Batch make_batch(const float* dQ, int64_t B, int64_t T, int64_t nprobe, int64_t 
     Batch q;
     q.dQ = dQ; q.B = (int)B; q.T = (int)T; q.nprobe = (int)nprobe; q.k = (int)k;
     return q;
+}
+
+// Does this sub-batch run as the two-pass pipeline?  By the handle's mode -- except a call that asks for list scores, which
+// needs the exact score of EVERY candidate and so runs as the single exact pass (the two are identical by construction).
+inline bool two_pass_mode(const clb_searcher* s, const Batch& q) {
+    return s->mode == 1 && s->approx_ok && q.T <= 32 && !q.d_list_scores;
 }
 
 struct Timed {
@@ -450,7 +466,7 @@ int run_retrieve(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) 
     const int B = q.B, T = q.T, nprobe = q.nprobe;
     const int TT = token_tiles(T), Tpad = TT * 32;
     const int n_tiles = (int)((s->K + 31) / 32);
-    const bool want_half = s->mode == 1 && s->approx_ok && T <= 32;
+    const bool want_half = two_pass_mode(s, q);
     w.x1_table = false;
     w.have_range = false;
     w.cell8 = false;
@@ -615,7 +631,35 @@ int mark_and_compact_impl(clb_searcher* s, Workspace& w, hipStream_t st, const B
     return CLB_OK;
 }
 
+// S3l: the candidates of the B queries from b0 on are the caller's lists (list_kernels.hpp) -- the listed passages go into
+// the candidate bitmap, and the compaction reads it through the handle's live bitmap as every query's filter word
+// (CLB_FILTER_CANDIDATES: marked AND filter), which drops the passages without embeddings as CLB_FILTER_ALL drops them
+int list_and_compact(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int B, bool timed) {
+    FilterArgs fa{};
+    fa.live = s->live.as<uint32_t>();
+    for (int i = 0; i < B && i < kFilterQueries; ++i) fa.bits[i] = fa.live;
+    fa.all = 0;
+    const int L = (int)q.list_stride;
+    uint32_t* bitmap = w.bitmap.as<uint32_t>() + (size_t)b0 * w.W;
+    int* blocksum = w.blocksum.as<int>() + (size_t)b0 * w.nblk_bitmap;
+    {
+        Timed t(s, timed ? KID_MARK : -1, st);
+        hipLaunchKernelGGL(list_mark_kernel, dim3((L + 255) / 256, B), dim3(256), 0, st, q.d_list_pids + (size_t)b0 * L,
+                           q.d_list_lens + b0, L, s->pid_offset, (int)s->n_docs, bitmap, w.W);
+    }
+    {
+        Timed t(s, timed ? KID_COMPACT : -1, st);
+        hipLaunchKernelGGL(bitmap_count_kernel<true>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st, bitmap, blocksum, w.W, fa);
+        hipLaunchKernelGGL(bitmap_emit_kernel<true>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st, bitmap, blocksum,
+                           w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap, s->doc_off.as<uint32_t>(),
+                           w.cand_hdr.as<uint2>() + (size_t)b0 * w.cand_cap, w.W, w.cand_cap, w.ncand.as<int>() + b0, fa);
+    }
+    CLB_HIP(hipGetLastError());
+    return CLB_OK;
+}
+
 int mark_and_compact(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int B, int Tpad, int NPs, bool timed) {
+    if (q.d_list_pids) return list_and_compact(s, w, st, q, b0, B, timed);
     bool filt = false;
     for (int b = b0; q.filt && b < b0 + B; ++b) filt |= q.filt[b] != nullptr;
     return filt ? mark_and_compact_impl<true>(s, w, st, q, b0, B, Tpad, NPs, timed)
@@ -752,11 +796,23 @@ void launch_after(const clb_searcher* s, Workspace& w, hipStream_t st, const Bat
                        w.after_n.as<int>() + b0);
 }
 
+// L2 for queries b0 .. b0 + n - 1 of a call that asks for list scores (list_scores_kernel; nothing otherwise), behind the
+// exact scores of all their candidates and the boost of a prior
+void launch_list_scores(const clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int n) {
+    if (!q.d_list_scores) return;
+    const int L = (int)q.list_stride;
+    hipLaunchKernelGGL(list_scores_kernel, dim3((L + 255) / 256, n), dim3(256), 0, st, q.d_list_pids + (size_t)b0 * L,
+                       q.d_list_lens + b0, L, s->pid_offset, (int)s->n_docs, w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap,
+                       w.ncand.as<int>() + b0, w.scores.as<float>() + (size_t)b0 * w.cand_cap, w.cand_cap,
+                       q.d_list_scores + (size_t)b0 * L);
+}
+
 // S7 of the general-shape path for queries b0 .. b0 + n - 1, the exact scores of all their candidates in place (with a
 // prior: boosted first; with cursors: the candidates after them) -- with a grouping: one collapse, then the top-k forms
 // rank its list
 int topk_of(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int n) {
     launch_boost(w, st, q, b0, n, nullptr, nullptr, nullptr);
+    launch_list_scores(s, w, st, q, b0, n);
     if (q.d_after_s) {
         launch_after(s, w, st, q, b0, n, nullptr, nullptr);
         return launch_topk(s, w, st, q, b0, n, w.after_list.as<int>(), w.after_n.as<int>(), 0);
@@ -913,7 +969,7 @@ int launch_select(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q,
 int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
     const float* dQ = q.dQ;
     const int B = q.B, T = q.T, k = q.k, phase = q.phase;
-    const bool two_pass = s->mode == 1 && s->approx_ok && T <= 32;
+    const bool two_pass = two_pass_mode(s, q);
     if (phase != 0 && !two_pass) return fail(CLB_EUNSUPPORTED, "the two-phase sharded search needs the two-pass mode");
     if (s->generic || T > 128) return run_search_general(s, w, st, q);
     s->prof.chain = nullptr;           // the first timed kernel of a call records its own start
@@ -1055,6 +1111,7 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
     const int* tnlist = nlist;
     auto collapse_exact = [&]() {
         launch_boost(w, st, q, 0, B, list, nlist, nullptr);     // with a prior: the exact scores become E = e + weight * value
+        launch_list_scores(s, w, st, q, 0, B);                  // (a call with list scores is the exact pass: list == nullptr)
         if (q.d_after_s) {      // with cursors (never with a grouping): only what lies after them is ranked
             launch_after(s, w, st, q, 0, B, list, nlist);
             tlist = w.after_list.as<int>(); tnlist = w.after_n.as<int>();
@@ -1148,9 +1205,10 @@ inline int64_t request_hits(const clb_search_request& r) { return r.per_group > 
 
 // EVERY rule of a search request and of the sizes of its call, in the order the entry points have always answered: first
 // what needs no searcher -- the struct itself, the per_group range, a finite weight, the cursor pair, the combinations that
-// are not offered, NaN cursors where the host can see them -- then the handle and the sizes (check_search_args), the route's
-// buffers and phase 1's group_base, then what is bound to the searcher (filters, grouping, prior) and the batch limit of a
-// filtered phase 1.  *filt_count as check_filters gives it.
+// are not offered, NaN cursors where the host can see them, the fields of the candidate lists -- then the handle and the sizes
+// (check_search_args), the route's buffers, the listed pids where the host can see them and phase 1's group_base, then what is
+// bound to the searcher (filters, grouping, prior) and the batch limit of a filtered phase 1.  *filt_count as check_filters
+// gives it, or with candidate lists the most candidates one of them can give.
 // route_buffers(): the route's own refusals of its plain parameters (the exchange buffers of a phase), answered where they
 // always were -- directly behind the sizes.
 template <class RouteBuffers>
@@ -1179,13 +1237,38 @@ int check_request(const clb_searcher* s, const clb_search_request* r, int64_t T,
         return fail(CLB_EARGUMENT, "phase 2 takes no filters: it continues on the candidates phase 1 left on the slot");
     for (int64_t b = 0; route == Route::host && after && b < B; ++b)
         if (std::isnan(r->after_scores[b])) return fail(CLB_EARGUMENT, "the cursor score of query %lld is NaN", (long long)b);
+    // candidate lists: the pair, the stride, and the two places they are not offered; on the host route every length
+    if ((r->list_pids == nullptr) != (r->list_lens == nullptr))
+        return fail(CLB_EARGUMENT, "list_pids and list_lens must both be given or both be null");
+    const bool listed = r->list_pids != nullptr;
+    if (!listed && r->list_scores) return fail(CLB_EARGUMENT, "list_scores without candidate lists (list_pids / list_lens)");
+    if (listed && (r->list_stride < 1 || r->list_stride > (int64_t)0x7fffffff))
+        return fail(CLB_EARGUMENT, "list_stride must be 1..2^31-1, got %lld", (long long)r->list_stride);
+    for (int64_t b = 0; listed && r->filters && b < B; ++b)
+        if (r->filters[b])                  // a list IS the candidate set
+            return fail(CLB_EUNSUPPORTED, "candidate lists together with filters are not supported");
+    if (phases && listed) return fail(CLB_EUNSUPPORTED, "the phase calls of a shard group take no candidate lists");
+    for (int64_t b = 0; route == Route::host && listed && b < B; ++b)
+        if (r->list_lens[b] < 0 || r->list_lens[b] > r->list_stride)
+            return fail(CLB_EARGUMENT, "the candidate list of query %lld has length %lld, outside 0..list_stride=%lld", (long long)b,
+                        (long long)r->list_lens[b], (long long)r->list_stride);
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     CLB_TRY(route_buffers());
+    // ... and, where the host can see them, every listed pid against the handle's range (the device route skips such a pid)
+    for (int64_t b = 0; route == Route::host && listed && b < B; ++b)
+        for (int64_t i = 0; i < r->list_lens[b]; ++i) {
+            const int64_t pid = r->list_pids[b * r->list_stride + i];
+            if (pid <= s->pid_offset || pid - s->pid_offset > s->n_docs)
+                return fail(CLB_EBOUNDS, "candidate list of query %lld, position %lld: pid %lld outside %lld..%lld", (long long)b,
+                            (long long)i, (long long)pid, (long long)s->pid_offset + 1, (long long)(s->pid_offset + s->n_docs));
+        }
     if (route == Route::phase1 && r->grouping && r->group_base < 0)
         return fail(CLB_EARGUMENT, "group_base must be >= 0, got %lld", (long long)r->group_base);
     CLB_TRY(check_filters(s, r->filters, B, r->scope, filt_count));
     CLB_TRY(check_grouping(s, r->grouping));
     CLB_TRY(check_prior(s, r->prior, r->prior_weight));
+    // a listed query has at most min(list_stride, n_docs) candidates: a host value, like a filter's population
+    if (listed) *filt_count = (size_t)std::min<int64_t>(r->list_stride, s->n_docs);
     if (route == Route::phase1) {
         bool filtered = false;
         for (int64_t b = 0; r->filters && b < B; ++b) filtered |= r->filters[b] != nullptr;
@@ -1199,15 +1282,16 @@ int check_request(const clb_searcher* s, const clb_search_request* r, int64_t T,
 
 // The sub-batch of queries b0 .. b0 + B - 1 of a call that carries the request r (checked by check_request, which gave
 // filt_count), with everything of r that every route hands to run_search alike: the sub-batch's slice of the handle array --
-// nullptr when none of its queries is filtered --, the grouping with its base and hits, the prior with its weight.  The
-// cursors stay with the route: it knows where they live.
+// nullptr when none of its queries is filtered --, the grouping with its base and hits, the prior with its weight, the stride
+// of the candidate lists.  The cursors and the list arrays stay with the route: it knows where they live.
 Batch make_batch(const float* dQ, int64_t B, int64_t T, int64_t nprobe, int64_t k, const clb_search_request& r, int64_t b0,
                  size_t filt_count) {
     Batch q = make_batch(dQ, B, T, nprobe, k);
     q.filt_all = r.scope == CLB_FILTER_ALL;
     for (int64_t b = b0; r.filters && b < b0 + q.B; ++b)
         if (r.filters[b]) q.filt = r.filters + b0;
-    q.filt_now = q.filt && q.filt_all ? filt_count : 0;
+    q.filt_now = (q.filt && q.filt_all) || r.list_pids ? filt_count : 0;
+    q.list_stride = r.list_pids ? r.list_stride : 0;
     q.grp = r.grouping; q.group_base = r.group_base; q.per_group = (int)request_hits(r);
     q.prior = r.prior; q.prior_weight = r.prior_weight;
     return q;
@@ -2049,6 +2133,10 @@ int clb_search_batch_request_device_slot(clb_searcher* s, int slot, const float*
     CLB_TRY(for_sub_batches(s, *w, T, B, nprobe, k, r, filt_count, [&](int64_t b0, Batch& q) -> int {
         q.dQ = d_Q + (size_t)b0 * T * s->dim;
         if (r.after_scores) { q.d_after_s = r.after_scores + b0; q.d_after_p = r.after_pids + b0; }
+        if (r.list_pids) {         // the sub-batch's own rows of the caller's device arrays
+            q.d_list_pids = r.list_pids + (size_t)b0 * r.list_stride; q.d_list_lens = r.list_lens + b0;
+            q.d_list_scores = r.list_scores ? r.list_scores + (size_t)b0 * r.list_stride : nullptr;
+        }
         q.d_out_pids = hits ? w->hit_p.as<int64_t>() : d_out_pids + (size_t)b0 * k;
         q.d_out_scores = hits ? w->hit_s.as<float>() : d_out_scores + (size_t)b0 * k;
         q.d_hit_pids = d_out_pids + (size_t)b0 * k * hits;
@@ -2075,9 +2163,22 @@ int clb_search_batch_request(clb_searcher* s, const float* Q, int64_t T, int64_t
     Workspace& w = *wp;
     hipStream_t st = s->stream;
     std::vector<int> nc((size_t)B), fl((size_t)B);
+    const size_t L = r.list_pids ? (size_t)r.list_stride : 0;
+    if (L) {        // room for one sub-batch's rows of the candidate lists
+        const size_t rows = (size_t)std::min<int64_t>(kSubBatch, B);
+        CLB_TRY(w.lst_pids.ensure(sizeof(int64_t) * rows * L));
+        CLB_TRY(w.lst_lens.ensure(sizeof(int64_t) * rows));
+        if (r.list_scores) CLB_TRY(w.lst_scores.ensure(sizeof(float) * rows * L));
+    }
     // the queries go up into the slot's own buffer and the results come back from it, sub-batch by sub-batch
     CLB_TRY(for_sub_batches(s, w, T, B, nprobe, k, r, filt_count, [&](int64_t b0, Batch& q) -> int {
         CLB_HIP(hipMemcpyAsync(w.Qdev.p, Q + (size_t)b0 * T * s->dim, sizeof(float) * q.B * T * s->dim, hipMemcpyHostToDevice, st));
+        if (L) {                   // the sub-batch's lists go up beside its queries
+            CLB_HIP(hipMemcpyAsync(w.lst_pids.p, r.list_pids + (size_t)b0 * L, sizeof(int64_t) * q.B * L, hipMemcpyHostToDevice, st));
+            CLB_HIP(hipMemcpyAsync(w.lst_lens.p, r.list_lens + b0, sizeof(int64_t) * q.B, hipMemcpyHostToDevice, st));
+            q.d_list_pids = w.lst_pids.as<int64_t>(); q.d_list_lens = w.lst_lens.as<int64_t>();
+            q.d_list_scores = r.list_scores ? w.lst_scores.as<float>() : nullptr;
+        }
         if (r.after_scores) {      // the sub-batch's cursors go up beside its queries
             CLB_HIP(hipMemcpyAsync(w.after_cur_s.p, r.after_scores + b0, sizeof(float) * q.B, hipMemcpyHostToDevice, st));
             CLB_HIP(hipMemcpyAsync(w.after_cur_p.p, r.after_pids + b0, sizeof(int64_t) * q.B, hipMemcpyHostToDevice, st));
@@ -2093,6 +2194,8 @@ int clb_search_batch_request(clb_searcher* s, const float* Q, int64_t T, int64_t
         CLB_HIP(hipMemcpyAsync(out_scores + (size_t)b0 * km, w.outs.p, sizeof(float) * q.B * km, hipMemcpyDeviceToHost, st));
         CLB_HIP(hipMemcpyAsync(nc.data() + b0, reported_count(w, q), sizeof(int) * q.B, hipMemcpyDeviceToHost, st));
         CLB_HIP(hipMemcpyAsync(fl.data() + b0, w.flags.p, sizeof(int) * q.B, hipMemcpyDeviceToHost, st));
+        if (q.d_list_scores)
+            CLB_HIP(hipMemcpyAsync(r.list_scores + (size_t)b0 * L, w.lst_scores.p, sizeof(float) * q.B * L, hipMemcpyDeviceToHost, st));
         return CLB_OK;
     }));
     CLB_HIP(hipStreamSynchronize(st));
@@ -2193,7 +2296,7 @@ int clb_search_shard_phase2_request_slot(clb_searcher* s, int slot, const float*
 
 // ---- the named entry points: each its own refusal (if it has one), a request, one call -----------------------------------
 // (request fields in order: struct_bytes, filters, scope, pad_short, grouping, per_group, group_base, prior, prior_weight,
-// after_scores, after_pids; what a named entry leaves out is zero)
+// after_scores, after_pids, list_pids, list_lens, list_stride, list_scores; what a named entry leaves out is zero)
 constexpr int64_t kReq = sizeof(clb_search_request);
 
 int clb_search_batch_device(clb_searcher* s, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
@@ -2303,6 +2406,30 @@ int clb_search_batch_after(clb_searcher* s, const float* Q, int64_t T, int64_t B
     CLB_TRY(check_after_entry(s, out_pids, out_scores));
     const clb_search_request r = {kReq, filters, scope, /*pad_short=*/1, nullptr, 0, 0, nullptr, 0.f, after_scores, after_pids};
     return clb_search_batch_request(s, Q, T, B, nprobe, k, &r, out_pids, out_scores, n_cand);
+}
+
+// the listed entries' own refusal: without lists they would be the unlisted search, which has entries of its own
+static int check_listed_entry(const int64_t* list_pids, const int64_t* list_lens) {
+    return list_pids || list_lens ? CLB_OK : fail(CLB_EARGUMENT, "list_pids and list_lens are null (without lists: clb_search_batch)");
+}
+
+int clb_search_batch_listed(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                            const int64_t* list_pids, const int64_t* list_lens, int64_t list_stride, float* list_scores,
+                            int64_t* out_pids, float* out_scores, int64_t* n_cand) {
+    CLB_TRY(check_listed_entry(list_pids, list_lens));
+    const clb_search_request r = {kReq, nullptr, CLB_FILTER_CANDIDATES, /*pad_short=*/1, nullptr, 0, 0, nullptr, 0.f, nullptr, nullptr,
+                                  list_pids, list_lens, list_stride, list_scores};
+    return clb_search_batch_request(s, Q, T, B, nprobe, k, &r, out_pids, out_scores, n_cand);
+}
+
+int clb_search_batch_listed_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                        int64_t k, const int64_t* d_list_pids, const int64_t* d_list_lens, int64_t list_stride,
+                                        float* d_list_scores, int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand,
+                                        void* hip_stream) {
+    CLB_TRY(check_listed_entry(d_list_pids, d_list_lens));
+    const clb_search_request r = {kReq, nullptr, CLB_FILTER_CANDIDATES, 0, nullptr, 0, 0, nullptr, 0.f, nullptr, nullptr,
+                                  d_list_pids, d_list_lens, list_stride, d_list_scores};
+    return clb_search_batch_request_device_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_out_pids, d_out_scores, d_n_cand, hip_stream);
 }
 
 int clb_search_shard_phase1(clb_searcher* s, const float* d_Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,

@@ -251,13 +251,14 @@ class DeviceSearch:
         return self.generation != self.s.generation
 
     def replay(self, graph, Qstatic, filters=None, scope="candidates", grouping=None, per_group=None, prior=None,
-               prior_weight=1.0, after=None):
+               prior_weight=1.0, after=None, candidates=None, candidate_scores=None):
         """`graph.replay()` for a graph `capture` returned, made safe against appends: when the searcher has grown since
         the capture, the sizing pass runs again and the search is captured anew before anything is replayed.  Returns the
         graph that was replayed (keep it for the next call).  `after`: the cursor tensors the graph was captured with -- it
-        reads their CONTENTS at every replay."""
+        reads their CONTENTS at every replay; `candidates` / `candidate_scores` likewise."""
         if self.graph_is_stale():
-            graph = self.capture(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after)
+            graph = self.capture(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after, candidates,
+                                 candidate_scores)
         graph.replay()
         return graph
 
@@ -287,15 +288,36 @@ class DeviceSearch:
                                 f"int64[{self.B}]")
         return tuple(after)
 
+    def _check_lists(self, candidates, candidate_scores):
+        """The candidate lists go to the kernels as bare pointers, like the queries: a pair of contiguous tensors on this device,
+        pids int64 [B, L] (L >= 1) and lens int64 [B] -- and, when given, candidate_scores float32 [B, L] -- or refused."""
+        import torch
+        from ._lib import ArgumentError
+
+        def ok(t, dtype, shape):
+            return (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == self.dev and t.is_contiguous()
+                    and tuple(t.shape) == shape)
+        pair = isinstance(candidates, (tuple, list)) and len(candidates) == 2
+        L = int(candidates[0].shape[1]) if pair and isinstance(candidates[0], torch.Tensor) and candidates[0].dim() == 2 else 0
+        if not (pair and L >= 1 and ok(candidates[0], torch.int64, (self.B, L)) and ok(candidates[1], torch.int64, (self.B,))):
+            raise ArgumentError(f"candidates must be a pair of contiguous tensors on {self.dev}: pids int64[{self.B}, L] (L >= 1) "
+                                f"and lens int64[{self.B}]")
+        if candidate_scores is not None and not ok(candidate_scores, torch.float32, (self.B, L)):
+            raise ArgumentError(f"candidate_scores must be a contiguous float32[{self.B}, {L}] tensor on {self.dev}")
+        return candidates[0], candidates[1], L, candidate_scores, False
+
     def _request(self, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0, after=None,
-                 group_base: int = 0):
+                 group_base: int = 0, candidates=None, candidate_scores=None):
         """The clb_search_request of a call of this shard (searcher.search_request), its cursors as device tensors.  A call
         without keywords takes the request made at construction: it has nothing to check and nothing to point at."""
-        if filters is None and grouping is None and per_group is None and prior is None and after is None and scope == "candidates":
+        if (filters is None and grouping is None and per_group is None and prior is None and after is None
+                and scope == "candidates" and candidates is None and candidate_scores is None):
             return self._plain
         return search_request(self.s, self.B, filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
                               prior_weight=prior_weight, after=after, group_base=group_base,
-                              cursor_arrays=lambda cursors, _B: self._check_cursors(cursors))
+                              cursor_arrays=lambda cursors, _B: self._check_cursors(cursors), candidates=candidates,
+                              candidate_scores=candidate_scores,
+                              candidate_arrays=lambda lists, scores, _B: self._check_lists(lists, scores))
 
     def _stream(self) -> int:
         return self._current_stream(self.dev).cuda_stream
@@ -397,7 +419,7 @@ class DeviceSearch:
         return block if g else (self.out_p, self.out_s)
 
     def capture(self, Qstatic, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0,
-                after=None):
+                after=None, candidates=None, candidate_scores=None):
         """A HIP graph of one search over the STATIC query buffer `Qstatic` (B, T, dim): the library enqueues nothing but
         kernels and memsets on the stream it is handed, so the nine launches of a search can be captured once and
         replayed -- write the next queries into `Qstatic` (e.g. let the encoder write there), `graph.replay()`, read
@@ -410,7 +432,9 @@ class DeviceSearch:
         addresses -- keep them open while it is replayed; with `per_group` the results are in `hit_p` / `hit_s`.  `prior` /
         `prior_weight` likewise: the graph holds the prior's device address and the weight.  `after` (a pair of device
         tensors, as in __call__): the graph holds their ADDRESSES, not their values -- to page, copy the last row of `out_s` /
-        `out_p` into them and replay."""
+        `out_p` into them and replay.  `candidates` / `candidate_scores` (device tensors, as in __call__): the graph holds
+        their ADDRESSES too -- to re-rank under a graph, write the next batch's pids and lengths into the same tensors and
+        replay (the sizing pass grows the slot for this stride; a larger stride needs a new capture)."""
         import torch
         self._check_queries(Qstatic)
         self.generation = self.s.generation
@@ -418,15 +442,15 @@ class DeviceSearch:
         side = torch.cuda.Stream(self.dev)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after)
+            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after, candidates, candidate_scores)
         cur.wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after)
+            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after, candidates, candidate_scores)
         return graph
 
     def __call__(self, Qdev, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0,
-                 after=None):
+                 after=None, candidates=None, candidate_scores=None):
         """Qdev: torch float32 tensor holding B queries laid out (B, T, dim) contiguous == Julia (dim, T, B).  One call of
         clb_search_batch_request_device_slot, whatever the keywords.
         `filters`: one PassageFilter or a sequence of B entries (None = unfiltered), `scope` "candidates" / "all"
@@ -440,11 +464,16 @@ class DeviceSearch:
         (Searcher.search_batch); not with `per_group`.
         `after`: a pair of device tensors (scores float32[B], pids int64[B]) on the searcher's device, one cursor per query --
         the next k results past it, always padded (Searcher.search_batch; the cursors stay on the device); a NaN score
-        gives an empty page here.  Not with `grouping`, `per_group` or `prior`."""
+        gives an empty page here.  Not with `grouping`, `per_group` or `prior`.
+        `candidates`: a pair of device tensors (pids int64[B, L], lens int64[B]) on the searcher's device -- row b's first
+        lens[b] entries are query b's candidate set (Searcher.search_batch; the lists stay on the device, nothing is raised
+        about their contents: a length is clamped to 0..L, a pid outside the searcher's range is skipped).  With
+        `candidate_scores` (float32[B, L]) the call also writes every listed passage's exact score at its position, -Inf
+        where the position holds no candidate, and runs as the single exact pass.  Not with `filters`."""
         import torch
         self._check_queries(Qdev)
         req = self._request(filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
-                            prior_weight=prior_weight, after=after)
+                            prior_weight=prior_weight, after=after, candidates=candidates, candidate_scores=candidate_scores)
         out_p, out_s = self.out_p, self.out_s
         if per_group is not None:
             m = int(req.per_group)

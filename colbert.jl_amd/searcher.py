@@ -201,16 +201,84 @@ def _after_arrays(after, B: int):
     return s, p
 
 
+def _candidate_keywords(candidates, filters, want_scores=False):
+    """The `candidates=` of a search call against the keywords it is not offered with, and the score output against it."""
+    from ._lib import ArgumentError, Unsupported
+    if candidates is None:
+        if want_scores:
+            raise ArgumentError("candidate scores need candidates=: they are the scores of the listed passages")
+        return
+    if filters is not None and (not isinstance(filters, (list, tuple)) or any(f is not None for f in filters)):
+        raise Unsupported("candidates= together with filter(s)= is not supported: a list is the candidate set")
+
+
+def _int64_list(a, what: str) -> np.ndarray:
+    """An array of integers as int64, or ArgumentError: a float or a value past int64 is no pid and no length."""
+    from ._lib import ArgumentError
+    try:
+        raw = np.asarray(a)
+    except (TypeError, ValueError) as e:
+        raise ArgumentError(f"{what} must be integers: {e}") from None
+    if raw.size == 0 and raw.dtype.kind == "f":       # np.asarray([]) is float64
+        raw = raw.astype(np.int64)
+    if raw.dtype.kind not in "iu" or (raw.size and raw.dtype.kind == "u" and int(raw.max()) > np.iinfo(np.int64).max):
+        raise ArgumentError(f"{what} must be integers that fit int64, got dtype {raw.dtype}")
+    return raw.astype(np.int64, copy=False)
+
+
+def _candidate_arrays(candidates, want_scores, B: int):
+    """`candidates=` of Searcher.search_batch as the host arrays the C ABI takes: (pids, lens, L, scores or None, ragged).
+    A sequence of B integer arrays (ragged) is padded with 0 into one block whose stride is the longest list; a pair
+    `(pids (L, B), lens [B])` is taken as it is.  pids / scores are (L, B) column-major: row b of the C arrays is [:, b]."""
+    from ._lib import ArgumentError
+    pair = isinstance(candidates, tuple) and len(candidates) == 2 and np.ndim(candidates[0]) == 2
+    if pair:
+        block = _int64_list(candidates[0], "the candidate pids")
+        lens = _int64_list(candidates[1], "the candidate list lengths").reshape(-1)
+        L = block.shape[0]
+        if L < 1 or block.shape[1] != B or lens.size != B:
+            raise ArgumentError(f"candidates=(pids, lens) holds one list per query: pids {block.shape} (L >= 1, B) and {lens.size} "
+                                f"lengths for {B} queries")
+        if lens.size and (int(lens.min()) < 0 or int(lens.max()) > L):
+            raise ArgumentError(f"the candidate list lengths must lie in 0..{L}, got {int(lens.min())}..{int(lens.max())}")
+        pids = np.asfortranarray(block)
+    else:
+        if isinstance(candidates, (str, bytes)) or not hasattr(candidates, "__len__"):
+            raise ArgumentError("candidates must be a sequence of integer arrays, one per query, or a pair (pids (L, B), lens [B])")
+        if len(candidates) != B:
+            raise ArgumentError(f"candidates holds one list per query: {len(candidates)} lists for {B} queries")
+        lists = [_int64_list(c, f"the candidate list of query {b}").reshape(-1) for b, c in enumerate(candidates)]
+        lens = np.array([c.size for c in lists], dtype=np.int64)
+        L = max(1, int(lens.max()) if B else 1)
+        pids = np.zeros((L, B), dtype=np.int64, order="F")
+        for b, c in enumerate(lists):
+            pids[:c.size, b] = c
+    scores = np.full((L, B), -np.inf, dtype=np.float32, order="F") if want_scores else None
+    return pids, np.ascontiguousarray(lens), L, scores, not pair
+
+
 def search_request(searcher, B: int, *, filters=None, scope="candidates", grouping=None, per_group=None, prior=None,
-                   prior_weight=1.0, after=None, pad_short=False, group_base: int = 0, cursor_arrays=_after_arrays) -> SearchRequest:
+                   prior_weight=1.0, after=None, pad_short=False, group_base: int = 0, cursor_arrays=_after_arrays,
+                   candidates=None, candidate_scores=None, candidate_arrays=_candidate_arrays) -> SearchRequest:
     """The keywords of a search call of `searcher` over B queries, checked on the host, as the clb_search_request every
     search entry point takes (include/colbert_hip.h).  Raises what the helpers above raise, in their order: scope, `after`
     against the keywords it is not offered with, the cursors, the prior and its weight (never with `per_group`), `per_group`,
     the filters, the grouping.  With filters or cursors the host route always pads.  `cursor_arrays(after, B)` gives the two cursor
     arrays: host arrays here, DeviceSearch passes its own check of device tensors.  The request holds a reference to every
-    array it points at (`_keep`): it is valid as long as it lives."""
+    array it points at (`_keep`): it is valid as long as it lives.
+    `candidates` (Searcher.search_batch) with `candidate_scores` (true: the call is to leave the list scores): never with
+    filters (Unsupported); `candidate_arrays(candidates, candidate_scores, B)` gives (pids, lens, L, scores or None, ragged) --
+    host arrays here, with the int64 conversion and the padding of ragged lists, device tensors from DeviceSearch -- which
+    the request keeps as `lists`; with lists the host route always pads."""
+    _scope_code(scope)
+    _candidate_keywords(candidates, filters, candidate_scores is not None and candidate_scores is not False)
     r = SearchRequest(struct_bytes=C.sizeof(SearchRequest), scope=_scope_code(scope), group_base=int(group_base),
-                      pad_short=1 if (pad_short or filters is not None or after is not None) else 0)
+                      pad_short=1 if (pad_short or filters is not None or after is not None or candidates is not None) else 0)
+    r.lists = None
+    if candidates is not None:
+        r.lists = tuple(candidate_arrays(candidates, candidate_scores, B))
+        ptr = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+        r.list_pids, r.list_lens, r.list_stride, r.list_scores = ptr(r.lists[0]), ptr(r.lists[1]), int(r.lists[2]), ptr(r.lists[3])
     cursors = ()
     if after is not None:
         _after_keywords(after, grouping, per_group, prior)
@@ -648,7 +716,8 @@ class Searcher:
 
     # -- search -----------------------------------------------------------------------------------
     def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates", grouping=None,
-                          per_group=None, prior=None, prior_weight=1.0, after=None):
+                          per_group=None, prior=None, prior_weight=1.0, after=None, candidates=None,
+                          return_candidate_scores=False):
         """search() after encode_queries (searching.jl:102-127).  Q: (dim, T) Float32.
         Returns (pids Int64[k] 1-based, scores Float32[k]).
         `filter` (a PassageFilter of this searcher): search among its passages only -- scope "candidates": the query's
@@ -663,17 +732,26 @@ class Searcher:
         `prior` (a PassagePrior of this searcher) with `prior_weight`: rank by score + prior_weight * value and return that
         sum as the score (Searcher.search_batch); short results as without a prior.
         `after` (a pair (score, pid), e.g. `next_cursor` of the previous page): the next k results past that cursor, always
-        padded (Searcher.search_batch); not with `grouping`, `per_group` or `prior`."""
+        padded (Searcher.search_batch); not with `grouping`, `per_group` or `prior`.
+        `candidates` (one array of pids): re-rank exactly these passages (Searcher.search_batch), always padded; with
+        `return_candidate_scores=True` the call returns (pids, scores, candidate_scores), the third the score of every listed
+        pid at its position.  Not with `filter`."""
         q = colmajor(Q, np.float32)
         if q.ndim != 2 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T)")
         _scope_code(scope)
         _after_keywords(after, grouping, per_group, prior)
+        _candidate_keywords(candidates, None if filter is None else [filter], return_candidate_scores)
+        if candidates is not None:
+            out = self.search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe, scope=scope, grouping=grouping,
+                                    per_group=per_group, prior=prior, prior_weight=prior_weight,
+                                    after=None if after is None else self._one_cursor(after), candidates=[candidates],
+                                    return_candidate_scores=return_candidate_scores)
+            self.last_num_candidates = int(out[2][0])
+            one = (np.asfortranarray(out[0][..., 0]), np.asfortranarray(out[1][..., 0]))
+            return one + (out[3][0],) if return_candidate_scores else one
         if after is not None:
-            from ._lib import ArgumentError
-            if not isinstance(after, (tuple, list)) or len(after) != 2:
-                raise ArgumentError("after must be a pair (score, pid)")
-            after = ([after[0]], [after[1]])
+            after = self._one_cursor(after)
         if filter is not None or grouping is not None or per_group is not None or prior is not None or after is not None:
             p, s, n = self.search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe,
                                         filters=None if filter is None else [filter], scope=scope, grouping=grouping,
@@ -687,8 +765,17 @@ class Searcher:
         self.last_num_candidates = ncand.value
         return pids, scores
 
+    @staticmethod
+    def _one_cursor(after):
+        """The `after=(score, pid)` of a one-query call as the pair of one-element arrays search_batch takes."""
+        from ._lib import ArgumentError
+        if not isinstance(after, (tuple, list)) or len(after) != 2:
+            raise ArgumentError("after must be a pair (score, pid)")
+        return ([after[0]], [after[1]])
+
     def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
-                     scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0, after=None):
+                     scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0, after=None,
+                     candidates=None, return_candidate_scores=False):
         """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B]); one call of clb_search_batch_request.
         `filters`: one PassageFilter for every query, or a sequence of B entries (None = that query is unfiltered); with
         filters the results are always padded (pid 0 / -Inf past n_candidates[b], the count AFTER the filter) and `scope`
@@ -709,19 +796,34 @@ class Searcher:
         page walks the whole ranking in pieces of k, bit for bit.  A score of +Inf means no cursor for that query, -Inf an
         empty page, NaN is ArgumentError.  The result is always padded (pid 0 / -Inf; a page of padding alone is the end) and
         n_candidates is that of the call without cursors, the same on every page.  Composes with `filters` in both scopes;
-        not with `grouping`, `per_group` or `prior` (Unsupported)."""
+        not with `grouping`, `per_group` or `prior` (Unsupported).
+        `candidates`: re-rank given passages -- the candidate set of query b is the list the caller names, not the query's
+        probes (`nprobe` is checked and otherwise unused).  A sequence of B integer arrays (ragged; any order, duplicates
+        allowed; pids as search returns them), or a pair `(pids (L, B), lens [B])` whose column b holds query b's list in its
+        first lens[b] rows.  The candidates are the distinct listed passages that hold embeddings; the result is bit for bit
+        that of `filters=make_filter(pids=list), scope="all"` and is always padded.  A pid outside the searcher's range is
+        BoundsError naming the query and the position.  Composes with `grouping`, `per_group`, `prior` and `after` as a
+        scope="all" filter does; not with `filters` (Unsupported).
+        `return_candidate_scores=True` (needs `candidates`): a fourth result, the exact score of every listed passage at its
+        input position (with a prior: E), -Inf where the position holds no candidate -- a list of B float32 arrays of the
+        input lengths for ragged lists, an (L, B) array for the pair form.  They are passage scores: a grouping or cursors
+        do not change them.  Such a call scores every candidate exactly: it runs as the single exact pass whatever the mode."""
         q = colmajor(Q, np.float32)
         if q.ndim != 3 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T, B)")
         B = q.shape[2]
         req = search_request(self, B, filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
-                             prior_weight=prior_weight, after=after, pad_short=pad_short)
+                             prior_weight=prior_weight, after=after, pad_short=pad_short, candidates=candidates,
+                             candidate_scores=bool(return_candidate_scores))
         shape = (k, B) if per_group is None else (int(req.per_group), k, B)
         pids = np.zeros(shape, dtype=np.int64, order="F"); scores = np.zeros(shape, dtype=np.float32, order="F")
         ncand = np.zeros(B, dtype=np.int64)
         check(request_entry("clb_search_batch_request")(self._h, fptr(q), q.shape[1], B, nprobe or self.config.nprobe, k, req,
                                                         fptr(pids), fptr(scores), fptr(ncand)))
-        return pids, scores, ncand
+        if not return_candidate_scores:
+            return pids, scores, ncand
+        _, lens, _, cs, ragged = req.lists
+        return pids, scores, ncand, ([cs[:int(n), b].copy() for b, n in enumerate(lens)] if ragged else cs)
 
     def retrieve(self, Q, nprobe: Optional[int] = None):
         """retrieve (src/search/ranking.jl:23-44): ascending candidate pids."""
@@ -744,17 +846,19 @@ class Searcher:
                 "eps": eps.value, "n_rescore": nr.value}
 
     def search(self, query: str, k: int, *, filter=None, scope="candidates", grouping=None, per_group=None, prior=None,
-               prior_weight=1.0, after=None):
+               prior_weight=1.0, after=None, candidates=None, return_candidate_scores=False):
         """search(searcher, query::String, k) (searching.jl:93-128); `filter` / `scope` / `grouping` / `per_group` / `prior` /
-        `prior_weight` / `after` as in search_embeddings."""
+        `prior_weight` / `after` / `candidates` / `return_candidate_scores` as in search_embeddings."""
         _scope_code(scope)
         _after_keywords(after, grouping, per_group, prior)
+        _candidate_keywords(candidates, None if filter is None else [filter], return_candidate_scores)
         if self.encoder is None:
             raise ColBERTError("no query encoder attached: pass encoder=... or use search_embeddings(Q, k)")
         Q = self.encoder.encode_queries([query])
         assert Q.shape[2] == 1 and Q.shape[1] == self.config.query_maxlen, Q.shape
         return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope, grouping=grouping, per_group=per_group,
-                                      prior=prior, prior_weight=prior_weight, after=after)
+                                      prior=prior, prior_weight=prior_weight, after=after, candidates=candidates,
+                                      return_candidate_scores=return_candidate_scores)
 
     def text_search(self, k: int, nprobe: Optional[int] = None, graph: bool = True) -> "TextSearch":
         """A session for repeated `search(searcher, query::String, k)` calls with everything after the tokenizer on the
@@ -974,11 +1078,13 @@ class TextSearch:
 
 
 def search(searcher: Searcher, query, k: int, *, filter=None, scope="candidates", grouping=None, per_group=None, prior=None,
-           prior_weight=1.0, after=None):
+           prior_weight=1.0, after=None, candidates=None, return_candidate_scores=False):
     """The reference's exported `search` (src/ColBERT.jl:40).  `query` may be a string (needs an
     encoder) or a (dim, T) Float32 matrix of query embeddings.  `filter` / `scope` / `grouping` / `per_group` / `prior` /
-    `prior_weight` / `after`: Searcher.search_embeddings."""
+    `prior_weight` / `after` / `candidates` / `return_candidate_scores`: Searcher.search_embeddings."""
     more = {} if after is None else {"after": after}      # (a ShardedSearcher answers a cursor with Unsupported itself)
+    if candidates is not None or return_candidate_scores:  # (... and candidate lists likewise)
+        more.update(candidates=candidates, return_candidate_scores=return_candidate_scores)
     if prior is None and prior_weight == 1.0:      # (a call without a prior hands over the keywords it always has)
         if isinstance(query, str):
             return searcher.search(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group, **more)

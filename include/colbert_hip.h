@@ -595,8 +595,8 @@ int clb_debug_prior_tau_device(const float* d_all_top, const int64_t* d_all_gid,
  * the searcher is looked at.  Zero-initialise the struct, set struct_bytes, then the fields of the features in use:
  * everything left zero / NULL means "none".
  * Refused combinations, all CLB_EUNSUPPORTED: a prior with per_group > 1 (the hits are built from approximate MaxSim scores),
- * cursors with a grouping, cursors with a prior; on the phase routes also per_group > 1 and cursors, and phase 2 takes no
- * filters (it continues on the candidates phase 1 left on the slot).
+ * cursors with a grouping, cursors with a prior, candidate lists with filters; on the phase routes also per_group > 1,
+ * cursors and candidate lists, and phase 2 takes no filters (it continues on the candidates phase 1 left on the slot).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct clb_search_request {
     int64_t struct_bytes;                 /* sizeof this struct: anything else is CLB_EARGUMENT */
@@ -610,6 +610,10 @@ typedef struct clb_search_request {
     float prior_weight;
     const float* after_scores;            /* cursors, [B] each, both or neither: HOST arrays on the host route (a NaN score */
     const int64_t* after_pids;            /* is CLB_EARGUMENT), DEVICE arrays on the device route */
+    const int64_t* list_pids;             /* candidate lists ("Re-rank given passages" below), both or neither: [B][list_stride] */
+    const int64_t* list_lens;             /* pids and [B] lengths; HOST arrays on the host route, DEVICE arrays on the device route */
+    int64_t list_stride;                  /* L >= 1: entries per row of list_pids / list_scores */
+    float* list_scores;                   /* or NULL.  The one OUTPUT a request carries: [B][list_stride], where the lists live */
 } clb_search_request;
 /* The host route: clb_search_batch and every clb_search_batch_* entry without _device.  With per_group > 1 the outputs
  * hold B * k * per_group entries. */
@@ -631,6 +635,45 @@ int clb_search_shard_phase2_request_slot(clb_searcher* s, int slot, const float*
                                          const int64_t* d_all_gid, const float* d_all_mabs, int64_t n_shards, int64_t* d_out_pids,
                                          float* d_out_scores, int64_t* d_out_gids, int64_t* d_n_cand, int64_t* d_edge_gids,
                                          void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Re-rank given passages: the candidate set of every query is a pid list of the caller's -- first-stage results of another
+ * retriever, labelled pairs, teacher scores -- with no handle to create or destroy.  A call carries lists for the whole
+ * batch or for none.  Query b's list is the first list_lens[b] entries (0 <= list_lens[b] <= L = list_stride) of row b of
+ * list_pids; entries are pids as search returns them (1-based, pid_offset added), in any order, duplicates allowed.
+ *   candidates: the DISTINCT listed passages that lie in the handle's range and hold at least one embedding (a passage
+ *            without embeddings -- empty at create, emptied by remove / update -- never is one, as under CLB_FILTER_ALL).
+ *            nprobe is validated and otherwise unused; a query of length 0 has no candidates.
+ *   result:  bit for bit that of clb_search_batch_filtered with a CLB_FILTER_ALL filter made from the same pids -- pids, fp32
+ *            scores, n_cand, pid 0 / -Inf padding.  Always padded: a short list is no error.
+ *   list_scores (optional, [B][L] fp32): the exact fp32 score of the passage at every INPUT position -- MaxSim, or with a prior
+ *            E = fl32(e + fl32(weight * value)) -- the bits the ranked output reports for that pid; every occurrence of a
+ *            duplicate receives it.  -Inf where the position holds no candidate: positions >= list_lens[b], pids outside the
+ *            handle's range, passages without embeddings.  They are PASSAGE scores: a grouping or cursors do not change them,
+ *            nor do the handle's mode, gather form or score-row form.  A call that asks for them needs the exact score of every
+ *            candidate and runs as the single exact pass whatever clb_searcher_set_mode says (the two-pass mode is identical
+ *            to it by construction; the handle's mode is left as it was).
+ * Lists compose with everything that acts after candidate making -- grouping, per_group, prior, cursors (through
+ * clb_search_batch_request*; what those refuse among themselves stays refused) -- and are refused with filters (any non-NULL
+ * entry: CLB_EUNSUPPORTED, a list IS the candidate set) and on the phase routes of a shard group (CLB_EUNSUPPORTED).
+ * Host route: every check runs before any device work.  One of list_pids / list_lens NULL with the other set, list_stride < 1
+ * or a length outside 0..L is CLB_EARGUMENT; a pid outside pid_offset+1 .. pid_offset+n_docs is CLB_EBOUNDS naming the query and
+ * the position.
+ * Device route: stream-ordered, no host synchronisation, capturable, and nothing can be raised about the arrays' CONTENTS: a
+ * length is clamped to 0..L and a pid outside the range is skipped (another shard's pid, as clb_filter_create_pids_global skips
+ * it).  A captured graph holds the ADDRESSES of the three arrays: to re-rank under a graph, write the next batch's pids and
+ * lengths into the same buffers and replay.  The slot's candidate capacity is sized from min(list_stride, n_docs), a host
+ * value: a slot's first listed call, or one with a larger stride, may grow it (outside a capture); later calls allocate
+ * nothing.  Batches above 64 queries run as sub-batches, each reading its own rows.
+ * list_pids == NULL and list_lens == NULL here is CLB_EARGUMENT (without lists: clb_search_batch / ..._device_slot).
+ * ---------------------------------------------------------------------------------------------- */
+int clb_search_batch_listed(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                            const int64_t* list_pids, const int64_t* list_lens, int64_t list_stride,
+                            float* list_scores /* may be NULL */, int64_t* out_pids, float* out_scores, int64_t* n_cand);
+int clb_search_batch_listed_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                        int64_t k, const int64_t* d_list_pids, const int64_t* d_list_lens, int64_t list_stride,
+                                        float* d_list_scores /* may be NULL */, int64_t* d_out_pids, float* d_out_scores,
+                                        int64_t* d_n_cand, void* hip_stream);
 
 /* retrieve()  (src/search/ranking.jl:23-44) on its own -- test hook.  out_pids needs n_docs entries. */
 int clb_retrieve(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe, int64_t* out_pids,
