@@ -72,7 +72,7 @@ class SearchRequest(C.Structure):
     """clb_search_request (include/colbert_hip.h), field for field: what a search call carries besides queries, sizes and outputs."""
     _fields_ = [("struct_bytes", C.c_int64), ("filters", C.POINTER(C.c_void_p)), ("scope", C.c_int), ("pad_short", C.c_int),
                 ("grouping", C.c_void_p), ("per_group", C.c_int64), ("group_base", C.c_int64), ("prior", C.c_void_p),
-                ("prior_weight", C.c_float), ("after_scores", C.c_void_p), ("after_pids", C.c_void_p),
+                ("prior_weight", C.c_float), ("list_prior", C.c_void_p), ("after_scores", C.c_void_p), ("after_pids", C.c_void_p),
                 ("list_pids", C.c_void_p), ("list_lens", C.c_void_p), ("list_stride", C.c_int64), ("list_scores", C.c_void_p)]
 
 
@@ -216,6 +216,12 @@ def lib() -> C.CDLL:
             l.clb_search_batch_listed.argtypes = [vp, vp, i64_, i64_, i64_, i64_, vp, vp, i64_, vp, vp, vp, vp]
             l.clb_search_batch_listed_device_slot.restype = ci
             l.clb_search_batch_listed_device_slot.argtypes = [vp, ci, vp, i64_, i64_, i64_, i64_, vp, vp, i64_, vp, vp, vp, vp, vp]
+        if hasattr(l, "clb_search_batch_listed_prior"):         # (likewise)
+            l.clb_search_batch_listed_prior.restype = ci
+            l.clb_search_batch_listed_prior.argtypes = [vp, vp, i64_, i64_, i64_, i64_, vp, vp, i64_, vp, C.c_float, vp, vp, vp, vp]
+            l.clb_search_batch_listed_prior_device_slot.restype = ci
+            l.clb_search_batch_listed_prior_device_slot.argtypes = [vp, ci, vp, i64_, i64_, i64_, i64_, vp, vp, i64_, vp, C.c_float,
+                                                                    vp, vp, vp, vp, vp]
         l.clb_merge_topk_grouped_device.restype = ci
         l.clb_merge_topk_grouped_device.argtypes = [ci, vp, vp, vp, i64_, i64_, i64_, vp, vp, vp, vp, vp, vp]
         l.clb_packed_grouped_bytes.restype = i64_

@@ -8,6 +8,9 @@
 // bitmap_emit_kernel with the handle's live bitmap as every query's filter word) makes the ascending, de-duplicated
 // candidate list without the passages that hold no embeddings -- exactly the list a CLB_FILTER_ALL filter of the same pids
 // gives.  list_scores_kernel, behind the exact scores, carries every candidate's score back to the positions it was listed at.
+// With list priors (one fp32 value per list position, the additive term of prior_kernels.hpp per query AND passage) a third,
+// list_slot_kernel behind the compaction, leaves the lowest list position of every candidate slot: the boost reads the value
+// there, so of a duplicate's values the first counts, on every route and in every launch order.
 // Nothing here can raise: a length is clamped to 0..L and a pid outside the handle's range is skipped (another shard's pid,
 // as filter_mark_kernel<true> skips it); the host route checks both before any device work.
 #pragma once
@@ -38,6 +41,20 @@ static __global__ __launch_bounds__(256) void list_mark_kernel(const int64_t* __
     atomicOr(&bitmap[(size_t)b * W + (p >> 5)], 1u << (p & 31));
 }
 
+// the slot of local passage p among a query's n ascending candidates c, or -1
+__device__ __forceinline__ int list_slot(const uint32_t* __restrict__ c, int n, int p) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (c[mid] < (uint32_t)p) lo = mid + 1; else hi = mid;
+    }
+    return lo < n && c[lo] == (uint32_t)p ? lo : -1;
+}
+// the number of candidate slots of query b as the kernels read it
+__device__ __forceinline__ int list_ncand(const int* __restrict__ ncand, int b, size_t cand_cap) {
+    return (int)min((size_t)max(ncand[b], 0), cand_cap);
+}
+
 // L2: one thread per list position, behind the exact scores of ALL candidates (with a prior: the boosted ones).  The
 // candidates of a query are an ascending list of local pids (cand, ncand entries): a binary search finds the listed
 // passage's slot, whose score goes to out[b][i] -- every occurrence of a duplicate finds the same slot.  -Inf for a position
@@ -54,17 +71,38 @@ static __global__ __launch_bounds__(256) void list_scores_kernel(const int64_t* 
     if (i < list_len(lens, b, L)) {
         const int p = list_local(pids[(size_t)b * L + i], pid_offset, n_docs);
         if (p >= 0) {
-            const uint32_t* c = cand + (size_t)b * cand_cap;
-            int lo = 0, hi = (int)min((size_t)max(ncand[b], 0), cand_cap);
-            while (lo < hi) {
-                const int mid = lo + ((hi - lo) >> 1);
-                if (c[mid] < (uint32_t)p) lo = mid + 1; else hi = mid;
-            }
-            const int n = (int)min((size_t)max(ncand[b], 0), cand_cap);
-            if (lo < n && c[lo] == (uint32_t)p) v = scores[(size_t)b * cand_cap + lo];
+            const int slot = list_slot(cand + (size_t)b * cand_cap, list_ncand(ncand, b, cand_cap), p);
+            if (slot >= 0) v = scores[(size_t)b * cand_cap + slot];
         }
     }
     out[(size_t)b * L + i] = v;
+}
+
+// the fill in front of L3: slot_pos[i] = INT_MAX ("no position yet") for the n words the launch's queries can reach.  A
+// kernel, like fill_pad_kernel, not a memset: it is ordered against its neighbours like every other launch of the search,
+// on a stream and as a node of a captured graph.  grid = ceil(n / 256), block = 256.
+static __global__ __launch_bounds__(256) void list_slot_fill_kernel(int* __restrict__ slot_pos, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) slot_pos[i] = 0x7fffffff;
+}
+
+// L3 (list priors): one thread per list position, behind the compaction.  slot_pos[b][slot] (row stride pos_stride, INT_MAX
+// on entry) becomes the LOWEST position i < len that lists the slot's passage: the position whose value is the passage's
+// term.  Every candidate came from the list, so every slot receives a position; a position past the length, a pid outside
+// the handle's range and a passage that is no candidate touch nothing -- their values are never read.  A slot index at or
+// past pos_stride cannot arise (a listed query has at most min(L, n_docs) candidates) and is skipped.
+// grid = (ceil(L / 256), B), block = 256.
+static __global__ __launch_bounds__(256) void list_slot_kernel(const int64_t* __restrict__ pids, const int64_t* __restrict__ lens,
+                                                               int L, int64_t pid_offset, int n_docs,
+                                                               const uint32_t* __restrict__ cand, const int* __restrict__ ncand,
+                                                               size_t cand_cap, int* __restrict__ slot_pos, size_t pos_stride) {
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= list_len(lens, b, L)) return;
+    const int p = list_local(pids[(size_t)b * L + i], pid_offset, n_docs);
+    if (p < 0) return;
+    const int slot = list_slot(cand + (size_t)b * cand_cap, list_ncand(ncand, b, cand_cap), p);
+    if (slot < 0 || (size_t)slot >= pos_stride) return;
+    atomicMin(&slot_pos[(size_t)b * pos_stride + slot], i);
 }
 
 }  // namespace clb

@@ -18,15 +18,38 @@
 
 namespace clb {
 
-// P1.  scores[b][slot] = fl(scores[b][slot] + fl(weight * prior[cand[b][slot]])) for the query's nlist[b] listed slots or, with
-// list == nullptr, its ncand[b] candidate slots 0, 1, ...  mabs (optional, [B]): max |new score| over those slots (NaN
-// ignored), the M of prior_tau_kernel.  grid = B, block = 1024.
+// Where P1 reads the value of a candidate slot.  A resident prior: values[cand[slot]], one value per local passage.  List
+// priors (kListed; list_kernels.hpp): the values travel beside the caller's candidate lists, row b of stride L for query b,
+// and slot_pos[b][slot] (stride pos_stride) is the lowest list position that names the slot's passage (list_slot_kernel).
+// Such values come straight from the caller on the device route, where nothing can be raised: a value that is not finite,
+// or whose product with the weight is not finite, counts as 0 -- what the host route would have refused.
+struct PriorTerm {
+    const float* values;
+    const int* slot_pos;
+    int L;
+    size_t pos_stride;
+};
+template <bool kListed>
+__device__ __forceinline__ float prior_value(const PriorTerm& t, int b, uint32_t passage, int slot, float weight) {
+    if (!kListed) return t.values[passage];
+    if ((size_t)slot >= t.pos_stride) return 0.f;      // (a listed query has no more candidates than that: never taken)
+    const int pos = t.slot_pos[(size_t)b * t.pos_stride + slot];
+    if (pos < 0 || pos >= t.L) return 0.f;             // (every candidate came from the list: never taken)
+    const float v = t.values[(size_t)b * t.L + pos];
+    const bool fin = fabsf(v) < __builtin_inff() && fabsf(__fmul_rn(weight, v)) < __builtin_inff();
+    return fin ? v : 0.f;
+}
+
+// P1.  scores[b][slot] = fl(scores[b][slot] + fl(weight * value(slot))) for the query's nlist[b] listed slots or, with
+// list == nullptr, its ncand[b] candidate slots 0, 1, ...; value(slot) by PriorTerm.  mabs (optional, [B]): max |new score|
+// over those slots (NaN ignored), the M of prior_tau_kernel.  grid = B, block = 1024.
+template <bool kListed>
 static __global__ __launch_bounds__(1024) void prior_boost_kernel(float* __restrict__ scores,
                                                                  const uint32_t* __restrict__ cand,
                                                                  const int* __restrict__ ncand,
                                                                  const int* __restrict__ list /*optional*/,
                                                                  const int* __restrict__ nlist,
-                                                                 const float* __restrict__ prior, float weight,
+                                                                 PriorTerm term, float weight,
                                                                  size_t cand_cap, float* __restrict__ mabs /*optional*/) {
     __shared__ unsigned int s_max;
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -38,7 +61,7 @@ static __global__ __launch_bounds__(1024) void prior_boost_kernel(float* __restr
     float m = 0.f;
     for (int i = tid; i < n; i += 1024) {
         const int slot = lst ? lst[i] : i;
-        const float pi = __fmul_rn(weight, prior[cnd[slot]]);
+        const float pi = __fmul_rn(weight, prior_value<kListed>(term, b, cnd[slot], slot, weight));
         const float v = __fadd_rn(sc[slot], pi);
         sc[slot] = v;
         m = fmaxf(m, fabsf(v));

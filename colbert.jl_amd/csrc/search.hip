@@ -136,6 +136,11 @@ struct Workspace {
     // candidate lists (list_kernels.hpp) on the host route, sized by the first listed call: the sub-batch's rows of the pid
     // block, its lengths and, when the call asks for them, its list scores
     DevBuf lst_pids, lst_lens, lst_scores;
+    // ... with list priors (one value per list position), sized once a call has passed them: on the host route the sub-batch's
+    // rows of the value block (lst_prior), and on every route the lowest list position of every candidate slot (slot_pos,
+    // list_slot_kernel), 4 bytes per query and candidate of the slot's capacity
+    bool list_prior = false;
+    DevBuf lst_prior, slot_pos;
     DevBuf g_cells, g_keys, g_keys2, g_vals, g_vals2, g_scratch, g_sort_tmp;   // general-shape path (generic_kernels.hpp)
 };
 
@@ -219,6 +224,10 @@ struct Batch {
     const int64_t* d_list_pids = nullptr; const int64_t* d_list_lens = nullptr;
     int64_t list_stride = 0;
     float* d_list_scores = nullptr;
+    // ... with list priors: the sub-batch's rows of the value block ([B][list_stride]) on the device, beside d_list_pids; the
+    // additive term of candidate p is prior_weight * the value at p's lowest list position (nullptr: none, and the sub-batch
+    // launches exactly what it launches without them).  Never together with `prior`: a call has one additive term
+    const float* d_list_prior = nullptr;
     bool stats_keep = false;    // the 2nd, 3rd ... sub-batch of one call: the work counters accumulate over the call
     int phase = 0, n_shards = 0;    // two-phase sharded search (run_search)
     float* d_local_top = nullptr; const float* d_all_top = nullptr;
@@ -306,10 +315,10 @@ int next_pow2(int x) {
 // filt_count: the largest filter population of a CLB_FILTER_ALL call (0 otherwise) -- such a query's candidates are its
 // filter's passages, however few the IVF lists would give
 int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_t nprobe, int64_t k, size_t filt_count,
-                           bool grouped, int64_t per_group, bool prior, bool after) {
+                           bool grouped, int64_t per_group, bool prior, bool after, bool list_prior) {
     const int64_t t_tuned = T <= 128 ? T : 0;       // queries of up to 128 tokens take the tuned (or batched general) kernels
     if (B <= w.Bcap && T <= w.Tcap && t_tuned <= w.Ttuned && nprobe <= w.npcap && k <= w.kcap && filt_count <= w.filt_cap &&
-        (!grouped || w.grouped) && per_group <= w.mcap && (!prior || w.prior) && (!after || w.after))
+        (!grouped || w.grouped) && per_group <= w.mcap && (!prior || w.prior) && (!after || w.after) && (!list_prior || w.list_prior))
         return CLB_OK;
     CLB_HIP(hipDeviceSynchronize());       // buffers may be in use on any of the caller's streams
     B = std::max(B, w.Bcap); T = std::max(T, w.Tcap);
@@ -394,9 +403,13 @@ int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, 
             CLB_TRY(w.hit_n.ensure(sizeof(int) * B));
         }
     }
-    if (prior || w.prior) {         // ... and one that has searched with a prior, this
+    if (prior || w.prior || list_prior || w.list_prior) {   // ... and one that has searched with a prior or list priors, this
         CLB_TRY(w.prior_tau.ensure(sizeof(float) * 2 * B));
         w.prior = true;
+    }
+    if (list_prior || w.list_prior) {   // ... and one that has searched with list priors, this as well
+        CLB_TRY(w.slot_pos.ensure(sizeof(int) * B * w.cand_cap));
+        w.list_prior = true;
     }
     if (after || w.after) {         // ... and one that has searched after a cursor, these
         CLB_TRY(w.after_list.ensure(sizeof(int) * B * w.cand_cap));
@@ -413,8 +426,8 @@ int ensure_workspace_sized(clb_searcher* s, Workspace& w, int64_t B, int64_t T, 
 }
 
 int ensure_workspace(clb_searcher* s, Workspace& w, int64_t B, int64_t T, int64_t nprobe, int64_t k, size_t filt_count = 0,
-                     bool grouped = false, int64_t per_group = 0, bool prior = false, bool after = false) {
-    const int rc = ensure_workspace_sized(s, w, B, T, nprobe, k, filt_count, grouped, per_group, prior, after);
+                     bool grouped = false, int64_t per_group = 0, bool prior = false, bool after = false, bool list_prior = false) {
+    const int rc = ensure_workspace_sized(s, w, B, T, nprobe, k, filt_count, grouped, per_group, prior, after, list_prior);
     if (rc) {
         w.Bcap = 0;       // some buffers may have grown and others not: the next call sizes all of them again
         // a candidate set the size of a filter that does not fit is this call's own request, not a fault of the device
@@ -631,6 +644,10 @@ int mark_and_compact_impl(clb_searcher* s, Workspace& w, hipStream_t st, const B
     return CLB_OK;
 }
 
+// entries per query of slot_pos in a call with list priors: the most candidates a listed query can have (filt_now =
+// min(list_stride, n_docs) <= cand_cap), so that the fill in front of list_slot_kernel touches no more than the lists can reach
+inline size_t slot_pos_stride(const Batch& q) { return (std::max<size_t>(q.filt_now, 1) + 3) & ~(size_t)3; }
+
 // S3l: the candidates of the B queries from b0 on are the caller's lists (list_kernels.hpp) -- the listed passages go into
 // the candidate bitmap, and the compaction reads it through the handle's live bitmap as every query's filter word
 // (CLB_FILTER_CANDIDATES: marked AND filter), which drops the passages without embeddings as CLB_FILTER_ALL drops them
@@ -653,6 +670,18 @@ int list_and_compact(clb_searcher* s, Workspace& w, hipStream_t st, const Batch&
         hipLaunchKernelGGL(bitmap_emit_kernel<true>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st, bitmap, blocksum,
                            w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap, s->doc_off.as<uint32_t>(),
                            w.cand_hdr.as<uint2>() + (size_t)b0 * w.cand_cap, w.W, w.cand_cap, w.ncand.as<int>() + b0, fa);
+    }
+    if (q.d_list_prior) {
+        // with list priors: the lowest list position of every candidate slot (list_slot_kernel), which the boosts read the
+        // values through.  A listed query has at most filt_now candidates: only that many slots of a row are filled and read
+        Timed t(s, timed ? KID_COMPACT : -1, st);
+        const size_t ps = slot_pos_stride(q);
+        int* slot_pos = w.slot_pos.as<int>() + (size_t)b0 * ps;
+        hipLaunchKernelGGL(list_slot_fill_kernel, dim3((unsigned)(((size_t)B * ps + 255) / 256)), dim3(256), 0, st, slot_pos,
+                           (size_t)B * ps);
+        hipLaunchKernelGGL(list_slot_kernel, dim3((L + 255) / 256, B), dim3(256), 0, st, q.d_list_pids + (size_t)b0 * L,
+                           q.d_list_lens + b0, L, s->pid_offset, (int)s->n_docs, w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap,
+                           w.ncand.as<int>() + b0, w.cand_cap, slot_pos, ps);
     }
     CLB_HIP(hipGetLastError());
     return CLB_OK;
@@ -776,12 +805,25 @@ int launch_topk(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, i
 
 // P1 for queries b0 .. b0 + n - 1 of a call with a prior (prior_boost_kernel; nothing otherwise): the scores of the listed
 // slots (list / nlist) or, with list == nullptr, of all candidates become score + weight * value; mabs: prior_tau's M, or nullptr
+// With list priors (q.d_list_prior, never together with q.prior) the same kernel reads the term of a slot from the query's row
+// of the value block, at the position list_slot_kernel left in slot_pos.
 void launch_boost(Workspace& w, hipStream_t st, const Batch& q, int b0, int n, const int* list, const int* nlist, float* mabs) {
-    if (!q.prior) return;
-    hipLaunchKernelGGL(prior_boost_kernel, dim3(n), dim3(1024), 0, st, w.scores.as<float>() + (size_t)b0 * w.cand_cap,
-                       w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap, w.ncand.as<int>() + b0,
-                       list ? list + (size_t)b0 * w.cand_cap : nullptr, list ? nlist + b0 : nullptr,
-                       q.prior->values.as<float>(), q.prior_weight, w.cand_cap, mabs ? mabs + b0 : nullptr);
+    if (!q.prior && !q.d_list_prior) return;
+    float* scores = w.scores.as<float>() + (size_t)b0 * w.cand_cap;
+    const uint32_t* cand = w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap;
+    const int* l = list ? list + (size_t)b0 * w.cand_cap : nullptr;
+    const int* nl = list ? nlist + b0 : nullptr;
+    if (q.prior) {
+        hipLaunchKernelGGL(prior_boost_kernel<false>, dim3(n), dim3(1024), 0, st, scores, cand, w.ncand.as<int>() + b0, l, nl,
+                           PriorTerm{q.prior->values.as<float>(), nullptr, 0, 0}, q.prior_weight, w.cand_cap,
+                           mabs ? mabs + b0 : nullptr);
+        return;
+    }
+    const size_t ps = slot_pos_stride(q);
+    hipLaunchKernelGGL(prior_boost_kernel<true>, dim3(n), dim3(1024), 0, st, scores, cand, w.ncand.as<int>() + b0, l, nl,
+                       PriorTerm{q.d_list_prior + (size_t)b0 * q.list_stride, w.slot_pos.as<int>() + (size_t)b0 * ps,
+                                 (int)q.list_stride, ps},
+                       q.prior_weight, w.cand_cap, mabs ? mabs + b0 : nullptr);
 }
 
 // A2 for queries b0 .. b0 + n - 1 of a call with cursors (after_filter_kernel): of the listed slots (list / nlist) or, with
@@ -1010,9 +1052,10 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
                 const dim3 approx_grid = gxq > 0 && B > 1 ? dim3(gxq, B) : dim3(8 * kWgPerGroup);
                 launch_pass1(s, w, st, dQ, approx_grid, B, T);
             }
-            if (q.prior && phase == 0) {
-                // with a prior (the whole search): the selection cuts on the BOOSTED approximate scores, at their k-th largest --
-                // with a grouping the k-th best group's -- lowered by the rounding slack (prior_tau_kernel)
+            if ((q.prior || q.d_list_prior) && phase == 0) {
+                // with a prior or list priors (the whole search): the selection cuts on the BOOSTED approximate scores, at their
+                // k-th largest -- with a grouping the k-th best group's -- lowered by the rounding slack (prior_tau_kernel, DESIGN
+                // section 5)
                 Timed t(s, KID_SELECT, st);
                 float* ptau = w.prior_tau.as<float>();
                 float* mabs = ptau + w.Bcap;
@@ -1221,11 +1264,17 @@ int check_request(const clb_searcher* s, const clb_search_request* r, int64_t T,
                     (long long)r->struct_bytes, sizeof(clb_search_request));
     if (r->per_group < 0 || r->per_group > CLB_MAX_PER_GROUP) return bad_per_group(r->per_group);
     if (r->per_group && !r->grouping) return hits_without_grouping();
-    if (r->prior && !std::isfinite(r->prior_weight))
+    if ((r->prior || r->list_prior) && !std::isfinite(r->prior_weight))
         return fail(CLB_EARGUMENT, "prior_weight must be finite, got %g", (double)r->prior_weight);
     if ((r->after_scores == nullptr) != (r->after_pids == nullptr))
         return fail(CLB_EARGUMENT, "after_scores and after_pids must both be given or both be null");
     const bool after = r->after_scores != nullptr, phases = route == Route::phase1 || route == Route::phase2;
+    if (r->list_prior && r->prior)          // one additive term per call
+        return fail(CLB_EUNSUPPORTED, "list priors together with a prior are not supported: a call has one additive term");
+    if (r->list_prior && r->per_group > 1)  // as with a prior: the extended list is built from approximate MaxSim scores
+        return fail(CLB_EUNSUPPORTED, "per_group together with list priors is not supported: the hits of a grouped search take "
+                                      "no additive term");
+    if (after && r->list_prior) return fail(CLB_EUNSUPPORTED, "cursors together with list priors are not supported");
     if (r->prior && r->per_group > 1)       // group_extend_kernel builds the extended list from approximate MaxSim scores
         return fail(CLB_EUNSUPPORTED, "per_group together with a prior is not supported: the hits of a grouped search take no prior");
     if (after && r->grouping)               // a cursor continues the ranking of PASSAGES by MaxSim
@@ -1242,6 +1291,7 @@ int check_request(const clb_searcher* s, const clb_search_request* r, int64_t T,
         return fail(CLB_EARGUMENT, "list_pids and list_lens must both be given or both be null");
     const bool listed = r->list_pids != nullptr;
     if (!listed && r->list_scores) return fail(CLB_EARGUMENT, "list_scores without candidate lists (list_pids / list_lens)");
+    if (!listed && r->list_prior) return fail(CLB_EARGUMENT, "list_prior without candidate lists (list_pids / list_lens)");
     if (listed && (r->list_stride < 1 || r->list_stride > (int64_t)0x7fffffff))
         return fail(CLB_EARGUMENT, "list_stride must be 1..2^31-1, got %lld", (long long)r->list_stride);
     for (int64_t b = 0; listed && r->filters && b < B; ++b)
@@ -1252,6 +1302,21 @@ int check_request(const clb_searcher* s, const clb_search_request* r, int64_t T,
         if (r->list_lens[b] < 0 || r->list_lens[b] > r->list_stride)
             return fail(CLB_EARGUMENT, "the candidate list of query %lld has length %lld, outside 0..list_stride=%lld", (long long)b,
                         (long long)r->list_lens[b], (long long)r->list_stride);
+    // ... and every list prior the call can read: finite, and finite when multiplied by the weight (clb_prior's two rules)
+    if (route == Route::host && listed && r->list_prior) {
+        float vmax = 0.f;
+        for (int64_t b = 0; b < B; ++b)
+            for (int64_t i = 0; i < r->list_lens[b]; ++i) {
+                const float v = r->list_prior[b * r->list_stride + i];
+                if (!std::isfinite(v))
+                    return fail(CLB_EARGUMENT, "the list prior of query %lld, position %lld is not a finite number", (long long)b,
+                                (long long)i);
+                vmax = std::max(vmax, std::fabs(v));
+            }
+        if (!(std::fabs((double)r->prior_weight) * (double)vmax < (double)FLT_MAX))
+            return fail(CLB_EARGUMENT, "prior_weight %g times the largest listed |value| %g is not below FLT_MAX",
+                        (double)r->prior_weight, (double)vmax);
+    }
     CLB_TRY(check_search_args(s, T, B, nprobe, k));
     CLB_TRY(route_buffers());
     // ... and, where the host can see them, every listed pid against the handle's range (the device route skips such a pid)
@@ -1320,7 +1385,7 @@ int for_sub_batches(clb_searcher* s, Workspace& w, int64_t T, int64_t B, int64_t
     for (int64_t b0 = 0; b0 < B; b0 += kSubBatch) {
         Batch q = make_batch(nullptr, std::min<int64_t>(kSubBatch, B - b0), T, nprobe, k, r, b0, filt_count);
         CLB_TRY(ensure_workspace(s, w, q.B, T, nprobe, k, filt_count, r.grouping != nullptr, q.per_group, r.prior != nullptr,
-                                 r.after_scores != nullptr));
+                                 r.after_scores != nullptr, r.list_prior != nullptr));
         q.stats_keep = b0 > 0;
         CLB_TRY(run_one(b0, q));
     }
@@ -2136,6 +2201,7 @@ int clb_search_batch_request_device_slot(clb_searcher* s, int slot, const float*
         if (r.list_pids) {         // the sub-batch's own rows of the caller's device arrays
             q.d_list_pids = r.list_pids + (size_t)b0 * r.list_stride; q.d_list_lens = r.list_lens + b0;
             q.d_list_scores = r.list_scores ? r.list_scores + (size_t)b0 * r.list_stride : nullptr;
+            q.d_list_prior = r.list_prior ? r.list_prior + (size_t)b0 * r.list_stride : nullptr;
         }
         q.d_out_pids = hits ? w->hit_p.as<int64_t>() : d_out_pids + (size_t)b0 * k;
         q.d_out_scores = hits ? w->hit_s.as<float>() : d_out_scores + (size_t)b0 * k;
@@ -2169,6 +2235,7 @@ int clb_search_batch_request(clb_searcher* s, const float* Q, int64_t T, int64_t
         CLB_TRY(w.lst_pids.ensure(sizeof(int64_t) * rows * L));
         CLB_TRY(w.lst_lens.ensure(sizeof(int64_t) * rows));
         if (r.list_scores) CLB_TRY(w.lst_scores.ensure(sizeof(float) * rows * L));
+        if (r.list_prior) CLB_TRY(w.lst_prior.ensure(sizeof(float) * rows * L));
     }
     // the queries go up into the slot's own buffer and the results come back from it, sub-batch by sub-batch
     CLB_TRY(for_sub_batches(s, w, T, B, nprobe, k, r, filt_count, [&](int64_t b0, Batch& q) -> int {
@@ -2178,6 +2245,10 @@ int clb_search_batch_request(clb_searcher* s, const float* Q, int64_t T, int64_t
             CLB_HIP(hipMemcpyAsync(w.lst_lens.p, r.list_lens + b0, sizeof(int64_t) * q.B, hipMemcpyHostToDevice, st));
             q.d_list_pids = w.lst_pids.as<int64_t>(); q.d_list_lens = w.lst_lens.as<int64_t>();
             q.d_list_scores = r.list_scores ? w.lst_scores.as<float>() : nullptr;
+            if (r.list_prior) {
+                CLB_HIP(hipMemcpyAsync(w.lst_prior.p, r.list_prior + (size_t)b0 * L, sizeof(float) * q.B * L, hipMemcpyHostToDevice, st));
+                q.d_list_prior = w.lst_prior.as<float>();
+            }
         }
         if (r.after_scores) {      // the sub-batch's cursors go up beside its queries
             CLB_HIP(hipMemcpyAsync(w.after_cur_s.p, r.after_scores + b0, sizeof(float) * q.B, hipMemcpyHostToDevice, st));
@@ -2296,7 +2367,7 @@ int clb_search_shard_phase2_request_slot(clb_searcher* s, int slot, const float*
 
 // ---- the named entry points: each its own refusal (if it has one), a request, one call -----------------------------------
 // (request fields in order: struct_bytes, filters, scope, pad_short, grouping, per_group, group_base, prior, prior_weight,
-// after_scores, after_pids, list_pids, list_lens, list_stride, list_scores; what a named entry leaves out is zero)
+// list_prior, after_scores, after_pids, list_pids, list_lens, list_stride, list_scores; what a named entry leaves out is zero)
 constexpr int64_t kReq = sizeof(clb_search_request);
 
 int clb_search_batch_device(clb_searcher* s, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
@@ -2361,7 +2432,7 @@ int clb_search_batch_after_device_slot(clb_searcher* s, int slot, const float* d
                                        const int64_t* d_after_pids, int64_t* d_out_pids, float* d_out_scores,
                                        int64_t* d_n_cand, void* hip_stream) {
     CLB_TRY(check_after_entry(s, d_out_pids, d_out_scores));
-    const clb_search_request r = {kReq, filters, scope, 0, nullptr, 0, 0, nullptr, 0.f, d_after_scores, d_after_pids};
+    const clb_search_request r = {kReq, filters, scope, 0, nullptr, 0, 0, nullptr, 0.f, nullptr, d_after_scores, d_after_pids};
     return clb_search_batch_request_device_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_out_pids, d_out_scores, d_n_cand, hip_stream);
 }
 
@@ -2404,7 +2475,7 @@ int clb_search_batch_after(clb_searcher* s, const float* Q, int64_t T, int64_t B
                            const clb_filter* const* filters, int scope, const float* after_scores, const int64_t* after_pids,
                            int64_t* out_pids, float* out_scores, int64_t* n_cand) {
     CLB_TRY(check_after_entry(s, out_pids, out_scores));
-    const clb_search_request r = {kReq, filters, scope, /*pad_short=*/1, nullptr, 0, 0, nullptr, 0.f, after_scores, after_pids};
+    const clb_search_request r = {kReq, filters, scope, /*pad_short=*/1, nullptr, 0, 0, nullptr, 0.f, nullptr, after_scores, after_pids};
     return clb_search_batch_request(s, Q, T, B, nprobe, k, &r, out_pids, out_scores, n_cand);
 }
 
@@ -2418,7 +2489,7 @@ int clb_search_batch_listed(clb_searcher* s, const float* Q, int64_t T, int64_t 
                             int64_t* out_pids, float* out_scores, int64_t* n_cand) {
     CLB_TRY(check_listed_entry(list_pids, list_lens));
     const clb_search_request r = {kReq, nullptr, CLB_FILTER_CANDIDATES, /*pad_short=*/1, nullptr, 0, 0, nullptr, 0.f, nullptr, nullptr,
-                                  list_pids, list_lens, list_stride, list_scores};
+                                  nullptr, list_pids, list_lens, list_stride, list_scores};
     return clb_search_batch_request(s, Q, T, B, nprobe, k, &r, out_pids, out_scores, n_cand);
 }
 
@@ -2428,7 +2499,27 @@ int clb_search_batch_listed_device_slot(clb_searcher* s, int slot, const float* 
                                         void* hip_stream) {
     CLB_TRY(check_listed_entry(d_list_pids, d_list_lens));
     const clb_search_request r = {kReq, nullptr, CLB_FILTER_CANDIDATES, 0, nullptr, 0, 0, nullptr, 0.f, nullptr, nullptr,
-                                  d_list_pids, d_list_lens, list_stride, d_list_scores};
+                                  nullptr, d_list_pids, d_list_lens, list_stride, d_list_scores};
+    return clb_search_batch_request_device_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_out_pids, d_out_scores, d_n_cand, hip_stream);
+}
+
+// ... with list priors: the listed request with the value block and the weight (list_prior == NULL: exactly the listed call)
+int clb_search_batch_listed_prior(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                                  const int64_t* list_pids, const int64_t* list_lens, int64_t list_stride, const float* list_prior,
+                                  float weight, float* list_scores, int64_t* out_pids, float* out_scores, int64_t* n_cand) {
+    CLB_TRY(check_listed_entry(list_pids, list_lens));
+    const clb_search_request r = {kReq, nullptr, CLB_FILTER_CANDIDATES, /*pad_short=*/1, nullptr, 0, 0, nullptr, weight, list_prior,
+                                  nullptr, nullptr, list_pids, list_lens, list_stride, list_scores};
+    return clb_search_batch_request(s, Q, T, B, nprobe, k, &r, out_pids, out_scores, n_cand);
+}
+
+int clb_search_batch_listed_prior_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                              int64_t k, const int64_t* d_list_pids, const int64_t* d_list_lens,
+                                              int64_t list_stride, const float* d_list_prior, float weight, float* d_list_scores,
+                                              int64_t* d_out_pids, float* d_out_scores, int64_t* d_n_cand, void* hip_stream) {
+    CLB_TRY(check_listed_entry(d_list_pids, d_list_lens));
+    const clb_search_request r = {kReq, nullptr, CLB_FILTER_CANDIDATES, 0, nullptr, 0, 0, nullptr, weight, d_list_prior,
+                                  nullptr, nullptr, d_list_pids, d_list_lens, list_stride, d_list_scores};
     return clb_search_batch_request_device_slot(s, slot, d_Q, T, B, nprobe, k, &r, d_out_pids, d_out_scores, d_n_cand, hip_stream);
 }
 

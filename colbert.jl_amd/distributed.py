@@ -251,14 +251,14 @@ class DeviceSearch:
         return self.generation != self.s.generation
 
     def replay(self, graph, Qstatic, filters=None, scope="candidates", grouping=None, per_group=None, prior=None,
-               prior_weight=1.0, after=None, candidates=None, candidate_scores=None):
+               prior_weight=1.0, after=None, candidates=None, candidate_scores=None, candidate_priors=None):
         """`graph.replay()` for a graph `capture` returned, made safe against appends: when the searcher has grown since
         the capture, the sizing pass runs again and the search is captured anew before anything is replayed.  Returns the
         graph that was replayed (keep it for the next call).  `after`: the cursor tensors the graph was captured with -- it
-        reads their CONTENTS at every replay; `candidates` / `candidate_scores` likewise."""
+        reads their CONTENTS at every replay; `candidates` / `candidate_scores` / `candidate_priors` likewise."""
         if self.graph_is_stale():
             graph = self.capture(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after, candidates,
-                                 candidate_scores)
+                                 candidate_scores, candidate_priors)
         graph.replay()
         return graph
 
@@ -306,18 +306,33 @@ class DeviceSearch:
             raise ArgumentError(f"candidate_scores must be a contiguous float32[{self.B}, {L}] tensor on {self.dev}")
         return candidates[0], candidates[1], L, candidate_scores, False
 
+    def _check_list_priors(self, candidate_priors, lists):
+        """The list priors go to the kernels as a bare pointer beside the lists: a contiguous float32 [B, L] tensor on this
+        device, or refused.  Nothing is read back: the largest |value| the weight is checked against is 0 (a value whose
+        product with the weight is not finite counts as 0 on the device)."""
+        import torch
+        from ._lib import ArgumentError
+        L = lists[2]
+        t = candidate_priors
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.dev and t.is_contiguous()
+                and tuple(t.shape) == (self.B, L)):
+            raise ArgumentError(f"candidate_priors must be a contiguous float32[{self.B}, {L}] tensor on {self.dev}")
+        return t, 0.0
+
     def _request(self, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0, after=None,
-                 group_base: int = 0, candidates=None, candidate_scores=None):
+                 group_base: int = 0, candidates=None, candidate_scores=None, candidate_priors=None):
         """The clb_search_request of a call of this shard (searcher.search_request), its cursors as device tensors.  A call
         without keywords takes the request made at construction: it has nothing to check and nothing to point at."""
         if (filters is None and grouping is None and per_group is None and prior is None and after is None
-                and scope == "candidates" and candidates is None and candidate_scores is None):
+                and scope == "candidates" and candidates is None and candidate_scores is None and candidate_priors is None):
             return self._plain
         return search_request(self.s, self.B, filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
                               prior_weight=prior_weight, after=after, group_base=group_base,
                               cursor_arrays=lambda cursors, _B: self._check_cursors(cursors), candidates=candidates,
                               candidate_scores=candidate_scores,
-                              candidate_arrays=lambda lists, scores, _B: self._check_lists(lists, scores))
+                              candidate_arrays=lambda lists, scores, _B: self._check_lists(lists, scores),
+                              candidate_priors=candidate_priors,
+                              candidate_prior_arrays=lambda values, lists, _B: self._check_list_priors(values, lists))
 
     def _stream(self) -> int:
         return self._current_stream(self.dev).cuda_stream
@@ -419,7 +434,7 @@ class DeviceSearch:
         return block if g else (self.out_p, self.out_s)
 
     def capture(self, Qstatic, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0,
-                after=None, candidates=None, candidate_scores=None):
+                after=None, candidates=None, candidate_scores=None, candidate_priors=None):
         """A HIP graph of one search over the STATIC query buffer `Qstatic` (B, T, dim): the library enqueues nothing but
         kernels and memsets on the stream it is handed, so the nine launches of a search can be captured once and
         replayed -- write the next queries into `Qstatic` (e.g. let the encoder write there), `graph.replay()`, read
@@ -434,7 +449,8 @@ class DeviceSearch:
         tensors, as in __call__): the graph holds their ADDRESSES, not their values -- to page, copy the last row of `out_s` /
         `out_p` into them and replay.  `candidates` / `candidate_scores` (device tensors, as in __call__): the graph holds
         their ADDRESSES too -- to re-rank under a graph, write the next batch's pids and lengths into the same tensors and
-        replay (the sizing pass grows the slot for this stride; a larger stride needs a new capture)."""
+        replay (the sizing pass grows the slot for this stride; a larger stride needs a new capture).  `candidate_priors`
+        likewise: the graph holds the ADDRESS of the value block and the weight -- write the next batch's values beside its pids."""
         import torch
         self._check_queries(Qstatic)
         self.generation = self.s.generation
@@ -442,15 +458,17 @@ class DeviceSearch:
         side = torch.cuda.Stream(self.dev)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after, candidates, candidate_scores)
+            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after, candidates, candidate_scores,
+                 candidate_priors)
         cur.wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after, candidates, candidate_scores)
+            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after, candidates, candidate_scores,
+                 candidate_priors)
         return graph
 
     def __call__(self, Qdev, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0,
-                 after=None, candidates=None, candidate_scores=None):
+                 after=None, candidates=None, candidate_scores=None, candidate_priors=None):
         """Qdev: torch float32 tensor holding B queries laid out (B, T, dim) contiguous == Julia (dim, T, B).  One call of
         clb_search_batch_request_device_slot, whatever the keywords.
         `filters`: one PassageFilter or a sequence of B entries (None = unfiltered), `scope` "candidates" / "all"
@@ -469,11 +487,16 @@ class DeviceSearch:
         lens[b] entries are query b's candidate set (Searcher.search_batch; the lists stay on the device, nothing is raised
         about their contents: a length is clamped to 0..L, a pid outside the searcher's range is skipped).  With
         `candidate_scores` (float32[B, L]) the call also writes every listed passage's exact score at its position, -Inf
-        where the position holds no candidate, and runs as the single exact pass.  Not with `filters`."""
+        where the position holds no candidate, and runs as the single exact pass.  Not with `filters`.
+        `candidate_priors` (float32[B, L] on the searcher's device, needs `candidates`) with `prior_weight`: rank by score +
+        prior_weight * the value beside a passage's first occurrence (Searcher.search_batch).  Nothing is raised about the
+        values: one that is not finite, or whose product with the weight is not finite, counts as 0.  Not with `prior`,
+        `per_group` > 1 or `after`."""
         import torch
         self._check_queries(Qdev)
         req = self._request(filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
-                            prior_weight=prior_weight, after=after, candidates=candidates, candidate_scores=candidate_scores)
+                            prior_weight=prior_weight, after=after, candidates=candidates, candidate_scores=candidate_scores,
+                            candidate_priors=candidate_priors)
         out_p, out_s = self.out_p, self.out_s
         if per_group is not None:
             m = int(req.per_group)

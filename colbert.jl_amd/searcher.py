@@ -212,6 +212,66 @@ def _candidate_keywords(candidates, filters, want_scores=False):
         raise Unsupported("candidates= together with filter(s)= is not supported: a list is the candidate set")
 
 
+def _candidate_prior_keywords(candidate_priors, candidates, prior=None, per_group=None, after=None):
+    """The `candidate_priors=` of a search call against the keywords it is not offered with: it needs `candidates=`, and a call
+    has one additive term (the rules of `prior=`)."""
+    from ._lib import ArgumentError, Unsupported
+    if candidate_priors is None:
+        return
+    if candidates is None:
+        raise ArgumentError("candidate_priors needs candidates=: it holds one value per listed passage")
+    if prior is not None:
+        raise Unsupported("candidate_priors together with prior is not supported: a call has one additive term")
+    if isinstance(per_group, (int, np.integer)) and not isinstance(per_group, bool) and int(per_group) > 1:
+        raise Unsupported("per_group together with candidate_priors is not supported: the hits of a grouped search take no "
+                          "additive term (per_group=1 is the grouped search itself)")
+    if after is not None:
+        raise Unsupported("after together with candidate_priors is not supported: a cursor continues the ranking of passages "
+                          "by MaxSim")
+
+
+def _float32_list(a, what: str) -> np.ndarray:
+    """An array of numbers as float32, or ArgumentError."""
+    from ._lib import ArgumentError
+    try:
+        raw = np.asarray(a)
+    except (TypeError, ValueError) as e:
+        raise ArgumentError(f"{what} must be numbers: {e}") from None
+    if raw.dtype.kind not in "iuf" and raw.size:
+        raise ArgumentError(f"{what} must be numbers, got dtype {raw.dtype}")
+    with np.errstate(over="ignore"):
+        return raw.astype(np.float32)
+
+
+def _candidate_prior_arrays(candidate_priors, lists, B: int):
+    """`candidate_priors=` of Searcher.search_batch beside the arrays of `candidates=` (`lists`, from _candidate_arrays) as the
+    host block the C ABI takes and the largest listed |value|: (values (L, B) column-major float32, max_abs).  Ragged lists
+    take a sequence of B arrays of the lists' lengths, padded with 0; the pair form takes an (L, B) block.  Only the values
+    at positions below a list's length count: one of them that is not finite is ArgumentError."""
+    from ._lib import ArgumentError
+    _, lens, L, _, ragged = lists
+    if ragged:
+        if isinstance(candidate_priors, (str, bytes)) or not hasattr(candidate_priors, "__len__") or len(candidate_priors) != B:
+            raise ArgumentError(f"candidate_priors holds one array of values per candidate list: {B} arrays for {B} queries")
+        vals = np.zeros((L, B), dtype=np.float32, order="F")
+        for b, v in enumerate(candidate_priors):
+            v = _float32_list(v, f"the candidate priors of query {b}").reshape(-1)
+            if v.size != int(lens[b]):
+                raise ArgumentError(f"the candidate priors of query {b} hold {v.size} values for a list of {int(lens[b])} pids")
+            vals[:v.size, b] = v
+    else:
+        vals = _float32_list(candidate_priors, "the candidate priors")
+        if vals.shape != (L, B):
+            raise ArgumentError(f"candidate_priors must be an (L={L}, B={B}) block beside candidates=(pids, lens), got {vals.shape}")
+        vals = np.asfortranarray(vals)
+    listed = np.arange(L)[:, None] < np.asarray(lens)[None, :]
+    bad = np.argwhere(listed & ~np.isfinite(vals))
+    if bad.size:
+        b = int(bad[:, 1].min()); i = int(bad[bad[:, 1] == b, 0].min())
+        raise ArgumentError(f"the candidate prior of query {b}, position {i} is not a finite number")
+    return vals, float(np.abs(vals[listed]).max()) if listed.any() else 0.0
+
+
 def _int64_list(a, what: str) -> np.ndarray:
     """An array of integers as int64, or ArgumentError: a float or a value past int64 is no pid and no length."""
     from ._lib import ArgumentError
@@ -259,7 +319,8 @@ def _candidate_arrays(candidates, want_scores, B: int):
 
 def search_request(searcher, B: int, *, filters=None, scope="candidates", grouping=None, per_group=None, prior=None,
                    prior_weight=1.0, after=None, pad_short=False, group_base: int = 0, cursor_arrays=_after_arrays,
-                   candidates=None, candidate_scores=None, candidate_arrays=_candidate_arrays) -> SearchRequest:
+                   candidates=None, candidate_scores=None, candidate_arrays=_candidate_arrays, candidate_priors=None,
+                   candidate_prior_arrays=_candidate_prior_arrays) -> SearchRequest:
     """The keywords of a search call of `searcher` over B queries, checked on the host, as the clb_search_request every
     search entry point takes (include/colbert_hip.h).  Raises what the helpers above raise, in their order: scope, `after`
     against the keywords it is not offered with, the cursors, the prior and its weight (never with `per_group`), `per_group`,
@@ -269,9 +330,14 @@ def search_request(searcher, B: int, *, filters=None, scope="candidates", groupi
     `candidates` (Searcher.search_batch) with `candidate_scores` (true: the call is to leave the list scores): never with
     filters (Unsupported); `candidate_arrays(candidates, candidate_scores, B)` gives (pids, lens, L, scores or None, ragged) --
     host arrays here, with the int64 conversion and the padding of ragged lists, device tensors from DeviceSearch -- which
-    the request keeps as `lists`; with lists the host route always pads."""
+    the request keeps as `lists`; with lists the host route always pads.
+    `candidate_priors` (Searcher.search_batch) with `prior_weight`: needs `candidates` (ArgumentError), never with `prior`,
+    `per_group` > 1 or `after` (Unsupported); `candidate_prior_arrays(candidate_priors, lists, B)` gives (values, max_abs) -- the
+    host block here, checked value by value, the device tensor from DeviceSearch with max_abs 0 (nothing is read back) -- and
+    the weight is checked against that max_abs as a prior's is."""
     _scope_code(scope)
     _candidate_keywords(candidates, filters, candidate_scores is not None and candidate_scores is not False)
+    _candidate_prior_keywords(candidate_priors, candidates, prior, per_group, after)
     r = SearchRequest(struct_bytes=C.sizeof(SearchRequest), scope=_scope_code(scope), group_base=int(group_base),
                       pad_short=1 if (pad_short or filters is not None or after is not None or candidates is not None) else 0)
     r.lists = None
@@ -279,6 +345,11 @@ def search_request(searcher, B: int, *, filters=None, scope="candidates", groupi
         r.lists = tuple(candidate_arrays(candidates, candidate_scores, B))
         ptr = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
         r.list_pids, r.list_lens, r.list_stride, r.list_scores = ptr(r.lists[0]), ptr(r.lists[1]), int(r.lists[2]), ptr(r.lists[3])
+        if candidate_priors is not None:
+            values, max_abs = candidate_prior_arrays(candidate_priors, r.lists, B)
+            r.prior_weight = _weight_value(prior_weight, max_abs)
+            r.list_prior = ptr(values)
+            r.lists += (values,)
     cursors = ()
     if after is not None:
         _after_keywords(after, grouping, per_group, prior)
@@ -717,7 +788,7 @@ class Searcher:
     # -- search -----------------------------------------------------------------------------------
     def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates", grouping=None,
                           per_group=None, prior=None, prior_weight=1.0, after=None, candidates=None,
-                          return_candidate_scores=False):
+                          return_candidate_scores=False, candidate_priors=None):
         """search() after encode_queries (searching.jl:102-127).  Q: (dim, T) Float32.
         Returns (pids Int64[k] 1-based, scores Float32[k]).
         `filter` (a PassageFilter of this searcher): search among its passages only -- scope "candidates": the query's
@@ -735,18 +806,22 @@ class Searcher:
         padded (Searcher.search_batch); not with `grouping`, `per_group` or `prior`.
         `candidates` (one array of pids): re-rank exactly these passages (Searcher.search_batch), always padded; with
         `return_candidate_scores=True` the call returns (pids, scores, candidate_scores), the third the score of every listed
-        pid at its position.  Not with `filter`."""
+        pid at its position.  Not with `filter`.
+        `candidate_priors` (one array of values, one per listed pid) with `prior_weight`: rank the listed passages by score +
+        prior_weight * value (Searcher.search_batch); not with `prior`, `per_group` > 1 or `after`."""
         q = colmajor(Q, np.float32)
         if q.ndim != 2 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T)")
         _scope_code(scope)
         _after_keywords(after, grouping, per_group, prior)
         _candidate_keywords(candidates, None if filter is None else [filter], return_candidate_scores)
+        _candidate_prior_keywords(candidate_priors, candidates, prior, per_group, after)
         if candidates is not None:
             out = self.search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe, scope=scope, grouping=grouping,
                                     per_group=per_group, prior=prior, prior_weight=prior_weight,
                                     after=None if after is None else self._one_cursor(after), candidates=[candidates],
-                                    return_candidate_scores=return_candidate_scores)
+                                    return_candidate_scores=return_candidate_scores,
+                                    candidate_priors=None if candidate_priors is None else [candidate_priors])
             self.last_num_candidates = int(out[2][0])
             one = (np.asfortranarray(out[0][..., 0]), np.asfortranarray(out[1][..., 0]))
             return one + (out[3][0],) if return_candidate_scores else one
@@ -775,7 +850,7 @@ class Searcher:
 
     def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
                      scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0, after=None,
-                     candidates=None, return_candidate_scores=False):
+                     candidates=None, return_candidate_scores=False, candidate_priors=None):
         """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B]); one call of clb_search_batch_request.
         `filters`: one PassageFilter for every query, or a sequence of B entries (None = that query is unfiltered); with
         filters the results are always padded (pid 0 / -Inf past n_candidates[b], the count AFTER the filter) and `scope`
@@ -807,14 +882,21 @@ class Searcher:
         `return_candidate_scores=True` (needs `candidates`): a fourth result, the exact score of every listed passage at its
         input position (with a prior: E), -Inf where the position holds no candidate -- a list of B float32 arrays of the
         input lengths for ragged lists, an (L, B) array for the pair form.  They are passage scores: a grouping or cursors
-        do not change them.  Such a call scores every candidate exactly: it runs as the single exact pass whatever the mode."""
+        do not change them.  Such a call scores every candidate exactly: it runs as the single exact pass whatever the mode.
+        `candidate_priors` (needs `candidates`) with `prior_weight`: re-rank with first-stage scores -- one value per listed pid,
+        a sequence of B arrays of the lists' lengths or an (L, B) block beside the pair form.  Candidate p of query b is ranked
+        by E = fl32(e + fl32(prior_weight * v)), v the value at p's FIRST occurrence in query b's list, and E is the score
+        returned (and the candidate score): bit for bit the one-query call with `prior=make_prior(dense)` whose dense vector
+        holds v for the listed passages and 0 elsewhere, without a handle and per query.  Values must be finite and keep
+        |prior_weight| * max|value| below FLT_MAX (ArgumentError, naming the query and the position).  Composes with
+        `grouping` (`per_group=1` included); not with `prior`, `per_group` > 1 or `after` (Unsupported)."""
         q = colmajor(Q, np.float32)
         if q.ndim != 3 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T, B)")
         B = q.shape[2]
         req = search_request(self, B, filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
                              prior_weight=prior_weight, after=after, pad_short=pad_short, candidates=candidates,
-                             candidate_scores=bool(return_candidate_scores))
+                             candidate_scores=bool(return_candidate_scores), candidate_priors=candidate_priors)
         shape = (k, B) if per_group is None else (int(req.per_group), k, B)
         pids = np.zeros(shape, dtype=np.int64, order="F"); scores = np.zeros(shape, dtype=np.float32, order="F")
         ncand = np.zeros(B, dtype=np.int64)
@@ -822,7 +904,7 @@ class Searcher:
                                                         fptr(pids), fptr(scores), fptr(ncand)))
         if not return_candidate_scores:
             return pids, scores, ncand
-        _, lens, _, cs, ragged = req.lists
+        _, lens, _, cs, ragged = req.lists[:5]
         return pids, scores, ncand, ([cs[:int(n), b].copy() for b, n in enumerate(lens)] if ragged else cs)
 
     def retrieve(self, Q, nprobe: Optional[int] = None):
@@ -846,19 +928,20 @@ class Searcher:
                 "eps": eps.value, "n_rescore": nr.value}
 
     def search(self, query: str, k: int, *, filter=None, scope="candidates", grouping=None, per_group=None, prior=None,
-               prior_weight=1.0, after=None, candidates=None, return_candidate_scores=False):
+               prior_weight=1.0, after=None, candidates=None, return_candidate_scores=False, candidate_priors=None):
         """search(searcher, query::String, k) (searching.jl:93-128); `filter` / `scope` / `grouping` / `per_group` / `prior` /
-        `prior_weight` / `after` / `candidates` / `return_candidate_scores` as in search_embeddings."""
+        `prior_weight` / `after` / `candidates` / `return_candidate_scores` / `candidate_priors` as in search_embeddings."""
         _scope_code(scope)
         _after_keywords(after, grouping, per_group, prior)
         _candidate_keywords(candidates, None if filter is None else [filter], return_candidate_scores)
+        _candidate_prior_keywords(candidate_priors, candidates, prior, per_group, after)
         if self.encoder is None:
             raise ColBERTError("no query encoder attached: pass encoder=... or use search_embeddings(Q, k)")
         Q = self.encoder.encode_queries([query])
         assert Q.shape[2] == 1 and Q.shape[1] == self.config.query_maxlen, Q.shape
         return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope, grouping=grouping, per_group=per_group,
                                       prior=prior, prior_weight=prior_weight, after=after, candidates=candidates,
-                                      return_candidate_scores=return_candidate_scores)
+                                      return_candidate_scores=return_candidate_scores, candidate_priors=candidate_priors)
 
     def text_search(self, k: int, nprobe: Optional[int] = None, graph: bool = True) -> "TextSearch":
         """A session for repeated `search(searcher, query::String, k)` calls with everything after the tokenizer on the
@@ -1078,13 +1161,15 @@ class TextSearch:
 
 
 def search(searcher: Searcher, query, k: int, *, filter=None, scope="candidates", grouping=None, per_group=None, prior=None,
-           prior_weight=1.0, after=None, candidates=None, return_candidate_scores=False):
+           prior_weight=1.0, after=None, candidates=None, return_candidate_scores=False, candidate_priors=None):
     """The reference's exported `search` (src/ColBERT.jl:40).  `query` may be a string (needs an
     encoder) or a (dim, T) Float32 matrix of query embeddings.  `filter` / `scope` / `grouping` / `per_group` / `prior` /
-    `prior_weight` / `after` / `candidates` / `return_candidate_scores`: Searcher.search_embeddings."""
+    `prior_weight` / `after` / `candidates` / `return_candidate_scores` / `candidate_priors`: Searcher.search_embeddings."""
     more = {} if after is None else {"after": after}      # (a ShardedSearcher answers a cursor with Unsupported itself)
     if candidates is not None or return_candidate_scores:  # (... and candidate lists likewise)
         more.update(candidates=candidates, return_candidate_scores=return_candidate_scores)
+    if candidate_priors is not None:                       # (... and their values; a weight other than 1 travels below)
+        more.update(candidate_priors=candidate_priors)
     if prior is None and prior_weight == 1.0:      # (a call without a prior hands over the keywords it always has)
         if isinstance(query, str):
             return searcher.search(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group, **more)

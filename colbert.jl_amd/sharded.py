@@ -13,8 +13,8 @@ keeps ONE global index on both sides (`group_base` of a shard + its local index)
 k best groups with those indices, the threshold counts a repeated index once, and the merge (merge_grouped_packed) keeps one
 record per group and counts a straddling candidate group once; under "single" every shard runs its whole grouped search and
 the same merge follows.  The hits of a grouped search (`per_group=` of `Searcher`) are not served across a shard group:
-the search calls accept the keyword and raise Unsupported.  Candidate lists (`candidates=` / `return_candidate_scores=` of
-`Searcher`) likewise.
+the search calls accept the keyword and raise Unsupported.  Candidate lists (`candidates=` / `return_candidate_scores=` /
+`candidate_priors=` of `Searcher`) likewise.
 Score priors (`make_prior`, `prior=`, `prior_weight=`): the values are cut at the shard boundaries, one PassagePrior per shard.
 Under "two_phase" the shards publish their k largest BOOSTED approximate scores and, per query, the largest such score by
 magnitude; the threshold of phase 2 is lowered by a rounding slack formed from the maximum of those magnitudes over ALL shards
@@ -536,7 +536,7 @@ class ShardedSearcher:
 
     def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
                      scope="candidates", protocol="auto", grouping=None, per_group=None, after=None, prior=None,
-                     prior_weight=1.0, candidates=None, return_candidate_scores=False):
+                     prior_weight=1.0, candidates=None, return_candidate_scores=False, candidate_priors=None):
         """B queries: Q (dim, T, B) -> (pids (k, B), scores (k, B), n_candidates[B]), GLOBAL pids, layouts and padding (pid 0 /
         -Inf) as `Searcher.search_batch`; n_candidates is the sum over the shards.  `filters`: one ShardedFilter or a sequence
         of B entries (None = that query is unfiltered); with filters the result is always padded.  Without, a query for which
@@ -553,12 +553,12 @@ class ShardedSearcher:
         with `grouping` (a group is represented by its candidate with the largest E), under every protocol.  The weight must be
         finite and keep |weight| * max|value| (over the whole group) below FLT_MAX: ArgumentError.
         `per_group`: anything but None raises Unsupported (the hits of a grouped search are a single handle's), and so does
-        `after` (a cursor continues the ranking of a single handle), and so do `candidates` / `return_candidate_scores`
-        (candidate lists are a single handle's)."""
+        `after` (a cursor continues the ranking of a single handle), and so do `candidates` / `return_candidate_scores` /
+        `candidate_priors` (candidate lists are a single handle's)."""
         if prior is None:       # (with a prior the refusal is the single handle's: _check_prior)
             self._no_per_group(per_group)
         self._no_after(after)
-        self._no_candidates(candidates, return_candidate_scores)
+        self._no_candidates(candidates, return_candidate_scores, candidate_priors)
         q = colmajor(Q, np.float32)
         if q.ndim != 3 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T, B)")
@@ -599,20 +599,20 @@ class ShardedSearcher:
                               "Searcher")
 
     @staticmethod
-    def _no_candidates(candidates, return_candidate_scores=False):
-        if candidates is not None or return_candidate_scores:
+    def _no_candidates(candidates, return_candidate_scores=False, candidate_priors=None):
+        if candidates is not None or return_candidate_scores or candidate_priors is not None:
             raise Unsupported("candidates= (re-rank given passages) is not supported across a shard group: search the unsharded "
                               "Searcher, or hand every shard's Searcher the lists (its device route skips another shard's pids)")
 
     def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates", protocol="auto",
                           grouping=None, per_group=None, after=None, prior=None, prior_weight=1.0, candidates=None,
-                          return_candidate_scores=False):
+                          return_candidate_scores=False, candidate_priors=None):
         """One query, Q (dim, T) -> (pids Int64[k], scores Float32[k]) as `Searcher.search_embeddings`; the candidate count
         (with a grouping: the candidate groups) is left in `last_num_candidates`.  `prior` / `prior_weight`: search_batch."""
         if prior is None:
             self._no_per_group(per_group)
         self._no_after(after)
-        self._no_candidates(candidates, return_candidate_scores)
+        self._no_candidates(candidates, return_candidate_scores, candidate_priors)
         q = colmajor(Q, np.float32)
         if q.ndim != 2 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T)")
@@ -623,12 +623,13 @@ class ShardedSearcher:
         return np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(s[:, 0])
 
     def search(self, query: str, k: int, *, filter=None, scope="candidates", protocol="auto", grouping=None, per_group=None,
-               after=None, prior=None, prior_weight=1.0, candidates=None, return_candidate_scores=False):
+               after=None, prior=None, prior_weight=1.0, candidates=None, return_candidate_scores=False,
+               candidate_priors=None):
         """search(searcher, query::String, k) over the group, with the attached encoder."""
         if prior is None:
             self._no_per_group(per_group)
         self._no_after(after)
-        self._no_candidates(candidates, return_candidate_scores)
+        self._no_candidates(candidates, return_candidate_scores, candidate_priors)
         self._check_prior(prior, prior_weight, per_group)         # before the encoder runs
         if self.encoder is None:
             raise ColBERTError("no query encoder attached: pass encoder=... or use search_embeddings(Q, k)")

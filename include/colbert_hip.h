@@ -595,8 +595,9 @@ int clb_debug_prior_tau_device(const float* d_all_top, const int64_t* d_all_gid,
  * the searcher is looked at.  Zero-initialise the struct, set struct_bytes, then the fields of the features in use:
  * everything left zero / NULL means "none".
  * Refused combinations, all CLB_EUNSUPPORTED: a prior with per_group > 1 (the hits are built from approximate MaxSim scores),
- * cursors with a grouping, cursors with a prior, candidate lists with filters; on the phase routes also per_group > 1,
- * cursors and candidate lists, and phase 2 takes no filters (it continues on the candidates phase 1 left on the slot).
+ * cursors with a grouping, cursors with a prior, candidate lists with filters, list priors with a prior, with per_group > 1 or
+ * with cursors; on the phase routes also per_group > 1, cursors and candidate lists, and phase 2 takes no filters (it
+ * continues on the candidates phase 1 left on the slot).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct clb_search_request {
     int64_t struct_bytes;                 /* sizeof this struct: anything else is CLB_EARGUMENT */
@@ -606,13 +607,15 @@ typedef struct clb_search_request {
     const clb_grouping* grouping;         /* or NULL */
     int64_t per_group;                    /* 0: none; 1: the grouped search itself; 2..CLB_MAX_PER_GROUP: hits (needs grouping) */
     int64_t group_base;                   /* phase routes with a grouping: the global index of the shard's first group */
-    const clb_prior* prior;               /* or NULL: prior_weight is then ignored */
-    float prior_weight;
+    const clb_prior* prior;               /* or NULL: without prior and list_prior, prior_weight is ignored */
+    float prior_weight;                   /* the weight of prior or of list_prior: finite, or CLB_EARGUMENT */
+    const float* list_prior;              /* or NULL.  List priors ("Re-rank given passages" below): [B][list_stride] values beside */
+                                          /* list_pids, where the lists live; needs the lists, never together with prior */
     const float* after_scores;            /* cursors, [B] each, both or neither: HOST arrays on the host route (a NaN score */
     const int64_t* after_pids;            /* is CLB_EARGUMENT), DEVICE arrays on the device route */
     const int64_t* list_pids;             /* candidate lists ("Re-rank given passages" below), both or neither: [B][list_stride] */
     const int64_t* list_lens;             /* pids and [B] lengths; HOST arrays on the host route, DEVICE arrays on the device route */
-    int64_t list_stride;                  /* L >= 1: entries per row of list_pids / list_scores */
+    int64_t list_stride;                  /* L >= 1: entries per row of list_pids / list_prior / list_scores */
     float* list_scores;                   /* or NULL.  The one OUTPUT a request carries: [B][list_stride], where the lists live */
 } clb_search_request;
 /* The host route: clb_search_batch and every clb_search_batch_* entry without _device.  With per_group > 1 the outputs
@@ -666,6 +669,28 @@ int clb_search_shard_phase2_request_slot(clb_searcher* s, int slot, const float*
  * value: a slot's first listed call, or one with a larger stride, may grow it (outside a capture); later calls allocate
  * nothing.  Batches above 64 queries run as sub-batches, each reading its own rows.
  * list_pids == NULL and list_lens == NULL here is CLB_EARGUMENT (without lists: clb_search_batch / ..._device_slot).
+ *
+ * List priors: re-rank with first-stage scores.  A listed call may carry one fp32 value per list position, list_prior[b][i]
+ * beside list_pids[b][i], and one finite weight for the batch (prior_weight): hybrid fusion E = MaxSim + w * first-stage score,
+ * teacher scores, a per-request boost -- an additive term per (query, passage), where a clb_prior holds one per passage.
+ *   value:   v_b(p) of candidate p of query b is the value at the LOWEST position i < list_lens[b] with list_pids[b][i] == p: of
+ *            a duplicate's values the first counts, on every route.  Values at positions >= list_lens[b], beside pids outside
+ *            the handle's range and beside passages without embeddings are never read as values.
+ *   result:  clb_prior's formulas -- pi = fl32(weight * v_b(p)), E = fl32(e(p) + pi), one rounded multiply and one rounded add,
+ *            never an fma -- the first k candidates by (E descending, pid ascending), the scores E.  Row b is bit for bit the
+ *            same handle's call for query b alone with the list and a clb_prior that holds v_b(p) for listed p and 0 elsewhere.
+ *            Candidates, n_cand and padding are those of the call without list priors; all-zero values or weight 0 give its bits.
+ *            list_scores then holds E at every input position.  In the two-pass mode the cut is that of a prior
+ *            (tau - 2 delta - 2 eps).
+ *   with:    a grouping (per_group 0 or 1: a group is represented by its candidate with the largest E).  CLB_EUNSUPPORTED
+ *            together with a prior (a call has ONE additive term), with per_group > 1 and with cursors; CLB_EARGUMENT without
+ *            lists and with a weight that is not finite.  All answered before the searcher is looked at.
+ * Host route, before any device work: a value at a position i < list_lens[b] that is not finite is CLB_EARGUMENT naming the
+ * query and the position, and so is |weight| * max |value| over those positions not below FLT_MAX.
+ * Device route: nothing can be raised about the values either -- one that is not finite, or whose product with the weight is
+ * not finite, counts as 0.  Stream-ordered and capturable like the lists: a graph holds the ADDRESS of the value block.  A
+ * slot's first call with list priors may grow it by 4 bytes per query and candidate of its capacity; later calls allocate
+ * nothing.  With list_prior == NULL the two entries below launch exactly what clb_search_batch_listed* launch.
  * ---------------------------------------------------------------------------------------------- */
 int clb_search_batch_listed(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
                             const int64_t* list_pids, const int64_t* list_lens, int64_t list_stride,
@@ -674,6 +699,15 @@ int clb_search_batch_listed_device_slot(clb_searcher* s, int slot, const float* 
                                         int64_t k, const int64_t* d_list_pids, const int64_t* d_list_lens, int64_t list_stride,
                                         float* d_list_scores /* may be NULL */, int64_t* d_out_pids, float* d_out_scores,
                                         int64_t* d_n_cand, void* hip_stream);
+int clb_search_batch_listed_prior(clb_searcher* s, const float* Q, int64_t T, int64_t B, int64_t nprobe, int64_t k,
+                                  const int64_t* list_pids, const int64_t* list_lens, int64_t list_stride,
+                                  const float* list_prior /* may be NULL */, float weight, float* list_scores /* may be NULL */,
+                                  int64_t* out_pids, float* out_scores, int64_t* n_cand);
+int clb_search_batch_listed_prior_device_slot(clb_searcher* s, int slot, const float* d_Q, int64_t T, int64_t B, int64_t nprobe,
+                                              int64_t k, const int64_t* d_list_pids, const int64_t* d_list_lens,
+                                              int64_t list_stride, const float* d_list_prior /* may be NULL */, float weight,
+                                              float* d_list_scores /* may be NULL */, int64_t* d_out_pids, float* d_out_scores,
+                                              int64_t* d_n_cand, void* hip_stream);
 
 /* retrieve()  (src/search/ranking.jl:23-44) on its own -- test hook.  out_pids needs n_docs entries. */
 int clb_retrieve(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe, int64_t* out_pids,
