@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import check, i64, lib, request_entry
-from .searcher import search_request
+from .searcher import SearchKeywords, search_request
 from .sharding import merge_topk_host
 
 
@@ -256,83 +256,73 @@ class DeviceSearch:
         the capture, the sizing pass runs again and the search is captured anew before anything is replayed.  Returns the
         graph that was replayed (keep it for the next call).  `after`: the cursor tensors the graph was captured with -- it
         reads their CONTENTS at every replay; `candidates` / `candidate_scores` / `candidate_priors` likewise."""
+        kw = SearchKeywords(filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
+                            prior_weight=prior_weight, after=after, candidates=candidates, candidate_scores=candidate_scores,
+                            candidate_priors=candidate_priors)
         if self.graph_is_stale():
-            graph = self.capture(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after, candidates,
-                                 candidate_scores, candidate_priors)
+            graph = self._capture(Qstatic, kw)
         graph.replay()
         return graph
+
+    def _fits(self, t, dtype, *shape) -> bool:
+        """`t` may go to the kernels as a bare pointer: a contiguous tensor of `dtype` on this device -- and, where a shape is
+        given, of that shape (None: any extent)."""
+        import torch
+        return (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == self.dev and t.is_contiguous()
+                and (not shape or (t.dim() == len(shape) and all(n is None or n == m for n, m in zip(shape, t.shape)))))
 
     def _check_queries(self, Qdev):
         """The C ABI takes a bare pointer: a tensor with fewer than B x T x dim contiguous floats on this device would
         be read past its end by the kernels, so it is refused here."""
         import torch
         from ._lib import ArgumentError
-        want = self.B * self.T * int(self.s.dim)
-        if (not isinstance(Qdev, torch.Tensor) or Qdev.dtype != torch.float32 or Qdev.device != self.dev
-                or not Qdev.is_contiguous() or Qdev.numel() != want):
+        if not (self._fits(Qdev, torch.float32) and Qdev.numel() == self.B * self.T * int(self.s.dim)):
             raise ArgumentError(f"queries must be a contiguous float32 tensor of {self.B} x {self.T} x {int(self.s.dim)} "
                                 f"elements on {self.dev}, got {getattr(Qdev, 'dtype', type(Qdev))} "
                                 f"{tuple(getattr(Qdev, 'shape', ()))} on {getattr(Qdev, 'device', '?')}")
 
-    def _check_cursors(self, after):
+    def _check_cursors(self, after, _B=None):
         """The cursor arrays go to the kernels as bare pointers, like the queries: a pair of contiguous tensors, float32[B] and
         int64[B], on this device, or refused."""
         import torch
         from ._lib import ArgumentError
-        ok = isinstance(after, (tuple, list)) and len(after) == 2
-        for t, dtype in zip(after if ok else (), (torch.float32, torch.int64)):
-            ok = ok and (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == self.dev and t.is_contiguous()
-                         and t.dim() == 1 and t.numel() == self.B)
-        if not ok:
+        if not (isinstance(after, (tuple, list)) and len(after) == 2 and self._fits(after[0], torch.float32, self.B)
+                and self._fits(after[1], torch.int64, self.B)):
             raise ArgumentError(f"after must be a pair of contiguous tensors on {self.dev}: scores float32[{self.B}] and pids "
                                 f"int64[{self.B}]")
         return tuple(after)
 
-    def _check_lists(self, candidates, candidate_scores):
+    def _check_lists(self, candidates, candidate_scores, _B=None):
         """The candidate lists go to the kernels as bare pointers, like the queries: a pair of contiguous tensors on this device,
         pids int64 [B, L] (L >= 1) and lens int64 [B] -- and, when given, candidate_scores float32 [B, L] -- or refused."""
         import torch
         from ._lib import ArgumentError
-
-        def ok(t, dtype, shape):
-            return (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == self.dev and t.is_contiguous()
-                    and tuple(t.shape) == shape)
-        pair = isinstance(candidates, (tuple, list)) and len(candidates) == 2
-        L = int(candidates[0].shape[1]) if pair and isinstance(candidates[0], torch.Tensor) and candidates[0].dim() == 2 else 0
-        if not (pair and L >= 1 and ok(candidates[0], torch.int64, (self.B, L)) and ok(candidates[1], torch.int64, (self.B,))):
+        if not (isinstance(candidates, (tuple, list)) and len(candidates) == 2 and self._fits(candidates[0], torch.int64, self.B, None)
+                and candidates[0].shape[1] >= 1 and self._fits(candidates[1], torch.int64, self.B)):
             raise ArgumentError(f"candidates must be a pair of contiguous tensors on {self.dev}: pids int64[{self.B}, L] (L >= 1) "
                                 f"and lens int64[{self.B}]")
-        if candidate_scores is not None and not ok(candidate_scores, torch.float32, (self.B, L)):
+        L = int(candidates[0].shape[1])
+        if candidate_scores is not None and not self._fits(candidate_scores, torch.float32, self.B, L):
             raise ArgumentError(f"candidate_scores must be a contiguous float32[{self.B}, {L}] tensor on {self.dev}")
         return candidates[0], candidates[1], L, candidate_scores, False
 
-    def _check_list_priors(self, candidate_priors, lists):
+    def _check_list_priors(self, candidate_priors, lists, _B=None):
         """The list priors go to the kernels as a bare pointer beside the lists: a contiguous float32 [B, L] tensor on this
         device, or refused.  Nothing is read back: the largest |value| the weight is checked against is 0 (a value whose
         product with the weight is not finite counts as 0 on the device)."""
         import torch
         from ._lib import ArgumentError
-        L = lists[2]
-        t = candidate_priors
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.dev and t.is_contiguous()
-                and tuple(t.shape) == (self.B, L)):
-            raise ArgumentError(f"candidate_priors must be a contiguous float32[{self.B}, {L}] tensor on {self.dev}")
-        return t, 0.0
+        if not self._fits(candidate_priors, torch.float32, self.B, lists[2]):
+            raise ArgumentError(f"candidate_priors must be a contiguous float32[{self.B}, {lists[2]}] tensor on {self.dev}")
+        return candidate_priors, 0.0
 
-    def _request(self, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0, after=None,
-                 group_base: int = 0, candidates=None, candidate_scores=None, candidate_priors=None):
-        """The clb_search_request of a call of this shard (searcher.search_request), its cursors as device tensors.  A call
-        without keywords takes the request made at construction: it has nothing to check and nothing to point at."""
-        if (filters is None and grouping is None and per_group is None and prior is None and after is None
-                and scope == "candidates" and candidates is None and candidate_scores is None and candidate_priors is None):
+    def _request(self, kw: SearchKeywords, group_base: int = 0):
+        """The clb_search_request of a call of this shard (searcher.search_request), its cursors and lists as device tensors.
+        A call without keywords takes the request made at construction: it has nothing to check and nothing to point at."""
+        if kw.plain:
             return self._plain
-        return search_request(self.s, self.B, filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
-                              prior_weight=prior_weight, after=after, group_base=group_base,
-                              cursor_arrays=lambda cursors, _B: self._check_cursors(cursors), candidates=candidates,
-                              candidate_scores=candidate_scores,
-                              candidate_arrays=lambda lists, scores, _B: self._check_lists(lists, scores),
-                              candidate_priors=candidate_priors,
-                              candidate_prior_arrays=lambda values, lists, _B: self._check_list_priors(values, lists))
+        return search_request(self.s, self.B, keywords=kw, group_base=group_base, cursor_arrays=self._check_cursors,
+                              candidate_arrays=self._check_lists, candidate_prior_arrays=self._check_list_priors)
 
     def _stream(self) -> int:
         return self._current_stream(self.dev).cuda_stream
@@ -356,10 +346,14 @@ class DeviceSearch:
         (clb_search_batch_request_device_slot with the grouping; with `prior` / `prior_weight`, this shard's PassagePrior and
         the group's weight, in the same request), then the global group index of every result and the edge groups of every
         query (clb_search_result_groups_slot), all into the packed grouped block, which is returned.  B <= 64."""
+        return self._grouped_shard(
+            Qdev, SearchKeywords(filters=filters, scope=scope, grouping=grouping, prior=prior, prior_weight=prior_weight), group_base)
+
+    def _grouped_shard(self, Qdev, kw: SearchKeywords, group_base: int):
         self._check_queries(Qdev)
         block = self._grouped_block()
-        gh = self.s._grouping_handle(grouping)
-        req = self._request(filters=filters, scope=scope, grouping=grouping, prior=prior, prior_weight=prior_weight)
+        gh = self.s._grouping_handle(kw.grouping)
+        req = self._request(kw)
         st = self._stream()
         check(self._search(
             self.s._h, self.slot, Qdev.data_ptr(), self.T, self.B, self.nprobe, self.k, req, self.g_out_p.data_ptr(),
@@ -380,24 +374,30 @@ class DeviceSearch:
         the published scores are the BOOSTED approximate scores, and the call returns (local_top, local_gid or None,
         local_mabs): local_mabs [B] float32 is the shard's largest boosted approximate score by magnitude per query, to be
         all-gathered with the others (phase 2 forms its rounding slack from the maximum over the shards)."""
+        top, gid, mabs = self._phase1_outputs(
+            Qdev, SearchKeywords(filters=filters, scope=scope, grouping=grouping, prior=prior, prior_weight=prior_weight), group_base)
+        if mabs is not None:
+            return top, gid, mabs
+        return top if gid is None else (top, gid)
+
+    def _phase1_outputs(self, Qdev, kw: SearchKeywords, group_base: int = 0):
+        """phase1 with its keywords as the record -> always (local_top, local_gid or None, local_mabs or None): gid with a
+        grouping, mabs with a prior."""
         import torch
         self._check_queries(Qdev)
-        req = self._request(filters=filters, scope=scope, grouping=grouping, prior=prior, prior_weight=prior_weight,
-                            group_base=group_base)
+        req = self._request(kw, group_base)
         if not hasattr(self, "local_top"):
             self.local_top = torch.empty((self.B, self.k), dtype=torch.float32, device=self.dev)
-        if grouping is not None and not hasattr(self, "local_gid"):
+        if kw.grouping is not None and not hasattr(self, "local_gid"):
             self.local_gid = torch.empty((self.B, self.k), dtype=torch.int64, device=self.dev)
-        if prior is not None and not hasattr(self, "local_mabs"):
+        if kw.prior is not None and not hasattr(self, "local_mabs"):
             self.local_mabs = torch.zeros(self.B, dtype=torch.float32, device=self.dev)
-        gid = self.local_gid if grouping is not None else None
-        mabs = self.local_mabs if prior is not None else None
+        gid = self.local_gid if kw.grouping is not None else None
+        mabs = self.local_mabs if kw.prior is not None else None
         check(self._phase1(
             self.s._h, self.slot, Qdev.data_ptr(), self.T, self.B, self.nprobe, self.k, req, self.local_top.data_ptr(),
             None if gid is None else gid.data_ptr(), None if mabs is None else mabs.data_ptr(), self._stream()))
-        if prior is not None:
-            return self.local_top, gid, mabs
-        return self.local_top if gid is None else (self.local_top, gid)
+        return self.local_top, gid, mabs
 
     def phase2(self, Qdev, all_top, all_gid=None, grouping=None, group_base: int = 0, prior=None, prior_weight=1.0,
                all_mabs=None):
@@ -411,20 +411,16 @@ class DeviceSearch:
         import torch
         from ._lib import ArgumentError
         self._check_queries(Qdev)
-        if (all_top.dtype != torch.float32 or all_top.dim() != 3 or tuple(all_top.shape[1:]) != (self.B, self.k)
-                or not all_top.is_contiguous() or all_top.device != self.dev):
+        if not self._fits(all_top, torch.float32, None, self.B, self.k):
             raise ArgumentError(f"all_top must be a contiguous float32 (n_shards, {self.B}, {self.k}) tensor on {self.dev}")
         g = grouping is not None
         if g:
-            if (all_gid is None or all_gid.dtype != torch.int64 or all_gid.shape != all_top.shape or not all_gid.is_contiguous()
-                    or all_gid.device != self.dev):
+            if not self._fits(all_gid, torch.int64, *all_top.shape):
                 raise ArgumentError(f"all_gid must be a contiguous int64 tensor of all_top's shape on {self.dev}")
             block = self._grouped_block()
-        req = self._request(grouping=grouping, prior=prior, prior_weight=prior_weight, group_base=group_base)
-        if prior is not None:
-            if (all_mabs is None or all_mabs.dtype != torch.float32 or tuple(all_mabs.shape) != (all_top.shape[0], self.B)
-                    or not all_mabs.is_contiguous() or all_mabs.device != self.dev):
-                raise ArgumentError(f"all_mabs must be a contiguous float32 (n_shards, {self.B}) tensor on {self.dev}")
+        req = self._request(SearchKeywords(grouping=grouping, prior=prior, prior_weight=prior_weight), group_base)
+        if prior is not None and not self._fits(all_mabs, torch.float32, all_top.shape[0], self.B):
+            raise ArgumentError(f"all_mabs must be a contiguous float32 (n_shards, {self.B}) tensor on {self.dev}")
         out_p, out_s, ncand = (self.g_out_p, self.g_out_s, self.g_ncand) if g else (self.out_p, self.out_s, self.ncand)
         check(self._phase2(
             self.s._h, self.slot, Qdev.data_ptr(), self.T, self.B, self.nprobe, self.k, req, all_top.data_ptr(),
@@ -451,6 +447,11 @@ class DeviceSearch:
         their ADDRESSES too -- to re-rank under a graph, write the next batch's pids and lengths into the same tensors and
         replay (the sizing pass grows the slot for this stride; a larger stride needs a new capture).  `candidate_priors`
         likewise: the graph holds the ADDRESS of the value block and the weight -- write the next batch's values beside its pids."""
+        return self._capture(Qstatic, SearchKeywords(
+            filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior, prior_weight=prior_weight, after=after,
+            candidates=candidates, candidate_scores=candidate_scores, candidate_priors=candidate_priors))
+
+    def _capture(self, Qstatic, kw: SearchKeywords):
         import torch
         self._check_queries(Qstatic)
         self.generation = self.s.generation
@@ -458,13 +459,11 @@ class DeviceSearch:
         side = torch.cuda.Stream(self.dev)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after, candidates, candidate_scores,
-                 candidate_priors)
+            self._run(Qstatic, kw)
         cur.wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self(Qstatic, filters, scope, grouping, per_group, prior, prior_weight, after, candidates, candidate_scores,
-                 candidate_priors)
+            self._run(Qstatic, kw)
         return graph
 
     def __call__(self, Qdev, filters=None, scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0,
@@ -492,13 +491,16 @@ class DeviceSearch:
         prior_weight * the value beside a passage's first occurrence (Searcher.search_batch).  Nothing is raised about the
         values: one that is not finite, or whose product with the weight is not finite, counts as 0.  Not with `prior`,
         `per_group` > 1 or `after`."""
+        return self._run(Qdev, SearchKeywords(
+            filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior, prior_weight=prior_weight, after=after,
+            candidates=candidates, candidate_scores=candidate_scores, candidate_priors=candidate_priors))
+
+    def _run(self, Qdev, kw: SearchKeywords):
         import torch
         self._check_queries(Qdev)
-        req = self._request(filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
-                            prior_weight=prior_weight, after=after, candidates=candidates, candidate_scores=candidate_scores,
-                            candidate_priors=candidate_priors)
+        req = self._request(kw)
         out_p, out_s = self.out_p, self.out_s
-        if per_group is not None:
+        if kw.per_group is not None:
             m = int(req.per_group)
             if getattr(self, "hit_p", None) is None or self.hit_p.shape[2] != m:
                 self.hit_p = torch.zeros((self.B, self.k, m), dtype=torch.int64, device=self.dev)

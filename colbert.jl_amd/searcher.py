@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass, replace
 from typing import Optional
 
 import numpy as np
@@ -40,18 +41,14 @@ def _per_group(per_group, grouping) -> int:
     return int(per_group)
 
 
-class PassageFilter:
-    """A set of passages resident in HBM as one bitmap (clb_filter, include/colbert_hip.h): made once by
-    `Searcher.make_filter`, reused over any number of searches of that searcher.  Keep it alive while a search that uses
-    it may still be running (or a graph that captured it may be replayed)."""
-
-    def __init__(self, searcher: "Searcher", handle, count: int):
-        self.searcher, self._h, self.count = searcher, handle, int(count)
+class Owned:
+    """Owns one resource and closes it once: `close()` (any number of times), the end of a `with` block, or collection --
+    also of an object whose constructor raised half way.  A subclass names `_release()`; `len()` is its `count`."""
+    closed = False
 
     def close(self):
-        if getattr(self, "_h", None):
-            lib().clb_filter_destroy(self._h)
-            self._h = None
+        self.closed = True
+        self._release()
 
     def __enter__(self):
         return self
@@ -69,11 +66,31 @@ class PassageFilter:
         return self.count
 
 
-class PassageGrouping:
+class ResidentHandle(Owned):
+    """An Owned library handle `_h` of one searcher; `_destroy` names the entry point that frees it."""
+
+    def _release(self):
+        if getattr(self, "_h", None):
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+
+class PassageFilter(ResidentHandle):
+    """A set of passages resident in HBM as one bitmap (clb_filter, include/colbert_hip.h): made once by
+    `Searcher.make_filter`, reused over any number of searches of that searcher.  Keep it alive while a search that uses
+    it may still be running (or a graph that captured it may be replayed)."""
+    _destroy = "clb_filter_destroy"
+
+    def __init__(self, searcher: "Searcher", handle, count: int):
+        self.searcher, self._h, self.count = searcher, handle, int(count)
+
+
+class PassageGrouping(ResidentHandle):
     """A map passage -> group (document) resident in HBM (clb_grouping, include/colbert_hip.h): made once by
     `Searcher.make_grouping`, reused over any number of grouped searches of that searcher.  Immutable; valid across
     `remove_passages` and `update_*`, not across an append (make another).  Keep it alive while a search that uses it may
     still be running (or a graph that captured it may be replayed).  `count`: the number of groups."""
+    _destroy = "clb_grouping_destroy"
 
     def __init__(self, searcher: "Searcher", handle, count: int, group_ids: np.ndarray):
         self.searcher, self._h, self.count = searcher, handle, int(count)
@@ -88,59 +105,20 @@ class PassageGrouping:
                               "(pid 0 pads a short result: cut the result at n_candidates first)")
         return self._ids[p - 1]
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().clb_grouping_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __len__(self):
-        return self.count
-
 
 FLT_MAX = float(np.finfo(np.float32).max)
 
 
-class PassagePrior:
+class PassagePrior(ResidentHandle):
     """One finite fp32 value per passage resident in HBM (clb_prior, include/colbert_hip.h): made once by
     `Searcher.make_prior`, reused over any number of searches of that searcher (`prior=`, `prior_weight=`: rank by
     MaxSim + prior_weight * value).  Immutable; valid across `remove_passages` and `update_*`, not across an append (make
     another).  Keep it alive while a search that uses it may still be running (or a graph that captured it may be
-    replayed).  `max_abs`: the largest |value|; `len()`: the number of values."""
+    replayed).  `max_abs`: the largest |value|; `count`, `len()`: the number of values."""
+    _destroy = "clb_prior_destroy"
 
     def __init__(self, searcher: "Searcher", handle, n: int, max_abs: float):
-        self.searcher, self._h, self._n, self.max_abs = searcher, handle, int(n), float(max_abs)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().clb_prior_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __len__(self):
-        return self._n
+        self.searcher, self._h, self.count, self.max_abs = searcher, handle, int(n), float(max_abs)
 
 
 def _prior_weight(prior, prior_weight, per_group) -> float:
@@ -228,6 +206,55 @@ def _candidate_prior_keywords(candidate_priors, candidates, prior=None, per_grou
     if after is not None:
         raise Unsupported("after together with candidate_priors is not supported: a cursor continues the ranking of passages "
                           "by MaxSim")
+
+
+def _one_cursor(after):
+    """The `after=(score, pid)` of a one-query call as the pair of one-element arrays search_batch takes."""
+    from ._lib import ArgumentError
+    if not isinstance(after, (tuple, list)) or len(after) != 2:
+        raise ArgumentError("after must be a pair (score, pid)")
+    return ([after[0]], [after[1]])
+
+
+@dataclass(frozen=True)
+class SearchKeywords:
+    """The keywords of one search call (Searcher.search_batch describes each), in DeviceSearch's positional order.  Every
+    public search method makes one from its own parameters; below that only the record travels, down to search_request.
+    `candidate_scores`: where a call returns the list scores, whether it is to (`return_candidate_scores`); on the device
+    route, the tensor they go to."""
+    filters: object = None
+    scope: object = "candidates"
+    grouping: object = None
+    per_group: object = None
+    prior: object = None
+    prior_weight: object = 1.0
+    after: object = None
+    candidates: object = None
+    candidate_scores: object = None
+    candidate_priors: object = None
+
+    def check(self):
+        """The keywords against each other, before anything is looked at more closely: the scope, then what `after`,
+        `candidates` and `candidate_priors` are not offered with."""
+        _scope_code(self.scope)
+        _after_keywords(self.after, self.grouping, self.per_group, self.prior)
+        _candidate_keywords(self.candidates, self.filters, self.candidate_scores is not None and self.candidate_scores is not False)
+        _candidate_prior_keywords(self.candidate_priors, self.candidates, self.prior, self.per_group, self.after)
+
+    @property
+    def plain(self) -> bool:
+        """No keyword is given: every field is at its default.  Spelled out, not looped, because DeviceSearch asks on every
+        call; tests/test_search_keywords_cpu.py walks the fields, so one that is missing here fails there."""
+        return (self.filters is None and self.scope == "candidates" and self.grouping is None and self.per_group is None
+                and self.prior is None and self.prior_weight == 1.0 and self.after is None and self.candidates is None
+                and self.candidate_scores is None and self.candidate_priors is None)
+
+    def for_one_query(self) -> "SearchKeywords":
+        """The keywords of a one-query call (`filter=`, `after=(score, pid)`, one list of candidates and of their priors) as
+        those of a batch of one."""
+        one = lambda v: None if v is None else [v]
+        return replace(self, filters=one(self.filters), after=None if self.after is None else _one_cursor(self.after),
+                       candidates=one(self.candidates), candidate_priors=one(self.candidate_priors))
 
 
 def _float32_list(a, what: str) -> np.ndarray:
@@ -320,8 +347,9 @@ def _candidate_arrays(candidates, want_scores, B: int):
 def search_request(searcher, B: int, *, filters=None, scope="candidates", grouping=None, per_group=None, prior=None,
                    prior_weight=1.0, after=None, pad_short=False, group_base: int = 0, cursor_arrays=_after_arrays,
                    candidates=None, candidate_scores=None, candidate_arrays=_candidate_arrays, candidate_priors=None,
-                   candidate_prior_arrays=_candidate_prior_arrays) -> SearchRequest:
-    """The keywords of a search call of `searcher` over B queries, checked on the host, as the clb_search_request every
+                   candidate_prior_arrays=_candidate_prior_arrays, keywords: Optional[SearchKeywords] = None) -> SearchRequest:
+    """The keywords of a search call of `searcher` over B queries -- by name, or as the ready-made record `keywords`, which then
+    counts alone -- checked on the host, as the clb_search_request every
     search entry point takes (include/colbert_hip.h).  Raises what the helpers above raise, in their order: scope, `after`
     against the keywords it is not offered with, the cursors, the prior and its weight (never with `per_group`), `per_group`,
     the filters, the grouping.  With filters or cursors the host route always pads.  `cursor_arrays(after, B)` gives the two cursor
@@ -335,36 +363,36 @@ def search_request(searcher, B: int, *, filters=None, scope="candidates", groupi
     `per_group` > 1 or `after` (Unsupported); `candidate_prior_arrays(candidate_priors, lists, B)` gives (values, max_abs) -- the
     host block here, checked value by value, the device tensor from DeviceSearch with max_abs 0 (nothing is read back) -- and
     the weight is checked against that max_abs as a prior's is."""
-    _scope_code(scope)
-    _candidate_keywords(candidates, filters, candidate_scores is not None and candidate_scores is not False)
-    _candidate_prior_keywords(candidate_priors, candidates, prior, per_group, after)
-    r = SearchRequest(struct_bytes=C.sizeof(SearchRequest), scope=_scope_code(scope), group_base=int(group_base),
-                      pad_short=1 if (pad_short or filters is not None or after is not None or candidates is not None) else 0)
+    kw = keywords if keywords is not None else SearchKeywords(
+        filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior, prior_weight=prior_weight, after=after,
+        candidates=candidates, candidate_scores=candidate_scores, candidate_priors=candidate_priors)
+    kw.check()
+    r = SearchRequest(struct_bytes=C.sizeof(SearchRequest), scope=_scope_code(kw.scope), group_base=int(group_base),
+                      pad_short=1 if (pad_short or kw.filters is not None or kw.after is not None or kw.candidates is not None) else 0)
     r.lists = None
-    if candidates is not None:
-        r.lists = tuple(candidate_arrays(candidates, candidate_scores, B))
-        ptr = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+    ptr = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+    if kw.candidates is not None:
+        r.lists = tuple(candidate_arrays(kw.candidates, kw.candidate_scores, B))
         r.list_pids, r.list_lens, r.list_stride, r.list_scores = ptr(r.lists[0]), ptr(r.lists[1]), int(r.lists[2]), ptr(r.lists[3])
-        if candidate_priors is not None:
-            values, max_abs = candidate_prior_arrays(candidate_priors, r.lists, B)
-            r.prior_weight = _weight_value(prior_weight, max_abs)
+        if kw.candidate_priors is not None:
+            values, max_abs = candidate_prior_arrays(kw.candidate_priors, r.lists, B)
+            r.prior_weight = _weight_value(kw.prior_weight, max_abs)
             r.list_prior = ptr(values)
             r.lists += (values,)
     cursors = ()
-    if after is not None:
-        _after_keywords(after, grouping, per_group, prior)
-        cursors = tuple(cursor_arrays(after, B))
-        r.after_scores, r.after_pids = (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data for a in cursors)
-    if prior is not None:
-        r.prior_weight = _prior_weight(prior, prior_weight, per_group)
-        r.prior = prior._h
-    if per_group is not None:
-        r.per_group = _per_group(per_group, grouping)
-    handles = None if filters is None else searcher._filter_handles(filters, B)
+    if kw.after is not None:
+        cursors = tuple(cursor_arrays(kw.after, B))
+        r.after_scores, r.after_pids = (ptr(a) for a in cursors)
+    if kw.prior is not None:
+        r.prior_weight = _prior_weight(kw.prior, kw.prior_weight, kw.per_group)
+        r.prior = kw.prior._h
+    if kw.per_group is not None:
+        r.per_group = _per_group(kw.per_group, kw.grouping)
+    handles = None if kw.filters is None else searcher._filter_handles(kw.filters, B)
     if handles is not None:
         r.filters = handles
-    if grouping is not None:
-        r.grouping = searcher._grouping_handle(grouping)
+    if kw.grouping is not None:
+        r.grouping = searcher._grouping_handle(kw.grouping)
     r._keep = (handles, cursors)
     return r
 
@@ -809,44 +837,27 @@ class Searcher:
         pid at its position.  Not with `filter`.
         `candidate_priors` (one array of values, one per listed pid) with `prior_weight`: rank the listed passages by score +
         prior_weight * value (Searcher.search_batch); not with `prior`, `per_group` > 1 or `after`."""
+        return self._search_embeddings(Q, k, nprobe, SearchKeywords(
+            filters=filter, scope=scope, grouping=grouping, per_group=per_group, prior=prior, prior_weight=prior_weight, after=after,
+            candidates=candidates, candidate_scores=True if return_candidate_scores else None, candidate_priors=candidate_priors))
+
+    def _search_embeddings(self, Q, k: int, nprobe, kw: SearchKeywords):
+        """search_embeddings with its keywords as the record of a ONE-QUERY call (`filters`: the filter)."""
         q = colmajor(Q, np.float32)
         if q.ndim != 2 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T)")
-        _scope_code(scope)
-        _after_keywords(after, grouping, per_group, prior)
-        _candidate_keywords(candidates, None if filter is None else [filter], return_candidate_scores)
-        _candidate_prior_keywords(candidate_priors, candidates, prior, per_group, after)
-        if candidates is not None:
-            out = self.search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe, scope=scope, grouping=grouping,
-                                    per_group=per_group, prior=prior, prior_weight=prior_weight,
-                                    after=None if after is None else self._one_cursor(after), candidates=[candidates],
-                                    return_candidate_scores=return_candidate_scores,
-                                    candidate_priors=None if candidate_priors is None else [candidate_priors])
-            self.last_num_candidates = int(out[2][0])
-            one = (np.asfortranarray(out[0][..., 0]), np.asfortranarray(out[1][..., 0]))
-            return one + (out[3][0],) if return_candidate_scores else one
-        if after is not None:
-            after = self._one_cursor(after)
-        if filter is not None or grouping is not None or per_group is not None or prior is not None or after is not None:
-            p, s, n = self.search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe,
-                                        filters=None if filter is None else [filter], scope=scope, grouping=grouping,
-                                        per_group=per_group, prior=prior, prior_weight=prior_weight, after=after)
-            self.last_num_candidates = int(n[0])
-            return np.asfortranarray(p[..., 0]), np.asfortranarray(s[..., 0])
-        pids = np.zeros(k, dtype=np.int64); scores = np.zeros(k, dtype=np.float32)
-        ncand = i64(0)
-        check(lib().clb_search(self._h, fptr(q), i64(q.shape[1]), i64(nprobe or self.config.nprobe), i64(k), fptr(pids),
-                               fptr(scores), C.byref(ncand)))
-        self.last_num_candidates = ncand.value
-        return pids, scores
-
-    @staticmethod
-    def _one_cursor(after):
-        """The `after=(score, pid)` of a one-query call as the pair of one-element arrays search_batch takes."""
-        from ._lib import ArgumentError
-        if not isinstance(after, (tuple, list)) or len(after) != 2:
-            raise ArgumentError("after must be a pair (score, pid)")
-        return ([after[0]], [after[1]])
+        kw.check()
+        if kw.plain:                               # clb_search: the call the reference makes, short results included
+            pids = np.zeros(k, dtype=np.int64); scores = np.zeros(k, dtype=np.float32)
+            ncand = i64(0)
+            check(lib().clb_search(self._h, fptr(q), i64(q.shape[1]), i64(nprobe or self.config.nprobe), i64(k), fptr(pids),
+                                   fptr(scores), C.byref(ncand)))
+            self.last_num_candidates = ncand.value
+            return pids, scores
+        out = self._search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe, False, kw.for_one_query())
+        self.last_num_candidates = int(out[2][0])
+        one = (np.asfortranarray(out[0][..., 0]), np.asfortranarray(out[1][..., 0]))
+        return one + (out[3][0],) if kw.candidate_scores else one
 
     def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
                      scope="candidates", grouping=None, per_group=None, prior=None, prior_weight=1.0, after=None,
@@ -890,19 +901,23 @@ class Searcher:
         holds v for the listed passages and 0 elsewhere, without a handle and per query.  Values must be finite and keep
         |prior_weight| * max|value| below FLT_MAX (ArgumentError, naming the query and the position).  Composes with
         `grouping` (`per_group=1` included); not with `prior`, `per_group` > 1 or `after` (Unsupported)."""
+        return self._search_batch(Q, k, nprobe, pad_short, SearchKeywords(
+            filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior, prior_weight=prior_weight, after=after,
+            candidates=candidates, candidate_scores=True if return_candidate_scores else None, candidate_priors=candidate_priors))
+
+    def _search_batch(self, Q, k: int, nprobe, pad_short, kw: SearchKeywords):
+        """search_batch with its keywords as the record."""
         q = colmajor(Q, np.float32)
         if q.ndim != 3 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T, B)")
         B = q.shape[2]
-        req = search_request(self, B, filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
-                             prior_weight=prior_weight, after=after, pad_short=pad_short, candidates=candidates,
-                             candidate_scores=bool(return_candidate_scores), candidate_priors=candidate_priors)
-        shape = (k, B) if per_group is None else (int(req.per_group), k, B)
+        req = search_request(self, B, keywords=kw, pad_short=pad_short)
+        shape = (k, B) if kw.per_group is None else (int(req.per_group), k, B)
         pids = np.zeros(shape, dtype=np.int64, order="F"); scores = np.zeros(shape, dtype=np.float32, order="F")
         ncand = np.zeros(B, dtype=np.int64)
         check(request_entry("clb_search_batch_request")(self._h, fptr(q), q.shape[1], B, nprobe or self.config.nprobe, k, req,
                                                         fptr(pids), fptr(scores), fptr(ncand)))
-        if not return_candidate_scores:
+        if not kw.candidate_scores:
             return pids, scores, ncand
         _, lens, _, cs, ragged = req.lists[:5]
         return pids, scores, ncand, ([cs[:int(n), b].copy() for b, n in enumerate(lens)] if ragged else cs)
@@ -930,18 +945,17 @@ class Searcher:
     def search(self, query: str, k: int, *, filter=None, scope="candidates", grouping=None, per_group=None, prior=None,
                prior_weight=1.0, after=None, candidates=None, return_candidate_scores=False, candidate_priors=None):
         """search(searcher, query::String, k) (searching.jl:93-128); `filter` / `scope` / `grouping` / `per_group` / `prior` /
-        `prior_weight` / `after` / `candidates` / `return_candidate_scores` / `candidate_priors` as in search_embeddings."""
-        _scope_code(scope)
-        _after_keywords(after, grouping, per_group, prior)
-        _candidate_keywords(candidates, None if filter is None else [filter], return_candidate_scores)
-        _candidate_prior_keywords(candidate_priors, candidates, prior, per_group, after)
+        `prior_weight` / `after` / `candidates` / `return_candidate_scores` / `candidate_priors` as in search_embeddings.
+        Keywords that conflict are answered before a missing encoder is."""
+        kw = SearchKeywords(
+            filters=filter, scope=scope, grouping=grouping, per_group=per_group, prior=prior, prior_weight=prior_weight, after=after,
+            candidates=candidates, candidate_scores=True if return_candidate_scores else None, candidate_priors=candidate_priors)
+        kw.check()
         if self.encoder is None:
             raise ColBERTError("no query encoder attached: pass encoder=... or use search_embeddings(Q, k)")
         Q = self.encoder.encode_queries([query])
         assert Q.shape[2] == 1 and Q.shape[1] == self.config.query_maxlen, Q.shape
-        return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope, grouping=grouping, per_group=per_group,
-                                      prior=prior, prior_weight=prior_weight, after=after, candidates=candidates,
-                                      return_candidate_scores=return_candidate_scores, candidate_priors=candidate_priors)
+        return self._search_embeddings(Q[:, :, 0], k, None, kw)
 
     def text_search(self, k: int, nprobe: Optional[int] = None, graph: bool = True) -> "TextSearch":
         """A session for repeated `search(searcher, query::String, k)` calls with everything after the tokenizer on the
@@ -1165,17 +1179,14 @@ def search(searcher: Searcher, query, k: int, *, filter=None, scope="candidates"
     """The reference's exported `search` (src/ColBERT.jl:40).  `query` may be a string (needs an
     encoder) or a (dim, T) Float32 matrix of query embeddings.  `filter` / `scope` / `grouping` / `per_group` / `prior` /
     `prior_weight` / `after` / `candidates` / `return_candidate_scores` / `candidate_priors`: Searcher.search_embeddings."""
-    more = {} if after is None else {"after": after}      # (a ShardedSearcher answers a cursor with Unsupported itself)
-    if candidates is not None or return_candidate_scores:  # (... and candidate lists likewise)
+    # `searcher` may be a ShardedSearcher or any object with these two methods: it always gets the four keywords below, and
+    # each later one only when the caller gave it (a ShardedSearcher answers a cursor or candidate lists with Unsupported itself)
+    more = {} if prior is None and prior_weight == 1.0 else {"prior": prior, "prior_weight": prior_weight}
+    if after is not None:
+        more.update(after=after)
+    if candidates is not None or return_candidate_scores:
         more.update(candidates=candidates, return_candidate_scores=return_candidate_scores)
-    if candidate_priors is not None:                       # (... and their values; a weight other than 1 travels below)
+    if candidate_priors is not None:
         more.update(candidate_priors=candidate_priors)
-    if prior is None and prior_weight == 1.0:      # (a call without a prior hands over the keywords it always has)
-        if isinstance(query, str):
-            return searcher.search(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group, **more)
-        return searcher.search_embeddings(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group, **more)
-    if isinstance(query, str):
-        return searcher.search(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
-                               prior_weight=prior_weight, **more)
-    return searcher.search_embeddings(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group, prior=prior,
-                                      prior_weight=prior_weight, **more)
+    call = searcher.search if isinstance(query, str) else searcher.search_embeddings
+    return call(query, k, filter=filter, scope=scope, grouping=grouping, per_group=per_group, **more)

@@ -34,7 +34,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._lib import ArgumentError, BoundsError, ColBERTError, Unsupported, check, colmajor, fptr, i64, lib
-from .searcher import PassageFilter, _no_prior_hits, _scope_code, _weight_value
+from .searcher import Owned, PassageFilter, SearchKeywords, _no_prior_hits, _scope_code, _weight_value
 
 _PROTOCOLS = ("auto", "two_phase", "single")
 _PIECE = 64          # queries per exchange: a filtered phase 1 carries at most 64 filter handles (include/colbert_hip.h)
@@ -136,7 +136,15 @@ def slice_groups(group_ids, bounds):
     return parts, bases
 
 
-class ShardedGrouping:
+class ShardedParts(Owned):
+    """One resident handle per local shard (`parts`), owned by a handle over the whole shard group (`group`)."""
+
+    def _release(self):
+        for part in getattr(self, "parts", ()):
+            part.close()
+
+
+class ShardedGrouping(ShardedParts):
     """A passage -> group (document) map over a shard group: one resident PassageGrouping per local shard (`parts`), made
     from that shard's slice of the ids, and the `group_base` of each (`bases`).  Made by `ShardedSearcher.make_grouping`
     and refused by any other group.  `count` is the number of groups of the whole collection.  An append to the group
@@ -156,21 +164,8 @@ class ShardedGrouping:
                               "(pid 0 pads a short result: cut the result at n_candidates first)")
         return self._ids[p - 1]
 
-    def close(self):
-        for g in self.parts:
-            g.close()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __len__(self):
-        return self.count
-
-
-class ShardedPrior:
+class ShardedPrior(ShardedParts):
     """One finite fp32 value per passage of a shard group: one resident PassagePrior per local shard (`parts`), made from that
     shard's slice of the values by `ShardedSearcher.make_prior` and refused by any other group.  `max_abs` is the largest
     |value| over ALL shards of the group (every rank holds the same number): the weight of a search is checked against it.
@@ -178,24 +173,10 @@ class ShardedPrior:
 
     def __init__(self, group: "ShardedSearcher", parts, max_abs: float, n: int):
         self.group, self.parts, self.max_abs, self.num_docs = group, list(parts), float(max_abs), int(n)
-        self.closed = False
-
-    def close(self):
-        self.closed = True
-        for p in self.parts:
-            p.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __len__(self):
-        return self.num_docs
+        self.count = self.num_docs                 # len(): the number of values
 
 
-class ShardedFilter:
+class ShardedFilter(ShardedParts):
     """A passage set over a shard group: one resident PassageFilter per local shard (`parts`), made by
     `ShardedSearcher.make_filter` and refused by any other group.  `count` is the population over the whole group.  An append
     to the group invalidates it (the library refuses it: "filter made before an append; make another"); a removal does not."""
@@ -203,18 +184,20 @@ class ShardedFilter:
     def __init__(self, group: "ShardedSearcher", parts, count: int):
         self.group, self.parts, self.count = group, list(parts), int(count)
 
-    def close(self):
-        for f in self.parts:
-            f.close()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __len__(self):
-        return self.count
+def _refuse_single_handle_keywords(kw: SearchKeywords):
+    """What a single handle serves and a shard group does not: the hits of a grouped search, cursors, candidate lists.  The
+    first thing every search call of a group answers (with a prior the `per_group` refusal is the single handle's:
+    ShardedSearcher._check_prior)."""
+    if kw.per_group is not None and kw.prior is None:
+        raise Unsupported("per_group= (the best passages of every group) is not supported across a shard group: search "
+                          "the unsharded Searcher, or the winners' passages with a filter and scope='all'")
+    if kw.after is not None:
+        raise Unsupported("after= (search after a cursor) is not supported across a shard group: search the unsharded "
+                          "Searcher")
+    if kw.candidates is not None or kw.candidate_scores or kw.candidate_priors is not None:
+        raise Unsupported("candidates= (re-rank given passages) is not supported across a shard group: search the unsharded "
+                          "Searcher, or hand every shard's Searcher the lists (its device route skips another shard's pids)")
 
 
 class ShardedSearcher:
@@ -422,16 +405,17 @@ class ShardedSearcher:
             raise
         return ShardedPrior(self, parts, float(m), v.size)
 
-    def _check_prior(self, prior, prior_weight, per_group):
+    def _check_prior(self, kw: SearchKeywords):
         """`prior=` / `prior_weight=` of a search call -> (the ShardedPrior or None, the weight for every shard)."""
+        prior = kw.prior
         if prior is None:
             return None, 1.0
-        _no_prior_hits(per_group)
+        _no_prior_hits(kw.per_group)
         if not isinstance(prior, ShardedPrior) or prior.group is not self or prior.closed:
             raise ColBERTError("prior is not an open ShardedPrior of this shard group")
         if prior.num_docs != self.num_docs:
             raise ArgumentError("prior made before an append; make another")
-        return prior, _weight_value(prior_weight, prior.max_abs)      # against the GROUP's largest |value|
+        return prior, _weight_value(kw.prior_weight, prior.max_abs)      # against the GROUP's largest |value|
 
     # -- search -----------------------------------------------------------------------------------
     def _run(self, i: int, T: int, B: int, k: int, nprobe: int):
@@ -445,93 +429,60 @@ class ShardedSearcher:
         """every local shard runs the two-pass mode for queries of T tokens (set the mode alike on all ranks)"""
         return all(s.mode == 1 for s in self.shards) and T <= 32
 
-    def _piece_grouped(self, runs, Qd, B: int, k: int, filters, scope: str, two_phase: bool, grouping, prior=None, weight=1.0):
-        """_piece with a grouping: between the phases the shards' k best groups travel as (score, global group index); at the
-        end every shard's packed grouped block (pids, scores, group indices, candidate groups, edge groups) is gathered and
-        merged with one record per group."""
-        import torch
-        from .distributed import all_gather_packed, all_gather_scores, merge_grouped_packed, packed_grouped_bytes
-        L = len(self.shards)
-        dev0 = runs[0].dev
-        f = [None if filters is None else filters[i] for i in range(L)]
-        pr = [None if prior is None else prior.parts[i] for i in range(L)]
-        if two_phase:
-            outs = [r.phase1(Qd[i], f[i], scope, grouping.parts[i], grouping.bases[i], pr[i], weight) for i, r in enumerate(runs)]
-            top = torch.stack([o[0].to(dev0) for o in outs]).view(L * B, k)
-            gid = torch.stack([o[1].to(dev0) for o in outs]).view(L * B, k)
-            if self.group is not None:
-                top = self._gather_tensor(top, all_gather_scores)
-                gid = self._gather_tensor(gid, all_gather_scores)
-            top, gid = top.reshape(-1, B, k), gid.reshape(-1, B, k)
-            mabs = None if prior is None else self._gather_mabs([o[2] for o in outs], dev0, B)
-            blocks = [r.phase2(Qd[i], top.to(r.dev).contiguous(), gid.to(r.dev).contiguous(), grouping.parts[i], grouping.bases[i],
-                               pr[i], weight, None if mabs is None else mabs.to(r.dev).contiguous())
-                      for i, r in enumerate(runs)]
-        else:
-            blocks = [r.search_grouped_shard(Qd[i], f[i], scope, grouping.parts[i], grouping.bases[i], pr[i], weight)
-                      for i, r in enumerate(runs)]
-        block = torch.cat([x.to(dev0) for x in blocks])
-        g = self._gather_tensor(block, all_gather_packed) if self.group is not None else block.view(1, -1)
-        lists = g.to(dev0).contiguous().view(-1, packed_grouped_bytes(k, B))
-        mp, ms, n = merge_grouped_packed(lists, B, k)
-        return mp.cpu().numpy(), ms.cpu().numpy(), n.cpu().numpy()
-
-    def _gather_mabs(self, parts, dev0, B: int):
-        """The shards' largest boosted approximate scores by magnitude ([B] each) -> (n_shards, B) over the whole group: the
-        extra number per query and shard that travels between the phases of a search with a prior."""
+    def _gather_blocks(self, parts, dev0, cols: int):
+        """One tensor per local shard -> the blocks of every shard of the group in shard order, as rows of `cols` entries: what
+        travels between the phases (this process's blocks, then one all-gather)."""
         import torch
         from .distributed import all_gather_scores
-        m = torch.stack([p.to(dev0) for p in parts]).view(-1, 1)
-        if self.group is not None:
-            m = self._gather_tensor(m, all_gather_scores)
-        return m.reshape(-1, B)
+        t = torch.stack([p.to(dev0) for p in parts]).view(-1, cols)
+        return self._gather_tensor(t, all_gather_scores) if self.group is not None else t
 
     def _piece(self, q, k: int, nprobe: int, filters, scope: str, two_phase: bool, grouping=None, prior=None, weight=1.0):
-        """One exchange for the queries q (dim, T, B <= 64) -> (pids (B, k), scores (B, k), n_cand [B]) as numpy."""
+        """One exchange for the queries q (dim, T, B <= 64) -> (pids (B, k), scores (B, k), n_cand [B]) as numpy.
+        Two-phase: phase 1 on every local shard, then the shards' k largest approximate scores travel -- with a grouping they are
+        those of its k best groups and their global group indices travel beside them, with a prior they are boosted and each
+        shard's largest one by magnitude per query travels too -- and phase 2 takes exactly what travelled.  Single: every shard
+        runs its whole search.  Then one block per process is gathered and merged: with a grouping the shards' packed grouped
+        blocks (pids, scores, group indices, candidate groups, edge groups), merged with one record per group; without, the
+        shards' packed top-k lists and the candidate counts."""
         import torch
-        from .distributed import all_gather_packed, all_gather_scores, merge_packed, packed_topk_bytes
+        from .distributed import all_gather_packed, merge_grouped_packed, merge_packed, packed_grouped_bytes, packed_topk_bytes
         T, B = q.shape[1], q.shape[2]
         L = len(self.shards)
         host_q = torch.from_numpy(np.array(q.transpose(2, 1, 0), order="C"))            # (B, T, dim), a copy of the caller's
         runs = [self._run(i, T, B, k, nprobe) for i in range(L)]
         Qd = [host_q.to(r.dev) for r in runs]
-        if grouping is not None:
-            return self._piece_grouped(runs, Qd, B, k, filters, scope, two_phase, grouping, prior, weight)
-        if two_phase and prior is not None:
-            f = [None if filters is None else filters[i] for i in range(L)]
-            outs = [r.phase1(Qd[i], f[i], scope, prior=prior.parts[i], prior_weight=weight) for i, r in enumerate(runs)]
-            dev0 = runs[0].dev
-            local = torch.stack([o[0].to(dev0) for o in outs]).view(L * B, k)
-            if self.group is not None:
-                local = self._gather_tensor(local, all_gather_scores)
-            all_top = local.reshape(-1, B, k)
-            mabs = self._gather_mabs([o[2] for o in outs], dev0, B)
-            for i, r in enumerate(runs):
-                r.phase2(Qd[i], all_top.to(r.dev).contiguous(), prior=prior.parts[i], prior_weight=weight,
-                         all_mabs=mabs.to(r.dev).contiguous())
-        elif two_phase:
-            tops = [r.phase1(Qd[i], None if filters is None else filters[i], scope) for i, r in enumerate(runs)]
-            dev0 = runs[0].dev
-            local = torch.stack([t.to(dev0) for t in tops]).view(L * B, k)             # this process's blocks
-            if self.group is not None:
-                local = self._gather_tensor(local, all_gather_scores)                   # (world, L * B, k)
-            all_top = local.reshape(-1, B, k)
-            for i, r in enumerate(runs):
-                r.phase2(Qd[i], all_top.to(r.dev).contiguous())
+        dev0 = runs[0].dev
+        kws = [SearchKeywords(filters=None if filters is None else filters[i], scope=scope,
+                              grouping=None if grouping is None else grouping.parts[i],
+                              prior=None if prior is None else prior.parts[i], prior_weight=weight) for i in range(L)]
+        bases = [0] * L if grouping is None else grouping.bases
+        if two_phase:
+            outs = [r._phase1_outputs(Qd[i], kws[i], bases[i]) for i, r in enumerate(runs)]
+            top = self._gather_blocks([o[0] for o in outs], dev0, k).reshape(-1, B, k)
+            gid = None if grouping is None else self._gather_blocks([o[1] for o in outs], dev0, k).reshape(-1, B, k)
+            mabs = None if prior is None else self._gather_blocks([o[2] for o in outs], dev0, 1).reshape(-1, B)
+            on = lambda t, r: None if t is None else t.to(r.dev).contiguous()
+            blocks = [r.phase2(Qd[i], on(top, r), on(gid, r), kws[i].grouping, bases[i], kws[i].prior, weight, on(mabs, r))
+                      for i, r in enumerate(runs)]
+        elif grouping is not None:
+            blocks = [r._grouped_shard(Qd[i], kws[i], bases[i]) for i, r in enumerate(runs)]
         else:
             for i, r in enumerate(runs):
-                r(Qd[i], None if filters is None else filters[i], scope, prior=None if prior is None else prior.parts[i],
-                  prior_weight=weight)
-        # one block per process: its shards' packed top-k lists, then its candidate counts
-        dev0 = runs[0].dev
-        nbytes = packed_topk_bytes(k, B)
-        ncand = torch.stack([r.ncand.to(dev0) for r in runs]).sum(0)
-        block = torch.cat([r.packed.to(dev0) for r in runs] + [ncand.view(torch.uint8)])
-        g = self._gather_tensor(block, all_gather_packed) if self.group is not None else block.view(1, -1)
-        g = g.to(dev0)
-        lists = g[:, :L * nbytes].contiguous().view(-1, nbytes)
-        n = g[:, L * nbytes:].contiguous().view(torch.int64).view(-1, B).sum(0)
-        mp, ms = merge_packed(lists, B, k)
+                r._run(Qd[i], kws[i])
+        if grouping is not None:
+            block = torch.cat([x.to(dev0) for x in blocks])
+        else:
+            ncand = torch.stack([r.ncand.to(dev0) for r in runs]).sum(0)
+            block = torch.cat([r.packed.to(dev0) for r in runs] + [ncand.view(torch.uint8)])
+        g = (self._gather_tensor(block, all_gather_packed) if self.group is not None else block.view(1, -1)).to(dev0)
+        if grouping is not None:
+            mp, ms, n = merge_grouped_packed(g.contiguous().view(-1, packed_grouped_bytes(k, B)), B, k)
+        else:
+            nbytes = packed_topk_bytes(k, B)
+            lists = g[:, :L * nbytes].contiguous().view(-1, nbytes)
+            n = g[:, L * nbytes:].contiguous().view(torch.int64).view(-1, B).sum(0)
+            mp, ms = merge_packed(lists, B, k)
         return mp.cpu().numpy(), ms.cpu().numpy(), n.cpu().numpy()
 
     def search_batch(self, Q, k: int, nprobe: Optional[int] = None, pad_short: bool = False, *, filters=None,
@@ -555,18 +506,22 @@ class ShardedSearcher:
         `per_group`: anything but None raises Unsupported (the hits of a grouped search are a single handle's), and so does
         `after` (a cursor continues the ranking of a single handle), and so do `candidates` / `return_candidate_scores` /
         `candidate_priors` (candidate lists are a single handle's)."""
-        if prior is None:       # (with a prior the refusal is the single handle's: _check_prior)
-            self._no_per_group(per_group)
-        self._no_after(after)
-        self._no_candidates(candidates, return_candidate_scores, candidate_priors)
+        return self._search_batch(Q, k, nprobe, pad_short, protocol, SearchKeywords(
+            filters=filters, scope=scope, grouping=grouping, per_group=per_group, prior=prior, prior_weight=prior_weight, after=after,
+            candidates=candidates, candidate_scores=return_candidate_scores or None, candidate_priors=candidate_priors))
+
+    def _search_batch(self, Q, k: int, nprobe, pad_short, protocol, kw: SearchKeywords):
+        """search_batch with its keywords as the record."""
+        _refuse_single_handle_keywords(kw)
         q = colmajor(Q, np.float32)
         if q.ndim != 3 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T, B)")
         if protocol not in _PROTOCOLS:
             raise ColBERTError(f"protocol must be one of {_PROTOCOLS}, got {protocol!r}")
+        scope, filters = kw.scope, kw.filters
         _scope_code(scope)
-        grouping = self._check_grouping(grouping)
-        prior, weight = self._check_prior(prior, prior_weight, per_group)
+        grouping = self._check_grouping(kw.grouping)
+        prior, weight = self._check_prior(kw)
         k, B = int(k), q.shape[2]
         nprobe = int(nprobe or self.shards[0].config.nprobe)
         per_shard = self._shard_filters(filters, B)
@@ -586,39 +541,22 @@ class ShardedSearcher:
                 raise BoundsError(f"query {b} has {int(ncand[b])} candidate {what}, fewer than k={k}")
         return pids, scores, ncand
 
-    @staticmethod
-    def _no_per_group(per_group):
-        if per_group is not None:
-            raise Unsupported("per_group= (the best passages of every group) is not supported across a shard group: search "
-                              "the unsharded Searcher, or the winners' passages with a filter and scope='all'")
-
-    @staticmethod
-    def _no_after(after):
-        if after is not None:
-            raise Unsupported("after= (search after a cursor) is not supported across a shard group: search the unsharded "
-                              "Searcher")
-
-    @staticmethod
-    def _no_candidates(candidates, return_candidate_scores=False, candidate_priors=None):
-        if candidates is not None or return_candidate_scores or candidate_priors is not None:
-            raise Unsupported("candidates= (re-rank given passages) is not supported across a shard group: search the unsharded "
-                              "Searcher, or hand every shard's Searcher the lists (its device route skips another shard's pids)")
-
     def search_embeddings(self, Q, k: int, nprobe: Optional[int] = None, *, filter=None, scope="candidates", protocol="auto",
                           grouping=None, per_group=None, after=None, prior=None, prior_weight=1.0, candidates=None,
                           return_candidate_scores=False, candidate_priors=None):
         """One query, Q (dim, T) -> (pids Int64[k], scores Float32[k]) as `Searcher.search_embeddings`; the candidate count
         (with a grouping: the candidate groups) is left in `last_num_candidates`.  `prior` / `prior_weight`: search_batch."""
-        if prior is None:
-            self._no_per_group(per_group)
-        self._no_after(after)
-        self._no_candidates(candidates, return_candidate_scores, candidate_priors)
+        return self._search_embeddings(Q, k, nprobe, protocol, SearchKeywords(
+            filters=filter, scope=scope, grouping=grouping, per_group=per_group, prior=prior, prior_weight=prior_weight, after=after,
+            candidates=candidates, candidate_scores=return_candidate_scores or None, candidate_priors=candidate_priors))
+
+    def _search_embeddings(self, Q, k: int, nprobe, protocol, kw: SearchKeywords):
+        """search_embeddings with its keywords as the record of a ONE-QUERY call (`filters`: the filter)."""
+        _refuse_single_handle_keywords(kw)
         q = colmajor(Q, np.float32)
         if q.ndim != 2 or q.shape[0] != self.dim:
             raise ColBERTError(f"Q must be (dim={self.dim}, T)")
-        p, s, n = self.search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe,
-                                    filters=None if filter is None else [filter], scope=scope, protocol=protocol,
-                                    grouping=grouping, per_group=per_group, prior=prior, prior_weight=prior_weight)
+        p, s, n = self._search_batch(q.reshape(q.shape + (1,), order="F"), k, nprobe, False, protocol, kw.for_one_query())
         self.last_num_candidates = int(n[0])
         return np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(s[:, 0])
 
@@ -626,16 +564,15 @@ class ShardedSearcher:
                after=None, prior=None, prior_weight=1.0, candidates=None, return_candidate_scores=False,
                candidate_priors=None):
         """search(searcher, query::String, k) over the group, with the attached encoder."""
-        if prior is None:
-            self._no_per_group(per_group)
-        self._no_after(after)
-        self._no_candidates(candidates, return_candidate_scores, candidate_priors)
-        self._check_prior(prior, prior_weight, per_group)         # before the encoder runs
+        kw = SearchKeywords(
+            filters=filter, scope=scope, grouping=grouping, per_group=per_group, prior=prior, prior_weight=prior_weight, after=after,
+            candidates=candidates, candidate_scores=return_candidate_scores or None, candidate_priors=candidate_priors)
+        _refuse_single_handle_keywords(kw)
+        self._check_prior(kw)                                     # before the encoder runs
         if self.encoder is None:
             raise ColBERTError("no query encoder attached: pass encoder=... or use search_embeddings(Q, k)")
         Q = self.encoder.encode_queries([query])
-        return self.search_embeddings(Q[:, :, 0], k, filter=filter, scope=scope, protocol=protocol, grouping=grouping,
-                                      prior=prior, prior_weight=prior_weight)
+        return self._search_embeddings(Q[:, :, 0], k, None, protocol, kw)
 
     # -- append: to the LAST shard, the only range that can grow without colliding with a neighbour -------------------
     def _owns_last(self) -> bool:
