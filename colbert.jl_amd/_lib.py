@@ -156,6 +156,15 @@ def lib() -> C.CDLL:
             l.clb_search_batch_prior_device_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                              C.c_int64, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p,
                                                              C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(l, "clb_filter_combine"):                   # (absent from a COLBERT_HIP_LIB build of an earlier commit)
+            l.clb_filter_combine.restype = C.c_int
+            l.clb_filter_combine.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_void_p)]
+            l.clb_filter_create_range.restype = C.c_int
+            l.clb_filter_create_range.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_void_p)]
+            l.clb_filter_extend.restype = C.c_int
+            l.clb_filter_extend.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+            l.clb_filter_bitmap.restype = C.c_int
+            l.clb_filter_bitmap.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         if hasattr(l, "clb_search_batch_after"):               # (absent from a COLBERT_HIP_LIB build of an earlier commit)
             l.clb_search_batch_after.restype = C.c_int
             l.clb_search_batch_after.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,

@@ -10,6 +10,7 @@
 
 #include "approx_kernels.hpp"
 #include "after_kernels.hpp"
+#include "filter_kernels.hpp"
 #include "generic_kernels.hpp"
 #include "group_kernels.hpp"
 #include "index_change_kernels.hpp"
@@ -2826,6 +2827,92 @@ int clb_filter_create_bitmap(clb_searcher* s, const uint32_t* words, int64_t n_w
         CLB_HIP(hipStreamSynchronize(s->stream));
     }
     return filter_finish(s, std::move(f), out);
+}
+
+// ---- composing filters on the device (filter_kernels.hpp): each writes the words of a fresh bitmap on the searcher's stream
+// and ends in filter_finish, which clears the tail bits and counts with creation's one read-back
+static unsigned word_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+int clb_filter_combine(clb_searcher* s, int op, const clb_filter* const* operands, int64_t n, clb_filter** out) {
+    if (out) *out = nullptr;
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    if (!out) return fail(CLB_EARGUMENT, "out is null");
+    if (op < CLB_FILTER_OP_AND || op > CLB_FILTER_OP_NOT)
+        return fail(CLB_EARGUMENT, "op must be CLB_FILTER_OP_AND (0), _OR (1), _ANDNOT (2) or _NOT (3), got %d", op);
+    if (n < 1 || n > CLB_MAX_FILTER_OPERANDS)
+        return fail(CLB_EARGUMENT, "n must be 1..%d operands, got %lld", CLB_MAX_FILTER_OPERANDS, (long long)n);
+    if (op == CLB_FILTER_OP_NOT && n != 1)
+        return fail(CLB_EARGUMENT, "CLB_FILTER_OP_NOT takes n = 1 operand, got %lld", (long long)n);
+    if (!operands) return fail(CLB_EARGUMENT, "operands is null");
+    for (int64_t i = 0; i < n; ++i)
+        if (!operands[i]) return fail(CLB_EARGUMENT, "operand %lld is null", (long long)i);
+    for (int64_t i = 0; i < n; ++i) {         // check_filters' rules and wording, by operand
+        if (operands[i]->owner != s->serial)
+            return fail(CLB_EARGUMENT, "the filter of operand %lld was made for another searcher", (long long)i);
+        if (operands[i]->n_docs != s->n_docs)
+            return fail(CLB_EARGUMENT, "the filter of operand %lld: filter made before an append; make another", (long long)i);
+    }
+    FilterPtr f(nullptr, clb_filter_destroy);
+    CLB_TRY(filter_new(s, f));
+    const int W = (int)((s->n_docs + 31) / 32);
+    if (W > 0) {
+        FilterOperands ops = {};
+        ops.n = (int)n;
+        for (int64_t i = 0; i < n; ++i) ops.bits[i] = operands[i]->bits.as<uint32_t>();
+        hipLaunchKernelGGL(filter_combine_kernel, dim3(word_blocks(W)), dim3(256), 0, s->stream, ops, op, W, f->bits.as<uint32_t>());
+    }
+    return filter_finish(s, std::move(f), out);
+}
+
+int clb_filter_create_range(clb_searcher* s, const clb_prior* values, float lo, float hi, int flags, clb_filter** out) {
+    if (out) *out = nullptr;
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    if (!out) return fail(CLB_EARGUMENT, "out is null");
+    if (!values) return fail(CLB_EARGUMENT, "values is null: a range is taken over a clb_prior");
+    if (lo != lo) return fail(CLB_EARGUMENT, "lo is NaN");
+    if (hi != hi) return fail(CLB_EARGUMENT, "hi is NaN");
+    if (flags & ~(CLB_RANGE_LO_OPEN | CLB_RANGE_HI_OPEN))
+        return fail(CLB_EARGUMENT, "flags must be a combination of CLB_RANGE_LO_OPEN (1) and CLB_RANGE_HI_OPEN (2), got %d", flags);
+    CLB_TRY(check_prior(s, values, 0.f));     // this searcher's, made for the passages it holds now
+    FilterPtr f(nullptr, clb_filter_destroy);
+    CLB_TRY(filter_new(s, f));
+    const int W = (int)((s->n_docs + 31) / 32);
+    if (W > 0)
+        hipLaunchKernelGGL(filter_range_kernel, dim3(word_blocks(s->n_docs)), dim3(256), 0, s->stream,
+                           (const float*)values->values.as<float>(), (int)s->n_docs, lo, hi, flags & CLB_RANGE_LO_OPEN,
+                           flags & CLB_RANGE_HI_OPEN, W, f->bits.as<uint32_t>());
+    return filter_finish(s, std::move(f), out);
+}
+
+int clb_filter_extend(clb_searcher* s, const clb_filter* f_old, int fill, clb_filter** out) {
+    if (out) *out = nullptr;
+    if (!s) return fail(CLB_EARGUMENT, "null searcher");
+    if (!out) return fail(CLB_EARGUMENT, "out is null");
+    if (!f_old) return fail(CLB_EARGUMENT, "f is null");
+    if (fill != 0 && fill != 1) return fail(CLB_EARGUMENT, "fill must be 0 (appended passages out) or 1 (in), got %d", fill);
+    if (f_old->owner != s->serial) return fail(CLB_EARGUMENT, "the filter f was made for another searcher");
+    if (f_old->n_docs > s->n_docs)       // (a handle never loses passages: not reachable through this library)
+        return fail(CLB_EARGUMENT, "the filter f holds %lld passages, the searcher %lld", (long long)f_old->n_docs, (long long)s->n_docs);
+    FilterPtr f(nullptr, clb_filter_destroy);
+    CLB_TRY(filter_new(s, f));
+    const int W = (int)((s->n_docs + 31) / 32);
+    if (W > 0)
+        hipLaunchKernelGGL(filter_extend_kernel, dim3(word_blocks(W)), dim3(256), 0, s->stream,
+                           (const uint32_t*)f_old->bits.as<uint32_t>(), (int)f_old->n_docs, fill ? ~0u : 0u, W, f->bits.as<uint32_t>());
+    return filter_finish(s, std::move(f), out);
+}
+
+int clb_filter_bitmap(const clb_filter* f, uint32_t* words, int64_t n_words) {
+    if (!f) return fail(CLB_EARGUMENT, "f is null");
+    const int64_t W = (f->n_docs + 31) / 32;
+    if (n_words != W)
+        return fail(CLB_EARGUMENT, "n_words=%lld, the filter's bitmap has ceil(n_docs / 32) = %lld words", (long long)n_words, (long long)W);
+    if (W > 0 && !words) return fail(CLB_EARGUMENT, "words is null");
+    if (W == 0) return CLB_OK;
+    CLB_TRY(use_device(f->device));
+    // creation ended with the read-back of the count on the stream that wrote the words: they are complete
+    CLB_HIP(hipMemcpy(words, f->bits.p, sizeof(uint32_t) * W, hipMemcpyDeviceToHost));
+    return CLB_OK;
 }
 
 int64_t clb_filter_count(const clb_filter* f) { return f ? f->count : 0; }

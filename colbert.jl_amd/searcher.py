@@ -28,6 +28,25 @@ def _scope_code(scope) -> int:
 
 MAX_PER_GROUP = 16                         # CLB_MAX_PER_GROUP
 
+_FILTER_OPS = {"and": 0, "or": 1, "andnot": 2, "not": 3}      # CLB_FILTER_OP_AND / _OR / _ANDNOT / _NOT
+MAX_FILTER_OPERANDS = 16                   # CLB_MAX_FILTER_OPERANDS
+
+
+def _range_bound(x, name: str, open_end: float) -> float:
+    """A bound of `make_range_filter` as the float32 the C ABI takes: None is the open end (-Inf / +Inf), anything but a
+    real number (a string, a bool, NaN) an ArgumentError."""
+    import numbers
+    from ._lib import ArgumentError
+    if x is None:
+        return float(open_end)
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (numbers.Real, np.floating, np.integer)):
+        raise ArgumentError(f"{name} must be a real number or None, got {x!r}")
+    with np.errstate(over="ignore"):
+        v = np.float32(x)
+    if np.isnan(v):
+        raise ArgumentError(f"{name} must be a real number or None, got NaN")
+    return float(v)
+
 
 def _per_group(per_group, grouping) -> int:
     """The `per_group=` of a search call as the integer the C ABI takes: it needs a grouping and lies in 1..16."""
@@ -78,11 +97,49 @@ class ResidentHandle(Owned):
 class PassageFilter(ResidentHandle):
     """A set of passages resident in HBM as one bitmap (clb_filter, include/colbert_hip.h): made once by
     `Searcher.make_filter`, reused over any number of searches of that searcher.  Keep it alive while a search that uses
-    it may still be running (or a graph that captured it may be replayed)."""
+    it may still be running (or a graph that captured it may be replayed).
+    Filters of one searcher compose on the device into new filters (`Searcher.combine_filters`): `a & b`, `a | b`, `a - b`
+    (a's passages that are not in b), `~a`; the operands are only read and may be closed as soon as the call returns.
+    `to_mask()` reads a filter back, `extended()` carries one over an append."""
     _destroy = "clb_filter_destroy"
 
     def __init__(self, searcher: "Searcher", handle, count: int):
         self.searcher, self._h, self.count = searcher, handle, int(count)
+        self.num_docs = int(getattr(searcher, "num_docs", 0))      # the searcher's passages when the filter was made
+
+    def __and__(self, other):
+        return self.searcher.combine_filters("and", [self, other])
+
+    def __or__(self, other):
+        return self.searcher.combine_filters("or", [self, other])
+
+    def __sub__(self, other):
+        return self.searcher.combine_filters("andnot", [self, other])
+
+    def __invert__(self):
+        return self.searcher.combine_filters("not", [self])
+
+    def to_mask(self) -> np.ndarray:
+        """The set as a boolean array of the `num_docs` entries the filter was made for (entry i = local passage i + 1), read
+        back from the device (clb_filter_bitmap)."""
+        if not self._h:
+            raise ColBERTError("to_mask: not an open PassageFilter")
+        words = np.zeros((self.num_docs + 31) // 32, dtype="<u4")
+        check(lib().clb_filter_bitmap(self._h, fptr(words), i64(words.size)))
+        return np.unpackbits(words.view(np.uint8), bitorder="little")[:self.num_docs].astype(np.bool_)
+
+    def extended(self, fill: bool = False) -> "PassageFilter":
+        """A new filter over the searcher's passages as they are NOW: the passages this filter was made for keep their bit,
+        the passages appended since are all out (`fill=False`) or all in (`fill=True`).  This filter is unchanged -- if an
+        append made it stale it stays refused by every search.  Of a current filter: a copy (clb_filter_extend)."""
+        from ._lib import ArgumentError
+        if not self._h:
+            raise ColBERTError("extended: not an open PassageFilter")
+        if not isinstance(fill, (bool, np.bool_)):
+            raise ArgumentError(f"fill must be True or False, got {fill!r}")
+        h = C.c_void_p()
+        check(lib().clb_filter_extend(self.searcher._h, self._h, C.c_int(int(fill)), C.byref(h)))
+        return PassageFilter(self.searcher, h, lib().clb_filter_count(h))
 
 
 class PassageGrouping(ResidentHandle):
@@ -754,6 +811,43 @@ class Searcher:
                 raise ColBERTError(f"filters[{j}] is not an open PassageFilter")
             arr[j] = f._h.value
         return arr
+
+    def combine_filters(self, op: str, filters) -> PassageFilter:
+        """A new filter from filters of this searcher, computed on the device (clb_filter_combine): `op` "and" (the
+        intersection of all), "or" (their union), "andnot" (filters[0] minus the union of the rest) or "not" (the complement
+        of the single filter).  1..16 filters, exactly one for "not"; "and" / "or" / "andnot" of one filter is a copy.  The
+        operands are only read -- the same one may appear twice, and they may be closed once the call returns.  `a & b`,
+        `a | b`, `a - b` and `~a` are the two-operand forms; this one avoids their temporaries."""
+        from ._lib import ArgumentError
+        if op not in _FILTER_OPS:
+            raise ArgumentError(f"op must be 'and', 'or', 'andnot' or 'not', got {op!r}")
+        filters = [filters] if isinstance(filters, PassageFilter) else list(filters)
+        n = len(filters)
+        if not 1 <= n <= MAX_FILTER_OPERANDS:
+            raise ArgumentError(f"combine_filters takes 1..{MAX_FILTER_OPERANDS} filters, got {n}")
+        if op == "not" and n != 1:
+            raise ArgumentError(f"'not' takes exactly one filter, got {n}")
+        for j, f in enumerate(filters):
+            if f is None:           # (an unfiltered query to _filter_handles; no operand here)
+                raise ColBERTError(f"filters[{j}] is not an open PassageFilter")
+        arr = self._filter_handles(filters, n)
+        h = C.c_void_p()
+        check(lib().clb_filter_combine(self._h, C.c_int(_FILTER_OPS[op]), arr, i64(n), C.byref(h)))
+        return PassageFilter(self, h, lib().clb_filter_count(h))
+
+    def make_range_filter(self, prior, lo=None, hi=None, lo_open: bool = False, hi_open: bool = False) -> PassageFilter:
+        """The passages whose value in `prior` (a PassagePrior of this searcher: the attribute, one fp32 value per passage)
+        lies between `lo` and `hi`, computed on the device (clb_filter_create_range).  `None` is an open end; a bound is
+        converted to float32 (integers are exact up to 2^24) and compared as IEEE does (-0 equals +0); `lo_open` / `hi_open`
+        exclude the bound itself.  lo > hi, or lo == hi with an open end, is the empty filter; lo == hi is equality.  A bound
+        that is not a real number is an ArgumentError."""
+        if not isinstance(prior, PassagePrior) or not prior._h:
+            raise ColBERTError("prior is not an open PassagePrior")
+        lo32, hi32 = _range_bound(lo, "lo", -np.inf), _range_bound(hi, "hi", np.inf)
+        flags = (1 if lo_open else 0) | (2 if hi_open else 0)           # CLB_RANGE_LO_OPEN / CLB_RANGE_HI_OPEN
+        h = C.c_void_p()
+        check(lib().clb_filter_create_range(self._h, prior._h, C.c_float(lo32), C.c_float(hi32), C.c_int(flags), C.byref(h)))
+        return PassageFilter(self, h, lib().clb_filter_count(h))
 
     # -- groupings --------------------------------------------------------------------------------
     def make_grouping(self, group_ids=None, group_lens=None) -> PassageGrouping:

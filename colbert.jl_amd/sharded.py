@@ -34,7 +34,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._lib import ArgumentError, BoundsError, ColBERTError, Unsupported, check, colmajor, fptr, i64, lib
-from .searcher import Owned, PassageFilter, SearchKeywords, _no_prior_hits, _scope_code, _weight_value
+from .searcher import Owned, PassageFilter, SearchKeywords, _no_prior_hits, _range_bound, _scope_code, _weight_value
 
 _PROTOCOLS = ("auto", "two_phase", "single")
 _PIECE = 64          # queries per exchange: a filtered phase 1 carries at most 64 filter handles (include/colbert_hip.h)
@@ -179,10 +179,38 @@ class ShardedPrior(ShardedParts):
 class ShardedFilter(ShardedParts):
     """A passage set over a shard group: one resident PassageFilter per local shard (`parts`), made by
     `ShardedSearcher.make_filter` and refused by any other group.  `count` is the population over the whole group.  An append
-    to the group invalidates it (the library refuses it: "filter made before an append; make another"); a removal does not."""
+    to the group invalidates it (the library refuses it: "filter made before an append; make another"); a removal does not.
+    Filters of one group compose part by part on the device (`ShardedSearcher.combine_filters`): `a & b`, `a | b`, `a - b`,
+    `~a`.  Carrying a filter over an append (`PassageFilter.extended`) is not offered across a shard group: make another."""
 
     def __init__(self, group: "ShardedSearcher", parts, count: int):
         self.group, self.parts, self.count = group, list(parts), int(count)
+        b = getattr(group, "_bounds", None)        # the group's passages when the filter was made
+        self._first_pid, self.num_docs = (int(b[0]), int(b[-1] - b[0])) if b is not None else (0, 0)
+
+    def __and__(self, other):
+        return self.group.combine_filters("and", [self, other])
+
+    def __or__(self, other):
+        return self.group.combine_filters("or", [self, other])
+
+    def __sub__(self, other):
+        return self.group.combine_filters("andnot", [self, other])
+
+    def __invert__(self):
+        return self.group.combine_filters("not", [self])
+
+    def to_mask(self) -> np.ndarray:
+        """The set as a boolean array over the group's passages (entry i = global pid first + i + 1), read back from the
+        device: the slices of THIS process's shards at their global positions.  With a process group every rank holds its
+        own shards' slices and False elsewhere -- rank r the passages of shards r L .. r L + L - 1 (L shards per rank; their
+        pids are `ShardedSearcher.shard_ranges` of those indices) -- and the element-wise OR over the ranks is the whole set;
+        no collective runs here."""
+        out = np.zeros(self.num_docs, dtype=np.bool_)
+        for part in self.parts:
+            at = int(part.searcher.pid_offset) - self._first_pid
+            out[at:at + part.num_docs] = part.to_mask()
+        return out
 
 
 def _refuse_single_handle_keywords(kw: SearchKeywords):
@@ -327,6 +355,41 @@ class ShardedSearcher:
                 f.close()
             raise
         return ShardedFilter(self, parts, count)
+
+    def _filter_of_parts(self, make) -> ShardedFilter:
+        """`make(j, shard)` -> the PassageFilter of local shard j; the group's count is summed over the ranks as make_filter
+        sums it (the one collective)."""
+        parts = []
+        try:
+            for j, s in enumerate(self.shards):
+                parts.append(make(j, s))
+            count = sum(f.count for f in parts)
+            if self.group is not None:
+                count = int(self._gather(np.array([[count]], dtype=np.int64)).sum())
+        except Exception:
+            for f in parts:
+                f.close()
+            raise
+        return ShardedFilter(self, parts, count)
+
+    def combine_filters(self, op: str, filters) -> ShardedFilter:
+        """`Searcher.combine_filters` over the group: the filters' parts are combined shard by shard on the device -- part j of
+        the result from part j of every operand, in the order given.  Operands of another group are refused."""
+        filters = [filters] if isinstance(filters, ShardedFilter) else list(filters)
+        for j, f in enumerate(filters):
+            if not isinstance(f, ShardedFilter) or f.group is not self:
+                raise ColBERTError(f"filters[{j}] is not a ShardedFilter of this shard group")
+        return self._filter_of_parts(lambda j, s: s.combine_filters(op, [f.parts[j] for f in filters]))
+
+    def make_range_filter(self, prior, lo=None, hi=None, lo_open: bool = False, hi_open: bool = False) -> ShardedFilter:
+        """`Searcher.make_range_filter` over the group: `prior` a ShardedPrior of this group, every local shard takes the
+        range over its own slice of the values.  The bounds are checked once, before any shard is called."""
+        if not isinstance(prior, ShardedPrior) or prior.group is not self or prior.closed:
+            raise ColBERTError("prior is not an open ShardedPrior of this shard group")
+        if prior.num_docs != self.num_docs:
+            raise ArgumentError("prior made before an append; make another")
+        _range_bound(lo, "lo", -np.inf), _range_bound(hi, "hi", np.inf)
+        return self._filter_of_parts(lambda j, s: s.make_range_filter(prior.parts[j], lo, hi, lo_open, hi_open))
 
     def _shard_filters(self, filters, B: int):
         """`filters` of a search call -> per local shard a list of B PassageFilters / None, or None when no query is filtered."""

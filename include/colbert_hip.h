@@ -326,6 +326,49 @@ int clb_search_shard_phase1_filtered_slot(clb_searcher* s, int slot, const float
                                           void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Composing filters on the device: a request carries several predicates at once ("this tenant's passages, published after
+ * day D, not in the hidden set"), and the operands -- other filters, a per-passage attribute held as a clb_prior -- are
+ * resident already.  Each call below makes a NEW immutable clb_filter bound to `s`, with the lifetime rules of every other
+ * filter; every search call, scope, route, captured graph and shard protocol takes it as it takes any other.  Operands are
+ * only read: they may be in use by searches in flight, may be destroyed as soon as the call returns, and the same operand may
+ * be named more than once.  Creation synchronises once, for the count (so it is not capturable); *out is NULL on every
+ * failure; all argument checks run before any device work, and those that need nothing of the searcher's state (a null s /
+ * out / operands / entry, an op outside the enum, the rules for n, a NaN bound, unknown flag bits, a fill outside 0 / 1) are
+ * answered on a machine without a GPU.
+ * ---------------------------------------------------------------------------------------------- */
+/* the set operations: AND the intersection of all operands, OR their union, ANDNOT operand 0 minus the union of the rest,
+ * NOT the complement of the single operand within the searcher's passages */
+enum { CLB_FILTER_OP_AND = 0, CLB_FILTER_OP_OR = 1, CLB_FILTER_OP_ANDNOT = 2, CLB_FILTER_OP_NOT = 3 };
+/* the most operands of one clb_filter_combine call: their word pointers travel in the kernel's arguments */
+enum { CLB_MAX_FILTER_OPERANDS = 16 };
+/* `operands`: a HOST array of n handles, 1 <= n <= CLB_MAX_FILTER_OPERANDS, and n == 1 exactly for CLB_FILTER_OP_NOT
+ * (anything else: CLB_EARGUMENT).  AND, OR and ANDNOT with n = 1 give a copy.  An operand made for another searcher, or made
+ * before an append, is CLB_EARGUMENT naming its index ("the filter of operand 2: filter made before an append; make
+ * another").  A searcher without passages gives a valid empty filter without a launch. */
+int clb_filter_combine(clb_searcher* s, int op, const clb_filter* const* operands, int64_t n, clb_filter** out);
+/* flags of clb_filter_create_range: the bound itself is outside the range */
+enum { CLB_RANGE_LO_OPEN = 1, CLB_RANGE_HI_OPEN = 2 };
+/* The passages whose value in `values` lies between lo and hi: passage p is in when
+ *     (flags & CLB_RANGE_LO_OPEN ? v > lo : v >= lo) && (flags & CLB_RANGE_HI_OPEN ? v < hi : v <= hi)
+ * for the stored fp32 value v, by IEEE comparison (-0 equals +0).  The attribute is a clb_prior: recency, quality, a tenant
+ * id.  Values are fp32, so integers are exact up to 2^24: an id or a day number beyond that does not survive
+ * clb_prior_create.  The prior must be this searcher's and made for the passages it holds now (CLB_EARGUMENT otherwise: "the
+ * prior was made for another searcher", "prior made before an append; make another").  A NaN bound and flag bits outside the
+ * two are CLB_EARGUMENT.  -Inf / +Inf as a bound is an open end (a prior's values are always finite).  lo > hi, or lo == hi
+ * with an open end, is a valid empty filter; lo == hi with both ends closed is equality, and membership in a few values is
+ * the CLB_FILTER_OP_OR of such filters.  (struct clb_prior: the clb_prior of "Score priors" below.) */
+int clb_filter_create_range(clb_searcher* s, const struct clb_prior* values, float lo, float hi, int flags, clb_filter** out);
+/* A filter made before an append, carried over it: `f` must be a filter of `s` with no more passages than `s` holds now
+ * (CLB_EARGUMENT otherwise).  The result has the searcher's current n_docs: the passages `f` knew keep their bit, the passages
+ * appended since are all out (fill = 0) or all in (fill = 1; anything else: CLB_EARGUMENT).  With equal n_docs it is a copy.
+ * `f` itself is unchanged and, if stale, stays refused by every search. */
+int clb_filter_extend(clb_searcher* s, const clb_filter* f, int fill, clb_filter** out);
+/* The words of a filter, copied to the host after waiting for the device work that made them: n_words must be the filter's
+ * ceil(n_docs / 32), else CLB_EARGUMENT; bits past n_docs are zero.  It works on any filter, stale ones and those whose
+ * searcher is gone included. */
+int clb_filter_bitmap(const clb_filter* f, uint32_t* words, int64_t n_words);
+
+/* ------------------------------------------------------------------------------------------------
  * Grouped search: rank DOCUMENTS by their best passage (no counterpart in the reference; the "collapse" of Elasticsearch and
  * Vespa, the docs2passages evaluation of upstream ColBERT).  A clb_grouping maps every local passage to a group.  The
  * caller's group_ids -- exactly n_docs entries, entry i = local passage i -- must be NON-DECREASING in pid, so that equal
