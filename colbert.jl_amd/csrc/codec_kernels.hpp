@@ -85,7 +85,7 @@ static __global__ __launch_bounds__(256) void decompress_dim128_kernel(const flo
             R[k4] = v.x; R[k4 + 1] = v.y; R[k4 + 2] = v.z; R[k4 + 3] = v.w;
         }
         float x[32];
-        decompress_lane_dims_fast<NBITS>(C + (size_t)(codes[e] - 1) * kDim + g, R, g, tbl, x);
+        decompress_lane_dims_fast<NBITS, true>(C + (size_t)(codes[e] - 1) * kDim + g, R, g, tbl, x);   // -0.0 stays -0.0
         if (el < n) {
 #pragma unroll
             for (int s = 0; s < 32; ++s) out[(size_t)e * kDim + 4 * s + g] = x[s];
@@ -243,10 +243,10 @@ static __global__ void pack_residuals_kernel(const float* __restrict__ C, const 
         const int p = 8 * j + bit;
         const int d = p / nbits, b = p % nbits;
         const float r = x[d] - c[d];
-        int lo = 0, hi = ncut + 1;  // Julia's searchsortedfirst
+        int lo = 0, hi = ncut + 1;  // Julia's searchsortedfirst: isless order, a NaN residual sorts after every cutoff
         while (lo < hi - 1) {
             const int m = lo + ((hi - lo) >> 1);
-            if (cutoffs[m - 1] < r) lo = m; else hi = m;
+            if (cutoffs[m - 1] < r || r != r) lo = m; else hi = m;
         }
         const int idx = hi - 1;
         byte |= (uint32_t)((idx >> b) & 1) << bit;

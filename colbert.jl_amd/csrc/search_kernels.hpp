@@ -605,6 +605,17 @@ __device__ __forceinline__ float div_by_reciprocal(float x, float den, float y) 
     const float r = fmaf(-den, q0, x);
     return fmaf(r, y, q0);
 }
+// The same quotient with the sign of a zero numerator kept, as IEEE division by a positive den keeps it (the form above
+// returns +0.0 for x = -0.0: nothing a score can see, but decompress() returns the vector itself).  nr = RN(den*q0 - x) =
+// -RN(x - den*q0) -- the fma is exact before its one rounding and rounding to nearest is symmetric -- so for x != 0 this is
+// the sequence above bit for bit and its check carries over; x = -0.0 gives q0 = -0, nr = +0 and (-0)*y + (-0) = -0.0,
+// x = +0.0 gives (-0)*y + (+0) = +0.0.  Its last fma needs a source modifier (8-byte encoding), so the search kernels keep
+// the form above.
+__device__ __forceinline__ float div_by_reciprocal_signed_zero(float x, float den, float y) {
+    const float q0 = x * y;
+    const float nr = fmaf(den, q0, -x);
+    return fmaf(-nr, y, q0);
+}
 
 // Bucket-weight table in LDS, replicated over the 32 banks: tbl[idx][bank] = weights[idx].  Lane L reads
 // tbl[idx][L & 31], so the data-dependent lookups of a wave never collide on a bank (a [field][byte] table indexed
@@ -620,7 +631,7 @@ __device__ __forceinline__ void fill_weight_table(float* tbl, const float* __res
 // weight table and the reciprocal division.  R = packed residual dwords.  The centroid values come either
 // straight from global memory (cent_row, used by the stand-alone decompress kernel) or from a staged LDS tile
 // (ctile != nullptr: slot(s, r) = s*16 + (r ^ (s & 15)), 16 B per slot -- see score_exact_kernel).
-template <int NBITS>
+template <int NBITS, bool SIGNED_ZERO = false>
 __device__ __forceinline__ void decompress_lane_dims_fast(const float* __restrict__ cent_row /*+g*/,
                                                           const uint32_t (&R)[NBITS * 4], int g,
                                                           const float* __restrict__ tbl, float (&x)[32],
@@ -646,7 +657,7 @@ __device__ __forceinline__ void decompress_lane_dims_fast(const float* __restric
     if (__builtin_expect(den > 1e-18f && den < 1e18f, 1)) {
         const float y = 1.0f / den;
 #pragma unroll
-        for (int s = 0; s < 32; ++s) x[s] = div_by_reciprocal(x[s], den, y);
+        for (int s = 0; s < 32; ++s) x[s] = SIGNED_ZERO ? div_by_reciprocal_signed_zero(x[s], den, y) : div_by_reciprocal(x[s], den, y);
     } else {
 #pragma unroll
         for (int s = 0; s < 32; ++s) x[s] = x[s] / den;

@@ -398,12 +398,13 @@ int orc_unbinarize(const uint8_t* bits, int nbits, int64_t dim, int64_t b, int64
     return ORC_OK;
 }
 
-/* residual.jl:348-351  searchsortedfirst(cutoffs, x) - 1, as Julia's binary search does it */
+/* residual.jl:348-351  searchsortedfirst(cutoffs, x) - 1, as Julia's binary search does it: the
+ * order is isless, under which NaN comes after every number -- a NaN lands in the last bucket */
 static inline int64_t searchsortedfirst_m1(const float* v, int64_t n, float x) {
     int64_t lo = 0, hi = n + 1; /* 1-based bounds, exclusive */
     while (lo < hi - 1) {
         int64_t m = lo + ((hi - lo) >> 1);
-        if (v[m - 1] < x) lo = m; else hi = m;
+        if (v[m - 1] < x || x != x) lo = m; else hi = m;
     }
     return hi - 1;
 }
