@@ -237,6 +237,13 @@ def lib() -> C.CDLL:
         l.clb_packed_grouped_bytes.argtypes = [i64_, i64_]
         l.clb_merge_topk_grouped_packed_device.restype = ci
         l.clb_merge_topk_grouped_packed_device.argtypes = [ci, vp, i64_, i64_, i64_, vp, vp, vp, vp]
+        if hasattr(l, "clb_maxsim_batch"):                    # (absent from a COLBERT_HIP_LIB build of an earlier commit)
+            l.clb_maxsim_batch_work_bytes.restype = i64_
+            l.clb_maxsim_batch_work_bytes.argtypes = [i64_, i64_, i64_]
+            l.clb_maxsim_batch.restype = ci
+            l.clb_maxsim_batch.argtypes = [ci, vp, i64_, i64_, i64_, vp, i64_, vp, i64_, vp, vp]
+            l.clb_maxsim_batch_device.restype = ci
+            l.clb_maxsim_batch_device.argtypes = [ci, vp, i64_, i64_, i64_, vp, i64_, vp, i64_, vp, vp, vp, i64_, vp]
         if hasattr(l, "clb_debug_nearest"):
             l.clb_debug_nearest_scratch_create.restype = ci
             l.clb_debug_nearest_scratch_create.argtypes = [ci, C.POINTER(vp)]

@@ -98,6 +98,57 @@ def _stream_of(t):
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
+def maxsim_batch(Q, D, doclens, owner=None, device: int = 0):
+    """maxsim (ranking.jl:69-86) of N un-indexed passages for a batch of queries in one call (clb_maxsim_batch): Q (dim, T, B),
+    D (dim, n) -- the passages' embeddings back to back --, doclens [N].  `owner` [N], 0-based: passage j is scored against
+    query owner[j] only -> (N,) float32; without it every query scores every passage -> (N, B).  Each score has the bits of
+    `maxsim(Q[:, :, q], D_j)`."""
+    q = colmajor(Q, np.float32); d = colmajor(D, np.float32)
+    if q.ndim != 3:
+        raise ValueError("Q must be (dim, T, B)")
+    dl = np.ascontiguousarray(doclens, dtype=np.int64)
+    ow = None if owner is None else np.ascontiguousarray(owner, dtype=np.int32)
+    if ow is not None and ow.size != dl.size:
+        raise ValueError("owner must hold one query number per passage")
+    dim, T, B = q.shape
+    scores = np.zeros(dl.size if ow is not None else (dl.size, B), dtype=np.float32, order="F")
+    check(lib().clb_maxsim_batch(device, fptr(q), i64(dim), i64(T), i64(B), fptr(d), i64(d.shape[1] if d.ndim == 2 else 0),
+                                 fptr(dl), i64(dl.size), fptr(ow) if ow is not None else None, fptr(scores)))
+    return scores
+
+
+def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, stream=None):
+    """`maxsim_batch` between the encoder's device outputs (clb_maxsim_batch_device): d_Q float32 (B, T, dim) -- what
+    query_embeddings_device writes --, d_D float32 (n, dim) and d_doclens int64 (N,) -- what doc_embeddings_device /
+    doc_embeddings_packed_device return --, owner int32 (N,) or None; all contiguous CUDA tensors.  Returns `out`: float32 (N,)
+    with owners, else (B, N) (row q = query q's scores).  Enqueued on `stream` (default: torch's current stream) and not
+    waited for; with `out` and `work` (uint8, clb_maxsim_batch_work_bytes long) given it allocates nothing, so it can be
+    captured in a graph.  Device doclens are not validated: see include/colbert_hip.h for what bad ones score."""
+    import torch
+    q = _dev_rows(d_Q, torch.float32); d = _dev_rows(d_D, torch.float32); dl = _dev_rows(d_doclens, torch.int64)
+    if q.dim() != 3 or d.dim() != 2 or d.shape[1] != q.shape[2]:
+        raise ValueError("d_Q must be (B, T, dim) and d_D (n, dim)")
+    B, T, dim = (int(x) for x in q.shape)
+    N = int(dl.numel())
+    ow = None if owner is None else _dev_rows(owner, torch.int32)
+    if ow is not None and ow.numel() != N:
+        raise ValueError("owner must hold one query number per passage")
+    need = int(lib().clb_maxsim_batch_work_bytes(i64(N), i64(B), i64(T)))
+    if out is None:
+        out = torch.empty(N if ow is not None else (B, N), dtype=torch.float32, device=q.device)
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=q.device)
+    o = _dev_rows(out, torch.float32); wk = _dev_rows(work)
+    if o.numel() != (N if ow is not None else N * B):
+        raise ValueError("out: one score per passage (owned) or per (query, passage)")
+    st = torch.cuda.current_stream(q.device).cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+    check(lib().clb_maxsim_batch_device(q.device.index, C.c_void_p(q.data_ptr()), i64(dim), i64(T), i64(B), C.c_void_p(d.data_ptr()),
+                                        i64(d.shape[0]), C.c_void_p(dl.data_ptr()), i64(N),
+                                        C.c_void_p(ow.data_ptr()) if ow is not None else None, C.c_void_p(o.data_ptr()),
+                                        C.c_void_p(wk.data_ptr()), i64(wk.numel() * wk.element_size()), C.c_void_p(st)))
+    return out
+
+
 class KMeansShard:
     """One rank's points of a sharded k-means (clb_kmeans_shard_*): uploaded once, one `pass_` per iteration.
     `data`: a (dim, n) numpy array (uploaded) or an (n, dim) float32 CUDA tensor (borrowed in place:

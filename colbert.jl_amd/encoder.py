@@ -322,3 +322,73 @@ class BertEncoder:
                                                        cfg.query_maxlen)
             out.append(self.query_embeddings(skiplist, ids, mask))
         return np.asfortranarray(np.concatenate(out, axis=2))
+
+    # -- texts that are in no index ---------------------------------------------------------------------
+    def _encode_passages_device(self, passages: List[str]):
+        """encode_passages with the result left on the device -> ((n, dim) float32 CUDA tensor, doclens int64 CUDA tensor):
+        every passage of the call as ONE batch sequence, packed (no padding rows) where the encoder can, else padded batches
+        of index_bsize."""
+        import torch
+        from ._lib import ArgumentError
+        cfg, dev = self.config, torch.device("cuda", self.device)
+        d_skip = torch.tensor(self.tokenizer.doc_skiplist(cfg.mask_punctuation), dtype=torch.int64, device=dev)
+        marker = np.int32(self.tokenizer.lookup(cfg.doc_token_id))
+        seqs = [e.ids[:cfg.doc_maxlen - 1] for e in self.tokenizer.tok.encode_batch(list(passages), add_special_tokens=True)]
+        toks = [np.concatenate([[e[0] + 1, marker], np.asarray(e[1:], dtype=np.int32) + 1]).astype(np.int32) for e in seqs]   # tensorize_docs' rows
+        lens = np.array([t.size for t in toks], dtype=np.int32)
+        rows = int(lens.sum())
+        buf = np.concatenate([np.concatenate(toks), np.concatenate([np.arange(n, dtype=np.int32) for n in lens]),
+                              np.repeat(np.arange(lens.size, dtype=np.int32), lens), [0], np.cumsum(lens)]).astype(np.int32)
+        d = torch.from_numpy(buf).to(dev)
+        try:
+            return self.doc_embeddings_packed_device(d[:rows], d[rows:2 * rows], d[2 * rows:3 * rows], d[3 * rows:], int(lens.max()), d_skip)
+        except ArgumentError:
+            pass                                            # this encoder cannot pack: padded batches, as encode_passages cuts them
+        embs, doclens = [], []
+        for off in range(0, len(toks), cfg.index_bsize):
+            part = toks[off:off + cfg.index_bsize]
+            ids = np.full((len(part), max(t.size for t in part)), self.tokenizer.pad_id, dtype=np.int32)
+            mask = np.zeros(ids.shape, dtype=np.uint8)
+            for j, t in enumerate(part):
+                ids[j, :t.size] = t
+                mask[j, :t.size] = 1
+            e, dl = self.doc_embeddings_device(torch.from_numpy(ids).to(dev), torch.from_numpy(mask).to(dev), d_skip)
+            embs.append(e); doclens.append(dl)
+        return torch.cat(embs).contiguous(), torch.cat(doclens)
+
+    def score_passages(self, queries: List[str], passages: List[List[str]], return_embeddings: bool = False):
+        """Re-rank texts that are in no index: passages[i] are the texts to score for queries[i].  The queries go through the
+        query chain, all passages through the device document chain as one concatenated sequence, then one
+        codec.maxsim_batch_device scores passage j against its own query -- no passage embedding crosses PCIe.  Returns one
+        float32 array per query (the scores of its passages, in input order); with return_embeddings also what was scored,
+        read back: Q (dim, query_maxlen, B), D (dim, n), doclens [N] (passages of query 0 first)."""
+        import torch
+        from . import codec
+        if len(queries) != len(passages):
+            raise ValueError("score_passages: one list of passages per query")
+        cfg, dev = self.config, torch.device("cuda", self.device)
+        counts = np.array([len(p) for p in passages], dtype=np.int64)
+        flat = [t for p in passages for t in p]
+        cut = np.cumsum(counts)[:-1]
+        B, T = len(queries), cfg.query_maxlen
+        empty = (np.zeros((self.dim, T, B), np.float32, order="F"), np.zeros((self.dim, 0), np.float32, order="F"), np.zeros(0, np.int64))
+        if B == 0 or not flat:
+            scores = [np.zeros(0, np.float32) for _ in queries]
+            if return_embeddings and B:
+                empty = (self.encode_queries(queries),) + empty[1:]
+            return (scores,) + empty if return_embeddings else scores
+        with torch.cuda.device(dev):
+            ids, mask = tokenization.tensorize_queries(cfg.query_token, cfg.attend_to_mask_tokens, self.tokenizer, list(queries), T)
+            d_q = torch.empty((B, T, self.dim), dtype=torch.float32, device=dev)
+            self.query_embeddings_device(torch.from_numpy(np.ascontiguousarray(ids.T)).to(dev),
+                                         torch.from_numpy(np.ascontiguousarray(mask.T).astype(np.uint8)).to(dev),
+                                         torch.tensor([self.tokenizer.pad_id], dtype=torch.int64, device=dev), d_q)      # searching.jl:62
+            d_D, d_len = self._encode_passages_device(flat)
+            owner = torch.from_numpy(np.repeat(np.arange(B, dtype=np.int32), counts)).to(dev)
+            d_s = codec.maxsim_batch_device(d_q, d_D.contiguous(), d_len, owner=owner)
+            self.check_last_ids()
+            scores = np.split(d_s.cpu().numpy(), cut)
+            if not return_embeddings:
+                return scores
+            return (scores, np.asfortranarray(d_q.cpu().numpy().transpose(2, 1, 0)), np.asfortranarray(d_D.cpu().numpy().T),
+                    d_len.cpu().numpy())

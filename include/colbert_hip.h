@@ -825,6 +825,30 @@ int clb_decompress(int device, int64_t dim, int nbits, const float* centroids, i
 /* maxsim  (src/search/ranking.jl:69-86) ; D is (dim, n_D) */
 int clb_maxsim(int device, const float* Q, int64_t dim, int64_t T, const float* D, int64_t n_D,
                const int64_t* pids, int64_t n_pids, const int64_t* doclens, int64_t n_docs, float* scores);
+/* maxsim for a BATCH of queries over passages that are in no index: the scorer between the encoder's device outputs
+ * (clb_encode_queries_device writes d_Q, clb_encode_docs_device / _packed_device write d_D and d_doclens).
+ *   d_Q (dim, T, B) fp32; d_D (dim, n_D) fp32, the embeddings of N passages back to back, 16-byte aligned; d_doclens int64 [N];
+ *   d_owner int32 [N] or NULL.
+ *   owned     (d_owner != NULL): passage j is scored against query owner[j] only; d_scores [N].
+ *   all pairs (d_owner == NULL): every query against every passage; d_scores (N, B), N fastest.
+ * Arithmetic: clb_maxsim's -- the canonical dot per (token, embedding), the maximum per token, acc = 0; acc = acc + max_t
+ * for t ascending -- so each score has the bits of maxsim(Q[:, :, q], D_j).  All T tokens count (query padding is the
+ * caller's business, as in search).  Served: dim % 4 == 0, 4 <= dim <= 1024 (tuned for 128), 1 <= T <= 128, B >= 1, N >= 0;
+ * anything else is CLB_EUNSUPPORTED (clb_maxsim is the route then).  N = 0 is CLB_OK with nothing launched.
+ * The device call is stream-ordered and not waited for, allocates nothing (d_work: clb_maxsim_batch_work_bytes bytes, 8-byte
+ * aligned; too small is CLB_EARGUMENT before any launch) and never synchronises with the host, so it can be captured in a
+ * graph.  It cannot validate device doclens and does not fault on bad ones: a negative doclen counts as 0, rows at or past
+ * n_D are never read, an owner outside 0..B-1 reads no query, and a passage left without a readable embedding or without a
+ * query scores -Inf.  The host call validates first, like clb_maxsim: CLB_EDIMENSION sum(doclens) != n_D (ranking.jl:71-74),
+ * CLB_EARGUMENT a doclen of 0, CLB_EBOUNDS an owner outside 0..B-1; then it uploads, runs the device call on a stream of
+ * its own and copies the scores back.  Not part of the Julia shim. */
+int64_t clb_maxsim_batch_work_bytes(int64_t N, int64_t B, int64_t T);
+int clb_maxsim_batch_device(int device, const float* d_Q, int64_t dim, int64_t T, int64_t B,
+                            const float* d_D, int64_t n_D, const int64_t* d_doclens, int64_t N,
+                            const int32_t* d_owner /* NULL: all pairs */, float* d_scores,
+                            void* d_work, int64_t work_bytes, void* hip_stream);
+int clb_maxsim_batch(int device, const float* Q, int64_t dim, int64_t T, int64_t B, const float* D, int64_t n_D,
+                     const int64_t* doclens, int64_t N, const int32_t* owner, float* scores);
 /* compress_into_codes!  (residual.jl:67-81) */
 int clb_compress_into_codes(int device, uint32_t* codes, int64_t n_codes, const float* centroids,
                             int64_t dim, int64_t K, const float* embs, int64_t n);

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""Dense MaxSim of un-indexed passages (`codec.maxsim_batch_device`) at dim 128, T = 32, two shapes:
+
+  rerank   B = 32 queries, `--per-query` (1 000) passages of ~80 embeddings each per query, owned form;
+  pairs    B = 32 queries against `--pairs-passages` (4 096) passages, all-pairs form.
+
+For each: the device call on resident tensors (HIP events around `--steps` calls), and the same work through the route it
+replaces on this same build -- `codec.maxsim` once per query from host arrays (host clock: every call uploads and waits).
+`--rounds` windows per side, interleaved with the order rotating; medians reported, every window kept, spread stated.
+Rates: the bytes the call must read (D, Q, doclens, owners) over its time against `clb_measure_read_rate` taken in the
+same run, and 2 dim T rows (x B for pairs) flop over its time against `--mfma-f32-tflops` (what
+tools/microbench/mfma_f32_peak.hip printed on the same machine).  Writes one JSON file; profiles/maxsim_batch.md is
+written from it by hand.  A measurement path only: it needs a GPU and fails without one."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, HERE)
+
+
+def unit(rng, dim, n):
+    x = rng.standard_normal((n, dim), dtype=np.float32)
+    return x / np.linalg.norm(x, axis=1, keepdims=True)
+
+
+def summary(v):
+    return {"ms": round(float(np.median(v)), 5), "windows_ms": [round(x, 5) for x in v], "spread_ms": round(float(max(v) - min(v)), 5)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--per-query", type=int, default=1000)
+    ap.add_argument("--pairs-passages", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=50, help="device calls per timed window")
+    ap.add_argument("--old-steps", type=int, default=1, help="passes of the per-query route per timed window")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--mfma-f32-tflops", type=float, default=None)
+    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "maxsim_batch.json"))
+    args = ap.parse_args()
+    import torch
+    import colbert_jl_amd as clb
+    from colbert_jl_amd import codec
+    from colbert_jl_amd._lib import measure_read_rate
+    if clb.lib().clb_device_count() < 1:
+        sys.exit("bench_maxsim_batch: no GPU")
+    dim, T, B = 128, 32, args.batch
+    rng = np.random.default_rng(2025)
+    Q = unit(rng, dim, T * B).reshape(B, T, dim)
+    shapes = {}
+    for name, N in (("rerank", B * args.per_query), ("pairs", args.pairs_passages)):
+        dl = np.clip(np.rint(rng.normal(80, 20, size=N)), 8, 180).astype(np.int64)
+        D = unit(rng, dim, int(dl.sum()))
+        owner = np.repeat(np.arange(B, dtype=np.int32), args.per_query) if name == "rerank" else None
+        shapes[name] = (dl, D, owner)
+
+    sides, work_of = {}, {}
+    for name, (dl, D, owner) in shapes.items():
+        N, rows = dl.size, int(dl.sum())
+        d_Q, d_D, d_l = torch.from_numpy(Q).cuda(), torch.from_numpy(D).cuda(), torch.from_numpy(dl).cuda()
+        d_o = None if owner is None else torch.from_numpy(owner).cuda()
+        out = torch.empty(N if owner is not None else (B, N), dtype=torch.float32, device="cuda")
+        work = torch.empty(int(clb.lib().clb_maxsim_batch_work_bytes(N, B, T)), dtype=torch.uint8, device="cuda")
+        sides[name + "_device"] = (lambda d_Q=d_Q, d_D=d_D, d_l=d_l, d_o=d_o, out=out, work=work:
+                                   codec.maxsim_batch_device(d_Q, d_D, d_l, owner=d_o, out=out, work=work))
+        Qh = [np.asfortranarray(Q[b].T) for b in range(B)]
+        Dh = np.asfortranarray(D.T)
+        pids = np.arange(1, N + 1)
+        if owner is not None:                          # every query's own passages: a slice of D and of the doclens
+            off = np.concatenate([[0], np.cumsum(dl)])
+            cut = [(b * args.per_query, (b + 1) * args.per_query) for b in range(B)]
+            parts = [(np.asfortranarray(Dh[:, off[a]:off[z]]), dl[a:z], np.arange(1, z - a + 1)) for a, z in cut]
+            old = lambda Qh=Qh, parts=parts: np.concatenate([codec.maxsim(Qh[b], *parts[b][::2], parts[b][1]) for b in range(B)])     # noqa: E731
+        else:
+            old = lambda Qh=Qh, Dh=Dh, pids=pids, dl=dl: np.stack([codec.maxsim(Qh[b], Dh, pids, dl) for b in range(B)])            # noqa: E731
+        sides[name + "_per_query_host"] = old
+        got, want = sides[name + "_device"]().cpu().numpy(), old()
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), name      # the two routes agree bit for bit at the timed size
+        flop = 2.0 * dim * T * rows * (1 if owner is not None else B)
+        byts = 4.0 * dim * rows + 4.0 * Q.size + 8.0 * N + (4.0 * N if owner is not None else 0)
+        work_of[name] = {"passages": N, "embeddings": rows, "flop": flop, "bytes": byts}
+
+    def device_window(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.steps):
+            call()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / args.steps
+
+    def host_window(call):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.old_steps):
+            call()
+        return (time.perf_counter() - t0) * 1e3 / args.old_steps
+
+    names = list(sides)
+    for n in names:
+        for _ in range(args.warmup if n.endswith("_device") else 1):
+            sides[n]()
+    torch.cuda.synchronize()
+    read_gbs = measure_read_rate(0)
+    ms = {n: [] for n in names}
+    for r in range(args.rounds):
+        rot = r % len(names)
+        for n in names[rot:] + names[:rot]:
+            ms[n].append((device_window if n.endswith("_device") else host_window)(sides[n]))
+    out = {"tool": "tools/bench_maxsim_batch.py", "device": torch.cuda.get_device_name(0), "dim": dim, "T": T, "B": B,
+           "steps_per_window": args.steps, "read_rate_gb_s": round(read_gbs, 1), "mfma_f32_tflops": args.mfma_f32_tflops,
+           "sides": {n: summary(ms[n]) for n in names}, "shapes": work_of}
+    for name, w in work_of.items():
+        t = out["sides"][name + "_device"]["ms"] * 1e-3
+        w["device_gb_s"] = round(w["bytes"] / t / 1e9, 1)
+        w["fraction_of_read_rate"] = round(w["bytes"] / t / 1e9 / read_gbs, 4)
+        w["device_tflops"] = round(w["flop"] / t / 1e12, 2)
+        if args.mfma_f32_tflops:
+            w["fraction_of_mfma_f32_rate"] = round(w["flop"] / t / 1e12 / args.mfma_f32_tflops, 4)
+        w["per_query_host_over_device"] = round(out["sides"][name + "_per_query_host"]["ms"] / out["sides"][name + "_device"]["ms"], 1)
+    print(json.dumps(out), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
