@@ -244,6 +244,13 @@ def lib() -> C.CDLL:
             l.clb_maxsim_batch.argtypes = [ci, vp, i64_, i64_, i64_, vp, i64_, vp, i64_, vp, vp]
             l.clb_maxsim_batch_device.restype = ci
             l.clb_maxsim_batch_device.argtypes = [ci, vp, i64_, i64_, i64_, vp, i64_, vp, i64_, vp, vp, vp, i64_, vp]
+        if hasattr(l, "clb_maxsim_batch_half"):               # (likewise)
+            l.clb_maxsim_batch_half_work_bytes.restype = i64_
+            l.clb_maxsim_batch_half_work_bytes.argtypes = [i64_, i64_, i64_, i64_]
+            l.clb_maxsim_batch_half.restype = ci
+            l.clb_maxsim_batch_half.argtypes = [ci, vp, ci, i64_, i64_, i64_, vp, ci, i64_, vp, i64_, vp, vp]
+            l.clb_maxsim_batch_half_device.restype = ci
+            l.clb_maxsim_batch_half_device.argtypes = [ci, vp, ci, i64_, i64_, i64_, vp, ci, i64_, vp, i64_, vp, vp, vp, i64_, vp]
         if hasattr(l, "clb_debug_nearest"):
             l.clb_debug_nearest_scratch_create.restype = ci
             l.clb_debug_nearest_scratch_create.argtypes = [ci, C.POINTER(vp)]

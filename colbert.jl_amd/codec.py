@@ -98,12 +98,38 @@ def _stream_of(t):
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
-def maxsim_batch(Q, D, doclens, owner=None, device: int = 0):
+F32, F16, BF16 = 0, 1, 2                                      # CLB_F32 / CLB_F16 / CLB_BF16 (include/colbert_hip.h)
+
+
+def to_bfloat16_bits(x) -> np.ndarray:
+    """float32 -> bfloat16 bit patterns (uint16, same shape and layout), round to nearest, ties to even; a NaN stays a quiet NaN."""
+    u = np.asarray(x, dtype=np.float32).view(np.uint32)
+    rounded = (u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    return np.where(nan, (u >> np.uint32(16)) | np.uint32(0x40), rounded).astype(np.uint16)
+
+
+def _host_16bit(a, dtype: str) -> np.ndarray:
+    """`a` rounded to nearest-even into `dtype`, column-major: the 16-bit host array clb_maxsim_batch_half takes"""
+    return colmajor(a, np.float16) if dtype == "float16" else np.asfortranarray(to_bfloat16_bits(colmajor(a, np.float32)))
+
+
+def maxsim_batch(Q, D, doclens, owner=None, device: int = 0, dtype=None):
     """maxsim (ranking.jl:69-86) of N un-indexed passages for a batch of queries in one call (clb_maxsim_batch): Q (dim, T, B),
     D (dim, n) -- the passages' embeddings back to back --, doclens [N].  `owner` [N], 0-based: passage j is scored against
     query owner[j] only -> (N,) float32; without it every query scores every passage -> (N, B).  Each score has the bits of
-    `maxsim(Q[:, :, q], D_j)`."""
-    q = colmajor(Q, np.float32); d = colmajor(D, np.float32)
+    `maxsim(Q[:, :, q], D_j)`.
+    dtype="float16" / "bfloat16" (implied by an np.float16 D): Q and D are rounded to nearest-even into that type, uploaded in 16
+    bits and multiplied by the 16-bit MFMA kernel (clb_maxsim_batch_half): exact products summed in fp32, within the bound of
+    DESIGN 4.2a of the float64 value on the rounded operands -- not the oracle's bits."""
+    if dtype is None and getattr(D, "dtype", None) == np.float16:
+        dtype = "float16"
+    if dtype not in (None, "float16", "bfloat16"):
+        raise ValueError("dtype must be None, 'float16' or 'bfloat16'")
+    if dtype is None:
+        q = colmajor(Q, np.float32); d = colmajor(D, np.float32)
+    else:
+        q = _host_16bit(Q, dtype); d = _host_16bit(D, dtype)
     if q.ndim != 3:
         raise ValueError("Q must be (dim, T, B)")
     dl = np.ascontiguousarray(doclens, dtype=np.int64)
@@ -112,8 +138,14 @@ def maxsim_batch(Q, D, doclens, owner=None, device: int = 0):
         raise ValueError("owner must hold one query number per passage")
     dim, T, B = q.shape
     scores = np.zeros(dl.size if ow is not None else (dl.size, B), dtype=np.float32, order="F")
-    check(lib().clb_maxsim_batch(device, fptr(q), i64(dim), i64(T), i64(B), fptr(d), i64(d.shape[1] if d.ndim == 2 else 0),
-                                 fptr(dl), i64(dl.size), fptr(ow) if ow is not None else None, fptr(scores)))
+    n_D = i64(d.shape[1] if d.ndim == 2 else 0)
+    if dtype is None:
+        check(lib().clb_maxsim_batch(device, fptr(q), i64(dim), i64(T), i64(B), fptr(d), n_D,
+                                     fptr(dl), i64(dl.size), fptr(ow) if ow is not None else None, fptr(scores)))
+    else:
+        ty = F16 if dtype == "float16" else BF16
+        check(lib().clb_maxsim_batch_half(device, fptr(q), ty, i64(dim), i64(T), i64(B), fptr(d), ty, n_D,
+                                          fptr(dl), i64(dl.size), fptr(ow) if ow is not None else None, fptr(scores)))
     return scores
 
 
@@ -123,9 +155,15 @@ def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, st
     doc_embeddings_packed_device return --, owner int32 (N,) or None; all contiguous CUDA tensors.  Returns `out`: float32 (N,)
     with owners, else (B, N) (row q = query q's scores).  Enqueued on `stream` (default: torch's current stream) and not
     waited for; with `out` and `work` (uint8, clb_maxsim_batch_work_bytes long) given it allocates nothing, so it can be
-    captured in a graph.  Device doclens are not validated: see include/colbert_hip.h for what bad ones score."""
+    captured in a graph.  Device doclens are not validated: see include/colbert_hip.h for what bad ones score.
+    A float16 / bfloat16 d_D takes the 16-bit kernel (clb_maxsim_batch_half_device): d_Q float32 (rounded on the device) or
+    d_D's dtype, `work` clb_maxsim_batch_half_work_bytes long."""
     import torch
-    q = _dev_rows(d_Q, torch.float32); d = _dev_rows(d_D, torch.float32); dl = _dev_rows(d_doclens, torch.int64)
+    half = {torch.float16: F16, torch.bfloat16: BF16}.get(d_D.dtype)
+    if half is not None and d_Q.dtype not in (torch.float32, d_D.dtype):
+        raise ValueError(f"d_Q must be float32 or {d_D.dtype}, got {d_Q.dtype}")
+    q = _dev_rows(d_Q, None if half is not None else torch.float32)
+    d = _dev_rows(d_D, None if half is not None else torch.float32); dl = _dev_rows(d_doclens, torch.int64)
     if q.dim() != 3 or d.dim() != 2 or d.shape[1] != q.shape[2]:
         raise ValueError("d_Q must be (B, T, dim) and d_D (n, dim)")
     B, T, dim = (int(x) for x in q.shape)
@@ -133,7 +171,10 @@ def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, st
     ow = None if owner is None else _dev_rows(owner, torch.int32)
     if ow is not None and ow.numel() != N:
         raise ValueError("owner must hold one query number per passage")
-    need = int(lib().clb_maxsim_batch_work_bytes(i64(N), i64(B), i64(T)))
+    if half is None:
+        need = int(lib().clb_maxsim_batch_work_bytes(i64(N), i64(B), i64(T)))
+    else:
+        need = int(lib().clb_maxsim_batch_half_work_bytes(i64(N), i64(B), i64(T), i64(dim)))
     if out is None:
         out = torch.empty(N if ow is not None else (B, N), dtype=torch.float32, device=q.device)
     if work is None:
@@ -142,10 +183,14 @@ def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, st
     if o.numel() != (N if ow is not None else N * B):
         raise ValueError("out: one score per passage (owned) or per (query, passage)")
     st = torch.cuda.current_stream(q.device).cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
-    check(lib().clb_maxsim_batch_device(q.device.index, C.c_void_p(q.data_ptr()), i64(dim), i64(T), i64(B), C.c_void_p(d.data_ptr()),
-                                        i64(d.shape[0]), C.c_void_p(dl.data_ptr()), i64(N),
-                                        C.c_void_p(ow.data_ptr()) if ow is not None else None, C.c_void_p(o.data_ptr()),
-                                        C.c_void_p(wk.data_ptr()), i64(wk.numel() * wk.element_size()), C.c_void_p(st)))
+    tail = (C.c_void_p(dl.data_ptr()), i64(N), C.c_void_p(ow.data_ptr()) if ow is not None else None, C.c_void_p(o.data_ptr()),
+            C.c_void_p(wk.data_ptr()), i64(wk.numel() * wk.element_size()), C.c_void_p(st))
+    if half is None:
+        check(lib().clb_maxsim_batch_device(q.device.index, C.c_void_p(q.data_ptr()), i64(dim), i64(T), i64(B), C.c_void_p(d.data_ptr()),
+                                            i64(d.shape[0]), *tail))
+    else:
+        check(lib().clb_maxsim_batch_half_device(q.device.index, C.c_void_p(q.data_ptr()), F32 if q.dtype == torch.float32 else half,
+                                                 i64(dim), i64(T), i64(B), C.c_void_p(d.data_ptr()), half, i64(d.shape[0]), *tail))
     return out
 
 

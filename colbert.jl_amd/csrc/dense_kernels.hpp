@@ -95,6 +95,47 @@ __device__ __forceinline__ void dense_tile_max(const dense_f32x4 acc, const int*
     }
 }
 
+// The group's offsets and owners into the LDS head and every maximum to -Inf; the barrier after it is the caller's.
+__device__ __forceinline__ void dense_group_begin(int64_t* __restrict__ s_off, int* __restrict__ s_own, uint32_t* __restrict__ s_pm,
+                                                  const int64_t* __restrict__ off, const int32_t* __restrict__ owner, int64_t p0,
+                                                  int np, int pm_words) {
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    for (int i = tid; i <= np; i += nthr) s_off[i] = off[p0 + i];
+    for (int i = tid; i < np; i += nthr) s_own[i] = owner ? owner[p0 + i] : 0;
+    const uint32_t key_ninf = f32_order_key(kNegInf);
+    for (int i = tid; i < pm_words; i += nthr) s_pm[i] = key_ninf;
+}
+
+// The passage of every row of the step of CH rows that begins at row c: the last p with off[p] <= row; -1 past n_rows.
+__device__ __forceinline__ void dense_step_passages(const int64_t* __restrict__ s_off, int* __restrict__ s_rowp, int64_t c, int n_rows,
+                                                    int CH, int np) {
+    for (int i = threadIdx.x; i < CH; i += blockDim.x) {
+        int p = -1;
+        if (i < n_rows) {
+            const int64_t e = c + i;
+            int a = 0, b = np;                          // s_off[a] <= e < s_off[b]
+            while (b - a > 1) {
+                const int m = (a + b) >> 1;
+                if (s_off[m] <= e) a = m; else b = m;
+            }
+            p = a;
+        }
+        s_rowp[i] = p;
+    }
+}
+
+// one ordered fp32 sum per (query, passage): acc = 0; acc = acc + max_t, t ascending (ranking.jl:83)
+__device__ __forceinline__ void dense_sum_maxima(const uint32_t* __restrict__ s_pm, int nq, int np, int G, int TP, int T, bool owned,
+                                                 int64_t p0, int q0, int64_t N, float* __restrict__ scores) {
+    for (int i = threadIdx.x; i < nq * np; i += blockDim.x) {
+        const int ql = i / np, p = i - ql * np;
+        const uint32_t* pm = s_pm + (ql * G + p) * TP;
+        float acc = 0.f;
+        for (int t = 0; t < T; ++t) acc = acc + f32_from_order_key(pm[t]);
+        scores[owned ? p0 + p : (int64_t)(q0 + ql) * N + p0 + p] = acc;
+    }
+}
+
 // KS = dim / 4 when the A and B operands live in registers (dim 128: KS 32), 0 = any dim, k walked at run time.
 // grid (ceil(N / G), owned ? 1 : ceil(B / QB)); block 64 * nw, nw waves of 16 rows each;
 // dynamic LDS = kDenseHeadBytes + 4 * (owned ? 1 : QB) * G * (T | 1) rounded up to 16 + 4 * 16 nw * dense_row_stride(dim).
@@ -119,10 +160,7 @@ static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const float* _
     const int pm_words = (owned ? 1 : QB) * G * TP;
     float* s_d = reinterpret_cast<float*>(dense_smem + kDenseHeadBytes + ((size_t)pm_words * 4 + 15) / 16 * 16);
 
-    for (int i = tid; i <= np; i += nthr) s_off[i] = off[p0 + i];
-    for (int i = tid; i < np; i += nthr) s_own[i] = owned ? owner[p0 + i] : 0;
-    const uint32_t key_ninf = f32_order_key(kNegInf);
-    for (int i = tid; i < pm_words; i += nthr) s_pm[i] = key_ninf;
+    dense_group_begin(s_off, s_own, s_pm, off, owner, p0, np, pm_words);
     __syncthreads();
     const int64_t lo = s_off[0], hi = s_off[np];
 
@@ -134,19 +172,7 @@ static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const float* _
             const int row = i / dim4, c4 = i - row * dim4;
             *reinterpret_cast<float4*>(s_d + row * stride + 4 * c4) = src[i];
         }
-        for (int i = tid; i < CH; i += nthr) {             // the passage of every row: the last p with off[p] <= e
-            int p = -1;
-            if (i < n_rows) {
-                const int64_t e = c + i;
-                int a = 0, b = np;                          // s_off[a] <= e < s_off[b]
-                while (b - a > 1) {
-                    const int m = (a + b) >> 1;
-                    if (s_off[m] <= e) a = m; else b = m;
-                }
-                p = a;
-            }
-            s_rowp[i] = p;
-        }
+        dense_step_passages(s_off, s_rowp, c, n_rows, CH, np);
         __syncthreads();
 
         const int rb = 16 * w;                              // this wave's rows of the step
@@ -199,14 +225,7 @@ static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const float* _
         __syncthreads();                                    // the step's rows and passages are read; the next step overwrites them
     }
 
-    // one ordered fp32 sum per (query, passage): acc = 0; acc = acc + max_t, t ascending (ranking.jl:83)
-    for (int i = tid; i < nq * np; i += nthr) {
-        const int ql = i / np, p = i - ql * np;
-        const uint32_t* pm = s_pm + (ql * G + p) * TP;
-        float acc = 0.f;
-        for (int t = 0; t < T; ++t) acc = acc + f32_from_order_key(pm[t]);
-        scores[owned ? p0 + p : (int64_t)(q0 + ql) * N + p0 + p] = acc;
-    }
+    dense_sum_maxima(s_pm, nq, np, G, TP, T, owned, p0, q0, N, scores);
 }
 
 }  // namespace clb

@@ -849,6 +849,27 @@ int clb_maxsim_batch_device(int device, const float* d_Q, int64_t dim, int64_t T
                             void* d_work, int64_t work_bytes, void* hip_stream);
 int clb_maxsim_batch(int device, const float* Q, int64_t dim, int64_t T, int64_t B, const float* D, int64_t n_D,
                      const int64_t* doclens, int64_t N, const int32_t* owner, float* scores);
+/* The same call on embeddings stored in 16 bits (dense_half_kernels.hpp): d_D (dim, n_D) in d_type = CLB_F16 or CLB_BF16;
+ * d_Q (dim, T, B) in q_type = CLB_F32 (the encoder's output: rounded to nearest-even into d_type on the device first, in the
+ * work buffer) or in d_type, used as it is.  Any other pair of types is CLB_EUNSUPPORTED.  Shapes, scores and owners as above.
+ * Arithmetic: the products of the 16-bit operands are exact in fp32 and summed in fp32 by v_mfma_f32_16x16x32_f16 / _bf16, the
+ * K-blocks of 32 ascending from +0; the maximum per token is exact; acc = 0; acc = acc + max_t for t ascending.  That is not
+ * clb_maxsim's chain: a score lies within 2 dim u sum_t |q_t| max_r |d_r| + T u sum_t |max_t|, u = 2^-23, of the float64 value on
+ * the rounded operands, and its bits depend on nothing but its own query and passage (not on the other passages, the form or Q's
+ * type).  fp16 subnormals, NaNs and signed-zero ties are outside the claim.  Served: dim % 8 == 0, 8 <= dim <= 1024 (tuned for
+ * 128), 1 <= T <= 128, B >= 1, N >= 0, else CLB_EUNSUPPORTED; d_Q, d_D and d_work 16-byte aligned.  Every other contract is
+ * clb_maxsim_batch_device's / clb_maxsim_batch's: argument errors before any launch, stream-ordered, no host wait, no
+ * allocation (d_work: clb_maxsim_batch_half_work_bytes bytes -- the offsets and the rounded Q), capturable, clamped doclens, -Inf
+ * for a passage without a readable row or with an owner outside the batch; the host call (Q and D host buffers in the named
+ * types) validates first.  Not part of the Julia shim. */
+enum { CLB_F32 = 0, CLB_F16 = 1, CLB_BF16 = 2 };
+int64_t clb_maxsim_batch_half_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim);
+int clb_maxsim_batch_half_device(int device, const void* d_Q, int q_type, int64_t dim, int64_t T, int64_t B,
+                                 const void* d_D, int d_type, int64_t n_D, const int64_t* d_doclens, int64_t N,
+                                 const int32_t* d_owner /* NULL: all pairs */, float* d_scores,
+                                 void* d_work, int64_t work_bytes, void* hip_stream);
+int clb_maxsim_batch_half(int device, const void* Q, int q_type, int64_t dim, int64_t T, int64_t B, const void* D, int d_type,
+                          int64_t n_D, const int64_t* doclens, int64_t N, const int32_t* owner, float* scores);
 /* compress_into_codes!  (residual.jl:67-81) */
 int clb_compress_into_codes(int device, uint32_t* codes, int64_t n_codes, const float* centroids,
                             int64_t dim, int64_t K, const float* embs, int64_t n);

@@ -10,7 +10,10 @@ replaces on this same build -- `codec.maxsim` once per query from host arrays (h
 Rates: the bytes the call must read (D, Q, doclens, owners) over its time against `clb_measure_read_rate` taken in the
 same run, and 2 dim T rows (x B for pairs) flop over its time against `--mfma-f32-tflops` (what
 tools/microbench/mfma_f32_peak.hip printed on the same machine).  Writes one JSON file; profiles/maxsim_batch.md is
-written from it by hand.  A measurement path only: it needs a GPU and fails without one."""
+written from it by hand.  `--dtype float16 | bfloat16`: the 16-bit kernel (embeddings stored in 16 bits, fp32 queries rounded
+on the device) beside the fp32 kernel on the same values, the two interleaved in the same windows; the per-query host route
+is left out, the 16-bit bytes and `--mfma-16bit-tflops` (if given) make the rates, and the largest error / bound against the
+fp32 call's scores is reported (profiles/maxsim_batch_half.md).  A measurement path only: it needs a GPU and fails without one."""
 import argparse
 import json
 import os
@@ -42,8 +45,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--mfma-f32-tflops", type=float, default=None)
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "maxsim_batch.json"))
+    ap.add_argument("--dtype", choices=["float32", "float16", "bfloat16"], default="float32")
+    ap.add_argument("--mfma-16bit-tflops", type=float, default=None)
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    half = args.dtype != "float32"
+    args.out = args.out or os.path.join(HERE, "profiles", f"maxsim_batch_{args.dtype}.json" if half else "maxsim_batch.json")
     import torch
     import colbert_jl_amd as clb
     from colbert_jl_amd import codec
@@ -69,6 +76,20 @@ def main():
         work = torch.empty(int(clb.lib().clb_maxsim_batch_work_bytes(N, B, T)), dtype=torch.uint8, device="cuda")
         sides[name + "_device"] = (lambda d_Q=d_Q, d_D=d_D, d_l=d_l, d_o=d_o, out=out, work=work:
                                    codec.maxsim_batch_device(d_Q, d_D, d_l, owner=d_o, out=out, work=work))
+        flop = 2.0 * dim * T * rows * (1 if owner is not None else B)
+        if half:                                       # the same values stored in 16 bits; its own out and work
+            d_Dh, out_h = d_D.to(getattr(torch, args.dtype)), torch.empty_like(out)
+            work_h = torch.empty(int(clb.lib().clb_maxsim_batch_half_work_bytes(N, B, T, dim)), dtype=torch.uint8, device="cuda")
+            sides[name + "_" + args.dtype + "_device"] = (lambda d_Q=d_Q, d_Dh=d_Dh, d_l=d_l, d_o=d_o, out_h=out_h, work_h=work_h:
+                                                     codec.maxsim_batch_device(d_Q, d_Dh, d_l, owner=d_o, out=out_h, work=work_h))
+            got, want = sides[name + "_" + args.dtype + "_device"]().cpu().numpy(), sides[name + "_device"]().cpu().numpy()
+            eps = 2.0 ** (-11 if args.dtype == "float16" else -8)      # unit-norm operands: each dot moves by at most 2 eps + eps^2
+            byts = 2.0 * dim * rows + 4.0 * Q.size + 8.0 * N + (4.0 * N if owner is not None else 0)
+            work_of[name] = {"passages": N, "embeddings": rows, "flop": flop, "bytes": byts,
+                             "max_abs_difference_from_fp32": float(np.abs(got - want).max()),
+                             "operand_rounding_bound": T * (2 * eps + eps * eps)}
+            assert work_of[name]["max_abs_difference_from_fp32"] <= work_of[name]["operand_rounding_bound"], name
+            continue
         Qh = [np.asfortranarray(Q[b].T) for b in range(B)]
         Dh = np.asfortranarray(D.T)
         pids = np.arange(1, N + 1)
@@ -82,7 +103,6 @@ def main():
         sides[name + "_per_query_host"] = old
         got, want = sides[name + "_device"]().cpu().numpy(), old()
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), name      # the two routes agree bit for bit at the timed size
-        flop = 2.0 * dim * T * rows * (1 if owner is not None else B)
         byts = 4.0 * dim * rows + 4.0 * Q.size + 8.0 * N + (4.0 * N if owner is not None else 0)
         work_of[name] = {"passages": N, "embeddings": rows, "flop": flop, "bytes": byts}
 
@@ -113,14 +133,20 @@ def main():
         rot = r % len(names)
         for n in names[rot:] + names[:rot]:
             ms[n].append((device_window if n.endswith("_device") else host_window)(sides[n]))
-    out = {"tool": "tools/bench_maxsim_batch.py", "device": torch.cuda.get_device_name(0), "dim": dim, "T": T, "B": B,
+    out = {"tool": "tools/bench_maxsim_batch.py", "device": torch.cuda.get_device_name(0), "dtype": args.dtype, "dim": dim, "T": T, "B": B,
            "steps_per_window": args.steps, "read_rate_gb_s": round(read_gbs, 1), "mfma_f32_tflops": args.mfma_f32_tflops,
            "sides": {n: summary(ms[n]) for n in names}, "shapes": work_of}
     for name, w in work_of.items():
-        t = out["sides"][name + "_device"]["ms"] * 1e-3
+        t32 = out["sides"][name + "_device"]["ms"] * 1e-3
+        t = out["sides"][name + "_" + args.dtype + "_device"]["ms"] * 1e-3 if half else t32
         w["device_gb_s"] = round(w["bytes"] / t / 1e9, 1)
         w["fraction_of_read_rate"] = round(w["bytes"] / t / 1e9 / read_gbs, 4)
         w["device_tflops"] = round(w["flop"] / t / 1e12, 2)
+        if half:
+            if args.mfma_16bit_tflops:
+                w["fraction_of_mfma_16bit_rate"] = round(w["flop"] / t / 1e12 / args.mfma_16bit_tflops, 4)
+            w["fp32_over_" + args.dtype] = round(t32 / t, 3)
+            continue
         if args.mfma_f32_tflops:
             w["fraction_of_mfma_f32_rate"] = round(w["flop"] / t / 1e12 / args.mfma_f32_tflops, 4)
         w["per_query_host_over_device"] = round(out["sides"][name + "_per_query_host"]["ms"] / out["sides"][name + "_device"]["ms"], 1)
