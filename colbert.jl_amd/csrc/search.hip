@@ -447,13 +447,24 @@ void launch_topn(clb_searcher* s, Workspace& w, hipStream_t st, int B, int Tpad)
                        w.sel.as<int>(), w.topn_blocks, Tpad);
 }
 
-template <int NBITS>
-void launch_score_exact(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, int B, int T, const int* list,
-                        const int* nlist, int grid_x) {
-    hipLaunchKernelGGL(score_exact_kernel<NBITS>, dim3(grid_x, B), dim3(256), 0, st, s->centroids.as<float>(),
-                       s->weights.as<float>(), s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(),
-                       w.cand_hdr.as<uint2>(), dQ, w.ncand.as<int>(), w.scores.as<float>(), T, w.cand_cap, list,
-                       nlist);
+// The candidate arrays of a run of queries on a slot, from query b0 on: rows of w.scores, w.cand and w.cand_hdr (`cap` =
+// w.cand_cap entries per query) and w.ncand.  Every stage launcher takes them so; only cands_of writes b0 * cand_cap for them
+struct Cands { float* scores; uint32_t* pid; uint2* hdr; int* n; size_t cap; };
+inline Cands cands_of(const Workspace& w, int b0 = 0) {
+    const size_t at = (size_t)b0 * w.cand_cap;
+    return {w.scores.as<float>() + at, w.cand.as<uint32_t>() + at, w.cand_hdr.as<uint2>() + at, w.ncand.as<int>() + b0, w.cand_cap};
+}
+
+// "The listed slots, or all candidates": rows of candidate slots ([B][cap]) with their counts ([B]); null: all candidates
+struct Subset {
+    const int* list = nullptr; const int* n = nullptr;
+    explicit operator bool() const { return list != nullptr; }
+    Subset from(int b0, size_t cap) const { return list ? Subset{list + (size_t)b0 * cap, n + b0} : Subset{}; }
+};
+// ... and the rows a stage WRITES such a list to, from query b0 on: it hands them on as the Subset the next stage reads
+struct SubsetOut { int* list; int* n; operator Subset() const { return {list, n}; } };
+inline SubsetOut subset_out(const DevBuf& list, const DevBuf& n, int b0, size_t cap) {
+    return {list.as<int>() + (size_t)b0 * cap, n.as<int>() + b0};
 }
 
 int select_by_sort(clb_searcher* s, Workspace& w, hipStream_t st, const float* cells, size_t stride_t, size_t stride_c,
@@ -586,13 +597,13 @@ FilterArgs filter_args(const clb_searcher* s, const Batch& q, int b0, int n) {
 }
 
 // S3: the union of the selected IVF lists as an ascending pid list + passage headers, for the B queries from b0 on
-// (w.sel, entries 0 .. B - 1 of Tpad x NPs -> cand, cand_hdr, ncand of queries b0 ...); shared by the tuned and the
-// general-shape path, whose per-query loop calls it one query at a time and untimed
+// (w.sel, entries 0 .. B - 1 of Tpad x NPs -> c.pid, c.hdr, c.n, the candidate arrays of queries b0 ...); shared by the
+// tuned and the general-shape path, whose per-query loop calls it one query at a time and untimed
 // FILT: some query of the launch carries a filter (S3f) -- the same launches with the filter operand; false: the
 // unfiltered kernels, launched as ever
 template <bool FILT>
-int mark_and_compact_impl(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int B, int Tpad, int NPs,
-                          bool timed) {
+int mark_and_compact_impl(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, const Cands& c, int b0, int B, int Tpad,
+                          int NPs, bool timed) {
     static_assert(kScanBlock * kWordsPerThread == 1024, "mark_count_kernel writes 1024-word count blocks");
     static_assert(kSubBatch <= kFilterQueries, "the filter handles of a sub-batch travel in one kernel argument block");
     FilterOperand<FILT> fa{};
@@ -600,9 +611,6 @@ int mark_and_compact_impl(clb_searcher* s, Workspace& w, hipStream_t st, const B
     const int T = q.T, nprobe = q.nprobe;
     uint32_t* bitmap = w.bitmap.as<uint32_t>() + (size_t)b0 * w.W;
     int* blocksum = w.blocksum.as<int>() + (size_t)b0 * w.nblk_bitmap;
-    uint32_t* cand = w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap;
-    uint2* cand_hdr = w.cand_hdr.as<uint2>() + (size_t)b0 * w.cand_cap;
-    int* ncand = w.ncand.as<int>() + b0;
     const int nslices = (w.nblk_bitmap + kMarkSliceBlocks - 1) / kMarkSliceBlocks;
     const int nslices_big = (w.nblk_bitmap + kMarkSliceBlocksBig - 1) / kMarkSliceBlocksBig;
     // every slice re-reads the query's lists: beyond 16 slices (2 M passages per shard) that costs more than the atomics
@@ -635,65 +643,70 @@ int mark_and_compact_impl(clb_searcher* s, Workspace& w, hipStream_t st, const B
         // after the sliced marking the bitmap already holds marked AND filter: only a filter that IS the candidate set
         // (CLB_FILTER_ALL) still has to reach the emit kernel
         if (FILT && (!sliced || q.filt_all))
-            hipLaunchKernelGGL(bitmap_emit_kernel<FILT>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st, bitmap, blocksum, cand,
-                               s->doc_off.as<uint32_t>(), cand_hdr, w.W, w.cand_cap, ncand, fa);
+            hipLaunchKernelGGL(bitmap_emit_kernel<FILT>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st, bitmap, blocksum, c.pid,
+                               s->doc_off.as<uint32_t>(), c.hdr, w.W, c.cap, c.n, fa);
         else
-            hipLaunchKernelGGL(bitmap_emit_kernel<false>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st, bitmap, blocksum, cand,
-                               s->doc_off.as<uint32_t>(), cand_hdr, w.W, w.cand_cap, ncand);
+            hipLaunchKernelGGL(bitmap_emit_kernel<false>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st, bitmap, blocksum, c.pid,
+                               s->doc_off.as<uint32_t>(), c.hdr, w.W, c.cap, c.n);
     }
     CLB_HIP(hipGetLastError());
     return CLB_OK;
 }
 
-// entries per query of slot_pos in a call with list priors: the most candidates a listed query can have (filt_now =
-// min(list_stride, n_docs) <= cand_cap), so that the fill in front of list_slot_kernel touches no more than the lists can reach
-inline size_t slot_pos_stride(const Batch& q) { return (std::max<size_t>(q.filt_now, 1) + 3) & ~(size_t)3; }
+// List priors: the lowest list position of every candidate slot from query b0 on (w.slot_pos, list_slot_kernel) in rows of
+// `stride` entries, the most candidates a listed query can have (filt_now = min(list_stride, n_docs) <= cand_cap), so that
+// the fill in front of list_slot_kernel touches no more than the lists can reach
+struct SlotPos { int* pos; size_t stride; };
+inline SlotPos slot_pos_of(const Workspace& w, const Batch& q, int b0) {
+    const size_t stride = (std::max<size_t>(q.filt_now, 1) + 3) & ~(size_t)3;
+    return {w.slot_pos.as<int>() + (size_t)b0 * stride, stride};
+}
 
 // S3l: the candidates of the B queries from b0 on are the caller's lists (list_kernels.hpp) -- the listed passages go into
 // the candidate bitmap, and the compaction reads it through the handle's live bitmap as every query's filter word
 // (CLB_FILTER_CANDIDATES: marked AND filter), which drops the passages without embeddings as CLB_FILTER_ALL drops them
-int list_and_compact(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int B, bool timed) {
+int list_and_compact(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, const Cands& c, int b0, int B, bool timed) {
     FilterArgs fa{};
     fa.live = s->live.as<uint32_t>();
     for (int i = 0; i < B && i < kFilterQueries; ++i) fa.bits[i] = fa.live;
     fa.all = 0;
     const int L = (int)q.list_stride;
+    const int64_t* pids = q.d_list_pids + (size_t)b0 * L;
+    const int64_t* lens = q.d_list_lens + b0;
     uint32_t* bitmap = w.bitmap.as<uint32_t>() + (size_t)b0 * w.W;
     int* blocksum = w.blocksum.as<int>() + (size_t)b0 * w.nblk_bitmap;
     {
         Timed t(s, timed ? KID_MARK : -1, st);
-        hipLaunchKernelGGL(list_mark_kernel, dim3((L + 255) / 256, B), dim3(256), 0, st, q.d_list_pids + (size_t)b0 * L,
-                           q.d_list_lens + b0, L, s->pid_offset, (int)s->n_docs, bitmap, w.W);
+        hipLaunchKernelGGL(list_mark_kernel, dim3((L + 255) / 256, B), dim3(256), 0, st, pids, lens, L, s->pid_offset,
+                           (int)s->n_docs, bitmap, w.W);
     }
     {
         Timed t(s, timed ? KID_COMPACT : -1, st);
         hipLaunchKernelGGL(bitmap_count_kernel<true>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st, bitmap, blocksum, w.W, fa);
-        hipLaunchKernelGGL(bitmap_emit_kernel<true>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st, bitmap, blocksum,
-                           w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap, s->doc_off.as<uint32_t>(),
-                           w.cand_hdr.as<uint2>() + (size_t)b0 * w.cand_cap, w.W, w.cand_cap, w.ncand.as<int>() + b0, fa);
+        hipLaunchKernelGGL(bitmap_emit_kernel<true>, dim3(w.nblk_bitmap, B), dim3(kScanBlock), 0, st, bitmap, blocksum, c.pid,
+                           s->doc_off.as<uint32_t>(), c.hdr, w.W, c.cap, c.n, fa);
     }
     if (q.d_list_prior) {
         // with list priors: the lowest list position of every candidate slot (list_slot_kernel), which the boosts read the
         // values through.  A listed query has at most filt_now candidates: only that many slots of a row are filled and read
         Timed t(s, timed ? KID_COMPACT : -1, st);
-        const size_t ps = slot_pos_stride(q);
-        int* slot_pos = w.slot_pos.as<int>() + (size_t)b0 * ps;
-        hipLaunchKernelGGL(list_slot_fill_kernel, dim3((unsigned)(((size_t)B * ps + 255) / 256)), dim3(256), 0, st, slot_pos,
-                           (size_t)B * ps);
-        hipLaunchKernelGGL(list_slot_kernel, dim3((L + 255) / 256, B), dim3(256), 0, st, q.d_list_pids + (size_t)b0 * L,
-                           q.d_list_lens + b0, L, s->pid_offset, (int)s->n_docs, w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap,
-                           w.ncand.as<int>() + b0, w.cand_cap, slot_pos, ps);
+        const SlotPos sp = slot_pos_of(w, q, b0);
+        hipLaunchKernelGGL(list_slot_fill_kernel, dim3((unsigned)(((size_t)B * sp.stride + 255) / 256)), dim3(256), 0, st, sp.pos,
+                           (size_t)B * sp.stride);
+        hipLaunchKernelGGL(list_slot_kernel, dim3((L + 255) / 256, B), dim3(256), 0, st, pids, lens, L, s->pid_offset,
+                           (int)s->n_docs, c.pid, c.n, c.cap, sp.pos, sp.stride);
     }
     CLB_HIP(hipGetLastError());
     return CLB_OK;
 }
 
 int mark_and_compact(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int B, int Tpad, int NPs, bool timed) {
-    if (q.d_list_pids) return list_and_compact(s, w, st, q, b0, B, timed);
+    const Cands c = cands_of(w, b0);
+    if (q.d_list_pids) return list_and_compact(s, w, st, q, c, b0, B, timed);
     bool filt = false;
     for (int b = b0; q.filt && b < b0 + B; ++b) filt |= q.filt[b] != nullptr;
-    return filt ? mark_and_compact_impl<true>(s, w, st, q, b0, B, Tpad, NPs, timed)
-                : mark_and_compact_impl<false>(s, w, st, q, b0, B, Tpad, NPs, timed);
+    return filt ? mark_and_compact_impl<true>(s, w, st, q, c, b0, B, Tpad, NPs, timed)
+                : mark_and_compact_impl<false>(s, w, st, q, c, b0, B, Tpad, NPs, timed);
 }
 
 int check_search_args(const clb_searcher* s, int64_t T, int64_t B, int64_t nprobe, int64_t k) {
@@ -733,33 +746,32 @@ inline const int* reported_count(const Workspace& w, const Batch& q) { return q.
 // emit kernel writes the short-result flag and the candidate count; rocPRIM's temporary storage lives in the workspace
 // slot (g_sort_tmp, sized on first use), so the sort is only enqueued -- no allocation and no host synchronisation per
 // query.  The price of keeping the count on the device: the sort covers cand_cap keys, not the query's own count.
-int topk_by_sort(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b, const int* list, const int* nlist) {
+// c / sub: the rows of query b of the sub-batch (cands_of, Subset::from).
+int topk_by_sort(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, const Cands& c, Subset sub, int b) {
     const int k = q.k;
-    const int cap = (int)w.cand_cap;
-    const float* sc = w.scores.as<float>() + (size_t)b * w.cand_cap;
-    const int* lst = list ? list + (size_t)b * w.cand_cap : nullptr;
-    const int* n_ptr = list ? nlist + b : w.ncand.as<int>() + b;
+    const int cap = (int)c.cap;
+    const int* n_ptr = sub ? sub.n : c.n;
     CLB_TRY(w.g_keys.ensure(sizeof(uint64_t) * std::max(cap, 1)));
     CLB_TRY(w.g_keys2.ensure(sizeof(uint64_t) * std::max(cap, 1)));
-    hipLaunchKernelGGL(generic_topk_keys_kernel, dim3((cap + 255) / 256), dim3(256), 0, st, sc, lst, n_ptr, cap,
+    hipLaunchKernelGGL(generic_topk_keys_kernel, dim3((cap + 255) / 256), dim3(256), 0, st, c.scores, sub.list, n_ptr, cap,
                        w.g_keys.as<unsigned long long>());
     CLB_TRY(sort_keys_u64(w.g_keys.as<uint64_t>(), w.g_keys2.as<uint64_t>(), (size_t)cap, st, &w.g_sort_tmp));
     hipLaunchKernelGGL(generic_topk_emit_kernel, dim3((std::max(k, 1) + 255) / 256), dim3(256), 0, st,
-                       w.g_keys2.as<unsigned long long>(), sc, w.cand.as<uint32_t>() + (size_t)b * w.cand_cap, lst, n_ptr,
-                       reported_count(w, q) + b, k, s->pid_offset, q.d_out_pids + (size_t)b * k, q.d_out_scores + (size_t)b * k,
-                       w.flags.as<int>() + b, q.d_n_cand ? q.d_n_cand + b : nullptr);
+                       w.g_keys2.as<unsigned long long>(), c.scores, c.pid, sub.list, n_ptr, reported_count(w, q) + b, k, s->pid_offset,
+                       q.d_out_pids + (size_t)b * k, q.d_out_scores + (size_t)b * k, w.flags.as<int>() + b,
+                       q.d_n_cand ? q.d_n_cand + b : nullptr);
     CLB_HIP(hipGetLastError());
     return CLB_OK;
 }
 
-// S7g-a for queries b0 .. b0 + n - 1 (group_collapse_kernel): the best slot of every group among the listed slots (list /
-// nlist, [B][cand_cap] / [B]) or, with list == nullptr, among all candidates, to out_list / out_n of the same layout
-void launch_collapse(Workspace& w, hipStream_t st, const Batch& q, int b0, int n, const int* list, const int* nlist,
-                     int* out_list, int* out_n) {
-    hipLaunchKernelGGL(group_collapse_kernel, dim3(n), dim3(1024), 0, st, w.scores.as<float>() + (size_t)b0 * w.cand_cap,
-                       w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap, w.ncand.as<int>() + b0,
-                       list ? list + (size_t)b0 * w.cand_cap : nullptr, list ? nlist + b0 : nullptr, q.grp->gid.as<uint32_t>(),
-                       w.cand_cap, out_list + (size_t)b0 * w.cand_cap, out_n + b0);
+// In the launchers below c and sub start at the first query of the launch, n is its number of queries (the grid) and b0 that
+// first query's place in the sub-batch, for the arrays that belong to the sub-batch.
+// S7g-a (group_collapse_kernel): the best slot of every group among the listed slots or, with a null sub, among all
+// candidates, to `out`, which the caller reads on as a Subset
+Subset launch_collapse(const Cands& c, Subset sub, hipStream_t st, const Batch& q, int n, SubsetOut out) {
+    hipLaunchKernelGGL(group_collapse_kernel, dim3(n), dim3(1024), 0, st, c.scores, c.pid, c.n, sub.list, sub.n,
+                       q.grp->gid.as<uint32_t>(), c.cap, out.list, out.n);
+    return out;
 }
 
 // the global group index of every result pid and the edge groups of every query's candidate list (group_result_kernel)
@@ -771,99 +783,99 @@ void launch_result_groups(const clb_searcher* s, Workspace& w, hipStream_t st, c
                        d_out_gids, d_edge_gids);
 }
 
-// S7g-f for queries b0 .. b0 + n - 1 of a call with hits (group_hits_kernel; nothing otherwise): the per_group best passages
-// of every result among the exact-scored set -- the re-scored list (list / nlist) or, with list == nullptr, all candidates
-void launch_hits(const clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int n, const int* list,
-                 const int* nlist) {
+// S7g-f of a call with hits (group_hits_kernel; nothing otherwise): the per_group best passages of every result among the
+// exact-scored set -- the re-scored list or, with a null sub, all candidates
+void launch_hits(const clb_searcher* s, const Cands& c, Subset sub, hipStream_t st, const Batch& q, int b0, int n) {
     if (q.per_group <= 0) return;
     const int64_t waves = (int64_t)n * q.k;
-    hipLaunchKernelGGL(group_hits_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st,
-                       w.scores.as<float>() + (size_t)b0 * w.cand_cap, w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap,
-                       w.ncand.as<int>() + b0, list ? list + (size_t)b0 * w.cand_cap : nullptr, list ? nlist + b0 : nullptr,
-                       q.grp->gid.as<uint32_t>(), s->n_docs, q.d_out_pids + (size_t)b0 * q.k, n, q.k, q.per_group, w.cand_cap,
-                       s->pid_offset, q.d_hit_pids + (size_t)b0 * q.k * q.per_group, q.d_hit_scores + (size_t)b0 * q.k * q.per_group);
+    const size_t hits_at = (size_t)b0 * q.k * q.per_group;
+    hipLaunchKernelGGL(group_hits_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, c.scores, c.pid, c.n, sub.list, sub.n,
+                       q.grp->gid.as<uint32_t>(), s->n_docs, q.d_out_pids + (size_t)b0 * q.k, n, q.k, q.per_group, c.cap,
+                       s->pid_offset, q.d_hit_pids + hits_at, q.d_hit_scores + hits_at);
 }
 
-// S7 for queries b0 .. b0 + n - 1: the single-work-group select + sort of topk_kernel, one work-group per query, or for
-// k above it a full stable sort per query.  list / nlist: the two-pass mode's re-scored passages ([B][cand_cap] / [B]) or
-// nullptr; ranked: topk_rank_kernel has already written the queries with short lists
-int launch_topk(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int n, const int* list, const int* nlist,
-                int ranked) {
+// S7: the single-work-group select + sort of topk_kernel, one work-group per query, or for k above it a full stable sort
+// per query.  sub: the slots to rank, or null for all candidates; ranked: topk_rank_kernel has already written the
+// queries with short lists
+int launch_topk(clb_searcher* s, Workspace& w, const Cands& c, Subset sub, hipStream_t st, const Batch& q, int b0, int n, int ranked) {
     if (q.k > kMaxTopK) {
-        for (int b = b0; b < b0 + n; ++b) CLB_TRY(topk_by_sort(s, w, st, q, b, list, nlist));
+        for (int i = 0; i < n; ++i) CLB_TRY(topk_by_sort(s, w, st, q, cands_of(w, b0 + i), sub.from(i, c.cap), b0 + i));
         return CLB_OK;
     }
     const int kpow2 = next_pow2(q.k);
     allow_large_topk_lds();
-    hipLaunchKernelGGL(topk_kernel, dim3(n), dim3(1024), sizeof(unsigned long long) * kpow2, st,
-                       w.scores.as<float>() + (size_t)b0 * w.cand_cap, w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap,
-                       reported_count(w, q) + b0, list ? list + (size_t)b0 * w.cand_cap : nullptr, list ? nlist + b0 : nullptr, q.k, kpow2,
-                       w.cand_cap, s->pid_offset, q.d_out_pids + (size_t)b0 * q.k, q.d_out_scores + (size_t)b0 * q.k,
-                       w.flags.as<int>() + b0, q.d_n_cand ? q.d_n_cand + b0 : nullptr, ranked);
+    hipLaunchKernelGGL(topk_kernel, dim3(n), dim3(1024), sizeof(unsigned long long) * kpow2, st, c.scores, c.pid,
+                       reported_count(w, q) + b0, sub.list, sub.n, q.k, kpow2, c.cap, s->pid_offset, q.d_out_pids + (size_t)b0 * q.k,
+                       q.d_out_scores + (size_t)b0 * q.k, w.flags.as<int>() + b0, q.d_n_cand ? q.d_n_cand + b0 : nullptr, ranked);
     CLB_HIP(hipGetLastError());
     return CLB_OK;
 }
 
-// P1 for queries b0 .. b0 + n - 1 of a call with a prior (prior_boost_kernel; nothing otherwise): the scores of the listed
-// slots (list / nlist) or, with list == nullptr, of all candidates become score + weight * value; mabs: prior_tau's M, or nullptr
+// P1 of a call with a prior (prior_boost_kernel; nothing otherwise): the scores of the listed slots or, with a null sub, of
+// all candidates become score + weight * value; mabs: where the queries' largest |boosted score| goes (prior_tau's M), or nullptr
 // With list priors (q.d_list_prior, never together with q.prior) the same kernel reads the term of a slot from the query's row
 // of the value block, at the position list_slot_kernel left in slot_pos.
-void launch_boost(Workspace& w, hipStream_t st, const Batch& q, int b0, int n, const int* list, const int* nlist, float* mabs) {
-    if (!q.prior && !q.d_list_prior) return;
-    float* scores = w.scores.as<float>() + (size_t)b0 * w.cand_cap;
-    const uint32_t* cand = w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap;
-    const int* l = list ? list + (size_t)b0 * w.cand_cap : nullptr;
-    const int* nl = list ? nlist + b0 : nullptr;
-    if (q.prior) {
-        hipLaunchKernelGGL(prior_boost_kernel<false>, dim3(n), dim3(1024), 0, st, scores, cand, w.ncand.as<int>() + b0, l, nl,
-                           PriorTerm{q.prior->values.as<float>(), nullptr, 0, 0}, q.prior_weight, w.cand_cap,
-                           mabs ? mabs + b0 : nullptr);
-        return;
+void launch_boost(const Workspace& w, const Cands& c, Subset sub, hipStream_t st, const Batch& q, int b0, int n, float* mabs) {
+    if (q.prior)
+        hipLaunchKernelGGL(prior_boost_kernel<false>, dim3(n), dim3(1024), 0, st, c.scores, c.pid, c.n, sub.list, sub.n,
+                           PriorTerm{q.prior->values.as<float>(), nullptr, 0, 0}, q.prior_weight, c.cap, mabs);
+    else if (q.d_list_prior) {
+        const SlotPos sp = slot_pos_of(w, q, b0);
+        hipLaunchKernelGGL(prior_boost_kernel<true>, dim3(n), dim3(1024), 0, st, c.scores, c.pid, c.n, sub.list, sub.n,
+                           PriorTerm{q.d_list_prior + (size_t)b0 * q.list_stride, sp.pos, (int)q.list_stride, sp.stride},
+                           q.prior_weight, c.cap, mabs);
     }
-    const size_t ps = slot_pos_stride(q);
-    hipLaunchKernelGGL(prior_boost_kernel<true>, dim3(n), dim3(1024), 0, st, scores, cand, w.ncand.as<int>() + b0, l, nl,
-                       PriorTerm{q.d_list_prior + (size_t)b0 * q.list_stride, w.slot_pos.as<int>() + (size_t)b0 * ps,
-                                 (int)q.list_stride, ps},
-                       q.prior_weight, w.cand_cap, mabs ? mabs + b0 : nullptr);
 }
 
-// A2 for queries b0 .. b0 + n - 1 of a call with cursors (after_filter_kernel): of the listed slots (list / nlist) or, with
-// list == nullptr, of all candidates, those after the query's cursor go to the slot's after_list / after_n, which the top-k
-// forms then rank.  The cursor arrays of q belong to the sub-batch, as list / nlist do.
-void launch_after(const clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int n, const int* list,
-                  const int* nlist) {
-    hipLaunchKernelGGL(after_filter_kernel, dim3(n), dim3(1024), 0, st, w.scores.as<float>() + (size_t)b0 * w.cand_cap,
-                       w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap, w.ncand.as<int>() + b0,
-                       list ? list + (size_t)b0 * w.cand_cap : nullptr, list ? nlist + b0 : nullptr, q.d_after_s + b0,
-                       q.d_after_p + b0, w.cand_cap, s->pid_offset, w.after_list.as<int>() + (size_t)b0 * w.cand_cap,
-                       w.after_n.as<int>() + b0);
+// A2 of a call with cursors (after_filter_kernel): of the listed slots or, with a null sub, of all candidates, those after
+// the query's cursor go to the slot's after_list / after_n, which the top-k forms then rank
+Subset launch_after(const clb_searcher* s, const Workspace& w, const Cands& c, Subset sub, hipStream_t st, const Batch& q, int b0,
+                    int n) {
+    const SubsetOut out = subset_out(w.after_list, w.after_n, b0, c.cap);
+    hipLaunchKernelGGL(after_filter_kernel, dim3(n), dim3(1024), 0, st, c.scores, c.pid, c.n, sub.list, sub.n, q.d_after_s + b0,
+                       q.d_after_p + b0, c.cap, s->pid_offset, out.list, out.n);
+    return out;
 }
 
-// L2 for queries b0 .. b0 + n - 1 of a call that asks for list scores (list_scores_kernel; nothing otherwise), behind the
-// exact scores of all their candidates and the boost of a prior
-void launch_list_scores(const clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int n) {
+// L2 of a call that asks for list scores (list_scores_kernel; nothing otherwise), behind the exact scores of all the
+// queries' candidates and the boost of a prior
+void launch_list_scores(const clb_searcher* s, const Cands& c, hipStream_t st, const Batch& q, int b0, int n) {
     if (!q.d_list_scores) return;
-    const int L = (int)q.list_stride;
-    hipLaunchKernelGGL(list_scores_kernel, dim3((L + 255) / 256, n), dim3(256), 0, st, q.d_list_pids + (size_t)b0 * L,
-                       q.d_list_lens + b0, L, s->pid_offset, (int)s->n_docs, w.cand.as<uint32_t>() + (size_t)b0 * w.cand_cap,
-                       w.ncand.as<int>() + b0, w.scores.as<float>() + (size_t)b0 * w.cand_cap, w.cand_cap,
-                       q.d_list_scores + (size_t)b0 * L);
+    const size_t L = (size_t)q.list_stride;
+    hipLaunchKernelGGL(list_scores_kernel, dim3(((int)L + 255) / 256, n), dim3(256), 0, st, q.d_list_pids + b0 * L, q.d_list_lens + b0,
+                       (int)L, s->pid_offset, (int)s->n_docs, c.pid, c.n, c.scores, c.cap, q.d_list_scores + b0 * L);
 }
 
-// S7 of the general-shape path for queries b0 .. b0 + n - 1, the exact scores of all their candidates in place (with a
-// prior: boosted first; with cursors: the candidates after them) -- with a grouping: one collapse, then the top-k forms
-// rank its list
-int topk_of(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int n) {
-    launch_boost(w, st, q, b0, n, nullptr, nullptr, nullptr);
-    launch_list_scores(s, w, st, q, b0, n);
-    if (q.d_after_s) {
-        launch_after(s, w, st, q, b0, n, nullptr, nullptr);
-        return launch_topk(s, w, st, q, b0, n, w.after_list.as<int>(), w.after_n.as<int>(), 0);
+// S7 for queries b0 .. b0 + n - 1, the exact scores of `rescored` (the sub-batch's list of the two-pass mode) or, null, of
+// all their candidates in place: a prior boosts them first, with cursors only the candidates after them go on, with a
+// grouping the best of every group (two-pass mode: grp_n, the group count of ALL candidates, stays what the call reports).
+// tuned: the tuned path, where the stage is the profile's `topk` row (untimed for k above the single-work-group sort) and the
+// ~1.2 k listed passages of a query are ranked by kRankBlocks work-groups first (no sorting network; a query whose list is
+// longer than kRankMax falls through to topk_kernel); the general-shape path has neither
+int rank_results(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, int b0, int n, Subset rescored, bool tuned) {
+    const Cands c = cands_of(w, b0);
+    rescored = rescored.from(b0, c.cap);
+    const bool timed = tuned && q.k <= kMaxTopK;
+    if (tuned && !timed) s->prof.chain = nullptr;
+    {
+        Timed t(s, timed ? KID_TOPK : -1, st);
+        launch_boost(w, c, rescored, st, q, b0, n, nullptr);
+        launch_list_scores(s, c, st, q, b0, n);     // (a call with list scores is the exact pass: rescored is null)
+        Subset ranked = rescored;
+        if (q.d_after_s) ranked = launch_after(s, w, c, rescored, st, q, b0, n);      // (never with a grouping)
+        if (q.grp)
+            ranked = launch_collapse(c, rescored, st, q, n, rescored ? subset_out(w.grp_list2, w.grp_n2, b0, c.cap)
+                                                                     : subset_out(w.grp_list, w.grp_n, b0, c.cap));
+        const int by_rank = timed && ranked;
+        if (by_rank)
+            hipLaunchKernelGGL(topk_rank_kernel, dim3(kRankBlocks, n), dim3(1024), 0, st, c.scores, c.pid, reported_count(w, q) + b0,
+                               ranked.list, ranked.n, q.k, c.cap, s->pid_offset, q.d_out_pids + (size_t)b0 * q.k,
+                               q.d_out_scores + (size_t)b0 * q.k, w.flags.as<int>() + b0, q.d_n_cand ? q.d_n_cand + b0 : nullptr);
+        CLB_TRY(launch_topk(s, w, c, ranked, st, q, b0, n, by_rank));
     }
-    if (!q.grp) return launch_topk(s, w, st, q, b0, n, nullptr, nullptr, 0);
-    launch_collapse(w, st, q, b0, n, nullptr, nullptr, w.grp_list.as<int>(), w.grp_n.as<int>());
-    CLB_TRY(launch_topk(s, w, st, q, b0, n, w.grp_list.as<int>(), w.grp_n.as<int>(), 0));
-    launch_hits(s, w, st, q, b0, n, nullptr, nullptr);
+    if (q.grp) launch_hits(s, c, rescored, st, q, b0, n);
+    if (q.grp && q.d_out_gids)
+        launch_result_groups(s, w, st, q.grp, q.group_base, q.d_out_pids, q.B, q.k, q.d_out_gids, q.d_edge_gids);
     return CLB_OK;
 }
 
@@ -907,32 +919,31 @@ int run_search_general(clb_searcher* s, Workspace& w, hipStream_t st, const Batc
             allow_dynamic_lds(reinterpret_cast<const void*>(generic_score_mfma_fast_kernel<64>), (int)lds);
         }
         auto score_kernel = s->dim <= 128 ? generic_score_mfma_fast_kernel<32> : generic_score_mfma_fast_kernel<64>;
+        const Cands c = cands_of(w);
         hipLaunchKernelGGL(score_kernel, grid, dim3(256), lds, st, s->centroids.as<float>(), s->weights.as<float>(),
-                           s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(), w.cand_hdr.as<uint2>(), w.ncand.as<int>(), dQ,
-                           (int)s->dim, s->nbits, T, w.cand_cap, w.scores.as<float>());
+                           s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(), c.hdr, c.n, dQ, (int)s->dim, s->nbits, T, c.cap,
+                           c.scores);
         CLB_HIP(hipGetLastError());
-        return topk_of(s, w, st, q, 0, B);
+        return rank_results(s, w, st, q, 0, B, Subset{}, /*tuned=*/false);
     }
     const int grid = 1024;
     const size_t max_len = (size_t)std::max<int64_t>(s->max_doclen, 1);
     CLB_TRY(w.g_scratch.ensure(sizeof(float) * grid * max_len * s->dim));
     for (int b = 0; b < B; ++b) {
         CLB_TRY(run_retrieve_general(s, w, st, q, b));
+        const Cands c = cands_of(w, b);
+        const float* Qb = dQ + (size_t)b * T * s->dim;
         if (T <= 16 * kGenericMaxTokenGroups && s->dim % 4 == 0)
             // fp32 MFMA, one wave per passage (the canonical arithmetic of the scalar kernel, bit for bit)
             hipLaunchKernelGGL(generic_score_mfma_kernel, dim3(grid), dim3(256), sizeof(float) * ((size_t)1 << s->nbits), st,
                                s->centroids.as<float>(), s->weights.as<float>(), s->codes0.as<uint32_t>(),
-                               s->residuals.as<uint8_t>(), w.cand_hdr.as<uint2>() + (size_t)b * w.cand_cap,
-                               w.ncand.as<int>() + b, dQ + (size_t)b * T * s->dim, (int)s->dim, s->nbits, T,
-                               w.scores.as<float>() + (size_t)b * w.cand_cap);
+                               s->residuals.as<uint8_t>(), c.hdr, c.n, Qb, (int)s->dim, s->nbits, T, c.scores);
         else
             hipLaunchKernelGGL(generic_score_kernel, dim3(grid), dim3(256), sizeof(float) * T, st, s->centroids.as<float>(),
-                               s->weights.as<float>(), s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(),
-                               w.cand_hdr.as<uint2>() + (size_t)b * w.cand_cap, w.ncand.as<int>() + b,
-                               dQ + (size_t)b * T * s->dim, (int)s->dim, s->nbits, T, w.g_scratch.as<float>(), max_len,
-                               w.scores.as<float>() + (size_t)b * w.cand_cap);
+                               s->weights.as<float>(), s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(), c.hdr, c.n, Qb,
+                               (int)s->dim, s->nbits, T, w.g_scratch.as<float>(), max_len, c.scores);
         CLB_HIP(hipGetLastError());
-        CLB_TRY(topk_of(s, w, st, q, b, 1));
+        CLB_TRY(rank_results(s, w, st, q, b, 1, Subset{}, /*tuned=*/false));
     }
     return CLB_OK;
 }
@@ -946,12 +957,27 @@ constexpr size_t kWideSelectCap = 131072;
 void launch_pass1(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, dim3 grid, int B, int T) {
     auto kern = w.cell8 ? (s->gather_lds ? score_approx32_kernel<false, 1, true> : score_approx32_kernel<false, 0, true>)
                         : (s->gather_lds ? score_approx32_kernel<false, 1, false> : score_approx32_kernel<false, 0, false>);
+    const Cands c = cands_of(w);
     hipLaunchKernelGGL(kern, grid, dim3(kApproxThreads), 0, st, s->weights.as<float>(),
                        s->codeinv.as<uint32_t>(), s->residuals.as<uint8_t>(), s->cbits, s->inv_lo, s->inv_step, dQ,
-                       w.cell8 ? w.cells8.as<uint32_t>() : w.cells_q.as<uint32_t>(), w.cand_hdr.as<uint2>(), w.ncand.as<int>(),
-                       w.scores.as<float>(), (int)s->K, T, B, w.cand_cap, w.tokmax.as<uint16_t>(), (const int*)nullptr,
-                       (const int*)nullptr, (const float*)nullptr, (unsigned long long*)nullptr,
-                       (const float4*)w.tscale.as<float4>());
+                       w.cell8 ? w.cells8.as<uint32_t>() : w.cells_q.as<uint32_t>(), c.hdr, c.n, c.scores, (int)s->K, T, B, c.cap,
+                       w.tokmax.as<uint16_t>(), (const int*)nullptr, (const int*)nullptr, (const float*)nullptr,
+                       (unsigned long long*)nullptr, (const float4*)w.tscale.as<float4>());
+}
+// ... as a search launches it (the profile's `score_approx` row), the grid by the candidates a query can have
+void launch_pass1_grid(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
+    Timed t(s, KID_SCORE_APPROX, st);
+    constexpr int kWgPerGroup = 32;   // x 8 XCD groups: one 12-wave work-group per CU
+    // Grid: XCD-affine 1-D launch (all work-groups of an XCD share one query's score table in L2) for
+    // large candidate sets; for small ones (a shard of a multi-GPU run: < ~6 k candidate passages per
+    // query, estimated from the mean IVF list) a (G, B) launch whose few waves per query each get a long
+    // run of passages -- the pipeline fill otherwise dominates.
+    const double est_cand = 0.5 * q.T * q.nprobe * (double)s->n_emb / (double)std::max<int64_t>(1, s->K);
+    // work-groups per query of the (G, B) launch (0 = the 1-D launch): enough to fill the chip for small batches,
+    // eight for large ones (measured at 4 and 8 shards, B = 8 ... 256: one or two per query cost 12 % of the pass
+    // at B = 256, sixteen and more cost as much at B = 32)
+    const int gxq = est_cand < 6000.0 ? std::max(8, 256 / q.B) : 0;
+    launch_pass1(s, w, st, q.dQ, gxq > 0 && q.B > 1 ? dim3(gxq, q.B) : dim3(8 * kWgPerGroup), q.B, q.T);
 }
 // The centroid side of the single-product score table in the error bound: when this batch's table was made that way -- and,
 // on a shard of a group, whenever a shard MAY make its tables that way (the threshold tau comes from every shard's
@@ -967,33 +993,155 @@ inline BoundOperands bound_operands(const clb_searcher* s, const Workspace& w) {
     ac.dc_max = bound_dc(s, w);
     return {ac, w.have_range ? (const float4*)w.tscale.as<float4>() : (const float4*)nullptr, w.cell8 ? 1 : 0};
 }
-int launch_select(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, const float* tau_in, bool coarse_tau = false) {
+int launch_select(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, const BoundOperands& bo, const float* tau_in,
+                  bool coarse_tau = false) {
     const float* dQ = q.dQ;
     const int B = q.B, T = q.T, k = q.k;
     // by the most candidates a query of THIS sub-batch can have: a slot that once grew for a large CLB_FILTER_ALL set
     // goes on selecting its unfiltered batches as before
     const size_t most = std::max(w.ivf_cap, q.filt_now);
     const bool wide = s->wide_select == 1 || (s->wide_select < 0 && most >= kWideSelectCap);
-    const BoundOperands bo = bound_operands(s, w);
+    const Cands c = cands_of(w);
     if (!wide) {
-        hipLaunchKernelGGL(select_margin_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), dQ, T, k,
-                           w.cand_cap, bo.ac, w.list.as<int>(), w.nlist.as<int>(), w.thresh.as<float>(),
+        hipLaunchKernelGGL(select_margin_kernel, dim3(B), dim3(1024), 0, st, c.scores, c.n, dQ, T, k,
+                           c.cap, bo.ac, w.list.as<int>(), w.nlist.as<int>(), w.thresh.as<float>(),
                            w.eps_pair.as<float>(), tau_in, coarse_tau ? 1 : 0, bo.tscale, bo.cell8);
         return CLB_OK;
     }
     CLB_TRY(w.wsel.ensure(sizeof(WideSel) * B));
     CLB_HIP(hipMemsetAsync(w.wsel.p, 0, sizeof(WideSel) * B, st));
     const dim3 grid(kWideBlocks, B);
-    hipLaunchKernelGGL(wide_minmax_kernel, grid, dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), dQ, T, w.cand_cap,
+    hipLaunchKernelGGL(wide_minmax_kernel, grid, dim3(1024), 0, st, c.scores, c.n, dQ, T, c.cap,
                        bo.ac, w.wsel.as<WideSel>(), w.eps_pair.as<float>(), bo.tscale, bo.cell8);
     if (!tau_in)
         for (int pass = 0; pass < 4; ++pass)
-            hipLaunchKernelGGL(wide_hist_kernel, grid, dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), k, w.cand_cap,
-                               w.wsel.as<WideSel>(), pass);
-    hipLaunchKernelGGL(wide_count_kernel, grid, dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), k, w.cand_cap,
-                       w.wsel.as<WideSel>(), tau_in);
-    hipLaunchKernelGGL(wide_emit_kernel, grid, dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), k, w.cand_cap,
+            hipLaunchKernelGGL(wide_hist_kernel, grid, dim3(1024), 0, st, c.scores, c.n, k, c.cap, w.wsel.as<WideSel>(), pass);
+    hipLaunchKernelGGL(wide_count_kernel, grid, dim3(1024), 0, st, c.scores, c.n, k, c.cap, w.wsel.as<WideSel>(), tau_in);
+    hipLaunchKernelGGL(wide_emit_kernel, grid, dim3(1024), 0, st, c.scores, c.n, k, c.cap,
                        (const WideSel*)w.wsel.as<WideSel>(), tau_in, w.list.as<int>(), w.nlist.as<int>(), w.thresh.as<float>());
+    return CLB_OK;
+}
+
+// ---- the stages of run_search, in its order ------------------------------------------------------------------------------
+// Phase 2 opens with the threshold over the shards' gathered records and the selection at it
+int phase2_threshold(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
+    const int B = q.B, k = q.k;
+    CLB_TRY(w.tau_glob.ensure(sizeof(float) * B));
+    const BoundOperands bo = bound_operands(s, w);
+    float* tau = w.tau_glob.as<float>();
+    if (q.prior)    // the k-th largest BOOSTED score (the k-th best group's) over the shards, lowered by the rounding slack at
+                    // the largest magnitude any shard saw (prior_global_tau_kernel)
+        hipLaunchKernelGGL(prior_global_tau_kernel, dim3(B), dim3(1024), 0, st, q.d_all_top, q.d_all_gid, q.d_all_mabs, q.n_shards,
+                           B, k, (const float*)nullptr, q.dQ, q.T, bo.ac, bo.tscale, bo.cell8, tau);
+    else if (q.grp)      // the k-th best GROUP over the shards: a group that straddles a cut counts once
+        hipLaunchKernelGGL(group_global_tau_kernel, dim3(B), dim3(1024), 0, st, q.d_all_top, q.d_all_gid, q.n_shards, B, k, tau);
+    else
+        hipLaunchKernelGGL(global_tau_kernel, dim3(B), dim3(1024), 0, st, q.d_all_top, q.n_shards, B, k, tau);
+    Timed t(s, KID_SELECT, st);
+    return launch_select(s, w, st, q, bo, tau);
+}
+
+// Behind pass 1 (two-pass mode, phases 0 and 1): the threshold of every query and the selection at it, the profile's
+// `select_margin` row.  *published: this was phase 1, which has left the shard's records for the exchange and goes no further
+int select_candidates(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, bool* published) {
+    const int B = q.B, k = q.k;
+    const Cands c = cands_of(w);
+    const BoundOperands bo = bound_operands(s, w);
+    const SubsetOut groups = subset_out(w.grp_list, w.grp_n, 0, c.cap);
+    *published = q.phase == 1;
+    if (q.phase == 1) {
+        {   // with a prior everything works on A = fl(a + pi), and the shard's largest |A| travels with it
+            Timed t(s, KID_SELECT, st);
+            launch_boost(w, c, Subset{}, st, q, 0, B, q.d_local_mabs);
+            if (q.grp) {    // the shard's k best groups by approximate score, with their global indices; the selection waits
+                            // for the threshold of phase 2
+                launch_collapse(c, Subset{}, st, q, B, groups);
+                hipLaunchKernelGGL(group_local_top_kernel, dim3(B), dim3(1024), 0, st, c.scores, c.pid, groups.list, groups.n,
+                                   q.grp->gid.as<uint32_t>(), q.group_base, k, c.cap, q.d_local_top, q.d_local_gid);
+            } else
+                CLB_TRY(launch_select(s, w, st, q, bo, nullptr));
+        }
+        if (!q.grp)     // the k largest approximate scores of the shard's local selection
+            hipLaunchKernelGGL(local_top_kernel, dim3(B), dim3(1024), 0, st, c.scores, w.list.as<int>(), w.nlist.as<int>(),
+                               w.thresh.as<float>(), k, c.cap, q.d_local_top);
+        CLB_HIP(hipGetLastError());
+        return CLB_OK;
+    }
+    Timed t(s, KID_SELECT, st);
+    if (q.prior || q.d_list_prior) {
+        // with a prior or list priors: the selection cuts on the BOOSTED approximate scores, at their k-th largest -- with a
+        // grouping the k-th best group's -- lowered by the rounding slack (prior_tau_kernel)
+        float* ptau = w.prior_tau.as<float>();
+        float* mabs = ptau + w.Bcap;
+        launch_boost(w, c, Subset{}, st, q, 0, B, mabs);
+        const Subset best = q.grp ? launch_collapse(c, Subset{}, st, q, B, groups) : Subset{};
+        hipLaunchKernelGGL(prior_tau_kernel, dim3(B), dim3(1024), 0, st, c.scores, c.n, best.list, best.n, k, c.cap,
+                           (const float*)mabs, q.dQ, q.T, bo.ac, bo.tscale, bo.cell8, ptau);
+        return launch_select(s, w, st, q, bo, ptau);
+    }
+    if (q.d_after_s) {
+        // with cursors: the cut sits at the k-th largest approximate score of the candidates that are SURELY after the
+        // cursor, and those surely before it leave the selection (after_cut_kernel)
+        hipLaunchKernelGGL(after_cut_kernel, dim3(B), dim3(1024), 0, st, c.scores, c.n, k, c.cap, q.d_after_s, q.dQ, q.T, bo.ac,
+                           bo.tscale, bo.cell8, w.after_tau.as<float>());
+        return launch_select(s, w, st, q, bo, w.after_tau.as<float>());
+    }
+    if (!q.grp) return launch_select(s, w, st, q, bo, nullptr, /*coarse_tau=*/true);
+    // grouped: the cut is at the k-th best GROUP by approximate score -- the best approximate score of
+    // every group, their k-th largest, and the unchanged selection at that tau
+    launch_collapse(c, Subset{}, st, q, B, groups);
+    hipLaunchKernelGGL(group_tau_kernel, dim3(B), dim3(1024), 0, st, c.scores, groups.list, groups.n, k, c.cap,
+                       w.grp_tau.as<float>());
+    CLB_TRY(launch_select(s, w, st, q, bo, w.grp_tau.as<float>()));
+    if (q.per_group > 0)    // hits: the list grows by the passages that can be among the per_group best of a listed group
+        hipLaunchKernelGGL(group_extend_kernel, dim3(B), dim3(1024), 0, st, c.scores, c.pid, c.n, q.grp->gid.as<uint32_t>(),
+                           w.thresh.as<float>(), q.per_group, c.cap, w.hit_cut.as<unsigned long long>(), w.hit_run.as<int>(),
+                           w.hit_list.as<int>(), w.hit_n.as<int>());
+    return CLB_OK;
+}
+
+// (defined behind rescore: the kernels come out in the code object in the order the host code first names their templates)
+int launch_score_exact(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, int B, int T, int grid_x);
+
+// Exact scores: of the rows of `rescored` that can hold a token maximum (two-pass mode: the pass-1 pipeline again over the
+// listed passages marks them, then only they are decompressed) or, null, of every candidate
+int rescore(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q, Subset rescored) {
+    const int B = q.B, T = q.T;
+    const Cands c = cands_of(w);
+    if (rescored) {
+        Timed t(s, KID_ROWS, st);
+        constexpr int kRowsGx = 256;
+        const dim3 rows_grid = B > 1 ? dim3(std::max(1, kRowsGx / B), B) : dim3(8 * 32);
+        // (the row sweep keeps the VGPR gather: its ~1 200 passages per query are faster with it on every workload measured)
+        auto rows_kernel = w.cell8 ? score_approx32_kernel<true, 0, true> : score_approx32_kernel<true, 0, false>;
+        hipLaunchKernelGGL(rows_kernel, rows_grid, dim3(kApproxThreads), 0, st, s->weights.as<float>(),
+                           s->codeinv.as<uint32_t>(), s->residuals.as<uint8_t>(), s->cbits, s->inv_lo, s->inv_step, q.dQ,
+                           w.cell8 ? w.cells8.as<uint32_t>() : w.cells_q.as<uint32_t>(), c.hdr, c.n, c.scores, (int)s->K, T, B,
+                           c.cap, w.tokmax.as<uint16_t>(), rescored.list, rescored.n, w.eps_pair.as<float>(),
+                           w.rowmask.as<unsigned long long>(), (const float4*)w.tscale.as<float4>());
+    }
+    Timed t(s, KID_SCORE_EXACT, st);
+    if (!rescored) return launch_score_exact(s, w, st, q.dQ, B, T, std::max(1, 2048 / B));
+    constexpr int kFlatGx = 768;   // one resident round at 3 work-groups per CU
+    hipLaunchKernelGGL(score_exact_flat_kernel, dim3(std::max(1, kFlatGx / B), B), dim3(256), 0, st, s->centroids.as<float>(),
+                       s->weights.as<float>(), s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(), c.hdr, q.dQ, c.scores, T,
+                       c.cap, rescored.list, rescored.n, w.rowmask.as<unsigned long long>());
+    return CLB_OK;
+}
+
+// exact scores of ALL candidates of B queries (the single exact pass), by the index's nbits
+int launch_score_exact(clb_searcher* s, Workspace& w, hipStream_t st, const float* dQ, int B, int T, int grid_x) {
+    const Cands c = cands_of(w);
+    decltype(&score_exact_kernel<1>) kern = nullptr;
+    switch (s->nbits) {
+        case 1: kern = score_exact_kernel<1>; break;
+        case 2: kern = score_exact_kernel<2>; break;
+        case 4: kern = score_exact_kernel<4>; break;
+        default: return fail(CLB_EUNSUPPORTED, "nbits=%d not supported by the HIP search path", s->nbits);
+    }
+    hipLaunchKernelGGL(kern, dim3(grid_x, B), dim3(256), 0, st, s->centroids.as<float>(), s->weights.as<float>(),
+                       s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(), c.hdr, dQ, c.n, c.scores, T, c.cap,
+                       (const int*)nullptr, (const int*)nullptr);
     return CLB_OK;
 }
 
@@ -1010,26 +1158,12 @@ int launch_select(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q,
 // lowered by the rounding slack at the largest magnitude of ALL shards (d_all_mabs, prior_global_tau_kernel) and boosts the
 // re-scored list in front of the ranking, as phase 0 does.
 int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
-    const float* dQ = q.dQ;
-    const int B = q.B, T = q.T, k = q.k, phase = q.phase;
     const bool two_pass = two_pass_mode(s, q);
-    if (phase != 0 && !two_pass) return fail(CLB_EUNSUPPORTED, "the two-phase sharded search needs the two-pass mode");
-    if (s->generic || T > 128) return run_search_general(s, w, st, q);
+    if (q.phase != 0 && !two_pass) return fail(CLB_EUNSUPPORTED, "the two-phase sharded search needs the two-pass mode");
+    if (s->generic || q.T > 128) return run_search_general(s, w, st, q);
     s->prof.chain = nullptr;           // the first timed kernel of a call records its own start
-    if (phase == 2) {
-        CLB_TRY(w.tau_glob.ensure(sizeof(float) * B));
-        if (q.prior) {  // the k-th largest BOOSTED score (the k-th best group's) over the shards, lowered by the rounding slack at
-                        // the largest magnitude any shard saw (prior_global_tau_kernel)
-            const BoundOperands bo = bound_operands(s, w);
-            hipLaunchKernelGGL(prior_global_tau_kernel, dim3(B), dim3(1024), 0, st, q.d_all_top, q.d_all_gid, q.d_all_mabs,
-                               q.n_shards, B, k, (const float*)nullptr, dQ, T, bo.ac, bo.tscale, bo.cell8, w.tau_glob.as<float>());
-        } else if (q.grp)      // the k-th best GROUP over the shards: a group that straddles a cut counts once
-            hipLaunchKernelGGL(group_global_tau_kernel, dim3(B), dim3(1024), 0, st, q.d_all_top, q.d_all_gid, q.n_shards, B, k,
-                               w.tau_glob.as<float>());
-        else
-            hipLaunchKernelGGL(global_tau_kernel, dim3(B), dim3(1024), 0, st, q.d_all_top, q.n_shards, B, k, w.tau_glob.as<float>());
-        Timed t(s, KID_SELECT, st);
-        CLB_TRY(launch_select(s, w, st, q, (const float*)w.tau_glob.as<float>()));
+    if (q.phase == 2) {
+        CLB_TRY(phase2_threshold(s, w, st, q));
     } else {
         CLB_TRY(run_retrieve(s, w, st, q));
         if (s->prof.counters) {
@@ -1038,157 +1172,23 @@ int run_search(clb_searcher* s, Workspace& w, hipStream_t st, const Batch& q) {
             s->prof.chain = nullptr;
         }
         if (two_pass) {
-            {
-                Timed t(s, KID_SCORE_APPROX, st);
-                constexpr int kWgPerGroup = 32;   // x 8 XCD groups: one 12-wave work-group per CU
-                // Grid: XCD-affine 1-D launch (all work-groups of an XCD share one query's score table in L2) for
-                // large candidate sets; for small ones (a shard of a multi-GPU run: < ~6 k candidate passages per
-                // query, estimated from the mean IVF list) a (G, B) launch whose few waves per query each get a long
-                // run of passages -- the pipeline fill otherwise dominates.
-                const double est_cand = 0.5 * T * q.nprobe * (double)s->n_emb / (double)std::max<int64_t>(1, s->K);
-                // work-groups per query of the (G, B) launch (0 = the 1-D launch): enough to fill the chip for small batches,
-                // eight for large ones (measured at 4 and 8 shards, B = 8 ... 256: one or two per query cost 12 % of the pass
-                // at B = 256, sixteen and more cost as much at B = 32)
-                const int gxq = est_cand < 6000.0 ? std::max(8, 256 / B) : 0;
-                const dim3 approx_grid = gxq > 0 && B > 1 ? dim3(gxq, B) : dim3(8 * kWgPerGroup);
-                launch_pass1(s, w, st, dQ, approx_grid, B, T);
-            }
-            if ((q.prior || q.d_list_prior) && phase == 0) {
-                // with a prior or list priors (the whole search): the selection cuts on the BOOSTED approximate scores, at their
-                // k-th largest -- with a grouping the k-th best group's -- lowered by the rounding slack (prior_tau_kernel, DESIGN
-                // section 5)
-                Timed t(s, KID_SELECT, st);
-                float* ptau = w.prior_tau.as<float>();
-                float* mabs = ptau + w.Bcap;
-                launch_boost(w, st, q, 0, B, nullptr, nullptr, mabs);
-                if (q.grp) launch_collapse(w, st, q, 0, B, nullptr, nullptr, w.grp_list.as<int>(), w.grp_n.as<int>());
-                const BoundOperands bo = bound_operands(s, w);
-                hipLaunchKernelGGL(prior_tau_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(),
-                                   q.grp ? (const int*)w.grp_list.as<int>() : (const int*)nullptr,
-                                   q.grp ? (const int*)w.grp_n.as<int>() : (const int*)nullptr, k, w.cand_cap, (const float*)mabs,
-                                   dQ, T, bo.ac, bo.tscale, bo.cell8, ptau);
-                CLB_TRY(launch_select(s, w, st, q, (const float*)ptau));
-            } else if (q.d_after_s) {
-                // with cursors (phase 0 only): the cut sits at the k-th largest approximate score of the candidates that are
-                // SURELY after the cursor, and those surely before it leave the selection (after_cut_kernel)
-                Timed t(s, KID_SELECT, st);
-                const BoundOperands bo = bound_operands(s, w);
-                hipLaunchKernelGGL(after_cut_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(), w.ncand.as<int>(), k,
-                                   w.cand_cap, q.d_after_s, dQ, T, bo.ac, bo.tscale, bo.cell8, w.after_tau.as<float>());
-                CLB_TRY(launch_select(s, w, st, q, (const float*)w.after_tau.as<float>()));
-            } else {
-                Timed t(s, KID_SELECT, st);
-                // phase 1 with a prior: everything below works on A = fl(a + pi), and the shard's largest |A| travels with it
-                if (phase == 1) launch_boost(w, st, q, 0, B, nullptr, nullptr, q.d_local_mabs);
-                if (q.grp && phase == 1) {
-                    // grouped phase 1: the shard's k best groups by approximate score, with their global indices; the
-                    // selection waits for the threshold of phase 2
-                    launch_collapse(w, st, q, 0, B, nullptr, nullptr, w.grp_list.as<int>(), w.grp_n.as<int>());
-                    hipLaunchKernelGGL(group_local_top_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(),
-                                       w.cand.as<uint32_t>(), w.grp_list.as<int>(), w.grp_n.as<int>(), q.grp->gid.as<uint32_t>(),
-                                       q.group_base, k, w.cand_cap, q.d_local_top, q.d_local_gid);
-                    CLB_HIP(hipGetLastError());
-                    return CLB_OK;
-                }
-                if (q.grp) {
-                    // grouped: the cut is at the k-th best GROUP by approximate score -- the best
-                    // approximate score of every group, their k-th largest, and the unchanged selection at that tau
-                    launch_collapse(w, st, q, 0, B, nullptr, nullptr, w.grp_list.as<int>(), w.grp_n.as<int>());
-                    hipLaunchKernelGGL(group_tau_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(), w.grp_list.as<int>(),
-                                       w.grp_n.as<int>(), k, w.cand_cap, w.grp_tau.as<float>());
-                    CLB_TRY(launch_select(s, w, st, q, (const float*)w.grp_tau.as<float>()));
-                    // hits: the list grows by the passages that can be among the per_group best of a listed group
-                    if (q.per_group > 0)
-                        hipLaunchKernelGGL(group_extend_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(),
-                                           w.cand.as<uint32_t>(), w.ncand.as<int>(), q.grp->gid.as<uint32_t>(),
-                                           w.thresh.as<float>(), q.per_group, w.cand_cap, w.hit_cut.as<unsigned long long>(),
-                                           w.hit_run.as<int>(), w.hit_list.as<int>(), w.hit_n.as<int>());
-                } else
-                    CLB_TRY(launch_select(s, w, st, q, nullptr, /*coarse_tau=*/phase == 0));
-            }
+            bool published = false;
+            launch_pass1_grid(s, w, st, q);
+            CLB_TRY(select_candidates(s, w, st, q, &published));
+            if (published) return CLB_OK;
         }
     }
-    // two-pass mode: only the selected passages go on
-    const bool extended = two_pass && q.grp && q.per_group > 0 && phase == 0;     // group_extend_kernel has left its own list
-    const int* list = two_pass ? (extended ? w.hit_list.as<int>() : w.list.as<int>()) : nullptr;
-    const int* nlist = two_pass ? (extended ? w.hit_n.as<int>() : w.nlist.as<int>()) : nullptr;
-    if (phase == 1) {
-        hipLaunchKernelGGL(local_top_kernel, dim3(B), dim3(1024), 0, st, w.scores.as<float>(), list, nlist,
-                           w.thresh.as<float>(), k, w.cand_cap, q.d_local_top);
-        CLB_HIP(hipGetLastError());
-        return CLB_OK;
-    }
-    const bool subset = list != nullptr;   // two-pass mode: re-score only the rows that matter
-    if (subset) {
-        Timed t(s, KID_ROWS, st);
-        // the pass-1 pipeline again, over the listed passages only: marks the rows that can hold a token maximum
-        constexpr int kRowsGx = 256;
-        const dim3 rows_grid = B > 1 ? dim3(std::max(1, kRowsGx / B), B) : dim3(8 * 32);
-        // (the row sweep keeps the VGPR gather: its ~1 200 passages per query are faster with it on every workload measured)
-        auto rows_kernel = w.cell8 ? score_approx32_kernel<true, 0, true> : score_approx32_kernel<true, 0, false>;
-        hipLaunchKernelGGL(rows_kernel, rows_grid, dim3(kApproxThreads), 0, st, s->weights.as<float>(),
-                           s->codeinv.as<uint32_t>(), s->residuals.as<uint8_t>(), s->cbits, s->inv_lo, s->inv_step, dQ,
-                           w.cell8 ? w.cells8.as<uint32_t>() : w.cells_q.as<uint32_t>(), w.cand_hdr.as<uint2>(), w.ncand.as<int>(),
-                           w.scores.as<float>(), (int)s->K, T, B, w.cand_cap, w.tokmax.as<uint16_t>(), list, nlist,
-                           w.eps_pair.as<float>(), w.rowmask.as<unsigned long long>(), (const float4*)w.tscale.as<float4>());
-    }
-    {
-        Timed t(s, KID_SCORE_EXACT, st);
-        const int gx = list ? std::max(1, 1024 / B) : std::max(1, 2048 / B);
-        constexpr int kFlatGx = 768;   // one resident round at 3 work-groups per CU
-        if (subset)
-            hipLaunchKernelGGL(score_exact_flat_kernel, dim3(std::max(1, kFlatGx / B), B), dim3(256), 0, st, s->centroids.as<float>(),
-                               s->weights.as<float>(), s->codes0.as<uint32_t>(), s->residuals.as<uint8_t>(),
-                               w.cand_hdr.as<uint2>(), dQ, w.scores.as<float>(), T, w.cand_cap, list, nlist,
-                               w.rowmask.as<unsigned long long>());
-        else
-            switch (s->nbits) {
-                case 1: launch_score_exact<1>(s, w, st, dQ, B, T, list, nlist, gx); break;
-                case 2: launch_score_exact<2>(s, w, st, dQ, B, T, list, nlist, gx); break;
-                case 4: launch_score_exact<4>(s, w, st, dQ, B, T, list, nlist, gx); break;
-                default: return fail(CLB_EUNSUPPORTED, "nbits=%d not supported by the HIP search path", s->nbits);
-            }
-    }
-    // what S7 ranks: the re-scored passages (two-pass mode) or all candidates -- with a grouping, the best of every group
-    // among them by exact score (two-pass mode: grp_n, the group count of ALL candidates, stays what the call reports)
-    const int* tlist = list;
-    const int* tnlist = nlist;
-    auto collapse_exact = [&]() {
-        launch_boost(w, st, q, 0, B, list, nlist, nullptr);     // with a prior: the exact scores become E = e + weight * value
-        launch_list_scores(s, w, st, q, 0, B);                  // (a call with list scores is the exact pass: list == nullptr)
-        if (q.d_after_s) {      // with cursors (never with a grouping): only what lies after them is ranked
-            launch_after(s, w, st, q, 0, B, list, nlist);
-            tlist = w.after_list.as<int>(); tnlist = w.after_n.as<int>();
-        }
-        if (!q.grp) return;
-        int* gl = list ? w.grp_list2.as<int>() : w.grp_list.as<int>();
-        int* gn = list ? w.grp_n2.as<int>() : w.grp_n.as<int>();
-        launch_collapse(w, st, q, 0, B, list, nlist, gl, gn);
-        tlist = gl; tnlist = gn;
-    };
-    if (k <= kMaxTopK) {
-        Timed t(s, KID_TOPK, st);
-        collapse_exact();
-        // two-pass mode: the ~1.2 k listed passages of a query are ranked by kRankBlocks work-groups (no sorting network);
-        // a query whose list is longer than kRankMax falls through to the one-work-group select + sort
-        const int ranked = tlist != nullptr;
-        if (ranked)
-            hipLaunchKernelGGL(topk_rank_kernel, dim3(kRankBlocks, B), dim3(1024), 0, st, w.scores.as<float>(),
-                               w.cand.as<uint32_t>(), reported_count(w, q), tlist, tnlist, k, w.cand_cap, s->pid_offset,
-                               q.d_out_pids, q.d_out_scores, w.flags.as<int>(), q.d_n_cand);
-        CLB_TRY(launch_topk(s, w, st, q, 0, B, tlist, tnlist, ranked));
-    } else {      // k above the single-work-group sort: a full stable sort per query, untimed
-        s->prof.chain = nullptr;
-        collapse_exact();
-        CLB_TRY(launch_topk(s, w, st, q, 0, B, tlist, tnlist, 0));
-    }
-    if (q.grp) launch_hits(s, w, st, q, 0, B, list, nlist);
-    if (q.grp && q.d_out_gids) launch_result_groups(s, w, st, q.grp, q.group_base, q.d_out_pids, B, k, q.d_out_gids, q.d_edge_gids);
+    // two-pass mode: only the selected passages go on -- with hits, the list group_extend_kernel has grown from the selection
+    const bool extended = q.grp && q.per_group > 0 && q.phase == 0;
+    const Subset rescored = !two_pass ? Subset{} : extended ? Subset{w.hit_list.as<int>(), w.hit_n.as<int>()}
+                                                            : Subset{w.list.as<int>(), w.nlist.as<int>()};
+    CLB_TRY(rescore(s, w, st, q, rescored));
+    CLB_TRY(rank_results(s, w, st, q, 0, q.B, rescored, /*tuned=*/true));
     if (s->prof.counters) {
-        hipLaunchKernelGGL(batch_stats_kernel, dim3(32, B), dim3(256), 0, st, w.cand.as<uint32_t>(),
-                           w.ncand.as<int>(), list, nlist, s->doc_off.as<uint32_t>(), w.cand_cap,
-                           w.stats.as<unsigned long long>(),
-                           subset ? w.rowmask.as<unsigned long long>() : (const unsigned long long*)nullptr, T);
+        const Cands c = cands_of(w);
+        hipLaunchKernelGGL(batch_stats_kernel, dim3(32, q.B), dim3(256), 0, st, c.pid, c.n, rescored.list, rescored.n,
+                           s->doc_off.as<uint32_t>(), c.cap, w.stats.as<unsigned long long>(),
+                           rescored ? w.rowmask.as<unsigned long long>() : (const unsigned long long*)nullptr, q.T);
     }
     CLB_HIP(hipGetLastError());
     return CLB_OK;
@@ -3100,10 +3100,8 @@ int clb_debug_scores(clb_searcher* s, const float* Q, int64_t T, int64_t nprobe,
         CLB_HIP(hipMemcpy(c.data(), w.cand.p, sizeof(uint32_t) * nc, hipMemcpyDeviceToHost));
         CLB_HIP(hipMemcpy(out_approx, w.scores.p, sizeof(float) * nc, hipMemcpyDeviceToHost));
     }
-    switch (s->nbits) {
-        case 2: launch_score_exact<2>(s, w, st, dQ, 1, (int)T, nullptr, nullptr, 2048); break;
-        default: return fail(CLB_EUNSUPPORTED, "nbits");
-    }
+    if (s->nbits != 2) return fail(CLB_EUNSUPPORTED, "nbits");
+    CLB_TRY(launch_score_exact(s, w, st, dQ, 1, (int)T, 2048));
     CLB_HIP(hipGetLastError());
     CLB_HIP(hipStreamSynchronize(st));
     if (nc) CLB_HIP(hipMemcpy(out_exact, w.scores.p, sizeof(float) * nc, hipMemcpyDeviceToHost));

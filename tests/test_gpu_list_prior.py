@@ -256,7 +256,7 @@ def test_list_priors_with_a_grouping(medium, medium_searcher):
 # ---- 6. the general-shape path ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", ["dim64-batched", "dim768-per-query"])
 def test_list_priors_on_the_general_path(oracle, shape):
-    """300 passages, every passage listed thrice with three distinct values: topk_of's boost, batched and one query at a time"""
+    """300 passages, every passage listed thrice with three distinct values: rank_results' boost, batched and one query at a time"""
     if shape == "dim64-batched":
         idx = synthetic.make_index(seed=531, n_docs=300, K=32, dim=64, nbits=4, doclen_mean=20, doclen_std=12)
         Qs, nprobe = synthetic.make_queries(idx, 631, 3, T=24), 2
