@@ -114,6 +114,73 @@ def _host_16bit(a, dtype: str) -> np.ndarray:
     return colmajor(a, np.float16) if dtype == "float16" else np.asfortranarray(to_bfloat16_bits(colmajor(a, np.float32)))
 
 
+I8 = 3                                                         # CLB_I8
+
+
+def quantize_rows(X):
+    """Per-embedding int8 quantisation, the host statement of dense_quantize_kernel (include/colbert_hip.h), bit for bit: X
+    (dim, ...) float32 -> (X8 int8 of X's shape, scale float32 of X.shape[1:]); s = fl32(amax / 127), q = clamp(rint(fl32(x / s)),
+    -127, 127) with ties to even, s == 0 -> zeros.  A non-finite value is an ArgumentError naming the embedding."""
+    from ._lib import ArgumentError
+    x = colmajor(X, np.float32)
+    bad = ~np.isfinite(x).all(axis=0)
+    if bad.any():
+        raise ArgumentError(f"quantize_rows: embedding {int(np.flatnonzero(bad.ravel(order='F'))[0])} holds a non-finite value")
+    s = (np.abs(x).max(axis=0, initial=np.float32(0)) / np.float32(127)).astype(np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        y = np.rint(x / s)                                      # float32 / float32: one IEEE division, as on the device
+    x8 = np.where(s == 0, np.float32(0), np.clip(y, -127, 127)).astype(np.int8)
+    return np.asfortranarray(x8), s
+
+
+def _int8_pair(a, what):
+    """(values int8 column-major, scales float32) of an operand given as floats (quantised here) or as a (values, scales) pair"""
+    if isinstance(a, tuple):
+        v, s = colmajor(a[0], np.int8), np.ascontiguousarray(np.asarray(a[1], dtype=np.float32).ravel(order="F"))
+        if s.size != v.size // max(v.shape[0], 1):
+            raise ValueError(f"{what}: one scale per embedding")
+        return v, s
+    if getattr(a, "dtype", None) == np.int8:
+        raise ValueError(f"{what}: int8 values need their scales, as a (values, scales) pair")
+    v, s = quantize_rows(a)
+    return v, np.ascontiguousarray(s.ravel(order="F"))
+
+
+def _maxsim_batch_int8(Q, D, doclens, owner, device):
+    (q, qs), (d, ds) = _int8_pair(Q, "Q"), _int8_pair(D, "D")
+    if q.ndim != 3:
+        raise ValueError("Q must be (dim, T, B)")
+    dl = np.ascontiguousarray(doclens, dtype=np.int64)
+    ow = None if owner is None else np.ascontiguousarray(owner, dtype=np.int32)
+    if ow is not None and ow.size != dl.size:
+        raise ValueError("owner must hold one query number per passage")
+    dim, T, B = q.shape
+    scores = np.zeros(dl.size if ow is not None else (dl.size, B), dtype=np.float32, order="F")
+    check(lib().clb_maxsim_batch_i8(device, fptr(q), I8, fptr(qs), i64(dim), i64(T), i64(B), fptr(d), fptr(ds),
+                                    i64(d.shape[1] if d.ndim == 2 else 0), fptr(dl), i64(dl.size),
+                                    fptr(ow) if ow is not None else None, fptr(scores)))
+    return scores
+
+
+def quantize_rows_device(d_X, out=None, stream=None):
+    """`quantize_rows` on the device (clb_quantize_rows_device): d_X float32 (..., dim), contiguous, dim % 16 == 0 -> (int8 of d_X's
+    shape, float32 scales of its leading shape).  `out`: that pair, preallocated.  Stream-ordered, not waited for; it cannot
+    report a non-finite value (defined, meaningless numbers)."""
+    import torch
+    x = _dev_rows(d_X, torch.float32)
+    if x.dim() < 2:
+        raise ValueError("d_X must be (..., dim)")
+    x8, s = out if out is not None else (torch.empty(x.shape, dtype=torch.int8, device=x.device),
+                                         torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device))
+    _dev_rows(x8, torch.int8); _dev_rows(s, torch.float32)
+    if x8.numel() != x.numel() or s.numel() * x.shape[-1] != x.numel():
+        raise ValueError("out: int8 of d_X's shape and one float32 scale per embedding")
+    st = torch.cuda.current_stream(x.device).cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+    check(lib().clb_quantize_rows_device(x.device.index, C.c_void_p(x.data_ptr()), i64(x.shape[-1]), i64(s.numel()),
+                                         C.c_void_p(x8.data_ptr()), C.c_void_p(s.data_ptr()), C.c_void_p(st)))
+    return x8, s
+
+
 def maxsim_batch(Q, D, doclens, owner=None, device: int = 0, dtype=None):
     """maxsim (ranking.jl:69-86) of N un-indexed passages for a batch of queries in one call (clb_maxsim_batch): Q (dim, T, B),
     D (dim, n) -- the passages' embeddings back to back --, doclens [N].  `owner` [N], 0-based: passage j is scored against
@@ -121,11 +188,18 @@ def maxsim_batch(Q, D, doclens, owner=None, device: int = 0, dtype=None):
     `maxsim(Q[:, :, q], D_j)`.
     dtype="float16" / "bfloat16" (implied by an np.float16 D): Q and D are rounded to nearest-even into that type, uploaded in 16
     bits and multiplied by the 16-bit MFMA kernel (clb_maxsim_batch_half): exact products summed in fp32, within the bound of
-    DESIGN 4.2a of the float64 value on the rounded operands -- not the oracle's bits."""
+    DESIGN 4.2a of the float64 value on the rounded operands -- not the oracle's bits.
+    dtype="int8" (implied by a Q or D given as a `(values int8, scales)` pair, which is used as it is): float operands are
+    quantised per embedding by `quantize_rows` and scored by the integer-MFMA kernel (clb_maxsim_batch_i8): exact integer dots,
+    each score bit-identical to the restatement in include/colbert_hip.h; its distance from the fp32 score is the format's."""
+    if dtype == "int8" or isinstance(Q, tuple) or isinstance(D, tuple) or (dtype is None and getattr(D, "dtype", None) == np.int8):
+        if dtype not in (None, "int8"):
+            raise ValueError("int8 operands take dtype None or 'int8'")
+        return _maxsim_batch_int8(Q, D, doclens, owner, device)
     if dtype is None and getattr(D, "dtype", None) == np.float16:
         dtype = "float16"
     if dtype not in (None, "float16", "bfloat16"):
-        raise ValueError("dtype must be None, 'float16' or 'bfloat16'")
+        raise ValueError("dtype must be None, 'float16', 'bfloat16' or 'int8'")
     if dtype is None:
         q = colmajor(Q, np.float32); d = colmajor(D, np.float32)
     else:
@@ -149,7 +223,40 @@ def maxsim_batch(Q, D, doclens, owner=None, device: int = 0, dtype=None):
     return scores
 
 
-def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, stream=None):
+def _maxsim_batch_int8_device(d_Q, d_D, d_doclens, owner, out, work, stream, d_scale, q_scale):
+    import torch
+    if d_D.dtype != torch.int8 or d_scale is None:
+        raise ValueError("int8 scoring takes an int8 d_D with d_scale, one float32 scale per embedding")
+    if (d_Q.dtype == torch.int8) != (q_scale is not None) or d_Q.dtype not in (torch.int8, torch.float32):
+        raise ValueError("d_Q must be float32 (quantised on the device) or int8 with q_scale")
+    q, d, dl, ds = _dev_rows(d_Q), _dev_rows(d_D), _dev_rows(d_doclens, torch.int64), _dev_rows(d_scale, torch.float32)
+    qs = None if q_scale is None else _dev_rows(q_scale, torch.float32)
+    if q.dim() != 3 or d.dim() != 2 or d.shape[1] != q.shape[2]:
+        raise ValueError("d_Q must be (B, T, dim) and d_D (n, dim)")
+    B, T, dim = (int(x) for x in q.shape)
+    N = int(dl.numel())
+    if ds.numel() != d.shape[0] or (qs is not None and qs.numel() != B * T):
+        raise ValueError("d_scale / q_scale: one scale per embedding")
+    ow = None if owner is None else _dev_rows(owner, torch.int32)
+    if ow is not None and ow.numel() != N:
+        raise ValueError("owner must hold one query number per passage")
+    if out is None:
+        out = torch.empty(N if ow is not None else (B, N), dtype=torch.float32, device=q.device)
+    if work is None:
+        work = torch.empty(int(lib().clb_maxsim_batch_i8_work_bytes(i64(N), i64(B), i64(T), i64(dim))), dtype=torch.uint8, device=q.device)
+    o = _dev_rows(out, torch.float32); wk = _dev_rows(work)
+    if o.numel() != (N if ow is not None else N * B):
+        raise ValueError("out: one score per passage (owned) or per (query, passage)")
+    st = torch.cuda.current_stream(q.device).cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+    check(lib().clb_maxsim_batch_i8_device(q.device.index, C.c_void_p(q.data_ptr()), F32 if qs is None else I8,
+                                           C.c_void_p(qs.data_ptr()) if qs is not None else None, i64(dim), i64(T), i64(B),
+                                           C.c_void_p(d.data_ptr()), C.c_void_p(ds.data_ptr()), i64(d.shape[0]), C.c_void_p(dl.data_ptr()),
+                                           i64(N), C.c_void_p(ow.data_ptr()) if ow is not None else None, C.c_void_p(o.data_ptr()),
+                                           C.c_void_p(wk.data_ptr()), i64(wk.numel() * wk.element_size()), C.c_void_p(st)))
+    return out
+
+
+def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, stream=None, *, d_scale=None, q_scale=None):
     """`maxsim_batch` between the encoder's device outputs (clb_maxsim_batch_device): d_Q float32 (B, T, dim) -- what
     query_embeddings_device writes --, d_D float32 (n, dim) and d_doclens int64 (N,) -- what doc_embeddings_device /
     doc_embeddings_packed_device return --, owner int32 (N,) or None; all contiguous CUDA tensors.  Returns `out`: float32 (N,)
@@ -157,9 +264,14 @@ def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, st
     waited for; with `out` and `work` (uint8, clb_maxsim_batch_work_bytes long) given it allocates nothing, so it can be
     captured in a graph.  Device doclens are not validated: see include/colbert_hip.h for what bad ones score.
     A float16 / bfloat16 d_D takes the 16-bit kernel (clb_maxsim_batch_half_device): d_Q float32 (rounded on the device) or
-    d_D's dtype, `work` clb_maxsim_batch_half_work_bytes long."""
+    d_D's dtype, `work` clb_maxsim_batch_half_work_bytes long.
+    An int8 d_D with `d_scale` (float32, one per embedding: what `quantize_rows_device` returns) takes the integer kernel
+    (clb_maxsim_batch_i8_device): d_Q float32 (quantised on the device) or int8 with `q_scale` (B, T); `work`
+    clb_maxsim_batch_i8_work_bytes long.  Any other mix of int8 operands and scales is a ValueError."""
     import torch
-    half = {torch.float16: F16, torch.bfloat16: BF16}.get(d_D.dtype)
+    if torch.int8 in (d_D.dtype, d_Q.dtype) or d_scale is not None or q_scale is not None:
+        return _maxsim_batch_int8_device(d_Q, d_D, d_doclens, owner, out, work, stream, d_scale, q_scale)
+    half ={torch.float16: F16, torch.bfloat16: BF16}.get(d_D.dtype)
     if half is not None and d_Q.dtype not in (torch.float32, d_D.dtype):
         raise ValueError(f"d_Q must be float32 or {d_D.dtype}, got {d_Q.dtype}")
     q = _dev_rows(d_Q, None if half is not None else torch.float32)

@@ -862,7 +862,7 @@ int clb_maxsim_batch(int device, const float* Q, int64_t dim, int64_t T, int64_t
  * allocation (d_work: clb_maxsim_batch_half_work_bytes bytes -- the offsets and the rounded Q), capturable, clamped doclens, -Inf
  * for a passage without a readable row or with an owner outside the batch; the host call (Q and D host buffers in the named
  * types) validates first.  Not part of the Julia shim. */
-enum { CLB_F32 = 0, CLB_F16 = 1, CLB_BF16 = 2 };
+enum { CLB_F32 = 0, CLB_F16 = 1, CLB_BF16 = 2, CLB_I8 = 3 };
 int64_t clb_maxsim_batch_half_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim);
 int clb_maxsim_batch_half_device(int device, const void* d_Q, int q_type, int64_t dim, int64_t T, int64_t B,
                                  const void* d_D, int d_type, int64_t n_D, const int64_t* d_doclens, int64_t N,
@@ -870,6 +870,39 @@ int clb_maxsim_batch_half_device(int device, const void* d_Q, int q_type, int64_
                                  void* d_work, int64_t work_bytes, void* hip_stream);
 int clb_maxsim_batch_half(int device, const void* Q, int q_type, int64_t dim, int64_t T, int64_t B, const void* D, int d_type,
                           int64_t n_D, const int64_t* doclens, int64_t N, const int32_t* owner, float* scores);
+/* The same call on embeddings stored as int8 with one fp32 scale each (dense_i8_kernels.hpp).  An int8 operand is a pair: the
+ * values, (dim, n) like every dense operand, and one finite scale >= 0 per embedding.
+ * Quantisation (clb_quantize_rows*, one definition for host and device), per embedding x:
+ *   amax = max_k |x_k|;  s = fl32(amax / 127) (IEEE division);  q_k = clamp(rint(fl32(x_k / s)), -127, 127), rint to nearest-even;
+ *   s == 0 gives q_k = 0.  Served: dim % 16 == 0, 16 <= dim <= 1024, else CLB_EUNSUPPORTED; X and X8 16-byte aligned on the device.
+ *   The host call refuses a non-finite value with CLB_EARGUMENT naming the embedding; the device call cannot report: a
+ *   non-finite value there gives defined but meaningless numbers, never a fault.
+ * Scoring, for query q and passage j (d_Q in q_type = CLB_I8 with d_qscale (T, B), or CLB_F32: quantised as above into the work
+ * buffer first, d_qscale ignored):
+ *   i(t, r) = sum_k q8[k, t] d8[k, r]            exact in int32 (v_mfma_i32_16x16x64_i8); |i| <= 2^24, so float(i) is exact
+ *   m_t     = max over the rows r of passage j of fl32(ds[r] * float(i(t, r)))
+ *   score   = acc = 0; for t ascending: acc = fl32(acc + fl32(qs[t] * m_t))
+ * The query scale is applied after the maximum (qs[t] >= 0 and fp32 multiplication is monotone: the same row is chosen).  Integer
+ * sums are exact and order-free, so every score equals this restatement bit for bit and depends on its own query and passage
+ * only.  A pair that received no row -- an empty clamped passage, an owner outside 0..B-1 -- scores -Inf, decided before any
+ * multiplication (qs[t] == 0 cannot make it NaN).  How far these scores lie from the fp32 scores of the unquantised embeddings
+ * is a property of the format, measured in profiles/maxsim_batch_int8.md, not part of the contract.
+ * Served: dim % 16 == 0, 16 <= dim <= 1024 (tuned for 128), 1 <= T <= 128, B >= 1, N >= 0, q_type CLB_F32 or CLB_I8, else
+ * CLB_EUNSUPPORTED; d_Q, d_D8 and d_work 16-byte aligned.  Every other contract is clb_maxsim_batch_device's /
+ * clb_maxsim_batch's: argument errors before any launch, stream-ordered, no host wait, no allocation (d_work:
+ * clb_maxsim_batch_i8_work_bytes bytes -- the offsets, and B T dim bytes + B T floats for a query quantised in the call),
+ * capturable, clamped doclens (no row at or past n_D is read, neither its bytes nor its scale).  The host call validates first
+ * and also refuses a negative or non-finite scale with CLB_EARGUMENT.  Not part of the Julia shim. */
+int clb_quantize_rows_device(int device, const float* d_X, int64_t dim, int64_t n, int8_t* d_X8, float* d_scale, void* hip_stream);
+int clb_quantize_rows(int device, const float* X, int64_t dim, int64_t n, int8_t* X8, float* scale);
+int64_t clb_maxsim_batch_i8_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim);
+int clb_maxsim_batch_i8_device(int device, const void* d_Q, int q_type, const float* d_qscale, int64_t dim, int64_t T, int64_t B,
+                               const int8_t* d_D8, const float* d_dscale, int64_t n_D, const int64_t* d_doclens, int64_t N,
+                               const int32_t* d_owner /* NULL: all pairs */, float* d_scores,
+                               void* d_work, int64_t work_bytes, void* hip_stream);
+int clb_maxsim_batch_i8(int device, const void* Q, int q_type, const float* qscale, int64_t dim, int64_t T, int64_t B,
+                        const int8_t* D8, const float* dscale, int64_t n_D, const int64_t* doclens, int64_t N, const int32_t* owner,
+                        float* scores);
 /* compress_into_codes!  (residual.jl:67-81) */
 int clb_compress_into_codes(int device, uint32_t* codes, int64_t n_codes, const float* centroids,
                             int64_t dim, int64_t K, const float* embs, int64_t n);
