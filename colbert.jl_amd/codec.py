@@ -146,22 +146,6 @@ def _int8_pair(a, what):
     return v, np.ascontiguousarray(s.ravel(order="F"))
 
 
-def _maxsim_batch_int8(Q, D, doclens, owner, device):
-    (q, qs), (d, ds) = _int8_pair(Q, "Q"), _int8_pair(D, "D")
-    if q.ndim != 3:
-        raise ValueError("Q must be (dim, T, B)")
-    dl = np.ascontiguousarray(doclens, dtype=np.int64)
-    ow = None if owner is None else np.ascontiguousarray(owner, dtype=np.int32)
-    if ow is not None and ow.size != dl.size:
-        raise ValueError("owner must hold one query number per passage")
-    dim, T, B = q.shape
-    scores = np.zeros(dl.size if ow is not None else (dl.size, B), dtype=np.float32, order="F")
-    check(lib().clb_maxsim_batch_i8(device, fptr(q), I8, fptr(qs), i64(dim), i64(T), i64(B), fptr(d), fptr(ds),
-                                    i64(d.shape[1] if d.ndim == 2 else 0), fptr(dl), i64(dl.size),
-                                    fptr(ow) if ow is not None else None, fptr(scores)))
-    return scores
-
-
 def quantize_rows_device(d_X, out=None, stream=None):
     """`quantize_rows` on the device (clb_quantize_rows_device): d_X float32 (..., dim), contiguous, dim % 16 == 0 -> (int8 of d_X's
     shape, float32 scales of its leading shape).  `out`: that pair, preallocated.  Stream-ordered, not waited for; it cannot
@@ -192,18 +176,17 @@ def maxsim_batch(Q, D, doclens, owner=None, device: int = 0, dtype=None):
     dtype="int8" (implied by a Q or D given as a `(values int8, scales)` pair, which is used as it is): float operands are
     quantised per embedding by `quantize_rows` and scored by the integer-MFMA kernel (clb_maxsim_batch_i8): exact integer dots,
     each score bit-identical to the restatement in include/colbert_hip.h; its distance from the fp32 score is the format's."""
-    if dtype == "int8" or isinstance(Q, tuple) or isinstance(D, tuple) or (dtype is None and getattr(D, "dtype", None) == np.int8):
+    int8 = dtype == "int8" or isinstance(Q, tuple) or isinstance(D, tuple) or (dtype is None and getattr(D, "dtype", None) == np.int8)
+    if int8:
         if dtype not in (None, "int8"):
             raise ValueError("int8 operands take dtype None or 'int8'")
-        return _maxsim_batch_int8(Q, D, doclens, owner, device)
-    if dtype is None and getattr(D, "dtype", None) == np.float16:
-        dtype = "float16"
-    if dtype not in (None, "float16", "bfloat16"):
-        raise ValueError("dtype must be None, 'float16', 'bfloat16' or 'int8'")
-    if dtype is None:
-        q = colmajor(Q, np.float32); d = colmajor(D, np.float32)
+        (q, qs), (d, ds) = _int8_pair(Q, "Q"), _int8_pair(D, "D")
     else:
-        q = _host_16bit(Q, dtype); d = _host_16bit(D, dtype)
+        if dtype is None and getattr(D, "dtype", None) == np.float16:
+            dtype = "float16"
+        if dtype not in (None, "float16", "bfloat16"):
+            raise ValueError("dtype must be None, 'float16', 'bfloat16' or 'int8'")
+        q, d = (colmajor(Q, np.float32), colmajor(D, np.float32)) if dtype is None else (_host_16bit(Q, dtype), _host_16bit(D, dtype))
     if q.ndim != 3:
         raise ValueError("Q must be (dim, T, B)")
     dl = np.ascontiguousarray(doclens, dtype=np.int64)
@@ -212,48 +195,16 @@ def maxsim_batch(Q, D, doclens, owner=None, device: int = 0, dtype=None):
         raise ValueError("owner must hold one query number per passage")
     dim, T, B = q.shape
     scores = np.zeros(dl.size if ow is not None else (dl.size, B), dtype=np.float32, order="F")
-    n_D = i64(d.shape[1] if d.ndim == 2 else 0)
-    if dtype is None:
-        check(lib().clb_maxsim_batch(device, fptr(q), i64(dim), i64(T), i64(B), fptr(d), n_D,
-                                     fptr(dl), i64(dl.size), fptr(ow) if ow is not None else None, fptr(scores)))
+    shape = (i64(dim), i64(T), i64(B))
+    tail = (i64(d.shape[1] if d.ndim == 2 else 0), fptr(dl), i64(dl.size), fptr(ow) if ow is not None else None, fptr(scores))
+    if int8:
+        check(lib().clb_maxsim_batch_i8(device, fptr(q), I8, fptr(qs), *shape, fptr(d), fptr(ds), *tail))
+    elif dtype is None:
+        check(lib().clb_maxsim_batch(device, fptr(q), *shape, fptr(d), *tail))
     else:
         ty = F16 if dtype == "float16" else BF16
-        check(lib().clb_maxsim_batch_half(device, fptr(q), ty, i64(dim), i64(T), i64(B), fptr(d), ty, n_D,
-                                          fptr(dl), i64(dl.size), fptr(ow) if ow is not None else None, fptr(scores)))
+        check(lib().clb_maxsim_batch_half(device, fptr(q), ty, *shape, fptr(d), ty, *tail))
     return scores
-
-
-def _maxsim_batch_int8_device(d_Q, d_D, d_doclens, owner, out, work, stream, d_scale, q_scale):
-    import torch
-    if d_D.dtype != torch.int8 or d_scale is None:
-        raise ValueError("int8 scoring takes an int8 d_D with d_scale, one float32 scale per embedding")
-    if (d_Q.dtype == torch.int8) != (q_scale is not None) or d_Q.dtype not in (torch.int8, torch.float32):
-        raise ValueError("d_Q must be float32 (quantised on the device) or int8 with q_scale")
-    q, d, dl, ds = _dev_rows(d_Q), _dev_rows(d_D), _dev_rows(d_doclens, torch.int64), _dev_rows(d_scale, torch.float32)
-    qs = None if q_scale is None else _dev_rows(q_scale, torch.float32)
-    if q.dim() != 3 or d.dim() != 2 or d.shape[1] != q.shape[2]:
-        raise ValueError("d_Q must be (B, T, dim) and d_D (n, dim)")
-    B, T, dim = (int(x) for x in q.shape)
-    N = int(dl.numel())
-    if ds.numel() != d.shape[0] or (qs is not None and qs.numel() != B * T):
-        raise ValueError("d_scale / q_scale: one scale per embedding")
-    ow = None if owner is None else _dev_rows(owner, torch.int32)
-    if ow is not None and ow.numel() != N:
-        raise ValueError("owner must hold one query number per passage")
-    if out is None:
-        out = torch.empty(N if ow is not None else (B, N), dtype=torch.float32, device=q.device)
-    if work is None:
-        work = torch.empty(int(lib().clb_maxsim_batch_i8_work_bytes(i64(N), i64(B), i64(T), i64(dim))), dtype=torch.uint8, device=q.device)
-    o = _dev_rows(out, torch.float32); wk = _dev_rows(work)
-    if o.numel() != (N if ow is not None else N * B):
-        raise ValueError("out: one score per passage (owned) or per (query, passage)")
-    st = torch.cuda.current_stream(q.device).cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
-    check(lib().clb_maxsim_batch_i8_device(q.device.index, C.c_void_p(q.data_ptr()), F32 if qs is None else I8,
-                                           C.c_void_p(qs.data_ptr()) if qs is not None else None, i64(dim), i64(T), i64(B),
-                                           C.c_void_p(d.data_ptr()), C.c_void_p(ds.data_ptr()), i64(d.shape[0]), C.c_void_p(dl.data_ptr()),
-                                           i64(N), C.c_void_p(ow.data_ptr()) if ow is not None else None, C.c_void_p(o.data_ptr()),
-                                           C.c_void_p(wk.data_ptr()), i64(wk.numel() * wk.element_size()), C.c_void_p(st)))
-    return out
 
 
 def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, stream=None, *, d_scale=None, q_scale=None):
@@ -269,40 +220,50 @@ def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, st
     (clb_maxsim_batch_i8_device): d_Q float32 (quantised on the device) or int8 with `q_scale` (B, T); `work`
     clb_maxsim_batch_i8_work_bytes long.  Any other mix of int8 operands and scales is a ValueError."""
     import torch
-    if torch.int8 in (d_D.dtype, d_Q.dtype) or d_scale is not None or q_scale is not None:
-        return _maxsim_batch_int8_device(d_Q, d_D, d_doclens, owner, out, work, stream, d_scale, q_scale)
-    half ={torch.float16: F16, torch.bfloat16: BF16}.get(d_D.dtype)
-    if half is not None and d_Q.dtype not in (torch.float32, d_D.dtype):
+    int8 = torch.int8 in (d_D.dtype, d_Q.dtype) or d_scale is not None or q_scale is not None
+    half = None if int8 else {torch.float16: F16, torch.bfloat16: BF16}.get(d_D.dtype)
+    if int8:
+        if d_D.dtype != torch.int8 or d_scale is None:
+            raise ValueError("int8 scoring takes an int8 d_D with d_scale, one float32 scale per embedding")
+        if (d_Q.dtype == torch.int8) != (q_scale is not None) or d_Q.dtype not in (torch.int8, torch.float32):
+            raise ValueError("d_Q must be float32 (quantised on the device) or int8 with q_scale")
+    elif half is not None and d_Q.dtype not in (torch.float32, d_D.dtype):
         raise ValueError(f"d_Q must be float32 or {d_D.dtype}, got {d_Q.dtype}")
-    q = _dev_rows(d_Q, None if half is not None else torch.float32)
-    d = _dev_rows(d_D, None if half is not None else torch.float32); dl = _dev_rows(d_doclens, torch.int64)
+    plain = None if int8 or half is not None else torch.float32
+    q, d, dl = _dev_rows(d_Q, plain), _dev_rows(d_D, plain), _dev_rows(d_doclens, torch.int64)
+    ds = _dev_rows(d_scale, torch.float32) if int8 else None
+    qs = None if q_scale is None else _dev_rows(q_scale, torch.float32)
     if q.dim() != 3 or d.dim() != 2 or d.shape[1] != q.shape[2]:
         raise ValueError("d_Q must be (B, T, dim) and d_D (n, dim)")
     B, T, dim = (int(x) for x in q.shape)
     N = int(dl.numel())
+    if int8 and (ds.numel() != d.shape[0] or (qs is not None and qs.numel() != B * T)):
+        raise ValueError("d_scale / q_scale: one scale per embedding")
     ow = None if owner is None else _dev_rows(owner, torch.int32)
     if ow is not None and ow.numel() != N:
         raise ValueError("owner must hold one query number per passage")
-    if half is None:
-        need = int(lib().clb_maxsim_batch_work_bytes(i64(N), i64(B), i64(T)))
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())      # noqa: E731
+    shape, sizes = (i64(dim), i64(T), i64(B)), (i64(N), i64(B), i64(T))
+    q_type = F32 if q.dtype == torch.float32 else (I8 if int8 else half)
+    if int8:
+        entry, work_bytes = lib().clb_maxsim_batch_i8_device, lambda: lib().clb_maxsim_batch_i8_work_bytes(*sizes, i64(dim))
+        operands = (ptr(q), q_type, ptr(qs), *shape, ptr(d), ptr(ds))
+    elif half is not None:
+        entry, work_bytes = lib().clb_maxsim_batch_half_device, lambda: lib().clb_maxsim_batch_half_work_bytes(*sizes, i64(dim))
+        operands = (ptr(q), q_type, *shape, ptr(d), half)
     else:
-        need = int(lib().clb_maxsim_batch_half_work_bytes(i64(N), i64(B), i64(T), i64(dim)))
+        entry, work_bytes = lib().clb_maxsim_batch_device, lambda: lib().clb_maxsim_batch_work_bytes(*sizes)
+        operands = (ptr(q), *shape, ptr(d))
     if out is None:
         out = torch.empty(N if ow is not None else (B, N), dtype=torch.float32, device=q.device)
     if work is None:
-        work = torch.empty(need, dtype=torch.uint8, device=q.device)
+        work = torch.empty(int(work_bytes()), dtype=torch.uint8, device=q.device)
     o = _dev_rows(out, torch.float32); wk = _dev_rows(work)
     if o.numel() != (N if ow is not None else N * B):
         raise ValueError("out: one score per passage (owned) or per (query, passage)")
     st = torch.cuda.current_stream(q.device).cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
-    tail = (C.c_void_p(dl.data_ptr()), i64(N), C.c_void_p(ow.data_ptr()) if ow is not None else None, C.c_void_p(o.data_ptr()),
-            C.c_void_p(wk.data_ptr()), i64(wk.numel() * wk.element_size()), C.c_void_p(st))
-    if half is None:
-        check(lib().clb_maxsim_batch_device(q.device.index, C.c_void_p(q.data_ptr()), i64(dim), i64(T), i64(B), C.c_void_p(d.data_ptr()),
-                                            i64(d.shape[0]), *tail))
-    else:
-        check(lib().clb_maxsim_batch_half_device(q.device.index, C.c_void_p(q.data_ptr()), F32 if q.dtype == torch.float32 else half,
-                                                 i64(dim), i64(T), i64(B), C.c_void_p(d.data_ptr()), half, i64(d.shape[0]), *tail))
+    check(entry(q.device.index, *operands, i64(d.shape[0]), ptr(dl), i64(N), ptr(ow), ptr(o), ptr(wk), i64(wk.numel() * wk.element_size()),
+                C.c_void_p(st)))
     return out
 
 

@@ -1,12 +1,11 @@
 // dense.hip -- MaxSim of un-indexed passages for a query batch (include/colbert_hip.h: clb_maxsim_batch*): the scorer between
-// the encoder's device outputs, with no index and no handle.  Kernels: dense_kernels.hpp (fp32 embeddings, the oracle's bits),
-// dense_half_kernels.hpp (fp16 / bf16 embeddings: clb_maxsim_batch_half*), dense_i8_kernels.hpp (int8 embeddings with one scale
-// each: clb_maxsim_batch_i8*, clb_quantize_rows*).
+// the encoder's device outputs, with no index and no handle.  One kernel frame (dense_kernels.hpp) for four embedding formats
+// (dense_formats.hpp): fp32 (clb_maxsim_batch*, the oracle's bits), fp16 / bf16 (clb_maxsim_batch_half*), int8 with one scale
+// each (clb_maxsim_batch_i8*, clb_quantize_rows*); one device path and one host-array path behind the six entry points.
 #include <algorithm>
 #include <cmath>
 
-#include "dense_half_kernels.hpp"
-#include "dense_i8_kernels.hpp"
+#include "dense_formats.hpp"
 
 using namespace clb;
 
@@ -14,22 +13,67 @@ namespace {
 
 inline int64_t align256(int64_t n) { return (n + 255) / 256 * 256; }
 
-int check_shape(int64_t dim, int64_t T, int64_t B, int64_t n_D, int64_t N) {
-    if (dim % 4 != 0 || dim < 4 || dim > 1024)
-        return fail(CLB_EUNSUPPORTED, "maxsim_batch serves dim %% 4 == 0, 4 <= dim <= 1024 (dim = %lld): score one query at a time with clb_maxsim", (long long)dim);
-    if (T < 1 || T > 128)
-        return fail(CLB_EUNSUPPORTED, "maxsim_batch serves 1 <= T <= 128 (T = %lld): score one query at a time with clb_maxsim", (long long)T);
-    if (B < 1 || N < 0 || n_D < 0) return fail(CLB_EARGUMENT, "maxsim_batch: B >= 1, N >= 0 and n_D >= 0 are required");
+// What the host needs of a format F: its sizes, its LDS layout, its kernels.  Indexed by D's type, CLB_F32 .. CLB_I8.
+typedef void (*DenseKernel)(const void*, const float*, int, int, int, const void*, const float*, const int64_t*, int64_t, const int32_t*,
+                            int, int, float*);
+struct DenseFormat {
+    int elem, dim_multiple;                             // bytes per element; dim is a multiple of one 16-byte column's elements
+    bool scaled;
+    DenseLayout (*layout)(int dim, int T, int QB, int G, int nw, bool owned);
+    DenseKernel k128, kany;                             // both operands in registers at dim 128; any served dim
+};
+template <typename F>
+DenseFormat dense_format() {
+    return {F::kElem, 16 / F::kElem, F::kScaled, dense_layout<F>, dense_maxsim_kernel<F, 128 / F::kK>, dense_maxsim_kernel<F, 0>};
+}
+const DenseFormat& format_of(int d_type) {
+    static const DenseFormat f[4] = {dense_format<DenseF32>(), dense_format<DenseF16>(), dense_format<DenseBF16>(), dense_format<DenseI8>()};
+    return f[d_type];
+}
+
+// One call, as every entry point states it.  Q and D are device arrays in run_dense_device, host arrays in run_dense_host.
+struct DenseCall {
+    const char* who;                                    // the name its messages carry: maxsim_batch, maxsim_batch_half, maxsim_batch_i8
+    int family;                                         // the entry point's: CLB_F32, CLB_F16 (D in either 16-bit type) or CLB_I8
+    int q_type, d_type;
+    const void* Q;
+    const float* qscale;
+    const void* D;
+    const float* dscale;
+    int64_t dim, T, B, n_D, N;
+    const int64_t* doclens;
+    const int32_t* owner;
+    float* scores;
+    void* work = nullptr;
+    int64_t work_bytes = 0;
+    hipStream_t st = nullptr;
+};
+
+int check_dim(const char* who, int m, int64_t dim, const char* advice) {
+    if (dim % m != 0 || dim < m || dim > 1024)
+        return fail(CLB_EUNSUPPORTED, "%s serves dim %% %d == 0, %d <= dim <= 1024 (dim = %lld)%s", who, m, m, (long long)dim, advice);
     return CLB_OK;
 }
 
-// How a launch is cut: G passages and QB queries per work-group, nw waves of 16 rows, and the dynamic LDS that takes.
+int check_shape(const DenseCall& c) {
+    const char* advice = c.family == CLB_F32 ? ": score one query at a time with clb_maxsim" : "";
+    if (c.family == CLB_I8 && c.q_type != CLB_F32 && c.q_type != CLB_I8)
+        return fail(CLB_EUNSUPPORTED, "%s serves Q in fp32 or int8 (q_type = %d)", c.who, c.q_type);
+    if (c.family == CLB_F16 && ((c.d_type != CLB_F16 && c.d_type != CLB_BF16) || (c.q_type != CLB_F32 && c.q_type != c.d_type)))
+        return fail(CLB_EUNSUPPORTED, "%s serves D in fp16 or bf16 and Q in fp32 or D's type (q_type = %d, d_type = %d)", c.who, c.q_type, c.d_type);
+    CLB_TRY(check_dim(c.who, format_of(c.d_type).dim_multiple, c.dim, advice));
+    if (c.T < 1 || c.T > 128) return fail(CLB_EUNSUPPORTED, "%s serves 1 <= T <= 128 (T = %lld)%s", c.who, (long long)c.T, advice);
+    if (c.B < 1 || c.N < 0 || c.n_D < 0) return fail(CLB_EARGUMENT, "%s: B >= 1, N >= 0 and n_D >= 0 are required", c.who);
+    return CLB_OK;
+}
+
+// How a launch is cut: G passages and QB queries per work-group, nw waves, and the dynamic LDS that takes (dense_layout).
 struct DensePlan {
     int G, QB, nw;
     unsigned gx, gy;
     size_t lds;
 };
-DensePlan plan_dense(int dim, int T, int64_t B, int64_t N, bool owned) {
+DensePlan plan_dense(const DenseFormat& f, int dim, int T, int64_t B, int64_t N, bool owned) {
     DensePlan p;
     const int TP = T | 1;
     const int g_target = (int)std::min<int64_t>(kDenseMaxGroup, std::max<int64_t>(1, (N + 2047) / 2048));   // >= ~2048 work-groups first
@@ -38,9 +82,23 @@ DensePlan plan_dense(int dim, int T, int64_t B, int64_t N, bool owned) {
     p.nw = dim <= 512 ? 4 : 2;
     p.gx = (unsigned)((N + p.G - 1) / p.G);
     p.gy = owned ? 1u : (unsigned)((B + p.QB - 1) / p.QB);
-    p.lds = kDenseHeadBytes + ((size_t)p.QB * p.G * TP * 4 + 15) / 16 * 16 + (size_t)4 * 16 * p.nw * dense_row_stride(dim);
+    p.lds = f.layout(dim, T, p.QB, p.G, p.nw, owned).total;
     return p;
 }
+
+// The work buffer: the clamped offsets (per-pair maxima never leave LDS); behind them, when Q arrives in fp32 and D does not
+// hold fp32, Q in D's format and -- a scaled format -- its scales.
+struct DenseWork {
+    int64_t off_bytes, q_bytes, s_bytes;
+    DenseWork(int d_type, int64_t N, int64_t B, int64_t T, int64_t dim) {
+        const DenseFormat& f = format_of(d_type);
+        const int64_t bt = std::max<int64_t>(B, 0) * std::max<int64_t>(T, 0);
+        off_bytes = align256((int64_t)sizeof(int64_t) * (std::max<int64_t>(N, 0) + 1));
+        q_bytes = d_type == CLB_F32 ? 0 : align256(f.elem * bt * std::max<int64_t>(dim, 0));
+        s_bytes = f.scaled ? align256(4 * bt) : 0;
+    }
+    int64_t total() const { return off_bytes + q_bytes + s_bytes; }
+};
 
 // What a host call checks before it uploads anything: the doclens against n_D, the owners against the batch.
 int check_host_lists(const int64_t* doclens, int64_t N, int64_t n_D, const int32_t* owner, int64_t B) {
@@ -59,58 +117,6 @@ int check_host_lists(const int64_t* doclens, int64_t N, int64_t n_D, const int32
     return CLB_OK;
 }
 
-// ---- 16-bit embeddings (dense_half_kernels.hpp) ----------------------------------------------------------------------------
-int check_half(int q_type, int d_type, int64_t dim, int64_t T, int64_t B, int64_t n_D, int64_t N) {
-    if ((d_type != CLB_F16 && d_type != CLB_BF16) || (q_type != CLB_F32 && q_type != d_type))
-        return fail(CLB_EUNSUPPORTED, "maxsim_batch_half serves D in fp16 or bf16 and Q in fp32 or D's type (q_type = %d, d_type = %d)", q_type, d_type);
-    if (dim % 8 != 0 || dim < 8 || dim > 1024)
-        return fail(CLB_EUNSUPPORTED, "maxsim_batch_half serves dim %% 8 == 0, 8 <= dim <= 1024 (dim = %lld)", (long long)dim);
-    if (T < 1 || T > 128) return fail(CLB_EUNSUPPORTED, "maxsim_batch_half serves 1 <= T <= 128 (T = %lld)", (long long)T);
-    if (B < 1 || N < 0 || n_D < 0) return fail(CLB_EARGUMENT, "maxsim_batch_half: B >= 1, N >= 0 and n_D >= 0 are required");
-    return CLB_OK;
-}
-
-// plan_dense's G, QB and grid; waves of 32 rows and the 16-bit rows' LDS footprint
-DensePlan plan_dense_half(int dim, int T, int64_t B, int64_t N, bool owned) {
-    DensePlan p = plan_dense(dim, T, B, N, owned);
-    p.lds = kDenseHeadBytes + ((size_t)p.QB * p.G * (T | 1) * 4 + 15) / 16 * 16 + (size_t)2 * kDenseHalfWaveRows * p.nw * dense_half_row_stride(dim);
-    return p;
-}
-
-template <typename H>
-int launch_half(const void* d_Q, bool q_f32, int dim, int T, int64_t B, const void* d_D, const int64_t* d_off, int64_t N,
-                const int32_t* d_owner, float* d_scores, void* d_qh, hipStream_t st) {
-    const bool owned = d_owner != nullptr;
-    const DensePlan p = plan_dense_half(dim, T, B, N, owned);
-    if (q_f32) {                                            // Q~ = Q rounded to nearest-even, behind the offsets in the work buffer
-        const int64_t n8 = B * T * dim / 8;
-        hipLaunchKernelGGL(dense_round_kernel<H>, dim3((unsigned)std::min<int64_t>((n8 + 255) / 256, 4096)), dim3(256), 0, st,
-                           (const float4*)d_Q, n8, (dense_u32x4*)d_qh);
-    }
-    auto kern = dim == 128 ? dense_maxsim_half_kernel<H, 4> : dense_maxsim_half_kernel<H, 0>;
-    if (p.lds > 64 * 1024) allow_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024);
-    hipLaunchKernelGGL(kern, dim3(p.gx, p.gy), dim3(64 * p.nw), p.lds, st, (const uint16_t*)(q_f32 ? d_qh : d_Q), dim, T, (int)B,
-                       (const uint16_t*)d_D, d_off, N, d_owner, p.G, p.QB, d_scores);
-    CLB_HIP(hipGetLastError());
-    return CLB_OK;
-}
-
-// ---- int8 embeddings with one fp32 scale each (dense_i8_kernels.hpp) --------------------------------------------------------
-int check_i8_dim(const char* who, int64_t dim) {
-    if (dim % 16 != 0 || dim < 16 || dim > 1024)
-        return fail(CLB_EUNSUPPORTED, "%s serves dim %% 16 == 0, 16 <= dim <= 1024 (dim = %lld)", who, (long long)dim);
-    return CLB_OK;
-}
-
-int check_i8(int q_type, int64_t dim, int64_t T, int64_t B, int64_t n_D, int64_t N) {
-    if (q_type != CLB_F32 && q_type != CLB_I8)
-        return fail(CLB_EUNSUPPORTED, "maxsim_batch_i8 serves Q in fp32 or int8 (q_type = %d)", q_type);
-    CLB_TRY(check_i8_dim("maxsim_batch_i8", dim));
-    if (T < 1 || T > 128) return fail(CLB_EUNSUPPORTED, "maxsim_batch_i8 serves 1 <= T <= 128 (T = %lld)", (long long)T);
-    if (B < 1 || N < 0 || n_D < 0) return fail(CLB_EARGUMENT, "maxsim_batch_i8: B >= 1, N >= 0 and n_D >= 0 are required");
-    return CLB_OK;
-}
-
 // one finite scale >= 0 per embedding
 int check_scales(const char* who, const char* what, const float* s, int64_t n) {
     for (int64_t i = 0; i < n; ++i)
@@ -119,146 +125,144 @@ int check_scales(const char* who, const char* what, const float* s, int64_t n) {
     return CLB_OK;
 }
 
-// plan_dense's G, QB and grid; waves of 64 rows, the int8 rows' and their scales' LDS footprint behind this kernel's own head
-DensePlan plan_dense_i8(int dim, int T, int64_t B, int64_t N, bool owned) {
-    DensePlan p = plan_dense(dim, T, B, N, owned);
-    p.lds = kDenseI8HeadBytes + ((size_t)p.QB * p.G * (T | 1) * 4 + 15) / 16 * 16 + (size_t)16 * kDenseI8WaveTiles * p.nw * (dense_i8_row_stride(dim) + 4);
-    return p;
-}
-
 void launch_quantize(const float* d_X, int dim, int64_t n, int8_t* d_X8, float* d_scale, hipStream_t st) {
     hipLaunchKernelGGL(dense_quantize_kernel, dim3((unsigned)std::min<int64_t>((n + 3) / 4, 8192)), dim3(256), 0, st, d_X, dim, n, d_X8, d_scale);
 }
 
-// Where the work buffer keeps a query quantised in the call: behind the offsets, values then scales.
-struct I8Work {
-    int64_t off_bytes, q_bytes, s_bytes;
-    I8Work(int64_t N, int64_t B, int64_t T, int64_t dim) {
-        const int64_t bt = std::max<int64_t>(B, 0) * std::max<int64_t>(T, 0);
-        off_bytes = align256((int64_t)sizeof(int64_t) * (std::max<int64_t>(N, 0) + 1));
-        q_bytes = align256(bt * std::max<int64_t>(dim, 0));
-        s_bytes = align256(4 * bt);
+
+// Every device entry point: checks, the work buffer's slices, the offsets, Q into D's format if it arrived in fp32, the kernel.
+int run_dense_device(int device, const DenseCall& c) {
+    CLB_TRY(check_shape(c));
+    const DenseFormat& f = format_of(c.d_type);
+    const bool q_f32 = c.q_type == CLB_F32, fp32 = c.d_type == CLB_F32;
+    if (c.N == 0) return CLB_OK;
+    if (!c.Q || !c.doclens || !c.scores || !c.work || ((!c.D || (f.scaled && !c.dscale)) && c.n_D > 0) || (f.scaled && !q_f32 && !c.qscale))
+        return fail(CLB_EARGUMENT, "%s: null argument", c.who);
+    if (fp32) {                                             // fp32 queries are read in dwords, the work buffer holds offsets only
+        if ((uintptr_t)c.D % 16 || (uintptr_t)c.work % 8)
+            return fail(CLB_EARGUMENT, "%s: D must be 16-byte aligned and the work buffer 8-byte aligned", c.who);
+    } else if ((uintptr_t)c.D % 16 || (uintptr_t)c.Q % 16 || (uintptr_t)c.work % 16) {
+        return fail(CLB_EARGUMENT, "%s: Q, %s and the work buffer must be 16-byte aligned", c.who, f.scaled ? "D8" : "D");
     }
-};
+    const DenseWork wk(c.d_type, c.N, c.B, c.T, c.dim);
+    if (c.work_bytes < wk.total())
+        return fail(CLB_EARGUMENT, "%s: work buffer of %lld bytes, clb_%s_work_bytes asks for %lld", c.who, (long long)c.work_bytes, c.who,
+                    (long long)wk.total());
+    const int dim = (int)c.dim, T = (int)c.T;
+    const DensePlan p = plan_dense(f, dim, T, c.B, c.N, c.owner != nullptr);
+    if (p.gy > 65535u || (c.N + p.G - 1) / p.G > 0x7fffffffLL)
+        return fail(CLB_EUNSUPPORTED, "%s: B = %lld, N = %lld exceed one launch", c.who, (long long)c.B, (long long)c.N);
+    CLB_TRY(use_device(device));
+    int64_t* d_off = reinterpret_cast<int64_t*>(c.work);
+    unsigned char* d_qf = reinterpret_cast<unsigned char*>(c.work) + wk.off_bytes;     // Q in D's format, then its scales
+    float* d_qs = reinterpret_cast<float*>(d_qf + wk.q_bytes);
+    const bool convert = q_f32 && !fp32;
+    // The order of the two launches ahead of the kernel is each format's own, as captured graphs hold it: a scaled format
+    // quantises Q before the offsets, a 16-bit format rounds it after them.
+    if (convert && f.scaled) launch_quantize(reinterpret_cast<const float*>(c.Q), dim, c.B * c.T, reinterpret_cast<int8_t*>(d_qf), d_qs, c.st);
+    hipLaunchKernelGGL(dense_offsets_kernel, dim3(1), dim3(1024), 0, c.st, c.doclens, c.N, c.n_D, d_off);
+    if (convert && !f.scaled) {                             // Q~ = Q rounded to nearest-even
+        const int64_t n8 = c.B * c.T * c.dim / 8;
+        hipLaunchKernelGGL(c.d_type == CLB_F16 ? dense_round_kernel<DenseF16> : dense_round_kernel<DenseBF16>,
+                           dim3((unsigned)std::min<int64_t>((n8 + 255) / 256, 4096)), dim3(256), 0, c.st, (const float4*)c.Q, n8, (dense_u32x4*)d_qf);
+    }
+    const DenseKernel kern = dim == 128 ? f.k128 : f.kany;
+    if (p.lds > 64 * 1024) allow_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024);
+    hipLaunchKernelGGL(kern, dim3(p.gx, p.gy), dim3(64 * p.nw), p.lds, c.st, convert ? (const void*)d_qf : c.Q,
+                       convert && f.scaled ? (const float*)d_qs : c.qscale, dim, T, (int)c.B, c.D, c.dscale, (const int64_t*)d_off, c.N, c.owner,
+                       p.G, p.QB, c.scores);
+    CLB_HIP(hipGetLastError());
+    return CLB_OK;
+}
+
+// Every host-array entry point: what a host call checks first, then upload, allocate, the device path, copy back, synchronise.
+int run_dense_host(int device, const DenseCall& h) {
+    CLB_TRY(check_shape(h));
+    const DenseFormat& f = format_of(h.d_type);
+    const bool q_f32 = h.q_type == CLB_F32;
+    if (h.N > 0 && (!h.doclens || !h.scores || !h.Q || (f.scaled && ((!q_f32 && !h.qscale) || (h.n_D > 0 && (!h.D || !h.dscale))))))
+        return fail(CLB_EARGUMENT, "%s: null argument", h.who);
+    if (f.scaled && h.N > 0 && !q_f32) CLB_TRY(check_scales(h.who, "query", h.qscale, h.B * h.T));
+    if (f.scaled && h.N > 0) CLB_TRY(check_scales(h.who, "passage", h.dscale, h.n_D));
+    CLB_TRY(check_host_lists(h.doclens, h.N, h.n_D, h.owner, h.B));
+    CLB_TRY(use_device(device));
+    if (h.N == 0) return CLB_OK;
+    hipStream_t st = nullptr;
+    CLB_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    const int64_t n_scores = h.owner ? h.N : h.N * h.B, wb = DenseWork(h.d_type, h.N, h.B, h.T, h.dim).total();
+    const bool qs_given = f.scaled && !q_f32;
+    DevBuf dQ, dQs, dD, dDs, dL, dO, dS, dW;
+    int rc = upload(dQ, h.Q, (size_t)(q_f32 ? 4 : f.elem) * h.dim * h.T * h.B, st);
+    if (!rc && qs_given) rc = upload(dQs, h.qscale, sizeof(float) * h.T * h.B, st);
+    if (!rc) rc = upload(dD, h.D, (size_t)f.elem * h.dim * h.n_D, st);
+    if (!rc && f.scaled) rc = upload(dDs, h.dscale, sizeof(float) * h.n_D, st);
+    if (!rc) rc = upload(dL, h.doclens, sizeof(int64_t) * h.N, st);
+    if (!rc && h.owner) rc = upload(dO, h.owner, sizeof(int32_t) * h.N, st);
+    if (!rc) rc = dS.alloc(sizeof(float) * n_scores);
+    if (!rc) rc = dW.alloc((size_t)wb);
+    if (!rc) {
+        DenseCall c = h;
+        c.Q = dQ.p, c.qscale = dQs.as<float>(), c.D = dD.p, c.dscale = dDs.as<float>(), c.doclens = dL.as<int64_t>();
+        c.owner = h.owner ? dO.as<int32_t>() : nullptr, c.scores = dS.as<float>(), c.work = dW.p, c.work_bytes = wb, c.st = st;
+        rc = run_dense_device(device, c);
+    }
+    if (!rc && hipMemcpyAsync(h.scores, dS.p, sizeof(float) * n_scores, hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = fail(CLB_EHIP, "%s: copying the scores back failed", h.who);
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(CLB_EHIP, "%s: hipStreamSynchronize failed", h.who);
+    (void)hipStreamDestroy(st);
+    return rc;
+}
 
 }  // namespace
 
 extern "C" {
 
-int64_t clb_maxsim_batch_work_bytes(int64_t N, int64_t B, int64_t T) {
-    (void)B; (void)T;                                   // the scratch is the clamped offsets: per-pair maxima never leave LDS
-    return align256((int64_t)sizeof(int64_t) * (std::max<int64_t>(N, 0) + 1));
-}
+int64_t clb_maxsim_batch_work_bytes(int64_t N, int64_t B, int64_t T) { return DenseWork(CLB_F32, N, B, T, 0).total(); }
+
+int64_t clb_maxsim_batch_half_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim) { return DenseWork(CLB_F16, N, B, T, dim).total(); }
+
+int64_t clb_maxsim_batch_i8_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim) { return DenseWork(CLB_I8, N, B, T, dim).total(); }
 
 int clb_maxsim_batch_device(int device, const float* d_Q, int64_t dim, int64_t T, int64_t B, const float* d_D, int64_t n_D,
                             const int64_t* d_doclens, int64_t N, const int32_t* d_owner, float* d_scores, void* d_work,
                             int64_t work_bytes, void* hip_stream) {
-    CLB_TRY(check_shape(dim, T, B, n_D, N));
-    if (N == 0) return CLB_OK;
-    if (!d_Q || !d_doclens || !d_scores || !d_work || (!d_D && n_D > 0)) return fail(CLB_EARGUMENT, "maxsim_batch: null argument");
-    if ((uintptr_t)d_D % 16 || (uintptr_t)d_work % 8) return fail(CLB_EARGUMENT, "maxsim_batch: D must be 16-byte aligned and the work buffer 8-byte aligned");
-    if (work_bytes < clb_maxsim_batch_work_bytes(N, B, T))
-        return fail(CLB_EARGUMENT, "maxsim_batch: work buffer of %lld bytes, clb_maxsim_batch_work_bytes asks for %lld", (long long)work_bytes,
-                    (long long)clb_maxsim_batch_work_bytes(N, B, T));
-    const bool owned = d_owner != nullptr;
-    const DensePlan p = plan_dense((int)dim, (int)T, B, N, owned);
-    if (p.gy > 65535u || (N + p.G - 1) / p.G > 0x7fffffffLL) return fail(CLB_EUNSUPPORTED, "maxsim_batch: B = %lld, N = %lld exceed one launch", (long long)B, (long long)N);
-    CLB_TRY(use_device(device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    int64_t* d_off = reinterpret_cast<int64_t*>(d_work);
-    hipLaunchKernelGGL(dense_offsets_kernel, dim3(1), dim3(1024), 0, st, d_doclens, N, n_D, d_off);
-    auto kern = dim == 128 ? dense_maxsim_kernel<32> : dense_maxsim_kernel<0>;
-    if (p.lds > 64 * 1024) allow_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024);
-    hipLaunchKernelGGL(kern, dim3(p.gx, p.gy), dim3(64 * p.nw), p.lds, st, d_Q, (int)dim, (int)T, (int)B, d_D, (const int64_t*)d_off, N,
-                       d_owner, p.G, p.QB, d_scores);
-    CLB_HIP(hipGetLastError());
-    return CLB_OK;
+    return run_dense_device(device, {"maxsim_batch", CLB_F32, CLB_F32, CLB_F32, d_Q, nullptr, d_D, nullptr, dim, T, B, n_D, N, d_doclens, d_owner,
+                                     d_scores, d_work, work_bytes, (hipStream_t)hip_stream});
 }
 
 int clb_maxsim_batch(int device, const float* Q, int64_t dim, int64_t T, int64_t B, const float* D, int64_t n_D,
                      const int64_t* doclens, int64_t N, const int32_t* owner, float* scores) {
-    CLB_TRY(check_shape(dim, T, B, n_D, N));
-    if (N > 0 && (!doclens || !scores || !Q)) return fail(CLB_EARGUMENT, "maxsim_batch: null argument");
-    CLB_TRY(check_host_lists(doclens, N, n_D, owner, B));
-    CLB_TRY(use_device(device));
-    if (N == 0) return CLB_OK;
-    hipStream_t st = nullptr;
-    CLB_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    const int64_t n_scores = owner ? N : N * B, wb = clb_maxsim_batch_work_bytes(N, B, T);
-    DevBuf dQ, dD, dL, dO, dS, dW;
-    int rc = upload(dQ, Q, sizeof(float) * dim * T * B, st);
-    if (!rc) rc = upload(dD, D, sizeof(float) * dim * n_D, st);
-    if (!rc) rc = upload(dL, doclens, sizeof(int64_t) * N, st);
-    if (!rc && owner) rc = upload(dO, owner, sizeof(int32_t) * N, st);
-    if (!rc) rc = dS.alloc(sizeof(float) * n_scores);
-    if (!rc) rc = dW.alloc((size_t)wb);
-    if (!rc)
-        rc = clb_maxsim_batch_device(device, dQ.as<float>(), dim, T, B, dD.as<float>(), n_D, dL.as<int64_t>(), N,
-                                     owner ? dO.as<int32_t>() : nullptr, dS.as<float>(), dW.p, wb, st);
-    if (!rc && hipMemcpyAsync(scores, dS.p, sizeof(float) * n_scores, hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = fail(CLB_EHIP, "maxsim_batch: copying the scores back failed");
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(CLB_EHIP, "maxsim_batch: hipStreamSynchronize failed");
-    (void)hipStreamDestroy(st);
-    return rc;
-}
-
-int64_t clb_maxsim_batch_half_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim) {
-    const int64_t q = std::max<int64_t>(B, 0) * std::max<int64_t>(T, 0) * std::max<int64_t>(dim, 0);   // Q~, when Q arrives in fp32
-    return clb_maxsim_batch_work_bytes(N, B, T) + align256(2 * q);
+    return run_dense_host(device, {"maxsim_batch", CLB_F32, CLB_F32, CLB_F32, Q, nullptr, D, nullptr, dim, T, B, n_D, N, doclens, owner, scores});
 }
 
 int clb_maxsim_batch_half_device(int device, const void* d_Q, int q_type, int64_t dim, int64_t T, int64_t B, const void* d_D,
                                  int d_type, int64_t n_D, const int64_t* d_doclens, int64_t N, const int32_t* d_owner,
                                  float* d_scores, void* d_work, int64_t work_bytes, void* hip_stream) {
-    CLB_TRY(check_half(q_type, d_type, dim, T, B, n_D, N));
-    if (N == 0) return CLB_OK;
-    if (!d_Q || !d_doclens || !d_scores || !d_work || (!d_D && n_D > 0)) return fail(CLB_EARGUMENT, "maxsim_batch_half: null argument");
-    if ((uintptr_t)d_D % 16 || (uintptr_t)d_Q % 16 || (uintptr_t)d_work % 16)
-        return fail(CLB_EARGUMENT, "maxsim_batch_half: Q, D and the work buffer must be 16-byte aligned");
-    if (work_bytes < clb_maxsim_batch_half_work_bytes(N, B, T, dim))
-        return fail(CLB_EARGUMENT, "maxsim_batch_half: work buffer of %lld bytes, clb_maxsim_batch_half_work_bytes asks for %lld",
-                    (long long)work_bytes, (long long)clb_maxsim_batch_half_work_bytes(N, B, T, dim));
-    const DensePlan p = plan_dense_half((int)dim, (int)T, B, N, d_owner != nullptr);
-    if (p.gy > 65535u || (N + p.G - 1) / p.G > 0x7fffffffLL)
-        return fail(CLB_EUNSUPPORTED, "maxsim_batch_half: B = %lld, N = %lld exceed one launch", (long long)B, (long long)N);
-    CLB_TRY(use_device(device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    int64_t* d_off = reinterpret_cast<int64_t*>(d_work);
-    void* d_qh = reinterpret_cast<unsigned char*>(d_work) + clb_maxsim_batch_work_bytes(N, B, T);
-    hipLaunchKernelGGL(dense_offsets_kernel, dim3(1), dim3(1024), 0, st, d_doclens, N, n_D, d_off);
-    return (d_type == CLB_F16 ? launch_half<DenseF16> : launch_half<DenseBF16>)(d_Q, q_type == CLB_F32, (int)dim, (int)T, B, d_D, d_off, N,
-                                                                                 d_owner, d_scores, d_qh, st);
+    return run_dense_device(device, {"maxsim_batch_half", CLB_F16, q_type, d_type, d_Q, nullptr, d_D, nullptr, dim, T, B, n_D, N, d_doclens,
+                                     d_owner, d_scores, d_work, work_bytes, (hipStream_t)hip_stream});
 }
 
 int clb_maxsim_batch_half(int device, const void* Q, int q_type, int64_t dim, int64_t T, int64_t B, const void* D, int d_type,
                           int64_t n_D, const int64_t* doclens, int64_t N, const int32_t* owner, float* scores) {
-    CLB_TRY(check_half(q_type, d_type, dim, T, B, n_D, N));
-    if (N > 0 && (!doclens || !scores || !Q)) return fail(CLB_EARGUMENT, "maxsim_batch_half: null argument");
-    CLB_TRY(check_host_lists(doclens, N, n_D, owner, B));
-    CLB_TRY(use_device(device));
-    if (N == 0) return CLB_OK;
-    hipStream_t st = nullptr;
-    CLB_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    const int64_t n_scores = owner ? N : N * B, wb = clb_maxsim_batch_half_work_bytes(N, B, T, dim);
-    DevBuf dQ, dD, dL, dO, dS, dW;
-    int rc = upload(dQ, Q, (size_t)(q_type == CLB_F32 ? 4 : 2) * dim * T * B, st);
-    if (!rc) rc = upload(dD, D, (size_t)2 * dim * n_D, st);
-    if (!rc) rc = upload(dL, doclens, sizeof(int64_t) * N, st);
-    if (!rc && owner) rc = upload(dO, owner, sizeof(int32_t) * N, st);
-    if (!rc) rc = dS.alloc(sizeof(float) * n_scores);
-    if (!rc) rc = dW.alloc((size_t)wb);
-    if (!rc)
-        rc = clb_maxsim_batch_half_device(device, dQ.p, q_type, dim, T, B, dD.p, d_type, n_D, dL.as<int64_t>(), N,
-                                          owner ? dO.as<int32_t>() : nullptr, dS.as<float>(), dW.p, wb, st);
-    if (!rc && hipMemcpyAsync(scores, dS.p, sizeof(float) * n_scores, hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = fail(CLB_EHIP, "maxsim_batch_half: copying the scores back failed");
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(CLB_EHIP, "maxsim_batch_half: hipStreamSynchronize failed");
-    (void)hipStreamDestroy(st);
-    return rc;
+    return run_dense_host(device, {"maxsim_batch_half", CLB_F16, q_type, d_type, Q, nullptr, D, nullptr, dim, T, B, n_D, N, doclens, owner,
+                                   scores});
+}
+
+int clb_maxsim_batch_i8_device(int device, const void* d_Q, int q_type, const float* d_qscale, int64_t dim, int64_t T, int64_t B,
+                               const int8_t* d_D8, const float* d_dscale, int64_t n_D, const int64_t* d_doclens, int64_t N,
+                               const int32_t* d_owner, float* d_scores, void* d_work, int64_t work_bytes, void* hip_stream) {
+    return run_dense_device(device, {"maxsim_batch_i8", CLB_I8, q_type, CLB_I8, d_Q, d_qscale, d_D8, d_dscale, dim, T, B, n_D, N, d_doclens, d_owner,
+                                     d_scores, d_work, work_bytes, (hipStream_t)hip_stream});
+}
+
+int clb_maxsim_batch_i8(int device, const void* Q, int q_type, const float* qscale, int64_t dim, int64_t T, int64_t B,
+                        const int8_t* D8, const float* dscale, int64_t n_D, const int64_t* doclens, int64_t N, const int32_t* owner,
+                        float* scores) {
+    return run_dense_host(device, {"maxsim_batch_i8", CLB_I8, q_type, CLB_I8, Q, qscale, D8, dscale, dim, T, B, n_D, N, doclens, owner, scores});
 }
 
 int clb_quantize_rows_device(int device, const float* d_X, int64_t dim, int64_t n, int8_t* d_X8, float* d_scale, void* hip_stream) {
-    CLB_TRY(check_i8_dim("quantize_rows", dim));
+    CLB_TRY(check_dim("quantize_rows", 16, dim, ""));
     if (n < 0) return fail(CLB_EARGUMENT, "quantize_rows: n >= 0 is required");
     if (n == 0) return CLB_OK;
     if (!d_X || !d_X8 || !d_scale) return fail(CLB_EARGUMENT, "quantize_rows: null argument");
@@ -270,7 +274,7 @@ int clb_quantize_rows_device(int device, const float* d_X, int64_t dim, int64_t 
 }
 
 int clb_quantize_rows(int device, const float* X, int64_t dim, int64_t n, int8_t* X8, float* scale) {
-    CLB_TRY(check_i8_dim("quantize_rows", dim));
+    CLB_TRY(check_dim("quantize_rows", 16, dim, ""));
     if (n < 0 || (n > 0 && (!X || !X8 || !scale))) return fail(CLB_EARGUMENT, "quantize_rows: n >= 0 and non-null buffers are required");
     for (int64_t e = 0; e < n; ++e)
         for (int64_t k = 0; k < dim; ++k)
@@ -288,80 +292,6 @@ int clb_quantize_rows(int device, const float* X, int64_t dim, int64_t n, int8_t
                 hipMemcpyAsync(scale, dS.p, sizeof(float) * n, hipMemcpyDeviceToHost, st) != hipSuccess))
         rc = fail(CLB_EHIP, "quantize_rows: copying the result back failed");
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(CLB_EHIP, "quantize_rows: hipStreamSynchronize failed");
-    (void)hipStreamDestroy(st);
-    return rc;
-}
-
-int64_t clb_maxsim_batch_i8_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim) {
-    const I8Work w(N, B, T, dim);                       // the offsets; Q8 and its scales, when Q arrives in fp32
-    return w.off_bytes + w.q_bytes + w.s_bytes;
-}
-
-int clb_maxsim_batch_i8_device(int device, const void* d_Q, int q_type, const float* d_qscale, int64_t dim, int64_t T, int64_t B,
-                               const int8_t* d_D8, const float* d_dscale, int64_t n_D, const int64_t* d_doclens, int64_t N,
-                               const int32_t* d_owner, float* d_scores, void* d_work, int64_t work_bytes, void* hip_stream) {
-    CLB_TRY(check_i8(q_type, dim, T, B, n_D, N));
-    if (N == 0) return CLB_OK;
-    if (!d_Q || !d_doclens || !d_scores || !d_work || ((!d_D8 || !d_dscale) && n_D > 0) || (q_type == CLB_I8 && !d_qscale))
-        return fail(CLB_EARGUMENT, "maxsim_batch_i8: null argument");
-    if ((uintptr_t)d_D8 % 16 || (uintptr_t)d_Q % 16 || (uintptr_t)d_work % 16)
-        return fail(CLB_EARGUMENT, "maxsim_batch_i8: Q, D8 and the work buffer must be 16-byte aligned");
-    const I8Work wk(N, B, T, dim);
-    if (work_bytes < wk.off_bytes + wk.q_bytes + wk.s_bytes)
-        return fail(CLB_EARGUMENT, "maxsim_batch_i8: work buffer of %lld bytes, clb_maxsim_batch_i8_work_bytes asks for %lld",
-                    (long long)work_bytes, (long long)(wk.off_bytes + wk.q_bytes + wk.s_bytes));
-    const DensePlan p = plan_dense_i8((int)dim, (int)T, B, N, d_owner != nullptr);
-    if (p.gy > 65535u || (N + p.G - 1) / p.G > 0x7fffffffLL)
-        return fail(CLB_EUNSUPPORTED, "maxsim_batch_i8: B = %lld, N = %lld exceed one launch", (long long)B, (long long)N);
-    CLB_TRY(use_device(device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    int64_t* d_off = reinterpret_cast<int64_t*>(d_work);
-    const int8_t* d_q8 = reinterpret_cast<const int8_t*>(d_Q);
-    if (q_type == CLB_F32) {                                // Q8 and its scales behind the offsets in the work buffer
-        int8_t* q8 = reinterpret_cast<int8_t*>(d_work) + wk.off_bytes;
-        float* qs = reinterpret_cast<float*>(q8 + wk.q_bytes);
-        launch_quantize(reinterpret_cast<const float*>(d_Q), (int)dim, B * T, q8, qs, st);
-        d_q8 = q8;
-        d_qscale = qs;
-    }
-    hipLaunchKernelGGL(dense_offsets_kernel, dim3(1), dim3(1024), 0, st, d_doclens, N, n_D, d_off);
-    auto kern = dim == 128 ? dense_maxsim_i8_kernel<2, kDenseI8WaveTiles> : dense_maxsim_i8_kernel<0, kDenseI8WaveTiles>;
-    if (p.lds > 64 * 1024) allow_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024);
-    hipLaunchKernelGGL(kern, dim3(p.gx, p.gy), dim3(64 * p.nw), p.lds, st, d_q8, d_qscale, (int)dim, (int)T, (int)B, d_D8, d_dscale,
-                       (const int64_t*)d_off, N, d_owner, p.G, p.QB, d_scores);
-    CLB_HIP(hipGetLastError());
-    return CLB_OK;
-}
-
-int clb_maxsim_batch_i8(int device, const void* Q, int q_type, const float* qscale, int64_t dim, int64_t T, int64_t B,
-                        const int8_t* D8, const float* dscale, int64_t n_D, const int64_t* doclens, int64_t N, const int32_t* owner,
-                        float* scores) {
-    CLB_TRY(check_i8(q_type, dim, T, B, n_D, N));
-    if (N > 0 && (!doclens || !scores || !Q || (q_type == CLB_I8 && !qscale) || (n_D > 0 && (!D8 || !dscale))))
-        return fail(CLB_EARGUMENT, "maxsim_batch_i8: null argument");
-    if (N > 0 && q_type == CLB_I8) CLB_TRY(check_scales("maxsim_batch_i8", "query", qscale, B * T));
-    if (N > 0) CLB_TRY(check_scales("maxsim_batch_i8", "passage", dscale, n_D));
-    CLB_TRY(check_host_lists(doclens, N, n_D, owner, B));
-    CLB_TRY(use_device(device));
-    if (N == 0) return CLB_OK;
-    hipStream_t st = nullptr;
-    CLB_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    const int64_t n_scores = owner ? N : N * B, wb = clb_maxsim_batch_i8_work_bytes(N, B, T, dim);
-    DevBuf dQ, dQs, dD, dDs, dL, dO, dS, dW;
-    int rc = upload(dQ, Q, (size_t)(q_type == CLB_F32 ? 4 : 1) * dim * T * B, st);
-    if (!rc && q_type == CLB_I8) rc = upload(dQs, qscale, sizeof(float) * T * B, st);
-    if (!rc) rc = upload(dD, D8, (size_t)dim * n_D, st);
-    if (!rc) rc = upload(dDs, dscale, sizeof(float) * n_D, st);
-    if (!rc) rc = upload(dL, doclens, sizeof(int64_t) * N, st);
-    if (!rc && owner) rc = upload(dO, owner, sizeof(int32_t) * N, st);
-    if (!rc) rc = dS.alloc(sizeof(float) * n_scores);
-    if (!rc) rc = dW.alloc((size_t)wb);
-    if (!rc)
-        rc = clb_maxsim_batch_i8_device(device, dQ.p, q_type, dQs.as<float>(), dim, T, B, dD.as<int8_t>(), dDs.as<float>(), n_D,
-                                        dL.as<int64_t>(), N, owner ? dO.as<int32_t>() : nullptr, dS.as<float>(), dW.p, wb, st);
-    if (!rc && hipMemcpyAsync(scores, dS.p, sizeof(float) * n_scores, hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = fail(CLB_EHIP, "maxsim_batch_i8: copying the scores back failed");
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(CLB_EHIP, "maxsim_batch_i8: hipStreamSynchronize failed");
     (void)hipStreamDestroy(st);
     return rc;
 }

@@ -1,24 +1,35 @@
-// dense_kernels.hpp -- MaxSim of un-indexed passages for a batch of queries (gfx950): fp32 embeddings in, fp32 scores out,
-// bit-identical to the CPU oracle's maxsim (ranking.jl:69-86).
-//   dot     v_mfma_f32_16x16x4_f32 with k walked in ascending order = the canonical d-ascending fmaf chain
-//           (search_kernels.hpp, generic_kernels.hpp): embeddings are tile rows, query tokens are tile columns
+// dense_kernels.hpp -- MaxSim of un-indexed passages for a batch of queries (gfx950): the one kernel frame of every
+// embedding format, fp32 scores out.  A format (dense_formats.hpp) supplies its element and fragment types, its MFMA, its
+// tile epilogue, its LDS row stride and head; everything below exists once.
+//   dot     one MFMA per K-block, the K-blocks in ascending order from +0: embeddings are tile rows, query tokens are tile
+//           columns.  Lane (r, g) holds, of K-block kb of row or token r, the FRAG consecutive elements at K kb + FRAG g --
+//           one fragment of sizeof(Frag) bytes, K = 4 FRAG -- and the same k in the A and the B operand.  The accumulator
+//           layout is the same for every format: lane (col r, g) holds the rows 4 g + i, i = 0..3.
 //   max     exact and order-free, so partial maxima of a passage combine in any order (LDS atomic max on order keys)
-//   sum     acc = 0; acc = acc + max_t for t ascending: one serial chain per (passage, query)
+//   sum     one serial chain per (passage, query), t ascending (dense_sum_maxima)
 //
 // Work split.  A work-group owns G consecutive PASSAGES (so its rows are consecutive and cut at passage boundaries) and, in
-// the all-pairs form, a block of QB queries.  It walks its rows in steps of 16 rows per wave: a step is brought from global
-// memory into LDS once with 16-byte loads (rows are contiguous, so the loads are dense), in rows padded to a stride = 4
-// mod 64 floats so that the MFMA A-operand reads -- lane (r, g) reads dim 4 s + g of row r -- touch 64 different banks.  At
-// dim 128 a wave then keeps its 16 rows as 32 VGPRs of A operand and re-uses them for every token tile of every query of
-// the block; the B operand of a token tile (16 tokens x 128 dims) is 32 VGPRs read from the query block.  Other dims walk
-// k at run time, the A operand read from LDS.
+// the all-pairs form, a block of QB queries.  It walks its rows in steps of 16 RT rows per wave (RT row tiles: F::kRowTiles):
+// a step is brought from global memory into LDS once with 16-byte loads (rows are contiguous, so the loads are dense), in
+// rows padded to the format's stride so that the A-operand reads are conflict-free.  At dim 128 (KB > 0) a wave keeps its
+// RT row tiles as registers of A operand and re-uses them for every token tile of every query of the block; other dims
+// (KB = 0) walk K at run time, both operands read where they lie.
+// Q residency (F::kResident, KB > 0, T <= 32).  The query's one or two token tiles are loaded when a wave meets a query it does
+// not hold and kept across owner runs, steps and -- in the all-pairs form, while the block holds one query -- the whole
+// work-group; a block of several queries reloads per (step, query).  Otherwise each token tile is read where it is used.
 // Segmentation.  Every row of a step knows its passage (s_rowp; -1 past the end of the group).  A tile whose 16 rows lie in
 // one passage reduces in registers (3 fmax, 2 shuffles) and issues one LDS atomic per token; a tile that straddles passages
 // issues one per (row, token), to the row's own passage -- a neighbour's row never reaches a maximum.  In the owned form a
-// wave multiplies a tile once per RUN of consecutive passages with the same owner.
+// wave multiplies a tile once per RUN of consecutive passages with the same owner, and only the row tiles that hold a row
+// of the run.
 // Long passages span several steps and several waves of their work-group: their partial maxima meet in the same LDS words.
-// Safety.  The offsets are a clamped scan (negative doclen = 0, every offset <= n_D), so no row at or past n_D is read; an
-// owner outside 0..B-1 multiplies nothing.  A (passage, query) that received no row keeps -Inf in every token and sums to -Inf.
+// K tail.  dim is a multiple of the 16 / kElem elements of a 16-byte column, so a lane's fragment lies wholly inside the row
+// or wholly past it; past it both operands are zero registers (nothing is read), and zeros add exact zeros (KB = 0 only).
+// Safety, all by construction and stated here once: the offsets are a clamped scan (negative doclen = 0, every offset <= n_D),
+// so no row at or past n_D is read -- neither its elements nor its scale; an owner outside 0..B-1 multiplies nothing and
+// reads no query scale; a token column past T reads token T - 1 and reaches no maximum; rows past the step's end (whatever
+// the LDS holds there) reach no maximum.  A (passage, query) that received no row keeps -Inf in every token and sums to -Inf.
+// No allocation, no host wait.
 #pragma once
 #include "common.hpp"
 
@@ -28,9 +39,26 @@ typedef float dense_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kDenseMaxGroup = 16;         // passages per work-group, at most
 constexpr int kDensePmWords = 4096;        // LDS words of per-(query, passage, token) maxima per work-group
-constexpr int kDenseHeadBytes = 1024;      // s_off (17 x 8) | s_rowp at 256 (<= 128 x 4) | s_own at 768 (16 x 4)
 
-__host__ __device__ inline int dense_row_stride(int dim) { return dim + (68 - dim % 64) % 64; }   // = 4 mod 64
+// The dynamic LDS of one launch, in bytes from its start: the head (s_off at 0, 17 x 8; s_own and s_rowp where the format puts
+// them), the maxima, the step's rows at `stride` bytes each, the step's row scales (scaled formats).  The kernel carves its
+// LDS by it and the host asks for `total`.
+struct DenseLayout {
+    int stride, step_rows, pm_words;
+    size_t pm, rows, scales, total;
+};
+template <typename F>
+__host__ __device__ inline DenseLayout dense_layout(int dim, int T, int QB, int G, int nw, bool owned) {
+    DenseLayout l;
+    l.stride = F::row_stride(dim);
+    l.step_rows = 16 * F::kRowTiles * nw;
+    l.pm_words = (owned ? 1 : QB) * G * (T | 1);
+    l.pm = F::kHeadBytes;
+    l.rows = l.pm + ((size_t)l.pm_words * 4 + 15) / 16 * 16;
+    l.scales = l.rows + (size_t)l.step_rows * l.stride;     // a multiple of 16: the stride is
+    l.total = l.scales + (F::kScaled ? (size_t)4 * l.step_rows : 0);
+    return l;
+}
 
 // offsets[j] = min(n_D, sum of max(0, min(doclens[i], n_D)) for i < j), j = 0..N.  One work-group; 4096 doclens per round.
 static __global__ __launch_bounds__(1024) void dense_offsets_kernel(const int64_t* __restrict__ doclens, int64_t N, int64_t n_D,
@@ -124,68 +152,153 @@ __device__ __forceinline__ void dense_step_passages(const int64_t* __restrict__ 
     }
 }
 
-// one ordered fp32 sum per (query, passage): acc = 0; acc = acc + max_t, t ascending (ranking.jl:83)
-__device__ __forceinline__ void dense_sum_maxima(const uint32_t* __restrict__ s_pm, int nq, int np, int G, int TP, int T, bool owned,
-                                                 int64_t p0, int q0, int64_t N, float* __restrict__ scores) {
+// One ordered fp32 sum per (query, passage): acc = 0; acc = acc + max_t, t ascending (ranking.jl:83).  A scaled format:
+// acc = acc + qs[t] * max_t, and -Inf where the pair received no row -- an empty (clamped) passage, or an owner outside the
+// batch, whose query scales are not read -- before any multiplication: qs[t] == 0 cannot turn it into a NaN.
+template <typename F>
+__device__ __forceinline__ void dense_sum_maxima(const uint32_t* __restrict__ s_pm, const int64_t* __restrict__ s_off,
+                                                 const int* __restrict__ s_own, const float* __restrict__ qscale, int nq, int np,
+                                                 int G, int TP, int T, int B, bool owned, int64_t p0, int q0, int64_t N,
+                                                 float* __restrict__ scores) {
     for (int i = threadIdx.x; i < nq * np; i += blockDim.x) {
         const int ql = i / np, p = i - ql * np;
         const uint32_t* pm = s_pm + (ql * G + p) * TP;
         float acc = 0.f;
-        for (int t = 0; t < T; ++t) acc = acc + f32_from_order_key(pm[t]);
+        if constexpr (F::kScaled) {
+            const int q = owned ? s_own[p] : q0 + ql;
+            if (s_off[p + 1] > s_off[p] && q >= 0 && q < B) {
+                const float* qs = qscale + (size_t)q * T;
+                for (int t = 0; t < T; ++t) acc = acc + qs[t] * f32_from_order_key(pm[t]);
+            } else {
+                acc = kNegInf;
+            }
+        } else {
+            for (int t = 0; t < T; ++t) acc = acc + f32_from_order_key(pm[t]);
+        }
         scores[owned ? p0 + p : (int64_t)(q0 + ql) * N + p0 + p] = acc;
     }
 }
 
-// KS = dim / 4 when the A and B operands live in registers (dim 128: KS 32), 0 = any dim, k walked at run time.
-// grid (ceil(N / G), owned ? 1 : ceil(B / QB)); block 64 * nw, nw waves of 16 rows each;
-// dynamic LDS = kDenseHeadBytes + 4 * (owned ? 1 : QB) * G * (T | 1) rounded up to 16 + 4 * 16 nw * dense_row_stride(dim).
-template <int KS>
-static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const float* __restrict__ Q, int dim, int T, int B,
-                                                                  const float* __restrict__ D, const int64_t* __restrict__ off,
+// One token tile against a wave's RT row tiles, those that hold a row of the run (bit j of `on`, wave-uniform).  KB > 0: KB
+// K-blocks of both operands from registers (a, b), tile after tile: its MFMA chain, its epilogue, its maxima.  KB = 0: K walked
+// at run time for all row tiles at once, A read from the LDS rows at arow, B once per K-block from the token at qtok (both
+// already at this lane's fragment), then the epilogues and maxima.
+template <typename F, int KB>
+__device__ __forceinline__ void dense_tiles(const typename F::Frag (*a)[KB > 0 ? KB : 1], const typename F::Frag* b,
+                                            const unsigned char* arow, int stride, const unsigned char* qtok, int dim, const float4* ds,
+                                            int on, const int* __restrict__ rowp, int pa, int pb, bool tok_ok,
+                                            uint32_t* __restrict__ pm, int TP, int t, int g) {
+    typedef typename F::Frag Frag;
+    constexpr int RT = F::kRowTiles, FB = (int)sizeof(Frag);
+    if constexpr (KB > 0) {
+#pragma unroll
+        for (int j = 0; j < RT; ++j) {
+            if (!(on >> j & 1)) continue;
+            typename F::Acc acc = {};
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) acc = F::mfma(a[j][kb], b[kb], acc);
+            dense_tile_max(F::epilogue(acc, ds[j]), rowp + 16 * j, pa, pb, tok_ok, pm, TP, t, g);
+        }
+    } else {
+        constexpr bool tail = 4 * FB > 16;                  // a K-block is wider than the 16-byte column dim is a multiple of
+        const Frag zero = {};
+        const int row_bytes = dim * F::kElem, nkb = (row_bytes + 4 * FB - 1) / (4 * FB);
+        typename F::Acc acc[RT];
+#pragma unroll
+        for (int j = 0; j < RT; ++j) acc[j] = typename F::Acc{};
+        for (int kb = 0; kb < nkb; ++kb) {
+            const bool k_ok = !tail || (4 * kb + g) * FB < row_bytes;    // past the row: zeros, nothing read
+            const Frag bk = k_ok ? *reinterpret_cast<const Frag*>(qtok + 4 * FB * kb) : zero;
+#pragma unroll
+            for (int j = 0; j < RT; ++j)
+                if (on >> j & 1)
+                    acc[j] = F::mfma(k_ok ? *reinterpret_cast<const Frag*>(arow + 16 * j * stride + 4 * FB * kb) : zero, bk, acc[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < RT; ++j)
+            if (on >> j & 1) dense_tile_max(F::epilogue(acc[j], ds[j]), rowp + 16 * j, pa, pb, tok_ok, pm, TP, t, g);
+    }
+}
+
+// F = the format (dense_formats.hpp).  KB = dim / F::kK K-blocks of both operands in registers (dim 128); 0 = any served dim.
+// Q (dim, T, B) and D (dim, n_D) hold F's elements, D 16-byte aligned and Q aligned to a fragment; qscale (T, B) and dscale
+// [n_D] fp32, read by a scaled format only.
+// grid (ceil(N / G), owned ? 1 : ceil(B / QB)); block 64 * nw; dynamic LDS = dense_layout<F>(dim, T, QB, G, nw, owned).total.
+template <typename F, int KB>
+static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const void* __restrict__ Qv, const float* __restrict__ qscale, int dim,
+                                                                  int T, int B, const void* __restrict__ Dv,
+                                                                  const float* __restrict__ dscale, const int64_t* __restrict__ off,
                                                                   int64_t N, const int32_t* __restrict__ owner, int G, int QB,
                                                                   float* __restrict__ scores) {
     extern __shared__ __align__(16) unsigned char dense_smem[];
-    const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
-    const int CH = (nthr >> 6) * 16;                       // rows per step of the work-group
-    const int stride = dense_row_stride(dim), TP = T | 1, ks = dim >> 2, dim4 = dim >> 2;
+    typedef typename F::Frag Frag;
+    typedef uint32_t col16 __attribute__((ext_vector_type(4)));                  // one 16-byte column of a row
+    constexpr int RT = F::kRowTiles, WR = 16 * RT, KR = KB > 0 ? KB : 1, FB = (int)sizeof(Frag);
+    const unsigned char* Q = static_cast<const unsigned char*>(Qv);
+    const unsigned char* D = static_cast<const unsigned char*>(Dv);
+    const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, r = lane & 15, g = lane >> 4;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar, so that what hangs on the wave's rows is wave-uniform to the compiler
     const bool owned = owner != nullptr;
+    const DenseLayout L = dense_layout<F>(dim, T, QB, G, nthr >> 6, owned);
+    const int CH = L.step_rows, stride = L.stride, TP = T | 1, cols = dim * F::kElem >> 4;   // rows per step; 16-byte columns per row
     const int64_t p0 = (int64_t)blockIdx.x * G;
     const int np = (int)(N - p0 < G ? N - p0 : G);
     const int q0 = owned ? 0 : (int)blockIdx.y * QB;
     const int nq = owned ? 1 : (B - q0 < QB ? B - q0 : QB);
     int64_t* s_off = reinterpret_cast<int64_t*>(dense_smem);
-    int* s_rowp = reinterpret_cast<int*>(dense_smem + 256);
-    int* s_own = reinterpret_cast<int*>(dense_smem + 768);
-    uint32_t* s_pm = reinterpret_cast<uint32_t*>(dense_smem + kDenseHeadBytes);
-    const int pm_words = (owned ? 1 : QB) * G * TP;
-    float* s_d = reinterpret_cast<float*>(dense_smem + kDenseHeadBytes + ((size_t)pm_words * 4 + 15) / 16 * 16);
+    int* s_own = reinterpret_cast<int*>(dense_smem + F::kOwnAt);
+    int* s_rowp = reinterpret_cast<int*>(dense_smem + F::kRowpAt);
+    uint32_t* s_pm = reinterpret_cast<uint32_t*>(dense_smem + L.pm);
+    unsigned char* s_d = dense_smem + L.rows;
+    float* s_ds = reinterpret_cast<float*>(dense_smem + L.scales);             // the step's row scales (scaled formats)
 
-    dense_group_begin(s_off, s_own, s_pm, off, owner, p0, np, pm_words);
+    dense_group_begin(s_off, s_own, s_pm, off, owner, p0, np, L.pm_words);
     __syncthreads();
     const int64_t lo = s_off[0], hi = s_off[np];
 
+    const Frag zero = {};
+    const bool resident = F::kResident && KB > 0 && T <= 32;
+    Frag bq[2][KR];                                        // the resident query's token tiles (resident only)
+    int q_res = -1;                                        // (wave-uniform) the query they hold
+    // lane (r, g)'s fragment of K-block 0 of token t of query q, t clamped to the last token; K-block kb lies 4 FB kb bytes on
+    auto q_tok = [&](int q, int t) { return Q + ((size_t)q * T + (t < T ? t : T - 1)) * dim * F::kElem + FB * g; };
+
     for (int64_t c = lo; c < hi; c += CH) {
         const int n_rows = (int)(hi - c < CH ? hi - c : CH);
-        // the step's rows, dense 16-byte loads (D + c * dim is 16-byte aligned: dim % 4 == 0), into padded LDS rows
-        const float4* src = reinterpret_cast<const float4*>(D + c * dim);
-        for (int i = tid; i < n_rows * dim4; i += nthr) {
-            const int row = i / dim4, c4 = i - row * dim4;
-            *reinterpret_cast<float4*>(s_d + row * stride + 4 * c4) = src[i];
+        // the step's rows, dense 16-byte loads (D + c * dim elements is 16-byte aligned), into padded LDS rows; their scales
+        const col16* src = reinterpret_cast<const col16*>(D + c * dim * F::kElem);
+        for (int i = tid; i < n_rows * cols; i += nthr) {
+            const int row = i / cols, col = i - row * cols;
+            *reinterpret_cast<col16*>(s_d + row * stride + 16 * col) = src[i];
         }
+        if constexpr (F::kScaled)
+            for (int i = tid; i < n_rows; i += nthr) s_ds[i] = dscale[c + i];
         dense_step_passages(s_off, s_rowp, c, n_rows, CH, np);
         __syncthreads();
 
-        const int rb = 16 * w;                              // this wave's rows of the step
+        const int rb = WR * w;                              // this wave's rows of the step: RT tiles of 16
         if (rb < n_rows) {
-            const int* rowp16 = s_rowp + rb;
-            const float* arow = s_d + (rb + r) * stride + g;
-            float a[KS > 0 ? KS : 1];
-            if (KS > 0) {
+            const int* rowp = s_rowp + rb;
+            const unsigned char* arow = s_d + (rb + r) * stride + FB * g;
+            Frag a[RT][KR];
+            float4 ds[RT];
+            uint32_t tf = 0, tl = 0;                        // (wave-uniform) byte j: tile j's first and last passage (< 16); none: first > last
 #pragma unroll
-                for (int s = 0; s < KS; ++s) a[s] = arow[4 * s];
+            for (int j = 0; j < RT; ++j) {
+                const bool live = rb + 16 * j < n_rows;
+                const int end = rb + 16 * j + 15 < n_rows ? rb + 16 * j + 15 : n_rows - 1;
+                tf |= (uint32_t)(live ? __builtin_amdgcn_readfirstlane(s_rowp[rb + 16 * j]) : 1) << (8 * j);
+                tl |= (uint32_t)(live ? __builtin_amdgcn_readfirstlane(s_rowp[end]) : 0) << (8 * j);
+                ds[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (F::kScaled)                   // the scales of the rows 4 g .. 4 g + 3 of the tile: this lane's accumulator entries
+                    if (live) ds[j] = *reinterpret_cast<const float4*>(s_ds + rb + 16 * j + 4 * g);
+                if (KB > 0) {
+#pragma unroll
+                    for (int kb = 0; kb < KB; ++kb) a[j][kb] = live ? *reinterpret_cast<const Frag*>(arow + 16 * j * stride + 4 * FB * kb) : zero;
+                }
             }
-            const int last = (rb + 16 < n_rows ? rb + 16 : n_rows) - 1;
-            const int pf = __builtin_amdgcn_readfirstlane(s_rowp[rb]), pl = __builtin_amdgcn_readfirstlane(s_rowp[last]);
+            const int last = (rb + WR < n_rows ? rb + WR : n_rows) - 1;
+            const int pf = (int)(tf & 255u), pl = __builtin_amdgcn_readfirstlane(s_rowp[last]);
             // runs of passages that one query scores: the whole span per query (all pairs), or the stretches of equal owner
             int pa = owned ? pf : 0, ql = 0;
             while (owned ? pa <= pl : ql < nq) {
@@ -202,30 +315,47 @@ static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const float* _
                 }
                 if (run_ok) {
                     uint32_t* pm = s_pm + (owned ? 0 : ql * G * TP);
-                    for (int t0 = 0; t0 < T; t0 += 16) {
-                        const int t = t0 + r;
-                        const bool tok_ok = t < T;
-                        const float* qrow = Q + ((size_t)q * T + (tok_ok ? t : T - 1)) * dim + g;   // B operand: lane (col r, k g)
-                        dense_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                        if (KS > 0) {
-                            float bq[KS > 0 ? KS : 1];
+                    int on = RT == 1;                      // (wave-uniform) bit j: tile j holds a row of the run; a wave's only tile always does
+                    if constexpr (RT > 1) {
 #pragma unroll
-                            for (int s = 0; s < KS; ++s) bq[s] = qrow[4 * s];
-#pragma unroll
-                            for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], bq[s], acc, 0, 0, 0);
-                        } else {
-                            for (int s = 0; s < ks; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * s], qrow[4 * s], acc, 0, 0, 0);
+                        for (int j = 0; j < RT; ++j) {
+                            const int f = (int)(tf >> (8 * j) & 255u), l = (int)(tl >> (8 * j) & 255u);
+                            on |= (int)(f <= pb && l >= pa && f <= l) << j;
                         }
-                        dense_tile_max(acc, rowp16, pa, pb, tok_ok, pm, TP, t, g);
+                    }
+                    if (resident) {
+                        if (q != q_res) {
+#pragma unroll
+                            for (int tt = 0; tt < 2; ++tt) {
+#pragma unroll
+                                for (int kb = 0; kb < KR; ++kb)
+                                    bq[tt][kb] = 16 * tt < T ? *reinterpret_cast<const Frag*>(q_tok(q, 16 * tt + r) + 4 * FB * kb) : zero;
+                            }
+                            q_res = q;
+                        }
+#pragma unroll
+                        for (int tt = 0; tt < 2; ++tt)
+                            if (16 * tt < T)
+                                dense_tiles<F, KB>(a, bq[tt], arow, stride, nullptr, dim, ds, on, rowp, pa, pb, 16 * tt + r < T, pm, TP, 16 * tt + r, g);
+                    } else {
+                        for (int t0 = 0; t0 < T; t0 += 16) {
+                            const unsigned char* qtok = q_tok(q, t0 + r);
+                            Frag bt[KR];
+                            if (KB > 0) {
+#pragma unroll
+                                for (int kb = 0; kb < KB; ++kb) bt[kb] = *reinterpret_cast<const Frag*>(qtok + 4 * FB * kb);
+                            }
+                            dense_tiles<F, KB>(a, bt, arow, stride, qtok, dim, ds, on, rowp, pa, pb, t0 + r < T, pm, TP, t0 + r, g);
+                        }
                     }
                 }
                 if (owned) pa = pb + 1; else ++ql;
             }
         }
-        __syncthreads();                                    // the step's rows and passages are read; the next step overwrites them
+        __syncthreads();                                    // the step's rows, scales and passages are read; the next step overwrites them
     }
 
-    dense_sum_maxima(s_pm, nq, np, G, TP, T, owned, p0, q0, N, scores);
+    dense_sum_maxima<F>(s_pm, s_off, s_own, qscale, nq, np, G, TP, T, B, owned, p0, q0, N, scores);
 }
 
 }  // namespace clb

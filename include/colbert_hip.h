@@ -849,7 +849,7 @@ int clb_maxsim_batch_device(int device, const float* d_Q, int64_t dim, int64_t T
                             void* d_work, int64_t work_bytes, void* hip_stream);
 int clb_maxsim_batch(int device, const float* Q, int64_t dim, int64_t T, int64_t B, const float* D, int64_t n_D,
                      const int64_t* doclens, int64_t N, const int32_t* owner, float* scores);
-/* The same call on embeddings stored in 16 bits (dense_half_kernels.hpp): d_D (dim, n_D) in d_type = CLB_F16 or CLB_BF16;
+/* The same call on embeddings stored in 16 bits (dense_formats.hpp): d_D (dim, n_D) in d_type = CLB_F16 or CLB_BF16;
  * d_Q (dim, T, B) in q_type = CLB_F32 (the encoder's output: rounded to nearest-even into d_type on the device first, in the
  * work buffer) or in d_type, used as it is.  Any other pair of types is CLB_EUNSUPPORTED.  Shapes, scores and owners as above.
  * Arithmetic: the products of the 16-bit operands are exact in fp32 and summed in fp32 by v_mfma_f32_16x16x32_f16 / _bf16, the
@@ -870,7 +870,7 @@ int clb_maxsim_batch_half_device(int device, const void* d_Q, int q_type, int64_
                                  void* d_work, int64_t work_bytes, void* hip_stream);
 int clb_maxsim_batch_half(int device, const void* Q, int q_type, int64_t dim, int64_t T, int64_t B, const void* D, int d_type,
                           int64_t n_D, const int64_t* doclens, int64_t N, const int32_t* owner, float* scores);
-/* The same call on embeddings stored as int8 with one fp32 scale each (dense_i8_kernels.hpp).  An int8 operand is a pair: the
+/* The same call on embeddings stored as int8 with one fp32 scale each (dense_formats.hpp).  An int8 operand is a pair: the
  * values, (dim, n) like every dense operand, and one finite scale >= 0 per embedding.
  * Quantisation (clb_quantize_rows*, one definition for host and device), per embedding x:
  *   amax = max_k |x_k|;  s = fl32(amax / 127) (IEEE division);  q_k = clamp(rint(fl32(x_k / s)), -127, 127), rint to nearest-even;

@@ -48,7 +48,8 @@ def case(oracle, dim, T, B, kind):
 
 
 SHAPES = [(128, 1, 1, "edges"), (128, 16, 3, "edges"), (128, 17, 3, "many"), (128, 32, 33, "edges"), (128, 32, 3, "many"),
-          (128, 33, 3, "edges"), (128, 128, 33, "edges"), (64, 32, 3, "many"), (8, 17, 1, "many"), (768, 16, 3, "edges")]
+          (128, 33, 3, "edges"), (128, 128, 33, "edges"), (64, 32, 3, "many"), (8, 17, 1, "many"), (768, 16, 3, "edges"),
+          (12, 17, 3, "edges")]
 
 
 @pytest.mark.parametrize("dim,T,B,kind", SHAPES)
