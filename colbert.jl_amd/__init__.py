@@ -8,6 +8,7 @@ from . import codec, storage, synthetic, tokenization  # noqa: F401
 from ._lib import (ArgumentError, BoundsError, ColBERTError, DimensionMismatch, DomainError, HipError,  # noqa: F401
                    Unsupported, build, declared_symbols, lib)
 from .codec import maxsim, maxsim_batch, maxsim_batch_device, quantize_rows, quantize_rows_device  # noqa: F401
+from .codec import dequantize_mx, quantize_mx, quantize_mx_device  # noqa: F401
 from .config import ColBERTConfig  # noqa: F401
 from .encoder import BertEncoder, encoder_plan  # noqa: F401
 from .indexer import Indexer, PrecomputedEncoder, index, train  # noqa: F401

@@ -251,6 +251,17 @@ def lib() -> C.CDLL:
             l.clb_maxsim_batch_half.argtypes = [ci, vp, ci, i64_, i64_, i64_, vp, ci, i64_, vp, i64_, vp, vp]
             l.clb_maxsim_batch_half_device.restype = ci
             l.clb_maxsim_batch_half_device.argtypes = [ci, vp, ci, i64_, i64_, i64_, vp, ci, i64_, vp, i64_, vp, vp, vp, i64_, vp]
+        if hasattr(l, "clb_maxsim_batch_mx"):                 # (likewise)
+            l.clb_quantize_mx.restype = ci
+            l.clb_quantize_mx.argtypes = [ci, vp, i64_, i64_, ci, vp, vp]
+            l.clb_quantize_mx_device.restype = ci
+            l.clb_quantize_mx_device.argtypes = [ci, vp, i64_, i64_, ci, vp, vp, vp]
+            l.clb_maxsim_batch_mx_work_bytes.restype = i64_
+            l.clb_maxsim_batch_mx_work_bytes.argtypes = [i64_, i64_, i64_, i64_]
+            l.clb_maxsim_batch_mx.restype = ci
+            l.clb_maxsim_batch_mx.argtypes = [ci, vp, ci, vp, i64_, i64_, i64_, vp, vp, ci, i64_, vp, i64_, vp, vp]
+            l.clb_maxsim_batch_mx_device.restype = ci
+            l.clb_maxsim_batch_mx_device.argtypes = [ci, vp, ci, vp, i64_, i64_, i64_, vp, vp, ci, i64_, vp, i64_, vp, vp, vp, i64_, vp]
         if hasattr(l, "clb_maxsim_batch_i8"):                 # (likewise)
             l.clb_quantize_rows.restype = ci
             l.clb_quantize_rows.argtypes = [ci, vp, i64_, i64_, vp, vp]

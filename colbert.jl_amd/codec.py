@@ -146,6 +146,102 @@ def _int8_pair(a, what):
     return v, np.ascontiguousarray(s.ravel(order="F"))
 
 
+MXFP8, MXFP4 = 4, 5                                            # CLB_MXFP8 / CLB_MXFP4
+_MX = {"mxfp8": (MXFP8, 3, -6, 7, 448.0, 8), "mxfp4": (MXFP4, 1, 0, 1, 6.0, 2)}    # code, mantissa bits, emin, bias, max, emax
+
+
+def _mx(fmt):
+    if fmt not in _MX:
+        raise ValueError("fmt must be 'mxfp8' or 'mxfp4'")
+    return _MX[fmt]
+
+
+def quantize_mx(X, fmt):
+    """OCP MX v1.0 quantisation, the host statement of dense_quantize_mx_kernel (include/colbert_hip.h), bit for bit: X (dim, ...)
+    float32, dim % 32 == 0 -> (values uint8 (dim, ...) for "mxfp8" / (dim / 2, ...) for "mxfp4", element 2 i in the low nibble of
+    byte i; scales uint8 (dim / 32, ...)).  Per block of 32: e = max(-127, ilogb(amax) - emax), scale byte e + 127 (127 for an
+    all-zero block), element = x 2^-e rounded to nearest-even in E4M3 / E2M1, saturated, sign kept.  A non-finite value is an
+    ArgumentError naming the embedding; a dim that is no multiple of 32 is Unsupported."""
+    from ._lib import ArgumentError, Unsupported
+    _, M, emin, bias, vmax, emax = _mx(fmt)
+    x = colmajor(X, np.float32)
+    dim = x.shape[0]
+    if dim % 32 or not 32 <= dim <= 1024:
+        raise Unsupported(f"quantize_mx serves dim % 32 == 0, 32 <= dim <= 1024 (dim = {dim})")
+    bad = ~np.isfinite(x).all(axis=0)
+    if bad.any():
+        raise ArgumentError(f"quantize_mx: embedding {int(np.flatnonzero(bad.ravel(order='F'))[0])} holds a non-finite value")
+    blocks = x.reshape((32, dim // 32) + x.shape[1:], order="F").astype(np.float64)       # [element, block, ...]: exact in float64
+    amax = np.abs(blocks).max(axis=0)
+    E = (amax.astype(np.float32).view(np.uint32) >> np.uint32(23)).astype(np.int64)        # biased fp32 exponent: ilogb + 127, 0 below 2^-126
+    byte = np.where(amax == 0, 127, np.maximum(E - emax, 0))
+    y = np.ldexp(blocks, (127 - byte)[None])                                            # x 2^-e
+    a = np.minimum(np.abs(y), vmax)
+    eq = np.maximum(np.frexp(a)[1] - 1, emin) - M                                          # the grid's step at a is 2^eq (a == 0: any step, rint(0) = 0)
+    r = np.ldexp(np.rint(np.ldexp(a, -eq)), eq)                                            # nearest-even, one rounding
+    er = np.where(r == 0, emin - 1, np.frexp(r)[1] - 1)
+    mant = np.where(er < emin, np.ldexp(r, M - emin), ((er + bias) << M) + (np.ldexp(r, M - er) - (1 << M))).astype(np.int64)
+    code = (mant | (np.signbit(y).astype(np.int64) << (7 if M == 3 else 3))).astype(np.uint8).reshape(x.shape, order="F")
+    if M == 1:
+        code = code[0::2] | (code[1::2] << np.uint8(4))
+    return np.asfortranarray(code), np.asfortranarray(byte.astype(np.uint8))
+
+
+def dequantize_mx(values, scales, fmt):
+    """The float32 embeddings an MX pair stands for: element code times 2^(scale byte - 127) per block of 32 (exact); NaN where
+    a code (E4M3 0x7F / 0xFF) or a scale byte (0xFF) is one."""
+    _, M, emin, bias, _, _ = _mx(fmt)
+    v, s = colmajor(values, np.uint8), colmajor(scales, np.uint8)
+    if M == 1:
+        both = np.empty((2 * v.shape[0],) + v.shape[1:], np.uint8, order="F")
+        both[0::2], both[1::2] = v & np.uint8(15), v >> np.uint8(4)
+        v = both
+    if v.shape[0] != 32 * s.shape[0] or v.shape[1:] != s.shape[1:]:
+        raise ValueError("one scale byte per block of 32 elements")
+    c = v.astype(np.int64)
+    field, mant, neg = (c >> M) & (15 if M == 3 else 3), c & ((1 << M) - 1), c >> (7 if M == 3 else 3) & 1
+    mag = np.where(field == 0, np.ldexp(mant.astype(np.float64), emin - M), np.ldexp(((1 << M) + mant).astype(np.float64), field - bias - M))
+    if M == 3:
+        mag = np.where((c & 0x7F) == 0x7F, np.nan, mag)
+    x = np.where(neg == 1, -mag, mag) * np.repeat(np.where(s == 255, np.nan, np.ldexp(1.0, s.astype(np.int64) - 127)), 32, axis=0)
+    return np.asfortranarray(x.astype(np.float32))
+
+
+def _mx_pair(a, what, fmt):
+    """(values, scale bytes) of an operand given as floats (quantised here) or as a (values uint8, scales uint8) pair"""
+    if isinstance(a, tuple):
+        v, s = colmajor(a[0], np.uint8), colmajor(a[1], np.uint8)
+        if getattr(a[0], "dtype", None) != np.uint8 or getattr(a[1], "dtype", None) != np.uint8:
+            raise ValueError(f"{what}: an MX operand is a (values uint8, scales uint8) pair")
+        return v, s
+    if getattr(a, "dtype", None) not in (np.float32, np.float64, np.float16):
+        raise ValueError(f"{what}: float values (quantised here) or a (values uint8, scales uint8) pair")
+    return quantize_mx(a, fmt)
+
+
+def quantize_mx_device(d_X, fmt, out=None, stream=None):
+    """`quantize_mx` on the device (clb_quantize_mx_device): d_X float32 (..., dim), contiguous, dim % 32 == 0 -> (values uint8
+    (..., dim) or (..., dim / 2), scales uint8 (..., dim / 32)).  `out`: that pair, preallocated.  Stream-ordered, not waited for; it
+    cannot report a non-finite value (defined, meaningless numbers)."""
+    import torch
+    code = _mx(fmt)[0]
+    x = _dev_rows(d_X, torch.float32)
+    if x.dim() < 2:
+        raise ValueError("d_X must be (..., dim)")
+    dim, lead = int(x.shape[-1]), tuple(x.shape[:-1])
+    vb = dim // 2 if code == MXFP4 else dim
+    v, s = out if out is not None else (torch.empty(lead + (vb,), dtype=torch.uint8, device=x.device),
+                                        torch.empty(lead + (dim // 32,), dtype=torch.uint8, device=x.device))
+    _dev_rows(v, torch.uint8); _dev_rows(s, torch.uint8)
+    n = x.numel() // max(dim, 1)
+    if v.numel() != n * vb or s.numel() != n * (dim // 32):
+        raise ValueError("out: the values' bytes and one scale byte per block of 32")
+    st = torch.cuda.current_stream(x.device).cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+    check(lib().clb_quantize_mx_device(x.device.index, C.c_void_p(x.data_ptr()), i64(dim), i64(n), code, C.c_void_p(v.data_ptr()),
+                                       C.c_void_p(s.data_ptr()), C.c_void_p(st)))
+    return v, s
+
+
 def quantize_rows_device(d_X, out=None, stream=None):
     """`quantize_rows` on the device (clb_quantize_rows_device): d_X float32 (..., dim), contiguous, dim % 16 == 0 -> (int8 of d_X's
     shape, float32 scales of its leading shape).  `out`: that pair, preallocated.  Stream-ordered, not waited for; it cannot
@@ -175,7 +271,25 @@ def maxsim_batch(Q, D, doclens, owner=None, device: int = 0, dtype=None):
     DESIGN 4.2a of the float64 value on the rounded operands -- not the oracle's bits.
     dtype="int8" (implied by a Q or D given as a `(values int8, scales)` pair, which is used as it is): float operands are
     quantised per embedding by `quantize_rows` and scored by the integer-MFMA kernel (clb_maxsim_batch_i8): exact integer dots,
-    each score bit-identical to the restatement in include/colbert_hip.h; its distance from the fp32 score is the format's."""
+    each score bit-identical to the restatement in include/colbert_hip.h; its distance from the fp32 score is the format's.
+    dtype="mxfp8" / "mxfp4": MX block-scaled embeddings scored by the scaled-MFMA kernel (clb_maxsim_batch_mx).  Float operands
+    are quantised by `quantize_mx` (Q always as "mxfp8", D as `dtype`); a `(values uint8, scales uint8)` pair is used as it is."""
+    if dtype in _MX:
+        (q, qs), (d, ds) = _mx_pair(Q, "Q", "mxfp8"), _mx_pair(D, "D", dtype)
+        if q.ndim != 3 or qs.shape != (q.shape[0] // 32,) + q.shape[1:]:
+            raise ValueError("Q must be (dim, T, B) with scales (dim / 32, T, B)")
+        dim, T, B = q.shape
+        n = d.shape[1] if d.ndim == 2 else 0
+        if d.ndim != 2 or d.shape[0] * (2 if dtype == "mxfp4" else 1) != dim or ds.shape != (dim // 32, n):
+            raise ValueError("D must hold (dim, n) elements with scales (dim / 32, n)")
+        dl = np.ascontiguousarray(doclens, dtype=np.int64)
+        ow = None if owner is None else np.ascontiguousarray(owner, dtype=np.int32)
+        if ow is not None and ow.size != dl.size:
+            raise ValueError("owner must hold one query number per passage")
+        scores = np.zeros(dl.size if ow is not None else (dl.size, B), dtype=np.float32, order="F")
+        check(lib().clb_maxsim_batch_mx(device, fptr(q), MXFP8, fptr(qs), i64(dim), i64(T), i64(B), fptr(d), fptr(ds), _MX[dtype][0], i64(n),
+                                        fptr(dl), i64(dl.size), fptr(ow) if ow is not None else None, fptr(scores)))
+        return scores
     int8 = dtype == "int8" or isinstance(Q, tuple) or isinstance(D, tuple) or (dtype is None and getattr(D, "dtype", None) == np.int8)
     if int8:
         if dtype not in (None, "int8"):
@@ -185,7 +299,7 @@ def maxsim_batch(Q, D, doclens, owner=None, device: int = 0, dtype=None):
         if dtype is None and getattr(D, "dtype", None) == np.float16:
             dtype = "float16"
         if dtype not in (None, "float16", "bfloat16"):
-            raise ValueError("dtype must be None, 'float16', 'bfloat16' or 'int8'")
+            raise ValueError("dtype must be None, 'float16', 'bfloat16', 'int8', 'mxfp8' or 'mxfp4'")
         q, d = (colmajor(Q, np.float32), colmajor(D, np.float32)) if dtype is None else (_host_16bit(Q, dtype), _host_16bit(D, dtype))
     if q.ndim != 3:
         raise ValueError("Q must be (dim, T, B)")
@@ -218,8 +332,13 @@ def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, st
     d_D's dtype, `work` clb_maxsim_batch_half_work_bytes long.
     An int8 d_D with `d_scale` (float32, one per embedding: what `quantize_rows_device` returns) takes the integer kernel
     (clb_maxsim_batch_i8_device): d_Q float32 (quantised on the device) or int8 with `q_scale` (B, T); `work`
-    clb_maxsim_batch_i8_work_bytes long.  Any other mix of int8 operands and scales is a ValueError."""
+    clb_maxsim_batch_i8_work_bytes long.  Any other mix of int8 operands and scales is a ValueError.
+    A uint8 d_D with a uint8 `d_scale` (n, dim / 32) is an MX pair (what `quantize_mx_device` returns) and takes the scaled-MFMA
+    kernel (clb_maxsim_batch_mx_device): d_D (n, dim) is MXFP8, (n, dim / 2) MXFP4; d_Q float32 (quantised to MXFP8 on the device) or
+    uint8 with a uint8 `q_scale` (B, T, dim / 32); `work` clb_maxsim_batch_mx_work_bytes long.  Any other mix is a ValueError."""
     import torch
+    if torch.uint8 in (d_D.dtype, d_Q.dtype) or torch.uint8 in (getattr(d_scale, "dtype", None), getattr(q_scale, "dtype", None)):
+        return _maxsim_batch_mx_device(d_Q, d_D, d_doclens, owner, out, work, stream, d_scale, q_scale)
     int8 = torch.int8 in (d_D.dtype, d_Q.dtype) or d_scale is not None or q_scale is not None
     half = None if int8 else {torch.float16: F16, torch.bfloat16: BF16}.get(d_D.dtype)
     if int8:
@@ -264,6 +383,40 @@ def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, st
     st = torch.cuda.current_stream(q.device).cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
     check(entry(q.device.index, *operands, i64(d.shape[0]), ptr(dl), i64(N), ptr(ow), ptr(o), ptr(wk), i64(wk.numel() * wk.element_size()),
                 C.c_void_p(st)))
+    return out
+
+
+def _maxsim_batch_mx_device(d_Q, d_D, d_doclens, owner, out, work, stream, d_scale, q_scale):
+    """maxsim_batch_device on an MX pair"""
+    import torch
+    if d_D.dtype != torch.uint8 or getattr(d_scale, "dtype", None) != torch.uint8:
+        raise ValueError("MX scoring takes a uint8 d_D with a uint8 d_scale, one byte per block of 32")
+    if d_Q.dtype not in (torch.uint8, torch.float32) or (d_Q.dtype == torch.uint8) != (q_scale is not None) or \
+            (q_scale is not None and q_scale.dtype != torch.uint8):
+        raise ValueError("d_Q must be float32 (quantised on the device) or uint8 with a uint8 q_scale")
+    q, d, ds, dl = _dev_rows(d_Q), _dev_rows(d_D), _dev_rows(d_scale), _dev_rows(d_doclens, torch.int64)
+    qs = None if q_scale is None else _dev_rows(q_scale)
+    if q.dim() != 3 or d.dim() != 2 or d.shape[1] not in (q.shape[2], q.shape[2] // 2):
+        raise ValueError("d_Q must be (B, T, dim) and d_D (n, dim) for MXFP8 or (n, dim / 2) for MXFP4")
+    B, T, dim = (int(x) for x in q.shape)
+    N, n = int(dl.numel()), int(d.shape[0])
+    if ds.numel() != n * (dim // 32) or (qs is not None and qs.numel() != B * T * (dim // 32)):
+        raise ValueError("d_scale / q_scale: one byte per block of 32 elements")
+    ow = None if owner is None else _dev_rows(owner, torch.int32)
+    if ow is not None and ow.numel() != N:
+        raise ValueError("owner must hold one query number per passage")
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())      # noqa: E731
+    if out is None:
+        out = torch.empty(N if ow is not None else (B, N), dtype=torch.float32, device=q.device)
+    if work is None:
+        work = torch.empty(int(lib().clb_maxsim_batch_mx_work_bytes(i64(N), i64(B), i64(T), i64(dim))), dtype=torch.uint8, device=q.device)
+    o = _dev_rows(out, torch.float32); wk = _dev_rows(work)
+    if o.numel() != (N if ow is not None else N * B):
+        raise ValueError("out: one score per passage (owned) or per (query, passage)")
+    st = torch.cuda.current_stream(q.device).cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+    check(lib().clb_maxsim_batch_mx_device(q.device.index, ptr(q), F32 if q.dtype == torch.float32 else MXFP8, ptr(qs), i64(dim), i64(T), i64(B),
+                                           ptr(d), ptr(ds), MXFP8 if d.shape[1] == dim else MXFP4, i64(n), ptr(dl), i64(N), ptr(ow), ptr(o),
+                                           ptr(wk), i64(wk.numel() * wk.element_size()), C.c_void_p(st)))
     return out
 
 

@@ -1,7 +1,8 @@
 // dense.hip -- MaxSim of un-indexed passages for a query batch (include/colbert_hip.h: clb_maxsim_batch*): the scorer between
-// the encoder's device outputs, with no index and no handle.  One kernel frame (dense_kernels.hpp) for four embedding formats
+// the encoder's device outputs, with no index and no handle.  One kernel frame (dense_kernels.hpp) for six embedding formats
 // (dense_formats.hpp): fp32 (clb_maxsim_batch*, the oracle's bits), fp16 / bf16 (clb_maxsim_batch_half*), int8 with one scale
-// each (clb_maxsim_batch_i8*, clb_quantize_rows*); one device path and one host-array path behind the six entry points.
+// each (clb_maxsim_batch_i8*, clb_quantize_rows*), MXFP8 / MXFP4 with one scale byte per block of 32 (clb_maxsim_batch_mx*,
+// clb_quantize_mx*); one device path and one host-array path behind the eight entry points.
 #include <algorithm>
 #include <cmath>
 
@@ -13,33 +14,38 @@ namespace {
 
 inline int64_t align256(int64_t n) { return (n + 255) / 256 * 256; }
 
-// What the host needs of a format F: its sizes, its LDS layout, its kernels.  Indexed by D's type, CLB_F32 .. CLB_I8.
-typedef void (*DenseKernel)(const void*, const float*, int, int, int, const void*, const float*, const int64_t*, int64_t, const int32_t*,
+// What the host needs of a format F: its sizes, its LDS layout, its kernels.  Indexed by D's type, CLB_F32 .. CLB_MXFP4.
+typedef void (*DenseKernel)(const void*, const void*, int, int, int, const void*, const void*, const int64_t*, int64_t, const int32_t*,
                             int, int, float*);
 struct DenseFormat {
-    int elem, dim_multiple;                             // bytes per element; dim is a multiple of one 16-byte column's elements
-    bool scaled;
+    int dim_multiple;                                   // dim is a multiple of one fragment's elements
+    bool scaled, has_scales;                            // one fp32 scale per embedding (applied around the product); any scales at all
+    int (*row_bytes)(int dim);                          // one embedding of D, of Q in D's family, and its scales
+    int (*q_bytes)(int dim);
+    int (*scale_bytes)(int dim);
     DenseLayout (*layout)(int dim, int T, int QB, int G, int nw, bool owned);
     DenseKernel k128, kany;                             // both operands in registers at dim 128; any served dim
 };
 template <typename F>
 DenseFormat dense_format() {
-    return {F::kElem, 16 / F::kElem, F::kScaled, dense_layout<F>, dense_maxsim_kernel<F, 128 / F::kK>, dense_maxsim_kernel<F, 0>};
+    return {F::kDimMultiple, F::kScaled, F::kHasScales, F::row_bytes, F::q_bytes, F::scale_bytes, dense_layout<F>,
+            dense_maxsim_kernel<F, 128 / F::kK>, dense_maxsim_kernel<F, 0>};
 }
 const DenseFormat& format_of(int d_type) {
-    static const DenseFormat f[4] = {dense_format<DenseF32>(), dense_format<DenseF16>(), dense_format<DenseBF16>(), dense_format<DenseI8>()};
+    static const DenseFormat f[6] = {dense_format<DenseF32>(), dense_format<DenseF16>(), dense_format<DenseBF16>(), dense_format<DenseI8>(),
+                                     dense_format<DenseMXFP8>(), dense_format<DenseMXFP4>()};
     return f[d_type];
 }
 
 // One call, as every entry point states it.  Q and D are device arrays in run_dense_device, host arrays in run_dense_host.
 struct DenseCall {
-    const char* who;                                    // the name its messages carry: maxsim_batch, maxsim_batch_half, maxsim_batch_i8
-    int family;                                         // the entry point's: CLB_F32, CLB_F16 (D in either 16-bit type) or CLB_I8
+    const char* who;                                    // the name its messages carry: maxsim_batch, maxsim_batch_half, maxsim_batch_i8, _mx
+    int family;                                         // the entry point's: CLB_F32, CLB_F16 (D in either 16-bit type), CLB_I8, CLB_MXFP8 (either MX)
     int q_type, d_type;
     const void* Q;
-    const float* qscale;
+    const void* qscale;
     const void* D;
-    const float* dscale;
+    const void* dscale;
     int64_t dim, T, B, n_D, N;
     const int64_t* doclens;
     const int32_t* owner;
@@ -61,6 +67,8 @@ int check_shape(const DenseCall& c) {
         return fail(CLB_EUNSUPPORTED, "%s serves Q in fp32 or int8 (q_type = %d)", c.who, c.q_type);
     if (c.family == CLB_F16 && ((c.d_type != CLB_F16 && c.d_type != CLB_BF16) || (c.q_type != CLB_F32 && c.q_type != c.d_type)))
         return fail(CLB_EUNSUPPORTED, "%s serves D in fp16 or bf16 and Q in fp32 or D's type (q_type = %d, d_type = %d)", c.who, c.q_type, c.d_type);
+    if (c.family == CLB_MXFP8 && ((c.d_type != CLB_MXFP8 && c.d_type != CLB_MXFP4) || (c.q_type != CLB_F32 && c.q_type != CLB_MXFP8)))
+        return fail(CLB_EUNSUPPORTED, "%s serves D in CLB_MXFP8 or CLB_MXFP4 and Q in fp32 or CLB_MXFP8 (q_type = %d, format = %d)", c.who, c.q_type, c.d_type);
     CLB_TRY(check_dim(c.who, format_of(c.d_type).dim_multiple, c.dim, advice));
     if (c.T < 1 || c.T > 128) return fail(CLB_EUNSUPPORTED, "%s serves 1 <= T <= 128 (T = %lld)%s", c.who, (long long)c.T, advice);
     if (c.B < 1 || c.N < 0 || c.n_D < 0) return fail(CLB_EARGUMENT, "%s: B >= 1, N >= 0 and n_D >= 0 are required", c.who);
@@ -94,8 +102,9 @@ struct DenseWork {
         const DenseFormat& f = format_of(d_type);
         const int64_t bt = std::max<int64_t>(B, 0) * std::max<int64_t>(T, 0);
         off_bytes = align256((int64_t)sizeof(int64_t) * (std::max<int64_t>(N, 0) + 1));
-        q_bytes = d_type == CLB_F32 ? 0 : align256(f.elem * bt * std::max<int64_t>(dim, 0));
-        s_bytes = f.scaled ? align256(4 * bt) : 0;
+        const int d = (int)std::min<int64_t>(std::max<int64_t>(dim, 0), 1 << 24);   // the formats size by int; a dim past 2^24 is unserved whatever this returns
+        q_bytes = d_type == CLB_F32 ? 0 : align256(f.q_bytes(d) * bt);
+        s_bytes = f.has_scales ? align256(f.scale_bytes(d) * bt) : 0;
     }
     int64_t total() const { return off_bytes + q_bytes + s_bytes; }
 };
@@ -125,8 +134,14 @@ int check_scales(const char* who, const char* what, const float* s, int64_t n) {
     return CLB_OK;
 }
 
-void launch_quantize(const float* d_X, int dim, int64_t n, int8_t* d_X8, float* d_scale, hipStream_t st) {
-    hipLaunchKernelGGL(dense_quantize_kernel, dim3((unsigned)std::min<int64_t>((n + 3) / 4, 8192)), dim3(256), 0, st, d_X, dim, n, d_X8, d_scale);
+// X into the values and scales of `format`: CLB_I8 (one fp32 scale per embedding), CLB_MXFP8 / CLB_MXFP4 (one byte per block)
+void launch_quantize(int format, const float* d_X, int dim, int64_t n, void* d_V, void* d_scale, hipStream_t st) {
+    const dim3 grid((unsigned)std::min<int64_t>((n + 3) / 4, 8192)), block(256);
+    if (format == CLB_I8)
+        hipLaunchKernelGGL(dense_quantize_kernel, grid, block, 0, st, d_X, dim, n, (int8_t*)d_V, (float*)d_scale);
+    else
+        hipLaunchKernelGGL(format == CLB_MXFP4 ? dense_quantize_mx_kernel<true> : dense_quantize_mx_kernel<false>, grid, block, 0, st, d_X, dim, n,
+                           (unsigned char*)d_V, (unsigned char*)d_scale);
 }
 
 
@@ -136,13 +151,15 @@ int run_dense_device(int device, const DenseCall& c) {
     const DenseFormat& f = format_of(c.d_type);
     const bool q_f32 = c.q_type == CLB_F32, fp32 = c.d_type == CLB_F32;
     if (c.N == 0) return CLB_OK;
-    if (!c.Q || !c.doclens || !c.scores || !c.work || ((!c.D || (f.scaled && !c.dscale)) && c.n_D > 0) || (f.scaled && !q_f32 && !c.qscale))
+    if (!c.Q || !c.doclens || !c.scores || !c.work || ((!c.D || (f.has_scales && !c.dscale)) && c.n_D > 0) || (f.has_scales && !q_f32 && !c.qscale))
         return fail(CLB_EARGUMENT, "%s: null argument", c.who);
     if (fp32) {                                             // fp32 queries are read in dwords, the work buffer holds offsets only
         if ((uintptr_t)c.D % 16 || (uintptr_t)c.work % 8)
             return fail(CLB_EARGUMENT, "%s: D must be 16-byte aligned and the work buffer 8-byte aligned", c.who);
     } else if ((uintptr_t)c.D % 16 || (uintptr_t)c.Q % 16 || (uintptr_t)c.work % 16) {
         return fail(CLB_EARGUMENT, "%s: Q, %s and the work buffer must be 16-byte aligned", c.who, f.scaled ? "D8" : "D");
+    } else if (f.has_scales && !f.scaled && f.scale_bytes((int)c.dim) % 4 == 0 && (uintptr_t)c.dscale % 4) {
+        return fail(CLB_EARGUMENT, "%s: the passages' scale bytes must be 4-byte aligned when dim %% 128 == 0", c.who);
     }
     const DenseWork wk(c.d_type, c.N, c.B, c.T, c.dim);
     if (c.work_bytes < wk.total())
@@ -154,14 +171,15 @@ int run_dense_device(int device, const DenseCall& c) {
         return fail(CLB_EUNSUPPORTED, "%s: B = %lld, N = %lld exceed one launch", c.who, (long long)c.B, (long long)c.N);
     CLB_TRY(use_device(device));
     int64_t* d_off = reinterpret_cast<int64_t*>(c.work);
-    unsigned char* d_qf = reinterpret_cast<unsigned char*>(c.work) + wk.off_bytes;     // Q in D's format, then its scales
-    float* d_qs = reinterpret_cast<float*>(d_qf + wk.q_bytes);
+    unsigned char* d_qf = reinterpret_cast<unsigned char*>(c.work) + wk.off_bytes;     // Q in D's family's query format, then its scales
+    unsigned char* d_qs = d_qf + wk.q_bytes;
     const bool convert = q_f32 && !fp32;
-    // The order of the two launches ahead of the kernel is each format's own, as captured graphs hold it: a scaled format
-    // quantises Q before the offsets, a 16-bit format rounds it after them.
-    if (convert && f.scaled) launch_quantize(reinterpret_cast<const float*>(c.Q), dim, c.B * c.T, reinterpret_cast<int8_t*>(d_qf), d_qs, c.st);
+    // The order of the two launches ahead of the kernel is each format's own, as captured graphs hold it: a format with scales
+    // quantises Q before the offsets (an MX family's query is MXFP8 whatever D holds), a 16-bit format rounds it after them.
+    if (convert && f.has_scales)
+        launch_quantize(f.scaled ? CLB_I8 : CLB_MXFP8, reinterpret_cast<const float*>(c.Q), dim, c.B * c.T, d_qf, d_qs, c.st);
     hipLaunchKernelGGL(dense_offsets_kernel, dim3(1), dim3(1024), 0, c.st, c.doclens, c.N, c.n_D, d_off);
-    if (convert && !f.scaled) {                             // Q~ = Q rounded to nearest-even
+    if (convert && !f.has_scales) {                         // Q~ = Q rounded to nearest-even
         const int64_t n8 = c.B * c.T * c.dim / 8;
         hipLaunchKernelGGL(c.d_type == CLB_F16 ? dense_round_kernel<DenseF16> : dense_round_kernel<DenseBF16>,
                            dim3((unsigned)std::min<int64_t>((n8 + 255) / 256, 4096)), dim3(256), 0, c.st, (const float4*)c.Q, n8, (dense_u32x4*)d_qf);
@@ -169,7 +187,7 @@ int run_dense_device(int device, const DenseCall& c) {
     const DenseKernel kern = dim == 128 ? f.k128 : f.kany;
     if (p.lds > 64 * 1024) allow_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024);
     hipLaunchKernelGGL(kern, dim3(p.gx, p.gy), dim3(64 * p.nw), p.lds, c.st, convert ? (const void*)d_qf : c.Q,
-                       convert && f.scaled ? (const float*)d_qs : c.qscale, dim, T, (int)c.B, c.D, c.dscale, (const int64_t*)d_off, c.N, c.owner,
+                       convert && f.has_scales ? (const void*)d_qs : c.qscale, dim, T, (int)c.B, c.D, c.dscale, (const int64_t*)d_off, c.N, c.owner,
                        p.G, p.QB, c.scores);
     CLB_HIP(hipGetLastError());
     return CLB_OK;
@@ -180,29 +198,30 @@ int run_dense_host(int device, const DenseCall& h) {
     CLB_TRY(check_shape(h));
     const DenseFormat& f = format_of(h.d_type);
     const bool q_f32 = h.q_type == CLB_F32;
-    if (h.N > 0 && (!h.doclens || !h.scores || !h.Q || (f.scaled && ((!q_f32 && !h.qscale) || (h.n_D > 0 && (!h.D || !h.dscale))))))
+    if (h.N > 0 && (!h.doclens || !h.scores || !h.Q || (f.has_scales && ((!q_f32 && !h.qscale) || (h.n_D > 0 && (!h.D || !h.dscale))))))
         return fail(CLB_EARGUMENT, "%s: null argument", h.who);
-    if (f.scaled && h.N > 0 && !q_f32) CLB_TRY(check_scales(h.who, "query", h.qscale, h.B * h.T));
-    if (f.scaled && h.N > 0) CLB_TRY(check_scales(h.who, "passage", h.dscale, h.n_D));
+    if (f.scaled && h.N > 0 && !q_f32) CLB_TRY(check_scales(h.who, "query", (const float*)h.qscale, h.B * h.T));
+    if (f.scaled && h.N > 0) CLB_TRY(check_scales(h.who, "passage", (const float*)h.dscale, h.n_D));
     CLB_TRY(check_host_lists(h.doclens, h.N, h.n_D, h.owner, h.B));
     CLB_TRY(use_device(device));
     if (h.N == 0) return CLB_OK;
     hipStream_t st = nullptr;
     CLB_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     const int64_t n_scores = h.owner ? h.N : h.N * h.B, wb = DenseWork(h.d_type, h.N, h.B, h.T, h.dim).total();
-    const bool qs_given = f.scaled && !q_f32;
+    const bool qs_given = f.has_scales && !q_f32;
+    const int dim = (int)h.dim;
     DevBuf dQ, dQs, dD, dDs, dL, dO, dS, dW;
-    int rc = upload(dQ, h.Q, (size_t)(q_f32 ? 4 : f.elem) * h.dim * h.T * h.B, st);
-    if (!rc && qs_given) rc = upload(dQs, h.qscale, sizeof(float) * h.T * h.B, st);
-    if (!rc) rc = upload(dD, h.D, (size_t)f.elem * h.dim * h.n_D, st);
-    if (!rc && f.scaled) rc = upload(dDs, h.dscale, sizeof(float) * h.n_D, st);
+    int rc = upload(dQ, h.Q, (size_t)(q_f32 ? 4 * dim : f.q_bytes(dim)) * h.T * h.B, st);
+    if (!rc && qs_given) rc = upload(dQs, h.qscale, (size_t)f.scale_bytes(dim) * h.T * h.B, st);
+    if (!rc) rc = upload(dD, h.D, (size_t)f.row_bytes(dim) * h.n_D, st);
+    if (!rc && f.has_scales) rc = upload(dDs, h.dscale, (size_t)f.scale_bytes(dim) * h.n_D, st);
     if (!rc) rc = upload(dL, h.doclens, sizeof(int64_t) * h.N, st);
     if (!rc && h.owner) rc = upload(dO, h.owner, sizeof(int32_t) * h.N, st);
     if (!rc) rc = dS.alloc(sizeof(float) * n_scores);
     if (!rc) rc = dW.alloc((size_t)wb);
     if (!rc) {
         DenseCall c = h;
-        c.Q = dQ.p, c.qscale = dQs.as<float>(), c.D = dD.p, c.dscale = dDs.as<float>(), c.doclens = dL.as<int64_t>();
+        c.Q = dQ.p, c.qscale = dQs.p, c.D = dD.p, c.dscale = dDs.p, c.doclens = dL.as<int64_t>();
         c.owner = h.owner ? dO.as<int32_t>() : nullptr, c.scores = dS.as<float>(), c.work = dW.p, c.work_bytes = wb, c.st = st;
         rc = run_dense_device(device, c);
     }
@@ -261,6 +280,66 @@ int clb_maxsim_batch_i8(int device, const void* Q, int q_type, const float* qsca
     return run_dense_host(device, {"maxsim_batch_i8", CLB_I8, q_type, CLB_I8, Q, qscale, D8, dscale, dim, T, B, n_D, N, doclens, owner, scores});
 }
 
+// one size for both passage formats: what the work buffer holds beside the offsets is the QUERY, MXFP8 either way (DenseMX's
+// q_bytes and scale_bytes do not depend on E2M1), so sizing by CLB_MXFP8 here equals run_dense_device's sizing by the passages' format
+int64_t clb_maxsim_batch_mx_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim) { return DenseWork(CLB_MXFP8, N, B, T, dim).total(); }
+
+int clb_maxsim_batch_mx_device(int device, const void* d_Q, int q_type, const uint8_t* d_qscale, int64_t dim, int64_t T, int64_t B,
+                               const uint8_t* d_D, const uint8_t* d_dscale, int format, int64_t n_D, const int64_t* d_doclens, int64_t N,
+                               const int32_t* d_owner, float* d_scores, void* d_work, int64_t work_bytes, void* hip_stream) {
+    return run_dense_device(device, {"maxsim_batch_mx", CLB_MXFP8, q_type, format, d_Q, d_qscale, d_D, d_dscale, dim, T, B, n_D, N, d_doclens,
+                                     d_owner, d_scores, d_work, work_bytes, (hipStream_t)hip_stream});
+}
+
+int clb_maxsim_batch_mx(int device, const void* Q, int q_type, const uint8_t* qscale, int64_t dim, int64_t T, int64_t B, const uint8_t* D,
+                        const uint8_t* dscale, int format, int64_t n_D, const int64_t* doclens, int64_t N, const int32_t* owner,
+                        float* scores) {
+    return run_dense_host(device, {"maxsim_batch_mx", CLB_MXFP8, q_type, format, Q, qscale, D, dscale, dim, T, B, n_D, N, doclens, owner, scores});
+}
+
+static int check_mx_format(int format) {
+    if (format != CLB_MXFP8 && format != CLB_MXFP4) return fail(CLB_EUNSUPPORTED, "quantize_mx serves CLB_MXFP8 and CLB_MXFP4 (format = %d)", format);
+    return CLB_OK;
+}
+
+int clb_quantize_mx_device(int device, const float* d_X, int64_t dim, int64_t n, int format, uint8_t* d_V, uint8_t* d_scale, void* hip_stream) {
+    CLB_TRY(check_mx_format(format));
+    CLB_TRY(check_dim("quantize_mx", 32, dim, ""));
+    if (n < 0) return fail(CLB_EARGUMENT, "quantize_mx: n >= 0 is required");
+    if (n == 0) return CLB_OK;
+    if (!d_X || !d_V || !d_scale) return fail(CLB_EARGUMENT, "quantize_mx: null argument");
+    if ((uintptr_t)d_X % 16 || (uintptr_t)d_V % 4) return fail(CLB_EARGUMENT, "quantize_mx: X must be 16-byte and the values 4-byte aligned");
+    CLB_TRY(use_device(device));
+    launch_quantize(format, d_X, (int)dim, n, d_V, d_scale, (hipStream_t)hip_stream);
+    CLB_HIP(hipGetLastError());
+    return CLB_OK;
+}
+
+int clb_quantize_mx(int device, const float* X, int64_t dim, int64_t n, int format, uint8_t* V, uint8_t* scale) {
+    CLB_TRY(check_mx_format(format));
+    CLB_TRY(check_dim("quantize_mx", 32, dim, ""));
+    if (n < 0 || (n > 0 && (!X || !V || !scale))) return fail(CLB_EARGUMENT, "quantize_mx: n >= 0 and non-null buffers are required");
+    for (int64_t e = 0; e < n; ++e)
+        for (int64_t k = 0; k < dim; ++k)
+            if (!std::isfinite(X[e * dim + k])) return fail(CLB_EARGUMENT, "quantize_mx: embedding %lld holds a non-finite value", (long long)e);
+    CLB_TRY(use_device(device));
+    if (n == 0) return CLB_OK;
+    const size_t v_bytes = (size_t)(format == CLB_MXFP4 ? dim / 2 : dim) * n, s_bytes = (size_t)(dim / 32) * n;
+    hipStream_t st = nullptr;
+    CLB_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    DevBuf dX, dV, dS;
+    int rc = upload(dX, X, sizeof(float) * dim * n, st);
+    if (!rc) rc = dV.alloc(v_bytes);
+    if (!rc) rc = dS.alloc(s_bytes);
+    if (!rc) rc = clb_quantize_mx_device(device, dX.as<float>(), dim, n, format, dV.as<uint8_t>(), dS.as<uint8_t>(), st);
+    if (!rc && (hipMemcpyAsync(V, dV.p, v_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipMemcpyAsync(scale, dS.p, s_bytes, hipMemcpyDeviceToHost, st) != hipSuccess))
+        rc = fail(CLB_EHIP, "quantize_mx: copying the result back failed");
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(CLB_EHIP, "quantize_mx: hipStreamSynchronize failed");
+    (void)hipStreamDestroy(st);
+    return rc;
+}
+
 int clb_quantize_rows_device(int device, const float* d_X, int64_t dim, int64_t n, int8_t* d_X8, float* d_scale, void* hip_stream) {
     CLB_TRY(check_dim("quantize_rows", 16, dim, ""));
     if (n < 0) return fail(CLB_EARGUMENT, "quantize_rows: n >= 0 is required");
@@ -268,7 +347,7 @@ int clb_quantize_rows_device(int device, const float* d_X, int64_t dim, int64_t 
     if (!d_X || !d_X8 || !d_scale) return fail(CLB_EARGUMENT, "quantize_rows: null argument");
     if ((uintptr_t)d_X % 16 || (uintptr_t)d_X8 % 16) return fail(CLB_EARGUMENT, "quantize_rows: X and X8 must be 16-byte aligned");
     CLB_TRY(use_device(device));
-    launch_quantize(d_X, (int)dim, n, d_X8, d_scale, (hipStream_t)hip_stream);
+    launch_quantize(CLB_I8, d_X, (int)dim, n, d_X8, d_scale, (hipStream_t)hip_stream);
     CLB_HIP(hipGetLastError());
     return CLB_OK;
 }

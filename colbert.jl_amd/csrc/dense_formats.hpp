@@ -1,9 +1,14 @@
 // dense_formats.hpp -- the embedding formats of the dense MaxSim kernel (dense_kernels.hpp: dense_maxsim_kernel<F, KB>) and the
-// kernels that bring fp32 queries into a format (dense_round_kernel, dense_quantize_kernel).  A format F supplies
-//   kElem, Frag       bytes per element; one lane's share of a K-block of one operand (K = kK = 4 sizeof(Frag) / kElem elements)
+// kernels that bring fp32 queries into a format (dense_round_kernel, dense_quantize_kernel, dense_quantize_mx_kernel).  A format
+// F supplies
+//   Frag, QFrag       one lane's share of a K-block (kK elements) of a row and of a query token: kFragBytes / kQFragBytes of values
+//   load_row, load_q  lane group g's fragment of a K-block, given the lane's first byte of it (the K-block's + kLaneBytes g), the
+//                     lane's scale byte and the bytes the row still holds from the K-block's start
+//   row_bytes(dim), q_bytes(dim), scale_bytes(dim), kDimMultiple   one embedding of D, of Q, its scales; what dim is a multiple of
 //   kRowTiles         16-row tiles a wave keeps and multiplies by every B operand
 //   kResident         whether a query of T <= 32 stays in registers (dense_kernels.hpp)
 //   kScaled           one fp32 scale per embedding: row scales staged in LDS per step, query scales applied in the sum
+//   kHasScales        any scales at all (kScaled, or block scales inside the fragments): staged behind the step's rows
 //   kHeadBytes, kOwnAt, kRowpAt   the LDS head: s_off (17 x 8) at 0, s_own (16 x 4), s_rowp (one int per row of a 4-wave step)
 //   row_stride(dim)   bytes from one LDS row to the next
 //   Acc, mfma         the accumulator and the instruction; epilogue(acc, ds): the accumulator as fp32, ds = its four rows' scales
@@ -56,6 +61,28 @@
 // SGPRs in lanes.  In the register path (KB > 0) the frame finishes a row tile -- chain, epilogue, maxima -- before it starts
 // the next: all chains first costs this format 16 more VGPRs and measured 2 % (owned) to 5 % (all pairs) slower
 // (profiles/dense_refactor.md).
+//
+// MX block-scaled (DenseMX<E2M1>: MXFP8 / MXFP4 passages, MXFP8 queries): v_mfma_scale_f32_16x16x128_f8f6f4 multiplies 128
+// elements and applies one E8M0 scale per block of 32 of each operand inside the product, so there is no epilogue multiply and
+// no query scale in the sum; A (rows, cbsz) and B (tokens, blgp) formats are independent.  At dim 128 a (row tile, token tile)
+// is ONE MFMA.  Layout, pinned by the exact test (tests/test_gpu_maxsim_batch_mx.py; a first build that gave every lane 32
+// consecutive E4M3 elements scored half of each block under another block's scale): an 8-bit operand is two halves of 64 --
+// lane (r, g) holds k = 16 g .. 16 g + 15 in registers 0-3 and k = 64 + 16 g .. in registers 4-7, two 16-byte reads 64 bytes
+// apart --, a 4-bit operand is k = 32 g .. 32 g + 31 in registers 0-3, one 16-byte read; block b's scale is the byte lane group
+// b supplies, so lane (r, g) reads scale byte g of its row whatever values it holds.  A piece past the row's end is zero
+// registers, a scale past it byte 127, neither read: dim % 32 == 0 suffices.  Rows per wave: 64 for both formats.  At dim 128
+// an MXFP8 row tile is 8 VGPRs + 1 scale, an MXFP4 one 4 + 1; the resident query 16 + 2.  128 rows per wave was the other
+// candidate for MXFP4 (8 tiles = 40 VGPRs): not built -- the frame packs a wave's first and last passage per tile into one
+// 32-bit scalar each (4 tiles), the step's row-to-passage table would double, and 64 rows keep the owned step at 20 KB of LDS
+// (256 rows x 80 B) + 1 KB of scales, so LDS allows 7 work-groups per CU where 40 KB would allow 3.  MXFP8: 256 x 144 B + 1 KB =
+// 37 KB, the int8 figures.  LDS rows at an odd number of 16-byte columns (144 / 80 B at dim 128), dim / 32 scale bytes per row
+// behind them (one dword per row at dim 128, staged in dwords; in bytes at other dims), where int8 keeps its fp32 scales.
+// Registers (hipcc -Rpass-analysis=kernel-resource-usage): MXFP8 KB = 1: 102 VGPRs, 4 waves per SIMD; KB = 0: 84, 5.  MXFP4
+// KB = 1: 87 VGPRs, 5 waves; KB = 0: 81, 5.  No AGPRs, no scratch, no VGPR spills; 53 (KB = 1) / 30 scalar values parked in
+// VGPR lanes, as for int8, not removed.  With one MFMA per tile, the tile's maximum (3 fmax, 2 shuffles, one LDS atomic per
+// token) is what the all-pairs form spends its issue slots on (read from the code; DESIGN 4.2a says what was considered).
+// Quantiser (dense_quantize_mx_kernel): plain integer / exact-fp32 code, not the hardware converts -- their saturation and
+// subnormal rounding were not measured against the numpy statement, and the integer form is the same code on host and device.
 #pragma once
 #include "dense_kernels.hpp"
 
@@ -64,11 +91,26 @@ namespace clb {
 typedef uint32_t dense_u32x4 __attribute__((ext_vector_type(4)));   // 8 halves: one lane's share of a K-block of one operand
 typedef int dense_i32x4 __attribute__((ext_vector_type(4)));        // 16 int8: one lane's share of a K-block; or one accumulator
 
-struct DenseF32 {
-    typedef float Frag;
+// What the formats whose two operands hold the same elements, ELEM bytes each, share: one fragment type, read as it lies.
+template <typename FRAG, int ELEM>
+struct DensePlain {
+    typedef FRAG Frag;
+    typedef FRAG QFrag;
+    static constexpr int kElem = ELEM, kFragBytes = (int)sizeof(FRAG), kQFragBytes = (int)sizeof(FRAG), kLaneBytes = (int)sizeof(FRAG), kDimMultiple = ELEM < 4 ? 16 / ELEM : 4;
+    __host__ __device__ static int row_bytes(int dim) { return ELEM * dim; }
+    __host__ __device__ static int q_bytes(int dim) { return ELEM * dim; }
+    // lane group g's fragment of a K-block, v already at it (its g-th); zeros, nothing read, where the row holds fewer than `left` bytes
+    static __device__ __forceinline__ FRAG load_row(const unsigned char* v, const unsigned char*, int g, int left) {
+        return (int)sizeof(FRAG) * g < left ? *reinterpret_cast<const FRAG*>(v) : FRAG{};
+    }
+    static __device__ __forceinline__ FRAG load_q(const unsigned char* v, const unsigned char* s, int g, int left) { return load_row(v, s, g, left); }
+};
+
+struct DenseF32 : DensePlain<float, 4> {
     typedef dense_f32x4 Acc;
-    static constexpr int kElem = 4, kK = 4, kRowTiles = 1, kHeadBytes = 1024, kOwnAt = 768, kRowpAt = 256;
-    static constexpr bool kResident = false, kScaled = false;
+    static constexpr int kK = 4, kRowTiles = 1, kHeadBytes = 1024, kOwnAt = 768, kRowpAt = 256;
+    static constexpr bool kResident = false, kScaled = false, kHasScales = false;
+    __host__ __device__ static int scale_bytes(int) { return 0; }
     __host__ __device__ static int row_stride(int dim) { return 4 * (dim + (68 - dim % 64) % 64); }   // = 4 mod 64 floats
     static __device__ __forceinline__ Acc mfma(Frag a, Frag b, Acc c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ dense_f32x4 epilogue(Acc acc, float4) { return acc; }
@@ -81,11 +123,11 @@ struct Dense16ByteFrag {
 };
 
 // The two 16-bit formats: the MFMA that multiplies them and the round-to-nearest-even from fp32 (NaN stays a quiet NaN).
-struct Dense16Bit : Dense16ByteFrag {
-    typedef dense_u32x4 Frag;
+struct Dense16Bit : Dense16ByteFrag, DensePlain<dense_u32x4, 2> {
     typedef dense_f32x4 Acc;
-    static constexpr int kElem = 2, kK = 32, kRowTiles = 2, kHeadBytes = 1024, kOwnAt = 768, kRowpAt = 256;
-    static constexpr bool kScaled = false;
+    static constexpr int kK = 32, kRowTiles = 2, kHeadBytes = 1024, kOwnAt = 768, kRowpAt = 256;
+    static constexpr bool kScaled = false, kHasScales = false;
+    __host__ __device__ static int scale_bytes(int) { return 0; }
     __host__ __device__ static int row_stride(int dim) { return padded(2 * dim); }
     static __device__ __forceinline__ dense_f32x4 epilogue(Acc acc, float4) { return acc; }
 };
@@ -108,11 +150,11 @@ struct DenseBF16 : Dense16Bit {
     }
 };
 
-struct DenseI8 : Dense16ByteFrag {
-    typedef dense_i32x4 Frag;
+struct DenseI8 : Dense16ByteFrag, DensePlain<dense_i32x4, 1> {
     typedef dense_i32x4 Acc;
-    static constexpr int kElem = 1, kK = 64, kRowTiles = 4, kHeadBytes = 1280, kOwnAt = 192, kRowpAt = 256;
-    static constexpr bool kScaled = true;
+    static constexpr int kK = 64, kRowTiles = 4, kHeadBytes = 1280, kOwnAt = 192, kRowpAt = 256;
+    static constexpr bool kScaled = true, kHasScales = true;
+    __host__ __device__ static int scale_bytes(int) { return 4; }
     __host__ __device__ static int row_stride(int dim) { return padded(dim); }
     static __device__ __forceinline__ Acc mfma(Frag a, Frag b, Acc c) { return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0); }
     // the int32 sums to fp32 (exact), each times its row's scale
@@ -120,6 +162,112 @@ struct DenseI8 : Dense16ByteFrag {
         return dense_f32x4{ds.x * (float)acc[0], ds.y * (float)acc[1], ds.z * (float)acc[2], ds.w * (float)acc[3]};
     }
 };
+
+// MX block-scaled embeddings (OCP MX v1.0): passages MXFP8 (E4M3) or MXFP4 (E2M1), queries always MXFP8, one E8M0 scale byte
+// per block of 32 elements.  A fragment is one block -- N16 16-byte columns of values and the block's scale byte, which
+// the instruction takes from the lane that holds the block; the zero fragment is zero values under scale byte 127.
+template <int N16>
+struct DenseMXFrag {
+    dense_u32x4 v[N16] = {};
+    uint32_t s = 127;
+};
+template <bool E2M1>
+struct DenseMX : Dense16ByteFrag {
+    typedef DenseMXFrag<E2M1 ? 1 : 2> Frag;
+    typedef DenseMXFrag<2> QFrag;
+    typedef dense_f32x4 Acc;
+    typedef int v8 __attribute__((ext_vector_type(8)));
+    static constexpr int kK = 128, kRowTiles = 4, kHeadBytes = 1280, kOwnAt = 192, kRowpAt = 256, kDimMultiple = 32;
+    static constexpr int kFragBytes = E2M1 ? 16 : 32, kQFragBytes = 32, kLaneBytes = 16;
+    static constexpr bool kScaled = false, kHasScales = true;     // no fp32 scale, no epilogue multiply: the scales are in the product
+    __host__ __device__ static int row_bytes(int dim) { return E2M1 ? dim >> 1 : dim; }
+    __host__ __device__ static int q_bytes(int dim) { return dim; }
+    __host__ __device__ static int scale_bytes(int dim) { return dim >> 5; }
+    __host__ __device__ static int row_stride(int dim) { return padded(row_bytes(dim)); }
+    // Lane group g's share of a K-block of 128 elements: v = the K-block's values + 16 g, s = its four scale bytes + g.  The
+    // instruction reads an 8-bit operand as two halves of 64: registers 0-3 are k = 16 g .. 16 g + 15, registers 4-7
+    // k = 64 + 16 g .. 64 + 16 g + 15 (measured: profiles/maxsim_batch_mx.md), a 4-bit operand as k = 32 g .. 32 g + 31; and it
+    // scales block b = k / 32 by the byte lane group b supplies, so the lane's scale operand is byte g whatever values it holds.
+    // `left`: the value bytes the row holds from v on; a 16-byte piece or a scale byte past them is zero / 127 and is not read.
+    template <int N16>
+    static __device__ __forceinline__ DenseMXFrag<N16> load(const unsigned char* v, const unsigned char* s, int g, int left) {
+        DenseMXFrag<N16> f;
+#pragma unroll
+        for (int i = 0; i < N16; ++i)
+            if (64 * i + 16 * g < left) f.v[i] = *reinterpret_cast<const dense_u32x4*>(v + 64 * i);
+        if (16 * N16 * g < left) f.s = s[0];
+        return f;
+    }
+    static __device__ __forceinline__ Frag load_row(const unsigned char* v, const unsigned char* s, int g, int left) { return load<E2M1 ? 1 : 2>(v, s, g, left); }
+    static __device__ __forceinline__ QFrag load_q(const unsigned char* v, const unsigned char* s, int g, int left) { return load<2>(v, s, g, left); }
+    template <int N16>
+    static __device__ __forceinline__ v8 operand(const DenseMXFrag<N16>& f) {
+        const dense_u32x4 hi = N16 == 2 ? f.v[N16 - 1] : dense_u32x4{};      // an E2M1 operand is the first four registers
+        return v8{(int)f.v[0][0], (int)f.v[0][1], (int)f.v[0][2], (int)f.v[0][3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+    }
+    // A = the rows in their format (cbsz: 0 E4M3, 4 E2M1), B = the tokens in E4M3 (blgp 0); each lane's scale in its byte 0
+    static __device__ __forceinline__ Acc mfma(const Frag& a, const QFrag& b, Acc c) {
+        return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(operand(a), operand(b), c, E2M1 ? 4 : 0, 0, 0, (int)a.s, 0, (int)b.s);
+    }
+    static __device__ __forceinline__ dense_f32x4 epilogue(Acc acc, float4) { return acc; }
+};
+typedef DenseMX<false> DenseMXFP8;
+typedef DenseMX<true> DenseMXFP4;
+
+// The element code of y, a value already divided by its block's scale: round to nearest-even onto the format's grid (E4M3:
+// 3 mantissa bits, least normal 2^-6, largest 448; E2M1: 1 bit, 1, 6), saturating; the sign is kept, a NaN gives the largest
+// magnitude, and no NaN code comes out.  Every step is exact but the one rintf, so host and device agree bit for bit.
+template <bool E2M1>
+__host__ __device__ inline uint32_t dense_mx_encode(float y) {
+    constexpr int M = E2M1 ? 1 : 3, EMIN = E2M1 ? 0 : -6, BIAS = E2M1 ? 1 : 7;
+    auto pow2 = [](int k) { return __builtin_bit_cast(float, (uint32_t)(k + 127) << 23); };
+    const float a = fminf(fabsf(y), E2M1 ? 6.f : 448.f);
+    const int ea = (int)(__builtin_bit_cast(uint32_t, a) >> 23) - 127;
+    const int eq = (ea > EMIN ? ea : EMIN) - M;                        // the grid's step at a is 2^eq
+    const float r = rintf(a * pow2(-eq)) * pow2(eq);
+    const uint32_t rb = __builtin_bit_cast(uint32_t, r);
+    const int er = (int)(rb >> 23) - 127;
+    const uint32_t mag = er < EMIN ? (uint32_t)(r * pow2(M - EMIN)) : ((uint32_t)(er + BIAS) << M | (rb >> (23 - M) & ((1u << M) - 1)));
+    return (__builtin_bit_cast(uint32_t, y) >> 31) << (E2M1 ? 3 : 7) | mag;
+}
+
+// X (dim, n) fp32 -> MX values V ((dim, n) bytes, or (dim / 2, n) for E2M1: element 2 i in the low nibble of byte i) and scale
+// bytes S (dim / 32, n), per block of 32: byte = max(0, E - emax) with E the biased fp32 exponent of the block's amax (= e + 127,
+// e = max(-127, ilogb(amax) - emax); emax = 8 / 2), 127 for amax == 0; element = dense_mx_encode(x * 2^-e), the product exact.
+// One wave per embedding, grid-stride; the row (dim <= 1024, dim % 32 == 0) is read once with float4 loads into at most 4
+// registers per lane; a block is the 8 float4 of 8 consecutive lanes, so its maximum is a 3-step butterfly among them; the
+// values leave as one dword (one half-word for E2M1) per lane and load, the scale byte from the block's first lane; no LDS.
+// A non-finite input gives defined, meaningless numbers (v_max_f32 drops a NaN, an infinite amax gives byte 255 - emax, the
+// encoder saturates).  X 16-byte aligned.
+template <bool E2M1>
+static __global__ __launch_bounds__(256) void dense_quantize_mx_kernel(const float* __restrict__ X, int dim, int64_t n,
+                                                                       unsigned char* __restrict__ V, unsigned char* __restrict__ S) {
+    constexpr int EMAX = E2M1 ? 2 : 8;
+    const int lane = threadIdx.x & 63, dim4 = dim >> 2, nblk = dim >> 5;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t e = wave; e < n; e += n_waves) {
+        const float4* src = reinterpret_cast<const float4*>(X + e * dim);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = lane + 64 * j;                                // (c < dim4 is uniform over a block's 8 lanes)
+            const float4 v = c < dim4 ? src[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+            float amax = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
+#pragma unroll
+            for (int d = 1; d < 8; d <<= 1) amax = fmaxf(amax, __shfl_xor(amax, d, 64));
+            if (c >= dim4) continue;
+            const int E = (int)(__float_as_uint(amax) >> 23);
+            const int byte = amax == 0.f ? 127 : (E > EMAX ? E - EMAX : 0);
+            const float inv = __uint_as_float((uint32_t)(254 - byte) << 23);      // 2^-e
+            const uint32_t c0 = dense_mx_encode<E2M1>(v.x * inv), c1 = dense_mx_encode<E2M1>(v.y * inv);
+            const uint32_t c2 = dense_mx_encode<E2M1>(v.z * inv), c3 = dense_mx_encode<E2M1>(v.w * inv);
+            if constexpr (E2M1)
+                reinterpret_cast<uint16_t*>(V + e * (dim >> 1))[c] = (uint16_t)(c0 | c1 << 4 | c2 << 8 | c3 << 12);
+            else
+                reinterpret_cast<uint32_t*>(V + e * dim)[c] = c0 | c1 << 8 | c2 << 16 | c3 << 24;
+            if ((lane & 7) == 0) S[e * nblk + (c >> 3)] = (unsigned char)byte;
+        }
+    }
+}
 
 // out[i] = round-to-nearest-even(in[i]) as H, 8 elements per thread and turn: n8 = n / 8, in and out 16-byte aligned.
 template <typename H>

@@ -1,9 +1,12 @@
 // dense_kernels.hpp -- MaxSim of un-indexed passages for a batch of queries (gfx950): the one kernel frame of every
-// embedding format, fp32 scores out.  A format (dense_formats.hpp) supplies its element and fragment types, its MFMA, its
-// tile epilogue, its LDS row stride and head; everything below exists once.
+// embedding format, fp32 scores out.  A format (dense_formats.hpp) supplies its fragment types and how one is read (rows and
+// query tokens each their own: their element formats may differ, and a fragment may carry a block scale), its MFMA, its tile
+// epilogue, its LDS row stride, scale bytes and head; everything below exists once.
 //   dot     one MFMA per K-block, the K-blocks in ascending order from +0: embeddings are tile rows, query tokens are tile
 //           columns.  Lane (r, g) holds, of K-block kb of row or token r, the FRAG consecutive elements at K kb + FRAG g --
-//           one fragment of sizeof(Frag) bytes, K = 4 FRAG -- and the same k in the A and the B operand.  The accumulator
+//           one fragment of F::kFragBytes (rows) or F::kQFragBytes (tokens) bytes, K = 4 FRAG -- and the same k in the A and
+//           the B operand.  Where a format's instruction orders K otherwise it says so in its load (F::load_row, F::load_q: the
+//           lane's first byte of the K-block, lane group g and the bytes the row still holds from the K-block's start).  The accumulator
 //           layout is the same for every format: lane (col r, g) holds the rows 4 g + i, i = 0..3.
 //   max     exact and order-free, so partial maxima of a passage combine in any order (LDS atomic max on order keys)
 //   sum     one serial chain per (passage, query), t ascending (dense_sum_maxima)
@@ -23,8 +26,9 @@
 // wave multiplies a tile once per RUN of consecutive passages with the same owner, and only the row tiles that hold a row
 // of the run.
 // Long passages span several steps and several waves of their work-group: their partial maxima meet in the same LDS words.
-// K tail.  dim is a multiple of the 16 / kElem elements of a 16-byte column, so a lane's fragment lies wholly inside the row
-// or wholly past it; past it both operands are zero registers (nothing is read), and zeros add exact zeros (KB = 0 only).
+// K tail.  dim is a multiple of the elements of one 16-byte piece of a fragment, so a piece lies wholly inside the row or
+// wholly past it; past it both operands hold zeros (nothing is read, neither values nor scale), and zeros add exact zeros
+// (KB = 0 only).
 // Safety, all by construction and stated here once: the offsets are a clamped scan (negative doclen = 0, every offset <= n_D),
 // so no row at or past n_D is read -- neither its elements nor its scale; an owner outside 0..B-1 multiplies nothing and
 // reads no query scale; a token column past T reads token T - 1 and reaches no maximum; rows past the step's end (whatever
@@ -39,9 +43,10 @@ typedef float dense_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kDenseMaxGroup = 16;         // passages per work-group, at most
 constexpr int kDensePmWords = 4096;        // LDS words of per-(query, passage, token) maxima per work-group
+constexpr int kDenseWholeRow = 1 << 30;    // "bytes left in the row" where the K-block lies wholly inside it
 
 // The dynamic LDS of one launch, in bytes from its start: the head (s_off at 0, 17 x 8; s_own and s_rowp where the format puts
-// them), the maxima, the step's rows at `stride` bytes each, the step's row scales (scaled formats).  The kernel carves its
+// them), the maxima, the step's rows at `stride` bytes each, the step's row scales (F::scale_bytes(dim) per row).  The kernel carves its
 // LDS by it and the host asks for `total`.
 struct DenseLayout {
     int stride, step_rows, pm_words;
@@ -56,7 +61,7 @@ __host__ __device__ inline DenseLayout dense_layout(int dim, int T, int QB, int 
     l.pm = F::kHeadBytes;
     l.rows = l.pm + ((size_t)l.pm_words * 4 + 15) / 16 * 16;
     l.scales = l.rows + (size_t)l.step_rows * l.stride;     // a multiple of 16: the stride is
-    l.total = l.scales + (F::kScaled ? (size_t)4 * l.step_rows : 0);
+    l.total = l.scales + (size_t)F::scale_bytes(dim) * l.step_rows;
     return l;
 }
 
@@ -157,7 +162,7 @@ __device__ __forceinline__ void dense_step_passages(const int64_t* __restrict__ 
 // batch, whose query scales are not read -- before any multiplication: qs[t] == 0 cannot turn it into a NaN.
 template <typename F>
 __device__ __forceinline__ void dense_sum_maxima(const uint32_t* __restrict__ s_pm, const int64_t* __restrict__ s_off,
-                                                 const int* __restrict__ s_own, const float* __restrict__ qscale, int nq, int np,
+                                                 const int* __restrict__ s_own, const void* __restrict__ qscale, int nq, int np,
                                                  int G, int TP, int T, int B, bool owned, int64_t p0, int q0, int64_t N,
                                                  float* __restrict__ scores) {
     for (int i = threadIdx.x; i < nq * np; i += blockDim.x) {
@@ -167,7 +172,7 @@ __device__ __forceinline__ void dense_sum_maxima(const uint32_t* __restrict__ s_
         if constexpr (F::kScaled) {
             const int q = owned ? s_own[p] : q0 + ql;
             if (s_off[p + 1] > s_off[p] && q >= 0 && q < B) {
-                const float* qs = qscale + (size_t)q * T;
+                const float* qs = static_cast<const float*>(qscale) + (size_t)q * T;
                 for (int t = 0; t < T; ++t) acc = acc + qs[t] * f32_from_order_key(pm[t]);
             } else {
                 acc = kNegInf;
@@ -181,15 +186,18 @@ __device__ __forceinline__ void dense_sum_maxima(const uint32_t* __restrict__ s_
 
 // One token tile against a wave's RT row tiles, those that hold a row of the run (bit j of `on`, wave-uniform).  KB > 0: KB
 // K-blocks of both operands from registers (a, b), tile after tile: its MFMA chain, its epilogue, its maxima.  KB = 0: K walked
-// at run time for all row tiles at once, A read from the LDS rows at arow, B once per K-block from the token at qtok (both
-// already at this lane's fragment), then the epilogues and maxima.
+// at run time for all row tiles at once, A read from the LDS rows at arow, B once per K-block from the token at qtok (this
+// lane's share of its row and token, F::kLaneBytes g bytes into K-block 0; asc and qsc: the lane's scale byte of K-block 0,
+// nsb bytes per row, null for a format without block scales), then the epilogues and maxima.
 template <typename F, int KB>
-__device__ __forceinline__ void dense_tiles(const typename F::Frag (*a)[KB > 0 ? KB : 1], const typename F::Frag* b,
-                                            const unsigned char* arow, int stride, const unsigned char* qtok, int dim, const float4* ds,
+__device__ __forceinline__ void dense_tiles(const typename F::Frag (*a)[KB > 0 ? KB : 1], const typename F::QFrag* b,
+                                            const unsigned char* arow, int stride, const unsigned char* asc, int nsb,
+                                            const unsigned char* qtok, const unsigned char* qsc, int dim, const float4* ds,
                                             int on, const int* __restrict__ rowp, int pa, int pb, bool tok_ok,
                                             uint32_t* __restrict__ pm, int TP, int t, int g) {
     typedef typename F::Frag Frag;
-    constexpr int RT = F::kRowTiles, FB = (int)sizeof(Frag);
+    typedef typename F::QFrag QFrag;
+    constexpr int RT = F::kRowTiles, FB = F::kFragBytes, QFB = F::kQFragBytes;
     if constexpr (KB > 0) {
 #pragma unroll
         for (int j = 0; j < RT; ++j) {
@@ -201,18 +209,18 @@ __device__ __forceinline__ void dense_tiles(const typename F::Frag (*a)[KB > 0 ?
         }
     } else {
         constexpr bool tail = 4 * FB > 16;                  // a K-block is wider than the 16-byte column dim is a multiple of
-        const Frag zero = {};
-        const int row_bytes = dim * F::kElem, nkb = (row_bytes + 4 * FB - 1) / (4 * FB);
+        const int row_bytes = F::row_bytes(dim), q_bytes = F::q_bytes(dim), nkb = (row_bytes + 4 * FB - 1) / (4 * FB);
         typename F::Acc acc[RT];
 #pragma unroll
         for (int j = 0; j < RT; ++j) acc[j] = typename F::Acc{};
         for (int kb = 0; kb < nkb; ++kb) {
-            const bool k_ok = !tail || (4 * kb + g) * FB < row_bytes;    // past the row: zeros, nothing read
-            const Frag bk = k_ok ? *reinterpret_cast<const Frag*>(qtok + 4 * FB * kb) : zero;
+            // what the row and the token still hold from this K-block on: past it a fragment is zeros and nothing is read
+            const int left = tail ? row_bytes - 4 * FB * kb : kDenseWholeRow, qleft = tail ? q_bytes - 4 * QFB * kb : kDenseWholeRow;
+            const QFrag bk = F::load_q(qtok + 4 * QFB * kb, qsc + 4 * kb, g, qleft);
 #pragma unroll
             for (int j = 0; j < RT; ++j)
                 if (on >> j & 1)
-                    acc[j] = F::mfma(k_ok ? *reinterpret_cast<const Frag*>(arow + 16 * j * stride + 4 * FB * kb) : zero, bk, acc[j]);
+                    acc[j] = F::mfma(F::load_row(arow + 16 * j * stride + 4 * FB * kb, asc + 16 * j * nsb + 4 * kb, g, left), bk, acc[j]);
         }
 #pragma unroll
         for (int j = 0; j < RT; ++j)
@@ -221,26 +229,32 @@ __device__ __forceinline__ void dense_tiles(const typename F::Frag (*a)[KB > 0 ?
 }
 
 // F = the format (dense_formats.hpp).  KB = dim / F::kK K-blocks of both operands in registers (dim 128); 0 = any served dim.
-// Q (dim, T, B) and D (dim, n_D) hold F's elements, D 16-byte aligned and Q aligned to a fragment; qscale (T, B) and dscale
-// [n_D] fp32, read by a scaled format only.
+// Q (dim, T, B) and D (dim, n_D) hold F's elements, D 16-byte aligned and Q aligned to 16 bytes or a fragment, whichever is
+// less; qscale (T, B) and dscale [n_D]: F::scale_bytes(dim) bytes per embedding (one fp32, or one byte per block of 32), read
+// by a format that has scales only.
 // grid (ceil(N / G), owned ? 1 : ceil(B / QB)); block 64 * nw; dynamic LDS = dense_layout<F>(dim, T, QB, G, nw, owned).total.
 template <typename F, int KB>
-static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const void* __restrict__ Qv, const float* __restrict__ qscale, int dim,
+static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const void* __restrict__ Qv, const void* __restrict__ qscale, int dim,
                                                                   int T, int B, const void* __restrict__ Dv,
-                                                                  const float* __restrict__ dscale, const int64_t* __restrict__ off,
+                                                                  const void* __restrict__ dscale, const int64_t* __restrict__ off,
                                                                   int64_t N, const int32_t* __restrict__ owner, int G, int QB,
                                                                   float* __restrict__ scores) {
     extern __shared__ __align__(16) unsigned char dense_smem[];
     typedef typename F::Frag Frag;
+    typedef typename F::QFrag QFrag;
     typedef uint32_t col16 __attribute__((ext_vector_type(4)));                  // one 16-byte column of a row
-    constexpr int RT = F::kRowTiles, WR = 16 * RT, KR = KB > 0 ? KB : 1, FB = (int)sizeof(Frag);
+    constexpr int RT = F::kRowTiles, WR = 16 * RT, KR = KB > 0 ? KB : 1, FB = F::kFragBytes, QFB = F::kQFragBytes;
     const unsigned char* Q = static_cast<const unsigned char*>(Qv);
     const unsigned char* D = static_cast<const unsigned char*>(Dv);
+    const unsigned char* QS = static_cast<const unsigned char*>(qscale);
     const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, r = lane & 15, g = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar, so that what hangs on the wave's rows is wave-uniform to the compiler
     const bool owned = owner != nullptr;
     const DenseLayout L = dense_layout<F>(dim, T, QB, G, nthr >> 6, owned);
-    const int CH = L.step_rows, stride = L.stride, TP = T | 1, cols = dim * F::kElem >> 4;   // rows per step; 16-byte columns per row
+    const int CH = L.step_rows, stride = L.stride, TP = T | 1, cols = F::row_bytes(dim) >> 4;   // rows per step; 16-byte columns per row
+    const int nsb = F::scale_bytes(dim);                                         // scale bytes per embedding
+    constexpr bool BS = F::kHasScales && !F::kScaled;                            // block scales inside the fragments: else no scale pointer lives
+    const int fsb = BS ? nsb : 0;
     const int64_t p0 = (int64_t)blockIdx.x * G;
     const int np = (int)(N - p0 < G ? N - p0 : G);
     const int q0 = owned ? 0 : (int)blockIdx.y * QB;
@@ -250,36 +264,48 @@ static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const void* __
     int* s_rowp = reinterpret_cast<int*>(dense_smem + F::kRowpAt);
     uint32_t* s_pm = reinterpret_cast<uint32_t*>(dense_smem + L.pm);
     unsigned char* s_d = dense_smem + L.rows;
-    float* s_ds = reinterpret_cast<float*>(dense_smem + L.scales);             // the step's row scales (scaled formats)
+    unsigned char* s_sc = dense_smem + L.scales;                                // the step's row scales, nsb bytes per row
+    float* s_ds = reinterpret_cast<float*>(s_sc);                               // (a format with one fp32 scale per row)
 
     dense_group_begin(s_off, s_own, s_pm, off, owner, p0, np, L.pm_words);
     __syncthreads();
     const int64_t lo = s_off[0], hi = s_off[np];
 
     const Frag zero = {};
+    const QFrag qzero = {};
     const bool resident = F::kResident && KB > 0 && T <= 32;
-    Frag bq[2][KR];                                        // the resident query's token tiles (resident only)
+    QFrag bq[2][KR];                                       // the resident query's token tiles (resident only)
     int q_res = -1;                                        // (wave-uniform) the query they hold
-    // lane (r, g)'s fragment of K-block 0 of token t of query q, t clamped to the last token; K-block kb lies 4 FB kb bytes on
-    auto q_tok = [&](int q, int t) { return Q + ((size_t)q * T + (t < T ? t : T - 1)) * dim * F::kElem + FB * g; };
+    // K-block 0 of token t of query q, t clamped to the last token; K-block kb lies 4 QFB kb bytes on.  q_sc: the same for its
+    // block scales, K-block kb 4 bytes on (a format whose fragments carry one)
+    auto q_tok = [&](int q, int t) { return Q + ((size_t)q * T + (t < T ? t : T - 1)) * F::q_bytes(dim) + F::kLaneBytes * g; };
+    auto q_sc = [&](int q, int t) { return BS ? QS + ((size_t)q * T + (t < T ? t : T - 1)) * nsb + g : nullptr; };
 
     for (int64_t c = lo; c < hi; c += CH) {
         const int n_rows = (int)(hi - c < CH ? hi - c : CH);
-        // the step's rows, dense 16-byte loads (D + c * dim elements is 16-byte aligned), into padded LDS rows; their scales
-        const col16* src = reinterpret_cast<const col16*>(D + c * dim * F::kElem);
+        // the step's rows, dense 16-byte loads (D + c rows is 16-byte aligned), into padded LDS rows; their scales -- those of
+        // the rows read, no others -- in dwords where a row's are whole dwords (then dscale + c rows is 4-byte aligned)
+        const col16* src = reinterpret_cast<const col16*>(D + c * F::row_bytes(dim));
         for (int i = tid; i < n_rows * cols; i += nthr) {
             const int row = i / cols, col = i - row * cols;
             *reinterpret_cast<col16*>(s_d + row * stride + 16 * col) = src[i];
         }
-        if constexpr (F::kScaled)
-            for (int i = tid; i < n_rows; i += nthr) s_ds[i] = dscale[c + i];
+        if constexpr (F::kHasScales) {
+            const unsigned char* ssrc = static_cast<const unsigned char*>(dscale) + c * nsb;
+            if (nsb % 4 == 0) {
+                for (int i = tid; i < n_rows * (nsb >> 2); i += nthr) reinterpret_cast<uint32_t*>(s_sc)[i] = reinterpret_cast<const uint32_t*>(ssrc)[i];
+            } else {
+                for (int i = tid; i < n_rows * nsb; i += nthr) s_sc[i] = ssrc[i];
+            }
+        }
         dense_step_passages(s_off, s_rowp, c, n_rows, CH, np);
         __syncthreads();
 
         const int rb = WR * w;                              // this wave's rows of the step: RT tiles of 16
         if (rb < n_rows) {
             const int* rowp = s_rowp + rb;
-            const unsigned char* arow = s_d + (rb + r) * stride + FB * g;
+            const unsigned char* arow = s_d + (rb + r) * stride + F::kLaneBytes * g;   // this lane's share of its row of tile 0, and its scale byte
+            const unsigned char* asc = BS ? s_sc + (rb + r) * nsb + g : nullptr;
             Frag a[RT][KR];
             float4 ds[RT];
             uint32_t tf = 0, tl = 0;                        // (wave-uniform) byte j: tile j's first and last passage (< 16); none: first > last
@@ -294,7 +320,8 @@ static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const void* __
                     if (live) ds[j] = *reinterpret_cast<const float4*>(s_ds + rb + 16 * j + 4 * g);
                 if (KB > 0) {
 #pragma unroll
-                    for (int kb = 0; kb < KB; ++kb) a[j][kb] = live ? *reinterpret_cast<const Frag*>(arow + 16 * j * stride + 4 * FB * kb) : zero;
+                    for (int kb = 0; kb < KB; ++kb)
+                        a[j][kb] = live ? F::load_row(arow + 16 * j * stride + 4 * FB * kb, asc + 16 * j * fsb + 4 * kb, g, kDenseWholeRow) : zero;
                 }
             }
             const int last = (rb + WR < n_rows ? rb + WR : n_rows) - 1;
@@ -329,23 +356,25 @@ static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const void* __
                             for (int tt = 0; tt < 2; ++tt) {
 #pragma unroll
                                 for (int kb = 0; kb < KR; ++kb)
-                                    bq[tt][kb] = 16 * tt < T ? *reinterpret_cast<const Frag*>(q_tok(q, 16 * tt + r) + 4 * FB * kb) : zero;
+                                    bq[tt][kb] = 16 * tt < T ? F::load_q(q_tok(q, 16 * tt + r) + 4 * QFB * kb, q_sc(q, 16 * tt + r) + 4 * kb, g, kDenseWholeRow) : qzero;
                             }
                             q_res = q;
                         }
 #pragma unroll
                         for (int tt = 0; tt < 2; ++tt)
                             if (16 * tt < T)
-                                dense_tiles<F, KB>(a, bq[tt], arow, stride, nullptr, dim, ds, on, rowp, pa, pb, 16 * tt + r < T, pm, TP, 16 * tt + r, g);
+                                dense_tiles<F, KB>(a, bq[tt], arow, stride, asc, fsb, nullptr, nullptr, dim, ds, on, rowp, pa, pb, 16 * tt + r < T, pm,
+                                                   TP, 16 * tt + r, g);
                     } else {
                         for (int t0 = 0; t0 < T; t0 += 16) {
                             const unsigned char* qtok = q_tok(q, t0 + r);
-                            Frag bt[KR];
+                            const unsigned char* qsc = q_sc(q, t0 + r);
+                            QFrag bt[KR];
                             if (KB > 0) {
 #pragma unroll
-                                for (int kb = 0; kb < KB; ++kb) bt[kb] = *reinterpret_cast<const Frag*>(qtok + 4 * FB * kb);
+                                for (int kb = 0; kb < KB; ++kb) bt[kb] = F::load_q(qtok + 4 * QFB * kb, qsc + 4 * kb, g, kDenseWholeRow);
                             }
-                            dense_tiles<F, KB>(a, bt, arow, stride, qtok, dim, ds, on, rowp, pa, pb, t0 + r < T, pm, TP, t0 + r, g);
+                            dense_tiles<F, KB>(a, bt, arow, stride, asc, fsb, qtok, qsc, dim, ds, on, rowp, pa, pb, t0 + r < T, pm, TP, t0 + r, g);
                         }
                     }
                 }

@@ -862,7 +862,7 @@ int clb_maxsim_batch(int device, const float* Q, int64_t dim, int64_t T, int64_t
  * allocation (d_work: clb_maxsim_batch_half_work_bytes bytes -- the offsets and the rounded Q), capturable, clamped doclens, -Inf
  * for a passage without a readable row or with an owner outside the batch; the host call (Q and D host buffers in the named
  * types) validates first.  Not part of the Julia shim. */
-enum { CLB_F32 = 0, CLB_F16 = 1, CLB_BF16 = 2, CLB_I8 = 3 };
+enum { CLB_F32 = 0, CLB_F16 = 1, CLB_BF16 = 2, CLB_I8 = 3, CLB_MXFP8 = 4, CLB_MXFP4 = 5 };
 int64_t clb_maxsim_batch_half_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim);
 int clb_maxsim_batch_half_device(int device, const void* d_Q, int q_type, int64_t dim, int64_t T, int64_t B,
                                  const void* d_D, int d_type, int64_t n_D, const int64_t* d_doclens, int64_t N,
@@ -903,6 +903,48 @@ int clb_maxsim_batch_i8_device(int device, const void* d_Q, int q_type, const fl
 int clb_maxsim_batch_i8(int device, const void* Q, int q_type, const float* qscale, int64_t dim, int64_t T, int64_t B,
                         const int8_t* D8, const float* dscale, int64_t n_D, const int64_t* doclens, int64_t N, const int32_t* owner,
                         float* scores);
+/* The same call on MX block-scaled embeddings (OCP MX v1.0; dense_formats.hpp).  An MX operand is a pair:
+ *   values  (dim, n) uint8 for CLB_MXFP8 -- E4M3: largest 448, no infinities, 0x7F / 0xFF are NaN -- or (dim / 2, n) uint8 for
+ *           CLB_MXFP4 -- E2M1: magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6; element 2 i in the low nibble of byte i;
+ *   scales  (dim / 32, n) uint8, E8M0: 2^(byte - 127), 0xFF is NaN.  Block j of an embedding is its elements 32 j .. 32 j + 31.
+ * Quantisation (clb_quantize_mx*, one definition for host and device), per block with amax = max_k |x_k|:
+ *   e = max(-127, ilogb(amax) - emax), emax = 8 (E4M3) or 2 (E2M1); scale byte = e + 127; amax == 0 gives byte 127;
+ *   element k = x_k 2^-e (exact) rounded to nearest-even in the element format and saturated to +-448 / +-6, sign kept (a
+ *   negative value that rounds to zero is -0); no NaN code is produced.  Every step is exact or one rounding.
+ *   Served: format CLB_MXFP8 or CLB_MXFP4, dim % 32 == 0, 32 <= dim <= 1024, else CLB_EUNSUPPORTED; d_X 16-byte, d_V 4-byte aligned.
+ *   The host call refuses a non-finite value with CLB_EARGUMENT naming the embedding; the device call cannot report: a
+ *   non-finite value there gives defined but meaningless numbers, never a fault.
+ * Scoring.  Queries are always MXFP8 (q_type = CLB_MXFP8 with d_qscale (dim / 32, T, B), or CLB_F32: quantised as above into the
+ * work buffer first, d_qscale ignored); passages are `format` = CLB_MXFP8 or CLB_MXFP4.  With q^ and d^ the decoded operands,
+ * scale included:
+ *   m_t   = max over the rows r of passage j of sum_k q^[k, t] d^[k, r]   (v_mfma_scale_f32_16x16x128_f8f6f4: every product is
+ *           exact, the sum is accumulated in fp32 by the instruction, the K-blocks of 128 ascending from +0)
+ *   score = acc = 0; for t ascending: acc = fl32(acc + m_t);  -Inf for a pair that received no row.
+ * Where every partial sum of a dot is exact in fp32 the score has the bits of that restatement in float64; otherwise it lies
+ * within 2 dim u sum_t |q^_t| max_r |d^_r| + T u sum_t |m_t|, u = 2^-10, of it (the 16-bit formats' form; u from the bare
+ * instruction, measured by tools/microbench/mfma_scale_mx.hip: its sum is NOT an fp32 chain -- over random blocks of every code
+ * the largest error is 2^-11.5 sum_k |q^ d^|, and 2^-23.0 where a block's codes lie in its top two binades, as most of a
+ * quantised embedding's do; profiles/maxsim_batch_mx.md has both and the kernel's largest error / bound), and its bits depend on
+ * its own query and passage only.  NaN codes and NaN
+ * scale bytes are outside the claim (they give NaN or any number, never a fault).  How far the scores lie from the fp32 scores
+ * of the unquantised embeddings is a property of the format, not part of the contract.
+ * Served: dim % 32 == 0, 32 <= dim <= 1024 (tuned for 128), 1 <= T <= 128, B >= 1, N >= 0, else CLB_EUNSUPPORTED; d_Q, d_D and d_work
+ * 16-byte aligned, d_dscale 4-byte aligned when dim % 128 == 0.  Every other contract is clb_maxsim_batch_device's /
+ * clb_maxsim_batch's: argument errors before any launch, stream-ordered, no host wait, no allocation (d_work:
+ * clb_maxsim_batch_mx_work_bytes bytes -- the offsets, and B T (dim + dim / 32) bytes for a query quantised in the call),
+ * capturable, clamped doclens (no row at or past n_D is read, neither its values nor its scale bytes); the host call
+ * validates first.  Not part of the Julia shim. */
+int clb_quantize_mx_device(int device, const float* d_X, int64_t dim, int64_t n, int format, uint8_t* d_V, uint8_t* d_scale,
+                           void* hip_stream);
+int clb_quantize_mx(int device, const float* X, int64_t dim, int64_t n, int format, uint8_t* V, uint8_t* scale);
+int64_t clb_maxsim_batch_mx_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim);
+int clb_maxsim_batch_mx_device(int device, const void* d_Q, int q_type, const uint8_t* d_qscale, int64_t dim, int64_t T, int64_t B,
+                               const uint8_t* d_D, const uint8_t* d_dscale, int format, int64_t n_D, const int64_t* d_doclens,
+                               int64_t N, const int32_t* d_owner /* NULL: all pairs */, float* d_scores,
+                               void* d_work, int64_t work_bytes, void* hip_stream);
+int clb_maxsim_batch_mx(int device, const void* Q, int q_type, const uint8_t* qscale, int64_t dim, int64_t T, int64_t B,
+                        const uint8_t* D, const uint8_t* dscale, int format, int64_t n_D, const int64_t* doclens, int64_t N,
+                        const int32_t* owner, float* scores);
 /* compress_into_codes!  (residual.jl:67-81) */
 int clb_compress_into_codes(int device, uint32_t* codes, int64_t n_codes, const float* centroids,
                             int64_t dim, int64_t K, const float* embs, int64_t n);
