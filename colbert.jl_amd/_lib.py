@@ -273,6 +273,11 @@ def lib() -> C.CDLL:
             l.clb_maxsim_batch_i8.argtypes = [ci, vp, ci, vp, i64_, i64_, i64_, vp, vp, i64_, vp, i64_, vp, vp]
             l.clb_maxsim_batch_i8_device.restype = ci
             l.clb_maxsim_batch_i8_device.argtypes = [ci, vp, ci, vp, i64_, i64_, i64_, vp, vp, i64_, vp, i64_, vp, vp, vp, i64_, vp]
+        if hasattr(l, "clb_maxsim_store_device"):             # (likewise)
+            l.clb_maxsim_store_work_bytes.restype = i64_
+            l.clb_maxsim_store_work_bytes.argtypes = [i64_, i64_, i64_, i64_, ci]
+            l.clb_maxsim_store_device.restype = ci
+            l.clb_maxsim_store_device.argtypes = [ci, vp, ci, vp, i64_, i64_, i64_, vp, vp, ci, i64_, vp, i64_, vp, i64_, vp, vp, vp, i64_, vp]
         if hasattr(l, "clb_debug_nearest"):
             l.clb_debug_nearest_scratch_create.restype = ci
             l.clb_debug_nearest_scratch_create.argtypes = [ci, C.POINTER(vp)]

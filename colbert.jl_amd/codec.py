@@ -321,7 +321,8 @@ def maxsim_batch(Q, D, doclens, owner=None, device: int = 0, dtype=None):
     return scores
 
 
-def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, stream=None, *, d_scale=None, q_scale=None):
+def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, stream=None, *, d_scale=None, q_scale=None, pids=None,
+                        store_offsets=None):
     """`maxsim_batch` between the encoder's device outputs (clb_maxsim_batch_device): d_Q float32 (B, T, dim) -- what
     query_embeddings_device writes --, d_D float32 (n, dim) and d_doclens int64 (N,) -- what doc_embeddings_device /
     doc_embeddings_packed_device return --, owner int32 (N,) or None; all contiguous CUDA tensors.  Returns `out`: float32 (N,)
@@ -335,8 +336,17 @@ def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, st
     clb_maxsim_batch_i8_work_bytes long.  Any other mix of int8 operands and scales is a ValueError.
     A uint8 d_D with a uint8 `d_scale` (n, dim / 32) is an MX pair (what `quantize_mx_device` returns) and takes the scaled-MFMA
     kernel (clb_maxsim_batch_mx_device): d_D (n, dim) is MXFP8, (n, dim / 2) MXFP4; d_Q float32 (quantised to MXFP8 on the device) or
-    uint8 with a uint8 `q_scale` (B, T, dim / 32); `work` clb_maxsim_batch_mx_work_bytes long.  Any other mix is a ValueError."""
+    uint8 with a uint8 `q_scale` (B, T, dim / 32); `work` clb_maxsim_batch_mx_work_bytes long.  Any other mix is a ValueError.
+    By passage id (clb_maxsim_store_device): with `pids` int64 (N,) and `store_offsets` int64 (P + 1,), d_D and d_scale are a
+    resident store -- stored passage p is the rows store_offsets[p] .. store_offsets[p + 1] - 1 -- and d_doclens must be None:
+    entry j scores stored passage pids[j], read where it lies, with the bits the contiguous call gives for the same rows; a pid
+    outside 0..P-1 (pad with -1) or an empty range scores -inf.  The format is chosen by dtype and scales as above; `work` is
+    clb_maxsim_store_work_bytes long."""
     import torch
+    if pids is not None or store_offsets is not None:
+        if pids is None or store_offsets is None or d_doclens is not None:
+            raise ValueError("pids and store_offsets go together, and d_doclens must be None with them")
+        return _maxsim_store_device(d_Q, d_D, pids, store_offsets, owner, out, work, stream, d_scale, q_scale)
     if torch.uint8 in (d_D.dtype, d_Q.dtype) or torch.uint8 in (getattr(d_scale, "dtype", None), getattr(q_scale, "dtype", None)):
         return _maxsim_batch_mx_device(d_Q, d_D, d_doclens, owner, out, work, stream, d_scale, q_scale)
     int8 = torch.int8 in (d_D.dtype, d_Q.dtype) or d_scale is not None or q_scale is not None
@@ -417,6 +427,49 @@ def _maxsim_batch_mx_device(d_Q, d_D, d_doclens, owner, out, work, stream, d_sca
     check(lib().clb_maxsim_batch_mx_device(q.device.index, ptr(q), F32 if q.dtype == torch.float32 else MXFP8, ptr(qs), i64(dim), i64(T), i64(B),
                                            ptr(d), ptr(ds), MXFP8 if d.shape[1] == dim else MXFP4, i64(n), ptr(dl), i64(N), ptr(ow), ptr(o),
                                            ptr(wk), i64(wk.numel() * wk.element_size()), C.c_void_p(st)))
+    return out
+
+
+def _maxsim_store_device(d_Q, d_D, pids, store_offsets, owner, out, work, stream, d_scale, q_scale):
+    """maxsim_batch_device by passage id: the store's format from d_D's dtype and the scales' (one entry point for all six)"""
+    import torch
+    q, d = _dev_rows(d_Q), _dev_rows(d_D)
+    pid, off = _dev_rows(pids, torch.int64), _dev_rows(store_offsets, torch.int64)
+    if q.dim() != 3 or d.dim() != 2 or off.numel() < 1:
+        raise ValueError("d_Q must be (B, T, dim), d_D (n, dim) and store_offsets (P + 1,)")
+    B, T, dim = (int(x) for x in q.shape)
+    mx = d.dtype == torch.uint8
+    if d.shape[1] not in ((dim, dim // 2) if mx else (dim,)):
+        raise ValueError("d_D must be (n, dim); an MXFP4 store (n, dim / 2)")
+    types = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16, torch.int8: I8, torch.uint8: MXFP8}
+    if d.dtype not in types or q.dtype not in types:
+        raise ValueError(f"no dense format for d_D {d.dtype} and d_Q {q.dtype}")
+    d_type = MXFP4 if mx and d.shape[1] != dim else types[d.dtype]
+    # the scales each operand's dtype asks for: one float32 per embedding (int8), one uint8 per block of 32 (MX), else none
+    want = {torch.int8: (torch.float32, 1), torch.uint8: (torch.uint8, dim // 32)}
+    scales = []
+    for name, t, s, rows in (("d_scale", d, d_scale, int(d.shape[0])), ("q_scale", q, q_scale, B * T)):
+        dt, per = want.get(t.dtype, (None, 0))
+        if (s is None) != (dt is None) or (s is not None and (_dev_rows(s).dtype != dt or s.numel() != rows * per)):
+            raise ValueError(f"{name}: {'none' if dt is None else f'{per} {dt} per embedding'} for a {t.dtype} operand")
+        scales.append(s)
+    ds, qs = scales
+    N = int(pid.numel())
+    ow = None if owner is None else _dev_rows(owner, torch.int32)
+    if ow is not None and ow.numel() != N:
+        raise ValueError("owner must hold one query number per entry of pids")
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())      # noqa: E731
+    if out is None:
+        out = torch.empty(N if ow is not None else (B, N), dtype=torch.float32, device=q.device)
+    if work is None:
+        work = torch.empty(int(lib().clb_maxsim_store_work_bytes(i64(N), i64(B), i64(T), i64(dim), d_type)), dtype=torch.uint8, device=q.device)
+    o = _dev_rows(out, torch.float32); wk = _dev_rows(work)
+    if o.numel() != (N if ow is not None else N * B):
+        raise ValueError("out: one score per entry (owned) or per (query, entry)")
+    st = torch.cuda.current_stream(q.device).cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+    check(lib().clb_maxsim_store_device(q.device.index, ptr(q), types[q.dtype], ptr(qs), i64(dim), i64(T), i64(B), ptr(d), ptr(ds), d_type,
+                                        i64(d.shape[0]), ptr(off), i64(off.numel() - 1), ptr(pid), i64(N), ptr(ow), ptr(o), ptr(wk),
+                                        i64(wk.numel() * wk.element_size()), C.c_void_p(st)))
     return out
 
 

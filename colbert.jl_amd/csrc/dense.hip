@@ -2,7 +2,8 @@
 // the encoder's device outputs, with no index and no handle.  One kernel frame (dense_kernels.hpp) for six embedding formats
 // (dense_formats.hpp): fp32 (clb_maxsim_batch*, the oracle's bits), fp16 / bf16 (clb_maxsim_batch_half*), int8 with one scale
 // each (clb_maxsim_batch_i8*, clb_quantize_rows*), MXFP8 / MXFP4 with one scale byte per block of 32 (clb_maxsim_batch_mx*,
-// clb_quantize_mx*); one device path and one host-array path behind the eight entry points.
+// clb_quantize_mx*); one device path and one host-array path behind the eight entry points, and the same device path behind
+// clb_maxsim_store_device, which scores passages listed by id where they lie in a resident store (any of the six formats).
 #include <algorithm>
 #include <cmath>
 
@@ -17,19 +18,23 @@ inline int64_t align256(int64_t n) { return (n + 255) / 256 * 256; }
 // What the host needs of a format F: its sizes, its LDS layout, its kernels.  Indexed by D's type, CLB_F32 .. CLB_MXFP4.
 typedef void (*DenseKernel)(const void*, const void*, int, int, int, const void*, const void*, const int64_t*, int64_t, const int32_t*,
                             int, int, float*);
+typedef void (*DenseStoreKernel)(const void*, const void*, int, int, int, const void*, const void*, const int64_t*, int64_t, const int32_t*,
+                                 int, int, float*, DenseStore);
 struct DenseFormat {
     int dim_multiple;                                   // dim is a multiple of one fragment's elements
     bool scaled, has_scales;                            // one fp32 scale per embedding (applied around the product); any scales at all
     int (*row_bytes)(int dim);                          // one embedding of D, of Q in D's family, and its scales
     int (*q_bytes)(int dim);
     int (*scale_bytes)(int dim);
-    DenseLayout (*layout)(int dim, int T, int QB, int G, int nw, bool owned);
+    DenseLayout (*layout)(int dim, int T, int QB, int G, int nw, bool owned, bool listed);
     DenseKernel k128, kany;                             // both operands in registers at dim 128; any served dim
+    DenseStoreKernel s128, sany;                        // the same two, passages listed by id in a resident store
 };
 template <typename F>
 DenseFormat dense_format() {
     return {F::kDimMultiple, F::kScaled, F::kHasScales, F::row_bytes, F::q_bytes, F::scale_bytes, dense_layout<F>,
-            dense_maxsim_kernel<F, 128 / F::kK>, dense_maxsim_kernel<F, 0>};
+            dense_maxsim_kernel<F, 128 / F::kK>, dense_maxsim_kernel<F, 0>, dense_maxsim_kernel<F, 128 / F::kK, DenseStore>,
+            dense_maxsim_kernel<F, 0, DenseStore>};
 }
 const DenseFormat& format_of(int d_type) {
     static const DenseFormat f[6] = {dense_format<DenseF32>(), dense_format<DenseF16>(), dense_format<DenseBF16>(), dense_format<DenseI8>(),
@@ -53,6 +58,11 @@ struct DenseCall {
     void* work = nullptr;
     int64_t work_bytes = 0;
     hipStream_t st = nullptr;
+    // a listed call (clb_maxsim_store_device): D / dscale / n_D are the store and its rows, doclens the store's offsets [P + 1],
+    // pids [N] the entries to score
+    bool listed = false;
+    const int64_t* pids = nullptr;
+    int64_t P = 0;
 };
 
 int check_dim(const char* who, int m, int64_t dim, const char* advice) {
@@ -63,6 +73,7 @@ int check_dim(const char* who, int m, int64_t dim, const char* advice) {
 
 int check_shape(const DenseCall& c) {
     const char* advice = c.family == CLB_F32 ? ": score one query at a time with clb_maxsim" : "";
+    if (c.family == CLB_F32 && c.q_type != CLB_F32) return fail(CLB_EUNSUPPORTED, "%s serves fp32 D with Q in fp32 (q_type = %d)", c.who, c.q_type);
     if (c.family == CLB_I8 && c.q_type != CLB_F32 && c.q_type != CLB_I8)
         return fail(CLB_EUNSUPPORTED, "%s serves Q in fp32 or int8 (q_type = %d)", c.who, c.q_type);
     if (c.family == CLB_F16 && ((c.d_type != CLB_F16 && c.d_type != CLB_BF16) || (c.q_type != CLB_F32 && c.q_type != c.d_type)))
@@ -72,6 +83,7 @@ int check_shape(const DenseCall& c) {
     CLB_TRY(check_dim(c.who, format_of(c.d_type).dim_multiple, c.dim, advice));
     if (c.T < 1 || c.T > 128) return fail(CLB_EUNSUPPORTED, "%s serves 1 <= T <= 128 (T = %lld)%s", c.who, (long long)c.T, advice);
     if (c.B < 1 || c.N < 0 || c.n_D < 0) return fail(CLB_EARGUMENT, "%s: B >= 1, N >= 0 and n_D >= 0 are required", c.who);
+    if (c.P < 0) return fail(CLB_EARGUMENT, "%s: P >= 0 is required", c.who);
     return CLB_OK;
 }
 
@@ -81,7 +93,7 @@ struct DensePlan {
     unsigned gx, gy;
     size_t lds;
 };
-DensePlan plan_dense(const DenseFormat& f, int dim, int T, int64_t B, int64_t N, bool owned) {
+DensePlan plan_dense(const DenseFormat& f, int dim, int T, int64_t B, int64_t N, bool owned, bool listed) {
     DensePlan p;
     const int TP = T | 1;
     const int g_target = (int)std::min<int64_t>(kDenseMaxGroup, std::max<int64_t>(1, (N + 2047) / 2048));   // >= ~2048 work-groups first
@@ -90,23 +102,24 @@ DensePlan plan_dense(const DenseFormat& f, int dim, int T, int64_t B, int64_t N,
     p.nw = dim <= 512 ? 4 : 2;
     p.gx = (unsigned)((N + p.G - 1) / p.G);
     p.gy = owned ? 1u : (unsigned)((B + p.QB - 1) / p.QB);
-    p.lds = f.layout(dim, T, p.QB, p.G, p.nw, owned).total;
+    p.lds = f.layout(dim, T, p.QB, p.G, p.nw, owned, listed).total;
     return p;
 }
 
 // The work buffer: the clamped offsets (per-pair maxima never leave LDS); behind them, when Q arrives in fp32 and D does not
-// hold fp32, Q in D's format and -- a scaled format -- its scales.
+// hold fp32, Q in D's format and -- a scaled format -- its scales.  A listed call has no offsets of its own (the kernel derives
+// them from the store's): its buffer is the converted Q alone, and 16 bytes at the least, so that it is never empty.
 struct DenseWork {
     int64_t off_bytes, q_bytes, s_bytes;
-    DenseWork(int d_type, int64_t N, int64_t B, int64_t T, int64_t dim) {
+    DenseWork(int d_type, int64_t N, int64_t B, int64_t T, int64_t dim, bool listed = false) {
         const DenseFormat& f = format_of(d_type);
         const int64_t bt = std::max<int64_t>(B, 0) * std::max<int64_t>(T, 0);
-        off_bytes = align256((int64_t)sizeof(int64_t) * (std::max<int64_t>(N, 0) + 1));
+        off_bytes = listed ? 0 : align256((int64_t)sizeof(int64_t) * (std::max<int64_t>(N, 0) + 1));
         const int d = (int)std::min<int64_t>(std::max<int64_t>(dim, 0), 1 << 24);   // the formats size by int; a dim past 2^24 is unserved whatever this returns
         q_bytes = d_type == CLB_F32 ? 0 : align256(f.q_bytes(d) * bt);
         s_bytes = f.has_scales ? align256(f.scale_bytes(d) * bt) : 0;
     }
-    int64_t total() const { return off_bytes + q_bytes + s_bytes; }
+    int64_t total() const { return std::max<int64_t>(off_bytes + q_bytes + s_bytes, 16); }
 };
 
 // What a host call checks before it uploads anything: the doclens against n_D, the owners against the batch.
@@ -151,7 +164,7 @@ int run_dense_device(int device, const DenseCall& c) {
     const DenseFormat& f = format_of(c.d_type);
     const bool q_f32 = c.q_type == CLB_F32, fp32 = c.d_type == CLB_F32;
     if (c.N == 0) return CLB_OK;
-    if (!c.Q || !c.doclens || !c.scores || !c.work || ((!c.D || (f.has_scales && !c.dscale)) && c.n_D > 0) || (f.has_scales && !q_f32 && !c.qscale))
+    if (!c.Q || !c.doclens || (c.listed && !c.pids) || !c.scores || !c.work || ((!c.D || (f.has_scales && !c.dscale)) && c.n_D > 0) || (f.has_scales && !q_f32 && !c.qscale))
         return fail(CLB_EARGUMENT, "%s: null argument", c.who);
     if (fp32) {                                             // fp32 queries are read in dwords, the work buffer holds offsets only
         if ((uintptr_t)c.D % 16 || (uintptr_t)c.work % 8)
@@ -161,12 +174,12 @@ int run_dense_device(int device, const DenseCall& c) {
     } else if (f.has_scales && !f.scaled && f.scale_bytes((int)c.dim) % 4 == 0 && (uintptr_t)c.dscale % 4) {
         return fail(CLB_EARGUMENT, "%s: the passages' scale bytes must be 4-byte aligned when dim %% 128 == 0", c.who);
     }
-    const DenseWork wk(c.d_type, c.N, c.B, c.T, c.dim);
+    const DenseWork wk(c.d_type, c.N, c.B, c.T, c.dim, c.listed);
     if (c.work_bytes < wk.total())
         return fail(CLB_EARGUMENT, "%s: work buffer of %lld bytes, clb_%s_work_bytes asks for %lld", c.who, (long long)c.work_bytes, c.who,
                     (long long)wk.total());
     const int dim = (int)c.dim, T = (int)c.T;
-    const DensePlan p = plan_dense(f, dim, T, c.B, c.N, c.owner != nullptr);
+    const DensePlan p = plan_dense(f, dim, T, c.B, c.N, c.owner != nullptr, c.listed);
     if (p.gy > 65535u || (c.N + p.G - 1) / p.G > 0x7fffffffLL)
         return fail(CLB_EUNSUPPORTED, "%s: B = %lld, N = %lld exceed one launch", c.who, (long long)c.B, (long long)c.N);
     CLB_TRY(use_device(device));
@@ -178,17 +191,25 @@ int run_dense_device(int device, const DenseCall& c) {
     // quantises Q before the offsets (an MX family's query is MXFP8 whatever D holds), a 16-bit format rounds it after them.
     if (convert && f.has_scales)
         launch_quantize(f.scaled ? CLB_I8 : CLB_MXFP8, reinterpret_cast<const float*>(c.Q), dim, c.B * c.T, d_qf, d_qs, c.st);
-    hipLaunchKernelGGL(dense_offsets_kernel, dim3(1), dim3(1024), 0, c.st, c.doclens, c.N, c.n_D, d_off);
+    if (!c.listed) hipLaunchKernelGGL(dense_offsets_kernel, dim3(1), dim3(1024), 0, c.st, c.doclens, c.N, c.n_D, d_off);
     if (convert && !f.has_scales) {                         // Q~ = Q rounded to nearest-even
         const int64_t n8 = c.B * c.T * c.dim / 8;
         hipLaunchKernelGGL(c.d_type == CLB_F16 ? dense_round_kernel<DenseF16> : dense_round_kernel<DenseBF16>,
                            dim3((unsigned)std::min<int64_t>((n8 + 255) / 256, 4096)), dim3(256), 0, c.st, (const float4*)c.Q, n8, (dense_u32x4*)d_qf);
     }
-    const DenseKernel kern = dim == 128 ? f.k128 : f.kany;
-    if (p.lds > 64 * 1024) allow_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024);
-    hipLaunchKernelGGL(kern, dim3(p.gx, p.gy), dim3(64 * p.nw), p.lds, c.st, convert ? (const void*)d_qf : c.Q,
-                       convert && f.has_scales ? (const void*)d_qs : c.qscale, dim, T, (int)c.B, c.D, c.dscale, (const int64_t*)d_off, c.N, c.owner,
-                       p.G, p.QB, c.scores);
+    const void* q = convert ? (const void*)d_qf : c.Q;
+    const void* qs = convert && f.has_scales ? (const void*)d_qs : c.qscale;
+    if (c.listed) {                                         // the store's own offsets: no scan, this is the call's only other launch
+        const DenseStoreKernel kern = dim == 128 ? f.s128 : f.sany;
+        if (p.lds > 64 * 1024) allow_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024);
+        hipLaunchKernelGGL(kern, dim3(p.gx, p.gy), dim3(64 * p.nw), p.lds, c.st, q, qs, dim, T, (int)c.B, c.D, c.dscale, c.doclens, c.N, c.owner,
+                           p.G, p.QB, c.scores, DenseStore{c.pids, c.P, c.n_D});
+    } else {
+        const DenseKernel kern = dim == 128 ? f.k128 : f.kany;
+        if (p.lds > 64 * 1024) allow_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024);
+        hipLaunchKernelGGL(kern, dim3(p.gx, p.gy), dim3(64 * p.nw), p.lds, c.st, q, qs, dim, T, (int)c.B, c.D, c.dscale, (const int64_t*)d_off, c.N,
+                           c.owner, p.G, p.QB, c.scores);
+    }
     CLB_HIP(hipGetLastError());
     return CLB_OK;
 }
@@ -295,6 +316,24 @@ int clb_maxsim_batch_mx(int device, const void* Q, int q_type, const uint8_t* qs
                         const uint8_t* dscale, int format, int64_t n_D, const int64_t* doclens, int64_t N, const int32_t* owner,
                         float* scores) {
     return run_dense_host(device, {"maxsim_batch_mx", CLB_MXFP8, q_type, format, Q, qscale, D, dscale, dim, T, B, n_D, N, doclens, owner, scores});
+}
+
+// The listed call: one entry point for the six formats, the family being what the contiguous call of d_type belongs to.
+static int family_of(int d_type) { return d_type == CLB_BF16 ? CLB_F16 : d_type == CLB_MXFP4 ? CLB_MXFP8 : d_type; }
+
+int64_t clb_maxsim_store_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim, int d_type) {
+    return DenseWork(d_type < CLB_F32 || d_type > CLB_MXFP4 ? CLB_F32 : d_type, N, B, T, dim, true).total();
+}
+
+int clb_maxsim_store_device(int device, const void* d_Q, int q_type, const void* d_qscale, int64_t dim, int64_t T, int64_t B,
+                            const void* d_store, const void* d_store_scale, int d_type, int64_t n_rows, const int64_t* d_store_off,
+                            int64_t P, const int64_t* d_pids, int64_t N, const int32_t* d_owner, float* d_scores, void* d_work,
+                            int64_t work_bytes, void* hip_stream) {
+    if (d_type < CLB_F32 || d_type > CLB_MXFP4) return fail(CLB_EUNSUPPORTED, "maxsim_store serves d_type CLB_F32 .. CLB_MXFP4 (d_type = %d)", d_type);
+    DenseCall c{"maxsim_store", family_of(d_type), q_type, d_type, d_Q, d_qscale, d_store, d_store_scale, dim, T, B, n_rows, N, d_store_off,
+                d_owner, d_scores, d_work, work_bytes, (hipStream_t)hip_stream};
+    c.listed = true, c.pids = d_pids, c.P = P;
+    return run_dense_device(device, c);
 }
 
 static int check_mx_format(int format) {

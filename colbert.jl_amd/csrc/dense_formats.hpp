@@ -83,6 +83,13 @@
 // token) is what the all-pairs form spends its issue slots on (read from the code; DESIGN 4.2a says what was considered).
 // Quantiser (dense_quantize_mx_kernel): plain integer / exact-fp32 code, not the hardware converts -- their saturation and
 // subnormal rounding were not measured against the numpy statement, and the integer form is the same code on host and device.
+//
+// Listed variant (dense_maxsim_kernel<F, KB, DenseStore>: passages by id in a resident store).  kShiftAt: where the head keeps the
+// entries' 16 x 8 store shifts -- behind s_own in the 1 KB heads; the 1280-byte heads have no room, so kListedHeadExtra = 128 more
+// bytes, for this variant only.  Registers, same flags (VGPRs / SGPRs in lanes / waves per SIMD; no AGPRs, no scratch, no VGPR
+// spills anywhere): fp32 KB = 32: 66 / 0 / 7, KB = 0: 29 / 0 / 8; fp16 and bf16 KB = 4: 108 / 3 / 4, KB = 0: 40 / 0 / 8; int8 KB = 2:
+// 105 / 25 / 4, KB = 0: 71 / 11 / 7; MXFP8 KB = 1: 101 / 37 / 4, KB = 0: 83 / 14 / 5; MXFP4 KB = 1: 85 / 38 / 5, KB = 0: 79 / 14 / 6 --
+// no occupancy below its unlisted twin's, whose figures (int8 KB = 0 today: 73 VGPRs, 13 in lanes, 6 waves) did not move.
 #pragma once
 #include "dense_kernels.hpp"
 
@@ -108,7 +115,7 @@ struct DensePlain {
 
 struct DenseF32 : DensePlain<float, 4> {
     typedef dense_f32x4 Acc;
-    static constexpr int kK = 4, kRowTiles = 1, kHeadBytes = 1024, kOwnAt = 768, kRowpAt = 256;
+    static constexpr int kK = 4, kRowTiles = 1, kHeadBytes = 1024, kOwnAt = 768, kRowpAt = 256, kShiftAt = 832, kListedHeadExtra = 0;
     static constexpr bool kResident = false, kScaled = false, kHasScales = false;
     __host__ __device__ static int scale_bytes(int) { return 0; }
     __host__ __device__ static int row_stride(int dim) { return 4 * (dim + (68 - dim % 64) % 64); }   // = 4 mod 64 floats
@@ -125,7 +132,7 @@ struct Dense16ByteFrag {
 // The two 16-bit formats: the MFMA that multiplies them and the round-to-nearest-even from fp32 (NaN stays a quiet NaN).
 struct Dense16Bit : Dense16ByteFrag, DensePlain<dense_u32x4, 2> {
     typedef dense_f32x4 Acc;
-    static constexpr int kK = 32, kRowTiles = 2, kHeadBytes = 1024, kOwnAt = 768, kRowpAt = 256;
+    static constexpr int kK = 32, kRowTiles = 2, kHeadBytes = 1024, kOwnAt = 768, kRowpAt = 256, kShiftAt = 832, kListedHeadExtra = 0;
     static constexpr bool kScaled = false, kHasScales = false;
     __host__ __device__ static int scale_bytes(int) { return 0; }
     __host__ __device__ static int row_stride(int dim) { return padded(2 * dim); }
@@ -152,7 +159,7 @@ struct DenseBF16 : Dense16Bit {
 
 struct DenseI8 : Dense16ByteFrag, DensePlain<dense_i32x4, 1> {
     typedef dense_i32x4 Acc;
-    static constexpr int kK = 64, kRowTiles = 4, kHeadBytes = 1280, kOwnAt = 192, kRowpAt = 256;
+    static constexpr int kK = 64, kRowTiles = 4, kHeadBytes = 1280, kOwnAt = 192, kRowpAt = 256, kShiftAt = 1280, kListedHeadExtra = 128;
     static constexpr bool kScaled = true, kHasScales = true;
     __host__ __device__ static int scale_bytes(int) { return 4; }
     __host__ __device__ static int row_stride(int dim) { return padded(dim); }
@@ -177,7 +184,7 @@ struct DenseMX : Dense16ByteFrag {
     typedef DenseMXFrag<2> QFrag;
     typedef dense_f32x4 Acc;
     typedef int v8 __attribute__((ext_vector_type(8)));
-    static constexpr int kK = 128, kRowTiles = 4, kHeadBytes = 1280, kOwnAt = 192, kRowpAt = 256, kDimMultiple = 32;
+    static constexpr int kK = 128, kRowTiles = 4, kHeadBytes = 1280, kOwnAt = 192, kRowpAt = 256, kShiftAt = 1280, kListedHeadExtra = 128, kDimMultiple = 32;
     static constexpr int kFragBytes = E2M1 ? 16 : 32, kQFragBytes = 32, kLaneBytes = 16;
     static constexpr bool kScaled = false, kHasScales = true;     // no fp32 scale, no epilogue multiply: the scales are in the product
     __host__ __device__ static int row_bytes(int dim) { return E2M1 ? dim >> 1 : dim; }

@@ -47,18 +47,19 @@ constexpr int kDenseWholeRow = 1 << 30;    // "bytes left in the row" where the 
 
 // The dynamic LDS of one launch, in bytes from its start: the head (s_off at 0, 17 x 8; s_own and s_rowp where the format puts
 // them), the maxima, the step's rows at `stride` bytes each, the step's row scales (F::scale_bytes(dim) per row).  The kernel carves its
-// LDS by it and the host asks for `total`.
+// LDS by it and the host asks for `total`.  listed (the by-id variant): the head also holds the entries' 16 x 8 store shifts at
+// F::kShiftAt, F::kListedHeadExtra bytes longer where the format's own head has no room for them; the unlisted layout is untouched.
 struct DenseLayout {
     int stride, step_rows, pm_words;
     size_t pm, rows, scales, total;
 };
 template <typename F>
-__host__ __device__ inline DenseLayout dense_layout(int dim, int T, int QB, int G, int nw, bool owned) {
+__host__ __device__ inline DenseLayout dense_layout(int dim, int T, int QB, int G, int nw, bool owned, bool listed = false) {
     DenseLayout l;
     l.stride = F::row_stride(dim);
     l.step_rows = 16 * F::kRowTiles * nw;
     l.pm_words = (owned ? 1 : QB) * G * (T | 1);
-    l.pm = F::kHeadBytes;
+    l.pm = F::kHeadBytes + (listed ? F::kListedHeadExtra : 0);
     l.rows = l.pm + ((size_t)l.pm_words * 4 + 15) / 16 * 16;
     l.scales = l.rows + (size_t)l.step_rows * l.stride;     // a multiple of 16: the stride is
     l.total = l.scales + (size_t)F::scale_bytes(dim) * l.step_rows;
@@ -128,12 +129,51 @@ __device__ __forceinline__ void dense_tile_max(const dense_f32x4 acc, const int*
     }
 }
 
+// What the listed variant of the kernel takes beside the frame's arguments: the entries to score and the store's extent.
+struct DenseStore {
+    const int64_t* pids;   // [N] stored passages, 0-based; outside 0..P-1: no rows
+    int64_t P, n_store;    // stored passages (off holds P + 1 offsets) and stored rows
+};
+__device__ __forceinline__ DenseStore dense_store_of() { return DenseStore{nullptr, 0, 0}; }
+__device__ __forceinline__ DenseStore dense_store_of(DenseStore s) { return s; }
+
 // The group's offsets and owners into the LDS head and every maximum to -Inf; the barrier after it is the caller's.
+// LISTED: the group is np <= 16 entries of a pid list and `off` the STORE's offsets [P + 1].  Lane i of wave 0 reads pid i and
+// clamps its range -- a pid outside 0..P-1 is an empty range at 0; start = clamp(off[pid], 0, n_store), end = clamp(off[pid + 1],
+// start, n_store), all before any row address is formed --; the local offsets are the prefix sum of the lengths (four shuffle
+// steps, no barrier of its own), and s_shift[i] = start - s_off[i]: local row e of entry i is store row e + s_shift[i] < end.
+template <bool LISTED>
 __device__ __forceinline__ void dense_group_begin(int64_t* __restrict__ s_off, int* __restrict__ s_own, uint32_t* __restrict__ s_pm,
                                                   const int64_t* __restrict__ off, const int32_t* __restrict__ owner, int64_t p0,
-                                                  int np, int pm_words) {
+                                                  int np, int pm_words, int64_t* __restrict__ s_shift, const int64_t* __restrict__ pids,
+                                                  int64_t P, int64_t n_store) {
     const int tid = threadIdx.x, nthr = blockDim.x;
-    for (int i = tid; i <= np; i += nthr) s_off[i] = off[p0 + i];
+    if constexpr (LISTED) {
+        if (tid < 64) {
+            int64_t start = 0, len = 0;
+            if (tid < np) {
+                const int64_t pid = pids[p0 + tid];
+                if (pid >= 0 && pid < P) {
+                    const int64_t a = off[pid], b = off[pid + 1];
+                    start = a < 0 ? 0 : (a > n_store ? n_store : a);
+                    len = (b < start ? start : (b > n_store ? n_store : b)) - start;
+                }
+            }
+            int64_t incl = len;
+#pragma unroll
+            for (int d = 1; d < kDenseMaxGroup; d <<= 1) {
+                const int64_t o = __shfl_up(incl, d, 64);
+                if (tid >= d) incl += o;
+            }
+            if (tid == 0) s_off[0] = 0;
+            if (tid < np) {
+                s_off[tid + 1] = incl;
+                s_shift[tid] = start - (incl - len);
+            }
+        }
+    } else {
+        for (int i = tid; i <= np; i += nthr) s_off[i] = off[p0 + i];
+    }
     for (int i = tid; i < np; i += nthr) s_own[i] = owner ? owner[p0 + i] : 0;
     const uint32_t key_ninf = f32_order_key(kNegInf);
     for (int i = tid; i < pm_words; i += nthr) s_pm[i] = key_ninf;
@@ -232,13 +272,24 @@ __device__ __forceinline__ void dense_tiles(const typename F::Frag (*a)[KB > 0 ?
 // Q (dim, T, B) and D (dim, n_D) hold F's elements, D 16-byte aligned and Q aligned to 16 bytes or a fragment, whichever is
 // less; qscale (T, B) and dscale [n_D]: F::scale_bytes(dim) bytes per embedding (one fp32, or one byte per block of 32), read
 // by a format that has scales only.
-// grid (ceil(N / G), owned ? 1 : ceil(B / QB)); block 64 * nw; dynamic LDS = dense_layout<F>(dim, T, QB, G, nw, owned).total.
-template <typename F, int KB>
+// grid (ceil(N / G), owned ? 1 : ceil(B / QB)); block 64 * nw; dynamic LDS = dense_layout<F>(dim, T, QB, G, nw, owned, LISTED).total.
+// LISTED (a DenseStore as the last argument): D and dscale are a resident store of n_store rows, `off` its offsets [P + 1] and the N
+// passages are the entries of `pids`: a work-group owns G consecutive ENTRIES.  Its prologue turns them into local offsets
+// (dense_group_begin), so everything from the row-to-passage map on runs on local row numbers as it does unlisted; only the
+// step's load differs: local row e of entry p is store row e + s_shift[p], one row at a time -- still dense 16-byte columns, its
+// scales per row --, and since a row's entry must be known before its address the map is resolved first, behind a barrier of
+// its own (the alternative, a search of the 17 LDS offsets inside the load loop, repeats the four dependent LDS reads once per
+// 16-byte column -- 8 to 32 times a row at dim 128 -- and puts them in front of every global load; the map is needed anyway.
+// Chosen from the code; the two were not timed against each other).
+// STORE: nothing (unlisted: the kernel's arguments are those above and no more), or one DenseStore (LISTED).
+template <typename F, int KB, typename... STORE>
 static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const void* __restrict__ Qv, const void* __restrict__ qscale, int dim,
                                                                   int T, int B, const void* __restrict__ Dv,
                                                                   const void* __restrict__ dscale, const int64_t* __restrict__ off,
                                                                   int64_t N, const int32_t* __restrict__ owner, int G, int QB,
-                                                                  float* __restrict__ scores) {
+                                                                  float* __restrict__ scores, STORE... store) {
+    constexpr bool LISTED = sizeof...(STORE) > 0;
+    const DenseStore st = dense_store_of(store...);
     extern __shared__ __align__(16) unsigned char dense_smem[];
     typedef typename F::Frag Frag;
     typedef typename F::QFrag QFrag;
@@ -250,7 +301,7 @@ static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const void* __
     const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, r = lane & 15, g = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar, so that what hangs on the wave's rows is wave-uniform to the compiler
     const bool owned = owner != nullptr;
-    const DenseLayout L = dense_layout<F>(dim, T, QB, G, nthr >> 6, owned);
+    const DenseLayout L = dense_layout<F>(dim, T, QB, G, nthr >> 6, owned, LISTED);
     const int CH = L.step_rows, stride = L.stride, TP = T | 1, cols = F::row_bytes(dim) >> 4;   // rows per step; 16-byte columns per row
     const int nsb = F::scale_bytes(dim);                                         // scale bytes per embedding
     constexpr bool BS = F::kHasScales && !F::kScaled;                            // block scales inside the fragments: else no scale pointer lives
@@ -262,12 +313,13 @@ static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const void* __
     int64_t* s_off = reinterpret_cast<int64_t*>(dense_smem);
     int* s_own = reinterpret_cast<int*>(dense_smem + F::kOwnAt);
     int* s_rowp = reinterpret_cast<int*>(dense_smem + F::kRowpAt);
+    int64_t* s_shift = reinterpret_cast<int64_t*>(dense_smem + F::kShiftAt);   // (LISTED only)
     uint32_t* s_pm = reinterpret_cast<uint32_t*>(dense_smem + L.pm);
     unsigned char* s_d = dense_smem + L.rows;
     unsigned char* s_sc = dense_smem + L.scales;                                // the step's row scales, nsb bytes per row
     float* s_ds = reinterpret_cast<float*>(s_sc);                               // (a format with one fp32 scale per row)
 
-    dense_group_begin(s_off, s_own, s_pm, off, owner, p0, np, L.pm_words);
+    dense_group_begin<LISTED>(s_off, s_own, s_pm, off, owner, p0, np, L.pm_words, s_shift, st.pids, st.P, st.n_store);
     __syncthreads();
     const int64_t lo = s_off[0], hi = s_off[np];
 
@@ -283,25 +335,52 @@ static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const void* __
 
     for (int64_t c = lo; c < hi; c += CH) {
         const int n_rows = (int)(hi - c < CH ? hi - c : CH);
-        // the step's rows, dense 16-byte loads (D + c rows is 16-byte aligned), into padded LDS rows; their scales -- those of
-        // the rows read, no others -- in dwords where a row's are whole dwords (then dscale + c rows is 4-byte aligned)
-        const col16* src = reinterpret_cast<const col16*>(D + c * F::row_bytes(dim));
-        for (int i = tid; i < n_rows * cols; i += nthr) {
-            const int row = i / cols, col = i - row * cols;
-            *reinterpret_cast<col16*>(s_d + row * stride + 16 * col) = src[i];
-        }
-        if constexpr (F::kHasScales) {
-            const unsigned char* ssrc = static_cast<const unsigned char*>(dscale) + c * nsb;
-            if (nsb % 4 == 0) {
-                for (int i = tid; i < n_rows * (nsb >> 2); i += nthr) reinterpret_cast<uint32_t*>(s_sc)[i] = reinterpret_cast<const uint32_t*>(ssrc)[i];
-            } else {
-                for (int i = tid; i < n_rows * nsb; i += nthr) s_sc[i] = ssrc[i];
+        if constexpr (LISTED) {
+            // every row's entry first, then the row from where the store keeps it: 16-byte columns of one row are consecutive,
+            // rows are not; its scales per row, in dwords where a row's are whole dwords, no row's but those read
+            dense_step_passages(s_off, s_rowp, c, n_rows, CH, np);
+            __syncthreads();
+            auto store_row = [&](int row) { return c + row + s_shift[s_rowp[row]]; };
+            for (int i = tid; i < n_rows * cols; i += nthr) {
+                const int row = i / cols, col = i - row * cols;
+                *reinterpret_cast<col16*>(s_d + row * stride + 16 * col) = reinterpret_cast<const col16*>(D + store_row(row) * F::row_bytes(dim))[col];
             }
+            if constexpr (F::kHasScales) {
+                const unsigned char* ssrc = static_cast<const unsigned char*>(dscale);
+                if (nsb % 4 == 0) {
+                    const int nsw = nsb >> 2;
+                    for (int i = tid; i < n_rows * nsw; i += nthr) {
+                        const int row = i / nsw;
+                        reinterpret_cast<uint32_t*>(s_sc)[i] = reinterpret_cast<const uint32_t*>(ssrc + store_row(row) * nsb)[i - row * nsw];
+                    }
+                } else {
+                    for (int i = tid; i < n_rows * nsb; i += nthr) {
+                        const int row = i / nsb;
+                        s_sc[i] = ssrc[store_row(row) * nsb + (i - row * nsb)];
+                    }
+                }
+            }
+        } else {
+            // the step's rows, dense 16-byte loads (D + c rows is 16-byte aligned), into padded LDS rows; their scales -- those of
+            // the rows read, no others -- in dwords where a row's are whole dwords (then dscale + c rows is 4-byte aligned)
+            const col16* src = reinterpret_cast<const col16*>(D + c * F::row_bytes(dim));
+            for (int i = tid; i < n_rows * cols; i += nthr) {
+                const int row = i / cols, col = i - row * cols;
+                *reinterpret_cast<col16*>(s_d + row * stride + 16 * col) = src[i];
+            }
+            if constexpr (F::kHasScales) {
+                const unsigned char* ssrc = static_cast<const unsigned char*>(dscale) + c * nsb;
+                if (nsb % 4 == 0) {
+                    for (int i = tid; i < n_rows * (nsb >> 2); i += nthr) reinterpret_cast<uint32_t*>(s_sc)[i] = reinterpret_cast<const uint32_t*>(ssrc)[i];
+                } else {
+                    for (int i = tid; i < n_rows * nsb; i += nthr) s_sc[i] = ssrc[i];
+                }
+            }
+            dense_step_passages(s_off, s_rowp, c, n_rows, CH, np);
         }
-        dense_step_passages(s_off, s_rowp, c, n_rows, CH, np);
         __syncthreads();
 
-        const int rb = WR * w;                              // this wave's rows of the step: RT tiles of 16
+        const int rb = WR * w;                             // this wave's rows of the step: RT tiles of 16
         if (rb < n_rows) {
             const int* rowp = s_rowp + rb;
             const unsigned char* arow = s_d + (rb + r) * stride + F::kLaneBytes * g;   // this lane's share of its row of tile 0, and its scale byte

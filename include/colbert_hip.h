@@ -945,6 +945,32 @@ int clb_maxsim_batch_mx_device(int device, const void* d_Q, int q_type, const ui
 int clb_maxsim_batch_mx(int device, const void* Q, int q_type, const uint8_t* qscale, int64_t dim, int64_t T, int64_t B,
                         const uint8_t* D, const uint8_t* dscale, int format, int64_t n_D, const int64_t* doclens, int64_t N,
                         const int32_t* owner, float* scores);
+/* The dense scorer BY PASSAGE ID: the listed passages' rows are read where they lie in a resident store, one entry point for the
+ * six formats.  A store is what the calls above take as D, plus row offsets:
+ *   d_store (dim, n_rows) in d_type = CLB_F32 .. CLB_MXFP4; d_store_scale its scales (CLB_I8: one fp32 per row; MX: dim / 32 bytes
+ *   per row; ignored otherwise); d_store_off int64 [P + 1]: stored passage p is the rows off[p] .. off[p + 1] - 1.
+ *   d_pids int64 [N], 0-based, in any order, repeats allowed; d_owner int32 [N] or NULL.
+ *   owned     entry j scores stored passage pids[j] against query owner[j]; d_scores [N].
+ *   all pairs every query against every entry; d_scores (N, B), N fastest.
+ * d_Q, q_type and d_qscale are the contiguous call's of d_type's format (clb_maxsim_batch_device, _half_device, _i8_device,
+ * _mx_device), with the same served type pairs, dim, T and alignments and the same codes for anything else.  Each score has exactly
+ * the bits that call gives for the same rows laid back to back: a pair's bits depend on its query and its passage only.
+ * Device arrays are not validated and bad ones do not fault; everything is clamped in the kernel before an address is formed:
+ *   a pid outside 0..P-1 scores -Inf (pad a ragged list with -1);
+ *   start = clamp(off[pid], 0, n_rows), end = clamp(off[pid + 1], start, n_rows): no row at or past n_rows is read, neither its
+ *   values nor its scales; an empty range scores -Inf;
+ *   an owner outside 0..B-1 reads no query and no query scale and scores -Inf.
+ * N = 0 is CLB_OK with nothing launched; argument errors (a null array is CLB_EARGUMENT) come before any launch.  The call is one
+ * launch -- two when Q arrives in fp32 for another format: its conversion --, stream-ordered, not waited for, allocates nothing
+ * and can be captured in a graph.  d_work: clb_maxsim_store_work_bytes bytes, 16-byte aligned -- the converted Q and its scales,
+ * no offsets; 16 bytes at the least, so it is never NULL.  There is no host-array twin: a store is resident by definition (upload
+ * the listed rows and use the contiguous host calls instead).  Not part of the Julia shim. */
+int64_t clb_maxsim_store_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim, int d_type);
+int clb_maxsim_store_device(int device, const void* d_Q, int q_type, const void* d_qscale, int64_t dim, int64_t T, int64_t B,
+                            const void* d_store, const void* d_store_scale, int d_type, int64_t n_rows,
+                            const int64_t* d_store_off, int64_t P, const int64_t* d_pids, int64_t N,
+                            const int32_t* d_owner /* NULL: all pairs */, float* d_scores,
+                            void* d_work, int64_t work_bytes, void* hip_stream);
 /* compress_into_codes!  (residual.jl:67-81) */
 int clb_compress_into_codes(int device, uint32_t* codes, int64_t n_codes, const float* centroids,
                             int64_t dim, int64_t K, const float* embs, int64_t n);
