@@ -9,6 +9,7 @@ from ._lib import (ArgumentError, BoundsError, ColBERTError, DimensionMismatch, 
                    Unsupported, build, declared_symbols, lib)
 from .codec import maxsim, maxsim_batch, maxsim_batch_device, quantize_rows, quantize_rows_device  # noqa: F401
 from .codec import dequantize_mx, quantize_mx, quantize_mx_device  # noqa: F401
+from .codec import binarize_rows, binarize_rows_device, unbinarize_rows  # noqa: F401
 from .config import ColBERTConfig  # noqa: F401
 from .encoder import BertEncoder, encoder_plan  # noqa: F401
 from .indexer import Indexer, PrecomputedEncoder, index, train  # noqa: F401

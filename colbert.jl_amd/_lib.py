@@ -273,6 +273,17 @@ def lib() -> C.CDLL:
             l.clb_maxsim_batch_i8.argtypes = [ci, vp, ci, vp, i64_, i64_, i64_, vp, vp, i64_, vp, i64_, vp, vp]
             l.clb_maxsim_batch_i8_device.restype = ci
             l.clb_maxsim_batch_i8_device.argtypes = [ci, vp, ci, vp, i64_, i64_, i64_, vp, vp, i64_, vp, i64_, vp, vp, vp, i64_, vp]
+        if hasattr(l, "clb_maxsim_batch_b1"):                 # (likewise)
+            l.clb_binarize_rows.restype = ci
+            l.clb_binarize_rows.argtypes = [ci, vp, i64_, i64_, vp, vp]
+            l.clb_binarize_rows_device.restype = ci
+            l.clb_binarize_rows_device.argtypes = [ci, vp, i64_, i64_, vp, vp, vp]
+            l.clb_maxsim_batch_b1_work_bytes.restype = i64_
+            l.clb_maxsim_batch_b1_work_bytes.argtypes = [i64_, i64_, i64_, i64_]
+            l.clb_maxsim_batch_b1.restype = ci
+            l.clb_maxsim_batch_b1.argtypes = [ci, vp, ci, vp, i64_, i64_, i64_, vp, vp, i64_, vp, i64_, vp, vp]
+            l.clb_maxsim_batch_b1_device.restype = ci
+            l.clb_maxsim_batch_b1_device.argtypes = [ci, vp, ci, vp, i64_, i64_, i64_, vp, vp, i64_, vp, i64_, vp, vp, vp, i64_, vp]
         if hasattr(l, "clb_maxsim_store_device"):             # (likewise)
             l.clb_maxsim_store_work_bytes.restype = i64_
             l.clb_maxsim_store_work_bytes.argtypes = [i64_, i64_, i64_, i64_, ci]

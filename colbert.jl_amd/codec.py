@@ -146,6 +146,48 @@ def _int8_pair(a, what):
     return v, np.ascontiguousarray(s.ravel(order="F"))
 
 
+B1 = 16                                                        # CLB_B1
+
+
+def binarize_rows(X):
+    """One sign bit per dimension and one scale per embedding, the statement of the 1-bit format (include/colbert_hip.h): X (dim, ...)
+    float32, dim % 128 == 0 -> (values uint8 (dim / 8, ...): bit k & 7 of byte k >> 3 is x_k >= 0, so -0.0 gives 1; scale float32 of
+    X.shape[1:]: the float64 mean of |x|, rounded once).  A non-finite value is an ArgumentError naming the embedding; a dim that is
+    no multiple of 128 is Unsupported."""
+    from ._lib import ArgumentError, Unsupported
+    x = colmajor(X, np.float32)
+    dim = x.shape[0]
+    if dim % 128 or not 128 <= dim <= 1024:
+        raise Unsupported(f"binarize_rows serves dim % 128 == 0, 128 <= dim <= 1024 (dim = {dim})")
+    bad = ~np.isfinite(x).all(axis=0)
+    if bad.any():
+        raise ArgumentError(f"binarize_rows: embedding {int(np.flatnonzero(bad.ravel(order='F'))[0])} holds a non-finite value")
+    s = np.abs(x).astype(np.float64).mean(axis=0).astype(np.float32)
+    return np.asfortranarray(np.packbits(x >= 0, axis=0, bitorder="little")), s
+
+
+def unbinarize_rows(values, scales):
+    """The float32 embeddings a 1-bit pair stands for: s (2 bit - 1)"""
+    v, s = colmajor(values, np.uint8), np.asarray(scales, dtype=np.float32)
+    if v.shape[1:] != s.shape:
+        raise ValueError("one scale per embedding")
+    signs = np.unpackbits(v, axis=0, bitorder="little").astype(np.float32) * np.float32(2) - np.float32(1)
+    return np.asfortranarray(signs * s[None])
+
+
+def _b1_pair(a, what):
+    """(bits uint8 column-major, scales float32) of passages given as floats (binarised here) or as a (values uint8, scales) pair"""
+    if isinstance(a, tuple):
+        if getattr(a[0], "dtype", None) != np.uint8:
+            raise ValueError(f"{what}: a 1-bit operand is a (values uint8, scales float32) pair")
+        v, s = colmajor(a[0], np.uint8), np.ascontiguousarray(np.asarray(a[1], dtype=np.float32).ravel(order="F"))
+        if s.size != v.size // max(v.shape[0], 1):
+            raise ValueError(f"{what}: one scale per embedding")
+        return v, s
+    v, s = binarize_rows(a)
+    return v, np.ascontiguousarray(s.ravel(order="F"))
+
+
 MXFP8, MXFP4 = 4, 5                                            # CLB_MXFP8 / CLB_MXFP4
 _MX = {"mxfp8": (MXFP8, 3, -6, 7, 448.0, 8), "mxfp4": (MXFP4, 1, 0, 1, 6.0, 2)}    # code, mantissa bits, emin, bias, max, emax
 
@@ -261,6 +303,26 @@ def quantize_rows_device(d_X, out=None, stream=None):
     return x8, s
 
 
+def binarize_rows_device(d_X, out=None, stream=None):
+    """`binarize_rows` on the device (clb_binarize_rows_device): d_X float32 (..., dim), contiguous, dim % 128 == 0 -> (uint8 bits
+    (..., dim / 8), float32 scales of its leading shape; the scale is summed in fp32, so it lies within (dim + 1) 2^-24 of the host's).
+    `out`: that pair, preallocated.  Stream-ordered, not waited for; it cannot report a non-finite value (defined, meaningless numbers)."""
+    import torch
+    x = _dev_rows(d_X, torch.float32)
+    if x.dim() < 2:
+        raise ValueError("d_X must be (..., dim)")
+    dim, lead = int(x.shape[-1]), tuple(x.shape[:-1])
+    v, s = out if out is not None else (torch.empty(lead + (dim // 8,), dtype=torch.uint8, device=x.device),
+                                        torch.empty(lead, dtype=torch.float32, device=x.device))
+    _dev_rows(v, torch.uint8); _dev_rows(s, torch.float32)
+    if v.numel() * 8 != x.numel() or s.numel() * dim != x.numel():
+        raise ValueError("out: one bit per element and one float32 scale per embedding")
+    st = torch.cuda.current_stream(x.device).cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+    check(lib().clb_binarize_rows_device(x.device.index, C.c_void_p(x.data_ptr()), i64(dim), i64(s.numel()),
+                                         C.c_void_p(v.data_ptr()), C.c_void_p(s.data_ptr()), C.c_void_p(st)))
+    return v, s
+
+
 def maxsim_batch(Q, D, doclens, owner=None, device: int = 0, dtype=None):
     """maxsim (ranking.jl:69-86) of N un-indexed passages for a batch of queries in one call (clb_maxsim_batch): Q (dim, T, B),
     D (dim, n) -- the passages' embeddings back to back --, doclens [N].  `owner` [N], 0-based: passage j is scored against
@@ -273,7 +335,10 @@ def maxsim_batch(Q, D, doclens, owner=None, device: int = 0, dtype=None):
     quantised per embedding by `quantize_rows` and scored by the integer-MFMA kernel (clb_maxsim_batch_i8): exact integer dots,
     each score bit-identical to the restatement in include/colbert_hip.h; its distance from the fp32 score is the format's.
     dtype="mxfp8" / "mxfp4": MX block-scaled embeddings scored by the scaled-MFMA kernel (clb_maxsim_batch_mx).  Float operands
-    are quantised by `quantize_mx` (Q always as "mxfp8", D as `dtype`); a `(values uint8, scales uint8)` pair is used as it is."""
+    are quantised by `quantize_mx` (Q always as "mxfp8", D as `dtype`); a `(values uint8, scales uint8)` pair is used as it is.
+    dtype="binary": passages as one sign bit per dimension with one scale each, queries in int8 (clb_maxsim_batch_b1): a float Q is
+    quantised by `quantize_rows`, a float D by `binarize_rows`; a `(values uint8, scales float32)` pair for D and an int8 pair for Q
+    are used as they are.  Exact integer dots: each score bit-identical to the restatement in include/colbert_hip.h."""
     if dtype in _MX:
         (q, qs), (d, ds) = _mx_pair(Q, "Q", "mxfp8"), _mx_pair(D, "D", dtype)
         if q.ndim != 3 or qs.shape != (q.shape[0] // 32,) + q.shape[1:]:
@@ -290,16 +355,17 @@ def maxsim_batch(Q, D, doclens, owner=None, device: int = 0, dtype=None):
         check(lib().clb_maxsim_batch_mx(device, fptr(q), MXFP8, fptr(qs), i64(dim), i64(T), i64(B), fptr(d), fptr(ds), _MX[dtype][0], i64(n),
                                         fptr(dl), i64(dl.size), fptr(ow) if ow is not None else None, fptr(scores)))
         return scores
-    int8 = dtype == "int8" or isinstance(Q, tuple) or isinstance(D, tuple) or (dtype is None and getattr(D, "dtype", None) == np.int8)
+    binary = dtype == "binary"
+    int8 = binary or dtype == "int8" or isinstance(Q, tuple) or isinstance(D, tuple) or (dtype is None and getattr(D, "dtype", None) == np.int8)
     if int8:
-        if dtype not in (None, "int8"):
+        if dtype not in (None, "int8", "binary"):
             raise ValueError("int8 operands take dtype None or 'int8'")
-        (q, qs), (d, ds) = _int8_pair(Q, "Q"), _int8_pair(D, "D")
+        (q, qs), (d, ds) = _int8_pair(Q, "Q"), (_b1_pair if binary else _int8_pair)(D, "D")
     else:
         if dtype is None and getattr(D, "dtype", None) == np.float16:
             dtype = "float16"
         if dtype not in (None, "float16", "bfloat16"):
-            raise ValueError("dtype must be None, 'float16', 'bfloat16', 'int8', 'mxfp8' or 'mxfp4'")
+            raise ValueError("dtype must be None, 'float16', 'bfloat16', 'int8', 'binary', 'mxfp8' or 'mxfp4'")
         q, d = (colmajor(Q, np.float32), colmajor(D, np.float32)) if dtype is None else (_host_16bit(Q, dtype), _host_16bit(D, dtype))
     if q.ndim != 3:
         raise ValueError("Q must be (dim, T, B)")
@@ -312,7 +378,7 @@ def maxsim_batch(Q, D, doclens, owner=None, device: int = 0, dtype=None):
     shape = (i64(dim), i64(T), i64(B))
     tail = (i64(d.shape[1] if d.ndim == 2 else 0), fptr(dl), i64(dl.size), fptr(ow) if ow is not None else None, fptr(scores))
     if int8:
-        check(lib().clb_maxsim_batch_i8(device, fptr(q), I8, fptr(qs), *shape, fptr(d), fptr(ds), *tail))
+        check((lib().clb_maxsim_batch_b1 if binary else lib().clb_maxsim_batch_i8)(device, fptr(q), I8, fptr(qs), *shape, fptr(d), fptr(ds), *tail))
     elif dtype is None:
         check(lib().clb_maxsim_batch(device, fptr(q), *shape, fptr(d), *tail))
     else:
@@ -334,6 +400,9 @@ def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, st
     An int8 d_D with `d_scale` (float32, one per embedding: what `quantize_rows_device` returns) takes the integer kernel
     (clb_maxsim_batch_i8_device): d_Q float32 (quantised on the device) or int8 with `q_scale` (B, T); `work`
     clb_maxsim_batch_i8_work_bytes long.  Any other mix of int8 operands and scales is a ValueError.
+    A uint8 d_D (n, dim / 8) with a float32 `d_scale` is a 1-bit pair (what `binarize_rows_device` returns) and takes the same integer
+    MFMA on bits widened in registers (clb_maxsim_batch_b1_device): d_Q float32 or int8 with `q_scale`, as for int8; `work`
+    clb_maxsim_batch_b1_work_bytes long.  The dtype of `d_scale` chooses between 1-bit and MX.
     A uint8 d_D with a uint8 `d_scale` (n, dim / 32) is an MX pair (what `quantize_mx_device` returns) and takes the scaled-MFMA
     kernel (clb_maxsim_batch_mx_device): d_D (n, dim) is MXFP8, (n, dim / 2) MXFP4; d_Q float32 (quantised to MXFP8 on the device) or
     uint8 with a uint8 `q_scale` (B, T, dim / 32); `work` clb_maxsim_batch_mx_work_bytes long.  Any other mix is a ValueError.
@@ -347,12 +416,13 @@ def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, st
         if pids is None or store_offsets is None or d_doclens is not None:
             raise ValueError("pids and store_offsets go together, and d_doclens must be None with them")
         return _maxsim_store_device(d_Q, d_D, pids, store_offsets, owner, out, work, stream, d_scale, q_scale)
-    if torch.uint8 in (d_D.dtype, d_Q.dtype) or torch.uint8 in (getattr(d_scale, "dtype", None), getattr(q_scale, "dtype", None)):
+    b1 = d_D.dtype == torch.uint8 and getattr(d_scale, "dtype", None) == torch.float32
+    if not b1 and (torch.uint8 in (d_D.dtype, d_Q.dtype) or torch.uint8 in (getattr(d_scale, "dtype", None), getattr(q_scale, "dtype", None))):
         return _maxsim_batch_mx_device(d_Q, d_D, d_doclens, owner, out, work, stream, d_scale, q_scale)
-    int8 = torch.int8 in (d_D.dtype, d_Q.dtype) or d_scale is not None or q_scale is not None
+    int8 = b1 or torch.int8 in (d_D.dtype, d_Q.dtype) or d_scale is not None or q_scale is not None
     half = None if int8 else {torch.float16: F16, torch.bfloat16: BF16}.get(d_D.dtype)
     if int8:
-        if d_D.dtype != torch.int8 or d_scale is None:
+        if (d_D.dtype != torch.int8 and not b1) or d_scale is None:
             raise ValueError("int8 scoring takes an int8 d_D with d_scale, one float32 scale per embedding")
         if (d_Q.dtype == torch.int8) != (q_scale is not None) or d_Q.dtype not in (torch.int8, torch.float32):
             raise ValueError("d_Q must be float32 (quantised on the device) or int8 with q_scale")
@@ -362,8 +432,8 @@ def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, st
     q, d, dl = _dev_rows(d_Q, plain), _dev_rows(d_D, plain), _dev_rows(d_doclens, torch.int64)
     ds = _dev_rows(d_scale, torch.float32) if int8 else None
     qs = None if q_scale is None else _dev_rows(q_scale, torch.float32)
-    if q.dim() != 3 or d.dim() != 2 or d.shape[1] != q.shape[2]:
-        raise ValueError("d_Q must be (B, T, dim) and d_D (n, dim)")
+    if q.dim() != 3 or d.dim() != 2 or d.shape[1] * (8 if b1 else 1) != q.shape[2]:
+        raise ValueError("d_Q must be (B, T, dim) and d_D (n, dim), 1-bit rows (n, dim / 8)")
     B, T, dim = (int(x) for x in q.shape)
     N = int(dl.numel())
     if int8 and (ds.numel() != d.shape[0] or (qs is not None and qs.numel() != B * T)):
@@ -374,7 +444,10 @@ def maxsim_batch_device(d_Q, d_D, d_doclens, owner=None, out=None, work=None, st
     ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())      # noqa: E731
     shape, sizes = (i64(dim), i64(T), i64(B)), (i64(N), i64(B), i64(T))
     q_type = F32 if q.dtype == torch.float32 else (I8 if int8 else half)
-    if int8:
+    if b1:
+        entry, work_bytes = lib().clb_maxsim_batch_b1_device, lambda: lib().clb_maxsim_batch_b1_work_bytes(*sizes, i64(dim))
+        operands = (ptr(q), q_type, ptr(qs), *shape, ptr(d), ptr(ds))
+    elif int8:
         entry, work_bytes = lib().clb_maxsim_batch_i8_device, lambda: lib().clb_maxsim_batch_i8_work_bytes(*sizes, i64(dim))
         operands = (ptr(q), q_type, ptr(qs), *shape, ptr(d), ptr(ds))
     elif half is not None:
@@ -431,22 +504,23 @@ def _maxsim_batch_mx_device(d_Q, d_D, d_doclens, owner, out, work, stream, d_sca
 
 
 def _maxsim_store_device(d_Q, d_D, pids, store_offsets, owner, out, work, stream, d_scale, q_scale):
-    """maxsim_batch_device by passage id: the store's format from d_D's dtype and the scales' (one entry point for all six)"""
+    """maxsim_batch_device by passage id: the store's format from d_D's dtype and the scales' (one entry point for all seven)"""
     import torch
     q, d = _dev_rows(d_Q), _dev_rows(d_D)
     pid, off = _dev_rows(pids, torch.int64), _dev_rows(store_offsets, torch.int64)
     if q.dim() != 3 or d.dim() != 2 or off.numel() < 1:
         raise ValueError("d_Q must be (B, T, dim), d_D (n, dim) and store_offsets (P + 1,)")
     B, T, dim = (int(x) for x in q.shape)
-    mx = d.dtype == torch.uint8
-    if d.shape[1] not in ((dim, dim // 2) if mx else (dim,)):
-        raise ValueError("d_D must be (n, dim); an MXFP4 store (n, dim / 2)")
+    b1 = d.dtype == torch.uint8 and getattr(d_scale, "dtype", None) == torch.float32      # the scales' dtype tells 1-bit rows from MX
+    mx = d.dtype == torch.uint8 and not b1
+    if d.shape[1] not in ((dim // 8,) if b1 else (dim, dim // 2) if mx else (dim,)):
+        raise ValueError("d_D must be (n, dim); an MXFP4 store (n, dim / 2), a 1-bit store (n, dim / 8)")
     types = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16, torch.int8: I8, torch.uint8: MXFP8}
     if d.dtype not in types or q.dtype not in types:
         raise ValueError(f"no dense format for d_D {d.dtype} and d_Q {q.dtype}")
-    d_type = MXFP4 if mx and d.shape[1] != dim else types[d.dtype]
-    # the scales each operand's dtype asks for: one float32 per embedding (int8), one uint8 per block of 32 (MX), else none
-    want = {torch.int8: (torch.float32, 1), torch.uint8: (torch.uint8, dim // 32)}
+    d_type = B1 if b1 else MXFP4 if mx and d.shape[1] != dim else types[d.dtype]
+    # the scales each operand's dtype asks for: one float32 per embedding (int8, 1-bit), one uint8 per block of 32 (MX), else none
+    want = {torch.int8: (torch.float32, 1), torch.uint8: (torch.float32, 1) if b1 else (torch.uint8, dim // 32)}
     scales = []
     for name, t, s, rows in (("d_scale", d, d_scale, int(d.shape[0])), ("q_scale", q, q_scale, B * T)):
         dt, per = want.get(t.dtype, (None, 0))

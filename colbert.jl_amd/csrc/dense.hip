@@ -1,9 +1,10 @@
 // dense.hip -- MaxSim of un-indexed passages for a query batch (include/colbert_hip.h: clb_maxsim_batch*): the scorer between
-// the encoder's device outputs, with no index and no handle.  One kernel frame (dense_kernels.hpp) for six embedding formats
+// the encoder's device outputs, with no index and no handle.  One kernel frame (dense_kernels.hpp) for seven embedding formats
 // (dense_formats.hpp): fp32 (clb_maxsim_batch*, the oracle's bits), fp16 / bf16 (clb_maxsim_batch_half*), int8 with one scale
 // each (clb_maxsim_batch_i8*, clb_quantize_rows*), MXFP8 / MXFP4 with one scale byte per block of 32 (clb_maxsim_batch_mx*,
-// clb_quantize_mx*); one device path and one host-array path behind the eight entry points, and the same device path behind
-// clb_maxsim_store_device, which scores passages listed by id where they lie in a resident store (any of the six formats).
+// clb_quantize_mx*), one sign bit per dimension with one scale each against int8 queries (clb_maxsim_batch_b1*,
+// clb_binarize_rows*); one device path and one host-array path behind the ten entry points, and the same device path behind
+// clb_maxsim_store_device, which scores passages listed by id where they lie in a resident store (any of the seven formats).
 #include <algorithm>
 #include <cmath>
 
@@ -15,7 +16,7 @@ namespace {
 
 inline int64_t align256(int64_t n) { return (n + 255) / 256 * 256; }
 
-// What the host needs of a format F: its sizes, its LDS layout, its kernels.  Indexed by D's type, CLB_F32 .. CLB_MXFP4.
+// What the host needs of a format F: its sizes, its LDS layout, its kernels.  One per type of D: CLB_F32 .. CLB_MXFP4, CLB_B1.
 typedef void (*DenseKernel)(const void*, const void*, int, int, int, const void*, const void*, const int64_t*, int64_t, const int32_t*,
                             int, int, float*);
 typedef void (*DenseStoreKernel)(const void*, const void*, int, int, int, const void*, const void*, const int64_t*, int64_t, const int32_t*,
@@ -36,16 +37,17 @@ DenseFormat dense_format() {
             dense_maxsim_kernel<F, 128 / F::kK>, dense_maxsim_kernel<F, 0>, dense_maxsim_kernel<F, 128 / F::kK, DenseStore>,
             dense_maxsim_kernel<F, 0, DenseStore>};
 }
-const DenseFormat& format_of(int d_type) {
-    static const DenseFormat f[6] = {dense_format<DenseF32>(), dense_format<DenseF16>(), dense_format<DenseBF16>(), dense_format<DenseI8>(),
-                                     dense_format<DenseMXFP8>(), dense_format<DenseMXFP4>()};
-    return f[d_type];
+bool is_format(int d_type) { return (d_type >= CLB_F32 && d_type <= CLB_MXFP4) || d_type == CLB_B1; }
+const DenseFormat& format_of(int d_type) {                // (d_type: is_format)
+    static const DenseFormat f[7] = {dense_format<DenseF32>(), dense_format<DenseF16>(), dense_format<DenseBF16>(), dense_format<DenseI8>(),
+                                     dense_format<DenseMXFP8>(), dense_format<DenseMXFP4>(), dense_format<DenseB1>()};
+    return f[d_type == CLB_B1 ? 6 : d_type];
 }
 
 // One call, as every entry point states it.  Q and D are device arrays in run_dense_device, host arrays in run_dense_host.
 struct DenseCall {
-    const char* who;                                    // the name its messages carry: maxsim_batch, maxsim_batch_half, maxsim_batch_i8, _mx
-    int family;                                         // the entry point's: CLB_F32, CLB_F16 (D in either 16-bit type), CLB_I8, CLB_MXFP8 (either MX)
+    const char* who;                                    // the name its messages carry: maxsim_batch, maxsim_batch_half, maxsim_batch_i8, _mx, _b1
+    int family;                                         // the entry point's: CLB_F32, CLB_F16 (D in either 16-bit type), CLB_I8, CLB_MXFP8 (either MX), CLB_B1
     int q_type, d_type;
     const void* Q;
     const void* qscale;
@@ -74,7 +76,7 @@ int check_dim(const char* who, int m, int64_t dim, const char* advice) {
 int check_shape(const DenseCall& c) {
     const char* advice = c.family == CLB_F32 ? ": score one query at a time with clb_maxsim" : "";
     if (c.family == CLB_F32 && c.q_type != CLB_F32) return fail(CLB_EUNSUPPORTED, "%s serves fp32 D with Q in fp32 (q_type = %d)", c.who, c.q_type);
-    if (c.family == CLB_I8 && c.q_type != CLB_F32 && c.q_type != CLB_I8)
+    if ((c.family == CLB_I8 || c.family == CLB_B1) && c.q_type != CLB_F32 && c.q_type != CLB_I8)
         return fail(CLB_EUNSUPPORTED, "%s serves Q in fp32 or int8 (q_type = %d)", c.who, c.q_type);
     if (c.family == CLB_F16 && ((c.d_type != CLB_F16 && c.d_type != CLB_BF16) || (c.q_type != CLB_F32 && c.q_type != c.d_type)))
         return fail(CLB_EUNSUPPORTED, "%s serves D in fp16 or bf16 and Q in fp32 or D's type (q_type = %d, d_type = %d)", c.who, c.q_type, c.d_type);
@@ -147,11 +149,13 @@ int check_scales(const char* who, const char* what, const float* s, int64_t n) {
     return CLB_OK;
 }
 
-// X into the values and scales of `format`: CLB_I8 (one fp32 scale per embedding), CLB_MXFP8 / CLB_MXFP4 (one byte per block)
+// X into the values and scales of `format`: CLB_I8, CLB_B1 (one fp32 scale per embedding), CLB_MXFP8 / CLB_MXFP4 (one byte per block)
 void launch_quantize(int format, const float* d_X, int dim, int64_t n, void* d_V, void* d_scale, hipStream_t st) {
     const dim3 grid((unsigned)std::min<int64_t>((n + 3) / 4, 8192)), block(256);
     if (format == CLB_I8)
         hipLaunchKernelGGL(dense_quantize_kernel, grid, block, 0, st, d_X, dim, n, (int8_t*)d_V, (float*)d_scale);
+    else if (format == CLB_B1)
+        hipLaunchKernelGGL(dense_binarize_kernel, grid, block, 0, st, d_X, dim, n, (unsigned char*)d_V, (float*)d_scale);
     else
         hipLaunchKernelGGL(format == CLB_MXFP4 ? dense_quantize_mx_kernel<true> : dense_quantize_mx_kernel<false>, grid, block, 0, st, d_X, dim, n,
                            (unsigned char*)d_V, (unsigned char*)d_scale);
@@ -301,6 +305,21 @@ int clb_maxsim_batch_i8(int device, const void* Q, int q_type, const float* qsca
     return run_dense_host(device, {"maxsim_batch_i8", CLB_I8, q_type, CLB_I8, Q, qscale, D8, dscale, dim, T, B, n_D, N, doclens, owner, scores});
 }
 
+int64_t clb_maxsim_batch_b1_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim) { return DenseWork(CLB_B1, N, B, T, dim).total(); }
+
+int clb_maxsim_batch_b1_device(int device, const void* d_Q, int q_type, const float* d_qscale, int64_t dim, int64_t T, int64_t B,
+                               const uint8_t* d_D1, const float* d_dscale, int64_t n_D, const int64_t* d_doclens, int64_t N,
+                               const int32_t* d_owner, float* d_scores, void* d_work, int64_t work_bytes, void* hip_stream) {
+    return run_dense_device(device, {"maxsim_batch_b1", CLB_B1, q_type, CLB_B1, d_Q, d_qscale, d_D1, d_dscale, dim, T, B, n_D, N, d_doclens, d_owner,
+                                     d_scores, d_work, work_bytes, (hipStream_t)hip_stream});
+}
+
+int clb_maxsim_batch_b1(int device, const void* Q, int q_type, const float* qscale, int64_t dim, int64_t T, int64_t B,
+                        const uint8_t* D1, const float* dscale, int64_t n_D, const int64_t* doclens, int64_t N, const int32_t* owner,
+                        float* scores) {
+    return run_dense_host(device, {"maxsim_batch_b1", CLB_B1, q_type, CLB_B1, Q, qscale, D1, dscale, dim, T, B, n_D, N, doclens, owner, scores});
+}
+
 // one size for both passage formats: what the work buffer holds beside the offsets is the QUERY, MXFP8 either way (DenseMX's
 // q_bytes and scale_bytes do not depend on E2M1), so sizing by CLB_MXFP8 here equals run_dense_device's sizing by the passages' format
 int64_t clb_maxsim_batch_mx_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim) { return DenseWork(CLB_MXFP8, N, B, T, dim).total(); }
@@ -318,18 +337,18 @@ int clb_maxsim_batch_mx(int device, const void* Q, int q_type, const uint8_t* qs
     return run_dense_host(device, {"maxsim_batch_mx", CLB_MXFP8, q_type, format, Q, qscale, D, dscale, dim, T, B, n_D, N, doclens, owner, scores});
 }
 
-// The listed call: one entry point for the six formats, the family being what the contiguous call of d_type belongs to.
+// The listed call: one entry point for the seven formats, the family being what the contiguous call of d_type belongs to.
 static int family_of(int d_type) { return d_type == CLB_BF16 ? CLB_F16 : d_type == CLB_MXFP4 ? CLB_MXFP8 : d_type; }
 
 int64_t clb_maxsim_store_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim, int d_type) {
-    return DenseWork(d_type < CLB_F32 || d_type > CLB_MXFP4 ? CLB_F32 : d_type, N, B, T, dim, true).total();
+    return DenseWork(is_format(d_type) ? d_type : CLB_F32, N, B, T, dim, true).total();
 }
 
 int clb_maxsim_store_device(int device, const void* d_Q, int q_type, const void* d_qscale, int64_t dim, int64_t T, int64_t B,
                             const void* d_store, const void* d_store_scale, int d_type, int64_t n_rows, const int64_t* d_store_off,
                             int64_t P, const int64_t* d_pids, int64_t N, const int32_t* d_owner, float* d_scores, void* d_work,
                             int64_t work_bytes, void* hip_stream) {
-    if (d_type < CLB_F32 || d_type > CLB_MXFP4) return fail(CLB_EUNSUPPORTED, "maxsim_store serves d_type CLB_F32 .. CLB_MXFP4 (d_type = %d)", d_type);
+    if (!is_format(d_type)) return fail(CLB_EUNSUPPORTED, "maxsim_store serves d_type CLB_F32 .. CLB_MXFP4 and CLB_B1 (d_type = %d)", d_type);
     DenseCall c{"maxsim_store", family_of(d_type), q_type, d_type, d_Q, d_qscale, d_store, d_store_scale, dim, T, B, n_rows, N, d_store_off,
                 d_owner, d_scores, d_work, work_bytes, (hipStream_t)hip_stream};
     c.listed = true, c.pids = d_pids, c.P = P;
@@ -375,6 +394,42 @@ int clb_quantize_mx(int device, const float* X, int64_t dim, int64_t n, int form
                 hipMemcpyAsync(scale, dS.p, s_bytes, hipMemcpyDeviceToHost, st) != hipSuccess))
         rc = fail(CLB_EHIP, "quantize_mx: copying the result back failed");
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(CLB_EHIP, "quantize_mx: hipStreamSynchronize failed");
+    (void)hipStreamDestroy(st);
+    return rc;
+}
+
+int clb_binarize_rows_device(int device, const float* d_X, int64_t dim, int64_t n, uint8_t* d_V, float* d_scale, void* hip_stream) {
+    CLB_TRY(check_dim("binarize_rows", 128, dim, ""));
+    if (n < 0) return fail(CLB_EARGUMENT, "binarize_rows: n >= 0 is required");
+    if (n == 0) return CLB_OK;
+    if (!d_X || !d_V || !d_scale) return fail(CLB_EARGUMENT, "binarize_rows: null argument");
+    if ((uintptr_t)d_X % 16 || (uintptr_t)d_V % 16) return fail(CLB_EARGUMENT, "binarize_rows: X and the bits must be 16-byte aligned");
+    CLB_TRY(use_device(device));
+    launch_quantize(CLB_B1, d_X, (int)dim, n, d_V, d_scale, (hipStream_t)hip_stream);
+    CLB_HIP(hipGetLastError());
+    return CLB_OK;
+}
+
+int clb_binarize_rows(int device, const float* X, int64_t dim, int64_t n, uint8_t* V, float* scale) {
+    CLB_TRY(check_dim("binarize_rows", 128, dim, ""));
+    if (n < 0 || (n > 0 && (!X || !V || !scale))) return fail(CLB_EARGUMENT, "binarize_rows: n >= 0 and non-null buffers are required");
+    for (int64_t e = 0; e < n; ++e)
+        for (int64_t k = 0; k < dim; ++k)
+            if (!std::isfinite(X[e * dim + k])) return fail(CLB_EARGUMENT, "binarize_rows: embedding %lld holds a non-finite value", (long long)e);
+    CLB_TRY(use_device(device));
+    if (n == 0) return CLB_OK;
+    const size_t v_bytes = (size_t)(dim / 8) * n;
+    hipStream_t st = nullptr;
+    CLB_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    DevBuf dX, dV, dS;
+    int rc = upload(dX, X, sizeof(float) * dim * n, st);
+    if (!rc) rc = dV.alloc(v_bytes);
+    if (!rc) rc = dS.alloc(sizeof(float) * n);
+    if (!rc) rc = clb_binarize_rows_device(device, dX.as<float>(), dim, n, dV.as<uint8_t>(), dS.as<float>(), st);
+    if (!rc && (hipMemcpyAsync(V, dV.p, v_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipMemcpyAsync(scale, dS.p, sizeof(float) * n, hipMemcpyDeviceToHost, st) != hipSuccess))
+        rc = fail(CLB_EHIP, "binarize_rows: copying the result back failed");
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(CLB_EHIP, "binarize_rows: hipStreamSynchronize failed");
     (void)hipStreamDestroy(st);
     return rc;
 }

@@ -1,5 +1,6 @@
 // dense_formats.hpp -- the embedding formats of the dense MaxSim kernel (dense_kernels.hpp: dense_maxsim_kernel<F, KB>) and the
-// kernels that bring fp32 queries into a format (dense_round_kernel, dense_quantize_kernel, dense_quantize_mx_kernel).  A format
+// kernels that bring fp32 embeddings into a format (dense_round_kernel, dense_quantize_kernel, dense_quantize_mx_kernel,
+// dense_binarize_kernel).  A format
 // F supplies
 //   Frag, QFrag       one lane's share of a K-block (kK elements) of a row and of a query token: kFragBytes / kQFragBytes of values
 //   load_row, load_q  lane group g's fragment of a K-block, given the lane's first byte of it (the K-block's + kLaneBytes g), the
@@ -62,6 +63,37 @@
 // the next: all chains first costs this format 16 more VGPRs and measured 2 % (owned) to 5 % (all pairs) slower
 // (profiles/dense_refactor.md).
 //
+// 1-bit sign rows against int8 queries (DenseB1): one bit per dimension and one fp32 scale per row, 16 + 4 B at dim 128.  gfx950
+// has no 1-bit matrix instruction, and needs none: a sign is +-1 and +-1 is an int8, so the row is widened in registers and
+// everything from the MFMA on -- v_mfma_i32_16x16x64_i8, the epilogue, the scales, the query side, the bit-exact restatement --
+// is DenseI8's (|i| <= 1024 * 127 < 2^24).  Only load_row is new: lane (r, g) reads the 16 bits at k = 64 kb + 16 g of its row
+// (kFragBytes = kLaneBytes = 2 stored bytes; Frag is the widened 16 int8).
+// The widening, chosen from the instruction count: 14 VALU per 16 bits, counted in the ISA -- v_not and v_lshl once (so that
+// every nibble is the high nibble of some byte), then per dword v_perm (replicate that byte), v_and 0x80402010 (byte j keeps its
+// own bit) and v_perm again, which reads the four bytes as SELECTORS into a constant: 0 selects 0x01, a selector >= 0x0d is the
+// constant 0xff, so a set bit becomes +1 and a clear one -1 with no arithmetic on the bytes at all.  Against it: bfe, multiply by
+// 0x00204081, mask, then 0 / 1 -> -1 / +1 is 16 to 20; feeding bytes 0 / 2 and seeding the accumulator with -sum_k q8[k, t]
+// saves the last step (12) but needs the sum per token tile -- two more MFMAs per (run, token tile) wherever the query is not
+// resident -- and a seed hook in the frame for 2 instructions per 16 bits; a nibble table in LDS is two dependent LDS reads per
+// 16 bits with random bank conflicts.  The widening runs once per row tile and step at dim 128 (KB = 2: 8 x 14 = 112 VALU per wave
+// and step, the A operand then resident for every token tile of every query), per K-block at other dims.
+// LDS: rows at padded(dim / 8) bytes -- 16 at dim 128, 48 at dim 256 and 384.  The 64 lanes of a read take 2 bytes each at
+// 16 r + 8 kb + 2 g: at dim 128 the 16 rows of a tile are 256 contiguous bytes, one per bank group of 4, and the lanes g = 0, 1
+// (2, 3) of a row share a dword, which is a broadcast: 32 dwords in 32 banks, conflict-free.  At a 48-byte stride row r starts
+// at bank 12 r mod 64, sixteen different multiples of 4: conflict-free as well (an unpadded 32 bytes would put rows r and r + 8
+// on the same bank).  A 4-wave step at dim 128 is 256 rows x 16 B = 4 KB + 1 KB of scales, against int8's 37 KB; with the 1280-byte
+// head and at most 16 KB of maxima a work-group needs 8.3 KB (owned, T = 32) to 22.3 KB, so the LDS allows 19 (owned) to 7 (all
+// pairs) work-groups per CU -- and registers, not LDS, now set the occupancy: 106 VGPRs = 4 waves per SIMD = 4 work-groups of 4
+// waves per CU, where int8 had 3 or 4 from its LDS.  4 row tiles per wave stands: it is the most the frame's packed first / last
+// passage scalars hold, the A operand is int8's 32 VGPRs, and fewer tiles would not raise the occupancy the registers set.
+// Decided from the code, not timed: the bank picture, 4 tiles against 2, and the widening routes against each other.
+// Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; VGPRs / SGPRs in VGPR lanes / waves per SIMD; no AGPRs, no
+// scratch, no VGPR spills): KB = 2: 106 / 27 / 4, KB = 0: 74 / 11 / 6; listed KB = 2: 105 / 27 / 4, KB = 0: 73 / 13 / 6.  Every
+// other instantiation's figures are what they were.  Measured (profiles/maxsim_batch_b1.md): 1.8x int8 in the owned form, 1.3x in
+// all pairs, and 2 % / 9 % SLOWER than MXFP4 at a third of its bytes -- at 9 % of the read rate the owned form is bound by issue
+// slots, not bytes: two MFMAs, four v_cvt_f32_i32 and four multiplies per tile where MXFP4 has one MFMA and no epilogue.
+// Quantiser (dense_binarize_kernel): a float4 is a nibble, 8 lanes' nibbles are OR-ed into a dword with 3 shuffles; no LDS.
+//
 // MX block-scaled (DenseMX<E2M1>: MXFP8 / MXFP4 passages, MXFP8 queries): v_mfma_scale_f32_16x16x128_f8f6f4 multiplies 128
 // elements and applies one E8M0 scale per block of 32 of each operand inside the product, so there is no epilogue multiply and
 // no query scale in the sum; A (rows, cbsz) and B (tokens, blgp) formats are independent.  At dim 128 a (row tile, token tile)
@@ -103,7 +135,8 @@ template <typename FRAG, int ELEM>
 struct DensePlain {
     typedef FRAG Frag;
     typedef FRAG QFrag;
-    static constexpr int kElem = ELEM, kFragBytes = (int)sizeof(FRAG), kQFragBytes = (int)sizeof(FRAG), kLaneBytes = (int)sizeof(FRAG), kDimMultiple = ELEM < 4 ? 16 / ELEM : 4;
+    static constexpr int kElem = ELEM, kFragBytes = (int)sizeof(FRAG), kQFragBytes = (int)sizeof(FRAG), kLaneBytes = (int)sizeof(FRAG), kQLaneBytes = (int)sizeof(FRAG);
+    static constexpr int kDimMultiple = ELEM < 4 ? 16 / ELEM : 4;
     __host__ __device__ static int row_bytes(int dim) { return ELEM * dim; }
     __host__ __device__ static int q_bytes(int dim) { return ELEM * dim; }
     // lane group g's fragment of a K-block, v already at it (its g-th); zeros, nothing read, where the row holds fewer than `left` bytes
@@ -170,6 +203,39 @@ struct DenseI8 : Dense16ByteFrag, DensePlain<dense_i32x4, 1> {
     }
 };
 
+// 1-bit sign rows against int8 queries: the row is stored as bits (2 bytes per lane and K-block) and widened to the int8
+// fragment of +-1 that DenseI8's MFMA, epilogue and scales take; the query side is DenseI8's as it stands.
+struct DenseB1 : Dense16ByteFrag {
+    typedef dense_i32x4 Frag;                            // the WIDENED row fragment: 16 int8 of +-1
+    typedef dense_i32x4 QFrag;
+    typedef dense_i32x4 Acc;
+    static constexpr int kK = 64, kRowTiles = 4, kHeadBytes = 1280, kOwnAt = 192, kRowpAt = 256, kShiftAt = 1280, kListedHeadExtra = 128, kDimMultiple = 128;
+    static constexpr int kFragBytes = 2, kQFragBytes = 16, kLaneBytes = 2, kQLaneBytes = 16;
+    static constexpr bool kScaled = true, kHasScales = true;
+    __host__ __device__ static int row_bytes(int dim) { return dim >> 3; }
+    __host__ __device__ static int q_bytes(int dim) { return dim; }
+    __host__ __device__ static int scale_bytes(int) { return 4; }
+    __host__ __device__ static int row_stride(int dim) { return padded(dim >> 3); }
+    // The 16 bits at v (k = 64 kb + 16 g .. + 15, least significant first) as 16 int8: bit 1 -> +1, bit 0 -> -1.  The bits are
+    // inverted once and a copy shifted by 4, so that every group of 4 is the HIGH nibble of some byte; per dword that byte is
+    // replicated (v_perm), each copy keeps its own bit (0x10 << j in byte j), and a second v_perm reads the result as
+    // selectors: 0 takes byte 0 of the table (0x01), anything >= 0x0d is the constant 0xff.
+    static __device__ __forceinline__ Frag load_row(const unsigned char* v, const unsigned char*, int, int) {
+        const uint32_t hn = ~(uint32_t)*reinterpret_cast<const uint16_t*>(v), hs = hn << 4;
+        const uint32_t src[4] = {hs, hn, hs, hn};
+        Frag f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t rep = __builtin_amdgcn_perm(src[i], src[i], i < 2 ? 0x00000000u : 0x01010101u);
+            f[i] = (int)__builtin_amdgcn_perm(0x01010101u, 0x01010101u, rep & 0x80402010u);
+        }
+        return f;
+    }
+    static __device__ __forceinline__ QFrag load_q(const unsigned char* v, const unsigned char* s, int g, int left) { return DenseI8::load_q(v, s, g, left); }
+    static __device__ __forceinline__ Acc mfma(Frag a, QFrag b, Acc c) { return DenseI8::mfma(a, b, c); }
+    static __device__ __forceinline__ dense_f32x4 epilogue(Acc acc, float4 ds) { return DenseI8::epilogue(acc, ds); }
+};
+
 // MX block-scaled embeddings (OCP MX v1.0): passages MXFP8 (E4M3) or MXFP4 (E2M1), queries always MXFP8, one E8M0 scale byte
 // per block of 32 elements.  A fragment is one block -- N16 16-byte columns of values and the block's scale byte, which
 // the instruction takes from the lane that holds the block; the zero fragment is zero values under scale byte 127.
@@ -185,7 +251,7 @@ struct DenseMX : Dense16ByteFrag {
     typedef dense_f32x4 Acc;
     typedef int v8 __attribute__((ext_vector_type(8)));
     static constexpr int kK = 128, kRowTiles = 4, kHeadBytes = 1280, kOwnAt = 192, kRowpAt = 256, kShiftAt = 1280, kListedHeadExtra = 128, kDimMultiple = 32;
-    static constexpr int kFragBytes = E2M1 ? 16 : 32, kQFragBytes = 32, kLaneBytes = 16;
+    static constexpr int kFragBytes = E2M1 ? 16 : 32, kQFragBytes = 32, kLaneBytes = 16, kQLaneBytes = 16;
     static constexpr bool kScaled = false, kHasScales = true;     // no fp32 scale, no epilogue multiply: the scales are in the product
     __host__ __device__ static int row_bytes(int dim) { return E2M1 ? dim >> 1 : dim; }
     __host__ __device__ static int q_bytes(int dim) { return dim; }
@@ -326,6 +392,36 @@ static __global__ __launch_bounds__(256) void dense_quantize_kernel(const float*
             dst[c] = word;
         }
         if (lane == 0) scale[e] = s;
+    }
+}
+
+// X (dim, n) fp32 -> sign bits V (dim / 8, n) -- bit k & 7 of byte k >> 3 is x_k >= 0, so -0.0 gives 1 and a NaN 0 -- and scale
+// [n]: s = (sum_k |x_k|) / dim, the least-squares scale of a sign code, summed in fp32 (each lane its own elements, then a
+// butterfly).  One wave per embedding, grid-stride; the row (dim <= 1024, dim % 128 == 0) is read once with float4 loads.  A
+// float4 is one nibble; a dword of V is the nibbles of 8 consecutive lanes, OR-ed together in 3 shuffle steps (dim / 4 is a
+// multiple of 32, so the 8 lanes are all inside the row or all past it) and written by the first of them; no LDS.  A non-finite
+// input gives defined, meaningless numbers.  X 16-byte, V 4-byte aligned.
+static __global__ __launch_bounds__(256) void dense_binarize_kernel(const float* __restrict__ X, int dim, int64_t n,
+                                                                    unsigned char* __restrict__ V, float* __restrict__ scale) {
+    const int lane = threadIdx.x & 63, dim4 = dim >> 2;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t e = wave; e < n; e += n_waves) {
+        const float4* src = reinterpret_cast<const float4*>(X + e * dim);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(V + e * (dim >> 3));
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = lane + 64 * j;
+            const float4 v = c < dim4 ? src[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+            sum += (fabsf(v.x) + fabsf(v.y)) + (fabsf(v.z) + fabsf(v.w));
+            uint32_t word = ((uint32_t)(v.x >= 0.f) | (uint32_t)(v.y >= 0.f) << 1 | (uint32_t)(v.z >= 0.f) << 2 | (uint32_t)(v.w >= 0.f) << 3) << (4 * (lane & 7));
+#pragma unroll
+            for (int d = 1; d < 8; d <<= 1) word |= (uint32_t)__shfl_xor((int)word, d, 64);
+            if (c < dim4 && (lane & 7) == 0) dst[c >> 3] = word;
+        }
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) sum += __shfl_xor(sum, d, 64);
+        if (lane == 0) scale[e] = sum / (float)dim;
     }
 }
 

@@ -5,7 +5,8 @@
 //   dot     one MFMA per K-block, the K-blocks in ascending order from +0: embeddings are tile rows, query tokens are tile
 //           columns.  Lane (r, g) holds, of K-block kb of row or token r, the FRAG consecutive elements at K kb + FRAG g --
 //           one fragment of F::kFragBytes (rows) or F::kQFragBytes (tokens) bytes, K = 4 FRAG -- and the same k in the A and
-//           the B operand.  Where a format's instruction orders K otherwise it says so in its load (F::load_row, F::load_q: the
+//           the B operand; lane group g's bytes begin F::kLaneBytes g (rows) / F::kQLaneBytes g (tokens) into the K-block, and a
+//           format may widen what it read (1-bit rows: 2 stored bytes become the 16 int8 of the register fragment).  Where a format's instruction orders K otherwise it says so in its load (F::load_row, F::load_q: the
 //           lane's first byte of the K-block, lane group g and the bytes the row still holds from the K-block's start).  The accumulator
 //           layout is the same for every format: lane (col r, g) holds the rows 4 g + i, i = 0..3.
 //   max     exact and order-free, so partial maxima of a passage combine in any order (LDS atomic max on order keys)
@@ -330,7 +331,7 @@ static __global__ __launch_bounds__(256) void dense_maxsim_kernel(const void* __
     int q_res = -1;                                        // (wave-uniform) the query they hold
     // K-block 0 of token t of query q, t clamped to the last token; K-block kb lies 4 QFB kb bytes on.  q_sc: the same for its
     // block scales, K-block kb 4 bytes on (a format whose fragments carry one)
-    auto q_tok = [&](int q, int t) { return Q + ((size_t)q * T + (t < T ? t : T - 1)) * F::q_bytes(dim) + F::kLaneBytes * g; };
+    auto q_tok = [&](int q, int t) { return Q + ((size_t)q * T + (t < T ? t : T - 1)) * F::q_bytes(dim) + F::kQLaneBytes * g; };
     auto q_sc = [&](int q, int t) { return BS ? QS + ((size_t)q * T + (t < T ? t : T - 1)) * nsb + g : nullptr; };
 
     for (int64_t c = lo; c < hi; c += CH) {

@@ -862,7 +862,7 @@ int clb_maxsim_batch(int device, const float* Q, int64_t dim, int64_t T, int64_t
  * allocation (d_work: clb_maxsim_batch_half_work_bytes bytes -- the offsets and the rounded Q), capturable, clamped doclens, -Inf
  * for a passage without a readable row or with an owner outside the batch; the host call (Q and D host buffers in the named
  * types) validates first.  Not part of the Julia shim. */
-enum { CLB_F32 = 0, CLB_F16 = 1, CLB_BF16 = 2, CLB_I8 = 3, CLB_MXFP8 = 4, CLB_MXFP4 = 5 };
+enum { CLB_F32 = 0, CLB_F16 = 1, CLB_BF16 = 2, CLB_I8 = 3, CLB_MXFP8 = 4, CLB_MXFP4 = 5, CLB_B1 = 16 /* passages only */ };
 int64_t clb_maxsim_batch_half_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim);
 int clb_maxsim_batch_half_device(int device, const void* d_Q, int q_type, int64_t dim, int64_t T, int64_t B,
                                  const void* d_D, int d_type, int64_t n_D, const int64_t* d_doclens, int64_t N,
@@ -902,6 +902,41 @@ int clb_maxsim_batch_i8_device(int device, const void* d_Q, int q_type, const fl
                                void* d_work, int64_t work_bytes, void* hip_stream);
 int clb_maxsim_batch_i8(int device, const void* Q, int q_type, const float* qscale, int64_t dim, int64_t T, int64_t B,
                         const int8_t* D8, const float* dscale, int64_t n_D, const int64_t* doclens, int64_t N, const int32_t* owner,
+                        float* scores);
+/* The same call on passages stored as ONE SIGN BIT per dimension with one fp32 scale each (dense_formats.hpp: DenseB1), scored
+ * asymmetrically: the queries keep 8 bits.  16 + 4 bytes per embedding at dim 128.  A 1-bit operand is a pair:
+ *   values  (dim / 8, n) uint8: bit k & 7 of byte k >> 3, least significant bit first, is 1 iff x_k >= 0 (so -0.0 gives 1, a NaN 0);
+ *   scales  one finite fp32 s >= 0 per embedding.  Decoded: d^_k = s (2 bit_k - 1).
+ * Quantisation (clb_binarize_rows*): the bits as above and s = (sum_k |x_k|) / dim, the least-squares scale of a sign code; the
+ *   device sums in fp32 in its reduction's order, so its s lies within (dim + 1) 2^-24 s of the exact quotient.  Served:
+ *   dim % 128 == 0, 128 <= dim <= 1024, else CLB_EUNSUPPORTED; d_X and d_V 16-byte aligned.  The host call refuses a non-finite
+ *   value with CLB_EARGUMENT naming the embedding; the device call cannot report: a non-finite value there gives defined but
+ *   meaningless numbers, never a fault.
+ * Scoring, for query q and passage j.  The queries are int8 with one fp32 scale per token exactly as for clb_maxsim_batch_i8
+ * (d_Q in q_type = CLB_I8 with d_qscale (T, B), or CLB_F32: quantised by clb_quantize_rows' rule into the work buffer first,
+ * d_qscale ignored); CLB_B1 is never a query type.  The bits are widened to int8 +-1 in registers and multiplied by the same
+ * instruction:
+ *   i(t, r) = sum_k q8[k, t] (2 bit[k, r] - 1)   exact in int32 (v_mfma_i32_16x16x64_i8); |i| <= 1024 * 127 < 2^24
+ *   m_t     = max over the rows r of passage j of fl32(ds[r] * float(i(t, r)))
+ *   score   = acc = 0; for t ascending: acc = fl32(acc + fl32(qs[t] * m_t));  -Inf for a pair that received no row
+ * Every score equals this restatement bit for bit and depends on its own query and passage only; it is also what
+ * clb_maxsim_batch_i8 gives for the unpacked +-1 values under the same scales.  How far the scores lie from the fp32 scores of the
+ * unquantised embeddings is a property of the format, measured in profiles/maxsim_batch_b1.md, not part of the contract.
+ * Served: dim % 128 == 0, 128 <= dim <= 1024 (a row is whole 16-byte columns; tuned for 128), 1 <= T <= 128, B >= 1, N >= 0, q_type
+ * CLB_F32 or CLB_I8, else CLB_EUNSUPPORTED; d_Q, d_D1 and d_work 16-byte aligned.  Every other contract is clb_maxsim_batch_i8's:
+ * argument errors before any launch, stream-ordered, no host wait, no allocation (d_work: clb_maxsim_batch_b1_work_bytes bytes --
+ * the offsets, and B T dim bytes + B T floats for a query quantised in the call), capturable, clamped doclens (no row at or past
+ * n_D is read, neither its bits nor its scale).  The host call validates first and also refuses a negative or non-finite scale
+ * with CLB_EARGUMENT.  Not part of the Julia shim. */
+int clb_binarize_rows_device(int device, const float* d_X, int64_t dim, int64_t n, uint8_t* d_V, float* d_scale, void* hip_stream);
+int clb_binarize_rows(int device, const float* X, int64_t dim, int64_t n, uint8_t* V, float* scale);
+int64_t clb_maxsim_batch_b1_work_bytes(int64_t N, int64_t B, int64_t T, int64_t dim);
+int clb_maxsim_batch_b1_device(int device, const void* d_Q, int q_type, const float* d_qscale, int64_t dim, int64_t T, int64_t B,
+                               const uint8_t* d_D1, const float* d_dscale, int64_t n_D, const int64_t* d_doclens, int64_t N,
+                               const int32_t* d_owner /* NULL: all pairs */, float* d_scores,
+                               void* d_work, int64_t work_bytes, void* hip_stream);
+int clb_maxsim_batch_b1(int device, const void* Q, int q_type, const float* qscale, int64_t dim, int64_t T, int64_t B,
+                        const uint8_t* D1, const float* dscale, int64_t n_D, const int64_t* doclens, int64_t N, const int32_t* owner,
                         float* scores);
 /* The same call on MX block-scaled embeddings (OCP MX v1.0; dense_formats.hpp).  An MX operand is a pair:
  *   values  (dim, n) uint8 for CLB_MXFP8 -- E4M3: largest 448, no infinities, 0x7F / 0xFF are NaN -- or (dim / 2, n) uint8 for
@@ -946,14 +981,14 @@ int clb_maxsim_batch_mx(int device, const void* Q, int q_type, const uint8_t* qs
                         const uint8_t* D, const uint8_t* dscale, int format, int64_t n_D, const int64_t* doclens, int64_t N,
                         const int32_t* owner, float* scores);
 /* The dense scorer BY PASSAGE ID: the listed passages' rows are read where they lie in a resident store, one entry point for the
- * six formats.  A store is what the calls above take as D, plus row offsets:
- *   d_store (dim, n_rows) in d_type = CLB_F32 .. CLB_MXFP4; d_store_scale its scales (CLB_I8: one fp32 per row; MX: dim / 32 bytes
- *   per row; ignored otherwise); d_store_off int64 [P + 1]: stored passage p is the rows off[p] .. off[p + 1] - 1.
+ * seven formats.  A store is what the calls above take as D, plus row offsets:
+ *   d_store (dim, n_rows) in d_type = CLB_F32 .. CLB_MXFP4 or CLB_B1 ((dim / 8, n_rows) bytes); d_store_scale its scales (CLB_I8 and
+ *   CLB_B1: one fp32 per row; MX: dim / 32 bytes per row; ignored otherwise); d_store_off int64 [P + 1]: stored passage p is the rows off[p] .. off[p + 1] - 1.
  *   d_pids int64 [N], 0-based, in any order, repeats allowed; d_owner int32 [N] or NULL.
  *   owned     entry j scores stored passage pids[j] against query owner[j]; d_scores [N].
  *   all pairs every query against every entry; d_scores (N, B), N fastest.
  * d_Q, q_type and d_qscale are the contiguous call's of d_type's format (clb_maxsim_batch_device, _half_device, _i8_device,
- * _mx_device), with the same served type pairs, dim, T and alignments and the same codes for anything else.  Each score has exactly
+ * _mx_device, _b1_device), with the same served type pairs, dim, T and alignments and the same codes for anything else.  Each score has exactly
  * the bits that call gives for the same rows laid back to back: a pair's bits depend on its query and its passage only.
  * Device arrays are not validated and bad ones do not fault; everything is clamped in the kernel before an address is formed:
  *   a pid outside 0..P-1 scores -Inf (pad a ragged list with -1);

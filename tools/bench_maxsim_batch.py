@@ -18,7 +18,10 @@ with one scale each by `quantize_rows_device`, fp32 queries quantised in the cal
 same values, all three interleaved in the same windows; its bytes make the read-rate fraction, and the largest and median
 |int8 score - fp32 score| are reported, not asserted: they are the format's (profiles/maxsim_batch_int8.md).  `--dtype mxfp8 |
 mxfp4`: the scaled-MFMA kernel (passages quantised by `quantize_mx_device`, fp32 queries quantised to MXFP8 in the call) beside
-the fp32, the float16 AND the int8 kernel, all four interleaved; the same figures (profiles/maxsim_batch_mx.md).
+the fp32, the float16 AND the int8 kernel, all four interleaved; the same figures (profiles/maxsim_batch_mx.md).  `--dtype binary`:
+the 1-bit kernel (passages binarised by `binarize_rows_device`, fp32 queries quantised to int8 in the call) beside the fp32, float16,
+int8 AND mxfp4 kernels, all five interleaved, with every quantised side's own bytes and share of the read rate
+(profiles/maxsim_batch_b1.md).
 A measurement path only: it needs a GPU and fails without one."""
 import argparse
 import json
@@ -51,7 +54,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--mfma-f32-tflops", type=float, default=None)
-    ap.add_argument("--dtype", choices=["float32", "float16", "bfloat16", "int8", "mxfp8", "mxfp4"], default="float32")
+    ap.add_argument("--dtype", choices=["float32", "float16", "bfloat16", "int8", "mxfp8", "mxfp4", "binary"], default="float32")
     ap.add_argument("--mfma-16bit-tflops", type=float, default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -83,8 +86,8 @@ def main():
         sides[name + "_device"] = (lambda d_Q=d_Q, d_D=d_D, d_l=d_l, d_o=d_o, out=out, work=work:
                                    codec.maxsim_batch_device(d_Q, d_D, d_l, owner=d_o, out=out, work=work))
         flop = 2.0 * dim * T * rows * (1 if owner is not None else B)
-        mx = args.dtype in ("mxfp8", "mxfp4")
-        if args.dtype == "int8" or mx:                 # the same values as int8 + scales, and in fp16: each its own out and work
+        mx, b1 = args.dtype in ("mxfp8", "mxfp4"), args.dtype == "binary"
+        if args.dtype == "int8" or mx or b1:                 # the same values as int8 + scales, and in fp16: each its own out and work
             d_Dh, out_h, out_8 = d_D.to(torch.float16), torch.empty_like(out), torch.empty_like(out)
             d_D8, d_ds = codec.quantize_rows_device(d_D)
             work_h = torch.empty(int(clb.lib().clb_maxsim_batch_half_work_bytes(N, B, T, dim)), dtype=torch.uint8, device="cuda")
@@ -93,16 +96,27 @@ def main():
                                                codec.maxsim_batch_device(d_Q, d_Dh, d_l, owner=d_o, out=out_h, work=work_h))
             sides[name + "_int8_device"] = (lambda d_Q=d_Q, d_D8=d_D8, d_ds=d_ds, d_l=d_l, d_o=d_o, out_8=out_8, work_8=work_8:
                                             codec.maxsim_batch_device(d_Q, d_D8, d_l, owner=d_o, out=out_8, work=work_8, d_scale=d_ds))
-            byts = 1.0 * dim * rows + 4.0 * rows + 4.0 * Q.size + 8.0 * N + (4.0 * N if owner is not None else 0)
-            if mx:                                     # the same values as an MX pair: its own out and work
-                (d_Dm, d_dm), out_m = codec.quantize_mx_device(d_D, args.dtype), torch.empty_like(out)
+            rest = 4.0 * Q.size + 8.0 * N + (4.0 * N if owner is not None else 0)
+            byts = 1.0 * dim * rows + 4.0 * rows + rest
+            side_bytes = {"int8": byts}
+            if mx or b1:                               # the same values as an MX pair: its own out and work
+                fmt = "mxfp4" if b1 else args.dtype
+                (d_Dm, d_dm), out_m = codec.quantize_mx_device(d_D, fmt), torch.empty_like(out)
                 work_m = torch.empty(int(clb.lib().clb_maxsim_batch_mx_work_bytes(N, B, T, dim)), dtype=torch.uint8, device="cuda")
-                sides[name + "_" + args.dtype + "_device"] = (lambda d_Q=d_Q, d_Dm=d_Dm, d_dm=d_dm, d_l=d_l, d_o=d_o, out_m=out_m, work_m=work_m:
-                                                              codec.maxsim_batch_device(d_Q, d_Dm, d_l, owner=d_o, out=out_m, work=work_m, d_scale=d_dm))
-                byts = 1.0 * d_Dm.numel() + d_dm.numel() + 4.0 * Q.size + 8.0 * N + (4.0 * N if owner is not None else 0)
+                sides[name + "_" + fmt + "_device"] = (lambda d_Q=d_Q, d_Dm=d_Dm, d_dm=d_dm, d_l=d_l, d_o=d_o, out_m=out_m, work_m=work_m:
+                                                       codec.maxsim_batch_device(d_Q, d_Dm, d_l, owner=d_o, out=out_m, work=work_m, d_scale=d_dm))
+                byts = side_bytes[fmt] = 1.0 * d_Dm.numel() + d_dm.numel() + rest
+            if b1:                                     # the same values as sign bits + scales: its own out and work
+                (d_Db, d_db), out_b = codec.binarize_rows_device(d_D), torch.empty_like(out)
+                work_b = torch.empty(int(clb.lib().clb_maxsim_batch_b1_work_bytes(N, B, T, dim)), dtype=torch.uint8, device="cuda")
+                sides[name + "_binary_device"] = (lambda d_Q=d_Q, d_Db=d_Db, d_db=d_db, d_l=d_l, d_o=d_o, out_b=out_b, work_b=work_b:
+                                                  codec.maxsim_batch_device(d_Q, d_Db, d_l, owner=d_o, out=out_b, work=work_b, d_scale=d_db))
+                byts = side_bytes["binary"] = 1.0 * d_Db.numel() + 4.0 * d_db.numel() + rest
             diff = np.abs(sides[name + "_" + args.dtype + "_device"]().cpu().numpy().astype(np.float64) - sides[name + "_device"]().cpu().numpy())
             work_of[name] = {"passages": N, "embeddings": rows, "flop": flop, "bytes": byts,
                              "max_abs_difference_from_fp32": float(diff.max()), "median_abs_difference_from_fp32": float(np.median(diff))}
+            if b1:
+                work_of[name]["side_bytes"] = side_bytes
             continue
         if half:                                       # the same values stored in 16 bits; its own out and work
             d_Dh, out_h = d_D.to(getattr(torch, args.dtype)), torch.empty_like(out)
@@ -170,8 +184,10 @@ def main():
         w["fraction_of_read_rate"] = round(w["bytes"] / t / 1e9 / read_gbs, 4)
         w["device_tflops"] = round(w["flop"] / t / 1e12, 2)
         if half:
-            if mx:
-                for other in ("float16", "int8"):
+            for side, sb in w.get("side_bytes", {}).items():      # every quantised side's own bytes over its own time
+                w[side + "_fraction_of_read_rate"] = round(sb / (out["sides"][name + "_" + side + "_device"]["ms"] * 1e-3) / 1e9 / read_gbs, 4)
+            if mx or b1:
+                for other in ("float16", "int8") + (("mxfp4",) if b1 else ()):
                     w[other + "_over_" + args.dtype] = round(out["sides"][name + "_" + other + "_device"]["ms"] * 1e-3 / t, 3)
             elif args.dtype == "int8":
                 w["float16_over_int8"] = round(out["sides"][name + "_float16_device"]["ms"] * 1e-3 / t, 3)

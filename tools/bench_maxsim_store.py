@@ -2,7 +2,7 @@
 """Dense MaxSim by passage id (`codec.maxsim_batch_device(pids=, store_offsets=)`) against the route it replaces, at the re-ranking
 shape of profiles/maxsim_batch.md: B = 32 queries x `--per-query` (1 000) listed passages, doclens N(80, 20), dim 128, T = 32,
 owned form, the passages drawn from a resident store of `--store-passages` (1 000 000) so that their rows are cold.  Per
-`--dtypes` format (float16, int8, mxfp4), three sides on the same lists:
+`--dtypes` format (float16, int8, mxfp4, binary), three sides on the same lists:
 
   listed    the listed call: rows read where they lie in the store;
   gather    the replaced route: row numbers from the two offset arrays, a device gather of rows and scales into contiguous
@@ -65,17 +65,18 @@ def main():
         if dtype == "float16":
             store, scale = torch.cat([c.half() for c in chunks]), None
         else:                                                            # quantised chunk by chunk: the fp32 store is never whole
-            quant = codec.quantize_rows_device if dtype == "int8" else (lambda x: codec.quantize_mx_device(x, dtype))
+            quant = {"int8": codec.quantize_rows_device, "binary": codec.binarize_rows_device}.get(dtype) or (lambda x: codec.quantize_mx_device(x, dtype))
             parts = [quant(torch.nn.functional.normalize(torch.randn(min(1 << 22, rows - a), dim, device="cuda"), dim=-1))
                      for a in range(0, rows, 1 << 22)]
             store, scale = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
             del parts
         del chunks
-        d_type = {"float16": 1, "int8": 3, "mxfp4": 5}[dtype]
+        d_type = {"float16": 1, "int8": 3, "mxfp4": 5, "binary": 16}[dtype]
         out = [torch.empty(N, dtype=torch.float32, device="cuda") for _ in range(3)]
         work = torch.empty(int(clb.lib().clb_maxsim_store_work_bytes(N, B, T, dim, d_type)), dtype=torch.uint8, device="cuda")
         work_c = torch.empty(int(max(clb.lib().clb_maxsim_batch_half_work_bytes(N, B, T, dim), clb.lib().clb_maxsim_batch_i8_work_bytes(N, B, T, dim),
-                                     clb.lib().clb_maxsim_batch_mx_work_bytes(N, B, T, dim))), dtype=torch.uint8, device="cuda")
+                                     clb.lib().clb_maxsim_batch_mx_work_bytes(N, B, T, dim), clb.lib().clb_maxsim_batch_b1_work_bytes(N, B, T, dim))),
+                             dtype=torch.uint8, device="cuda")
         ready = []
         for pid in pids:                                                 # the gathered side's operands, made once
             r, n = row_numbers(pid)
